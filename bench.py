@@ -2,7 +2,7 @@
 """Headline benchmark: BASELINE.json configs[1] — d=1024 nhead=16 L=12 bf16, batch-1 AR top-k(10)
 decode + 7 NAR stages of a 10 s utterance (S=47 phonemes, 3 s prompt -> 753 frames x 8 codebooks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 starts N ranks itself (one fresh process per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* in their environment, before this process has touched HIP) and relays rank 0's line; under
@@ -14,7 +14,7 @@ with ``--batch B`` one step = B utterances per GPU decoded together (BASELINE co
 S in [40, 54]; configs[3] = ``--batch 32 --gpus 8``, 256 utterances per step).  Utterances are independent,
 so N GPUs run N replicas (weak scaling): rank 0 owns the inputs, sorts them by length, scatters them over RCCL,
 every rank decodes its own, codes are gathered back; scatter and gather are inside the timed region.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  ``--dump-outputs DIR`` also writes the codes of the last timed step (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -35,6 +35,7 @@ S_TEXT, P_PROMPT, TOP_K, TEMP = 47, 225, 10, 1.0
 D_MODEL, N_HEAD, N_LAYER = 1024, 16, 12
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 METRIC = "AR codec-tokens/sec/GPU + NAR 7-stage p50 latency, d=1024 L=12 10s utterance"
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def weight_bytes(d: int, L: int, bpe: int) -> int:
@@ -140,7 +141,40 @@ def parse_args(argv=None):
     ap.add_argument("--no-graph", action="store_true", help="launch the AR step kernel by kernel (rocprofv3 --pmc cannot follow hipGraph replays)")
     ap.add_argument("--dry-run-cpu", action="store_true", help="tests only: gloo on CPU with a stand-in decoder, to exercise the "
                     "launcher / partition / scatter / gather path without a GPU; the line says so in `data`")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the codes the last timed "
+                    "step returned as DIR/codes_<j>.npy (float32, (1, T, 8), j = utterance of that step in input order)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir: str, codes) -> list:
+    """Writes codes[j] (what VALLE.inference / inference_batch returned for utterance j of the last timed step, (1, T, 8)
+    int64) as out_dir/codes_<j>.npy in float32, which holds every code (< 1025) exactly.  The inputs and sampler seeds of
+    every step are fixed by the arguments, so two builds run with the same arguments can be compared file for file.  Above
+    DUMP_CAP_BYTES in all, a fixed seeded sample of the utterances is written instead.  Returns the names written."""
+    import random
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = [int(c.numel()) * 4 for c in codes]
+    keep = list(range(len(codes)))
+    if sum(sizes) > DUMP_CAP_BYTES:
+        order = random.Random(0).sample(keep, len(keep))
+        keep, total = [], 0
+        for j in order:
+            if total + sizes[j] <= DUMP_CAP_BYTES:
+                keep.append(j)
+                total += sizes[j]
+        keep.sort()
+    names = []
+    for j in keep:
+        name = f"codes_{j}"
+        np.save(os.path.join(out_dir, name + ".npy"), codes[j].detach().cpu().numpy().astype(np.float32))
+        names.append(name)
+    return names
 
 
 # ------------------------------------------------------------------------------------------ launcher
@@ -313,6 +347,8 @@ def run_rank(args) -> int:
         _, _, tms_gemm, _ = run_phase(args.warmup + args.steps - 1, 1)
         os.environ.pop("VX_TIME_GEMMS")
         fence()
+    if rank == 0 and args.dump_outputs:  # the last timed step's utterances, in input order
+        dump_outputs(args.dump_outputs, outs[-per_step:])
     if rank == 0 and os.environ.get("VX_BENCH_DUMP"):  # tests: what rank 0 holds after the gather, in utterance order
         with open(os.environ["VX_BENCH_DUMP"], "w") as fh:
             json.dump([[int(c.shape[1]), int(c.sum())] for c in outs], fh)

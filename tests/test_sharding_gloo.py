@@ -150,3 +150,45 @@ def test_bench_batch32_two_ranks_returns_codes_in_utterance_order(tmp_path):
         assert T == 16 * S + 1 == want.shape[1] and chk == int(want.sum()), i
         total += T
     assert abs(rec["value"] * rec["ms_per_step"] * 1e-3 - total) < 0.01 * total
+
+
+def test_bench_dump_outputs_writes_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` at world size 2 on gloo (stand-in decoder): after 3 timed steps of 4 utterances per rank,
+    DIR holds the codes of the LAST timed step's 8 utterances, float32, in utterance order; a second run with the same
+    arguments writes the same arrays, and the result line reports the steps asked for."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from valle_amd.weights import synthetic_inputs
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4",
+                            "--dry-run-cpu", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == sorted(f"codes_{j}.npy" for j in range(8))
+        dumps.append({j: np.load(out / f"codes_{j}.npy") for j in range(8)})
+    model = bench._DryRunModel()
+    for j in range(8):
+        i = 3 * 8 + j  # warmup step + two timed steps of 2 x 4 utterances come first
+        x, xl, y = synthetic_inputs(bench.S_TEXT - 7 + (i % 15), bench.P_PROMPT, 8, seed=1 + i)
+        want = model.inference(x, xl, y, None).numpy().astype(np.float32)
+        assert dumps[0][j].dtype == np.float32 and np.array_equal(dumps[0][j], want), j
+        assert np.array_equal(dumps[0][j], dumps[1][j]), j
+
+
+def test_bench_refuses_zero_steps():
+    import subprocess
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run-cpu"], env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
