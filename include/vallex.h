@@ -173,6 +173,30 @@ int vx_batch_decode(vx_engine* e, int32_t n_slots, const vx_decode_params* param
 int vx_batch_result(vx_engine* e, int32_t slot, int64_t* tokens, int32_t capacity, int32_t* n_tokens,
                     int32_t* stop_reason);
 
+/* ---- continuous batching: a session over all max_batch slots in which finished utterances leave and new ones enter while the
+ * others keep decoding (bf16 engines with max_batch >= 2).  Every slot is VACANT, LIVE (admitted, decoding) or STOPPED (finished,
+ * result not read yet).  The step always runs over all max_batch slots (the graph vx_batch_decode uses at n_slots = max_batch);
+ * vacant and stopped slots skip the sampling, the K / V append, the attention and the logits.
+ *   vx_batch_open   ends any earlier session and makes every slot vacant (device state done, row 0; the slot's residual and
+ *                   logits rows zeroed).
+ *   vx_batch_admit  prefills n utterances into the given vacant slots and arms them with params[z]; the other slots' KV caches,
+ *                   rows and state are not touched.  Checks as vx_batch_prefill_all / vx_batch_decode (capacity clamp included).
+ *                   A slot outside [0, max_batch) or given twice: VX_ERR_ARG; a live or stopped-unread slot: VX_ERR_STATE.
+ *                   mode VX_ADMIT_BATCHED prefills all n in one pass over the concatenated rows (one synchronisation);
+ *                   VX_ADMIT_PER_SLOT runs vx_batch_prefill's path per slot (one synchronisation each; bitwise the static path).
+ *                   exp_noise / forced must be DEVICE pointers that stay valid until the slot's result is read.
+ *   vx_batch_run    replays the step until at least min_stopped (< 1: 1) live slots have stopped in this call, or none is left
+ *                   live; polls the stop flags every poll_steps steps (<= 0: the default).  stopped (capacity
+ *                   max_batch) receives the slots that stopped, n_stopped their number; vx_batch_result(slot) then returns a
+ *                   slot's tokens and stop reason and makes it vacant.  VX_ERR_CAPACITY as in vx_batch_decode, naming the slot
+ *                   (stopped / n_stopped are still filled); VX_ERR_STATE without an open session.
+ * vx_batch_prefill, vx_batch_prefill_all and vx_batch_decode end the session. */
+enum vx_admit_mode { VX_ADMIT_BATCHED = 0, VX_ADMIT_PER_SLOT = 1 };
+int vx_batch_open(vx_engine* e, void* stream);
+int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, const int64_t* const* text, const int32_t* S,
+                   const int64_t* const* prompt_cb0, const int32_t* P, const vx_decode_params* params, int32_t mode, void* stream);
+int vx_batch_run(vx_engine* e, int32_t min_stopped, int32_t poll_steps, int32_t* stopped, int32_t* n_stopped, void* stream);
+
 /* The NAR stages of n (<= 32) utterances in one pass: rows are concatenated so the GEMMs run at M ~ n x 1k.
  * Arguments are arrays of n pointers / sizes with the meaning of vx_nar's. */
 int vx_nar_batch(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,

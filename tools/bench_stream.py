@@ -1,0 +1,178 @@
+"""Continuous vs static batching at BASELINE configs[2] geometry (d=1024 nhead=16 L=12, 32 slots, bf16), one JSON line on stdout.
+
+    python tools/bench_stream.py [--n 128] [--slots 32] [--poll 4,8,16,32] [--refill 1,2,4,8]
+    python tools/bench_stream.py --ab-half-done [--lib path/to/libvallex.so]
+
+Default mode: a seeded queue of --n utterances, S uniform in [10, 94], P = 225 (synthetic weights: every utterance stops by the
+length rule, T = 16 S + 1 frames), decoded end to end (AR + 7 NAR stages) once through inference_batch, group by group, and once
+per (poll_steps, refill_at) setting through inference_stream.  Reported per run: codec-tokens/s (frames of all utterances over the
+wall time of the whole queue), slot occupancy (live slot-steps / launched slot-steps) and the mean / p95 latency of an utterance
+from queue start to its codes.
+
+--ab-half-done: device time per batched step with all 32 slots live, and with half of them done (teacher-forced lengths 753 and
+1), through vx_batch_decode, so that the same measurement runs on a library without the continuous-batching entry points."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def model(args, max_audio):
+    if args.lib:  # a library built from another revision: bind only the entry points it exports (the static batched path)
+        import ctypes as C
+
+        import valle_amd  # noqa: F401
+        from valle_amd import engine
+
+        probe = C.CDLL(os.path.abspath(args.lib))
+        engine._SIGS = {k: v for k, v in engine._SIGS.items() if hasattr(probe, k)}
+        engine.load_library(os.path.abspath(args.lib))
+    else:
+        import __graft_entry__ as ge
+
+        ge.build()
+    from valle_amd.config import ModelConfig
+    from valle_amd.models import VALLE
+    from valle_amd.weights import synthetic_state_dict
+
+    cfg = ModelConfig(decoder_dim=1024, nhead=16, num_decoder_layers=12, prefix_mode=1)
+    m = VALLE(1024, 16, 12, prefix_mode=1, precision="bf16", max_text=128, max_audio=max_audio, print_eos=False, max_batch=args.slots)
+    m.load_state_dict(synthetic_state_dict(cfg, 0))
+    return m.to("cuda:0").eval()
+
+
+def queue(n, seed):
+    import torch
+    from valle_amd.weights import synthetic_inputs
+
+    g = torch.Generator().manual_seed(seed)
+    S = torch.randint(10, 95, (n,), generator=g).tolist()
+    return [synthetic_inputs(s, 225, 8, seed=1000 + i) for i, s in enumerate(S)], S
+
+
+def count_steps(eng):
+    """Counts the batched steps the engine launches (vx_batch_decode / vx_batch_run) from its timings."""
+    box = [0]
+    for name in ("batch_decode", "batch_run"):
+        orig = getattr(eng, name)
+
+        def wrap(*a, _orig=orig, **k):
+            r = _orig(*a, **k)
+            box[0] += eng.timings()["batch_launches"]
+            return r
+
+        setattr(eng, name, wrap)
+    return box
+
+
+def summary(kind, t0, done_at, frames, steps, slots, **extra):
+    import numpy as np
+
+    wall = max(done_at.values()) - t0
+    lat = np.array([done_at[i] - t0 for i in sorted(done_at)])
+    return dict(kind=kind, tok_per_s=round(sum(frames) / wall, 1), wall_s=round(wall, 3),
+                occupancy=round(sum(frames) / (steps * slots), 4), steps=int(steps),
+                latency_mean_s=round(float(lat.mean()), 3), latency_p95_s=round(float(np.percentile(lat, 95)), 3), **extra)
+
+
+def run_queue(args):
+    import torch
+
+    m = model(args, 1792)
+    eng = m.engine()
+    steps = count_steps(eng)
+    utts, S = queue(args.n, args.seed)
+    frames = [16 * s + 1 for s in S]
+    seeds = list(range(1, args.n + 1))
+    B = args.slots
+    polls = [int(v) for v in args.poll.split(",")]
+    refills = [int(v) for v in args.refill.split(",")]
+    # warm-up: every shape class the timed runs use (graph capture, row buffers, NAR at the group's row count)
+    w, _ = queue(B, args.seed + 1)
+    m.inference_batch(w, top_k=10, seeds=list(range(B)))
+    for _ in m.inference_stream(w, top_k=10, seeds=list(range(B))):
+        pass
+    torch.cuda.synchronize()
+    runs = []
+
+    def static():
+        steps[0] = 0
+        done_at = {}
+        t0 = time.perf_counter()
+        for g0 in range(0, args.n, B):  # inference_batch's own grouping, timed group by group
+            out = m.inference_batch(utts[g0 : g0 + B], top_k=10, seeds=seeds[g0 : g0 + B])
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            for i in range(len(out)):
+                done_at[g0 + i] = now
+        return summary("static", t0, done_at, frames, steps[0], B)
+
+    def stream(poll, refill):
+        steps[0] = 0
+        done_at = {}
+        t0 = time.perf_counter()
+        for i, codes in m.inference_stream(utts, top_k=10, seeds=seeds, poll_steps=poll, refill_at=refill):
+            done_at[i] = time.perf_counter()  # codes are on the device, written by work already synchronised by the engine
+        return summary("stream", t0, done_at, frames, steps[0], B, poll_steps=poll, refill_at=refill)
+
+    for rep in range(args.reps):
+        runs.append(static())
+        for p in polls:
+            runs.append(stream(p, refills[0]))
+        for r in refills[1:]:
+            runs.append(stream(polls[0], r))
+    # codes of the two paths: identical AR tokens (same seeds, per-slot arithmetic) - checked once on the timed queue
+    ref = m.inference_batch(utts[:B], top_k=10, seeds=seeds[:B], batched_prefill=False)
+    got = dict(m.inference_stream(utts[:B], top_k=10, seeds=seeds[:B], batched_admit=False))
+    same = all(torch.equal(ref[i][0, :, 0], got[i][0, :, 0]) for i in range(B))
+    return dict(mode="queue", geometry="d=1024 nhead=16 L=12 bf16", slots=B, n=args.n, S_range=[10, 94], P=225,
+                frames=sum(frames), ar_codes_equal_static=same, runs=runs)
+
+
+def run_ab(args):
+    import torch
+
+    m = model(args, 1024)
+    eng = m.engine()
+    B = args.slots
+    from valle_amd.weights import synthetic_inputs
+
+    utts = [synthetic_inputs(47, 225, 8, seed=2000 + i) for i in range(B)]
+    texts = [u[0][0] for u in utts]
+    proms = [u[2][0, :, 0].contiguous() for u in utts]
+    g = torch.Generator().manual_seed(3)
+    full = [torch.randint(0, 1024, (753,), generator=g).cuda() for _ in range(B)]
+    out = {}
+    for name, forced in (("all_live", full), ("half_done", [f if b % 2 == 0 else f[:1] for b, f in enumerate(full)])):
+        vals = []
+        for rep in range(args.reps + 1):
+            eng.batch_prefill_all(texts, proms)
+            eng.batch_decode(B, top_k=10, forced=forced)
+            t = eng.timings()
+            if rep:  # the first is warm-up
+                vals.append(1e3 * t["batch_decode_ms"] / t["batch_launches"])
+        out[name] = dict(step_us=[round(v, 2) for v in vals], mean_us=round(sum(vals) / len(vals), 2))
+    return dict(mode="ab_half_done", lib=args.lib or "libvallex.so", slots=B, S=47, P=225, T=753, **out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=128)
+    ap.add_argument("--slots", type=int, default=32)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--poll", default="8", help="comma-separated poll_steps values (the first is used for the refill sweep)")
+    ap.add_argument("--refill", default="4", help="comma-separated refill_at values (the first is used for the poll sweep)")
+    ap.add_argument("--reps", type=int, default=1)
+    ap.add_argument("--ab-half-done", action="store_true")
+    ap.add_argument("--lib", default=None, help="--ab-half-done: load this libvallex.so instead of the package's")
+    args = ap.parse_args()
+    res = run_ab(args) if args.ab_half_done else run_queue(args)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

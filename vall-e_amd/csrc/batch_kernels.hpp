@@ -14,7 +14,8 @@ constexpr int BMAX = 64;  // slots per engine (up to four 16-row MFMA halves)
 typedef __bf16 bf16x8b_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-enum BgemmEpi { BE_QKV = 0, BE_RELU = 1, BE_PARTIAL = 2, BE_LOGITS = 3 };
+// BE_LOGITS_MAP: BE_LOGITS for the rows of a slot-mapped admission - A row z belongs to slot slot_map[z] (vx_batch_admit)
+enum BgemmEpi { BE_QKV = 0, BE_RELU = 1, BE_PARTIAL = 2, BE_LOGITS = 3, BE_LOGITS_MAP = 4 };
 
 struct BgemmArgs {
   const bf16* A;      // (32, K) activations, rows >= B hold finite stale values
@@ -34,6 +35,7 @@ struct BgemmArgs {
   int logits_stride;
   float* trace;       // BE_LOGITS, optional (VX_FLAG_TRACE_LOGITS): (slots, trace_rows, N) - row `pass` of every live slot
   int trace_rows;
+  const int* slot_map;  // BE_LOGITS_MAP: (B,) slot of every A row
   // cache warm-up for a LATER GEMM of the step (as GemvArgs.pf of the batch-1 step): workgroup b touches bytes
   // [b pf_slice, (b+1) pf_slice) of `pf` with 8 unused 16-byte loads per lane.  Speed only.
   const void* pf;
@@ -66,8 +68,9 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
 #pragma unroll
   for (int u = 0; u < NH; ++u) {
     st_done[u] = 0; st_row[u] = 0;
-    if (EPI == BE_QKV || EPI == BE_LOGITS) {
-      const int i = wave * NH + u, b = min(16 * (i >> 2) + 4 * g + (i & 3), a.B - 1);
+    if (EPI == BE_QKV || EPI == BE_LOGITS || EPI == BE_LOGITS_MAP) {
+      const int i = wave * NH + u, r = min(16 * (i >> 2) + 4 * g + (i & 3), a.B - 1);
+      const int b = EPI == BE_LOGITS_MAP ? a.slot_map[r] : r;
       st_done[u] = a.st[b].done;
       st_row[u] = EPI == BE_QKV ? a.st[b].row : a.st[b].pass;
     }
@@ -111,10 +114,11 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
       a.part[((size_t)kg * BMAX + b) * a.N + n] = x;
     } else if (EPI == BE_RELU) {
       a.f[(size_t)b * a.N + n] = (bf16)fmaxf(x + bias_v, 0.f);
-    } else if (EPI == BE_LOGITS) {
+    } else if (EPI == BE_LOGITS || EPI == BE_LOGITS_MAP) {
+      const int sb = EPI == BE_LOGITS_MAP ? a.slot_map[b] : b;
       if (!st_done[u]) {
-        a.logits[(size_t)b * a.logits_stride + n] = x;
-        if (a.trace != nullptr && st_row[u] < a.trace_rows) a.trace[((size_t)b * a.trace_rows + st_row[u]) * a.N + n] = x;
+        a.logits[(size_t)sb * a.logits_stride + n] = x;
+        if (a.trace != nullptr && st_row[u] < a.trace_rows) a.trace[((size_t)sb * a.trace_rows + st_row[u]) * a.N + n] = x;
       }
     } else {  // BE_QKV
       const float v = x + bias_v;
@@ -137,13 +141,13 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
 // x[b] += bias + sum_g part[g][b] (KG > 0; written back), then h[b] = bf16(LN(x[b]) * gamma + beta).
 // One workgroup per slot, thread t owns columns [4t, 4t+4): every load of the kernel (x, bias, the KG partials,
 // gamma, beta) is issued up front, so the kernel is one memory round trip plus two workgroup reductions.
+// The body reads x row b and writes h row hb (b == hb on the step; ln_batch_map_kernel packs mapped slots into rows 0..n-1).
 template <int KG>
-__global__ __launch_bounds__(256) void ln_batch_kernel(float* __restrict__ x, const float* __restrict__ part,
-                                                       const float* __restrict__ pbias, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, bf16* __restrict__ h, int d) {
+__device__ __forceinline__ void ln_batch_body(float* __restrict__ x, const float* __restrict__ part, const float* __restrict__ pbias,
+                                              const float* __restrict__ gamma, const float* __restrict__ beta, bf16* __restrict__ h,
+                                              int d, int b, int hb) {
   __shared__ float red[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x;
   const bool live = tid * 4 < d;
   const int k = live ? tid * 4 : 0;  // idle threads (d < 1024) load column 0 and contribute zeros
   float* xr = x + (size_t)b * d;
@@ -176,8 +180,21 @@ __global__ __launch_bounds__(256) void ln_batch_kernel(float* __restrict__ x, co
     pk.e[1] = (bf16)(d1 * rstd * gm.y + bt.y);
     pk.e[2] = (bf16)(d2 * rstd * gm.z + bt.z);
     pk.e[3] = (bf16)(d3 * rstd * gm.w + bt.w);
-    *reinterpret_cast<uint2*>(h + (size_t)b * d + k) = pk.u;
+    *reinterpret_cast<uint2*>(h + (size_t)hb * d + k) = pk.u;
   }
+}
+template <int KG>
+__global__ __launch_bounds__(256) void ln_batch_kernel(float* __restrict__ x, const float* __restrict__ part,
+                                                       const float* __restrict__ pbias, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, bf16* __restrict__ h, int d) {
+  ln_batch_body<KG>(x, part, pbias, gamma, beta, h, d, blockIdx.x, blockIdx.x);
+}
+// Slot-mapped admission (vx_batch_admit): workgroup z normalises slot slot_map[z]'s row of x into row z of h (the A operand of
+// the BE_LOGITS_MAP head).  x is only read.
+__global__ __launch_bounds__(256) void ln_batch_map_kernel(float* __restrict__ x, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, bf16* __restrict__ h, int d,
+                                                           const int* __restrict__ slot_map) {
+  ln_batch_body<0>(x, nullptr, nullptr, gamma, beta, h, d, slot_map[blockIdx.x], blockIdx.x);
 }
 
 // Single-query attention of every (slot, head): grid = (nhead, B), one workgroup walks all cached keys of its
@@ -195,6 +212,7 @@ __global__ __launch_bounds__(256) void attn_batch_kernel(const float* __restrict
   const int h = blockIdx.x, slot = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sub = lane % LPK, grp = lane / LPK;
+  const int done = st[slot].done;
   const int ctx = st[slot].row + 1;
   float qv[VEC];
 #pragma unroll
@@ -202,6 +220,10 @@ __global__ __launch_bounds__(256) void attn_batch_kernel(const float* __restrict
     const float4 t = *reinterpret_cast<const float4*>(q + (size_t)slot * d + h * HD + sub * VEC + i);
     qv[i] = t.x; qv[i + 1] = t.y; qv[i + 2] = t.z; qv[i + 3] = t.w;
   }
+  __builtin_amdgcn_sched_barrier(0);  // the q loads go out with the state's, not behind the branch on it
+  // finished and vacant slots: nothing reads their output (their logits and KV rows are no longer written), so they skip the walk
+  // over their cache and keep the finite row the last step wrote (zeros for a slot never filled).  Uniform per workgroup.
+  if (done) return;
   const bf16* kb = kv + (size_t)slot * kv_slot_stride + (size_t)h * ctx_max * HD + sub * VEC;
   const bf16* vb = kb + kv_v_offset;
   float M = -INFINITY, L = 0.f, acc[VEC];

@@ -91,6 +91,9 @@ struct LayerW {
 };
 
 constexpr int POLL_CHUNK = 32;
+// vx_batch_run's default stop-poll interval in steps (poll_steps <= 0): see DESIGN.md "Continuous batching" for the measurement
+constexpr int BATCH_POLL_DEFAULT = 8;
+enum SlotState { SLOT_VACANT = 0, SLOT_LIVE = 1, SLOT_STOPPED = 2 };  // continuous-batching session (vx_batch_open)
 
 struct vx_engine {
   vx_config cfg{};
@@ -158,6 +161,8 @@ struct vx_engine {
   std::unordered_map<int, hipGraphExec_t> bgraphs;
   int *d_seg_start = nullptr, *d_seg_len = nullptr;  // segments of the concatenated row buffer (batched NAR / prefill)
   int* d_seg_text = nullptr;                          // per-segment text length (prefix mask of a batched prefill)
+  int* d_seg_slot = nullptr;                          // slot of every segment of a slot-mapped batched prefill (vx_batch_admit)
+  const int* seg_slot = nullptr;                      // = d_seg_slot while such a prefill runs its stack, else nullptr (z -> z)
   // prenets (VX_FLAG_PRENET): scratch rows, conv weights re-laid out as [k][ci][co], decode-step vectors
   float *pn_a = nullptr, *pn_b = nullptr, *pn_h1 = nullptr, *pn_h2 = nullptr, *pn_text = nullptr, *d_zero = nullptr;
   float *ar_e = nullptr, *ar_h1 = nullptr, *ar_h2 = nullptr;
@@ -170,6 +175,12 @@ struct vx_engine {
   int nseg = 0, max_seg_len = 0;
   int bS[BMAX] = {}, bP[BMAX] = {}, bbos[BMAX] = {}, bngen[BMAX] = {}, breason[BMAX] = {};
   bool bprefilled[BMAX] = {};
+  // continuous-batching session (vx_batch_open / _admit / _run): per-slot state, the steps a live slot may still take before its
+  // stop rule must have fired, and whether its bound was clamped to the KV capacity
+  bool bsess = false;
+  int bslot[BMAX] = {};
+  long long bleft[BMAX] = {};
+  bool bcap[BMAX] = {};
   double t_bdecode = 0, n_blaunch = 0;
   // graph
   hipGraph_t graph = nullptr;
@@ -501,6 +512,7 @@ static int create_body(vx_engine* e) {
     VXC(dalloc_t(e, &e->d_seg_start, (size_t)BMAX));
     VXC(dalloc_t(e, &e->d_seg_len, (size_t)BMAX));
     VXC(dalloc_t(e, &e->d_seg_text, (size_t)BMAX));
+    VXC(dalloc_t(e, &e->d_seg_slot, (size_t)BMAX));
     // MFMA A operands always read 32 rows: rows of unused slots must hold finite values
     HIPC(hipMemsetAsync(e->bx, 0, (size_t)BMAX * d * 4, e->es));
     HIPC(hipMemsetAsync(e->bh, 0, (size_t)BMAX * d * 2, e->es));
@@ -1000,10 +1012,10 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
     VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
     if (tg) gemm_mark(e, 2.0 * M * 3 * d * d);
     }
-    if (fill_cache && e->nseg > 0) {  // batched prefill: segment z -> slot z
+    if (fill_cache && e->nseg > 0) {  // batched prefill: segment z -> slot z (slot seg_slot[z] when admitting)
       const size_t kvl = (size_t)2 * H * e->ctx_max * 64;  // elements per layer
       kv_scatter_seg_kernel<bf16><<<dim3(e->max_seg_len, e->nseg), 256, 0, e->es>>>(
-          (const bf16*)e->QKV, e->bkv + li * kvl, e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, d, 64, e->ctx_max);
+          (const bf16*)e->QKV, e->bkv + li * kvl, e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, d, 64, e->ctx_max, e->seg_slot);
     } else if (fill_cache) {
       char* kc = kv_base + li * kv_layer;
       char* vc = kc + kv_layer / 2;
@@ -1250,6 +1262,7 @@ extern "C" int vx_batch_prefill(vx_engine* e, int32_t slot, const int64_t* text,
                                 int32_t P, void* stream) {
   if (!e) return fail(VX_ERR_ARG, "null engine");
   if (slot < 0 || slot >= e->bmax) return fail(VX_ERR_ARG, "slot %d outside [0, max_batch=%d)", slot, e->bmax);
+  e->bsess = false;  // the static calls end a continuous-batching session
   return prefill_impl(e, slot, text, S, prompt_cb0, P, stream);
 }
 
@@ -1262,8 +1275,10 @@ static void launch_ln_batch(float* x, const float* part, int kgroups, const floa
                             bf16* h, int B, int d, hipStream_t s);
 template <int EPI> static int launch_bgemm(const BgemmArgs& a, hipStream_t s);
 
-extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S,
-                                    const int64_t* const* prompt_cb0, const int32_t* P, void* stream) {
+// slots == nullptr: segment z -> slot z (vx_batch_prefill_all).  Otherwise segment z -> slot slots[z] (vx_batch_admit): only those
+// slots' KV caches, bx / blogits / trace rows and ArState are written; bh rows are step scratch.
+static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, const int64_t* const* text, const int32_t* S,
+                              const int64_t* const* prompt_cb0, const int32_t* P, void* stream) {
   if (!e || !text || !S || !prompt_cb0 || !P) return fail(VX_ERR_ARG, "null argument");
   if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
   if (n < 1 || n > e->bmax) return fail(VX_ERR_ARG, "n %d outside [1, max_batch=%d]", n, e->bmax);
@@ -1290,6 +1305,7 @@ extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* cons
   HIPC(hipMemcpyAsync(e->d_seg_start, start.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
   HIPC(hipMemcpyAsync(e->d_seg_len, len.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
   HIPC(hipMemcpyAsync(e->d_seg_text, tlen.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
+  if (slots) HIPC(hipMemcpyAsync(e->d_seg_slot, slots, n * sizeof(int), hipMemcpyHostToDevice, e->es));
   HIPC(hipMemsetAsync(e->X, 0, rows * (size_t)d * 4, e->es));  // padding rows must stay finite (they feed V^T columns)
   static const long long bos_id = NUM_AUDIO_TOKENS + 1;  // valle.py:1006-1007
   for (int b = 0; b < n; ++b) {
@@ -1306,26 +1322,33 @@ extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* cons
                                            W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, xb + (size_t)S[b] * d, A);
   }
   e->nseg = n; e->max_seg_len = maxlen; e->seg_text_on = true;
+  e->seg_slot = slots ? e->d_seg_slot : nullptr;
   int rc = run_stack(e, e->ar_l, (int)rows, d, c.nhead, 0, -1, true);
-  e->nseg = 0; e->seg_text_on = false;
+  e->nseg = 0; e->seg_text_on = false; e->seg_slot = nullptr;
   VXC(rc);
   // decode state as of "pass 0 computed", last row of every segment = the slot's current activation
   for (int b = 0; b < n; ++b) {
-    HIPC(hipMemcpyAsync(e->bx + (size_t)b * d, e->X + (size_t)(start[b] + len[b] - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
-    ArState& st = e->h_bst[b];
+    const int sl = slots ? slots[b] : b;
+    HIPC(hipMemcpyAsync(e->bx + (size_t)sl * d, e->X + (size_t)(start[b] + len[b] - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
+    ArState& st = e->h_bst[sl];
     memset(&st, 0, sizeof st);
     st.S = S[b]; st.bos = bos; st.P = P[b]; st.row = len[b] - 1; st.pass = 0; st.kv_text = S[b];
     st.temperature = 1.0f; st.max_new = -1;
+    if (slots) HIPC(hipMemcpyAsync(e->bst + sl, &st, sizeof(ArState), hipMemcpyHostToDevice, e->es));
   }
-  HIPC(hipMemcpyAsync(e->bst, e->h_bst, (size_t)n * sizeof(ArState), hipMemcpyHostToDevice, e->es));
+  if (!slots) HIPC(hipMemcpyAsync(e->bst, e->h_bst, (size_t)n * sizeof(ArState), hipMemcpyHostToDevice, e->es));
   // first logits of every slot: final LayerNorm + head, as at the end of a batched step
-  launch_ln_batch(e->bx, nullptr, 0, nullptr, W<float>(e, "ar_decoder.norm.weight"), W<float>(e, "ar_decoder.norm.bias"), e->bh, n, d, e->es);
+  const float *ng = W<float>(e, "ar_decoder.norm.weight"), *nb = W<float>(e, "ar_decoder.norm.bias");
+  if (slots) ln_batch_map_kernel<<<n, 256, 0, e->es>>>(e->bx, ng, nb, e->bh, d, e->d_seg_slot);
+  else launch_ln_batch(e->bx, nullptr, 0, nullptr, ng, nb, e->bh, n, d, e->es);
   BgemmArgs hgm{};
   hgm.st = e->bst; hgm.B = n;
   hgm.A = e->bh; hgm.W = W<bf16>(e, "ar_predict_layer.weight"); hgm.N = AR_VOCAB; hgm.K = d; hgm.kgroups = 1;
   hgm.logits = e->blogits; hgm.logits_stride = LOGITS_CUR;
   hgm.trace = e->btrace; hgm.trace_rows = e->btok_stride;
-  VXC(launch_bgemm<BE_LOGITS>(hgm, e->es));
+  hgm.slot_map = slots ? e->d_seg_slot : nullptr;
+  if (slots) VXC(launch_bgemm<BE_LOGITS_MAP>(hgm, e->es));
+  else VXC(launch_bgemm<BE_LOGITS>(hgm, e->es));
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(e->ev_t[1], e->es));
   HIPC(hipStreamSynchronize(e->es));  // the staging state is reused by decode
@@ -1333,11 +1356,18 @@ extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* cons
   HIPC(hipEventElapsedTime(&ms, e->ev_t[0], e->ev_t[1]));
   e->t_prefill = ms;
   for (int b = 0; b < n; ++b) {
-    e->bS[b] = S[b]; e->bP[b] = P[b]; e->bbos[b] = bos;
-    e->bprefilled[b] = true; e->bngen[b] = 0; e->breason[b] = 0;
+    const int sl = slots ? slots[b] : b;
+    e->bS[sl] = S[b]; e->bP[sl] = P[b]; e->bbos[sl] = bos;
+    e->bprefilled[sl] = true; e->bngen[sl] = 0; e->breason[sl] = 0;
   }
   VXC(sync_out(e, stream));
   return VX_OK;
+}
+
+extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S,
+                                    const int64_t* const* prompt_cb0, const int32_t* P, void* stream) {
+  if (e) e->bsess = false;  // the static calls end a continuous-batching session
+  return batch_prefill_impl(e, n, nullptr, text, S, prompt_cb0, P, stream);
 }
 
 // One decode step: sample from the newest logits, append, run the 12-layer stack on the new
@@ -1859,56 +1889,76 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
   return VX_OK;
 }
 
+// The checks of one slot's decode parameters (no HIP call): its step bound (the steps after which the stop rule must have fired)
+// and whether that bound was clamped to the KV capacity.  S / P / bos are the slot's prefill geometry.
+static int batch_params_check(vx_engine* e, int slot, const vx_decode_params& p, int S, int P, int bos, long long* steps,
+                              bool* cap_limited, long long* room_out) {
+  if (p.struct_size != (int32_t)sizeof(vx_decode_params)) return fail(VX_ERR_ARG, "vx_decode_params.struct_size mismatch");
+  if (!(p.temperature > 0.f)) return fail(VX_ERR_ARG, "temperature must be > 0");
+  long long max_tok = 16LL * S + 1 - bos;
+  if (p.forced) max_tok = p.n_forced;
+  else if (p.max_new_tokens >= 0 && p.max_new_tokens < max_tok) max_tok = p.max_new_tokens;
+  const long long room = (long long)e->cfg.max_audio - bos - P;  // as in vx_ar_decode: clamp, fail only if it fills
+  *cap_limited = false;
+  if (max_tok > room) {
+    if (p.forced) return fail(VX_ERR_CAPACITY, "slot %d needs %lld audio rows, capacity %d", slot, bos + P + max_tok, e->cfg.max_audio);
+    max_tok = room; *cap_limited = true;
+  }
+  *steps = max_tok + (p.forced ? 1 : 0);
+  *room_out = room;
+  return VX_OK;
+}
+// Decode parameters into the slot's staging state (its prefill fields are already there).
+static void batch_params_stage(vx_engine* e, int slot, const vx_decode_params& p, bool cap_limited, long long room) {
+  ArState& st = e->h_bst[slot];
+  st.top_k = p.top_k; st.temperature = p.temperature; st.max_new = cap_limited ? (int)room : p.max_new_tokens;
+  st.exp_noise = p.exp_noise; st.noise_rows = p.noise_rows; st.seed = p.seed;
+  st.forced = p.forced ? (p.n_forced > 0 ? (const long long*)p.forced : (const long long*)e->btok) : nullptr;
+  st.n_forced = p.forced ? p.n_forced : 0;
+}
+// The executable graph of the B-slot step (captured on first use, one per B); nullptr with VX_FLAG_NO_GRAPH.
+static int batch_graph(vx_engine* e, int B, hipGraphExec_t* out) {
+  *out = nullptr;
+  if (e->cfg.flags & VX_FLAG_NO_GRAPH) return VX_OK;
+  auto it = e->bgraphs.find(B);
+  if (it != e->bgraphs.end()) { *out = it->second; return VX_OK; }
+  hipGraph_t gr = nullptr;
+  hipGraphExec_t gx = nullptr;
+  HIPC(hipStreamBeginCapture(e->es, hipStreamCaptureModeThreadLocal));
+  int r = enqueue_batch_step(e, B, e->es);
+  hipError_t ce = hipStreamEndCapture(e->es, &gr);
+  if (r != VX_OK) return r;
+  HIPC(ce);
+  HIPC(hipGraphInstantiate(&gx, gr, nullptr, nullptr, 0));
+  (void)hipGraphDestroy(gr);
+  e->bgraphs[B] = gx;
+  *out = gx;
+  return VX_OK;
+}
+
 extern "C" int vx_batch_decode(vx_engine* e, int32_t B, const vx_decode_params* params, void* stream) {
   if (!e || !params) return fail(VX_ERR_ARG, "null argument");
   if (B < 1 || B > e->bmax) return fail(VX_ERR_ARG, "n_slots %d outside [1, max_batch=%d]", B, e->bmax);
   const vx_config& c = e->cfg;
   ON_DEVICE(c.device);
+  e->bsess = false;  // the static calls end a continuous-batching session
   long long bound = 1;
   bool cap_limited[BMAX] = {};
   for (int b = 0; b < B; ++b) {
     const vx_decode_params& p = params[b];
     if (p.struct_size != (int32_t)sizeof(vx_decode_params)) return fail(VX_ERR_ARG, "vx_decode_params.struct_size mismatch");
     if (!e->bprefilled[b]) return fail(VX_ERR_STATE, "slot %d needs a fresh vx_batch_prefill", b);
-    if (!(p.temperature > 0.f)) return fail(VX_ERR_ARG, "temperature must be > 0");
-    long long max_tok = 16LL * e->bS[b] + 1 - e->bbos[b];
-    if (p.forced) max_tok = p.n_forced;
-    else if (p.max_new_tokens >= 0 && p.max_new_tokens < max_tok) max_tok = p.max_new_tokens;
-    const long long room = (long long)c.max_audio - e->bbos[b] - e->bP[b];  // as in vx_ar_decode: clamp, fail only if it fills
-    cap_limited[b] = false;
-    if (max_tok > room) {
-      if (p.forced) return fail(VX_ERR_CAPACITY, "slot %d needs %lld audio rows, capacity %d", b, e->bbos[b] + e->bP[b] + max_tok, c.max_audio);
-      max_tok = room; cap_limited[b] = true;
-    }
-    const long long steps = max_tok + (p.forced ? 1 : 0);
+    long long steps = 0, room = 0;
+    VXC(batch_params_check(e, b, p, e->bS[b], e->bP[b], e->bbos[b], &steps, &cap_limited[b], &room));
     if (steps > bound) bound = steps;
-    ArState& st = e->h_bst[b];
-    st.top_k = p.top_k; st.temperature = p.temperature; st.max_new = cap_limited[b] ? (int)room : p.max_new_tokens;
-    st.exp_noise = p.exp_noise; st.noise_rows = p.noise_rows; st.seed = p.seed;
-    st.forced = p.forced ? (p.n_forced > 0 ? (const long long*)p.forced : (const long long*)e->btok) : nullptr;
-    st.n_forced = p.forced ? p.n_forced : 0;
+    batch_params_stage(e, b, p, cap_limited[b], room);
     if (p.exp_noise && p.noise_rows <= 0) return fail(VX_ERR_ARG, "noise_rows must be > 0");
   }
   VXC(sync_in(e, stream));
   HIPC(hipMemcpyAsync(e->bst, e->h_bst, (size_t)B * sizeof(ArState), hipMemcpyHostToDevice, e->es));
   const bool graph = !(c.flags & VX_FLAG_NO_GRAPH);
   hipGraphExec_t gx = nullptr;
-  if (graph) {
-    auto it = e->bgraphs.find(B);
-    if (it == e->bgraphs.end()) {
-      hipGraph_t gr = nullptr;
-      HIPC(hipStreamBeginCapture(e->es, hipStreamCaptureModeThreadLocal));
-      int r = enqueue_batch_step(e, B, e->es);
-      hipError_t ce = hipStreamEndCapture(e->es, &gr);
-      if (r != VX_OK) return r;
-      HIPC(ce);
-      HIPC(hipGraphInstantiate(&gx, gr, nullptr, nullptr, 0));
-      (void)hipGraphDestroy(gr);
-      e->bgraphs[B] = gx;
-    } else {
-      gx = it->second;
-    }
-  }
+  VXC(batch_graph(e, B, &gx));
   HIPC(hipEventRecord(e->ev_t[2], e->es));
   long long launched = 0;
   int slot = 0;
@@ -1966,6 +2016,7 @@ extern "C" int vx_batch_result(vx_engine* e, int32_t slot, int64_t* tokens, int3
                                int32_t* stop_reason) {
   if (!e) return fail(VX_ERR_ARG, "null engine");
   if (slot < 0 || slot >= e->bmax) return fail(VX_ERR_ARG, "bad slot");
+  if (e->bsess && e->bslot[slot] == SLOT_LIVE) return fail(VX_ERR_STATE, "slot %d is still decoding", slot);
   ON_DEVICE(e->cfg.device);
   const int n = e->bngen[slot];
   if (n_tokens) *n_tokens = n;
@@ -1975,6 +2026,172 @@ extern "C" int vx_batch_result(vx_engine* e, int32_t slot, int64_t* tokens, int3
     std::vector<int> tmp(n);
     if (n) HIPC(hipMemcpy(tmp.data(), e->btok + (size_t)slot * e->btok_stride, (size_t)n * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) tokens[i] = tmp[i];
+  }
+  if (e->bsess && e->bslot[slot] == SLOT_STOPPED) e->bslot[slot] = SLOT_VACANT;  // read: the slot may be admitted into again
+  return VX_OK;
+}
+
+// ------------------------------------------------------------------------------ continuous batching
+// A session over all max_batch slots: every slot is vacant, live (admitted, decoding) or stopped (its result not read yet).  The
+// step always runs at B = max_batch (one graph, shared with vx_batch_decode); vacant and stopped slots have done = 1, so the
+// sampler, the K / V append, the attention and the logits skip them and their rows of the shared GEMMs are ignored.
+extern "C" int vx_batch_open(vx_engine* e, void* stream) {
+  if (!e) return fail(VX_ERR_ARG, "null engine");
+  if (e->bmax < 2) return fail(VX_ERR_UNSUPPORTED, "continuous batching needs an engine created with max_batch >= 2");
+  if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+  const int d = e->cfg.d_model;
+  ON_DEVICE(e->cfg.device);
+  VXC(sync_in(e, stream));
+  for (int b = 0; b < e->bmax; ++b) {
+    ArState& st = e->h_bst[b];
+    memset(&st, 0, sizeof st);
+    st.done = 1; st.row = 0; st.temperature = 1.0f; st.max_new = -1;
+  }
+  HIPC(hipMemcpyAsync(e->bst, e->h_bst, (size_t)e->bmax * sizeof(ArState), hipMemcpyHostToDevice, e->es));
+  // a vacant slot's rows still go through the step's GEMMs and LayerNorms: they must hold finite values
+  HIPC(hipMemsetAsync(e->bx, 0, (size_t)e->bmax * d * 4, e->es));
+  HIPC(hipMemsetAsync(e->blogits, 0, (size_t)e->bmax * LOGITS_CUR * 4, e->es));
+  HIPC(hipStreamSynchronize(e->es));  // the staging states are rewritten by the next admission
+  for (int b = 0; b < e->bmax; ++b) {
+    e->bslot[b] = SLOT_VACANT; e->bleft[b] = 0; e->bcap[b] = false;
+    e->bprefilled[b] = false; e->bngen[b] = 0; e->breason[b] = 0;
+  }
+  e->bsess = true;
+  VXC(sync_out(e, stream));
+  return VX_OK;
+}
+
+extern "C" int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, const int64_t* const* text, const int32_t* S,
+                              const int64_t* const* prompt_cb0, const int32_t* P, const vx_decode_params* params, int32_t mode,
+                              void* stream) {
+  if (!e || !slots || !text || !S || !prompt_cb0 || !P || !params) return fail(VX_ERR_ARG, "null argument");
+  if (!e->bsess) return fail(VX_ERR_STATE, "vx_batch_admit needs an open session (vx_batch_open)");
+  if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+  if (n < 1 || n > e->bmax) return fail(VX_ERR_ARG, "n %d outside [1, max_batch=%d]", n, e->bmax);
+  if (mode != VX_ADMIT_BATCHED && mode != VX_ADMIT_PER_SLOT) return fail(VX_ERR_ARG, "unknown admission mode %d", mode);
+  if (mode == VX_ADMIT_BATCHED && !use_mfma(e)) return fail(VX_ERR_UNSUPPORTED, "batched admission needs the bf16 MFMA row kernels");
+  const vx_config& c = e->cfg;
+  const int bos = c.prepend_bos ? 1 : 0;
+  // every check before anything is written: a refused admission leaves all slots as they were
+  bool seen[BMAX] = {};
+  for (int z = 0; z < n; ++z) {
+    const int sl = slots[z];
+    if (sl < 0 || sl >= e->bmax) return fail(VX_ERR_ARG, "slot %d outside [0, max_batch=%d)", sl, e->bmax);
+    if (seen[sl]) return fail(VX_ERR_ARG, "slot %d admitted twice", sl);
+    seen[sl] = true;
+    if (e->bslot[sl] == SLOT_LIVE) return fail(VX_ERR_STATE, "slot %d is live", sl);
+    if (e->bslot[sl] == SLOT_STOPPED) return fail(VX_ERR_STATE, "slot %d has stopped but its result was not read", sl);
+  }
+  long long steps[BMAX] = {}, room[BMAX] = {};
+  bool capl[BMAX] = {};
+  for (int z = 0; z < n; ++z) {
+    if (!text[z] || (!prompt_cb0[z] && P[z] > 0)) return fail(VX_ERR_ARG, "null argument (utterance %d)", z);
+    if (S[z] <= 0 || P[z] < 0) return fail(VX_ERR_ARG, "S must be > 0 (valle.py:991), P >= 0");
+    if (S[z] > c.max_text || bos + P[z] + 1 > c.max_audio) return fail(VX_ERR_CAPACITY, "S=%d / P=%d exceed capacity", S[z], P[z]);
+    if (bos + P[z] == 0) return fail(VX_ERR_ARG, "empty audio prefix needs prepend_bos");
+    const vx_decode_params& p = params[z];
+    VXC(batch_params_check(e, slots[z], p, S[z], P[z], bos, &steps[z], &capl[z], &room[z]));
+    if (p.exp_noise && p.noise_rows <= 0) return fail(VX_ERR_ARG, "noise_rows must be > 0");
+  }
+  ON_DEVICE(c.device);
+  if (mode == VX_ADMIT_PER_SLOT) {  // prefill_impl touches only its slot (and synchronises the engine stream per call)
+    for (int z = 0; z < n; ++z) VXC(prefill_impl(e, slots[z], text[z], S[z], prompt_cb0[z], P[z], stream));
+  } else {
+    VXC(batch_prefill_impl(e, n, slots, text, S, prompt_cb0, P, stream));
+  }
+  // arm: the prefill left each slot's state in h_bst[slot] and synchronised; add the decode parameters
+  VXC(sync_in(e, stream));
+  for (int z = 0; z < n; ++z) {
+    const int sl = slots[z];
+    batch_params_stage(e, sl, params[z], capl[z], room[z]);
+    HIPC(hipMemcpyAsync(e->bst + sl, &e->h_bst[sl], sizeof(ArState), hipMemcpyHostToDevice, e->es));
+    e->bslot[sl] = SLOT_LIVE; e->bleft[sl] = steps[z] < 1 ? 1 : steps[z]; e->bcap[sl] = capl[z];
+    e->bprefilled[sl] = false;
+  }
+  VXC(sync_out(e, stream));
+  return VX_OK;
+}
+
+extern "C" int vx_batch_run(vx_engine* e, int32_t min_stopped, int32_t poll_steps, int32_t* stopped, int32_t* n_stopped,
+                            void* stream) {
+  if (!e) return fail(VX_ERR_ARG, "null engine");
+  if (!e->bsess) return fail(VX_ERR_STATE, "vx_batch_run needs an open session (vx_batch_open)");
+  if (!stopped || !n_stopped) return fail(VX_ERR_ARG, "null argument");
+  *n_stopped = 0;
+  const int B = e->bmax;
+  if (poll_steps <= 0) poll_steps = BATCH_POLL_DEFAULT;
+  if (min_stopped < 1) min_stopped = 1;
+  long long bound = 0;  // steps until every live slot has exhausted its bound
+  int live = 0;
+  for (int b = 0; b < B; ++b)
+    if (e->bslot[b] == SLOT_LIVE) { ++live; if (e->bleft[b] > bound) bound = e->bleft[b]; }
+  if (live == 0) return VX_OK;
+  ON_DEVICE(e->cfg.device);
+  VXC(sync_in(e, stream));
+  hipGraphExec_t gx = nullptr;
+  VXC(batch_graph(e, B, &gx));
+  HIPC(hipEventRecord(e->ev_t[2], e->es));
+  long long launched = 0, at_poll[2] = {0, 0};
+  int ps = 0, found = 0;
+  bool done = false, pending[2] = {false, false};
+  // a polled state: every live slot that has stopped is reported; a live slot past its bound that has not is an error
+  auto take = [&](int sl) -> int {
+    const ArState* hs = e->h_bst + (size_t)(1 + sl) * BMAX;
+    for (int b = 0; b < B; ++b) {
+      if (e->bslot[b] != SLOT_LIVE) continue;
+      if (hs[b].done) {
+        e->bslot[b] = SLOT_STOPPED;
+        e->bngen[b] = hs[b].n_gen; e->breason[b] = hs[b].stop_reason;
+        stopped[found++] = b;
+        --live;
+      } else if (at_poll[sl] >= e->bleft[b]) {
+        return fail(VX_ERR_STATE, "batched decode of slot %d did not terminate within %lld steps", b, e->bleft[b]);
+      }
+    }
+    return VX_OK;
+  };
+  while (!done) {
+    const long long n = (bound - launched) < poll_steps ? (bound - launched) : poll_steps;
+    for (long long i = 0; i < n; ++i) {
+      if (gx) HIPC(hipGraphLaunch(gx, e->es));
+      else VXC(enqueue_batch_step(e, B, e->es));
+    }
+    launched += n;
+    HIPC(hipMemcpyAsync(e->h_bst + (size_t)(1 + ps) * BMAX, e->bst, (size_t)B * sizeof(ArState), hipMemcpyDeviceToHost, e->es));
+    HIPC(hipEventRecord(e->ev_poll[ps], e->es));
+    pending[ps] = true; at_poll[ps] = launched;
+    const int other = ps ^ 1;
+    if (pending[other]) {  // keep one chunk in flight while the previous one is inspected
+      HIPC(hipEventSynchronize(e->ev_poll[other]));
+      pending[other] = false;
+      VXC(take(other));
+      if (found >= min_stopped || live == 0) done = true;
+    }
+    if (!done && launched >= bound) {
+      HIPC(hipEventSynchronize(e->ev_poll[ps]));
+      pending[ps] = false;
+      VXC(take(ps));
+      done = true;  // every live slot was past its bound: all of them have stopped (or take() failed)
+    }
+    ps = other;
+  }
+  for (int sl = 0; sl < 2; ++sl)  // the chunk still in flight: wait for it and report what stopped in it too
+    if (pending[sl]) { HIPC(hipEventSynchronize(e->ev_poll[sl])); pending[sl] = false; VXC(take(sl)); }
+  HIPC(hipEventRecord(e->ev_t[3], e->es));
+  HIPC(hipStreamSynchronize(e->es));
+  HIPC(hipGetLastError());
+  float ms = 0.f;
+  HIPC(hipEventElapsedTime(&ms, e->ev_t[2], e->ev_t[3]));
+  e->t_bdecode = ms;
+  e->n_blaunch = (double)launched;
+  for (int b = 0; b < B; ++b)
+    if (e->bslot[b] == SLOT_LIVE) e->bleft[b] -= launched;
+  *n_stopped = found;
+  VXC(sync_out(e, stream));
+  for (int i = 0; i < found; ++i) {
+    const int b = stopped[i];
+    if (e->bcap[b] && e->breason[b] == VX_STOP_MAX_NEW)
+      return fail(VX_ERR_CAPACITY, "capacity exceeded in slot %d: the KV cache filled (max_audio = %d rows) before the stop rule fired; raise max_audio", b, e->cfg.max_audio);
   }
   return VX_OK;
 }

@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvallex.so")
 VX_PREC_F32, VX_PREC_BF16, VX_PREC_FP8_NAR = 0, 1, 2
 BMAX = 64  # slots per engine (csrc/batch_kernels.hpp)
 VX_FLAG_TRACE_LOGITS, VX_FLAG_NO_GRAPH, VX_FLAG_SIMPLE_ROWS, VX_FLAG_POST_NORM, VX_FLAG_PRENET, VX_FLAG_VALLF = 1, 2, 4, 8, 16, 32
+VX_ADMIT_BATCHED, VX_ADMIT_PER_SLOT = 0, 1
 STOP_REASONS = {0: "none", 1: "eos_argmax", 2: "eos_sample", 3: "length", 4: "max_new"}
 
 
@@ -62,6 +63,10 @@ _SIGS = {
                                        C.POINTER(C.c_int32), C.c_void_p]),
     "vx_batch_decode": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(VxDecodeParams), C.c_void_p]),
     "vx_batch_result": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vx_batch_open": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vx_batch_admit": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(VxDecodeParams), C.c_int32, C.c_void_p]),
+    "vx_batch_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "vx_nar_batch": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_void_p]),
     "vx_nar_batch_ex": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.c_void_p]),
     "vx_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
@@ -270,12 +275,12 @@ class Engine:
         P = (C.c_int32 * n)(*[p.numel() for p in proms])
         _check(self.lib.vx_batch_prefill_all(self.h, n, tp, S, pp, P, stream))
 
-    def batch_decode(self, n_slots: int, top_k=-100, temperature=1.0, seeds=None, exp_noise=None, forced=None,
-                     max_new_tokens=-1, stream=None):
-        """exp_noise / forced: optional per-slot lists of DEVICE tensors (kept alive here for the call)."""
-        arr = (VxDecodeParams * n_slots)()
-        keep = []
-        for b in range(n_slots):
+    @staticmethod
+    def _decode_params(n, top_k, temperature, seeds, exp_noise, forced, max_new_tokens):
+        """(VxDecodeParams array, per-entry list of the device tensors its pointers refer to)."""
+        arr = (VxDecodeParams * n)()
+        keep = [[] for _ in range(n)]
+        for b in range(n):
             p = arr[b]
             p.struct_size = C.sizeof(VxDecodeParams)
             p.top_k, p.temperature, p.max_new_tokens = int(top_k), float(temperature), int(max_new_tokens)
@@ -284,19 +289,59 @@ class Engine:
                 t = exp_noise[b].to(torch.float32).contiguous()
                 assert t.is_cuda and t.shape[1] == 1025
                 p.exp_noise, p.noise_rows = _ptr(t), t.shape[0]
-                keep.append(t)
+                keep[b].append(t)
             if forced is not None and forced[b] is not None:
                 t = forced[b].to(torch.int64).contiguous()
                 assert t.is_cuda
                 p.forced, p.n_forced = _ptr(t), t.numel()
-                keep.append(t)
+                keep[b].append(t)
+        return arr, keep
+
+    def batch_decode(self, n_slots: int, top_k=-100, temperature=1.0, seeds=None, exp_noise=None, forced=None,
+                     max_new_tokens=-1, stream=None):
+        """exp_noise / forced: optional per-slot lists of DEVICE tensors (kept alive here for the call)."""
+        arr, keep = self._decode_params(n_slots, top_k, temperature, seeds, exp_noise, forced, max_new_tokens)
         _check(self.lib.vx_batch_decode(self.h, n_slots, arr, stream))
+
+    # -- continuous batching (vx_batch_open / _admit / _run) ------------------------------------------
+    def batch_open(self, stream=None):
+        """Starts a session: every slot vacant."""
+        _check(self.lib.vx_batch_open(self.h, stream))
+        self._slot_keep = {}
+
+    def batch_admit(self, slots, texts, prompts_cb0, top_k=-100, temperature=1.0, seeds=None, exp_noise=None, forced=None,
+                    max_new_tokens=-1, batched=True, stream=None):
+        """Prefills ``texts[z]`` / ``prompts_cb0[z]`` into vacant slot ``slots[z]`` and arms it (seeds / exp_noise / forced per
+        utterance, as for ``batch_decode``).  ``batched``: one pass over the concatenated rows; False: the per-slot prefill.  The
+        device tensors a slot's parameters point to are kept until that slot's result is read."""
+        n = len(slots)
+        texts = [t.to(torch.int64).contiguous() for t in texts]
+        proms = [p.to(torch.int64).contiguous() for p in prompts_cb0]
+        arr, keep = self._decode_params(n, top_k, temperature, seeds, exp_noise, forced, max_new_tokens)
+        sl = (C.c_int32 * n)(*[int(s) for s in slots])
+        tp = (C.c_void_p * n)(*[_ptr(t) for t in texts])
+        pp = (C.c_void_p * n)(*[_ptr(p) for p in proms])
+        S = (C.c_int32 * n)(*[t.numel() for t in texts])
+        P = (C.c_int32 * n)(*[p.numel() for p in proms])
+        _check(self.lib.vx_batch_admit(self.h, n, sl, tp, S, pp, P, arr, VX_ADMIT_BATCHED if batched else VX_ADMIT_PER_SLOT, stream))
+        for s, k in zip(slots, keep):
+            self._slot_keep[int(s)] = k
+
+    def batch_run(self, min_stopped: int = 1, poll_steps: int = 0, stream=None):
+        """Decodes until at least ``min_stopped`` live slots have stopped (or none is live); returns the list of stopped slots."""
+        out = (C.c_int32 * max(self.max_batch, 1))()
+        n = C.c_int32()
+        code = self.lib.vx_batch_run(self.h, int(min_stopped), int(poll_steps), out, C.byref(n), stream)
+        self._last_stopped = [out[i] for i in range(n.value)]
+        _check(code)
+        return list(self._last_stopped)
 
     def batch_result(self, slot: int):
         n, reason = C.c_int32(), C.c_int32()
         _check(self.lib.vx_batch_result(self.h, slot, None, 0, C.byref(n), C.byref(reason)))
         toks = torch.empty(n.value, dtype=torch.int64)
         _check(self.lib.vx_batch_result(self.h, slot, _ptr(toks), n.value, C.byref(n), C.byref(reason)))
+        getattr(self, "_slot_keep", {}).pop(int(slot), None)  # continuous batching: the slot's device tensors may go now
         return toks, reason.value
 
     def nar_batch(self, texts, prompts, tokens, out_device=None, stream=None, forced_codes=None):

@@ -195,20 +195,14 @@ class VALLE:
         """Engine extension (BASELINE configs[2]): ``utterances`` = list of (x, x_lens, y[, enroll_x_lens]) as for
         ``inference``; up to ``max_batch`` of them advance together, one shared weight stream per AR step, each with
         its own KV cache / sampler / stop rule; the NAR stages then run per utterance.  Returns a list of (1,T_i,Q)."""
-        eng = self.engine()
-        if eng.max_batch < 2:
-            raise RuntimeError("construct the model with max_batch >= 2 for inference_batch")
-        Q, bos = self.num_quantizers, int(self.ar_audio_prepend_bos)
+        eng = self._batch_engine("inference_batch")
+        Q = self.num_quantizers
         out = [None] * len(utterances)
         for g0 in range(0, len(utterances), eng.max_batch):
             group = utterances[g0 : g0 + eng.max_batch]
             for b, u in enumerate(group):
-                x, x_lens, y = u[0], u[1], u[2]
-                assert x.ndim == 2 and x_lens.ndim == 1 and y.ndim == 3 and y.shape[0] == 1 and torch.all(x_lens > 0)
-                if x.shape[1] != int(x_lens.max()) or x.shape[0] != 1:
-                    raise RuntimeError("x must be one unpadded sequence per utterance")
-                if _ids_out_of_range(x, y[..., :Q]):
-                    raise IndexError("index out of range in self")
+                x, y = u[0], u[2]
+                self._check_batch_utterance(u)
                 if not (batched_prefill and eng.mfma_rows):
                     eng.batch_prefill(b, x[0], y[0, :, 0].contiguous())
             if batched_prefill and eng.mfma_rows:  # one pass over the concatenated rows of the whole group
@@ -217,29 +211,110 @@ class VALLE:
             eng.batch_decode(len(group), top_k=top_k, temperature=temperature, seeds=sd)
             todo = []  # (index, text_nar, prompts, tokens) of the utterances that go through the NAR stages
             for b, u in enumerate(group):
-                x, x_lens, y = u[0], u[1], u[2]
-                enroll = u[3] if len(u) > 3 else None
                 tokens, reason = eng.batch_result(b)
-                if tokens.numel() == 0 and not bos:
-                    raise SyntaxError("well trained model shouldn't reach here.")
-                if Q == 1 or tokens.numel() == 0:
-                    codes = torch.zeros((tokens.numel(), Q), dtype=torch.int64)
-                    codes[:, 0] = tokens
-                    out[g0 + b] = codes.unsqueeze(0).to(self.device)
-                    continue
-                text_nar = x[0]
-                if self.prefix_mode in [2, 4]:
-                    enrolled_len = int(enroll.max().item())
-                    text_nar = torch.concat([x[0][:1], x[0][enrolled_len - 1:]])
-                todo.append((g0 + b, text_nar, y[0, :, :Q].contiguous(), tokens))
-            if todo and batched_nar:
-                res = eng.nar_batch([t[1] for t in todo], [t[2] for t in todo], [t[3] for t in todo], out_device=self.device)
-                for (i, *_), r in zip(todo, res):
-                    out[i] = r.unsqueeze(0)
-            else:
-                for i, tn, pr, tk in todo:
-                    out[i] = eng.nar(tn, pr, tk, out_device=self.device).unsqueeze(0)
+                r = self._ar_finished(u, tokens)
+                if isinstance(r, torch.Tensor):
+                    out[g0 + b] = r
+                else:
+                    todo.append((g0 + b,) + r)
+            for i, r in self._run_nar(eng, todo, batched_nar):
+                out[i] = r
         return out
+
+    # ---- shared by inference_batch and inference_stream ----------------------------------------------
+    def _batch_engine(self, what: str):
+        eng = self.engine()
+        if eng.max_batch < 2:
+            raise RuntimeError(f"construct the model with max_batch >= 2 for {what}")
+        return eng
+
+    def _check_batch_utterance(self, u):
+        x, x_lens, y = u[0], u[1], u[2]
+        assert x.ndim == 2 and x_lens.ndim == 1 and y.ndim == 3 and y.shape[0] == 1 and torch.all(x_lens > 0)
+        if x.shape[1] != int(x_lens.max()) or x.shape[0] != 1:
+            raise RuntimeError("x must be one unpadded sequence per utterance")
+        if _ids_out_of_range(x, y[..., :self.num_quantizers]):
+            raise IndexError("index out of range in self")
+
+    def _ar_finished(self, u, tokens):
+        """An utterance's AR tokens -> its final (1, T, Q) codes when no NAR stage runs (Q == 1, empty output), else the
+        (text_nar, prompts, tokens) of its NAR stages (prefix-mode 2/4 trim as in inference, valle.py:1068-1079)."""
+        Q, bos = self.num_quantizers, int(self.ar_audio_prepend_bos)
+        x, y = u[0], u[2]
+        enroll = u[3] if len(u) > 3 else None
+        if tokens.numel() == 0 and not bos:
+            raise SyntaxError("well trained model shouldn't reach here.")
+        if Q == 1 or tokens.numel() == 0:
+            codes = torch.zeros((tokens.numel(), Q), dtype=torch.int64)
+            codes[:, 0] = tokens
+            return codes.unsqueeze(0).to(self.device)
+        text_nar = x[0]
+        if self.prefix_mode in [2, 4]:
+            enrolled_len = int(enroll.max().item())
+            text_nar = torch.concat([x[0][:1], x[0][enrolled_len - 1:]])
+        return (text_nar, y[0, :, :Q].contiguous(), tokens)
+
+    def _run_nar(self, eng, todo, batched_nar: bool):
+        """[(index, text_nar, prompts, tokens)] -> [(index, (1, T, Q) codes)]: one vx_nar_batch over all, or vx_nar each."""
+        if todo and batched_nar:
+            res = eng.nar_batch([t[1] for t in todo], [t[2] for t in todo], [t[3] for t in todo], out_device=self.device)
+            return [(t[0], r.unsqueeze(0)) for t, r in zip(todo, res)]
+        return [(i, eng.nar(tn, pr, tk, out_device=self.device).unsqueeze(0)) for i, tn, pr, tk in todo]
+
+    @torch.no_grad()
+    def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
+                         poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None):
+        """Engine extension: continuous batching.  A generator over ``utterances`` (as for ``inference_batch``) that yields
+        ``(index, codes)``, codes (1, T_i, Q) as ``inference_batch`` returns them, as utterances finish.  A slot whose utterance
+        stopped is refilled from the queue while the others keep decoding: new utterances are admitted once ``refill_at``
+        slots are free (default max_batch // 16, at least 1) and whenever the rest of the queue fits.  Finished utterances
+        wait for their NAR stages until ``nar_group`` (default max_batch) are pending or the queue is empty.  ``seeds[i]``
+        belongs to utterance i, so the codes do not depend on the schedule.  ``batched_admit=False`` prefills slot by slot
+        (bitwise the static path); ``poll_steps``: steps between stop polls (0: the engine default)."""
+        eng = self._batch_engine("inference_stream")
+        utterances = list(utterances)
+        for u in utterances:
+            self._check_batch_utterance(u)
+        N, B = len(utterances), eng.max_batch
+        if seeds is None:
+            seeds = [int(torch.randint(0, 2**62, (1,))) for _ in utterances]
+        elif len(seeds) < N:
+            raise ValueError(f"{len(seeds)} seeds for {N} utterances")
+        refill_at = max(1, B // 16) if refill_at is None else max(1, int(refill_at))
+        nar_group = B if nar_group is None else max(1, int(nar_group))
+        batched_admit = batched_admit and eng.mfma_rows
+        return self._stream(eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at)
+
+    def _stream(self, eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at):
+        N, B = len(utterances), eng.max_batch
+        eng.batch_open()
+        free = list(range(B))
+        live = {}      # slot -> utterance index
+        pending = []   # (index, text_nar, prompts, tokens) waiting for the NAR stages
+        nxt = 0        # next utterance of the queue
+        while nxt < N or live or pending:
+            k = min(len(free), N - nxt)
+            if k and (k >= refill_at or k == N - nxt or not live):
+                slots, free = free[:k], free[k:]
+                us = utterances[nxt : nxt + k]
+                eng.batch_admit(slots, [u[0][0] for u in us], [u[2][0, :, 0].contiguous() for u in us], top_k=top_k,
+                                temperature=temperature, seeds=seeds[nxt : nxt + k], batched=batched_admit)
+                live.update((s, nxt + z) for z, s in enumerate(slots))
+                nxt += k
+            if live:
+                need = 1 if nxt >= N else max(1, refill_at - len(free))
+                for s in eng.batch_run(need, poll_steps):
+                    i = live.pop(s)
+                    tokens, _ = eng.batch_result(s)
+                    free.append(s)
+                    r = self._ar_finished(utterances[i], tokens)
+                    if isinstance(r, torch.Tensor):
+                        yield i, r
+                    else:
+                        pending.append((i,) + r)
+            if pending and (len(pending) >= nar_group or nxt >= N):
+                done, pending = pending, []
+                yield from self._run_nar(eng, done, batched_nar)
 
     @torch.no_grad()
     def continual(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -274,6 +349,9 @@ class VALLF(VALLE):
         raise AttributeError("'VALLF' object has no attribute 'continual'")  # valle.py:1139 defines it on VALLE only
 
     def inference_batch(self, *a, **k):
+        raise NotImplementedError("VALL-F runs on the batch-1 path only")
+
+    def inference_stream(self, *a, **k):
         raise NotImplementedError("VALL-F runs on the batch-1 path only")
 
 
