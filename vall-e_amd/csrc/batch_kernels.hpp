@@ -14,7 +14,7 @@ constexpr int BMAX = 64;  // slots per engine (up to four 16-row MFMA halves)
 typedef __bf16 bf16x8b_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-// BE_LOGITS_MAP: BE_LOGITS for the rows of a slot-mapped admission - A row z belongs to slot slot_map[z] (vx_batch_admit)
+// BE_LOGITS_MAP: BE_LOGITS for the rows of a batched prefill - A row z belongs to slot slot_map[z]
 enum BgemmEpi { BE_QKV = 0, BE_RELU = 1, BE_PARTIAL = 2, BE_LOGITS = 3, BE_LOGITS_MAP = 4 };
 
 struct BgemmArgs {
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void ln_batch_kernel(float* __restrict__ x, co
                                                        const float* __restrict__ beta, bf16* __restrict__ h, int d) {
   ln_batch_body<KG>(x, part, pbias, gamma, beta, h, d, blockIdx.x, blockIdx.x);
 }
-// Slot-mapped admission (vx_batch_admit): workgroup z normalises slot slot_map[z]'s row of x into row z of h (the A operand of
+// Batched prefill: workgroup z normalises slot slot_map[z]'s row of x into row z of h (the A operand of
 // the BE_LOGITS_MAP head).  x is only read.
 __global__ __launch_bounds__(256) void ln_batch_map_kernel(float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, bf16* __restrict__ h, int d,

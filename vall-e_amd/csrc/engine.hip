@@ -1,6 +1,7 @@
 // libvallex.so — host side of the engine and the C ABI declared in include/vallex.h.
 // One engine = one model replica on one GPU: weights, KV cache, activation arena, a private
-// stream and the captured hipGraph of one AR decode step.
+// stream and the captured hipGraphs of the AR decode steps.  Every AR decode (batch-1, static
+// batch, continuous-batching session) runs through one polled replay loop, replay_polled().
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -161,8 +162,7 @@ struct vx_engine {
   std::unordered_map<int, hipGraphExec_t> bgraphs;
   int *d_seg_start = nullptr, *d_seg_len = nullptr;  // segments of the concatenated row buffer (batched NAR / prefill)
   int* d_seg_text = nullptr;                          // per-segment text length (prefix mask of a batched prefill)
-  int* d_seg_slot = nullptr;                          // slot of every segment of a slot-mapped batched prefill (vx_batch_admit)
-  const int* seg_slot = nullptr;                      // = d_seg_slot while such a prefill runs its stack, else nullptr (z -> z)
+  int* d_seg_slot = nullptr;                          // slot of every segment of a batched prefill
   // prenets (VX_FLAG_PRENET): scratch rows, conv weights re-laid out as [k][ci][co], decode-step vectors
   float *pn_a = nullptr, *pn_b = nullptr, *pn_h1 = nullptr, *pn_h2 = nullptr, *pn_text = nullptr, *d_zero = nullptr;
   float *ar_e = nullptr, *ar_h1 = nullptr, *ar_h2 = nullptr;
@@ -182,9 +182,7 @@ struct vx_engine {
   long long bleft[BMAX] = {};
   bool bcap[BMAX] = {};
   double t_bdecode = 0, n_blaunch = 0;
-  // graph
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t gexec = nullptr;
+  hipGraphExec_t gexec = nullptr;  // the batch-1 step
   // per-utterance state
   int S = 0, P = 0, bos = 0;
   bool prefilled = false, decoded = false;
@@ -543,10 +541,9 @@ extern "C" void vx_destroy(vx_engine* e) {
   if (!e) return;
   DevGuard dev_guard_(e->cfg.device);
   if (e->es) (void)hipStreamSynchronize(e->es);
-  for (auto& kvp : e->bgraphs) (void)hipGraphExecDestroy(kvp.second);
+  for (auto& kvp : e->bgraphs) if (kvp.second) (void)hipGraphExecDestroy(kvp.second);
   if (e->h_bst) (void)hipHostFree(e->h_bst);
   if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
-  if (e->graph) (void)hipGraphDestroy(e->graph);
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->d_noise) (void)hipFree(e->d_noise);
   if (e->d_forced) (void)hipFree(e->d_forced);
@@ -1012,10 +1009,10 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
     VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
     if (tg) gemm_mark(e, 2.0 * M * 3 * d * d);
     }
-    if (fill_cache && e->nseg > 0) {  // batched prefill: segment z -> slot z (slot seg_slot[z] when admitting)
+    if (fill_cache && e->nseg > 0) {  // batched prefill: segment z -> slot d_seg_slot[z]
       const size_t kvl = (size_t)2 * H * e->ctx_max * 64;  // elements per layer
       kv_scatter_seg_kernel<bf16><<<dim3(e->max_seg_len, e->nseg), 256, 0, e->es>>>(
-          (const bf16*)e->QKV, e->bkv + li * kvl, e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, d, 64, e->ctx_max, e->seg_slot);
+          (const bf16*)e->QKV, e->bkv + li * kvl, e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, d, 64, e->ctx_max, e->d_seg_slot);
     } else if (fill_cache) {
       char* kc = kv_base + li * kv_layer;
       char* vc = kc + kv_layer / 2;
@@ -1182,17 +1179,33 @@ static int enqueue_head(vx_engine* e, hipStream_t s, const float* x = nullptr, f
   return launch_gemv(e->bf16, a, e->num_cu, s);
 }
 
+// The checks of one utterance to prefill (no HIP call); idx >= 0 names it in a batch.
+static int check_utterance(vx_engine* e, const int64_t* text, int32_t S, const int64_t* prompt_cb0, int32_t P, int idx) {
+  if (!text || (!prompt_cb0 && P > 0))
+    return idx < 0 ? fail(VX_ERR_ARG, "null argument") : fail(VX_ERR_ARG, "null argument (utterance %d)", idx);
+  if (S <= 0 || P < 0) return fail(VX_ERR_ARG, "S must be > 0 (valle.py:991), P >= 0");
+  const vx_config& c = e->cfg;
+  const int A = (c.prepend_bos ? 1 : 0) + P;
+  if (S > c.max_text || A + 1 > c.max_audio) return fail(VX_ERR_CAPACITY, "S=%d / P=%d exceed capacity", S, P);
+  if (A == 0) return fail(VX_ERR_ARG, "empty audio prefix needs prepend_bos");
+  return VX_OK;
+}
+// The decode state of a prefilled utterance as of "pass 0 computed" (row = its last prefill row), without decode parameters.
+static void seed_state(ArState& st, int S, int P, int bos, int row, int kv_text, bool trace) {
+  memset(&st, 0, sizeof st);
+  st.S = S; st.bos = bos; st.P = P; st.row = row; st.kv_text = kv_text;
+  st.temperature = 1.0f; st.max_new = -1; st.trace_logits = trace ? 1 : 0;
+}
+
 // Shared by vx_ar_prefill (slot < 0: the batch-1 buffers) and vx_batch_prefill (slot >= 0).
 static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, const int64_t* prompt_cb0, int32_t P,
                         void* stream) {
-  if (!e || !text || (!prompt_cb0 && P > 0)) return fail(VX_ERR_ARG, "null argument");
+  if (!e) return fail(VX_ERR_ARG, "null argument");
   if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
-  if (S <= 0 || P < 0) return fail(VX_ERR_ARG, "S must be > 0 (valle.py:991), P >= 0");
+  VXC(check_utterance(e, text, S, prompt_cb0, P, -1));
   const vx_config& c = e->cfg;
   const bool vf = e->vallf;  // VALL-F: the stack runs over the audio rows only, the text is cross-attention memory (valle.py:598-632)
   const int bos = c.prepend_bos ? 1 : 0, A = bos + P, M = vf ? A : S + A, d = c.d_model;
-  if (S > c.max_text || A + 1 > c.max_audio) return fail(VX_ERR_CAPACITY, "S=%d / P=%d exceed capacity", S, P);
-  if (A == 0) return fail(VX_ERR_ARG, "empty audio prefix needs prepend_bos");
   if (slot >= e->bmax) return fail(VX_ERR_ARG, "slot %d >= max_batch %d", slot, e->bmax);
   ON_DEVICE(c.device);
   VXC(sync_in(e, stream));
@@ -1226,13 +1239,8 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
   if (vf) { e->mem_len = S; VXC(run_stack_f(e, e->ar_l, M, d, c.nhead, 0, -1, true, e->xkv_ar, S)); }
   else VXC(run_stack(e, e->ar_l, M, d, c.nhead, S, -1, true, kv_base));
   HIPC(hipMemcpyAsync(x_dst, e->X + (size_t)(M - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
-  // decode state as of "pass 0 computed"
   ArState& st = slot < 0 ? e->h_st[0] : e->h_bst[slot];
-  memset(&st, 0, sizeof st);
-  st.S = S; st.bos = bos; st.P = P; st.row = M - 1; st.pass = 0;
-  st.kv_text = e->vallf ? 0 : S;
-  st.temperature = 1.0f; st.max_new = -1;
-  st.trace_logits = (slot < 0 && (c.flags & VX_FLAG_TRACE_LOGITS)) ? 1 : 0;
+  seed_state(st, S, P, bos, M - 1, vf ? 0 : S, slot < 0 && (c.flags & VX_FLAG_TRACE_LOGITS));
   HIPC(hipMemcpyAsync(st_dst, &st, sizeof st, hipMemcpyHostToDevice, e->es));
   VXC(enqueue_head(e, e->es, x_dst, lg_dst, st_dst, true));
   HIPC(hipGetLastError());
@@ -1266,17 +1274,15 @@ extern "C" int vx_batch_prefill(vx_engine* e, int32_t slot, const int64_t* text,
   return prefill_impl(e, slot, text, S, prompt_cb0, P, stream);
 }
 
-// All slots' prefills as ONE pass over the concatenated rows (segment z = slot z, starts at a multiple of 64 rows):
+// Several slots' prefills as ONE pass over the concatenated rows (each segment starts at a multiple of 64 rows):
 // the GEMMs see sum(M_z) rows instead of 32 separate ~270-row problems, attention runs per segment with each
 // segment's own prefix mask, K/V go straight to each slot's cache.  Same results as vx_batch_prefill per slot up
 // to the GEMM kernel the dispatcher picks for the larger row count.
 static int ensure_rows(vx_engine* e, size_t rows, size_t audio_rows, size_t text_rows);
-static void launch_ln_batch(float* x, const float* part, int kgroups, const float* pbias, const float* gamma, const float* beta,
-                            bf16* h, int B, int d, hipStream_t s);
 template <int EPI> static int launch_bgemm(const BgemmArgs& a, hipStream_t s);
 
-// slots == nullptr: segment z -> slot z (vx_batch_prefill_all).  Otherwise segment z -> slot slots[z] (vx_batch_admit): only those
-// slots' KV caches, bx / blogits / trace rows and ArState are written; bh rows are step scratch.
+// Segment z -> slot slots[z]: only those slots' KV caches, bx / blogits / trace rows and ArState are written; bh rows are step
+// scratch.
 static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, const int64_t* const* text, const int32_t* S,
                               const int64_t* const* prompt_cb0, const int32_t* P, void* stream) {
   if (!e || !text || !S || !prompt_cb0 || !P) return fail(VX_ERR_ARG, "null argument");
@@ -1289,12 +1295,8 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
   size_t rows = 0;
   int maxlen = 0;
   for (int b = 0; b < n; ++b) {
-    if (!text[b] || (!prompt_cb0[b] && P[b] > 0)) return fail(VX_ERR_ARG, "null argument (utterance %d)", b);
-    if (S[b] <= 0 || P[b] < 0) return fail(VX_ERR_ARG, "S must be > 0 (valle.py:991), P >= 0");
-    const int A = bos + P[b];
-    if (S[b] > c.max_text || A + 1 > c.max_audio) return fail(VX_ERR_CAPACITY, "S=%d / P=%d exceed capacity", S[b], P[b]);
-    if (A == 0) return fail(VX_ERR_ARG, "empty audio prefix needs prepend_bos");
-    start[b] = (int)rows; len[b] = S[b] + A; tlen[b] = S[b];
+    VXC(check_utterance(e, text[b], S[b], prompt_cb0[b], P[b], b));
+    start[b] = (int)rows; len[b] = S[b] + bos + P[b]; tlen[b] = S[b];
     rows += (size_t)((len[b] + 63) / 64) * 64;
     if (len[b] > maxlen) maxlen = len[b];
   }
@@ -1305,7 +1307,7 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
   HIPC(hipMemcpyAsync(e->d_seg_start, start.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
   HIPC(hipMemcpyAsync(e->d_seg_len, len.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
   HIPC(hipMemcpyAsync(e->d_seg_text, tlen.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
-  if (slots) HIPC(hipMemcpyAsync(e->d_seg_slot, slots, n * sizeof(int), hipMemcpyHostToDevice, e->es));
+  HIPC(hipMemcpyAsync(e->d_seg_slot, slots, n * sizeof(int), hipMemcpyHostToDevice, e->es));
   HIPC(hipMemsetAsync(e->X, 0, rows * (size_t)d * 4, e->es));  // padding rows must stay finite (they feed V^T columns)
   static const long long bos_id = NUM_AUDIO_TOKENS + 1;  // valle.py:1006-1007
   for (int b = 0; b < n; ++b) {
@@ -1322,33 +1324,26 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
                                            W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, xb + (size_t)S[b] * d, A);
   }
   e->nseg = n; e->max_seg_len = maxlen; e->seg_text_on = true;
-  e->seg_slot = slots ? e->d_seg_slot : nullptr;
   int rc = run_stack(e, e->ar_l, (int)rows, d, c.nhead, 0, -1, true);
-  e->nseg = 0; e->seg_text_on = false; e->seg_slot = nullptr;
+  e->nseg = 0; e->seg_text_on = false;
   VXC(rc);
-  // decode state as of "pass 0 computed", last row of every segment = the slot's current activation
+  // last row of every segment = the slot's current activation
   for (int b = 0; b < n; ++b) {
-    const int sl = slots ? slots[b] : b;
+    const int sl = slots[b];
     HIPC(hipMemcpyAsync(e->bx + (size_t)sl * d, e->X + (size_t)(start[b] + len[b] - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
-    ArState& st = e->h_bst[sl];
-    memset(&st, 0, sizeof st);
-    st.S = S[b]; st.bos = bos; st.P = P[b]; st.row = len[b] - 1; st.pass = 0; st.kv_text = S[b];
-    st.temperature = 1.0f; st.max_new = -1;
-    if (slots) HIPC(hipMemcpyAsync(e->bst + sl, &st, sizeof(ArState), hipMemcpyHostToDevice, e->es));
+    seed_state(e->h_bst[sl], S[b], P[b], bos, len[b] - 1, S[b], false);
+    HIPC(hipMemcpyAsync(e->bst + sl, &e->h_bst[sl], sizeof(ArState), hipMemcpyHostToDevice, e->es));
   }
-  if (!slots) HIPC(hipMemcpyAsync(e->bst, e->h_bst, (size_t)n * sizeof(ArState), hipMemcpyHostToDevice, e->es));
   // first logits of every slot: final LayerNorm + head, as at the end of a batched step
-  const float *ng = W<float>(e, "ar_decoder.norm.weight"), *nb = W<float>(e, "ar_decoder.norm.bias");
-  if (slots) ln_batch_map_kernel<<<n, 256, 0, e->es>>>(e->bx, ng, nb, e->bh, d, e->d_seg_slot);
-  else launch_ln_batch(e->bx, nullptr, 0, nullptr, ng, nb, e->bh, n, d, e->es);
+  ln_batch_map_kernel<<<n, 256, 0, e->es>>>(e->bx, W<float>(e, "ar_decoder.norm.weight"), W<float>(e, "ar_decoder.norm.bias"), e->bh, d,
+                                            e->d_seg_slot);
   BgemmArgs hgm{};
   hgm.st = e->bst; hgm.B = n;
   hgm.A = e->bh; hgm.W = W<bf16>(e, "ar_predict_layer.weight"); hgm.N = AR_VOCAB; hgm.K = d; hgm.kgroups = 1;
   hgm.logits = e->blogits; hgm.logits_stride = LOGITS_CUR;
   hgm.trace = e->btrace; hgm.trace_rows = e->btok_stride;
-  hgm.slot_map = slots ? e->d_seg_slot : nullptr;
-  if (slots) VXC(launch_bgemm<BE_LOGITS_MAP>(hgm, e->es));
-  else VXC(launch_bgemm<BE_LOGITS>(hgm, e->es));
+  hgm.slot_map = e->d_seg_slot;
+  VXC(launch_bgemm<BE_LOGITS_MAP>(hgm, e->es));
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(e->ev_t[1], e->es));
   HIPC(hipStreamSynchronize(e->es));  // the staging state is reused by decode
@@ -1356,7 +1351,7 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
   HIPC(hipEventElapsedTime(&ms, e->ev_t[0], e->ev_t[1]));
   e->t_prefill = ms;
   for (int b = 0; b < n; ++b) {
-    const int sl = slots ? slots[b] : b;
+    const int sl = slots[b];
     e->bS[sl] = S[b]; e->bP[sl] = P[b]; e->bbos[sl] = bos;
     e->bprefilled[sl] = true; e->bngen[sl] = 0; e->breason[sl] = 0;
   }
@@ -1367,7 +1362,9 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
 extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S,
                                     const int64_t* const* prompt_cb0, const int32_t* P, void* stream) {
   if (e) e->bsess = false;  // the static calls end a continuous-batching session
-  return batch_prefill_impl(e, n, nullptr, text, S, prompt_cb0, P, stream);
+  int32_t slots[BMAX];  // segment z -> slot z
+  for (int z = 0; z < BMAX; ++z) slots[z] = z;
+  return batch_prefill_impl(e, n, slots, text, S, prompt_cb0, P, stream);
 }
 
 // One decode step: sample from the newest logits, append, run the 12-layer stack on the new
@@ -1641,26 +1638,100 @@ static int enqueue_ar_step_f(vx_engine* e, hipStream_t s) {
   return enqueue_head(e, s);
 }
 
+// The checks of one utterance's decode parameters (no HIP call) and its step bound: the launches after which the stop rule must
+// have fired (>= 1).  16 S + 1 tokens is the WORST case (valle.py:1047); a trained model stops at EOS long before it, so a long
+// text must not be refused up front: the bound is clamped to the rows the KV cache has (*cap_limited; `room` of them), and only a
+// decode that really fills them while the stop rule has not fired is a capacity error.  S / P / bos are the prefill geometry;
+// slot >= 0 names the batch slot in the message.
+static int decode_bound(vx_engine* e, int slot, const vx_decode_params& p, int S, int P, int bos, long long* steps,
+                        bool* cap_limited, long long* room) {
+  if (p.struct_size != (int32_t)sizeof(vx_decode_params)) return fail(VX_ERR_ARG, "vx_decode_params.struct_size mismatch");
+  if (!(p.temperature > 0.f)) return fail(VX_ERR_ARG, "temperature must be > 0");
+  long long max_tok = 16LL * S + 1 - bos;  // appended tokens (valle.py:1047: stops once bos + n_gen > 16 S)
+  if (p.forced) max_tok = p.n_forced;
+  else if (p.max_new_tokens >= 0 && p.max_new_tokens < max_tok) max_tok = p.max_new_tokens;
+  const int cap = e->cfg.max_audio;
+  *room = (long long)cap - bos - P;  // >= 1 (checked at prefill)
+  *cap_limited = false;
+  if (max_tok > *room) {
+    if (p.forced)
+      return slot < 0 ? fail(VX_ERR_CAPACITY, "need %lld audio rows, capacity %d", bos + P + max_tok, cap)
+                      : fail(VX_ERR_CAPACITY, "slot %d needs %lld audio rows, capacity %d", slot, bos + P + max_tok, cap);
+    max_tok = *room; *cap_limited = true;
+  }
+  // step j samples from logits j and appends token j+1; the step that appends the last admissible token also raises the stop
+  // flag, so max_tok launches suffice (teacher forcing needs one more to close the sequence); EOS can only end it earlier.
+  *steps = max_tok + (p.forced ? 1 : 0);
+  if (*steps < 1) *steps = 1;
+  return VX_OK;
+}
+
+// Captures enqueue(e->es) into *out on first use; with VX_FLAG_NO_GRAPH *out stays null and the step is enqueued directly.
+template <typename F> static int step_graph(vx_engine* e, hipGraphExec_t* out, F enqueue) {
+  if (*out || (e->cfg.flags & VX_FLAG_NO_GRAPH)) return VX_OK;
+  hipGraph_t gr = nullptr;
+  HIPC(hipStreamBeginCapture(e->es, hipStreamCaptureModeThreadLocal));
+  const int r = enqueue(e->es);
+  hipError_t ce = hipStreamEndCapture(e->es, &gr);
+  if (r == VX_OK && ce == hipSuccess) ce = hipGraphInstantiate(out, gr, nullptr, nullptr, 0);
+  if (gr) (void)hipGraphDestroy(gr);
+  VXC(r);
+  HIPC(ce);
+  return VX_OK;
+}
+
+// The decode loop of every AR path.  Replays the step (graph gx, or enqueue(e->es) when gx is null) in chunks of `chunk`
+// launches, `bound` at most, and copies the n device states `st` into the host buffers poll[0] / poll[1] in turn behind each
+// chunk.  One chunk stays in flight while the copy behind the previous one is inspected: inspect(snapshot, launches at that poll)
+// returns POLL_MORE, POLL_STOP or an error code.  The poll that reaches the bound ends the loop whatever it returns; the chunk
+// still in flight at the end is waited for and inspected too.  *ms spans ev_t[2] (in front of the first replay) to ev_t[3]
+// (behind the last poll copy).
+enum { POLL_MORE = VX_OK, POLL_STOP = -1 };
+template <typename F, typename I>
+static int replay_polled(vx_engine* e, hipGraphExec_t gx, F enqueue, long long bound, int chunk, const ArState* st, int n,
+                         ArState* const poll[2], I inspect, long long* launched, float* ms) {
+  long long at[2] = {0, 0};
+  bool pending[2] = {false, false}, done = false;
+  auto look = [&](int k) -> int {
+    HIPC(hipEventSynchronize(e->ev_poll[k]));
+    pending[k] = false;
+    const int r = inspect(poll[k], at[k]);
+    if (r == POLL_STOP) done = true;
+    return r == POLL_STOP ? VX_OK : r;
+  };
+  *launched = 0;
+  HIPC(hipEventRecord(e->ev_t[2], e->es));
+  for (int k = 0; !done; k ^= 1) {
+    const long long m = (bound - *launched) < chunk ? (bound - *launched) : chunk;
+    for (long long i = 0; i < m; ++i) {
+      if (gx) HIPC(hipGraphLaunch(gx, e->es));
+      else VXC(enqueue(e->es));
+    }
+    *launched += m;
+    HIPC(hipMemcpyAsync(poll[k], st, (size_t)n * sizeof(ArState), hipMemcpyDeviceToHost, e->es));
+    HIPC(hipEventRecord(e->ev_poll[k], e->es));
+    pending[k] = true; at[k] = *launched;
+    if (pending[k ^ 1]) VXC(look(k ^ 1));
+    if (!done && *launched >= bound) { VXC(look(k)); done = true; }
+  }
+  HIPC(hipEventRecord(e->ev_t[3], e->es));
+  for (int k = 0; k < 2; ++k)
+    if (pending[k]) VXC(look(k));
+  HIPC(hipEventSynchronize(e->ev_t[3]));
+  HIPC(hipGetLastError());
+  HIPC(hipEventElapsedTime(ms, e->ev_t[2], e->ev_t[3]));
+  return VX_OK;
+}
+
 extern "C" int vx_ar_decode(vx_engine* e, const vx_decode_params* p, void* stream) {
   if (!e || !p) return fail(VX_ERR_ARG, "null argument");
   if (p->struct_size != (int32_t)sizeof(vx_decode_params)) return fail(VX_ERR_ARG, "vx_decode_params.struct_size mismatch");
   if (!e->prefilled || e->decoded) return fail(VX_ERR_STATE, "vx_ar_decode needs a fresh vx_ar_prefill");
-  if (!(p->temperature > 0.f)) return fail(VX_ERR_ARG, "temperature must be > 0");
+  long long bound = 0, room = 0;
+  bool cap_limited = false;
+  VXC(decode_bound(e, -1, *p, e->S, e->P, e->bos, &bound, &cap_limited, &room));
   const vx_config& c = e->cfg;
   ON_DEVICE(c.device);
-  // upper bound on appended tokens (valle.py:1047: stops once bos + n_gen > 16 S)
-  long long max_tok = 16LL * e->S + 1 - e->bos;
-  if (p->forced) max_tok = p->n_forced;
-  else if (p->max_new_tokens >= 0 && p->max_new_tokens < max_tok) max_tok = p->max_new_tokens;
-  // 16 S + 1 is the WORST case (valle.py:1047); a trained model stops at EOS long before it, so a long text must not be
-  // refused up front: the launch bound is clamped to the rows the cache has, and only a decode that really fills them while
-  // the stop rule has not fired is a capacity error
-  const long long room = (long long)c.max_audio - e->bos - e->P;  // >= 1 (checked at prefill)
-  bool cap_limited = false;
-  if (max_tok > room) {
-    if (p->forced) return fail(VX_ERR_CAPACITY, "need %lld audio rows, capacity %d", e->bos + e->P + max_tok, c.max_audio);
-    max_tok = room; cap_limited = true;
-  }
   VXC(sync_in(e, stream));
   if (p->exp_noise) {
     if (p->noise_rows <= 0) return fail(VX_ERR_ARG, "noise_rows must be > 0");
@@ -1688,51 +1759,16 @@ extern "C" int vx_ar_decode(vx_engine* e, const vx_decode_params* p, void* strea
   st.n_forced = p->forced ? p->n_forced : 0;
   HIPC(hipMemcpyAsync(e->d_st, &st, sizeof st, hipMemcpyHostToDevice, e->es));
 
-  const bool graph = !(c.flags & VX_FLAG_NO_GRAPH);
-  if (graph && !e->gexec) {
-    HIPC(hipStreamBeginCapture(e->es, hipStreamCaptureModeThreadLocal));
-    int r = enqueue_ar_step(e, e->es);
-    hipError_t ce = hipStreamEndCapture(e->es, &e->graph);
-    if (r != VX_OK) return r;
-    HIPC(ce);
-    HIPC(hipGraphInstantiate(&e->gexec, e->graph, nullptr, nullptr, 0));
-  }
-  HIPC(hipEventRecord(e->ev_t[2], e->es));
-  // step j samples from logits j and appends token j+1; the step that appends the last
-  // admissible token also raises the stop flag, so max_tok launches suffice (teacher forcing
-  // needs one more to close the sequence); EOS can only end it earlier.
-  long long bound = max_tok + (p->forced ? 1 : 0);
-  if (bound < 1) bound = 1;
+  auto step = [e](hipStream_t s) { return enqueue_ar_step(e, s); };
+  VXC(step_graph(e, &e->gexec, step));
+  auto stop_rule = [&](const ArState* hs, long long at) -> int {
+    if (hs->done) return POLL_STOP;
+    return at < bound ? POLL_MORE : fail(VX_ERR_STATE, "decode did not terminate within %lld steps", bound);
+  };
+  ArState* const poll[2] = {e->h_st + 1, e->h_st + 2};
   long long launched = 0;
-  int slot = 0;
-  bool done = false;
-  bool pending[2] = {false, false};
-  while (!done) {
-    const long long n = (bound - launched) < POLL_CHUNK ? (bound - launched) : POLL_CHUNK;
-    for (long long i = 0; i < n; ++i) {
-      if (graph) HIPC(hipGraphLaunch(e->gexec, e->es));
-      else VXC(enqueue_ar_step(e, e->es));
-    }
-    launched += n;
-    HIPC(hipMemcpyAsync(&e->h_st[1 + slot], e->d_st, sizeof(ArState), hipMemcpyDeviceToHost, e->es));
-    HIPC(hipEventRecord(e->ev_poll[slot], e->es));
-    pending[slot] = true;
-    const int other = slot ^ 1;
-    // keep one chunk in flight while the previous one is inspected
-    if (pending[other]) {
-      HIPC(hipEventSynchronize(e->ev_poll[other]));
-      pending[other] = false;
-      if (e->h_st[1 + other].done) done = true;
-    }
-    if (!done && launched >= bound) {
-      HIPC(hipEventSynchronize(e->ev_poll[slot]));
-      pending[slot] = false;
-      if (!e->h_st[1 + slot].done) return fail(VX_ERR_STATE, "decode did not terminate within %lld steps", bound);
-      done = true;
-    }
-    slot = other;
-  }
-  HIPC(hipEventRecord(e->ev_t[3], e->es));
+  float ms = 0.f;
+  VXC(replay_polled(e, e->gexec, step, bound, POLL_CHUNK, e->d_st, 1, poll, stop_rule, &launched, &ms));
   HIPC(hipMemcpyAsync(&e->h_st[1], e->d_st, sizeof(ArState), hipMemcpyDeviceToHost, e->es));
   unsigned* h_ep = reinterpret_cast<unsigned*>(e->h_st + 3);
   HIPC(hipMemcpyAsync(h_ep, e->d_epoch, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, e->es));
@@ -1744,8 +1780,6 @@ extern "C" int vx_ar_decode(vx_engine* e, const vx_decode_params* p, void* strea
     HIPC(hipStreamSynchronize(e->es));
     return fail(VX_ERR_STATE, "decode step: hand-over %u of the sharded decode step timed out (set VX_AR_TP=0)", code);
   }
-  float ms = 0.f;
-  HIPC(hipEventElapsedTime(&ms, e->ev_t[2], e->ev_t[3]));
   e->t_decode = ms;
   e->n_launch = (double)launched;
   e->n_gen = e->h_st[1].n_gen;
@@ -1759,6 +1793,16 @@ extern "C" int vx_ar_decode(vx_engine* e, const vx_decode_params* p, void* strea
   return VX_OK;
 }
 
+// n int32 tokens at `src` (device) into the caller's int64 buffer (nothing without one)
+static int read_tokens(const int* src, int n, int64_t* tokens, int32_t capacity) {
+  if (!tokens) return VX_OK;
+  if (capacity < n) return fail(VX_ERR_CAPACITY, "token buffer too small (%d < %d)", capacity, n);
+  std::vector<int> tmp(n);
+  if (n) HIPC(hipMemcpy(tmp.data(), src, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i) tokens[i] = tmp[i];
+  return VX_OK;
+}
+
 extern "C" int vx_ar_result(vx_engine* e, int64_t* tokens, int32_t capacity, int32_t* n_tokens, int32_t* stop_reason,
                             int32_t* n_pass) {
   if (!e) return fail(VX_ERR_ARG, "null engine");
@@ -1767,13 +1811,7 @@ extern "C" int vx_ar_result(vx_engine* e, int64_t* tokens, int32_t capacity, int
   if (n_tokens) *n_tokens = e->n_gen;
   if (stop_reason) *stop_reason = e->stop_reason;
   if (n_pass) *n_pass = e->n_pass;
-  if (tokens) {
-    if (capacity < e->n_gen) return fail(VX_ERR_CAPACITY, "token buffer too small (%d < %d)", capacity, e->n_gen);
-    std::vector<int> tmp(e->n_gen);
-    if (e->n_gen) HIPC(hipMemcpy(tmp.data(), e->d_tokens, (size_t)e->n_gen * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < e->n_gen; ++i) tokens[i] = tmp[i];
-  }
-  return VX_OK;
+  return read_tokens(e->d_tokens, e->n_gen, tokens, capacity);
 }
 
 // ------------------------------------------------------------------------------ batched AR decode
@@ -1889,25 +1927,6 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
   return VX_OK;
 }
 
-// The checks of one slot's decode parameters (no HIP call): its step bound (the steps after which the stop rule must have fired)
-// and whether that bound was clamped to the KV capacity.  S / P / bos are the slot's prefill geometry.
-static int batch_params_check(vx_engine* e, int slot, const vx_decode_params& p, int S, int P, int bos, long long* steps,
-                              bool* cap_limited, long long* room_out) {
-  if (p.struct_size != (int32_t)sizeof(vx_decode_params)) return fail(VX_ERR_ARG, "vx_decode_params.struct_size mismatch");
-  if (!(p.temperature > 0.f)) return fail(VX_ERR_ARG, "temperature must be > 0");
-  long long max_tok = 16LL * S + 1 - bos;
-  if (p.forced) max_tok = p.n_forced;
-  else if (p.max_new_tokens >= 0 && p.max_new_tokens < max_tok) max_tok = p.max_new_tokens;
-  const long long room = (long long)e->cfg.max_audio - bos - P;  // as in vx_ar_decode: clamp, fail only if it fills
-  *cap_limited = false;
-  if (max_tok > room) {
-    if (p.forced) return fail(VX_ERR_CAPACITY, "slot %d needs %lld audio rows, capacity %d", slot, bos + P + max_tok, e->cfg.max_audio);
-    max_tok = room; *cap_limited = true;
-  }
-  *steps = max_tok + (p.forced ? 1 : 0);
-  *room_out = room;
-  return VX_OK;
-}
 // Decode parameters into the slot's staging state (its prefill fields are already there).
 static void batch_params_stage(vx_engine* e, int slot, const vx_decode_params& p, bool cap_limited, long long room) {
   ArState& st = e->h_bst[slot];
@@ -1916,23 +1935,45 @@ static void batch_params_stage(vx_engine* e, int slot, const vx_decode_params& p
   st.forced = p.forced ? (p.n_forced > 0 ? (const long long*)p.forced : (const long long*)e->btok) : nullptr;
   st.n_forced = p.forced ? p.n_forced : 0;
 }
-// The executable graph of the B-slot step (captured on first use, one per B); nullptr with VX_FLAG_NO_GRAPH.
-static int batch_graph(vx_engine* e, int B, hipGraphExec_t* out) {
-  *out = nullptr;
-  if (e->cfg.flags & VX_FLAG_NO_GRAPH) return VX_OK;
-  auto it = e->bgraphs.find(B);
-  if (it != e->bgraphs.end()) { *out = it->second; return VX_OK; }
-  hipGraph_t gr = nullptr;
-  hipGraphExec_t gx = nullptr;
-  HIPC(hipStreamBeginCapture(e->es, hipStreamCaptureModeThreadLocal));
-  int r = enqueue_batch_step(e, B, e->es);
-  hipError_t ce = hipStreamEndCapture(e->es, &gr);
-  if (r != VX_OK) return r;
-  HIPC(ce);
-  HIPC(hipGraphInstantiate(&gx, gr, nullptr, nullptr, 0));
-  (void)hipGraphDestroy(gr);
-  e->bgraphs[B] = gx;
-  *out = gx;
+
+// Replays the B-slot step until min_stopped live slots (all of them, if fewer are live) have stopped and lists those in
+// stopped[0 .. *n_stopped).  Slot b < B is vacant, live or stopped by bslot[b]; a live slot may take bleft[b] more steps.  A
+// stopped slot keeps the n_gen / stop_reason of the poll that first saw it done: the sampler skips a done slot, so they are final.
+static int run_slots(vx_engine* e, int B, int min_stopped, int chunk, int32_t* stopped, int32_t* n_stopped) {
+  *n_stopped = 0;
+  long long bound = 0;  // steps until every live slot has exhausted its bound
+  int live = 0;
+  for (int b = 0; b < B; ++b)
+    if (e->bslot[b] == SLOT_LIVE) { ++live; if (e->bleft[b] > bound) bound = e->bleft[b]; }
+  if (live == 0) return VX_OK;
+  auto step = [e, B](hipStream_t s) { return enqueue_batch_step(e, B, s); };
+  hipGraphExec_t& gx = e->bgraphs[B];
+  VXC(step_graph(e, &gx, step));
+  int found = 0;
+  // every live slot that has stopped is reported; a live slot past its bound that has not is an error
+  auto take = [&](const ArState* hs, long long at) -> int {
+    for (int b = 0; b < B; ++b) {
+      if (e->bslot[b] != SLOT_LIVE) continue;
+      if (hs[b].done) {
+        e->bslot[b] = SLOT_STOPPED;
+        e->bngen[b] = hs[b].n_gen; e->breason[b] = hs[b].stop_reason;
+        stopped[found++] = b;
+        --live;
+      } else if (at >= e->bleft[b]) {
+        return fail(VX_ERR_STATE, "batched decode of slot %d did not terminate within %lld steps", b, e->bleft[b]);
+      }
+    }
+    return found >= min_stopped || live == 0 ? POLL_STOP : POLL_MORE;
+  };
+  ArState* const poll[2] = {e->h_bst + BMAX, e->h_bst + 2 * BMAX};
+  long long launched = 0;
+  float ms = 0.f;
+  VXC(replay_polled(e, gx, step, bound, chunk, e->bst, B, poll, take, &launched, &ms));
+  e->t_bdecode = ms;
+  e->n_blaunch = (double)launched;
+  for (int b = 0; b < B; ++b)
+    if (e->bslot[b] == SLOT_LIVE) e->bleft[b] -= launched;
+  *n_stopped = found;
   return VX_OK;
 }
 
@@ -1942,72 +1983,24 @@ extern "C" int vx_batch_decode(vx_engine* e, int32_t B, const vx_decode_params* 
   const vx_config& c = e->cfg;
   ON_DEVICE(c.device);
   e->bsess = false;  // the static calls end a continuous-batching session
-  long long bound = 1;
-  bool cap_limited[BMAX] = {};
   for (int b = 0; b < B; ++b) {
     const vx_decode_params& p = params[b];
     if (p.struct_size != (int32_t)sizeof(vx_decode_params)) return fail(VX_ERR_ARG, "vx_decode_params.struct_size mismatch");
     if (!e->bprefilled[b]) return fail(VX_ERR_STATE, "slot %d needs a fresh vx_batch_prefill", b);
-    long long steps = 0, room = 0;
-    VXC(batch_params_check(e, b, p, e->bS[b], e->bP[b], e->bbos[b], &steps, &cap_limited[b], &room));
-    if (steps > bound) bound = steps;
-    batch_params_stage(e, b, p, cap_limited[b], room);
+    long long room = 0;
+    VXC(decode_bound(e, b, p, e->bS[b], e->bP[b], e->bbos[b], &e->bleft[b], &e->bcap[b], &room));
+    batch_params_stage(e, b, p, e->bcap[b], room);
     if (p.exp_noise && p.noise_rows <= 0) return fail(VX_ERR_ARG, "noise_rows must be > 0");
   }
+  for (int b = 0; b < e->bmax; ++b) e->bslot[b] = b < B ? SLOT_LIVE : SLOT_VACANT;
   VXC(sync_in(e, stream));
   HIPC(hipMemcpyAsync(e->bst, e->h_bst, (size_t)B * sizeof(ArState), hipMemcpyHostToDevice, e->es));
-  const bool graph = !(c.flags & VX_FLAG_NO_GRAPH);
-  hipGraphExec_t gx = nullptr;
-  VXC(batch_graph(e, B, &gx));
-  HIPC(hipEventRecord(e->ev_t[2], e->es));
-  long long launched = 0;
-  int slot = 0;
-  bool done = false, pending[2] = {false, false};
-  auto all_done = [&](int sl) {
-    const ArState* hs = e->h_bst + (size_t)(1 + sl) * BMAX;
-    for (int b = 0; b < B; ++b) if (!hs[b].done) return false;
-    return true;
-  };
-  while (!done) {
-    const long long n = (bound - launched) < POLL_CHUNK ? (bound - launched) : POLL_CHUNK;
-    for (long long i = 0; i < n; ++i) {
-      if (graph) HIPC(hipGraphLaunch(gx, e->es));
-      else VXC(enqueue_batch_step(e, B, e->es));
-    }
-    launched += n;
-    HIPC(hipMemcpyAsync(e->h_bst + (size_t)(1 + slot) * BMAX, e->bst, (size_t)B * sizeof(ArState), hipMemcpyDeviceToHost, e->es));
-    HIPC(hipEventRecord(e->ev_poll[slot], e->es));
-    pending[slot] = true;
-    const int other = slot ^ 1;
-    if (pending[other]) {
-      HIPC(hipEventSynchronize(e->ev_poll[other]));
-      pending[other] = false;
-      if (all_done(other)) done = true;
-    }
-    if (!done && launched >= bound) {
-      HIPC(hipEventSynchronize(e->ev_poll[slot]));
-      pending[slot] = false;
-      if (!all_done(slot)) return fail(VX_ERR_STATE, "batched decode did not terminate within %lld steps", bound);
-      done = true;
-    }
-    slot = other;
-  }
-  HIPC(hipEventRecord(e->ev_t[3], e->es));
-  HIPC(hipMemcpyAsync(e->h_bst + BMAX, e->bst, (size_t)B * sizeof(ArState), hipMemcpyDeviceToHost, e->es));
-  HIPC(hipStreamSynchronize(e->es));
-  HIPC(hipGetLastError());
-  float ms = 0.f;
-  HIPC(hipEventElapsedTime(&ms, e->ev_t[2], e->ev_t[3]));
-  e->t_bdecode = ms;
-  e->n_blaunch = (double)launched;
-  for (int b = 0; b < B; ++b) {
-    e->bngen[b] = e->h_bst[BMAX + b].n_gen;
-    e->breason[b] = e->h_bst[BMAX + b].stop_reason;
-    e->bprefilled[b] = false;
-  }
+  int32_t stopped[BMAX], n_stopped = 0;
+  VXC(run_slots(e, B, B, POLL_CHUNK, stopped, &n_stopped));
+  for (int b = 0; b < B; ++b) e->bprefilled[b] = false;
   VXC(sync_out(e, stream));
   for (int b = 0; b < B; ++b)
-    if (cap_limited[b] && e->breason[b] == VX_STOP_MAX_NEW)
+    if (e->bcap[b] && e->breason[b] == VX_STOP_MAX_NEW)
       return fail(VX_ERR_CAPACITY, "capacity exceeded in slot %d: the KV cache filled (max_audio = %d rows) before the stop rule fired; raise max_audio", b, c.max_audio);
   return VX_OK;
 }
@@ -2021,12 +2014,7 @@ extern "C" int vx_batch_result(vx_engine* e, int32_t slot, int64_t* tokens, int3
   const int n = e->bngen[slot];
   if (n_tokens) *n_tokens = n;
   if (stop_reason) *stop_reason = e->breason[slot];
-  if (tokens) {
-    if (capacity < n) return fail(VX_ERR_CAPACITY, "token buffer too small (%d < %d)", capacity, n);
-    std::vector<int> tmp(n);
-    if (n) HIPC(hipMemcpy(tmp.data(), e->btok + (size_t)slot * e->btok_stride, (size_t)n * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) tokens[i] = tmp[i];
-  }
+  VXC(read_tokens(e->btok + (size_t)slot * e->btok_stride, n, tokens, capacity));
   if (e->bsess && e->bslot[slot] == SLOT_STOPPED) e->bslot[slot] = SLOT_VACANT;  // read: the slot may be admitted into again
   return VX_OK;
 }
@@ -2043,9 +2031,8 @@ extern "C" int vx_batch_open(vx_engine* e, void* stream) {
   ON_DEVICE(e->cfg.device);
   VXC(sync_in(e, stream));
   for (int b = 0; b < e->bmax; ++b) {
-    ArState& st = e->h_bst[b];
-    memset(&st, 0, sizeof st);
-    st.done = 1; st.row = 0; st.temperature = 1.0f; st.max_new = -1;
+    seed_state(e->h_bst[b], 0, 0, 0, 0, 0, false);
+    e->h_bst[b].done = 1;
   }
   HIPC(hipMemcpyAsync(e->bst, e->h_bst, (size_t)e->bmax * sizeof(ArState), hipMemcpyHostToDevice, e->es));
   // a vacant slot's rows still go through the step's GEMMs and LayerNorms: they must hold finite values
@@ -2085,12 +2072,9 @@ extern "C" int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, con
   long long steps[BMAX] = {}, room[BMAX] = {};
   bool capl[BMAX] = {};
   for (int z = 0; z < n; ++z) {
-    if (!text[z] || (!prompt_cb0[z] && P[z] > 0)) return fail(VX_ERR_ARG, "null argument (utterance %d)", z);
-    if (S[z] <= 0 || P[z] < 0) return fail(VX_ERR_ARG, "S must be > 0 (valle.py:991), P >= 0");
-    if (S[z] > c.max_text || bos + P[z] + 1 > c.max_audio) return fail(VX_ERR_CAPACITY, "S=%d / P=%d exceed capacity", S[z], P[z]);
-    if (bos + P[z] == 0) return fail(VX_ERR_ARG, "empty audio prefix needs prepend_bos");
+    VXC(check_utterance(e, text[z], S[z], prompt_cb0[z], P[z], z));
     const vx_decode_params& p = params[z];
-    VXC(batch_params_check(e, slots[z], p, S[z], P[z], bos, &steps[z], &capl[z], &room[z]));
+    VXC(decode_bound(e, slots[z], p, S[z], P[z], bos, &steps[z], &capl[z], &room[z]));
     if (p.exp_noise && p.noise_rows <= 0) return fail(VX_ERR_ARG, "noise_rows must be > 0");
   }
   ON_DEVICE(c.device);
@@ -2105,7 +2089,7 @@ extern "C" int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, con
     const int sl = slots[z];
     batch_params_stage(e, sl, params[z], capl[z], room[z]);
     HIPC(hipMemcpyAsync(e->bst + sl, &e->h_bst[sl], sizeof(ArState), hipMemcpyHostToDevice, e->es));
-    e->bslot[sl] = SLOT_LIVE; e->bleft[sl] = steps[z] < 1 ? 1 : steps[z]; e->bcap[sl] = capl[z];
+    e->bslot[sl] = SLOT_LIVE; e->bleft[sl] = steps[z]; e->bcap[sl] = capl[z];
     e->bprefilled[sl] = false;
   }
   VXC(sync_out(e, stream));
@@ -2118,77 +2102,11 @@ extern "C" int vx_batch_run(vx_engine* e, int32_t min_stopped, int32_t poll_step
   if (!e->bsess) return fail(VX_ERR_STATE, "vx_batch_run needs an open session (vx_batch_open)");
   if (!stopped || !n_stopped) return fail(VX_ERR_ARG, "null argument");
   *n_stopped = 0;
-  const int B = e->bmax;
-  if (poll_steps <= 0) poll_steps = BATCH_POLL_DEFAULT;
-  if (min_stopped < 1) min_stopped = 1;
-  long long bound = 0;  // steps until every live slot has exhausted its bound
-  int live = 0;
-  for (int b = 0; b < B; ++b)
-    if (e->bslot[b] == SLOT_LIVE) { ++live; if (e->bleft[b] > bound) bound = e->bleft[b]; }
-  if (live == 0) return VX_OK;
   ON_DEVICE(e->cfg.device);
   VXC(sync_in(e, stream));
-  hipGraphExec_t gx = nullptr;
-  VXC(batch_graph(e, B, &gx));
-  HIPC(hipEventRecord(e->ev_t[2], e->es));
-  long long launched = 0, at_poll[2] = {0, 0};
-  int ps = 0, found = 0;
-  bool done = false, pending[2] = {false, false};
-  // a polled state: every live slot that has stopped is reported; a live slot past its bound that has not is an error
-  auto take = [&](int sl) -> int {
-    const ArState* hs = e->h_bst + (size_t)(1 + sl) * BMAX;
-    for (int b = 0; b < B; ++b) {
-      if (e->bslot[b] != SLOT_LIVE) continue;
-      if (hs[b].done) {
-        e->bslot[b] = SLOT_STOPPED;
-        e->bngen[b] = hs[b].n_gen; e->breason[b] = hs[b].stop_reason;
-        stopped[found++] = b;
-        --live;
-      } else if (at_poll[sl] >= e->bleft[b]) {
-        return fail(VX_ERR_STATE, "batched decode of slot %d did not terminate within %lld steps", b, e->bleft[b]);
-      }
-    }
-    return VX_OK;
-  };
-  while (!done) {
-    const long long n = (bound - launched) < poll_steps ? (bound - launched) : poll_steps;
-    for (long long i = 0; i < n; ++i) {
-      if (gx) HIPC(hipGraphLaunch(gx, e->es));
-      else VXC(enqueue_batch_step(e, B, e->es));
-    }
-    launched += n;
-    HIPC(hipMemcpyAsync(e->h_bst + (size_t)(1 + ps) * BMAX, e->bst, (size_t)B * sizeof(ArState), hipMemcpyDeviceToHost, e->es));
-    HIPC(hipEventRecord(e->ev_poll[ps], e->es));
-    pending[ps] = true; at_poll[ps] = launched;
-    const int other = ps ^ 1;
-    if (pending[other]) {  // keep one chunk in flight while the previous one is inspected
-      HIPC(hipEventSynchronize(e->ev_poll[other]));
-      pending[other] = false;
-      VXC(take(other));
-      if (found >= min_stopped || live == 0) done = true;
-    }
-    if (!done && launched >= bound) {
-      HIPC(hipEventSynchronize(e->ev_poll[ps]));
-      pending[ps] = false;
-      VXC(take(ps));
-      done = true;  // every live slot was past its bound: all of them have stopped (or take() failed)
-    }
-    ps = other;
-  }
-  for (int sl = 0; sl < 2; ++sl)  // the chunk still in flight: wait for it and report what stopped in it too
-    if (pending[sl]) { HIPC(hipEventSynchronize(e->ev_poll[sl])); pending[sl] = false; VXC(take(sl)); }
-  HIPC(hipEventRecord(e->ev_t[3], e->es));
-  HIPC(hipStreamSynchronize(e->es));
-  HIPC(hipGetLastError());
-  float ms = 0.f;
-  HIPC(hipEventElapsedTime(&ms, e->ev_t[2], e->ev_t[3]));
-  e->t_bdecode = ms;
-  e->n_blaunch = (double)launched;
-  for (int b = 0; b < B; ++b)
-    if (e->bslot[b] == SLOT_LIVE) e->bleft[b] -= launched;
-  *n_stopped = found;
+  VXC(run_slots(e, e->bmax, min_stopped < 1 ? 1 : min_stopped, poll_steps > 0 ? poll_steps : BATCH_POLL_DEFAULT, stopped, n_stopped));
   VXC(sync_out(e, stream));
-  for (int i = 0; i < found; ++i) {
+  for (int i = 0; i < *n_stopped; ++i) {
     const int b = stopped[i];
     if (e->bcap[b] && e->breason[b] == VX_STOP_MAX_NEW)
       return fail(VX_ERR_CAPACITY, "capacity exceeded in slot %d: the KV cache filled (max_audio = %d rows) before the stop rule fired; raise max_audio", b, e->cfg.max_audio);

@@ -439,7 +439,7 @@ __global__ __launch_bounds__(256) void kv_scatter_kernel(const T* __restrict__ q
 }
 
 // Batched prefill: row j of segment z (rows seg_start[z] + j of the concatenated buffer) -> position j of slot
-// seg_slot[z]'s cache (seg_slot == nullptr: slot z).  grid = (max segment length, segments).
+// seg_slot[z]'s cache.  grid = (max segment length, segments).
 template <typename T>
 __global__ __launch_bounds__(256) void kv_scatter_seg_kernel(const T* __restrict__ qkv, T* __restrict__ kv_layer,
                                                              size_t slot_stride, size_t v_offset,
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(256) void kv_scatter_seg_kernel(const T* __restrict
   const int j = blockIdx.x, z = blockIdx.y;
   if (j >= seg_len[z]) return;
   const size_t r = (size_t)seg_start[z] + j;
-  T* kc = kv_layer + (size_t)(seg_slot != nullptr ? seg_slot[z] : z) * slot_stride;
+  T* kc = kv_layer + (size_t)seg_slot[z] * slot_stride;
   T* vc = kc + v_offset;
   for (int i = threadIdx.x; i < d; i += 256) {
     const int h = i / hd, c = i - h * hd;

@@ -136,25 +136,11 @@ class VALLE:
                   max_new_tokens: int = -1) -> torch.Tensor:
         """Same contract as the reference (valle.py:961-985): x (1,S) int64, x_lens (1,), y (1,P,8) int64 →
         (1,T,num_quantizers) int64 on the model's device.  ``exp_noise`` / ``max_new_tokens`` are extras."""
-        assert x.ndim == 2, x.shape  # valle.py:986-991
-        assert x_lens.ndim == 1, x_lens.shape
-        assert y.ndim == 3, y.shape
-        assert y.shape[0] == 1, y.shape
-        assert torch.all(x_lens > 0)
-        S = int(x_lens.max())
-        if x.shape[1] != S or x.shape[0] != 1:
-            # the reference builds its mask from x_lens.max() but concatenates all of x: any padding makes
-            # its attention shapes disagree (valle.py:1009-1038)
-            raise RuntimeError(f"x must be one unpadded sequence: x {tuple(x.shape)} vs x_lens.max() {S}")
+        u = (x, x_lens, y, enroll_x_lens)
+        self._check_utterance(u)
         eng = self.engine()
-        Q, bos = self.num_quantizers, int(self.ar_audio_prepend_bos)
-        if _ids_out_of_range(x, y[..., :Q]):
-            raise IndexError("index out of range in self")  # what nn.Embedding raises in the reference
-        text = x[0]
-        prompts = y[0, :, :Q].contiguous()
-        P = prompts.shape[0]
-
-        eng.ar_prefill(text, prompts[:, 0].contiguous())
+        S, P, bos = x.shape[1], y.shape[1], int(self.ar_audio_prepend_bos)
+        eng.ar_prefill(x[0], y[0, :, 0].contiguous())
         n_max = max(1, 16 * S + 2 - bos)
         rng_state = None
         seed = 0
@@ -171,22 +157,12 @@ class VALLE:
             torch.set_rng_state(rng_state)
             for _ in range(tokens.numel() + 1):
                 torch.empty(1, NUM_AUDIO_TOKENS + 1).exponential_(1)
-        if tokens.numel() == 0 and max_new_tokens != 0:
-            if not bos:
-                raise SyntaxError("well trained model shouldn't reach here.")  # valle.py:1049-1052
+        r = self._ar_finished(u, tokens, max_new_tokens)
         if self.print_eos:
             print(f"{self.MODEL_NAME} EOS [{P} -> {P + bos + tokens.numel()}]")  # valle.py:1054 / 646
-        if Q == 1 or tokens.numel() == 0:
-            codes = torch.zeros((tokens.numel(), Q), dtype=torch.int64)
-            codes[:, 0] = tokens
-            return codes.unsqueeze(0).to(self.device)
-
-        text_nar = text
-        if self.prefix_mode in [2, 4]:  # valle.py:1068-1079
-            enrolled_len = int(enroll_x_lens.max().item())
-            text_nar = torch.concat([text[:1], text[enrolled_len - 1:]])
-        codes = eng.nar(text_nar, prompts, tokens, out_device=self.device)
-        return codes.unsqueeze(0)
+        if isinstance(r, torch.Tensor):
+            return r
+        return eng.nar(*r, out_device=self.device).unsqueeze(0)
 
 
     @torch.no_grad()
@@ -202,7 +178,7 @@ class VALLE:
             group = utterances[g0 : g0 + eng.max_batch]
             for b, u in enumerate(group):
                 x, y = u[0], u[2]
-                self._check_batch_utterance(u)
+                self._check_utterance(u)
                 if not (batched_prefill and eng.mfma_rows):
                     eng.batch_prefill(b, x[0], y[0, :, 0].contiguous())
             if batched_prefill and eng.mfma_rows:  # one pass over the concatenated rows of the whole group
@@ -221,28 +197,33 @@ class VALLE:
                 out[i] = r
         return out
 
-    # ---- shared by inference_batch and inference_stream ----------------------------------------------
+    # ---- shared by inference, inference_batch and inference_stream ------------------------------------
     def _batch_engine(self, what: str):
         eng = self.engine()
         if eng.max_batch < 2:
             raise RuntimeError(f"construct the model with max_batch >= 2 for {what}")
         return eng
 
-    def _check_batch_utterance(self, u):
+    def _check_utterance(self, u):
+        """The reference's checks of one (x, x_lens, y[, enroll_x_lens]) (valle.py:986-991)."""
         x, x_lens, y = u[0], u[1], u[2]
         assert x.ndim == 2 and x_lens.ndim == 1 and y.ndim == 3 and y.shape[0] == 1 and torch.all(x_lens > 0)
-        if x.shape[1] != int(x_lens.max()) or x.shape[0] != 1:
-            raise RuntimeError("x must be one unpadded sequence per utterance")
+        S = int(x_lens.max())
+        if x.shape[1] != S or x.shape[0] != 1:
+            # the reference builds its mask from x_lens.max() but concatenates all of x: any padding makes
+            # its attention shapes disagree (valle.py:1009-1038)
+            raise RuntimeError(f"x must be one unpadded sequence: x {tuple(x.shape)} vs x_lens.max() {S}")
         if _ids_out_of_range(x, y[..., :self.num_quantizers]):
-            raise IndexError("index out of range in self")
+            raise IndexError("index out of range in self")  # what nn.Embedding raises in the reference
 
-    def _ar_finished(self, u, tokens):
+    def _ar_finished(self, u, tokens, max_new_tokens: int = -1):
         """An utterance's AR tokens -> its final (1, T, Q) codes when no NAR stage runs (Q == 1, empty output), else the
-        (text_nar, prompts, tokens) of its NAR stages (prefix-mode 2/4 trim as in inference, valle.py:1068-1079)."""
+        (text_nar, prompts, tokens) of its NAR stages (prefix-mode 2/4 trim, valle.py:1068-1079).  An empty output without
+        a BOS row is the reference's SyntaxError (valle.py:1049-1052), unless max_new_tokens == 0 asked for it."""
         Q, bos = self.num_quantizers, int(self.ar_audio_prepend_bos)
         x, y = u[0], u[2]
         enroll = u[3] if len(u) > 3 else None
-        if tokens.numel() == 0 and not bos:
+        if tokens.numel() == 0 and not bos and max_new_tokens != 0:
             raise SyntaxError("well trained model shouldn't reach here.")
         if Q == 1 or tokens.numel() == 0:
             codes = torch.zeros((tokens.numel(), Q), dtype=torch.int64)
@@ -274,7 +255,7 @@ class VALLE:
         eng = self._batch_engine("inference_stream")
         utterances = list(utterances)
         for u in utterances:
-            self._check_batch_utterance(u)
+            self._check_utterance(u)
         N, B = len(utterances), eng.max_batch
         if seeds is None:
             seeds = [int(torch.randint(0, 2**62, (1,))) for _ in utterances]
