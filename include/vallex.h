@@ -65,11 +65,16 @@ enum vx_flags {
                                prenets in front of the position embeddings, fp32; batch-1 path only */
   VX_FLAG_POST_NORM = 8,    /* norm_first=False (valle.py:60, transformer.py:303-308): x = norm(x + block(x)), no final
                                encoder norms; batch-1 path only (max_batch must be <= 1) */
-  VX_FLAG_VALLF = 32        /* the cross-attention variant VALLF (valle.py:49-719, --model-name VALL-F): both stacks are
+  VX_FLAG_VALLF = 32,       /* the cross-attention variant VALLF (valle.py:49-719, --model-name VALL-F): both stacks are
                                TransformerDecoderLayers (modules/transformer.py:409-601) - causal / unmasked self-attention over
                                the AUDIO rows only, cross-attention over the embedded text, three norms per layer.  Same entry
                                points (VALLF.inference, valle.py:566-710, has VALLE.inference's signature); the state_dict gains
                                layers.N.multihead_attn.* and layers.N.norm3.*.  Batch-1 path only */
+  VX_FLAG_KV_FP8 = 64       /* the slot caches of the batched decode (vx_batch_*) hold OCP e4m3 codes with one E8M0 scale per
+                               16 channels of a K / V row instead of bf16 values: 0.53x the bytes the batched
+                               step's attention reads.  Needs max_batch >= 2, VX_PREC_BF16 or VX_PREC_FP8_NAR, head_dim 64 and a
+                               pre-norm VALL-E without prenets (else VX_ERR_UNSUPPORTED, before any HIP call).  The batch-1 cache
+                               (vx_ar_*) stays bf16 */
 };
 
 /* Mirrors VALLE.__init__ (valle.py:727-760) / get_model (models/__init__.py:112-124). */
@@ -220,7 +225,9 @@ int vx_get_timings(vx_engine* e, double* out, int32_t n);
  * "ar_x" (d fp32 residual stream of the last AR row), "nar_x" (N x d fp32 after the last stage),
  * "batch_logits" (64 x 1088 fp32: newest logits row of every slot), "batch_argmax" / "batch_sampled"
  * (64 x (max_audio+2) int32 per pass), "batch_trace" (max_batch x (max_audio+2) x 1025 fp32: every pass's logits row of every
- * slot, engines created with VX_FLAG_TRACE_LOGITS and max_batch > 1). */
+ * slot, engines created with VX_FLAG_TRACE_LOGITS and max_batch > 1), "batch_kv" (the slot caches, max_batch > 1:
+ * [slot][layer][K|V][head][max_text+max_audio][64] bf16, or e4m3 bytes with VX_FLAG_KV_FP8), "batch_kv_scale" (VX_FLAG_KV_FP8: the
+ * E8M0 scale bytes, [slot][layer][K|V][head][max_text+max_audio][4]). */
 int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t offset_bytes, int64_t nbytes);
 
 /* Kernel-level entry points (device pointers, fp32 unless noted) used by tests/ to check each

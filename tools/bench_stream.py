@@ -1,13 +1,17 @@
 """Continuous vs static batching at BASELINE configs[2] geometry (d=1024 nhead=16 L=12, 32 slots, bf16), one JSON line on stdout.
 
     python tools/bench_stream.py [--n 128] [--slots 32] [--poll 4,8,16,32] [--refill 1,2,4,8]
+    python tools/bench_stream.py --kv-cache bf16,fp8 [--slots 64 --text-len 94] [--reps 2]
     python tools/bench_stream.py --ab-half-done [--lib path/to/libvallex.so]
 
 Default mode: a seeded queue of --n utterances, S uniform in [10, 94], P = 225 (synthetic weights: every utterance stops by the
 length rule, T = 16 S + 1 frames), decoded end to end (AR + 7 NAR stages) once through inference_batch, group by group, and once
 per (poll_steps, refill_at) setting through inference_stream.  Reported per run: codec-tokens/s (frames of all utterances over the
 wall time of the whole queue), slot occupancy (live slot-steps / launched slot-steps) and the mean / p95 latency of an utterance
-from queue start to its codes.
+from queue start to its codes, the device time per batched step (step_us) and the bytes of the model's slot KV caches.
+
+--kv-cache: the slot-cache formats to run (comma-separated: bf16, fp8).  With both, each format gets its own model on the same
+queue and the runs alternate between them rep by rep (static, then stream, per format).
 
 --ab-half-done: device time per batched step with all 32 slots live, and with half of them done (teacher-forced lengths 753 and
 1), through vx_batch_decode, so that the same measurement runs on a library without the continuous-batching entry points."""
@@ -21,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def model(args, max_audio):
+def model(args, max_audio, kv_cache="bf16"):
     if args.lib:  # a library built from another revision: bind only the entry points it exports (the static batched path)
         import ctypes as C
 
@@ -40,29 +44,32 @@ def model(args, max_audio):
     from valle_amd.weights import synthetic_state_dict
 
     cfg = ModelConfig(decoder_dim=1024, nhead=16, num_decoder_layers=12, prefix_mode=1)
-    m = VALLE(1024, 16, 12, prefix_mode=1, precision="bf16", max_text=128, max_audio=max_audio, print_eos=False, max_batch=args.slots)
+    m = VALLE(1024, 16, 12, prefix_mode=1, precision=args.precision, max_text=128, max_audio=max_audio, print_eos=False,
+              max_batch=args.slots, **({"kv_cache": kv_cache} if kv_cache != "bf16" else {}))
     m.load_state_dict(synthetic_state_dict(cfg, 0))
     return m.to("cuda:0").eval()
 
 
-def queue(n, seed):
+def queue(n, seed, text_len=None):
     import torch
     from valle_amd.weights import synthetic_inputs
 
     g = torch.Generator().manual_seed(seed)
-    S = torch.randint(10, 95, (n,), generator=g).tolist()
+    S = [text_len] * n if text_len else torch.randint(10, 95, (n,), generator=g).tolist()
     return [synthetic_inputs(s, 225, 8, seed=1000 + i) for i, s in enumerate(S)], S
 
 
 def count_steps(eng):
-    """Counts the batched steps the engine launches (vx_batch_decode / vx_batch_run) from its timings."""
-    box = [0]
+    """Counts the batched steps the engine launches (vx_batch_decode / vx_batch_run) and their device ms, from its timings."""
+    box = [0, 0.0]
     for name in ("batch_decode", "batch_run"):
         orig = getattr(eng, name)
 
         def wrap(*a, _orig=orig, **k):
             r = _orig(*a, **k)
-            box[0] += eng.timings()["batch_launches"]
+            t = eng.timings()
+            box[0] += t["batch_launches"]
+            box[1] += t["batch_decode_ms"]
             return r
 
         setattr(eng, name, wrap)
@@ -79,28 +86,44 @@ def summary(kind, t0, done_at, frames, steps, slots, **extra):
                 latency_mean_s=round(float(lat.mean()), 3), latency_p95_s=round(float(np.percentile(lat, 95)), 3), **extra)
 
 
+def slot_cache_bytes(eng):
+    """bytes of an engine's slot KV caches: max_batch x L x (K, V) x heads x (max_text + max_audio) rows x 64 channels, 2 bytes a
+    value in bf16, 1 byte + 1/16 scale byte in fp8"""
+    c = eng.cfg
+    vals = eng.max_batch * c.num_decoder_layers * 2 * c.decoder_dim * (eng.max_text + eng.max_audio)
+    return vals * 2 if eng.kv_cache == "bf16" else vals + vals // 16
+
+
 def run_queue(args):
     import torch
 
-    m = model(args, 1792)
-    eng = m.engine()
-    steps = count_steps(eng)
-    utts, S = queue(args.n, args.seed)
+    kvs = args.kv_cache.split(",")
+    utts, S = queue(args.n, args.seed, args.text_len)
     frames = [16 * s + 1 for s in S]
     seeds = list(range(1, args.n + 1))
     B = args.slots
     polls = [int(v) for v in args.poll.split(",")]
     refills = [int(v) for v in args.refill.split(",")]
-    # warm-up: every shape class the timed runs use (graph capture, row buffers, NAR at the group's row count)
-    w, _ = queue(B, args.seed + 1)
-    m.inference_batch(w, top_k=10, seeds=list(range(B)))
-    for _ in m.inference_stream(w, top_k=10, seeds=list(range(B))):
-        pass
-    torch.cuda.synchronize()
+    models = {}
+    for kv in kvs:
+        m = model(args, 1792, kv)
+        eng = m.engine()
+        models[kv] = (m, count_steps(eng), slot_cache_bytes(eng))
+        # warm-up: every shape class the timed runs use (graph capture, row buffers, NAR at the group's row count)
+        w, _ = queue(B, args.seed + 1, args.text_len)
+        m.inference_batch(w, top_k=10, seeds=list(range(B)))
+        for _ in m.inference_stream(w, top_k=10, seeds=list(range(B))):
+            pass
+        torch.cuda.synchronize()
     runs = []
 
-    def static():
-        steps[0] = 0
+    def extra(kv):
+        steps = models[kv][1]
+        return dict(kv_cache=kv, slot_cache_bytes=models[kv][2], step_us=round(1e3 * steps[1] / max(steps[0], 1), 2))
+
+    def static(kv):
+        m, steps, _ = models[kv]
+        steps[0], steps[1] = 0, 0.0
         done_at = {}
         t0 = time.perf_counter()
         for g0 in range(0, args.n, B):  # inference_batch's own grouping, timed group by group
@@ -109,34 +132,41 @@ def run_queue(args):
             now = time.perf_counter()
             for i in range(len(out)):
                 done_at[g0 + i] = now
-        return summary("static", t0, done_at, frames, steps[0], B)
+        return summary("static", t0, done_at, frames, steps[0], B, **extra(kv))
 
-    def stream(poll, refill):
-        steps[0] = 0
+    def stream(kv, poll, refill):
+        m, steps, _ = models[kv]
+        steps[0], steps[1] = 0, 0.0
         done_at = {}
         t0 = time.perf_counter()
         for i, codes in m.inference_stream(utts, top_k=10, seeds=seeds, poll_steps=poll, refill_at=refill):
             done_at[i] = time.perf_counter()  # codes are on the device, written by work already synchronised by the engine
-        return summary("stream", t0, done_at, frames, steps[0], B, poll_steps=poll, refill_at=refill)
+        return summary("stream", t0, done_at, frames, steps[0], B, poll_steps=poll, refill_at=refill, **extra(kv))
 
     for rep in range(args.reps):
-        runs.append(static())
-        for p in polls:
-            runs.append(stream(p, refills[0]))
-        for r in refills[1:]:
-            runs.append(stream(polls[0], r))
-    # codes of the two paths: identical AR tokens (same seeds, per-slot arithmetic) - checked once on the timed queue
-    ref = m.inference_batch(utts[:B], top_k=10, seeds=seeds[:B], batched_prefill=False)
-    got = dict(m.inference_stream(utts[:B], top_k=10, seeds=seeds[:B], batched_admit=False))
-    same = all(torch.equal(ref[i][0, :, 0], got[i][0, :, 0]) for i in range(B))
-    return dict(mode="queue", geometry="d=1024 nhead=16 L=12 bf16", slots=B, n=args.n, S_range=[10, 94], P=225,
-                frames=sum(frames), ar_codes_equal_static=same, runs=runs)
+        for kv in kvs:  # the formats alternate rep by rep on the same queue
+            runs.append(static(kv))
+            for p in polls:
+                runs.append(stream(kv, p, refills[0]))
+            for r in refills[1:]:
+                runs.append(stream(kv, polls[0], r))
+    # codes of the two paths: identical AR tokens (same seeds, per-slot arithmetic) - checked once on the timed queue, per format
+    same = {}
+    for kv in kvs:
+        m = models[kv][0]
+        ref = m.inference_batch(utts[:B], top_k=10, seeds=seeds[:B], batched_prefill=False)
+        got = dict(m.inference_stream(utts[:B], top_k=10, seeds=seeds[:B], batched_admit=False))
+        same[kv] = all(torch.equal(ref[i][0, :, 0], got[i][0, :, 0]) for i in range(len(ref)))
+    return dict(mode="queue", geometry=f"d=1024 nhead=16 L=12 {args.precision}", slots=B, n=args.n,
+                S_range=[args.text_len] * 2 if args.text_len else [10, 94], P=225, frames=sum(frames),
+                ar_codes_equal_static=same if len(kvs) > 1 else same[kvs[0]], runs=runs)
 
 
 def run_ab(args):
     import torch
 
-    m = model(args, 1024)
+    kv = args.kv_cache.split(",")[0]
+    m = model(args, 1024, kv)
     eng = m.engine()
     B = args.slots
     from valle_amd.weights import synthetic_inputs
@@ -156,7 +186,7 @@ def run_ab(args):
             if rep:  # the first is warm-up
                 vals.append(1e3 * t["batch_decode_ms"] / t["batch_launches"])
         out[name] = dict(step_us=[round(v, 2) for v in vals], mean_us=round(sum(vals) / len(vals), 2))
-    return dict(mode="ab_half_done", lib=args.lib or "libvallex.so", slots=B, S=47, P=225, T=753, **out)
+    return dict(mode="ab_half_done", lib=args.lib or "libvallex.so", kv_cache=kv, slots=B, S=47, P=225, T=753, **out)
 
 
 def main():
@@ -169,7 +199,12 @@ def main():
     ap.add_argument("--reps", type=int, default=1)
     ap.add_argument("--ab-half-done", action="store_true")
     ap.add_argument("--lib", default=None, help="--ab-half-done: load this libvallex.so instead of the package's")
+    ap.add_argument("--kv-cache", default="bf16", help="slot-cache formats, comma-separated: bf16, fp8 (both: an A/B on one queue)")
+    ap.add_argument("--precision", default="bf16", help="bf16 | fp8nar")
+    ap.add_argument("--text-len", type=int, default=None, help="every utterance S = this (default: S uniform in [10, 94])")
     args = ap.parse_args()
+    if not args.kv_cache or any(kv not in ("bf16", "fp8") for kv in args.kv_cache.split(",")):
+        ap.error("--kv-cache: comma-separated bf16 / fp8")
     res = run_ab(args) if args.ab_half_done else run_queue(args)
     print(json.dumps(res))
 

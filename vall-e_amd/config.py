@@ -92,3 +92,5 @@ def add_model_arguments(parser: argparse.ArgumentParser):
     parser.add_argument("--prepend-bos", type=str2bool, default=False)
     parser.add_argument("--num-quantizers", type=int, default=8)
     parser.add_argument("--scaling-xformers", type=str2bool, default=False)
+    # engine option (not in the reference): storage of the batched decode's slot KV caches (get_model forwards it)
+    parser.add_argument("--kv-cache", type=str, choices=("bf16", "fp8"), default=None)

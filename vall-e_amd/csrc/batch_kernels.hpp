@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include "ar_kernels.hpp"
 #include "mfma_kernels.hpp"
+#include "mx_kernels.hpp"
 
 namespace vx {
 
@@ -40,7 +41,42 @@ struct BgemmArgs {
   // [b pf_slice, (b+1) pf_slice) of `pf` with 8 unused 16-byte loads per lane.  Speed only.
   const void* pf;
   unsigned pf_slice, pf_total;
+  // BE_QKV with fp8 slot caches (VX_FLAG_KV_FP8): this layer's code / scale bases of slot 0, indexed as `kv` (kv8s by index >> 4)
+  uint8_t* kv8;
+  uint8_t* kv8s;
 };
+
+// ---- fp8 slot caches (VX_FLAG_KV_FP8) ----------------------------------------------------------------------------------------
+// Every K / V row of a head (64 channels) is four blocks of 16 consecutive channels; a block is 16 OCP e4m3 codes plus one E8M0
+// scale byte (value = code x 2^(byte - 127)).  Codes sit at the bf16 cache's element index (one byte each), the block's scale at
+// that index >> 4.  The source values are the bf16 values the bf16 cache would hold.  Mirrored by tests/kv8_ref.py.
+// Scale: the smallest byte with amax <= 448 x 2^(byte - 127) - the MX rule (mx_block_scale) plus one where that rule would clip
+// the block's largest element - so no value is clamped; the multiply by 2^(127 - byte) is exact and lands in [-448, 448].
+__device__ __forceinline__ uint32_t kv8_block_scale(float amax, float& inv) {
+  const uint32_t E = (__float_as_uint(amax) >> 23) & 0xffu;
+  uint32_t byte = max(E, 8u) - 8u;
+  if (amax * __uint_as_float((254u - byte) << 23) > 448.f) ++byte;
+  inv = __uint_as_float((254u - byte) << 23);  // 2^(127 - byte)
+  return byte;
+}
+// 2^(byte - 127) as an fp32 factor (byte 0: the subnormal 2^-127)
+__device__ __forceinline__ float kv8_scale(uint32_t byte) { return __uint_as_float(byte ? byte << 23 : 0x00400000u); }
+// one code, RNE (the argument is already scaled into [-448, 448])
+__device__ __forceinline__ uint32_t kv8_code(float v) { return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0, false) & 0xffu; }
+__device__ __forceinline__ void kv8_unpack(const uint4& r, float (&o)[16]) {
+  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[k], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[k], true);
+    o[4 * k] = lo[0]; o[4 * k + 1] = lo[1]; o[4 * k + 2] = hi[0]; o[4 * k + 3] = hi[1];
+  }
+}
+// sum over aligned groups of 4 lanes; every lane of the group gets the group sum
+__device__ __forceinline__ float group4_sum_dpp(float v) {
+  v += dpp_f<0xB1>(0.f, v);
+  v += dpp_f<0x4E>(0.f, v);
+  return v;
+}
 
 // C[b][n] = sum_k A[b][k] W[n][k] on v_mfma_f32_16x16x32_bf16: one workgroup = one 16-row n tile (x one K
 // group), its 4 waves take 4 K slices of NS steps and are summed through LDS in wave order.  Lane
@@ -49,7 +85,8 @@ struct BgemmArgs {
 // The operands of the kernel's FIRST loads (A, W, sizes) are explicit leading arguments: with the build's
 // `-amdgpu-kernarg-preload-count` they arrive in SGPRs at wave launch (hipcc does not preload by-value structs), so the weight
 // and activation loads do not wait for a kernarg fetch.  nk = (N << 16) | K.
-template <int EPI, int NS, int NH, bool PF = false>  // NH 16-row halves of slots: 2 (B <= 32) or 4 (B <= 64)
+// KV8 (BE_QKV): K / V rows go to the fp8 slot caches (a.kv8 / a.kv8s) instead of the bf16 ones.
+template <int EPI, int NS, int NH, bool PF = false, bool KV8 = false>  // NH 16-row halves of slots: 2 (B <= 32) or 4 (B <= 64)
 __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_, const bf16* __restrict__ W_, unsigned nk, int kgroups,
                                                     const BgemmArgs a) {
   __shared__ float red[4][4 * NH][64];
@@ -109,6 +146,18 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
     const int i = wave * NH + u;
     const float x = ((red[0][i][lane] + red[1][i][lane]) + red[2][i][lane]) + red[3][i][lane];
     const int b = 16 * (i >> 2) + 4 * g + (i & 3);
+    // fp8 slot caches: the 16 lanes of this DPP row hold channels n0 .. n0 + 15 of slot b, i.e. one cache block.  Its scale is
+    // reduced here, ahead of the branches below, whose conditions are uniform per row, so every lane of the row takes part.
+    float k8v = 0.f;
+    uint32_t k8s = 0;
+    if constexpr (EPI == BE_QKV && KV8) {
+      k8v = (float)(bf16)(x + bias_v);  // the value the bf16 cache would hold
+      float am = group8_max_dpp(fabsf(k8v));
+      am = fmaxf(am, dpp_f<0x140>(am, am));  // row_mirror: the other 8 lanes of the row
+      float inv;
+      k8s = kv8_block_scale(am, inv);
+      k8v *= inv;
+    }
     if (b >= a.B || n >= a.N) continue;
     if (EPI == BE_PARTIAL) {
       a.part[((size_t)kg * BMAX + b) * a.N + n] = x;
@@ -127,8 +176,14 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
         a.q[(size_t)b * a.d + ii] = v;
       } else if (!st_done[u]) {
         const int h = ii / a.hd, cc = ii - h * a.hd;
-        bf16* base = a.kv + (size_t)b * a.kv_slot_stride + (sec == 2 ? a.kv_v_offset : 0);
-        base[((size_t)h * a.ctx_max + st_row[u]) * a.hd + cc] = (bf16)v;
+        if constexpr (KV8) {
+          const size_t at = (size_t)b * a.kv_slot_stride + (sec == 2 ? a.kv_v_offset : 0) + ((size_t)h * a.ctx_max + st_row[u]) * a.hd + cc;
+          a.kv8[at] = (uint8_t)kv8_code(k8v);
+          if (c == 0) a.kv8s[at >> 4] = (uint8_t)k8s;
+        } else {
+          bf16* base = a.kv + (size_t)b * a.kv_slot_stride + (sec == 2 ? a.kv_v_offset : 0);
+          base[((size_t)h * a.ctx_max + st_row[u]) * a.hd + cc] = (bf16)v;
+        }
       }
     }
   }
@@ -295,6 +350,161 @@ __global__ __launch_bounds__(256) void attn_batch_kernel(const float* __restrict
   if (tid < HD) {
     // every wave scored at least one live key (ctx >= 1 and the first pass covers key 0 in wave 0; a wave whose keys were all past
     // ctx has M = -inf, L = 0, acc = 0 and weight 0)
+    const float Ma = fmaxf(fmaxf(sm_red[0], sm_red[1]), fmaxf(sm_red[2], sm_red[3]));
+    float o = 0.f, l = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float wgt = (sm_red[w] == -INFINITY) ? 0.f : expf(sm_red[w] - Ma);
+      float ow = 0.f, lw = 0.f;
+#pragma unroll
+      for (int gidx = 0; gidx < KPW; ++gidx) { ow += sm_o[w * KPW + gidx][tid]; lw += sm_l[w * KPW + gidx]; }
+      o = fmaf(wgt, ow, o);
+      l = fmaf(wgt, lw, l);
+    }
+    out[(size_t)slot * d + h * HD + tid] = (bf16)(o / l);
+  }
+}
+
+// Prefill rows -> fp8 slot caches (the fp8 forms of kv_scatter_kernel / kv_scatter_seg_kernel): one thread per 16-channel block of
+// a K or V row.  codes / scales: this layer's bases of slot 0 (or of the prefilled slot), indexed as in BgemmArgs.kv8 / kv8s.
+// seg_start == nullptr: row j of the buffer -> position j of the slot at codes (grid.x = rows); otherwise row j of segment z ->
+// position j of slot seg_slot[z] (grid = (max segment length, segments)).
+__global__ __launch_bounds__(256) void kv8_scatter_kernel(const bf16* __restrict__ qkv, uint8_t* __restrict__ codes,
+                                                          uint8_t* __restrict__ scales, size_t slot_stride, size_t v_offset,
+                                                          const int* __restrict__ seg_start, const int* __restrict__ seg_len,
+                                                          const int* __restrict__ seg_slot, int d, int ctx_max) {
+  constexpr int HD = 64;
+  const int j = blockIdx.x, z = blockIdx.y;
+  size_t r = j, base = 0;
+  if (seg_start != nullptr) {
+    if (j >= seg_len[z]) return;
+    r = (size_t)seg_start[z] + j;
+    base = (size_t)seg_slot[z] * slot_stride;
+  }
+  const int nb = d / 16;  // blocks per K (or V) row
+  for (int t = threadIdx.x; t < 2 * nb; t += blockDim.x) {
+    const int sec = t >= nb, i = 16 * (t - sec * nb);
+    const int h = i / HD, cc = i - h * HD;
+    const bf16* src = qkv + r * 3 * d + (size_t)(1 + sec) * d + i;
+    float f[2][8];
+    unpack<bf16>(ld16(src), f[0]);
+    unpack<bf16>(ld16(src + 8), f[1]);
+    float am = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) am = fmaxf(am, fmaxf(fabsf(f[0][k]), fabsf(f[1][k])));
+    float inv;
+    const uint32_t sb = kv8_block_scale(am, inv);
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float* p = f[k >> 1] + 4 * (k & 1);
+      int pk = __builtin_amdgcn_cvt_pk_fp8_f32(p[0] * inv, p[1] * inv, 0, false);
+      pk = __builtin_amdgcn_cvt_pk_fp8_f32(p[2] * inv, p[3] * inv, pk, true);
+      w[k] = (uint32_t)pk;
+    }
+    const size_t at = base + (sec ? v_offset : 0) + ((size_t)h * ctx_max + j) * HD + cc;
+    *reinterpret_cast<uint4*>(codes + at) = make_uint4(w[0], w[1], w[2], w[3]);
+    scales[at >> 4] = (uint8_t)sb;
+  }
+}
+
+// attn_batch_kernel on the fp8 slot caches: one 16-byte load carries a key's 16-channel block, so 4 lanes hold a key and a wave
+// scores 16 keys per pass.  The block scales (one byte per key and lane) multiply the lane's partial dot before the 4-lane sum
+// (K) and the lane's softmax weight (V): both are exact power-of-two factors.
+template <int HD, int UNR>  // UNR keys per lane and register set: 4 (default) or 2 (VX_KV8_UNR=2, A/B runs)
+__global__ __launch_bounds__(256) void attn_batch8_kernel(const float* __restrict__ q, const uint8_t* __restrict__ kv,
+                                                          const uint8_t* __restrict__ kvs, size_t kv_slot_stride, size_t kv_v_offset,
+                                                          const ArState* __restrict__ st, int ctx_max, int d, float scale,
+                                                          bf16* __restrict__ out) {
+  constexpr int VEC = 16, LPK = HD / VEC, KPW = 64 / LPK, KPB = 4 * KPW;
+  __shared__ float sm_red[4];
+  __shared__ __attribute__((aligned(16))) float sm_o[4 * KPW][HD + 1];
+  __shared__ float sm_l[4 * KPW];
+  const int h = blockIdx.x, slot = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sub = lane % LPK, grp = lane / LPK;
+  const int done = st[slot].done;
+  const int ctx = st[slot].row + 1;
+  float qv[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; i += 4) {
+    const float4 t = *reinterpret_cast<const float4*>(q + (size_t)slot * d + h * HD + sub * VEC + i);
+    qv[i] = t.x; qv[i + 1] = t.y; qv[i + 2] = t.z; qv[i + 3] = t.w;
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if (done) return;  // finished and vacant slots, as attn_batch_kernel
+  const size_t ko = (size_t)slot * kv_slot_stride + (size_t)h * ctx_max * HD;
+  const uint8_t* kb = kv + ko + sub * VEC;
+  const uint8_t* vb = kb + kv_v_offset;
+  const uint8_t* ksb = kvs + (ko >> 4) + sub;
+  const uint8_t* vsb = ksb + (kv_v_offset >> 4);
+  float M = -INFINITY, L = 0.f, acc[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
+  constexpr int STEP = UNR * KPB;
+  // two register sets, clamped unconditional loads: as attn_batch_kernel
+  uint4 kr0[UNR], vr0[UNR], kr1[UNR], vr1[UNR];
+  uint32_t ks0[UNR], vs0[UNR], ks1[UNR], vs1[UNR];
+  auto issue = [&](uint4 (&kr)[UNR], uint4 (&vr)[UNR], uint32_t (&ks)[UNR], uint32_t (&vs)[UNR], int base) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = min(base + u * KPB + wave * KPW + grp, ctx - 1);
+      kr[u] = *reinterpret_cast<const uint4*>(kb + (size_t)j * HD);
+      vr[u] = *reinterpret_cast<const uint4*>(vb + (size_t)j * HD);
+      ks[u] = ksb[(size_t)j * (HD / 16)];
+      vs[u] = vsb[(size_t)j * (HD / 16)];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto score = [&](const uint4 (&kr)[UNR], const uint4 (&vr)[UNR], const uint32_t (&ks)[UNR], const uint32_t (&vs)[UNR], int base) {
+    float sc[UNR], mloc = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = base + u * KPB + wave * KPW + grp;
+      float kf[VEC];
+      kv8_unpack(kr[u], kf);
+      float dot = 0.f;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) dot = fmaf(kf[i], qv[i], dot);
+      dot = group4_sum_dpp(dot * kv8_scale(ks[u]));
+      sc[u] = (j < ctx) ? dot * scale : -INFINITY;
+      mloc = fmaxf(mloc, sc[u]);
+    }
+    const float Mn = fmaxf(M, wave_max_dpp(mloc));
+    const float corr = (M == -INFINITY) ? 0.f : expf(M - Mn);
+    L *= corr;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) acc[i] *= corr;
+    M = Mn;
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      float vf[VEC];
+      kv8_unpack(vr[u], vf);
+      const float p = (sc[u] == -INFINITY) ? 0.f : expf(sc[u] - M);
+      L += p;
+      const float pv = p * kv8_scale(vs[u]);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) acc[i] = fmaf(pv, vf[i], acc[i]);
+    }
+  };
+  issue(kr0, vr0, ks0, vs0, 0);
+  for (int base = 0;;) {
+    issue(kr1, vr1, ks1, vs1, base + STEP);
+    score(kr0, vr0, ks0, vs0, base);
+    base += STEP;
+    if (base >= ctx) break;
+    issue(kr0, vr0, ks0, vs0, base + STEP);
+    score(kr1, vr1, ks1, vs1, base);
+    base += STEP;
+    if (base >= ctx) break;
+  }
+  const int gi = wave * KPW + grp;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) sm_o[gi][sub * VEC + i] = acc[i];
+  if (sub == 0) sm_l[gi] = L;
+  if (lane == 0) sm_red[wave] = M;
+  __syncthreads();
+  if (tid < HD) {
     const float Ma = fmaxf(fmaxf(sm_red[0], sm_red[1]), fmaxf(sm_red[2], sm_red[3]));
     float o = 0.f, l = 0.f;
 #pragma unroll

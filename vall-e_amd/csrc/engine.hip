@@ -155,6 +155,8 @@ struct vx_engine {
   float *bx = nullptr, *bq = nullptr, *bpart = nullptr, *blogits = nullptr, *btrace = nullptr;
   vx::bf16 *bh = nullptr, *batt = nullptr, *bff = nullptr, *bkv = nullptr;
   size_t bkv_slot = 0;  // elements per slot
+  bool kv8 = false;                           // VX_FLAG_KV_FP8: the slot caches are bkv8 / bkv8s, bkv stays null
+  uint8_t *bkv8 = nullptr, *bkv8s = nullptr;  // e4m3 codes (bkv_slot bytes per slot), E8M0 scales (one per 16 codes)
   ArState* bst = nullptr;    // device, BMAX
   ArState* h_bst = nullptr;  // pinned: [0..BMAX) staging, [BMAX..3*BMAX) two poll slots
   int *btok = nullptr, *bsamp = nullptr, *bargm = nullptr;
@@ -372,6 +374,10 @@ extern "C" int vx_create(const vx_config* cfg, vx_engine** out) {
   if (c.max_batch < 0 || c.max_batch > BMAX) return fail(VX_ERR_ARG, "max_batch must be 0..%d", BMAX);
   if (c.max_batch > 1 && (c.precision == VX_PREC_F32 || c.d_model % 128))
     return fail(VX_ERR_UNSUPPORTED, "batched decode needs bf16 precision and d_model % 128 == 0");
+  if ((c.flags & VX_FLAG_KV_FP8) && (c.max_batch < 2 || c.precision == VX_PREC_F32 || c.d_model / c.nhead != 64 ||
+                                     (c.flags & (VX_FLAG_POST_NORM | VX_FLAG_PRENET | VX_FLAG_VALLF))))
+    return fail(VX_ERR_UNSUPPORTED, "VX_FLAG_KV_FP8 needs max_batch >= 2, bf16 / fp8nar precision, head_dim 64 and a pre-norm VALL-E "
+                                    "without prenets");
 
   ON_DEVICE(c.device);
   vx_engine* e = new vx_engine();
@@ -499,7 +505,13 @@ static int create_body(vx_engine* e) {
     VXC(dalloc_t(e, &e->bh, (size_t)BMAX * d));
     VXC(dalloc_t(e, &e->batt, (size_t)BMAX * d));
     VXC(dalloc_t(e, &e->bff, (size_t)BMAX * 4 * d));
-    VXC(dalloc_t(e, &e->bkv, (size_t)e->bmax * e->bkv_slot));
+    e->kv8 = c.flags & VX_FLAG_KV_FP8;
+    if (e->kv8) {
+      VXC(dalloc_t(e, &e->bkv8, (size_t)e->bmax * e->bkv_slot));
+      VXC(dalloc_t(e, &e->bkv8s, (size_t)e->bmax * e->bkv_slot / 16));
+    } else {
+      VXC(dalloc_t(e, &e->bkv, (size_t)e->bmax * e->bkv_slot));
+    }
     VXC(dalloc_t(e, &e->bst, (size_t)BMAX));
     VXC(dalloc_t(e, &e->btok, (size_t)BMAX * e->btok_stride));
     VXC(dalloc_t(e, &e->bsamp, (size_t)BMAX * e->btok_stride));
@@ -958,8 +970,9 @@ static bool mx_on(const vx_engine* e, int ada_stage, int M, int d) {
   return e->fp8nar && ada_stage >= 0 && M >= (v ? atoi(v) : 4096) && !(e->cfg.flags & VX_FLAG_POST_NORM) && use_mfma(e) && d % 256 == 0;
 }
 
+// kv_base: the cache fill_cache writes (default: the batch-1 cache); kv8_slot >= 0: kv_base is that slot's fp8 cache instead
 static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int d, int H, int text_len, int ada_stage,
-                     bool fill_cache, char* kv_base = nullptr) {
+                     bool fill_cache, char* kv_base = nullptr, int kv8_slot = -1) {
   if (kv_base == nullptr) kv_base = (char*)e->kv;
   const bool post = e->cfg.flags & VX_FLAG_POST_NORM;
   const int hd = d / H;
@@ -1011,8 +1024,17 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
     }
     if (fill_cache && e->nseg > 0) {  // batched prefill: segment z -> slot d_seg_slot[z]
       const size_t kvl = (size_t)2 * H * e->ctx_max * 64;  // elements per layer
-      kv_scatter_seg_kernel<bf16><<<dim3(e->max_seg_len, e->nseg), 256, 0, e->es>>>(
-          (const bf16*)e->QKV, e->bkv + li * kvl, e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, d, 64, e->ctx_max, e->d_seg_slot);
+      if (e->kv8)
+        kv8_scatter_kernel<<<dim3(e->max_seg_len, e->nseg), 256, 0, e->es>>>((const bf16*)e->QKV, e->bkv8 + li * kvl, e->bkv8s + li * kvl / 16,
+                                                                             e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, e->d_seg_slot,
+                                                                             d, e->ctx_max);
+      else
+        kv_scatter_seg_kernel<bf16><<<dim3(e->max_seg_len, e->nseg), 256, 0, e->es>>>(
+            (const bf16*)e->QKV, e->bkv + li * kvl, e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, d, 64, e->ctx_max, e->d_seg_slot);
+    } else if (fill_cache && kv8_slot >= 0) {  // per-slot prefill into an fp8 slot cache
+      const size_t kvl = (size_t)2 * H * e->ctx_max * 64, at = (size_t)kv8_slot * e->bkv_slot + li * kvl;
+      kv8_scatter_kernel<<<M, 256, 0, e->es>>>((const bf16*)e->QKV, e->bkv8 + at, e->bkv8s + at / 16, 0, kvl / 2, nullptr, nullptr, nullptr,
+                                               d, e->ctx_max);
     } else if (fill_cache) {
       char* kc = kv_base + li * kv_layer;
       char* vc = kc + kv_layer / 2;
@@ -1232,12 +1254,12 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
     embed_pos_kernel<<<A, 256, 0, e->es>>>(e->ids_audio, 1, 0, W<float>(e, "ar_audio_embedding.word_embeddings.weight"), 1025 + bos, d,
                                            W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, e->X + (size_t)(vf ? 0 : S) * d, A);
   }
-  char* kv_base = slot < 0 ? (char*)e->kv : (char*)(e->bkv + (size_t)slot * e->bkv_slot);
+  char* kv_base = slot < 0 ? (char*)e->kv : e->kv8 ? nullptr : (char*)(e->bkv + (size_t)slot * e->bkv_slot);
   float* x_dst = slot < 0 ? e->ar_x : e->bx + (size_t)slot * d;
   float* lg_dst = slot < 0 ? e->ar_logits : e->blogits + (size_t)slot * LOGITS_CUR;
   ArState* st_dst = slot < 0 ? e->d_st : e->bst + slot;
   if (vf) { e->mem_len = S; VXC(run_stack_f(e, e->ar_l, M, d, c.nhead, 0, -1, true, e->xkv_ar, S)); }
-  else VXC(run_stack(e, e->ar_l, M, d, c.nhead, S, -1, true, kv_base));
+  else VXC(run_stack(e, e->ar_l, M, d, c.nhead, S, -1, true, kv_base, slot >= 0 && e->kv8 ? slot : -1));
   HIPC(hipMemcpyAsync(x_dst, e->X + (size_t)(M - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
   ArState& st = slot < 0 ? e->h_st[0] : e->h_bst[slot];
   seed_state(st, S, P, bos, M - 1, vf ? 0 : S, slot < 0 && (c.flags & VX_FLAG_TRACE_LOGITS));
@@ -1815,13 +1837,13 @@ extern "C" int vx_ar_result(vx_engine* e, int64_t* tokens, int32_t capacity, int
 }
 
 // ------------------------------------------------------------------------------ batched AR decode
-template <int EPI, int NH> static int launch_bgemm_h(const BgemmArgs& a, int ns, int grid, hipStream_t s) {
+template <int EPI, int NH, bool KV8> static int launch_bgemm_h(const BgemmArgs& a, int ns, int grid, hipStream_t s) {
   if (a.N > 65535 || a.K > 65535) return fail(VX_ERR_UNSUPPORTED, "bgemm: N=%d K=%d", a.N, a.K);  // (N << 16) | K travels as one argument
   const unsigned nk = ((unsigned)a.N << 16) | (unsigned)a.K;
 #define BG(NSV)                                                                                              \
   if (ns == NSV) {                                                                                           \
-    if (a.pf != nullptr) bgemm_kernel<EPI, NSV, NH, true><<<grid, 256, 0, s>>>(a.A, a.W, nk, a.kgroups, a);   \
-    else bgemm_kernel<EPI, NSV, NH><<<grid, 256, 0, s>>>(a.A, a.W, nk, a.kgroups, a);                         \
+    if (a.pf != nullptr) bgemm_kernel<EPI, NSV, NH, true, KV8><<<grid, 256, 0, s>>>(a.A, a.W, nk, a.kgroups, a); \
+    else bgemm_kernel<EPI, NSV, NH, false, KV8><<<grid, 256, 0, s>>>(a.A, a.W, nk, a.kgroups, a);                \
     return VX_OK;                                                                                            \
   }
   BG(1) BG(2) BG(4) BG(8)
@@ -1837,13 +1859,15 @@ static void bgemm_prefetch(BgemmArgs& a, const void* Wn, int Nn, int Kn) {
   if (slice > 32768) slice = 32768;
   a.pf = Wn; a.pf_slice = (unsigned)slice; a.pf_total = (unsigned)total;
 }
-template <int EPI> static int launch_bgemm(const BgemmArgs& a, hipStream_t s) {
+// KV8 (BE_QKV only): write the fp8 slot caches a.kv8 / a.kv8s
+template <int EPI, bool KV8> static int launch_bgemm(const BgemmArgs& a, hipStream_t s) {
   const int ns = a.K / (a.kgroups * 128);
   const int grid = ((a.N + 15) / 16) * a.kgroups;
   if (ns * a.kgroups * 128 != a.K) return fail(VX_ERR_UNSUPPORTED, "bgemm: K=%d kgroups=%d", a.K, a.kgroups);
   // two 16-slot MFMA halves up to 32 slots, four up to 64
-  return a.B <= 32 ? launch_bgemm_h<EPI, 2>(a, ns, grid, s) : launch_bgemm_h<EPI, 4>(a, ns, grid, s);
+  return a.B <= 32 ? launch_bgemm_h<EPI, 2, KV8>(a, ns, grid, s) : launch_bgemm_h<EPI, 4, KV8>(a, ns, grid, s);
 }
+template <int EPI> static int launch_bgemm(const BgemmArgs& a, hipStream_t s) { return launch_bgemm<EPI, false>(a, s); }
 static int kgroups_for(int K) { return (K / 128) >= 4 ? 4 : 1; }
 static void launch_ln_batch(float* x, const float* part, int kgroups, const float* pbias, const float* gamma, const float* beta,
                             bf16* h, int B, int d, hipStream_t s) {
@@ -1873,6 +1897,8 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
   // (profiles/r02_ab_batch_prefetch.log) - between two GEMMs of the batched step sit an attention kernel that streams 87 MB of
   // K / V and the LayerNorm, and the memory system is not idle as in the batch-1 step.
   static const int pf_dist = getenv("VX_BATCH_PREFETCH") ? atoi(getenv("VX_BATCH_PREFETCH")) : 0;
+  // keys per lane and register set of the fp8-cache attention (VX_KV8_UNR=2: A/B runs; anything else: 4)
+  static const int kv8_unr = getenv("VX_KV8_UNR") ? atoi(getenv("VX_KV8_UNR")) : 4;
   struct PfW { const void* W; int N, K; };
   std::vector<PfW> seq;
   for (int li = 0; li < L; ++li) {
@@ -1893,11 +1919,23 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
     BgemmArgs a{};
     a.st = e->bst; a.B = B; a.d = d; a.hd = hd; a.ctx_max = e->ctx_max;
     a.A = e->bh; a.W = (const bf16*)l.in_w; a.bias = l.in_b; a.N = 3 * d; a.K = d; a.kgroups = 1;
-    a.q = e->bq; a.kv = e->bkv + (size_t)li * kv_layer; a.kv_slot_stride = e->bkv_slot; a.kv_v_offset = kv_layer / 2;
+    a.q = e->bq; a.kv_slot_stride = e->bkv_slot; a.kv_v_offset = kv_layer / 2;
     warm(a, 4 * li);
-    VXC(launch_bgemm<BE_QKV>(a, s));
-    attn_batch_kernel<64><<<dim3(H, B), 256, 0, s>>>(e->bq, e->bkv + (size_t)li * kv_layer, e->bkv_slot, kv_layer / 2, e->bst,
-                                                     e->ctx_max, d, scale, e->batt);
+    if (e->kv8) {
+      a.kv8 = e->bkv8 + (size_t)li * kv_layer; a.kv8s = e->bkv8s + (size_t)li * kv_layer / 16;
+      VXC((launch_bgemm<BE_QKV, true>(a, s)));
+      if (kv8_unr == 2)
+        attn_batch8_kernel<64, 2><<<dim3(H, B), 256, 0, s>>>(e->bq, a.kv8, a.kv8s, e->bkv_slot, kv_layer / 2, e->bst, e->ctx_max, d,
+                                                             scale, e->batt);
+      else
+        attn_batch8_kernel<64, 4><<<dim3(H, B), 256, 0, s>>>(e->bq, a.kv8, a.kv8s, e->bkv_slot, kv_layer / 2, e->bst, e->ctx_max, d,
+                                                             scale, e->batt);
+    } else {
+      a.kv = e->bkv + (size_t)li * kv_layer;
+      VXC(launch_bgemm<BE_QKV>(a, s));
+      attn_batch_kernel<64><<<dim3(H, B), 256, 0, s>>>(e->bq, e->bkv + (size_t)li * kv_layer, e->bkv_slot, kv_layer / 2, e->bst,
+                                                       e->ctx_max, d, scale, e->batt);
+    }
     BgemmArgs o{};
     o.st = e->bst; o.B = B;
     o.A = e->batt; o.W = (const bf16*)l.out_w; o.N = d; o.K = d; o.kgroups = kg_d; o.part = e->bpart;
@@ -2431,6 +2469,11 @@ extern "C" int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t
   else if (n == "batch_logits" && e->bmax > 1) { src = (const char*)e->blogits; size = (int64_t)BMAX * LOGITS_CUR * 4; }
   else if (n == "batch_argmax" && e->bmax > 1) { src = (const char*)e->bargm; size = (int64_t)BMAX * e->btok_stride * 4; }
   else if (n == "batch_sampled" && e->bmax > 1) { src = (const char*)e->bsamp; size = (int64_t)BMAX * e->btok_stride * 4; }
+  else if (n == "batch_kv" && e->bmax > 1) {
+    src = e->kv8 ? (const char*)e->bkv8 : (const char*)e->bkv;
+    size = (int64_t)e->bmax * e->bkv_slot * (e->kv8 ? 1 : 2);
+  }
+  else if (n == "batch_kv_scale" && e->kv8) { src = (const char*)e->bkv8s; size = (int64_t)e->bmax * e->bkv_slot / 16; }
   else return fail(VX_ERR_ARG, "unknown buffer '%s'", name);
   if (off < 0 || nbytes < 0 || off + nbytes > size) return fail(VX_ERR_ARG, "read of '%s' out of range (%lld+%lld > %lld)", name, (long long)off, (long long)nbytes, (long long)size);
   HIPC(hipStreamSynchronize(e->es));  // the copy below runs on the null stream, which the engine's non-blocking stream does not order with

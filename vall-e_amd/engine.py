@@ -18,6 +18,8 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvallex.so")
 VX_PREC_F32, VX_PREC_BF16, VX_PREC_FP8_NAR = 0, 1, 2
 BMAX = 64  # slots per engine (csrc/batch_kernels.hpp)
 VX_FLAG_TRACE_LOGITS, VX_FLAG_NO_GRAPH, VX_FLAG_SIMPLE_ROWS, VX_FLAG_POST_NORM, VX_FLAG_PRENET, VX_FLAG_VALLF = 1, 2, 4, 8, 16, 32
+VX_FLAG_KV_FP8 = 64
+KV_CACHES = ("bf16", "fp8")  # storage of the batched decode's slot caches (VX_FLAG_KV_FP8)
 VX_ADMIT_BATCHED, VX_ADMIT_PER_SLOT = 0, 1
 STOP_REASONS = {0: "none", 1: "eos_argmax", 2: "eos_sample", 3: "length", 4: "max_new"}
 
@@ -151,7 +153,10 @@ class Engine:
     """One model replica on one GPU (see include/vallex.h for the contract of each call)."""
 
     def __init__(self, cfg, precision: str = "bf16", max_text: int = 256, max_audio: int = 2048, device: int = 0,
-                 trace_logits: bool = False, no_graph: bool = False, simple_rows: bool = False, max_batch: int = 0):
+                 trace_logits: bool = False, no_graph: bool = False, simple_rows: bool = False, max_batch: int = 0,
+                 kv_cache: str = "bf16"):
+        if kv_cache not in KV_CACHES:
+            raise ValueError(f"kv_cache must be one of {KV_CACHES}, got {kv_cache!r}")
         self.lib = load_library()
         self.cfg = cfg
         self.device = int(device)
@@ -166,9 +171,11 @@ class Engine:
         c.flags = (VX_FLAG_TRACE_LOGITS if trace_logits else 0) | (VX_FLAG_NO_GRAPH if no_graph else 0) | \
                   (VX_FLAG_SIMPLE_ROWS if simple_rows else 0) | (0 if getattr(cfg, "norm_first", True) else VX_FLAG_POST_NORM) | \
                   (VX_FLAG_PRENET if getattr(cfg, "add_prenet", False) else 0) | \
-                  (VX_FLAG_VALLF if getattr(cfg, "is_vallf", False) else 0)
+                  (VX_FLAG_VALLF if getattr(cfg, "is_vallf", False) else 0) | \
+                  (VX_FLAG_KV_FP8 if kv_cache == "fp8" else 0)
         c.max_batch = int(max_batch)
         self.max_text, self.max_audio, self.trace_logits, self.max_batch = max_text, max_audio, trace_logits, int(max_batch)
+        self.kv_cache = kv_cache
         self.mfma_rows = c.precision != VX_PREC_F32 and not simple_rows
         h = C.c_void_p()
         _check(self.lib.vx_create(C.byref(c), C.byref(h)))

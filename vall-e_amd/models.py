@@ -32,7 +32,9 @@ def _ids_out_of_range(x: torch.Tensor, y: torch.Tensor) -> bool:
 
 class VALLE:
     """Decoder-only VALL-E (inference only).  Engine-specific keyword arguments (not in the
-    reference): ``precision`` ("bf16" | "fp32"), ``max_text``, ``max_audio`` (capacities),
+    reference): ``precision`` ("bf16" | "fp32" | "fp8nar"), ``max_text``, ``max_audio`` (capacities), ``max_batch`` (slots of
+    ``inference_batch`` / ``inference_stream``), ``kv_cache`` ("bf16" | "fp8": storage of those slots' KV caches; "fp8" needs
+    max_batch >= 2, a bf16 / fp8nar precision, head_dim 64 and a pre-norm VALL-E without prenets),
     ``sampling`` ("device": on-GPU counter RNG seeded from torch's global generator;
     "torch_cpu": reproduce the exact Exp(1) stream torch.multinomial would consume on CPU)."""
 
@@ -44,7 +46,7 @@ class VALLE:
             precision=kwargs.pop("precision", "bf16"), max_text=kwargs.pop("max_text", 512),
             max_audio=kwargs.pop("max_audio", 4096), trace_logits=kwargs.pop("trace_logits", False),
             no_graph=kwargs.pop("no_graph", False), simple_rows=kwargs.pop("simple_rows", False),
-            max_batch=kwargs.pop("max_batch", 0))
+            max_batch=kwargs.pop("max_batch", 0), kv_cache=kwargs.pop("kv_cache", "bf16"))
         self.sampling = kwargs.pop("sampling", "device")
         self.print_eos = kwargs.pop("print_eos", True)
         self.cfg = ModelConfig(model_name=self.MODEL_NAME, decoder_dim=d_model, nhead=nhead, num_decoder_layers=num_layers, norm_first=norm_first,
@@ -53,6 +55,18 @@ class VALLE:
                                num_quantizers=kwargs.pop("num_quantizers", 8))
         if kwargs:
             raise TypeError(f"unexpected arguments {sorted(kwargs)}")
+        kv = self.engine_opts["kv_cache"]
+        if kv not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache must be 'bf16' or 'fp8', got {kv!r}")
+        if kv == "fp8":  # the engine refuses these too (VX_FLAG_KV_FP8); here they fail before an engine exists
+            if self.engine_opts["max_batch"] < 2:
+                raise NotImplementedError("kv_cache='fp8' is the batched decode's slot cache: it needs max_batch >= 2")
+            if self.engine_opts["precision"] not in ("bf16", "fp8nar"):
+                raise NotImplementedError("kv_cache='fp8' needs precision 'bf16' or 'fp8nar'")
+            if not norm_first or add_prenet or self.cfg.is_vallf:
+                raise NotImplementedError("kv_cache='fp8' needs a pre-norm VALL-E without prenets")
+            if d_model % nhead or d_model // nhead != 64:
+                raise NotImplementedError("kv_cache='fp8' needs head_dim 64")
         if (not norm_first or add_prenet or self.cfg.is_vallf) and self.engine_opts.get("max_batch", 0) > 1:
             raise NotImplementedError("norm_first=False / add_prenet=True / VALL-F run on the batch-1 path only (inference_batch needs the defaults)")
         if self.cfg.is_vallf and self.engine_opts["precision"] == "fp8nar":
@@ -135,7 +149,9 @@ class VALLE:
                   top_k: int = -100, temperature: float = 1.0, exp_noise: Optional[torch.Tensor] = None,
                   max_new_tokens: int = -1) -> torch.Tensor:
         """Same contract as the reference (valle.py:961-985): x (1,S) int64, x_lens (1,), y (1,P,8) int64 →
-        (1,T,num_quantizers) int64 on the model's device.  ``exp_noise`` / ``max_new_tokens`` are extras."""
+        (1,T,num_quantizers) int64 on the model's device.  ``exp_noise`` / ``max_new_tokens`` are extras.
+        This batch-1 path keeps its own bf16 KV cache on every model, ``kv_cache="fp8"`` included (that option only
+        changes the slot caches of ``inference_batch`` / ``inference_stream``)."""
         u = (x, x_lens, y, enroll_x_lens)
         self._check_utterance(u)
         eng = self.engine()
@@ -347,7 +363,7 @@ def get_model(params) -> VALLE:
         raise NotImplementedError(f"model {cfg.model_name!r}: only VALL-E and VALL-F are built (DESIGN.md)")
     extra = {}
     get = params.get if isinstance(params, dict) else lambda k, d=None: getattr(params, k, d)
-    for k in ("precision", "max_text", "max_audio", "sampling"):
+    for k in ("precision", "max_text", "max_audio", "sampling", "max_batch", "kv_cache"):
         if get(k, None) is not None:
             extra[k] = get(k)
     return cls(cfg.decoder_dim, cfg.nhead, cfg.num_decoder_layers, norm_first=cfg.norm_first, add_prenet=cfg.add_prenet,
