@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of one environment switch on the default bench (batch-1 AR step), alternating processes on one box:
-#   tests/probes/ar_ab.sh VAR rounds value [value ...]        e.g.  ar_ab.sh VX_AR_NT 3 0 1
+#   tests/probes/ar_ab.sh VAR rounds value [value ...]        e.g.  ar_ab.sh VX_AR_PREFETCH 3 0 2
 VAR=$1; N=$2; shift 2
 for i in $(seq $N); do
   for v in "$@"; do

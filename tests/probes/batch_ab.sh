@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of one environment switch on the batched bench (BASELINE configs[2]: --batch 32), alternating processes on one box:
-#   tests/probes/batch_ab.sh VAR rounds value [value ...]        e.g.  batch_ab.sh VX_BATCH_LNFUSE 2 0 1
+#   tests/probes/batch_ab.sh VAR rounds value [value ...]        e.g.  batch_ab.sh VX_GEMM_TAIL 2 0 1
 VAR=$1; N=$2; shift 2
 for i in $(seq $N); do
   for v in "$@"; do

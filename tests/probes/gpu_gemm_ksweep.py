@@ -21,9 +21,8 @@ def bench(M, N, K, iters=50):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / iters
 
-alg = os.environ.get("VX_GEMM_ALG", "0")
 for (M, N) in [(1025, 3072), (1025, 1024), (1025, 4096), (1024, 3072), (128, 3072)]:
     row = {}
     for K in (256, 512, 1024, 2048, 4096):
         row[K] = round(bench(M, N, K), 1)
-    print(json.dumps(dict(alg=alg, M=M, N=N, us_by_K=row)), flush=True)
+    print(json.dumps(dict(M=M, N=N, us_by_K=row)), flush=True)

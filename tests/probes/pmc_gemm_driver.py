@@ -1,5 +1,5 @@
 """Torch-free driver: one bf16 GEMM through vx_op_gemm for rocprofv3 --pmc (traffic / MFMA counters).
-usage: python3 tests/probes/pmc_gemm_driver.py M N K [iters] [form]   (VX_GEMM_ALG selects the kernel)
+usage: python3 tests/probes/pmc_gemm_driver.py M N K [iters] [form]   (the shape selects the kernel: mfma_gemm_dispatch)
 form (optional): "bf16" = bf16 output + bias, "qkv" = the same + V^T copy of the last third, "relu" = bf16 output + ReLU, "resid" = fp32
 residual update (vx_op_gemm_rows: the forms the engine's row path launches); default: fp32 output + bias (vx_op_gemm)."""
 import ctypes as C

@@ -20,10 +20,7 @@ enum GemvPro { PRO_COPY = 0, PRO_LN = 1, PRO_ATTN = 2 };
 enum GemvEpi { EPI_PLAIN = 0, EPI_BIAS = 1, EPI_RELU = 2, EPI_RESID = 3, EPI_QKV = 4, EPI_LOGITS = 5, EPI_POS = 6 };  // POS: + bias + alpha * pe[audio position] (last prenet layer)
 
 constexpr int LOGITS_CUR = 1088;     // floats reserved for the newest logits row at the buffer head; trace rows follow
-#ifndef VX_ATT_NSPLIT
-#define VX_ATT_NSPLIT 8  // A/B builds: hipcc -DVX_ATT_NSPLIT=4 (profiles/r02_notes.md)
-#endif
-constexpr int ATT_NSPLIT = VX_ATT_NSPLIT;  // key splits per head in the decode attention
+constexpr int ATT_NSPLIT = 8;  // key splits per head in the decode attention (4 and 16 measured slower, profiles/r02_notes.md)
 constexpr int ATT_PSTRIDE = 4 + 64;  // floats per partial: {m, l, -, -, o[64]}
 
 struct GemvArgs {
@@ -53,7 +50,6 @@ struct GemvArgs {
   const void* pf;
   unsigned pf_slice, pf_total;
   int kid;  // position in the decode step (probe builds: VX_KSTAMP; -1 = not stamped)
-  int nt;   // non-temporal weight loads (decode step, VX_AR_NT)
 };
 
 // y = W x (+epilogue).  One wave owns RPW rows at a time; a row is KCH 16-byte loads per lane;
@@ -63,8 +59,7 @@ struct GemvArgs {
 // available), so those loads do not wait for a kernarg fetch - one memory round trip per wave otherwise.  hipcc does not
 // preload by-value structs, so GemvArgs alone would not qualify; everything else is read from it after the weight loads
 // are out.   xin = a.part for PRO_ATTN, a.x otherwise;  nk = (N << 16) | K.
-// NT: the weight stream uses non-temporal loads (global_load_dwordx4 ... nt): each weight byte is read once per token by one CU.
-template <typename WT, int KCH, int RPW, int PRO, int NPF = 0, bool NT = false>
+template <typename WT, int KCH, int RPW, int PRO, int NPF = 0>
 __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ W_, const float* __restrict__ xin,
                                                    const float* __restrict__ gamma_, const float* __restrict__ beta_,
                                                    unsigned nk, const GemvArgs a) {
@@ -123,7 +118,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ W_, 
 #pragma unroll
       for (int c = 0; c < KCH; ++c) {
         const int k = min((c * 64 + lane) * VEC, K - VEC);
-        w[r][c] = NT ? ld16nt(W + (size_t)row * K + k) : ld16(W + (size_t)row * K + k);
+        w[r][c] = ld16(W + (size_t)row * K + k);
       }
     }
   };

@@ -37,10 +37,6 @@ struct BgemmArgs {
   float* trace;       // BE_LOGITS, optional (VX_FLAG_TRACE_LOGITS): (slots, trace_rows, N) - row `pass` of every live slot
   int trace_rows;
   const int* slot_map;  // BE_LOGITS_MAP: (B,) slot of every A row
-  // cache warm-up for a LATER GEMM of the step (as GemvArgs.pf of the batch-1 step): workgroup b touches bytes
-  // [b pf_slice, (b+1) pf_slice) of `pf` with 8 unused 16-byte loads per lane.  Speed only.
-  const void* pf;
-  unsigned pf_slice, pf_total;
   // BE_QKV with fp8 slot caches (VX_FLAG_KV_FP8): this layer's code / scale bases of slot 0, indexed as `kv` (kv8s by index >> 4)
   uint8_t* kv8;
   uint8_t* kv8s;
@@ -86,7 +82,7 @@ __device__ __forceinline__ float group4_sum_dpp(float v) {
 // `-amdgpu-kernarg-preload-count` they arrive in SGPRs at wave launch (hipcc does not preload by-value structs), so the weight
 // and activation loads do not wait for a kernarg fetch.  nk = (N << 16) | K.
 // KV8 (BE_QKV): K / V rows go to the fp8 slot caches (a.kv8 / a.kv8s) instead of the bf16 ones.
-template <int EPI, int NS, int NH, bool PF = false, bool KV8 = false>  // NH 16-row halves of slots: 2 (B <= 32) or 4 (B <= 64)
+template <int EPI, int NS, int NH, bool KV8 = false>  // NH 16-row halves of slots: 2 (B <= 32) or 4 (B <= 64)
 __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_, const bf16* __restrict__ W_, unsigned nk, int kgroups,
                                                     const BgemmArgs a) {
   __shared__ float red[4][4 * NH][64];
@@ -119,14 +115,6 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
   for (int s = 0; s < NS; ++s)
 #pragma unroll
     for (int h = 0; h < NH; ++h) af[h][s] = *reinterpret_cast<const bf16x8b_t*>(ap + (size_t)16 * h * K + s * 32);
-  // a later GEMM's weights, requested behind this kernel's own loads (vmcnt retires in order: the waits of the MFMAs do not cover them)
-  uint4 pfv[PF ? 8 : 1];
-  if (PF) {
-    const unsigned lim = min(a.pf_slice, a.pf_total - min(a.pf_total, blockIdx.x * a.pf_slice));
-    const char* pb = reinterpret_cast<const char*>(a.pf) + min((size_t)blockIdx.x * a.pf_slice, (size_t)a.pf_total - 16);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) pfv[i] = *reinterpret_cast<const uint4*>(pb + min((unsigned)(i * 4096 + tid * 16), max(lim, 16u) - 16u));
-  }
   f32x4_t acc[NH];
 #pragma unroll
   for (int h = 0; h < NH; ++h) acc[h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -186,10 +174,6 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
         }
       }
     }
-  }
-  if (PF) {  // the warm-up loads stay live (and unwaited) until here
-#pragma unroll
-    for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(pfv[i].x), "v"(pfv[i].y), "v"(pfv[i].z), "v"(pfv[i].w));
   }
 }
 
@@ -411,12 +395,12 @@ __global__ __launch_bounds__(256) void kv8_scatter_kernel(const bf16* __restrict
 // attn_batch_kernel on the fp8 slot caches: one 16-byte load carries a key's 16-channel block, so 4 lanes hold a key and a wave
 // scores 16 keys per pass.  The block scales (one byte per key and lane) multiply the lane's partial dot before the 4-lane sum
 // (K) and the lane's softmax weight (V): both are exact power-of-two factors.
-template <int HD, int UNR>  // UNR keys per lane and register set: 4 (default) or 2 (VX_KV8_UNR=2, A/B runs)
+template <int HD>
 __global__ __launch_bounds__(256) void attn_batch8_kernel(const float* __restrict__ q, const uint8_t* __restrict__ kv,
                                                           const uint8_t* __restrict__ kvs, size_t kv_slot_stride, size_t kv_v_offset,
                                                           const ArState* __restrict__ st, int ctx_max, int d, float scale,
                                                           bf16* __restrict__ out) {
-  constexpr int VEC = 16, LPK = HD / VEC, KPW = 64 / LPK, KPB = 4 * KPW;
+  constexpr int VEC = 16, LPK = HD / VEC, KPW = 64 / LPK, KPB = 4 * KPW, UNR = 4;
   __shared__ float sm_red[4];
   __shared__ __attribute__((aligned(16))) float sm_o[4 * KPW][HD + 1];
   __shared__ float sm_l[4 * KPW];

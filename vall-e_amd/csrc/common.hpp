@@ -94,10 +94,6 @@ template <typename T> __device__ __forceinline__ void unpack(const uint4& r, flo
 }
 template <typename T> __device__ __forceinline__ uint4 ld16(const T* p) { return *reinterpret_cast<const uint4*>(p); }
 typedef unsigned vx_u32x4 __attribute__((ext_vector_type(4)));
-template <typename T> __device__ __forceinline__ uint4 ld16nt(const T* p) {  // global_load_dwordx4 ... nt
-  const vx_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const vx_u32x4*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
 
 // ---- DPP reductions (VALU cross-lane, no LDS round trip; ds_bpermute-based __shfl costs ~10x) ----
 // dpp_ctrl: 0xB1 quad_perm[1,0,3,2], 0x4E quad_perm[2,3,0,1], 0x124/0x128 row_ror:4/8,

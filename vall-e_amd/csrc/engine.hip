@@ -727,9 +727,6 @@ static void launch_gemv_inst(const GemvArgs& a, int grid, hipStream_t s) {
   const float* xin = PRO == PRO_ATTN ? a.part : a.x;
   const unsigned nk = ((unsigned)a.N << 16) | (unsigned)a.K;  // N, K < 65536 (checked by the caller: K <= 4096, N <= 4 d)
   if (a.kid >= 0) grid += VX_KSTAMP_EXTRA;  // probe builds: one extra workgroup that only records the time (common.hpp)
-  if constexpr (std::is_same<WT, bf16>::value) {
-    if (a.nt && a.pf != nullptr) { gemv_kernel<WT, KCH, RPW, PRO, 8, true><<<grid, 256, 0, s>>>(a.W, xin, a.gamma, a.beta, nk, a); return; }
-  }
   if (a.pf != nullptr) gemv_kernel<WT, KCH, RPW, PRO, 8><<<grid, 256, 0, s>>>(a.W, xin, a.gamma, a.beta, nk, a);
   else gemv_kernel<WT, KCH, RPW, PRO, 0><<<grid, 256, 0, s>>>(a.W, xin, a.gamma, a.beta, nk, a);
 }
@@ -739,29 +736,10 @@ static void launch_gemv_inst(const GemvArgs& a, int grid, hipStream_t s) {
 struct GemvPlan { int grid, kch, rpw; };
 static GemvPlan gemv_plan(int N, int K, int vec, int num_cu) {
   const int need_kch = (K + 64 * vec - 1) / (64 * vec);
-  // A/B switches (tests/probes/ar_ab.sh): VX_AR_GRID_MULT = workgroups per CU of the decode GEMVs (default 1),
-  // VX_AR_HEAD_WGS = workgroups of the 1025-row head GEMV (default: one per CU)
-  static const int mult = [] { const char* v = getenv("VX_AR_GRID_MULT"); const int m = v ? atoi(v) : 1; return m >= 1 && m <= 4 ? m : 1; }();
-  static const int head_wgs = [] { const char* v = getenv("VX_AR_HEAD_WGS"); return v ? atoi(v) : 65; }();
-  // VX_AR_WGS="NxK:wgs,NxK:wgs,...": workgroups of the GEMV with that shape (A/B runs), e.g. "1024x1024:64,1024x4096:128"
-  static const std::vector<std::array<int, 3>> wgs_tab = [] {
-    std::vector<std::array<int, 3>> t;
-    const char* v = getenv("VX_AR_WGS");
-    while (v && *v) {
-      int n = 0, k = 0, w = 0, used = 0;
-      if (sscanf(v, "%dx%d:%d%n", &n, &k, &w, &used) == 3 && w > 0) t.push_back({n, k, w});
-      else break;
-      v += used;
-      if (*v == ',') ++v;
-    }
-    return t;
-  }();
-  GemvPlan p{num_cu * mult, 1, 1};
-  // the 1025-row head streams 2 MB: 65 workgroups of 4 waves x 4 rows (one pass) finish sooner than one workgroup per CU with one or
-  // two rows per wave (A/B on one box, alternating processes: 230.6 vs 236.7 us per step; 129: 234; profiles/r02_notes.md)
-  if (N == AR_VOCAB && head_wgs > 0) p.grid = head_wgs;
-  for (const auto& t : wgs_tab)
-    if (t[0] == N && t[1] == K) p.grid = t[2];
+  // one workgroup per CU (two measured slower, profiles/r02_notes.md).  The 1025-row head streams 2 MB: 65 workgroups of 4 waves x
+  // 4 rows (one pass) finish sooner than one workgroup per CU with one or two rows per wave (A/B on one box, alternating
+  // processes: 230.6 vs 236.7 us per step; 129: 234)
+  GemvPlan p{N == AR_VOCAB ? 65 : num_cu, 1, 1};
   while (p.kch < need_kch) p.kch <<= 1;
   if ((N + 3) / 4 < p.grid) p.grid = (N + 3) / 4;
   const int need_rpw = (N + p.grid * 4 - 1) / (p.grid * 4);
@@ -845,13 +823,7 @@ static int gemm_rows_t(bool mfma, const T* A, const T* Wt, const float* bias, vo
   if constexpr (std::is_same<T, bf16>::value) {
     if (mfma) return mfma_gemm_dispatch(A, Wt, bias, C, M, N, K, epi, out_f32, s, (bf16*)vt, vt_n0, vt_ld);
   }
-  dim3 grid((N + 63) / 64, (M + 63) / 64);
-  if (epi == GE_RESID) gemm_simple_kernel<T, float, GE_RESID><<<grid, 256, 0, s>>>(A, Wt, bias, (float*)C, M, N, K);
-  else if (epi == GE_PLAIN) gemm_simple_kernel<T, float, GE_PLAIN><<<grid, 256, 0, s>>>(A, Wt, bias, (float*)C, M, N, K);
-  else if (epi == GE_BIAS && out_f32) gemm_simple_kernel<T, float, GE_BIAS><<<grid, 256, 0, s>>>(A, Wt, bias, (float*)C, M, N, K);
-  else if (epi == GE_RELU && out_f32) gemm_simple_kernel<T, float, GE_RELU><<<grid, 256, 0, s>>>(A, Wt, bias, (float*)C, M, N, K);
-  else if (epi == GE_BIAS) gemm_simple_kernel<T, T, GE_BIAS><<<grid, 256, 0, s>>>(A, Wt, bias, (T*)C, M, N, K);
-  else gemm_simple_kernel<T, T, GE_RELU><<<grid, 256, 0, s>>>(A, Wt, bias, (T*)C, M, N, K);
+  gemm_simple_launch(A, Wt, bias, C, M, N, K, epi, out_f32, s);
   return VX_OK;
 }
 
@@ -984,20 +956,17 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
   const bool mx = mx_on(e, ada_stage, M, d);
   const bool tg = time_gemms() && ada_stage >= 0;  // NAR stages only
   const size_t sstride = (size_t)M * d;
-  // VX_SPLIT_D / VX_SPLIT_FF (A/B runs): K slices of the out-projection / FFN2 (1 = no slabs, residual add in the GEMM epilogue)
-  static const int env_sp_d = getenv("VX_SPLIT_D") ? atoi(getenv("VX_SPLIT_D")) : 0;
-  static const int env_sp_ff = getenv("VX_SPLIT_FF") ? atoi(getenv("VX_SPLIT_FF")) : 0;
-  auto pick = [](int env, int K, int dflt) { return (env == 1 || env == 2 || env == 4) && K % (64 * env) == 0 ? env : dflt; };
-  // default: the largest of 4 / 2 / 1 slices that keeps (128^2 tiles) x slices within one round of the chip's CUs - at 1025 rows
-  // 72 tiles x 4 slices were 288 workgroups, i.e. two rounds, and four slabs for the next LayerNorm to fold (A/B on one box:
-  // NAR 7 stages 9.38 ms with 4 / 4 slices, 8.97 ms with 2 / 2; the 272-row prefill is fastest with 4 / 4: 0.91 vs 0.99 ms)
+  // K slices of the out-projection / FFN2 (1 = no slabs, residual add in the GEMM epilogue): the largest of 4 / 2 / 1 that keeps
+  // (128^2 tiles) x slices within one round of the chip's CUs - at 1025 rows 72 tiles x 4 slices were 288 workgroups, i.e. two
+  // rounds, and four slabs for the next LayerNorm to fold (A/B on one box: NAR 7 stages 9.38 ms with 4 / 4 slices, 8.97 ms with
+  // 2 / 2; the 272-row prefill is fastest with 4 / 4: 0.91 vs 0.99 ms)
   auto fit = [&](int K) {
     const long long tiles = (long long)((M + 127) / 128) * (d / 128);
     for (int sp = split_for(K); sp > 1; sp >>= 1)
       if (tiles * sp <= e->num_cu) return sp;
     return 1;
   };
-  const int sp_d = pick(env_sp_d, d, fit(d)), sp_ff = pick(env_sp_ff, 4 * d, fit(4 * d));
+  const int sp_d = fit(d), sp_ff = fit(4 * d);
   Fold pend;  // FFN2 slabs of the previous layer, folded by the next norm (pre-norm) or by the trailing fold pass
   for (size_t li = 0; li < layers.size(); ++li) {
     const LayerW& l = layers[li];
@@ -1196,7 +1165,6 @@ static int enqueue_head(vx_engine* e, hipStream_t s, const float* x = nullptr, f
   a.pro = (post && prefilled) ? PRO_COPY : PRO_LN; a.epi = EPI_LOGITS;
   a.st = st ? st : e->d_st;
   a.kid = (!prefilled && st == nullptr) ? 61 : -1;  // the decode step's head (probe builds)
-  a.nt = (pfW != nullptr && getenv("VX_AR_NT")) ? atoi(getenv("VX_AR_NT")) : 0;
   if (pfW) gemv_prefetch(a, pfW, pfN, pfK, e->bf16, e->num_cu);  // decode step: the next token's first GEMVs
   return launch_gemv(e->bf16, a, e->num_cu, s);
 }
@@ -1478,7 +1446,6 @@ static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
   // L2 / Infinity-Cache warm-up (GemvArgs.pf): GEMV i of the step also requests the weights of GEMV i + dist, in step order
   // [QKV_0, out_0, FFN1_0, FFN2_0, QKV_1, ..., FFN2_{L-1}, head] and wrapping into the next token's step.
   static const int pf_dist = getenv("VX_AR_PREFETCH") ? atoi(getenv("VX_AR_PREFETCH")) : 2;
-  static const int ar_nt = getenv("VX_AR_NT") ? atoi(getenv("VX_AR_NT")) : 0;  // A/B switch: non-temporal weight loads
   struct PfW { const void* W; int N, K; };
   std::vector<PfW> seq;
   for (int li = 0; li < c.num_layers; ++li) {
@@ -1509,7 +1476,7 @@ static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
       else { a.gamma = e->ar_l[li - 1].n2_g; a.beta = e->ar_l[li - 1].n2_b; a.xnorm_out = e->ar_xn; res = e->ar_xn; }
     }
     warm(a, 4 * li);
-    a.nt = ar_nt; a.kid = 1 + 5 * li;
+    a.kid = 1 + 5 * li;
     VXC(launch_gemv(e->bf16, a, e->num_cu, s));
 #define AD(HDV)                                                                                                                                              \
   if (hd == HDV) {                                                                                                                                           \
@@ -1528,7 +1495,7 @@ static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
     o.W = l.out_w; o.bias = l.out_b; o.part = e->ar_part; o.y = e->ar_x; o.N = d; o.K = d; o.pro = PRO_ATTN; o.epi = EPI_RESID;
     o.res = res;
     warm(o, 4 * li + 1);
-    o.nt = ar_nt; o.kid = 3 + 5 * li;
+    o.kid = 3 + 5 * li;
     VXC(launch_gemv(e->bf16, o, e->num_cu, s));
     // f = relu(linear1(LN2(x)))
     GemvArgs f{};
@@ -1537,7 +1504,7 @@ static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
     f.N = 4 * d; f.K = d; f.pro = PRO_LN; f.epi = EPI_RELU;
     if (post) { f.gamma = l.n1_g; f.beta = l.n1_b; f.xnorm_out = e->ar_xn; }  // x = norm1(x + sa(x)), kept in ar_xn
     warm(f, 4 * li + 2);
-    f.nt = ar_nt; f.kid = 4 + 5 * li;
+    f.kid = 4 + 5 * li;
     VXC(launch_gemv(e->bf16, f, e->num_cu, s));
     // x += linear2(f)
     GemvArgs g{};
@@ -1545,7 +1512,7 @@ static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
     g.W = l.w2; g.bias = l.b2; g.x = e->ar_f; g.y = e->ar_x; g.N = d; g.K = 4 * d; g.pro = PRO_COPY; g.epi = EPI_RESID;
     if (post) g.res = e->ar_xn;  // raw sum norm1(..) + ff(..); its norm2 runs in the next layer's (or the head's) prologue
     warm(g, 4 * li + 3);
-    g.nt = ar_nt; g.kid = 5 + 5 * li;
+    g.kid = 5 + 5 * li;
     VXC(launch_gemv(e->bf16, g, e->num_cu, s));
   }
   if (pf_dist > 0) {
@@ -1840,24 +1807,14 @@ extern "C" int vx_ar_result(vx_engine* e, int64_t* tokens, int32_t capacity, int
 template <int EPI, int NH, bool KV8> static int launch_bgemm_h(const BgemmArgs& a, int ns, int grid, hipStream_t s) {
   if (a.N > 65535 || a.K > 65535) return fail(VX_ERR_UNSUPPORTED, "bgemm: N=%d K=%d", a.N, a.K);  // (N << 16) | K travels as one argument
   const unsigned nk = ((unsigned)a.N << 16) | (unsigned)a.K;
-#define BG(NSV)                                                                                              \
-  if (ns == NSV) {                                                                                           \
-    if (a.pf != nullptr) bgemm_kernel<EPI, NSV, NH, true, KV8><<<grid, 256, 0, s>>>(a.A, a.W, nk, a.kgroups, a); \
-    else bgemm_kernel<EPI, NSV, NH, false, KV8><<<grid, 256, 0, s>>>(a.A, a.W, nk, a.kgroups, a);                \
-    return VX_OK;                                                                                            \
+#define BG(NSV)                                                                       \
+  if (ns == NSV) {                                                                    \
+    bgemm_kernel<EPI, NSV, NH, KV8><<<grid, 256, 0, s>>>(a.A, a.W, nk, a.kgroups, a); \
+    return VX_OK;                                                                     \
   }
   BG(1) BG(2) BG(4) BG(8)
 #undef BG
   return fail(VX_ERR_UNSUPPORTED, "bgemm: %d steps per wave", ns);
-}
-// Points `a` at the weights of a later GEMM of the batched step (BgemmArgs.pf): an even share per workgroup, 32 KB at most.
-static void bgemm_prefetch(BgemmArgs& a, const void* Wn, int Nn, int Kn) {
-  const size_t total = (size_t)Nn * Kn * 2;
-  const int grid = ((a.N + 15) / 16) * a.kgroups;
-  if (Wn == nullptr || total >= (1ull << 32) || total < 16 || grid <= 0) return;
-  size_t slice = ((total + grid - 1) / grid + 15) & ~(size_t)15;
-  if (slice > 32768) slice = 32768;
-  a.pf = Wn; a.pf_slice = (unsigned)slice; a.pf_total = (unsigned)total;
 }
 // KV8 (BE_QKV only): write the fp8 slot caches a.kv8 / a.kv8s
 template <int EPI, bool KV8> static int launch_bgemm(const BgemmArgs& a, hipStream_t s) {
@@ -1891,26 +1848,9 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd;  // elements
   const float scale = 1.0f / sqrtf((float)hd);
   const int kg_d = kgroups_for(d), kg_ff = kgroups_for(4 * d);
-  // cache warm-up as in the batch-1 step: GEMM i of the step also requests the weights of GEMM i + dist, in step order
-  // [QKV_0, out_0, FFN1_0, FFN2_0, QKV_1, ..., FFN2_{L-1}, head], wrapping into the next step.  OFF by default
-  // (VX_BATCH_PREFETCH=<dist> turns it on): at 32 slots it measured 528-531 us per step against 524-526 without
-  // (profiles/r02_ab_batch_prefetch.log) - between two GEMMs of the batched step sit an attention kernel that streams 87 MB of
-  // K / V and the LayerNorm, and the memory system is not idle as in the batch-1 step.
-  static const int pf_dist = getenv("VX_BATCH_PREFETCH") ? atoi(getenv("VX_BATCH_PREFETCH")) : 0;
-  // keys per lane and register set of the fp8-cache attention (VX_KV8_UNR=2: A/B runs; anything else: 4)
-  static const int kv8_unr = getenv("VX_KV8_UNR") ? atoi(getenv("VX_KV8_UNR")) : 4;
-  struct PfW { const void* W; int N, K; };
-  std::vector<PfW> seq;
-  for (int li = 0; li < L; ++li) {
-    const LayerW& l = e->ar_l[li];
-    seq.push_back({l.in_w, 3 * d, d}); seq.push_back({l.out_w, d, d}); seq.push_back({l.w1, 4 * d, d}); seq.push_back({l.w2, d, 4 * d});
-  }
-  seq.push_back({W<void>(e, "ar_predict_layer.weight"), AR_VOCAB, d});
-  auto warm = [&](BgemmArgs& g, int idx) {
-    if (pf_dist <= 0) return;
-    const PfW& n = seq[(idx + pf_dist) % seq.size()];
-    bgemm_prefetch(g, n.W, n.N, n.K);
-  };
+  // no warm-up of a later GEMM's weights as in the batch-1 step: at 32 slots it measured 528-531 us per step against 524-526
+  // without (profiles/r02_ab_batch_prefetch.log) - between two GEMMs of the batched step sit an attention kernel that streams
+  // 87 MB of K / V and the LayerNorm, and the memory system is not idle as in the batch-1 step.
   for (int li = 0; li < L; ++li) {
     const LayerW& l = e->ar_l[li];
     // LN1 (+ the FFN2 partial sums of the previous layer)
@@ -1920,16 +1860,11 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
     a.st = e->bst; a.B = B; a.d = d; a.hd = hd; a.ctx_max = e->ctx_max;
     a.A = e->bh; a.W = (const bf16*)l.in_w; a.bias = l.in_b; a.N = 3 * d; a.K = d; a.kgroups = 1;
     a.q = e->bq; a.kv_slot_stride = e->bkv_slot; a.kv_v_offset = kv_layer / 2;
-    warm(a, 4 * li);
     if (e->kv8) {
       a.kv8 = e->bkv8 + (size_t)li * kv_layer; a.kv8s = e->bkv8s + (size_t)li * kv_layer / 16;
       VXC((launch_bgemm<BE_QKV, true>(a, s)));
-      if (kv8_unr == 2)
-        attn_batch8_kernel<64, 2><<<dim3(H, B), 256, 0, s>>>(e->bq, a.kv8, a.kv8s, e->bkv_slot, kv_layer / 2, e->bst, e->ctx_max, d,
-                                                             scale, e->batt);
-      else
-        attn_batch8_kernel<64, 4><<<dim3(H, B), 256, 0, s>>>(e->bq, a.kv8, a.kv8s, e->bkv_slot, kv_layer / 2, e->bst, e->ctx_max, d,
-                                                             scale, e->batt);
+      attn_batch8_kernel<64><<<dim3(H, B), 256, 0, s>>>(e->bq, a.kv8, a.kv8s, e->bkv_slot, kv_layer / 2, e->bst, e->ctx_max, d,
+                                                        scale, e->batt);
     } else {
       a.kv = e->bkv + (size_t)li * kv_layer;
       VXC(launch_bgemm<BE_QKV>(a, s));
@@ -1939,18 +1874,15 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
     BgemmArgs o{};
     o.st = e->bst; o.B = B;
     o.A = e->batt; o.W = (const bf16*)l.out_w; o.N = d; o.K = d; o.kgroups = kg_d; o.part = e->bpart;
-    warm(o, 4 * li + 1);
     VXC(launch_bgemm<BE_PARTIAL>(o, s));
     launch_ln_batch(e->bx, e->bpart, kg_d, l.out_b, l.n2_g, l.n2_b, e->bh, B, d, s);
     BgemmArgs f{};
     f.st = e->bst; f.B = B;
     f.A = e->bh; f.W = (const bf16*)l.w1; f.bias = l.b1; f.N = 4 * d; f.K = d; f.kgroups = 1; f.f = e->bff;
-    warm(f, 4 * li + 2);
     VXC(launch_bgemm<BE_RELU>(f, s));
     BgemmArgs g{};
     g.st = e->bst; g.B = B;
     g.A = e->bff; g.W = (const bf16*)l.w2; g.N = d; g.K = 4 * d; g.kgroups = kg_ff; g.part = e->bpart;
-    warm(g, 4 * li + 3);
     VXC(launch_bgemm<BE_PARTIAL>(g, s));
   }
   launch_ln_batch(e->bx, e->bpart, kg_ff, e->ar_l[L - 1].b2, W<float>(e, "ar_decoder.norm.weight"),
@@ -1960,7 +1892,6 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
   hgm.A = e->bh; hgm.W = W<bf16>(e, "ar_predict_layer.weight"); hgm.N = AR_VOCAB; hgm.K = d; hgm.kgroups = 1;
   hgm.logits = e->blogits; hgm.logits_stride = LOGITS_CUR;
   hgm.trace = e->btrace; hgm.trace_rows = e->btok_stride;
-  warm(hgm, 4 * L);
   VXC(launch_bgemm<BE_LOGITS>(hgm, s));
   return VX_OK;
 }

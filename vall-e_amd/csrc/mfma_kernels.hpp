@@ -16,21 +16,19 @@ namespace vx {
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
-// 128x128x64 tile, 4 waves as 2(M) x 2(N), each wave 64x64 = 2x2 MFMA tiles of 32x32.
-// LDS: double-buffered [128 rows][64 bf16] images of A and W (128-byte rows), 16-byte chunks
-// XOR-swizzled by ((row >> 1) & 7) so the 16 rows a ds_read_b128 lane group touches fall on 16
-// distinct 16-byte slots of the 256-byte bank row (T2).  The lane groups of ds_read_b128 are NOT 16 consecutive
-// lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31}, ...): `row & 7` looks right on paper and measures 2-way
-// (SQ_LDS_BANK_CONFLICT = half of SQ_LDS_IDX_ACTIVE); tests/probes/lds_conflicts.py checks a swizzle against the groups.  Global->register->LDS staging with
-// the next tile's global loads issued before the current tile's MFMAs (T14 split).
-// RING = 64 / 32: the same tile and epilogues on the staging scheme of the 256^2 kernel below - operands go global -> LDS with
-// global_load_lds_dwordx4 (no staging registers, no ds_write) into a ring of FOUR stages of RING k (128 KB / 64 KB of LDS), the
-// fragments of stage s+1 are read while stage s is multiplied (two register sets), one counted-vmcnt wait + raw s_barrier per
-// stage.  At M ~ 1k rows a CU holds one workgroup = one wave per SIMD, so nothing but the wave's own instruction stream can overlap
-// the LDS phase with the matrix phase: the register-staged loop spends 0.65 us per 64 of k where the MFMAs alone need 0.21.
+// 128x128 tile, 4 waves as 2(M) x 2(N), each wave 64x64 = 2x2 MFMA tiles of 32x32.
+// Operands go global -> LDS with global_load_lds_dwordx4 (no staging registers, no ds_write) into a ring of FOUR stages of RING
+// k (RING = 64 / 32: 128 KB / 64 KB of LDS), the fragments of stage s+1 are read while stage s is multiplied (two register sets),
+// one counted-vmcnt wait + raw s_barrier per stage.  At M ~ 1k rows a CU holds one workgroup = one wave per SIMD, so nothing but
+// the wave's own instruction stream can overlap the LDS phase with the matrix phase: a register-staged loop spent 0.65 us per 64
+// of k where the MFMAs alone need 0.21.
+// RING = 64: 128-byte rows, 16-byte chunks XOR-swizzled by ((row >> 1) & 7) so the 16 rows a ds_read_b128 lane group touches
+// fall on 16 distinct 16-byte slots of the 256-byte bank row (T2).  The lane groups of ds_read_b128 are NOT 16 consecutive lanes
+// ({0-3,12-15,20-27}, {4-11,16-19,28-31}, ...): `row & 7` looks right on paper and measures 2-way (SQ_LDS_BANK_CONFLICT = half
+// of SQ_LDS_IDX_ACTIVE); tests/probes/lds_conflicts.py checks a swizzle against the groups.
 // RING = 32 keeps two workgroups per CU possible: grids of 288 workgroups (FFN1 and the split-K slices at 1025 rows) otherwise run
 // as two rounds on 256 CUs.  Its rows are 64 bytes: chunk position = chunk ^ ((0 - (row >> 2)) & 3) (as in the 256^2 kernel).
-template <int EPI, bool OUT_F32, int RING = 0>
+template <int EPI, bool OUT_F32, int RING>
 __global__ __launch_bounds__(256) void mfma_gemm_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W,
                                                         const float* __restrict__ bias, void* __restrict__ Cv, int M,
                                                         int N, int K, bf16* __restrict__ vt, int vt_n0, int vt_ld, int ld) {
@@ -40,28 +38,17 @@ __global__ __launch_bounds__(256) void mfma_gemm_kernel(const bf16* __restrict__
   // Which tile: launch slot lin = x + gx (y + gy z) runs on XCD lin % 8.  With gx % 8 == 0 (QKV, FFN1) an N tile's M tiles already
   // share an XCD.  The split-K launches of the N = d GEMMs (gx = 8, gz slices) put an N tile's slices AND all M tiles on one
   // XCD: per 64 of k it then pulls gy gz A tiles + gz W tiles over the fabric (FFN2 at 1025 rows: 20 tiles = 320 KB per XCD and
-  // step, 5.9 TB/s chip-wide at the measured 0.43 us per step).  VX_GEMM_XCD_Z (A/B): XCD x takes slice x % gz of the N tiles
-  // [(x / gz) gz, +gz) instead - gy A tiles + gz W tiles (11 tiles = 176 KB).  Speed only: a bijection of the grid.
-  int bxi = blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
-#ifdef VX_GEMM_XCD_Z
-  if (gridDim.z > 1 && gridDim.x == 8) {
-    const int gy = gridDim.y, gz = gridDim.z;
-    const int lin = blockIdx.x + 8 * (blockIdx.y + gy * blockIdx.z), xcd = lin & 7, idx = lin >> 3;  // idx < gy gz
-    bzi = xcd % gz;
-    bxi = (xcd / gz) * gz + idx / gy;
-    byi = idx % gy;
-  }
-#endif
-  A += (size_t)bzi * K;
-  W += (size_t)bzi * K;
-  if (OUT_F32) Cv = reinterpret_cast<float*>(Cv) + (size_t)bzi * M * N;
-  constexpr int BM = 128, BN = 128, BK = 64;
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  // layout: [buf][A|W][128 rows * 128 B]
+  // step, 5.9 TB/s chip-wide at the measured 0.43 us per step).
+  const int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+  A += (size_t)bz * K;
+  W += (size_t)bz * K;
+  if (OUT_F32) Cv = reinterpret_cast<float*>(Cv) + (size_t)bz * M * N;
+  constexpr int BM = 128, BN = 128;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];  // [stage][A|W][128 rows * RING * 2 B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 31, h = lane >> 5;
-  const int m0 = byi * BM, n0 = bxi * BN;
+  const int m0 = by * BM, n0 = bx * BN;
 
   f32x16_t acc[2][2];
 #pragma unroll
@@ -77,199 +64,114 @@ __global__ __launch_bounds__(256) void mfma_gemm_kernel(const bf16* __restrict__
     for (int j = 0; j < 2; ++j) bias_r[j] = bias[min(n0 + wn * 64 + j * 32 + r, N - 1)];
   }
 
-  if constexpr (RING != 0) {
-    constexpr int RK = RING;              // k per stage
-    constexpr int RB = RK * 2;            // bytes per row of a stage
-    constexpr int CPR = RB / 16;          // 16-byte chunks per row: 8 / 4
-    constexpr int KS = RK / 16;           // MFMA k-steps per stage: 4 / 2
-    constexpr int OPB = BM * RB;          // bytes per operand stage: 16 KB / 8 KB
-    constexpr int NI = OPB / 4096;        // LDS-DMA instructions per operand stage: 4 / 2
-    constexpr int ND = 2 * NI;            // ... per stage
-    auto swz = [](int row) { return RB == 128 ? ((row >> 1) & 7) : ((0 - (row >> 2)) & 3); };
-    const int nk = K / RK;
-    // slot q = tid + 256 i of an operand stage -> row q / CPR = row0 + (256 / CPR) i, position tid % CPR, which holds source chunk
-    // position ^ swz(row); swz has period 16 / 16 rows resp. and 256 / CPR is a multiple of it: the same chunk for every i
-    const int row0 = tid / CPR;
-    const int csrc = ((tid % CPR) ^ swz(row0)) * 8;  // elements
-    const bf16 *sA[NI], *sW[NI];
+  constexpr int RK = RING;              // k per stage
+  constexpr int RB = RK * 2;            // bytes per row of a stage
+  constexpr int CPR = RB / 16;          // 16-byte chunks per row: 8 / 4
+  constexpr int KS = RK / 16;           // MFMA k-steps per stage: 4 / 2
+  constexpr int OPB = BM * RB;          // bytes per operand stage: 16 KB / 8 KB
+  constexpr int NI = OPB / 4096;        // LDS-DMA instructions per operand stage: 4 / 2
+  constexpr int ND = 2 * NI;            // ... per stage
+  auto swz = [](int row) { return RB == 128 ? ((row >> 1) & 7) : ((0 - (row >> 2)) & 3); };
+  const int nk = K / RK;
+  // slot q = tid + 256 i of an operand stage -> row q / CPR = row0 + (256 / CPR) i, position tid % CPR, which holds source chunk
+  // position ^ swz(row); swz has period 16 / 16 rows resp. and 256 / CPR is a multiple of it: the same chunk for every i
+  const int row0 = tid / CPR;
+  const int csrc = ((tid % CPR) ^ swz(row0)) * 8;  // elements
+  const bf16 *sA[NI], *sW[NI];
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      sA[i] = A + (size_t)min(m0 + row0 + (256 / CPR) * i, M - 1) * ld + csrc;
-      sW[i] = W + (size_t)min(n0 + row0 + (256 / CPR) * i, N - 1) * ld + csrc;
-    }
-    const int dbase = (tid - lane) * 16;  // wave-uniform LDS byte offset of lane 0's slot (the DMA adds lane * 16)
-    auto stage = [&](int st) {
-      unsigned char* base = lds + (st & 3) * (2 * OPB);
-      const int k0 = st * RK;
+  for (int i = 0; i < NI; ++i) {
+    sA[i] = A + (size_t)min(m0 + row0 + (256 / CPR) * i, M - 1) * ld + csrc;
+    sW[i] = W + (size_t)min(n0 + row0 + (256 / CPR) * i, N - 1) * ld + csrc;
+  }
+  const int dbase = (tid - lane) * 16;  // wave-uniform LDS byte offset of lane 0's slot (the DMA adds lane * 16)
+  auto stage = [&](int st) {
+    unsigned char* base = lds + (st & 3) * (2 * OPB);
+    const int k0 = st * RK;
 #pragma unroll
-      for (int i = 0; i < NI; ++i)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sA[i] + k0),
-                                         (__attribute__((address_space(3))) void*)(base + dbase + 4096 * i), 16, 0, 0);
+    for (int i = 0; i < NI; ++i)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sA[i] + k0),
+                                       (__attribute__((address_space(3))) void*)(base + dbase + 4096 * i), 16, 0, 0);
 #pragma unroll
-      for (int i = 0; i < NI; ++i)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sW[i] + k0),
-                                         (__attribute__((address_space(3))) void*)(base + OPB + dbase + 4096 * i), 16, 0, 0);
-    };
-    bf16x8_t fa0[KS][2], fb0[KS][2], fa1[KS][2], fb1[KS][2];
-    auto lread = [&](int st, bf16x8_t (&fa)[KS][2], bf16x8_t (&fb)[KS][2]) {
-      const unsigned char* ba = lds + (st & 3) * (2 * OPB);
-      const unsigned char* bw = ba + OPB;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int row = wm * 64 + i * 32 + r;
-          fa[ks][i] = *reinterpret_cast<const bf16x8_t*>(ba + row * RB + (((ks * 2 + h) ^ swz(row)) << 4));
-          const int col = wn * 64 + i * 32 + r;
-          fb[ks][i] = *reinterpret_cast<const bf16x8_t*>(bw + col * RB + (((ks * 2 + h) ^ swz(col)) << 4));
-        }
-    };
-    auto mm = [&](const bf16x8_t (&fa)[KS][2], const bf16x8_t (&fb)[KS][2]) {
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks][i], fb[ks][j], acc[i][j], 0, 0, 0);
-    };
-    // Step on stage st (st + 3 < nk): [issue stage st+3 into the slot stage st-1 left two barriers ago] [read the fragments of
-    // stage st+1] [MFMAs of stage st] [counted vmcnt: stage st+2 landed, only stage st+3 may be in flight] [barrier]
-    auto steady = [&](int st, bf16x8_t (&fa)[KS][2], bf16x8_t (&fb)[KS][2], bf16x8_t (&na)[KS][2], bf16x8_t (&nb)[KS][2]) {
-      stage(st + 3);
-      lread(st + 1, na, nb);
-      mm(fa, fb);
-#pragma unroll
-      for (int i = 0; i < ND; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);  // VMEM (LDS-DMA)
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-      }
-#pragma unroll
-      for (int i = 0; i < 4 * KS - ND; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 4 * KS / (4 * KS - ND), 0);  // DS read
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      }
-      if (ND == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-    };
-    // the last three stages (and short K): nothing, or less, left to issue
-    auto tail = [&](int st, bf16x8_t (&fa)[KS][2], bf16x8_t (&fb)[KS][2], bf16x8_t (&na)[KS][2], bf16x8_t (&nb)[KS][2]) {
-      const bool more = st + 3 < nk;  // uniform
-      if (more) stage(st + 3);
-      if (st + 1 < nk) lread(st + 1, na, nb);
-      mm(fa, fb);
-      if (more && ND == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-      else if (more) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    };
-    VX_STAMP(0);
-    const int pre = nk < 3 ? nk : 3;
-    for (int st = 0; st < pre; ++st) stage(st);
-    VX_STAMP(1);
-    // stages 0 and 1 landed everywhere (older loads too)
-    if (pre == 3 && ND == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-    else if (pre == 3) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    lread(0, fa0, fb0);
-    VX_STAMP(2);
-    int st = 0;
-    for (; st + 4 < nk; st += 2) {
-      steady(st, fa0, fb0, fa1, fb1);
-      steady(st + 1, fa1, fb1, fa0, fb0);
-    }
-    VX_STAMP(3);
-    for (; st < nk; st += 2) {
-      tail(st, fa0, fb0, fa1, fb1);
-      if (st + 1 < nk) tail(st + 1, fa1, fb1, fa0, fb0);
-    }
-    VX_STAMP(4);
-    // the bias values were loaded at kernel entry; with the hand-counted waits above hipcc no longer knows that they have landed
-    // and put a vmcnt(0) in front of EVERY guarded store of the fp32 epilogue (64 serialised stores, 7 us): one use here, in the
-    // block that dominates the epilogue, settles it
-    asm volatile("" : "+v"(bias_r[0]), "+v"(bias_r[1]));
-  } else {
-  // staging: 1024 16-byte chunks per operand tile, 4 per thread; THREE register sets so that three
-  // K tiles of global loads are in flight while one is being multiplied (at M ~ 1k rows there is
-  // about one workgroup per CU, so nothing else hides the load latency: one tile ahead ran at
-  // ~20 GB/s per CU).  Tile t always lives in set t % 3; vmcnt retires in order, so the wait in
-  // front of each LDS store only covers that tile's loads.
-  uint4 ra[3][4], rw[3][4];
-  auto gload = [&](auto SET, int k0) {
-    constexpr int S = decltype(SET)::value;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = tid + i * 256, row = q >> 3, c = q & 7;
-      ra[S][i] = ld16(A + (size_t)min(m0 + row, M - 1) * ld + k0 + c * 8);
-      rw[S][i] = ld16(W + (size_t)min(n0 + row, N - 1) * ld + k0 + c * 8);
-    }
+    for (int i = 0; i < NI; ++i)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sW[i] + k0),
+                                       (__attribute__((address_space(3))) void*)(base + OPB + dbase + 4096 * i), 16, 0, 0);
   };
-  auto lstore = [&](auto SET, int buf) {
-    constexpr int S = decltype(SET)::value;
-    unsigned char* ba = lds + buf * 32768;
-    unsigned char* bw = ba + 16384;
+  bf16x8_t fa0[KS][2], fb0[KS][2], fa1[KS][2], fb1[KS][2];
+  auto lread = [&](int st, bf16x8_t (&fa)[KS][2], bf16x8_t (&fb)[KS][2]) {
+    const unsigned char* ba = lds + (st & 3) * (2 * OPB);
+    const unsigned char* bw = ba + OPB;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = tid + i * 256, row = q >> 3, c = q & 7;
-      const int off = row * 128 + ((c ^ ((row >> 1) & 7)) << 4);
-      *reinterpret_cast<uint4*>(ba + off) = ra[S][i];
-      *reinterpret_cast<uint4*>(bw + off) = rw[S][i];
-    }
-  };
-  auto compute = [&](int cur) {
-    const unsigned char* ba = lds + cur * 32768;
-    const unsigned char* bw = ba + 16384;
-    // all 16 fragment reads of the K tile first, then the 16 MFMAs behind counted lgkmcnt waits: with one wave per SIMD
-    // nothing else hides LDS latency, and read-4 / wait / multiply-4 per 16 of K exposed it four times per tile
-    bf16x8_t fa[4][2], fb[4][2];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
+    for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int row = wm * 64 + i * 32 + r;
-        fa[ks][i] = *reinterpret_cast<const bf16x8_t*>(ba + row * 128 + (((ks * 2 + h) ^ ((row >> 1) & 7)) << 4));
+        fa[ks][i] = *reinterpret_cast<const bf16x8_t*>(ba + row * RB + (((ks * 2 + h) ^ swz(row)) << 4));
         const int col = wn * 64 + i * 32 + r;
-        fb[ks][i] = *reinterpret_cast<const bf16x8_t*>(bw + col * 128 + (((ks * 2 + h) ^ ((col >> 1) & 7)) << 4));
+        fb[ks][i] = *reinterpret_cast<const bf16x8_t*>(bw + col * RB + (((ks * 2 + h) ^ swz(col)) << 4));
       }
-    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto mm = [&](const bf16x8_t (&fa)[KS][2], const bf16x8_t (&fb)[KS][2]) {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
+    for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks][i], fb[ks][j], acc[i][j], 0, 0, 0);
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  const int nk = K / BK;
-  // one pipeline step for tile t (set S = t % 3, next tile's set N = (t + 1) % 3)
-  auto step = [&](auto SET, auto NEXT, int t) {
-    // set S was freed by the LDS store at the end of step t-1.  UNCONDITIONAL (k clamped): a load under a
-    // branch makes hipcc's vmcnt bookkeeping conservative and the wait before the LDS store below
-    // degenerates to vmcnt(0), i.e. a one-tile pipeline.
-    gload(SET, min((t + 3) * BK, K - BK));
-    compute(t & 1);
-    if (t + 1 < nk) lstore(NEXT, (t + 1) & 1);
-    __syncthreads();
+  // Step on stage st (st + 3 < nk): [issue stage st+3 into the slot stage st-1 left two barriers ago] [read the fragments of
+  // stage st+1] [MFMAs of stage st] [counted vmcnt: stage st+2 landed, only stage st+3 may be in flight] [barrier]
+  auto steady = [&](int st, bf16x8_t (&fa)[KS][2], bf16x8_t (&fb)[KS][2], bf16x8_t (&na)[KS][2], bf16x8_t (&nb)[KS][2]) {
+    stage(st + 3);
+    lread(st + 1, na, nb);
+    mm(fa, fb);
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);  // VMEM (LDS-DMA)
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+    }
+#pragma unroll
+    for (int i = 0; i < 4 * KS - ND; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x100, 4 * KS / (4 * KS - ND), 0);  // DS read
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    }
+    if (ND == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
+  };
+  // the last three stages (and short K): nothing, or less, left to issue
+  auto tail = [&](int st, bf16x8_t (&fa)[KS][2], bf16x8_t (&fb)[KS][2], bf16x8_t (&na)[KS][2], bf16x8_t (&nb)[KS][2]) {
+    const bool more = st + 3 < nk;  // uniform
+    if (more) stage(st + 3);
+    if (st + 1 < nk) lread(st + 1, na, nb);
+    mm(fa, fb);
+    if (more && ND == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+    else if (more) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
   };
   VX_STAMP(0);
-  gload(I0{}, 0);
-  gload(I1{}, min(BK, K - BK));
-  gload(I2{}, min(2 * BK, K - BK));
+  const int pre = nk < 3 ? nk : 3;
+  for (int st = 0; st < pre; ++st) stage(st);
   VX_STAMP(1);
-  lstore(I0{}, 0);
-  __syncthreads();
+  // stages 0 and 1 landed everywhere (older loads too)
+  if (pre == 3 && ND == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+  else if (pre == 3) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  lread(0, fa0, fb0);
   VX_STAMP(2);
-  int kt = 0;
-  for (; kt + 3 <= nk; kt += 3) {
-    step(I0{}, I1{}, kt);
-    step(I1{}, I2{}, kt + 1);
-    step(I2{}, I0{}, kt + 2);
-    if (kt == 0) VX_STAMP(3);  // after the first three K tiles
+  int st = 0;
+  for (; st + 4 < nk; st += 2) {
+    steady(st, fa0, fb0, fa1, fb1);
+    steady(st + 1, fa1, fb1, fa0, fb0);
   }
-  if (kt < nk) step(I0{}, I1{}, kt);
-  if (kt + 1 < nk) step(I1{}, I2{}, kt + 1);
+  VX_STAMP(3);
+  for (; st < nk; st += 2) {
+    tail(st, fa0, fb0, fa1, fb1);
+    if (st + 1 < nk) tail(st + 1, fa1, fb1, fa0, fb0);
+  }
   VX_STAMP(4);
-  }
+  // the bias values were loaded at kernel entry; with the hand-counted waits above hipcc no longer knows that they have landed
+  // and put a vmcnt(0) in front of EVERY guarded store of the fp32 epilogue (64 serialised stores, 7 us): one use here, in front
+  // of the epilogue, settles it
+  asm volatile("" : "+v"(bias_r[0]), "+v"(bias_r[1]));
 
   // epilogue: C/D map of 32x32 MFMA: col = lane&31, row = (v&3) + 8*(v>>2) + 4*(lane>>5)
   if constexpr (!OUT_F32) {
@@ -702,7 +604,6 @@ __global__ __launch_bounds__(512) void mfma256_kernel(const bf16* __restrict__ A
 //  * A K-tile is four PHASES; phase p multiplies one quadrant of the wave's 128 x 64 output (16 MFMAs):
 //        p0: read A-sub0 (8 ds_read_b128), multiply A0 x B0       p1: read B-sub1 (4), A0 x B1
 //        p2: read A-sub1 (8), A1 x B0                               p3: read B-sub0 of the NEXT K-tile (4), A1 x B1
-//    (SCHED 0, kept for A/B: B-sub0 read with A-sub0 in p0, quadrants A0B0 A0B1 A1B1 A1B0, reads 12 / 4 / 8 / 0)
 //    Each phase = [fragment reads + ONE half-tile staged by LDS-DMA (2 loads per lane) + counted vmcnt] barrier [16 MFMAs at raised
 //    priority] barrier.  The two row groups (the two waves of every SIMD) run ONE BARRIER APART: while one multiplies, the other
 //    reads fragments and issues loads, so the matrix pipe and the LDS pipe of a SIMD are both busy all the time.
@@ -775,10 +676,7 @@ __global__ __launch_bounds__(256) void p8_tail_reduce_kernel(const float* __rest
   }
 }
 
-#ifndef VX_P8_SCHED
-#define VX_P8_SCHED 1
-#endif
-template <int EPI, bool OUT_F32, int SCHED = VX_P8_SCHED, bool TAIL = false>
+template <int EPI, bool OUT_F32, bool TAIL = false>
 __global__ __launch_bounds__(512) void mfma256p_kernel(const bf16* __restrict__ A, const bf16* __restrict__ W,
                                                        const float* __restrict__ bias, void* __restrict__ Cv, int M, int N,
                                                        int K, bf16* __restrict__ vt, int vt_n0, int vt_ld, int ntn,
@@ -838,9 +736,8 @@ __global__ __launch_bounds__(512) void mfma256p_kernel(const bf16* __restrict__ 
     l_n0 = (tile - mt * ntn) * 256;
     l_kt = kt0;
   };
-  // SCHED 0: kind 0: A-h0, 1: B-h0, 2: B-h1, 3: A-h1; SCHED 1: kind 0: B-h0, 1: A-h0, 2: B-h1, 3: A-h1 of the stream's current
-  // K-tile (the order of first use); kind 0 opens the next K-tile
-  constexpr int KA0 = SCHED == 0 ? 0 : 1, KB0 = SCHED == 0 ? 1 : 0, KB1 = 2, KA1 = 3;
+  // kind 0: B-h0, 1: A-h0, 2: B-h1, 3: A-h1 of the stream's current K-tile (the order of first use); kind 0 opens the next K-tile
+  constexpr int KA0 = 1, KB0 = 0, KB1 = 2, KA1 = 3;
   auto stage = [&](auto kindc, auto bufc) {
     constexpr int kind = decltype(kindc)::value, buf = decltype(bufc)::value;
     constexpr bool isA = kind == KA0 || kind == KA1;
@@ -913,21 +810,12 @@ __global__ __launch_bounds__(512) void mfma256p_kernel(const bf16* __restrict__ 
     using SK = std::integral_constant<int, (x + 2) & 3>;
     using SB = std::integral_constant<int, ((x + 6) >> 2) & 1>;
     using NB = std::integral_constant<int, ((x >> 2) & 1) ^ 1>;
-    if (SCHED == 0) {  // fragment reads per phase 12 / 4 / 8 / 0; quadrants A0B0, A0B1, A1B1, A1B0
-      if (p == 0) {
-        read_b(CB{}, I0{}, fb0);
-        read_a(CB{}, I0{});
-      } else if (p == 1) {
-        read_b(CB{}, I1{}, fb1);
-      } else if (p == 2) {
-        read_a(CB{}, I1{});
-      }
-    } else {  // 8 / 4 / 8 / 4: quadrants A0B0, A0B1, A1B0, A1B1, the last phase reads the NEXT K-tile's B-sub0 (B0 is dead by then)
-      if (p == 0) read_a(CB{}, I0{});
-      else if (p == 1) read_b(CB{}, I1{}, fb1);
-      else if (p == 2) read_a(CB{}, I1{});
-      else read_b(NB{}, I0{}, fb0);
-    }
+    // fragment reads per phase 8 / 4 / 8 / 4: quadrants A0B0, A0B1, A1B0, A1B1, the last phase reads the NEXT K-tile's B-sub0 (B0
+    // is dead by then)
+    if (p == 0) read_a(CB{}, I0{});
+    else if (p == 1) read_b(CB{}, I1{}, fb1);
+    else if (p == 2) read_a(CB{}, I1{});
+    else read_b(NB{}, I0{}, fb0);
     stage(SK{}, SB{});
     if (lax) {  // 8 operand loads + 32 stores (+ the bias load)
       if (EPI != GE_PLAIN) asm volatile("s_waitcnt vmcnt(41)\n\ts_barrier" ::: "memory");
@@ -940,8 +828,8 @@ __global__ __launch_bounds__(512) void mfma256p_kernel(const bf16* __restrict__ 
     __builtin_amdgcn_s_setprio(1);
     if (p == 0) mm(I0{}, I0{}, fb0);
     else if (p == 1) mm(I0{}, I2{}, fb1);
-    else if (p == 2) { if (SCHED == 0) mm(I4{}, I2{}, fb1); else mm(I4{}, I0{}, fb0); }
-    else { if (SCHED == 0) mm(I4{}, I0{}, fb0); else mm(I4{}, I2{}, fb1); }
+    else if (p == 2) mm(I4{}, I0{}, fb0);
+    else mm(I4{}, I2{}, fb1);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_barrier" ::: "memory");
@@ -966,7 +854,7 @@ __global__ __launch_bounds__(512) void mfma256p_kernel(const bf16* __restrict__ 
   stage(I0{}, I1{});
   stage(I1{}, I1{});
   asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-  if (SCHED == 1) read_b(I0{}, I0{}, fb0);  // event 0: B-sub0 of the first K-tile (every later one is read in the phase before its K-tile)
+  read_b(I0{}, I0{}, fb0);  // event 0: B-sub0 of the first K-tile (every later one is read in the phase before its K-tile)
   if (wr == 1) asm volatile("s_barrier" ::: "memory");  // the second row group runs one barrier behind the first from here on
   __builtin_amdgcn_sched_barrier(0);
 
@@ -1101,15 +989,9 @@ __global__ __launch_bounds__(512) void mfma256p_kernel(const bf16* __restrict__ 
   if (wr == 0) asm volatile("s_barrier" ::: "memory");  // every wave has passed the same number of barriers
 }
 
-// Main loop of the 128^2 kernel for a grid of `wgs` workgroups: the LDS-DMA ring with 64-k stages (128 KB of LDS, one workgroup
-// per CU) when the grid fits one round, the 32-k ring (64 KB, two per CU) otherwise.  VX_GEMM_RING = 0 / 32 / 64 forces the
-// register-staged loop / one ring for A/B runs.
-static inline int gemm_ring128(long long wgs) {
-  static const int forced = [] { const char* v = getenv("VX_GEMM_RING"); return (v && *v >= '0' && *v <= '9') ? atoi(v) : -1; }();
-  if (forced == 0 || forced == 32 || forced == 64) return forced;
-  const int ncu = vx_cu_count();
-  return wgs <= ncu ? 64 : 32;
-}
+// LDS-DMA ring of the 128^2 kernel for a grid of `wgs` workgroups: 64-k stages (128 KB of LDS, one workgroup per CU) when the
+// grid fits one round, 32-k stages (64 KB, two per CU) otherwise.
+static inline int gemm_ring128(long long wgs) { return wgs <= vx_cu_count() ? 64 : 32; }
 
 // Tail split of the persistent 8-phase GEMM (VX_GEMM_TAIL=1; OFF by default, see below): when the last round of 256^2 tiles would
 // occupy few of the workgroups (544 tiles on 256 CUs: two full rounds, then 32 tiles at the price of a third), those tiles are split
@@ -1148,115 +1030,82 @@ static inline P8Tail p8_tail_plan(int ntiles, int grid, int K, hipStream_t s) {
 static inline int mfma_gemm_dispatch(const bf16* A, const bf16* W, const float* bias, void* C, int M, int N, int K,
                                      int epi, bool out_f32, hipStream_t s, bf16* vt = nullptr, int vt_n0 = 0,
                                      int vt_ld = 0) {
-  if (K % 64 != 0 || N % 64 != 0) {
-    // shapes outside the tiling: scalar-FMA fallback
-    dim3 g((N + 63) / 64, (M + 63) / 64);
-    if (epi == GE_RESID) gemm_simple_kernel<bf16, float, GE_RESID><<<g, 256, 0, s>>>(A, W, bias, (float*)C, M, N, K);
-    else if (epi == GE_PLAIN) gemm_simple_kernel<bf16, float, GE_PLAIN><<<g, 256, 0, s>>>(A, W, bias, (float*)C, M, N, K);
-    else if (epi == GE_BIAS && out_f32) gemm_simple_kernel<bf16, float, GE_BIAS><<<g, 256, 0, s>>>(A, W, bias, (float*)C, M, N, K);
-    else if (epi == GE_RELU && out_f32) gemm_simple_kernel<bf16, float, GE_RELU><<<g, 256, 0, s>>>(A, W, bias, (float*)C, M, N, K);
-    else if (epi == GE_BIAS) gemm_simple_kernel<bf16, bf16, GE_BIAS><<<g, 256, 0, s>>>(A, W, bias, (bf16*)C, M, N, K);
-    else gemm_simple_kernel<bf16, bf16, GE_RELU><<<g, 256, 0, s>>>(A, W, bias, (bf16*)C, M, N, K);
+  if (K % 64 != 0 || N % 64 != 0) {  // shapes outside the tiling
+    gemm_simple_launch(A, W, bias, C, M, N, K, epi, out_f32, s);
     return 0;
   }
-  // alg 0 (default): 128x128 shared tiles when there are enough of them, wave tiles + in-kernel split-K otherwise;
-  // 1 / 2 force one or the other (A/B runs)
-  static const int alg = [] { const char* v = getenv("VX_GEMM_ALG"); return v ? atoi(v) : 0; }();
   const long long tiles64 = (long long)((M + 63) / 64) * (N / 64);
-  if ((alg == 3 || (alg == 0 && M >= 4096)) && N % 256 == 0 && K >= 128) {  // K % 64 == 0 checked above  // enough 256^2 tiles for several per CU
-    const int ntn = N / 256, ntm = (M + 255) / 256;
+  if (M >= 4096 && N % 256 == 0 && K >= 128) {  // enough 256^2 tiles for several per CU
+    const int ntn = N / 256, ntm = (M + 255) / 256, nt_all = ntn * ntm;
     const int ncu = vx_cu_count();
-    const int grid256 = ntn * ntm < ncu ? ntn * ntm : ncu;  // one persistent workgroup per CU (128 KB of LDS each)
+    const int grid256 = nt_all < ncu ? nt_all : ncu;  // one persistent workgroup per CU (128 KB of LDS each)
     // the 8-phase schedule needs whole pairs of 64-k tiles and 32-bit byte offsets into A and W; any other K or size runs the
     // 32-k ring (mfma256_kernel)
     const bool p8 = K % 128 == 0 && (size_t)M * K * 2 < 0xFFFF0000ull && (size_t)N * K * 2 < 0xFFFF0000ull;
-    const P8Tail tl = p8 ? p8_tail_plan(ntn * ntm, grid256, K, s) : P8Tail{nullptr, 0};  // all forms; in this model only the K = 4096 one (FFN2) ever splits
-#define M2(E, F)                                                                                                         \
-  do {                                                                                                                  \
-    static bool attr_dev[16] = {}; bool& attr_done = attr_dev[vx_cur_device()];                                                                                      \
-    if (!attr_done) {                                                                                                   \
-      (void)hipFuncSetAttribute((const void*)mfma256_kernel<E, F>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);  \
-      (void)hipFuncSetAttribute((const void*)mfma256p_kernel<E, F>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 2048); \
-      (void)hipFuncSetAttribute((const void*)mfma256p_kernel<E, F, VX_P8_SCHED, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 2048); \
-      attr_done = true;                                                                                                 \
-    }                                                                                                                   \
-    if (p8 && tl.split > 1) {                                                                                     \
-      const int nt_all = ntn * ntm, rem_t = nt_all % grid256;                                                           \
-      mfma256p_kernel<E, F, VX_P8_SCHED, true><<<grid256, 512, 131072 + 2048, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, ntn, nt_all, tl); \
-      p8_tail_reduce_kernel<E, F><<<dim3(rem_t, 16), 256, 0, s>>>(tl.ws, tl.split, nt_all - rem_t, ntn, nt_all, bias, C, M, N, vt, vt_n0, vt_ld); \
-    } else if (p8) {                                                                                                     \
-      mfma256p_kernel<E, F><<<grid256, 512, 131072 + 2048, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, ntn, ntn * ntm, tl); \
-    } else {                                                                                                             \
-      mfma256_kernel<E, F><<<grid256, 512, 131072, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, ntn, ntn * ntm);        \
-    }                                                                                                                   \
-  } while (0)
-    if (N % 256 == 0) {
-      if (epi == GE_RESID) M2(GE_RESID, true);
-      else if (epi == GE_PLAIN) M2(GE_PLAIN, true);
-      else if (epi == GE_BIAS && out_f32) M2(GE_BIAS, true);
-      else if (epi == GE_RELU && out_f32) M2(GE_RELU, true);
-      else if (epi == GE_BIAS) M2(GE_BIAS, false);
-      else M2(GE_RELU, false);
-      return 0;
-    }
-#undef M2
-  }
-  if (alg == 1 || (alg == 0 && N % 128 == 0 && tiles64 >= 512)) {
-    dim3 grid((N + 127) / 128, (M + 127) / 128);
-#define MG(E, F)                                                                                                        \
-  do {                                                                                                                  \
-    static bool attr_dev[16] = {}; bool& attr_done = attr_dev[vx_cur_device()];                                                                                      \
-    if (!attr_done) {                                                                                                   \
-      (void)hipFuncSetAttribute((const void*)mfma_gemm_kernel<E, F>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
-      (void)hipFuncSetAttribute((const void*)mfma_gemm_kernel<E, F, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072); \
-      (void)hipFuncSetAttribute((const void*)mfma_gemm_kernel<E, F, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
-      attr_done = true;                                                                                                 \
-    }                                                                                                                   \
-    const int ring = gemm_ring128((long long)grid.x * grid.y);                                                          \
-    if (ring == 64) mfma_gemm_kernel<E, F, 64><<<grid, 256, 131072, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, K);   \
-    else if (ring == 32) mfma_gemm_kernel<E, F, 32><<<grid, 256, 65536, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, K); \
-    else mfma_gemm_kernel<E, F><<<grid, 256, 65536, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, K);                  \
-  } while (0)
-    if (epi == GE_RESID) MG(GE_RESID, true);
-    else if (epi == GE_PLAIN) MG(GE_PLAIN, true);
-    else if (epi == GE_BIAS && out_f32) MG(GE_BIAS, true);
-    else if (epi == GE_RELU && out_f32) MG(GE_RELU, true);
-    else if (epi == GE_BIAS) MG(GE_BIAS, false);
-    else MG(GE_RELU, false);
-#undef MG
+    const P8Tail tl = p8 ? p8_tail_plan(nt_all, grid256, K, s) : P8Tail{nullptr, 0};  // all forms; in this model only the K = 4096 one (FFN2) ever splits
+    gemm_epi_dispatch(epi, out_f32, [&](auto E, auto F) {
+      constexpr int EPI = decltype(E)::value;
+      constexpr bool OUT_F32 = decltype(F)::value;
+      static bool attr_dev[16] = {};
+      bool& attr_done = attr_dev[vx_cur_device()];
+      if (!attr_done) {
+        (void)hipFuncSetAttribute((const void*)mfma256_kernel<EPI, OUT_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+        (void)hipFuncSetAttribute((const void*)mfma256p_kernel<EPI, OUT_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 2048);
+        (void)hipFuncSetAttribute((const void*)mfma256p_kernel<EPI, OUT_F32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072 + 2048);
+        attr_done = true;
+      }
+      if (p8 && tl.split > 1) {
+        const int rem_t = nt_all % grid256;
+        mfma256p_kernel<EPI, OUT_F32, true><<<grid256, 512, 131072 + 2048, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, ntn, nt_all, tl);
+        p8_tail_reduce_kernel<EPI, OUT_F32><<<dim3(rem_t, 16), 256, 0, s>>>(tl.ws, tl.split, nt_all - rem_t, ntn, nt_all, bias, C, M, N, vt, vt_n0, vt_ld);
+      } else if (p8) {
+        mfma256p_kernel<EPI, OUT_F32><<<grid256, 512, 131072 + 2048, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, ntn, nt_all, tl);
+      } else {
+        mfma256_kernel<EPI, OUT_F32><<<grid256, 512, 131072, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, ntn, nt_all);
+      }
+    });
     return 0;
   }
+  if (N % 128 == 0 && tiles64 >= 512) {
+    const dim3 grid(N / 128, (M + 127) / 128);
+    const int ring = gemm_ring128((long long)grid.x * grid.y);
+    gemm_epi_dispatch(epi, out_f32, [&](auto E, auto F) {
+      constexpr int EPI = decltype(E)::value;
+      constexpr bool OUT_F32 = decltype(F)::value;
+      static bool attr_dev[16] = {};
+      bool& attr_done = attr_dev[vx_cur_device()];
+      if (!attr_done) {
+        (void)hipFuncSetAttribute((const void*)mfma_gemm_kernel<EPI, OUT_F32, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+        (void)hipFuncSetAttribute((const void*)mfma_gemm_kernel<EPI, OUT_F32, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+        attr_done = true;
+      }
+      if (ring == 64) mfma_gemm_kernel<EPI, OUT_F32, 64><<<grid, 256, 131072, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, K);
+      else mfma_gemm_kernel<EPI, OUT_F32, 32><<<grid, 256, 65536, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, K);
+    });
+    return 0;
+  }
+  // wave tiles; split K inside the workgroup when the tile grid alone cannot fill 4 waves on each of the 256 CUs
   const int mtiles = (M + 63) / 64;
   const size_t lds = 131072;
-#define WG(E, F, S)                                                                                                     \
-  do {                                                                                                                  \
-    static bool attr_dev[16] = {}; bool& attr_done = attr_dev[vx_cur_device()];                                                                                      \
-    if (!attr_done) {                                                                                                   \
-      (void)hipFuncSetAttribute((const void*)wgemm_kernel<E, F, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      attr_done = true;                                                                                                 \
-    }                                                                                                                   \
-    const int ngr = (S == 1) ? (N + 255) / 256 : N / 64;                                                                \
-    const int ngp = (ngr + 7) / 8 * 8;                                                                                  \
-    wgemm_kernel<E, F, S><<<mtiles * ngp, 256, lds, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, ngr, ngp);             \
-  } while (0)
-  // split K inside the workgroup when the tile grid alone cannot fill 4 waves on each of the 256 CUs
   const bool split = (K % 256 == 0) && tiles64 < 512;
-  if (split) {
-    if (epi == GE_RESID) WG(GE_RESID, true, 4);
-    else if (epi == GE_PLAIN) WG(GE_PLAIN, true, 4);
-    else if (epi == GE_BIAS && out_f32) WG(GE_BIAS, true, 4);
-    else if (epi == GE_RELU && out_f32) WG(GE_RELU, true, 4);
-    else if (epi == GE_BIAS) WG(GE_BIAS, false, 4);
-    else WG(GE_RELU, false, 4);
-  } else {
-    if (epi == GE_RESID) WG(GE_RESID, true, 1);
-    else if (epi == GE_PLAIN) WG(GE_PLAIN, true, 1);
-    else if (epi == GE_BIAS && out_f32) WG(GE_BIAS, true, 1);
-    else if (epi == GE_RELU && out_f32) WG(GE_RELU, true, 1);
-    else if (epi == GE_BIAS) WG(GE_BIAS, false, 1);
-    else WG(GE_RELU, false, 1);
-  }
-#undef WG
+  gemm_epi_dispatch(epi, out_f32, [&](auto E, auto F) {
+    constexpr int EPI = decltype(E)::value;
+    constexpr bool OUT_F32 = decltype(F)::value;
+    auto launch = [&](auto SPLITK) {
+      constexpr int S = decltype(SPLITK)::value;
+      static bool attr_dev[16] = {};
+      bool& attr_done = attr_dev[vx_cur_device()];
+      if (!attr_done) {
+        (void)hipFuncSetAttribute((const void*)wgemm_kernel<EPI, OUT_F32, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_done = true;
+      }
+      const int ngr = (S == 1) ? (N + 255) / 256 : N / 64;
+      const int ngp = (ngr + 7) / 8 * 8;
+      wgemm_kernel<EPI, OUT_F32, S><<<mtiles * ngp, 256, lds, s>>>(A, W, bias, C, M, N, K, vt, vt_n0, vt_ld, ngr, ngp);
+    };
+    if (split) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 1>{});
+  });
   return 0;
 }
 
@@ -1265,16 +1114,15 @@ static inline int mfma_gemm_dispatch(const bf16* A, const bf16* W, const float* 
 static inline int mfma_gemm_partial(const bf16* A, const bf16* W, float* slabs, int M, int N, int K, int splits, hipStream_t s) {
   static bool attr_dev[16] = {}; bool& attr_done = attr_dev[vx_cur_device()];
   if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)mfma_gemm_kernel<GE_PLAIN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     (void)hipFuncSetAttribute((const void*)mfma_gemm_kernel<GE_PLAIN, true, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     (void)hipFuncSetAttribute((const void*)mfma_gemm_kernel<GE_PLAIN, true, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     attr_done = true;
   }
   dim3 grid(N / 128, (M + 127) / 128, splits);
-  const int ring = gemm_ring128((long long)grid.x * grid.y * grid.z);
-  if (ring == 64) mfma_gemm_kernel<GE_PLAIN, true, 64><<<grid, 256, 131072, s>>>(A, W, nullptr, slabs, M, N, K / splits, nullptr, 0, 0, K);
-  else if (ring == 32) mfma_gemm_kernel<GE_PLAIN, true, 32><<<grid, 256, 65536, s>>>(A, W, nullptr, slabs, M, N, K / splits, nullptr, 0, 0, K);
-  else mfma_gemm_kernel<GE_PLAIN, true><<<grid, 256, 65536, s>>>(A, W, nullptr, slabs, M, N, K / splits, nullptr, 0, 0, K);
+  if (gemm_ring128((long long)grid.x * grid.y * grid.z) == 64)
+    mfma_gemm_kernel<GE_PLAIN, true, 64><<<grid, 256, 131072, s>>>(A, W, nullptr, slabs, M, N, K / splits, nullptr, 0, 0, K);
+  else
+    mfma_gemm_kernel<GE_PLAIN, true, 32><<<grid, 256, 65536, s>>>(A, W, nullptr, slabs, M, N, K / splits, nullptr, 0, 0, K);
   return 0;
 }
 
@@ -1633,22 +1481,17 @@ static inline int mfma_attn_dispatch(const bf16* qkv, const bf16* vt, int vt_ld,
   // the kernel addresses both operands with 32-bit byte offsets (from the segment's first row / the V^T buffer's start)
   if ((unsigned long long)rows * 3ull * d * 2ull >= (1ull << 32) || (unsigned long long)d * vt_ld * 2ull >= (1ull << 32)) return 1;
   // fewer than ~2 workgroups per CU: split the keys over two wave groups inside the workgroup (4 waves = all 4 SIMDs)
-  static const int kgsel = [] { const char* v = getenv("VX_ATTN_KG"); return v ? atoi(v) : 0; }();  // A/B runs
-  static const int nwsel = [] { const char* v = getenv("VX_ATTN_NW"); return v ? atoi(v) : 0; }();  // A/B runs: query waves per workgroup
   static bool attr_dev[16] = {}; bool& attr_done = attr_dev[vx_cur_device()];
   if (!attr_done) {
     (void)hipFuncSetAttribute((const void*)mfma_attn_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)mfma_attn_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     attr_done = true;
   }
   const long long nwg2 = (long long)((rows + 63) / 64) * H * (seg_start ? nseg : 1);
-  const int kg = kgsel ? kgsel : (nwg2 < 512 ? 2 : 1);  // 4 groups measured slower than 2 at batch-1 NAR (10.7 vs 10.3 ms)
+  const int kg = nwg2 < 512 ? 2 : 1;  // 4 groups measured slower than 2 at batch-1 NAR (10.7 vs 10.3 ms)
   // many workgroups (batched NAR / prefill): FOUR query waves share every staged K / V tile (128 query rows per workgroup)
-  const int nw = kg != 1 ? 2 : nwsel ? (nwsel == 4 ? 4 : 2) : (nwg2 >= 2048 ? 4 : 2);  // 8 waves: 105.4 vs 101.8 ms (profiles/r03_notes.md)
+  const int nw = kg != 1 ? 2 : (nwg2 >= 2048 ? 4 : 2);  // 8 waves: 105.4 vs 101.8 ms (profiles/r03_notes.md)
   dim3 grid((rows + 32 * nw - 1) / (32 * nw), H, seg_start ? nseg : 1);
-  if (kg == 4)
-    mfma_attn_kernel<2, 4><<<grid, 2 * 4 * 64, 131072, s>>>(qkv, vt, out, M, vt_ld, d, text_len, seg_start, seg_len, seg_text);
-  else if (kg == 2)
+  if (kg == 2)
     mfma_attn_kernel<2, 2><<<grid, 2 * 2 * 64, 65536, s>>>(qkv, vt, out, M, vt_ld, d, text_len, seg_start, seg_len, seg_text);
   else if (nw == 4)
     mfma_attn_kernel<4, 1><<<grid, 4 * 64, 32768, s>>>(qkv, vt, out, M, vt_ld, d, text_len, seg_start, seg_len, seg_text);

@@ -4,6 +4,8 @@
 // they ARE the product path in fp32 precision (token-exact parity mode) and the A/B reference
 // for the MFMA kernels (mfma_kernels.hpp) that replace them in bf16 precision.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace vx {
@@ -198,6 +200,19 @@ __global__ __launch_bounds__(256) void project_vec_kernel(const float* __restric
 // ---- scalar-FMA tiled GEMM: C[M,N] = A[M,K] . W[N,K]^T (+bias)(relu)(+residual) ------------
 enum GemmEpi { GE_PLAIN = 0, GE_BIAS = 1, GE_RELU = 2, GE_RESID = 3 };
 
+// Calls f(integral_constant<int, EPI>, bool_constant<OUT_F32>) for a run-time epilogue: GE_RESID and GE_PLAIN always write
+// fp32, GE_BIAS and GE_RELU write fp32 only when out_f32 is set (the input type otherwise).
+template <class F>
+static inline void gemm_epi_dispatch(int epi, bool out_f32, F&& f) {
+  using std::integral_constant;
+  if (epi == GE_RESID) f(integral_constant<int, GE_RESID>{}, std::true_type{});
+  else if (epi == GE_PLAIN) f(integral_constant<int, GE_PLAIN>{}, std::true_type{});
+  else if (epi == GE_BIAS && out_f32) f(integral_constant<int, GE_BIAS>{}, std::true_type{});
+  else if (epi == GE_RELU && out_f32) f(integral_constant<int, GE_RELU>{}, std::true_type{});
+  else if (epi == GE_BIAS) f(integral_constant<int, GE_BIAS>{}, std::false_type{});
+  else f(integral_constant<int, GE_RELU>{}, std::false_type{});
+}
+
 template <typename T, typename OT, int EPI>
 __global__ __launch_bounds__(256) void gemm_simple_kernel(const T* __restrict__ A, const T* __restrict__ W,
                                                           const float* __restrict__ bias, OT* __restrict__ C,
@@ -253,6 +268,17 @@ __global__ __launch_bounds__(256) void gemm_simple_kernel(const T* __restrict__ 
       else *c = from_f32<OT>(v);
     }
   }
+}
+
+// the scalar-FMA GEMM for any shape: fp32 rows, and bf16 shapes outside the MFMA tilings
+template <typename T>
+static inline void gemm_simple_launch(const T* A, const T* W, const float* bias, void* C, int M, int N, int K, int epi,
+                                      bool out_f32, hipStream_t s) {
+  const dim3 grid((N + 63) / 64, (M + 63) / 64);
+  gemm_epi_dispatch(epi, out_f32, [&](auto E, auto F) {
+    using OT = std::conditional_t<decltype(F)::value, float, T>;
+    gemm_simple_kernel<T, OT, decltype(E)::value><<<grid, 256, 0, s>>>(A, W, bias, (OT*)C, M, N, K);
+  });
 }
 
 // ---- tiled attention over rows (prefill mask or none) --------------------------------------
