@@ -297,6 +297,24 @@ def test_batched_nar_matches_per_utterance_nar_and_reference():
     assert torch.equal(eng.nar(texts[0], proms[0], tks[0]).cpu(), single[0])
 
 
+def test_batched_nar_on_a_batch1_engine_matches_a_batch_engine():
+    """An engine created with max_batch = 1 still runs vx_nar_batch (its segment arrays come with the engine): the same
+    codes as a max_batch = 4 engine on the same inputs, for three utterances and for one."""
+    _, _, m1 = _setup(max_batch=1)
+    _, _, m4 = _setup(max_batch=4)
+    e1, e4 = m1.engine(), m4.engine()
+    u = _utts([(6, 30), (9, 12), (4, 55)])
+    texts = [x[0] for x, _, _ in u]
+    proms = [y[0].contiguous() for _, _, y in u]
+    tks = [torch.randint(0, 1024, (16 * x.shape[1] + 1,), generator=torch.Generator().manual_seed(i)) for i, (x, _, _) in enumerate(u)]
+    for k in (3, 1):
+        a = [c.cpu() for c in e1.nar_batch(texts[:k], proms[:k], tks[:k])]
+        b = [c.cpu() for c in e4.nar_batch(texts[:k], proms[:k], tks[:k])]
+        for x, y, t in zip(a, b, tks):
+            assert x.shape == (t.numel(), 8)
+            assert torch.equal(x, y)
+
+
 @pytest.mark.parametrize("bos", [False, True])
 def test_batched_prefill_matches_per_slot_prefill(bos):
     """vx_batch_prefill_all (one pass over the concatenated rows, per-segment prefix mask, K/V scattered straight into

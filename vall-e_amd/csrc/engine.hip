@@ -162,19 +162,17 @@ struct vx_engine {
   int *btok = nullptr, *bsamp = nullptr, *bargm = nullptr;
   int btok_stride = 0;
   std::unordered_map<int, hipGraphExec_t> bgraphs;
-  int *d_seg_start = nullptr, *d_seg_len = nullptr;  // segments of the concatenated row buffer (batched NAR / prefill)
-  int* d_seg_text = nullptr;                          // per-segment text length (prefix mask of a batched prefill)
-  int* d_seg_slot = nullptr;                          // slot of every segment of a batched prefill
+  // segment layout of the concatenated row passes (seg_layout): start and length per segment, and for a batched prefill each
+  // segment's text length (prefix mask) and slot
+  int *d_seg_start = nullptr, *d_seg_len = nullptr, *d_seg_text = nullptr, *d_seg_slot = nullptr;
   // prenets (VX_FLAG_PRENET): scratch rows, conv weights re-laid out as [k][ci][co], decode-step vectors
   float *pn_a = nullptr, *pn_b = nullptr, *pn_h1 = nullptr, *pn_h2 = nullptr, *pn_text = nullptr, *d_zero = nullptr;
   float *ar_e = nullptr, *ar_h1 = nullptr, *ar_h2 = nullptr;
   float* convT[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
   float* slab = nullptr;                              // split-K slabs of the N = d row GEMMs (4 x slab_rows x d fp32)
   int slab_rows = 0;
-  bool seg_text_on = false;                           // true only while a batched prefill runs its stack
   long long *bp_text = nullptr, *bp_audio = nullptr;  // id staging of the batched prefill
   size_t cap_audio = 0, cap_text = 0;                 // rows the id / yemb / logits staging buffers hold
-  int nseg = 0, max_seg_len = 0;
   int bS[BMAX] = {}, bP[BMAX] = {}, bbos[BMAX] = {}, bngen[BMAX] = {}, breason[BMAX] = {};
   bool bprefilled[BMAX] = {};
   // continuous-batching session (vx_batch_open / _admit / _run): per-slot state, the steps a live slot may still take before its
@@ -393,6 +391,12 @@ extern "C" int vx_create(const vx_config* cfg, vx_engine** out) {
   return VX_OK;
 }
 
+// Every engine batches its row passes (a batch-1 engine still runs vx_nar_batch): the segment arrays, BMAX entries each.
+static int seg_alloc(vx_engine* e) {
+  for (int** p : {&e->d_seg_start, &e->d_seg_len, &e->d_seg_text, &e->d_seg_slot}) VXC(dalloc_t(e, p, (size_t)BMAX));
+  return VX_OK;
+}
+
 static int create_body(vx_engine* e) {
   const vx_config& c = e->cfg;
   const bool hd64 = c.d_model / c.nhead == 64 && (c.num_quantizers == 1 || c.nar_d_model / c.nar_nhead == 64);
@@ -519,10 +523,7 @@ static int create_body(vx_engine* e) {
     HIPC(hipHostMalloc((void**)&e->h_bst, 3 * BMAX * sizeof(ArState)));
     VXC(dalloc_t(e, &e->bp_text, (size_t)BMAX * c.max_text));
     VXC(dalloc_t(e, &e->bp_audio, (size_t)BMAX * (c.max_audio + 1)));
-    VXC(dalloc_t(e, &e->d_seg_start, (size_t)BMAX));
-    VXC(dalloc_t(e, &e->d_seg_len, (size_t)BMAX));
-    VXC(dalloc_t(e, &e->d_seg_text, (size_t)BMAX));
-    VXC(dalloc_t(e, &e->d_seg_slot, (size_t)BMAX));
+    VXC(seg_alloc(e));
     // MFMA A operands always read 32 rows: rows of unused slots must hold finite values
     HIPC(hipMemsetAsync(e->bx, 0, (size_t)BMAX * d * 4, e->es));
     HIPC(hipMemsetAsync(e->bh, 0, (size_t)BMAX * d * 2, e->es));
@@ -545,6 +546,7 @@ static int create_body(vx_engine* e) {
       VXC(dalloc_t(e, &t.s8, t.numel / 32));
     }
   }
+  if (c.max_batch <= 1) VXC(seg_alloc(e));  // after the weights: no small block in the arena moves for lack of a batch block
   HIPC(hipStreamSynchronize(e->es));  // the fills above are done before the caller's uploads (other streams) begin
   return VX_OK;
 }
@@ -881,14 +883,20 @@ static int cast_rows(vx_engine* e, const float* x, void* out, size_t n) {
   return VX_OK;
 }
 
-static int attn_rows(vx_engine* e, const void* qkv, void* out, int M, int d, int H, int text_len) {
+// How the rows of e->X are laid out: n == 0, one plain sequence; otherwise n concatenated utterances (seg_layout), segment z
+// at rows [start[z], start[z] + len[z]) of the buffer (device arrays), with its own prefix mask (text, optional: text_len
+// applies to all) and its own KV slot (slot, optional).
+struct RowSegs {
+  int n = 0, max_len = 0;
+  const int *start = nullptr, *len = nullptr, *text = nullptr, *slot = nullptr;
+};
+
+static int attn_rows(vx_engine* e, const void* qkv, void* out, int M, int d, int H, int text_len, const RowSegs& segs) {
   const int hd = d / H;
   const float scale = 1.0f / sqrtf((float)hd);
-  if (e->nseg > 0 || use_mfma(e)) {
-    const int rc = e->nseg > 0  // batched NAR: one launch over all segments of the concatenated rows
-        ? mfma_attn_dispatch((const bf16*)qkv, (const bf16*)e->VT, e->vt_ld, (bf16*)out, M, d, H, text_len, e->es,
-                             e->d_seg_start, e->d_seg_len, e->nseg, e->max_seg_len, e->seg_text_on ? e->d_seg_text : nullptr)
-        : mfma_attn_dispatch((const bf16*)qkv, (const bf16*)e->VT, e->vt_ld, (bf16*)out, M, d, H, text_len, e->es);
+  if (segs.n > 0 || use_mfma(e)) {  // segments: one launch over all of them
+    const int rc = mfma_attn_dispatch((const bf16*)qkv, (const bf16*)e->VT, e->vt_ld, (bf16*)out, M, d, H, text_len, e->es,
+                                      segs.start, segs.len, segs.n, segs.max_len, segs.text);
     return rc == 0 ? VX_OK : fail(VX_ERR_UNSUPPORTED, "attention: a sequence's q/k/v rows or the V^T buffer exceed 4 GB (rows %d, d %d)", M, d);
   }
   dim3 grid((M + 63) / 64, H);
@@ -904,8 +912,8 @@ static int attn_rows(vx_engine* e, const void* qkv, void* out, int M, int d, int
 }
 
 // One encoder stack over M rows held in e->X (valle.py:1035-1038 / 1125-1127).  `ada_stage` < 0:
-// plain LayerNorm (AR); otherwise the stage's AdaLN vectors.  If kv_layer0 is non-null the K/V
-// rows are also scattered into the decode cache.
+// plain LayerNorm (AR); otherwise the stage's AdaLN vectors.  `segs`: the row layout; `kv`: where
+// the K/V rows also go (KvDst).
 static int split_for(int K) {  // K slices of the split-K GEMMs: a multiple of the 64-wide K tile each
   for (int sp = 4; sp > 1; sp >>= 1)
     if (K % (64 * sp) == 0) return sp;
@@ -942,10 +950,16 @@ static bool mx_on(const vx_engine* e, int ada_stage, int M, int d) {
   return e->fp8nar && ada_stage >= 0 && M >= (v ? atoi(v) : 4096) && !(e->cfg.flags & VX_FLAG_POST_NORM) && use_mfma(e) && d % 256 == 0;
 }
 
-// kv_base: the cache fill_cache writes (default: the batch-1 cache); kv8_slot >= 0: kv_base is that slot's fp8 cache instead
+// Where run_stack also writes every layer's K / V rows: nowhere (NAR stages), a bf16 / fp32 cache in the layout of e->kv at
+// `base`, the fp8 cache of slot `slot`, or each segment's rows to the slot cache its entry of RowSegs::slot names.
+struct KvDst {
+  enum Kind { NONE, CACHE, FP8_SLOT, SEG_SLOTS } kind = NONE;
+  char* base = nullptr;  // CACHE
+  int slot = 0;          // FP8_SLOT
+};
+
 static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int d, int H, int text_len, int ada_stage,
-                     bool fill_cache, char* kv_base = nullptr, int kv8_slot = -1) {
-  if (kv_base == nullptr) kv_base = (char*)e->kv;
+                     const RowSegs& segs, KvDst kv) {
   const bool post = e->cfg.flags & VX_FLAG_POST_NORM;
   const int hd = d / H;
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
@@ -991,26 +1005,25 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
     VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
     if (tg) gemm_mark(e, 2.0 * M * 3 * d * d);
     }
-    if (fill_cache && e->nseg > 0) {  // batched prefill: segment z -> slot d_seg_slot[z]
-      const size_t kvl = (size_t)2 * H * e->ctx_max * 64;  // elements per layer
+    const size_t kvl = (size_t)2 * H * e->ctx_max * 64;  // elements per layer of a slot cache
+    if (kv.kind == KvDst::SEG_SLOTS) {  // batched prefill: segment z -> slot segs.slot[z]
       if (e->kv8)
-        kv8_scatter_kernel<<<dim3(e->max_seg_len, e->nseg), 256, 0, e->es>>>((const bf16*)e->QKV, e->bkv8 + li * kvl, e->bkv8s + li * kvl / 16,
-                                                                             e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, e->d_seg_slot,
-                                                                             d, e->ctx_max);
+        kv8_scatter_kernel<<<dim3(segs.max_len, segs.n), 256, 0, e->es>>>((const bf16*)e->QKV, e->bkv8 + li * kvl, e->bkv8s + li * kvl / 16,
+                                                                           e->bkv_slot, kvl / 2, segs.start, segs.len, segs.slot, d, e->ctx_max);
       else
-        kv_scatter_seg_kernel<bf16><<<dim3(e->max_seg_len, e->nseg), 256, 0, e->es>>>(
-            (const bf16*)e->QKV, e->bkv + li * kvl, e->bkv_slot, kvl / 2, e->d_seg_start, e->d_seg_len, d, 64, e->ctx_max, e->d_seg_slot);
-    } else if (fill_cache && kv8_slot >= 0) {  // per-slot prefill into an fp8 slot cache
-      const size_t kvl = (size_t)2 * H * e->ctx_max * 64, at = (size_t)kv8_slot * e->bkv_slot + li * kvl;
+        kv_scatter_seg_kernel<bf16><<<dim3(segs.max_len, segs.n), 256, 0, e->es>>>(
+            (const bf16*)e->QKV, e->bkv + li * kvl, e->bkv_slot, kvl / 2, segs.start, segs.len, d, 64, e->ctx_max, segs.slot);
+    } else if (kv.kind == KvDst::FP8_SLOT) {  // per-slot prefill into an fp8 slot cache
+      const size_t at = (size_t)kv.slot * e->bkv_slot + li * kvl;
       kv8_scatter_kernel<<<M, 256, 0, e->es>>>((const bf16*)e->QKV, e->bkv8 + at, e->bkv8s + at / 16, 0, kvl / 2, nullptr, nullptr, nullptr,
                                                d, e->ctx_max);
-    } else if (fill_cache) {
-      char* kc = kv_base + li * kv_layer;
+    } else if (kv.kind == KvDst::CACHE) {
+      char* kc = kv.base + li * kv_layer;
       char* vc = kc + kv_layer / 2;
       if (e->bf16) kv_scatter_kernel<bf16><<<M, 256, 0, e->es>>>((const bf16*)e->QKV, (bf16*)kc, (bf16*)vc, M, d, hd, e->ctx_max);
       else kv_scatter_kernel<float><<<M, 256, 0, e->es>>>((const float*)e->QKV, (float*)kc, (float*)vc, M, d, hd, e->ctx_max);
     }
-    VXC(attn_rows(e, e->QKV, e->ATT, M, d, H, text_len));
+    VXC(attn_rows(e, e->QKV, e->ATT, M, d, H, text_len, segs));
     Fold fo;  // out-projection: x += out_proj(attn), folded into the norm that follows when split
     if (tg && !mx) gemm_mark(e, 0);  // (MXFP8 stages: only the fp8 GEMMs are timed; the out-projection stays bf16)
     if (splitk && sp_d > 1) {
@@ -1110,7 +1123,7 @@ static int run_stack_f(vx_engine* e, const std::vector<LayerW>& layers, int M, i
       if (e->bf16) kv_scatter_kernel<bf16><<<M, 256, 0, e->es>>>((const bf16*)e->QKV, (bf16*)kc, (bf16*)vc, M, d, hd, e->ctx_max);
       else kv_scatter_kernel<float><<<M, 256, 0, e->es>>>((const float*)e->QKV, (float*)kc, (float*)vc, M, d, hd, e->ctx_max);
     }
-    VXC(attn_rows(e, e->QKV, e->ATT, M, d, H, text_len));
+    VXC(attn_rows(e, e->QKV, e->ATT, M, d, H, text_len, RowSegs()));
     VXC(gemm_rows(e, e->ATT, l.out_w, l.out_b, e->X, M, d, d, GE_RESID, true));
     // cross-attention over the text: x += mha(norm2(x), memory) (540-545); post-norm x = norm2(x + mha(x, memory)) (551-557)
     if (!post) VXC(ln_rows(e, e->X, l.n2_g, l.n2_b, aw[1], ab[1], e->Hn, M, d));
@@ -1222,12 +1235,14 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
     embed_pos_kernel<<<A, 256, 0, e->es>>>(e->ids_audio, 1, 0, W<float>(e, "ar_audio_embedding.word_embeddings.weight"), 1025 + bos, d,
                                            W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, e->X + (size_t)(vf ? 0 : S) * d, A);
   }
-  char* kv_base = slot < 0 ? (char*)e->kv : e->kv8 ? nullptr : (char*)(e->bkv + (size_t)slot * e->bkv_slot);
+  const KvDst kv = slot < 0 ? KvDst{KvDst::CACHE, (char*)e->kv}
+                 : e->kv8  ? KvDst{KvDst::FP8_SLOT, nullptr, slot}
+                           : KvDst{KvDst::CACHE, (char*)(e->bkv + (size_t)slot * e->bkv_slot)};
   float* x_dst = slot < 0 ? e->ar_x : e->bx + (size_t)slot * d;
   float* lg_dst = slot < 0 ? e->ar_logits : e->blogits + (size_t)slot * LOGITS_CUR;
   ArState* st_dst = slot < 0 ? e->d_st : e->bst + slot;
   if (vf) { e->mem_len = S; VXC(run_stack_f(e, e->ar_l, M, d, c.nhead, 0, -1, true, e->xkv_ar, S)); }
-  else VXC(run_stack(e, e->ar_l, M, d, c.nhead, S, -1, true, kv_base, slot >= 0 && e->kv8 ? slot : -1));
+  else VXC(run_stack(e, e->ar_l, M, d, c.nhead, S, -1, RowSegs(), kv));
   HIPC(hipMemcpyAsync(x_dst, e->X + (size_t)(M - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
   ArState& st = slot < 0 ? e->h_st[0] : e->h_bst[slot];
   seed_state(st, S, P, bos, M - 1, vf ? 0 : S, slot < 0 && (c.flags & VX_FLAG_TRACE_LOGITS));
@@ -1271,6 +1286,27 @@ extern "C" int vx_batch_prefill(vx_engine* e, int32_t slot, const int64_t* text,
 static int ensure_rows(vx_engine* e, size_t rows, size_t audio_rows, size_t text_rows);
 template <int EPI> static int launch_bgemm(const BgemmArgs& a, hipStream_t s);
 
+// n utterances of len[z] rows as segments of e->X, each starting at a multiple of 64 rows: start[z] (n + 1 entries, start[n] =
+// all rows), row buffers and the id / embedding staging (audio_rows / text_rows) grown to fit, the layout uploaded on e->es,
+// X zeroed over all rows (padding rows must stay finite: they feed V^T columns).  text / slot (optional): per-segment prefix
+// lengths / slots.  The host arrays must outlive the pass (the uploads are asynchronous).
+static int seg_layout(vx_engine* e, int n, const int* len, const int* text, const int* slot, int d, size_t audio_rows,
+                      size_t text_rows, int* start, RowSegs& segs) {
+  segs = RowSegs{n, 0, e->d_seg_start, e->d_seg_len, text ? e->d_seg_text : nullptr, slot ? e->d_seg_slot : nullptr};
+  start[0] = 0;
+  for (int z = 0; z < n; ++z) {
+    start[z + 1] = start[z] + (len[z] + 63) / 64 * 64;
+    if (len[z] > segs.max_len) segs.max_len = len[z];
+  }
+  VXC(ensure_rows(e, start[n], audio_rows, text_rows));
+  HIPC(hipMemcpyAsync(e->d_seg_start, start, n * sizeof(int), hipMemcpyHostToDevice, e->es));
+  HIPC(hipMemcpyAsync(e->d_seg_len, len, n * sizeof(int), hipMemcpyHostToDevice, e->es));
+  if (text) HIPC(hipMemcpyAsync(e->d_seg_text, text, n * sizeof(int), hipMemcpyHostToDevice, e->es));
+  if (slot) HIPC(hipMemcpyAsync(e->d_seg_slot, slot, n * sizeof(int), hipMemcpyHostToDevice, e->es));
+  HIPC(hipMemsetAsync(e->X, 0, (size_t)start[n] * d * 4, e->es));
+  return VX_OK;
+}
+
 // Segment z -> slot slots[z]: only those slots' KV caches, bx / blogits / trace rows and ArState are written; bh rows are step
 // scratch.
 static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, const int64_t* const* text, const int32_t* S,
@@ -1281,24 +1317,16 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
   if (!e->bf16 || !use_mfma(e)) return fail(VX_ERR_UNSUPPORTED, "vx_batch_prefill_all needs the bf16 MFMA row kernels");
   const vx_config& c = e->cfg;
   const int bos = c.prepend_bos ? 1 : 0, d = c.d_model;
-  std::vector<int> start(n), len(n), tlen(n);
-  size_t rows = 0;
-  int maxlen = 0;
+  std::vector<int> start(n + 1), len(n), tlen(n);
   for (int b = 0; b < n; ++b) {
     VXC(check_utterance(e, text[b], S[b], prompt_cb0[b], P[b], b));
-    start[b] = (int)rows; len[b] = S[b] + bos + P[b]; tlen[b] = S[b];
-    rows += (size_t)((len[b] + 63) / 64) * 64;
-    if (len[b] > maxlen) maxlen = len[b];
+    len[b] = S[b] + bos + P[b]; tlen[b] = S[b];
   }
   ON_DEVICE(c.device);
-  VXC(ensure_rows(e, rows, e->cap_audio, e->cap_text));
   VXC(sync_in(e, stream));
   HIPC(hipEventRecord(e->ev_t[0], e->es));
-  HIPC(hipMemcpyAsync(e->d_seg_start, start.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
-  HIPC(hipMemcpyAsync(e->d_seg_len, len.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
-  HIPC(hipMemcpyAsync(e->d_seg_text, tlen.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
-  HIPC(hipMemcpyAsync(e->d_seg_slot, slots, n * sizeof(int), hipMemcpyHostToDevice, e->es));
-  HIPC(hipMemsetAsync(e->X, 0, rows * (size_t)d * 4, e->es));  // padding rows must stay finite (they feed V^T columns)
+  RowSegs segs;
+  VXC(seg_layout(e, n, len.data(), tlen.data(), slots, d, e->cap_audio, e->cap_text, start.data(), segs));
   static const long long bos_id = NUM_AUDIO_TOKENS + 1;  // valle.py:1006-1007
   for (int b = 0; b < n; ++b) {
     const int A = bos + P[b];
@@ -1313,10 +1341,7 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
     embed_pos_kernel<<<A, 256, 0, e->es>>>(ia, 1, 0, W<float>(e, "ar_audio_embedding.word_embeddings.weight"), 1025 + bos, d,
                                            W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, xb + (size_t)S[b] * d, A);
   }
-  e->nseg = n; e->max_seg_len = maxlen; e->seg_text_on = true;
-  int rc = run_stack(e, e->ar_l, (int)rows, d, c.nhead, 0, -1, true);
-  e->nseg = 0; e->seg_text_on = false;
-  VXC(rc);
+  VXC(run_stack(e, e->ar_l, start[n], d, c.nhead, 0, -1, segs, KvDst{KvDst::SEG_SLOTS}));
   // last row of every segment = the slot's current activation
   for (int b = 0; b < n; ++b) {
     const int sl = slots[b];
@@ -2084,115 +2109,150 @@ extern "C" int vx_batch_run(vx_engine* e, int32_t min_stopped, int32_t poll_step
 }
 
 // ------------------------------------------------------------------------------ NAR
-// forced (optional, (T, Q)): stage i's argmax is still what codes_out reports, but the embedding that feeds stage i+1 is
+// The NAR stages (valle.py:1063-1134) of n utterances, checked by the caller: text_nar[b] (S2[b] ids), prompts[b] ((P[b], Q)
+// codes) and ar_tokens[b] (T[b] codes of codebook 0) -> codes_out[b] ((T[b], Q)).  segmented: the rows of all utterances are
+// concatenated (seg_layout), so the GEMMs run at M ~ n x 1k rows where the MFMA kernels are efficient and attention runs per
+// segment in one launch; otherwise n == 1 and its rows start at 0, unpadded.
+// forced (optional, (T, Q) each): stage i's argmax is still what codes_out reports, but the embedding that feeds stage i+1 is
 // taken from forced[:, i+1] - the input the reference itself gave that stage when `forced` are its codes (valle.py:1133-1134).
-// stage_logits (optional, (Q-1, T, 1024) fp32, host or device): every stage's logits rows (valle.py:1128).
-static int nar_impl(vx_engine* e, const int64_t* text_nar, int32_t S2, const int64_t* prompts, int32_t P,
-                    const int64_t* ar_tokens, int32_t T, int64_t* codes_out, void* stream, bool pos_before_prenet,
-                    const int64_t* forced = nullptr, float* stage_logits = nullptr) {
-  if (!e || !text_nar || !ar_tokens || !codes_out || (P > 0 && !prompts)) return fail(VX_ERR_ARG, "null argument");
-  if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+// Unsegmented only: prenets, VALL-F, pos_before_prenet (VALLE.continual) and stage_logits ((Q-1, T, 1024) fp32, host or
+// device: every stage's logits rows, valle.py:1128).
+static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* text_nar, const int32_t* S2,
+                   const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens, const int32_t* T,
+                   int64_t* const* codes_out, const int64_t* const* forced, void* stream, bool pos_before_prenet = false,
+                   float* stage_logits = nullptr) {
   const vx_config& c = e->cfg;
-  const int Q = c.num_quantizers;
-  if (S2 <= 0 || T <= 0 || P < 0) return fail(VX_ERR_ARG, "bad S2/P/T");
-  if (S2 > c.max_text || P + T > c.max_audio) return fail(VX_ERR_CAPACITY, "S2=%d P+T=%d exceed capacity", S2, P + T);
+  const int Q = c.num_quantizers, dn = c.nar_d_model;
+  const bool vf = e->vallf, prenet = c.flags & VX_FLAG_PRENET, post = c.flags & VX_FLAG_POST_NORM;
+  // per utterance: its rows in X, tx = text rows in front of its audio rows (VALL-F, valle.py:650-708: the stack runs over the
+  // audio rows, the NAR text is cross-attention memory), its offsets into the audio / generated / text id staging
+  std::vector<int> start(n + 1), len(n), tx(n), aoff(n), toff(n), soff(n);
+  int arows = 0, trows = 0, srows = 0;
+  for (int b = 0; b < n; ++b) {
+    tx[b] = vf ? 0 : S2[b];
+    len[b] = tx[b] + P[b] + T[b];
+    aoff[b] = arows; toff[b] = trows; soff[b] = srows;
+    arows += P[b] + T[b]; trows += T[b]; srows += S2[b];
+  }
   ON_DEVICE(c.device);
   VXC(sync_in(e, stream));
   HIPC(hipEventRecord(e->ev_t[4], e->es));
-  const bool vf = e->vallf;  // VALL-F (valle.py:650-708): the stack runs over the audio rows, the NAR text is cross-attention memory
-  const int dn = c.nar_d_model, A = P + T, N = vf ? A : S2 + A, tx = vf ? 0 : S2;  // tx = text rows in front of the audio rows in X
-  // y = [prompt codebook 0 | AR tokens] (valle.py:1064-1066)
-  if (P) HIPC(hipMemcpyAsync(e->ids_prompts, prompts, (size_t)P * Q * 8, hipMemcpyDefault, e->es));
-  HIPC(hipMemcpyAsync(e->ids_samples, ar_tokens, (size_t)T * 8, hipMemcpyDefault, e->es));
-  copy_col_kernel<<<(T + 255) / 256, 256, 0, e->es>>>(e->ids_samples, e->d_codes, T, Q, 0);
-  if (forced) HIPC(hipMemcpyAsync(e->d_fcodes, forced, (size_t)T * Q * 8, hipMemcpyDefault, e->es));
+  RowSegs segs;
+  if (segmented) VXC(seg_layout(e, n, len.data(), nullptr, nullptr, dn, arows, srows, start.data(), segs));
+  else start[1] = len[0];
+  const int rows = start[n];
+  auto emb = [&](int j) { return W<float>(e, "nar_audio_embeddings." + std::to_string(j) + ".word_embeddings.weight"); };
+  for (int b = 0; b < n; ++b) {  // y = [prompt codebook 0 | AR tokens] (valle.py:1064-1066)
+    long long* idp = e->ids_prompts + (size_t)aoff[b] * Q;  // (P_b, Q) rows; region sized for P+T rows per utterance
+    long long* ids = e->ids_samples + toff[b];
+    float* ye = e->yemb + (size_t)aoff[b] * dn;
+    if (P[b]) HIPC(hipMemcpyAsync(idp, prompts[b], (size_t)P[b] * Q * 8, hipMemcpyDefault, e->es));
+    HIPC(hipMemcpyAsync(ids, ar_tokens[b], (size_t)T[b] * 8, hipMemcpyDefault, e->es));
+    copy_col_kernel<<<(T[b] + 255) / 256, 256, 0, e->es>>>(ids, e->d_codes + (size_t)toff[b] * Q, T[b], Q, 0);
+    if (forced) HIPC(hipMemcpyAsync(e->d_fcodes + (size_t)toff[b] * Q, forced[b], (size_t)T[b] * Q * 8, hipMemcpyDefault, e->es));
+    if (Q == 1) continue;
+    HIPC(hipMemcpyAsync(e->ids_text + soff[b], text_nar[b], (size_t)S2[b] * 8, hipMemcpyDefault, e->es));
+    if (P[b]) embed_accum_kernel<<<P[b], 256, 0, e->es>>>(idp, Q, 0, emb(0), 1025, dn, ye, P[b], 1);
+    embed_accum_kernel<<<T[b], 256, 0, e->es>>>(ids, 1, 0, emb(0), 1025, dn, ye + (size_t)P[b] * dn, T[b], 1);
+    if (c.prefix_mode != 0 && P[b])  // valle.py:1110-1113
+      for (int j = 1; j < Q; ++j) embed_accum_kernel<<<P[b], 256, 0, e->es>>>(idp, Q, j, emb(j), 1024, dn, ye, P[b], 0);
+  }
   if (Q > 1) {
-    HIPC(hipMemcpyAsync(e->ids_text, text_nar, (size_t)S2 * 8, hipMemcpyDefault, e->es));
-    auto emb = [&](int j) { return W<float>(e, "nar_audio_embeddings." + std::to_string(j) + ".word_embeddings.weight"); };
-    if (P) embed_accum_kernel<<<P, 256, 0, e->es>>>(e->ids_prompts, Q, 0, emb(0), 1025, dn, e->yemb, P, 1);
-    embed_accum_kernel<<<T, 256, 0, e->es>>>(e->ids_samples, 1, 0, emb(0), 1025, dn, e->yemb + (size_t)P * dn, T, 1);
-    if (c.prefix_mode != 0 && P)  // valle.py:1110-1113
-      for (int j = 1; j < Q; ++j) embed_accum_kernel<<<P, 256, 0, e->es>>>(e->ids_prompts, Q, j, emb(j), 1024, dn, e->yemb, P, 0);
     const float* a_txt = W<float>(e, "nar_text_position.alpha");
     const float* a_aud = W<float>(e, "nar_audio_position.alpha");
-    const bool prenet = c.flags & VX_FLAG_PRENET;
     if (prenet) {  // x = position(nar_text_prenet(embedding)) once (valle.py:1081-1083); kept in pn_text for every stage
-      embed_accum_kernel<<<S2, 256, 0, e->es>>>(e->ids_text, 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"), 512, dn, e->pn_a, S2, 1);
-      VXC(text_prenet_rows(e, 1, e->pn_a, e->pn_a, S2, dn));
-      add_pos_kernel<<<S2, 256, 0, e->es>>>(e->pn_a, dn, a_txt, e->pe_nar, 0, e->pn_text, S2);
+      embed_accum_kernel<<<S2[0], 256, 0, e->es>>>(e->ids_text, 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"), 512, dn, e->pn_a, S2[0], 1);
+      VXC(text_prenet_rows(e, 1, e->pn_a, e->pn_a, S2[0], dn));
+      add_pos_kernel<<<S2[0], 256, 0, e->es>>>(e->pn_a, dn, a_txt, e->pe_nar, 0, e->pn_text, S2[0]);
     }
     if (vf) {  // the text memory's K / V per layer, once for all stages (same memory and weights in every stage, valle.py:664-688)
-      if (prenet) HIPC(hipMemcpyAsync(e->X, e->pn_text, (size_t)S2 * dn * 4, hipMemcpyDeviceToDevice, e->es));
-      else embed_pos_kernel<<<S2, 256, 0, e->es>>>(e->ids_text, 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"), 512, dn,
-                                                   a_txt, e->pe_nar, 0, e->X, S2);
-      VXC(cast_rows(e, e->X, e->Hn, (size_t)S2 * dn));
-      VXC(memory_kv(e, e->nar_l, e->xkv_nar, S2, dn, c.nar_nhead));
+      if (prenet) HIPC(hipMemcpyAsync(e->X, e->pn_text, (size_t)S2[0] * dn * 4, hipMemcpyDeviceToDevice, e->es));
+      else embed_pos_kernel<<<S2[0], 256, 0, e->es>>>(e->ids_text, 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"), 512, dn,
+                                                      a_txt, e->pe_nar, 0, e->X, S2[0]);
+      VXC(cast_rows(e, e->X, e->Hn, (size_t)S2[0] * dn));
+      VXC(memory_kv(e, e->nar_l, e->xkv_nar, S2[0], dn, c.nar_nhead));
     }
     for (int i = 0; i < Q - 1; ++i) {
-      if (prenet) {
-        if (!vf) HIPC(hipMemcpyAsync(e->X, e->pn_text, (size_t)S2 * dn * 4, hipMemcpyDeviceToDevice, e->es));
-        if (pos_before_prenet) {  // VALLE.continual, prefix mode 0 (valle.py:1193-1194)
-          add_pos_kernel<<<A, 256, 0, e->es>>>(e->yemb, dn, a_aud, e->pe_nar, 0, e->pn_a, A);
-          VXC(audio_prenet_rows(e, 1, e->pn_a, e->X + (size_t)tx * dn, A, dn));
-        } else {  // valle.py:1092-1093, 1121-1122
-          VXC(audio_prenet_rows(e, 1, e->yemb, e->pn_b, A, dn));
-          add_pos_kernel<<<A, 256, 0, e->es>>>(e->pn_b, dn, a_aud, e->pe_nar, 0, e->X + (size_t)tx * dn, A);
+      for (int b = 0; b < n; ++b) {
+        float* xb = e->X + (size_t)start[b] * dn;
+        float* xa = xb + (size_t)tx[b] * dn;  // the audio rows
+        const float* ye = e->yemb + (size_t)aoff[b] * dn;
+        const int A = P[b] + T[b];
+        if (prenet) {
+          if (!vf) HIPC(hipMemcpyAsync(xb, e->pn_text, (size_t)S2[b] * dn * 4, hipMemcpyDeviceToDevice, e->es));
+          if (pos_before_prenet) {  // VALLE.continual, prefix mode 0 (valle.py:1193-1194)
+            add_pos_kernel<<<A, 256, 0, e->es>>>(ye, dn, a_aud, e->pe_nar, 0, e->pn_a, A);
+            VXC(audio_prenet_rows(e, 1, e->pn_a, xa, A, dn));
+          } else {  // valle.py:1092-1093, 1121-1122
+            VXC(audio_prenet_rows(e, 1, ye, e->pn_b, A, dn));
+            add_pos_kernel<<<A, 256, 0, e->es>>>(e->pn_b, dn, a_aud, e->pe_nar, 0, xa, A);
+          }
+        } else {
+          if (!vf) embed_pos_kernel<<<S2[b], 256, 0, e->es>>>(e->ids_text + soff[b], 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"),
+                                                              512, dn, a_txt, e->pe_nar, 0, xb, S2[b]);
+          add_pos_kernel<<<A, 256, 0, e->es>>>(ye, dn, a_aud, e->pe_nar, 0, xa, A);
         }
-      } else {
-        if (!vf) embed_pos_kernel<<<S2, 256, 0, e->es>>>(e->ids_text, 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"), 512, dn,
-                                                         a_txt, e->pe_nar, 0, e->X, S2);
-        add_pos_kernel<<<A, 256, 0, e->es>>>(e->yemb, dn, a_aud, e->pe_nar, 0, e->X + (size_t)tx * dn, A);
       }
-      if (vf) VXC(run_stack_f(e, e->nar_l, N, dn, c.nar_nhead, -1, i, false, e->xkv_nar, S2));
-      else VXC(run_stack(e, e->nar_l, N, dn, c.nar_nhead, -1, i, false));
-      // final AdaLN + predict layer on the T generated rows only (valle.py:1128)
-      if (c.flags & VX_FLAG_POST_NORM) {  // no final norm (valle.py:242-246): the rows are already norm2'd
-        VXC(cast_rows(e, e->X + (size_t)(tx + P) * dn, e->Hn, (size_t)T * dn));
-      } else {
-        const float* fw = ada_vec(e, i, e->npl * c.nar_num_layers);
-        VXC(ln_rows(e, e->X + (size_t)(tx + P) * dn, W<float>(e, "nar_decoder.norm.norm.weight"),
-                    W<float>(e, "nar_decoder.norm.norm.bias"), fw, fw + dn, e->Hn, T, dn));
+      if (vf) VXC(run_stack_f(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, false, e->xkv_nar, S2[0]));
+      else VXC(run_stack(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, segs, KvDst()));
+      // final AdaLN + predict layer on the generated rows only (valle.py:1128), compacted to [sum T][dn]
+      const float* fw = post ? nullptr : ada_vec(e, i, e->npl * c.nar_num_layers);
+      for (int b = 0; b < n; ++b) {
+        const float* xr = e->X + (size_t)(start[b] + tx[b] + P[b]) * dn;
+        void* hr = (char*)e->Hn + (size_t)toff[b] * dn * e->esz;
+        if (post) VXC(cast_rows(e, xr, hr, (size_t)T[b] * dn));  // no final norm (valle.py:242-246): the rows are already norm2'd
+        else VXC(ln_rows(e, xr, W<float>(e, "nar_decoder.norm.norm.weight"), W<float>(e, "nar_decoder.norm.norm.bias"), fw, fw + dn, hr,
+                         T[b], dn));
       }
       VXC(gemm_rows(e, e->Hn, W<void>(e, "nar_predict_layers." + std::to_string(i) + ".weight"), nullptr, e->nar_logits,
-                    T, 1024, dn, GE_PLAIN, true));
-      argmax_rows_kernel<<<(T + 3) / 4, 256, 0, e->es>>>(e->nar_logits, 1024, T, e->ids_samples, e->d_codes, Q, i + 1);
-      if (stage_logits) HIPC(hipMemcpyAsync(stage_logits + (size_t)i * T * 1024, e->nar_logits, (size_t)T * 1024 * 4, hipMemcpyDefault, e->es));
-      if (forced && i < Q - 2) pick_col_kernel<<<(T + 255) / 256, 256, 0, e->es>>>(e->d_fcodes, Q, i + 1, e->ids_samples, T);
-      if (i < Q - 2) {  // valle.py:1104-1108 / 1133-1134
-        if (c.prefix_mode == 0 && P)
-          embed_accum_kernel<<<P, 256, 0, e->es>>>(e->ids_prompts, Q, i + 1, emb(i + 1), 1024, dn, e->yemb, P, 0);
-        embed_accum_kernel<<<T, 256, 0, e->es>>>(e->ids_samples, 1, 0, emb(i + 1), 1024, dn, e->yemb + (size_t)P * dn, T, 0);
-      }
+                    trows, 1024, dn, GE_PLAIN, true));
+      argmax_rows_kernel<<<(trows + 3) / 4, 256, 0, e->es>>>(e->nar_logits, 1024, trows, e->ids_samples, e->d_codes, Q, i + 1);
+      if (stage_logits) HIPC(hipMemcpyAsync(stage_logits + (size_t)i * trows * 1024, e->nar_logits, (size_t)trows * 1024 * 4, hipMemcpyDefault, e->es));
+      if (forced && i < Q - 2)  // teacher forcing: the next stage sees the caller's codes of this stage (all segments at once)
+        pick_col_kernel<<<(trows + 255) / 256, 256, 0, e->es>>>(e->d_fcodes, Q, i + 1, e->ids_samples, trows);
+      if (i < Q - 2)  // valle.py:1104-1108 / 1133-1134
+        for (int b = 0; b < n; ++b) {
+          float* ye = e->yemb + (size_t)aoff[b] * dn;
+          if (c.prefix_mode == 0 && P[b])
+            embed_accum_kernel<<<P[b], 256, 0, e->es>>>(e->ids_prompts + (size_t)aoff[b] * Q, Q, i + 1, emb(i + 1), 1024, dn, ye, P[b], 0);
+          embed_accum_kernel<<<T[b], 256, 0, e->es>>>(e->ids_samples + toff[b], 1, 0, emb(i + 1), 1024, dn, ye + (size_t)P[b] * dn, T[b], 0);
+        }
     }
   }
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(e->ev_t[5], e->es));
-  HIPC(hipMemcpyAsync(codes_out, e->d_codes, (size_t)T * Q * 8, hipMemcpyDefault, e->es));
+  for (int b = 0; b < n; ++b)
+    HIPC(hipMemcpyAsync(codes_out[b], e->d_codes + (size_t)toff[b] * Q, (size_t)T[b] * Q * 8, hipMemcpyDefault, e->es));
   HIPC(hipStreamSynchronize(e->es));
   float ms = 0.f;
   HIPC(hipEventElapsedTime(&ms, e->ev_t[4], e->ev_t[5]));
   e->t_nar = ms;
   gemm_collect(e);
-  e->last_T = T; e->last_N = N;
+  e->last_T = trows; e->last_N = rows;
   VXC(sync_out(e, stream));
   return VX_OK;
 }
 
 extern "C" int vx_nar(vx_engine* e, const int64_t* text_nar, int32_t S2, const int64_t* prompts, int32_t P,
                       const int64_t* ar_tokens, int32_t T, int64_t* codes_out, void* stream) {
-  return nar_impl(e, text_nar, S2, prompts, P, ar_tokens, T, codes_out, stream, false);
+  return vx_nar_ex(e, text_nar, S2, prompts, P, ar_tokens, T, codes_out, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int vx_nar_ex(vx_engine* e, const int64_t* text_nar, int32_t S2, const int64_t* prompts, int32_t P,
                          const int64_t* ar_tokens, int32_t T, int64_t* codes_out, const int64_t* forced_codes,
                          float* stage_logits, int32_t continual, void* stream) {
-  return nar_impl(e, text_nar, S2, prompts, P, ar_tokens, T, codes_out, stream, continual && e && e->cfg.prefix_mode == 0,
-                  forced_codes, stage_logits);
+  if (!e || !text_nar || !ar_tokens || !codes_out || (P > 0 && !prompts)) return fail(VX_ERR_ARG, "null argument");
+  if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+  const vx_config& c = e->cfg;
+  if (S2 <= 0 || T <= 0 || P < 0) return fail(VX_ERR_ARG, "bad S2/P/T");
+  if (S2 > c.max_text || P + T > c.max_audio) return fail(VX_ERR_CAPACITY, "S2=%d P+T=%d exceed capacity", S2, P + T);
+  return nar_run(e, 1, false, &text_nar, &S2, &prompts, &P, &ar_tokens, &T, &codes_out, forced_codes ? &forced_codes : nullptr,
+                 stream, continual && c.prefix_mode == 0, stage_logits);
 }
 
 extern "C" int vx_nar_continual(vx_engine* e, const int64_t* text_nar, int32_t S2, const int64_t* prompts, int32_t P,
                                 const int64_t* ar_tokens, int32_t T, int64_t* codes_out, void* stream) {
-  return nar_impl(e, text_nar, S2, prompts, P, ar_tokens, T, codes_out, stream, e && e->cfg.prefix_mode == 0);
+  return vx_nar_ex(e, text_nar, S2, prompts, P, ar_tokens, T, codes_out, nullptr, nullptr, 1, stream);
 }
 
 // Row buffers are sized for one utterance at vx_create; the batched NAR concatenates up to max_batch of them.
@@ -2246,129 +2306,31 @@ static int ensure_rows(vx_engine* e, size_t rows, size_t audio_rows, size_t text
   return VX_OK;
 }
 
-// The NAR stages of n utterances at once (valle.py:1063-1134 per utterance): rows of all utterances are
-// concatenated (each segment starts at a multiple of 64 rows), so the GEMMs run at M ~ n x 1k rows where the
-// MFMA kernels are efficient, and attention runs per segment in one launch.
-static int nar_batch_impl(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
-                          const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens,
-                          const int32_t* T, int64_t* const* codes_out, const int64_t* const* forced, void* stream) {
+extern "C" int vx_nar_batch(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
+                            const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens,
+                            const int32_t* T, int64_t* const* codes_out, void* stream) {
+  return vx_nar_batch_ex(e, n, text_nar, S2, prompts, P, ar_tokens, T, codes_out, nullptr, stream);
+}
+// The NAR stages of n utterances at once, their rows concatenated (nar_run).
+extern "C" int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
+                               const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens,
+                               const int32_t* T, int64_t* const* codes_out, const int64_t* const* forced_codes, void* stream) {
   if (e && e->vallf) return fail(VX_ERR_UNSUPPORTED, "vx_nar_batch: VALL-F runs on the batch-1 path only");
   if (!e || !text_nar || !S2 || !prompts || !P || !ar_tokens || !T || !codes_out) return fail(VX_ERR_ARG, "null argument");
   if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
   const vx_config& c = e->cfg;
-  const int Q = c.num_quantizers, dn = c.nar_d_model;
   if (n < 1 || n > BMAX) return fail(VX_ERR_ARG, "n must be 1..%d", BMAX);
-  if (!e->bf16 || !use_mfma(e) || Q < 2) return fail(VX_ERR_UNSUPPORTED, "vx_nar_batch needs bf16 MFMA rows and num_quantizers > 1");
+  if (!e->bf16 || !use_mfma(e) || c.num_quantizers < 2) return fail(VX_ERR_UNSUPPORTED, "vx_nar_batch needs bf16 MFMA rows and num_quantizers > 1");
   if (c.flags & VX_FLAG_PRENET) return fail(VX_ERR_UNSUPPORTED, "vx_nar_batch: prenet models run on the batch-1 path only");
-  ON_DEVICE(c.device);
-  std::vector<int> start(n), len(n), aoff(n), toff(n), soff(n);
-  size_t rows = 0, arows = 0, trows = 0, srows = 0;
-  int maxlen = 0;
   for (int b = 0; b < n; ++b) {
     if (S2[b] <= 0 || T[b] <= 0 || P[b] < 0 || !text_nar[b] || !ar_tokens[b] || !codes_out[b] || (P[b] > 0 && !prompts[b]) ||
-        (forced && !forced[b]))
+        (forced_codes && !forced_codes[b]))
       return fail(VX_ERR_ARG, "bad utterance %d", b);
     // per-utterance limits: positions index the sine table (pe_rows rows) separately for text and audio
     if (S2[b] > e->pe_rows || P[b] + T[b] > e->pe_rows)
       return fail(VX_ERR_CAPACITY, "utterance %d: S2=%d / P+T=%d exceed the %d positions of the sine table", b, S2[b], P[b] + T[b], e->pe_rows);
-    start[b] = (int)rows; len[b] = S2[b] + P[b] + T[b];
-    aoff[b] = (int)arows; toff[b] = (int)trows; soff[b] = (int)srows;
-    rows += (size_t)((len[b] + 63) / 64) * 64;
-    arows += P[b] + T[b]; trows += T[b]; srows += S2[b];
-    if (len[b] > maxlen) maxlen = len[b];
   }
-  VXC(ensure_rows(e, rows, arows, srows));
-  VXC(sync_in(e, stream));
-  HIPC(hipEventRecord(e->ev_t[4], e->es));
-  if (!e->d_seg_start) {  // engines created with max_batch == 1 may still batch their NAR stages
-    HIPC(hipMalloc((void**)&e->d_seg_start, BMAX * sizeof(int)));
-    HIPC(hipMalloc((void**)&e->d_seg_len, BMAX * sizeof(int)));
-    e->allocs.push_back(e->d_seg_start); e->allocs.push_back(e->d_seg_len);
-  }
-  HIPC(hipMemcpyAsync(e->d_seg_start, start.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
-  HIPC(hipMemcpyAsync(e->d_seg_len, len.data(), n * sizeof(int), hipMemcpyHostToDevice, e->es));
-  HIPC(hipMemsetAsync(e->X, 0, rows * (size_t)dn * 4, e->es));  // padding rows must stay finite (they feed V^T columns)
-  auto emb = [&](int j) { return W<float>(e, "nar_audio_embeddings." + std::to_string(j) + ".word_embeddings.weight"); };
-  for (int b = 0; b < n; ++b) {
-    long long* idp = e->ids_prompts + (size_t)aoff[b] * Q;   // (P_b, Q) rows; region sized for P+T rows per utterance
-    long long* ids = e->ids_samples + toff[b];
-    if (P[b]) HIPC(hipMemcpyAsync(idp, prompts[b], (size_t)P[b] * Q * 8, hipMemcpyDefault, e->es));
-    HIPC(hipMemcpyAsync(ids, ar_tokens[b], (size_t)T[b] * 8, hipMemcpyDefault, e->es));
-    if (forced) HIPC(hipMemcpyAsync(e->d_fcodes + (size_t)toff[b] * Q, forced[b], (size_t)T[b] * Q * 8, hipMemcpyDefault, e->es));
-    HIPC(hipMemcpyAsync(e->ids_text + soff[b], text_nar[b], (size_t)S2[b] * 8, hipMemcpyDefault, e->es));
-    copy_col_kernel<<<(T[b] + 255) / 256, 256, 0, e->es>>>(ids, e->d_codes + (size_t)toff[b] * Q, T[b], Q, 0);
-    float* ye = e->yemb + (size_t)aoff[b] * dn;
-    if (P[b]) embed_accum_kernel<<<P[b], 256, 0, e->es>>>(idp, Q, 0, emb(0), 1025, dn, ye, P[b], 1);
-    embed_accum_kernel<<<T[b], 256, 0, e->es>>>(ids, 1, 0, emb(0), 1025, dn, ye + (size_t)P[b] * dn, T[b], 1);
-    if (c.prefix_mode != 0 && P[b])
-      for (int j = 1; j < Q; ++j) embed_accum_kernel<<<P[b], 256, 0, e->es>>>(idp, Q, j, emb(j), 1024, dn, ye, P[b], 0);
-  }
-  const float* a_txt = W<float>(e, "nar_text_position.alpha");
-  const float* a_aud = W<float>(e, "nar_audio_position.alpha");
-  e->nseg = n; e->max_seg_len = maxlen;
-  int rc = VX_OK;
-  for (int i = 0; i < Q - 1 && rc == VX_OK; ++i) {
-    for (int b = 0; b < n; ++b) {
-      float* xb = e->X + (size_t)start[b] * dn;
-      embed_pos_kernel<<<S2[b], 256, 0, e->es>>>(e->ids_text + soff[b], 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"),
-                                                 512, dn, a_txt, e->pe_nar, 0, xb, S2[b]);
-      add_pos_kernel<<<P[b] + T[b], 256, 0, e->es>>>(e->yemb + (size_t)aoff[b] * dn, dn, a_aud, e->pe_nar, 0,
-                                                     xb + (size_t)S2[b] * dn, P[b] + T[b]);
-    }
-    rc = run_stack(e, e->nar_l, (int)rows, dn, c.nar_nhead, -1, i, false);
-    if (rc != VX_OK) break;
-    const bool post = c.flags & VX_FLAG_POST_NORM;
-    const float* fw = post ? nullptr : ada_vec(e, i, e->npl * c.nar_num_layers);
-    for (int b = 0; b < n && rc == VX_OK; ++b) {  // final AdaLN (pre-norm only) on the generated rows, compacted to [sum T][dn]
-      const float* xr = e->X + (size_t)(start[b] + S2[b] + P[b]) * dn;
-      bf16* hr = (bf16*)e->Hn + (size_t)toff[b] * dn;
-      rc = post ? cast_rows(e, xr, hr, (size_t)T[b] * dn)
-                : ln_rows(e, xr, W<float>(e, "nar_decoder.norm.norm.weight"), W<float>(e, "nar_decoder.norm.norm.bias"), fw,
-                          fw + dn, hr, T[b], dn);
-    }
-    if (rc != VX_OK) break;
-    const int nseg_keep = e->nseg;
-    e->nseg = 0;  // the predict GEMM below is a plain GEMM
-    rc = gemm_rows(e, e->Hn, W<void>(e, "nar_predict_layers." + std::to_string(i) + ".weight"), nullptr, e->nar_logits,
-                   (int)trows, 1024, dn, GE_PLAIN, true);
-    e->nseg = nseg_keep;
-    if (rc != VX_OK) break;
-    argmax_rows_kernel<<<((int)trows + 3) / 4, 256, 0, e->es>>>(e->nar_logits, 1024, (int)trows, e->ids_samples, e->d_codes, Q, i + 1);
-    if (forced && i < Q - 2)  // teacher forcing: the next stage sees the caller's codes of this stage (all segments at once)
-      pick_col_kernel<<<((int)trows + 255) / 256, 256, 0, e->es>>>(e->d_fcodes, Q, i + 1, e->ids_samples, (int)trows);
-    if (i < Q - 2)
-      for (int b = 0; b < n; ++b) {
-        float* ye = e->yemb + (size_t)aoff[b] * dn;
-        if (c.prefix_mode == 0 && P[b])
-          embed_accum_kernel<<<P[b], 256, 0, e->es>>>(e->ids_prompts + (size_t)aoff[b] * Q, Q, i + 1, emb(i + 1), 1024, dn, ye, P[b], 0);
-        embed_accum_kernel<<<T[b], 256, 0, e->es>>>(e->ids_samples + toff[b], 1, 0, emb(i + 1), 1024, dn, ye + (size_t)P[b] * dn, T[b], 0);
-      }
-  }
-  e->nseg = 0;
-  VXC(rc);
-  HIPC(hipGetLastError());
-  HIPC(hipEventRecord(e->ev_t[5], e->es));
-  for (int b = 0; b < n; ++b)
-    HIPC(hipMemcpyAsync(codes_out[b], e->d_codes + (size_t)toff[b] * Q, (size_t)T[b] * Q * 8, hipMemcpyDefault, e->es));
-  HIPC(hipStreamSynchronize(e->es));
-  float ms = 0.f;
-  HIPC(hipEventElapsedTime(&ms, e->ev_t[4], e->ev_t[5]));
-  e->t_nar = ms;
-  gemm_collect(e);
-  e->last_T = (int)trows; e->last_N = (int)rows;
-  VXC(sync_out(e, stream));
-  return VX_OK;
-}
-
-extern "C" int vx_nar_batch(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
-                            const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens,
-                            const int32_t* T, int64_t* const* codes_out, void* stream) {
-  return nar_batch_impl(e, n, text_nar, S2, prompts, P, ar_tokens, T, codes_out, nullptr, stream);
-}
-extern "C" int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
-                               const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens,
-                               const int32_t* T, int64_t* const* codes_out, const int64_t* const* forced_codes, void* stream) {
-  return nar_batch_impl(e, n, text_nar, S2, prompts, P, ar_tokens, T, codes_out, forced_codes, stream);
+  return nar_run(e, n, true, text_nar, S2, prompts, P, ar_tokens, T, codes_out, forced_codes, stream);
 }
 
 extern "C" int vx_get_timings(vx_engine* e, double* out, int32_t n) {
