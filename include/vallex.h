@@ -257,6 +257,19 @@ int vx_op_layernorm_mx(const float* x, const float* gamma, const float* beta, co
                        void* s_out, int32_t rows, int32_t d, void* stream);
 int vx_op_attention(int32_t prec, int32_t use_mfma, const void* qkv, void* out, int32_t rows, int32_t nhead,
                     int32_t hd, int32_t text_len_for_ar_mask /* <0: no mask */, void* stream);
+/* The segmented flash attention of batched NAR / batched prefill: qkv (rows, 3 nhead hd) bf16, hd == 64; segment z is rows
+ * [seg_start[z], seg_start[z] + seg_len[z]) (starts multiples of 64, increasing, not overlapping), with its own prefix mask
+ * seg_text[z] in [0, seg_len[z]] (seg_text NULL: no mask).  Segment arrays on the host; out rows outside the segments are not
+ * written.  A bad layout is VX_ERR_ARG before any HIP call.  Synchronises `stream`. */
+int vx_op_attention_segs(const void* qkv, void* out, int32_t rows, int32_t nhead, int32_t hd, int32_t nseg, const int32_t* seg_start,
+                         const int32_t* seg_len, const int32_t* seg_text /* nullable */, void* stream);
+/* The batched decode step's attention over B slot caches (kv_fp8: the e4m3 codes + E8M0 scale bytes, else bf16): q (B, 64 nhead)
+ * fp32, out (B, 64 nhead) bf16; slot b's K at kv + b slot_stride, V at + v_offset (elements), element (h ctx_max + j) 64 + c,
+ * scales at that index >> 4 of kv_scale.  ctx / done: host arrays; slot b attends to keys [0, ctx[b]); done slots are skipped
+ * (their out rows are not written).  Synchronises `stream`. */
+int vx_op_attn_slots(int32_t kv_fp8, const float* q, const void* kv, const void* kv_scale, int64_t slot_stride, int64_t v_offset,
+                     int32_t ctx_max, int32_t B, int32_t nhead, const int32_t* ctx, const int32_t* done /* nullable */, void* out,
+                     void* stream);
 int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
                  int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 int vx_op_convert_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);

@@ -151,3 +151,58 @@ def test_state_dict_layout_matches_reference(case):
     for k, shape, dtype in ref["keys"]:
         assert str(sd[k].dtype).replace("torch.", "") == dtype, k
     assert sorted((a, b) for a, b in ref["shared"]) == sorted(tied_keys(cfg).items())  # valle.py:261-271
+
+
+def _i32(vals):
+    import ctypes as C
+
+    return (C.c_int32 * len(vals))(*vals)
+
+
+@pytest.mark.parametrize("starts,lens,texts,match", [
+    ([0, 96], [64, 10], None, "multiple of 64"),          # unaligned start
+    ([0, 64], [100, 10], None, "overlaps"),               # segment 0 runs into segment 1
+    ([128, 0], [10, 10], None, "overlaps or precedes"),   # starts out of order
+    ([0, 64], [64, 0], None, "empty"),                    # empty segment
+    ([0, 64], [64, 200], None, "outside"),                # runs past the buffer (rows = 256)
+    ([0, 64], [64, 10], [0, 11], "seg_text"),             # text longer than the segment
+    ([0, 64], [64, 10], [-1, 3], "seg_text"),
+])
+def test_attention_segs_rejects_bad_layout_without_gpu(lib, starts, lens, texts, match):
+    """vx_op_attention_segs validates the segment layout on the host before any HIP call (null device pointers are never used)."""
+    rc = lib.vx_op_attention_segs(None, None, 256, 4, 64, len(starts), _i32(starts), _i32(lens), None if texts is None else _i32(texts),
+                                  None)
+    assert rc == 1 and match.encode() in lib.vx_last_error()
+
+
+def test_attention_segs_rejects_bad_shape_without_gpu(lib):
+    one = _i32([0])
+    assert lib.vx_op_attention_segs(None, None, 256, 8, 32, 1, one, _i32([64]), None, None) == 5  # head_dim 32: unsupported
+    assert b"head_dim" in lib.vx_last_error()
+    for nseg in (0, 65):
+        z = _i32([64 * i for i in range(max(nseg, 1))])
+        assert lib.vx_op_attention_segs(None, None, 65 * 64, 4, 64, nseg, z, _i32([1] * max(nseg, 1)), None, None) == 1
+        assert b"nseg" in lib.vx_last_error()
+
+
+@pytest.mark.parametrize("B,ctx,done,stride,voff,match", [
+    (2, [0, 5], None, 4096, 2048, "ctx[0]"),              # empty context on a live slot
+    (2, [5, 33], None, 4096, 2048, "ctx[1]"),             # ctx > ctx_max
+    (65, [1] * 65, None, 4096, 2048, "B 65"),             # more slots than BMAX
+    (0, [1], None, 4096, 2048, "B 0"),
+    (2, [5, 5], None, 4096, 2040, "multiples of 16"),     # V offset off the fp8 scale grid
+    (2, [5, 5], None, 4100, 2048, "multiples of 16"),
+])
+def test_attn_slots_rejects_bad_arguments_without_gpu(lib, B, ctx, done, stride, voff, match):
+    for fp8 in (0, 1):
+        rc = lib.vx_op_attn_slots(fp8, None, None, None if not fp8 else 8, stride, voff, 32, B, 1, _i32(ctx),
+                                  None if done is None else _i32(done), None, None)
+        assert rc == 1 and match.encode() in lib.vx_last_error(), (fp8, lib.vx_last_error())
+
+
+def test_attn_slots_done_slots_skip_the_ctx_check_without_gpu(lib):
+    """ctx is only checked on live slots (a done slot's ctx is never read); the fp8 form needs its scale bytes."""
+    rc = lib.vx_op_attn_slots(0, None, None, None, 4096, 2048, 32, 2, 1, _i32([0, 40]), _i32([1, 0]), None, None)
+    assert rc == 1 and b"ctx[1]" in lib.vx_last_error()
+    rc = lib.vx_op_attn_slots(1, None, None, None, 4096, 2048, 32, 1, 1, _i32([5]), None, None, None)
+    assert rc == 1 and b"kv_scale" in lib.vx_last_error()

@@ -2556,6 +2556,90 @@ extern "C" int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float
   return VX_OK;
 }
 
+// Segmented flash attention (the batched NAR / batched prefill launch of attn_rows) on caller rows: nseg segments of a bf16 qkv
+// buffer of `rows` rows, described by host arrays.  seg_text == NULL: no mask; otherwise each segment's prefix mask.
+extern "C" int vx_op_attention_segs(const void* qkv, void* out, int32_t rows, int32_t nhead, int32_t hd, int32_t nseg,
+                                    const int32_t* seg_start, const int32_t* seg_len, const int32_t* seg_text, void* stream) {
+  if (hd != 64) return fail(VX_ERR_UNSUPPORTED, "attention_segs: head_dim %d", hd);
+  if (nhead < 1 || rows < 1) return fail(VX_ERR_ARG, "attention_segs: nhead %d, rows %d", nhead, rows);
+  if (nseg < 1 || nseg > BMAX) return fail(VX_ERR_ARG, "attention_segs: nseg %d outside [1, %d]", nseg, BMAX);
+  if (!seg_start || !seg_len) return fail(VX_ERR_ARG, "attention_segs: null segment array");
+  int max_len = 0;
+  for (int z = 0; z < nseg; ++z) {
+    const long long st = seg_start[z], ln = seg_len[z];
+    if (st < 0 || st % 64) return fail(VX_ERR_ARG, "attention_segs: segment %d starts at row %lld, not a multiple of 64", z, st);
+    if (z > 0 && st < (long long)seg_start[z - 1] + seg_len[z - 1])
+      return fail(VX_ERR_ARG, "attention_segs: segment %d (start %lld) overlaps or precedes segment %d", z, st, z - 1);
+    if (ln < 1 || st + ln > rows) return fail(VX_ERR_ARG, "attention_segs: segment %d [%lld, %lld + %lld) outside [0, %d) or empty", z, st, st, ln, rows);
+    if (seg_text && (seg_text[z] < 0 || seg_text[z] > ln))
+      return fail(VX_ERR_ARG, "attention_segs: seg_text[%d] = %d outside [0, len %lld]", z, seg_text[z], ln);
+    max_len = std::max(max_len, (int)ln);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int d = nhead * hd;
+  const int vt_ld = ((rows + 63) / 64) * 64 + 64;  // as the engine (the key-group split reads one tile past the last)
+  struct Scratch {  // freed on every exit path
+    bf16* vt = nullptr;
+    int* segs = nullptr;
+    ~Scratch() { (void)hipFree(vt); (void)hipFree(segs); }
+  } t;
+  HIPC(hipMalloc((void**)&t.vt, (size_t)d * vt_ld * 2));
+  HIPC(hipMalloc((void**)&t.segs, (size_t)3 * nseg * sizeof(int)));
+  HIPC(hipMemcpyAsync(t.segs, seg_start, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(t.segs + nseg, seg_len, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  if (seg_text) HIPC(hipMemcpyAsync(t.segs + 2 * nseg, seg_text, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  vt_from_qkv_kernel<<<dim3((vt_ld + 255) / 256, d), 256, 0, s>>>((const bf16*)qkv, t.vt, rows, d, vt_ld);
+  const int rc = mfma_attn_dispatch((const bf16*)qkv, t.vt, vt_ld, (bf16*)out, rows, d, nhead, -1, s, t.segs, t.segs + nseg, nseg,
+                                    max_len, seg_text ? t.segs + 2 * nseg : nullptr);
+  const hipError_t le = hipGetLastError();
+  const hipError_t se = hipStreamSynchronize(s);  // the scratch is in use until the stream has drained, whatever happened
+  if (rc) return fail(VX_ERR_UNSUPPORTED, "attention_segs: rows x 3 d or d x vt_ld exceed 4 GB");
+  HIPC(le);
+  HIPC(se);
+  return VX_OK;
+}
+
+// The batched decode step's single-query attention (attn_batch_kernel / attn_batch8_kernel) on a caller cache of B slots, indexed
+// as the engine's slot caches: slot b at b * slot_stride elements, V at v_offset, element (h * ctx_max + j) * 64 + c; fp8 scale
+// bytes at that index >> 4 of kv_scale.  ctx / done: host arrays (done may be NULL: every slot live).
+extern "C" int vx_op_attn_slots(int32_t kv_fp8, const float* q, const void* kv, const void* kv_scale, int64_t slot_stride,
+                                int64_t v_offset, int32_t ctx_max, int32_t B, int32_t nhead, const int32_t* ctx, const int32_t* done,
+                                void* out, void* stream) {
+  if (B < 1 || B > BMAX) return fail(VX_ERR_ARG, "attn_slots: B %d outside [1, %d]", B, BMAX);
+  if (nhead < 1 || ctx_max < 1) return fail(VX_ERR_ARG, "attn_slots: nhead %d, ctx_max %d", nhead, ctx_max);
+  if (v_offset < 0 || slot_stride < 0 || v_offset % 16 || slot_stride % 16)
+    return fail(VX_ERR_ARG, "attn_slots: v_offset %lld and slot_stride %lld must be non-negative multiples of 16", (long long)v_offset,
+                (long long)slot_stride);
+  if (!ctx) return fail(VX_ERR_ARG, "attn_slots: null ctx");
+  if (kv_fp8 && !kv_scale) return fail(VX_ERR_ARG, "attn_slots: fp8 caches need kv_scale");
+  std::vector<ArState> h(B);  // zero-initialised: only row and done are read
+  for (int b = 0; b < B; ++b) {
+    h[b].done = done ? (done[b] != 0) : 0;
+    if (!h[b].done && (ctx[b] < 1 || ctx[b] > ctx_max))
+      return fail(VX_ERR_ARG, "attn_slots: ctx[%d] = %d outside [1, ctx_max %d]", b, ctx[b], ctx_max);
+    h[b].row = ctx[b] - 1;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int d = 64 * nhead;
+  struct Scratch {  // freed on every exit path
+    ArState* st = nullptr;
+    ~Scratch() { (void)hipFree(st); }
+  } t;
+  HIPC(hipMalloc((void**)&t.st, (size_t)B * sizeof(ArState)));
+  HIPC(hipMemcpyAsync(t.st, h.data(), (size_t)B * sizeof(ArState), hipMemcpyHostToDevice, s));
+  if (kv_fp8)
+    attn_batch8_kernel<64><<<dim3(nhead, B), 256, 0, s>>>(q, (const uint8_t*)kv, (const uint8_t*)kv_scale, (size_t)slot_stride,
+                                                          (size_t)v_offset, t.st, ctx_max, d, 0.125f, (bf16*)out);
+  else
+    attn_batch_kernel<64><<<dim3(nhead, B), 256, 0, s>>>(q, (const bf16*)kv, (size_t)slot_stride, (size_t)v_offset, t.st, ctx_max, d,
+                                                         0.125f, (bf16*)out);
+  const hipError_t le = hipGetLastError();
+  const hipError_t se = hipStreamSynchronize(s);
+  HIPC(le);
+  HIPC(se);
+  return VX_OK;
+}
+
 #ifdef VX_PROBES
 #include "probe_entry.hpp"
 #endif

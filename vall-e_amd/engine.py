@@ -80,6 +80,9 @@ _SIGS = {
     "vx_op_gemm_mx": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p] * 3),
     "vx_op_layernorm_mx": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_void_p]),
     "vx_op_attention": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
+    "vx_op_attention_segs": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3 + [C.c_void_p]),
+    "vx_op_attn_slots": (C.c_int, [C.c_int32] + [C.c_void_p] * 3 + [C.c_int64, C.c_int64] + [C.c_int32] * 3
+                         + [C.POINTER(C.c_int32)] * 2 + [C.c_void_p, C.c_void_p]),
     "vx_op_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "vx_op_convert_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
@@ -473,6 +476,45 @@ def op_attention(qkv, nhead, text_len=-1, mfma=False):
     out = torch.empty((rows, d), dtype=qkv.dtype, device=qkv.device)
     _check(lib.vx_op_attention(_prec(qkv), int(mfma), _ptr(qkv), _ptr(out), rows, nhead, d // nhead, text_len,
                                current_stream_ptr(qkv.device)))
+    return out
+
+
+def _i32(vals):
+    return None if vals is None else (C.c_int32 * len(vals))(*[int(v) for v in vals])
+
+
+def op_attention_segs(qkv, nhead, starts, lens, texts=None, out=None):
+    """Segmented flash attention (vx_op_attention_segs) over bf16 qkv (rows, 3 d): segment z = rows [starts[z], starts[z] + lens[z]),
+    prefix mask texts[z] (None: no mask).  `out` (rows, d) bf16 may be supplied: rows outside the segments are left as they are."""
+    lib = load_library()
+    assert qkv.dtype == torch.bfloat16
+    rows, d3 = qkv.shape
+    d = d3 // 3
+    if out is None:
+        out = torch.zeros((rows, d), dtype=qkv.dtype, device=qkv.device)
+    assert out.dtype == torch.bfloat16 and out.shape == (rows, d)
+    _check(lib.vx_op_attention_segs(_ptr(qkv), _ptr(out), rows, nhead, d // nhead, len(starts), _i32(starts), _i32(lens), _i32(texts),
+                                    current_stream_ptr(qkv.device)))
+    return out
+
+
+def op_attn_slots(q, kv, kv_scale, ctx, done, ctx_max, out=None, slot_stride=None, v_offset=None):
+    """The batched decode attention (vx_op_attn_slots) of B = len(ctx) slots: q (B, d) fp32; kv bf16 (bf16 caches) or uint8 e4m3
+    codes with kv_scale uint8 scale bytes (fp8 caches).  kv may be a strided view (B, 2, H, ctx_max, 64) - one layer of a larger
+    cache - whose data pointer is the layer base; slot_stride / v_offset (elements) default to its strides of dims 0 and 1, and
+    kv_scale's data pointer is the matching scale base.  done (None: all live): slots whose `out` rows are left as they are."""
+    lib = load_library()
+    B, d = q.shape
+    assert q.dtype == torch.float32 and q.is_contiguous() and len(ctx) == B and (done is None or len(done) == B)
+    fp8 = kv.dtype == torch.uint8
+    assert fp8 == (kv_scale is not None)
+    slot_stride = kv.stride(0) if slot_stride is None else slot_stride
+    v_offset = kv.stride(1) if v_offset is None else v_offset
+    if out is None:
+        out = torch.zeros((B, d), dtype=torch.bfloat16, device=q.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == (B, d)
+    _check(lib.vx_op_attn_slots(int(fp8), _ptr(q), kv.data_ptr(), None if kv_scale is None else kv_scale.data_ptr(), slot_stride,
+                                v_offset, ctx_max, B, d // 64, _i32(ctx), _i32(done), _ptr(out), current_stream_ptr(q.device)))
     return out
 
 
