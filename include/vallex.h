@@ -69,11 +69,15 @@ enum vx_flags {
                                TransformerDecoderLayers (modules/transformer.py:409-601) - causal / unmasked self-attention over
                                the AUDIO rows only, cross-attention over the embedded text, three norms per layer.  Same entry
                                points (VALLF.inference, valle.py:566-710, has VALLE.inference's signature); the state_dict gains
-                               layers.N.multihead_attn.* and layers.N.norm3.*.  Batch-1 path only */
+                               layers.N.multihead_attn.* and layers.N.norm3.*.  With max_batch >= 2 (pre-norm, no prenets,
+                               head_dim 64, d_model % 128 == 0, bf16 precision, bf16 slot caches) the slots decode VALL-F too:
+                               every slot keeps its own text memory (2 L max_text d bf16).  VALL-F slots are prefilled one by
+                               one (vx_batch_prefill, VX_ADMIT_PER_SLOT) and their NAR stages run per utterance (vx_nar);
+                               vx_batch_prefill_all, VX_ADMIT_BATCHED and vx_nar_batch return VX_ERR_UNSUPPORTED */
   VX_FLAG_KV_FP8 = 64       /* the slot caches of the batched decode (vx_batch_*) hold OCP e4m3 codes with one E8M0 scale per
                                16 channels of a K / V row instead of bf16 values: 0.53x the bytes the batched
                                step's attention reads.  Needs max_batch >= 2, VX_PREC_BF16 or VX_PREC_FP8_NAR, head_dim 64 and a
-                               pre-norm VALL-E without prenets (else VX_ERR_UNSUPPORTED, before any HIP call).  The batch-1 cache
+                               pre-norm VALL-E without prenets (else VX_ERR_UNSUPPORTED, before any HIP call; VALL-F included).  The batch-1 cache
                                (vx_ar_*) stays bf16 */
 };
 
@@ -166,12 +170,13 @@ int vx_nar_continual(vx_engine* e, const int64_t* text_nar, int32_t S2, const in
  * vx_batch_prefill = vx_ar_prefill into a slot; vx_batch_decode runs the shared step until every one of
  * slots [0, n_slots) has stopped (params[i] for slot i; exp_noise / forced must be DEVICE pointers that stay
  * valid during the call); vx_batch_result = vx_ar_result of a slot.  The NAR stages then run per utterance
- * with vx_nar. */
+ * with vx_nar.  VALL-F engines (VX_FLAG_VALLF): vx_batch_prefill also writes the slot's text memory; the step adds each layer's
+ * cross-attention over it. */
 int vx_batch_prefill(vx_engine* e, int32_t slot, const int64_t* text, int32_t S, const int64_t* prompt_cb0, int32_t P,
                      void* stream);
 /* All n slots' prefills in one pass over the concatenated rows (slot z = utterance z): same contract as n calls of
- * vx_batch_prefill(z, text[z], S[z], prompt_cb0[z], P[z]); bf16 engines only.  The pointer arrays and S / P live on
- * the host, text[z] / prompt_cb0[z] may be host or device pointers. */
+ * vx_batch_prefill(z, text[z], S[z], prompt_cb0[z], P[z]); bf16 VALL-E engines only (VALL-F: VX_ERR_UNSUPPORTED).  The
+ * pointer arrays and S / P live on the host, text[z] / prompt_cb0[z] may be host or device pointers. */
 int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S,
                          const int64_t* const* prompt_cb0, const int32_t* P, void* stream);
 int vx_batch_decode(vx_engine* e, int32_t n_slots, const vx_decode_params* params, void* stream);
@@ -189,6 +194,7 @@ int vx_batch_result(vx_engine* e, int32_t slot, int64_t* tokens, int32_t capacit
  *                   A slot outside [0, max_batch) or given twice: VX_ERR_ARG; a live or stopped-unread slot: VX_ERR_STATE.
  *                   mode VX_ADMIT_BATCHED prefills all n in one pass over the concatenated rows (one synchronisation);
  *                   VX_ADMIT_PER_SLOT runs vx_batch_prefill's path per slot (one synchronisation each; bitwise the static path).
+ *                   VALL-F engines admit per slot only: VX_ADMIT_BATCHED returns VX_ERR_UNSUPPORTED.
  *                   exp_noise / forced must be DEVICE pointers that stay valid until the slot's result is read.
  *   vx_batch_run    replays the step until at least min_stopped (< 1: 1) live slots have stopped in this call, or none is left
  *                   live; polls the stop flags every poll_steps steps (<= 0: the default).  stopped (capacity
@@ -203,7 +209,7 @@ int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, const int64_t*
 int vx_batch_run(vx_engine* e, int32_t min_stopped, int32_t poll_steps, int32_t* stopped, int32_t* n_stopped, void* stream);
 
 /* The NAR stages of n (<= 32) utterances in one pass: rows are concatenated so the GEMMs run at M ~ n x 1k.
- * Arguments are arrays of n pointers / sizes with the meaning of vx_nar's. */
+ * Arguments are arrays of n pointers / sizes with the meaning of vx_nar's.  VALL-E only (VALL-F: VX_ERR_UNSUPPORTED). */
 int vx_nar_batch(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
                  const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens, const int32_t* T,
                  int64_t* const* codes_out, void* stream);
@@ -270,6 +276,12 @@ int vx_op_attention_segs(const void* qkv, void* out, int32_t rows, int32_t nhead
 int vx_op_attn_slots(int32_t kv_fp8, const float* q, const void* kv, const void* kv_scale, int64_t slot_stride, int64_t v_offset,
                      int32_t ctx_max, int32_t B, int32_t nhead, const int32_t* ctx, const int32_t* done /* nullable */, void* out,
                      void* stream);
+/* The VALL-F slot step's cross-attention over B slots' text memory: q (B, 64 nhead) fp32, mem bf16, out (B, 64 nhead) bf16; slot b's
+ * K at mem + b slot_stride, V at + v_offset (elements, multiples of 8), element (h max_text + j) 64 + c.  len / done: host arrays;
+ * slot b attends to keys [0, len[b]), 1 <= len[b] <= max_text; done slots are skipped (their out rows are not written).
+ * Synchronises `stream`. */
+int vx_op_attn_mem_slots(const float* q, const void* mem, int64_t slot_stride, int64_t v_offset, int32_t max_text, int32_t B,
+                         int32_t nhead, const int32_t* len, const int32_t* done /* nullable */, void* out, void* stream);
 int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
                  int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 int vx_op_convert_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);

@@ -3,6 +3,8 @@
     python tools/bench_stream.py [--n 128] [--slots 32] [--poll 4,8,16,32] [--refill 1,2,4,8]
     python tools/bench_stream.py --kv-cache bf16,fp8 [--slots 64 --text-len 94] [--reps 2]
     python tools/bench_stream.py --ab-half-done [--lib path/to/libvallex.so]
+    python tools/bench_stream.py --model-name VALL-F [...]
+    python tools/bench_stream.py --step-times [--model-name VALL-F,VALL-E] [--reps 3]
 
 Default mode: a seeded queue of --n utterances, S uniform in [10, 94], P = 225 (synthetic weights: every utterance stops by the
 length rule, T = 16 S + 1 frames), decoded end to end (AR + 7 NAR stages) once through inference_batch, group by group, and once
@@ -14,7 +16,12 @@ from queue start to its codes, the device time per batched step (step_us) and th
 queue and the runs alternate between them rep by rep (static, then stream, per format).
 
 --ab-half-done: device time per batched step with all 32 slots live, and with half of them done (teacher-forced lengths 753 and
-1), through vx_batch_decode, so that the same measurement runs on a library without the continuous-batching entry points."""
+1), through vx_batch_decode, so that the same measurement runs on a library without the continuous-batching entry points.
+
+--model-name: VALL-E (default) or VALL-F (the cross-attention variant; its slots are prefilled and admitted one by one and its NAR
+stages run per utterance).  --step-times: for each of the comma-separated model names, in one process, the device time per
+batched step with all slots live (S = 47, P = 225, 753 teacher-forced tokens, vx_batch_decode) and of the batch-1 step on the same
+utterance (vx_ar_decode; not with --skip-batch1), --reps times each after a warm-up."""
 import argparse
 import json
 import os
@@ -25,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def model(args, max_audio, kv_cache="bf16"):
+def model(args, max_audio, kv_cache="bf16", name=None):
     if args.lib:  # a library built from another revision: bind only the entry points it exports (the static batched path)
         import ctypes as C
 
@@ -40,12 +47,14 @@ def model(args, max_audio, kv_cache="bf16"):
 
         ge.build()
     from valle_amd.config import ModelConfig
-    from valle_amd.models import VALLE
+    from valle_amd.models import VALLE, VALLF
     from valle_amd.weights import synthetic_state_dict
 
-    cfg = ModelConfig(decoder_dim=1024, nhead=16, num_decoder_layers=12, prefix_mode=1)
-    m = VALLE(1024, 16, 12, prefix_mode=1, precision=args.precision, max_text=128, max_audio=max_audio, print_eos=False,
-              max_batch=args.slots, **({"kv_cache": kv_cache} if kv_cache != "bf16" else {}))
+    name = name or args.model_name
+    cls = VALLF if name.lower() in ("vall-f", "vallf") else VALLE
+    cfg = ModelConfig(model_name=cls.MODEL_NAME, decoder_dim=1024, nhead=16, num_decoder_layers=12, prefix_mode=1)
+    m = cls(1024, 16, 12, prefix_mode=1, precision=args.precision, max_text=128, max_audio=max_audio, print_eos=False,
+            max_batch=args.slots, **({"kv_cache": kv_cache} if kv_cache != "bf16" else {}))
     m.load_state_dict(synthetic_state_dict(cfg, 0))
     return m.to("cuda:0").eval()
 
@@ -157,7 +166,7 @@ def run_queue(args):
         ref = m.inference_batch(utts[:B], top_k=10, seeds=seeds[:B], batched_prefill=False)
         got = dict(m.inference_stream(utts[:B], top_k=10, seeds=seeds[:B], batched_admit=False))
         same[kv] = all(torch.equal(ref[i][0, :, 0], got[i][0, :, 0]) for i in range(len(ref)))
-    return dict(mode="queue", geometry=f"d=1024 nhead=16 L=12 {args.precision}", slots=B, n=args.n,
+    return dict(mode="queue", model=args.model_name, geometry=f"d=1024 nhead=16 L=12 {args.precision}", slots=B, n=args.n,
                 S_range=[args.text_len] * 2 if args.text_len else [10, 94], P=225, frames=sum(frames),
                 ar_codes_equal_static=same if len(kvs) > 1 else same[kvs[0]], runs=runs)
 
@@ -189,6 +198,47 @@ def run_ab(args):
     return dict(mode="ab_half_done", lib=args.lib or "libvallex.so", kv_cache=kv, slots=B, S=47, P=225, T=753, **out)
 
 
+def run_step_times(args):
+    import torch
+    from valle_amd.weights import synthetic_inputs
+
+    B = args.slots
+    utts = [synthetic_inputs(47, 225, 8, seed=2000 + i) for i in range(B)]
+    g = torch.Generator().manual_seed(3)
+    full = [torch.randint(0, 1024, (753,), generator=g) for _ in range(B)]
+    res = dict(mode="step_times", slots=B, S=47, P=225, T=753, models={})
+    for name in args.model_name.split(","):
+        m = model(args, 1024, "bf16", name)
+        eng = m.engine()
+        slot_us, b1_us = [], []
+        for rep in range(args.reps + 1):  # the first is warm-up (graph capture)
+            for b, u in enumerate(utts):
+                eng.batch_prefill(b, u[0][0], u[2][0, :, 0].contiguous())
+            eng.batch_decode(B, top_k=10, forced=[f.cuda() for f in full])
+            t = eng.timings()
+            if rep:
+                slot_us.append(1e3 * t["batch_decode_ms"] / t["batch_launches"])
+            if args.skip_batch1:
+                continue
+            eng.ar_prefill(utts[0][0][0], utts[0][2][0, :, 0].contiguous())
+            eng.ar_decode(top_k=10, forced=full[0])
+            t = eng.timings()
+            if rep:
+                b1_us.append(1e3 * t["decode_ms"] / t["launches"])
+        s_mean = sum(slot_us) / len(slot_us)
+        if args.skip_batch1:
+            res["models"][name] = dict(slot_step_us=[round(v, 2) for v in slot_us], slot_step_mean_us=round(s_mean, 2))
+            continue
+        b_mean = sum(b1_us) / len(b1_us)
+        res["models"][name] = dict(slot_step_us=[round(v, 2) for v in slot_us], slot_step_mean_us=round(s_mean, 2),
+                                   batch1_step_us=[round(v, 2) for v in b1_us], batch1_step_mean_us=round(b_mean, 2),
+                                   slot_tok_per_s=round(B * 1e6 / s_mean, 1), batch1_tok_per_s=round(1e6 / b_mean, 1),
+                                   slot_vs_batch1_tok_per_s=round(B * b_mean / s_mean, 2))
+        del m, eng
+        torch.cuda.synchronize()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=128)
@@ -202,10 +252,13 @@ def main():
     ap.add_argument("--kv-cache", default="bf16", help="slot-cache formats, comma-separated: bf16, fp8 (both: an A/B on one queue)")
     ap.add_argument("--precision", default="bf16", help="bf16 | fp8nar")
     ap.add_argument("--text-len", type=int, default=None, help="every utterance S = this (default: S uniform in [10, 94])")
+    ap.add_argument("--model-name", default="VALL-E", help="VALL-E | VALL-F (--step-times: comma-separated)")
+    ap.add_argument("--step-times", action="store_true")
+    ap.add_argument("--skip-batch1", action="store_true", help="--step-times: the batched step only (e.g. under a kernel trace)")
     args = ap.parse_args()
     if not args.kv_cache or any(kv not in ("bf16", "fp8") for kv in args.kv_cache.split(",")):
         ap.error("--kv-cache: comma-separated bf16 / fp8")
-    res = run_ab(args) if args.ab_half_done else run_queue(args)
+    res = run_ab(args) if args.ab_half_done else run_step_times(args) if args.step_times else run_queue(args)
     print(json.dumps(res))
 
 

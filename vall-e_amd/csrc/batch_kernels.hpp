@@ -1,8 +1,9 @@
 // Batched AR decode: up to 32 utterances ("slots") advance one token per step and share ONE stream of
 // the 304 MB of weights (BASELINE configs[2]: padded per-slot KV cache, hipGraph-captured step).
 // Per layer: ln_batch -> bgemm(QKV) -> attn_batch -> bgemm(out, partial) -> ln_batch(+partials) ->
-// bgemm(FFN1) -> bgemm(FFN2, partial); the partial sums of the two N = d GEMMs are reduced, in a fixed
-// order, by the LayerNorm kernel that follows them anyway.
+// bgemm(FFN1) -> bgemm(FFN2, partial); the partial sums of the N = d GEMMs are reduced, in a fixed
+// order, by the LayerNorm kernel that follows them anyway.  VALL-F layers insert their cross-attention after the second
+// ln_batch: bgemm(query, BE_BIAS) -> attn_batch<MEM> over the slot's text memory -> bgemm(out, partial) -> ln_batch(+partials).
 #pragma once
 #include "common.hpp"
 #include "ar_kernels.hpp"
@@ -16,17 +17,18 @@ typedef __bf16 bf16x8b_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 // BE_LOGITS_MAP: BE_LOGITS for the rows of a batched prefill - A row z belongs to slot slot_map[z]
-enum BgemmEpi { BE_QKV = 0, BE_RELU = 1, BE_PARTIAL = 2, BE_LOGITS = 3, BE_LOGITS_MAP = 4 };
+// BE_BIAS: q = A W^T + bias as fp32 rows (N columns), every row < B (the VALL-F cross-attention query)
+enum BgemmEpi { BE_QKV = 0, BE_RELU = 1, BE_PARTIAL = 2, BE_LOGITS = 3, BE_LOGITS_MAP = 4, BE_BIAS = 5 };
 
 struct BgemmArgs {
   const bf16* A;      // (32, K) activations, rows >= B hold finite stale values
   const bf16* W;      // (N, K)
-  const float* bias;  // (N,) [BE_QKV, BE_RELU]
+  const float* bias;  // (N,) [BE_QKV, BE_RELU, BE_BIAS]
   int N, K, B;
   int kgroups;        // K split over workgroups (BE_PARTIAL); 1 otherwise
   const ArState* st;  // (32,) per-slot state
   // outputs
-  float* q;           // BE_QKV: (32, d)
+  float* q;           // BE_QKV: (32, d); BE_BIAS: (32, N)
   bf16* kv;           // BE_QKV: this layer's cache base of slot 0; slot stride kv_slot_stride elements
   size_t kv_slot_stride, kv_v_offset;  // elements
   int d, hd, ctx_max;
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
   const bf16* ap = A_ + (size_t)c * K + kbeg + 8 * g;
   // epilogue operands first (clamped, unconditional): fetched after the K loop they are one more exposed memory round trip
   float bias_v = 0.f;
-  if (EPI == BE_QKV || EPI == BE_RELU) bias_v = a.bias[min(n0 + c, a.N - 1)];
+  if (EPI == BE_QKV || EPI == BE_RELU || EPI == BE_BIAS) bias_v = a.bias[min(n0 + c, a.N - 1)];
   int st_done[NH], st_row[NH];  // st_row: KV row (BE_QKV) / pass index of the logits row being produced (BE_LOGITS trace)
 #pragma unroll
   for (int u = 0; u < NH; ++u) {
@@ -151,6 +153,8 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const bf16* __restrict__ A_,
       a.part[((size_t)kg * BMAX + b) * a.N + n] = x;
     } else if (EPI == BE_RELU) {
       a.f[(size_t)b * a.N + n] = (bf16)fmaxf(x + bias_v, 0.f);
+    } else if (EPI == BE_BIAS) {
+      a.q[(size_t)b * a.N + n] = x + bias_v;
     } else if (EPI == BE_LOGITS || EPI == BE_LOGITS_MAP) {
       const int sb = EPI == BE_LOGITS_MAP ? a.slot_map[b] : b;
       if (!st_done[u]) {
@@ -239,7 +243,9 @@ __global__ __launch_bounds__(256) void ln_batch_map_kernel(float* __restrict__ x
 // Single-query attention of every (slot, head): grid = (nhead, B), one workgroup walks all cached keys of its
 // head (running max / sum across passes) and writes the normalised output as the bf16 A operand of the
 // out-projection.  Same inner structure as attn_decode_kernel.
-template <int HD>
+// MEM (VALL-F cross-attention): the keys are the slot's text memory, st[slot].S of them (kv / kv_slot_stride / ctx_max describe
+// the memory buffer) instead of the st[slot].row + 1 cached self-attention keys.
+template <int HD, bool MEM = false>
 __global__ __launch_bounds__(256) void attn_batch_kernel(const float* __restrict__ q, const bf16* __restrict__ kv,
                                                          size_t kv_slot_stride, size_t kv_v_offset,
                                                          const ArState* __restrict__ st, int ctx_max, int d, float scale,
@@ -252,7 +258,7 @@ __global__ __launch_bounds__(256) void attn_batch_kernel(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sub = lane % LPK, grp = lane / LPK;
   const int done = st[slot].done;
-  const int ctx = st[slot].row + 1;
+  const int ctx = MEM ? st[slot].S : st[slot].row + 1;
   float qv[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; i += 4) {

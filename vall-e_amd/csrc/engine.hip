@@ -157,6 +157,9 @@ struct vx_engine {
   size_t bkv_slot = 0;  // elements per slot
   bool kv8 = false;                           // VX_FLAG_KV_FP8: the slot caches are bkv8 / bkv8s, bkv stays null
   uint8_t *bkv8 = nullptr, *bkv8s = nullptr;  // e4m3 codes (bkv_slot bytes per slot), E8M0 scales (one per 16 codes)
+  // VALL-F: the text memory of every slot, [slot][layer][K|V][head][max_text][64] (xkv_ar's layout per slot); bmem_slot elements
+  vx::bf16* bmem = nullptr;
+  size_t bmem_slot = 0;
   ArState* bst = nullptr;    // device, BMAX
   ArState* h_bst = nullptr;  // pinned: [0..BMAX) staging, [BMAX..3*BMAX) two poll slots
   int *btok = nullptr, *bsamp = nullptr, *bargm = nullptr;
@@ -366,8 +369,8 @@ extern "C" int vx_create(const vx_config* cfg, vx_engine** out) {
   if (c.precision == VX_PREC_FP8_NAR && (c.num_quantizers < 2 || c.nar_d_model % 256 || c.nar_d_model / c.nar_nhead != 64 ||
                                          (c.flags & (VX_FLAG_POST_NORM | VX_FLAG_PRENET | VX_FLAG_SIMPLE_ROWS))))
     return fail(VX_ERR_UNSUPPORTED, "VX_PREC_FP8_NAR needs a pre-norm NAR stack without prenets, head_dim 64 and nar_d_model % 256 == 0");
-  if ((c.flags & (VX_FLAG_POST_NORM | VX_FLAG_PRENET | VX_FLAG_VALLF)) && c.max_batch > 1)
-    return fail(VX_ERR_UNSUPPORTED, "post-norm / prenet / VALL-F models run on the batch-1 path only");
+  if ((c.flags & (VX_FLAG_POST_NORM | VX_FLAG_PRENET)) && c.max_batch > 1)
+    return fail(VX_ERR_UNSUPPORTED, "post-norm / prenet models (VALL-E or VALL-F) run on the batch-1 path only");
   if ((c.flags & VX_FLAG_VALLF) && c.precision == VX_PREC_FP8_NAR) return fail(VX_ERR_UNSUPPORTED, "VX_PREC_FP8_NAR is built for VALL-E only");
   if (c.max_batch < 0 || c.max_batch > BMAX) return fail(VX_ERR_ARG, "max_batch must be 0..%d", BMAX);
   if (c.max_batch > 1 && (c.precision == VX_PREC_F32 || c.d_model % 128))
@@ -515,6 +518,10 @@ static int create_body(vx_engine* e) {
       VXC(dalloc_t(e, &e->bkv8s, (size_t)e->bmax * e->bkv_slot / 16));
     } else {
       VXC(dalloc_t(e, &e->bkv, (size_t)e->bmax * e->bkv_slot));
+    }
+    if (e->vallf) {  // 2 L max_text d bf16 per slot; rows at and past a slot's text length are never read
+      e->bmem_slot = (size_t)c.num_layers * 2 * d * c.max_text;
+      VXC(dalloc_t(e, &e->bmem, (size_t)e->bmax * e->bmem_slot));
     }
     VXC(dalloc_t(e, &e->bst, (size_t)BMAX));
     VXC(dalloc_t(e, &e->btok, (size_t)BMAX * e->btok_stride));
@@ -1100,10 +1107,11 @@ static int cross_attn_rows(vx_engine* e, const void* q, const void* kc, const vo
 }
 
 // One decoder stack over the M audio rows held in e->X (valle.py:626-632 AR with text_len = 0: causal; valle.py:682-688 NAR
-// with text_len < 0: no mask).  Memory K / V of layer li at xkv + li * per_layer, Sk text rows.  Plain epilogue adds (no
+// with text_len < 0: no mask).  Memory K / V of layer li at xkv + li * per_layer, Sk text rows.  Self-attention K / V go to the
+// decode cache at kv_dst ([L][2][H][ctx_max][hd]: e->kv or a slot's cache; null: not kept).  Plain epilogue adds (no
 // split-K slabs): this variant is built for parity, not tuned.
 static int run_stack_f(vx_engine* e, const std::vector<LayerW>& layers, int M, int d, int H, int text_len, int ada_stage,
-                       bool fill_cache, const void* xkv, int Sk) {
+                       void* kv_dst, const void* xkv, int Sk) {
   const bool post = e->cfg.flags & VX_FLAG_POST_NORM;
   const int hd = d / H;
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
@@ -1117,8 +1125,8 @@ static int run_stack_f(vx_engine* e, const std::vector<LayerW>& layers, int M, i
     if (!post) VXC(ln_rows(e, e->X, l.n1_g, l.n1_b, aw[0], ab[0], e->Hn, M, d));
     else if (li == 0) VXC(cast_rows(e, e->X, e->Hn, (size_t)M * d));
     VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
-    if (fill_cache) {
-      char* kc = (char*)e->kv + li * kv_layer;
+    if (kv_dst) {
+      char* kc = (char*)kv_dst + li * kv_layer;
       char* vc = kc + kv_layer / 2;
       if (e->bf16) kv_scatter_kernel<bf16><<<M, 256, 0, e->es>>>((const bf16*)e->QKV, (bf16*)kc, (bf16*)vc, M, d, hd, e->ctx_max);
       else kv_scatter_kernel<float><<<M, 256, 0, e->es>>>((const float*)e->QKV, (float*)kc, (float*)vc, M, d, hd, e->ctx_max);
@@ -1210,6 +1218,7 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
   const bool vf = e->vallf;  // VALL-F: the stack runs over the audio rows only, the text is cross-attention memory (valle.py:598-632)
   const int bos = c.prepend_bos ? 1 : 0, A = bos + P, M = vf ? A : S + A, d = c.d_model;
   if (slot >= e->bmax) return fail(VX_ERR_ARG, "slot %d >= max_batch %d", slot, e->bmax);
+  void* xkv = slot < 0 ? e->xkv_ar : (void*)(e->bmem + (size_t)slot * e->bmem_slot);  // VALL-F: this utterance's text memory
   ON_DEVICE(c.device);
   VXC(sync_in(e, stream));
   HIPC(hipEventRecord(e->ev_t[0], e->es));
@@ -1223,7 +1232,7 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
     embed_accum_kernel<<<S, 256, 0, e->es>>>(e->ids_text, 1, 0, W<float>(e, "ar_text_embedding.word_embeddings.weight"), 512, d, e->pn_a, S, 1);
     VXC(text_prenet_rows(e, 0, e->pn_a, e->pn_a, S, d));
     add_pos_kernel<<<S, 256, 0, e->es>>>(e->pn_a, d, W<float>(e, "ar_text_position.alpha"), e->pe_ar, 0, e->X, S);
-    if (vf) { VXC(cast_rows(e, e->X, e->Hn, (size_t)S * d)); VXC(memory_kv(e, e->ar_l, e->xkv_ar, S, d, c.nhead)); }
+    if (vf) { VXC(cast_rows(e, e->X, e->Hn, (size_t)S * d)); VXC(memory_kv(e, e->ar_l, xkv, S, d, c.nhead)); }
     embed_accum_kernel<<<A, 256, 0, e->es>>>(e->ids_audio, 1, 0, W<float>(e, "ar_audio_embedding.word_embeddings.weight"), 1025 + bos, d, e->pn_a, A, 1);
     VXC(audio_prenet_rows(e, 0, e->pn_a, e->pn_b, A, d));
     add_pos_kernel<<<A, 256, 0, e->es>>>(e->pn_b, d, W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, e->X + (size_t)(vf ? 0 : S) * d, A);
@@ -1231,7 +1240,7 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
     embed_pos_kernel<<<S, 256, 0, e->es>>>(e->ids_text, 1, 0, W<float>(e, "ar_text_embedding.word_embeddings.weight"), 512, d,
                                            W<float>(e, "ar_text_position.alpha"), e->pe_ar, 0, e->X, S);
     // VALL-F: the text rows become the per-layer memory K / V (projected once, valle.py:598-602), then the audio rows take X
-    if (vf) { VXC(cast_rows(e, e->X, e->Hn, (size_t)S * d)); VXC(memory_kv(e, e->ar_l, e->xkv_ar, S, d, c.nhead)); }
+    if (vf) { VXC(cast_rows(e, e->X, e->Hn, (size_t)S * d)); VXC(memory_kv(e, e->ar_l, xkv, S, d, c.nhead)); }
     embed_pos_kernel<<<A, 256, 0, e->es>>>(e->ids_audio, 1, 0, W<float>(e, "ar_audio_embedding.word_embeddings.weight"), 1025 + bos, d,
                                            W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, e->X + (size_t)(vf ? 0 : S) * d, A);
   }
@@ -1241,7 +1250,10 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
   float* x_dst = slot < 0 ? e->ar_x : e->bx + (size_t)slot * d;
   float* lg_dst = slot < 0 ? e->ar_logits : e->blogits + (size_t)slot * LOGITS_CUR;
   ArState* st_dst = slot < 0 ? e->d_st : e->bst + slot;
-  if (vf) { e->mem_len = S; VXC(run_stack_f(e, e->ar_l, M, d, c.nhead, 0, -1, true, e->xkv_ar, S)); }
+  if (vf) {  // kv is a CACHE destination: VX_FLAG_KV_FP8 is refused for VALL-F
+    if (slot < 0) e->mem_len = S;
+    VXC(run_stack_f(e, e->ar_l, M, d, c.nhead, 0, -1, kv.base, xkv, S));
+  }
   else VXC(run_stack(e, e->ar_l, M, d, c.nhead, S, -1, RowSegs(), kv));
   HIPC(hipMemcpyAsync(x_dst, e->X + (size_t)(M - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
   ArState& st = slot < 0 ? e->h_st[0] : e->h_bst[slot];
@@ -1376,6 +1388,7 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
 
 extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S,
                                     const int64_t* const* prompt_cb0, const int32_t* P, void* stream) {
+  if (e && e->vallf) return fail(VX_ERR_UNSUPPORTED, "vx_batch_prefill_all: VALL-F prefills slot by slot (vx_batch_prefill)");
   if (e) e->bsess = false;  // the static calls end a continuous-batching session
   int32_t slots[BMAX];  // segment z -> slot z
   for (int z = 0; z < BMAX; ++z) slots[z] = z;
@@ -1858,7 +1871,10 @@ static void launch_ln_batch(float* x, const float* part, int kgroups, const floa
   else ln_batch_kernel<1><<<B, 256, 0, s>>>(x, part, pbias, gamma, beta, h, d);
 }
 
-// One batched step: every slot samples its next token, then the L layers run once over all B slots.
+// One batched step: every slot samples its next token, then the L layers run once over all B slots.  VALL-F (pre-norm,
+// TransformerDecoderLayer as in enqueue_ar_step_f): the self-attention cache holds audio rows only (kv_text = 0), and each layer
+// adds the cross-attention over the slot's text memory (bmem) between the self-attention and the feed-forward block: 11 launches
+// per layer instead of 7.
 static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
   const vx_config& c = e->cfg;
   const int d = c.d_model, H = c.nhead, hd = 64, L = c.num_layers;
@@ -1901,6 +1917,20 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
     o.A = e->batt; o.W = (const bf16*)l.out_w; o.N = d; o.K = d; o.kgroups = kg_d; o.part = e->bpart;
     VXC(launch_bgemm<BE_PARTIAL>(o, s));
     launch_ln_batch(e->bx, e->bpart, kg_d, l.out_b, l.n2_g, l.n2_b, e->bh, B, d, s);
+    if (e->vallf) {  // q = in_proj[0:d](norm2(x)); x += out_proj(attention over the text memory); then norm3 for the FFN
+      const size_t mem_layer = (size_t)2 * d * c.max_text;  // elements
+      BgemmArgs cq{};
+      cq.st = e->bst; cq.B = B;
+      cq.A = e->bh; cq.W = (const bf16*)l.cin_w; cq.bias = l.cin_b; cq.N = d; cq.K = d; cq.kgroups = 1; cq.q = e->bq;
+      VXC(launch_bgemm<BE_BIAS>(cq, s));
+      attn_batch_kernel<64, true><<<dim3(H, B), 256, 0, s>>>(e->bq, e->bmem + (size_t)li * mem_layer, e->bmem_slot, mem_layer / 2, e->bst,
+                                                             c.max_text, d, scale, e->batt);
+      BgemmArgs co{};
+      co.st = e->bst; co.B = B;
+      co.A = e->batt; co.W = (const bf16*)l.cout_w; co.N = d; co.K = d; co.kgroups = kg_d; co.part = e->bpart;
+      VXC(launch_bgemm<BE_PARTIAL>(co, s));
+      launch_ln_batch(e->bx, e->bpart, kg_d, l.cout_b, l.n3_g, l.n3_b, e->bh, B, d, s);
+    }
     BgemmArgs f{};
     f.st = e->bst; f.B = B;
     f.A = e->bh; f.W = (const bf16*)l.w1; f.bias = l.b1; f.N = 4 * d; f.K = d; f.kgroups = 1; f.f = e->bff;
@@ -2051,6 +2081,7 @@ extern "C" int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, con
   if (n < 1 || n > e->bmax) return fail(VX_ERR_ARG, "n %d outside [1, max_batch=%d]", n, e->bmax);
   if (mode != VX_ADMIT_BATCHED && mode != VX_ADMIT_PER_SLOT) return fail(VX_ERR_ARG, "unknown admission mode %d", mode);
   if (mode == VX_ADMIT_BATCHED && !use_mfma(e)) return fail(VX_ERR_UNSUPPORTED, "batched admission needs the bf16 MFMA row kernels");
+  if (mode == VX_ADMIT_BATCHED && e->vallf) return fail(VX_ERR_UNSUPPORTED, "batched admission: VALL-F admits slot by slot (VX_ADMIT_PER_SLOT)");
   const vx_config& c = e->cfg;
   const int bos = c.prepend_bos ? 1 : 0;
   // every check before anything is written: a refused admission leaves all slots as they were
@@ -2193,7 +2224,7 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
           add_pos_kernel<<<A, 256, 0, e->es>>>(ye, dn, a_aud, e->pe_nar, 0, xa, A);
         }
       }
-      if (vf) VXC(run_stack_f(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, false, e->xkv_nar, S2[0]));
+      if (vf) VXC(run_stack_f(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, nullptr, e->xkv_nar, S2[0]));
       else VXC(run_stack(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, segs, KvDst()));
       // final AdaLN + predict layer on the generated rows only (valle.py:1128), compacted to [sum T][dn]
       const float* fw = post ? nullptr : ada_vec(e, i, e->npl * c.nar_num_layers);
@@ -2315,7 +2346,7 @@ extern "C" int vx_nar_batch(vx_engine* e, int32_t n, const int64_t* const* text_
 extern "C" int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
                                const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens,
                                const int32_t* T, int64_t* const* codes_out, const int64_t* const* forced_codes, void* stream) {
-  if (e && e->vallf) return fail(VX_ERR_UNSUPPORTED, "vx_nar_batch: VALL-F runs on the batch-1 path only");
+  if (e && e->vallf) return fail(VX_ERR_UNSUPPORTED, "vx_nar_batch: VALL-F runs its NAR stages per utterance (vx_nar)");
   if (!e || !text_nar || !S2 || !prompts || !P || !ar_tokens || !T || !codes_out) return fail(VX_ERR_ARG, "null argument");
   if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
   const vx_config& c = e->cfg;
@@ -2633,6 +2664,40 @@ extern "C" int vx_op_attn_slots(int32_t kv_fp8, const float* q, const void* kv, 
   else
     attn_batch_kernel<64><<<dim3(nhead, B), 256, 0, s>>>(q, (const bf16*)kv, (size_t)slot_stride, (size_t)v_offset, t.st, ctx_max, d,
                                                          0.125f, (bf16*)out);
+  const hipError_t le = hipGetLastError();
+  const hipError_t se = hipStreamSynchronize(s);
+  HIPC(le);
+  HIPC(se);
+  return VX_OK;
+}
+
+// The VALL-F slot step's cross-attention (attn_batch_kernel<64, MEM>) on a caller memory of B slots, bf16, indexed as the engine's
+// slot memory: slot b at b * slot_stride elements, V at v_offset, element (h * max_text + j) * 64 + c.  len / done: host arrays;
+// slot b attends to keys [0, len[b]) (done may be NULL: every slot live).
+extern "C" int vx_op_attn_mem_slots(const float* q, const void* mem, int64_t slot_stride, int64_t v_offset, int32_t max_text, int32_t B,
+                                    int32_t nhead, const int32_t* len, const int32_t* done, void* out, void* stream) {
+  if (B < 1 || B > BMAX) return fail(VX_ERR_ARG, "attn_mem_slots: B %d outside [1, %d]", B, BMAX);
+  if (nhead < 1 || max_text < 1) return fail(VX_ERR_ARG, "attn_mem_slots: nhead %d, max_text %d", nhead, max_text);
+  if (v_offset < 0 || slot_stride < 0 || v_offset % 8 || slot_stride % 8)
+    return fail(VX_ERR_ARG, "attn_mem_slots: v_offset %lld and slot_stride %lld must be non-negative multiples of 8", (long long)v_offset,
+                (long long)slot_stride);
+  if (!len) return fail(VX_ERR_ARG, "attn_mem_slots: null len");
+  std::vector<ArState> h(B);  // zero-initialised: only S and done are read
+  for (int b = 0; b < B; ++b) {
+    h[b].done = done ? (done[b] != 0) : 0;
+    if (!h[b].done && (len[b] < 1 || len[b] > max_text))
+      return fail(VX_ERR_ARG, "attn_mem_slots: len[%d] = %d outside [1, max_text %d]", b, len[b], max_text);
+    h[b].S = len[b];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  struct Scratch {  // freed on every exit path
+    ArState* st = nullptr;
+    ~Scratch() { (void)hipFree(st); }
+  } t;
+  HIPC(hipMalloc((void**)&t.st, (size_t)B * sizeof(ArState)));
+  HIPC(hipMemcpyAsync(t.st, h.data(), (size_t)B * sizeof(ArState), hipMemcpyHostToDevice, s));
+  attn_batch_kernel<64, true><<<dim3(nhead, B), 256, 0, s>>>(q, (const bf16*)mem, (size_t)slot_stride, (size_t)v_offset, t.st, max_text,
+                                                             64 * nhead, 0.125f, (bf16*)out);
   const hipError_t le = hipGetLastError();
   const hipError_t se = hipStreamSynchronize(s);
   HIPC(le);

@@ -83,6 +83,8 @@ _SIGS = {
     "vx_op_attention_segs": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3 + [C.c_void_p]),
     "vx_op_attn_slots": (C.c_int, [C.c_int32] + [C.c_void_p] * 3 + [C.c_int64, C.c_int64] + [C.c_int32] * 3
                          + [C.POINTER(C.c_int32)] * 2 + [C.c_void_p, C.c_void_p]),
+    "vx_op_attn_mem_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 3
+                             + [C.POINTER(C.c_int32)] * 2 + [C.c_void_p, C.c_void_p]),
     "vx_op_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "vx_op_convert_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
@@ -515,6 +517,22 @@ def op_attn_slots(q, kv, kv_scale, ctx, done, ctx_max, out=None, slot_stride=Non
     assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == (B, d)
     _check(lib.vx_op_attn_slots(int(fp8), _ptr(q), kv.data_ptr(), None if kv_scale is None else kv_scale.data_ptr(), slot_stride,
                                 v_offset, ctx_max, B, d // 64, _i32(ctx), _i32(done), _ptr(out), current_stream_ptr(q.device)))
+    return out
+
+
+def op_attn_mem_slots(q, mem, lens, done, out=None):
+    """The VALL-F slot step's cross-attention (vx_op_attn_mem_slots) of B = len(lens) slots: q (B, d) fp32; mem bf16 (B, 2, H, max_text,
+    64) - or a strided view of one layer of the engine's slot memory - slot b attends to its first lens[b] rows.  done (None: all
+    live): slots whose `out` rows are left as they are."""
+    lib = load_library()
+    B, d = q.shape
+    assert q.dtype == torch.float32 and q.is_contiguous() and len(lens) == B and (done is None or len(done) == B)
+    assert mem.dtype == torch.bfloat16 and mem.dim() == 5 and mem.shape[0] == B and mem.shape[4] == 64
+    if out is None:
+        out = torch.zeros((B, d), dtype=torch.bfloat16, device=q.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == (B, d)
+    _check(lib.vx_op_attn_mem_slots(_ptr(q), mem.data_ptr(), mem.stride(0), mem.stride(1), mem.shape[3], B, d // 64, _i32(lens),
+                                    _i32(done), _ptr(out), current_stream_ptr(q.device)))
     return out
 
 

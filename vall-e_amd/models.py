@@ -67,8 +67,13 @@ class VALLE:
                 raise NotImplementedError("kv_cache='fp8' needs a pre-norm VALL-E without prenets")
             if d_model % nhead or d_model // nhead != 64:
                 raise NotImplementedError("kv_cache='fp8' needs head_dim 64")
-        if (not norm_first or add_prenet or self.cfg.is_vallf) and self.engine_opts.get("max_batch", 0) > 1:
-            raise NotImplementedError("norm_first=False / add_prenet=True / VALL-F run on the batch-1 path only (inference_batch needs the defaults)")
+        if (not norm_first or add_prenet) and self.engine_opts.get("max_batch", 0) > 1:
+            raise NotImplementedError("norm_first=False / add_prenet=True run on the batch-1 path only (inference_batch needs the defaults)")
+        if self.cfg.is_vallf and self.engine_opts["max_batch"] > 1:  # the engine refuses these too (vx_create)
+            if self.engine_opts["precision"] != "bf16":
+                raise NotImplementedError("VALL-F with max_batch >= 2 needs precision 'bf16'")
+            if d_model % nhead or d_model // nhead != 64 or d_model % 128:
+                raise NotImplementedError("VALL-F with max_batch >= 2 needs head_dim 64 and d_model % 128 == 0")
         if self.cfg.is_vallf and self.engine_opts["precision"] == "fp8nar":
             raise NotImplementedError("precision 'fp8nar' is built for VALL-E only")
         # head_dim 64 is the tuned geometry; 4/8/16/32 (the reference's own test: decoder_dim 64, nhead 16, valle_test.py:93-95)
@@ -338,18 +343,31 @@ class VALLF(VALLE):
     """The cross-attention variant (valle.py:49-719; ``--model-name VALL-F``): ``inference`` has VALLE.inference's signature and
     result (valle.py:566-710).  The text is embedded once as the memory of a TransformerDecoder whose target is the audio
     sequence alone; the reference masks memory positions >= x_lens (all-false for the unpadded batch-1 input it accepts).
-    The reference's VALLF has no ``continual`` and no batched entry point; neither has this one."""
+    The reference's VALLF has no ``continual`` and no batched entry point.  This one has no ``continual`` either; built with
+    ``max_batch >= 2`` (pre-norm, no prenets, head_dim 64, d_model % 128 == 0, bf16) it has ``inference_batch`` and
+    ``inference_stream``, which prefill and admit slot by slot and run the NAR stages per utterance (``batched_prefill``,
+    ``batched_admit`` and ``batched_nar`` are ignored)."""
 
     MODEL_NAME = "VALL-F"
 
     def continual(self, *a, **k):
         raise AttributeError("'VALLF' object has no attribute 'continual'")  # valle.py:1139 defines it on VALLE only
 
-    def inference_batch(self, *a, **k):
-        raise NotImplementedError("VALL-F runs on the batch-1 path only")
+    def _vallf_batched(self, what: str):
+        if self.engine_opts["max_batch"] < 2:
+            raise NotImplementedError(f"VALL-F {what} needs a model built with max_batch >= 2 (otherwise batch-1 path only)")
 
-    def inference_stream(self, *a, **k):
-        raise NotImplementedError("VALL-F runs on the batch-1 path only")
+    def inference_batch(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, batched_nar: bool = True,
+                        batched_prefill: bool = True):
+        self._vallf_batched("inference_batch")
+        return super().inference_batch(utterances, top_k=top_k, temperature=temperature, seeds=seeds, batched_nar=False,
+                                       batched_prefill=False)
+
+    def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
+                         poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None):
+        self._vallf_batched("inference_stream")
+        return super().inference_stream(utterances, top_k=top_k, temperature=temperature, seeds=seeds, nar_group=nar_group,
+                                        poll_steps=poll_steps, batched_admit=False, batched_nar=False, refill_at=refill_at)
 
 
 def get_model(params) -> VALLE:
