@@ -70,7 +70,7 @@ enum vx_flags {
                                the AUDIO rows only, cross-attention over the embedded text, three norms per layer.  Same entry
                                points (VALLF.inference, valle.py:566-710, has VALLE.inference's signature); the state_dict gains
                                layers.N.multihead_attn.* and layers.N.norm3.*.  With max_batch >= 2 (pre-norm, no prenets,
-                               head_dim 64, d_model % 128 == 0, bf16 precision, bf16 slot caches) the slots decode VALL-F too:
+                               head_dim 64, d_model in {128, 256, 512, 1024}, bf16 precision, bf16 slot caches) the slots decode VALL-F too:
                                every slot keeps its own text memory (2 L max_text d bf16).  VALL-F slots are prefilled one by
                                one (vx_batch_prefill, VX_ADMIT_PER_SLOT) and their NAR stages run per utterance (vx_nar);
                                vx_batch_prefill_all, VX_ADMIT_BATCHED and vx_nar_batch return VX_ERR_UNSUPPORTED */
@@ -98,7 +98,8 @@ typedef struct vx_config {
   int32_t max_audio;       /* capacity: audio rows = [BOS] + prompt frames + generated frames */
   int32_t device;          /* HIP device ordinal */
   int32_t flags;           /* enum vx_flags */
-  int32_t max_batch;       /* slots for batched AR decode (vx_batch_*): 0/1 = batch-1 only, <= 64; bf16 only */
+  int32_t max_batch;       /* slots for batched AR decode (vx_batch_*): 0/1 = batch-1 only, <= 64; bf16 only, head_dim 64 and
+                              d_model in {128, 256, 512, 1024} (else VX_ERR_UNSUPPORTED, before any HIP call) */
 } vx_config;
 
 /* Sampling / stop-rule parameters of one AR decode (VALLE.inference args top_k, temperature,
@@ -282,6 +283,25 @@ int vx_op_attn_slots(int32_t kv_fp8, const float* q, const void* kv, const void*
  * Synchronises `stream`. */
 int vx_op_attn_mem_slots(const float* q, const void* mem, int64_t slot_stride, int64_t v_offset, int32_t max_text, int32_t B,
                          int32_t nhead, const int32_t* len, const int32_t* done /* nullable */, void* out, void* stream);
+/* One launch of the batched step's GEMM (bgemm_kernel; C[b][n] = sum_k A[b][k] W[n][k] on bf16 A (32 rows if B <= 32, else 64;
+ * rows >= B are read but unused) and W (N, K)) in its epilogue epi: 0 QKV (q (B, d) fp32 = C + bias for n < d; the K / V columns
+ * go to row row[b] of live slots' caches, indexed as in vx_op_attn_slots (hd 64): bf16 kv, or with kv8 e4m3 codes in kv and E8M0
+ * scale bytes in kv8s), 1 RELU (f (B, N) bf16 = ReLU(C + bias)), 2 PARTIAL (part[g][b][n] fp32, (kgroups, 64, N): the sum over
+ * K group g), 3 LOGITS (logits[b * logits_stride + n] = C for live slots, and trace[(b trace_rows + pass[b]) N + n] when trace
+ * != NULL and pass[b] < trace_rows), 4 LOGITS_MAP (3 with row z written to slot slot_map[z]; done / pass indexed by slot),
+ * 5 BIAS (q (B, N) fp32 = C + bias).  K = ns kgroups 128 with ns in {1, 2, 4, 8}; kgroups > 1 for PARTIAL only.  done / row /
+ * pass: host arrays (nullable: zeros) of B entries, 64 for LOGITS_MAP; slot_map: host.  Bad arguments: VX_ERR_ARG before any
+ * HIP call.  Synchronises `stream`. */
+int vx_op_bgemm(int32_t epi, int32_t kv8, const void* A_bf16, const void* W_bf16, const float* bias, int32_t N, int32_t K, int32_t B,
+                int32_t kgroups, const int32_t* done, const int32_t* row, const int32_t* pass, float* q, void* kv, void* kv8s,
+                int64_t kv_slot_stride, int64_t kv_v_offset, int32_t d, int32_t ctx_max, void* f_bf16, float* part, float* logits,
+                int32_t logits_stride, float* trace, int32_t trace_rows, const int32_t* slot_map, void* stream);
+/* The batched step's LayerNorm: kgroups 1 or 4: t = pbias + part[0][b] + ... + part[kgroups-1][b] (in that order; part
+ * (kgroups, 64, d)), x[b] += t written back; kgroups 0: x only read.  Then h[b] (bf16) = LN(x[b]) gamma + beta (eps 1e-5), for
+ * b < B.  slot_map (host, kgroups 0): batched prefill's form, h[z] = LN(x[slot_map[z]]).  d a multiple of 4, <= 1024.  Bad
+ * arguments: VX_ERR_ARG before any HIP call.  Synchronises `stream`. */
+int vx_op_ln_batch(float* x, const float* part, int32_t kgroups, const float* pbias, const float* gamma, const float* beta, void* h_bf16,
+                   int32_t B, int32_t d, const int32_t* slot_map /* nullable */, void* stream);
 int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
                  int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 int vx_op_convert_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);

@@ -206,3 +206,155 @@ def test_attn_slots_done_slots_skip_the_ctx_check_without_gpu(lib):
     assert rc == 1 and b"ctx[1]" in lib.vx_last_error()
     rc = lib.vx_op_attn_slots(1, None, None, None, 4096, 2048, 32, 1, 1, _i32([5]), None, None, None)
     assert rc == 1 and b"kv_scale" in lib.vx_last_error()
+
+
+# ---- vx_op_bgemm / vx_op_ln_batch: every argument check fires on the host, before any HIP call -----------------------------------
+# Every case below is invalid in exactly one way; pointers are passed only where a check further down needs them (never used).
+_P = 4096  # a non-null stand-in for a device pointer
+
+
+def _bgemm(lib, epi=2, kv8=0, A=_P, W=_P, bias=_P, N=256, K=256, B=4, kgroups=1, done=None, row=None, pass_=None, q=_P, kv=_P,
+           kv8s=_P, stride=4096, voff=2048, d=0, ctx_max=32, f=_P, part=_P, logits=_P, logits_stride=1088, trace=None, trace_rows=0,
+           slot_map=None):
+    opt = lambda v: None if v is None else _i32(v)  # noqa: E731
+    return lib.vx_op_bgemm(epi, kv8, A, W, bias, N, K, B, kgroups, opt(done), opt(row), opt(pass_), q, kv, kv8s, stride, voff, d,
+                           ctx_max, f, part, logits, logits_stride, trace, trace_rows, opt(slot_map), None)
+
+
+@pytest.mark.parametrize("kw,match", [
+    (dict(epi=6), "unknown epilogue"),
+    (dict(epi=-1), "unknown epilogue"),
+    (dict(epi=2, kv8=1), "kv8"),                                   # fp8 caches outside the QKV epilogue
+    (dict(epi=3, kv8=1), "kv8"),
+    (dict(B=0), "B 0"),
+    (dict(B=65), "B 65"),
+    (dict(N=65536), "N 65536"),                                    # (N << 16) | K travels as one kernel argument
+    (dict(K=65536 * 2), "K 131072"),
+    (dict(N=0), "N 0"),
+    (dict(K=384), "K 384"),                                        # ns = 3
+    (dict(K=768), "K 768"),                                        # ns = 6
+    (dict(K=2048, kgroups=1), "K 2048"),                           # ns = 16
+    (dict(K=1024, kgroups=4, epi=3), "kgroups 4"),                 # split K outside BE_PARTIAL: the groups would race
+    (dict(K=1024, kgroups=0), "kgroups 0"),
+    (dict(K=64), "K 64"),                                          # less than one 128-wide slice
+    (dict(A=None), "null A"),
+    (dict(W=None), "null A or W"),
+    (dict(epi=0, N=768, d=128), "N == 3 d"),                       # QKV N != 3 d
+    (dict(epi=0, N=288, K=128, d=96), "d % 64"),                   # QKV d % 64 != 0
+    (dict(epi=0, N=768, d=256, q=None), "QKV needs q"),
+    (dict(epi=0, N=768, d=256, kv=None), "QKV needs q"),
+    (dict(epi=0, kv8=1, N=768, d=256, kv8s=None), "fp8"),
+    (dict(epi=0, N=768, d=256, bias=None), "needs bias"),
+    (dict(epi=1, bias=None), "needs bias"),
+    (dict(epi=5, bias=None), "needs bias"),
+    (dict(epi=0, N=768, d=256, ctx_max=0), "ctx_max 0"),
+    (dict(epi=0, kv8=1, N=768, d=256, voff=2040), "V offset 2040"),  # off the fp8 scale grid
+    (dict(epi=0, N=768, d=256, row=[0, 1, 32, 2]), "row[2]"),       # the KV row past the cache
+    (dict(epi=0, N=768, d=256, row=[0, 1, -1, 2]), "row[2]"),
+    (dict(epi=1, f=None), "needs f"),
+    (dict(epi=5, q=None), "needs q"),
+    (dict(epi=2, part=None), "needs part"),
+    (dict(epi=3, logits=None), "logits"),
+    (dict(epi=3, N=1025, logits_stride=1024), "stride"),
+    (dict(epi=3, trace=_P, trace_rows=0), "trace_rows 0"),
+    (dict(epi=3, pass_=[0, 0, -3, 0]), "pass[2]"),
+    (dict(epi=4, slot_map=None), "needs slot_map"),
+    (dict(epi=4, slot_map=[0, 1, 64, 2]), "slot_map[2] = 64"),
+    (dict(epi=4, slot_map=[0, -1, 3, 2]), "slot_map[1] = -1"),
+])
+def test_bgemm_rejects_bad_arguments_without_gpu(lib, kw, match):
+    rc = _bgemm(lib, **kw)
+    assert rc == 1 and match.encode() in lib.vx_last_error(), (kw, lib.vx_last_error())
+
+
+def test_bgemm_done_slots_skip_the_row_check_without_gpu(lib):
+    """a done slot's KV row is never written, so only live slots' rows are checked"""
+    rc = _bgemm(lib, epi=0, N=768, d=256, row=[0, 99, 5, 40], done=[0, 1, 0, 0])
+    assert rc == 1 and b"row[3]" in lib.vx_last_error()
+
+
+def _ln(lib, x=_P, part=_P, kgroups=4, pbias=_P, gamma=_P, beta=_P, h=_P, B=4, d=256, slot_map=None):
+    return lib.vx_op_ln_batch(x, part, kgroups, pbias, gamma, beta, h, B, d, None if slot_map is None else _i32(slot_map), None)
+
+
+@pytest.mark.parametrize("kw,match", [
+    (dict(d=258), "d 258"),                  # float4 columns
+    (dict(d=1028), "d 1028"),                # 256 threads x 4 columns
+    (dict(d=0), "d 0"),
+    (dict(B=0), "B 0"),
+    (dict(B=65), "B 65"),
+    (dict(kgroups=2), "kgroups 2"),
+    (dict(kgroups=8), "kgroups 8"),
+    (dict(x=None), "null x"),
+    (dict(gamma=None), "null x"),
+    (dict(beta=None), "null x"),
+    (dict(h=None), "null x"),
+    (dict(part=None), "needs part"),
+    (dict(kgroups=1, pbias=None), "needs part"),
+    (dict(kgroups=1, slot_map=[0, 1, 2, 3]), "no partials"),
+    (dict(kgroups=0, slot_map=[0, 1, 64, 3]), "slot_map[2] = 64"),
+    (dict(kgroups=0, slot_map=[0, 1, 2, -5]), "slot_map[3] = -5"),
+])
+def test_ln_batch_rejects_bad_arguments_without_gpu(lib, kw, match):
+    rc = _ln(lib, **kw)
+    assert rc == 1 and match.encode() in lib.vx_last_error(), (kw, lib.vx_last_error())
+
+
+# ---- batched decode widths: d_model in {128, 256, 512, 1024} ----------------------------------------------------------------------
+def _batch_cfg(d, max_batch=4, flags=0):
+    import ctypes as C
+    from valle_amd.engine import VxConfig
+
+    c = VxConfig()
+    c.struct_size = C.sizeof(VxConfig)
+    c.d_model, c.nhead, c.num_layers = d, d // 64, 2
+    c.nar_d_model, c.nar_nhead, c.nar_num_layers = d, d // 64, 2
+    c.num_quantizers, c.prefix_mode, c.precision, c.max_text, c.max_audio = 8, 1, 1, 16, 64
+    c.flags, c.max_batch = flags, max_batch
+    return c
+
+
+@pytest.mark.parametrize("d", [384, 640, 768, 896])
+def test_vx_create_refuses_batched_widths_without_a_bgemm_form(lib, d):
+    """head_dim 64 and d % 128 == 0, but K = d (or 4 d) needs 3, 5, 6 or 7 steps per wave: refused up front (it used to construct and
+    fail at the first batched step with 'bgemm: 6 steps per wave').  Batch-1 engines of these widths stay accepted."""
+    import ctypes as C
+    from valle_amd.engine import VX_FLAG_VALLF
+
+    for flags in (0, VX_FLAG_VALLF):
+        h = C.c_void_p()
+        assert lib.vx_create(C.byref(_batch_cfg(d, flags=flags)), C.byref(h)) == 5, lib.vx_last_error()
+        assert b"d_model in {128, 256, 512, 1024}" in lib.vx_last_error()
+    h = C.c_void_p()
+    rc = lib.vx_create(C.byref(_batch_cfg(d, max_batch=1)), C.byref(h))
+    if rc == 0:  # a GPU is present: the engine exists
+        lib.vx_destroy(h)
+    else:
+        assert rc == 2, lib.vx_last_error()  # passes the configuration checks; fails in its first HIP call without a GPU
+
+
+@pytest.mark.parametrize("d", [128, 256, 512, 1024])
+def test_vx_create_accepts_the_batched_widths(lib, d):
+    import ctypes as C
+
+    h = C.c_void_p()
+    rc = lib.vx_create(C.byref(_batch_cfg(d)), C.byref(h))
+    if rc == 0:
+        lib.vx_destroy(h)
+    else:
+        assert rc == 2, lib.vx_last_error()
+
+
+@pytest.mark.parametrize("d", [384, 640, 768, 896])
+def test_host_mirror_refuses_batched_widths_without_a_bgemm_form(d):
+    from valle_amd.models import VALLE, VALLF
+
+    for cls in (VALLE, VALLF):
+        with pytest.raises(NotImplementedError, match="d_model in"):
+            cls(d, d // 64, 2, max_batch=4)
+        cls(d, d // 64, 2)  # batch-1: accepted
+    with pytest.raises(NotImplementedError, match="d_model in"):
+        VALLE(d, d // 64, 2, max_batch=4, kv_cache="fp8")
+    for d_ok in (128, 256, 512, 1024):
+        VALLE(d_ok, d_ok // 64, 2, max_batch=4)
+        VALLF(d_ok, d_ok // 64, 2, max_batch=4)

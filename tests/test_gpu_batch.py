@@ -178,6 +178,44 @@ def test_every_slot_half_against_fp32_oracle(B):
     assert agree_min >= 0.90  # 33-token slots: three undecided rows (the decided ones are exact, above)
 
 
+@pytest.mark.parametrize("d,nhead", [(128, 2), (512, 8)])
+def test_other_widths_teacher_forced_against_fp32_oracle(d, nhead):
+    """The widths no other test decodes in batch: d = 128 (every bgemm at one step per wave, kgroups 1) and d = 512 (the
+    out-projection split over 4 K groups at one step per wave, FFN2 at four), batched prefill included.  Each slot teacher-forced
+    with its own fp32-oracle greedy tokens: every pass's logits within 3 % of the row scale, argmax exact where the oracle's margin
+    allows."""
+    from oracle import valle_oracle as vo
+
+    B = 3
+    cfg, sd, m = _setup(max_batch=B, d=d, nhead=nhead, L=2, trace_logits=True)
+    eng = m.engine()
+    utts = _utts([(4, 17), (6, 9), (3, 26)])
+    om = vo.OracleModel(sd, cfg.decoder_dim, cfg.nhead, cfg.num_decoder_layers, 1, False, 8)
+    refs = []
+    with _few_threads():
+        for x, xl, y in utts:
+            tr = {}
+            codes = vo.inference_cached(om, x, xl, y, None, 1, 1.0, None, trace=tr, skip_nar=True)
+            refs.append((codes[0, :40, 0].contiguous(), torch.stack(tr["ar_logits"])[:40]))
+    eng.batch_prefill_all([u[0][0] for u in utts], [u[2][0, :, 0].contiguous() for u in utts])  # writes trace row 0 (pass 0)
+    eng.batch_decode(B, top_k=1, forced=[r[0].cuda() for r in refs])
+    stride = eng.max_audio + 2
+    arg = eng.read("batch_argmax", (BMAX, stride), dtype=torch.int32)
+    for b, (toks, ref_logits) in enumerate(refs):
+        got_toks, reason = eng.batch_result(b)
+        assert torch.equal(got_toks, toks) and reason == 4
+        n = min(ref_logits.shape[0], toks.numel())  # passes both computed
+        tr = eng.read("batch_trace", (n, 1025), offset_bytes=b * stride * 1025 * 4)
+        scale = ref_logits[:n].abs().amax(1)
+        err = (tr - ref_logits[:n]).abs().amax(1)
+        assert bool((err <= 0.03 * scale).all()), (d, b, float((err / scale).max()))
+        top2 = ref_logits[:n].topk(2, dim=1)[0]
+        decided = (top2[:, 0] - top2[:, 1]) > 2 * 0.03 * scale
+        same = arg[b, :n].long() == ref_logits[:n].argmax(1)
+        assert bool(same[decided].all()), (d, b, int((~same[decided]).sum()))
+        print("d", d, "slot", b, "worst rel logit err %.4f" % float((err / scale).max()), "argmax agreement %.3f" % float(same.float().mean()))
+
+
 @pytest.mark.parametrize("B,precision,every", [(32, "bf16", 2), (64, "fp8nar", 8)])
 def test_batch_full_length_mixed_slots_teacher_forced(B, precision, every):
     """BASELINE configs[2] (32 slots, bf16) and configs[4] (64 slots, 20 s outputs, MXFP8 NAR GEMMs) at size against the reference,

@@ -373,8 +373,10 @@ extern "C" int vx_create(const vx_config* cfg, vx_engine** out) {
     return fail(VX_ERR_UNSUPPORTED, "post-norm / prenet models (VALL-E or VALL-F) run on the batch-1 path only");
   if ((c.flags & VX_FLAG_VALLF) && c.precision == VX_PREC_FP8_NAR) return fail(VX_ERR_UNSUPPORTED, "VX_PREC_FP8_NAR is built for VALL-E only");
   if (c.max_batch < 0 || c.max_batch > BMAX) return fail(VX_ERR_ARG, "max_batch must be 0..%d", BMAX);
-  if (c.max_batch > 1 && (c.precision == VX_PREC_F32 || c.d_model % 128))
-    return fail(VX_ERR_UNSUPPORTED, "batched decode needs bf16 precision and d_model % 128 == 0");
+  // bgemm_kernel runs K = ns x kgroups x 128 with ns in {1, 2, 4, 8} and kgroups_for(K) in {1, 4}: the step's K = d and 4 d fit
+  // those forms at exactly these four widths (384, 640, 768 and 896 would need ns = 3, 5, 6 or 7)
+  if (c.max_batch > 1 && (c.precision == VX_PREC_F32 || (c.d_model != 128 && c.d_model != 256 && c.d_model != 512 && c.d_model != 1024)))
+    return fail(VX_ERR_UNSUPPORTED, "batched decode needs bf16 precision and d_model in {128, 256, 512, 1024}");
   if ((c.flags & VX_FLAG_KV_FP8) && (c.max_batch < 2 || c.precision == VX_PREC_F32 || c.d_model / c.nhead != 64 ||
                                      (c.flags & (VX_FLAG_POST_NORM | VX_FLAG_PRENET | VX_FLAG_VALLF))))
     return fail(VX_ERR_UNSUPPORTED, "VX_FLAG_KV_FP8 needs max_batch >= 2, bf16 / fp8nar precision, head_dim 64 and a pre-norm VALL-E "
@@ -2698,6 +2700,120 @@ extern "C" int vx_op_attn_mem_slots(const float* q, const void* mem, int64_t slo
   HIPC(hipMemcpyAsync(t.st, h.data(), (size_t)B * sizeof(ArState), hipMemcpyHostToDevice, s));
   attn_batch_kernel<64, true><<<dim3(nhead, B), 256, 0, s>>>(q, (const bf16*)mem, (size_t)slot_stride, (size_t)v_offset, t.st, max_text,
                                                              64 * nhead, 0.125f, (bf16*)out);
+  const hipError_t le = hipGetLastError();
+  const hipError_t se = hipStreamSynchronize(s);
+  HIPC(le);
+  HIPC(se);
+  return VX_OK;
+}
+
+// One bgemm_kernel launch of the batched step (through launch_bgemm, so only the engine's own instances run) on caller buffers.
+// done / row / pass: host arrays (nullable: zeros) of B entries, BMAX entries indexed by slot for BE_LOGITS_MAP; uploaded as ArState.
+extern "C" int vx_op_bgemm(int32_t epi, int32_t kv8, const void* A, const void* W, const float* bias, int32_t N, int32_t K, int32_t B,
+                           int32_t kgroups, const int32_t* done, const int32_t* row, const int32_t* pass, float* q, void* kv, void* kv8s,
+                           int64_t kv_slot_stride, int64_t kv_v_offset, int32_t d, int32_t ctx_max, void* f, float* part, float* logits,
+                           int32_t logits_stride, float* trace, int32_t trace_rows, const int32_t* slot_map, void* stream) {
+  if (epi < BE_QKV || epi > BE_BIAS) return fail(VX_ERR_ARG, "bgemm: unknown epilogue %d", epi);
+  if (kv8 && epi != BE_QKV) return fail(VX_ERR_ARG, "bgemm: kv8 needs the QKV epilogue");
+  if (B < 1 || B > BMAX) return fail(VX_ERR_ARG, "bgemm: B %d outside [1, %d]", B, BMAX);
+  if (N < 1 || N > 65535 || K < 1 || K > 65535) return fail(VX_ERR_ARG, "bgemm: N %d, K %d outside [1, 65535]", N, K);
+  if (kgroups < 1 || (epi != BE_PARTIAL && kgroups != 1)) return fail(VX_ERR_ARG, "bgemm: kgroups %d (> 1 for BE_PARTIAL only)", kgroups);
+  const int ns = K / (kgroups * 128);
+  if (ns * kgroups * 128 != K || (ns != 1 && ns != 2 && ns != 4 && ns != 8))
+    return fail(VX_ERR_ARG, "bgemm: K %d is not ns x kgroups %d x 128 with ns in {1, 2, 4, 8}", K, kgroups);
+  if (!A || !W) return fail(VX_ERR_ARG, "bgemm: null A or W");
+  if ((epi == BE_QKV || epi == BE_RELU || epi == BE_BIAS) && !bias) return fail(VX_ERR_ARG, "bgemm: epilogue %d needs bias", epi);
+  const bool map = epi == BE_LOGITS_MAP;
+  const int nst = map ? BMAX : B;
+  if (epi == BE_QKV) {
+    if (d < 64 || d % 64 || N != 3 * d) return fail(VX_ERR_ARG, "bgemm: QKV needs d %% 64 == 0 and N == 3 d (d %d, N %d)", d, N);
+    if (!q || !kv || (kv8 && !kv8s)) return fail(VX_ERR_ARG, "bgemm: QKV needs q and the %s cache", kv8 ? "fp8 (codes + scales)" : "bf16");
+    if (ctx_max < 1 || kv_slot_stride < 0 || kv_v_offset < 0 || (kv8 && (kv_slot_stride % 16 || kv_v_offset % 16)))
+      return fail(VX_ERR_ARG, "bgemm: ctx_max %d, slot stride %lld, V offset %lld", ctx_max, (long long)kv_slot_stride,
+                  (long long)kv_v_offset);
+    for (int b = 0; b < B; ++b)
+      if (!(done && done[b]) && (row ? row[b] : 0) >= ctx_max) return fail(VX_ERR_ARG, "bgemm: row[%d] outside [0, ctx_max %d)", b, ctx_max);
+  }
+  if (epi == BE_RELU && !f) return fail(VX_ERR_ARG, "bgemm: BE_RELU needs f");
+  if (epi == BE_BIAS && !q) return fail(VX_ERR_ARG, "bgemm: BE_BIAS needs q");
+  if (epi == BE_PARTIAL && !part) return fail(VX_ERR_ARG, "bgemm: BE_PARTIAL needs part");
+  if (epi == BE_LOGITS || map) {
+    if (!logits || logits_stride < N) return fail(VX_ERR_ARG, "bgemm: logits need a buffer and a stride >= N (%d)", logits_stride);
+    if (trace && trace_rows < 1) return fail(VX_ERR_ARG, "bgemm: trace_rows %d", trace_rows);
+  }
+  if (map) {
+    if (!slot_map) return fail(VX_ERR_ARG, "bgemm: BE_LOGITS_MAP needs slot_map");
+    for (int z = 0; z < B; ++z)
+      if (slot_map[z] < 0 || slot_map[z] >= BMAX) return fail(VX_ERR_ARG, "bgemm: slot_map[%d] = %d outside [0, %d)", z, slot_map[z], BMAX);
+  }
+  std::vector<ArState> h(nst);  // zero-initialised: only done, row and pass are read
+  for (int b = 0; b < nst; ++b) {
+    h[b].done = done ? (done[b] != 0) : 0;
+    h[b].row = row ? row[b] : 0;
+    h[b].pass = pass ? pass[b] : 0;
+    if (h[b].row < 0 || h[b].pass < 0) return fail(VX_ERR_ARG, "bgemm: row[%d] / pass[%d] negative", b, b);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  struct Scratch {  // freed on every exit path
+    ArState* st = nullptr;
+    int* map = nullptr;
+    ~Scratch() { (void)hipFree(st); (void)hipFree(map); }
+  } t;
+  HIPC(hipMalloc((void**)&t.st, (size_t)nst * sizeof(ArState)));
+  HIPC(hipMemcpyAsync(t.st, h.data(), (size_t)nst * sizeof(ArState), hipMemcpyHostToDevice, s));
+  if (map) {
+    HIPC(hipMalloc((void**)&t.map, (size_t)B * sizeof(int)));
+    HIPC(hipMemcpyAsync(t.map, slot_map, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  BgemmArgs a{};
+  a.A = (const bf16*)A; a.W = (const bf16*)W; a.bias = bias; a.N = N; a.K = K; a.B = B; a.kgroups = kgroups; a.st = t.st;
+  a.q = q; a.kv_slot_stride = (size_t)kv_slot_stride; a.kv_v_offset = (size_t)kv_v_offset; a.d = d; a.hd = 64; a.ctx_max = ctx_max;
+  a.f = (bf16*)f; a.part = part; a.logits = logits; a.logits_stride = logits_stride; a.trace = trace; a.trace_rows = trace_rows;
+  a.slot_map = t.map;
+  if (kv8) { a.kv8 = (uint8_t*)kv; a.kv8s = (uint8_t*)kv8s; } else { a.kv = (bf16*)kv; }
+  int rc = VX_OK;
+  switch (epi) {
+    case BE_QKV: rc = kv8 ? launch_bgemm<BE_QKV, true>(a, s) : launch_bgemm<BE_QKV>(a, s); break;
+    case BE_RELU: rc = launch_bgemm<BE_RELU>(a, s); break;
+    case BE_PARTIAL: rc = launch_bgemm<BE_PARTIAL>(a, s); break;
+    case BE_LOGITS: rc = launch_bgemm<BE_LOGITS>(a, s); break;
+    case BE_LOGITS_MAP: rc = launch_bgemm<BE_LOGITS_MAP>(a, s); break;
+    default: rc = launch_bgemm<BE_BIAS>(a, s); break;
+  }
+  const hipError_t le = hipGetLastError();
+  const hipError_t se = hipStreamSynchronize(s);  // the scratch is in use until the stream has drained
+  if (rc != VX_OK) return rc;
+  HIPC(le);
+  HIPC(se);
+  return VX_OK;
+}
+
+// The batched step's LayerNorm (ln_batch_kernel<kgroups>, kgroups 0 / 1 / 4) or, with a host slot_map, batched prefill's
+// ln_batch_map_kernel, on caller buffers.
+extern "C" int vx_op_ln_batch(float* x, const float* part, int32_t kgroups, const float* pbias, const float* gamma, const float* beta,
+                              void* h, int32_t B, int32_t d, const int32_t* slot_map, void* stream) {
+  if (d < 4 || d > 1024 || d % 4) return fail(VX_ERR_ARG, "ln_batch: d %d (a multiple of 4 in [4, 1024])", d);
+  if (B < 1 || B > BMAX) return fail(VX_ERR_ARG, "ln_batch: B %d outside [1, %d]", B, BMAX);
+  if (kgroups != 0 && kgroups != 1 && kgroups != 4) return fail(VX_ERR_ARG, "ln_batch: kgroups %d (0, 1 or 4)", kgroups);
+  if (!x || !gamma || !beta || !h) return fail(VX_ERR_ARG, "ln_batch: null x, gamma, beta or h");
+  if (kgroups && (!part || !pbias)) return fail(VX_ERR_ARG, "ln_batch: kgroups %d needs part and pbias", kgroups);
+  if (slot_map) {
+    if (kgroups) return fail(VX_ERR_ARG, "ln_batch: the slot_map form adds no partials (kgroups %d)", kgroups);
+    for (int z = 0; z < B; ++z)
+      if (slot_map[z] < 0 || slot_map[z] >= BMAX) return fail(VX_ERR_ARG, "ln_batch: slot_map[%d] = %d outside [0, %d)", z, slot_map[z], BMAX);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  struct Scratch {  // freed on every exit path
+    int* map = nullptr;
+    ~Scratch() { (void)hipFree(map); }
+  } t;
+  if (slot_map) {
+    HIPC(hipMalloc((void**)&t.map, (size_t)B * sizeof(int)));
+    HIPC(hipMemcpyAsync(t.map, slot_map, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    ln_batch_map_kernel<<<B, 256, 0, s>>>(x, gamma, beta, (bf16*)h, d, t.map);
+  } else {
+    launch_ln_batch(x, kgroups ? part : nullptr, kgroups, pbias, gamma, beta, (bf16*)h, B, d, s);
+  }
   const hipError_t le = hipGetLastError();
   const hipError_t se = hipStreamSynchronize(s);
   HIPC(le);

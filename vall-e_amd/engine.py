@@ -21,6 +21,7 @@ VX_FLAG_TRACE_LOGITS, VX_FLAG_NO_GRAPH, VX_FLAG_SIMPLE_ROWS, VX_FLAG_POST_NORM, 
 VX_FLAG_KV_FP8 = 64
 KV_CACHES = ("bf16", "fp8")  # storage of the batched decode's slot caches (VX_FLAG_KV_FP8)
 VX_ADMIT_BATCHED, VX_ADMIT_PER_SLOT = 0, 1
+BE_QKV, BE_RELU, BE_PARTIAL, BE_LOGITS, BE_LOGITS_MAP, BE_BIAS = range(6)  # bgemm_kernel epilogues (csrc/batch_kernels.hpp)
 STOP_REASONS = {0: "none", 1: "eos_argmax", 2: "eos_sample", 3: "length", 4: "max_new"}
 
 
@@ -85,6 +86,11 @@ _SIGS = {
                          + [C.POINTER(C.c_int32)] * 2 + [C.c_void_p, C.c_void_p]),
     "vx_op_attn_mem_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 3
                              + [C.POINTER(C.c_int32)] * 2 + [C.c_void_p, C.c_void_p]),
+    "vx_op_bgemm": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3
+                    + [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p,
+                    C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
+    "vx_op_ln_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                       C.c_void_p]),
     "vx_op_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "vx_op_convert_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
@@ -534,6 +540,35 @@ def op_attn_mem_slots(q, mem, lens, done, out=None):
     _check(lib.vx_op_attn_mem_slots(_ptr(q), mem.data_ptr(), mem.stride(0), mem.stride(1), mem.shape[3], B, d // 64, _i32(lens),
                                     _i32(done), _ptr(out), current_stream_ptr(q.device)))
     return out
+
+
+def op_bgemm(epi, A, W, bias, B, kgroups=1, done=None, row=None, pass_=None, q=None, kv=None, kv_scale=None, d=0, ctx_max=0,
+             f=None, part=None, logits=None, trace=None, slot_map=None):
+    """One launch of the batched step's GEMM (vx_op_bgemm) in epilogue `epi` (BE_*) on A bf16 (32 or 64, K), W bf16 (N, K) and the
+    caller's output buffers, which are written in place: q fp32, kv a strided (slots, 2, H, ctx_max, 64) view of a bf16 cache or of
+    uint8 e4m3 codes (kv_scale: the matching scale bytes), f bf16 (>= B, N), part fp32 (kgroups, 64, N), logits fp32 (rows, stride),
+    trace fp32 (slots, trace_rows, N).  done / row / pass_ / slot_map: host sequences (None: zeros)."""
+    lib = load_library()
+    assert A.dtype == W.dtype == torch.bfloat16 and A.is_contiguous() and W.is_contiguous()
+    N, K = W.shape
+    kv8 = kv is not None and kv.dtype == torch.uint8
+    assert kv8 == (kv_scale is not None)
+    ls = 0 if logits is None else logits.stride(0)
+    tr = 0 if trace is None else trace.shape[1]
+    _check(lib.vx_op_bgemm(epi, int(kv8), _ptr(A), _ptr(W), _ptr(bias), N, K, B, kgroups, _i32(done), _i32(row), _i32(pass_), _ptr(q),
+                           None if kv is None else kv.data_ptr(), None if kv_scale is None else kv_scale.data_ptr(),
+                           0 if kv is None else kv.stride(0), 0 if kv is None else kv.stride(1), d, ctx_max, _ptr(f), _ptr(part),
+                           None if logits is None else logits.data_ptr(), ls, _ptr(trace), tr, _i32(slot_map), current_stream_ptr(A.device)))
+
+
+def op_ln_batch(x, gamma, beta, h, B, part=None, pbias=None, kgroups=0, slot_map=None):
+    """The batched step's LayerNorm (vx_op_ln_batch) in place: x fp32 (64, d) (written back when kgroups > 0), part fp32
+    (kgroups, 64, d), h bf16 (>= B, d); slot_map (host sequence, kgroups 0): batched prefill's mapped form."""
+    lib = load_library()
+    d = x.shape[1]
+    assert x.dtype == torch.float32 and h.dtype == torch.bfloat16
+    _check(lib.vx_op_ln_batch(_ptr(x), _ptr(part), kgroups, _ptr(pbias), _ptr(gamma), _ptr(beta), _ptr(h), B, d, _i32(slot_map),
+                              current_stream_ptr(x.device)))
 
 
 def op_sample(logits, top_k, temperature, exp_noise):

@@ -30,11 +30,17 @@ def _ids_out_of_range(x: torch.Tensor, y: torch.Tensor) -> bool:
     return bool(torch.stack(flags).any())
 
 
+# d_model of batched decode (max_batch >= 2): the step's GEMM kernel runs K = ns x kgroups x 128 with ns in {1, 2, 4, 8} and
+# kgroups in {1, 4}, which K = d and K = 4 d fit at these widths only (vx_create refuses the others)
+BATCH_WIDTHS = (128, 256, 512, 1024)
+
+
 class VALLE:
     """Decoder-only VALL-E (inference only).  Engine-specific keyword arguments (not in the
     reference): ``precision`` ("bf16" | "fp32" | "fp8nar"), ``max_text``, ``max_audio`` (capacities), ``max_batch`` (slots of
-    ``inference_batch`` / ``inference_stream``), ``kv_cache`` ("bf16" | "fp8": storage of those slots' KV caches; "fp8" needs
-    max_batch >= 2, a bf16 / fp8nar precision, head_dim 64 and a pre-norm VALL-E without prenets),
+    ``inference_batch`` / ``inference_stream``; >= 2 needs head_dim 64 and d_model in BATCH_WIDTHS), ``kv_cache`` ("bf16" |
+    "fp8": storage of those slots' KV caches; "fp8" needs max_batch >= 2, a bf16 / fp8nar precision, head_dim 64 and a pre-norm
+    VALL-E without prenets),
     ``sampling`` ("device": on-GPU counter RNG seeded from torch's global generator;
     "torch_cpu": reproduce the exact Exp(1) stream torch.multinomial would consume on CPU)."""
 
@@ -72,8 +78,8 @@ class VALLE:
         if self.cfg.is_vallf and self.engine_opts["max_batch"] > 1:  # the engine refuses these too (vx_create)
             if self.engine_opts["precision"] != "bf16":
                 raise NotImplementedError("VALL-F with max_batch >= 2 needs precision 'bf16'")
-            if d_model % nhead or d_model // nhead != 64 or d_model % 128:
-                raise NotImplementedError("VALL-F with max_batch >= 2 needs head_dim 64 and d_model % 128 == 0")
+            if d_model % nhead or d_model // nhead != 64:
+                raise NotImplementedError("VALL-F with max_batch >= 2 needs head_dim 64")
         if self.cfg.is_vallf and self.engine_opts["precision"] == "fp8nar":
             raise NotImplementedError("precision 'fp8nar' is built for VALL-E only")
         # head_dim 64 is the tuned geometry; 4/8/16/32 (the reference's own test: decoder_dim 64, nhead 16, valle_test.py:93-95)
@@ -85,6 +91,8 @@ class VALLE:
             raise NotImplementedError(f"head_dim must be 4, 8, 16, 32 or 64 (got {hds}; DESIGN.md)")
         if any(h != 64 for h in hds) and self.engine_opts.get("max_batch", 0) > 1:
             raise NotImplementedError("inference_batch needs head_dim 64")
+        if self.engine_opts.get("max_batch", 0) > 1 and d_model not in BATCH_WIDTHS:  # the engine refuses these too (vx_create)
+            raise NotImplementedError(f"batched decode (max_batch >= 2) needs d_model in {BATCH_WIDTHS} (got {d_model}; DESIGN.md 4.3)")
         self.ar_audio_prepend_bos = self.cfg.prepend_bos
         self.num_quantizers = self.cfg.num_quantizers
         self.prefix_mode = prefix_mode
@@ -344,7 +352,7 @@ class VALLF(VALLE):
     result (valle.py:566-710).  The text is embedded once as the memory of a TransformerDecoder whose target is the audio
     sequence alone; the reference masks memory positions >= x_lens (all-false for the unpadded batch-1 input it accepts).
     The reference's VALLF has no ``continual`` and no batched entry point.  This one has no ``continual`` either; built with
-    ``max_batch >= 2`` (pre-norm, no prenets, head_dim 64, d_model % 128 == 0, bf16) it has ``inference_batch`` and
+    ``max_batch >= 2`` (pre-norm, no prenets, head_dim 64, d_model in {128, 256, 512, 1024}, bf16) it has ``inference_batch`` and
     ``inference_stream``, which prefill and admit slot by slot and run the NAR stages per utterance (``batched_prefill``,
     ``batched_admit`` and ``batched_nar`` are ignored)."""
 
