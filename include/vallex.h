@@ -103,7 +103,13 @@ typedef struct vx_config {
 } vx_config;
 
 /* Sampling / stop-rule parameters of one AR decode (VALLE.inference args top_k, temperature,
- * valle.py:967-968; topk_sampling valle.py:1287-1302). */
+ * valle.py:967-968; topk_sampling valle.py:1287-1302).  The filters run in the reference's order: logits / temperature,
+ * top-k, then the nucleus (top-p) filter of top_k_top_p_filtering (valle.py:1262-1282), then the multinomial.  top_p: 0
+ * (what every zero-initialised struct holds) or any value >= 1 is off; a value in (0, 1) keeps the smallest prefix of the
+ * sorted (tempered, top-k-filtered) distribution whose cumulative probability exceeds top_p, the largest token always, and
+ * every token tied with the boundary token; what top-k removed stays removed.  NaN or a negative value: VX_ERR_ARG, before
+ * any HIP call (vx_ar_decode, vx_batch_decode, vx_batch_admit).  Per utterance: the slots of one batch or session may mix
+ * top_p values. */
 typedef struct vx_decode_params {
   int32_t struct_size;
   int32_t top_k;            /* <= 0: no filtering (the reference default -100) */
@@ -114,6 +120,7 @@ typedef struct vx_decode_params {
   uint64_t seed;            /* device counter RNG seed, used when exp_noise == NULL */
   const int64_t* forced;    /* optional teacher forcing: token appended at pass i = forced[i]     */
   int32_t n_forced;         /*   (the sample is still drawn and recorded); decode ends after them */
+  float top_p;              /* nucleus filter: 0 or >= 1 = off, (0, 1) = on (fills the tail padding: sizeof stays 56) */
 } vx_decode_params;
 
 const char* vx_last_error(void);
@@ -304,6 +311,11 @@ int vx_op_ln_batch(float* x, const float* part, int32_t kgroups, const float* pb
                    int32_t B, int32_t d, const int32_t* slot_map /* nullable */, void* stream);
 int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
                  int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
+/* vx_op_sample with the nucleus filter after top-k (top_p as in vx_decode_params: 0 or >= 1 off, NaN / negative VX_ERR_ARG).
+ * V <= 1088 runs the decode step's own sampler (the four-wave kernel every step form launches); V > 1088 with top_p on is
+ * VX_ERR_UNSUPPORTED (the single-wave kernel has no nucleus stage), with top_p off it is vx_op_sample. */
+int vx_op_sample_topp(const float* logits, int32_t V, int32_t top_k, float temperature, float top_p, const float* exp_noise,
+                      int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 int vx_op_convert_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);
 
 #ifdef __cplusplus

@@ -677,6 +677,91 @@ __global__ __launch_bounds__(64) void sample_embed_kernel(const SampleArgs a) {
   }
 }
 
+// ---- nucleus (top-p) filter (valle.py:1262-1282) on order keys ----
+// The reference sorts the filtered logits, takes c = cumsum(softmax) and removes sorted position k >= 1 when c[k-1] > top_p.
+// Sorted position k holds an entry of key K; c[k-1] is then at least the mass of all keys > K, and with the tie rule below
+// exactly that: an entry is kept iff the mass of the strictly larger keys is <= top_p.  That mass falls as the key rises, so
+// the kept set is {key >= tau} for the largest key tau whose inclusive mass G(tau) = sum(p : key >= tau) exceeds top_p (no
+// such key: nothing is removed).  Ties: torch's sort order among equal logits is unspecified; every token tied with tau is
+// kept, as the top-k threshold keeps its ties.  Masses are p = e / Z in unsigned 1.31 fixed point, so every sum is an integer
+// sum and the kept set cannot depend on summation order, slot or timing; top_p becomes floor(top_p 2^31) (G > top_p <=>
+// G > floor(top_p 2^31) for integer G).
+__device__ __forceinline__ uint32_t topp_mass(float e, float Z) { return __float2uint_rn((e / Z) * 2147483648.0f); }
+
+// Fast path (wave 0, top-k on with k <= 64): the candidates are the keys >= T (the top-k threshold).  They are compacted into
+// LDS (key, e), one per lane; lane i then sums the masses of the larger candidates (uniform loop over the cnt candidates,
+// readlane broadcasts), which is the exclusive mass of the sorted prefix without sorting.  Returns false (nothing written)
+// when more than 64 keys tie at or above T: the block path takes over.  *T2 = the nucleus threshold, *Z2 = the sum of e
+// over the kept candidates (the renormalisation of valle.py:1301, in a fixed DPP order).
+template <int NV0>
+__device__ __forceinline__ bool topp_fast_wave(const float (&w0)[NV0], float temp, float mx, float Z, uint32_t T, uint32_t TP,
+                                               int V, int lane, uint32_t* ck, float* ce, uint32_t* T2, float* Z2) {
+  int cnt = 0;
+#pragma unroll
+  for (int j = 0; j < NV0; ++j) {
+    const float x = (temp != 1.0f) ? w0[j] / temp : w0[j];
+    const bool in = (j * 64 + lane < V) && order_key(x) >= T;
+    const unsigned long long mk = __ballot(in);
+    if (mk == 0ull) continue;  // uniform
+    const int pos = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+    if (in && pos < 64) { ck[pos] = order_key(x); ce[pos] = expf(x - mx); }
+    cnt += __popcll(mk);
+  }
+  if (cnt > 64) return false;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // same wave writes and reads: the LDS queue is in order
+  const uint32_t k = (lane < cnt) ? ck[lane] : 0u;
+  const float e = (lane < cnt) ? ce[lane] : 0.f;
+  const uint32_t m = topp_mass(e, Z);
+  uint32_t ex = 0u;
+  for (int j = 0; j < cnt; ++j) {
+    const uint32_t kj = __builtin_amdgcn_readlane(k, j), mj = __builtin_amdgcn_readlane(m, j);
+    ex += (kj > k) ? mj : 0u;
+  }
+  const bool kept = lane < cnt && ex <= TP;
+  *T2 = wave_umin_dpp(kept ? k : 0xffffffffu);
+  *Z2 = wave_sum_dpp(kept ? e : 0.f);
+  return true;
+}
+
+// General path (all 256 threads; no top-k, k > 64, or > 64 ties): radix select of tau over the 32-bit keys, 8 bits per pass.
+// Pass p adds the masses of the keys that share the p bytes chosen so far into 256 bins of the next byte (integer LDS atomics:
+// the sum is exact whatever their order); after a barrier every wave scans the same histogram (lane l: bins 4l..4l+3, suffix
+// sums across lanes) and picks the highest bin b with A + mass(bins >= b) > TP, A = the mass of the keys above the prefix.
+// hist: 4 x 256 zeroed words (one histogram per pass, so no pass has to clear one behind a barrier).  Returns 0 if the total
+// mass does not exceed TP (nothing removed).
+template <int NVT>
+__device__ __forceinline__ uint32_t topp_radix_block(const uint32_t (&key)[NVT], const uint32_t (&m)[NVT], uint32_t TP, int lane,
+                                                     uint32_t* hist) {
+  uint32_t P = 0u, A = 0u;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int sh = 24 - 8 * p;
+    uint32_t* h = hist + 256 * p;
+#pragma unroll
+    for (int j = 0; j < NVT; ++j)
+      if (m[j] != 0u && (p == 0 || (key[j] >> (sh + 8)) == P)) atomicAdd(h + ((key[j] >> sh) & 255u), m[j]);
+    __syncthreads();
+    const uint4 hb = reinterpret_cast<const uint4*>(h)[lane];
+    uint32_t suf = (hb.x + hb.y) + (hb.z + hb.w);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t t = __shfl_down(suf, off);
+      if (lane + off < 64) suf += t;
+    }
+    // mass of bins >= 4 lane + i
+    const uint32_t s3 = suf - ((hb.x + hb.y) + hb.z), s2 = s3 + hb.z, s1 = s2 + hb.y, s0 = s1 + hb.x;
+    const int n = __popcll(__ballot(A + s0 > TP)) + __popcll(__ballot(A + s1 > TP)) + __popcll(__ballot(A + s2 > TP)) +
+                  __popcll(__ballot(A + s3 > TP));
+    if (n == 0) return 0u;  // uniform; only at p == 0 (afterwards the chosen prefix carries mass > TP - A)
+    const int b = n - 1, nb = b + 1;
+    const int q = nb & 3;
+    const uint32_t sel = q == 0 ? s0 : q == 1 ? s1 : q == 2 ? s2 : s3;
+    if (nb < 256) A += __builtin_amdgcn_readlane(sel, nb >> 2);
+    P = (P << 8) | (uint32_t)b;
+  }
+  return P;
+}
+
 // Four-wave variant used by the decode step: the single-wave kernel above executes ~3000 instructions
 // serially; here thread t owns logits t, t+256, ... (NVT each) for the elementwise work and the four
 // block-level reductions, while wave 0 alone also holds all keys (NV0 per lane) for the exact top-k select.
@@ -691,6 +776,10 @@ __device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, c
   __shared__ int s_ai[4], s_si[4];
   __shared__ uint32_t cand_lds[64];
   __shared__ uint32_t s_T;
+  __shared__ float s_ce[64], s_Z2;  // nucleus filter
+  __shared__ __attribute__((aligned(16))) uint32_t s_hist[4 * 256];
+  __shared__ uint32_t s_T2;
+  __shared__ int s_fast;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = a.V;
   float qn[NVT];
@@ -713,6 +802,8 @@ __device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, c
   const float temp = s.temperature;
   const int top_k = s.top_k;
   const bool filt = top_k > 0 && top_k < V;  // uniform
+  const float top_p = s.top_p;
+  const bool nucleus = top_p > 0.f && top_p < 1.f;  // uniform
   const unsigned long long seed = s.seed;
   const int n_gen = s.n_gen, bos = s.bos, S = s.S, max_new = s.max_new, n_forced = s.n_forced;
   const long long* forced = s.forced;
@@ -763,8 +854,44 @@ __device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, c
   }
   zs = wave_sum_dpp(zs);
   if (lane == 0) s_f[wave] = zs;
+  if (nucleus) *reinterpret_cast<uint4*>(s_hist + 4 * tid) = make_uint4(0u, 0u, 0u, 0u);  // behind the barrier below
   __syncthreads();
-  const float Z = ((s_f[0] + s_f[1]) + s_f[2]) + s_f[3];
+  float Z = ((s_f[0] + s_f[1]) + s_f[2]) + s_f[3];
+
+  // nucleus (top-p) filter, valle.py:1262-1282: a second key threshold T2, kept = key >= T2 as well (topp_fast_wave /
+  // topp_radix_block above); the softmax is renormalised over what is left (Z).  Off (top_p 0 or >= 1): one uniform branch.
+  if (nucleus) {
+    const uint32_t TP = __float2uint_rd(top_p * 2147483648.0f);
+    if (wave == 0) {
+      uint32_t t2 = 0u;
+      float z2 = 0.f;
+      const bool fast = filt && top_k <= 64 && topp_fast_wave<NV0>(w0, temp, mx, Z, T, TP, V, lane, cand_lds, s_ce, &t2, &z2);
+      if (lane == 0) { s_fast = fast ? 1 : 0; s_T2 = t2; s_Z2 = z2; }
+    }
+    __syncthreads();
+    uint32_t T2;
+    if (s_fast) {
+      T2 = s_T2;
+      Z = s_Z2;
+    } else {
+      uint32_t key[NVT], m[NVT];
+#pragma unroll
+      for (int j = 0; j < NVT; ++j) {
+        key[j] = order_key(v[j]);
+        m[j] = keep[j] ? topp_mass(e[j], Z) : 0u;
+      }
+      T2 = topp_radix_block<NVT>(key, m, TP, lane, s_hist);
+      zs = 0.f;
+#pragma unroll
+      for (int j = 0; j < NVT; ++j) zs += (keep[j] && key[j] >= T2) ? e[j] : 0.f;
+      zs = wave_sum_dpp(zs);
+      if (lane == 0) s_f[wave] = zs;  // the last read of s_f was four barriers ago
+      __syncthreads();
+      Z = ((s_f[0] + s_f[1]) + s_f[2]) + s_f[3];
+    }
+#pragma unroll
+    for (int j = 0; j < NVT; ++j) keep[j] = keep[j] && order_key(v[j]) >= T2;
+  }
 
   // multinomial(p, 1) == argmax(p / q), q ~ Exp(1)
   ValIdx sm{-1.f, 0x7fffffff};

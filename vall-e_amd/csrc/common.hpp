@@ -252,6 +252,7 @@ struct ArState {
   int32_t trace_logits;
   int32_t kv_text;    // rows in front of the audio sub-sequence in the KV cache: S for VALL-E (text rows are cached), 0 for VALL-F
                       // (the text is cross-attention memory); audio position of KV row r = r - kv_text (valle.py:1013-1016)
+  float top_p;        // nucleus filter (vx_decode_params.top_p): in (0, 1) filters, 0 = off (the host maps >= 1 to 0)
 };
 
 }  // namespace vx

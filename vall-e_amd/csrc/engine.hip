@@ -1672,10 +1672,18 @@ static int enqueue_ar_step_f(vx_engine* e, hipStream_t s) {
 // text must not be refused up front: the bound is clamped to the rows the KV cache has (*cap_limited; `room` of them), and only a
 // decode that really fills them while the stop rule has not fired is a capacity error.  S / P / bos are the prefill geometry;
 // slot >= 0 names the batch slot in the message.
+// top_p: NaN or negative is an error; 0 and >= 1 are off (stored as 0), (0, 1) filters.
+static int check_top_p(float top_p) {
+  if (!(top_p >= 0.f)) return fail(VX_ERR_ARG, "top_p must be >= 0 (0 or >= 1: off), got %g", (double)top_p);
+  return VX_OK;
+}
+static float state_top_p(float top_p) { return top_p > 0.f && top_p < 1.f ? top_p : 0.f; }
+
 static int decode_bound(vx_engine* e, int slot, const vx_decode_params& p, int S, int P, int bos, long long* steps,
                         bool* cap_limited, long long* room) {
   if (p.struct_size != (int32_t)sizeof(vx_decode_params)) return fail(VX_ERR_ARG, "vx_decode_params.struct_size mismatch");
   if (!(p.temperature > 0.f)) return fail(VX_ERR_ARG, "temperature must be > 0");
+  VXC(check_top_p(p.top_p));
   long long max_tok = 16LL * S + 1 - bos;  // appended tokens (valle.py:1047: stops once bos + n_gen > 16 S)
   if (p.forced) max_tok = p.n_forced;
   else if (p.max_new_tokens >= 0 && p.max_new_tokens < max_tok) max_tok = p.max_new_tokens;
@@ -1782,6 +1790,7 @@ extern "C" int vx_ar_decode(vx_engine* e, const vx_decode_params* p, void* strea
   }
   ArState& st = e->h_st[0];
   st.top_k = p->top_k; st.temperature = p->temperature; st.max_new = cap_limited ? (int)room : p->max_new_tokens;
+  st.top_p = state_top_p(p->top_p);
   st.exp_noise = p->exp_noise ? e->d_noise : nullptr;
   st.noise_rows = p->noise_rows; st.seed = p->seed;
   st.forced = p->forced ? (p->n_forced > 0 ? e->d_forced : (const long long*)e->d_tokens) : nullptr;
@@ -1957,6 +1966,7 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
 static void batch_params_stage(vx_engine* e, int slot, const vx_decode_params& p, bool cap_limited, long long room) {
   ArState& st = e->h_bst[slot];
   st.top_k = p.top_k; st.temperature = p.temperature; st.max_new = cap_limited ? (int)room : p.max_new_tokens;
+  st.top_p = state_top_p(p.top_p);
   st.exp_noise = p.exp_noise; st.noise_rows = p.noise_rows; st.seed = p.seed;
   st.forced = p.forced ? (p.n_forced > 0 ? (const long long*)p.forced : (const long long*)e->btok) : nullptr;
   st.n_forced = p.forced ? p.n_forced : 0;
@@ -2006,6 +2016,10 @@ static int run_slots(vx_engine* e, int B, int min_stopped, int chunk, int32_t* s
 extern "C" int vx_batch_decode(vx_engine* e, int32_t B, const vx_decode_params* params, void* stream) {
   if (!e || !params) return fail(VX_ERR_ARG, "null argument");
   if (B < 1 || B > e->bmax) return fail(VX_ERR_ARG, "n_slots %d outside [1, max_batch=%d]", B, e->bmax);
+  for (int b = 0; b < B; ++b) {  // the parameter checks that need no slot state, before any HIP call
+    if (params[b].struct_size != (int32_t)sizeof(vx_decode_params)) return fail(VX_ERR_ARG, "vx_decode_params.struct_size mismatch");
+    VXC(check_top_p(params[b].top_p));
+  }
   const vx_config& c = e->cfg;
   ON_DEVICE(c.device);
   e->bsess = false;  // the static calls end a continuous-batching session
@@ -2579,6 +2593,41 @@ extern "C" int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float
   // the single-wave one for larger test vocabularies
   if (V <= 17 * 64) sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(sa);
   else sample_embed_kernel<32><<<1, 64, 0, s>>>(sa);
+  HIPC(hipGetLastError());
+  int host[16];
+  HIPC(hipMemcpyAsync(host, scratch, sizeof host, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  out[0] = host[4];
+  out[1] = host[8];
+  (void)hipFree(dst); (void)hipFree(scratch); (void)hipFree(fz);
+  return VX_OK;
+}
+
+// vx_op_sample with the nucleus filter: the same scratch state with top_p, on the decode step's four-wave sampler.
+extern "C" int vx_op_sample_topp(const float* logits, int32_t V, int32_t top_k, float temperature, float top_p,
+                                 const float* exp_noise, int32_t* out, void* stream) {
+  if (!logits || !out) return fail(VX_ERR_ARG, "null argument");
+  VXC(check_top_p(top_p));
+  const float tp = state_top_p(top_p);
+  if (tp == 0.f) return vx_op_sample(logits, V, top_k, temperature, exp_noise, out, stream);
+  if (V < 2 || V > 17 * 64) return fail(VX_ERR_UNSUPPORTED, "sample_topp: V=%d (the nucleus filter is built for V <= 1088)", V);
+  hipStream_t s = (hipStream_t)stream;
+  ArState h{};
+  h.S = 1 << 20; h.kv_text = h.S; h.top_k = top_k; h.temperature = temperature; h.max_new = -1; h.top_p = tp;
+  h.exp_noise = exp_noise; h.noise_rows = 1; h.seed = 1;
+  ArState* dst = nullptr;
+  int* scratch = nullptr;
+  float* fz = nullptr;
+  HIPC(hipMalloc((void**)&dst, sizeof h));
+  HIPC(hipMalloc((void**)&scratch, 16 * sizeof(int)));
+  HIPC(hipMalloc((void**)&fz, 4096 * sizeof(float)));
+  HIPC(hipMemsetAsync(fz, 0, 4096 * sizeof(float), s));
+  HIPC(hipMemcpyAsync(dst, &h, sizeof h, hipMemcpyHostToDevice, s));
+  SampleArgs sa{};
+  sa.logits = logits; sa.V = V; sa.st = dst;
+  sa.tokens = scratch; sa.sampled = scratch + 4; sa.argmaxes = scratch + 8;
+  sa.emb = fz; sa.alpha = fz; sa.pe = fz; sa.x = fz + 2048; sa.d = 0;
+  sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(sa);
   HIPC(hipGetLastError());
   int host[16];
   HIPC(hipMemcpyAsync(host, scratch, sizeof host, hipMemcpyDeviceToHost, s));

@@ -35,7 +35,7 @@ class VxDecodeParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("top_k", C.c_int32), ("temperature", C.c_float), ("max_new_tokens", C.c_int32),
         ("exp_noise", C.c_void_p), ("noise_rows", C.c_int64), ("seed", C.c_uint64),
-        ("forced", C.c_void_p), ("n_forced", C.c_int32),
+        ("forced", C.c_void_p), ("n_forced", C.c_int32), ("top_p", C.c_float),
     ]
 
 
@@ -92,6 +92,8 @@ _SIGS = {
     "vx_op_ln_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                        C.c_void_p]),
     "vx_op_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "vx_op_sample_topp": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
+                                    C.c_void_p]),
     "vx_op_convert_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
@@ -232,10 +234,11 @@ class Engine:
         _check(self.lib.vx_ar_prefill(self.h, _ptr(text), text.numel(), _ptr(prompt_cb0), prompt_cb0.numel(), stream))
 
     def ar_decode(self, top_k: int = -100, temperature: float = 1.0, exp_noise: Optional[torch.Tensor] = None,
-                  seed: int = 0, max_new_tokens: int = -1, forced: Optional[torch.Tensor] = None, stream=None):
+                  seed: int = 0, max_new_tokens: int = -1, forced: Optional[torch.Tensor] = None, stream=None, top_p: float = 1.0):
         p = VxDecodeParams()
         p.struct_size = C.sizeof(VxDecodeParams)
         p.top_k, p.temperature, p.max_new_tokens, p.seed = int(top_k), float(temperature), int(max_new_tokens), int(seed)
+        p.top_p = _struct_top_p(top_p)
         keep = []
         if exp_noise is not None:
             exp_noise = exp_noise.to(torch.float32).contiguous()
@@ -294,14 +297,19 @@ class Engine:
         _check(self.lib.vx_batch_prefill_all(self.h, n, tp, S, pp, P, stream))
 
     @staticmethod
-    def _decode_params(n, top_k, temperature, seeds, exp_noise, forced, max_new_tokens):
-        """(VxDecodeParams array, per-entry list of the device tensors its pointers refer to)."""
+    def _decode_params(n, top_k, temperature, seeds, exp_noise, forced, max_new_tokens, top_p=1.0):
+        """(VxDecodeParams array, per-entry list of the device tensors its pointers refer to).  ``top_k`` / ``top_p``: one
+        value for every entry, or a sequence of n (the slots of one batch may mix filters)."""
         arr = (VxDecodeParams * n)()
         keep = [[] for _ in range(n)]
+        tks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
+        tps = list(top_p) if isinstance(top_p, (list, tuple)) else [top_p] * n
+        assert len(tks) == n and len(tps) == n
         for b in range(n):
             p = arr[b]
             p.struct_size = C.sizeof(VxDecodeParams)
-            p.top_k, p.temperature, p.max_new_tokens = int(top_k), float(temperature), int(max_new_tokens)
+            p.top_k, p.temperature, p.max_new_tokens = int(tks[b]), float(temperature), int(max_new_tokens)
+            p.top_p = _struct_top_p(tps[b])
             p.seed = int(seeds[b]) if seeds is not None else b + 1
             if exp_noise is not None and exp_noise[b] is not None:
                 t = exp_noise[b].to(torch.float32).contiguous()
@@ -316,9 +324,10 @@ class Engine:
         return arr, keep
 
     def batch_decode(self, n_slots: int, top_k=-100, temperature=1.0, seeds=None, exp_noise=None, forced=None,
-                     max_new_tokens=-1, stream=None):
-        """exp_noise / forced: optional per-slot lists of DEVICE tensors (kept alive here for the call)."""
-        arr, keep = self._decode_params(n_slots, top_k, temperature, seeds, exp_noise, forced, max_new_tokens)
+                     max_new_tokens=-1, stream=None, top_p=1.0):
+        """exp_noise / forced: optional per-slot lists of DEVICE tensors (kept alive here for the call).  top_k / top_p: one value
+        or one per slot."""
+        arr, keep = self._decode_params(n_slots, top_k, temperature, seeds, exp_noise, forced, max_new_tokens, top_p)
         _check(self.lib.vx_batch_decode(self.h, n_slots, arr, stream))
 
     # -- continuous batching (vx_batch_open / _admit / _run) ------------------------------------------
@@ -328,14 +337,14 @@ class Engine:
         self._slot_keep = {}
 
     def batch_admit(self, slots, texts, prompts_cb0, top_k=-100, temperature=1.0, seeds=None, exp_noise=None, forced=None,
-                    max_new_tokens=-1, batched=True, stream=None):
+                    max_new_tokens=-1, batched=True, stream=None, top_p=1.0):
         """Prefills ``texts[z]`` / ``prompts_cb0[z]`` into vacant slot ``slots[z]`` and arms it (seeds / exp_noise / forced per
         utterance, as for ``batch_decode``).  ``batched``: one pass over the concatenated rows; False: the per-slot prefill.  The
         device tensors a slot's parameters point to are kept until that slot's result is read."""
         n = len(slots)
         texts = [t.to(torch.int64).contiguous() for t in texts]
         proms = [p.to(torch.int64).contiguous() for p in prompts_cb0]
-        arr, keep = self._decode_params(n, top_k, temperature, seeds, exp_noise, forced, max_new_tokens)
+        arr, keep = self._decode_params(n, top_k, temperature, seeds, exp_noise, forced, max_new_tokens, top_p)
         sl = (C.c_int32 * n)(*[int(s) for s in slots])
         tp = (C.c_void_p * n)(*[_ptr(t) for t in texts])
         pp = (C.c_void_p * n)(*[_ptr(p) for p in proms])
@@ -395,6 +404,14 @@ class Engine:
 
 
 # ---- kernel-level ops (parity tests call the HIP kernels through the same C ABI) -------------------
+def _struct_top_p(top_p) -> float:
+    """vx_decode_params.top_p of a Python top_p: 1.0 (the reference's default, no nucleus filter) -> 0, the struct's "off",
+    so that calls without the keyword pass exactly the bytes they passed before the field existed.  Other values go through
+    unchanged (the engine refuses NaN and negative values, treats >= 1 as off)."""
+    top_p = float(top_p)
+    return 0.0 if top_p == 1.0 else top_p
+
+
 def _prec(t_or_name) -> int:
     if isinstance(t_or_name, str):
         return VX_PREC_BF16 if t_or_name == "bf16" else VX_PREC_F32
@@ -576,6 +593,15 @@ def op_sample(logits, top_k, temperature, exp_noise):
     out = (C.c_int32 * 2)()
     _check(lib.vx_op_sample(_ptr(logits), logits.numel(), int(top_k), float(temperature), _ptr(exp_noise), out,
                             current_stream_ptr(logits.device)))
+    return out[0], out[1]
+
+
+def op_sample_topp(logits, top_k, temperature, top_p, exp_noise):
+    """vx_op_sample_topp: (sampled, argmax) of one logits row under temperature, top-k and the nucleus filter."""
+    lib = load_library()
+    out = (C.c_int32 * 2)()
+    _check(lib.vx_op_sample_topp(_ptr(logits), logits.numel(), int(top_k), float(temperature), _struct_top_p(top_p),
+                                 _ptr(exp_noise), out, current_stream_ptr(logits.device)))
     return out[0], out[1]
 
 

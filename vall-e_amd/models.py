@@ -35,6 +35,17 @@ def _ids_out_of_range(x: torch.Tensor, y: torch.Tensor) -> bool:
 BATCH_WIDTHS = (128, 256, 512, 1024)
 
 
+def _check_top_p(top_p) -> float:
+    """The nucleus filter's ``top_p`` (top_k_top_p_filtering, valle.py:1262-1282): a number in (0, 1]; 1.0 is off."""
+    try:
+        v = float(top_p)
+    except (TypeError, ValueError):
+        raise ValueError(f"top_p must be a number in (0, 1], got {top_p!r}") from None
+    if not 0.0 < v <= 1.0:  # NaN fails too
+        raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+    return v
+
+
 class VALLE:
     """Decoder-only VALL-E (inference only).  Engine-specific keyword arguments (not in the
     reference): ``precision`` ("bf16" | "fp32" | "fp8nar"), ``max_text``, ``max_audio`` (capacities), ``max_batch`` (slots of
@@ -42,7 +53,9 @@ class VALLE:
     "fp8": storage of those slots' KV caches; "fp8" needs max_batch >= 2, a bf16 / fp8nar precision, head_dim 64 and a pre-norm
     VALL-E without prenets),
     ``sampling`` ("device": on-GPU counter RNG seeded from torch's global generator;
-    "torch_cpu": reproduce the exact Exp(1) stream torch.multinomial would consume on CPU)."""
+    "torch_cpu": reproduce the exact Exp(1) stream torch.multinomial would consume on CPU).  ``inference``,
+    ``inference_batch`` and ``inference_stream`` take a ``top_p`` keyword (default 1.0, off): the reference's nucleus filter
+    (top_k_top_p_filtering, valle.py:1262-1282) after temperature and top-k, which its VALLE.inference does not expose."""
 
     MODEL_NAME = "VALL-E"  # what the EOS line prints and get_model dispatches on (models/__init__.py:98-124)
 
@@ -160,11 +173,12 @@ class VALLE:
     @torch.no_grad()
     def inference(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor, enroll_x_lens: Optional[torch.Tensor],
                   top_k: int = -100, temperature: float = 1.0, exp_noise: Optional[torch.Tensor] = None,
-                  max_new_tokens: int = -1) -> torch.Tensor:
+                  max_new_tokens: int = -1, top_p: float = 1.0) -> torch.Tensor:
         """Same contract as the reference (valle.py:961-985): x (1,S) int64, x_lens (1,), y (1,P,8) int64 →
-        (1,T,num_quantizers) int64 on the model's device.  ``exp_noise`` / ``max_new_tokens`` are extras.
+        (1,T,num_quantizers) int64 on the model's device.  ``exp_noise`` / ``max_new_tokens`` / ``top_p`` are extras.
         This batch-1 path keeps its own bf16 KV cache on every model, ``kv_cache="fp8"`` included (that option only
         changes the slot caches of ``inference_batch`` / ``inference_stream``)."""
+        top_p = _check_top_p(top_p)
         u = (x, x_lens, y, enroll_x_lens)
         self._check_utterance(u)
         eng = self.engine()
@@ -178,7 +192,8 @@ class VALLE:
             exp_noise = torch.stack([torch.empty(1, NUM_AUDIO_TOKENS + 1).exponential_(1)[0] for _ in range(n_max)])
         elif exp_noise is None:
             seed = int(torch.randint(0, 2**62, (1,)))
-        eng.ar_decode(top_k=top_k, temperature=temperature, exp_noise=exp_noise, seed=seed, max_new_tokens=max_new_tokens)
+        eng.ar_decode(top_k=top_k, temperature=temperature, exp_noise=exp_noise, seed=seed, max_new_tokens=max_new_tokens,
+                      top_p=top_p)
         tokens, reason, n_pass = eng.ar_result()
         if rng_state is not None:
             # leave the global generator where the reference would: one draw per executed pass, including
@@ -196,10 +211,11 @@ class VALLE:
 
     @torch.no_grad()
     def inference_batch(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, batched_nar: bool = True,
-                        batched_prefill: bool = True):
+                        batched_prefill: bool = True, top_p: float = 1.0):
         """Engine extension (BASELINE configs[2]): ``utterances`` = list of (x, x_lens, y[, enroll_x_lens]) as for
         ``inference``; up to ``max_batch`` of them advance together, one shared weight stream per AR step, each with
         its own KV cache / sampler / stop rule; the NAR stages then run per utterance.  Returns a list of (1,T_i,Q)."""
+        top_p = _check_top_p(top_p)
         eng = self._batch_engine("inference_batch")
         Q = self.num_quantizers
         out = [None] * len(utterances)
@@ -213,7 +229,7 @@ class VALLE:
             if batched_prefill and eng.mfma_rows:  # one pass over the concatenated rows of the whole group
                 eng.batch_prefill_all([u[0][0] for u in group], [u[2][0, :, 0].contiguous() for u in group])
             sd = [int(torch.randint(0, 2**62, (1,))) for _ in group] if seeds is None else list(seeds[g0 : g0 + len(group)])
-            eng.batch_decode(len(group), top_k=top_k, temperature=temperature, seeds=sd)
+            eng.batch_decode(len(group), top_k=top_k, temperature=temperature, seeds=sd, top_p=top_p)
             todo = []  # (index, text_nar, prompts, tokens) of the utterances that go through the NAR stages
             for b, u in enumerate(group):
                 tokens, reason = eng.batch_result(b)
@@ -273,7 +289,8 @@ class VALLE:
 
     @torch.no_grad()
     def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
-                         poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None):
+                         poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None,
+                         top_p: float = 1.0):
         """Engine extension: continuous batching.  A generator over ``utterances`` (as for ``inference_batch``) that yields
         ``(index, codes)``, codes (1, T_i, Q) as ``inference_batch`` returns them, as utterances finish.  A slot whose utterance
         stopped is refilled from the queue while the others keep decoding: new utterances are admitted once ``refill_at``
@@ -281,6 +298,7 @@ class VALLE:
         wait for their NAR stages until ``nar_group`` (default max_batch) are pending or the queue is empty.  ``seeds[i]``
         belongs to utterance i, so the codes do not depend on the schedule.  ``batched_admit=False`` prefills slot by slot
         (bitwise the static path); ``poll_steps``: steps between stop polls (0: the engine default)."""
+        top_p = _check_top_p(top_p)
         eng = self._batch_engine("inference_stream")
         utterances = list(utterances)
         for u in utterances:
@@ -293,9 +311,11 @@ class VALLE:
         refill_at = max(1, B // 16) if refill_at is None else max(1, int(refill_at))
         nar_group = B if nar_group is None else max(1, int(nar_group))
         batched_admit = batched_admit and eng.mfma_rows
-        return self._stream(eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at)
+        return self._stream(eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at,
+                            top_p)
 
-    def _stream(self, eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at):
+    def _stream(self, eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at,
+                top_p=1.0):
         N, B = len(utterances), eng.max_batch
         eng.batch_open()
         free = list(range(B))
@@ -308,7 +328,7 @@ class VALLE:
                 slots, free = free[:k], free[k:]
                 us = utterances[nxt : nxt + k]
                 eng.batch_admit(slots, [u[0][0] for u in us], [u[2][0, :, 0].contiguous() for u in us], top_k=top_k,
-                                temperature=temperature, seeds=seeds[nxt : nxt + k], batched=batched_admit)
+                                temperature=temperature, seeds=seeds[nxt : nxt + k], batched=batched_admit, top_p=top_p)
                 live.update((s, nxt + z) for z, s in enumerate(slots))
                 nxt += k
             if live:
@@ -366,16 +386,18 @@ class VALLF(VALLE):
             raise NotImplementedError(f"VALL-F {what} needs a model built with max_batch >= 2 (otherwise batch-1 path only)")
 
     def inference_batch(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, batched_nar: bool = True,
-                        batched_prefill: bool = True):
+                        batched_prefill: bool = True, top_p: float = 1.0):
         self._vallf_batched("inference_batch")
         return super().inference_batch(utterances, top_k=top_k, temperature=temperature, seeds=seeds, batched_nar=False,
-                                       batched_prefill=False)
+                                       batched_prefill=False, top_p=top_p)
 
     def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
-                         poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None):
+                         poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None,
+                         top_p: float = 1.0):
         self._vallf_batched("inference_stream")
         return super().inference_stream(utterances, top_k=top_k, temperature=temperature, seeds=seeds, nar_group=nar_group,
-                                        poll_steps=poll_steps, batched_admit=False, batched_nar=False, refill_at=refill_at)
+                                        poll_steps=poll_steps, batched_admit=False, batched_nar=False, refill_at=refill_at,
+                                        top_p=top_p)
 
 
 def get_model(params) -> VALLE:
