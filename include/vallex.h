@@ -230,7 +230,8 @@ int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* text_nar, con
 /* Device-time of the last calls, measured with HIP events on the engine's stream:
  * out[0] prefill ms, out[1] AR decode ms, out[2] NAR ms, out[3] AR passes, out[4] graph launches, out[5] batched decode ms,
  * out[6] batched graph launches; with VX_TIME_GEMMS=1 in the environment also out[7] = ms spent in the QKV / out-projection / FFN
- * GEMM launches of the last NAR call and out[8] = their FLOPs (2 M N K each). */
+ * GEMM launches of the last NAR call and out[8] = their FLOPs (2 M N K each); out[9] kernel launches per pass of the batch-1 decode
+ * step (nodes of its captured graph; 0 before the first vx_ar_decode and with VX_FLAG_NO_GRAPH). */
 int vx_get_timings(vx_engine* e, double* out, int32_t n);
 
 /* Parity-test taps: copies an internal buffer to host memory (synchronises the engine stream).
@@ -241,8 +242,13 @@ int vx_get_timings(vx_engine* e, double* out, int32_t n);
  * (64 x (max_audio+2) int32 per pass), "batch_trace" (max_batch x (max_audio+2) x 1025 fp32: every pass's logits row of every
  * slot, engines created with VX_FLAG_TRACE_LOGITS and max_batch > 1), "batch_kv" (the slot caches, max_batch > 1:
  * [slot][layer][K|V][head][max_text+max_audio][64] bf16, or e4m3 bytes with VX_FLAG_KV_FP8), "batch_kv_scale" (VX_FLAG_KV_FP8: the
- * E8M0 scale bytes, [slot][layer][K|V][head][max_text+max_audio][4]). */
+ * E8M0 scale bytes, [slot][layer][K|V][head][max_text+max_audio][4]), "ar_kv" (the batch-1 KV cache,
+ * [layer][K|V][head][max_text+max_audio][head_dim], fp32 on VX_PREC_F32 engines, else bf16). */
 int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t offset_bytes, int64_t nbytes);
+
+/* Bytes vx_read_buffer's tap `name` holds on an engine created with *cfg, for the taps whose size follows from the
+ * configuration alone ("ar_kv"); VX_ERR_ARG for any other name.  Host only: no HIP call. */
+int vx_buffer_bytes(const vx_config* cfg, const char* name, int64_t* bytes);
 
 /* Kernel-level entry points (device pointers, fp32 unless noted) used by tests/ to check each
  * HIP kernel against the oracle's corresponding torch op.  prec selects the storage type the

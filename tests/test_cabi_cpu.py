@@ -358,3 +358,43 @@ def test_host_mirror_refuses_batched_widths_without_a_bgemm_form(d):
     for d_ok in (128, 256, 512, 1024):
         VALLE(d_ok, d_ok // 64, 2, max_batch=4)
         VALLF(d_ok, d_ok // 64, 2, max_batch=4)
+
+
+# ---- the batch-1 KV cache tap ("ar_kv") --------------------------------------------------------------------------------------------
+def test_ar_kv_tap_size_without_gpu(lib):
+    """vx_read_buffer's "ar_kv" ([layer][K|V][head][max_text + max_audio][head_dim], fp32 on fp32 engines, else bf16) spans exactly
+    the cache: vx_buffer_bytes gives the size its range check uses, and Engine.read_ar_kv asks for exactly that many bytes.  Names
+    without a configuration-sized tap, and a bad struct, are refused before any HIP call."""
+    import ctypes as C
+    from valle_amd.config import ModelConfig
+    from valle_amd.engine import VX_PREC_BF16, VX_PREC_F32, VX_PREC_FP8_NAR, Engine, VxConfig
+
+    c = VxConfig()
+    c.struct_size = C.sizeof(VxConfig)
+    c.d_model, c.nhead, c.num_layers, c.max_text, c.max_audio = 512, 8, 3, 40, 1000
+    n = C.c_int64()
+    for prec, esz in ((VX_PREC_F32, 4), (VX_PREC_BF16, 2), (VX_PREC_FP8_NAR, 2)):
+        c.precision = prec
+        assert lib.vx_buffer_bytes(C.byref(c), b"ar_kv", C.byref(n)) == 0, lib.vx_last_error()
+        assert n.value == 3 * 2 * 8 * 1040 * 64 * esz
+    for bad in (b"ar_kv_", b"batch_kv", b"ar_logits"):
+        assert lib.vx_buffer_bytes(C.byref(c), bad, C.byref(n)) == 1
+        assert bad in lib.vx_last_error()
+    c.struct_size = 0
+    assert lib.vx_buffer_bytes(C.byref(c), b"ar_kv", C.byref(n)) == 1
+    assert b"struct_size" in lib.vx_last_error()
+
+    class Tap:  # records what the reader asks vx_read_buffer for
+        def vx_read_buffer(self, h, name, dst, off, nbytes):
+            self.call = (name, off, nbytes)
+            return 0
+
+    for precision, dtype, prec in (("fp32", torch.float32, VX_PREC_F32), ("bf16", torch.bfloat16, VX_PREC_BF16)):
+        e = Engine.__new__(Engine)
+        e.lib, e.h, e.precision, e.max_text, e.max_audio = Tap(), None, precision, 40, 1000
+        e.cfg = ModelConfig(decoder_dim=512, nhead=8, num_decoder_layers=3)
+        kv = e.read_ar_kv()
+        assert kv.shape == (3, 2, 8, 1040, 64) and kv.dtype == dtype
+        c.struct_size, c.precision = C.sizeof(VxConfig), prec
+        assert lib.vx_buffer_bytes(C.byref(c), b"ar_kv", C.byref(n)) == 0
+        assert e.lib.call == (b"ar_kv", 0, n.value)

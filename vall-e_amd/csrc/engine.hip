@@ -186,6 +186,7 @@ struct vx_engine {
   bool bcap[BMAX] = {};
   double t_bdecode = 0, n_blaunch = 0;
   hipGraphExec_t gexec = nullptr;  // the batch-1 step
+  int gexec_nodes = 0;             // kernel launches captured in it (vx_get_timings out[9])
   // per-utterance state
   int S = 0, P = 0, bos = 0;
   bool prefilled = false, decoded = false;
@@ -1704,12 +1705,17 @@ static int decode_bound(vx_engine* e, int slot, const vx_decode_params& p, int S
 }
 
 // Captures enqueue(e->es) into *out on first use; with VX_FLAG_NO_GRAPH *out stays null and the step is enqueued directly.
-template <typename F> static int step_graph(vx_engine* e, hipGraphExec_t* out, F enqueue) {
+template <typename F> static int step_graph(vx_engine* e, hipGraphExec_t* out, F enqueue, int* n_nodes = nullptr) {
   if (*out || (e->cfg.flags & VX_FLAG_NO_GRAPH)) return VX_OK;
   hipGraph_t gr = nullptr;
   HIPC(hipStreamBeginCapture(e->es, hipStreamCaptureModeThreadLocal));
   const int r = enqueue(e->es);
   hipError_t ce = hipStreamEndCapture(e->es, &gr);
+  if (r == VX_OK && ce == hipSuccess && n_nodes) {
+    size_t nn = 0;
+    ce = hipGraphGetNodes(gr, nullptr, &nn);
+    *n_nodes = (int)nn;
+  }
   if (r == VX_OK && ce == hipSuccess) ce = hipGraphInstantiate(out, gr, nullptr, nullptr, 0);
   if (gr) (void)hipGraphDestroy(gr);
   VXC(r);
@@ -1798,7 +1804,7 @@ extern "C" int vx_ar_decode(vx_engine* e, const vx_decode_params* p, void* strea
   HIPC(hipMemcpyAsync(e->d_st, &st, sizeof st, hipMemcpyHostToDevice, e->es));
 
   auto step = [e](hipStream_t s) { return enqueue_ar_step(e, s); };
-  VXC(step_graph(e, &e->gexec, step));
+  VXC(step_graph(e, &e->gexec, step, &e->gexec_nodes));
   auto stop_rule = [&](const ArState* hs, long long at) -> int {
     if (hs->done) return POLL_STOP;
     return at < bound ? POLL_MORE : fail(VX_ERR_STATE, "decode did not terminate within %lld steps", bound);
@@ -2382,9 +2388,25 @@ extern "C" int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* te
 
 extern "C" int vx_get_timings(vx_engine* e, double* out, int32_t n) {
   if (!e || !out) return fail(VX_ERR_ARG, "null argument");
-  const double v[9] = {e->t_prefill, e->t_decode, e->t_nar, (double)e->n_pass, e->n_launch, e->t_bdecode, e->n_blaunch,
-                       e->t_gemm, e->gemm_flops_done};
-  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
+  const double v[10] = {e->t_prefill, e->t_decode, e->t_nar, (double)e->n_pass, e->n_launch, e->t_bdecode, e->n_blaunch,
+                        e->t_gemm, e->gemm_flops_done, (double)e->gexec_nodes};
+  for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
+  return VX_OK;
+}
+
+// Bytes of the taps whose size follows from the configuration alone (vx_buffer_bytes; vx_read_buffer's range check of the same)
+static int64_t config_buffer_bytes(const vx_config& c, const std::string& n) {
+  const int64_t esz = c.precision == VX_PREC_F32 ? 4 : 2;
+  if (n == "ar_kv") return (int64_t)c.num_layers * 2 * c.d_model * ((int64_t)c.max_text + c.max_audio) * esz;
+  return -1;
+}
+
+extern "C" int vx_buffer_bytes(const vx_config* cfg, const char* name, int64_t* bytes) {
+  if (!cfg || !name || !bytes) return fail(VX_ERR_ARG, "null argument");
+  if (cfg->struct_size != (int32_t)sizeof(vx_config)) return fail(VX_ERR_ARG, "vx_config.struct_size mismatch");
+  const int64_t b = config_buffer_bytes(*cfg, name);
+  if (b < 0) return fail(VX_ERR_ARG, "no configuration-sized buffer '%s'", name);
+  *bytes = b;
   return VX_OK;
 }
 
@@ -2413,6 +2435,7 @@ extern "C" int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t
     src = e->kv8 ? (const char*)e->bkv8 : (const char*)e->bkv;
     size = (int64_t)e->bmax * e->bkv_slot * (e->kv8 ? 1 : 2);
   }
+  else if (n == "ar_kv") { src = (const char*)e->kv; size = config_buffer_bytes(e->cfg, n); }
   else if (n == "batch_kv_scale" && e->kv8) { src = (const char*)e->bkv8s; size = (int64_t)e->bmax * e->bkv_slot / 16; }
   else return fail(VX_ERR_ARG, "unknown buffer '%s'", name);
   if (off < 0 || nbytes < 0 || off + nbytes > size) return fail(VX_ERR_ARG, "read of '%s' out of range (%lld+%lld > %lld)", name, (long long)off, (long long)nbytes, (long long)size);

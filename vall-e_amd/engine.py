@@ -74,6 +74,7 @@ _SIGS = {
     "vx_nar_batch_ex": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.c_void_p]),
     "vx_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
     "vx_read_buffer": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "vx_buffer_bytes": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     "vx_op_layernorm": (C.c_int, [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p]),
     "vx_op_gemv": (C.c_int, [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "vx_op_gemm": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]),
@@ -392,15 +393,24 @@ class Engine:
         return outs
 
     def timings(self):
-        buf = (C.c_double * 9)()
-        _check(self.lib.vx_get_timings(self.h, buf, 9))
+        buf = (C.c_double * 10)()
+        _check(self.lib.vx_get_timings(self.h, buf, 10))
         return dict(prefill_ms=buf[0], decode_ms=buf[1], nar_ms=buf[2], n_pass=int(buf[3]), launches=int(buf[4]),
-                    batch_decode_ms=buf[5], batch_launches=int(buf[6]), nar_gemm_ms=buf[7], nar_gemm_flops=buf[8])
+                    batch_decode_ms=buf[5], batch_launches=int(buf[6]), nar_gemm_ms=buf[7], nar_gemm_flops=buf[8],
+                    step_kernels=int(buf[9]))
 
     def read(self, name: str, shape, dtype=torch.float32, offset_bytes: int = 0) -> torch.Tensor:
         out = torch.empty(shape, dtype=dtype)
         _check(self.lib.vx_read_buffer(self.h, name.encode(), _ptr(out), offset_bytes, out.numel() * out.element_size()))
         return out
+
+    def read_ar_kv(self) -> torch.Tensor:
+        """The batch-1 KV cache as (L, 2, H, max_text + max_audio, head_dim): K and V of every layer, fp32 on fp32 engines,
+        else bfloat16 (the values the decode attention reads)."""
+        L, H = self.cfg.num_decoder_layers, self.cfg.nhead
+        hd = self.cfg.decoder_dim // H
+        dtype = torch.float32 if self.precision in ("fp32", "f32") else torch.bfloat16
+        return self.read("ar_kv", (L, 2, H, self.max_text + self.max_audio, hd), dtype)
 
 
 # ---- kernel-level ops (parity tests call the HIP kernels through the same C ABI) -------------------
