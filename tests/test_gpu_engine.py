@@ -648,6 +648,8 @@ def test_vallf_fp32_engine_reproduces_reference_codes(name):
     assert codes.shape == g.codes.shape
     assert torch.equal(codes, g.codes)
     e = m.engine()
+    c = g.cfg  # the step's shape: sampler, 8 launches per layer (the 5 of a VALL-E layer + the cross-attention block), head
+    assert e.timings()["step_kernels"] == 8 * c.num_decoder_layers + 2 + (3 if c.add_prenet else 0)
     for step, ref in zip(g.ar_probe_steps, g.ar_probe_logits):
         got = e.read("ar_logits", (1025,), offset_bytes=step * 1025 * 4)
         assert (got - ref).abs().max() <= 2e-4, step

@@ -655,6 +655,18 @@ static float* ada_vec(vx_engine* e, int stage, int site) {
   return e->ada + ((size_t)stage * sites + site) * 2 * e->cfg.nar_d_model;
 }
 
+// The norm sites of a stack, n = npl * layer + k with k indexing the layer's norms in block order ({n1, n2}; VALL-F {n1, n2, n3}),
+// numbered as the AdaLN sites.  Block k of layer li (0 self-attention, [1 cross-attention,] npl - 1 feed-forward) is fronted by
+// front_site(li, k): pre-norm, the block's own norm; post-norm, the closing norm of the block before it (x = norm(x + block(x)),
+// transformer.py:303-308), and -1 in front of layer 0 (the embedding goes in as it is).  front_site(L, 0) closes a post-norm stack.
+struct NormW { const float *g, *b; };
+static int front_site(const vx_engine* e, int li, int k) { return e->npl * li + k - ((e->cfg.flags & VX_FLAG_POST_NORM) ? 1 : 0); }
+static NormW norm_at(const vx_engine* e, const std::vector<LayerW>& layers, int n) {
+  const LayerW& l = layers[n / e->npl];
+  const int k = n % e->npl;
+  return k == 0 ? NormW{l.n1_g, l.n1_b} : k == 1 ? NormW{l.n2_g, l.n2_b} : NormW{l.n3_g, l.n3_b};
+}
+
 extern "C" int vx_finalize_weights(vx_engine* e) {
   if (!e) return fail(VX_ERR_ARG, "null engine");
   ON_DEVICE(e->cfg.device);
@@ -921,9 +933,41 @@ static int attn_rows(vx_engine* e, const void* qkv, void* out, int M, int d, int
   return fail(VX_ERR_UNSUPPORTED, "attention: head_dim %d", hd);
 }
 
-// One encoder stack over M rows held in e->X (valle.py:1035-1038 / 1125-1127).  `ada_stage` < 0:
-// plain LayerNorm (AR); otherwise the stage's AdaLN vectors.  `segs`: the row layout; `kv`: where
-// the K/V rows also go (KvDst).
+// ---- VALL-F (valle.py:49-719): the text memory of the TransformerDecoderLayers (modules/transformer.py:409-601) ------------
+// Text memory -> per-layer K / V in the decode-cache layout (nhead, max_text, hd).  `mem` = S rows of the embedded text in
+// operand precision (e->Hn).  The packed cross in_proj is applied whole (the q third of the result is unused): every output
+// element is its own dot product, so rows [d, 3d) equal linear(mem, w[d:], b[d:]) of torch's _in_projection_packed.
+static int memory_kv(vx_engine* e, const std::vector<LayerW>& layers, void* xkv, int S, int d, int H) {
+  const int hd = d / H;
+  const size_t per_layer = (size_t)2 * d * e->cfg.max_text * e->esz;
+  for (size_t li = 0; li < layers.size(); ++li) {
+    VXC(gemm_rows(e, e->Hn, layers[li].cin_w, layers[li].cin_b, e->QKV, S, 3 * d, d, GE_BIAS, false, false));
+    char* kc = (char*)xkv + li * per_layer;
+    char* vc = kc + per_layer / 2;
+    if (e->bf16) kv_scatter_kernel<bf16><<<S, 256, 0, e->es>>>((const bf16*)e->QKV, (bf16*)kc, (bf16*)vc, S, d, hd, e->cfg.max_text);
+    else kv_scatter_kernel<float><<<S, 256, 0, e->es>>>((const float*)e->QKV, (float*)kc, (float*)vc, S, d, hd, e->cfg.max_text);
+  }
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+static int cross_attn_rows(vx_engine* e, const void* q, const void* kc, const void* vc, void* out, int M, int d, int H, int Sk) {
+  const int hd = d / H;
+  const float scale = 1.0f / sqrtf((float)hd);
+  dim3 grid((M + 63) / 64, H);
+#define CA(HDV)                                                                                                                  \
+  if (hd == HDV) {                                                                                                               \
+    if (e->bf16) cross_attn_rows_kernel<bf16, HDV><<<grid, 256, 0, e->es>>>((const bf16*)q, d, (const bf16*)kc, (const bf16*)vc, \
+                                                                            e->cfg.max_text, (bf16*)out, d, M, Sk, scale);       \
+    else cross_attn_rows_kernel<float, HDV><<<grid, 256, 0, e->es>>>((const float*)q, d, (const float*)kc, (const float*)vc,     \
+                                                                     e->cfg.max_text, (float*)out, d, M, Sk, scale);             \
+    return VX_OK;                                                                                                                \
+  }
+  CA(64) CA(32) CA(16) CA(8) CA(4)
+#undef CA
+  return fail(VX_ERR_UNSUPPORTED, "cross-attention: head_dim %d", hd);
+}
+
 static int split_for(int K) {  // K slices of the split-K GEMMs: a multiple of the 64-wide K tile each
   for (int sp = 4; sp > 1; sp >>= 1)
     if (K % (64 * sp) == 0) return sp;
@@ -967,18 +1011,28 @@ struct KvDst {
   char* base = nullptr;  // CACHE
   int slot = 0;          // FP8_SLOT
 };
+// The text memory a VALL-F stack cross-attends to: layer li's K / V at kv + li * 2 d max_text elements (memory_kv's layout), `rows`
+// text rows.  kv == nullptr: none (VALL-E).
+struct TextMem { const void* kv = nullptr; int rows = 0; };
 
+// One stack over M rows held in e->X: encoder layers (valle.py:1035-1038 / 1125-1127) or, with a text memory, VALL-F decoder
+// layers (valle.py:626-632 / 682-688, transformer.py:536-558), whose cross-attention block sits between the self-attention and
+// the feed-forward block.  `ada_stage` < 0: plain LayerNorm (AR); otherwise the stage's AdaLN vectors.  `segs`: the row layout;
+// `kv`: where the K/V rows also go (KvDst).
 static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int d, int H, int text_len, int ada_stage,
-                     const RowSegs& segs, KvDst kv) {
-  const bool post = e->cfg.flags & VX_FLAG_POST_NORM;
+                     const RowSegs& segs, KvDst kv, TextMem mem = TextMem()) {
+  const bool post = e->cfg.flags & VX_FLAG_POST_NORM, cross = mem.kv != nullptr;
+  if (cross && segs.n > 0) return fail(VX_ERR_UNSUPPORTED, "cross-attention over segmented rows");
   const int hd = d / H;
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
+  const size_t mem_layer = (size_t)2 * d * e->cfg.max_text * e->esz;
   // The two N = d GEMMs of a layer (out-projection, FFN2) at M ~ 1k rows: 128^2 tiles alone are 72 workgroups, so K is
   // split over 2-4 workgroups per tile, every slice writes an fp32 slab, and the LayerNorm that follows the GEMM anyway
   // adds bias + slabs to x in a fixed order.  Larger M (batched rows) has enough tiles and adds in the GEMM epilogue.
-  const bool splitk = use_mfma(e) && M < 4096 && M <= e->slab_rows && d % 128 == 0 && d >= 128 && !mx_on(e, ada_stage, M, d);
+  // Not with a text memory: the VALL-F stack is a parity path, and slabs would change its bf16 summation order.
+  const bool splitk = !cross && use_mfma(e) && M < 4096 && M <= e->slab_rows && d % 128 == 0 && d >= 128 && !mx_on(e, ada_stage, M, d);
   const bool mx = mx_on(e, ada_stage, M, d);
-  const bool tg = time_gemms() && ada_stage >= 0;  // NAR stages only
+  const bool tg = time_gemms() && ada_stage >= 0;  // NAR stages only (the cross-attention block is not timed)
   const size_t sstride = (size_t)M * d;
   // K slices of the out-projection / FFN2 (1 = no slabs, residual add in the GEMM epilogue): the largest of 4 / 2 / 1 that keeps
   // (128^2 tiles) x slices within one round of the chip's CUs - at 1025 rows 72 tiles x 4 slices were 288 workgroups, i.e. two
@@ -991,30 +1045,36 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
     return 1;
   };
   const int sp_d = fit(d), sp_ff = fit(4 * d);
-  Fold pend;  // FFN2 slabs of the previous layer, folded by the next norm (pre-norm) or by the trailing fold pass
-  for (size_t li = 0; li < layers.size(); ++li) {
-    const LayerW& l = layers[li];
-    const float *aw1 = nullptr, *ab1 = nullptr, *aw2 = nullptr, *ab2 = nullptr;
-    if (ada_stage >= 0) {
-      aw1 = ada_vec(e, ada_stage, 2 * (int)li); ab1 = aw1 + d;
-      aw2 = ada_vec(e, ada_stage, 2 * (int)li + 1); ab2 = aw2 + d;
+  Fold pend;  // split-K slabs of the GEMM that closed the previous block, folded by the next norm (or the trailing fold pass)
+  // The norm in front of block k of layer li (front_site) into Hn, folding `pend`; post-norm also writes x = norm(x).  Post-norm
+  // layer 0 casts x as it is.  MXFP8 (pre-norm, no slabs): the LayerNorm quantises its own row into Hn8 / SHn.
+  auto norm_in = [&](int li, int k) -> int {
+    const int n = front_site(e, li, k);
+    if (n < 0) return cast_rows(e, e->X, e->Hn, (size_t)M * d);
+    const NormW nw = norm_at(e, layers, n);
+    const float* aw = ada_stage >= 0 ? ada_vec(e, ada_stage, n) : nullptr;
+    const float* ab = aw ? aw + d : nullptr;
+    if (mx) {
+      layernorm_rows_mx_kernel<4><<<(M + 3) / 4, 256, 0, e->es>>>(e->X, nw.g, nw.b, aw, ab, e->Hn8, e->SHn, M, d, e->mx_ld);
+      return VX_OK;
     }
-    // pre-norm (transformer.py:296-302): Hn = norm1(x).  post-norm (303-308): the block reads x itself; Hn already
-    // holds it in operand precision from the previous layer's norm2 (layer 0: cast here)
-    if (mx) {  // MXFP8 QKV: the LayerNorm quantises its own row, the GEMM writes bf16 q/k/v (+ V^T) for the bf16 attention
-      layernorm_rows_mx_kernel<4><<<(M + 3) / 4, 256, 0, e->es>>>(e->X, l.n1_g, l.n1_b, aw1, ab1, e->Hn8, e->SHn, M, d, e->mx_ld);
-      if (tg) gemm_mark(e, 0);
+    const Fold f = pend;
+    pend = Fold();
+    return ln_rows(e, e->X, nw.g, nw.b, aw, ab, e->Hn, M, d, post ? e->X : nullptr, f);
+  };
+  for (int li = 0; li < (int)layers.size(); ++li) {
+    const LayerW& l = layers[li];
+    // self-attention: pre-norm x += sa(norm(x)) (transformer.py:296-302); post-norm x = norm(x + sa(x)) (303-308)
+    VXC(norm_in(li, 0));
+    if (tg) gemm_mark(e, 0);
+    if (mx) {  // MXFP8 QKV: the GEMM writes bf16 q/k/v (+ V^T) for the bf16 attention
       if (mx_gemm_dispatch(e->Hn8, e->SHn, e->mx_ld, l.in_q8, l.in_s8, 3 * d, l.in_b, e->QKV, nullptr, 0, M, 3 * d, d, GE_BIAS,
                            MX_OUT_BF16, e->es, (bf16*)e->VT, 2 * d, e->vt_ld))
         return fail(VX_ERR_UNSUPPORTED, "mx gemm: shape %d x %d x %d", M, 3 * d, d);
-      if (tg) gemm_mark(e, 2.0 * M * 3 * d * d);
     } else {
-    if (!post) { VXC(ln_rows(e, e->X, l.n1_g, l.n1_b, aw1, ab1, e->Hn, M, d, nullptr, pend)); pend = Fold(); }
-    else if (li == 0) VXC(cast_rows(e, e->X, e->Hn, (size_t)M * d));
-    if (tg) gemm_mark(e, 0);
-    VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
-    if (tg) gemm_mark(e, 2.0 * M * 3 * d * d);
+      VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
     }
+    if (tg) gemm_mark(e, 2.0 * M * 3 * d * d);
     const size_t kvl = (size_t)2 * H * e->ctx_max * 64;  // elements per layer of a slot cache
     if (kv.kind == KvDst::SEG_SLOTS) {  // batched prefill: segment z -> slot segs.slot[z]
       if (e->kv8)
@@ -1034,122 +1094,44 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
       else kv_scatter_kernel<float><<<M, 256, 0, e->es>>>((const float*)e->QKV, (float*)kc, (float*)vc, M, d, hd, e->ctx_max);
     }
     VXC(attn_rows(e, e->QKV, e->ATT, M, d, H, text_len, segs));
-    Fold fo;  // out-projection: x += out_proj(attn), folded into the norm that follows when split
+    // out-projection: x += out_proj(attn), folded into the norm that follows when split
     if (tg && !mx) gemm_mark(e, 0);  // (MXFP8 stages: only the fp8 GEMMs are timed; the out-projection stays bf16)
     if (splitk && sp_d > 1) {
       VXC(mfma_gemm_partial((const bf16*)e->ATT, (const bf16*)l.out_w, e->slab, M, d, d, sp_d, e->es));
-      fo.part = e->slab; fo.nsplit = sp_d; fo.stride = sstride; fo.bias = l.out_b;
+      pend.part = e->slab; pend.nsplit = sp_d; pend.stride = sstride; pend.bias = l.out_b;
     } else {
       VXC(gemm_rows(e, e->ATT, l.out_w, l.out_b, e->X, M, d, d, GE_RESID, true));
     }
     if (tg && !mx) gemm_mark(e, 2.0 * M * d * d);
-    if (mx) {  // MXFP8 FFN: LN2 -> fp8, FFN1's epilogue quantises its ReLU output per 32-wide block, FFN2 adds into x
-      layernorm_rows_mx_kernel<4><<<(M + 3) / 4, 256, 0, e->es>>>(e->X, l.n2_g, l.n2_b, aw2, ab2, e->Hn8, e->SHn, M, d, e->mx_ld);
-      if (tg) gemm_mark(e, 0);
+    if (cross) {  // cross-attention over the text: x += mha(norm(x), memory) (transformer.py:540-545, 551-557)
+      VXC(norm_in(li, 1));
+      VXC(gemm_rows(e, e->Hn, l.cin_w, l.cin_b, e->QKV, M, d, d, GE_BIAS, false, false));  // q = rows [0, d) of the packed in_proj
+      const char* xk = (const char*)mem.kv + li * mem_layer;
+      VXC(cross_attn_rows(e, e->QKV, xk, xk + mem_layer / 2, e->ATT, M, d, H, mem.rows));
+      VXC(gemm_rows(e, e->ATT, l.cout_w, l.cout_b, e->X, M, d, d, GE_RESID, true));
+    }
+    // feed-forward: x += ff(norm(x)); post-norm x = norm(x + ff(x))
+    VXC(norm_in(li, e->npl - 1));
+    if (tg) gemm_mark(e, 0);
+    if (mx) {  // MXFP8 FFN: FFN1's epilogue quantises its ReLU output per 32-wide block, FFN2 adds into x
       if (mx_gemm_dispatch(e->Hn8, e->SHn, e->mx_ld, l.w1_q8, l.w1_s8, 4 * d, l.b1, e->FF8, e->SFF, e->mx_ld, M, 4 * d, d, GE_RELU,
                            MX_OUT_MX, e->es) ||
           mx_gemm_dispatch(e->FF8, e->SFF, e->mx_ld, l.w2_q8, l.w2_s8, d, l.b2, e->X, nullptr, 0, M, d, 4 * d, GE_RESID, MX_OUT_F32, e->es))
         return fail(VX_ERR_UNSUPPORTED, "mx gemm: FFN shapes at M=%d d=%d", M, d);
-      if (tg) gemm_mark(e, 2.0 * 2.0 * M * 4 * d * d);
-      continue;
-    }
-    if (!post) VXC(ln_rows(e, e->X, l.n2_g, l.n2_b, aw2, ab2, e->Hn, M, d, nullptr, fo));
-    else VXC(ln_rows(e, e->X, l.n1_g, l.n1_b, aw1, ab1, e->Hn, M, d, e->X, fo));  // x = norm1(x + sa(x))
-    if (tg) gemm_mark(e, 0);
-    VXC(gemm_rows(e, e->Hn, l.w1, l.b1, e->FF, M, 4 * d, d, GE_RELU, false));
-    Fold ff;
-    if (splitk && sp_ff > 1) {
-      VXC(mfma_gemm_partial((const bf16*)e->FF, (const bf16*)l.w2, e->slab, M, d, 4 * d, sp_ff, e->es));
-      ff.part = e->slab; ff.nsplit = sp_ff; ff.stride = sstride; ff.bias = l.b2;
     } else {
-      VXC(gemm_rows(e, e->FF, l.w2, l.b2, e->X, M, d, 4 * d, GE_RESID, true));
+      VXC(gemm_rows(e, e->Hn, l.w1, l.b1, e->FF, M, 4 * d, d, GE_RELU, false));
+      if (splitk && sp_ff > 1) {
+        VXC(mfma_gemm_partial((const bf16*)e->FF, (const bf16*)l.w2, e->slab, M, d, 4 * d, sp_ff, e->es));
+        pend.part = e->slab; pend.nsplit = sp_ff; pend.stride = sstride; pend.bias = l.b2;
+      } else {
+        VXC(gemm_rows(e, e->FF, l.w2, l.b2, e->X, M, d, 4 * d, GE_RESID, true));
+      }
     }
     if (tg) gemm_mark(e, 2.0 * 2.0 * M * 4 * d * d);
-    if (post) VXC(ln_rows(e, e->X, l.n2_g, l.n2_b, aw2, ab2, e->Hn, M, d, e->X, ff));  // x = norm2(x + ff(x))
-    else pend = ff;
   }
-  if (pend.part != nullptr)  // the last layer's FFN2 slabs: x += b2 + slabs (no norm: the caller applies the final one)
+  if (post) VXC(norm_in((int)layers.size(), 0));  // the last block's closing norm
+  else if (pend.part != nullptr)  // the last layer's FFN2 slabs: x += b2 + slabs (no norm: the caller applies the final one)
     VXC(ln_rows(e, e->X, nullptr, nullptr, nullptr, nullptr, nullptr, M, d, nullptr, pend));
-  HIPC(hipGetLastError());
-  return VX_OK;
-}
-
-// ---- VALL-F (valle.py:49-719): stacks of TransformerDecoderLayers (modules/transformer.py:409-601) -------------------------
-// Text memory -> per-layer K / V in the decode-cache layout (nhead, max_text, hd).  `mem` = S rows of the embedded text in
-// operand precision (e->Hn).  The packed cross in_proj is applied whole (the q third of the result is unused): every output
-// element is its own dot product, so rows [d, 3d) equal linear(mem, w[d:], b[d:]) of torch's _in_projection_packed.
-static int memory_kv(vx_engine* e, const std::vector<LayerW>& layers, void* xkv, int S, int d, int H) {
-  const int hd = d / H;
-  const size_t per_layer = (size_t)2 * d * e->cfg.max_text * e->esz;
-  for (size_t li = 0; li < layers.size(); ++li) {
-    VXC(gemm_rows(e, e->Hn, layers[li].cin_w, layers[li].cin_b, e->QKV, S, 3 * d, d, GE_BIAS, false, false));
-    char* kc = (char*)xkv + li * per_layer;
-    char* vc = kc + per_layer / 2;
-    if (e->bf16) kv_scatter_kernel<bf16><<<S, 256, 0, e->es>>>((const bf16*)e->QKV, (bf16*)kc, (bf16*)vc, S, d, hd, e->cfg.max_text);
-    else kv_scatter_kernel<float><<<S, 256, 0, e->es>>>((const float*)e->QKV, (float*)kc, (float*)vc, S, d, hd, e->cfg.max_text);
-  }
-  HIPC(hipGetLastError());
-  return VX_OK;
-}
-
-static int cross_attn_rows(vx_engine* e, const void* q, const void* kc, const void* vc, void* out, int M, int d, int H, int Sk) {
-  const int hd = d / H;
-  const float scale = 1.0f / sqrtf((float)hd);
-  dim3 grid((M + 63) / 64, H);
-#define CA(HDV)                                                                                                                  \
-  if (hd == HDV) {                                                                                                               \
-    if (e->bf16) cross_attn_rows_kernel<bf16, HDV><<<grid, 256, 0, e->es>>>((const bf16*)q, d, (const bf16*)kc, (const bf16*)vc, \
-                                                                            e->cfg.max_text, (bf16*)out, d, M, Sk, scale);       \
-    else cross_attn_rows_kernel<float, HDV><<<grid, 256, 0, e->es>>>((const float*)q, d, (const float*)kc, (const float*)vc,     \
-                                                                     e->cfg.max_text, (float*)out, d, M, Sk, scale);             \
-    return VX_OK;                                                                                                                \
-  }
-  CA(64) CA(32) CA(16) CA(8) CA(4)
-#undef CA
-  return fail(VX_ERR_UNSUPPORTED, "cross-attention: head_dim %d", hd);
-}
-
-// One decoder stack over the M audio rows held in e->X (valle.py:626-632 AR with text_len = 0: causal; valle.py:682-688 NAR
-// with text_len < 0: no mask).  Memory K / V of layer li at xkv + li * per_layer, Sk text rows.  Self-attention K / V go to the
-// decode cache at kv_dst ([L][2][H][ctx_max][hd]: e->kv or a slot's cache; null: not kept).  Plain epilogue adds (no
-// split-K slabs): this variant is built for parity, not tuned.
-static int run_stack_f(vx_engine* e, const std::vector<LayerW>& layers, int M, int d, int H, int text_len, int ada_stage,
-                       void* kv_dst, const void* xkv, int Sk) {
-  const bool post = e->cfg.flags & VX_FLAG_POST_NORM;
-  const int hd = d / H;
-  const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
-  const size_t per_layer = (size_t)2 * d * e->cfg.max_text * e->esz;
-  for (size_t li = 0; li < layers.size(); ++li) {
-    const LayerW& l = layers[li];
-    const float *aw[3] = {nullptr, nullptr, nullptr}, *ab[3] = {nullptr, nullptr, nullptr};
-    if (ada_stage >= 0)
-      for (int k = 0; k < 3; ++k) { aw[k] = ada_vec(e, ada_stage, 3 * (int)li + k); ab[k] = aw[k] + d; }
-    // self-attention: pre-norm x += sa(norm1(x)) (transformer.py:536-539); post-norm x = norm1(x + sa(x)) (547-550)
-    if (!post) VXC(ln_rows(e, e->X, l.n1_g, l.n1_b, aw[0], ab[0], e->Hn, M, d));
-    else if (li == 0) VXC(cast_rows(e, e->X, e->Hn, (size_t)M * d));
-    VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
-    if (kv_dst) {
-      char* kc = (char*)kv_dst + li * kv_layer;
-      char* vc = kc + kv_layer / 2;
-      if (e->bf16) kv_scatter_kernel<bf16><<<M, 256, 0, e->es>>>((const bf16*)e->QKV, (bf16*)kc, (bf16*)vc, M, d, hd, e->ctx_max);
-      else kv_scatter_kernel<float><<<M, 256, 0, e->es>>>((const float*)e->QKV, (float*)kc, (float*)vc, M, d, hd, e->ctx_max);
-    }
-    VXC(attn_rows(e, e->QKV, e->ATT, M, d, H, text_len, RowSegs()));
-    VXC(gemm_rows(e, e->ATT, l.out_w, l.out_b, e->X, M, d, d, GE_RESID, true));
-    // cross-attention over the text: x += mha(norm2(x), memory) (540-545); post-norm x = norm2(x + mha(x, memory)) (551-557)
-    if (!post) VXC(ln_rows(e, e->X, l.n2_g, l.n2_b, aw[1], ab[1], e->Hn, M, d));
-    else VXC(ln_rows(e, e->X, l.n1_g, l.n1_b, aw[0], ab[0], e->Hn, M, d, e->X));
-    VXC(gemm_rows(e, e->Hn, l.cin_w, l.cin_b, e->QKV, M, d, d, GE_BIAS, false, false));  // q = rows [0, d) of the packed in_proj
-    const char* xk = (const char*)xkv + li * per_layer;
-    VXC(cross_attn_rows(e, e->QKV, xk, xk + per_layer / 2, e->ATT, M, d, H, Sk));
-    VXC(gemm_rows(e, e->ATT, l.cout_w, l.cout_b, e->X, M, d, d, GE_RESID, true));
-    // feed-forward: x += ff(norm3(x)) (546); post-norm x = norm3(x + ff(x)) (558)
-    if (!post) VXC(ln_rows(e, e->X, l.n3_g, l.n3_b, aw[2], ab[2], e->Hn, M, d));
-    else VXC(ln_rows(e, e->X, l.n2_g, l.n2_b, aw[1], ab[1], e->Hn, M, d, e->X));
-    VXC(gemm_rows(e, e->Hn, l.w1, l.b1, e->FF, M, 4 * d, d, GE_RELU, false));
-    VXC(gemm_rows(e, e->FF, l.w2, l.b2, e->X, M, d, 4 * d, GE_RESID, true));
-    if (post) VXC(ln_rows(e, e->X, l.n3_g, l.n3_b, aw[2], ab[2], e->Hn, M, d, e->X));
-  }
   HIPC(hipGetLastError());
   return VX_OK;
 }
@@ -1181,9 +1163,10 @@ static int enqueue_head(vx_engine* e, hipStream_t s, const float* x = nullptr, f
   a.W = W<void>(e, "ar_predict_layer.weight");
   a.bias = nullptr;
   a.x = x ? x : e->ar_x;
-  // post-norm: the last layer's closing norm (norm2 of an encoder layer, norm3 of a VALL-F decoder layer)
-  a.gamma = post ? (e->vallf ? e->ar_l.back().n3_g : e->ar_l.back().n2_g) : W<float>(e, "ar_decoder.norm.weight");
-  a.beta = post ? (e->vallf ? e->ar_l.back().n3_b : e->ar_l.back().n2_b) : W<float>(e, "ar_decoder.norm.bias");
+  // post-norm: the stack's closing norm (norm2 of an encoder layer, norm3 of a VALL-F decoder layer)
+  const NormW fin = post ? norm_at(e, e->ar_l, front_site(e, c.num_layers, 0))
+                         : NormW{W<float>(e, "ar_decoder.norm.weight"), W<float>(e, "ar_decoder.norm.bias")};
+  a.gamma = fin.g; a.beta = fin.b;
   a.y = logits ? logits : e->ar_logits;
   a.N = AR_VOCAB; a.K = c.d_model;
   a.pro = (post && prefilled) ? PRO_COPY : PRO_LN; a.epi = EPI_LOGITS;
@@ -1253,11 +1236,9 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
   float* x_dst = slot < 0 ? e->ar_x : e->bx + (size_t)slot * d;
   float* lg_dst = slot < 0 ? e->ar_logits : e->blogits + (size_t)slot * LOGITS_CUR;
   ArState* st_dst = slot < 0 ? e->d_st : e->bst + slot;
-  if (vf) {  // kv is a CACHE destination: VX_FLAG_KV_FP8 is refused for VALL-F
-    if (slot < 0) e->mem_len = S;
-    VXC(run_stack_f(e, e->ar_l, M, d, c.nhead, 0, -1, kv.base, xkv, S));
-  }
-  else VXC(run_stack(e, e->ar_l, M, d, c.nhead, S, -1, RowSegs(), kv));
+  if (vf && slot < 0) e->mem_len = S;
+  // VALL-F: causal over the audio rows (text_len 0), kv a CACHE destination (VX_FLAG_KV_FP8 is refused for VALL-F)
+  VXC(run_stack(e, e->ar_l, M, d, c.nhead, vf ? 0 : S, -1, RowSegs(), kv, vf ? TextMem{xkv, S} : TextMem()));
   HIPC(hipMemcpyAsync(x_dst, e->X + (size_t)(M - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
   ArState& st = slot < 0 ? e->h_st[0] : e->h_bst[slot];
   seed_state(st, S, P, bos, M - 1, vf ? 0 : S, slot < 0 && (c.flags & VX_FLAG_TRACE_LOGITS));
@@ -1398,10 +1379,6 @@ extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* cons
   return batch_prefill_impl(e, n, slots, text, S, prompt_cb0, P, stream);
 }
 
-// One decode step: sample from the newest logits, append, run the 12-layer stack on the new
-// token, produce the next logits.  Every kernel reads its position from e->d_st, so the same
-// launch sequence (captured once as a hipGraph) serves every pass.
-static int enqueue_ar_step_f(vx_engine* e, hipStream_t s);
 // The layers and the head of the XCD-sharded step (ar_tp.hpp); the sampling launch in front of them is the caller's (it writes
 // the fp32 embedding into ar_x and zeroes accumulator 1).  Launch n = 2 li (attention half), 2 li + 1 (feed-forward half), 2 L
 // (head) normalises accumulator n % 3, adds into (n + 1) % 3 and zeroes (n + 2) % 3; layer 0's attention half reads ar_x instead.
@@ -1458,35 +1435,70 @@ static SampleArgs step_sample_args(vx_engine* e) {
   sa.zero_acc = e->tp ? e->tp_xacc + TP_D : nullptr;  // accumulator 1: layer 0's attention half adds into it
   return sa;
 }
+// y_emb = ar_audio_prenet(E[tok]); x = y_emb + alpha * pe (valle.py:1013-1015): three fp32 GEMVs, ar_e -> ar_x
+static int enqueue_audio_prenet(vx_engine* e, hipStream_t s) {
+  const int d = e->cfg.d_model;
+  GemvArgs p0{}, p1{}, p2{};
+  p0.st = p1.st = p2.st = e->d_st;
+  p0.kid = p1.kid = p2.kid = -1;
+  p0.W = W<void>(e, "ar_audio_prenet.0.weight"); p0.bias = W<float>(e, "ar_audio_prenet.0.bias");
+  p0.x = e->ar_e; p0.y = e->ar_h1; p0.N = PRENET_H; p0.K = d; p0.pro = PRO_COPY; p0.epi = EPI_RELU;
+  p1.W = W<void>(e, "ar_audio_prenet.3.weight"); p1.bias = W<float>(e, "ar_audio_prenet.3.bias");
+  p1.x = e->ar_h1; p1.y = e->ar_h2; p1.N = PRENET_H; p1.K = PRENET_H; p1.pro = PRO_COPY; p1.epi = EPI_RELU;
+  p2.W = W<void>(e, "ar_audio_prenet.6.weight"); p2.bias = W<float>(e, "ar_audio_prenet.6.bias");
+  p2.x = e->ar_h2; p2.y = e->ar_x; p2.N = d; p2.K = PRENET_H; p2.pro = PRO_COPY; p2.epi = EPI_POS;
+  p2.pe = e->pe_ar; p2.pos_alpha = W<float>(e, "ar_audio_position.alpha");
+  VXC(launch_gemv(false, p0, e->num_cu, s));
+  VXC(launch_gemv(false, p1, e->num_cu, s));
+  return launch_gemv(false, p2, e->num_cu, s);
+}
+
+// Split-KV attention of the step's query ar_q over one cache, (nhead, ctx_max, hd) per K / V, into ar_part: keys 0 .. ArState.row
+// (causal), or with fixed_ctx the first ArState.S (the text memory).  kid >= 0: stamped (probe builds: one extra workgroup).
+template <typename T>
+static int launch_attn_decode_t(vx_engine* e, hipStream_t s, const T* kc, const T* vc, int ctx_max, int fixed_ctx, int kid) {
+  const int H = e->cfg.nhead, hd = e->cfg.d_model / H;
+  const float scale = 1.0f / sqrtf((float)hd);
+  const int grid = H * ATT_NSPLIT + (kid >= 0 ? VX_KSTAMP_EXTRA : 0);
+  const float* q = e->ar_q;
+  float* part = e->ar_part;
+  switch (hd) {
+    case 64: attn_decode_kernel<T, 64><<<grid, 256, 0, s>>>(q, kc, vc, part, e->d_st, ctx_max, scale, kid, fixed_ctx); break;
+    case 32: attn_decode_small_kernel<T, 32><<<grid, 256, 0, s>>>(q, kc, vc, part, e->d_st, ctx_max, scale, kid, fixed_ctx); break;
+    case 16: attn_decode_small_kernel<T, 16><<<grid, 256, 0, s>>>(q, kc, vc, part, e->d_st, ctx_max, scale, kid, fixed_ctx); break;
+    case 8: attn_decode_small_kernel<T, 8><<<grid, 256, 0, s>>>(q, kc, vc, part, e->d_st, ctx_max, scale, kid, fixed_ctx); break;
+    case 4: attn_decode_small_kernel<T, 4><<<grid, 256, 0, s>>>(q, kc, vc, part, e->d_st, ctx_max, scale, kid, fixed_ctx); break;
+    default: return fail(VX_ERR_UNSUPPORTED, "decode attention: head_dim %d", hd);
+  }
+  return VX_OK;
+}
+static int launch_attn_decode(vx_engine* e, hipStream_t s, const void* kc, const void* vc, int ctx_max, int fixed_ctx, int kid) {
+  if (e->bf16) return launch_attn_decode_t(e, s, (const bf16*)kc, (const bf16*)vc, ctx_max, fixed_ctx, kid);
+  return launch_attn_decode_t(e, s, (const float*)kc, (const float*)vc, ctx_max, fixed_ctx, kid);
+}
+
+// One decode step: sample from the newest logits, append, run the stack on the new token, produce the next logits.  Every kernel
+// reads its position from e->d_st, so the same launch sequence (captured once as a hipGraph) serves every pass.  Per layer: QKV
+// GEMV, attention over the cached audio rows, out-projection; VALL-F (valle.py:613-647, transformer.py:536-560) then its
+// cross-attention block: query GEMV (rows [0, d) of the packed multihead_attn in_proj), single-query attention over the layer's
+// text memory, its out-projection; then FFN1, FFN2.  Every norm runs in the prologue of the GEMV that consumes it (front_site).
+// Post-norm (transformer.py:303-308): ar_x holds the raw sum x + block(x) of the previous block, and the prologue that normalises
+// it also leaves the normalised vector in ar_xn as the base of the next residual add.
 static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
-  if (e->vallf) return enqueue_ar_step_f(e, s);
   const vx_config& c = e->cfg;
   const int d = c.d_model, H = c.nhead, hd = d / H;
-  const bool post = c.flags & VX_FLAG_POST_NORM;
-  const SampleArgs sa = step_sample_args(e);
-  const bool prenet = c.flags & VX_FLAG_PRENET;
-  sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(sa);
+  sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(step_sample_args(e));
   if (e->tp) return enqueue_ar_step_tp(e, s);
-  if (prenet) {  // y_emb = ar_audio_prenet(E[tok]); x = y_emb + alpha * pe (valle.py:1013-1015): three fp32 GEMVs
-    GemvArgs p0{}, p1{}, p2{};
-    p0.st = p1.st = p2.st = e->d_st;
-    p0.kid = p1.kid = p2.kid = -1;
-    p0.W = W<void>(e, "ar_audio_prenet.0.weight"); p0.bias = W<float>(e, "ar_audio_prenet.0.bias");
-    p0.x = e->ar_e; p0.y = e->ar_h1; p0.N = PRENET_H; p0.K = d; p0.pro = PRO_COPY; p0.epi = EPI_RELU;
-    p1.W = W<void>(e, "ar_audio_prenet.3.weight"); p1.bias = W<float>(e, "ar_audio_prenet.3.bias");
-    p1.x = e->ar_h1; p1.y = e->ar_h2; p1.N = PRENET_H; p1.K = PRENET_H; p1.pro = PRO_COPY; p1.epi = EPI_RELU;
-    p2.W = W<void>(e, "ar_audio_prenet.6.weight"); p2.bias = W<float>(e, "ar_audio_prenet.6.bias");
-    p2.x = e->ar_h2; p2.y = e->ar_x; p2.N = d; p2.K = PRENET_H; p2.pro = PRO_COPY; p2.epi = EPI_POS;
-    p2.pe = e->pe_ar; p2.pos_alpha = W<float>(e, "ar_audio_position.alpha");
-    VXC(launch_gemv(false, p0, e->num_cu, s));
-    VXC(launch_gemv(false, p1, e->num_cu, s));
-    VXC(launch_gemv(false, p2, e->num_cu, s));
-  }
+  if (c.flags & VX_FLAG_PRENET) VXC(enqueue_audio_prenet(e, s));
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
-  const float scale = 1.0f / sqrtf((float)hd);
+  const size_t mem_layer = (size_t)2 * d * c.max_text * e->esz;
+  // Stamp ids (probe builds, step_sample_args): the 64-entry ring holds 5 launches per layer and 61 for the head, so a VALL-F
+  // layer's 8 launches do not fit and stay unstamped (-1: no extra workgroup).
+  auto kid = [&](int li, int j) { return e->vallf ? -1 : 1 + 5 * li + j; };
   // L2 / Infinity-Cache warm-up (GemvArgs.pf): GEMV i of the step also requests the weights of GEMV i + dist, in step order
-  // [QKV_0, out_0, FFN1_0, FFN2_0, QKV_1, ..., FFN2_{L-1}, head] and wrapping into the next token's step.
-  static const int pf_dist = getenv("VX_AR_PREFETCH") ? atoi(getenv("VX_AR_PREFETCH")) : 2;
+  // [QKV_0, out_0, FFN1_0, FFN2_0, QKV_1, ..., FFN2_{L-1}, head] and wrapping into the next token's step.  VALL-E only.
+  static const int pf_env = getenv("VX_AR_PREFETCH") ? atoi(getenv("VX_AR_PREFETCH")) : 2;
+  const int pf_dist = e->vallf ? 0 : pf_env;
   struct PfW { const void* W; int N, K; };
   std::vector<PfW> seq;
   for (int li = 0; li < c.num_layers; ++li) {
@@ -1499,171 +1511,71 @@ static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
     const PfW& n = seq[(idx + pf_dist) % seq.size()];
     gemv_prefetch(a, n.W, n.N, n.K, e->bf16, e->num_cu);
   };
+  // The norm in front of block k of layer li into a's prologue (none in front of post-norm layer 0).  Returns the residual base
+  // of the block's closing GEMV: post-norm the normalised vector in ar_xn, else null (ar_x itself).
+  auto norm_in = [&](GemvArgs& a, int li, int k) -> const float* {
+    const int n = front_site(e, li, k);
+    if (n < 0) { a.pro = PRO_COPY; return nullptr; }
+    const NormW nw = norm_at(e, e->ar_l, n);
+    a.pro = PRO_LN; a.gamma = nw.g; a.beta = nw.b;
+    if (!(c.flags & VX_FLAG_POST_NORM)) return nullptr;
+    a.xnorm_out = e->ar_xn;
+    return e->ar_xn;
+  };
   for (int li = 0; li < c.num_layers; ++li) {
     const LayerW& l = e->ar_l[li];
     char* kc = (char*)e->kv + (size_t)li * kv_layer;
     char* vc = kc + kv_layer / 2;
+    // qkv = in_proj(norm(x)); k,v appended to the cache (transformer.py:297-301); x += out_proj(attn)
     GemvArgs a{};
     a.st = e->d_st; a.d = d; a.hd = hd; a.ctx_max = e->ctx_max; a.nhead = H;
-    // qkv = in_proj(LN1(x)); k,v appended to the cache (transformer.py:297-301)
-    a.W = l.in_w; a.bias = l.in_b; a.x = e->ar_x; a.gamma = l.n1_g; a.beta = l.n1_b;
-    a.N = 3 * d; a.K = d; a.pro = PRO_LN; a.epi = EPI_QKV; a.q = e->ar_q; a.kcache = kc; a.vcache = vc;
-    // post-norm (transformer.py:303-308): ar_x holds the raw sum x + block(x) of the previous sub-layer and the norm that
-    // follows it is fused into the NEXT kernel's prologue, which also leaves the normalised vector in ar_xn as the
-    // base of the next residual add.  Layer 0 reads the fresh embedding as is.
-    const float* res = nullptr;  // residual base of this layer's attention block (null: ar_x itself)
-    if (post) {
-      if (li == 0) { a.pro = PRO_COPY; }
-      else { a.gamma = e->ar_l[li - 1].n2_g; a.beta = e->ar_l[li - 1].n2_b; a.xnorm_out = e->ar_xn; res = e->ar_xn; }
-    }
+    a.W = l.in_w; a.bias = l.in_b; a.x = e->ar_x;
+    a.N = 3 * d; a.K = d; a.epi = EPI_QKV; a.q = e->ar_q; a.kcache = kc; a.vcache = vc;
+    const float* res = norm_in(a, li, 0);
     warm(a, 4 * li);
-    a.kid = 1 + 5 * li;
+    a.kid = kid(li, 0);
     VXC(launch_gemv(e->bf16, a, e->num_cu, s));
-#define AD(HDV)                                                                                                                                              \
-  if (hd == HDV) {                                                                                                                                           \
-    if (e->bf16) attn_decode_small_kernel<bf16, HDV><<<H * ATT_NSPLIT + VX_KSTAMP_EXTRA, 256, 0, s>>>(e->ar_q, (const bf16*)kc, (const bf16*)vc, e->ar_part, e->d_st, e->ctx_max, scale, 2 + 5 * li); \
-    else attn_decode_small_kernel<float, HDV><<<H * ATT_NSPLIT + VX_KSTAMP_EXTRA, 256, 0, s>>>(e->ar_q, (const float*)kc, (const float*)vc, e->ar_part, e->d_st, e->ctx_max, scale, 2 + 5 * li);      \
-  }
-    if (hd == 64) {
-      if (e->bf16) attn_decode_kernel<bf16, 64><<<H * ATT_NSPLIT + VX_KSTAMP_EXTRA, 256, 0, s>>>(e->ar_q, (const bf16*)kc, (const bf16*)vc, e->ar_part, e->d_st, e->ctx_max, scale, 2 + 5 * li);
-      else attn_decode_kernel<float, 64><<<H * ATT_NSPLIT + VX_KSTAMP_EXTRA, 256, 0, s>>>(e->ar_q, (const float*)kc, (const float*)vc, e->ar_part, e->d_st, e->ctx_max, scale, 2 + 5 * li);
-    }
-    AD(32) AD(16) AD(8) AD(4)
-#undef AD
-    // x += out_proj(attn)
+    VXC(launch_attn_decode(e, s, kc, vc, e->ctx_max, 0, kid(li, 1)));
     GemvArgs o{};
     o.st = e->d_st; o.hd = hd; o.nhead = H;
     o.W = l.out_w; o.bias = l.out_b; o.part = e->ar_part; o.y = e->ar_x; o.N = d; o.K = d; o.pro = PRO_ATTN; o.epi = EPI_RESID;
     o.res = res;
     warm(o, 4 * li + 1);
-    o.kid = 3 + 5 * li;
+    o.kid = kid(li, 2);
     VXC(launch_gemv(e->bf16, o, e->num_cu, s));
-    // f = relu(linear1(LN2(x)))
+    if (e->vallf) {  // q = in_proj[0:d](norm(x)); x += out_proj(attention over the text memory, ArState.S rows)
+      GemvArgs q{};
+      q.st = e->d_st; q.kid = -1;
+      q.W = l.cin_w; q.bias = l.cin_b; q.x = e->ar_x; q.y = e->ar_q; q.N = d; q.K = d; q.epi = EPI_BIAS;
+      const float* cres = norm_in(q, li, 1);
+      VXC(launch_gemv(e->bf16, q, e->num_cu, s));
+      const char* xk = (const char*)e->xkv_ar + (size_t)li * mem_layer;
+      VXC(launch_attn_decode(e, s, xk, xk + mem_layer / 2, c.max_text, 1, -1));
+      GemvArgs co{};
+      co.st = e->d_st; co.hd = hd; co.nhead = H; co.kid = -1;
+      co.W = l.cout_w; co.bias = l.cout_b; co.part = e->ar_part; co.y = e->ar_x; co.N = d; co.K = d; co.pro = PRO_ATTN; co.epi = EPI_RESID;
+      co.res = cres;
+      VXC(launch_gemv(e->bf16, co, e->num_cu, s));
+    }
+    // f = relu(linear1(norm(x))); x += linear2(f)
     GemvArgs f{};
     f.st = e->d_st;
-    f.W = l.w1; f.bias = l.b1; f.x = e->ar_x; f.gamma = l.n2_g; f.beta = l.n2_b; f.y = e->ar_f;
-    f.N = 4 * d; f.K = d; f.pro = PRO_LN; f.epi = EPI_RELU;
-    if (post) { f.gamma = l.n1_g; f.beta = l.n1_b; f.xnorm_out = e->ar_xn; }  // x = norm1(x + sa(x)), kept in ar_xn
+    f.W = l.w1; f.bias = l.b1; f.x = e->ar_x; f.y = e->ar_f; f.N = 4 * d; f.K = d; f.epi = EPI_RELU;
+    const float* fres = norm_in(f, li, e->npl - 1);
     warm(f, 4 * li + 2);
-    f.kid = 4 + 5 * li;
+    f.kid = kid(li, 3);
     VXC(launch_gemv(e->bf16, f, e->num_cu, s));
-    // x += linear2(f)
     GemvArgs g{};
     g.st = e->d_st;
     g.W = l.w2; g.bias = l.b2; g.x = e->ar_f; g.y = e->ar_x; g.N = d; g.K = 4 * d; g.pro = PRO_COPY; g.epi = EPI_RESID;
-    if (post) g.res = e->ar_xn;  // raw sum norm1(..) + ff(..); its norm2 runs in the next layer's (or the head's) prologue
+    g.res = fres;
     warm(g, 4 * li + 3);
-    g.kid = 5 + 5 * li;
+    g.kid = kid(li, 4);
     VXC(launch_gemv(e->bf16, g, e->num_cu, s));
   }
   if (pf_dist > 0) {
     const PfW& n = seq[(4 * c.num_layers + pf_dist) % seq.size()];
-    VXC(enqueue_head(e, s, nullptr, nullptr, nullptr, false, n.W, n.N, n.K));
-  } else {
-    VXC(enqueue_head(e, s));
-  }
-  return VX_OK;
-}
-
-// The VALL-F decode step (valle.py:613-647 with a KV cache; TransformerDecoderLayer, modules/transformer.py:536-560): per
-// layer QKV GEMV, causal attention over the cached AUDIO rows, out-projection, cross-attention query GEMV (rows [0, d) of the
-// packed multihead_attn in_proj), single-query attention over the layer's cached text memory (fixed length), its
-// out-projection, FFN1, FFN2: 8 launches per layer.  Post-norm: every norm runs in the prologue of the kernel that consumes it
-// and leaves the normalised vector in ar_xn as the next residual base (as in the VALL-E step).
-static int enqueue_ar_step_f(vx_engine* e, hipStream_t s) {
-  const vx_config& c = e->cfg;
-  const int d = c.d_model, H = c.nhead, hd = d / H;
-  const bool post = c.flags & VX_FLAG_POST_NORM;
-  SampleArgs sa{};
-  sa.logits = e->ar_logits; sa.V = AR_VOCAB; sa.st = e->d_st;
-  sa.tokens = e->d_tokens; sa.sampled = e->d_sampled; sa.argmaxes = e->d_argmax;
-  sa.emb = W<float>(e, "ar_audio_embedding.word_embeddings.weight");
-  sa.alpha = W<float>(e, "ar_audio_position.alpha");
-  sa.pe = e->pe_ar; sa.x = e->ar_x; sa.d = d; sa.kid = -1;
-  const bool prenet = c.flags & VX_FLAG_PRENET;
-  if (prenet) { sa.alpha = e->d_zero; sa.x = e->ar_e; }
-  sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(sa);
-  if (prenet) {
-    GemvArgs p0{}, p1{}, p2{};
-    p0.st = p1.st = p2.st = e->d_st;
-    p0.kid = p1.kid = p2.kid = -1;
-    p0.W = W<void>(e, "ar_audio_prenet.0.weight"); p0.bias = W<float>(e, "ar_audio_prenet.0.bias");
-    p0.x = e->ar_e; p0.y = e->ar_h1; p0.N = PRENET_H; p0.K = d; p0.pro = PRO_COPY; p0.epi = EPI_RELU;
-    p1.W = W<void>(e, "ar_audio_prenet.3.weight"); p1.bias = W<float>(e, "ar_audio_prenet.3.bias");
-    p1.x = e->ar_h1; p1.y = e->ar_h2; p1.N = PRENET_H; p1.K = PRENET_H; p1.pro = PRO_COPY; p1.epi = EPI_RELU;
-    p2.W = W<void>(e, "ar_audio_prenet.6.weight"); p2.bias = W<float>(e, "ar_audio_prenet.6.bias");
-    p2.x = e->ar_h2; p2.y = e->ar_x; p2.N = d; p2.K = PRENET_H; p2.pro = PRO_COPY; p2.epi = EPI_POS;
-    p2.pe = e->pe_ar; p2.pos_alpha = W<float>(e, "ar_audio_position.alpha");
-    VXC(launch_gemv(false, p0, e->num_cu, s));
-    VXC(launch_gemv(false, p1, e->num_cu, s));
-    VXC(launch_gemv(false, p2, e->num_cu, s));
-  }
-  const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
-  const size_t xkv_layer = (size_t)2 * d * c.max_text * e->esz;
-  const float scale = 1.0f / sqrtf((float)hd);
-  auto attend = [&](const char* kc, const char* vc, int ctx_max, int fixed_ctx) -> int {
-#define ADF(HDV)                                                                                                                       \
-  if (hd == HDV) {                                                                                                                     \
-    if (e->bf16) attn_decode_small_kernel<bf16, HDV><<<H * ATT_NSPLIT, 256, 0, s>>>(e->ar_q, (const bf16*)kc, (const bf16*)vc, e->ar_part, e->d_st, ctx_max, scale, -1, fixed_ctx); \
-    else attn_decode_small_kernel<float, HDV><<<H * ATT_NSPLIT, 256, 0, s>>>(e->ar_q, (const float*)kc, (const float*)vc, e->ar_part, e->d_st, ctx_max, scale, -1, fixed_ctx);      \
-    return VX_OK;                                                                                                                      \
-  }
-    if (hd == 64) {
-      if (e->bf16) attn_decode_kernel<bf16, 64><<<H * ATT_NSPLIT, 256, 0, s>>>(e->ar_q, (const bf16*)kc, (const bf16*)vc, e->ar_part, e->d_st, ctx_max, scale, -1, fixed_ctx);
-      else attn_decode_kernel<float, 64><<<H * ATT_NSPLIT, 256, 0, s>>>(e->ar_q, (const float*)kc, (const float*)vc, e->ar_part, e->d_st, ctx_max, scale, -1, fixed_ctx);
-      return VX_OK;
-    }
-    ADF(32) ADF(16) ADF(8) ADF(4)
-#undef ADF
-    return fail(VX_ERR_UNSUPPORTED, "decode attention: head_dim %d", hd);
-  };
-  for (int li = 0; li < c.num_layers; ++li) {
-    const LayerW& l = e->ar_l[li];
-    const char* kc = (const char*)e->kv + (size_t)li * kv_layer;
-    const char* vc = kc + kv_layer / 2;
-    const char* xk = (const char*)e->xkv_ar + (size_t)li * xkv_layer;
-    const char* xv = xk + xkv_layer / 2;
-    const float* res = nullptr;  // residual base of the sub-block (null: ar_x itself)
-    // self-attention
-    GemvArgs a{};
-    a.st = e->d_st; a.d = d; a.hd = hd; a.ctx_max = e->ctx_max; a.nhead = H; a.kid = -1;
-    a.W = l.in_w; a.bias = l.in_b; a.x = e->ar_x; a.gamma = l.n1_g; a.beta = l.n1_b;
-    a.N = 3 * d; a.K = d; a.pro = PRO_LN; a.epi = EPI_QKV; a.q = e->ar_q; a.kcache = (void*)kc; a.vcache = (void*)vc;
-    if (post) {
-      if (li == 0) a.pro = PRO_COPY;  // the fresh embedding, no norm in front of the first block
-      else { a.gamma = e->ar_l[li - 1].n3_g; a.beta = e->ar_l[li - 1].n3_b; a.xnorm_out = e->ar_xn; res = e->ar_xn; }
-    }
-    VXC(launch_gemv(e->bf16, a, e->num_cu, s));
-    VXC(attend(kc, vc, e->ctx_max, 0));
-    GemvArgs o{};
-    o.st = e->d_st; o.hd = hd; o.nhead = H; o.kid = -1;
-    o.W = l.out_w; o.bias = l.out_b; o.part = e->ar_part; o.y = e->ar_x; o.N = d; o.K = d; o.pro = PRO_ATTN; o.epi = EPI_RESID; o.res = res;
-    VXC(launch_gemv(e->bf16, o, e->num_cu, s));
-    // cross-attention: q = in_proj[0:d](norm2(x)) (post-norm: norm1 of the raw sum, which is also the next residual base)
-    GemvArgs q{};
-    q.st = e->d_st; q.kid = -1;
-    q.W = l.cin_w; q.bias = l.cin_b; q.x = e->ar_x; q.y = e->ar_q; q.N = d; q.K = d; q.pro = PRO_LN; q.epi = EPI_BIAS;
-    q.gamma = post ? l.n1_g : l.n2_g; q.beta = post ? l.n1_b : l.n2_b;
-    if (post) q.xnorm_out = e->ar_xn;
-    VXC(launch_gemv(e->bf16, q, e->num_cu, s));
-    VXC(attend(xk, xv, c.max_text, 1));  // length = ArState.S (the current utterance's text rows), read on the device
-    GemvArgs co{};
-    co.st = e->d_st; co.hd = hd; co.nhead = H; co.kid = -1;
-    co.W = l.cout_w; co.bias = l.cout_b; co.part = e->ar_part; co.y = e->ar_x; co.N = d; co.K = d; co.pro = PRO_ATTN; co.epi = EPI_RESID;
-    co.res = post ? e->ar_xn : nullptr;
-    VXC(launch_gemv(e->bf16, co, e->num_cu, s));
-    // feed-forward
-    GemvArgs f{};
-    f.st = e->d_st; f.kid = -1;
-    f.W = l.w1; f.bias = l.b1; f.x = e->ar_x; f.y = e->ar_f; f.N = 4 * d; f.K = d; f.pro = PRO_LN; f.epi = EPI_RELU;
-    f.gamma = post ? l.n2_g : l.n3_g; f.beta = post ? l.n2_b : l.n3_b;
-    if (post) f.xnorm_out = e->ar_xn;
-    VXC(launch_gemv(e->bf16, f, e->num_cu, s));
-    GemvArgs g{};
-    g.st = e->d_st; g.kid = -1;
-    g.W = l.w2; g.bias = l.b2; g.x = e->ar_f; g.y = e->ar_x; g.N = d; g.K = 4 * d; g.pro = PRO_COPY; g.epi = EPI_RESID;
-    if (post) g.res = e->ar_xn;
-    VXC(launch_gemv(e->bf16, g, e->num_cu, s));
+    return enqueue_head(e, s, nullptr, nullptr, nullptr, false, n.W, n.N, n.K);
   }
   return enqueue_head(e, s);
 }
@@ -1889,7 +1801,7 @@ static void launch_ln_batch(float* x, const float* part, int kgroups, const floa
 }
 
 // One batched step: every slot samples its next token, then the L layers run once over all B slots.  VALL-F (pre-norm,
-// TransformerDecoderLayer as in enqueue_ar_step_f): the self-attention cache holds audio rows only (kv_text = 0), and each layer
+// TransformerDecoderLayer as in enqueue_ar_step): the self-attention cache holds audio rows only (kv_text = 0), and each layer
 // adds the cross-attention over the slot's text memory (bmem) between the self-attention and the feed-forward block: 11 launches
 // per layer instead of 7.
 static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
@@ -2246,8 +2158,7 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
           add_pos_kernel<<<A, 256, 0, e->es>>>(ye, dn, a_aud, e->pe_nar, 0, xa, A);
         }
       }
-      if (vf) VXC(run_stack_f(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, nullptr, e->xkv_nar, S2[0]));
-      else VXC(run_stack(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, segs, KvDst()));
+      VXC(run_stack(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, segs, KvDst(), vf ? TextMem{e->xkv_nar, S2[0]} : TextMem()));
       // final AdaLN + predict layer on the generated rows only (valle.py:1128), compacted to [sum T][dn]
       const float* fw = post ? nullptr : ada_vec(e, i, e->npl * c.nar_num_layers);
       for (int b = 0; b < n; ++b) {
