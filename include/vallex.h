@@ -324,6 +324,68 @@ int vx_op_sample_topp(const float* logits, int32_t V, int32_t top_k, float tempe
                       int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 int vx_op_convert_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);
 
+/* ---- EnCodec-24 kHz decoder: codec tokens -> waveform (what valle/bin/infer.py:251-253 does with VALLE.inference's result
+ * through valle/data/tokenizer.py:241-242).  A handle of its own: the codec has its own weights and lifetime and is usable
+ * without a vx_engine.  Decode only; fp32 storage and accumulation.  Geometry as transformers' EncodecConfig: the decoder is
+ * conv(hidden -> 16 filters, kernel) -> LSTM + skip -> 4 x [ELU, transposed conv (k = 2 ratio, stride ratio, channels halved),
+ * residual block (res_kernel, hidden width C / 2)] -> ELU -> conv(filters -> 1, last_kernel); stride-1 convolutions are causal
+ * with reflect padding, weight norm is folded by the caller. */
+typedef struct vx_codec vx_codec;
+enum vx_codec_flags {
+  VX_CODEC_LSTM_GRAPH = 1 /* replay the LSTM's time steps as a captured linear chain instead of launching them one by one: the
+                             same kernels and results; measured slower at one utterance and equal at 32 / 64,
+                             so it is off by default */
+};
+typedef struct vx_codec_config {
+  int32_t struct_size;   /* = sizeof(vx_codec_config) */
+  int32_t hidden;        /* decoder input channels (128) */
+  int32_t filters;       /* num_filters (32): the LSTM runs at 16 * filters channels, which must be 64, 128, 256 or 512 */
+  int32_t ratios[4];     /* up-sampling ratios in decoder order (8, 5, 4, 2) */
+  int32_t kernel;        /* first convolution (7) */
+  int32_t last_kernel;   /* last convolution (7) */
+  int32_t res_kernel;    /* residual blocks' first convolution (3) */
+  int32_t n_codebooks;   /* codebooks loaded (8 for 6 kbps; <= 32) */
+  int32_t codebook_size; /* 1024 */
+  int32_t codebook_dim;  /* = hidden */
+  int32_t lstm_layers;   /* 1 or 2 */
+  int32_t max_frames;    /* capacity: frames per utterance */
+  int32_t max_batch;     /* capacity: utterances per call, <= 64 */
+  int32_t device;        /* HIP device ordinal */
+  int32_t flags;         /* enum vx_codec_flags */
+} vx_codec_config;
+
+/* Geometry the kernels do not serve: VX_ERR_UNSUPPORTED, before any HIP call.  Device memory is allocated by vx_codec_finalize. */
+int vx_codec_create(const vx_codec_config* cfg, vx_codec** out);
+void vx_codec_destroy(vx_codec* c);
+/* Keys: the local EncodecModel's state_dict names with weight norm removed - decoder.layers.N.conv.weight / .bias,
+ * decoder.layers.N.block.1|3.conv.*, decoder.layers.N.shortcut.conv.*, decoder.layers.1.lstm.weight_ih_l0 ... bias_hh_l1,
+ * quantizer.layers.q.codebook.embed - host fp32 in torch's layouts.  Unknown key or wrong shape: VX_ERR_WEIGHTS. */
+int vx_codec_set_weight(vx_codec* c, const char* key, const float* data, const int64_t* shape, int32_t ndim);
+/* Packs and uploads the weights, allocates the workspace.  A missing tensor: VX_ERR_WEIGHTS. */
+int vx_codec_finalize(vx_codec* c);
+/* n utterances: codes[i] HOST int64 (n_q, T[i]), wav_out[i] DEVICE fp32 of hop * T[i] samples (hop = product of the ratios,
+ * 320).  Checked before any HIP call: a code outside [0, codebook_size), n_q outside [1, n_codebooks], T[i] < 1 or n < 1 ->
+ * VX_ERR_ARG; T[i] > max_frames or n > max_batch -> VX_ERR_CAPACITY.  The work runs on the decoder's own stream, ordered after
+ * what is already enqueued on `stream`, and `stream` waits for it before the call returns; the host waits only for the previous
+ * call's staging copy.  Calls on one handle must not overlap.  A vx_codec_finalize that failed leaves a handle that answers
+ * VX_ERR_STATE to finalize and decode: destroy it. */
+int vx_codec_decode(vx_codec* c, int32_t n, const int64_t* const* codes, const int32_t* T, int32_t n_q, float* const* wav_out,
+                    void* stream);
+
+/* The codec's kernels on caller data (parity tests).  x / out: device fp32 time-major rows; w / bias: HOST fp32 in torch's
+ * layouts, packed as vx_codec_finalize packs them; seg_frames: HOST nseg + 1 frame offsets (seg_frames[0] = 0) of the
+ * concatenated utterances, `rate` rows per frame.  No tap and no LSTM state crosses a segment start.  Synchronous.
+ * conv: w (c_out, c_in, k), causal, reflect rule, ELU on the operand when elu != 0.  convtr: w (c_in, c_out, 2 stride), the
+ * stride rightmost samples trimmed, out has stride x the rows.  lstm: per layer w_ih / w_hh (4 width, width), b_ih / b_hh
+ * (4 width), gate order i, f, g, o; y = lstm(x) + x. */
+int vx_op_codec_conv(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out, int32_t k,
+                     int32_t elu, int32_t nseg, const int32_t* seg_frames, int32_t rate, void* stream);
+int vx_op_codec_convtr(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out, int32_t stride,
+                       int32_t elu, int32_t nseg, const int32_t* seg_frames, int32_t rate, void* stream);
+int vx_op_codec_lstm(const float* x, const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
+                     const float* const* b_hh, float* y, int32_t width, int32_t layers, int32_t nseg, const int32_t* seg_frames,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

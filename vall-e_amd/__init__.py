@@ -1,4 +1,13 @@
 """MI355X-native VALL-E inference engine (drop-in for ``valle.models.VALLE.inference``)."""
 from .config import ModelConfig, add_model_arguments, NUM_AUDIO_TOKENS, NUM_TEXT_TOKENS  # noqa: F401
 
-__all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_TOKENS"]
+
+__all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_TOKENS", "AudioTokenizer", "CodecConfig", "EncodecDecoder"]
+
+
+def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
+    if name in ("AudioTokenizer", "CodecConfig", "EncodecDecoder"):
+        from . import codec
+
+        return getattr(codec, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,253 @@
+"""EnCodec-24 kHz decoder on the GPU: codec tokens -> waveform, the step `valle/bin/infer.py:251-253` takes right after
+`VALLE.inference` (through `valle/data/tokenizer.py:241-242`).  Decode only; the encoder, resampling and file I/O stay on the
+host.  The kernels are csrc/codec_kernels.hpp behind `vx_codec_*` (include/vallex.h); there is no CPU fallback.
+
+    dec = EncodecDecoder(max_frames=2048)
+    dec.load_state_dict(encodec_model.state_dict(), strict=False)   # decoder.* and quantizer.* keys are taken
+    wav = dec.to("cuda").decode(codes.transpose(2, 1))              # codes (1, T, 8) from VALLE.inference -> (1, 1, 320 T)
+"""
+from __future__ import annotations
+
+import ctypes as C
+from collections import OrderedDict
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import engine as _e
+
+_WN = "parametrizations.weight.original"
+
+
+@dataclass(frozen=True)
+class CodecConfig:
+    """Geometry of the decoder; the defaults are the 24 kHz model (transformers' `EncodecConfig()`)."""
+    hidden: int = 128
+    filters: int = 32
+    ratios: Tuple[int, int, int, int] = (8, 5, 4, 2)
+    kernel: int = 7
+    last_kernel: int = 7
+    res_kernel: int = 3
+    lstm_layers: int = 2
+    codebook_size: int = 1024
+    n_codebooks: int = 8  # 6 kbps, what the reference's tokenizer sets
+
+    @property
+    def width(self) -> int:
+        return 16 * self.filters
+
+    @property
+    def hop(self) -> int:
+        return int(np.prod(self.ratios))
+
+
+def expected_keys(cfg: CodecConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Key -> shape with weight norm removed (the names `vx_codec_set_weight` takes)."""
+    W = cfg.width
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    s["decoder.layers.0.conv.weight"] = (W, cfg.hidden, cfg.kernel)
+    s["decoder.layers.0.conv.bias"] = (W,)
+    for l in range(cfg.lstm_layers):
+        for n, shp in (("weight_ih", (4 * W, W)), ("weight_hh", (4 * W, W)), ("bias_ih", (4 * W,)), ("bias_hh", (4 * W,))):
+            s[f"decoder.layers.1.lstm.{n}_l{l}"] = shp
+    c = W
+    for i, r in enumerate(cfg.ratios):
+        up, res = 3 + 3 * i, 4 + 3 * i
+        s[f"decoder.layers.{up}.conv.weight"] = (c, c // 2, 2 * r)
+        s[f"decoder.layers.{up}.conv.bias"] = (c // 2,)
+        c //= 2
+        p = f"decoder.layers.{res}."
+        s[p + "block.1.conv.weight"] = (c // 2, c, cfg.res_kernel)
+        s[p + "block.1.conv.bias"] = (c // 2,)
+        s[p + "block.3.conv.weight"] = (c, c // 2, 1)
+        s[p + "block.3.conv.bias"] = (c,)
+        s[p + "shortcut.conv.weight"] = (c, c, 1)
+        s[p + "shortcut.conv.bias"] = (c,)
+    last = 3 + 3 * len(cfg.ratios)
+    s[f"decoder.layers.{last}.conv.weight"] = (1, c, cfg.last_kernel)
+    s[f"decoder.layers.{last}.conv.bias"] = (1,)
+    for q in range(cfg.n_codebooks):
+        s[f"quantizer.layers.{q}.codebook.embed"] = (cfg.codebook_size, cfg.hidden)
+    return s
+
+
+def pack_state_dict(cfg: CodecConfig, sd: Dict[str, torch.Tensor], strict: bool = True):
+    """Either accepted layout -> (fp32 tensors under the plain names, missing, unexpected).  Weight norm (w = g v / |v|, the norm
+    over all dimensions but the first) is folded in fp64 and rounded once.  With strict=False keys outside the decoder and
+    the loaded codebooks (the encoder, EMA statistics, further codebooks) are ignored."""
+    want = expected_keys(cfg)
+    out: Dict[str, torch.Tensor] = {}
+    used = set()
+    for k, shp in want.items():
+        if k in sd:
+            t = sd[k].detach().to("cpu", torch.float64)
+            used.add(k)
+        elif k.endswith(".conv.weight") and k[:-len("weight")] + _WN + "1" in sd:
+            kg, kv = k[:-len("weight")] + _WN + "0", k[:-len("weight")] + _WN + "1"
+            if kg not in sd:
+                continue
+            g, v = sd[kg].detach().to("cpu", torch.float64), sd[kv].detach().to("cpu", torch.float64)
+            if g.numel() != v.shape[0]:
+                raise RuntimeError(f"size mismatch for {kg}: {tuple(g.shape)} against {tuple(v.shape)}")
+            t = g.reshape(-1, 1, 1) * v / v.flatten(1).norm(dim=1).reshape(-1, 1, 1)
+            used.update((kg, kv))
+        else:
+            continue
+        if tuple(t.shape) != tuple(shp):
+            raise RuntimeError(f"size mismatch for {k}: {tuple(t.shape)}, expected {tuple(shp)}")
+        out[k] = t.to(torch.float32).contiguous()
+    missing = [k for k in want if k not in out]
+    unexpected = [k for k in sd if k not in used]
+    if strict and (missing or unexpected):
+        raise RuntimeError(f"Error(s) in loading state_dict for EncodecDecoder: missing {missing}, unexpected {unexpected}")
+    return out, missing, unexpected
+
+
+class EncodecDecoder:
+    """codes -> 24 kHz waveform in HIP.  `max_frames` / `max_batch` are capacities (frames per utterance, utterances per
+    `decode_batch` call; the workspace is allocated for them on first use)."""
+
+    def __init__(self, config: Optional[CodecConfig] = None, max_frames: int = 2048, max_batch: int = 1, lstm_graph: bool = False):
+        self.cfg = config or CodecConfig()
+        if len(self.cfg.ratios) != 4:
+            raise NotImplementedError("four up-sampling stages")
+        self.max_frames, self.max_batch = int(max_frames), int(max_batch)
+        self.lstm_graph = bool(lstm_graph)  # LSTM steps replayed as a captured chain instead of plain launches (not faster)
+        self.device = torch.device("cpu")
+        self._sd: Dict[str, torch.Tensor] = {}
+        self._h = None
+        self._final = False
+
+    # ---- weights ------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict, strict: bool = True):
+        """Accepts the local EncodecModel's names (`decoder.layers.N.conv.parametrizations.weight.original0/1`, the LSTM's torch
+        names, `quantizer.layers.q.codebook.embed`) and the same names with weight norm removed (`...conv.weight`)."""
+        from .models import _IncompatibleKeys
+
+        packed, missing, unexpected = pack_state_dict(self.cfg, state_dict, strict)
+        self._sd.update(packed)
+        self._drop()
+        return _IncompatibleKeys(missing, unexpected)
+
+    def state_dict(self):
+        return OrderedDict((k, self._sd[k]) for k in expected_keys(self.cfg) if k in self._sd)
+
+    def to(self, device):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._drop()
+        return self
+
+    def cuda(self, index: int = 0):
+        return self.to(torch.device("cuda", index))
+
+    def eval(self):
+        return self
+
+    def _drop(self):
+        if self._h is not None:
+            _e.load_library().vx_codec_destroy(self._h)
+            self._h = None
+            self._final = False
+
+    close = _drop
+
+    def __del__(self):
+        try:
+            self._drop()
+        except Exception:
+            pass
+
+    def _config_struct(self) -> "_e.VxCodecConfig":
+        c, g = _e.VxCodecConfig(), self.cfg
+        c.struct_size = C.sizeof(_e.VxCodecConfig)
+        c.hidden, c.filters, c.kernel, c.last_kernel, c.res_kernel = g.hidden, g.filters, g.kernel, g.last_kernel, g.res_kernel
+        for i, r in enumerate(g.ratios):
+            c.ratios[i] = r
+        c.n_codebooks, c.codebook_size, c.codebook_dim, c.lstm_layers = g.n_codebooks, g.codebook_size, g.hidden, g.lstm_layers
+        c.max_frames, c.max_batch, c.device = self.max_frames, self.max_batch, self.device.index or 0
+        c.flags = _e.VX_CODEC_LSTM_GRAPH if self.lstm_graph else 0
+        return c
+
+    def handle(self, finalize: bool = True):
+        """The C handle, created on first use; finalising it needs the GPU (there is no CPU path)."""
+        lib = _e.load_library()
+        if finalize and self.device.type != "cuda":
+            raise RuntimeError("valle_amd.EncodecDecoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        if self._h is None:
+            h = C.c_void_p()
+            _e._check(lib.vx_codec_create(C.byref(self._config_struct()), C.byref(h)))
+            self._h = h
+            for k, t in self._sd.items():
+                shp = (C.c_int64 * t.dim())(*t.shape)
+                _e._check(lib.vx_codec_set_weight(h, k.encode(), t.data_ptr(), shp, t.dim()))
+        if finalize and not self._final:
+            try:
+                _e._check(lib.vx_codec_finalize(self._h))
+            except Exception:
+                self._drop()  # a handle whose finalize failed refuses further use: the next call starts from a fresh one
+                raise
+            self._final = True
+        return self._h
+
+    # ---- decode -------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def decode_batch(self, codes: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+        """codes[i]: (n_q, T_i) or (1, n_q, T_i) int64, the same n_q for all -> [(1, 1, hop T_i) float32 on the device]."""
+        cs = []
+        for c in codes:
+            if c.dim() == 3:
+                assert c.shape[0] == 1, "one utterance per entry"
+                c = c[0]
+            assert c.dim() == 2 and c.dtype == torch.int64, "codes are (n_q, T) int64"
+            cs.append(c.detach().to("cpu").contiguous())
+        assert cs and all(c.shape[0] == cs[0].shape[0] for c in cs), "every utterance of a call has the same n_q"
+        if self.device.type != "cuda":
+            raise RuntimeError("valle_amd.EncodecDecoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        outs = [torch.empty((1, 1, self.cfg.hop * c.shape[1]), dtype=torch.float32, device=self.device) for c in cs]
+        self._decode_raw(cs, [o.data_ptr() for o in outs])
+        return outs
+
+    def _decode_raw(self, cs, out_ptrs, finalize: bool = True):
+        """vx_codec_decode on host code tensors and raw output pointers (the argument checks run before any device work)."""
+        n = len(cs)
+        lib = _e.load_library()
+        h = self.handle(finalize)
+        cp = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
+        T = (C.c_int32 * n)(*[c.shape[1] for c in cs])
+        op = (C.c_void_p * n)(*out_ptrs)
+        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
+        _e._check(lib.vx_codec_decode(h, n, cp, T, cs[0].shape[0], op, stream))
+
+    def decode(self, codes: torch.Tensor) -> torch.Tensor:
+        """(1, n_q, T) or (n_q, T) int64 -> (1, 1, hop T) float32 on the device."""
+        return self.decode_batch([codes])[0]
+
+
+class AudioTokenizer:
+    """The decode half of the reference's `valle.data.tokenizer.AudioTokenizer` (tokenizer.py:241-242) on the GPU:
+    `decode([(frames, None)])` with frames (B, n_q, T), as `infer.py:251-253` passes `encoded_frames.transpose(2, 1)`.
+    `encode` is out of scope (the prompt is tokenised on the host as before)."""
+
+    sample_rate = 24000
+    channels = 1
+
+    def __init__(self, decoder: EncodecDecoder):
+        self.decoder = decoder
+
+    @property
+    def device(self):
+        return self.decoder.device
+
+    def decode(self, frames) -> torch.Tensor:
+        assert len(frames) == 1, "one (codes, scale) pair: the 24 kHz model decodes whole utterances"
+        codes, scale = frames[0]
+        assert scale is None, "the 24 kHz model does not normalise"
+        wavs = self.decoder.decode_batch([codes[b] for b in range(codes.shape[0])])
+        return torch.cat(wavs, dim=0)  # (B, 1, hop T)
+
+    def encode(self, wav):
+        raise NotImplementedError("valle_amd.AudioTokenizer decodes only; tokenise prompts with the reference's tokenizer")

@@ -1,0 +1,634 @@
+// EnCodec-24 kHz decoder behind the C ABI (include/vallex.h, vx_codec_*): weights, workspace and the launch sequence of
+// codec_kernels.hpp.  A handle of its own: the codec has its own weights and lifetime and runs without a VALL-E engine.
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/vallex.h"
+#include "codec_kernels.hpp"
+
+using namespace vx;
+
+extern "C" void vx_internal_set_error(const char* msg);  // engine.hip: the message vx_last_error() returns
+
+static int cfail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  vx_internal_set_error(buf);
+  return code;
+}
+#define CHIPC(expr)                                                                                                    \
+  do {                                                                                                                 \
+    hipError_t e_ = (expr);                                                                                            \
+    if (e_ != hipSuccess)                                                                                              \
+      return cfail(VX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);              \
+  } while (0)
+#define CVXC(expr)              \
+  do {                          \
+    int r_ = (expr);            \
+    if (r_ != VX_OK) return r_; \
+  } while (0)
+
+namespace {
+
+struct CDevGuard {
+  int prev = -1;
+  hipError_t err = hipSuccess;
+  explicit CDevGuard(int dev) {
+    err = hipGetDevice(&prev);
+    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
+    else if (err == hipSuccess) prev = -1;
+  }
+  ~CDevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+struct HostW {
+  std::vector<int64_t> shape;
+  std::vector<float> v;
+  bool set = false;
+};
+
+// ---- weight packing (host): torch layouts -> the [N][K] operands of codec_gemm_rows -------------------------------------
+// conv (O, C, k): k index = tap * C + c, tap 0 = oldest sample
+std::vector<float> pack_conv(const float* w, int O, int Cc, int k) {
+  std::vector<float> p((size_t)O * Cc * k);
+  for (int o = 0; o < O; ++o)
+    for (int c = 0; c < Cc; ++c)
+      for (int j = 0; j < k; ++j) p[((size_t)o * k + j) * Cc + c] = w[((size_t)o * Cc + c) * k + j];
+  return p;
+}
+// transposed conv (Cin, Cout, 2s), stride s: row n = r * Cout + co; k < Cin: x[t-1] with W[ci][co][r + s]; then x[t] with W[ci][co][r]
+std::vector<float> pack_convtr(const float* w, int Cin, int Cout, int s) {
+  std::vector<float> p((size_t)s * Cout * 2 * Cin);
+  for (int r = 0; r < s; ++r)
+    for (int co = 0; co < Cout; ++co)
+      for (int ci = 0; ci < Cin; ++ci) {
+        const size_t n = (size_t)r * Cout + co;
+        p[n * 2 * Cin + ci] = w[((size_t)ci * Cout + co) * 2 * s + r + s];
+        p[n * 2 * Cin + Cin + ci] = w[((size_t)ci * Cout + co) * 2 * s + r];
+      }
+  return p;
+}
+
+int upload(const std::vector<float>& h, float** d) {
+  CHIPC(hipMalloc((void**)d, h.size() * sizeof(float) + 16));
+  CHIPC(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  return VX_OK;
+}
+
+// ---- launches --------------------------------------------------------------------------------------------------------
+int launch_gemm(CodecGemmArgs a, hipStream_t s) {
+  bool vec = true;
+  for (int p = 0; p < a.nparts; ++p) vec = vec && (a.part[p].C % 16 == 0);
+  if (a.M <= 0) return VX_OK;
+  if (a.N <= 32) {
+    dim3 g((unsigned)((a.M + 127) / 128), (unsigned)((a.N + 31) / 32));
+    if (vec) codec_gemm_rows<4, 1, true><<<g, 256, 0, s>>>(a);
+    else codec_gemm_rows<4, 1, false><<<g, 256, 0, s>>>(a);
+  } else {
+    dim3 g((unsigned)((a.M + 63) / 64), (unsigned)((a.N + 63) / 64));
+    if (vec) codec_gemm_rows<2, 2, true><<<g, 256, 0, s>>>(a);
+    else codec_gemm_rows<2, 2, false><<<g, 256, 0, s>>>(a);
+  }
+  CHIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// causal k-tap convolution over rows (reflect rule); wp packed by pack_conv.  c_out == 1 runs the bandwidth kernel.
+int run_conv(const float* x, const float* wp, const float* bias, float* out, long M, int cin, int cout, int k, int elu,
+             const int* seg, int nseg, int rate, hipStream_t s) {
+  if (cout == 1 && elu) {
+    if (M > 0) codec_conv_out<<<(unsigned)((M + 255) / 256), 256, 0, s>>>(x, wp, bias, out, M, cin, k, seg, nseg, rate);
+    CHIPC(hipGetLastError());
+    return VX_OK;
+  }
+  CodecGemmArgs a{};
+  a.part[0] = CodecPart{x, cin, k, CODEC_PAD_REFLECT, elu};
+  a.nparts = 1;
+  a.W = wp; a.bias = bias; a.out = out; a.M = M; a.N = cout; a.K = cin * k; a.seg = seg; a.nseg = nseg; a.rate = rate;
+  return launch_gemm(a, s);
+}
+
+// transposed convolution k = 2 stride over M input rows -> M * stride output rows; wp / bias_rep packed ([stride * cout])
+int run_convtr(const float* x, const float* wp, const float* bias_rep, float* out, long M, int cin, int cout, int stride, int elu,
+               const int* seg, int nseg, int rate, hipStream_t s) {
+  CodecGemmArgs a{};
+  a.part[0] = CodecPart{x, cin, 2, CODEC_PAD_ZERO, elu};
+  a.nparts = 1;
+  a.W = wp; a.bias = bias_rep; a.out = out; a.M = M; a.N = stride * cout; a.K = 2 * cin; a.seg = seg; a.nseg = nseg; a.rate = rate;
+  return launch_gemm(a, s);
+}
+
+struct LstmDev {
+  float *wih0 = nullptr, *b0 = nullptr, *whh0 = nullptr, *w1 = nullptr, *b1 = nullptr;
+};
+
+bool lstm_width_ok(int H) { return H == 64 || H == 128 || H == 256 || H == 512; }
+
+void launch_lstm_step(const CodecLstmArgs& a, int H, unsigned grid, int st, hipStream_t s) {
+  switch (H) {
+    case 64: codec_lstm_step<1><<<grid, 256, 0, s>>>(a, st); break;
+    case 128: codec_lstm_step<2><<<grid, 256, 0, s>>>(a, st); break;
+    case 256: codec_lstm_step<4><<<grid, 256, 0, s>>>(a, st); break;
+    default: codec_lstm_step<8><<<grid, 256, 0, s>>>(a, st); break;
+  }
+}
+
+constexpr int CODEC_LSTM_CHAIN = 64;  // step launches per replay of the captured chain
+
+// x [rows][H] -> y = lstm(x) + x; gin [rows][4H], h0 / h1 [rows][H], c0 / c1 [nseg][H] are workspace.  chain == nullptr: one plain
+// launch per step.  Otherwise the steps are replayed as a captured LINEAR chain of CODEC_LSTM_CHAIN step launches and one
+// node that advances the step counter: `meta` (device {nseg, step}) was written by the caller, *chain is captured on first use
+// (s must not be the null stream) and serves every batch and length of the handle.
+int run_lstm(const LstmDev& w, const float* x, float* gin, float* h0, float* h1, float* c0, float* c1, float* y, int H, int layers,
+             const int* seg_dev, const int* seg_host, int nseg, hipStream_t s, hipGraphExec_t* chain = nullptr, int* meta = nullptr) {
+  const long rows = seg_host[nseg];
+  int Tmax = 0;
+  for (int b = 0; b < nseg; ++b) Tmax = std::max(Tmax, seg_host[b + 1] - seg_host[b]);
+  CodecGemmArgs g{};
+  g.part[0] = CodecPart{x, H, 1, CODEC_PAD_ZERO, 0};
+  g.nparts = 1;
+  g.W = w.wih0; g.bias = w.b0; g.out = gin; g.M = rows; g.N = 4 * H; g.K = H; g.seg = seg_dev; g.nseg = nseg; g.rate = 1;
+  CVXC(launch_gemm(g, s));
+  CodecLstmArgs a{};
+  a.gin0 = gin; a.whh0 = w.whh0; a.w1 = w.w1; a.b1 = w.b1; a.xin = x; a.h0 = h0; a.h1 = h1; a.y = y; a.c0 = c0; a.c1 = c1;
+  a.seg = seg_dev; a.nseg = nseg; a.H = H; a.layers = layers;
+  const unsigned grid = (unsigned)(layers * H / 4);
+  const int steps = Tmax + layers - 1;
+  if (!chain) {
+    for (int st = 0; st < steps; ++st) launch_lstm_step(a, H, grid, st, s);
+    CHIPC(hipGetLastError());
+    return VX_OK;
+  }
+  if (!*chain) {
+    a.meta = meta;
+    a.nseg = 0;
+    hipGraph_t graph = nullptr;
+    CHIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    for (int st = 0; st < CODEC_LSTM_CHAIN; ++st) launch_lstm_step(a, H, grid, st, s);
+    codec_lstm_advance<<<1, 64, 0, s>>>(meta, CODEC_LSTM_CHAIN);
+    const hipError_t ce = hipStreamEndCapture(s, &graph);
+    if (ce != hipSuccess) return cfail(VX_ERR_HIP, "capturing the LSTM chain failed: %s", hipGetErrorString(ce));
+    const hipError_t ie = hipGraphInstantiate(chain, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ie != hipSuccess) { *chain = nullptr; return cfail(VX_ERR_HIP, "instantiating the LSTM chain failed: %s", hipGetErrorString(ie)); }
+  }
+  for (int st = 0; st < steps; st += CODEC_LSTM_CHAIN) CHIPC(hipGraphLaunch(*chain, s));
+  return VX_OK;
+}
+
+// LSTM weights (torch layouts, host) -> device operands: W_ih0, b_ih0 + b_hh0, W_hh0, [W_ih1 | W_hh1], b_ih1 + b_hh1
+int pack_lstm(const float* const* wih, const float* const* whh, const float* const* bih, const float* const* bhh, int H, int layers,
+              LstmDev* d) {
+  std::vector<float> b0(4 * H);
+  for (int i = 0; i < 4 * H; ++i) b0[i] = bih[0][i] + bhh[0][i];
+  CVXC(upload(std::vector<float>(wih[0], wih[0] + (size_t)4 * H * H), &d->wih0));
+  CVXC(upload(std::vector<float>(whh[0], whh[0] + (size_t)4 * H * H), &d->whh0));
+  CVXC(upload(b0, &d->b0));
+  if (layers == 2) {
+    std::vector<float> w1((size_t)4 * H * 2 * H), b1(4 * H);
+    for (int n = 0; n < 4 * H; ++n) {
+      memcpy(&w1[(size_t)n * 2 * H], wih[1] + (size_t)n * H, H * sizeof(float));
+      memcpy(&w1[(size_t)n * 2 * H + H], whh[1] + (size_t)n * H, H * sizeof(float));
+      b1[n] = bih[1][n] + bhh[1][n];
+    }
+    CVXC(upload(w1, &d->w1));
+    CVXC(upload(b1, &d->b1));
+  }
+  return VX_OK;
+}
+void free_lstm(LstmDev& d) {
+  for (float* p : {d.wih0, d.b0, d.whh0, d.w1, d.b1}) (void)hipFree(p);
+  d = LstmDev{};
+}
+
+int check_segs(const int32_t* seg, int nseg) {
+  if (!seg || nseg < 1 || nseg > CODEC_MAX_SEG) return cfail(VX_ERR_ARG, "segments: 1..%d expected, got %d", CODEC_MAX_SEG, nseg);
+  if (seg[0] != 0) return cfail(VX_ERR_ARG, "segment starts begin at 0");
+  for (int i = 0; i < nseg; ++i)
+    if (seg[i + 1] <= seg[i]) return cfail(VX_ERR_ARG, "segment %d is empty or starts are not increasing", i);
+  return VX_OK;
+}
+
+struct Stage {
+  int cin, cout, stride;
+  float *up_w = nullptr, *up_b = nullptr;    // packed transposed conv, bias repeated per phase
+  float *c3_w = nullptr, *c3_b = nullptr;    // block.1: cout -> cout / 2, k = res_kernel
+  float *mix_w = nullptr, *mix_b = nullptr;  // [block.3 | shortcut]: K = cout / 2 + cout, bias = sum of the two
+};
+
+}  // namespace
+
+struct vx_codec {
+  vx_codec_config cfg{};
+  int W = 0;  // LSTM width = 16 * filters
+  std::map<std::string, HostW> w;
+  bool allocated = false;  // device objects may exist: vx_codec_destroy frees them
+  bool finalized = false;  // every upload and allocation succeeded: set as vx_codec_finalize's last statement
+  bool failed = false;     // a finalize failed half way: the handle refuses further use
+  hipStream_t own = nullptr;                 // the decoder's stream (the LSTM chain cannot be captured on the null stream)
+  hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_copy = nullptr;
+  hipGraphExec_t chain = nullptr;
+  float* cb = nullptr;  // [n_codebooks][size][dim]
+  float *c0_w = nullptr, *c0_b = nullptr, *last_w = nullptr, *last_b = nullptr;
+  LstmDev lstm;
+  std::vector<Stage> stages;
+  // workspace
+  long cap_frames = 0, chunk_frames = 0, per_frame = 0;
+  // int32 staging: {nseg, step} | frame offsets [max_batch + 1] | per-group relative offsets [2 (max_batch + 1)] | codes [n_q][frames]
+  int *codes_dev = nullptr, *codes_host = nullptr;
+  size_t stage_ints = 0;
+  float *x0 = nullptr, *xc = nullptr, *gin = nullptr, *h0 = nullptr, *h1 = nullptr, *y = nullptr, *c0 = nullptr, *c1 = nullptr;
+  float *bufA = nullptr, *bufH = nullptr, *bufB = nullptr;
+};
+
+static std::map<std::string, std::vector<int64_t>> codec_expected(const vx_codec_config& c) {
+  std::map<std::string, std::vector<int64_t>> s;
+  const int64_t W = 16 * (int64_t)c.filters;
+  char k[128];
+  s["decoder.layers.0.conv.weight"] = {W, c.hidden, c.kernel};
+  s["decoder.layers.0.conv.bias"] = {W};
+  for (int l = 0; l < c.lstm_layers; ++l) {
+    snprintf(k, sizeof k, "decoder.layers.1.lstm.weight_ih_l%d", l); s[k] = {4 * W, W};
+    snprintf(k, sizeof k, "decoder.layers.1.lstm.weight_hh_l%d", l); s[k] = {4 * W, W};
+    snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_ih_l%d", l); s[k] = {4 * W};
+    snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_hh_l%d", l); s[k] = {4 * W};
+  }
+  int64_t ch = W;
+  for (int i = 0; i < 4; ++i) {
+    const int up = 3 + 3 * i, res = 4 + 3 * i;
+    snprintf(k, sizeof k, "decoder.layers.%d.conv.weight", up); s[k] = {ch, ch / 2, 2 * (int64_t)c.ratios[i]};
+    snprintf(k, sizeof k, "decoder.layers.%d.conv.bias", up); s[k] = {ch / 2};
+    ch /= 2;
+    snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.weight", res); s[k] = {ch / 2, ch, c.res_kernel};
+    snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.bias", res); s[k] = {ch / 2};
+    snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.weight", res); s[k] = {ch, ch / 2, 1};
+    snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.bias", res); s[k] = {ch};
+    snprintf(k, sizeof k, "decoder.layers.%d.shortcut.conv.weight", res); s[k] = {ch, ch, 1};
+    snprintf(k, sizeof k, "decoder.layers.%d.shortcut.conv.bias", res); s[k] = {ch};
+  }
+  s["decoder.layers.15.conv.weight"] = {1, ch, c.last_kernel};
+  s["decoder.layers.15.conv.bias"] = {1};
+  for (int q = 0; q < c.n_codebooks; ++q) {
+    snprintf(k, sizeof k, "quantizer.layers.%d.codebook.embed", q); s[k] = {c.codebook_size, c.codebook_dim};
+  }
+  return s;
+}
+
+extern "C" int vx_codec_create(const vx_codec_config* cfg, vx_codec** out) {
+  if (!cfg || !out) return cfail(VX_ERR_ARG, "vx_codec_create: null argument");
+  if (cfg->struct_size != (int32_t)sizeof(vx_codec_config))
+    return cfail(VX_ERR_ARG, "vx_codec_config.struct_size %d != %d", cfg->struct_size, (int)sizeof(vx_codec_config));
+  const vx_codec_config& c = *cfg;
+  if (c.hidden < 1 || c.filters < 1 || c.codebook_size < 1 || c.codebook_dim < 1 || c.n_codebooks < 1 || c.max_frames < 1 ||
+      c.max_batch < 1 || c.kernel < 1 || c.last_kernel < 1 || c.res_kernel < 1 || c.lstm_layers < 0 || c.device < 0 ||
+      (c.flags & ~VX_CODEC_LSTM_GRAPH))
+    return cfail(VX_ERR_ARG, "vx_codec_config: sizes must be positive and flags known");
+  for (int i = 0; i < 4; ++i)
+    if (c.ratios[i] < 1) return cfail(VX_ERR_ARG, "vx_codec_config.ratios[%d] = %d", i, c.ratios[i]);
+  const int W = 16 * c.filters;
+  if (c.codebook_dim != c.hidden) return cfail(VX_ERR_UNSUPPORTED, "codebook_dim %d != hidden %d", c.codebook_dim, c.hidden);
+  if (c.lstm_layers < 1 || c.lstm_layers > 2) return cfail(VX_ERR_UNSUPPORTED, "lstm_layers %d: the step kernel serves 1 or 2", c.lstm_layers);
+  if (!lstm_width_ok(W)) return cfail(VX_ERR_UNSUPPORTED, "LSTM width 16 * filters = %d: the step kernel serves 64, 128, 256, 512", W);
+  if (c.kernel > 15 || c.last_kernel > 15 || c.res_kernel > 15) return cfail(VX_ERR_UNSUPPORTED, "kernel sizes above 15");
+  if (c.n_codebooks > CODEC_MAX_Q) return cfail(VX_ERR_UNSUPPORTED, "n_codebooks %d > %d", c.n_codebooks, CODEC_MAX_Q);
+  if (c.max_batch > CODEC_MAX_SEG) return cfail(VX_ERR_UNSUPPORTED, "max_batch %d > %d", c.max_batch, CODEC_MAX_SEG);
+  long hop = 1;
+  for (int i = 0; i < 4; ++i) hop *= c.ratios[i];
+  if (hop * (long)c.max_frames * c.max_batch >= (1L << 40)) return cfail(VX_ERR_UNSUPPORTED, "capacity too large");
+  vx_codec* e = new vx_codec();
+  e->cfg = c;
+  e->W = W;
+  for (auto& kv : codec_expected(c)) e->w[kv.first].shape = kv.second;
+  *out = e;
+  return VX_OK;
+}
+
+static void codec_free_device(vx_codec* e) {
+  for (float* p : {e->cb, e->c0_w, e->c0_b, e->last_w, e->last_b, e->x0, e->xc, e->gin, e->h0, e->h1, e->y, e->c0, e->c1, e->bufA,
+                   e->bufH, e->bufB})
+    (void)hipFree(p);
+  free_lstm(e->lstm);
+  for (Stage& st : e->stages)
+    for (float* p : {st.up_w, st.up_b, st.c3_w, st.c3_b, st.mix_w, st.mix_b}) (void)hipFree(p);
+  (void)hipFree(e->codes_dev);
+  (void)hipHostFree(e->codes_host);
+  if (e->chain) (void)hipGraphExecDestroy(e->chain);
+  for (hipEvent_t ev : {e->ev_in, e->ev_out, e->ev_copy})
+    if (ev) (void)hipEventDestroy(ev);
+  if (e->own) (void)hipStreamDestroy(e->own);
+}
+
+extern "C" void vx_codec_destroy(vx_codec* e) {
+  if (!e) return;
+  if (e->allocated) {
+    CDevGuard g(e->cfg.device);
+    if (e->own) (void)hipStreamSynchronize(e->own);
+    codec_free_device(e);
+  }
+  delete e;
+}
+
+extern "C" int vx_codec_set_weight(vx_codec* e, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
+  if (!e || !key || !data || !shape) return cfail(VX_ERR_ARG, "vx_codec_set_weight: null argument");
+  if (e->finalized) return cfail(VX_ERR_STATE, "vx_codec_set_weight after vx_codec_finalize");
+  auto it = e->w.find(key);
+  if (it == e->w.end()) return cfail(VX_ERR_WEIGHTS, "unknown key %s", key);
+  HostW& t = it->second;
+  bool same = (size_t)ndim == t.shape.size();
+  size_t n = 1;
+  for (int i = 0; same && i < ndim; ++i) { same = shape[i] == t.shape[i]; n *= (size_t)shape[i]; }
+  if (!same) return cfail(VX_ERR_WEIGHTS, "wrong shape for %s", key);
+  t.v.assign(data, data + n);
+  t.set = true;
+  return VX_OK;
+}
+
+static int alloc_f(float** p, size_t n) {
+  CHIPC(hipMalloc((void**)p, n * sizeof(float) + 16));
+  return VX_OK;
+}
+
+extern "C" int vx_codec_finalize(vx_codec* e) {
+  if (!e) return cfail(VX_ERR_ARG, "vx_codec_finalize: null handle");
+  if (e->finalized) return VX_OK;
+  if (e->failed) return cfail(VX_ERR_STATE, "vx_codec_finalize failed earlier on this handle: destroy it and create a new one");
+  for (auto& kv : e->w)
+    if (!kv.second.set) return cfail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
+  const vx_codec_config& c = e->cfg;
+  e->failed = true;     // until the last statement: a finalize that stops at a HIP error leaves a handle that refuses further use
+  CDevGuard g(c.device);
+  CHIPC(g.err);
+  e->allocated = true;  // from here vx_codec_destroy frees what was allocated
+  const int W = e->W;
+  char k[128], k2[128];
+  auto host = [&](const char* key) -> const std::vector<float>& { return e->w[key].v; };
+  {
+    std::vector<float> cb((size_t)c.n_codebooks * c.codebook_size * c.codebook_dim);
+    for (int q = 0; q < c.n_codebooks; ++q) {
+      snprintf(k, sizeof k, "quantizer.layers.%d.codebook.embed", q);
+      memcpy(&cb[(size_t)q * c.codebook_size * c.codebook_dim], host(k).data(), host(k).size() * sizeof(float));
+    }
+    CVXC(upload(cb, &e->cb));
+  }
+  CVXC(upload(pack_conv(host("decoder.layers.0.conv.weight").data(), W, c.hidden, c.kernel), &e->c0_w));
+  CVXC(upload(host("decoder.layers.0.conv.bias"), &e->c0_b));
+  {
+    const float *wih[2] = {}, *whh[2] = {}, *bih[2] = {}, *bhh[2] = {};
+    for (int l = 0; l < c.lstm_layers; ++l) {
+      snprintf(k, sizeof k, "decoder.layers.1.lstm.weight_ih_l%d", l); wih[l] = host(k).data();
+      snprintf(k, sizeof k, "decoder.layers.1.lstm.weight_hh_l%d", l); whh[l] = host(k).data();
+      snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_ih_l%d", l); bih[l] = host(k).data();
+      snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_hh_l%d", l); bhh[l] = host(k).data();
+    }
+    CVXC(pack_lstm(wih, whh, bih, bhh, W, c.lstm_layers, &e->lstm));
+  }
+  int ch = W;
+  long rate = 1, per_frame = 0;
+  e->stages.resize(4);
+  for (int i = 0; i < 4; ++i) {
+    Stage& st = e->stages[i];
+    const int up = 3 + 3 * i, res = 4 + 3 * i, r = c.ratios[i];
+    st.cin = ch; st.cout = ch / 2; st.stride = r;
+    snprintf(k, sizeof k, "decoder.layers.%d.conv.weight", up);
+    CVXC(upload(pack_convtr(host(k).data(), ch, ch / 2, r), &st.up_w));
+    snprintf(k, sizeof k, "decoder.layers.%d.conv.bias", up);
+    std::vector<float> rep((size_t)r * (ch / 2));
+    for (int p = 0; p < r; ++p) memcpy(&rep[(size_t)p * (ch / 2)], host(k).data(), (ch / 2) * sizeof(float));
+    CVXC(upload(rep, &st.up_b));
+    ch /= 2;
+    rate *= r;
+    per_frame = std::max(per_frame, rate * ch);
+    const int hd = ch / 2;
+    snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.weight", res);
+    CVXC(upload(pack_conv(host(k).data(), hd, ch, c.res_kernel), &st.c3_w));
+    snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.bias", res);
+    CVXC(upload(host(k), &st.c3_b));
+    snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.weight", res);
+    snprintf(k2, sizeof k2, "decoder.layers.%d.shortcut.conv.weight", res);
+    std::vector<float> mix((size_t)ch * (hd + ch)), mb(ch);
+    for (int n = 0; n < ch; ++n) {
+      memcpy(&mix[(size_t)n * (hd + ch)], host(k).data() + (size_t)n * hd, hd * sizeof(float));
+      memcpy(&mix[(size_t)n * (hd + ch) + hd], host(k2).data() + (size_t)n * ch, ch * sizeof(float));
+    }
+    snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.bias", res);
+    snprintf(k2, sizeof k2, "decoder.layers.%d.shortcut.conv.bias", res);
+    for (int n = 0; n < ch; ++n) mb[n] = host(k)[n] + host(k2)[n];
+    CVXC(upload(mix, &st.mix_w));
+    CVXC(upload(mb, &st.mix_b));
+  }
+  CVXC(upload(pack_conv(host("decoder.layers.15.conv.weight").data(), 1, ch, c.last_kernel), &e->last_w));
+  CVXC(upload(host("decoder.layers.15.conv.bias"), &e->last_b));
+  for (auto& kv : e->w) std::vector<float>().swap(kv.second.v);  // the host copies are not needed any more
+
+  // workspace: the LSTM part holds every frame of a call; the up-sampling part runs over groups of whole utterances of at
+  // most chunk_frames frames (its rows are 320x as many)
+  e->cap_frames = (long)c.max_frames * c.max_batch;
+  e->chunk_frames = std::min(e->cap_frames, std::max<long>(c.max_frames, 8192));
+  e->per_frame = std::max<long>(per_frame, 2 * rate);
+  const size_t F = (size_t)e->cap_frames;
+  CVXC(alloc_f(&e->x0, F * c.hidden));
+  CVXC(alloc_f(&e->xc, F * W));
+  CVXC(alloc_f(&e->gin, F * 4 * W));
+  CVXC(alloc_f(&e->h0, F * W));
+  CVXC(alloc_f(&e->h1, F * W));
+  CVXC(alloc_f(&e->y, F * W));
+  CVXC(alloc_f(&e->c0, (size_t)c.max_batch * W));
+  CVXC(alloc_f(&e->c1, (size_t)c.max_batch * W));
+  CVXC(alloc_f(&e->bufA, (size_t)e->chunk_frames * e->per_frame));
+  CVXC(alloc_f(&e->bufB, (size_t)e->chunk_frames * e->per_frame));
+  CVXC(alloc_f(&e->bufH, (size_t)e->chunk_frames * e->per_frame / 2));
+  e->stage_ints = 2 + F * c.n_codebooks + 3 * (size_t)(c.max_batch + 1);
+  CHIPC(hipMalloc((void**)&e->codes_dev, e->stage_ints * sizeof(int)));
+  CHIPC(hipHostMalloc((void**)&e->codes_host, e->stage_ints * sizeof(int)));
+  CHIPC(hipStreamCreateWithFlags(&e->own, hipStreamNonBlocking));
+  CHIPC(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
+  CHIPC(hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming));
+  CHIPC(hipEventCreateWithFlags(&e->ev_copy, hipEventDisableTiming));
+  CHIPC(hipEventRecord(e->ev_copy, e->own));
+  e->failed = false;
+  e->finalized = true;
+  return VX_OK;
+}
+
+extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* codes, const int32_t* T, int32_t n_q,
+                               float* const* wav_out, void* stream) {
+  if (!e || !codes || !T || !wav_out) return cfail(VX_ERR_ARG, "vx_codec_decode: null argument");
+  const vx_codec_config& c = e->cfg;
+  if (n < 1) return cfail(VX_ERR_ARG, "n = %d utterances", n);
+  if (n > c.max_batch) return cfail(VX_ERR_CAPACITY, "n = %d utterances > max_batch %d", n, c.max_batch);
+  if (n_q < 1 || n_q > c.n_codebooks) return cfail(VX_ERR_ARG, "n_q = %d outside [1, %d]", n_q, c.n_codebooks);
+  long total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!codes[i] || !wav_out[i]) return cfail(VX_ERR_ARG, "utterance %d: null pointer", i);
+    if (T[i] < 1) return cfail(VX_ERR_ARG, "utterance %d: T = %d", i, T[i]);
+    if (T[i] > c.max_frames) return cfail(VX_ERR_CAPACITY, "utterance %d: T = %d > max_frames %d", i, T[i], c.max_frames);
+    total += T[i];
+  }
+  for (int i = 0; i < n; ++i)
+    for (long j = 0; j < (long)n_q * T[i]; ++j)
+      if (codes[i][j] < 0 || codes[i][j] >= c.codebook_size)
+        return cfail(VX_ERR_ARG, "utterance %d: code %lld outside [0, %d)", i, (long long)codes[i][j], c.codebook_size);
+  if (!e->finalized) return cfail(VX_ERR_STATE, "vx_codec_decode before vx_codec_finalize");
+  CDevGuard g(c.device);
+  CHIPC(g.err);
+  // The work runs on the decoder's own stream, ordered after everything already enqueued on `stream`; `stream` waits for it
+  // before the call returns (as the engine's entry points do).  The host waits only for the previous call's staging copy.
+  hipStream_t s = e->own;
+  CHIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
+  CHIPC(hipStreamWaitEvent(s, e->ev_in, 0));
+  const int W = e->W;
+
+  CHIPC(hipEventSynchronize(e->ev_copy));  // the previous call's copy out of the pinned buffer has completed
+  int* hc = e->codes_host;
+  const int MB1 = c.max_batch + 1;
+  hc[0] = n;
+  hc[1] = 0;
+  int* hseg = hc + 2;
+  int* hrel = hseg + MB1;
+  int* hcodes = hrel + 2 * MB1;
+  std::vector<int> seg(n + 1, 0);
+  for (int i = 0; i < n; ++i) seg[i + 1] = seg[i] + T[i];
+  for (int i = 0; i < n; ++i)
+    for (int q = 0; q < n_q; ++q)
+      for (int t = 0; t < T[i]; ++t) hcodes[(size_t)q * total + seg[i] + t] = (int)codes[i][(size_t)q * T[i] + t];
+  memcpy(hseg, seg.data(), (n + 1) * sizeof(int));
+  struct Group { int u0, u1, off; };
+  std::vector<Group> groups;
+  int used = 0;
+  for (int u0 = 0; u0 < n;) {
+    int u1 = u0 + 1;
+    while (u1 < n && (long)seg[u1 + 1] - seg[u0] <= e->chunk_frames) ++u1;
+    groups.push_back(Group{u0, u1, used});
+    for (int u = u0; u <= u1; ++u) hrel[used++] = seg[u] - seg[u0];
+    u0 = u1;
+  }
+  const size_t ints = 2 + 3 * (size_t)MB1 + (size_t)n_q * total;
+  CHIPC(hipMemcpyAsync(e->codes_dev, hc, ints * sizeof(int), hipMemcpyHostToDevice, s));
+  CHIPC(hipEventRecord(e->ev_copy, s));
+  int* dmeta = e->codes_dev;
+  const int* dseg = e->codes_dev + 2;
+  const int* drel = dseg + MB1;
+  const int* dcodes = drel + 2 * MB1;
+
+  const long e0 = total * c.hidden;
+  codec_rvq_rows<<<(unsigned)((e0 + 255) / 256), 256, 0, s>>>(dcodes, e->cb, e->x0, total, n_q, c.codebook_size, c.codebook_dim);
+  CHIPC(hipGetLastError());
+  CVXC(run_conv(e->x0, e->c0_w, e->c0_b, e->xc, total, c.hidden, W, c.kernel, 0, dseg, n, 1, s));
+  CVXC(run_lstm(e->lstm, e->xc, e->gin, e->h0, e->h1, e->c0, e->c1, e->y, W, c.lstm_layers, dseg, seg.data(), n, s,
+                (c.flags & VX_CODEC_LSTM_GRAPH) ? &e->chain : nullptr, dmeta));
+
+  for (const Group& gr : groups) {
+    const int ns = gr.u1 - gr.u0;
+    const int* sg = drel + gr.off;
+    const long frames = seg[gr.u1] - seg[gr.u0];
+    const float* x = e->y + (size_t)seg[gr.u0] * W;
+    long rate = 1;
+    for (const Stage& st : e->stages) {
+      CVXC(run_convtr(x, st.up_w, st.up_b, e->bufA, frames * rate, st.cin, st.cout, st.stride, 1, sg, ns, (int)rate, s));
+      rate *= st.stride;
+      const int ch = st.cout, hd = ch / 2;
+      CVXC(run_conv(e->bufA, st.c3_w, st.c3_b, e->bufH, frames * rate, ch, hd, c.res_kernel, 1, sg, ns, (int)rate, s));
+      CodecGemmArgs a{};
+      a.part[0] = CodecPart{e->bufH, hd, 1, CODEC_PAD_ZERO, 1};
+      a.part[1] = CodecPart{e->bufA, ch, 1, CODEC_PAD_ZERO, 0};
+      a.nparts = 2;
+      a.W = st.mix_w; a.bias = st.mix_b; a.out = e->bufB; a.M = frames * rate; a.N = ch; a.K = hd + ch;
+      a.seg = sg; a.nseg = ns; a.rate = (int)rate;
+      CVXC(launch_gemm(a, s));
+      x = e->bufB;
+    }
+    const int ch = e->stages.back().cout;
+    CVXC(run_conv(e->bufB, e->last_w, e->last_b, e->bufH, frames * rate, ch, 1, c.last_kernel, 1, sg, ns, (int)rate, s));
+    for (int u = gr.u0; u < gr.u1; ++u)
+      CHIPC(hipMemcpyAsync(wav_out[u], e->bufH + (size_t)(seg[u] - seg[gr.u0]) * rate, (size_t)T[u] * rate * sizeof(float),
+                           hipMemcpyDeviceToDevice, s));
+  }
+  CHIPC(hipEventRecord(e->ev_out, s));
+  CHIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
+  return VX_OK;
+}
+
+// ---- op-level test entries: x / out device fp32 rows, weights and biases HOST fp32 in torch's layouts (packed here exactly as
+// vx_codec_finalize packs them), seg_frames HOST nseg + 1 frame offsets.  Synchronous. ----------------------------------------
+namespace {
+struct OpSeg {
+  int* d = nullptr;
+  ~OpSeg() { (void)hipFree(d); }
+  int init(const int32_t* seg, int nseg) {
+    CHIPC(hipMalloc((void**)&d, (nseg + 1) * sizeof(int)));
+    CHIPC(hipMemcpy(d, seg, (nseg + 1) * sizeof(int), hipMemcpyHostToDevice));
+    return VX_OK;
+  }
+};
+struct OpBuf {
+  float* d = nullptr;
+  ~OpBuf() { (void)hipFree(d); }
+};
+}  // namespace
+
+extern "C" int vx_op_codec_conv(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out, int32_t k,
+                                int32_t elu, int32_t nseg, const int32_t* seg_frames, int32_t rate, void* stream) {
+  if (!x || !w || !out || c_in < 1 || c_out < 1 || k < 1 || k > 15 || rate < 1) return cfail(VX_ERR_ARG, "vx_op_codec_conv: bad argument");
+  CVXC(check_segs(seg_frames, nseg));
+  hipStream_t s = (hipStream_t)stream;
+  OpSeg sg;
+  OpBuf wp, bp;
+  CVXC(sg.init(seg_frames, nseg));
+  CVXC(upload(pack_conv(w, c_out, c_in, k), &wp.d));
+  if (bias) CVXC(upload(std::vector<float>(bias, bias + c_out), &bp.d));
+  CVXC(run_conv(x, wp.d, bp.d, out, (long)seg_frames[nseg] * rate, c_in, c_out, k, elu, sg.d, nseg, rate, s));
+  CHIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+extern "C" int vx_op_codec_convtr(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out,
+                                  int32_t stride, int32_t elu, int32_t nseg, const int32_t* seg_frames, int32_t rate, void* stream) {
+  if (!x || !w || !out || c_in < 1 || c_out < 1 || stride < 1 || rate < 1) return cfail(VX_ERR_ARG, "vx_op_codec_convtr: bad argument");
+  CVXC(check_segs(seg_frames, nseg));
+  hipStream_t s = (hipStream_t)stream;
+  OpSeg sg;
+  OpBuf wp, bp;
+  CVXC(sg.init(seg_frames, nseg));
+  CVXC(upload(pack_convtr(w, c_in, c_out, stride), &wp.d));
+  if (bias) {
+    std::vector<float> rep((size_t)stride * c_out);
+    for (int p = 0; p < stride; ++p) memcpy(&rep[(size_t)p * c_out], bias, c_out * sizeof(float));
+    CVXC(upload(rep, &bp.d));
+  }
+  CVXC(run_convtr(x, wp.d, bp.d, out, (long)seg_frames[nseg] * rate, c_in, c_out, stride, elu, sg.d, nseg, rate, s));
+  CHIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+extern "C" int vx_op_codec_lstm(const float* x, const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
+                                const float* const* b_hh, float* y, int32_t width, int32_t layers, int32_t nseg,
+                                const int32_t* seg_frames, void* stream) {
+  if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !y) return cfail(VX_ERR_ARG, "vx_op_codec_lstm: null argument");
+  if (layers < 1 || layers > 2 || !lstm_width_ok(width)) return cfail(VX_ERR_UNSUPPORTED, "vx_op_codec_lstm: width %d, layers %d", width, layers);
+  CVXC(check_segs(seg_frames, nseg));
+  hipStream_t s = (hipStream_t)stream;
+  OpSeg sg;
+  CVXC(sg.init(seg_frames, nseg));
+  LstmDev d;
+  int r = pack_lstm(w_ih, w_hh, b_ih, b_hh, width, layers, &d);
+  const size_t rows = seg_frames[nseg];
+  OpBuf gin, h0, h1, c0, c1;
+  if (r == VX_OK) r = alloc_f(&gin.d, rows * 4 * width);
+  if (r == VX_OK) r = alloc_f(&h0.d, rows * width);
+  if (r == VX_OK) r = alloc_f(&h1.d, rows * width);
+  if (r == VX_OK) r = alloc_f(&c0.d, (size_t)nseg * width);
+  if (r == VX_OK) r = alloc_f(&c1.d, (size_t)nseg * width);
+  if (r == VX_OK) r = run_lstm(d, x, gin.d, h0.d, h1.d, c0.d, c1.d, y, width, layers, sg.d, seg_frames, nseg, s);
+  if (r == VX_OK && hipStreamSynchronize(s) != hipSuccess) r = cfail(VX_ERR_HIP, "vx_op_codec_lstm: synchronise failed");
+  free_lstm(d);
+  return r;
+}

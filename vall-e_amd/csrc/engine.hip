@@ -53,6 +53,8 @@ static int fail(int code, const char* fmt, ...) {
   } while (0)
 
 extern "C" const char* vx_last_error(void) { return g_err.c_str(); }
+// codec.hip (the vx_codec_* entry points) reports through the same thread-local message; not part of the C ABI
+extern "C" __attribute__((visibility("hidden"))) void vx_internal_set_error(const char* msg) { g_err = msg ? msg : ""; }
 
 // Every entry point runs on the engine's device and leaves the caller's current device as it found it.
 struct DevGuard {

@@ -21,6 +21,7 @@ VX_FLAG_TRACE_LOGITS, VX_FLAG_NO_GRAPH, VX_FLAG_SIMPLE_ROWS, VX_FLAG_POST_NORM, 
 VX_FLAG_KV_FP8 = 64
 KV_CACHES = ("bf16", "fp8")  # storage of the batched decode's slot caches (VX_FLAG_KV_FP8)
 VX_ADMIT_BATCHED, VX_ADMIT_PER_SLOT = 0, 1
+VX_CODEC_LSTM_GRAPH = 1
 BE_QKV, BE_RELU, BE_PARTIAL, BE_LOGITS, BE_LOGITS_MAP, BE_BIAS = range(6)  # bgemm_kernel epilogues (csrc/batch_kernels.hpp)
 STOP_REASONS = {0: "none", 1: "eos_argmax", 2: "eos_sample", 3: "length", 4: "max_new"}
 
@@ -37,6 +38,12 @@ class VxDecodeParams(C.Structure):
         ("exp_noise", C.c_void_p), ("noise_rows", C.c_int64), ("seed", C.c_uint64),
         ("forced", C.c_void_p), ("n_forced", C.c_int32), ("top_p", C.c_float),
     ]
+
+
+class VxCodecConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("hidden", C.c_int32), ("filters", C.c_int32), ("ratios", C.c_int32 * 4)] + \
+               [(n, C.c_int32) for n in ("kernel", "last_kernel", "res_kernel", "n_codebooks", "codebook_size", "codebook_dim",
+                                         "lstm_layers", "max_frames", "max_batch", "device", "flags")]
 
 
 class VxError(RuntimeError):
@@ -96,6 +103,17 @@ _SIGS = {
     "vx_op_sample_topp": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
                                     C.c_void_p]),
     "vx_op_convert_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # EnCodec decoder (codec.py)
+    "vx_codec_create": (C.c_int, [C.POINTER(VxCodecConfig), C.POINTER(C.c_void_p)]),
+    "vx_codec_destroy": (None, [C.c_void_p]),
+    "vx_codec_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "vx_codec_finalize": (C.c_int, [C.c_void_p]),
+    "vx_codec_decode": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32,
+                                  C.POINTER(C.c_void_p), C.c_void_p]),
+    "vx_op_codec_conv": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
+    "vx_op_codec_convtr": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
+    "vx_op_codec_lstm": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(C.c_int32), C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so
