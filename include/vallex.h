@@ -324,17 +324,25 @@ int vx_op_sample_topp(const float* logits, int32_t V, int32_t top_k, float tempe
                       int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 int vx_op_convert_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);
 
-/* ---- EnCodec-24 kHz decoder: codec tokens -> waveform (what valle/bin/infer.py:251-253 does with VALLE.inference's result
- * through valle/data/tokenizer.py:241-242).  A handle of its own: the codec has its own weights and lifetime and is usable
- * without a vx_engine.  Decode only; fp32 storage and accumulation.  Geometry as transformers' EncodecConfig: the decoder is
+/* ---- EnCodec-24 kHz codec: codec tokens -> waveform (what valle/bin/infer.py:251-253 does with VALLE.inference's result
+ * through valle/data/tokenizer.py:241-242) and, on a handle created with VX_CODEC_ENCODER, prompt waveform -> codec tokens
+ * (tokenize_audio, valle/data/tokenizer.py:238-254).  A handle of its own: the codec has its own weights and lifetime and is
+ * usable without a vx_engine.  fp32 storage and accumulation.  Geometry as transformers' EncodecConfig: the decoder is
  * conv(hidden -> 16 filters, kernel) -> LSTM + skip -> 4 x [ELU, transposed conv (k = 2 ratio, stride ratio, channels halved),
  * residual block (res_kernel, hidden width C / 2)] -> ELU -> conv(filters -> 1, last_kernel); stride-1 convolutions are causal
- * with reflect padding, weight norm is folded by the caller. */
+ * with reflect padding, weight norm is folded by the caller.  The encoder is its mirror: conv(1 -> filters,
+ * kernel) -> 4 x [residual block, ELU, strided conv (k = 2 ratio, stride ratio, channels doubled; ratios in reverse order)] ->
+ * LSTM + skip -> ELU -> conv(16 filters -> hidden, last_kernel) -> residual vector quantiser (nearest code per stage, first
+ * index on ties).  Every convolution pads k - stride on the left and, on the right, what completes the last window (output
+ * length ceil(L / stride)), both reflect. */
 typedef struct vx_codec vx_codec;
 enum vx_codec_flags {
-  VX_CODEC_LSTM_GRAPH = 1 /* replay the LSTM's time steps as a captured linear chain instead of launching them one by one: the
+  VX_CODEC_LSTM_GRAPH = 1, /* replay the LSTM's time steps as a captured linear chain instead of launching them one by one: the
                              same kernels and results; measured slower at one utterance and equal at 32 / 64,
                              so it is off by default */
+  VX_CODEC_ENCODER = 2    /* the handle also encodes: vx_codec_finalize needs the encoder.* tensors as well and allocates the
+                             encoder's staging; codebook_size must be a multiple of 32 and codebook_dim a multiple of 8, <= 128.
+                             Without the flag nothing changes: no encoder tensor is known and vx_codec_encode is refused */
 };
 typedef struct vx_codec_config {
   int32_t struct_size;   /* = sizeof(vx_codec_config) */
@@ -359,7 +367,9 @@ int vx_codec_create(const vx_codec_config* cfg, vx_codec** out);
 void vx_codec_destroy(vx_codec* c);
 /* Keys: the local EncodecModel's state_dict names with weight norm removed - decoder.layers.N.conv.weight / .bias,
  * decoder.layers.N.block.1|3.conv.*, decoder.layers.N.shortcut.conv.*, decoder.layers.1.lstm.weight_ih_l0 ... bias_hh_l1,
- * quantizer.layers.q.codebook.embed - host fp32 in torch's layouts.  Unknown key or wrong shape: VX_ERR_WEIGHTS. */
+ * quantizer.layers.q.codebook.embed - host fp32 in torch's layouts; with VX_CODEC_ENCODER also encoder.layers.N.conv.weight /
+ * .bias (N = 0, 3, 6, 9, 12, 15), encoder.layers.N.block.1|3.conv.*, encoder.layers.N.shortcut.conv.* (N = 1, 4, 7, 10) and
+ * encoder.layers.13.lstm.*.  Unknown key or wrong shape: VX_ERR_WEIGHTS. */
 int vx_codec_set_weight(vx_codec* c, const char* key, const float* data, const int64_t* shape, int32_t ndim);
 /* Packs and uploads the weights, allocates the workspace.  A missing tensor: VX_ERR_WEIGHTS. */
 int vx_codec_finalize(vx_codec* c);
@@ -371,6 +381,23 @@ int vx_codec_finalize(vx_codec* c);
  * VX_ERR_STATE to finalize and decode: destroy it. */
 int vx_codec_decode(vx_codec* c, int32_t n, const int64_t* const* codes, const int32_t* T, int32_t n_q, float* const* wav_out,
                     void* stream);
+
+/* n utterances: wav[i] DEVICE fp32, n_samples[i] mono 24 kHz samples (any length >= 1, not only multiples of the hop);
+ * codes_out[i] DEVICE int64 (n_q, T_i), T_i = ceil(n_samples[i] / hop).  The utterances are encoded as one ragged batch and every
+ * one gets bitwise the codes it gets alone.  Checked before any HIP call, in this order (the first that applies is returned):
+ * null arguments -> VX_ERR_ARG; a handle without VX_CODEC_ENCODER -> VX_ERR_STATE; n < 1 -> VX_ERR_ARG; n > max_batch ->
+ * VX_ERR_CAPACITY; n_q outside [1, n_codebooks] -> VX_ERR_ARG; then per utterance in order: a null pointer or n_samples[i] < 1
+ * -> VX_ERR_ARG, n_samples[i] > max_frames * hop -> VX_ERR_CAPACITY; last a handle that is not finalised -> VX_ERR_STATE.
+ * Non-finite samples are not
+ * checked (their codes are unspecified but in range).  Stream ordering as vx_codec_decode. */
+int vx_codec_encode(vx_codec* c, int32_t n, const float* const* wav, const int32_t* n_samples, int32_t n_q, int64_t* const* codes_out,
+                    void* stream);
+
+/* Test-only (parity tests, like the vx_op_* entries below): the quantiser's input of the last vx_codec_encode on this handle
+ * ([rows][hidden] fp32, the call's frames in utterance order) copied to `out` (DEVICE).  rows above that call's frame count, or
+ * any rows when no encode has run since finalize or a vx_codec_decode ran after it (it reuses the buffer): VX_ERR_ARG.  Not an
+ * encoder handle or not finalised: VX_ERR_STATE. */
+int vx_codec_last_embeddings(vx_codec* c, float* out, int64_t rows, void* stream);
 
 /* The codec's kernels on caller data (parity tests).  x / out: device fp32 time-major rows; w / bias: HOST fp32 in torch's
  * layouts, packed as vx_codec_finalize packs them; seg_frames: HOST nseg + 1 frame offsets (seg_frames[0] = 0) of the
@@ -385,6 +412,16 @@ int vx_op_codec_convtr(const float* x, const float* w, const float* bias, float*
 int vx_op_codec_lstm(const float* x, const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
                      const float* const* b_hh, float* y, int32_t width, int32_t layers, int32_t nseg, const int32_t* seg_frames,
                      void* stream);
+
+/* Encoder side.  conv_strided: x device rows of nseg utterances with HOST row offsets seg_rows_in (rate 1), w HOST (c_out, c_in,
+ * k); utterance i gives ceil(len_i / stride) output rows, concatenated.  stride > 1 needs k = 2 stride; stride = 1 is the causal
+ * convolution, and c_in = 1 there runs the first convolution's kernel (no ELU).  rvq_encode: emb device [rows][dim], codebooks
+ * HOST [n_q][size][dim], codes_out DEVICE int32 [n_q][rows]: per stage the first index of the smallest |e|^2 - 2 r.e, then
+ * r -= e.  Synchronous. */
+int vx_op_codec_conv_strided(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out, int32_t k,
+                             int32_t stride, int32_t elu, int32_t nseg, const int32_t* seg_rows_in, void* stream);
+int vx_op_codec_rvq_encode(const float* emb, const float* codebooks, int32_t* codes_out, int64_t rows, int32_t n_q, int32_t size,
+                           int32_t dim, void* stream);
 
 #ifdef __cplusplus
 }

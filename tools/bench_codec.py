@@ -9,7 +9,12 @@ wall times, each ending in a device synchronise.  Implementations: `hip` (the de
 `hip_graph` (the same decoder with the steps replayed as the captured chain), `torch_gpu` (stock conv1d / conv_transpose1d / nn.LSTM, one
 utterance after the other), `torch_gpu_batched` (the same ops on the whole (B, C, L) batch in one call: every utterance of a
 point has the same length, so padding rules are per row as they should be), `torch_host` (16 threads, two utterances scaled to
-B).  The yardsticks are tests/encodec_ref's formula with nn.LSTM in place of its Python loop."""
+B).  The yardsticks are tests/encodec_ref's formula with nn.LSTM in place of its Python loop.
+
+    python tools/bench_codec.py --encode [--points 1x225,32x225,64x225]   # prompt waveform -> codes, T frames = 320 T samples
+
+`--encode` times `encode_batch` (device waveforms in, device codes out) against tests/encodec_enc_ref's formula on stock torch ops
+(strided conv1d, nn.LSTM, the quantiser's distance matrix by matmul and argmax) per utterance, in one batched call, and on the host."""
 import argparse
 import json
 import os
@@ -67,13 +72,123 @@ def torch_decoder(sd, geo, device):
     return run
 
 
+def torch_encoder(sd, geo, device):
+    """Stock-op encoder on `device` in fp32, (B, 1, L) -> (B, n_q, T); L a multiple of the hop here (no right pad)."""
+    import torch
+    import torch.nn.functional as F
+
+    import encodec_enc_ref as E
+    import encodec_ref as R
+
+    P = {k: v.to(device) for k, v in R.fold_weight_norm(sd, torch.float32).items()}
+    res, down, li, last = E.enc_layer_index(geo)
+    lstm = torch.nn.LSTM(geo.width, geo.width, geo.lstm_layers).to(device)
+    for n, p in lstm.named_parameters():
+        p.data.copy_(P[f"encoder.layers.{li}.lstm." + n])
+    cbs = [P[f"quantizer.layers.{q}.codebook.embed"] for q in range(geo.n_codebooks)]
+    sq = [c.pow(2).sum(1)[None] for c in cbs]
+
+    def conv(x, w, b, stride=1):
+        k = w.shape[-1]
+        left = k - stride
+        extra = -(-x.shape[-1] // stride) * stride - x.shape[-1]
+        if left or extra:
+            ext = max(0, max(left, extra) - x.shape[-1] + 1)
+            xp = F.pad(F.pad(x, (0, ext)), (left, extra), mode="reflect")
+            x = xp[..., : xp.shape[-1] - ext]
+        return F.conv1d(x, w, b, stride=stride)
+
+    @torch.no_grad()
+    def run(wav):
+        x = conv(wav.to(device), P["encoder.layers.0.conv.weight"], P["encoder.layers.0.conv.bias"])
+        for i, r in enumerate(E.enc_ratios(geo)):
+            p = f"encoder.layers.{res[i]}."
+            h = conv(F.elu(x), P[p + "block.1.conv.weight"], P[p + "block.1.conv.bias"])
+            h = conv(F.elu(h), P[p + "block.3.conv.weight"], P[p + "block.3.conv.bias"])
+            x = conv(x, P[p + "shortcut.conv.weight"], P[p + "shortcut.conv.bias"]) + h
+            x = conv(F.elu(x), P[f"encoder.layers.{down[i]}.conv.weight"], P[f"encoder.layers.{down[i]}.conv.bias"], r)
+        x = lstm(x.permute(2, 0, 1))[0].permute(1, 2, 0) + x
+        x = conv(F.elu(x), P[f"encoder.layers.{last}.conv.weight"], P[f"encoder.layers.{last}.conv.bias"])
+        B, D, T = x.shape
+        r = x.transpose(1, 2).reshape(B * T, D)
+        out = []
+        for cb, s2 in zip(cbs, sq):
+            idx = (-(r.pow(2).sum(1, keepdim=True) - 2 * r @ cb.T + s2)).max(dim=1).indices
+            out.append(idx)
+            r = r - cb[idx]
+        return torch.stack(out).reshape(len(cbs), B, T).transpose(0, 1)
+
+    return run
+
+
+def main_encode(args):
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build()
+    import encodec_enc_ref as E
+    from valle_amd.codec import EncodecDecoder
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_codec.py measures on the GPU; none found")
+    torch.set_num_threads(16)
+    points = [tuple(int(v) for v in p.split("x")) for p in args.points.split(",")]
+    sd = E.make_enc_weights(E.FULL, 3)
+    enc = EncodecDecoder(max_frames=max(t for _, t in points), max_batch=max(b for b, _ in points), encoder=True)
+    enc.load_state_dict(sd)
+    enc.to("cuda:0")
+    gpu_ref = torch_encoder(sd, E.FULL, "cuda:0")
+    host_ref = torch_encoder(sd, E.FULL, "cpu")
+    sync = torch.cuda.synchronize
+
+    def timed(fn):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return time.perf_counter() - t0
+
+    out = {"bench": "codec_encode", "reps": args.reps, "host_threads": torch.get_num_threads(), "points": []}
+    for B, T in points:
+        host_wavs = [E.make_wave(320 * T, 200 + b) for b in range(B)]
+        wavs = [w.to("cuda:0") for w in host_wavs]
+        stacked = torch.cat(wavs)
+        impls = {"hip": lambda: enc.encode_batch(wavs)}
+        row = {"B": B, "T": T, "samples": 320 * T}
+        if not args.only_hip:
+            impls["torch_gpu"] = lambda: [gpu_ref(w) for w in wavs]
+            impls["torch_gpu_batched"] = lambda: gpu_ref(stacked)
+            if not args.skip_host:
+                impls["torch_host"] = lambda: [host_ref(w) for w in host_wavs[:min(B, 2)]]
+            ours = torch.cat(enc.encode_batch(wavs))
+            row["hip_vs_torch_gpu_code_agreement"] = float((ours == gpu_ref(stacked)).double().mean())
+        for fn in impls.values():
+            timed(fn)
+        times = {k: [] for k in impls}
+        for _ in range(args.reps):
+            for k, fn in impls.items():
+                times[k].append(timed(fn))
+        for k, v in times.items():
+            scale = B / min(B, 2) if k == "torch_host" else 1.0
+            row[k + "_ms"] = round(1e3 * statistics.median(v) * scale, 3)
+            row[k + "_min_ms"] = round(1e3 * min(v) * scale, 3)
+        out["points"].append(row)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
-    ap.add_argument("--points", default="1x753,32x753,64x1505")
+    ap.add_argument("--points", default=None, help="BxT,...; default 1x753,32x753,64x1505, with --encode 1x225,32x225,64x225")
+    ap.add_argument("--encode", action="store_true", help="time the encoder (waveform -> codes) instead of the decoder")
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--only-hip", action="store_true", help="time the HIP decoder alone (for a kernel trace)")
     args = ap.parse_args()
+    if args.points is None:
+        args.points = "1x225,32x225,64x225" if args.encode else "1x753,32x753,64x1505"
+    if args.encode:
+        return main_encode(args)
     import torch
 
     import __graft_entry__ as ge

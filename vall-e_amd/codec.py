@@ -1,10 +1,14 @@
-"""EnCodec-24 kHz decoder on the GPU: codec tokens -> waveform, the step `valle/bin/infer.py:251-253` takes right after
-`VALLE.inference` (through `valle/data/tokenizer.py:241-242`).  Decode only; the encoder, resampling and file I/O stay on the
-host.  The kernels are csrc/codec_kernels.hpp behind `vx_codec_*` (include/vallex.h); there is no CPU fallback.
+"""EnCodec-24 kHz codec on the GPU.  Decode: codec tokens -> waveform, the step `valle/bin/infer.py:251-253` takes right after
+`VALLE.inference` (through `valle/data/tokenizer.py:241-242`).  Encode (`encoder=True`): prompt waveform -> codec tokens, the
+step `tokenize_audio` takes before it (`valle/data/tokenizer.py:238-254`), at 6 kbps (8 codebooks), mono, one chunk, no
+normalisation.  Resampling and file I/O stay on the host.  The kernels are csrc/codec_kernels.hpp behind `vx_codec_*`
+(include/vallex.h); there is no CPU fallback.
 
-    dec = EncodecDecoder(max_frames=2048)
-    dec.load_state_dict(encodec_model.state_dict(), strict=False)   # decoder.* and quantizer.* keys are taken
-    wav = dec.to("cuda").decode(codes.transpose(2, 1))              # codes (1, T, 8) from VALLE.inference -> (1, 1, 320 T)
+    dec = EncodecDecoder(max_frames=2048, encoder=True)
+    dec.load_state_dict(encodec_model.state_dict(), strict=False)   # decoder.*, encoder.* and quantizer.* keys are taken
+    dec.to("cuda")
+    codes = dec.encode(prompt_wav)                                  # (1, 1, L) float32 at 24 kHz -> (1, 8, ceil(L / 320)) int64
+    wav = dec.decode(frames.transpose(2, 1))                        # frames (1, T, 8) from VALLE.inference -> (1, 1, 320 T)
 """
 from __future__ import annotations
 
@@ -43,8 +47,9 @@ class CodecConfig:
         return int(np.prod(self.ratios))
 
 
-def expected_keys(cfg: CodecConfig) -> "OrderedDict[str, Tuple[int, ...]]":
-    """Key -> shape with weight norm removed (the names `vx_codec_set_weight` takes)."""
+def expected_keys(cfg: CodecConfig, encoder: bool = False) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Key -> shape with weight norm removed (the names `vx_codec_set_weight` takes): the decoder and the codebooks, then with
+    `encoder` the encoder's (its ratios are the decoder's reversed)."""
     W = cfg.width
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
     s["decoder.layers.0.conv.weight"] = (W, cfg.hidden, cfg.kernel)
@@ -70,14 +75,37 @@ def expected_keys(cfg: CodecConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     s[f"decoder.layers.{last}.conv.bias"] = (1,)
     for q in range(cfg.n_codebooks):
         s[f"quantizer.layers.{q}.codebook.embed"] = (cfg.codebook_size, cfg.hidden)
+    if not encoder:
+        return s
+    c = cfg.filters
+    s["encoder.layers.0.conv.weight"] = (c, 1, cfg.kernel)
+    s["encoder.layers.0.conv.bias"] = (c,)
+    for i, r in enumerate(reversed(cfg.ratios)):
+        res, down = 1 + 3 * i, 3 + 3 * i
+        p = f"encoder.layers.{res}."
+        s[p + "block.1.conv.weight"] = (c // 2, c, cfg.res_kernel)
+        s[p + "block.1.conv.bias"] = (c // 2,)
+        s[p + "block.3.conv.weight"] = (c, c // 2, 1)
+        s[p + "block.3.conv.bias"] = (c,)
+        s[p + "shortcut.conv.weight"] = (c, c, 1)
+        s[p + "shortcut.conv.bias"] = (c,)
+        s[f"encoder.layers.{down}.conv.weight"] = (2 * c, c, 2 * r)
+        s[f"encoder.layers.{down}.conv.bias"] = (2 * c,)
+        c *= 2
+    li = 1 + 3 * len(cfg.ratios)
+    for l in range(cfg.lstm_layers):
+        for n, shp in (("weight_ih", (4 * W, W)), ("weight_hh", (4 * W, W)), ("bias_ih", (4 * W,)), ("bias_hh", (4 * W,))):
+            s[f"encoder.layers.{li}.lstm.{n}_l{l}"] = shp
+    s[f"encoder.layers.{li + 2}.conv.weight"] = (cfg.hidden, W, cfg.last_kernel)
+    s[f"encoder.layers.{li + 2}.conv.bias"] = (cfg.hidden,)
     return s
 
 
-def pack_state_dict(cfg: CodecConfig, sd: Dict[str, torch.Tensor], strict: bool = True):
+def pack_state_dict(cfg: CodecConfig, sd: Dict[str, torch.Tensor], strict: bool = True, encoder: bool = False):
     """Either accepted layout -> (fp32 tensors under the plain names, missing, unexpected).  Weight norm (w = g v / |v|, the norm
     over all dimensions but the first) is folded in fp64 and rounded once.  With strict=False keys outside the decoder and
-    the loaded codebooks (the encoder, EMA statistics, further codebooks) are ignored."""
-    want = expected_keys(cfg)
+    the loaded codebooks (the encoder unless `encoder`, EMA statistics, further codebooks) are ignored."""
+    want = expected_keys(cfg, encoder)
     out: Dict[str, torch.Tensor] = {}
     used = set()
     for k, shp in want.items():
@@ -106,15 +134,18 @@ def pack_state_dict(cfg: CodecConfig, sd: Dict[str, torch.Tensor], strict: bool 
 
 
 class EncodecDecoder:
-    """codes -> 24 kHz waveform in HIP.  `max_frames` / `max_batch` are capacities (frames per utterance, utterances per
-    `decode_batch` call; the workspace is allocated for them on first use)."""
+    """codes -> 24 kHz waveform in HIP and, with `encoder=True`, waveform -> codes on the same handle.  `max_frames` / `max_batch`
+    are capacities (frames per utterance, i.e. `max_frames * hop` samples to encode, and utterances per `decode_batch` /
+    `encode_batch` call; the workspace is allocated for them on first use)."""
 
-    def __init__(self, config: Optional[CodecConfig] = None, max_frames: int = 2048, max_batch: int = 1, lstm_graph: bool = False):
+    def __init__(self, config: Optional[CodecConfig] = None, max_frames: int = 2048, max_batch: int = 1, lstm_graph: bool = False,
+                 encoder: bool = False):
         self.cfg = config or CodecConfig()
         if len(self.cfg.ratios) != 4:
             raise NotImplementedError("four up-sampling stages")
         self.max_frames, self.max_batch = int(max_frames), int(max_batch)
         self.lstm_graph = bool(lstm_graph)  # LSTM steps replayed as a captured chain instead of plain launches (not faster)
+        self.encoder = bool(encoder)
         self.device = torch.device("cpu")
         self._sd: Dict[str, torch.Tensor] = {}
         self._h = None
@@ -123,16 +154,17 @@ class EncodecDecoder:
     # ---- weights ------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accepts the local EncodecModel's names (`decoder.layers.N.conv.parametrizations.weight.original0/1`, the LSTM's torch
-        names, `quantizer.layers.q.codebook.embed`) and the same names with weight norm removed (`...conv.weight`)."""
+        names, `quantizer.layers.q.codebook.embed`; with `encoder=True` the `encoder.layers.N...` names too) and the same names
+        with weight norm removed (`...conv.weight`)."""
         from .models import _IncompatibleKeys
 
-        packed, missing, unexpected = pack_state_dict(self.cfg, state_dict, strict)
+        packed, missing, unexpected = pack_state_dict(self.cfg, state_dict, strict, self.encoder)
         self._sd.update(packed)
         self._drop()
         return _IncompatibleKeys(missing, unexpected)
 
     def state_dict(self):
-        return OrderedDict((k, self._sd[k]) for k in expected_keys(self.cfg) if k in self._sd)
+        return OrderedDict((k, self._sd[k]) for k in expected_keys(self.cfg, self.encoder) if k in self._sd)
 
     def to(self, device):
         self.device = torch.device(device)
@@ -169,7 +201,7 @@ class EncodecDecoder:
             c.ratios[i] = r
         c.n_codebooks, c.codebook_size, c.codebook_dim, c.lstm_layers = g.n_codebooks, g.codebook_size, g.hidden, g.lstm_layers
         c.max_frames, c.max_batch, c.device = self.max_frames, self.max_batch, self.device.index or 0
-        c.flags = _e.VX_CODEC_LSTM_GRAPH if self.lstm_graph else 0
+        c.flags = (_e.VX_CODEC_LSTM_GRAPH if self.lstm_graph else 0) | (_e.VX_CODEC_ENCODER if self.encoder else 0)
         return c
 
     def handle(self, finalize: bool = True):
@@ -227,10 +259,50 @@ class EncodecDecoder:
         return self.decode_batch([codes])[0]
 
 
+    # ---- encode -------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def encode_batch(self, wavs: Sequence[torch.Tensor], n_q: Optional[int] = None) -> List[torch.Tensor]:
+        """wavs[i]: (L_i,), (1, L_i) or (1, 1, L_i) float32 mono at 24 kHz, any L_i >= 1 -> [(1, n_q, ceil(L_i / hop)) int64 on the
+        device], all utterances in one ragged launch sequence (each bitwise what it gets alone)."""
+        if not self.encoder:
+            raise RuntimeError("this EncodecDecoder was built without encoder=True")
+        if self.device.type != "cuda":
+            raise RuntimeError("valle_amd.EncodecDecoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        n_q = self.cfg.n_codebooks if n_q is None else int(n_q)
+        ws = []
+        for w in wavs:
+            assert w.dtype == torch.float32 and w.numel() == w.shape[-1], "one mono float32 waveform per entry"
+            ws.append(w.detach().reshape(-1).to(self.device).contiguous())
+        outs = [torch.empty((1, n_q, -(-w.numel() // self.cfg.hop)), dtype=torch.int64, device=self.device) for w in ws]
+        self._encode_raw([w.data_ptr() for w in ws], [w.numel() for w in ws], n_q, [o.data_ptr() for o in outs])
+        return outs
+
+    def _encode_raw(self, wav_ptrs, lengths, n_q, out_ptrs, finalize: bool = True):
+        """vx_codec_encode on raw pointers (the argument checks run before any device work)."""
+        n = len(wav_ptrs)
+        lib = _e.load_library()
+        h = self.handle(finalize)
+        wp = (C.c_void_p * n)(*wav_ptrs)
+        L = (C.c_int32 * n)(*lengths)
+        op = (C.c_void_p * n)(*out_ptrs)
+        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
+        _e._check(lib.vx_codec_encode(h, n, wp, L, n_q, op, stream))
+
+    def last_embeddings(self, frames: int) -> torch.Tensor:
+        """(frames, hidden) float32: the quantiser's input of the last encode call, its utterances concatenated (parity tests)."""
+        out = torch.empty((frames, self.cfg.hidden), dtype=torch.float32, device=self.device)
+        _e._check(_e.load_library().vx_codec_last_embeddings(self.handle(), out.data_ptr(), frames, _e.current_stream_ptr(self.device)))
+        return out
+
+    def encode(self, wav: torch.Tensor, n_q: Optional[int] = None) -> torch.Tensor:
+        """(1, 1, L), (1, L) or (L,) float32 -> (1, n_q, ceil(L / hop)) int64 on the device."""
+        return self.encode_batch([wav], n_q)[0]
+
+
 class AudioTokenizer:
-    """The decode half of the reference's `valle.data.tokenizer.AudioTokenizer` (tokenizer.py:241-242) on the GPU:
-    `decode([(frames, None)])` with frames (B, n_q, T), as `infer.py:251-253` passes `encoded_frames.transpose(2, 1)`.
-    `encode` is out of scope (the prompt is tokenised on the host as before)."""
+    """The reference's `valle.data.tokenizer.AudioTokenizer` (tokenizer.py:238-254) on the GPU: `encode(wav)` with wav (B, 1, L)
+    returns `[(codes (B, n_q, T), None)]` as `tokenize_audio` hands it on (needs `EncodecDecoder(encoder=True)`), and
+    `decode([(frames, None)])` takes frames (B, n_q, T), as `infer.py:251-253` passes `encoded_frames.transpose(2, 1)`."""
 
     sample_rate = 24000
     channels = 1
@@ -249,5 +321,7 @@ class AudioTokenizer:
         wavs = self.decoder.decode_batch([codes[b] for b in range(codes.shape[0])])
         return torch.cat(wavs, dim=0)  # (B, 1, hop T)
 
-    def encode(self, wav):
-        raise NotImplementedError("valle_amd.AudioTokenizer decodes only; tokenise prompts with the reference's tokenizer")
+    def encode(self, wav: torch.Tensor):
+        assert wav.dim() == 3 and wav.shape[1] == 1, "wav is (B, 1, L): mono"
+        codes = self.decoder.encode_batch([wav[b] for b in range(wav.shape[0])])
+        return [(torch.cat(codes, dim=0), None)]  # every row of a (B, 1, L) tensor has the same length

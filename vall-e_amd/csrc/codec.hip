@@ -1,5 +1,5 @@
-// EnCodec-24 kHz decoder behind the C ABI (include/vallex.h, vx_codec_*): weights, workspace and the launch sequence of
-// codec_kernels.hpp.  A handle of its own: the codec has its own weights and lifetime and runs without a VALL-E engine.
+// EnCodec-24 kHz decoder and encoder behind the C ABI (include/vallex.h, vx_codec_*): weights, workspace and the launch
+// sequences of codec_kernels.hpp.  A handle of its own: the codec has its own weights and lifetime and runs without a VALL-E engine.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -127,6 +127,58 @@ int run_convtr(const float* x, const float* wp, const float* bias_rep, float* ou
   return launch_gemm(a, s);
 }
 
+// encoder: first convolution 1 -> cout over raw samples (seg: sample offsets, rate 1)
+int run_conv_in(const float* x, const float* w, const float* bias, float* out, long M, int cout, int k, const int* seg, int nseg,
+                hipStream_t s) {
+  const long n = M * cout;
+  if (n > 0) codec_conv_in<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(x, w, bias, out, M, cout, k, seg, nseg);
+  CHIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// encoder: strided convolution k = 2 stride; M_out output rows with starts seg_out, input rows' starts seg_in (both rate 1);
+// wp packed by pack_conv
+int run_conv_strided(const float* x, const float* wp, const float* bias, float* out, long M_out, int cin, int cout, int stride, int elu,
+                     const int* seg_out, const int* seg_in, int nseg, hipStream_t s) {
+  CodecGemmArgs a{};
+  a.part[0] = CodecPart{x, cin, 2 * stride, CODEC_PAD_REFLECT, elu};
+  a.nparts = 1;
+  a.W = wp; a.bias = bias; a.out = out; a.M = M_out; a.N = cout; a.K = 2 * stride * cin; a.seg = seg_out; a.nseg = nseg; a.rate = 1;
+  a.seg_in = seg_in; a.stride = stride;
+  if (M_out <= 0) return VX_OK;
+  const bool vec = cin % 16 == 0;
+  if (a.N <= 32) {
+    dim3 g((unsigned)((a.M + 127) / 128), (unsigned)((a.N + 31) / 32));
+    if (vec) codec_gemm_rows<4, 1, true, true><<<g, 256, 0, s>>>(a);
+    else codec_gemm_rows<4, 1, false, true><<<g, 256, 0, s>>>(a);
+  } else {
+    dim3 g((unsigned)((a.M + 63) / 64), (unsigned)((a.N + 63) / 64));
+    if (vec) codec_gemm_rows<2, 2, true, true><<<g, 256, 0, s>>>(a);
+    else codec_gemm_rows<2, 2, false, true><<<g, 256, 0, s>>>(a);
+  }
+  CHIPC(hipGetLastError());
+  return VX_OK;
+}
+
+bool rvq_shape_ok(int S, int D) { return S >= 32 && S % 32 == 0 && D >= 8 && D % 8 == 0 && D <= CODEC_RVQ_MAX_D; }
+
+// |e_j|^2 in fp64, rounded once
+std::vector<float> codebook_sq(const float* cb, size_t n, int D) {
+  std::vector<float> o(n);
+  for (size_t j = 0; j < n; ++j) {
+    double a = 0;
+    for (int c = 0; c < D; ++c) a += (double)cb[j * D + c] * cb[j * D + c];
+    o[j] = (float)a;
+  }
+  return o;
+}
+
+int run_rvq_encode(const float* emb, const float* cb, const float* cb_sq, int* codes, long rows, int n_q, int S, int D, hipStream_t s) {
+  if (rows > 0) codec_rvq_encode<<<(unsigned)((rows + CODEC_RVQ_ROWS - 1) / CODEC_RVQ_ROWS), 256, 0, s>>>(emb, cb, cb_sq, codes, rows, n_q, S, D);
+  CHIPC(hipGetLastError());
+  return VX_OK;
+}
+
 struct LstmDev {
   float *wih0 = nullptr, *b0 = nullptr, *whh0 = nullptr, *w1 = nullptr, *b1 = nullptr;
 };
@@ -218,6 +270,13 @@ int check_segs(const int32_t* seg, int nseg) {
   return VX_OK;
 }
 
+struct EncStage {
+  int c, stride;                             // c -> 2c at `stride`
+  float *c3_w = nullptr, *c3_b = nullptr;    // block.1: c -> c / 2, k = res_kernel
+  float *mix_w = nullptr, *mix_b = nullptr;  // [block.3 | shortcut]
+  float *dn_w = nullptr, *dn_b = nullptr;    // strided convolution, packed by pack_conv
+};
+
 struct Stage {
   int cin, cout, stride;
   float *up_w = nullptr, *up_b = nullptr;    // packed transposed conv, bias repeated per phase
@@ -248,6 +307,14 @@ struct vx_codec {
   size_t stage_ints = 0;
   float *x0 = nullptr, *xc = nullptr, *gin = nullptr, *h0 = nullptr, *h1 = nullptr, *y = nullptr, *c0 = nullptr, *c1 = nullptr;
   float *bufA = nullptr, *bufH = nullptr, *bufB = nullptr;
+  // encoder (VX_CODEC_ENCODER)
+  bool enc = false;
+  float *cb_sq = nullptr;  // [n_codebooks][size]
+  float *e0_w = nullptr, *e0_b = nullptr, *elast_w = nullptr, *elast_b = nullptr, *wav = nullptr;
+  LstmDev elstm;
+  std::vector<EncStage> estages;
+  long long **ptrs_dev = nullptr, **ptrs_host = nullptr;  // the utterances' output tensors
+  long last_frames = 0;  // frames of the last vx_codec_encode (what x0 holds of it)
 };
 
 static std::map<std::string, std::vector<int64_t>> codec_expected(const vx_codec_config& c) {
@@ -280,6 +347,30 @@ static std::map<std::string, std::vector<int64_t>> codec_expected(const vx_codec
   for (int q = 0; q < c.n_codebooks; ++q) {
     snprintf(k, sizeof k, "quantizer.layers.%d.codebook.embed", q); s[k] = {c.codebook_size, c.codebook_dim};
   }
+  if (!(c.flags & VX_CODEC_ENCODER)) return s;
+  ch = c.filters;
+  s["encoder.layers.0.conv.weight"] = {ch, 1, c.kernel};
+  s["encoder.layers.0.conv.bias"] = {ch};
+  for (int i = 0; i < 4; ++i) {
+    const int res = 1 + 3 * i, dn = 3 + 3 * i;
+    snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.weight", res); s[k] = {ch / 2, ch, c.res_kernel};
+    snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.bias", res); s[k] = {ch / 2};
+    snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.weight", res); s[k] = {ch, ch / 2, 1};
+    snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.bias", res); s[k] = {ch};
+    snprintf(k, sizeof k, "encoder.layers.%d.shortcut.conv.weight", res); s[k] = {ch, ch, 1};
+    snprintf(k, sizeof k, "encoder.layers.%d.shortcut.conv.bias", res); s[k] = {ch};
+    snprintf(k, sizeof k, "encoder.layers.%d.conv.weight", dn); s[k] = {2 * ch, ch, 2 * (int64_t)c.ratios[3 - i]};
+    snprintf(k, sizeof k, "encoder.layers.%d.conv.bias", dn); s[k] = {2 * ch};
+    ch *= 2;
+  }
+  for (int l = 0; l < c.lstm_layers; ++l) {
+    snprintf(k, sizeof k, "encoder.layers.13.lstm.weight_ih_l%d", l); s[k] = {4 * W, W};
+    snprintf(k, sizeof k, "encoder.layers.13.lstm.weight_hh_l%d", l); s[k] = {4 * W, W};
+    snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_ih_l%d", l); s[k] = {4 * W};
+    snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_hh_l%d", l); s[k] = {4 * W};
+  }
+  s["encoder.layers.15.conv.weight"] = {c.hidden, W, c.last_kernel};
+  s["encoder.layers.15.conv.bias"] = {c.hidden};
   return s;
 }
 
@@ -290,7 +381,7 @@ extern "C" int vx_codec_create(const vx_codec_config* cfg, vx_codec** out) {
   const vx_codec_config& c = *cfg;
   if (c.hidden < 1 || c.filters < 1 || c.codebook_size < 1 || c.codebook_dim < 1 || c.n_codebooks < 1 || c.max_frames < 1 ||
       c.max_batch < 1 || c.kernel < 1 || c.last_kernel < 1 || c.res_kernel < 1 || c.lstm_layers < 0 || c.device < 0 ||
-      (c.flags & ~VX_CODEC_LSTM_GRAPH))
+      (c.flags & ~(VX_CODEC_LSTM_GRAPH | VX_CODEC_ENCODER)))
     return cfail(VX_ERR_ARG, "vx_codec_config: sizes must be positive and flags known");
   for (int i = 0; i < 4; ++i)
     if (c.ratios[i] < 1) return cfail(VX_ERR_ARG, "vx_codec_config.ratios[%d] = %d", i, c.ratios[i]);
@@ -304,6 +395,13 @@ extern "C" int vx_codec_create(const vx_codec_config* cfg, vx_codec** out) {
   long hop = 1;
   for (int i = 0; i < 4; ++i) hop *= c.ratios[i];
   if (hop * (long)c.max_frames * c.max_batch >= (1L << 40)) return cfail(VX_ERR_UNSUPPORTED, "capacity too large");
+  if (c.flags & VX_CODEC_ENCODER) {
+    if (!rvq_shape_ok(c.codebook_size, c.codebook_dim))
+      return cfail(VX_ERR_UNSUPPORTED, "encoder: codebook %d x %d: the search kernel serves sizes in multiples of 32 and dims in multiples of 8 up to %d",
+                   c.codebook_size, c.codebook_dim, CODEC_RVQ_MAX_D);
+    if (c.filters % 2) return cfail(VX_ERR_UNSUPPORTED, "encoder: filters %d is odd", c.filters);
+    if (hop * (long)c.max_frames >= (1L << 31)) return cfail(VX_ERR_UNSUPPORTED, "encoder: max_frames * hop samples exceed int32");
+  }
   vx_codec* e = new vx_codec();
   e->cfg = c;
   e->W = W;
@@ -317,6 +415,12 @@ static void codec_free_device(vx_codec* e) {
                    e->bufH, e->bufB})
     (void)hipFree(p);
   free_lstm(e->lstm);
+  for (float* p : {e->cb_sq, e->e0_w, e->e0_b, e->elast_w, e->elast_b, e->wav}) (void)hipFree(p);
+  free_lstm(e->elstm);
+  for (EncStage& st : e->estages)
+    for (float* p : {st.c3_w, st.c3_b, st.mix_w, st.mix_b, st.dn_w, st.dn_b}) (void)hipFree(p);
+  (void)hipFree(e->ptrs_dev);
+  (void)hipHostFree(e->ptrs_host);
   for (Stage& st : e->stages)
     for (float* p : {st.up_w, st.up_b, st.c3_w, st.c3_b, st.mix_w, st.mix_b}) (void)hipFree(p);
   (void)hipFree(e->codes_dev);
@@ -427,6 +531,60 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
   }
   CVXC(upload(pack_conv(host("decoder.layers.15.conv.weight").data(), 1, ch, c.last_kernel), &e->last_w));
   CVXC(upload(host("decoder.layers.15.conv.bias"), &e->last_b));
+  e->enc = (c.flags & VX_CODEC_ENCODER) != 0;
+  if (e->enc) {
+    {
+      std::vector<float> sq;
+      for (int q = 0; q < c.n_codebooks; ++q) {
+        snprintf(k, sizeof k, "quantizer.layers.%d.codebook.embed", q);
+        const std::vector<float> one = codebook_sq(host(k).data(), (size_t)c.codebook_size, c.codebook_dim);
+        sq.insert(sq.end(), one.begin(), one.end());
+      }
+      CVXC(upload(sq, &e->cb_sq));
+    }
+    CVXC(upload(pack_conv(host("encoder.layers.0.conv.weight").data(), c.filters, 1, c.kernel), &e->e0_w));
+    CVXC(upload(host("encoder.layers.0.conv.bias"), &e->e0_b));
+    int ec = c.filters;
+    e->estages.resize(4);
+    for (int i = 0; i < 4; ++i) {
+      EncStage& st = e->estages[i];
+      const int res = 1 + 3 * i, dn = 3 + 3 * i, hd = ec / 2;
+      st.c = ec; st.stride = c.ratios[3 - i];
+      snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.weight", res);
+      CVXC(upload(pack_conv(host(k).data(), hd, ec, c.res_kernel), &st.c3_w));
+      snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.bias", res);
+      CVXC(upload(host(k), &st.c3_b));
+      snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.weight", res);
+      snprintf(k2, sizeof k2, "encoder.layers.%d.shortcut.conv.weight", res);
+      std::vector<float> mix((size_t)ec * (hd + ec)), mb(ec);
+      for (int n = 0; n < ec; ++n) {
+        memcpy(&mix[(size_t)n * (hd + ec)], host(k).data() + (size_t)n * hd, hd * sizeof(float));
+        memcpy(&mix[(size_t)n * (hd + ec) + hd], host(k2).data() + (size_t)n * ec, ec * sizeof(float));
+      }
+      snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.bias", res);
+      snprintf(k2, sizeof k2, "encoder.layers.%d.shortcut.conv.bias", res);
+      for (int n = 0; n < ec; ++n) mb[n] = host(k)[n] + host(k2)[n];
+      CVXC(upload(mix, &st.mix_w));
+      CVXC(upload(mb, &st.mix_b));
+      snprintf(k, sizeof k, "encoder.layers.%d.conv.weight", dn);
+      CVXC(upload(pack_conv(host(k).data(), 2 * ec, ec, 2 * st.stride), &st.dn_w));
+      snprintf(k, sizeof k, "encoder.layers.%d.conv.bias", dn);
+      CVXC(upload(host(k), &st.dn_b));
+      ec *= 2;
+    }
+    {
+      const float *wih[2] = {}, *whh[2] = {}, *bih[2] = {}, *bhh[2] = {};
+      for (int l = 0; l < c.lstm_layers; ++l) {
+        snprintf(k, sizeof k, "encoder.layers.13.lstm.weight_ih_l%d", l); wih[l] = host(k).data();
+        snprintf(k, sizeof k, "encoder.layers.13.lstm.weight_hh_l%d", l); whh[l] = host(k).data();
+        snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_ih_l%d", l); bih[l] = host(k).data();
+        snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_hh_l%d", l); bhh[l] = host(k).data();
+      }
+      CVXC(pack_lstm(wih, whh, bih, bhh, W, c.lstm_layers, &e->elstm));
+    }
+    CVXC(upload(pack_conv(host("encoder.layers.15.conv.weight").data(), c.hidden, W, c.last_kernel), &e->elast_w));
+    CVXC(upload(host("encoder.layers.15.conv.bias"), &e->elast_b));
+  }
   for (auto& kv : e->w) std::vector<float>().swap(kv.second.v);  // the host copies are not needed any more
 
   // workspace: the LSTM part holds every frame of a call; the up-sampling part runs over groups of whole utterances of at
@@ -443,10 +601,19 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
   CVXC(alloc_f(&e->y, F * W));
   CVXC(alloc_f(&e->c0, (size_t)c.max_batch * W));
   CVXC(alloc_f(&e->c1, (size_t)c.max_batch * W));
-  CVXC(alloc_f(&e->bufA, (size_t)e->chunk_frames * e->per_frame));
-  CVXC(alloc_f(&e->bufB, (size_t)e->chunk_frames * e->per_frame));
-  CVXC(alloc_f(&e->bufH, (size_t)e->chunk_frames * e->per_frame / 2));
+  // encoder: the same three buffers hold its stages (filters channels per sample at most, as the decoder's last stage), plus one
+  // row per utterance and stage for the rounded-up row counts
+  const size_t slack = e->enc ? (size_t)c.max_batch * W : 0;
+  CVXC(alloc_f(&e->bufA, (size_t)e->chunk_frames * e->per_frame + slack));
+  CVXC(alloc_f(&e->bufB, (size_t)e->chunk_frames * e->per_frame + slack));
+  CVXC(alloc_f(&e->bufH, (size_t)e->chunk_frames * e->per_frame / 2 + slack));
   e->stage_ints = 2 + F * c.n_codebooks + 3 * (size_t)(c.max_batch + 1);
+  if (e->enc) {
+    e->stage_ints += 8 * (size_t)(c.max_batch + 1);  // four more row tables per utterance group
+    CVXC(alloc_f(&e->wav, (size_t)e->chunk_frames * rate));
+    CHIPC(hipMalloc((void**)&e->ptrs_dev, (size_t)c.max_batch * sizeof(void*)));
+    CHIPC(hipHostMalloc((void**)&e->ptrs_host, (size_t)c.max_batch * sizeof(void*)));
+  }
   CHIPC(hipMalloc((void**)&e->codes_dev, e->stage_ints * sizeof(int)));
   CHIPC(hipHostMalloc((void**)&e->codes_host, e->stage_ints * sizeof(int)));
   CHIPC(hipStreamCreateWithFlags(&e->own, hipStreamNonBlocking));
@@ -520,6 +687,7 @@ extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* cod
   const int* dcodes = drel + 2 * MB1;
 
   const long e0 = total * c.hidden;
+  e->last_frames = 0;  // x0 no longer holds an encode's embeddings
   codec_rvq_rows<<<(unsigned)((e0 + 255) / 256), 256, 0, s>>>(dcodes, e->cb, e->x0, total, n_q, c.codebook_size, c.codebook_dim);
   CHIPC(hipGetLastError());
   CVXC(run_conv(e->x0, e->c0_w, e->c0_b, e->xc, total, c.hidden, W, c.kernel, 0, dseg, n, 1, s));
@@ -553,6 +721,130 @@ extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* cod
                            hipMemcpyDeviceToDevice, s));
   }
   CHIPC(hipEventRecord(e->ev_out, s));
+  CHIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
+  return VX_OK;
+}
+
+extern "C" int vx_codec_encode(vx_codec* e, int32_t n, const float* const* wav, const int32_t* n_samples, int32_t n_q,
+                               int64_t* const* codes_out, void* stream) {
+  if (!e || !wav || !n_samples || !codes_out) return cfail(VX_ERR_ARG, "vx_codec_encode: null argument");
+  const vx_codec_config& c = e->cfg;
+  if (!(c.flags & VX_CODEC_ENCODER)) return cfail(VX_ERR_STATE, "vx_codec_encode on a handle created without VX_CODEC_ENCODER");
+  if (n < 1) return cfail(VX_ERR_ARG, "n = %d utterances", n);
+  if (n > c.max_batch) return cfail(VX_ERR_CAPACITY, "n = %d utterances > max_batch %d", n, c.max_batch);
+  if (n_q < 1 || n_q > c.n_codebooks) return cfail(VX_ERR_ARG, "n_q = %d outside [1, %d]", n_q, c.n_codebooks);
+  long hop = 1;
+  for (int i = 0; i < 4; ++i) hop *= c.ratios[i];
+  const long max_samples = (long)c.max_frames * hop;
+  for (int i = 0; i < n; ++i) {
+    if (!wav[i] || !codes_out[i]) return cfail(VX_ERR_ARG, "utterance %d: null pointer", i);
+    if (n_samples[i] < 1) return cfail(VX_ERR_ARG, "utterance %d: %d samples", i, n_samples[i]);
+    if (n_samples[i] > max_samples)
+      return cfail(VX_ERR_CAPACITY, "utterance %d: %d samples > max_frames %d x %ld", i, n_samples[i], c.max_frames, hop);
+  }
+  if (!e->finalized) return cfail(VX_ERR_STATE, "vx_codec_encode before vx_codec_finalize");
+  CDevGuard g(c.device);
+  CHIPC(g.err);
+  hipStream_t s = e->own;  // ordering as vx_codec_decode
+  CHIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
+  CHIPC(hipStreamWaitEvent(s, e->ev_in, 0));
+  const int W = e->W;
+
+  CHIPC(hipEventSynchronize(e->ev_copy));
+  int* hc = e->codes_host;
+  const int MB1 = c.max_batch + 1;
+  hc[0] = n;
+  hc[1] = 0;
+  int* hseg = hc + 2;          // frame offsets of the call
+  int* hrel = hseg + MB1;      // per group: frame offsets relative to the group (stage 4 rows)
+  int* hlv = hrel + 2 * MB1;   // per stage 0..3: per group row offsets, [4][2 MB1]
+  std::vector<int> seg(n + 1, 0);
+  auto cdiv = [](long a, long b) { return (a + b - 1) / b; };
+  for (int i = 0; i < n; ++i) seg[i + 1] = seg[i] + (int)cdiv(n_samples[i], hop);
+  const long total = seg[n];
+  memcpy(hseg, seg.data(), (n + 1) * sizeof(int));
+  struct Group { int u0, u1, off; long rows[5]; };
+  std::vector<Group> groups;
+  int used = 0;
+  for (int u0 = 0; u0 < n;) {
+    int u1 = u0 + 1;
+    while (u1 < n && (long)seg[u1 + 1] - seg[u0] <= e->chunk_frames) ++u1;
+    Group gr{u0, u1, used, {0, 0, 0, 0, 0}};
+    long acc[5] = {0, 0, 0, 0, 0};
+    for (int u = u0; u <= u1; ++u) {
+      for (int l = 0; l < 4; ++l) hlv[l * 2 * MB1 + used] = (int)acc[l];
+      hrel[used] = (int)acc[4];
+      ++used;
+      if (u == u1) break;
+      long rows = n_samples[u];
+      acc[0] += rows;
+      for (int l = 0; l < 4; ++l) {
+        rows = cdiv(rows, e->estages[l].stride);
+        acc[l + 1] += rows;
+      }
+    }
+    for (int l = 0; l < 5; ++l) gr.rows[l] = acc[l];
+    groups.push_back(gr);
+    u0 = u1;
+  }
+  for (int i = 0; i < n; ++i) e->ptrs_host[i] = (long long*)codes_out[i];
+  const size_t ints = 2 + 11 * (size_t)MB1;
+  CHIPC(hipMemcpyAsync(e->codes_dev, hc, ints * sizeof(int), hipMemcpyHostToDevice, s));
+  CHIPC(hipMemcpyAsync(e->ptrs_dev, e->ptrs_host, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, s));
+  CHIPC(hipEventRecord(e->ev_copy, s));
+  const int* dseg = e->codes_dev + 2;
+  const int* drel = dseg + MB1;
+  const int* dlv = drel + 2 * MB1;
+  int* dcodes = e->codes_dev + 2 + 11 * MB1;  // [n_q][total]
+
+  for (const Group& gr : groups) {
+    const int ns = gr.u1 - gr.u0;
+    const int* sg[5] = {dlv + gr.off, dlv + 2 * MB1 + gr.off, dlv + 4 * MB1 + gr.off, dlv + 6 * MB1 + gr.off, drel + gr.off};
+    long off = 0;
+    for (int u = gr.u0; u < gr.u1; ++u) {
+      CHIPC(hipMemcpyAsync(e->wav + off, wav[u], (size_t)n_samples[u] * sizeof(float), hipMemcpyDeviceToDevice, s));
+      off += n_samples[u];
+    }
+    CVXC(run_conv_in(e->wav, e->e0_w, e->e0_b, e->bufA, gr.rows[0], c.filters, c.kernel, sg[0], ns, s));
+    for (int l = 0; l < 4; ++l) {
+      const EncStage& st = e->estages[l];
+      const int ch = st.c, hd = ch / 2;
+      CVXC(run_conv(e->bufA, st.c3_w, st.c3_b, e->bufH, gr.rows[l], ch, hd, c.res_kernel, 1, sg[l], ns, 1, s));
+      CodecGemmArgs a{};
+      a.part[0] = CodecPart{e->bufH, hd, 1, CODEC_PAD_ZERO, 1};
+      a.part[1] = CodecPart{e->bufA, ch, 1, CODEC_PAD_ZERO, 0};
+      a.nparts = 2;
+      a.W = st.mix_w; a.bias = st.mix_b; a.out = e->bufB; a.M = gr.rows[l]; a.N = ch; a.K = hd + ch;
+      a.seg = sg[l]; a.nseg = ns; a.rate = 1;
+      CVXC(launch_gemm(a, s));
+      float* out = l == 3 ? e->xc + (size_t)seg[gr.u0] * W : e->bufA;
+      CVXC(run_conv_strided(e->bufB, st.dn_w, st.dn_b, out, gr.rows[l + 1], ch, 2 * ch, st.stride, 1, sg[l + 1], sg[l], ns, s));
+    }
+  }
+  CVXC(run_lstm(e->elstm, e->xc, e->gin, e->h0, e->h1, e->c0, e->c1, e->y, W, c.lstm_layers, dseg, seg.data(), n, s));
+  e->last_frames = 0;
+  CVXC(run_conv(e->y, e->elast_w, e->elast_b, e->x0, total, W, c.hidden, c.last_kernel, 1, dseg, n, 1, s));
+  e->last_frames = total;
+  CVXC(run_rvq_encode(e->x0, e->cb, e->cb_sq, dcodes, total, n_q, c.codebook_size, c.codebook_dim, s));
+  const long nc = total * n_q;
+  codec_codes_out<<<(unsigned)((nc + 255) / 256), 256, 0, s>>>(dcodes, e->ptrs_dev, dseg, n, total, n_q);
+  CHIPC(hipGetLastError());
+  CHIPC(hipEventRecord(e->ev_out, s));
+  CHIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
+  return VX_OK;
+}
+
+// The embeddings (the quantiser's input, [rows][hidden]) of the last vx_codec_encode, rows in the order of its utterances: copied to
+// `out` (device) on the codec's stream, `stream` ordered after it.  For the parity tests.
+extern "C" int vx_codec_last_embeddings(vx_codec* e, float* out, int64_t rows, void* stream) {
+  if (!e || !out) return cfail(VX_ERR_ARG, "vx_codec_last_embeddings: null argument");
+  if (!(e->cfg.flags & VX_CODEC_ENCODER) || !e->finalized) return cfail(VX_ERR_STATE, "vx_codec_last_embeddings: no finalised encoder");
+  if (rows < 1 || rows > e->last_frames)
+    return cfail(VX_ERR_ARG, "vx_codec_last_embeddings: rows = %lld, the last encode had %ld frames", (long long)rows, e->last_frames);
+  CDevGuard g(e->cfg.device);
+  CHIPC(g.err);
+  CHIPC(hipMemcpyAsync(out, e->x0, (size_t)rows * e->cfg.hidden * sizeof(float), hipMemcpyDeviceToDevice, e->own));
+  CHIPC(hipEventRecord(e->ev_out, e->own));
   CHIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
   return VX_OK;
 }
@@ -631,4 +923,44 @@ extern "C" int vx_op_codec_lstm(const float* x, const float* const* w_ih, const 
   if (r == VX_OK && hipStreamSynchronize(s) != hipSuccess) r = cfail(VX_ERR_HIP, "vx_op_codec_lstm: synchronise failed");
   free_lstm(d);
   return r;
+}
+
+// Encoder convolution on caller data: x device rows [seg_rows_in[nseg]][c_in], w HOST (c_out, c_in, k), out device rows
+// [sum ceil(len_i / stride)][c_out].  stride == 1: the causal convolution (c_in == 1 runs the first convolution's kernel, elu must be
+// 0 there); stride > 1: k must be 2 stride.
+extern "C" int vx_op_codec_conv_strided(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out,
+                                        int32_t k, int32_t stride, int32_t elu, int32_t nseg, const int32_t* seg_rows_in, void* stream) {
+  if (!x || !w || !out || c_in < 1 || c_out < 1 || k < 1 || k > 32 || stride < 1) return cfail(VX_ERR_ARG, "vx_op_codec_conv_strided: bad argument");
+  if (stride > 1 && k != 2 * stride) return cfail(VX_ERR_UNSUPPORTED, "vx_op_codec_conv_strided: k = %d, stride = %d (k = 2 stride is served)", k, stride);
+  if (c_in == 1 && stride == 1 && elu) return cfail(VX_ERR_UNSUPPORTED, "vx_op_codec_conv_strided: the first convolution has no ELU");
+  CVXC(check_segs(seg_rows_in, nseg));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> so(nseg + 1, 0);
+  for (int i = 0; i < nseg; ++i) so[i + 1] = so[i] + (seg_rows_in[i + 1] - seg_rows_in[i] + stride - 1) / stride;
+  OpSeg sg, sgo;
+  OpBuf wp, bp;
+  CVXC(sg.init(seg_rows_in, nseg));
+  CVXC(sgo.init(so.data(), nseg));
+  CVXC(upload(pack_conv(w, c_out, c_in, k), &wp.d));
+  if (bias) CVXC(upload(std::vector<float>(bias, bias + c_out), &bp.d));
+  if (stride > 1) CVXC(run_conv_strided(x, wp.d, bp.d, out, so[nseg], c_in, c_out, stride, elu, sgo.d, sg.d, nseg, s));
+  else if (c_in == 1) CVXC(run_conv_in(x, wp.d, bp.d, out, so[nseg], c_out, k, sg.d, nseg, s));
+  else CVXC(run_conv(x, wp.d, bp.d, out, so[nseg], c_in, c_out, k, elu, sg.d, nseg, 1, s));
+  CHIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+// The quantiser's search on caller data: emb device [rows][dim], codebooks HOST [n_q][size][dim], codes_out device int32 [n_q][rows].
+extern "C" int vx_op_codec_rvq_encode(const float* emb, const float* codebooks, int32_t* codes_out, int64_t rows, int32_t n_q,
+                                      int32_t size, int32_t dim, void* stream) {
+  if (!emb || !codebooks || !codes_out || rows < 1 || n_q < 1 || n_q > CODEC_MAX_Q) return cfail(VX_ERR_ARG, "vx_op_codec_rvq_encode: bad argument");
+  if (size < 1 || dim < 1 || !rvq_shape_ok(size, dim)) return cfail(VX_ERR_UNSUPPORTED, "vx_op_codec_rvq_encode: codebook %d x %d", size, dim);
+  hipStream_t s = (hipStream_t)stream;
+  OpBuf cb, sq;
+  const size_t n = (size_t)n_q * size;
+  CVXC(upload(std::vector<float>(codebooks, codebooks + n * dim), &cb.d));
+  CVXC(upload(codebook_sq(codebooks, n, dim), &sq.d));
+  CVXC(run_rvq_encode(emb, cb.d, sq.d, codes_out, rows, n_q, size, dim, s));
+  CHIPC(hipStreamSynchronize(s));
+  return VX_OK;
 }

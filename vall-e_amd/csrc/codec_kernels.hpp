@@ -1,4 +1,5 @@
-// EnCodec-24 kHz decoder kernels (codes -> waveform), fp32 storage and fp32 accumulation (the parity mode).
+// EnCodec-24 kHz kernels, decoder (codes -> waveform) and encoder (waveform -> codes), fp32 storage and fp32 accumulation (the
+// parity mode).
 //
 // Layout: time-major rows [frames * rate, C]; the rows of a ragged batch are concatenated and every kernel receives the
 // segment starts (in FRAMES, seg[n] = total) plus the rows-per-frame rate of its operand, as run_stack does for the NAR rows.
@@ -17,6 +18,17 @@
 //                      unit's four gate rows in registers and walks the utterances; finished utterances are skipped.  The decoder
 //                      replays the steps as a captured linear chain of CODEC_LSTM_CHAIN launches (codec.hip).
 //   codec_conv_out     the last convolution (C -> 1): one output sample per lane, bandwidth work.
+//
+// Encoder.  An utterance of L samples has ceil(L / 2), ceil(. / 4), ... rows per stage, so the segment starts are passed in ROWS
+// per stage (rate = 1), one table per stage:
+//   codec_conv_in      the first convolution (1 -> C, k = 7) over the raw samples: K = 7 is no matrix shape, one output value per lane.
+//   codec_gemm_rows<.., STRIDED>  the down-sampling convolution (k = 2r, stride r) as the same row GEMM: output row t of a segment
+//                      gathers input rows t r - r .. t r + r - 1 of the SAME segment of the input table (K = 2r C_in); rows before
+//                      the segment mirror (reflect), rows past its end mirror too (the `extra` pad that completes the last
+//                      window), a mirror image outside the segment reads the zero extension.  The residual blocks, the LSTM and
+//                      the last convolution are the decoder's kernels.
+//   codec_rvq_encode   the residual vector quantiser's nearest-code search, all stages in one launch (below).
+//   codec_codes_out    int32 codes [n_q][rows] -> every utterance's own int64 (n_q, T_i) tensor.
 #pragma once
 #include "common.hpp"
 
@@ -47,6 +59,22 @@ __device__ __forceinline__ long codec_tap_row(long t, int j, int k, long len, in
   return i < len ? i : -1;
 }
 
+// Encoder form: tap j of the k-tap window of OUTPUT row t at `stride` (left pad k - stride, reflect; right `extra` pad, reflect).
+// An input not longer than the left pad is zero-extended to k - stride + 1 rows before it is mirrored (lenx below); the right
+// pad is shorter than the left one (extra < stride <= k - stride), so the left pad decides the extension.
+__device__ __forceinline__ long codec_tap_row_strided(long t, int j, int k, int stride, long len) {
+  long i = t * stride + j - (k - stride);
+  if (i < 0) {
+    i = -i;
+    return i < len ? i : -1;
+  }
+  if (i < len) return i;
+  const long lenx = len > k - stride ? len : (long)(k - stride) + 1;
+  if (i < lenx) return -1;
+  i = 2 * (lenx - 1) - i;
+  return (i >= 0 && i < len) ? i : -1;
+}
+
 struct CodecPart {
   const float* x;  // rows [*, C]
   int C, taps, pad, elu;
@@ -62,12 +90,15 @@ struct CodecGemmArgs {
   int N, K;
   const int* seg;     // nseg + 1 frame offsets (device)
   int nseg, rate;     // rows per frame of the operand rows (= of the GEMM's M rows)
+  // STRIDED only (one part, pad = reflect): seg holds the OUTPUT rows' starts (rate 1), seg_in the input rows' starts
+  const int* seg_in;
+  int stride;
 };
 
 // BM = 32 * WM rows x BN = 32 * WN columns per workgroup of WM * WN waves (one 32x32 accumulator tile each), BK = 16.
 // LDS tiles are [row][BK + 1] (odd stride: the per-lane operand reads A[l & 31][l >> 5] hit 32 different banks).
 // VEC: every part's C is a multiple of 16, so a K chunk lies in one tap of one part and is loaded as float4.
-template <int WM, int WN, bool VEC>
+template <int WM, int WN, bool VEC, bool STRIDED = false>
 __global__ __launch_bounds__(WM * WN * 64) void codec_gemm_rows(const CodecGemmArgs a) {
   constexpr int BM = 32 * WM, BN = 32 * WN, BK = 16, LD = BK + 1, NT = WM * WN * 64;
   constexpr int A_V = BM * BK / 4 / NT > 0 ? BM * BK / 4 / NT : 1;   // float4 per thread of the A tile
@@ -80,14 +111,26 @@ __global__ __launch_bounds__(WM * WN * 64) void codec_gemm_rows(const CodecGemmA
   const int n0 = blockIdx.y * BN;
 
   // this thread's A rows: slot v covers tile row (tid + v * NT) / 4, k quad (tid + v * NT) % 4
-  long seg_lo[A_V], seg_len[A_V];
+  // STRIDED: seg_lo / seg_len describe the INPUT segment and row_t is the output row's index inside its own segment
+  long seg_lo[A_V], seg_len[A_V], row_t[A_V];
 #pragma unroll
   for (int v = 0; v < A_V; ++v) {
     const int idx = tid + v * NT;
     const long row = m0 + idx / 4;
     seg_lo[v] = 0;
     seg_len[v] = 0;
-    if (idx < BM * BK / 4 && row < a.M) codec_find_seg(a.seg, a.nseg, a.rate, row, seg_lo[v], seg_len[v]);
+    row_t[v] = 0;
+    if (idx < BM * BK / 4 && row < a.M) {
+      if (STRIDED) {
+        int s = 0;
+        while (s + 1 < a.nseg && (long)a.seg[s + 1] <= row) ++s;
+        row_t[v] = row - a.seg[s];
+        seg_lo[v] = a.seg_in[s];
+        seg_len[v] = (long)a.seg_in[s + 1] - seg_lo[v];
+      } else {
+        codec_find_seg(a.seg, a.nseg, a.rate, row, seg_lo[v], seg_len[v]);
+      }
+    }
   }
 
   float ra[A_V][4], rb[B_V][4];
@@ -104,7 +147,8 @@ __global__ __launch_bounds__(WM * WN * 64) void codec_gemm_rows(const CodecGemmA
         if (a.nparts > 1 && k >= a.part[0].taps * a.part[0].C) { k -= a.part[0].taps * a.part[0].C; p = 1; }
         const CodecPart& P = a.part[p];
         const int tap = k / P.C, c = k - tap * P.C;
-        const long src = codec_tap_row(row - seg_lo[v], tap, P.taps, seg_len[v], P.pad);
+        const long src = STRIDED ? codec_tap_row_strided(row_t[v], tap, P.taps, a.stride, seg_len[v])
+                                 : codec_tap_row(row - seg_lo[v], tap, P.taps, seg_len[v], P.pad);
         if (k0 + kq < a.K && src >= 0) {
           const float4 f = *reinterpret_cast<const float4*>(P.x + (seg_lo[v] + src) * P.C + c);
           ra[v][0] = f.x; ra[v][1] = f.y; ra[v][2] = f.z; ra[v][3] = f.w;
@@ -121,7 +165,8 @@ __global__ __launch_bounds__(WM * WN * 64) void codec_gemm_rows(const CodecGemmA
           if (a.nparts > 1 && k >= a.part[0].taps * a.part[0].C) { k -= a.part[0].taps * a.part[0].C; p = 1; }
           const CodecPart& P = a.part[p];
           const int tap = k / P.C, c = k - tap * P.C;
-          const long src = codec_tap_row(row - seg_lo[v], tap, P.taps, seg_len[v], P.pad);
+          const long src = STRIDED ? codec_tap_row_strided(row_t[v], tap, P.taps, a.stride, seg_len[v])
+                                   : codec_tap_row(row - seg_lo[v], tap, P.taps, seg_len[v], P.pad);
           if (src >= 0) {
             const float f = P.x[(seg_lo[v] + src) * P.C + c];
             ra[v][q] = P.elu ? codec_elu(f) : f;
@@ -333,6 +378,129 @@ __global__ __launch_bounds__(256) void codec_conv_out(const float* __restrict__ 
     }
   }
   out[row] = acc + (bias ? bias[0] : 0.f);
+}
+
+// First convolution of the encoder: out[row][o] = bias[o] + sum_j x[src(row, j)] w[o * taps + j] over the raw samples (C_in = 1);
+// one output value per lane, o fastest.  seg: sample offsets of the utterances (rate 1).
+__global__ __launch_bounds__(256) void codec_conv_in(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                     float* __restrict__ out, long M, int Cout, int taps, const int* __restrict__ seg,
+                                                     int nseg) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M * Cout) return;
+  const long row = i / Cout;
+  const int o = (int)(i - row * Cout);
+  long lo, len;
+  codec_find_seg(seg, nseg, 1, row, lo, len);
+  float acc = 0.f;
+  for (int j = 0; j < taps; ++j) {
+    const long src = codec_tap_row(row - lo, j, taps, len, CODEC_PAD_REFLECT);
+    if (src >= 0) acc = fmaf(x[lo + src], w[o * taps + j], acc);
+  }
+  out[i] = acc + (bias ? bias[o] : 0.f);
+}
+
+// Residual vector quantiser, encode side.  One workgroup owns CODEC_RVQ_ROWS frames and keeps their residual [32][D] in LDS over
+// all n_q stages (the stages depend on each other, the frames do not).  Per stage the [32, D] x [D, S] product runs on the fp32
+// matrix instruction: wave w takes the 32-code tiles w, w + 4, ...; lane half h = lane >> 5 walks k = h D / 2 .. (h + 1) D / 2 - 1
+// of ITS codebook row (contiguous float4 loads from the L2-resident codebook) against the same k of the residual, two
+// accumulators over alternating k.  The distance is formed as |e_j|^2 - 2 r.e_j: the |r|^2 every code of a frame shares is
+// dropped, so the compared numbers are not differences of large near-equal sums (|r|^2 is the largest term as long as the
+// residual is far from every code), and |e_j|^2 comes from the host in fp64, rounded once.  Arg-min is lexicographic in
+// (distance, index) at every level - lane, 32-lane half, workgroup - which is the first index of the smallest distance, as
+// torch.max of the negated distance gives.  Then r -= e_idx and idx goes to codes[q][row].
+constexpr int CODEC_RVQ_ROWS = 32;
+constexpr int CODEC_RVQ_MAX_D = 128;
+
+__device__ __forceinline__ void codec_rvq_better(float d, int i, float& bd, int& bi) {
+  if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
+}
+
+__global__ __launch_bounds__(256) void codec_rvq_encode(const float* __restrict__ emb, const float* __restrict__ cb,
+                                                        const float* __restrict__ cb_sq, int* __restrict__ codes, long rows, int n_q,
+                                                        int S, int D) {
+  constexpr int BM = CODEC_RVQ_ROWS;
+  __shared__ float Rs[BM * (CODEC_RVQ_MAX_D + 1)];
+  __shared__ float best_d[4][BM];
+  __shared__ int best_i[4][BM];
+  __shared__ int pick[BM];
+  const int LD = D + 1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
+  const long m0 = (long)blockIdx.x * BM;
+  for (int i = tid; i < BM * D; i += 256) {
+    const int r = i / D, c = i - r * D;
+    Rs[r * LD + c] = m0 + r < rows ? emb[(m0 + r) * D + c] : 0.f;
+  }
+  __syncthreads();
+  typedef float f32x16 __attribute__((ext_vector_type(16)));
+  const int KH = D / 2;  // k values per lane half; D % 8 == 0 (checked by the host), so KH % 4 == 0
+  const float* ap = Rs + col * LD + half * KH;
+  for (int q = 0; q < n_q; ++q) {
+    const float* E = cb + (long)q * S * D;
+    const float* E2 = cb_sq + (long)q * S;
+    float bd[16];
+    int bi[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { bd[r] = INFINITY; bi[r] = 0x7fffffff; }
+    for (int n0 = wave * 32; n0 < S; n0 += 128) {
+      const int n = n0 + col;  // S % 32 == 0 (checked by the host)
+      const float* ep = E + (long)n * D + half * KH;
+      f32x16 acc0 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      f32x16 acc1 = acc0;
+      for (int k = 0; k < KH; k += 4) {
+        const float4 b = *reinterpret_cast<const float4*>(ep + k);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[k], b.x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[k + 1], b.y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[k + 2], b.z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[k + 3], b.w, acc1, 0, 0, 0);
+      }
+      const float e2 = E2[n];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) codec_rvq_better(fmaf(-2.f, acc0[r] + acc1[r], e2), n, bd[r], bi[r]);
+    }
+    // D layout: column = lane & 31 (the code), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5): reduce over the 32 lanes of a half
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+#pragma unroll
+      for (int off = 1; off < 32; off <<= 1) {
+        const float od = __shfl_xor(bd[r], off, 64);
+        const int oi = __shfl_xor(bi[r], off, 64);
+        codec_rvq_better(od, oi, bd[r], bi[r]);
+      }
+      if (col == 0) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+        best_d[wave][row] = bd[r];
+        best_i[wave][row] = bi[r];
+      }
+    }
+    __syncthreads();
+    if (tid < BM) {
+      float d = best_d[0][tid];
+      int i = best_i[0][tid];
+      for (int w = 1; w < 4; ++w) codec_rvq_better(best_d[w][tid], best_i[w][tid], d, i);
+      if (i < 0 || i >= S) i = 0;  // every distance NaN: any in-range index (non-finite input is not checked)
+      pick[tid] = i;
+      if (m0 + tid < rows) codes[(long)q * rows + m0 + tid] = i;
+    }
+    __syncthreads();
+    for (int i = tid; i < BM * D; i += 256) {
+      const int r = i / D, c = i - r * D;
+      Rs[r * LD + c] -= E[(long)pick[r] * D + c];
+    }
+    __syncthreads();
+  }
+}
+
+// codes [n_q][rows] int32 of the concatenated utterances -> out[u] (n_q, T_u) int64, seg: frame offsets.
+__global__ __launch_bounds__(256) void codec_codes_out(const int* __restrict__ codes, long long* const* __restrict__ out,
+                                                       const int* __restrict__ seg, int nseg, long rows, int n_q) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * n_q) return;
+  const int q = (int)(i / rows);
+  const long row = i - (long)q * rows;
+  int s = 0;
+  while (s + 1 < nseg && (long)seg[s + 1] <= row) ++s;
+  const long lo = seg[s], len = (long)seg[s + 1] - lo;
+  out[s][(long)q * len + (row - lo)] = codes[i];
 }
 
 }  // namespace vx

@@ -21,7 +21,7 @@ VX_FLAG_TRACE_LOGITS, VX_FLAG_NO_GRAPH, VX_FLAG_SIMPLE_ROWS, VX_FLAG_POST_NORM, 
 VX_FLAG_KV_FP8 = 64
 KV_CACHES = ("bf16", "fp8")  # storage of the batched decode's slot caches (VX_FLAG_KV_FP8)
 VX_ADMIT_BATCHED, VX_ADMIT_PER_SLOT = 0, 1
-VX_CODEC_LSTM_GRAPH = 1
+VX_CODEC_LSTM_GRAPH, VX_CODEC_ENCODER = 1, 2
 BE_QKV, BE_RELU, BE_PARTIAL, BE_LOGITS, BE_LOGITS_MAP, BE_BIAS = range(6)  # bgemm_kernel epilogues (csrc/batch_kernels.hpp)
 STOP_REASONS = {0: "none", 1: "eos_argmax", 2: "eos_sample", 3: "length", 4: "max_new"}
 
@@ -103,13 +103,18 @@ _SIGS = {
     "vx_op_sample_topp": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
                                     C.c_void_p]),
     "vx_op_convert_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    # EnCodec decoder (codec.py)
+    # EnCodec decoder and encoder (codec.py)
     "vx_codec_create": (C.c_int, [C.POINTER(VxCodecConfig), C.POINTER(C.c_void_p)]),
     "vx_codec_destroy": (None, [C.c_void_p]),
     "vx_codec_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "vx_codec_finalize": (C.c_int, [C.c_void_p]),
     "vx_codec_decode": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32,
                                   C.POINTER(C.c_void_p), C.c_void_p]),
+    "vx_codec_encode": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32,
+                                  C.POINTER(C.c_void_p), C.c_void_p]),
+    "vx_codec_last_embeddings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "vx_op_codec_conv_strided": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_void_p]),
+    "vx_op_codec_rvq_encode": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "vx_op_codec_conv": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
     "vx_op_codec_convtr": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
     "vx_op_codec_lstm": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
