@@ -423,6 +423,30 @@ int vx_op_codec_conv_strided(const float* x, const float* w, const float* bias, 
 int vx_op_codec_rvq_encode(const float* emb, const float* codebooks, int32_t* codes_out, int64_t rows, int32_t n_q, int32_t size,
                            int32_t dim, void* stream);
 
+/* ---- Sample-rate conversion and mix-down in front of the encoder (what tokenize_audio does through convert_audio,
+ * valle/data/tokenizer.py:245-254) and behind the decoder.  A handle of its own: no weights, no vx_codec.  The rule is the
+ * Hann-windowed sinc of width 6 at roll-off 0.99: with g = gcd(orig, new), o = orig / g, n = new / g, base = 0.99 min(o, n),
+ *   x[i] = mean_c in[c][i]   (fp32, channels summed in order, then divided by their count)
+ *   y[j] = (base / o) sum_i x[i] sinc(pi t) cos^2(pi t / 12),  t = (i / o - j / n) base,  over |t| < 6, x = 0 outside [0, L)
+ * for j < ceil(n L / o); orig == new returns x bit for bit.  The coefficients [n phases][taps] are computed in fp64 at create
+ * (the scale folded in) and rounded once; a sample's products are accumulated in ascending i whatever the batch. */
+typedef struct vx_resampler vx_resampler;
+/* Host only, no HIP call (the table goes to the device current at the first vx_resample).  Null out, a rate <= 0 or
+ * max_batch < 1 -> VX_ERR_ARG; a table above 2^24 coefficients or a rate pair whose taps do not fit the kernel's window ->
+ * VX_ERR_UNSUPPORTED. */
+int vx_resampler_create(int32_t orig_hz, int32_t new_hz, int32_t max_batch, vx_resampler** out);
+void vx_resampler_destroy(vx_resampler* r);
+/* ceil(n L / o), the samples vx_resample writes for n_samples = L; -1 for a rate <= 0 or L < 1.  Host only. */
+int64_t vx_resample_length(int32_t orig_hz, int32_t new_hz, int64_t n_samples);
+/* n utterances of one rate pair: in[i] DEVICE fp32 (channels[i], n_samples[i]) channel-major, out[i] DEVICE fp32 of
+ * vx_resample_length(...) samples.  Every utterance is bitwise what it is alone; no tap crosses an utterance.  Checked before
+ * any HIP call, in this order: null arguments or n < 1 -> VX_ERR_ARG; n > max_batch -> VX_ERR_CAPACITY; then per utterance a
+ * null pointer, channels[i] < 1 or n_samples[i] < 1 -> VX_ERR_ARG, an output length beyond int32 ->
+ * VX_ERR_UNSUPPORTED.  The work is enqueued on `stream`; the host waits only for the previous call's staging copy.
+ * Calls on one handle must not overlap. */
+int vx_resample(vx_resampler* r, int32_t n, const float* const* in, const int32_t* channels, const int32_t* n_samples,
+                float* const* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

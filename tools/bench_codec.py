@@ -14,7 +14,13 @@ B).  The yardsticks are tests/encodec_ref's formula with nn.LSTM in place of its
     python tools/bench_codec.py --encode [--points 1x225,32x225,64x225]   # prompt waveform -> codes, T frames = 320 T samples
 
 `--encode` times `encode_batch` (device waveforms in, device codes out) against tests/encodec_enc_ref's formula on stock torch ops
-(strided conv1d, nn.LSTM, the quantiser's distance matrix by matmul and argmax) per utterance, in one batched call, and on the host."""
+(strided conv1d, nn.LSTM, the quantiser's distance matrix by matmul and argmax) per utterance, in one batched call, and on the host.
+
+    python tools/bench_codec.py --resample [--reps 21]
+
+`--resample` times the prompt's way to 24 kHz mono (`Resampler(48000, 24000)`): one 3 s stereo 48 kHz prompt, and 32 prompts of
+1.5 .. 4.6 s with one or two channels in one ragged call, against tests/resample_ref's polyphase form on stock torch GPU ops (channel
+mean, pad, conv1d with stride, per utterance), and next to `encode_batch` of the resampled prompts, the step it precedes."""
 import argparse
 import json
 import os
@@ -177,14 +183,79 @@ def main_encode(args):
     print(json.dumps(out))
 
 
+def main_resample(args):
+    import torch
+    import torch.nn.functional as F
+
+    import __graft_entry__ as ge
+
+    ge.build()
+    import encodec_enc_ref as E
+    import resample_ref as RR
+    from valle_amd.codec import EncodecDecoder, Resampler
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_codec.py measures on the GPU; none found")
+    orig, new = 48000, 24000
+    rs = Resampler(orig, new, max_batch=32).to("cuda:0")
+    enc = EncodecDecoder(max_frames=768, max_batch=32, encoder=True)
+    enc.load_state_dict(E.make_enc_weights(E.FULL, 3))
+    enc.to("cuda:0")
+    k64, W = RR.polyphase_kernel(orig, new)
+    kern = k64.float()[:, None, :].to("cuda:0")
+    o, n, _ = RR.ratio(orig, new)
+
+    @torch.no_grad()
+    def torch_one(w):
+        y = F.conv1d(F.pad(w.mean(0)[None, None], (W, W + o)), kern, stride=o)
+        return y[0].T.reshape(-1)[:RR.out_length(orig, new, w.shape[1])]
+
+    sync = torch.cuda.synchronize
+
+    def timed(fn):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return time.perf_counter() - t0
+
+    cases = {"1 prompt, 3 s stereo": [RR.make_noise(3 * orig, 1, channels=2) * 0.1],
+             "32 prompts, 1.5 .. 4.6 s, 1 or 2 channels": [RR.make_noise(orig * 3 // 2 + 4801 * b, 10 + b, channels=1 + b % 2) * 0.1
+                                                           for b in range(32)]}
+    out = {"bench": "codec_resample", "orig_hz": orig, "new_hz": new, "reps": args.reps, "points": []}
+    for name, host_wavs in cases.items():
+        wavs = [w.to("cuda:0") for w in host_wavs]
+        mono = rs.resample_batch(wavs)
+        ref = [torch_one(w) for w in wavs]
+        row = {"case": name, "B": len(wavs), "input_samples": sum(w.shape[1] for w in wavs),
+               "hip_vs_torch_gpu_max_abs_diff": max(float((a[0, 0] - b).abs().max()) for a, b in zip(mono, ref))}
+        impls = {"hip": lambda: rs.resample_batch(wavs), "torch_gpu": lambda: [torch_one(w) for w in wavs],
+                 "hip_encode_after": lambda: enc.encode_batch(mono)}
+        for fn in impls.values():
+            timed(fn)
+            timed(fn)
+        times = {k: [] for k in impls}
+        for _ in range(args.reps):
+            for k, fn in impls.items():
+                times[k].append(timed(fn))
+        for k, v in times.items():
+            row[k + "_ms"] = round(1e3 * statistics.median(v), 3)
+            row[k + "_min_ms"] = round(1e3 * min(v), 3)
+        out["points"].append(row)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--points", default=None, help="BxT,...; default 1x753,32x753,64x1505, with --encode 1x225,32x225,64x225")
     ap.add_argument("--encode", action="store_true", help="time the encoder (waveform -> codes) instead of the decoder")
+    ap.add_argument("--resample", action="store_true", help="time the resampler in front of the encoder (48 kHz stereo -> 24 kHz mono)")
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--only-hip", action="store_true", help="time the HIP decoder alone (for a kernel trace)")
     args = ap.parse_args()
+    if args.resample:
+        return main_resample(args)
     if args.points is None:
         args.points = "1x225,32x225,64x225" if args.encode else "1x753,32x753,64x1505"
     if args.encode:

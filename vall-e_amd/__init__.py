@@ -2,11 +2,12 @@
 from .config import ModelConfig, add_model_arguments, NUM_AUDIO_TOKENS, NUM_TEXT_TOKENS  # noqa: F401
 
 
-__all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_TOKENS", "AudioTokenizer", "CodecConfig", "EncodecDecoder"]
+__all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_TOKENS", "AudioTokenizer", "CodecConfig", "EncodecDecoder",
+           "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
-    if name in ("AudioTokenizer", "CodecConfig", "EncodecDecoder"):
+    if name in ("AudioTokenizer", "CodecConfig", "EncodecDecoder", "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio"):
         from . import codec
 
         return getattr(codec, name)

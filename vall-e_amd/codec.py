@@ -1,18 +1,24 @@
 """EnCodec-24 kHz codec on the GPU.  Decode: codec tokens -> waveform, the step `valle/bin/infer.py:251-253` takes right after
 `VALLE.inference` (through `valle/data/tokenizer.py:241-242`).  Encode (`encoder=True`): prompt waveform -> codec tokens, the
 step `tokenize_audio` takes before it (`valle/data/tokenizer.py:238-254`), at 6 kbps (8 codebooks), mono, one chunk, no
-normalisation.  Resampling and file I/O stay on the host.  The kernels are csrc/codec_kernels.hpp behind `vx_codec_*`
-(include/vallex.h); there is no CPU fallback.
+normalisation.  A prompt at another rate or with several channels goes through `Resampler` first (`convert_audio`'s mix-down
+and windowed-sinc resampling, in HIP: pass `sr=`), and `decode(..., sr=)` returns the waveform at a caller's rate.  WAV files
+are read and written with the standard library (`load_wav`, `save_wav`, `tokenize_audio`).  The kernels are
+csrc/codec_kernels.hpp behind `vx_codec_*` / `vx_resample*` (include/vallex.h); there is no CPU fallback.
 
     dec = EncodecDecoder(max_frames=2048, encoder=True)
     dec.load_state_dict(encodec_model.state_dict(), strict=False)   # decoder.*, encoder.* and quantizer.* keys are taken
     dec.to("cuda")
     codes = dec.encode(prompt_wav)                                  # (1, 1, L) float32 at 24 kHz -> (1, 8, ceil(L / 320)) int64
     wav = dec.decode(frames.transpose(2, 1))                        # frames (1, T, 8) from VALLE.inference -> (1, 1, 320 T)
+    codes = dec.encode(stereo_44k, sr=44100)                        # (2, L) at 44.1 kHz: mixed down and resampled on the GPU first
+    [(codes, _)] = tokenize_audio(AudioTokenizer(dec), "prompt.wav")
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+import wave
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -23,6 +29,7 @@ import torch
 from . import engine as _e
 
 _WN = "parametrizations.weight.original"
+SAMPLE_RATE = 24000  # the model's rate
 
 
 @dataclass(frozen=True)
@@ -133,6 +140,150 @@ def pack_state_dict(cfg: CodecConfig, sd: Dict[str, torch.Tensor], strict: bool 
     return out, missing, unexpected
 
 
+def resample_length(orig_hz: int, new_hz: int, n_samples: int) -> int:
+    """ceil(n L / o) with o, n the rates over their gcd: the samples a resampled waveform of L samples has (host only)."""
+    r = int(_e.load_library().vx_resample_length(int(orig_hz), int(new_hz), int(n_samples)))
+    if r < 0:
+        raise ValueError(f"resample_length({orig_hz}, {new_hz}, {n_samples}): rates and length must be positive")
+    return r
+
+
+class Resampler:
+    """`encodec.utils.convert_audio`'s mono path on the GPU: the channel mean, then `torchaudio.transforms.Resample(orig_hz,
+    new_hz)` with its defaults (Hann-windowed sinc, width 6, roll-off 0.99; include/vallex.h states the rule).  One rate pair per
+    object, up to `max_batch` utterances of any lengths and channel counts per `resample_batch` call."""
+
+    def __init__(self, orig_hz: int, new_hz: int, max_batch: int = 1):
+        self.orig_hz, self.new_hz, self.max_batch = int(orig_hz), int(new_hz), int(max_batch)
+        self.device = torch.device("cpu")
+        self._h = None
+        self._bound = None  # the device of the handle's first call: the C side keeps its tables there
+        self._handle()      # a rate pair the kernel does not serve is refused here
+
+    def _handle(self):
+        if self._h is None:
+            h = C.c_void_p()
+            _e._check(_e.load_library().vx_resampler_create(self.orig_hz, self.new_hz, self.max_batch, C.byref(h)))
+            self._h, self._bound = h, None
+        return self._h
+
+    def to(self, device):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self._bound is not None and self._bound != self.device:
+            self.close()  # another device gets a fresh handle on its first call
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            _e.load_library().vx_resampler_destroy(self._h)
+            self._h = self._bound = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def output_length(self, n_samples: int) -> int:
+        return resample_length(self.orig_hz, self.new_hz, n_samples)
+
+    @torch.no_grad()
+    def resample_batch(self, wavs: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+        """wavs[i]: (L_i,), (C_i, L_i) or (1, C_i, L_i) float32 -> [(1, 1, ceil(n L_i / o)) float32 on the device], every utterance
+        bitwise what it is alone."""
+        ws = []
+        for w in wavs:
+            assert w.dtype == torch.float32 and 1 <= w.dim() <= 3, "waveforms are float32 (L,), (C, L) or (1, C, L)"
+            if w.dim() == 3:
+                assert w.shape[0] == 1, "one utterance per entry"
+                w = w[0]
+            ws.append(w.detach().reshape(-1, w.shape[-1]))
+        if self.device.type != "cuda":
+            raise RuntimeError("valle_amd.Resampler runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        ws = [w.to(self.device).contiguous() for w in ws]
+        outs = [torch.empty((1, 1, self.output_length(w.shape[1])), dtype=torch.float32, device=self.device) for w in ws]
+        with torch.cuda.device(self.device):
+            self._resample_raw([w.data_ptr() for w in ws], [w.shape[0] for w in ws], [w.shape[1] for w in ws],
+                               [o.data_ptr() for o in outs])
+        return outs
+
+    def _resample_raw(self, in_ptrs, channels, lengths, out_ptrs):
+        """vx_resample on raw pointers (the argument checks run before any device work)."""
+        n = len(in_ptrs)
+        ip = (C.c_void_p * n)(*in_ptrs)
+        ch = (C.c_int32 * n)(*channels)
+        L = (C.c_int32 * n)(*lengths)
+        op = (C.c_void_p * n)(*out_ptrs)
+        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
+        h = self._handle()
+        if self.device.type == "cuda":
+            self._bound = self.device
+        _e._check(_e.load_library().vx_resample(h, n, ip, ch, L, op, stream))
+
+    def __call__(self, wav: torch.Tensor) -> torch.Tensor:
+        return self.resample_batch([wav])[0]
+
+
+_RESAMPLERS: Dict[Tuple[int, int, torch.device], Resampler] = {}
+
+
+def convert_audio(wav: torch.Tensor, sr: int, target_sr: int = 24000, target_channels: int = 1) -> torch.Tensor:
+    """`encodec.utils.convert_audio(wav, sr, target_sr, target_channels)` for the mono target: wav (C, L) float32 on the GPU ->
+    (1, L') at `target_sr` on the GPU (at sr == target_sr: the channel mean).  Resamplers are kept per rate pair and device."""
+    if target_channels != 1:
+        raise NotImplementedError(f"convert_audio: target_channels = {target_channels}; the mono target is served")
+    assert wav.dim() == 2, "wav is (C, L)"
+    if wav.device.type != "cuda":
+        raise RuntimeError("valle_amd.convert_audio runs only on an MI355X: move the waveform to 'cuda' first (no CPU fallback)")
+    key = (int(sr), int(target_sr), wav.device)
+    if key not in _RESAMPLERS:
+        _RESAMPLERS[key] = Resampler(sr, target_sr).to(wav.device)
+    return _RESAMPLERS[key](wav)[0]
+
+
+# ---- WAV files (standard library only) ----------------------------------------------------------------------------------
+def load_wav(path: str) -> Tuple[torch.Tensor, int]:
+    """PCM WAV of 8 (unsigned), 16, 24 or 32 bits -> (wav (C, L) float32 in [-1, 1), sample rate), as `torchaudio.load` scales
+    integer PCM: by 2^-(bits - 1)."""
+    with wave.open(path, "rb") as f:
+        nch, width, sr, n = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
+        raw = f.readframes(n)
+    if width == 1:
+        a = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+    elif width == 2:
+        a = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+    elif width == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        a = (v - ((v & 0x800000) << 1)).astype(np.float32) / 8388608.0
+    elif width == 4:
+        a = (np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0).astype(np.float32)
+    else:
+        raise ValueError(f"{path}: {8 * width}-bit samples; PCM of 8, 16, 24 or 32 bits is read")
+    return torch.from_numpy(np.ascontiguousarray(a.reshape(-1, nch).T)), sr
+
+
+def save_wav(path: str, wav: torch.Tensor, sr: int) -> None:
+    """wav (L,), (C, L) or (1, C, L) float in [-1, 1) -> 16-bit PCM: round(x 32768) clamped to the int16 range."""
+    w = wav.detach().to("cpu", torch.float32)
+    w = w.reshape(-1, w.shape[-1])
+    q = np.clip(np.rint(w.numpy().astype(np.float64) * 32768.0), -32768, 32767).astype("<i2")
+    with wave.open(path, "wb") as f:
+        f.setnchannels(q.shape[0])
+        f.setsampwidth(2)
+        f.setframerate(int(sr))
+        f.writeframes(np.ascontiguousarray(q.T).tobytes())
+
+
+def tokenize_audio(tokenizer: "AudioTokenizer", audio_path: str):
+    """The reference's `tokenize_audio` (tokenizer.py:245-254): file -> mono at the tokenizer's rate -> `[(codes (1, n_q, T),
+    None)]`, with the conversion on the GPU."""
+    wav, sr = load_wav(audio_path)
+    return tokenizer.encode(wav.unsqueeze(0).to(tokenizer.device), sr=sr)
+
+
 class EncodecDecoder:
     """codes -> 24 kHz waveform in HIP and, with `encoder=True`, waveform -> codes on the same handle.  `max_frames` / `max_batch`
     are capacities (frames per utterance, i.e. `max_frames * hop` samples to encode, and utterances per `decode_batch` /
@@ -150,6 +301,7 @@ class EncodecDecoder:
         self._sd: Dict[str, torch.Tensor] = {}
         self._h = None
         self._final = False
+        self._resamplers: Dict[Tuple[int, int], Resampler] = {}
 
     # ---- weights ------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict: bool = True):
@@ -171,7 +323,17 @@ class EncodecDecoder:
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._drop()
+        for r in self._resamplers.values():
+            r.close()
+        self._resamplers = {}
         return self
+
+    def resampler(self, orig_hz: int, new_hz: int) -> Resampler:
+        """The object's `Resampler` for a rate pair (kept per pair, `max_batch` utterances per call)."""
+        key = (int(orig_hz), int(new_hz))
+        if key not in self._resamplers:
+            self._resamplers[key] = Resampler(key[0], key[1], self.max_batch).to(self.device)
+        return self._resamplers[key]
 
     def cuda(self, index: int = 0):
         return self.to(torch.device("cuda", index))
@@ -227,8 +389,9 @@ class EncodecDecoder:
 
     # ---- decode -------------------------------------------------------------------------------------
     @torch.no_grad()
-    def decode_batch(self, codes: Sequence[torch.Tensor]) -> List[torch.Tensor]:
-        """codes[i]: (n_q, T_i) or (1, n_q, T_i) int64, the same n_q for all -> [(1, 1, hop T_i) float32 on the device]."""
+    def decode_batch(self, codes: Sequence[torch.Tensor], sr: Optional[int] = None) -> List[torch.Tensor]:
+        """codes[i]: (n_q, T_i) or (1, n_q, T_i) int64, the same n_q for all -> [(1, 1, hop T_i) float32 on the device]; with
+        `sr` other than 24000 the waveforms are resampled to it on the GPU."""
         cs = []
         for c in codes:
             if c.dim() == 3:
@@ -241,6 +404,8 @@ class EncodecDecoder:
             raise RuntimeError("valle_amd.EncodecDecoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
         outs = [torch.empty((1, 1, self.cfg.hop * c.shape[1]), dtype=torch.float32, device=self.device) for c in cs]
         self._decode_raw(cs, [o.data_ptr() for o in outs])
+        if sr is not None and int(sr) != SAMPLE_RATE:
+            outs = self.resampler(SAMPLE_RATE, sr).resample_batch(outs)
         return outs
 
     def _decode_raw(self, cs, out_ptrs, finalize: bool = True):
@@ -254,21 +419,25 @@ class EncodecDecoder:
         stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
         _e._check(lib.vx_codec_decode(h, n, cp, T, cs[0].shape[0], op, stream))
 
-    def decode(self, codes: torch.Tensor) -> torch.Tensor:
-        """(1, n_q, T) or (n_q, T) int64 -> (1, 1, hop T) float32 on the device."""
-        return self.decode_batch([codes])[0]
+    def decode(self, codes: torch.Tensor, sr: Optional[int] = None) -> torch.Tensor:
+        """(1, n_q, T) or (n_q, T) int64 -> (1, 1, hop T) float32 on the device (at `sr`: resampled from 24 kHz)."""
+        return self.decode_batch([codes], sr)[0]
 
 
     # ---- encode -------------------------------------------------------------------------------------
     @torch.no_grad()
-    def encode_batch(self, wavs: Sequence[torch.Tensor], n_q: Optional[int] = None) -> List[torch.Tensor]:
+    def encode_batch(self, wavs: Sequence[torch.Tensor], n_q: Optional[int] = None, sr: Optional[int] = None) -> List[torch.Tensor]:
         """wavs[i]: (L_i,), (1, L_i) or (1, 1, L_i) float32 mono at 24 kHz, any L_i >= 1 -> [(1, n_q, ceil(L_i / hop)) int64 on the
-        device], all utterances in one ragged launch sequence (each bitwise what it gets alone)."""
+        device], all utterances in one ragged launch sequence (each bitwise what it gets alone).  With `sr` given the entries
+        are (L_i,), (C_i, L_i) or (1, C_i, L_i) at that rate and are mixed down and resampled on the GPU first, as the
+        reference's `convert_audio(wav, sr, 24000, 1)` does (mono input at 24000 goes to the encoder as it is)."""
         if not self.encoder:
             raise RuntimeError("this EncodecDecoder was built without encoder=True")
         if self.device.type != "cuda":
             raise RuntimeError("valle_amd.EncodecDecoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
         n_q = self.cfg.n_codebooks if n_q is None else int(n_q)
+        if sr is not None and (int(sr) != SAMPLE_RATE or any(w.numel() != w.shape[-1] for w in wavs)):
+            wavs = self.resampler(sr, SAMPLE_RATE).resample_batch(wavs)  # at 24 kHz: the channel mean alone
         ws = []
         for w in wavs:
             assert w.dtype == torch.float32 and w.numel() == w.shape[-1], "one mono float32 waveform per entry"
@@ -294,9 +463,9 @@ class EncodecDecoder:
         _e._check(_e.load_library().vx_codec_last_embeddings(self.handle(), out.data_ptr(), frames, _e.current_stream_ptr(self.device)))
         return out
 
-    def encode(self, wav: torch.Tensor, n_q: Optional[int] = None) -> torch.Tensor:
-        """(1, 1, L), (1, L) or (L,) float32 -> (1, n_q, ceil(L / hop)) int64 on the device."""
-        return self.encode_batch([wav], n_q)[0]
+    def encode(self, wav: torch.Tensor, n_q: Optional[int] = None, sr: Optional[int] = None) -> torch.Tensor:
+        """(1, 1, L), (1, L) or (L,) float32 -> (1, n_q, ceil(L / hop)) int64 on the device; `sr` as in `encode_batch`."""
+        return self.encode_batch([wav], n_q, sr)[0]
 
 
 class AudioTokenizer:
@@ -314,14 +483,18 @@ class AudioTokenizer:
     def device(self):
         return self.decoder.device
 
-    def decode(self, frames) -> torch.Tensor:
+    def decode(self, frames, sr: Optional[int] = None) -> torch.Tensor:
         assert len(frames) == 1, "one (codes, scale) pair: the 24 kHz model decodes whole utterances"
         codes, scale = frames[0]
         assert scale is None, "the 24 kHz model does not normalise"
-        wavs = self.decoder.decode_batch([codes[b] for b in range(codes.shape[0])])
-        return torch.cat(wavs, dim=0)  # (B, 1, hop T)
+        wavs = self.decoder.decode_batch([codes[b] for b in range(codes.shape[0])], sr)
+        return torch.cat(wavs, dim=0)  # (B, 1, hop T), at `sr`: (B, 1, ceil(sr hop T / 24000))
 
-    def encode(self, wav: torch.Tensor):
-        assert wav.dim() == 3 and wav.shape[1] == 1, "wav is (B, 1, L): mono"
-        codes = self.decoder.encode_batch([wav[b] for b in range(wav.shape[0])])
-        return [(torch.cat(codes, dim=0), None)]  # every row of a (B, 1, L) tensor has the same length
+    def encode(self, wav: torch.Tensor, sr: Optional[int] = None):
+        """wav (B, 1, L) at 24 kHz; with `sr` given: (B, C, L) at that rate, mixed down and resampled on the GPU."""
+        if sr is None:
+            assert wav.dim() == 3 and wav.shape[1] == 1, "wav is (B, 1, L): mono"
+        else:
+            assert wav.dim() == 3, "wav is (B, C, L)"
+        codes = self.decoder.encode_batch([wav[b] for b in range(wav.shape[0])], sr=sr)
+        return [(torch.cat(codes, dim=0), None)]  # every row of a (B, C, L) tensor has the same length

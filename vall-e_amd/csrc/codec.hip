@@ -1,10 +1,14 @@
 // EnCodec-24 kHz decoder and encoder behind the C ABI (include/vallex.h, vx_codec_*): weights, workspace and the launch
 // sequences of codec_kernels.hpp.  A handle of its own: the codec has its own weights and lifetime and runs without a VALL-E engine.
+// At the end of the file: the sample-rate converter in front of the encoder (vx_resampler_*), a handle without weights.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -962,5 +966,219 @@ extern "C" int vx_op_codec_rvq_encode(const float* emb, const float* codebooks, 
   CVXC(upload(codebook_sq(codebooks, n, dim), &sq.d));
   CVXC(run_rvq_encode(emb, cb.d, sq.d, codes_out, rows, n_q, size, dim, s));
   CHIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+// ---- sample-rate conversion and mix-down (vx_resampler_*, codec_resample) -------------------------------------------------------
+struct vx_resampler {
+  int orig = 0, neu = 0, max_batch = 0;
+  int o = 1, n = 1, T = 1, tile_out = 256;
+  std::vector<float> coef;        // [T][n], scale folded in, zero past a phase's count
+  std::vector<int> first, count;  // [n]
+  // device side: made on the device that is current at the first vx_resample
+  int device = -1;
+  float* d_coef = nullptr;
+  int* d_phase = nullptr;  // first [n] | count [n]
+  // per call: in pointers [max_batch] | out pointers [max_batch] | tile0 [max_batch + 1] | len_in | chans | len_out [max_batch each]
+  char *stage_dev = nullptr, *stage_host = nullptr;
+  size_t stage_bytes = 0;
+  hipEvent_t ev_copy = nullptr, ev_done = nullptr;
+};
+
+namespace {
+
+constexpr long RESAMPLE_MAX_TABLE = 1L << 24;
+constexpr int RESAMPLE_WIDTH = 6;  // lowpass_filter_width; roll-off 0.99 = 99 / 100 below
+
+long gcd_l(long a, long b) {
+  while (b) { const long t = a % b; a = b; b = t; }
+  return a;
+}
+
+// Input k (relative to q o) lies inside the window of phase p: |t| < 6 with t = (k n - p o) base / (o n), base = 99 min(o, n) / 100,
+// in exact integers, so that a phase's taps are exactly the i with |i - j o / n| < 6 o / base and both ends move forward with j.
+bool tap_inside(long k, long p, long o, long n) {
+  __int128 d = (__int128)k * n - (__int128)p * o;
+  if (d < 0) d = -d;
+  return d * 99 * std::min(o, n) < (__int128)(100 * RESAMPLE_WIDTH) * o * n;
+}
+
+int resampler_build(vx_resampler* r) {
+  const long g = gcd_l(r->orig, r->neu), o = r->orig / g, n = r->neu / g;
+  r->o = (int)o;
+  r->n = (int)n;
+  if (o == n) {  // the same rate: the mixed-down input itself
+    r->T = 1; r->tile_out = 256;
+    r->coef = {1.f}; r->first = {0}; r->count = {1};
+    return VX_OK;
+  }
+  const double base = 0.99 * (double)std::min(o, n), R = RESAMPLE_WIDTH * (double)o / base;
+  if ((double)n * (2.0 * R + 2.0) > (double)RESAMPLE_MAX_TABLE)
+    return cfail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz needs %ld phases of about %.0f taps: above %ld coefficients", r->orig,
+                 r->neu, n, 2.0 * R, RESAMPLE_MAX_TABLE);
+  if (2.0 * R + 4.0 > RESAMPLE_SPAN)
+    return cfail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz: %.0f taps per sample exceed the kernel's window of %d", r->orig, r->neu,
+                 2.0 * R, RESAMPLE_SPAN);
+  r->first.resize(n);
+  r->count.resize(n);
+  int T = 1;
+  for (long p = 0; p < n; ++p) {
+    long k = (long)floor((double)p * o / n - R) - 1;
+    while (!tap_inside(k, p, o, n)) ++k;
+    int cnt = 0;
+    while (tap_inside(k + cnt, p, o, n)) ++cnt;
+    r->first[p] = (int)k;
+    r->count[p] = cnt;
+    T = std::max(T, cnt);
+  }
+  r->T = T;
+  r->coef.assign((size_t)T * n, 0.f);
+  const double pi = 3.14159265358979323846;
+  for (long p = 0; p < n; ++p)
+    for (int k = 0; k < r->count[p]; ++k) {
+      const double t = (double)((__int128)(r->first[p] + k) * n - (__int128)p * o) * base / ((double)o * (double)n);
+      const double sinc = t == 0.0 ? 1.0 : sin(pi * t) / (pi * t);
+      const double win = cos(pi * t / (2.0 * RESAMPLE_WIDTH));
+      r->coef[(size_t)k * n + p] = (float)(base / (double)o * sinc * win * win);
+    }
+  // outputs per workgroup: their input span, < (tile - 1) o / n + 2 R + 1 samples, has to fit the staged window
+  auto need = [&](long t) { return (long)ceil((double)(t - 1) * o / n + 2.0 * R) + 2; };
+  long t = 256;
+  if (need(t) > RESAMPLE_SPAN) {
+    t = std::max(1L, (long)(((double)RESAMPLE_SPAN - 2.0 - 2.0 * R) * n / o) + 1);
+    while (t > 1 && need(t) > RESAMPLE_SPAN) --t;
+    if (t >= 64) t &= ~63L;
+  }
+  if (need(t) > RESAMPLE_SPAN)
+    return cfail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz: one sample's window exceeds %d inputs", r->orig, r->neu, RESAMPLE_SPAN);
+  r->tile_out = (int)t;
+  return VX_OK;
+}
+
+void resampler_free_device(vx_resampler* r) {
+  (void)hipFree(r->d_coef);
+  (void)hipFree(r->d_phase);
+  (void)hipFree(r->stage_dev);
+  (void)hipHostFree(r->stage_host);
+  for (hipEvent_t ev : {r->ev_copy, r->ev_done})
+    if (ev) (void)hipEventDestroy(ev);
+  r->d_coef = nullptr; r->d_phase = nullptr; r->stage_dev = nullptr; r->stage_host = nullptr; r->ev_copy = r->ev_done = nullptr;
+}
+
+// First use: the tables go to the current device.  VX_POISON=1 fills the fresh allocations with 0xFF bytes first, as the engine does.
+int resampler_init_device(vx_resampler* r) {
+  int dev = 0;
+  CHIPC(hipGetDevice(&dev));
+  r->device = dev;
+  const char* pv = getenv("VX_POISON");
+  const bool poison = pv && atoi(pv) != 0;
+  const size_t nc = r->coef.size(), MB = (size_t)r->max_batch;
+  r->stage_bytes = 2 * MB * sizeof(void*) + (4 * MB + 1) * sizeof(int);
+  CHIPC(hipMalloc((void**)&r->d_coef, nc * sizeof(float)));
+  CHIPC(hipMalloc((void**)&r->d_phase, 2 * (size_t)r->n * sizeof(int)));
+  CHIPC(hipMalloc((void**)&r->stage_dev, r->stage_bytes));
+  if (poison) {
+    CHIPC(hipMemset(r->d_coef, 0xFF, nc * sizeof(float)));
+    CHIPC(hipMemset(r->d_phase, 0xFF, 2 * (size_t)r->n * sizeof(int)));
+    CHIPC(hipMemset(r->stage_dev, 0xFF, r->stage_bytes));
+  }
+  CHIPC(hipHostMalloc((void**)&r->stage_host, r->stage_bytes));
+  CHIPC(hipMemcpy(r->d_coef, r->coef.data(), nc * sizeof(float), hipMemcpyHostToDevice));
+  CHIPC(hipMemcpy(r->d_phase, r->first.data(), (size_t)r->n * sizeof(int), hipMemcpyHostToDevice));
+  CHIPC(hipMemcpy(r->d_phase + r->n, r->count.data(), (size_t)r->n * sizeof(int), hipMemcpyHostToDevice));
+  CHIPC(hipEventCreateWithFlags(&r->ev_copy, hipEventDisableTiming));
+  CHIPC(hipEventCreateWithFlags(&r->ev_done, hipEventDisableTiming));
+  return VX_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t vx_resample_length(int32_t orig_hz, int32_t new_hz, int64_t n_samples) {
+  if (orig_hz <= 0 || new_hz <= 0 || n_samples < 1) {
+    cfail(VX_ERR_ARG, "vx_resample_length: %d -> %d Hz, %lld samples", orig_hz, new_hz, (long long)n_samples);
+    return -1;
+  }
+  const long g = gcd_l(orig_hz, new_hz), o = orig_hz / g, n = new_hz / g;
+  return (int64_t)(((__int128)n * n_samples + o - 1) / o);
+}
+
+extern "C" int vx_resampler_create(int32_t orig_hz, int32_t new_hz, int32_t max_batch, vx_resampler** out) {
+  if (!out) return cfail(VX_ERR_ARG, "vx_resampler_create: null argument");
+  if (orig_hz <= 0 || new_hz <= 0) return cfail(VX_ERR_ARG, "vx_resampler_create: rates %d -> %d Hz", orig_hz, new_hz);
+  if (max_batch < 1) return cfail(VX_ERR_ARG, "vx_resampler_create: max_batch = %d", max_batch);
+  vx_resampler* r = new vx_resampler();
+  r->orig = orig_hz; r->neu = new_hz; r->max_batch = max_batch;
+  const int rc = resampler_build(r);
+  if (rc != VX_OK) { delete r; return rc; }
+  *out = r;
+  return VX_OK;
+}
+
+extern "C" void vx_resampler_destroy(vx_resampler* r) {
+  if (!r) return;
+  if (r->device >= 0) {
+    CDevGuard g(r->device);
+    if (r->ev_done) (void)hipEventSynchronize(r->ev_done);
+    resampler_free_device(r);
+  }
+  delete r;
+}
+
+extern "C" int vx_resample(vx_resampler* r, int32_t n, const float* const* in, const int32_t* channels, const int32_t* n_samples,
+                           float* const* out, void* stream) {
+  if (!r || !in || !channels || !n_samples || !out) return cfail(VX_ERR_ARG, "vx_resample: null argument");
+  if (n < 1) return cfail(VX_ERR_ARG, "vx_resample: n = %d utterances", n);
+  if (n > r->max_batch) return cfail(VX_ERR_CAPACITY, "vx_resample: n = %d utterances > max_batch %d", n, r->max_batch);
+  std::vector<int> tile0(n + 1, 0), len_out(n);
+  for (int i = 0; i < n; ++i) {
+    if (!in[i] || !out[i]) return cfail(VX_ERR_ARG, "vx_resample: utterance %d: null pointer", i);
+    if (channels[i] < 1) return cfail(VX_ERR_ARG, "vx_resample: utterance %d: %d channels", i, channels[i]);
+    if (n_samples[i] < 1) return cfail(VX_ERR_ARG, "vx_resample: utterance %d: %d samples", i, n_samples[i]);
+    const long lo = ((long)r->n * n_samples[i] + r->o - 1) / r->o;
+    if (lo > 0x7fffffffL) return cfail(VX_ERR_UNSUPPORTED, "vx_resample: utterance %d: %ld output samples exceed int32", i, lo);
+    len_out[i] = (int)lo;
+    const long tiles = tile0[i] + (lo + r->tile_out - 1) / r->tile_out;
+    if (tiles > 0x7fffffffL) return cfail(VX_ERR_UNSUPPORTED, "vx_resample: utterance %d: the call's output tiles exceed int32", i);
+    tile0[i + 1] = (int)tiles;
+  }
+  if (r->device < 0) {
+    const int rc = resampler_init_device(r);
+    if (rc != VX_OK) {
+      resampler_free_device(r);
+      r->device = -1;
+      return rc;
+    }
+  }
+  CDevGuard g(r->device);
+  CHIPC(g.err);
+  hipStream_t s = (hipStream_t)stream;
+  CHIPC(hipEventSynchronize(r->ev_copy));      // the previous call's copy out of the pinned buffer has completed
+  CHIPC(hipStreamWaitEvent(s, r->ev_done, 0));  // and its kernel, on whatever stream it ran, is done with the device tables
+  const size_t MB = (size_t)r->max_batch;
+  const float** hin = (const float**)r->stage_host;
+  float** hout = (float**)(r->stage_host + MB * sizeof(void*));
+  int* hint = (int*)(r->stage_host + 2 * MB * sizeof(void*));
+  for (int i = 0; i < n; ++i) {
+    hin[i] = in[i];
+    hout[i] = out[i];
+    hint[MB + 1 + i] = n_samples[i];
+    hint[2 * MB + 1 + i] = channels[i];
+    hint[3 * MB + 1 + i] = len_out[i];
+  }
+  memcpy(hint, tile0.data(), (n + 1) * sizeof(int));
+  CHIPC(hipMemcpyAsync(r->stage_dev, r->stage_host, r->stage_bytes, hipMemcpyHostToDevice, s));
+  CHIPC(hipEventRecord(r->ev_copy, s));
+  ResampleArgs a{};
+  a.in = (const float* const*)r->stage_dev;
+  a.out = (float* const*)(r->stage_dev + MB * sizeof(void*));
+  const int* dint = (const int*)(r->stage_dev + 2 * MB * sizeof(void*));
+  a.tile0 = dint; a.len_in = dint + MB + 1; a.chans = dint + 2 * MB + 1; a.len_out = dint + 3 * MB + 1;
+  a.coef = r->d_coef; a.first = r->d_phase; a.count = r->d_phase + r->n;
+  a.nseg = n; a.o = r->o; a.n = r->n; a.T = r->T; a.tile_out = r->tile_out;
+  const unsigned grid = (unsigned)std::min(tile0[n], 2048);
+  if ((long)r->T * r->n <= RESAMPLE_TAB) codec_resample<true><<<grid, 256, 0, s>>>(a);
+  else codec_resample<false><<<grid, 256, 0, s>>>(a);
+  CHIPC(hipGetLastError());
+  CHIPC(hipEventRecord(r->ev_done, s));
   return VX_OK;
 }

@@ -29,6 +29,7 @@
 //                      the last convolution are the decoder's kernels.
 //   codec_rvq_encode   the residual vector quantiser's nearest-code search, all stages in one launch (below).
 //   codec_codes_out    int32 codes [n_q][rows] -> every utterance's own int64 (n_q, T_i) tensor.
+//   codec_resample     windowed-sinc sample-rate conversion with the channel mean, per utterance (vx_resample; described at the kernel).
 #pragma once
 #include "common.hpp"
 
@@ -397,6 +398,97 @@ __global__ __launch_bounds__(256) void codec_conv_in(const float* __restrict__ x
     if (src >= 0) acc = fmaf(x[lo + src], w[o * taps + j], acc);
   }
   out[i] = acc + (bias ? bias[o] : 0.f);
+}
+
+// Sample-rate conversion with the mix-down folded in (in front of codec_conv_in, and behind codec_conv_out for a caller's playback
+// rate).  With o = orig / gcd, n = new / gcd, output j = q n + p of an utterance reads the inputs i = q o + first[p] + k,
+// k < count[p] (every i with |i - j o / n| < 6 o / base: the window is zero beyond), against coef[k][p]: tap-major, so the lanes
+// of consecutive outputs read consecutive coefficients (no LDS bank conflict, coalesced from memory).  The table is built on the
+// host in fp64 with the scale folded in and rounded once; it is kept in LDS when it has at most RESAMPLE_TAB entries.
+// One workgroup owns tile_out <= 256 consecutive outputs of ONE utterance, one per lane: it stages their input span into LDS
+// with aligned float4 loads per channel (scalar loads where a quad leaves the row), channel c added to the staged sum in order
+// and the last one divided by C, so multi-channel input is never written out as mono; samples outside [0, L) are staged as
+// zero, so no tap reaches another utterance.  Every lane then runs its taps in ascending i (first product, then an fmaf
+// chain): the order depends neither on the grid nor on the other utterances of the call.
+constexpr int RESAMPLE_SPAN = 6144;  // staged input samples per tile (the host sizes tile_out for it)
+constexpr int RESAMPLE_TAB = 8192;   // coefficients held in LDS
+
+struct ResampleArgs {
+  const float* const* in;  // [nseg] (C, L) channel-major
+  float* const* out;       // [nseg]
+  const int* tile0;        // [nseg + 1] first tile of every utterance
+  const int* len_in;       // [nseg] L
+  const int* chans;        // [nseg] C
+  const int* len_out;      // [nseg] ceil(n L / o)
+  const float* coef;       // [T][n]
+  const int* first;        // [n] offset of phase p's first tap from q o
+  const int* count;        // [n] taps of phase p, 1 .. T
+  int nseg, o, n, T, tile_out;
+};
+
+template <bool TAB_LDS>
+__global__ __launch_bounds__(256) void codec_resample(const ResampleArgs a) {
+  __shared__ float S[RESAMPLE_SPAN];
+  __shared__ float Ct[TAB_LDS ? RESAMPLE_TAB : 1];
+  const int tid = threadIdx.x;
+  if (TAB_LDS)
+    for (int i = tid; i < a.T * a.n; i += 256) Ct[i] = a.coef[i];
+  const int total = a.tile0[a.nseg];
+  for (int tile = blockIdx.x; tile < total; tile += gridDim.x) {
+    int s = 0;  // the utterance of the tile: the last s with tile0[s] <= tile (every utterance has a tile)
+    for (int hi_s = a.nseg; hi_s - s > 1;) {
+      const int mid = (s + hi_s) >> 1;
+      if (a.tile0[mid] <= tile) s = mid;
+      else hi_s = mid;
+    }
+    const float* x = a.in[s];
+    const long L = a.len_in[s];
+    const int C = a.chans[s], Lo = a.len_out[s];
+    const int j0 = (tile - a.tile0[s]) * a.tile_out;           // < Lo
+    const int j1 = (int)min((long)j0 + a.tile_out - 1, (long)Lo - 1);
+    const int q0 = j0 / a.n, p0 = j0 - q0 * a.n, q1 = j1 / a.n, p1 = j1 - q1 * a.n;
+    const long lo = (long)q0 * a.o + a.first[p0];              // first and one past the last input of the tile: both ends move
+    const long hi = (long)q1 * a.o + a.first[p1] + a.count[p1];  // forward with j
+    __syncthreads();  // the table is staged; the previous tile's reads of S are done
+    for (int c = 0; c < C; ++c) {
+      const float* row = x + (long)c * L;
+      // quads aligned in memory: row + i4 is a multiple of 16 bytes
+      const long mis = (long)((((unsigned long long)row >> 2) + (unsigned long long)lo) & 3);
+      for (long i4 = lo - mis + 4L * tid; i4 < hi; i4 += 4 * 256) {
+        float f[4];
+        if (i4 >= 0 && i4 + 3 < L) {
+          const float4 v = *reinterpret_cast<const float4*>(row + i4);
+          f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) f[e] = (i4 + e >= 0 && i4 + e < L) ? row[i4 + e] : 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const long idx = i4 + e - lo;
+          if (idx < 0 || idx >= hi - lo || idx >= RESAMPLE_SPAN) continue;
+          const float sum = c ? S[idx] + f[e] : f[e];
+          S[idx] = c == C - 1 ? sum / (float)C : sum;
+        }
+      }
+      __syncthreads();  // the next channel's quads are aligned differently: another thread continues this sample's sum
+    }
+    const int j = j0 + min(tid, j1 - j0);  // no index past j1 is formed (j0 + tid could pass int32 at the longest outputs)
+    if (tid <= j1 - j0) {
+      const int q = j / a.n, p = j - q * a.n;
+      const int cnt = a.count[p];
+      const float* sp = S + ((long)q * a.o + a.first[p] - lo);
+      float acc;
+      if (TAB_LDS) {
+        acc = sp[0] * Ct[p];
+        for (int k = 1; k < cnt; ++k) acc = fmaf(sp[k], Ct[k * a.n + p], acc);
+      } else {
+        acc = sp[0] * a.coef[p];
+        for (int k = 1; k < cnt; ++k) acc = fmaf(sp[k], a.coef[(long)k * a.n + p], acc);
+      }
+      a.out[s][j] = acc;
+    }
+  }
 }
 
 // Residual vector quantiser, encode side.  One workgroup owns CODEC_RVQ_ROWS frames and keeps their residual [32][D] in LDS over

@@ -119,6 +119,12 @@ _SIGS = {
     "vx_op_codec_convtr": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
     "vx_op_codec_lstm": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                    C.POINTER(C.c_int32), C.c_void_p]),
+    # sample-rate conversion and mix-down (codec.Resampler)
+    "vx_resampler_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "vx_resampler_destroy": (None, [C.c_void_p]),
+    "vx_resample_length": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "vx_resample": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                              C.POINTER(C.c_void_p), C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so
