@@ -227,11 +227,44 @@ int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* text_nar, con
                     const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens, const int32_t* T,
                     int64_t* const* codes_out, const int64_t* const* forced_codes, void* stream);
 
+/* ---- scoring: how well does the model predict GIVEN codes.  The reference reports this as its validation numbers: VALLE.forward
+ * computes F.cross_entropy(reduction="sum") and MulticlassAccuracy(top_k=10, ignore_index=1024) for the AR decoder
+ * (valle.py:827-881) and for a NAR stage (valle.py:886-950).  vx_score computes the per-row terms of both, teacher-forced, on the
+ * inference prompt layout: codes (A, Q) int64 row-major (host or device), frames [0, P) are the prompt, frames [P, A) are scored,
+ * T = A - P.
+ *   AR  (valle.py:863-877): rows [text | (BOS) codes[:, 0]] go through the AR stack ONCE under the reference mask (text rows see
+ *       text, audio rows are causal; VALL-F: the text is the cross-attention memory), no KV cache is written; the T + 1 rows that
+ *       predict codes[P, 0] ... codes[A-1, 0], EOS give nll_ar[j] = logsumexp(logits_j) - logits_j[target_j] and rank_ar[j] = the
+ *       number of logits strictly greater than the target's (ties count for the target; top-k accuracy = rank < k).  Without
+ *       prepend_bos these are input rows P-1 ... A-1, so P >= 1 is required; with it rows P ... A, and P = 0 (or P = 1 without
+ *       BOS) is the reference's validation form at batch size 1: sum(nll_ar) is its summed AR loss, mean(rank_ar[target != 1024]
+ *       < 10) its ArTop10Accuracy.
+ *   NAR (valle.py:886-950 / 1063-1134): stage i = 0 .. Q-2 runs as in vx_nar_ex with prompts = codes[:P], codebook 0 =
+ *       codes[P:, 0] and forced_codes = codes[P:]; its logits rows are scored against codes[P:, i+1] into nll_nar[i][t] /
+ *       rank_nar[i][t] ((Q-1, T) row-major).  Q = 1 models skip this part.  text_nar / S2 as for vx_nar.
+ * Outputs may be host or device memory; any may be NULL, and a part whose two outputs are both NULL is skipped with its inputs
+ * unread (text for AR, text_nar for NAR).  Checked before any work is enqueued: null arguments, P outside [0, A), S <= 0 ->
+ * VX_ERR_ARG; weights not finalised -> VX_ERR_STATE; S > max_text or A + 1 > max_audio -> VX_ERR_CAPACITY; codes in host memory
+ * outside [0, 1024) -> VX_ERR_ARG (device codes are clamped by the embedding, and an out-of-range TARGET scores nll = NaN, rank =
+ * -1).  Every precision mode serves it; VX_PREC_FP8_NAR runs the stages on MXFP8 under the row threshold of vx_nar.  No decode
+ * state is touched: a vx_ar_decode after vx_ar_prefill + vx_score, or a session's slots, continue as if it had not run. */
+int vx_score(vx_engine* e, const int64_t* text, int32_t S, const int64_t* text_nar, int32_t S2, const int64_t* codes /* (A, Q) */,
+             int32_t A, int32_t P, float* nll_ar /* (T+1) */, int32_t* rank_ar /* (T+1) */, float* nll_nar /* (Q-1, T) */,
+             int32_t* rank_nar /* (Q-1, T) */, void* stream);
+/* vx_score of n (<= 64) utterances in one pass over the concatenated rows: the AR part as vx_batch_prefill_all's segmented stack
+ * (per-segment prefix masks, no KV destination), the NAR part as vx_nar_batch_ex's.  Arguments are host arrays of n pointers /
+ * sizes with vx_score's meaning; output arrays may be NULL as there.  Works on engines of any max_batch.  bf16 / fp8nar VALL-E
+ * with the MFMA row kernels and without prenets; anything else: VX_ERR_UNSUPPORTED (use vx_score per utterance). */
+int vx_score_batch(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S, const int64_t* const* text_nar,
+                   const int32_t* S2, const int64_t* const* codes, const int32_t* A, const int32_t* P, float* const* nll_ar,
+                   int32_t* const* rank_ar, float* const* nll_nar, int32_t* const* rank_nar, void* stream);
+
 /* Device-time of the last calls, measured with HIP events on the engine's stream:
  * out[0] prefill ms, out[1] AR decode ms, out[2] NAR ms, out[3] AR passes, out[4] graph launches, out[5] batched decode ms,
  * out[6] batched graph launches; with VX_TIME_GEMMS=1 in the environment also out[7] = ms spent in the QKV / out-projection / FFN
  * GEMM launches of the last NAR call and out[8] = their FLOPs (2 M N K each); out[9] kernel launches per pass of the batch-1 decode
- * step (nodes of its captured graph; 0 before the first vx_ar_decode and with VX_FLAG_NO_GRAPH). */
+ * step (nodes of its captured graph; 0 before the first vx_ar_decode and with VX_FLAG_NO_GRAPH); out[10] / out[11] ms of the AR / NAR
+ * part of the last vx_score or vx_score_batch. */
 int vx_get_timings(vx_engine* e, double* out, int32_t n);
 
 /* Parity-test taps: copies an internal buffer to host memory (synchronises the engine stream).
@@ -243,7 +276,8 @@ int vx_get_timings(vx_engine* e, double* out, int32_t n);
  * slot, engines created with VX_FLAG_TRACE_LOGITS and max_batch > 1), "batch_kv" (the slot caches, max_batch > 1:
  * [slot][layer][K|V][head][max_text+max_audio][64] bf16, or e4m3 bytes with VX_FLAG_KV_FP8), "batch_kv_scale" (VX_FLAG_KV_FP8: the
  * E8M0 scale bytes, [slot][layer][K|V][head][max_text+max_audio][4]), "ar_kv" (the batch-1 KV cache,
- * [layer][K|V][head][max_text+max_audio][head_dim], fp32 on VX_PREC_F32 engines, else bf16). */
+ * [layer][K|V][head][max_text+max_audio][head_dim], fp32 on VX_PREC_F32 engines, else bf16), "score_ar_argmax" (int32 per AR row
+ * of the last vx_score / vx_score_batch, utterances concatenated: the argmax of the scored logits rows). */
 int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t offset_bytes, int64_t nbytes);
 
 /* Bytes vx_read_buffer's tap `name` holds on an engine created with *cfg, for the taps whose size follows from the
@@ -315,6 +349,15 @@ int vx_op_bgemm(int32_t epi, int32_t kv8, const void* A_bf16, const void* W_bf16
  * arguments: VX_ERR_ARG before any HIP call.  Synchronises `stream`. */
 int vx_op_ln_batch(float* x, const float* part, int32_t kgroups, const float* pbias, const float* gamma, const float* beta, void* h_bf16,
                    int32_t B, int32_t d, const int32_t* slot_map /* nullable */, void* stream);
+/* The scoring reduction (nll_rows_kernel; reference op: F.cross_entropy(reduction="none") and the rank behind
+ * MulticlassAccuracy(top_k), valle.py:873-881): `rows` rows of V <= 1088 fp32 logits with leading dimension ld, one int64 target
+ * per row, all DEVICE pointers.  nll[r] = logsumexp(row) - row[target] (max-subtracted, summed in a fixed order: a row's result
+ * does not depend on rows; -inf entries add 0; a -inf target entry gives +inf); rank[r] = entries strictly greater than the
+ * target's (ties count for the target); argmax[r] = first index of the maximum (torch.argmax's rule).  A target outside [0, V):
+ * nll NaN, rank -1, nothing read out of bounds.  Null pointers, rows < 1, V outside [1, 1088], ld < V: VX_ERR_ARG before any HIP
+ * call. */
+int vx_op_nll_rows(const float* logits, int32_t rows, int32_t V, int32_t ld, const int64_t* targets, float* nll, int32_t* rank,
+                   int32_t* argmax, void* stream);
 int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
                  int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 /* vx_op_sample with the nucleus filter after top-k (top_p as in vx_decode_params: 0 or >= 1 off, NaN / negative VX_ERR_ARG).

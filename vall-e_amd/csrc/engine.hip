@@ -152,6 +152,16 @@ struct vx_engine {
   float *yemb = nullptr, *nar_logits = nullptr, *ada = nullptr;
   long long *ids_text = nullptr, *ids_audio = nullptr, *ids_prompts = nullptr, *ids_samples = nullptr, *d_codes = nullptr;
   long long* d_fcodes = nullptr;  // teacher-forced NAR stages (vx_nar_ex): the caller's (T, Q) codes
+  // scoring (vx_score / vx_score_batch), allocated at the first call: logits rows of the AR scoring pass (sc_ld floats each),
+  // per-row results and int64 targets for sc_cap rows; the predict layer padded to NLL_MAXV rows for the MFMA GEMM; VALL-F:
+  // the text memory of the scored utterance (xkv_ar's layout - the batch-1 decode's own memory is not touched)
+  float *sc_logits = nullptr, *sc_nll = nullptr;
+  int *sc_rank = nullptr, *sc_argmax = nullptr;
+  long long* sc_tgt = nullptr;
+  size_t sc_cap = 0;
+  int sc_ld = 0, sc_rows = 0;  // sc_rows: AR rows scored by the last call (tap "score_ar_argmax")
+  void *sc_head = nullptr, *xkv_score = nullptr;
+  double t_score_ar = 0, t_score_nar = 0;
   // batched decode (slots)
   int bmax = 0;
   float *bx = nullptr, *bq = nullptr, *bpart = nullptr, *blogits = nullptr, *btrace = nullptr;
@@ -669,6 +679,15 @@ static NormW norm_at(const vx_engine* e, const std::vector<LayerW>& layers, int 
   return k == 0 ? NormW{l.n1_g, l.n1_b} : k == 1 ? NormW{l.n2_g, l.n2_b} : NormW{l.n3_g, l.n3_b};
 }
 
+// The scoring head (vx_score on MFMA engines): ar_predict_layer padded with zero rows to NLL_MAXV.  A derived operand like the
+// sharded step's re-laid-out matrices: rebuilt by every vx_finalize_weights once it exists, so a reload is scored on its own head.
+static int score_head_refresh(vx_engine* e) {
+  const size_t d = e->cfg.d_model;
+  HIPC(hipMemsetAsync(e->sc_head, 0, (size_t)NLL_MAXV * d * 2, e->es));
+  HIPC(hipMemcpyAsync(e->sc_head, e->w.at("ar_predict_layer.weight").p, (size_t)AR_VOCAB * d * 2, hipMemcpyDeviceToDevice, e->es));
+  return VX_OK;
+}
+
 extern "C" int vx_finalize_weights(vx_engine* e) {
   if (!e) return fail(VX_ERR_ARG, "null engine");
   ON_DEVICE(e->cfg.device);
@@ -741,6 +760,7 @@ extern "C" int vx_finalize_weights(vx_engine* e) {
     }
     HIPC(hipGetLastError());
   }
+  if (e->sc_head != nullptr) VXC(score_head_refresh(e));  // weights reloaded on a handle that has scored before
   HIPC(hipStreamSynchronize(e->es));
   e->finalized = true;
   return VX_OK;
@@ -2084,10 +2104,14 @@ extern "C" int vx_batch_run(vx_engine* e, int32_t min_stopped, int32_t poll_step
 // taken from forced[:, i+1] - the input the reference itself gave that stage when `forced` are its codes (valle.py:1133-1134).
 // Unsegmented only: prenets, VALL-F, pos_before_prenet (VALLE.continual) and stage_logits ((Q-1, T, 1024) fp32, host or
 // device: every stage's logits rows, valle.py:1128).
+// Scoring outputs of nar_run (vx_score): per utterance (Q-1, T_b) arrays, host or device; either may be null.  Needs `forced`:
+// stage i's rows are scored against forced[:, i+1] (valle.py:886-950 at the inference prompt layout).  The caller has reserved
+// e->sc_* for sum(T) rows.
+struct NarScore { float* const* nll; int32_t* const* rank; };
 static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* text_nar, const int32_t* S2,
                    const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens, const int32_t* T,
                    int64_t* const* codes_out, const int64_t* const* forced, void* stream, bool pos_before_prenet = false,
-                   float* stage_logits = nullptr) {
+                   float* stage_logits = nullptr, const NarScore* score = nullptr) {
   const vx_config& c = e->cfg;
   const int Q = c.num_quantizers, dn = c.nar_d_model;
   const bool vf = e->vallf, prenet = c.flags & VX_FLAG_PRENET, post = c.flags & VX_FLAG_POST_NORM;
@@ -2173,6 +2197,14 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
       VXC(gemm_rows(e, e->Hn, W<void>(e, "nar_predict_layers." + std::to_string(i) + ".weight"), nullptr, e->nar_logits,
                     trows, 1024, dn, GE_PLAIN, true));
       argmax_rows_kernel<<<(trows + 3) / 4, 256, 0, e->es>>>(e->nar_logits, 1024, trows, e->ids_samples, e->d_codes, Q, i + 1);
+      if (score) {
+        nll_rows_kernel<<<(trows + NLL_ROWS_PER_WG - 1) / NLL_ROWS_PER_WG, 256, 0, e->es>>>(e->nar_logits, trows, 1024, 1024, e->d_fcodes, Q, i + 1,
+                                                                                   e->sc_nll, e->sc_rank, nullptr);
+        for (int b = 0; b < n; ++b) {
+          if (score->nll) HIPC(hipMemcpyAsync(score->nll[b] + (size_t)i * T[b], e->sc_nll + toff[b], (size_t)T[b] * 4, hipMemcpyDefault, e->es));
+          if (score->rank) HIPC(hipMemcpyAsync(score->rank[b] + (size_t)i * T[b], e->sc_rank + toff[b], (size_t)T[b] * 4, hipMemcpyDefault, e->es));
+        }
+      }
       if (stage_logits) HIPC(hipMemcpyAsync(stage_logits + (size_t)i * trows * 1024, e->nar_logits, (size_t)trows * 1024 * 4, hipMemcpyDefault, e->es));
       if (forced && i < Q - 2)  // teacher forcing: the next stage sees the caller's codes of this stage (all segments at once)
         pick_col_kernel<<<(trows + 255) / 256, 256, 0, e->es>>>(e->d_fcodes, Q, i + 1, e->ids_samples, trows);
@@ -2187,7 +2219,7 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
   }
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(e->ev_t[5], e->es));
-  for (int b = 0; b < n; ++b)
+  for (int b = 0; codes_out && b < n; ++b)  // (scoring passes no codes_out)
     HIPC(hipMemcpyAsync(codes_out[b], e->d_codes + (size_t)toff[b] * Q, (size_t)T[b] * Q * 8, hipMemcpyDefault, e->es));
   HIPC(hipStreamSynchronize(e->es));
   float ms = 0.f;
@@ -2299,11 +2331,240 @@ extern "C" int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* te
   return nar_run(e, n, true, text_nar, S2, prompts, P, ar_tokens, T, codes_out, forced_codes, stream);
 }
 
+// ------------------------------------------------------------------------------ scoring (vx_score / vx_score_batch)
+// Teacher-forced likelihood of given codes: the AR stack over the whole sequence in one row pass (the prefill's mask, no KV
+// destination) and the NAR stages through nar_run with forced codes; every scored logits row is reduced on the device by
+// nll_rows_kernel.  Nothing the decode paths keep (ArState, the batch-1 cache and text memory, the slot caches) is written.
+
+// Scratch of the scoring passes for `rows` scored rows, and the once-built operands: the AR predict layer padded with zero rows
+// to NLL_MAXV (a multiple of the MFMA tile; the nll kernel reads V = 1025 of the ld = 1088 columns), VALL-F's text memory.
+static int score_reserve(vx_engine* e, size_t rows) {
+  const vx_config& c = e->cfg;
+  const int d = c.d_model;
+  if (use_mfma(e) && e->sc_head == nullptr) {
+    HIPC(hipMalloc(&e->sc_head, (size_t)NLL_MAXV * d * 2));
+    e->allocs.push_back(e->sc_head);
+    VXC(score_head_refresh(e));
+  }
+  if (e->vallf && e->xkv_score == nullptr) VXC(dalloc(e, &e->xkv_score, (size_t)c.num_layers * 2 * d * c.max_text * e->esz));
+  e->sc_ld = use_mfma(e) ? NLL_MAXV : AR_VOCAB;
+  if (rows <= e->sc_cap) return VX_OK;
+  HIPC(hipStreamSynchronize(e->es));
+  e->sc_rows = 0;  // the "score_ar_argmax" tap describes the buffer that goes away here
+  auto regrow = [&](void** p, size_t bytes) -> int {
+    for (auto& q : e->allocs) if (*p && q == *p) { (void)hipFree(q); q = nullptr; }
+    HIPC(hipMalloc(p, bytes));
+    if (poison_on()) { HIPC(hipMemsetAsync(*p, 0xFF, bytes, e->es)); HIPC(hipStreamSynchronize(e->es)); }
+    e->allocs.push_back(*p);
+    return VX_OK;
+  };
+  VXC(regrow((void**)&e->sc_logits, rows * e->sc_ld * 4));
+  VXC(regrow((void**)&e->sc_nll, rows * 4));
+  VXC(regrow((void**)&e->sc_rank, rows * 4));
+  VXC(regrow((void**)&e->sc_argmax, rows * 4));
+  VXC(regrow((void**)&e->sc_tgt, rows * 8));
+  e->sc_cap = rows;
+  return VX_OK;
+}
+
+// true when p is ordinary host memory (or HIP cannot tell, as on a machine without a device): such codes are range-checked here
+static bool host_readable(const void* p) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return true; }
+  return at.type == hipMemoryTypeHost || at.type == hipMemoryTypeUnregistered;
+}
+
+// The checks of one utterance to score (no HIP call before the last one, which only asks where `codes` lives); idx >= 0 names it
+// in a batch.  S2 <= 0 with text_nar == NULL is legal when the NAR part is skipped.
+static int check_score_utterance(vx_engine* e, const int64_t* text, int32_t S, const int64_t* text_nar, int32_t S2, const int64_t* codes,
+                                 int32_t A, int32_t P, bool want_ar, bool want_nar, int idx) {
+  const vx_config& c = e->cfg;
+  const int Q = c.num_quantizers;
+  char who[32] = "";
+  if (idx >= 0) snprintf(who, sizeof who, " (utterance %d)", idx);
+  if (!codes || (want_ar && !text) || (want_nar && !text_nar)) return fail(VX_ERR_ARG, "null argument%s", who);
+  if (A < 1 || P < 0 || P >= A) return fail(VX_ERR_ARG, "P=%d outside [0, A=%d)%s", P, A, who);
+  if ((want_ar && S <= 0) || (want_nar && S2 <= 0)) return fail(VX_ERR_ARG, "S / S2 must be > 0 (valle.py:991)%s", who);
+  if (want_ar && !c.prepend_bos && P < 1)
+    return fail(VX_ERR_ARG, "P=0 needs prepend_bos: without a BOS row no input row predicts the first frame%s", who);
+  if ((want_ar && S > c.max_text) || (want_nar && S2 > c.max_text) || A + 1 > c.max_audio)
+    return fail(VX_ERR_CAPACITY, "S=%d / S2=%d / A=%d exceed capacity (max_text %d, max_audio %d)%s", S, S2, A, c.max_text, c.max_audio, who);
+  if (host_readable(codes))
+    for (size_t i = 0; i < (size_t)A * Q; ++i)
+      if (codes[i] < 0 || codes[i] >= NUM_AUDIO_TOKENS)
+        return fail(VX_ERR_ARG, "code %lld at frame %zu, codebook %zu outside [0, %d)%s", (long long)codes[i], i / Q, i % Q, NUM_AUDIO_TOKENS, who);
+  return VX_OK;
+}
+
+// The AR scoring pass of n utterances (segmented: concatenated rows as in batch_prefill_impl; else n == 1, rows from 0): rows
+// [text | (BOS) codes[:, 0]] through the AR stack under the prefix mask, final norm + predict layer on the T + 1 rows that
+// predict codes[P, 0] ... codes[A-1, 0], EOS (valle.py:863-877), then nll_rows_kernel.  Outputs per utterance, T_b + 1 entries.
+static int score_ar_run(vx_engine* e, int n, bool segmented, const int64_t* const* text, const int32_t* S, const int64_t* const* codes,
+                        const int32_t* A, const int32_t* P, float* const* nll, int32_t* const* rank) {
+  const vx_config& c = e->cfg;
+  const int Q = c.num_quantizers, d = c.d_model, bos = c.prepend_bos ? 1 : 0;
+  const bool vf = e->vallf, prenet = c.flags & VX_FLAG_PRENET, post = c.flags & VX_FLAG_POST_NORM;
+  std::vector<int> start(n + 1), len(n), tlen(n), aoff(n), soff(n), roff(n + 1);
+  int arows = 0, srows = 0;
+  roff[0] = 0;
+  for (int b = 0; b < n; ++b) {
+    tlen[b] = vf ? 0 : S[b];
+    len[b] = tlen[b] + bos + A[b];
+    aoff[b] = arows; soff[b] = srows;
+    arows += A[b] + 1; srows += S[b];
+    roff[b + 1] = roff[b] + (A[b] - P[b]) + 1;
+  }
+  HIPC(hipEventRecord(e->ev_t[0], e->es));
+  RowSegs segs;
+  if (segmented) VXC(seg_layout(e, n, len.data(), tlen.data(), nullptr, d, arows, srows, start.data(), segs));
+  else { start[0] = 0; start[1] = len[0]; }
+  VXC(score_reserve(e, roff[n]));
+  static const long long bos_id = NUM_AUDIO_TOKENS + 1;  // valle.py:1006-1007
+  if (bos) HIPC(hipMemcpyAsync(e->ids_audio, &bos_id, 8, hipMemcpyHostToDevice, e->es));
+  const float* w_txt = W<float>(e, "ar_text_embedding.word_embeddings.weight");
+  const float* w_aud = W<float>(e, "ar_audio_embedding.word_embeddings.weight");
+  const float* a_txt = W<float>(e, "ar_text_position.alpha");
+  const float* a_aud = W<float>(e, "ar_audio_position.alpha");
+  for (int b = 0; b < n; ++b) {
+    long long* it = e->ids_text + soff[b];
+    long long* ic = e->d_fcodes + (size_t)aoff[b] * Q;  // the (A_b, Q) codes
+    HIPC(hipMemcpyAsync(it, text[b], (size_t)S[b] * 8, hipMemcpyDefault, e->es));
+    HIPC(hipMemcpyAsync(ic, codes[b], (size_t)A[b] * Q * 8, hipMemcpyDefault, e->es));
+    float* xb = e->X + (size_t)start[b] * d;
+    float* xa = xb + (size_t)tlen[b] * d;  // the audio rows
+    if (prenet) {  // embedding -> prenet -> position (valle.py:995-997, 1013-1015); unsegmented only
+      embed_accum_kernel<<<S[b], 256, 0, e->es>>>(it, 1, 0, w_txt, 512, d, e->pn_a, S[b], 1);
+      VXC(text_prenet_rows(e, 0, e->pn_a, e->pn_a, S[b], d));
+      add_pos_kernel<<<S[b], 256, 0, e->es>>>(e->pn_a, d, a_txt, e->pe_ar, 0, e->X, S[b]);
+    } else {
+      embed_pos_kernel<<<S[b], 256, 0, e->es>>>(it, 1, 0, w_txt, 512, d, a_txt, e->pe_ar, 0, e->X + (size_t)start[b] * d, S[b]);
+    }
+    // VALL-F: the text rows become the per-layer memory K / V (valle.py:598-602), then the audio rows take X from row 0
+    if (vf) { VXC(cast_rows(e, e->X, e->Hn, (size_t)S[b] * d)); VXC(memory_kv(e, e->ar_l, e->xkv_score, S[b], d, c.nhead)); }
+    if (prenet) {
+      if (bos) embed_accum_kernel<<<1, 256, 0, e->es>>>(e->ids_audio, 1, 0, w_aud, 1025 + bos, d, e->pn_a, 1, 1);
+      embed_accum_kernel<<<A[b], 256, 0, e->es>>>(ic, Q, 0, w_aud, 1025 + bos, d, e->pn_a + (size_t)bos * d, A[b], 1);
+      VXC(audio_prenet_rows(e, 0, e->pn_a, e->pn_b, bos + A[b], d));
+      add_pos_kernel<<<bos + A[b], 256, 0, e->es>>>(e->pn_b, d, a_aud, e->pe_ar, 0, xa, bos + A[b]);
+    } else {
+      if (bos) embed_pos_kernel<<<1, 256, 0, e->es>>>(e->ids_audio, 1, 0, w_aud, 1025 + bos, d, a_aud, e->pe_ar, 0, xa, 1);
+      embed_pos_kernel<<<A[b], 256, 0, e->es>>>(ic, Q, 0, w_aud, 1025 + bos, d, a_aud, e->pe_ar, bos, xa + (size_t)bos * d, A[b]);
+    }
+  }
+  VXC(run_stack(e, e->ar_l, start[n], d, c.nhead, segmented ? 0 : tlen[0], -1, segs, KvDst(),
+                vf ? TextMem{e->xkv_score, S[0]} : TextMem()));
+  // final norm (pre-norm; a post-norm stack's rows are already normalised) on the scored rows, compacted to [sum (T + 1)][d]
+  for (int b = 0; b < n; ++b) {
+    const int T = A[b] - P[b], first = tlen[b] + (bos ? P[b] : P[b] - 1);
+    const float* xr = e->X + (size_t)(start[b] + first) * d;
+    void* hr = (char*)e->Hn + (size_t)roff[b] * d * e->esz;
+    if (post) VXC(cast_rows(e, xr, hr, (size_t)(T + 1) * d));
+    else VXC(ln_rows(e, xr, W<float>(e, "ar_decoder.norm.weight"), W<float>(e, "ar_decoder.norm.bias"), nullptr, nullptr, hr, T + 1, d));
+    score_targets_kernel<<<(T + 1 + 255) / 256, 256, 0, e->es>>>(e->d_fcodes + (size_t)aoff[b] * Q, Q, 0, P[b], T, NUM_AUDIO_TOKENS, 1,
+                                                                 e->sc_tgt + roff[b]);
+  }
+  const int R = roff[n], ld = e->sc_ld;
+  VXC(gemm_rows(e, e->Hn, e->sc_head ? e->sc_head : W<void>(e, "ar_predict_layer.weight"), nullptr, e->sc_logits, R, ld, d, GE_PLAIN, true));
+  nll_rows_kernel<<<(R + NLL_ROWS_PER_WG - 1) / NLL_ROWS_PER_WG, 256, 0, e->es>>>(e->sc_logits, R, AR_VOCAB, ld, e->sc_tgt, 1, 0, e->sc_nll,
+                                                                           e->sc_rank, e->sc_argmax);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(e->ev_t[1], e->es));
+  for (int b = 0; b < n; ++b) {
+    const size_t nb = (size_t)(roff[b + 1] - roff[b]) * 4;
+    if (nll && nll[b]) HIPC(hipMemcpyAsync(nll[b], e->sc_nll + roff[b], nb, hipMemcpyDefault, e->es));
+    if (rank && rank[b]) HIPC(hipMemcpyAsync(rank[b], e->sc_rank + roff[b], nb, hipMemcpyDefault, e->es));
+  }
+  HIPC(hipStreamSynchronize(e->es));  // the host arrays above and the staging are free again
+  float ms = 0.f;
+  HIPC(hipEventElapsedTime(&ms, e->ev_t[0], e->ev_t[1]));
+  e->t_score_ar = ms;
+  e->sc_rows = R;
+  return VX_OK;
+}
+
+// The NAR scoring pass: nar_run on prompts = codes[:P], ar_tokens = codes[P:, 0] (as a strided view is not what nar_run takes,
+// the column is staged through the device), forced = codes[P:].
+static int score_nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* text_nar, const int32_t* S2, const int64_t* const* codes,
+                         const int32_t* A, const int32_t* P, float* const* nll, int32_t* const* rank, void* stream) {
+  const int Q = e->cfg.num_quantizers;
+  std::vector<const int64_t*> forced(n), tok(n);
+  std::vector<int32_t> T(n);
+  size_t trows = 0;
+  for (int b = 0; b < n; ++b) { T[b] = A[b] - P[b]; trows += T[b]; }
+  ON_DEVICE(e->cfg.device);
+  VXC(score_reserve(e, trows));
+  // codebook 0 of the scored frames, contiguous per utterance: gathered on the device into sc_tgt (free between the two passes)
+  VXC(sync_in(e, stream));
+  size_t off = 0;
+  for (int b = 0; b < n; ++b) {
+    forced[b] = codes[b] + (size_t)P[b] * Q;
+    HIPC(hipMemcpyAsync(e->d_fcodes, forced[b], (size_t)T[b] * Q * 8, hipMemcpyDefault, e->es));
+    score_targets_kernel<<<(T[b] + 255) / 256, 256, 0, e->es>>>(e->d_fcodes, Q, 0, 0, T[b], 0, 0, e->sc_tgt + off);
+    tok[b] = (const int64_t*)(e->sc_tgt + off);
+    off += T[b];
+  }
+  HIPC(hipGetLastError());
+  const NarScore sc{nll, rank};
+  // what nar_run records about "the last NAR call" (timings out[2] / out[7] / out[8], the sizes of the nar_logits / nar_x taps) stays
+  // that of the caller's own last vx_nar: the taps' buffers are scratch, but their sizes and the timings are not scoring's to change
+  const double t_nar = e->t_nar, t_gemm = e->t_gemm, flops = e->gemm_flops_done;
+  const int last_T = e->last_T, last_N = e->last_N;
+  const int rc = nar_run(e, n, segmented, text_nar, S2, codes, P, tok.data(), T.data(), nullptr, forced.data(), stream, false, nullptr, &sc);
+  e->t_score_nar = e->t_nar;
+  e->t_nar = t_nar; e->t_gemm = t_gemm; e->gemm_flops_done = flops;
+  e->last_T = last_T; e->last_N = last_N;
+  return rc;
+}
+
+extern "C" int vx_score(vx_engine* e, const int64_t* text, int32_t S, const int64_t* text_nar, int32_t S2, const int64_t* codes,
+                        int32_t A, int32_t P, float* nll_ar, int32_t* rank_ar, float* nll_nar, int32_t* rank_nar, void* stream) {
+  if (!e) return fail(VX_ERR_ARG, "null argument");
+  if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+  const bool want_ar = nll_ar || rank_ar, want_nar = (nll_nar || rank_nar) && e->cfg.num_quantizers > 1;
+  VXC(check_score_utterance(e, text, S, text_nar, S2, codes, A, P, want_ar, want_nar, -1));
+  ON_DEVICE(e->cfg.device);
+  if (want_ar) {
+    VXC(sync_in(e, stream));
+    VXC(score_ar_run(e, 1, false, &text, &S, &codes, &A, &P, &nll_ar, &rank_ar));
+    VXC(sync_out(e, stream));
+  }
+  if (want_nar) VXC(score_nar_run(e, 1, false, &text_nar, &S2, &codes, &A, &P, nll_nar ? &nll_nar : nullptr, rank_nar ? &rank_nar : nullptr, stream));
+  return VX_OK;
+}
+
+extern "C" int vx_score_batch(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S, const int64_t* const* text_nar,
+                              const int32_t* S2, const int64_t* const* codes, const int32_t* A, const int32_t* P, float* const* nll_ar,
+                              int32_t* const* rank_ar, float* const* nll_nar, int32_t* const* rank_nar, void* stream) {
+  if (!e) return fail(VX_ERR_ARG, "null argument");
+  if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+  const vx_config& c = e->cfg;
+  if (e->vallf) return fail(VX_ERR_UNSUPPORTED, "vx_score_batch: VALL-F scores per utterance (vx_score)");
+  if (c.flags & VX_FLAG_PRENET) return fail(VX_ERR_UNSUPPORTED, "vx_score_batch: prenet models score per utterance (vx_score)");
+  if (!e->bf16 || !use_mfma(e)) return fail(VX_ERR_UNSUPPORTED, "vx_score_batch needs the bf16 MFMA row kernels; use vx_score");
+  const bool want_ar = nll_ar || rank_ar, want_nar = (nll_nar || rank_nar) && c.num_quantizers > 1;
+  if (!codes || !A || !P || (want_ar && (!text || !S)) || (want_nar && (!text_nar || !S2))) return fail(VX_ERR_ARG, "null argument");
+  if (n < 1 || n > BMAX) return fail(VX_ERR_ARG, "n must be 1..%d", BMAX);
+  for (int b = 0; b < n; ++b) {
+    VXC(check_score_utterance(e, want_ar ? text[b] : nullptr, want_ar ? S[b] : 0, want_nar ? text_nar[b] : nullptr, want_nar ? S2[b] : 0,
+                              codes[b], A[b], P[b], want_ar, want_nar, b));
+    if ((nll_ar && !nll_ar[b]) || (rank_ar && !rank_ar[b]) || (nll_nar && !nll_nar[b]) || (rank_nar && !rank_nar[b]))
+      return fail(VX_ERR_ARG, "null output (utterance %d)", b);
+  }
+  ON_DEVICE(c.device);
+  if (want_ar) {
+    VXC(sync_in(e, stream));
+    VXC(score_ar_run(e, n, true, text, S, codes, A, P, nll_ar, rank_ar));
+    VXC(sync_out(e, stream));
+  }
+  if (want_nar) VXC(score_nar_run(e, n, true, text_nar, S2, codes, A, P, nll_nar, rank_nar, stream));
+  return VX_OK;
+}
+
 extern "C" int vx_get_timings(vx_engine* e, double* out, int32_t n) {
   if (!e || !out) return fail(VX_ERR_ARG, "null argument");
-  const double v[10] = {e->t_prefill, e->t_decode, e->t_nar, (double)e->n_pass, e->n_launch, e->t_bdecode, e->n_blaunch,
-                        e->t_gemm, e->gemm_flops_done, (double)e->gexec_nodes};
-  for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
+  const double v[12] = {e->t_prefill, e->t_decode, e->t_nar, (double)e->n_pass, e->n_launch, e->t_bdecode, e->n_blaunch,
+                        e->t_gemm, e->gemm_flops_done, (double)e->gexec_nodes, e->t_score_ar, e->t_score_nar};
+  for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
   return VX_OK;
 }
 
@@ -2349,6 +2610,7 @@ extern "C" int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t
     size = (int64_t)e->bmax * e->bkv_slot * (e->kv8 ? 1 : 2);
   }
   else if (n == "ar_kv") { src = (const char*)e->kv; size = config_buffer_bytes(e->cfg, n); }
+  else if (n == "score_ar_argmax" && e->sc_argmax) { src = (const char*)e->sc_argmax; size = (int64_t)e->sc_rows * 4; }
   else if (n == "batch_kv_scale" && e->kv8) { src = (const char*)e->bkv8s; size = (int64_t)e->bmax * e->bkv_slot / 16; }
   else return fail(VX_ERR_ARG, "unknown buffer '%s'", name);
   if (off < 0 || nbytes < 0 || off + nbytes > size) return fail(VX_ERR_ARG, "read of '%s' out of range (%lld+%lld > %lld)", name, (long long)off, (long long)nbytes, (long long)size);
@@ -2506,6 +2768,18 @@ extern "C" int vx_op_attention(int32_t prec, int32_t mfma, const void* qkv, void
 
 // Stand-alone sampling check: runs the step's sampling kernel on caller logits with a scratch
 // state (no stop-rule side effects are reported; out[0] = sampled index, out[1] = argmax).
+extern "C" int vx_op_nll_rows(const float* logits, int32_t rows, int32_t V, int32_t ld, const int64_t* targets, float* nll,
+                              int32_t* rank, int32_t* argmax, void* stream) {
+  if (!logits || !targets || !nll || !rank || !argmax) return fail(VX_ERR_ARG, "null argument");
+  if (rows < 1) return fail(VX_ERR_ARG, "rows must be >= 1 (got %d)", rows);
+  if (V < 1 || V > NLL_MAXV) return fail(VX_ERR_ARG, "V=%d outside [1, %d]", V, NLL_MAXV);
+  if (ld < V) return fail(VX_ERR_ARG, "ld=%d < V=%d", ld, V);
+  nll_rows_kernel<<<(rows + NLL_ROWS_PER_WG - 1) / NLL_ROWS_PER_WG, 256, 0, (hipStream_t)stream>>>(
+      logits, rows, V, ld, (const long long*)targets, 1, 0, nll, rank, argmax);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
 extern "C" int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
                             int32_t* out, void* stream) {
   if (V < 2 || V > 2048) return fail(VX_ERR_UNSUPPORTED, "sample: V=%d", V);

@@ -505,6 +505,84 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   }
 }
 
+// ---- scoring: logits rows -> negative log-likelihood, rank and argmax of a given target (F.cross_entropy(reduction="none") and
+// the rank behind MulticlassAccuracy(top_k), valle.py:827-881 / 886-950) -------------------------------------------------------
+// Row r holds V <= NLL_MAXV fp32 logits at logits + r * ld; its target is targets[r * t_stride + t_off] (int64).
+//   nll[r]    = logsumexp(row) - row[target], max-subtracted; the sum runs in fp64 in a fixed order (lane-local in ascending
+//               column order, then the butterfly over the 64 lanes), so a row's result depends neither on `rows` nor on where
+//               the row sits in the launch.  -inf entries add 0; a target entry of -inf gives +inf (never NaN).
+//   rank[r]   = entries STRICTLY greater than row[target]: ties count in the target's favour (the direction of the sampler's
+//               top-k threshold, which keeps ties), so top-k accuracy is rank < k.
+//   argmax[r] = the first index of the largest value (ValIdx `better`: on equal values the lower index wins), the rule of
+//               argmax_rows_kernel and torch.argmax.
+// A target outside [0, V) (device targets only: host targets are refused before the launch): the load is clamped, nll = NaN and
+// rank = -1.  One wave per row, 4 rows per workgroup; the row is read once and stays in registers for both passes.  Any of
+// nll / rank / argmax may be null.
+constexpr int NLL_MAXV = 1088, NLL_ROWS_PER_WG = 4;
+__global__ __launch_bounds__(256) void nll_rows_kernel(const float* __restrict__ logits, int rows, int V, int ld,
+                                                       const long long* __restrict__ targets, int t_stride, int t_off,
+                                                       float* __restrict__ nll, int* __restrict__ rank, int* __restrict__ argmax) {
+  constexpr int NV = NLL_MAXV / 64;
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * NLL_ROWS_PER_WG + (threadIdx.x >> 6);
+  if (r >= rows) return;  // wave-uniform
+  const float* row = logits + (size_t)r * ld;
+  const long long t_raw = targets[(size_t)r * t_stride + t_off];
+  const bool t_ok = t_raw >= 0 && t_raw < V;
+  const int t = t_ok ? (int)t_raw : 0;
+  float v[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = i * 64 + lane;
+    v[i] = c < V ? row[c] : -INFINITY;  // padding behaves as a -inf entry: adds 0, is never greater, never the argmax of a real row
+  }
+  // pass 1: maximum and its first index
+  ValIdx best{-INFINITY, 0x7fffffff};
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = i * 64 + lane;
+    if (c < V) best = better(best, ValIdx{v[i], c});
+  }
+  best = wave_argmax(best);
+  // pass 2 (registers only): the target's value, the sum and the rank
+  float tv_l = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+    if (i == (t >> 6)) tv_l = v[i];
+  const float tv = __shfl(tv_l, t & 63, WAVE);
+  double s = 0.0;
+  int gt = 0;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    s += (double)expf(v[i] - best.v);  // exp(-inf) = 0
+    gt += v[i] > tv ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o, WAVE);
+    gt += __shfl_xor(gt, o, WAVE);
+  }
+  if (lane != 0) return;
+  if (argmax) argmax[r] = best.i;
+  if (rank) rank[r] = t_ok ? gt : -1;
+  if (nll) {
+    float out;
+    if (!t_ok) out = __int_as_float(0x7fc00000);
+    else if (tv == -INFINITY) out = INFINITY;
+    else out = (float)(((double)best.v - (double)tv) + log(s));
+    nll[r] = out;
+  }
+}
+
+// dst[j] = codes[(row0 + j) * Q + col] for j < n, then `tail` entries equal to tail_id: the AR targets of a scored utterance
+// (codebook 0 of the scored frames, then EOS; valle.py:863-877)
+__global__ void score_targets_kernel(const long long* __restrict__ codes, int Q, int col, int row0, int n, long long tail_id,
+                                     int tail, long long* __restrict__ dst) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) dst[j] = codes[(size_t)(row0 + j) * Q + col];
+  else if (j < n + tail) dst[j] = tail_id;
+}
+
 __global__ void copy_col_kernel(const long long* __restrict__ src, long long* __restrict__ codes, int rows, int Q, int col) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r < rows) codes[(size_t)r * Q + col] = src[r];

@@ -79,6 +79,9 @@ _SIGS = {
     "vx_batch_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "vx_nar_batch": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_void_p]),
     "vx_nar_batch_ex": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.c_void_p]),
+    "vx_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
+                 + [C.c_void_p] * 4 + [C.c_void_p]),
+    "vx_score_batch": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 11 + [C.c_void_p]),
     "vx_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
     "vx_read_buffer": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int64]),
     "vx_buffer_bytes": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
@@ -99,6 +102,7 @@ _SIGS = {
                     C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     "vx_op_ln_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                        C.c_void_p]),
+    "vx_op_nll_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_void_p]),
     "vx_op_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "vx_op_sample_topp": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
                                     C.c_void_p]),
@@ -421,6 +425,58 @@ class Engine:
                                         ptrs(outs), fc, stream))
         return outs
 
+    # -- scoring (vx_score / vx_score_batch) ----------------------------------------------------------
+    def score(self, text: torch.Tensor, text_nar: torch.Tensor, codes: torch.Tensor, prompt_frames: int, ar: bool = True,
+              nar: bool = True, stream=None):
+        """Teacher-forced score of ``codes`` (A, Q) with the first ``prompt_frames`` frames as the prompt (vx_score).  Returns
+        device tensors (ar_nll (T+1,) fp32, ar_rank (T+1,) int32, nar_nll (Q-1, T) fp32, nar_rank (Q-1, T) int32); a part that
+        is switched off (or the NAR part of a Q = 1 model) is None."""
+        text = text.to(torch.int64).contiguous()
+        text_nar = text_nar.to(torch.int64).contiguous()
+        codes = codes.to(torch.int64).contiguous()
+        A, Q = codes.shape
+        assert Q == self.cfg.num_quantizers, (Q, self.cfg.num_quantizers)
+        P, T = int(prompt_frames), A - int(prompt_frames)
+        dev = torch.device("cuda", self.device)
+        nar = nar and Q > 1
+        an = torch.empty(max(T + 1, 0), dtype=torch.float32, device=dev) if ar else None
+        ak = torch.empty(max(T + 1, 0), dtype=torch.int32, device=dev) if ar else None
+        nn_ = torch.empty((Q - 1, max(T, 0)), dtype=torch.float32, device=dev) if nar else None
+        nk = torch.empty((Q - 1, max(T, 0)), dtype=torch.int32, device=dev) if nar else None
+        _check(self.lib.vx_score(self.h, _ptr(text), text.numel(), _ptr(text_nar), text_nar.numel(), _ptr(codes), A, P,
+                                 _ptr(an), _ptr(ak), _ptr(nn_), _ptr(nk), stream))
+        return an, ak, nn_, nk
+
+    def score_batch(self, texts, texts_nar, codes, prompt_frames, ar: bool = True, nar: bool = True, stream=None):
+        """``score`` of n utterances in one pass over the concatenated rows (vx_score_batch): lists of per-utterance tensors and
+        prompt lengths -> list of per-utterance (ar_nll, ar_rank, nar_nll, nar_rank) device tensors."""
+        n, Q = len(texts), self.cfg.num_quantizers
+        texts = [t.to(torch.int64).contiguous() for t in texts]
+        texts_nar = [t.to(torch.int64).contiguous() for t in texts_nar]
+        codes = [c.to(torch.int64).contiguous() for c in codes]
+        P = [int(p) for p in prompt_frames]
+        A = [c.shape[0] for c in codes]
+        dev = torch.device("cuda", self.device)
+        nar = nar and Q > 1
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        an = [mk(max(a - p + 1, 0), torch.float32) for a, p in zip(A, P)] if ar else None
+        ak = [mk(max(a - p + 1, 0), torch.int32) for a, p in zip(A, P)] if ar else None
+        nn_ = [mk((Q - 1, max(a - p, 0)), torch.float32) for a, p in zip(A, P)] if nar else None
+        nk = [mk((Q - 1, max(a - p, 0)), torch.int32) for a, p in zip(A, P)] if nar else None
+        ptrs = lambda ts: None if ts is None else (C.c_void_p * n)(*[_ptr(t) for t in ts])
+        ints = lambda vs: (C.c_int32 * n)(*vs)
+        _check(self.lib.vx_score_batch(self.h, n, ptrs(texts), ints([t.numel() for t in texts]), ptrs(texts_nar),
+                                       ints([t.numel() for t in texts_nar]), ptrs(codes), ints(A), ints(P), ptrs(an), ptrs(ak),
+                                       ptrs(nn_), ptrs(nk), stream))
+        none = [None] * n
+        return list(zip(an or none, ak or none, nn_ or none, nk or none))
+
+    def score_timings(self):
+        """Device ms of the AR and the NAR part of the last ``score`` / ``score_batch``."""
+        buf = (C.c_double * 12)()
+        _check(self.lib.vx_get_timings(self.h, buf, 12))
+        return dict(score_ar_ms=buf[10], score_nar_ms=buf[11])
+
     def timings(self):
         buf = (C.c_double * 10)()
         _check(self.lib.vx_get_timings(self.h, buf, 10))
@@ -625,6 +681,21 @@ def op_ln_batch(x, gamma, beta, h, B, part=None, pbias=None, kgroups=0, slot_map
     assert x.dtype == torch.float32 and h.dtype == torch.bfloat16
     _check(lib.vx_op_ln_batch(_ptr(x), _ptr(part), kgroups, _ptr(pbias), _ptr(gamma), _ptr(beta), _ptr(h), B, d, _i32(slot_map),
                               current_stream_ptr(x.device)))
+
+
+def op_nll_rows(logits, targets, V=None):
+    """nll_rows_kernel on device logits (rows, ld) fp32 (a row's first V columns; default all) and int64 targets (rows,):
+    (nll fp32, rank int32, argmax int32), each (rows,)."""
+    lib = load_library()
+    rows, ld = logits.shape
+    V = ld if V is None else int(V)
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and targets.dtype == torch.int64
+    nll = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    rank = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    am = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    _check(lib.vx_op_nll_rows(_ptr(logits), rows, V, ld, _ptr(targets.contiguous()), _ptr(nll), _ptr(rank), _ptr(am),
+                              current_stream_ptr(logits.device)))
+    return nll, rank, am
 
 
 def op_sample(logits, top_k, temperature, exp_noise):

@@ -10,7 +10,8 @@ does on the host: argument checks, the prefix-mode text trim, RNG bookkeeping, e
 from __future__ import annotations
 
 from collections import OrderedDict, namedtuple
-from typing import Optional
+from dataclasses import dataclass
+from typing import List, Optional
 
 import torch
 
@@ -44,6 +45,43 @@ def _check_top_p(top_p) -> float:
     if not 0.0 < v <= 1.0:  # NaN fails too
         raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
     return v
+
+
+@dataclass
+class ScoreResult:
+    """What ``VALLE.score`` returns: the per-row terms of the reference's validation numbers (VALLE.forward, valle.py:827-881 for
+    the AR decoder, 886-950 for a NAR stage) and their aggregates.  T scored frames, Q codebooks.
+      ar_nll (T+1,) fp32 / ar_rank (T+1,) int32   rows predicting codes[P:, 0] and the closing EOS
+      nar_nll (Q-1, T) / nar_rank (Q-1, T)        stage i's rows against codes[P:, i+1]; None for Q = 1
+      ar_loss, nar_loss[i]                        sums of the nll (F.cross_entropy(reduction="sum"))
+      ar_topk_acc, nar_topk_acc[i]                mean(rank < top_k) over the rows whose target is not EOS (1024), the
+                                                  reference's MulticlassAccuracy(top_k, ignore_index=1024)"""
+    ar_nll: Optional[torch.Tensor]
+    ar_rank: Optional[torch.Tensor]
+    nar_nll: Optional[torch.Tensor]
+    nar_rank: Optional[torch.Tensor]
+    ar_loss: Optional[float]
+    nar_loss: Optional[List[float]]
+    ar_topk_acc: Optional[float]
+    nar_topk_acc: Optional[List[float]]
+    top_k: int = 10
+
+
+def aggregate_score(ar_nll, ar_rank, ar_targets, nar_nll, nar_rank, nar_targets, top_k: int = 10) -> ScoreResult:
+    """Per-row scores -> ScoreResult.  ``ar_targets`` (T+1,) / ``nar_targets`` (Q-1, T): the ids the rows were scored against;
+    rows whose target is NUM_AUDIO_TOKENS (EOS) count in the losses and not in the accuracies, as in the reference, where the
+    loss has no ignore_index and the metric has ignore_index=1024 (valle.py:873-881)."""
+    def acc(rank, tgt):
+        keep = tgt.to(rank.device) != NUM_AUDIO_TOKENS
+        return float((rank[keep] < top_k).float().mean()) if bool(keep.any()) else float("nan")
+
+    ar_loss = ar_acc = nar_loss = nar_acc = None
+    if ar_nll is not None:
+        ar_loss, ar_acc = float(ar_nll.double().sum()), acc(ar_rank, ar_targets)
+    if nar_nll is not None:
+        nar_loss = [float(r.double().sum()) for r in nar_nll]
+        nar_acc = [acc(r, t) for r, t in zip(nar_rank, nar_targets)]
+    return ScoreResult(ar_nll, ar_rank, nar_nll, nar_rank, ar_loss, nar_loss, ar_acc, nar_acc, int(top_k))
 
 
 class VALLE:
@@ -345,6 +383,69 @@ class VALLE:
             if pending and (len(pending) >= nar_group or nxt >= N):
                 done, pending = pending, []
                 yield from self._run_nar(eng, done, batched_nar)
+
+    # ---- scoring ---------------------------------------------------------------------------------------
+    def _score_args(self, x, x_lens, y, prompt_frames, enroll_x_lens, top_k):
+        """Checks of one utterance to score, as ``inference``'s, -> (text, text_nar, codes (A, Q), P)."""
+        self._check_utterance((x, x_lens, y, enroll_x_lens))
+        Q, bos = self.num_quantizers, int(self.ar_audio_prepend_bos)
+        A, P = int(y.shape[1]), int(prompt_frames)
+        if y.shape[2] < Q:
+            raise ValueError(f"y has {y.shape[2]} codebooks, the model {Q}")
+        if not 0 <= P < A:
+            raise ValueError(f"prompt_frames must be in [0, {A}) (got {P})")
+        if P == 0 and not bos:
+            raise ValueError("prompt_frames=0 needs prepend_bos: without a BOS row nothing predicts the first frame")
+        if int(top_k) < 1:
+            raise ValueError(f"top_k must be >= 1 (got {top_k})")
+        text_nar = x[0]
+        if self.prefix_mode in [2, 4] and enroll_x_lens is not None:  # the NAR text trim of inference (valle.py:1068-1079)
+            enrolled_len = int(enroll_x_lens.max().item())
+            text_nar = torch.concat([x[0][:1], x[0][enrolled_len - 1:]])
+        return x[0], text_nar, y[0, :, :Q].contiguous(), P
+
+    @staticmethod
+    def _score_result(codes, P, parts, top_k) -> ScoreResult:
+        an, ak, nn_, nk = parts
+        eos = torch.full((1,), NUM_AUDIO_TOKENS, dtype=torch.int64, device=codes.device)
+        return aggregate_score(an, ak, torch.cat([codes[P:, 0], eos]), nn_, nk, codes[P:, 1:].t(), top_k)
+
+    @torch.no_grad()
+    def score(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor, prompt_frames: int = 0, top_k: int = 10,
+              enroll_x_lens: Optional[torch.Tensor] = None) -> ScoreResult:
+        """Engine extension: how well the model predicts the given codes, teacher-forced (vx_score).  x (1,S), x_lens (1,), y
+        (1,A,Q) as for ``inference``; the first ``prompt_frames`` frames of y are the prompt, the others are scored.  With
+        ``prompt_frames=0`` on a prepend_bos model (or 1 without BOS) ``ar_loss`` / ``ar_topk_acc`` are the reference's summed
+        AR loss and ArTop10Accuracy of VALLE.forward at batch size 1 (valle.py:863-881).  ``enroll_x_lens``: the text trim of
+        prefix modes 2 / 4, as in ``inference``."""
+        text, text_nar, codes, P = self._score_args(x, x_lens, y, prompt_frames, enroll_x_lens, top_k)
+        return self._score_result(codes, P, self.engine().score(text, text_nar, codes, P), top_k)
+
+    @torch.no_grad()
+    def score_batch(self, utterances, prompt_frames=0, top_k: int = 10) -> List[ScoreResult]:
+        """``score`` of several utterances, (x, x_lens, y[, enroll_x_lens]) each; ``prompt_frames``: one value or one per
+        utterance.  Groups of at most max_batch (64 on a batch-1 engine) go through one pass over the concatenated rows
+        (vx_score_batch); where the engine has no such pass (fp32, VALL-F, prenets, other head sizes) every utterance is
+        scored by itself."""
+        from .engine import BMAX, VxError
+
+        eng = self.engine()
+        Ps = list(prompt_frames) if isinstance(prompt_frames, (list, tuple)) else [prompt_frames] * len(utterances)
+        if len(Ps) != len(utterances):
+            raise ValueError(f"{len(Ps)} prompt_frames for {len(utterances)} utterances")
+        args = [self._score_args(u[0], u[1], u[2], p, u[3] if len(u) > 3 else None, top_k) for u, p in zip(utterances, Ps)]
+        group = eng.max_batch if eng.max_batch >= 2 else BMAX
+        out = []
+        for g0 in range(0, len(args), group):
+            g = args[g0 : g0 + group]
+            try:
+                parts = eng.score_batch([a[0] for a in g], [a[1] for a in g], [a[2] for a in g], [a[3] for a in g])
+            except VxError as err:
+                if err.code != 5:  # VX_ERR_UNSUPPORTED: exactly where vx_score_batch refuses
+                    raise
+                parts = [eng.score(*a) for a in g]
+            out += [self._score_result(a[2], a[3], p, top_k) for a, p in zip(g, parts)]
+        return out
 
     @torch.no_grad()
     def continual(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
