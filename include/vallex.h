@@ -73,12 +73,23 @@ enum vx_flags {
                                head_dim 64, d_model in {128, 256, 512, 1024}, bf16 precision, bf16 slot caches) the slots decode VALL-F too:
                                every slot keeps its own text memory (2 L max_text d bf16).  VALL-F slots are prefilled one by
                                one (vx_batch_prefill, VX_ADMIT_PER_SLOT) and their NAR stages run per utterance (vx_nar);
-                               vx_batch_prefill_all, VX_ADMIT_BATCHED and vx_nar_batch return VX_ERR_UNSUPPORTED */
-  VX_FLAG_KV_FP8 = 64       /* the slot caches of the batched decode (vx_batch_*) hold OCP e4m3 codes with one E8M0 scale per
+                               vx_batch_prefill_all, VX_ADMIT_BATCHED and vx_nar_batch return VX_ERR_UNSUPPORTED unless
+                               VX_FLAG_VALLF_ROWS is set too */
+  VX_FLAG_KV_FP8 = 64,      /* the slot caches of the batched decode (vx_batch_*) hold OCP e4m3 codes with one E8M0 scale per
                                16 channels of a K / V row instead of bf16 values: 0.53x the bytes the batched
                                step's attention reads.  Needs max_batch >= 2, VX_PREC_BF16 or VX_PREC_FP8_NAR, head_dim 64 and a
                                pre-norm VALL-E without prenets (else VX_ERR_UNSUPPORTED, before any HIP call; VALL-F included).  The batch-1 cache
                                (vx_ar_*) stays bf16 */
+  VX_FLAG_VALLF_ROWS = 128  /* VALL-F row passes over concatenated utterances: vx_batch_prefill_all, VX_ADMIT_BATCHED and
+                               vx_nar_batch / vx_nar_batch_ex accept the engine; the cross-attention of those passes runs per
+                               segment over each utterance's own text memory (cross_attn_seg_kernel, bf16 MFMA).  Valid only
+                               together with VX_FLAG_VALLF and max_batch >= 2 within the VALL-F slot limits (pre-norm, no prenets,
+                               head_dim 64, d_model in {128, 256, 512, 1024}, bf16 precision, bf16 slot caches); anything else is
+                               VX_ERR_UNSUPPORTED from vx_create, before any HIP call.  Cost: the engine also keeps a packed
+                               text-memory buffer for the batched NAR pass, [layer][K|V][head][text rows][64] bf16 =
+                               2 nar_num_layers nar_d_model bf16 per text row, max_text rows at vx_create and grown with the
+                               other row buffers to the sum of the texts of the largest vx_nar_batch call.  Without the flag a
+                               VALL-F engine behaves exactly as before.  vx_score_batch still refuses VALL-F */
 };
 
 /* Mirrors VALLE.__init__ (valle.py:727-760) / get_model (models/__init__.py:112-124). */
@@ -183,8 +194,9 @@ int vx_nar_continual(vx_engine* e, const int64_t* text_nar, int32_t S2, const in
 int vx_batch_prefill(vx_engine* e, int32_t slot, const int64_t* text, int32_t S, const int64_t* prompt_cb0, int32_t P,
                      void* stream);
 /* All n slots' prefills in one pass over the concatenated rows (slot z = utterance z): same contract as n calls of
- * vx_batch_prefill(z, text[z], S[z], prompt_cb0[z], P[z]); bf16 VALL-E engines only (VALL-F: VX_ERR_UNSUPPORTED).  The
- * pointer arrays and S / P live on the host, text[z] / prompt_cb0[z] may be host or device pointers. */
+ * vx_batch_prefill(z, text[z], S[z], prompt_cb0[z], P[z]); bf16 VALL-E engines, and VALL-F engines created with
+ * VX_FLAG_VALLF_ROWS (the rows are then the audio rows only, every slot's text memory is written through the same slot map; other
+ * VALL-F engines: VX_ERR_UNSUPPORTED).  The pointer arrays and S / P live on the host, text[z] / prompt_cb0[z] may be host or device pointers. */
 int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S,
                          const int64_t* const* prompt_cb0, const int32_t* P, void* stream);
 int vx_batch_decode(vx_engine* e, int32_t n_slots, const vx_decode_params* params, void* stream);
@@ -202,7 +214,7 @@ int vx_batch_result(vx_engine* e, int32_t slot, int64_t* tokens, int32_t capacit
  *                   A slot outside [0, max_batch) or given twice: VX_ERR_ARG; a live or stopped-unread slot: VX_ERR_STATE.
  *                   mode VX_ADMIT_BATCHED prefills all n in one pass over the concatenated rows (one synchronisation);
  *                   VX_ADMIT_PER_SLOT runs vx_batch_prefill's path per slot (one synchronisation each; bitwise the static path).
- *                   VALL-F engines admit per slot only: VX_ADMIT_BATCHED returns VX_ERR_UNSUPPORTED.
+ *                   VALL-F engines without VX_FLAG_VALLF_ROWS admit per slot only: VX_ADMIT_BATCHED returns VX_ERR_UNSUPPORTED.
  *                   exp_noise / forced must be DEVICE pointers that stay valid until the slot's result is read.
  *   vx_batch_run    replays the step until at least min_stopped (< 1: 1) live slots have stopped in this call, or none is left
  *                   live; polls the stop flags every poll_steps steps (<= 0: the default).  stopped (capacity
@@ -217,7 +229,8 @@ int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, const int64_t*
 int vx_batch_run(vx_engine* e, int32_t min_stopped, int32_t poll_steps, int32_t* stopped, int32_t* n_stopped, void* stream);
 
 /* The NAR stages of n (<= 32) utterances in one pass: rows are concatenated so the GEMMs run at M ~ n x 1k.
- * Arguments are arrays of n pointers / sizes with the meaning of vx_nar's.  VALL-E only (VALL-F: VX_ERR_UNSUPPORTED). */
+ * Arguments are arrays of n pointers / sizes with the meaning of vx_nar's.  VALL-E engines, and VALL-F engines created with
+ * VX_FLAG_VALLF_ROWS (every S2 <= max_text, else VX_ERR_CAPACITY naming the utterance; other VALL-F engines: VX_ERR_UNSUPPORTED). */
 int vx_nar_batch(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
                  const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens, const int32_t* T,
                  int64_t* const* codes_out, void* stream);
@@ -317,6 +330,15 @@ int vx_op_attention(int32_t prec, int32_t use_mfma, const void* qkv, void* out, 
  * written.  A bad layout is VX_ERR_ARG before any HIP call.  Synchronises `stream`. */
 int vx_op_attention_segs(const void* qkv, void* out, int32_t rows, int32_t nhead, int32_t hd, int32_t nseg, const int32_t* seg_start,
                          const int32_t* seg_len, const int32_t* seg_text /* nullable */, void* stream);
+/* The segmented cross-attention of the VALL-F row passes (VX_FLAG_VALLF_ROWS): q (rows, ldq) bf16, head h at columns [64 h, 64 h +
+ * 64), ldq >= 64 nhead and a multiple of 8; out (rows, 64 nhead) bf16.  Segments as in vx_op_attention_segs.  Segment z attends to all
+ * klen[z] keys of its own memory and to nothing else: element (head h, key j, channel c) of K at mem + mem_off[z] + h head_stride +
+ * 64 j + c, V at the same index + v_offset (bf16 elements; mem_off, head_stride and v_offset non-negative multiples of 8,
+ * 1 <= klen[z] <= head_stride / 64).  Memory rows at and past klen[z] are never read.  mem_off / klen: host arrays.  out rows
+ * outside the segments are not written.  A bad layout is VX_ERR_ARG before any HIP call.  Synchronises `stream`. */
+int vx_op_cross_attention_segs(const void* q, int32_t ldq, const void* mem, const int64_t* mem_off, int64_t head_stride,
+                               int64_t v_offset, const int32_t* klen, void* out, int32_t rows, int32_t nhead, int32_t nseg,
+                               const int32_t* seg_start, const int32_t* seg_len, void* stream);
 /* The batched decode step's attention over B slot caches (kv_fp8: the e4m3 codes + E8M0 scale bytes, else bf16): q (B, 64 nhead)
  * fp32, out (B, 64 nhead) bf16; slot b's K at kv + b slot_stride, V at + v_offset (elements), element (h ctx_max + j) 64 + c,
  * scales at that index >> 4 of kv_scale.  ctx / done: host arrays; slot b attends to keys [0, ctx[b]); done slots are skipped

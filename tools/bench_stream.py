@@ -5,6 +5,7 @@
     python tools/bench_stream.py --ab-half-done [--lib path/to/libvallex.so]
     python tools/bench_stream.py --model-name VALL-F [...]
     python tools/bench_stream.py --step-times [--model-name VALL-F,VALL-E] [--reps 3]
+    python tools/bench_stream.py --vallf-rows [--reps 2] [--nar-only]
 
 Default mode: a seeded queue of --n utterances, S uniform in [10, 94], P = 225 (synthetic weights: every utterance stops by the
 length rule, T = 16 S + 1 frames), decoded end to end (AR + 7 NAR stages) once through inference_batch, group by group, and once
@@ -21,7 +22,13 @@ queue and the runs alternate between them rep by rep (static, then stream, per f
 --model-name: VALL-E (default) or VALL-F (the cross-attention variant; its slots are prefilled and admitted one by one and its NAR
 stages run per utterance).  --step-times: for each of the comma-separated model names, in one process, the device time per
 batched step with all slots live (S = 47, P = 225, 753 teacher-forced tokens, vx_batch_decode) and of the batch-1 step on the same
-utterance (vx_ar_decode; not with --skip-batch1), --reps times each after a warm-up."""
+utterance (vx_ar_decode; not with --skip-batch1), --reps times each after a warm-up.
+
+--vallf-rows: one VALL-F model built with batched_rows=True (VX_FLAG_VALLF_ROWS), two A/Bs alternating in one process: the NAR
+stages of --slots utterances (S = 47, P = 225, T = 753) as one vx_nar_batch pass against the loop of vx_nar over the same
+utterances (device ms of the passes), and the --n utterance queue through inference_stream with batched_admit / batched_nar on
+against the same queue with both off (the path of a model without the option).  Also written to profiles/vallf_rows_times.json.
+--nar-only: the NAR A/B alone, one repetition (e.g. under a kernel trace)."""
 import argparse
 import json
 import os
@@ -32,7 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def model(args, max_audio, kv_cache="bf16", name=None):
+def model(args, max_audio, kv_cache="bf16", name=None, **opts):
     if args.lib:  # a library built from another revision: bind only the entry points it exports (the static batched path)
         import ctypes as C
 
@@ -54,7 +61,7 @@ def model(args, max_audio, kv_cache="bf16", name=None):
     cls = VALLF if name.lower() in ("vall-f", "vallf") else VALLE
     cfg = ModelConfig(model_name=cls.MODEL_NAME, decoder_dim=1024, nhead=16, num_decoder_layers=12, prefix_mode=1)
     m = cls(1024, 16, 12, prefix_mode=1, precision=args.precision, max_text=128, max_audio=max_audio, print_eos=False,
-            max_batch=args.slots, **({"kv_cache": kv_cache} if kv_cache != "bf16" else {}))
+            max_batch=args.slots, **({"kv_cache": kv_cache} if kv_cache != "bf16" else {}), **opts)
     m.load_state_dict(synthetic_state_dict(cfg, 0))
     return m.to("cuda:0").eval()
 
@@ -239,6 +246,68 @@ def run_step_times(args):
     return res
 
 
+def run_vallf_rows(args):
+    import torch
+    from valle_amd.weights import synthetic_inputs
+
+    B = args.slots
+    m = model(args, 1792, "bf16", "VALL-F", batched_rows=True)
+    eng = m.engine()
+    res = dict(mode="vallf_rows", geometry=f"d=1024 nhead=16 L=12 {args.precision}", slots=B)
+    # the NAR stages of B utterances: one batched pass against the per-utterance loop, device ms (vx_get_timings)
+    S, P, T = 47, 225, 753
+    utts = [synthetic_inputs(S, P, 8, seed=2000 + i) for i in range(B)]
+    g = torch.Generator().manual_seed(3)
+    texts = [u[0][0] for u in utts]
+    proms = [u[2][0].contiguous() for u in utts]
+    toks = [torch.randint(0, 1024, (T,), generator=g) for _ in range(B)]
+    batched_ms, loop_ms = [], []
+    for rep in range((1 if args.nar_only else args.reps) + 1):  # the first is warm-up (row buffers grow to the batch's rows)
+        eng.nar_batch(texts, proms, toks, out_device="cuda")
+        b = eng.timings()["nar_ms"]
+        one = 0.0
+        for i in range(B):
+            eng.nar(texts[i], proms[i], toks[i], out_device="cuda")
+            one += eng.timings()["nar_ms"]
+        if rep:
+            batched_ms.append(b)
+            loop_ms.append(one)
+    mean = lambda v: sum(v) / len(v)
+    res["nar"] = dict(utterances=B, S=S, P=P, T=T, batched_ms=[round(v, 3) for v in batched_ms], per_utterance_loop_ms=[round(v, 3) for v in loop_ms],
+                      batched_mean_ms=round(mean(batched_ms), 3), loop_mean_ms=round(mean(loop_ms), 3),
+                      loop_over_batched=round(mean(loop_ms) / mean(batched_ms), 2))
+    if not args.nar_only:
+        queue_utts, Sq = queue(args.n, args.seed, args.text_len)
+        frames = [16 * s + 1 for s in Sq]
+        seeds = list(range(1, args.n + 1))
+        poll, refill = int(args.poll.split(",")[0]), int(args.refill.split(",")[0])
+        steps = count_steps(eng)
+        w, _ = queue(B, args.seed + 1, args.text_len)
+        for on in (True, False):  # warm-up of both paths
+            for _ in m.inference_stream(w, top_k=10, seeds=list(range(B)), batched_admit=on, batched_nar=on):
+                pass
+        torch.cuda.synchronize()
+        runs = []
+        for rep in range(args.reps):
+            for on in (True, False):  # alternating on the same queue
+                steps[0], steps[1] = 0, 0.0
+                done_at = {}
+                t0 = time.perf_counter()
+                for i, codes in m.inference_stream(queue_utts, top_k=10, seeds=seeds, poll_steps=poll, refill_at=refill, batched_admit=on,
+                                                   batched_nar=on):
+                    done_at[i] = time.perf_counter()
+                runs.append(summary("stream", t0, done_at, frames, steps[0], B, batched_rows=on, poll_steps=poll, refill_at=refill,
+                                    step_us=round(1e3 * steps[1] / max(steps[0], 1), 2)))
+        tps = lambda on: mean([r["tok_per_s"] for r in runs if r["batched_rows"] == on])
+        res["queue"] = dict(n=args.n, S_range=[args.text_len] * 2 if args.text_len else [10, 94], P=225, frames=sum(frames), runs=runs,
+                            tok_per_s_batched=round(tps(True), 1), tok_per_s_per_utterance=round(tps(False), 1),
+                            batched_over_per_utterance=round(tps(True) / tps(False), 2))
+        with open(os.path.join(ROOT, "profiles", "vallf_rows_times.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=128)
@@ -255,10 +324,12 @@ def main():
     ap.add_argument("--model-name", default="VALL-E", help="VALL-E | VALL-F (--step-times: comma-separated)")
     ap.add_argument("--step-times", action="store_true")
     ap.add_argument("--skip-batch1", action="store_true", help="--step-times: the batched step only (e.g. under a kernel trace)")
+    ap.add_argument("--vallf-rows", action="store_true", help="VALL-F with batched_rows=True: batched NAR / admission against per utterance")
+    ap.add_argument("--nar-only", action="store_true", help="--vallf-rows: the NAR A/B alone, one repetition")
     args = ap.parse_args()
     if not args.kv_cache or any(kv not in ("bf16", "fp8") for kv in args.kv_cache.split(",")):
         ap.error("--kv-cache: comma-separated bf16 / fp8")
-    res = run_ab(args) if args.ab_half_done else run_step_times(args) if args.step_times else run_queue(args)
+    res = run_vallf_rows(args) if args.vallf_rows else run_ab(args) if args.ab_half_done else run_step_times(args) if args.step_times else run_queue(args)
     print(json.dumps(res))
 
 

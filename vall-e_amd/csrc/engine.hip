@@ -172,6 +172,12 @@ struct vx_engine {
   // VALL-F: the text memory of every slot, [slot][layer][K|V][head][max_text][64] (xkv_ar's layout per slot); bmem_slot elements
   vx::bf16* bmem = nullptr;
   size_t bmem_slot = 0;
+  // VX_FLAG_VALLF_ROWS: the segmented row passes' text memories (TextMem).  xmem_rows: the batched NAR's packed per-call buffer,
+  // [layer][K|V][head][cap_text][64] bf16 (grown by ensure_rows with cap_text); per-segment descriptors on the device
+  bool vf_rows = false;
+  vx::bf16* xmem_rows = nullptr;
+  long long* d_mem_off = nullptr;
+  int *d_mem_klen = nullptr, *d_mem_trow = nullptr;
   ArState* bst = nullptr;    // device, BMAX
   ArState* h_bst = nullptr;  // pinned: [0..BMAX) staging, [BMAX..3*BMAX) two poll slots
   int *btok = nullptr, *bsamp = nullptr, *bargm = nullptr;
@@ -365,6 +371,13 @@ extern "C" int vx_create(const vx_config* cfg, vx_engine** out) {
   if (c.num_quantizers < 1 || c.num_quantizers > 8) return fail(VX_ERR_ARG, "num_quantizers must be 1..8");
   if (c.prefix_mode != 0 && c.prefix_mode != 1 && c.prefix_mode != 2 && c.prefix_mode != 4)
     return fail(VX_ERR_ARG, "prefix_mode must be 0/1/2/4");
+  // ahead of the general geometry rules, so that a refused combination is reported against the flag that asked for it
+  if ((c.flags & VX_FLAG_VALLF_ROWS) &&
+      (!(c.flags & VX_FLAG_VALLF) || c.max_batch < 2 || c.precision != VX_PREC_BF16 || c.d_model / c.nhead != 64 ||
+       (c.num_quantizers > 1 && c.nar_nhead > 0 && c.nar_d_model / c.nar_nhead != 64) ||
+       (c.flags & (VX_FLAG_POST_NORM | VX_FLAG_PRENET | VX_FLAG_KV_FP8 | VX_FLAG_SIMPLE_ROWS))))
+    return fail(VX_ERR_UNSUPPORTED, "VX_FLAG_VALLF_ROWS needs VX_FLAG_VALLF, max_batch >= 2, bf16 precision, head_dim 64, a pre-norm model "
+                                    "without prenets, bf16 slot caches and the MFMA row kernels");
   // head_dim 64 is the built geometry (MFMA attention, batched decode); 4 / 8 / 16 / 32 run on the plain kernels, batch-1
   // only: the reference's own tests use decoder_dim 64 / nhead 16 and half of that for the NAR stack (valle_test.py:93-95)
   auto hd_ok = [](int hd) { return hd == 4 || hd == 8 || hd == 16 || hd == 32 || hd == 64; };
@@ -558,6 +571,13 @@ static int create_body(vx_engine* e) {
   if (e->vallf) {  // K / V of the text memory per layer, in the decode-cache layout with max_text rows per head
     VXC(dalloc(e, &e->xkv_ar, (size_t)c.num_layers * 2 * d * c.max_text * e->esz));
     if (c.num_quantizers > 1) VXC(dalloc(e, &e->xkv_nar, (size_t)c.nar_num_layers * 2 * dn * c.max_text * e->esz));
+  }
+  e->vf_rows = c.flags & VX_FLAG_VALLF_ROWS;
+  if (e->vf_rows) {
+    if (c.num_quantizers > 1) VXC(dalloc_t(e, &e->xmem_rows, (size_t)c.nar_num_layers * 2 * dn * e->cap_text));
+    VXC(dalloc_t(e, &e->d_mem_off, (size_t)BMAX));
+    VXC(dalloc_t(e, &e->d_mem_klen, (size_t)BMAX));
+    VXC(dalloc_t(e, &e->d_mem_trow, (size_t)BMAX));
   }
   // weights
   for (auto& k : e->keys) {
@@ -1035,7 +1055,33 @@ struct KvDst {
 };
 // The text memory a VALL-F stack cross-attends to: layer li's K / V at kv + li * 2 d max_text elements (memory_kv's layout), `rows`
 // text rows.  kv == nullptr: none (VALL-E).
-struct TextMem { const void* kv = nullptr; int rows = 0; };
+// Segmented rows (VX_FLAG_VALLF_ROWS): every segment has its own memory in cross_attn_seg_kernel's addressing - layer li at kv +
+// li * layer_stride elements, segment z's K there at off[z] + head * head_stride + key * 64, V at + v_offset, klen[z] keys (off /
+// klen: device arrays) - and `rows` is unused.
+struct TextMem {
+  const void* kv = nullptr; int rows = 0;
+  const long long* off = nullptr; const int* klen = nullptr;
+  long long layer_stride = 0, head_stride = 0, v_offset = 0;
+};
+// The text memories of n segments at once: `trows` concatenated text rows (segment z = rows [trow[z], trow[z] + S[z]), no padding)
+// in operand precision in e->Hn -> one in_proj GEMM per layer over all of them (the packed cross in_proj whole, N = 3 d, as
+// memory_kv) and one scatter launch into every segment's memory (`mem`, written through the same descriptors run_stack reads).
+// Uploads the descriptors; the host arrays must outlive the pass.
+static int memory_kv_segs(vx_engine* e, const std::vector<LayerW>& layers, const TextMem& mem, int n, const long long* off,
+                          const int* S, const int* trow, int trows, int d) {
+  int max_s = 0;
+  for (int z = 0; z < n; ++z) max_s = std::max(max_s, S[z]);
+  HIPC(hipMemcpyAsync(e->d_mem_off, off, n * sizeof(long long), hipMemcpyHostToDevice, e->es));
+  HIPC(hipMemcpyAsync(e->d_mem_klen, S, n * sizeof(int), hipMemcpyHostToDevice, e->es));
+  HIPC(hipMemcpyAsync(e->d_mem_trow, trow, n * sizeof(int), hipMemcpyHostToDevice, e->es));
+  for (size_t li = 0; li < layers.size(); ++li) {
+    VXC(gemm_rows(e, e->Hn, layers[li].cin_w, layers[li].cin_b, e->QKV, trows, 3 * d, d, GE_BIAS, false, false));
+    mem_scatter_seg_kernel<<<dim3(max_s, n), 256, 0, e->es>>>((const bf16*)e->QKV, (bf16*)mem.kv + li * mem.layer_stride, e->d_mem_off,
+                                                              mem.head_stride, mem.v_offset, e->d_mem_trow, e->d_mem_klen, d);
+  }
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
 
 // One stack over M rows held in e->X: encoder layers (valle.py:1035-1038 / 1125-1127) or, with a text memory, VALL-F decoder
 // layers (valle.py:626-632 / 682-688, transformer.py:536-558), whose cross-attention block sits between the self-attention and
@@ -1044,7 +1090,7 @@ struct TextMem { const void* kv = nullptr; int rows = 0; };
 static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int d, int H, int text_len, int ada_stage,
                      const RowSegs& segs, KvDst kv, TextMem mem = TextMem()) {
   const bool post = e->cfg.flags & VX_FLAG_POST_NORM, cross = mem.kv != nullptr;
-  if (cross && segs.n > 0) return fail(VX_ERR_UNSUPPORTED, "cross-attention over segmented rows");
+  if (cross && segs.n > 0 && mem.off == nullptr) return fail(VX_ERR_UNSUPPORTED, "cross-attention over segmented rows");
   const int hd = d / H;
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
   const size_t mem_layer = (size_t)2 * d * e->cfg.max_text * e->esz;
@@ -1129,7 +1175,10 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
       VXC(norm_in(li, 1));
       VXC(gemm_rows(e, e->Hn, l.cin_w, l.cin_b, e->QKV, M, d, d, GE_BIAS, false, false));  // q = rows [0, d) of the packed in_proj
       const char* xk = (const char*)mem.kv + li * mem_layer;
-      VXC(cross_attn_rows(e, e->QKV, xk, xk + mem_layer / 2, e->ATT, M, d, H, mem.rows));
+      if (segs.n > 0)  // every segment over its own memory (VX_FLAG_VALLF_ROWS)
+        cross_attn_seg_launch((const bf16*)e->QKV, d, (const bf16*)mem.kv + li * mem.layer_stride, mem.off, mem.head_stride, mem.v_offset,
+                              mem.klen, (bf16*)e->ATT, d, H, segs.start, segs.len, segs.n, segs.max_len, e->es);
+      else VXC(cross_attn_rows(e, e->QKV, xk, xk + mem_layer / 2, e->ATT, M, d, H, mem.rows));
       VXC(gemm_rows(e, e->ATT, l.cout_w, l.cout_b, e->X, M, d, d, GE_RESID, true));
     }
     // feed-forward: x += ff(norm(x)); post-norm x = norm(x + ff(x))
@@ -1307,16 +1356,17 @@ template <int EPI> static int launch_bgemm(const BgemmArgs& a, hipStream_t s);
 // n utterances of len[z] rows as segments of e->X, each starting at a multiple of 64 rows: start[z] (n + 1 entries, start[n] =
 // all rows), row buffers and the id / embedding staging (audio_rows / text_rows) grown to fit, the layout uploaded on e->es,
 // X zeroed over all rows (padding rows must stay finite: they feed V^T columns).  text / slot (optional): per-segment prefix
-// lengths / slots.  The host arrays must outlive the pass (the uploads are asynchronous).
+// lengths / slots.  min_rows: rows the buffers must hold besides (VALL-F: the concatenated text rows pass through them on their
+// way to the text memory).  The host arrays must outlive the pass (the uploads are asynchronous).
 static int seg_layout(vx_engine* e, int n, const int* len, const int* text, const int* slot, int d, size_t audio_rows,
-                      size_t text_rows, int* start, RowSegs& segs) {
+                      size_t text_rows, int* start, RowSegs& segs, size_t min_rows = 0) {
   segs = RowSegs{n, 0, e->d_seg_start, e->d_seg_len, text ? e->d_seg_text : nullptr, slot ? e->d_seg_slot : nullptr};
   start[0] = 0;
   for (int z = 0; z < n; ++z) {
     start[z + 1] = start[z] + (len[z] + 63) / 64 * 64;
     if (len[z] > segs.max_len) segs.max_len = len[z];
   }
-  VXC(ensure_rows(e, start[n], audio_rows, text_rows));
+  VXC(ensure_rows(e, std::max((size_t)start[n], min_rows), audio_rows, text_rows));
   HIPC(hipMemcpyAsync(e->d_seg_start, start, n * sizeof(int), hipMemcpyHostToDevice, e->es));
   HIPC(hipMemcpyAsync(e->d_seg_len, len, n * sizeof(int), hipMemcpyHostToDevice, e->es));
   if (text) HIPC(hipMemcpyAsync(e->d_seg_text, text, n * sizeof(int), hipMemcpyHostToDevice, e->es));
@@ -1335,36 +1385,60 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
   if (!e->bf16 || !use_mfma(e)) return fail(VX_ERR_UNSUPPORTED, "vx_batch_prefill_all needs the bf16 MFMA row kernels");
   const vx_config& c = e->cfg;
   const int bos = c.prepend_bos ? 1 : 0, d = c.d_model;
-  std::vector<int> start(n + 1), len(n), tlen(n);
+  // VALL-F (VX_FLAG_VALLF_ROWS): the rows are the audio rows only, causal (prefix 0) as the per-slot prefill; the text goes to the
+  // slots' text memories
+  const bool vf = e->vallf;
+  std::vector<int> start(n + 1), len(n), tlen(n), soff(n);
+  std::vector<long long> moff(n);
+  int srows = 0;
   for (int b = 0; b < n; ++b) {
+    if (vf && S[b] > c.max_text)  // the slot's text memory holds max_text keys; nothing has been written yet
+      return fail(VX_ERR_CAPACITY, "utterance %d: a text of %d tokens exceeds max_text=%d", b, S[b], c.max_text);
     VXC(check_utterance(e, text[b], S[b], prompt_cb0[b], P[b], b));
-    len[b] = S[b] + bos + P[b]; tlen[b] = S[b];
+    tlen[b] = vf ? 0 : S[b];
+    len[b] = tlen[b] + bos + P[b];
+    soff[b] = srows; srows += S[b];
+    moff[b] = (long long)slots[b] * (long long)e->bmem_slot;
   }
   ON_DEVICE(c.device);
   VXC(sync_in(e, stream));
   HIPC(hipEventRecord(e->ev_t[0], e->es));
   RowSegs segs;
-  VXC(seg_layout(e, n, len.data(), tlen.data(), slots, d, e->cap_audio, e->cap_text, start.data(), segs));
+  VXC(seg_layout(e, n, len.data(), tlen.data(), slots, d, e->cap_audio, e->cap_text, start.data(), segs, vf ? srows : 0));
+  TextMem tmem;
+  if (vf) {  // text rows (concatenated, rows [0, sum S) of X) -> every slot's memory in bmem, then X is the audio rows' again
+    for (int b = 0; b < n; ++b) {
+      long long* it = e->bp_text + (size_t)b * c.max_text;
+      HIPC(hipMemcpyAsync(it, text[b], (size_t)S[b] * 8, hipMemcpyDefault, e->es));
+      embed_pos_kernel<<<S[b], 256, 0, e->es>>>(it, 1, 0, W<float>(e, "ar_text_embedding.word_embeddings.weight"), 512, d,
+                                                W<float>(e, "ar_text_position.alpha"), e->pe_ar, 0, e->X + (size_t)soff[b] * d, S[b]);
+    }
+    VXC(cast_rows(e, e->X, e->Hn, (size_t)srows * d));
+    tmem.kv = e->bmem; tmem.off = e->d_mem_off; tmem.klen = e->d_mem_klen;
+    tmem.head_stride = (long long)c.max_text * 64; tmem.v_offset = (long long)c.max_text * d; tmem.layer_stride = 2 * tmem.v_offset;
+    VXC(memory_kv_segs(e, e->ar_l, tmem, n, moff.data(), S, soff.data(), srows, d));
+    HIPC(hipMemsetAsync(e->X, 0, (size_t)start[n] * d * 4, e->es));
+  }
   static const long long bos_id = NUM_AUDIO_TOKENS + 1;  // valle.py:1006-1007
   for (int b = 0; b < n; ++b) {
     const int A = bos + P[b];
     long long* it = e->bp_text + (size_t)b * c.max_text;
     long long* ia = e->bp_audio + (size_t)b * (c.max_audio + 1);
-    HIPC(hipMemcpyAsync(it, text[b], (size_t)S[b] * 8, hipMemcpyDefault, e->es));
+    if (!vf) HIPC(hipMemcpyAsync(it, text[b], (size_t)S[b] * 8, hipMemcpyDefault, e->es));
     if (bos) HIPC(hipMemcpyAsync(ia, &bos_id, 8, hipMemcpyHostToDevice, e->es));
     if (P[b]) HIPC(hipMemcpyAsync(ia + bos, prompt_cb0[b], (size_t)P[b] * 8, hipMemcpyDefault, e->es));
     float* xb = e->X + (size_t)start[b] * d;
-    embed_pos_kernel<<<S[b], 256, 0, e->es>>>(it, 1, 0, W<float>(e, "ar_text_embedding.word_embeddings.weight"), 512, d,
-                                              W<float>(e, "ar_text_position.alpha"), e->pe_ar, 0, xb, S[b]);
+    if (!vf) embed_pos_kernel<<<S[b], 256, 0, e->es>>>(it, 1, 0, W<float>(e, "ar_text_embedding.word_embeddings.weight"), 512, d,
+                                                       W<float>(e, "ar_text_position.alpha"), e->pe_ar, 0, xb, S[b]);
     embed_pos_kernel<<<A, 256, 0, e->es>>>(ia, 1, 0, W<float>(e, "ar_audio_embedding.word_embeddings.weight"), 1025 + bos, d,
-                                           W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, xb + (size_t)S[b] * d, A);
+                                           W<float>(e, "ar_audio_position.alpha"), e->pe_ar, 0, xb + (size_t)tlen[b] * d, A);
   }
-  VXC(run_stack(e, e->ar_l, start[n], d, c.nhead, 0, -1, segs, KvDst{KvDst::SEG_SLOTS}));
+  VXC(run_stack(e, e->ar_l, start[n], d, c.nhead, 0, -1, segs, KvDst{KvDst::SEG_SLOTS}, tmem));
   // last row of every segment = the slot's current activation
   for (int b = 0; b < n; ++b) {
     const int sl = slots[b];
     HIPC(hipMemcpyAsync(e->bx + (size_t)sl * d, e->X + (size_t)(start[b] + len[b] - 1) * d, (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
-    seed_state(e->h_bst[sl], S[b], P[b], bos, len[b] - 1, S[b], false);
+    seed_state(e->h_bst[sl], S[b], P[b], bos, len[b] - 1, tlen[b], false);
     HIPC(hipMemcpyAsync(e->bst + sl, &e->h_bst[sl], sizeof(ArState), hipMemcpyHostToDevice, e->es));
   }
   // first logits of every slot: final LayerNorm + head, as at the end of a batched step
@@ -1394,7 +1468,7 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
 
 extern "C" int vx_batch_prefill_all(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S,
                                     const int64_t* const* prompt_cb0, const int32_t* P, void* stream) {
-  if (e && e->vallf) return fail(VX_ERR_UNSUPPORTED, "vx_batch_prefill_all: VALL-F prefills slot by slot (vx_batch_prefill)");
+  if (e && e->vallf && !e->vf_rows) return fail(VX_ERR_UNSUPPORTED, "vx_batch_prefill_all: VALL-F prefills slot by slot (vx_batch_prefill)");
   if (e) e->bsess = false;  // the static calls end a continuous-batching session
   int32_t slots[BMAX];  // segment z -> slot z
   for (int z = 0; z < BMAX; ++z) slots[z] = z;
@@ -2037,7 +2111,7 @@ extern "C" int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, con
   if (n < 1 || n > e->bmax) return fail(VX_ERR_ARG, "n %d outside [1, max_batch=%d]", n, e->bmax);
   if (mode != VX_ADMIT_BATCHED && mode != VX_ADMIT_PER_SLOT) return fail(VX_ERR_ARG, "unknown admission mode %d", mode);
   if (mode == VX_ADMIT_BATCHED && !use_mfma(e)) return fail(VX_ERR_UNSUPPORTED, "batched admission needs the bf16 MFMA row kernels");
-  if (mode == VX_ADMIT_BATCHED && e->vallf) return fail(VX_ERR_UNSUPPORTED, "batched admission: VALL-F admits slot by slot (VX_ADMIT_PER_SLOT)");
+  if (mode == VX_ADMIT_BATCHED && e->vallf && !e->vf_rows) return fail(VX_ERR_UNSUPPORTED, "batched admission: VALL-F admits slot by slot (VX_ADMIT_PER_SLOT)");
   const vx_config& c = e->cfg;
   const int bos = c.prepend_bos ? 1 : 0;
   // every check before anything is written: a refused admission leaves all slots as they were
@@ -2053,6 +2127,8 @@ extern "C" int vx_batch_admit(vx_engine* e, int32_t n, const int32_t* slots, con
   long long steps[BMAX] = {}, room[BMAX] = {};
   bool capl[BMAX] = {};
   for (int z = 0; z < n; ++z) {
+    if (mode == VX_ADMIT_BATCHED && e->vallf && S[z] > c.max_text)
+      return fail(VX_ERR_CAPACITY, "utterance %d: a text of %d tokens exceeds max_text=%d", z, S[z], c.max_text);
     VXC(check_utterance(e, text[z], S[z], prompt_cb0[z], P[z], z));
     const vx_decode_params& p = params[z];
     VXC(decode_bound(e, slots[z], p, S[z], P[z], bos, &steps[z], &capl[z], &room[z]));
@@ -2118,6 +2194,7 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
   // per utterance: its rows in X, tx = text rows in front of its audio rows (VALL-F, valle.py:650-708: the stack runs over the
   // audio rows, the NAR text is cross-attention memory), its offsets into the audio / generated / text id staging
   std::vector<int> start(n + 1), len(n), tx(n), aoff(n), toff(n), soff(n);
+  std::vector<long long> moff(n);  // VALL-F, segmented: each segment's text memory (uploaded asynchronously: lives until the final sync)
   int arows = 0, trows = 0, srows = 0;
   for (int b = 0; b < n; ++b) {
     tx[b] = vf ? 0 : S2[b];
@@ -2129,7 +2206,7 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
   VXC(sync_in(e, stream));
   HIPC(hipEventRecord(e->ev_t[4], e->es));
   RowSegs segs;
-  if (segmented) VXC(seg_layout(e, n, len.data(), nullptr, nullptr, dn, arows, srows, start.data(), segs));
+  if (segmented) VXC(seg_layout(e, n, len.data(), nullptr, nullptr, dn, arows, srows, start.data(), segs, vf ? srows : 0));
   else start[1] = len[0];
   const int rows = start[n];
   auto emb = [&](int j) { return W<float>(e, "nar_audio_embeddings." + std::to_string(j) + ".word_embeddings.weight"); };
@@ -2156,7 +2233,23 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
       VXC(text_prenet_rows(e, 1, e->pn_a, e->pn_a, S2[0], dn));
       add_pos_kernel<<<S2[0], 256, 0, e->es>>>(e->pn_a, dn, a_txt, e->pe_nar, 0, e->pn_text, S2[0]);
     }
-    if (vf) {  // the text memory's K / V per layer, once for all stages (same memory and weights in every stage, valle.py:664-688)
+    // segmented VALL-F (VX_FLAG_VALLF_ROWS): all segments' text rows, concatenated without padding in rows [0, sum S2) of X, become
+    // the packed memory xmem_rows (segment b's keys at text row soff[b] of every head) - once for all seven stages.  X is zeroed
+    // again afterwards: the stages write the audio rows only and the padding rows between segments stay as seg_layout left them.
+    TextMem tmem;
+    if (vf && segmented) {
+      for (int b = 0; b < n; ++b) {
+        moff[b] = (long long)soff[b] * 64;
+        embed_pos_kernel<<<S2[b], 256, 0, e->es>>>(e->ids_text + soff[b], 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"), 512, dn,
+                                                   a_txt, e->pe_nar, 0, e->X + (size_t)soff[b] * dn, S2[b]);
+      }
+      VXC(cast_rows(e, e->X, e->Hn, (size_t)srows * dn));
+      tmem.kv = e->xmem_rows; tmem.off = e->d_mem_off; tmem.klen = e->d_mem_klen;
+      tmem.head_stride = (long long)e->cap_text * 64; tmem.v_offset = (long long)e->cap_text * dn; tmem.layer_stride = 2 * tmem.v_offset;
+      VXC(memory_kv_segs(e, e->nar_l, tmem, n, moff.data(), S2, soff.data(), srows, dn));
+      HIPC(hipMemsetAsync(e->X, 0, (size_t)rows * dn * 4, e->es));
+    } else if (vf) {  // the text memory's K / V per layer, once for all stages (same memory and weights in every stage, valle.py:664-688)
+      tmem = TextMem{e->xkv_nar, S2[0]};
       if (prenet) HIPC(hipMemcpyAsync(e->X, e->pn_text, (size_t)S2[0] * dn * 4, hipMemcpyDeviceToDevice, e->es));
       else embed_pos_kernel<<<S2[0], 256, 0, e->es>>>(e->ids_text, 1, 0, W<float>(e, "nar_text_embedding.word_embeddings.weight"), 512, dn,
                                                       a_txt, e->pe_nar, 0, e->X, S2[0]);
@@ -2184,7 +2277,7 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
           add_pos_kernel<<<A, 256, 0, e->es>>>(ye, dn, a_aud, e->pe_nar, 0, xa, A);
         }
       }
-      VXC(run_stack(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, segs, KvDst(), vf ? TextMem{e->xkv_nar, S2[0]} : TextMem()));
+      VXC(run_stack(e, e->nar_l, rows, dn, c.nar_nhead, -1, i, segs, KvDst(), tmem));
       // final AdaLN + predict layer on the generated rows only (valle.py:1128), compacted to [sum T][dn]
       const float* fw = post ? nullptr : ada_vec(e, i, e->npl * c.nar_num_layers);
       for (int b = 0; b < n; ++b) {
@@ -2301,6 +2394,8 @@ static int ensure_rows(vx_engine* e, size_t rows, size_t audio_rows, size_t text
   VXC(regrow((void**)&e->ids_samples, audio_rows * 8));
   VXC(regrow((void**)&e->d_codes, audio_rows * 8 * 8));
   VXC(regrow((void**)&e->d_fcodes, audio_rows * 8 * 8));
+  if (e->xmem_rows != nullptr)  // VX_FLAG_VALLF_ROWS: the packed text memory of the batched NAR, cap_text rows per head
+    VXC(regrow((void**)&e->xmem_rows, (size_t)c.nar_num_layers * 2 * c.nar_d_model * text_rows * 2));
   return VX_OK;
 }
 
@@ -2313,7 +2408,7 @@ extern "C" int vx_nar_batch(vx_engine* e, int32_t n, const int64_t* const* text_
 extern "C" int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* text_nar, const int32_t* S2,
                                const int64_t* const* prompts, const int32_t* P, const int64_t* const* ar_tokens,
                                const int32_t* T, int64_t* const* codes_out, const int64_t* const* forced_codes, void* stream) {
-  if (e && e->vallf) return fail(VX_ERR_UNSUPPORTED, "vx_nar_batch: VALL-F runs its NAR stages per utterance (vx_nar)");
+  if (e && e->vallf && !e->vf_rows) return fail(VX_ERR_UNSUPPORTED, "vx_nar_batch: VALL-F runs its NAR stages per utterance (vx_nar)");
   if (!e || !text_nar || !S2 || !prompts || !P || !ar_tokens || !T || !codes_out) return fail(VX_ERR_ARG, "null argument");
   if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
   const vx_config& c = e->cfg;
@@ -2327,6 +2422,8 @@ extern "C" int vx_nar_batch_ex(vx_engine* e, int32_t n, const int64_t* const* te
     // per-utterance limits: positions index the sine table (pe_rows rows) separately for text and audio
     if (S2[b] > e->pe_rows || P[b] + T[b] > e->pe_rows)
       return fail(VX_ERR_CAPACITY, "utterance %d: S2=%d / P+T=%d exceed the %d positions of the sine table", b, S2[b], P[b] + T[b], e->pe_rows);
+    if (e->vallf && S2[b] > c.max_text)  // a text memory holds max_text keys (slot memory and packed buffer alike)
+      return fail(VX_ERR_CAPACITY, "utterance %d: S2=%d exceeds max_text=%d", b, S2[b], c.max_text);
   }
   return nar_run(e, n, true, text_nar, S2, prompts, P, ar_tokens, T, codes_out, forced_codes, stream);
 }
@@ -2886,6 +2983,53 @@ extern "C" int vx_op_attention_segs(const void* qkv, void* out, int32_t rows, in
   const hipError_t le = hipGetLastError();
   const hipError_t se = hipStreamSynchronize(s);  // the scratch is in use until the stream has drained, whatever happened
   if (rc) return fail(VX_ERR_UNSUPPORTED, "attention_segs: rows x 3 d or d x vt_ld exceed 4 GB");
+  HIPC(le);
+  HIPC(se);
+  return VX_OK;
+}
+
+// Segmented cross-attention (cross_attn_seg_kernel, the VX_FLAG_VALLF_ROWS row passes) on caller buffers: segments and per-segment
+// memories described by host arrays.
+extern "C" int vx_op_cross_attention_segs(const void* q, int32_t ldq, const void* mem, const int64_t* mem_off, int64_t head_stride,
+                                          int64_t v_offset, const int32_t* klen, void* out, int32_t rows, int32_t nhead, int32_t nseg,
+                                          const int32_t* seg_start, const int32_t* seg_len, void* stream) {
+  if (nhead < 1 || rows < 1) return fail(VX_ERR_ARG, "cross_attention_segs: nhead %d, rows %d", nhead, rows);
+  if (nseg < 1 || nseg > BMAX) return fail(VX_ERR_ARG, "cross_attention_segs: nseg %d outside [1, %d]", nseg, BMAX);
+  if (!seg_start || !seg_len || !mem_off || !klen) return fail(VX_ERR_ARG, "cross_attention_segs: null segment array");
+  if ((long long)nhead * 64 > ldq || ldq % 8) return fail(VX_ERR_ARG, "cross_attention_segs: ldq %d must be a multiple of 8 and >= 64 nhead (%d)", ldq, nhead * 64);
+  if (head_stride < 64 || v_offset < 0 || head_stride % 8 || v_offset % 8)
+    return fail(VX_ERR_ARG, "cross_attention_segs: head_stride %lld (>= 64) and v_offset %lld must be non-negative multiples of 8",
+                (long long)head_stride, (long long)v_offset);
+  int max_len = 0;
+  for (int z = 0; z < nseg; ++z) {
+    const long long st = seg_start[z], ln = seg_len[z];
+    if (st < 0 || st % 64) return fail(VX_ERR_ARG, "cross_attention_segs: segment %d starts at row %lld, not a multiple of 64", z, st);
+    if (z > 0 && st < (long long)seg_start[z - 1] + seg_len[z - 1])
+      return fail(VX_ERR_ARG, "cross_attention_segs: segment %d (start %lld) overlaps or precedes segment %d", z, st, z - 1);
+    if (ln < 1 || st + ln > rows) return fail(VX_ERR_ARG, "cross_attention_segs: segment %d [%lld, %lld + %lld) outside [0, %d) or empty", z, st, st, ln, rows);
+    if (klen[z] < 1 || (long long)klen[z] * 64 > head_stride)
+      return fail(VX_ERR_ARG, "cross_attention_segs: klen[%d] = %d outside [1, head_stride / 64 = %lld]", z, klen[z], (long long)head_stride / 64);
+    if (mem_off[z] < 0 || mem_off[z] % 8) return fail(VX_ERR_ARG, "cross_attention_segs: mem_off[%d] = %lld must be a non-negative multiple of 8", z, (long long)mem_off[z]);
+    max_len = std::max(max_len, (int)ln);
+  }
+  if (!q || !mem || !out) return fail(VX_ERR_ARG, "cross_attention_segs: null q, mem or out");
+  hipStream_t s = (hipStream_t)stream;
+  struct Scratch {  // freed on every exit path
+    int* segs = nullptr;
+    long long* off = nullptr;
+    ~Scratch() { (void)hipFree(segs); (void)hipFree(off); }
+  } t;
+  std::vector<long long> off(mem_off, mem_off + nseg);
+  HIPC(hipMalloc((void**)&t.segs, (size_t)3 * nseg * sizeof(int)));
+  HIPC(hipMalloc((void**)&t.off, (size_t)nseg * sizeof(long long)));
+  HIPC(hipMemcpyAsync(t.segs, seg_start, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(t.segs + nseg, seg_len, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(t.segs + 2 * nseg, klen, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(t.off, off.data(), nseg * sizeof(long long), hipMemcpyHostToDevice, s));
+  cross_attn_seg_launch((const bf16*)q, ldq, (const bf16*)mem, t.off, head_stride, v_offset, t.segs + 2 * nseg, (bf16*)out, nhead * 64, nhead,
+                        t.segs, t.segs + nseg, nseg, max_len, s);
+  const hipError_t le = hipGetLastError();
+  const hipError_t se = hipStreamSynchronize(s);  // the scratch is in use until the stream has drained, whatever happened
   HIPC(le);
   HIPC(se);
   return VX_OK;

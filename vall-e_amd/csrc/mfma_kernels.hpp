@@ -1500,4 +1500,198 @@ static inline int mfma_attn_dispatch(const bf16* qkv, const bf16* vt, int vt_ld,
   return 0;
 }
 
+// ---- segmented cross-attention (VALL-F, VX_FLAG_VALLF_ROWS): every segment of a concatenated row buffer attends to its OWN
+// text memory.  Segment z = rows [seg_start[z], seg_start[z] + seg_len[z]) of q (bf16, ldq elements per row, head h at columns
+// [64 h, 64 h + 64)) and of out (bf16, ldo elements per row).  Its memory: klen[z] keys, element (head h, key j, channel c) of K at
+// mem + mem_off[z] + h * head_stride + j * 64 + c, V at the same index + v_offset - one form for the packed per-call buffer of the
+// batched NAR and for the slot memory (through a slot map folded into mem_off).  No mask but the key count (valle.py:631, 687).
+// Workgroup = 4 waves x 32 queries over 64-key tiles (double-buffered in LDS), the orientation and the online softmax of
+// mfma_attn_kernel: S^T = K . Q^T, O^T = V^T . P^T with bf16 P, fp32 accumulation, keys in ascending tile order - no atomics.
+// K rows are [key][64], the A operand of the first product as they lie.  V arrives [key][64] as well and is transposed on its way
+// into LDS (16-byte global loads, 2-byte LDS stores, once per (segment, head, key tile, query block)) into the regrouped V^T rows
+// mfma_attn_kernel reads.  Keys at and past klen[z] are never loaded: the row index of every load is clamped to klen[z] - 1, their
+// scores are replaced by -inf before the tile maximum and their V^T columns are stored as zeros (P = 0 would not silence a NaN).
+// Rows outside the segments are not written.
+__global__ __launch_bounds__(256) void cross_attn_seg_kernel(const bf16* __restrict__ q, int ldq, const bf16* __restrict__ mem,
+                                                             const long long* __restrict__ mem_off, long long head_stride,
+                                                             long long v_offset, const int* __restrict__ klen,
+                                                             bf16* __restrict__ out, int ldo, const int* __restrict__ seg_start,
+                                                             const int* __restrict__ seg_len) {
+  constexpr int HD = 64, NW = 4;
+  const int bx = blockIdx.x, head = blockIdx.y, bz = blockIdx.z;
+  const int M = seg_len[bz];
+  if (bx * 32 * NW >= M) return;
+  const int r0 = seg_start[bz], Sk = klen[bz];
+  __shared__ __attribute__((aligned(16))) unsigned char lds_raw[2 * 2 * 8192];  // [buf][K | V^T][64 rows * 128 B]
+  auto ldsp = [&](int buf, int kv) { return lds_raw + (size_t)(buf * 2 + kv) * 8192; };
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const int qrow = bx * (32 * NW) + wave * 32 + r;
+  const bool qvalid = qrow < M;
+  q += (size_t)r0 * ldq;
+  out += (size_t)r0 * ldo;
+  const bf16* __restrict__ const kbase = mem + mem_off[bz] + (long long)head * head_stride;
+  const bf16* __restrict__ const vbase = kbase + v_offset;
+
+  bf16x8_t qf[4];  // the 4 k-steps of 16 dims, scaled by 1/sqrt(64) = 2^-3 (exact in bf16)
+  {
+    const bf16* qp = q + (size_t)min(qrow, M - 1) * ldq + head * HD + 8 * hh;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + ks * 16);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) qf[ks][j] = (bf16)((float)qf[ks][j] * 0.125f);
+    }
+  }
+  const int limit = qvalid ? Sk : 0;
+  const int ntiles = (Sk + 63) / 64;
+
+  // a tile = 512 16-byte chunks per operand, two per thread: chunk (key row, 8 channels)
+  struct TileRegs { uint4 k[2], v[2]; };
+  TileRegs R;
+  auto gload = [&](int kt) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + i * 256, row = c >> 3, ch = c & 7;
+      const size_t at = (size_t)min(kt + row, Sk - 1) * HD + ch * 8;
+      R.k[i] = ld16(kbase + at);
+      R.v[i] = ld16(vbase + at);
+    }
+  };
+  auto lstore = [&](int kt, int buf) {
+    unsigned char* kb = ldsp(buf, 0);
+    unsigned char* vb = ldsp(buf, 1);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + i * 256, row = c >> 3, ch = c & 7;
+      *reinterpret_cast<uint4*>(kb + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = R.k[i];
+      // V^T: key `row` of the tile -> column position of the regrouped row (mfma_attn_kernel's lstore): 16-key group g, chunk 2g holds
+      // keys {0-3, 8-11} of the group, chunk 2g + 1 keys {4-7, 12-15}
+      const int g = row >> 4, quad = (row >> 2) & 3;
+      const int chunk = 2 * g + (quad & 1), pos = (quad >> 1) * 4 + (row & 3);
+      const bool live = kt + row < Sk;
+      union { uint4 u; unsigned short s[8]; } pk;
+      pk.u = R.v[i];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int dim = ch * 8 + j;
+        *reinterpret_cast<unsigned short*>(vb + dim * 128 + ((chunk ^ ((dim >> 1) & 7)) << 4) + pos * 2) = live ? pk.s[j] : (unsigned short)0;
+      }
+    }
+  };
+
+  f32x16_t accO[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) accO[t][v] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;  // l_run: this half-wave's share of the row sum
+
+  gload(0);
+  lstore(0, 0);
+  __syncthreads();
+  for (int it = 0; it < ntiles; ++it) {
+    const int cur = it & 1, kt = it * 64;
+    if (it + 1 < ntiles) gload(kt + 64);
+    const unsigned char* kb = ldsp(cur, 0);
+    const unsigned char* vb = ldsp(cur, 1);
+    const int swz = (r >> 1) & 7;  // rows r and r + 32 swizzle alike
+    f32x16_t accS[2];
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) accS[sub][v] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(kb + (sub * 32 + r) * 128 + (((ks * 2 + hh) ^ swz) << 4));
+        accS[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], accS[sub], 0, 0, 0);
+      }
+    }
+    // register v of half hh holds key (v & 3) + 8 (v >> 2) + 4 hh of the sub-tile; only the last tile can be partial, and the
+    // select costs nothing next to the tile's staging, so every tile takes it
+    float mloc = -INFINITY;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const int kgi = kt + sub * 32 + (v & 3) + 8 * (v >> 2) + 4 * hh;
+        accS[sub][v] = (kgi < limit) ? accS[sub][v] : -INFINITY;
+        mloc = fmaxf(mloc, accS[sub][v]);
+      }
+    mloc = fmaxf(mloc, xor32_f(mloc));
+    const float m_new = fmaxf(m_run, mloc);
+    const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // a query row past the segment sees nothing: exp(-inf - 0) = 0
+    constexpr float LOG2E = 1.4426950408889634f;
+    const float corr = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_use) * LOG2E);
+    l_run *= corr;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) accO[t][v] *= corr;
+    m_run = m_new;
+    bf16x8_t pf[2][2];
+    float l0 = 0.f, l1 = 0.f;  // two chains, fixed order
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int v = 0; v < 16; v += 2) {
+        const float p0 = __builtin_amdgcn_exp2f((accS[sub][v] - m_use) * LOG2E);
+        const float p1 = __builtin_amdgcn_exp2f((accS[sub][v + 1] - m_use) * LOG2E);
+        l0 += p0; l1 += p1;
+        pf[sub][v >> 3][v & 7] = (bf16)p0;
+        pf[sub][v >> 3][(v & 7) + 1] = (bf16)p1;
+      }
+    l_run += l0 + l1;
+    // O^T += V^T . P^T : element j of half hh is key 16 s2 + 8 (j >> 2) + 4 hh + (j & 3) of the sub-tile = chunk 2 (2 sub + s2) + hh
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(vb + (t * 32 + r) * 128 + (((2 * (2 * sub + s2) + hh) ^ swz) << 4));
+          accO[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[sub][s2], accO[t], 0, 0, 0);
+        }
+    if (it + 1 < ntiles) lstore(kt + 64, cur ^ 1);  // the other buffer: its readers passed the barrier that ended iteration it - 1
+    __syncthreads();
+  }
+  if (qvalid) {
+    const float inv = 1.0f / (l_run + xor32_f(l_run));
+    bf16* op = out + (size_t)qrow * ldo + head * HD;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {  // registers 4 g4 .. 4 g4 + 3 = dims 32 t + 8 g4 + 4 hh + 0..3
+        union { bf16 b[4]; uint2 u; } pk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pk.b[j] = (bf16)(accO[t][4 * g4 + j] * inv);
+        *reinterpret_cast<uint2*>(op + t * 32 + 8 * g4 + 4 * hh) = pk.u;
+      }
+  }
+}
+
+// One launch over all segments; max_seg_len = the longest segment (grid.x covers it, shorter segments' surplus blocks return).
+static inline void cross_attn_seg_launch(const bf16* q, int ldq, const bf16* mem, const long long* mem_off, long long head_stride,
+                                         long long v_offset, const int* klen, bf16* out, int ldo, int H, const int* seg_start,
+                                         const int* seg_len, int nseg, int max_seg_len, hipStream_t s) {
+  cross_attn_seg_kernel<<<dim3((max_seg_len + 127) / 128, H, nseg), 256, 0, s>>>(q, ldq, mem, mem_off, head_stride, v_offset, klen, out,
+                                                                                 ldo, seg_start, seg_len);
+}
+
+// Text rows -> per-segment K / V memory in cross_attn_seg_kernel's addressing: row trow[z] + j of a packed (rows, 3 d) in_proj
+// result (K at columns [d, 2d), V at [2d, 3d)) -> key j of segment z.  grid = (longest text, segments), 16-byte copies.
+__global__ __launch_bounds__(256) void mem_scatter_seg_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ mem,
+                                                              const long long* __restrict__ mem_off, long long head_stride,
+                                                              long long v_offset, const int* __restrict__ trow,
+                                                              const int* __restrict__ klen, int d) {
+  const int j = blockIdx.x, z = blockIdx.y;
+  if (j >= klen[z]) return;
+  const bf16* src = qkv + (size_t)(trow[z] + j) * 3 * d + d;
+  bf16* dst = mem + mem_off[z] + (long long)j * 64;
+  for (int i = threadIdx.x; i < 2 * d / 8; i += 256) {  // chunk i: 8 channels of K (i < d / 8) or V
+    const int sec = i >= d / 8, c8 = (i - sec * (d / 8)) * 8, h = c8 >> 6, c = c8 & 63;
+    *reinterpret_cast<uint4*>(dst + (long long)h * head_stride + sec * v_offset + c) = ld16(src + sec * d + c8);
+  }
+}
+
 }  // namespace vx

@@ -19,6 +19,7 @@ VX_PREC_F32, VX_PREC_BF16, VX_PREC_FP8_NAR = 0, 1, 2
 BMAX = 64  # slots per engine (csrc/batch_kernels.hpp)
 VX_FLAG_TRACE_LOGITS, VX_FLAG_NO_GRAPH, VX_FLAG_SIMPLE_ROWS, VX_FLAG_POST_NORM, VX_FLAG_PRENET, VX_FLAG_VALLF = 1, 2, 4, 8, 16, 32
 VX_FLAG_KV_FP8 = 64
+VX_FLAG_VALLF_ROWS = 128  # VALL-F: batched prefill / admission / NAR over concatenated rows (Engine(batched_rows=True))
 KV_CACHES = ("bf16", "fp8")  # storage of the batched decode's slot caches (VX_FLAG_KV_FP8)
 VX_ADMIT_BATCHED, VX_ADMIT_PER_SLOT = 0, 1
 VX_CODEC_LSTM_GRAPH, VX_CODEC_ENCODER = 1, 2
@@ -93,6 +94,8 @@ _SIGS = {
     "vx_op_layernorm_mx": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_void_p]),
     "vx_op_attention": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
     "vx_op_attention_segs": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 3 + [C.c_void_p]),
+    "vx_op_cross_attention_segs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.c_int64,
+                                             C.POINTER(C.c_int32), C.c_void_p] + [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 2 + [C.c_void_p]),
     "vx_op_attn_slots": (C.c_int, [C.c_int32] + [C.c_void_p] * 3 + [C.c_int64, C.c_int64] + [C.c_int32] * 3
                          + [C.POINTER(C.c_int32)] * 2 + [C.c_void_p, C.c_void_p]),
     "vx_op_attn_mem_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 3
@@ -201,9 +204,11 @@ class Engine:
 
     def __init__(self, cfg, precision: str = "bf16", max_text: int = 256, max_audio: int = 2048, device: int = 0,
                  trace_logits: bool = False, no_graph: bool = False, simple_rows: bool = False, max_batch: int = 0,
-                 kv_cache: str = "bf16"):
+                 kv_cache: str = "bf16", batched_rows: bool = False):
         if kv_cache not in KV_CACHES:
             raise ValueError(f"kv_cache must be one of {KV_CACHES}, got {kv_cache!r}")
+        if batched_rows and not getattr(cfg, "is_vallf", False):
+            raise ValueError("batched_rows=True is the VALL-F option (VX_FLAG_VALLF_ROWS): a VALL-E engine batches its row passes as it is")
         self.lib = load_library()
         self.cfg = cfg
         self.device = int(device)
@@ -219,10 +224,13 @@ class Engine:
                   (VX_FLAG_SIMPLE_ROWS if simple_rows else 0) | (0 if getattr(cfg, "norm_first", True) else VX_FLAG_POST_NORM) | \
                   (VX_FLAG_PRENET if getattr(cfg, "add_prenet", False) else 0) | \
                   (VX_FLAG_VALLF if getattr(cfg, "is_vallf", False) else 0) | \
-                  (VX_FLAG_KV_FP8 if kv_cache == "fp8" else 0)
+                  (VX_FLAG_KV_FP8 if kv_cache == "fp8" else 0) | (VX_FLAG_VALLF_ROWS if batched_rows else 0)
         c.max_batch = int(max_batch)
         self.max_text, self.max_audio, self.trace_logits, self.max_batch = max_text, max_audio, trace_logits, int(max_batch)
         self.kv_cache = kv_cache
+        # VALL-F only: the engine also keeps a packed text-memory buffer for the batched NAR pass (2 nar_layers nar_dim bf16 per text
+        # row, grown with the other row buffers) and accepts batch_prefill_all / batch_admit(batched=True) / nar_batch
+        self.batched_rows = bool(batched_rows)
         self.mfma_rows = c.precision != VX_PREC_F32 and not simple_rows
         h = C.c_void_p()
         _check(self.lib.vx_create(C.byref(c), C.byref(h)))
@@ -615,6 +623,27 @@ def op_attention_segs(qkv, nhead, starts, lens, texts=None, out=None):
     assert out.dtype == torch.bfloat16 and out.shape == (rows, d)
     _check(lib.vx_op_attention_segs(_ptr(qkv), _ptr(out), rows, nhead, d // nhead, len(starts), _i32(starts), _i32(lens), _i32(texts),
                                     current_stream_ptr(qkv.device)))
+    return out
+
+
+def op_cross_attention_segs(q, mem, mem_off, head_stride, v_offset, klens, nhead, starts, lens, out=None):
+    """Segmented cross-attention (vx_op_cross_attention_segs): q (rows, ldq) bf16, head h at columns [64 h, 64 h + 64); segment z = rows
+    [starts[z], starts[z] + lens[z]) attends to the klens[z] keys of its own memory: element (h, j, c) of K at mem.flatten()[mem_off[z]
+    + h head_stride + 64 j + c], V at + v_offset.  `out` (rows, 64 nhead) bf16 may be supplied: rows outside the segments are left as
+    they are."""
+    lib = load_library()
+    assert q.dtype == torch.bfloat16 and q.dim() == 2 and q.is_contiguous() and mem.dtype == torch.bfloat16 and mem.is_contiguous()
+    rows, ldq = q.shape
+    if out is None:
+        out = torch.zeros((rows, 64 * nhead), dtype=torch.bfloat16, device=q.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == (rows, 64 * nhead)
+    n = len(starts)
+    assert len(lens) == n and len(klens) == n and len(mem_off) == n
+    need = max(int(o) + (nhead - 1) * int(head_stride) + int(v_offset) + int(k) * 64 for o, k in zip(mem_off, klens))
+    assert need <= mem.numel(), "a segment's memory lies outside `mem`"
+    off = (C.c_int64 * n)(*[int(v) for v in mem_off])
+    _check(lib.vx_op_cross_attention_segs(_ptr(q), ldq, _ptr(mem), off, int(head_stride), int(v_offset), _i32(klens), _ptr(out), rows,
+                                          nhead, n, _i32(starts), _i32(lens), current_stream_ptr(q.device)))
     return out
 
 

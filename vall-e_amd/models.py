@@ -103,7 +103,8 @@ class VALLE:
             precision=kwargs.pop("precision", "bf16"), max_text=kwargs.pop("max_text", 512),
             max_audio=kwargs.pop("max_audio", 4096), trace_logits=kwargs.pop("trace_logits", False),
             no_graph=kwargs.pop("no_graph", False), simple_rows=kwargs.pop("simple_rows", False),
-            max_batch=kwargs.pop("max_batch", 0), kv_cache=kwargs.pop("kv_cache", "bf16"))
+            max_batch=kwargs.pop("max_batch", 0), kv_cache=kwargs.pop("kv_cache", "bf16"),
+            batched_rows=bool(kwargs.pop("batched_rows", False)))
         self.sampling = kwargs.pop("sampling", "device")
         self.print_eos = kwargs.pop("print_eos", True)
         self.cfg = ModelConfig(model_name=self.MODEL_NAME, decoder_dim=d_model, nhead=nhead, num_decoder_layers=num_layers, norm_first=norm_first,
@@ -124,6 +125,13 @@ class VALLE:
                 raise NotImplementedError("kv_cache='fp8' needs a pre-norm VALL-E without prenets")
             if d_model % nhead or d_model // nhead != 64:
                 raise NotImplementedError("kv_cache='fp8' needs head_dim 64")
+        if self.engine_opts["batched_rows"]:  # the engine refuses these too (VX_FLAG_VALLF_ROWS); here they fail before one exists
+            if not self.cfg.is_vallf:
+                raise ValueError("batched_rows=True is the VALL-F option: a VALL-E model batches its prefill, admission and NAR as it is")
+            if self.engine_opts["max_batch"] < 2:
+                raise NotImplementedError("batched_rows=True needs max_batch >= 2")
+            if not norm_first or add_prenet or self.engine_opts["simple_rows"]:
+                raise NotImplementedError("batched_rows=True needs a pre-norm VALL-F without prenets on the MFMA row kernels")
         if (not norm_first or add_prenet) and self.engine_opts.get("max_batch", 0) > 1:
             raise NotImplementedError("norm_first=False / add_prenet=True run on the batch-1 path only (inference_batch needs the defaults)")
         if self.cfg.is_vallf and self.engine_opts["max_batch"] > 1:  # the engine refuses these too (vx_create)
@@ -474,8 +482,12 @@ class VALLF(VALLE):
     sequence alone; the reference masks memory positions >= x_lens (all-false for the unpadded batch-1 input it accepts).
     The reference's VALLF has no ``continual`` and no batched entry point.  This one has no ``continual`` either; built with
     ``max_batch >= 2`` (pre-norm, no prenets, head_dim 64, d_model in {128, 256, 512, 1024}, bf16) it has ``inference_batch`` and
-    ``inference_stream``, which prefill and admit slot by slot and run the NAR stages per utterance (``batched_prefill``,
-    ``batched_admit`` and ``batched_nar`` are ignored)."""
+    ``inference_stream``.  By default these prefill and admit slot by slot and run the NAR stages per utterance
+    (``batched_prefill``, ``batched_admit`` and ``batched_nar`` are ignored).  Built with ``batched_rows=True`` as well
+    (VX_FLAG_VALLF_ROWS) they honour the three switches as VALLE does: the prefill / admission of a group and the NAR stages of a
+    group each run as one pass over the concatenated audio rows, with the cross-attention of every utterance over its own text
+    memory.  The option costs a packed text-memory buffer for the batched NAR pass (2 nar_layers nar_dim bf16 per text row of a
+    group) and is refused on a VALLE model."""
 
     MODEL_NAME = "VALL-F"
 
@@ -489,16 +501,18 @@ class VALLF(VALLE):
     def inference_batch(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, batched_nar: bool = True,
                         batched_prefill: bool = True, top_p: float = 1.0):
         self._vallf_batched("inference_batch")
-        return super().inference_batch(utterances, top_k=top_k, temperature=temperature, seeds=seeds, batched_nar=False,
-                                       batched_prefill=False, top_p=top_p)
+        rows = self.engine_opts["batched_rows"]
+        return super().inference_batch(utterances, top_k=top_k, temperature=temperature, seeds=seeds, batched_nar=rows and batched_nar,
+                                       batched_prefill=rows and batched_prefill, top_p=top_p)
 
     def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
                          poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None,
                          top_p: float = 1.0):
         self._vallf_batched("inference_stream")
+        rows = self.engine_opts["batched_rows"]
         return super().inference_stream(utterances, top_k=top_k, temperature=temperature, seeds=seeds, nar_group=nar_group,
-                                        poll_steps=poll_steps, batched_admit=False, batched_nar=False, refill_at=refill_at,
-                                        top_p=top_p)
+                                        poll_steps=poll_steps, batched_admit=rows and batched_admit, batched_nar=rows and batched_nar,
+                                        refill_at=refill_at, top_p=top_p)
 
 
 def get_model(params) -> VALLE:
@@ -512,7 +526,7 @@ def get_model(params) -> VALLE:
         raise NotImplementedError(f"model {cfg.model_name!r}: only VALL-E and VALL-F are built (DESIGN.md)")
     extra = {}
     get = params.get if isinstance(params, dict) else lambda k, d=None: getattr(params, k, d)
-    for k in ("precision", "max_text", "max_audio", "sampling", "max_batch", "kv_cache"):
+    for k in ("precision", "max_text", "max_audio", "sampling", "max_batch", "kv_cache", "batched_rows"):
         if get(k, None) is not None:
             extra[k] = get(k)
     return cls(cfg.decoder_dim, cfg.nhead, cfg.num_decoder_layers, norm_first=cfg.norm_first, add_prenet=cfg.add_prenet,
