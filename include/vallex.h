@@ -80,7 +80,7 @@ enum vx_flags {
                                step's attention reads.  Needs max_batch >= 2, VX_PREC_BF16 or VX_PREC_FP8_NAR, head_dim 64 and a
                                pre-norm VALL-E without prenets (else VX_ERR_UNSUPPORTED, before any HIP call; VALL-F included).  The batch-1 cache
                                (vx_ar_*) stays bf16 */
-  VX_FLAG_VALLF_ROWS = 128  /* VALL-F row passes over concatenated utterances: vx_batch_prefill_all, VX_ADMIT_BATCHED and
+  VX_FLAG_VALLF_ROWS = 128, /* VALL-F row passes over concatenated utterances: vx_batch_prefill_all, VX_ADMIT_BATCHED and
                                vx_nar_batch / vx_nar_batch_ex accept the engine; the cross-attention of those passes runs per
                                segment over each utterance's own text memory (cross_attn_seg_kernel, bf16 MFMA).  Valid only
                                together with VX_FLAG_VALLF and max_batch >= 2 within the VALL-F slot limits (pre-norm, no prenets,
@@ -90,6 +90,22 @@ enum vx_flags {
                                2 nar_num_layers nar_d_model bf16 per text row, max_text rows at vx_create and grown with the
                                other row buffers to the sum of the texts of the largest vx_nar_batch call.  Without the flag a
                                VALL-F engine behaves exactly as before.  vx_score_batch still refuses VALL-F */
+  VX_FLAG_LOGPROBS = 256    /* generation also records the model's log-probability of every token it emits (what every serving
+                               engine returns next to its tokens; best-of-N synthesis ranks candidates by it without a second
+                               scoring pass).  AR: per pass i, lp[i] = z[t] - logsumexp(z) on the RAW logits row z (before
+                               temperature, top-k and top-p), t = forced[i] where teacher forcing supplies a token, 1024 (EOS) when
+                               pass i ended the decode with VX_STOP_EOS_ARGMAX / VX_STOP_EOS_SAMPLE, else the sampled token (tap
+                               "ar_sampled"; it is the appended token whenever one is appended).  A teacher-forced decode of n tokens has
+                               n + 1 passes (the pass behind the last forced token closes it and appends nothing; its value is that
+                               of its sample), an EOS stop n_tokens + 1, every other stop n_tokens.  lp[:n_tokens] lines up with the
+                               tokens and after an EOS stop lp[n_tokens] is the EOS term: their sum is -sum(nll_ar) of vx_score for
+                               the same codes.  NAR: per stage and generated row, max(row) - logsumexp(row), the log-probability of
+                               the code the stage picked.  Sums are max-subtracted, run in fp64 in a fixed order (a slot's value
+                               depends neither on the batch size nor on the slot), -inf entries add 0, a -inf target gives -inf.
+                               Valid with every configuration vx_create accepts.  The sampler and the NAR argmax run as separate
+                               instantiations / kernels chosen on the host: without the flag the launches, the graph, the tokens and
+                               the allocations are what they were.  Cost: one fp32 per pass (and per slot), (Q-1) fp32 per NAR row
+                                */
 };
 
 /* Mirrors VALLE.__init__ (valle.py:727-760) / get_model (models/__init__.py:112-124). */
@@ -182,6 +198,17 @@ int vx_nar_ex(vx_engine* e, const int64_t* text_nar, int32_t S2, const int64_t* 
  * prenets in prefix mode 0, where continual() applies the audio position BEFORE the audio prenet (valle.py:1193-1194). */
 int vx_nar_continual(vx_engine* e, const int64_t* text_nar, int32_t S2, const int64_t* prompts, int32_t P,
            const int64_t* ar_tokens, int32_t T, int64_t* codes_out, void* stream);
+
+/* VX_FLAG_LOGPROBS: lp of the last vx_ar_decode, n = n_pass values into the HOST buffer `out` (out NULL: only *n).  No flag:
+ * VX_ERR_UNSUPPORTED; no finished decode: VX_ERR_STATE; capacity < n_pass: VX_ERR_CAPACITY.  Blocks like vx_ar_result. */
+int vx_ar_logprobs(vx_engine* e, float* out, int32_t capacity, int32_t* n);
+/* The same for a slot of vx_batch_decode or of a session.  In a session it must be read while the slot is STOPPED, i.e. before the
+ * vx_batch_result that vacates it (else VX_ERR_STATE). */
+int vx_batch_logprobs(vx_engine* e, int32_t slot, float* out, int32_t capacity, int32_t* n);
+/* Utterance `utt` of the last vx_nar / vx_nar_ex / vx_nar_continual / vx_nar_batch / vx_nar_batch_ex call (kept on the device until
+ * the next one): out (Q-1, T) fp32 row-major, host or device, capacity in elements.  Under forced_codes the value is still that of
+ * the stage's own argmax, which is what codes_out reports.  Same error rules as above; utt outside the call: VX_ERR_ARG. */
+int vx_nar_logprobs(vx_engine* e, int32_t utt, float* out, int64_t capacity);
 
 /* ---- batched AR decode (BASELINE configs[2]): up to max_batch utterances ("slots") advance one token per
  * step and share one stream of the weights; every slot has its own padded KV cache, stop rule and sampler
@@ -387,6 +414,11 @@ int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperatur
  * VX_ERR_UNSUPPORTED (the single-wave kernel has no nucleus stage), with top_p off it is vx_op_sample. */
 int vx_op_sample_topp(const float* logits, int32_t V, int32_t top_k, float temperature, float top_p, const float* exp_noise,
                       int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
+/* vx_op_sample_topp on the sampler instantiation of VX_FLAG_LOGPROBS: same arguments and same [sampled, argmax] result, plus
+ * lp_out[0] (host) = the log-probability of the sampled token on the raw row.  V <= 1088 only (else VX_ERR_UNSUPPORTED); argument
+ * checks as vx_op_sample_topp, before any HIP call. */
+int vx_op_sample_logprob(const float* logits, int32_t V, int32_t top_k, float temperature, float top_p,
+                         const float* exp_noise, int32_t* out_token_argmax, float* lp_out, void* stream);
 int vx_op_convert_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);
 
 /* ---- EnCodec-24 kHz codec: codec tokens -> waveform (what valle/bin/infer.py:251-253 does with VALLE.inference's result

@@ -767,8 +767,36 @@ __device__ __forceinline__ uint32_t topp_radix_block(const uint32_t (&key)[NVT],
 // block-level reductions, while wave 0 alone also holds all keys (NV0 per lane) for the exact top-k select.
 // Body of the four-wave sampler.  v[j] = logit j * 256 + tid (any value past V), `lg` = the whole row for wave 0's exact top-k
 // select (global memory in the stand-alone kernel, LDS when the predict-layer launch samples in place, ar_tp.hpp).
-template <int NVT, int NV0, typename Book>
-__device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, const ArState& s, float (&v)[NVT], float (&w0)[NV0], int slot, Book&& book) {
+// LP (VX_FLAG_LOGPROBS, a compile-time switch: the instantiation without it holds none of this): the pass also records
+//   lp[pass] = z[t] - logsumexp(z)
+// of the RAW row z (before temperature, top-k and top-p), t = the forced token where teacher forcing supplies one, lp_eos (1024)
+// when this pass ends the decode on EOS, else the sampled token.  The raw row is kept in registers beside the tempered one; the sum
+// of exp(z - max) runs in fp64 in a fixed order (thread-local in ascending j, butterfly over the 64 lanes, the four waves in
+// order), so a slot's value depends neither on the batch size nor on the slot; the wave partials cross LDS behind a barrier the
+// sampler has anyway.  -inf entries add 0, a -inf target gives -inf (never NaN), a token outside the row (a forced id can be)
+// gives NaN and reads nothing.  One thread evaluates the fp64 log and stores, behind the embedding's stores.  The LP kernel itself lives in logprob.hip.
+template <bool LP> __device__ __forceinline__ double* lp_partials() {
+  if constexpr (LP) {
+    __shared__ double s_lp[4];
+    return s_lp;
+  } else {
+    return nullptr;
+  }
+}
+// *dst = z[t] - max - log(sum) by the thread that holds z[t] (thread t & 255, register t >> 8); t outside [0, V): NaN by thread 0
+template <int NVT>
+__device__ __forceinline__ void lp_store(const float (&vr)[NVT], int t, int V, int tid, float mx, double sum, float* dst) {
+  const bool t_ok = t >= 0 && t < V;
+  if (t_ok ? tid != (t & 255) : tid != 0) return;
+  float zt = 0.f;
+#pragma unroll
+  for (int j = 0; j < NVT; ++j)
+    if (j == (t >> 8)) zt = vr[j];
+  *dst = !t_ok ? __int_as_float(0x7fc00000) : zt == -INFINITY ? -INFINITY : (float)(((double)zt - (double)mx) - log(sum));
+}
+template <int NVT, int NV0, bool LP, typename Book>
+__device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, const ArState& s, float (&v)[NVT], float (&w0)[NV0], int slot, Book&& book,
+                                             float* lp_out = nullptr, int lp_eos = -1) {
   // `s` = the decode state as the kernel read it in its FIRST round trip (one copy of the whole struct next to the logits loads;
   // read field by field where it was used, the state cost five dependent round trips: done, pass + exp_noise, noise_rows, ...);
   // `st` is written only.  w0 = wave 0's copy of the whole row for the exact top-k select, requested up front as well.
@@ -799,6 +827,11 @@ __device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, c
     if (i >= V) v[j] = -INFINITY;
     qn[j] = (nz != nullptr && i < V) ? nz[i] : 1.f;
   }
+  [[maybe_unused]] float vr[NVT];  // LP: the raw row (v is tempered in place below)
+  if constexpr (LP) {
+#pragma unroll
+    for (int j = 0; j < NVT; ++j) vr[j] = v[j];
+  }
   const float temp = s.temperature;
   const int top_k = s.top_k;
   const bool filt = top_k > 0 && top_k < V;  // uniform
@@ -821,6 +854,14 @@ __device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, c
   am = ValIdx{s_av[0], s_ai[0]};
 #pragma unroll
   for (int w = 1; w < 4; ++w) am = better(am, ValIdx{s_av[w], s_ai[w]});
+  if constexpr (LP) {  // this wave's part of sum(exp(z - max)); read behind the barrier in front of Z
+    double sl = 0.0;
+#pragma unroll
+    for (int j = 0; j < NVT; ++j) sl += (double)expf(vr[j] - am.v);  // exp(-inf) = 0
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sl += __shfl_xor(sl, o, WAVE);
+    if (lane == 0) lp_partials<LP>()[wave] = sl;
+  }
 
   if (temp != 1.0f) {  // valle.py:1296-1297
 #pragma unroll
@@ -857,6 +898,11 @@ __device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, c
   if (nucleus) *reinterpret_cast<uint4*>(s_hist + 4 * tid) = make_uint4(0u, 0u, 0u, 0u);  // behind the barrier below
   __syncthreads();
   float Z = ((s_f[0] + s_f[1]) + s_f[2]) + s_f[3];
+  [[maybe_unused]] double lp_sum = 0.0;
+  if constexpr (LP) {
+    const double* sp = lp_partials<LP>();
+    lp_sum = ((sp[0] + sp[1]) + sp[2]) + sp[3];
+  }
 
   // nucleus (top-p) filter, valle.py:1262-1282: a second key threshold T2, kept = key >= T2 as well (topp_fast_wave /
   // topp_radix_block above); the softmax is renormalised over what is left (Z).  Off (top_p 0 or >= 1): one uniform branch.
@@ -942,7 +988,13 @@ __device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, c
     if (reason != 0) { st->done = 1; st->stop_reason = reason; }
     if (go) { st->row = row; st->pass = pass + 1; }
   }
-  if (!go) return;
+  // LP: lp_store - the one thread that holds z[t] evaluates and stores the value, behind the embedding's loads and stores on the
+  // path that goes on (the fp64 log is off the step's critical tail), at once on the path that stops
+  if (!go) {
+    if constexpr (LP) lp_store<NVT>(vr, ((reason == 1 || reason == 2) && lp_eos >= 0) ? lp_eos : tok, V, tid, am.v, lp_sum,
+                                    lp_out + (size_t)slot * a.tok_stride + pass);
+    return;
+  }
   const int apos = row - s.kv_text;
   for (int c = tid * 4; c < a.d; c += 1024) {
     const float4 ev = *reinterpret_cast<const float4*>(a.emb + (size_t)tok * a.d + c);
@@ -952,6 +1004,8 @@ __device__ __forceinline__ void sample4_body(const SampleArgs& a, ArState* st, c
     o.z = __fadd_rn(ev.z, __fmul_rn(alpha, pv.z)); o.w = __fadd_rn(ev.w, __fmul_rn(alpha, pv.w));
     *reinterpret_cast<float4*>(xout + c) = o;
   }
+  if constexpr (LP) lp_store<NVT>(vr, ((reason == 1 || reason == 2) && lp_eos >= 0) ? lp_eos : tok, V, tid, am.v, lp_sum,
+                                  lp_out + (size_t)slot * a.tok_stride + pass);
 #ifdef VX_STAMPS
   VX_KSTAMP_SELF(a.kid, pass + 1, vx_t0);  // slot = the pass index every later kernel of this step reads
 #endif
@@ -995,7 +1049,7 @@ __global__ __launch_bounds__(256) void sample_embed4_kernel(const SampleArgs a) 
     }
   };
   if (s.done) { book(); return; }  // uniform
-  sample4_body<NVT, NV0>(a, st, s, v, w0, slot, book);
+  sample4_body<NVT, NV0, false>(a, st, s, v, w0, slot, book);
 }
 
 }  // namespace vx

@@ -26,6 +26,7 @@ __device__ unsigned long long* g_fq_stamps = nullptr;
 #include "mfma_kernels.hpp"
 #include "batch_kernels.hpp"
 #include "mx_kernels.hpp"
+#include "logprob.hpp"
 
 using namespace vx;
 
@@ -203,6 +204,14 @@ struct vx_engine {
   long long bleft[BMAX] = {};
   bool bcap[BMAX] = {};
   double t_bdecode = 0, n_blaunch = 0;
+  // VX_FLAG_LOGPROBS: the model's log-probability of every emitted token.  d_lp / blp: one fp32 per pass next to d_sampled /
+  // bsamp (same indexing), written by the sampler's LP instantiation; nar_lp: [stage][generated rows of the last NAR call], written
+  // by argmax_lp_rows_kernel, with that call's row offset and length per utterance.  All null without the flag.
+  bool lpon = false;
+  float *d_lp = nullptr, *blp = nullptr, *nar_lp = nullptr;
+  int bnpass[BMAX] = {};  // passes of a stopped slot's decode (0: none finished)
+  std::vector<int> nlp_off, nlp_T;
+  int nlp_rows = 0;
   hipGraphExec_t gexec = nullptr;  // the batch-1 step
   int gexec_nodes = 0;             // kernel launches captured in it (vx_get_timings out[9])
   // per-utterance state
@@ -408,6 +417,10 @@ extern "C" int vx_create(const vx_config* cfg, vx_engine** out) {
     return fail(VX_ERR_UNSUPPORTED, "VX_FLAG_KV_FP8 needs max_batch >= 2, bf16 / fp8nar precision, head_dim 64 and a pre-norm VALL-E "
                                     "without prenets");
 
+#ifdef VX_STAMPS
+  if (c.flags & VX_FLAG_LOGPROBS)  // its sampler lives in logprob.hip, which the stamp ring (a device global of this unit) does not reach
+    return fail(VX_ERR_UNSUPPORTED, "VX_FLAG_LOGPROBS is not available in the in-kernel stamp build: its sampler launch would go unstamped");
+#endif
   ON_DEVICE(c.device);
   vx_engine* e = new vx_engine();
   e->cfg = c;
@@ -589,6 +602,13 @@ static int create_body(vx_engine* e) {
     }
   }
   if (c.max_batch <= 1) VXC(seg_alloc(e));  // after the weights: no small block in the arena moves for lack of a batch block
+  e->lpon = c.flags & VX_FLAG_LOGPROBS;
+  if (e->lpon) {  // last: every other block sits where it sits without the flag
+    HIPC(logprob_load());
+    VXC(dalloc_t(e, &e->d_lp, (size_t)c.max_audio + 2));
+    if (c.max_batch > 1) VXC(dalloc_t(e, &e->blp, (size_t)BMAX * e->btok_stride));
+    if (c.num_quantizers > 1) VXC(dalloc_t(e, &e->nar_lp, (size_t)(c.num_quantizers - 1) * e->cap_audio));
+  }
   HIPC(hipStreamSynchronize(e->es));  // the fills above are done before the caller's uploads (other streams) begin
   return VX_OK;
 }
@@ -1327,7 +1347,7 @@ static int prefill_impl(vx_engine* e, int slot, const int64_t* text, int32_t S, 
     e->n_gen = 0; e->n_pass = 1; e->stop_reason = 0;
   } else {
     e->bS[slot] = S; e->bP[slot] = P; e->bbos[slot] = bos;
-    e->bprefilled[slot] = true; e->bngen[slot] = 0; e->breason[slot] = 0;
+    e->bprefilled[slot] = true; e->bngen[slot] = 0; e->breason[slot] = 0; e->bnpass[slot] = 0;
   }
   VXC(sync_out(e, stream));
   return VX_OK;
@@ -1460,7 +1480,7 @@ static int batch_prefill_impl(vx_engine* e, int32_t n, const int32_t* slots, con
   for (int b = 0; b < n; ++b) {
     const int sl = slots[b];
     e->bS[sl] = S[b]; e->bP[sl] = P[b]; e->bbos[sl] = bos;
-    e->bprefilled[sl] = true; e->bngen[sl] = 0; e->breason[sl] = 0;
+    e->bprefilled[sl] = true; e->bngen[sl] = 0; e->breason[sl] = 0; e->bnpass[sl] = 0;
   }
   VXC(sync_out(e, stream));
   return VX_OK;
@@ -1583,7 +1603,8 @@ static int launch_attn_decode(vx_engine* e, hipStream_t s, const void* kc, const
 static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
   const vx_config& c = e->cfg;
   const int d = c.d_model, H = c.nhead, hd = d / H;
-  sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(step_sample_args(e));
+  if (e->lpon) launch_sample_lp(step_sample_args(e), e->d_lp, NUM_AUDIO_TOKENS, 1, s);
+  else sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(step_sample_args(e));
   if (e->tp) return enqueue_ar_step_tp(e, s);
   if (c.flags & VX_FLAG_PRENET) VXC(enqueue_audio_prenet(e, s));
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
@@ -1866,6 +1887,23 @@ extern "C" int vx_ar_result(vx_engine* e, int64_t* tokens, int32_t capacity, int
   return read_tokens(e->d_tokens, e->n_gen, tokens, capacity);
 }
 
+// n fp32 values at `src` (device) into the caller's host buffer (nothing without one)
+static int read_logprobs(const float* src, int n, float* out, int32_t capacity) {
+  if (!out) return VX_OK;
+  if (capacity < n) return fail(VX_ERR_CAPACITY, "log-probability buffer too small (%d < %d)", capacity, n);
+  if (n) HIPC(hipMemcpy(out, src, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return VX_OK;
+}
+
+extern "C" int vx_ar_logprobs(vx_engine* e, float* out, int32_t capacity, int32_t* n) {
+  if (!e) return fail(VX_ERR_ARG, "null engine");
+  if (!e->lpon) return fail(VX_ERR_UNSUPPORTED, "vx_ar_logprobs needs an engine created with VX_FLAG_LOGPROBS");
+  if (!e->decoded) return fail(VX_ERR_STATE, "no finished decode");
+  ON_DEVICE(e->cfg.device);
+  if (n) *n = e->n_pass;
+  return read_logprobs(e->d_lp, e->n_pass, out, capacity);
+}
+
 // ------------------------------------------------------------------------------ batched AR decode
 template <int EPI, int NH, bool KV8> static int launch_bgemm_h(const BgemmArgs& a, int ns, int grid, hipStream_t s) {
   if (a.N > 65535 || a.K > 65535) return fail(VX_ERR_UNSUPPORTED, "bgemm: N=%d K=%d", a.N, a.K);  // (N << 16) | K travels as one argument
@@ -1910,7 +1948,8 @@ static int enqueue_batch_step(vx_engine* e, int B, hipStream_t s) {
   sa.alpha = W<float>(e, "ar_audio_position.alpha");
   sa.pe = e->pe_ar; sa.x = e->bx; sa.d = d;
   sa.logits_stride = LOGITS_CUR; sa.tok_stride = e->btok_stride;
-  sample_embed4_kernel<5, 17><<<B, 256, 0, s>>>(sa);
+  if (e->lpon) launch_sample_lp(sa, e->blp, NUM_AUDIO_TOKENS, B, s);
+  else sample_embed4_kernel<5, 17><<<B, 256, 0, s>>>(sa);
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd;  // elements
   const float scale = 1.0f / sqrtf((float)hd);
   const int kg_d = kgroups_for(d), kg_ff = kgroups_for(4 * d);
@@ -2007,6 +2046,7 @@ static int run_slots(vx_engine* e, int B, int min_stopped, int chunk, int32_t* s
       if (hs[b].done) {
         e->bslot[b] = SLOT_STOPPED;
         e->bngen[b] = hs[b].n_gen; e->breason[b] = hs[b].stop_reason;
+        e->bnpass[b] = hs[b].pass + 1;
         stopped[found++] = b;
         --live;
       } else if (at >= e->bleft[b]) {
@@ -2073,6 +2113,19 @@ extern "C" int vx_batch_result(vx_engine* e, int32_t slot, int64_t* tokens, int3
   return VX_OK;
 }
 
+// The log-probabilities of a slot's decode.  A session's slot must be STOPPED (vx_batch_result vacates it); after vx_batch_decode
+// every decoded slot answers until it is prefilled again.
+extern "C" int vx_batch_logprobs(vx_engine* e, int32_t slot, float* out, int32_t capacity, int32_t* n) {
+  if (!e) return fail(VX_ERR_ARG, "null engine");
+  if (!e->lpon) return fail(VX_ERR_UNSUPPORTED, "vx_batch_logprobs needs an engine created with VX_FLAG_LOGPROBS");
+  if (slot < 0 || slot >= e->bmax) return fail(VX_ERR_ARG, "bad slot");
+  if (e->bsess && e->bslot[slot] != SLOT_STOPPED) return fail(VX_ERR_STATE, "slot %d holds no finished, unread decode", slot);
+  if (e->bnpass[slot] <= 0) return fail(VX_ERR_STATE, "slot %d has no finished decode", slot);
+  ON_DEVICE(e->cfg.device);
+  if (n) *n = e->bnpass[slot];
+  return read_logprobs(e->blp + (size_t)slot * e->btok_stride, e->bnpass[slot], out, capacity);
+}
+
 // ------------------------------------------------------------------------------ continuous batching
 // A session over all max_batch slots: every slot is vacant, live (admitted, decoding) or stopped (its result not read yet).  The
 // step always runs at B = max_batch (one graph, shared with vx_batch_decode); vacant and stopped slots have done = 1, so the
@@ -2095,7 +2148,7 @@ extern "C" int vx_batch_open(vx_engine* e, void* stream) {
   HIPC(hipStreamSynchronize(e->es));  // the staging states are rewritten by the next admission
   for (int b = 0; b < e->bmax; ++b) {
     e->bslot[b] = SLOT_VACANT; e->bleft[b] = 0; e->bcap[b] = false;
-    e->bprefilled[b] = false; e->bngen[b] = 0; e->breason[b] = 0;
+    e->bprefilled[b] = false; e->bngen[b] = 0; e->breason[b] = 0; e->bnpass[b] = 0;
   }
   e->bsess = true;
   VXC(sync_out(e, stream));
@@ -2203,6 +2256,7 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
     arows += P[b] + T[b]; trows += T[b]; srows += S2[b];
   }
   ON_DEVICE(c.device);
+  if (e->lpon && !score) { e->nlp_off.clear(); e->nlp_T.clear(); }  // nar_lp is about to be overwritten: a call that fails leaves none
   VXC(sync_in(e, stream));
   HIPC(hipEventRecord(e->ev_t[4], e->es));
   RowSegs segs;
@@ -2289,7 +2343,10 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
       }
       VXC(gemm_rows(e, e->Hn, W<void>(e, "nar_predict_layers." + std::to_string(i) + ".weight"), nullptr, e->nar_logits,
                     trows, 1024, dn, GE_PLAIN, true));
-      argmax_rows_kernel<<<(trows + 3) / 4, 256, 0, e->es>>>(e->nar_logits, 1024, trows, e->ids_samples, e->d_codes, Q, i + 1);
+      if (e->lpon && !score)  // VX_FLAG_LOGPROBS: the same argmax, and the log-probability of the picked code per row
+        launch_argmax_lp_rows(e->nar_logits, trows, e->ids_samples, e->d_codes, Q, i + 1, e->nar_lp + (size_t)i * trows, e->es);
+      else
+        argmax_rows_kernel<<<(trows + 3) / 4, 256, 0, e->es>>>(e->nar_logits, 1024, trows, e->ids_samples, e->d_codes, Q, i + 1);
       if (score) {
         nll_rows_kernel<<<(trows + NLL_ROWS_PER_WG - 1) / NLL_ROWS_PER_WG, 256, 0, e->es>>>(e->nar_logits, trows, 1024, 1024, e->d_fcodes, Q, i + 1,
                                                                                    e->sc_nll, e->sc_rank, nullptr);
@@ -2320,7 +2377,27 @@ static int nar_run(vx_engine* e, int n, bool segmented, const int64_t* const* te
   e->t_nar = ms;
   gemm_collect(e);
   e->last_T = trows; e->last_N = rows;
+  if (e->lpon && !score) {
+    e->nlp_off.assign(toff.begin(), toff.end());
+    e->nlp_T.assign(T, T + n);
+    e->nlp_rows = trows;
+  }
   VXC(sync_out(e, stream));
+  return VX_OK;
+}
+
+extern "C" int vx_nar_logprobs(vx_engine* e, int32_t utt, float* out, int64_t capacity) {
+  if (!e) return fail(VX_ERR_ARG, "null engine");
+  if (!e->lpon) return fail(VX_ERR_UNSUPPORTED, "vx_nar_logprobs needs an engine created with VX_FLAG_LOGPROBS");
+  if (e->nlp_T.empty()) return fail(VX_ERR_STATE, "no finished NAR call");
+  if (utt < 0 || utt >= (int)e->nlp_T.size()) return fail(VX_ERR_ARG, "utterance %d outside the last NAR call's [0, %d)", utt, (int)e->nlp_T.size());
+  if (!out) return fail(VX_ERR_ARG, "null argument");
+  const int Q = e->cfg.num_quantizers, T = e->nlp_T[utt];
+  if (capacity < (int64_t)(Q - 1) * T) return fail(VX_ERR_CAPACITY, "log-probability buffer too small (%lld < %lld)", (long long)capacity, (long long)(Q - 1) * T);
+  ON_DEVICE(e->cfg.device);
+  for (int i = 0; i < Q - 1; ++i)
+    HIPC(hipMemcpyAsync(out + (size_t)i * T, e->nar_lp + (size_t)i * e->nlp_rows + e->nlp_off[utt], (size_t)T * 4, hipMemcpyDefault, e->es));
+  HIPC(hipStreamSynchronize(e->es));
   return VX_OK;
 }
 
@@ -2394,6 +2471,10 @@ static int ensure_rows(vx_engine* e, size_t rows, size_t audio_rows, size_t text
   VXC(regrow((void**)&e->ids_samples, audio_rows * 8));
   VXC(regrow((void**)&e->d_codes, audio_rows * 8 * 8));
   VXC(regrow((void**)&e->d_fcodes, audio_rows * 8 * 8));
+  if (e->nar_lp != nullptr) {  // VX_FLAG_LOGPROBS; the last call's values do not survive the move
+    VXC(regrow((void**)&e->nar_lp, (size_t)(c.num_quantizers - 1) * audio_rows * 4));
+    e->nlp_off.clear(); e->nlp_T.clear();
+  }
   if (e->xmem_rows != nullptr)  // VX_FLAG_VALLF_ROWS: the packed text memory of the batched NAR, cap_text rows per head
     VXC(regrow((void**)&e->xmem_rows, (size_t)c.nar_num_layers * 2 * c.nar_d_model * text_rows * 2));
   return VX_OK;
@@ -2942,6 +3023,43 @@ extern "C" int vx_op_sample_topp(const float* logits, int32_t V, int32_t top_k, 
   out[0] = host[4];
   out[1] = host[8];
   (void)hipFree(dst); (void)hipFree(scratch); (void)hipFree(fz);
+  return VX_OK;
+}
+
+// vx_op_sample_topp on the sampler's VX_FLAG_LOGPROBS instantiation (logprob.hip): the same scratch state, the same [sampled, argmax], and
+// lp_out[0] = the log-probability of the sampled token on the raw row (lp_eos < 0: an EOS argmax does not redirect it).
+extern "C" int vx_op_sample_logprob(const float* logits, int32_t V, int32_t top_k, float temperature, float top_p,
+                                    const float* exp_noise, int32_t* out, float* lp_out, void* stream) {
+  if (!logits || !out || !lp_out) return fail(VX_ERR_ARG, "null argument");
+  VXC(check_top_p(top_p));
+  if (V < 2 || V > 17 * 64) return fail(VX_ERR_UNSUPPORTED, "sample_logprob: V=%d (built for 2 <= V <= 1088)", V);
+  hipStream_t s = (hipStream_t)stream;
+  ArState h{};
+  h.S = 1 << 20; h.kv_text = h.S; h.top_k = top_k; h.temperature = temperature; h.max_new = -1; h.top_p = state_top_p(top_p);
+  h.exp_noise = exp_noise; h.noise_rows = 1; h.seed = 1;
+  struct Scratch {  // freed on every return
+    ArState* dst = nullptr;
+    int* words = nullptr;
+    float* fz = nullptr;
+    ~Scratch() { (void)hipFree(dst); (void)hipFree(words); (void)hipFree(fz); }
+  } m;
+  HIPC(hipMalloc((void**)&m.dst, sizeof h));
+  HIPC(hipMalloc((void**)&m.words, 16 * sizeof(int)));
+  HIPC(hipMalloc((void**)&m.fz, 4096 * sizeof(float)));
+  HIPC(hipMemsetAsync(m.fz, 0, 4096 * sizeof(float), s));
+  HIPC(hipMemcpyAsync(m.dst, &h, sizeof h, hipMemcpyHostToDevice, s));
+  SampleArgs sa{};
+  sa.logits = logits; sa.V = V; sa.st = m.dst;
+  sa.tokens = m.words; sa.sampled = m.words + 4; sa.argmaxes = m.words + 8;
+  sa.emb = m.fz; sa.alpha = m.fz; sa.pe = m.fz; sa.x = m.fz + 2048; sa.d = 0;
+  launch_sample_lp(sa, reinterpret_cast<float*>(m.words + 12), -1, 1, s);
+  HIPC(hipGetLastError());
+  int host[16];
+  HIPC(hipMemcpyAsync(host, m.words, sizeof host, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  out[0] = host[4];
+  out[1] = host[8];
+  memcpy(lp_out, &host[12], sizeof(float));
   return VX_OK;
 }
 

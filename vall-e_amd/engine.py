@@ -20,6 +20,7 @@ BMAX = 64  # slots per engine (csrc/batch_kernels.hpp)
 VX_FLAG_TRACE_LOGITS, VX_FLAG_NO_GRAPH, VX_FLAG_SIMPLE_ROWS, VX_FLAG_POST_NORM, VX_FLAG_PRENET, VX_FLAG_VALLF = 1, 2, 4, 8, 16, 32
 VX_FLAG_KV_FP8 = 64
 VX_FLAG_VALLF_ROWS = 128  # VALL-F: batched prefill / admission / NAR over concatenated rows (Engine(batched_rows=True))
+VX_FLAG_LOGPROBS = 256  # generation records the log-probability of every emitted token (Engine(logprobs=True))
 KV_CACHES = ("bf16", "fp8")  # storage of the batched decode's slot caches (VX_FLAG_KV_FP8)
 VX_ADMIT_BATCHED, VX_ADMIT_PER_SLOT = 0, 1
 VX_CODEC_LSTM_GRAPH, VX_CODEC_ENCODER = 1, 2
@@ -65,6 +66,9 @@ _SIGS = {
     "vx_ar_prefill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "vx_ar_decode": (C.c_int, [C.c_void_p, C.POINTER(VxDecodeParams), C.c_void_p]),
     "vx_ar_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vx_ar_logprobs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "vx_batch_logprobs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "vx_nar_logprobs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
     "vx_nar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "vx_nar_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_int32, C.c_void_p]),
@@ -109,6 +113,8 @@ _SIGS = {
     "vx_op_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "vx_op_sample_topp": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
                                     C.c_void_p]),
+    "vx_op_sample_logprob": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_float), C.c_void_p]),
     "vx_op_convert_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     # EnCodec decoder and encoder (codec.py)
     "vx_codec_create": (C.c_int, [C.POINTER(VxCodecConfig), C.POINTER(C.c_void_p)]),
@@ -204,7 +210,7 @@ class Engine:
 
     def __init__(self, cfg, precision: str = "bf16", max_text: int = 256, max_audio: int = 2048, device: int = 0,
                  trace_logits: bool = False, no_graph: bool = False, simple_rows: bool = False, max_batch: int = 0,
-                 kv_cache: str = "bf16", batched_rows: bool = False):
+                 kv_cache: str = "bf16", batched_rows: bool = False, logprobs: bool = False):
         if kv_cache not in KV_CACHES:
             raise ValueError(f"kv_cache must be one of {KV_CACHES}, got {kv_cache!r}")
         if batched_rows and not getattr(cfg, "is_vallf", False):
@@ -224,13 +230,16 @@ class Engine:
                   (VX_FLAG_SIMPLE_ROWS if simple_rows else 0) | (0 if getattr(cfg, "norm_first", True) else VX_FLAG_POST_NORM) | \
                   (VX_FLAG_PRENET if getattr(cfg, "add_prenet", False) else 0) | \
                   (VX_FLAG_VALLF if getattr(cfg, "is_vallf", False) else 0) | \
-                  (VX_FLAG_KV_FP8 if kv_cache == "fp8" else 0) | (VX_FLAG_VALLF_ROWS if batched_rows else 0)
+                  (VX_FLAG_KV_FP8 if kv_cache == "fp8" else 0) | (VX_FLAG_VALLF_ROWS if batched_rows else 0) | \
+                  (VX_FLAG_LOGPROBS if logprobs else 0)
         c.max_batch = int(max_batch)
         self.max_text, self.max_audio, self.trace_logits, self.max_batch = max_text, max_audio, trace_logits, int(max_batch)
         self.kv_cache = kv_cache
         # VALL-F only: the engine also keeps a packed text-memory buffer for the batched NAR pass (2 nar_layers nar_dim bf16 per text
         # row, grown with the other row buffers) and accepts batch_prefill_all / batch_admit(batched=True) / nar_batch
         self.batched_rows = bool(batched_rows)
+        # every decode and NAR call also records the log-probability of what it emitted (ar_logprobs / batch_logprobs / nar_logprobs)
+        self.logprobs = bool(logprobs)
         self.mfma_rows = c.precision != VX_PREC_F32 and not simple_rows
         h = C.c_void_p()
         _check(self.lib.vx_create(C.byref(c), C.byref(h)))
@@ -299,6 +308,33 @@ class Engine:
         toks = torch.empty(n.value, dtype=torch.int64)
         _check(self.lib.vx_ar_result(self.h, _ptr(toks), n.value, C.byref(n), C.byref(reason), C.byref(npass)))
         return toks, reason.value, npass.value
+
+    def _logprobs(self, fn, *lead):
+        n = C.c_int32()
+        _check(fn(self.h, *lead, None, 0, C.byref(n)))
+        out = torch.empty(n.value, dtype=torch.float32)
+        _check(fn(self.h, *lead, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def ar_logprobs(self) -> torch.Tensor:
+        """(n_pass,) fp32 on the host: the log-probability of every pass of the last ``ar_decode`` (vx_ar_logprobs); needs
+        ``logprobs=True``."""
+        return self._logprobs(self.lib.vx_ar_logprobs)
+
+    def batch_logprobs(self, slot: int) -> torch.Tensor:
+        """``ar_logprobs`` of a slot (vx_batch_logprobs).  In a session: before the ``batch_result`` that vacates the slot."""
+        return self._logprobs(self.lib.vx_batch_logprobs, int(slot))
+
+    def nar_logprobs(self, utt: int, T: int) -> torch.Tensor:
+        """(Q-1, T) fp32 on the host: per stage and generated frame the log-probability of the code the stage picked, for
+        utterance ``utt`` of the last NAR call (vx_nar_logprobs)."""
+        out = torch.empty((max(self.cfg.num_quantizers - 1, 0), int(T)), dtype=torch.float32)
+        _check(self.lib.vx_nar_logprobs(self.h, int(utt), _ptr(out), out.numel()))
+        return out
+
+    @staticmethod
+    def op_sample_logprob(logits, top_k, temperature, top_p, exp_noise):
+        return op_sample_logprob(logits, top_k, temperature, top_p, exp_noise)
 
     def nar(self, text_nar: torch.Tensor, prompts: torch.Tensor, ar_tokens: torch.Tensor, out_device=None, stream=None,
             continual: bool = False, forced_codes: Optional[torch.Tensor] = None, stage_logits: bool = False):
@@ -742,6 +778,17 @@ def op_sample_topp(logits, top_k, temperature, top_p, exp_noise):
     _check(lib.vx_op_sample_topp(_ptr(logits), logits.numel(), int(top_k), float(temperature), _struct_top_p(top_p),
                                  _ptr(exp_noise), out, current_stream_ptr(logits.device)))
     return out[0], out[1]
+
+
+def op_sample_logprob(logits, top_k, temperature, top_p, exp_noise):
+    """vx_op_sample_logprob: (sampled, argmax, lp) - ``op_sample_topp`` on the sampler instantiation that also records the
+    log-probability of the sampled token on the raw row."""
+    lib = load_library()
+    out = (C.c_int32 * 2)()
+    lp = C.c_float()
+    _check(lib.vx_op_sample_logprob(_ptr(logits), logits.numel(), int(top_k), float(temperature), _struct_top_p(top_p),
+                                    _ptr(exp_noise), out, C.byref(lp), current_stream_ptr(logits.device)))
+    return out[0], out[1], lp.value
 
 
 def launch_floor(n_kernels=62, grid=256, block=256, iters=200):  # the three probes below need load_probe_library()

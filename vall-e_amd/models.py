@@ -84,6 +84,52 @@ def aggregate_score(ar_nll, ar_rank, ar_targets, nar_nll, nar_rank, nar_targets,
     return ScoreResult(ar_nll, ar_rank, nar_nll, nar_rank, ar_loss, nar_loss, ar_acc, nar_acc, int(top_k))
 
 
+EOS_STOPS = (1, 2)  # VX_STOP_EOS_ARGMAX, VX_STOP_EOS_SAMPLE: the pass that stopped the decode is scored at EOS
+
+
+@dataclass
+class GenLogProbs:
+    """What generation reports next to the codes on a model built with ``logprobs=True`` (VX_FLAG_LOGPROBS): the model's
+    log-probability of every token it emitted, on the raw logits (before temperature, top-k and top-p).
+      ar (n_pass,) fp32     pass i: log p(t_i), t_i the appended token (the forced one under teacher forcing), EOS for the pass
+                            that ended the decode on EOS, else the sampled token.  ar[:n_tokens] lines up with codebook 0 of the
+                            codes; after an EOS stop ar[n_tokens] is the EOS term and the sum is -ScoreResult.ar_loss of the codes
+      nar (Q-1, T) fp32     stage i, frame t: log p of the code the stage picked (its argmax); None when Q == 1 or T == 0
+      n_tokens, stop_reason of the AR decode (engine.STOP_REASONS)"""
+    ar: torch.Tensor
+    nar: Optional[torch.Tensor]
+    n_tokens: int
+    stop_reason: int
+
+    @property
+    def ar_mean(self) -> float:
+        """Mean log-probability per emitted AR token, the closing EOS included when the decode stopped on it (NaN when nothing
+        was emitted): the length-normalised score best-of-N ranks by."""
+        n = self.n_tokens + (1 if self.stop_reason in EOS_STOPS else 0)
+        return float(self.ar[:n].double().mean()) if n > 0 else float("nan")
+
+
+@dataclass
+class BestOf:
+    """What ``inference_best_of`` reports next to the winner's codes: the winner's ``index`` among the n candidates, their
+    ``seeds``, ``ar_mean`` (n floats, GenLogProbs.ar_mean) and ``tokens`` (the n codebook-0 sequences), and the winner's
+    ``logprobs``."""
+    index: int
+    seeds: List[int]
+    ar_mean: List[float]
+    tokens: List[torch.Tensor]
+    logprobs: Optional[GenLogProbs] = None
+
+
+def best_of_index(ar_mean) -> int:
+    """Best-of-N's choice: the highest mean log-probability, ties to the lower index; a candidate that emitted nothing (NaN)
+    ranks last."""
+    vals = [float("-inf") if v != v else float(v) for v in ar_mean]
+    if not vals:
+        raise ValueError("no candidates")
+    return max(range(len(vals)), key=lambda i: (vals[i], -i))
+
+
 class VALLE:
     """Decoder-only VALL-E (inference only).  Engine-specific keyword arguments (not in the
     reference): ``precision`` ("bf16" | "fp32" | "fp8nar"), ``max_text``, ``max_audio`` (capacities), ``max_batch`` (slots of
@@ -93,7 +139,11 @@ class VALLE:
     ``sampling`` ("device": on-GPU counter RNG seeded from torch's global generator;
     "torch_cpu": reproduce the exact Exp(1) stream torch.multinomial would consume on CPU).  ``inference``,
     ``inference_batch`` and ``inference_stream`` take a ``top_p`` keyword (default 1.0, off): the reference's nucleus filter
-    (top_k_top_p_filtering, valle.py:1262-1282) after temperature and top-k, which its VALLE.inference does not expose."""
+    (top_k_top_p_filtering, valle.py:1262-1282) after temperature and top-k, which its VALLE.inference does not expose.
+    ``logprobs=True`` (VX_FLAG_LOGPROBS, any configuration): generation also records the model's log-probability of every token it
+    emits; ``inference`` / ``inference_batch`` / ``inference_stream`` then accept ``return_logprobs=True`` and return
+    ``(codes, GenLogProbs)`` per utterance, and ``inference_best_of`` (max_batch >= 2) samples n candidates of one utterance and
+    keeps the most likely.  Without it nothing changes."""
 
     MODEL_NAME = "VALL-E"  # what the EOS line prints and get_model dispatches on (models/__init__.py:98-124)
 
@@ -104,7 +154,7 @@ class VALLE:
             max_audio=kwargs.pop("max_audio", 4096), trace_logits=kwargs.pop("trace_logits", False),
             no_graph=kwargs.pop("no_graph", False), simple_rows=kwargs.pop("simple_rows", False),
             max_batch=kwargs.pop("max_batch", 0), kv_cache=kwargs.pop("kv_cache", "bf16"),
-            batched_rows=bool(kwargs.pop("batched_rows", False)))
+            batched_rows=bool(kwargs.pop("batched_rows", False)), logprobs=bool(kwargs.pop("logprobs", False)))
         self.sampling = kwargs.pop("sampling", "device")
         self.print_eos = kwargs.pop("print_eos", True)
         self.cfg = ModelConfig(model_name=self.MODEL_NAME, decoder_dim=d_model, nhead=nhead, num_decoder_layers=num_layers, norm_first=norm_first,
@@ -219,12 +269,14 @@ class VALLE:
     @torch.no_grad()
     def inference(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor, enroll_x_lens: Optional[torch.Tensor],
                   top_k: int = -100, temperature: float = 1.0, exp_noise: Optional[torch.Tensor] = None,
-                  max_new_tokens: int = -1, top_p: float = 1.0) -> torch.Tensor:
+                  max_new_tokens: int = -1, top_p: float = 1.0, return_logprobs: bool = False) -> torch.Tensor:
         """Same contract as the reference (valle.py:961-985): x (1,S) int64, x_lens (1,), y (1,P,8) int64 →
         (1,T,num_quantizers) int64 on the model's device.  ``exp_noise`` / ``max_new_tokens`` / ``top_p`` are extras.
         This batch-1 path keeps its own bf16 KV cache on every model, ``kv_cache="fp8"`` included (that option only
-        changes the slot caches of ``inference_batch`` / ``inference_stream``)."""
+        changes the slot caches of ``inference_batch`` / ``inference_stream``).  ``return_logprobs=True`` (models built with
+        ``logprobs=True``): returns ``(codes, GenLogProbs)``."""
         top_p = _check_top_p(top_p)
+        self._check_logprobs(return_logprobs)
         u = (x, x_lens, y, enroll_x_lens)
         self._check_utterance(u)
         eng = self.engine()
@@ -241,6 +293,7 @@ class VALLE:
         eng.ar_decode(top_k=top_k, temperature=temperature, exp_noise=exp_noise, seed=seed, max_new_tokens=max_new_tokens,
                       top_p=top_p)
         tokens, reason, n_pass = eng.ar_result()
+        lp_ar = eng.ar_logprobs() if return_logprobs else None
         if rng_state is not None:
             # leave the global generator where the reference would: one draw per executed pass, including
             # the pass that trips the stop rule (valle.py:1040-1055)
@@ -251,44 +304,106 @@ class VALLE:
         if self.print_eos:
             print(f"{self.MODEL_NAME} EOS [{P} -> {P + bos + tokens.numel()}]")  # valle.py:1054 / 646
         if isinstance(r, torch.Tensor):
-            return r
-        return eng.nar(*r, out_device=self.device).unsqueeze(0)
+            return (r, GenLogProbs(lp_ar, None, tokens.numel(), reason)) if return_logprobs else r
+        codes = eng.nar(*r, out_device=self.device).unsqueeze(0)
+        if return_logprobs:
+            return codes, GenLogProbs(lp_ar, eng.nar_logprobs(0, tokens.numel()), tokens.numel(), reason)
+        return codes
 
 
     @torch.no_grad()
     def inference_batch(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, batched_nar: bool = True,
-                        batched_prefill: bool = True, top_p: float = 1.0):
+                        batched_prefill: bool = True, top_p: float = 1.0, return_logprobs: bool = False):
         """Engine extension (BASELINE configs[2]): ``utterances`` = list of (x, x_lens, y[, enroll_x_lens]) as for
         ``inference``; up to ``max_batch`` of them advance together, one shared weight stream per AR step, each with
-        its own KV cache / sampler / stop rule; the NAR stages then run per utterance.  Returns a list of (1,T_i,Q)."""
+        its own KV cache / sampler / stop rule; the NAR stages then run per utterance.  Returns a list of (1,T_i,Q), with
+        ``return_logprobs=True`` (models built with ``logprobs=True``) a list of ((1,T_i,Q), GenLogProbs)."""
         top_p = _check_top_p(top_p)
+        self._check_logprobs(return_logprobs)
         eng = self._batch_engine("inference_batch")
         Q = self.num_quantizers
         out = [None] * len(utterances)
         for g0 in range(0, len(utterances), eng.max_batch):
             group = utterances[g0 : g0 + eng.max_batch]
-            for b, u in enumerate(group):
-                x, y = u[0], u[2]
-                self._check_utterance(u)
-                if not (batched_prefill and eng.mfma_rows):
-                    eng.batch_prefill(b, x[0], y[0, :, 0].contiguous())
-            if batched_prefill and eng.mfma_rows:  # one pass over the concatenated rows of the whole group
-                eng.batch_prefill_all([u[0][0] for u in group], [u[2][0, :, 0].contiguous() for u in group])
-            sd = [int(torch.randint(0, 2**62, (1,))) for _ in group] if seeds is None else list(seeds[g0 : g0 + len(group)])
-            eng.batch_decode(len(group), top_k=top_k, temperature=temperature, seeds=sd, top_p=top_p)
+            sd = self._ar_group(eng, group, None if seeds is None else list(seeds[g0 : g0 + len(group)]), top_k, temperature, top_p,
+                                batched_prefill)
             todo = []  # (index, text_nar, prompts, tokens) of the utterances that go through the NAR stages
+            glp = {}   # index -> GenLogProbs (return_logprobs)
             for b, u in enumerate(group):
+                lp_ar = eng.batch_logprobs(b) if return_logprobs else None
                 tokens, reason = eng.batch_result(b)
+                if return_logprobs:
+                    glp[g0 + b] = GenLogProbs(lp_ar, None, tokens.numel(), reason)
                 r = self._ar_finished(u, tokens)
                 if isinstance(r, torch.Tensor):
                     out[g0 + b] = r
                 else:
                     todo.append((g0 + b,) + r)
-            for i, r in self._run_nar(eng, todo, batched_nar):
+            for i, r in self._run_nar(eng, todo, batched_nar, glp if return_logprobs else None):
                 out[i] = r
+            if return_logprobs:
+                for i in glp:
+                    out[i] = (out[i], glp[i])
         return out
 
+    def _ar_group(self, eng, group, seeds, top_k, temperature, top_p, batched_prefill):
+        """Prefills ``group`` (at most max_batch utterances) into slots 0.. and decodes them together; returns the seeds used
+        (drawn from torch's global generator when none are given)."""
+        for b, u in enumerate(group):
+            x, y = u[0], u[2]
+            self._check_utterance(u)
+            if not (batched_prefill and eng.mfma_rows):
+                eng.batch_prefill(b, x[0], y[0, :, 0].contiguous())
+        if batched_prefill and eng.mfma_rows:  # one pass over the concatenated rows of the whole group
+            eng.batch_prefill_all([u[0][0] for u in group], [u[2][0, :, 0].contiguous() for u in group])
+        sd = [int(torch.randint(0, 2**62, (1,))) for _ in group] if seeds is None else seeds
+        eng.batch_decode(len(group), top_k=top_k, temperature=temperature, seeds=sd, top_p=top_p)
+        return sd
+
+    @torch.no_grad()
+    def inference_best_of(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor, enroll_x_lens: Optional[torch.Tensor],
+                          n: int, top_k: int = -100, temperature: float = 1.0, top_p: float = 1.0, seeds=None):
+        """Engine extension: best-of-N synthesis.  The utterance (arguments as for ``inference``) is sampled ``n`` times with
+        ``n`` different seeds (``seeds``, or drawn as ``inference_batch`` draws them) in the slots of the batched decode, in
+        groups of max_batch; the candidates are ranked by their mean AR log-probability (GenLogProbs.ar_mean, which the decode
+        itself recorded: no scoring pass), highest first, ties to the lower index, and the NAR stages run for the winner only.
+        Returns ``(codes (1,T,Q), BestOf)``; the codes are what ``inference_batch`` returns for the utterance with the winner's
+        seed.  Needs a model built with ``logprobs=True`` (ValueError) and ``max_batch >= 2`` (NotImplementedError)."""
+        top_p = _check_top_p(top_p)
+        self._check_logprobs(True, "inference_best_of")
+        if self.engine_opts["max_batch"] < 2:
+            raise NotImplementedError("inference_best_of decodes its candidates in the slots of the batched decode: it needs max_batch >= 2")
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"n must be >= 1 (got {n})")
+        if seeds is not None and len(seeds) != n:
+            raise ValueError(f"{len(seeds)} seeds for n = {n} candidates")
+        u = (x, x_lens, y, enroll_x_lens)
+        self._check_utterance(u)
+        eng = self._batch_engine("inference_best_of")
+        rows = self.engine_opts["batched_rows"] if self.cfg.is_vallf else True  # as inference_batch's defaults on this model
+        used, cands = [], []
+        for g0 in range(0, n, eng.max_batch):
+            k = min(eng.max_batch, n - g0)
+            used += self._ar_group(eng, [u] * k, None if seeds is None else [int(s) for s in seeds[g0 : g0 + k]], top_k, temperature,
+                                   top_p, rows)
+            for b in range(k):
+                lp_ar = eng.batch_logprobs(b)
+                tokens, reason = eng.batch_result(b)
+                cands.append((tokens, GenLogProbs(lp_ar, None, tokens.numel(), reason)))
+        means = [c[1].ar_mean for c in cands]
+        w = best_of_index(means)
+        tokens, lp = cands[w]
+        glp = {0: lp}
+        r = self._ar_finished(u, tokens)
+        codes = r if isinstance(r, torch.Tensor) else self._run_nar(eng, [(0,) + r], rows, glp)[0][1]
+        return codes, BestOf(w, used, means, [c[0] for c in cands], lp)
+
     # ---- shared by inference, inference_batch and inference_stream ------------------------------------
+    def _check_logprobs(self, wanted: bool, what: str = "return_logprobs=True"):
+        if wanted and not self.engine_opts["logprobs"]:
+            raise ValueError(f"{what} needs a model built with logprobs=True (VX_FLAG_LOGPROBS)")
+
     def _batch_engine(self, what: str):
         eng = self.engine()
         if eng.max_batch < 2:
@@ -326,25 +441,36 @@ class VALLE:
             text_nar = torch.concat([x[0][:1], x[0][enrolled_len - 1:]])
         return (text_nar, y[0, :, :Q].contiguous(), tokens)
 
-    def _run_nar(self, eng, todo, batched_nar: bool):
-        """[(index, text_nar, prompts, tokens)] -> [(index, (1, T, Q) codes)]: one vx_nar_batch over all, or vx_nar each."""
+    def _run_nar(self, eng, todo, batched_nar: bool, glp=None):
+        """[(index, text_nar, prompts, tokens)] -> [(index, (1, T, Q) codes)]: one vx_nar_batch over all, or vx_nar each.
+        ``glp`` (index -> GenLogProbs): each utterance's ``nar`` is filled in from the call that ran its stages."""
         if todo and batched_nar:
             res = eng.nar_batch([t[1] for t in todo], [t[2] for t in todo], [t[3] for t in todo], out_device=self.device)
+            if glp is not None:
+                for z, t in enumerate(todo):
+                    glp[t[0]].nar = eng.nar_logprobs(z, t[3].numel())
             return [(t[0], r.unsqueeze(0)) for t, r in zip(todo, res)]
-        return [(i, eng.nar(tn, pr, tk, out_device=self.device).unsqueeze(0)) for i, tn, pr, tk in todo]
+        out = []
+        for i, tn, pr, tk in todo:
+            out.append((i, eng.nar(tn, pr, tk, out_device=self.device).unsqueeze(0)))
+            if glp is not None:
+                glp[i].nar = eng.nar_logprobs(0, tk.numel())
+        return out
 
     @torch.no_grad()
     def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
                          poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None,
-                         top_p: float = 1.0):
+                         top_p: float = 1.0, return_logprobs: bool = False):
         """Engine extension: continuous batching.  A generator over ``utterances`` (as for ``inference_batch``) that yields
         ``(index, codes)``, codes (1, T_i, Q) as ``inference_batch`` returns them, as utterances finish.  A slot whose utterance
         stopped is refilled from the queue while the others keep decoding: new utterances are admitted once ``refill_at``
         slots are free (default max_batch // 16, at least 1) and whenever the rest of the queue fits.  Finished utterances
         wait for their NAR stages until ``nar_group`` (default max_batch) are pending or the queue is empty.  ``seeds[i]``
         belongs to utterance i, so the codes do not depend on the schedule.  ``batched_admit=False`` prefills slot by slot
-        (bitwise the static path); ``poll_steps``: steps between stop polls (0: the engine default)."""
+        (bitwise the static path); ``poll_steps``: steps between stop polls (0: the engine default).  ``return_logprobs=True``
+        (models built with ``logprobs=True``): yields ``(index, (codes, GenLogProbs))``."""
         top_p = _check_top_p(top_p)
+        self._check_logprobs(return_logprobs)
         eng = self._batch_engine("inference_stream")
         utterances = list(utterances)
         for u in utterances:
@@ -358,11 +484,13 @@ class VALLE:
         nar_group = B if nar_group is None else max(1, int(nar_group))
         batched_admit = batched_admit and eng.mfma_rows
         return self._stream(eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at,
-                            top_p)
+                            top_p, return_logprobs)
 
     def _stream(self, eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at,
-                top_p=1.0):
+                top_p=1.0, return_logprobs=False):
         N, B = len(utterances), eng.max_batch
+        glp = {} if return_logprobs else None  # index -> GenLogProbs of the utterances not yet yielded
+        give = (lambda i, c: (i, (c, glp.pop(i)))) if return_logprobs else (lambda i, c: (i, c))
         eng.batch_open()
         free = list(range(B))
         live = {}      # slot -> utterance index
@@ -381,16 +509,20 @@ class VALLE:
                 need = 1 if nxt >= N else max(1, refill_at - len(free))
                 for s in eng.batch_run(need, poll_steps):
                     i = live.pop(s)
-                    tokens, _ = eng.batch_result(s)
+                    lp_ar = eng.batch_logprobs(s) if return_logprobs else None  # while the slot is STOPPED: the result vacates it
+                    tokens, reason = eng.batch_result(s)
+                    if return_logprobs:
+                        glp[i] = GenLogProbs(lp_ar, None, tokens.numel(), reason)
                     free.append(s)
                     r = self._ar_finished(utterances[i], tokens)
                     if isinstance(r, torch.Tensor):
-                        yield i, r
+                        yield give(i, r)
                     else:
                         pending.append((i,) + r)
             if pending and (len(pending) >= nar_group or nxt >= N):
                 done, pending = pending, []
-                yield from self._run_nar(eng, done, batched_nar)
+                for i, c in self._run_nar(eng, done, batched_nar, glp):
+                    yield give(i, c)
 
     # ---- scoring ---------------------------------------------------------------------------------------
     def _score_args(self, x, x_lens, y, prompt_frames, enroll_x_lens, top_k):
@@ -499,20 +631,20 @@ class VALLF(VALLE):
             raise NotImplementedError(f"VALL-F {what} needs a model built with max_batch >= 2 (otherwise batch-1 path only)")
 
     def inference_batch(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, batched_nar: bool = True,
-                        batched_prefill: bool = True, top_p: float = 1.0):
+                        batched_prefill: bool = True, top_p: float = 1.0, return_logprobs: bool = False):
         self._vallf_batched("inference_batch")
         rows = self.engine_opts["batched_rows"]
         return super().inference_batch(utterances, top_k=top_k, temperature=temperature, seeds=seeds, batched_nar=rows and batched_nar,
-                                       batched_prefill=rows and batched_prefill, top_p=top_p)
+                                       batched_prefill=rows and batched_prefill, top_p=top_p, return_logprobs=return_logprobs)
 
     def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
                          poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None,
-                         top_p: float = 1.0):
+                         top_p: float = 1.0, return_logprobs: bool = False):
         self._vallf_batched("inference_stream")
         rows = self.engine_opts["batched_rows"]
         return super().inference_stream(utterances, top_k=top_k, temperature=temperature, seeds=seeds, nar_group=nar_group,
                                         poll_steps=poll_steps, batched_admit=rows and batched_admit, batched_nar=rows and batched_nar,
-                                        refill_at=refill_at, top_p=top_p)
+                                        refill_at=refill_at, top_p=top_p, return_logprobs=return_logprobs)
 
 
 def get_model(params) -> VALLE:
@@ -526,7 +658,7 @@ def get_model(params) -> VALLE:
         raise NotImplementedError(f"model {cfg.model_name!r}: only VALL-E and VALL-F are built (DESIGN.md)")
     extra = {}
     get = params.get if isinstance(params, dict) else lambda k, d=None: getattr(params, k, d)
-    for k in ("precision", "max_text", "max_audio", "sampling", "max_batch", "kv_cache", "batched_rows"):
+    for k in ("precision", "max_text", "max_audio", "sampling", "max_batch", "kv_cache", "batched_rows", "logprobs"):
         if get(k, None) is not None:
             extra[k] = get(k)
     return cls(cfg.decoder_dim, cfg.nhead, cfg.num_decoder_layers, norm_first=cfg.norm_first, add_prenet=cfg.add_prenet,
