@@ -299,12 +299,36 @@ int vx_score_batch(vx_engine* e, int32_t n, const int64_t* const* text, const in
                    const int32_t* S2, const int64_t* const* codes, const int32_t* A, const int32_t* P, float* const* nll_ar,
                    int32_t* const* rank_ar, float* const* nll_nar, int32_t* const* rank_nar, void* stream);
 
+/* ---- alignment: the attention the AR decoder pays to the text while it predicts each frame, and per-token timestamps from it.
+ * The utterance is laid out as for vx_score (codes (A, Q), frames [0, P) the prompt, T = A - P) and goes through the same
+ * teacher-forced row pass; row i of the outputs is the input row that predicts frame P + i (the row that predicts EOS is not
+ * included).  For every tapped layer l and head h, p_lh[i, s] is the softmax probability that row puts on text token s: in VALL-E
+ * the text columns of its self-attention (the softmax runs over all S text keys and the audio keys up to the row itself), in
+ * VALL-F its cross-attention over the S memory keys.  This is what the reference's attention module returns with
+ * need_weights=True (modules/activation.py:205-251), which its layers never ask for.
+ *   attn (T, c1 - c0) fp32       sum_lh head_w[l, h] p_lh[i, c0 + j], the text window [c0, c1), 0 <= c0 < c1 <= S
+ *   mass (T) fp32, nullable      sum_lh head_w[l, h] sum_{s < S} p_lh[i, s]: the weighted share of the row's attention that goes
+ *                                to the text at all (1 for VALL-F)
+ *   path (T) int32, nullable     the monotonic path j(0) = 0, j(T-1) = c1 - c0 - 1, steps of 0 or 1, that maximises
+ *   path_score double, nullable    sum_i log(max(attn[i, j(i)], FLT_MIN)), computed in fp64, ties staying in the column;
+ *                                T < c1 - c0 admits no such path: path is all -1 and path_score -inf, which is not an error
+ *   per_head (L, H, T, c1 - c0) fp32, nullable   p_lh itself, every layer and head, zero-weight ones included
+ * head_w: HOST array (L, H) fp32 of weights used as given, or NULL for the uniform 1 / (L H); a layer whose weights are all zero
+ * is not tapped unless per_head is wanted.  Outputs may be host or device memory.  The sum over heads and layers runs in a fixed
+ * order without atomics: the same call gives the same bits.  Checked before any work is enqueued: the checks of vx_score's AR part
+ * (P = 0 needs prepend_bos); a window outside the text, a negative or non-finite weight, all weights zero -> VX_ERR_ARG; S >
+ * max_text, A + 1 > max_audio, or a path over more than 4096 text tokens -> VX_ERR_CAPACITY.  Every engine vx_score serves; no
+ * decode state is touched. */
+int vx_align(vx_engine* e, const int64_t* text, int32_t S, const int64_t* codes /* (A, Q) */, int32_t A, int32_t P, int32_t c0,
+             int32_t c1, const float* head_w /* (L, H) host, nullable */, float* attn /* (T, c1-c0) */, float* mass /* (T) */,
+             int32_t* path /* (T) */, double* path_score, float* per_head /* (L, H, T, c1-c0) */, void* stream);
+
 /* Device-time of the last calls, measured with HIP events on the engine's stream:
  * out[0] prefill ms, out[1] AR decode ms, out[2] NAR ms, out[3] AR passes, out[4] graph launches, out[5] batched decode ms,
  * out[6] batched graph launches; with VX_TIME_GEMMS=1 in the environment also out[7] = ms spent in the QKV / out-projection / FFN
  * GEMM launches of the last NAR call and out[8] = their FLOPs (2 M N K each); out[9] kernel launches per pass of the batch-1 decode
  * step (nodes of its captured graph; 0 before the first vx_ar_decode and with VX_FLAG_NO_GRAPH); out[10] / out[11] ms of the AR / NAR
- * part of the last vx_score or vx_score_batch. */
+ * part of the last vx_score or vx_score_batch; out[12] ms of the last vx_align (row set-up, stack, taps and path). */
 int vx_get_timings(vx_engine* e, double* out, int32_t n);
 
 /* Parity-test taps: copies an internal buffer to host memory (synchronises the engine stream).
@@ -407,6 +431,20 @@ int vx_op_ln_batch(float* x, const float* part, int32_t kgroups, const float* pb
  * call. */
 int vx_op_nll_rows(const float* logits, int32_t rows, int32_t V, int32_t ld, const int64_t* targets, float* nll, int32_t* rank,
                    int32_t* argmax, void* stream);
+/* The attention tap of vx_align (attn_text_rows_kernel) on caller buffers, all DEVICE pointers: `rows` query rows, head h of row i
+ * at q + i ldq + h hd; key j of head h at k + j ldk + h k_head_stride (elements of the type prec selects; packed (M, 3 d) rows: ldk
+ * = 3 d, k_head_stride = hd; the memory layout (nhead, max_text, hd): ldk = hd, k_head_stride = max_text hd).  causal != 0: row i
+ * sees keys [0, text_len + row0 + i + 1), the text keys and the audio keys up to its own (row0: audio position of row 0); causal
+ * == 0: keys [0, text_len).  attn (rows, c1 - c0) += sum_h head_w[h] p_h[i, c0 + j], mass (rows, nullable) += sum_h head_w[h]
+ * sum_{s < text_len} p_h[i, s] (first != 0: stored instead of added); per_head (nhead, rows, c1 - c0), nullable: p_h of every
+ * head.  A zero-weight head is skipped unless per_head is given.  hd in {4, 8, 16, 32, 64}.  A row's result does not depend on
+ * rows or on its place in the launch.  Bad arguments: VX_ERR_ARG before any HIP call. */
+int vx_op_attn_text_rows(int32_t prec, const void* q, int64_t ldq, const void* k, int64_t ldk, int64_t k_head_stride, int32_t rows,
+                         int32_t row0, int32_t nhead, int32_t hd, int32_t text_len, int32_t causal, int32_t c0, int32_t c1,
+                         const float* head_w, float* attn, float* mass, float* per_head, int32_t first, void* stream);
+/* The path of vx_align (mono_path_kernel) on a caller map: attn (T, Sw) fp32, path (T) int32, score (1) double, DEVICE pointers;
+ * Sw <= 4096 (else VX_ERR_CAPACITY).  Synchronises `stream`. */
+int vx_op_mono_path(const float* attn, int32_t T, int32_t Sw, int32_t* path, double* score, void* stream);
 int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
                  int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 /* vx_op_sample with the nucleus filter after top-k (top_p as in vx_decode_params: 0 or >= 1 off, NaN / negative VX_ERR_ARG).

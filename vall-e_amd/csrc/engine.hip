@@ -27,6 +27,7 @@ __device__ unsigned long long* g_fq_stamps = nullptr;
 #include "batch_kernels.hpp"
 #include "mx_kernels.hpp"
 #include "logprob.hpp"
+#include "align.hpp"
 
 using namespace vx;
 
@@ -163,6 +164,14 @@ struct vx_engine {
   int sc_ld = 0, sc_rows = 0;  // sc_rows: AR rows scored by the last call (tap "score_ar_argmax")
   void *sc_head = nullptr, *xkv_score = nullptr;
   double t_score_ar = 0, t_score_nar = 0;
+  // alignment (vx_align), allocated at the first call and grown on demand: the (T, Sw) map, the per-row text mass, the path with
+  // its score and back-pointers, the (L, H) head weights and, when the caller's per-head buffer is host memory, its staging
+  float *al_attn = nullptr, *al_mass = nullptr, *al_w = nullptr, *al_ph = nullptr;
+  int* al_path = nullptr;
+  double* al_score = nullptr;
+  unsigned char* al_bp = nullptr;
+  size_t al_cells = 0, al_rows = 0, al_ph_cells = 0;
+  double t_align = 0;
   // batched decode (slots)
   int bmax = 0;
   float *bx = nullptr, *bq = nullptr, *bpart = nullptr, *blogits = nullptr, *btrace = nullptr;
@@ -1083,6 +1092,27 @@ struct TextMem {
   const long long* off = nullptr; const int* klen = nullptr;
   long long layer_stride = 0, head_stride = 0, v_offset = 0;
 };
+// The attention tap of run_stack (vx_align): `rows` rows of the pass from row `row` of e->X on, row i being audio position
+// row0 + i, accumulate the head-weighted attention they pay to the text columns [c0, c1) of `text_len` text tokens
+// (attn_text_rows_kernel, align.hpp).  w: the (L, H) weights on the device, hw: the same on the host - a layer whose weights are
+// all zero is not launched unless per_head, (L, H, rows, c1 - c0), is wanted.  Unsegmented AR passes only.
+struct AttnTap {
+  const float *w = nullptr, *hw = nullptr;
+  int row = 0, rows = 0, row0 = 0, text_len = 0, c0 = 0, c1 = 0;
+  float *attn = nullptr, *mass = nullptr, *per_head = nullptr;
+};
+static int tap_layer(vx_engine* e, const AttnTap& t, int li, int H, int hd, const void* q, long long ldq, const void* k, long long ldk,
+                     long long k_head_stride, int causal, bool& first) {
+  bool any = t.per_head != nullptr;
+  for (int h = 0; h < H && !any; ++h) any = t.hw[li * H + h] != 0.f;
+  if (!any) return VX_OK;
+  float* ph = t.per_head ? t.per_head + (size_t)li * H * t.rows * (t.c1 - t.c0) : nullptr;
+  if (launch_attn_text_rows(e->bf16, q, ldq, k, ldk, k_head_stride, t.rows, t.row0, H, hd, t.text_len, causal, t.c0, t.c1, t.w + li * H,
+                            t.attn, t.mass, ph, first ? 1 : 0, e->es))
+    return fail(VX_ERR_UNSUPPORTED, "attention tap: head_dim %d", hd);
+  first = false;
+  return VX_OK;
+}
 // The text memories of n segments at once: `trows` concatenated text rows (segment z = rows [trow[z], trow[z] + S[z]), no padding)
 // in operand precision in e->Hn -> one in_proj GEMM per layer over all of them (the packed cross in_proj whole, N = 3 d, as
 // memory_kv) and one scatter launch into every segment's memory (`mem`, written through the same descriptors run_stack reads).
@@ -1108,9 +1138,11 @@ static int memory_kv_segs(vx_engine* e, const std::vector<LayerW>& layers, const
 // the feed-forward block.  `ada_stage` < 0: plain LayerNorm (AR); otherwise the stage's AdaLN vectors.  `segs`: the row layout;
 // `kv`: where the K/V rows also go (KvDst).
 static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int d, int H, int text_len, int ada_stage,
-                     const RowSegs& segs, KvDst kv, TextMem mem = TextMem()) {
+                     const RowSegs& segs, KvDst kv, TextMem mem = TextMem(), const AttnTap* tap = nullptr) {
   const bool post = e->cfg.flags & VX_FLAG_POST_NORM, cross = mem.kv != nullptr;
   if (cross && segs.n > 0 && mem.off == nullptr) return fail(VX_ERR_UNSUPPORTED, "cross-attention over segmented rows");
+  if (tap && (segs.n > 0 || ada_stage >= 0)) return fail(VX_ERR_UNSUPPORTED, "attention tap on a segmented or NAR pass");
+  bool tap_first = true;  // the first tapped layer stores, the others add
   const int hd = d / H;
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
   const size_t mem_layer = (size_t)2 * d * e->cfg.max_text * e->esz;
@@ -1163,6 +1195,9 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
       VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
     }
     if (tg) gemm_mark(e, 2.0 * M * 3 * d * d);
+    if (tap && !cross)  // VALL-E: the text columns of the self-attention of the tapped rows, from the packed q / k rows
+      VXC(tap_layer(e, *tap, li, H, hd, (const char*)e->QKV + (size_t)tap->row * 3 * d * e->esz, 3 * d, (const char*)e->QKV + d * e->esz,
+                    3 * d, hd, 1, tap_first));
     const size_t kvl = (size_t)2 * H * e->ctx_max * 64;  // elements per layer of a slot cache
     if (kv.kind == KvDst::SEG_SLOTS) {  // batched prefill: segment z -> slot segs.slot[z]
       if (e->kv8)
@@ -1195,6 +1230,9 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
       VXC(norm_in(li, 1));
       VXC(gemm_rows(e, e->Hn, l.cin_w, l.cin_b, e->QKV, M, d, d, GE_BIAS, false, false));  // q = rows [0, d) of the packed in_proj
       const char* xk = (const char*)mem.kv + li * mem_layer;
+      if (tap)  // VALL-F: the cross-attention of the tapped rows over this layer's memory K
+        VXC(tap_layer(e, *tap, li, H, hd, (const char*)e->QKV + (size_t)tap->row * d * e->esz, d, xk, hd, (long long)e->cfg.max_text * hd, 0,
+                      tap_first));
       if (segs.n > 0)  // every segment over its own memory (VX_FLAG_VALLF_ROWS)
         cross_attn_seg_launch((const bf16*)e->QKV, d, (const bf16*)mem.kv + li * mem.layer_stride, mem.off, mem.head_stride, mem.v_offset,
                               mem.klen, (bf16*)e->ATT, d, H, segs.start, segs.len, segs.n, segs.max_len, e->es);
@@ -2574,15 +2612,22 @@ static int check_score_utterance(vx_engine* e, const int64_t* text, int32_t S, c
   return VX_OK;
 }
 
-// The AR scoring pass of n utterances (segmented: concatenated rows as in batch_prefill_impl; else n == 1, rows from 0): rows
-// [text | (BOS) codes[:, 0]] through the AR stack under the prefix mask, final norm + predict layer on the T + 1 rows that
-// predict codes[P, 0] ... codes[A-1, 0], EOS (valle.py:863-877), then nll_rows_kernel.  Outputs per utterance, T_b + 1 entries.
-static int score_ar_run(vx_engine* e, int n, bool segmented, const int64_t* const* text, const int32_t* S, const int64_t* const* codes,
-                        const int32_t* A, const int32_t* P, float* const* nll, int32_t* const* rank) {
+// The rows of the teacher-forced AR pass, shared by scoring and alignment: the layout of n utterances (segmented: concatenated
+// rows as in batch_prefill_impl; else n == 1, rows from 0) and their set-up in e->X - [text | (BOS) codes[:, 0]] embedded, through
+// the prenets where the model has them, positions added; VALL-F: the text rows become the memory K / V in e->xkv_score and the
+// audio rows start at row 0.  The ids go to ids_text / d_fcodes ((A_b, Q) codes of utterance b at frame offset aoff[b]).
+struct ScoreRows {
+  std::vector<int> start, len, tlen, aoff, soff, roff;  // roff: offsets of the T_b + 1 scored rows
+  RowSegs segs;
+};
+static int score_rows_setup(vx_engine* e, int n, bool segmented, const int64_t* const* text, const int32_t* S, const int64_t* const* codes,
+                            const int32_t* A, const int32_t* P, ScoreRows& r) {
   const vx_config& c = e->cfg;
   const int Q = c.num_quantizers, d = c.d_model, bos = c.prepend_bos ? 1 : 0;
-  const bool vf = e->vallf, prenet = c.flags & VX_FLAG_PRENET, post = c.flags & VX_FLAG_POST_NORM;
-  std::vector<int> start(n + 1), len(n), tlen(n), aoff(n), soff(n), roff(n + 1);
+  const bool vf = e->vallf, prenet = c.flags & VX_FLAG_PRENET;
+  r.start.assign(n + 1, 0); r.len.assign(n, 0); r.tlen.assign(n, 0); r.aoff.assign(n, 0); r.soff.assign(n, 0); r.roff.assign(n + 1, 0);
+  std::vector<int>&start = r.start, &len = r.len, &tlen = r.tlen, &aoff = r.aoff, &soff = r.soff, &roff = r.roff;
+  RowSegs& segs = r.segs;
   int arows = 0, srows = 0;
   roff[0] = 0;
   for (int b = 0; b < n; ++b) {
@@ -2592,8 +2637,6 @@ static int score_ar_run(vx_engine* e, int n, bool segmented, const int64_t* cons
     arows += A[b] + 1; srows += S[b];
     roff[b + 1] = roff[b] + (A[b] - P[b]) + 1;
   }
-  HIPC(hipEventRecord(e->ev_t[0], e->es));
-  RowSegs segs;
   if (segmented) VXC(seg_layout(e, n, len.data(), tlen.data(), nullptr, d, arows, srows, start.data(), segs));
   else { start[0] = 0; start[1] = len[0]; }
   VXC(score_reserve(e, roff[n]));
@@ -2629,6 +2672,23 @@ static int score_ar_run(vx_engine* e, int n, bool segmented, const int64_t* cons
       embed_pos_kernel<<<A[b], 256, 0, e->es>>>(ic, Q, 0, w_aud, 1025 + bos, d, a_aud, e->pe_ar, bos, xa + (size_t)bos * d, A[b]);
     }
   }
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// The AR scoring pass of n utterances: the rows of score_rows_setup through the AR stack under the prefix mask, final norm +
+// predict layer on the T + 1 rows that predict codes[P, 0] ... codes[A-1, 0], EOS (valle.py:863-877), then nll_rows_kernel.
+// Outputs per utterance, T_b + 1 entries.
+static int score_ar_run(vx_engine* e, int n, bool segmented, const int64_t* const* text, const int32_t* S, const int64_t* const* codes,
+                        const int32_t* A, const int32_t* P, float* const* nll, int32_t* const* rank) {
+  const vx_config& c = e->cfg;
+  const int Q = c.num_quantizers, d = c.d_model, bos = c.prepend_bos ? 1 : 0;
+  const bool vf = e->vallf, post = c.flags & VX_FLAG_POST_NORM;
+  HIPC(hipEventRecord(e->ev_t[0], e->es));
+  ScoreRows sr;
+  VXC(score_rows_setup(e, n, segmented, text, S, codes, A, P, sr));
+  const std::vector<int>&start = sr.start, &tlen = sr.tlen, &aoff = sr.aoff, &roff = sr.roff;
+  const RowSegs& segs = sr.segs;
   VXC(run_stack(e, e->ar_l, start[n], d, c.nhead, segmented ? 0 : tlen[0], -1, segs, KvDst(),
                 vf ? TextMem{e->xkv_score, S[0]} : TextMem()));
   // final norm (pre-norm; a post-norm stack's rows are already normalised) on the scored rows, compacted to [sum (T + 1)][d]
@@ -2738,11 +2798,99 @@ extern "C" int vx_score_batch(vx_engine* e, int32_t n, const int64_t* const* tex
   return VX_OK;
 }
 
+// ------------------------------------------------------------------------------ alignment (vx_align)
+// The attention the AR decoder pays to the text while it predicts each frame, from the same teacher-forced row pass as scoring
+// (score_rows_setup + run_stack with an attention tap; no final norm, no predict layer), and the best monotonic path through it.
+// Like scoring it writes nothing the decode paths keep.
+
+// Scratch of vx_align for a (T, Sw) map, nw head weights and, when staged, ph_cells per-head cells.
+static int align_reserve(vx_engine* e, size_t T, size_t Sw, size_t nw, size_t ph_cells) {
+  auto regrow = [&](void** p, size_t bytes) -> int {
+    for (auto& q : e->allocs) if (*p && q == *p) { (void)hipFree(q); q = nullptr; }
+    HIPC(hipMalloc(p, bytes));
+    if (poison_on()) { HIPC(hipMemsetAsync(*p, 0xFF, bytes, e->es)); HIPC(hipStreamSynchronize(e->es)); }
+    e->allocs.push_back(*p);
+    return VX_OK;
+  };
+  if (e->al_w == nullptr) { VXC(regrow((void**)&e->al_w, nw * 4)); VXC(regrow((void**)&e->al_score, 8)); }
+  if (T * Sw > e->al_cells || T > e->al_rows || ph_cells > e->al_ph_cells) HIPC(hipStreamSynchronize(e->es));
+  if (T * Sw > e->al_cells) {
+    VXC(regrow((void**)&e->al_attn, T * Sw * 4));
+    VXC(regrow((void**)&e->al_bp, T * Sw));
+    e->al_cells = T * Sw;
+  }
+  if (T > e->al_rows) {
+    VXC(regrow((void**)&e->al_mass, T * 4));
+    VXC(regrow((void**)&e->al_path, T * 4));
+    e->al_rows = T;
+  }
+  if (ph_cells > e->al_ph_cells) {
+    VXC(regrow((void**)&e->al_ph, ph_cells * 4));
+    e->al_ph_cells = ph_cells;
+  }
+  return VX_OK;
+}
+
+// The (L, H) head weights of a tap as given or uniform; VX_ERR_ARG unless every entry is finite and >= 0 and one is > 0.
+static int align_weights(const float* head_w, int n, std::vector<float>& hw) {
+  hw.assign(n, 1.0f / (float)n);
+  if (head_w == nullptr) return VX_OK;
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    if (!std::isfinite(head_w[i]) || head_w[i] < 0.f) return fail(VX_ERR_ARG, "head_w[%d] = %g: weights must be finite and >= 0", i, (double)head_w[i]);
+    any = any || head_w[i] > 0.f;
+    hw[i] = head_w[i];
+  }
+  if (!any) return fail(VX_ERR_ARG, "head_w is all zero: no head to align by");
+  return VX_OK;
+}
+
+extern "C" int vx_align(vx_engine* e, const int64_t* text, int32_t S, const int64_t* codes, int32_t A, int32_t P, int32_t c0, int32_t c1,
+                        const float* head_w, float* attn, float* mass, int32_t* path, double* path_score, float* per_head, void* stream) {
+  if (!e || !attn) return fail(VX_ERR_ARG, "null argument");
+  if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+  const vx_config& c = e->cfg;
+  const int L = c.num_layers, H = c.nhead, d = c.d_model, bos = c.prepend_bos ? 1 : 0;
+  if (!(0 <= c0 && c0 < c1 && c1 <= S)) return fail(VX_ERR_ARG, "text window [%d, %d) outside [0, S=%d)", c0, c1, S);
+  std::vector<float> hw;
+  VXC(align_weights(head_w, L * H, hw));
+  VXC(check_score_utterance(e, text, S, nullptr, 0, codes, A, P, true, false, -1));
+  const int T = A - P, Sw = c1 - c0, first = bos ? P : P - 1;
+  if ((path || path_score) && Sw > ALIGN_MAX_SW) return fail(VX_ERR_CAPACITY, "a path over %d text tokens (at most %d)", Sw, ALIGN_MAX_SW);
+  ON_DEVICE(c.device);
+  VXC(sync_in(e, stream));
+  HIPC(hipEventRecord(e->ev_t[0], e->es));
+  ScoreRows sr;
+  VXC(score_rows_setup(e, 1, false, &text, &S, &codes, &A, &P, sr));
+  const size_t ph_cells = (size_t)L * H * T * Sw;
+  const bool ph_staged = per_head && host_readable(per_head);
+  VXC(align_reserve(e, T, Sw, (size_t)L * H, ph_staged ? ph_cells : 0));
+  HIPC(hipMemcpyAsync(e->al_w, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, e->es));
+  AttnTap tap;
+  tap.w = e->al_w; tap.hw = hw.data();
+  tap.row = sr.tlen[0] + first; tap.rows = T; tap.row0 = first; tap.text_len = S; tap.c0 = c0; tap.c1 = c1;
+  tap.attn = e->al_attn; tap.mass = e->al_mass; tap.per_head = !per_head ? nullptr : ph_staged ? e->al_ph : per_head;
+  VXC(run_stack(e, e->ar_l, sr.start[1], d, H, sr.tlen[0], -1, sr.segs, KvDst(), e->vallf ? TextMem{e->xkv_score, S} : TextMem(), &tap));
+  if (path || path_score) launch_mono_path(e->al_attn, T, Sw, e->al_bp, e->al_path, e->al_score, e->es);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(e->ev_t[1], e->es));
+  HIPC(hipMemcpyAsync(attn, e->al_attn, (size_t)T * Sw * 4, hipMemcpyDefault, e->es));
+  if (mass) HIPC(hipMemcpyAsync(mass, e->al_mass, (size_t)T * 4, hipMemcpyDefault, e->es));
+  if (path) HIPC(hipMemcpyAsync(path, e->al_path, (size_t)T * 4, hipMemcpyDefault, e->es));
+  if (path_score) HIPC(hipMemcpyAsync(path_score, e->al_score, 8, hipMemcpyDefault, e->es));
+  if (ph_staged) HIPC(hipMemcpyAsync(per_head, e->al_ph, ph_cells * 4, hipMemcpyDefault, e->es));
+  HIPC(hipStreamSynchronize(e->es));  // the host arrays above and the staging are free again
+  float ms = 0.f;
+  HIPC(hipEventElapsedTime(&ms, e->ev_t[0], e->ev_t[1]));
+  e->t_align = ms;
+  return sync_out(e, stream);
+}
+
 extern "C" int vx_get_timings(vx_engine* e, double* out, int32_t n) {
   if (!e || !out) return fail(VX_ERR_ARG, "null argument");
-  const double v[12] = {e->t_prefill, e->t_decode, e->t_nar, (double)e->n_pass, e->n_launch, e->t_bdecode, e->n_blaunch,
-                        e->t_gemm, e->gemm_flops_done, (double)e->gexec_nodes, e->t_score_ar, e->t_score_nar};
-  for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
+  const double v[13] = {e->t_prefill, e->t_decode, e->t_nar, (double)e->n_pass, e->n_launch, e->t_bdecode, e->n_blaunch,
+                        e->t_gemm, e->gemm_flops_done, (double)e->gexec_nodes, e->t_score_ar, e->t_score_nar, e->t_align};
+  for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
   return VX_OK;
 }
 
@@ -2941,6 +3089,35 @@ extern "C" int vx_op_attention(int32_t prec, int32_t mfma, const void* qkv, void
     attn_rows_simple_kernel<float, 64><<<grid, 256, 0, s>>>((const float*)qkv, (float*)out, rows, d, text_len, scale);
   }
   HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// The two alignment kernels on caller (device) buffers: see align.hpp for the operands.
+extern "C" int vx_op_attn_text_rows(int32_t prec, const void* q, int64_t ldq, const void* k, int64_t ldk, int64_t k_head_stride,
+                                    int32_t rows, int32_t row0, int32_t nhead, int32_t hd, int32_t text_len, int32_t causal, int32_t c0,
+                                    int32_t c1, const float* head_w, float* attn, float* mass, float* per_head, int32_t first,
+                                    void* stream) {
+  if (!q || !k || !head_w || !attn) return fail(VX_ERR_ARG, "null argument");
+  if (rows < 1 || nhead < 1 || text_len < 1 || row0 < 0) return fail(VX_ERR_ARG, "rows, nhead and text_len must be >= 1, row0 >= 0");
+  if (!(0 <= c0 && c0 < c1 && c1 <= text_len)) return fail(VX_ERR_ARG, "text window [%d, %d) outside [0, %d)", c0, c1, text_len);
+  if (launch_attn_text_rows(prec == VX_PREC_BF16, q, ldq, k, ldk, k_head_stride, rows, row0, nhead, hd, text_len, causal ? 1 : 0, c0, c1,
+                            head_w, attn, mass, per_head, first ? 1 : 0, (hipStream_t)stream))
+    return fail(VX_ERR_UNSUPPORTED, "attention tap: head_dim %d", hd);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+extern "C" int vx_op_mono_path(const float* attn, int32_t T, int32_t Sw, int32_t* path, double* score, void* stream) {
+  if (!attn || !path || !score) return fail(VX_ERR_ARG, "null argument");
+  if (T < 1 || Sw < 1) return fail(VX_ERR_ARG, "T and Sw must be >= 1");
+  if (Sw > ALIGN_MAX_SW) return fail(VX_ERR_CAPACITY, "a path over %d text tokens (at most %d)", Sw, ALIGN_MAX_SW);
+  unsigned char* bp = nullptr;
+  HIPC(hipMalloc((void**)&bp, (size_t)T * Sw));
+  launch_mono_path(attn, T, Sw, bp, path, score, (hipStream_t)stream);
+  const hipError_t err = hipGetLastError(), err2 = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(bp);
+  HIPC(err);
+  HIPC(err2);
   return VX_OK;
 }
 

@@ -87,6 +87,8 @@ _SIGS = {
     "vx_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
                  + [C.c_void_p] * 4 + [C.c_void_p]),
     "vx_score_batch": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 11 + [C.c_void_p]),
+    "vx_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+                 + [C.c_void_p] * 6 + [C.c_void_p]),
     "vx_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
     "vx_read_buffer": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int64]),
     "vx_buffer_bytes": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
@@ -110,6 +112,9 @@ _SIGS = {
     "vx_op_ln_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                        C.c_void_p]),
     "vx_op_nll_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_void_p]),
+    "vx_op_attn_text_rows": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 8
+                             + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
+    "vx_op_mono_path": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vx_op_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "vx_op_sample_topp": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
                                     C.c_void_p]),
@@ -515,6 +520,41 @@ class Engine:
         none = [None] * n
         return list(zip(an or none, ak or none, nn_ or none, nk or none))
 
+    # -- alignment (vx_align) --------------------------------------------------------------------------
+    def align(self, text: torch.Tensor, codes: torch.Tensor, prompt_frames: int, c0: int = 0, c1: Optional[int] = None,
+              head_w: Optional[torch.Tensor] = None, path: bool = True, per_head: bool = False, stream=None):
+        """The attention the AR decoder pays to text tokens [c0, c1) while it predicts frames prompt_frames .. A-1 of ``codes``
+        (A, Q), teacher-forced (vx_align).  ``head_w``: (L, H) weights used as given (None: uniform).  Returns device tensors
+        (attn (T, c1-c0) fp32, mass (T,) fp32, path (T,) int32 or None, path_score (1,) float64 or None, per_head (L, H, T, c1-c0)
+        fp32 or None)."""
+        text = text.to(torch.int64).contiguous()
+        codes = codes.to(torch.int64).contiguous()
+        A, Q = codes.shape
+        assert Q == self.cfg.num_quantizers, (Q, self.cfg.num_quantizers)
+        S, P = text.numel(), int(prompt_frames)
+        c0, c1 = int(c0), S if c1 is None else int(c1)
+        T, Sw = max(A - P, 0), max(c1 - c0, 0)
+        L, H = self.cfg.num_decoder_layers, self.cfg.nhead
+        hw = None
+        if head_w is not None:
+            hw = torch.as_tensor(head_w).detach().to("cpu", torch.float32).contiguous()
+            assert tuple(hw.shape) == (L, H), (tuple(hw.shape), (L, H))
+        dev = torch.device("cuda", self.device)
+        attn = torch.empty((T, Sw), dtype=torch.float32, device=dev)
+        mass = torch.empty(T, dtype=torch.float32, device=dev)
+        pth = torch.empty(T, dtype=torch.int32, device=dev) if path else None
+        psc = torch.empty(1, dtype=torch.float64, device=dev) if path else None
+        ph = torch.empty((L, H, T, Sw), dtype=torch.float32, device=dev) if per_head else None
+        _check(self.lib.vx_align(self.h, _ptr(text), S, _ptr(codes), A, P, c0, c1, _ptr(hw), _ptr(attn), _ptr(mass), _ptr(pth),
+                                 _ptr(psc), _ptr(ph), stream))
+        return attn, mass, pth, psc, ph
+
+    def align_ms(self) -> float:
+        """Device ms of the last ``align``."""
+        buf = (C.c_double * 13)()
+        _check(self.lib.vx_get_timings(self.h, buf, 13))
+        return buf[12]
+
     def score_timings(self):
         """Device ms of the AR and the NAR part of the last ``score`` / ``score_batch``."""
         buf = (C.c_double * 12)()
@@ -761,6 +801,44 @@ def op_nll_rows(logits, targets, V=None):
     _check(lib.vx_op_nll_rows(_ptr(logits), rows, V, ld, _ptr(targets.contiguous()), _ptr(nll), _ptr(rank), _ptr(am),
                               current_stream_ptr(logits.device)))
     return nll, rank, am
+
+
+ALIGN_TILE_ROWS = 32  # query rows of one workgroup of attn_text_rows_kernel (csrc/align.hpp)
+
+
+def op_attn_text_rows(q, k, nhead, hd, text_len, causal, c0, c1, head_w, attn, mass=None, per_head=None, first=True, row0=0,
+                      ldk=None, k_head_stride=None):
+    """attn_text_rows_kernel on device buffers (vx_op_attn_text_rows): q (rows, ldq), head h at columns [h hd, (h + 1) hd); k any
+    contiguous tensor, key j of head h at k.flatten()[j ldk + h k_head_stride:][:hd] (default: rows of q's width, heads side by
+    side).  ``attn`` (rows, c1-c0) fp32 and ``mass`` (rows,) are updated in place (``first``: stored); ``per_head`` (nhead, rows,
+    c1-c0) is filled.  The operands' extents are checked here: the kernel trusts them."""
+    lib = load_library()
+    assert q.dim() == 2 and q.is_contiguous() and k.is_contiguous() and q.dtype == k.dtype
+    rows, ldq = q.shape
+    ldk = k.shape[-1] if ldk is None else int(ldk)
+    khs = hd if k_head_stride is None else int(k_head_stride)
+    nkeys = text_len + row0 + rows if causal else text_len
+    assert nhead * hd <= ldq and (nkeys - 1) * ldk + (nhead - 1) * khs + hd <= k.numel(), "q / k smaller than the launch reads"
+    Sw = c1 - c0
+    assert head_w.dtype == torch.float32 and head_w.numel() == nhead and head_w.is_cuda
+    assert attn.dtype == torch.float32 and attn.is_contiguous() and tuple(attn.shape) == (rows, Sw)
+    assert mass is None or (mass.dtype == torch.float32 and mass.numel() == rows)
+    assert per_head is None or (per_head.dtype == torch.float32 and per_head.is_contiguous() and tuple(per_head.shape) == (nhead, rows, Sw))
+    _check(lib.vx_op_attn_text_rows(_prec(q), _ptr(q), ldq, _ptr(k), ldk, khs, rows, int(row0), nhead, hd, text_len, int(bool(causal)),
+                                    c0, c1, _ptr(head_w), _ptr(attn), _ptr(mass), _ptr(per_head), int(bool(first)),
+                                    current_stream_ptr(q.device)))
+    return attn
+
+
+def op_mono_path(attn):
+    """mono_path_kernel on a device map (T, Sw) fp32 (vx_op_mono_path): (path (T,) int32, score (1,) float64), on the device."""
+    lib = load_library()
+    assert attn.dtype == torch.float32 and attn.dim() == 2 and attn.is_contiguous() and attn.is_cuda
+    T, Sw = attn.shape
+    path = torch.empty(T, dtype=torch.int32, device=attn.device)
+    score = torch.empty(1, dtype=torch.float64, device=attn.device)
+    _check(lib.vx_op_mono_path(_ptr(attn), T, Sw, _ptr(path), _ptr(score), current_stream_ptr(attn.device)))
+    return path, score
 
 
 def op_sample(logits, top_k, temperature, exp_noise):

@@ -130,6 +130,81 @@ def best_of_index(ar_mean) -> int:
     return max(range(len(vals)), key=lambda i: (vals[i], -i))
 
 
+FRAME_RATE = 75.0  # codec frames per second (EnCodec at 24 kHz, hop 320)
+
+
+@dataclass
+class Alignment:
+    """What ``VALLE.align`` returns: the attention the AR decoder pays to the text while it predicts each of the T scored frames,
+    over the Sw text tokens of the window, and the timestamps that follow from it.
+      attn (T, Sw) fp32        head-weighted softmax probability of frame t on text token j (VALL-E: the text columns of the
+                               self-attention; VALL-F: the cross-attention over the text memory)
+      text_mass (T,) fp32      weighted share of frame t's attention that goes to the text at all (1 for VALL-F)
+      path (T,) int32 / None   the best monotonic path (token 0 at frame 0, token Sw-1 at frame T-1, steps of 0 or 1); None when
+                               T < Sw, i.e. the audio is too short to speak every token
+      path_score float         sum_t log attn[t, path[t]] (-inf without a path)
+      spans (Sw, 2) int32      [start, end) frame of each text token on the path; None without a path
+      seconds (Sw, 2) fp32     spans / 75.0
+      token_mass (Sw,) fp32    attn.sum(0): how much attention each token received in all (near 0: a skipped token)
+      per_head (L, H, T, Sw)   every head's own map, when asked for"""
+    attn: torch.Tensor
+    text_mass: torch.Tensor
+    path: Optional[torch.Tensor]
+    path_score: float
+    spans: Optional[torch.Tensor]
+    seconds: Optional[torch.Tensor]
+    token_mass: torch.Tensor
+    per_head: Optional[torch.Tensor] = None
+
+
+def path_spans(path: torch.Tensor, Sw: int) -> torch.Tensor:
+    """(Sw, 2) int32 [start, end) frame of each token of a monotonic path (T,) that visits every column 0 .. Sw-1 in order."""
+    p = path.to(torch.int64)
+    counts = torch.bincount(p, minlength=Sw)
+    end = torch.cumsum(counts, 0)
+    return torch.stack([end - counts, end], 1).to(torch.int32)
+
+
+def make_alignment(attn, text_mass, path, path_score, per_head=None) -> Alignment:
+    """Engine outputs -> Alignment (spans, seconds and token_mass computed here with torch)."""
+    score = float(path_score) if path_score is not None else float("-inf")
+    if path is None or (path.numel() and int(path[0]) < 0):
+        path = spans = seconds = None
+    else:
+        spans = path_spans(path, attn.shape[1])
+        seconds = spans.to(torch.float32) / FRAME_RATE
+    return Alignment(attn, text_mass, path, score, spans, seconds, attn.sum(0), per_head)
+
+
+def head_weights(heads, L: int, H: int) -> Optional[torch.Tensor]:
+    """``align``'s ``heads`` -> None (all heads, uniform) or an (L, H) fp32 tensor that sums to 1: a list of (layer, head) pairs
+    (uniform over them) or an (L, H) tensor of non-negative weights (normalised)."""
+    if heads is None:
+        return None
+    if isinstance(heads, torch.Tensor):
+        w = heads.detach().to("cpu", torch.float64)
+        if tuple(w.shape) != (L, H):
+            raise ValueError(f"heads tensor must be ({L}, {H}), got {tuple(w.shape)}")
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()) or float(w.sum()) <= 0:
+            raise ValueError("heads weights must be finite, >= 0 and not all zero")
+        return (w / w.sum()).to(torch.float32)
+    pairs = list(heads)
+    if not pairs:
+        raise ValueError("heads is empty: no head to align by")
+    w = torch.zeros((L, H), dtype=torch.float64)
+    for pr in pairs:
+        try:
+            l, h = (int(v) for v in pr)
+        except (TypeError, ValueError):
+            raise ValueError(f"heads must be (layer, head) pairs, got {pr!r}") from None
+        if not (0 <= l < L and 0 <= h < H):
+            raise ValueError(f"head {(l, h)} outside ({L}, {H})")
+        if w[l, h] != 0:
+            raise ValueError(f"head {(l, h)} listed twice")
+        w[l, h] = 1.0
+    return (w / w.sum()).to(torch.float32)
+
+
 class VALLE:
     """Decoder-only VALL-E (inference only).  Engine-specific keyword arguments (not in the
     reference): ``precision`` ("bf16" | "fp32" | "fp8nar"), ``max_text``, ``max_audio`` (capacities), ``max_batch`` (slots of
@@ -143,7 +218,10 @@ class VALLE:
     ``logprobs=True`` (VX_FLAG_LOGPROBS, any configuration): generation also records the model's log-probability of every token it
     emits; ``inference`` / ``inference_batch`` / ``inference_stream`` then accept ``return_logprobs=True`` and return
     ``(codes, GenLogProbs)`` per utterance, and ``inference_best_of`` (max_batch >= 2) samples n candidates of one utterance and
-    keeps the most likely.  Without it nothing changes."""
+    keeps the most likely.  Without it nothing changes.
+    ``align`` (vx_align, any configuration) returns the attention of the AR decoder over the text for given codes and the
+    per-token timestamps that follow from it (``Alignment``); ``inference(..., return_alignment=True)`` runs it on what it
+    generated."""
 
     MODEL_NAME = "VALL-E"  # what the EOS line prints and get_model dispatches on (models/__init__.py:98-124)
 
@@ -269,14 +347,25 @@ class VALLE:
     @torch.no_grad()
     def inference(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor, enroll_x_lens: Optional[torch.Tensor],
                   top_k: int = -100, temperature: float = 1.0, exp_noise: Optional[torch.Tensor] = None,
-                  max_new_tokens: int = -1, top_p: float = 1.0, return_logprobs: bool = False) -> torch.Tensor:
+                  max_new_tokens: int = -1, top_p: float = 1.0, return_logprobs: bool = False,
+                  return_alignment: bool = False) -> torch.Tensor:
         """Same contract as the reference (valle.py:961-985): x (1,S) int64, x_lens (1,), y (1,P,8) int64 →
         (1,T,num_quantizers) int64 on the model's device.  ``exp_noise`` / ``max_new_tokens`` / ``top_p`` are extras.
         This batch-1 path keeps its own bf16 KV cache on every model, ``kv_cache="fp8"`` included (that option only
         changes the slot caches of ``inference_batch`` / ``inference_stream``).  ``return_logprobs=True`` (models built with
-        ``logprobs=True``): returns ``(codes, GenLogProbs)``."""
+        ``logprobs=True``): returns ``(codes, GenLogProbs)``.  ``return_alignment=True``: ``align`` of the prompt plus the
+        generated codes follows the synthesis and the call returns ``(codes, Alignment)`` (with both flags ``(codes, GenLogProbs,
+        Alignment)``); the codes are those of the same call without the flag."""
         top_p = _check_top_p(top_p)
         self._check_logprobs(return_logprobs)
+        if return_alignment:
+            res = self.inference(x, x_lens, y, enroll_x_lens, top_k=top_k, temperature=temperature, exp_noise=exp_noise,
+                                 max_new_tokens=max_new_tokens, top_p=top_p, return_logprobs=return_logprobs)
+            codes = res[0] if return_logprobs else res
+            Q = self.num_quantizers
+            full = torch.cat([y[:, :, :Q].to(codes.device), codes], 1)
+            al = self.align(x, x_lens, full, y.shape[1], enroll_x_lens=enroll_x_lens)
+            return (codes, res[1], al) if return_logprobs else (codes, al)
         u = (x, x_lens, y, enroll_x_lens)
         self._check_utterance(u)
         eng = self.engine()
@@ -586,6 +675,29 @@ class VALLE:
                 parts = [eng.score(*a) for a in g]
             out += [self._score_result(a[2], a[3], p, top_k) for a, p in zip(g, parts)]
         return out
+
+    # ---- alignment -------------------------------------------------------------------------------------
+    def _align_args(self, x, x_lens, y, prompt_frames, enroll_x_lens, heads):
+        """Checks of one utterance to align, before any engine exists -> (text, codes (A, Q), P, c0, head weights or None)."""
+        text, _, codes, P = self._score_args(x, x_lens, y, prompt_frames, enroll_x_lens, 10)
+        S = int(text.numel())
+        c0 = 0 if enroll_x_lens is None else int(torch.as_tensor(enroll_x_lens).max().item())
+        if not 0 <= c0 < S:
+            raise ValueError(f"enroll_x_lens={c0}: the text window [{c0}, {S}) is empty or outside the text")
+        return text, codes, P, c0, head_weights(heads, self.cfg.num_decoder_layers, self.cfg.nhead)
+
+    @torch.no_grad()
+    def align(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor, prompt_frames: int,
+              enroll_x_lens: Optional[torch.Tensor] = None, heads=None, per_head: bool = False) -> Alignment:
+        """Engine extension: when is each text token spoken (vx_align).  x (1,S), x_lens (1,), y (1,A,Q) as for ``score``: the
+        first ``prompt_frames`` frames of y are the prompt, and the attention of the AR decoder over the text is taken, teacher-
+        forced, on the rows that predict the other T = A - prompt_frames frames.  The text window is [enroll_x_lens or 0, S): with
+        a transcribed prompt the generated frames speak only the text after it.  ``heads``: None (every head of every layer,
+        uniform), a list of (layer, head) pairs (uniform over them) or an (L, H) tensor of weights (normalised to sum 1).
+        ``per_head=True`` also returns every head's own map, to pick alignment heads on a trained checkpoint."""
+        text, codes, P, c0, hw = self._align_args(x, x_lens, y, prompt_frames, enroll_x_lens, heads)
+        attn, mass, path, score, ph = self.engine().align(text, codes, P, c0=c0, head_w=hw, per_head=per_head)
+        return make_alignment(attn, mass, path, score, ph)
 
     @torch.no_grad()
     def continual(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
