@@ -323,12 +323,26 @@ int vx_align(vx_engine* e, const int64_t* text, int32_t S, const int64_t* codes 
              int32_t c1, const float* head_w /* (L, H) host, nullable */, float* attn /* (T, c1-c0) */, float* mass /* (T) */,
              int32_t* path /* (T) */, double* path_score, float* per_head /* (L, H, T, c1-c0) */, void* stream);
 
+/* vx_align of n utterances in one pass over the concatenated rows (the rows of vx_score_batch).  text, S, codes, A, P, c0, c1, attn,
+ * mass, path, path_score: HOST arrays of n pointers / sizes with vx_align's meaning; head_w is shared by all utterances.  mass, path
+ * and path_score may be NULL, and so may any of their entries; the paths of all utterances that asked for one run side by side in
+ * one launch.  There is no per_head here: finding heads stays with vx_align.  The tap runs on the matrix pipe
+ * (attn_text_seg_kernel, bf16 operands, fp32 accumulation): the maps agree with vx_align's within the bf16 bound of DESIGN.md 4.7,
+ * not bit for bit.  An utterance's results do not depend on the others of the call, and the same call gives the same bits.  Served:
+ * the engines of vx_score_batch that are pre-norm - bf16 / fp8nar VALL-E with the MFMA row kernels (head_dim 64), no prenets - and
+ * n <= 64, on engines of any max_batch; anything else: VX_ERR_UNSUPPORTED (use vx_align per utterance).  The checks are vx_align's,
+ * per utterance, and name the utterance; all are made before any work is enqueued.  No decode state is touched; out[12] of
+ * vx_get_timings reports the call. */
+int vx_align_batch(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S, const int64_t* const* codes, const int32_t* A,
+                   const int32_t* P, const int32_t* c0, const int32_t* c1, const float* head_w /* (L, H) host, nullable */,
+                   float* const* attn, float* const* mass, int32_t* const* path, double* const* path_score, void* stream);
+
 /* Device-time of the last calls, measured with HIP events on the engine's stream:
  * out[0] prefill ms, out[1] AR decode ms, out[2] NAR ms, out[3] AR passes, out[4] graph launches, out[5] batched decode ms,
  * out[6] batched graph launches; with VX_TIME_GEMMS=1 in the environment also out[7] = ms spent in the QKV / out-projection / FFN
  * GEMM launches of the last NAR call and out[8] = their FLOPs (2 M N K each); out[9] kernel launches per pass of the batch-1 decode
  * step (nodes of its captured graph; 0 before the first vx_ar_decode and with VX_FLAG_NO_GRAPH); out[10] / out[11] ms of the AR / NAR
- * part of the last vx_score or vx_score_batch; out[12] ms of the last vx_align (row set-up, stack, taps and path). */
+ * part of the last vx_score or vx_score_batch; out[12] ms of the last vx_align or vx_align_batch (row set-up, stack, taps and path). */
 int vx_get_timings(vx_engine* e, double* out, int32_t n);
 
 /* Parity-test taps: copies an internal buffer to host memory (synchronises the engine stream).
@@ -445,6 +459,19 @@ int vx_op_attn_text_rows(int32_t prec, const void* q, int64_t ldq, const void* k
 /* The path of vx_align (mono_path_kernel) on a caller map: attn (T, Sw) fp32, path (T) int32, score (1) double, DEVICE pointers;
  * Sw <= 4096 (else VX_ERR_CAPACITY).  Synchronises `stream`. */
 int vx_op_mono_path(const float* attn, int32_t T, int32_t Sw, int32_t* path, double* score, void* stream);
+
+/* The batched tap of vx_align_batch (attn_text_seg_kernel, then the heads in head order) on caller buffers.  q / k: DEVICE bf16,
+ * row i, head h at q[i * ld + h * 64 + c] (the packed (M, 3 d) rows: k = q + d, ld = 3 d).  desc: HOST, nseg x 9 values per segment:
+ * start (first row, a multiple of 64), text_len, qfirst (index within the segment of the first tapped row), rows, row0 (audio index
+ * of that row: tapped row i sees keys [0, text_len + row0 + i + 1) of its segment), c0, c1, cell_off, row_off (where the segment's
+ * (rows, c1 - c0) cells / rows start in attn / mass).  head_w (nhead) DEVICE; attn (cells) and mass (rows_total, nullable) DEVICE
+ * fp32, stored (first != 0) or added to.  Synchronises the stream. */
+int vx_op_attn_text_segs(const void* q, const void* k, int64_t ld, int32_t nseg, const int64_t* desc, int32_t nhead, const float* head_w,
+                         float* attn, float* mass, int64_t cells, int64_t rows_total, int32_t first, void* stream);
+
+/* mono_path_seg_kernel: n maps in one launch, one workgroup each.  desc: HOST, n x 4 values per map: T, Sw, cell_off (of the map in
+ * attn), row_off (of its path in path); score: n doubles.  attn, path, score DEVICE.  Synchronises the stream. */
+int vx_op_mono_path_segs(const float* attn, int32_t n, const int64_t* desc, int32_t* path, double* score, void* stream);
 int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
                  int32_t* out_token_argmax /* [2]: sampled, argmax */, void* stream);
 /* vx_op_sample with the nucleus filter after top-k (top_p as in vx_decode_params: 0 or >= 1 off, NaN / negative VX_ERR_ARG).

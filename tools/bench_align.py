@@ -4,6 +4,12 @@ of the same utterance (out[10] of vx_get_timings: the same row pass with a final
 and the path).  Device times are HIP events on the engine's stream; each figure is the median of 20 calls after 3 warm-ups.
 
     python tools/bench_align.py [--out profiles/align_times.json]
+
+--batch N[,N...]: the batched call instead (vx_align_batch, every layer tapped, paths included): n copies of each of the two
+utterances through align_batch, next to ``align`` called n times in a loop (the sum of its n device times) and to the AR scoring
+pass of the same batch (score_batch, out[10]).  Writes profiles/align_batch_times.json.
+
+    python tools/bench_align.py --batch 1,8,32 [--out profiles/align_batch_times.json]
 """
 import json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,7 +44,34 @@ def timed(fn, read, n=20, warm=3):
     return {"device_median": med(dev), "device_min": min(dev), "device_max": max(dev), "host_wall_median": med(wall)}
 
 
-for name, S, T in (("cfg1_S47_T753", 47, 753), ("cfg4_S94_T1505", 94, 1505)):
+CASES = (("cfg1_S47_T753", 47, 753), ("cfg4_S94_T1505", 94, 1505))
+if "--batch" in sys.argv:
+    for name, S, T in CASES:
+        x, xl, y = synthetic_inputs(S, P + T, seed=1)
+        text, codes = x[0].cuda(), y[0].contiguous().cuda()
+        out[name] = {"S": S, "T": T}
+        for n in [int(v) for v in sys.argv[sys.argv.index("--batch") + 1].split(",")]:
+            texts, cs, Ps = [text] * n, [codes] * n, [P] * n
+            loop_ms = []
+
+            def loop():
+                loop_ms.append(0.0)
+                for _ in range(n):
+                    e.align(text, codes, P)
+                    loop_ms[-1] += e.align_ms()
+
+            r = {"align_loop_ms": timed(loop, lambda: loop_ms[-1]),
+                 "score_batch_ar_ms": timed(lambda: e.score_batch(texts, texts, cs, Ps, nar=False), lambda: e.score_timings()["score_ar_ms"]),
+                 "align_batch_ms": timed(lambda: e.align_batch(texts, cs, Ps), e.align_ms)}
+            r["loop_to_align_batch_ratio"] = r["align_loop_ms"]["device_median"] / r["align_batch_ms"]["device_median"]
+            r["align_batch_to_score_batch_ar_ratio"] = r["align_batch_ms"]["device_median"] / r["score_batch_ar_ms"]["device_median"]
+            out[name][f"n{n}"] = r
+            print(json.dumps({name: {f"n{n}": r}}), flush=True)
+    path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "align_batch_times.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    sys.exit(0)
+for name, S, T in CASES:
     x, xl, y = synthetic_inputs(S, P + T, seed=1)
     text, codes = x[0].cuda(), y[0].contiguous().cuda()
     r = {"S": S, "T": T}

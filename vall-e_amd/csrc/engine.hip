@@ -171,6 +171,12 @@ struct vx_engine {
   double* al_score = nullptr;
   unsigned char* al_bp = nullptr;
   size_t al_cells = 0, al_rows = 0, al_ph_cells = 0;
+  // ... of vx_align_batch besides: every head's own cells and row masses (align_seg_scratch), the descriptors of the tap and of
+  // the path launch (2 BMAX), one path score per utterance (BMAX)
+  float* al_scr = nullptr;
+  AlignSeg* al_segs = nullptr;
+  double* al_bscore = nullptr;
+  size_t al_scr_floats = 0;
   double t_align = 0;
   // batched decode (slots)
   int bmax = 0;
@@ -1095,11 +1101,17 @@ struct TextMem {
 // The attention tap of run_stack (vx_align): `rows` rows of the pass from row `row` of e->X on, row i being audio position
 // row0 + i, accumulate the head-weighted attention they pay to the text columns [c0, c1) of `text_len` text tokens
 // (attn_text_rows_kernel, align.hpp).  w: the (L, H) weights on the device, hw: the same on the host - a layer whose weights are
-// all zero is not launched unless per_head, (L, H, rows, c1 - c0), is wanted.  Unsegmented AR passes only.
+// all zero is not launched unless per_head, (L, H, rows, c1 - c0), is wanted.  On a segmented AR pass (vx_align_batch) the rows,
+// windows and output offsets are per segment: segs, nseg descriptors on the device (align.hpp), max_rows the largest T_z, attn /
+// mass the packed outputs of `cells` cells / `rows_total` rows, scr the per-head scratch; no per_head there.
 struct AttnTap {
   const float *w = nullptr, *hw = nullptr;
   int row = 0, rows = 0, row0 = 0, text_len = 0, c0 = 0, c1 = 0;
   float *attn = nullptr, *mass = nullptr, *per_head = nullptr;
+  const AlignSeg* segs = nullptr;
+  int nseg = 0, max_rows = 0;
+  long long cells = 0, rows_total = 0;
+  float* scr = nullptr;
 };
 static int tap_layer(vx_engine* e, const AttnTap& t, int li, int H, int hd, const void* q, long long ldq, const void* k, long long ldk,
                      long long k_head_stride, int causal, bool& first) {
@@ -1110,6 +1122,16 @@ static int tap_layer(vx_engine* e, const AttnTap& t, int li, int H, int hd, cons
   if (launch_attn_text_rows(e->bf16, q, ldq, k, ldk, k_head_stride, t.rows, t.row0, H, hd, t.text_len, causal, t.c0, t.c1, t.w + li * H,
                             t.attn, t.mass, ph, first ? 1 : 0, e->es))
     return fail(VX_ERR_UNSUPPORTED, "attention tap: head_dim %d", hd);
+  first = false;
+  return VX_OK;
+}
+// The tap of one layer of a segmented pass: attn_text_seg_kernel over every segment, then the heads in head order.
+static int tap_layer_segs(vx_engine* e, const AttnTap& t, int li, int H, int d, bool& first) {
+  bool any = false;
+  for (int h = 0; h < H && !any; ++h) any = t.hw[li * H + h] != 0.f;
+  if (!any) return VX_OK;
+  launch_attn_text_segs(e->QKV, (const char*)e->QKV + d * e->esz, 3 * d, t.segs, t.nseg, t.max_rows, H, t.w + li * H, t.scr, t.cells,
+                        t.rows_total, t.attn, t.mass, first ? 1 : 0, e->es);
   first = false;
   return VX_OK;
 }
@@ -1141,7 +1163,9 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
                      const RowSegs& segs, KvDst kv, TextMem mem = TextMem(), const AttnTap* tap = nullptr) {
   const bool post = e->cfg.flags & VX_FLAG_POST_NORM, cross = mem.kv != nullptr;
   if (cross && segs.n > 0 && mem.off == nullptr) return fail(VX_ERR_UNSUPPORTED, "cross-attention over segmented rows");
-  if (tap && (segs.n > 0 || ada_stage >= 0)) return fail(VX_ERR_UNSUPPORTED, "attention tap on a segmented or NAR pass");
+  if (tap && ada_stage >= 0) return fail(VX_ERR_UNSUPPORTED, "attention tap on a NAR pass");
+  if (tap && segs.n > 0 && (cross || tap->segs == nullptr || !use_mfma(e)))
+    return fail(VX_ERR_UNSUPPORTED, "attention tap on a segmented pass: bf16 self-attention rows of head_dim 64 with per-segment descriptors only");
   bool tap_first = true;  // the first tapped layer stores, the others add
   const int hd = d / H;
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
@@ -1195,7 +1219,9 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
       VXC(gemm_rows(e, e->Hn, l.in_w, l.in_b, e->QKV, M, 3 * d, d, GE_BIAS, false, use_mfma(e)));
     }
     if (tg) gemm_mark(e, 2.0 * M * 3 * d * d);
-    if (tap && !cross)  // VALL-E: the text columns of the self-attention of the tapped rows, from the packed q / k rows
+    if (tap && segs.n > 0)  // ... of every segment's tapped rows, on the matrix pipe
+      VXC(tap_layer_segs(e, *tap, li, H, d, tap_first));
+    else if (tap && !cross)  // VALL-E: the text columns of the self-attention of the tapped rows, from the packed q / k rows
       VXC(tap_layer(e, *tap, li, H, hd, (const char*)e->QKV + (size_t)tap->row * 3 * d * e->esz, 3 * d, (const char*)e->QKV + d * e->esz,
                     3 * d, hd, 1, tap_first));
     const size_t kvl = (size_t)2 * H * e->ctx_max * 64;  // elements per layer of a slot cache
@@ -2803,8 +2829,9 @@ extern "C" int vx_score_batch(vx_engine* e, int32_t n, const int64_t* const* tex
 // (score_rows_setup + run_stack with an attention tap; no final norm, no predict layer), and the best monotonic path through it.
 // Like scoring it writes nothing the decode paths keep.
 
-// Scratch of vx_align for a (T, Sw) map, nw head weights and, when staged, ph_cells per-head cells.
-static int align_reserve(vx_engine* e, size_t T, size_t Sw, size_t nw, size_t ph_cells) {
+// Scratch of vx_align / vx_align_batch for maps of `cells` cells and T rows in all, nw head weights and, when staged, ph_cells
+// per-head cells; scr_floats: the per-head scratch of the batched tap (0: none).
+static int align_reserve(vx_engine* e, size_t cells, size_t T, size_t nw, size_t ph_cells, size_t scr_floats = 0) {
   auto regrow = [&](void** p, size_t bytes) -> int {
     for (auto& q : e->allocs) if (*p && q == *p) { (void)hipFree(q); q = nullptr; }
     HIPC(hipMalloc(p, bytes));
@@ -2813,11 +2840,19 @@ static int align_reserve(vx_engine* e, size_t T, size_t Sw, size_t nw, size_t ph
     return VX_OK;
   };
   if (e->al_w == nullptr) { VXC(regrow((void**)&e->al_w, nw * 4)); VXC(regrow((void**)&e->al_score, 8)); }
-  if (T * Sw > e->al_cells || T > e->al_rows || ph_cells > e->al_ph_cells) HIPC(hipStreamSynchronize(e->es));
-  if (T * Sw > e->al_cells) {
-    VXC(regrow((void**)&e->al_attn, T * Sw * 4));
-    VXC(regrow((void**)&e->al_bp, T * Sw));
-    e->al_cells = T * Sw;
+  if (scr_floats && e->al_segs == nullptr) {
+    VXC(regrow((void**)&e->al_segs, (size_t)2 * BMAX * sizeof(AlignSeg)));
+    VXC(regrow((void**)&e->al_bscore, (size_t)BMAX * 8));
+  }
+  if (cells > e->al_cells || T > e->al_rows || ph_cells > e->al_ph_cells || scr_floats > e->al_scr_floats) HIPC(hipStreamSynchronize(e->es));
+  if (cells > e->al_cells) {
+    VXC(regrow((void**)&e->al_attn, cells * 4));
+    VXC(regrow((void**)&e->al_bp, cells));
+    e->al_cells = cells;
+  }
+  if (scr_floats > e->al_scr_floats) {
+    VXC(regrow((void**)&e->al_scr, scr_floats * 4));
+    e->al_scr_floats = scr_floats;
   }
   if (T > e->al_rows) {
     VXC(regrow((void**)&e->al_mass, T * 4));
@@ -2864,7 +2899,7 @@ extern "C" int vx_align(vx_engine* e, const int64_t* text, int32_t S, const int6
   VXC(score_rows_setup(e, 1, false, &text, &S, &codes, &A, &P, sr));
   const size_t ph_cells = (size_t)L * H * T * Sw;
   const bool ph_staged = per_head && host_readable(per_head);
-  VXC(align_reserve(e, T, Sw, (size_t)L * H, ph_staged ? ph_cells : 0));
+  VXC(align_reserve(e, (size_t)T * Sw, T, (size_t)L * H, ph_staged ? ph_cells : 0));
   HIPC(hipMemcpyAsync(e->al_w, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, e->es));
   AttnTap tap;
   tap.w = e->al_w; tap.hw = hw.data();
@@ -2880,6 +2915,74 @@ extern "C" int vx_align(vx_engine* e, const int64_t* text, int32_t S, const int6
   if (path_score) HIPC(hipMemcpyAsync(path_score, e->al_score, 8, hipMemcpyDefault, e->es));
   if (ph_staged) HIPC(hipMemcpyAsync(per_head, e->al_ph, ph_cells * 4, hipMemcpyDefault, e->es));
   HIPC(hipStreamSynchronize(e->es));  // the host arrays above and the staging are free again
+  float ms = 0.f;
+  HIPC(hipEventElapsedTime(&ms, e->ev_t[0], e->ev_t[1]));
+  e->t_align = ms;
+  return sync_out(e, stream);
+}
+
+// vx_align of n utterances in one segmented row pass (the rows of vx_score_batch): the tap runs on the matrix pipe over every
+// utterance's rows at once (attn_text_seg_kernel), then one path launch over the utterances that asked for a path.
+extern "C" int vx_align_batch(vx_engine* e, int32_t n, const int64_t* const* text, const int32_t* S, const int64_t* const* codes,
+                              const int32_t* A, const int32_t* P, const int32_t* c0, const int32_t* c1, const float* head_w,
+                              float* const* attn, float* const* mass, int32_t* const* path, double* const* path_score, void* stream) {
+  if (!e) return fail(VX_ERR_ARG, "null argument");
+  if (!e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+  const vx_config& c = e->cfg;
+  if (e->vallf) return fail(VX_ERR_UNSUPPORTED, "vx_align_batch: VALL-F aligns per utterance (vx_align)");
+  if (c.flags & (VX_FLAG_PRENET | VX_FLAG_POST_NORM)) return fail(VX_ERR_UNSUPPORTED, "vx_align_batch: prenet and post-norm models align per utterance (vx_align)");
+  if (!e->bf16 || !use_mfma(e)) return fail(VX_ERR_UNSUPPORTED, "vx_align_batch needs the bf16 MFMA row kernels (head_dim 64); use vx_align");
+  if (!text || !S || !codes || !A || !P || !c0 || !c1 || !attn) return fail(VX_ERR_ARG, "null argument");
+  if (n < 1 || n > BMAX) return fail(VX_ERR_ARG, "n must be 1..%d", BMAX);
+  const int L = c.num_layers, H = c.nhead, d = c.d_model, bos = c.prepend_bos ? 1 : 0;
+  std::vector<float> hw;
+  VXC(align_weights(head_w, L * H, hw));
+  std::vector<AlignSeg> sg(n), psg;
+  std::vector<int> pidx;  // the utterances that asked for a path
+  long long cells = 0, rows = 0;
+  int max_rows = 0, max_sw = 0;
+  for (int b = 0; b < n; ++b) {
+    if (!attn[b]) return fail(VX_ERR_ARG, "null output (utterance %d)", b);
+    if (!(0 <= c0[b] && c0[b] < c1[b] && c1[b] <= S[b]))
+      return fail(VX_ERR_ARG, "text window [%d, %d) outside [0, S=%d) (utterance %d)", c0[b], c1[b], S[b], b);
+    VXC(check_score_utterance(e, text[b], S[b], nullptr, 0, codes[b], A[b], P[b], true, false, b));
+    const int T = A[b] - P[b], Sw = c1[b] - c0[b], first = bos ? P[b] : P[b] - 1;
+    const bool want_path = (path && path[b]) || (path_score && path_score[b]);
+    if (want_path && Sw > ALIGN_MAX_SW)
+      return fail(VX_ERR_CAPACITY, "a path over %d text tokens (at most %d) (utterance %d)", Sw, ALIGN_MAX_SW, b);
+    sg[b] = AlignSeg{0, S[b], S[b] + first, T, first, c0[b], c1[b], 0, cells, rows};
+    if (want_path) { psg.push_back(sg[b]); pidx.push_back(b); max_sw = std::max(max_sw, Sw); }
+    cells += (long long)T * Sw; rows += T;
+    max_rows = std::max(max_rows, T);
+  }
+  ON_DEVICE(c.device);
+  VXC(sync_in(e, stream));
+  HIPC(hipEventRecord(e->ev_t[0], e->es));
+  ScoreRows sr;
+  VXC(score_rows_setup(e, n, true, text, S, codes, A, P, sr));
+  for (int b = 0; b < n; ++b) sg[b].start = sr.start[b];
+  for (size_t z = 0; z < psg.size(); ++z) psg[z].start = sr.start[pidx[z]];
+  VXC(align_reserve(e, cells, rows, (size_t)L * H, 0, align_seg_scratch(H, cells, rows)));
+  HIPC(hipMemcpyAsync(e->al_w, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, e->es));
+  HIPC(hipMemcpyAsync(e->al_segs, sg.data(), (size_t)n * sizeof(AlignSeg), hipMemcpyHostToDevice, e->es));
+  if (!psg.empty()) HIPC(hipMemcpyAsync(e->al_segs + BMAX, psg.data(), psg.size() * sizeof(AlignSeg), hipMemcpyHostToDevice, e->es));
+  AttnTap tap;
+  tap.w = e->al_w; tap.hw = hw.data();
+  tap.segs = e->al_segs; tap.nseg = n; tap.max_rows = max_rows; tap.cells = cells; tap.rows_total = rows; tap.scr = e->al_scr;
+  tap.attn = e->al_attn; tap.mass = e->al_mass;
+  VXC(run_stack(e, e->ar_l, sr.start[n], d, H, 0, -1, sr.segs, KvDst(), TextMem(), &tap));
+  if (!psg.empty()) launch_mono_path_segs(e->al_attn, e->al_segs + BMAX, (int)psg.size(), max_sw, e->al_bp, e->al_path, e->al_bscore, e->es);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(e->ev_t[1], e->es));
+  for (int b = 0; b < n; ++b) {
+    const size_t T = sg[b].rows, Sw = sg[b].c1 - sg[b].c0;
+    HIPC(hipMemcpyAsync(attn[b], e->al_attn + sg[b].cell_off, T * Sw * 4, hipMemcpyDefault, e->es));
+    if (mass && mass[b]) HIPC(hipMemcpyAsync(mass[b], e->al_mass + sg[b].row_off, T * 4, hipMemcpyDefault, e->es));
+    if (path && path[b]) HIPC(hipMemcpyAsync(path[b], e->al_path + sg[b].row_off, T * 4, hipMemcpyDefault, e->es));
+  }
+  for (size_t z = 0; z < pidx.size(); ++z)
+    if (path_score && path_score[pidx[z]]) HIPC(hipMemcpyAsync(path_score[pidx[z]], e->al_bscore + z, 8, hipMemcpyDefault, e->es));
+  HIPC(hipStreamSynchronize(e->es));  // the host arrays above are free again
   float ms = 0.f;
   HIPC(hipEventElapsedTime(&ms, e->ev_t[0], e->ev_t[1]));
   e->t_align = ms;
@@ -3115,6 +3218,87 @@ extern "C" int vx_op_mono_path(const float* attn, int32_t T, int32_t Sw, int32_t
   HIPC(hipMalloc((void**)&bp, (size_t)T * Sw));
   launch_mono_path(attn, T, Sw, bp, path, score, (hipStream_t)stream);
   const hipError_t err = hipGetLastError(), err2 = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(bp);
+  HIPC(err);
+  HIPC(err2);
+  return VX_OK;
+}
+
+// The kernels of the batched tap on caller (device) buffers.  desc: n x 9 host values per segment (start, text_len, qfirst, rows,
+// row0, c0, c1, cell_off, row_off), see AlignSeg; cells / rows_total: the extents of attn / mass.  The per-head scratch is
+// allocated here, filled with NaN first.
+static int op_align_segs(const int64_t* desc, int32_t n, int nf, std::vector<AlignSeg>& sg) {
+  sg.resize(n);
+  for (int z = 0; z < n; ++z) {
+    const int64_t* v = desc + (size_t)z * nf;
+    sg[z] = nf == 9 ? AlignSeg{(int)v[0], (int)v[1], (int)v[2], (int)v[3], (int)v[4], (int)v[5], (int)v[6], 0, v[7], v[8]}
+                    : AlignSeg{0, 0, 0, (int)v[0], 0, 0, (int)v[1], 0, v[2], v[3]};
+  }
+  return VX_OK;
+}
+
+extern "C" int vx_op_attn_text_segs(const void* q, const void* k, int64_t ld, int32_t nseg, const int64_t* desc, int32_t nhead,
+                                    const float* head_w, float* attn, float* mass, int64_t cells, int64_t rows_total, int32_t first,
+                                    void* stream) {
+  if (!q || !k || !desc || !head_w || !attn) return fail(VX_ERR_ARG, "null argument");
+  if (nseg < 1 || nhead < 1 || cells < 1 || rows_total < 1) return fail(VX_ERR_ARG, "nseg, nhead, cells and rows_total must be >= 1");
+  std::vector<AlignSeg> sg;
+  VXC(op_align_segs(desc, nseg, 9, sg));
+  int max_rows = 0;
+  for (int z = 0; z < nseg; ++z) {
+    const AlignSeg& g = sg[z];
+    if (g.start < 0 || g.start % 64 || g.text_len < 1 || g.qfirst < 0 || g.rows < 1 || g.row0 < 0)
+      return fail(VX_ERR_ARG, "segment %d: start must be a multiple of 64, text_len and rows >= 1, qfirst and row0 >= 0", z);
+    if (!(0 <= g.c0 && g.c0 < g.c1 && g.c1 <= g.text_len)) return fail(VX_ERR_ARG, "segment %d: text window [%d, %d) outside [0, %d)", z, g.c0, g.c1, g.text_len);
+    if (g.cell_off < 0 || g.cell_off + (long long)g.rows * (g.c1 - g.c0) > cells || g.row_off < 0 || g.row_off + g.rows > rows_total)
+      return fail(VX_ERR_ARG, "segment %d: its cells or rows lie outside the outputs", z);
+    max_rows = std::max(max_rows, g.rows);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t scr_bytes = align_seg_scratch(nhead, cells, rows_total) * 4;
+  void *d_sg = nullptr, *scr = nullptr;
+  HIPC(hipMalloc(&d_sg, sg.size() * sizeof(AlignSeg)));
+  hipError_t err = hipMalloc(&scr, scr_bytes);
+  if (err == hipSuccess) err = hipMemcpyAsync(d_sg, sg.data(), sg.size() * sizeof(AlignSeg), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess) err = hipMemsetAsync(scr, 0xFF, scr_bytes, s);
+  if (err == hipSuccess) {
+    launch_attn_text_segs(q, k, ld, (const AlignSeg*)d_sg, nseg, max_rows, nhead, head_w, (float*)scr, cells, rows_total, attn, mass,
+                          first ? 1 : 0, s);
+    err = hipGetLastError();
+  }
+  const hipError_t err2 = hipStreamSynchronize(s);
+  (void)hipFree(d_sg);
+  (void)hipFree(scr);
+  HIPC(err);
+  HIPC(err2);
+  return VX_OK;
+}
+
+// desc: n x 4 host values per map (T, Sw, cell_off, row_off); path: the packed rows; score: n values.
+extern "C" int vx_op_mono_path_segs(const float* attn, int32_t n, const int64_t* desc, int32_t* path, double* score, void* stream) {
+  if (!attn || !desc || !path || !score) return fail(VX_ERR_ARG, "null argument");
+  if (n < 1) return fail(VX_ERR_ARG, "n must be >= 1");
+  std::vector<AlignSeg> sg;
+  VXC(op_align_segs(desc, n, 4, sg));
+  int max_sw = 0;
+  long long cells = 0;
+  for (int z = 0; z < n; ++z) {
+    if (sg[z].rows < 1 || sg[z].c1 < 1 || sg[z].cell_off < 0 || sg[z].row_off < 0) return fail(VX_ERR_ARG, "map %d: T and Sw must be >= 1, offsets >= 0", z);
+    if (sg[z].c1 > ALIGN_MAX_SW) return fail(VX_ERR_CAPACITY, "a path over %d text tokens (at most %d)", sg[z].c1, ALIGN_MAX_SW);
+    max_sw = std::max(max_sw, sg[z].c1);
+    cells = std::max(cells, sg[z].cell_off + (long long)sg[z].rows * sg[z].c1);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  void *d_sg = nullptr, *bp = nullptr;
+  HIPC(hipMalloc(&d_sg, sg.size() * sizeof(AlignSeg)));
+  hipError_t err = hipMalloc(&bp, (size_t)cells);
+  if (err == hipSuccess) err = hipMemcpyAsync(d_sg, sg.data(), sg.size() * sizeof(AlignSeg), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess) {
+    launch_mono_path_segs(attn, (const AlignSeg*)d_sg, n, max_sw, (unsigned char*)bp, path, score, s);
+    err = hipGetLastError();
+  }
+  const hipError_t err2 = hipStreamSynchronize(s);
+  (void)hipFree(d_sg);
   (void)hipFree(bp);
   HIPC(err);
   HIPC(err2);

@@ -89,6 +89,7 @@ _SIGS = {
     "vx_score_batch": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 11 + [C.c_void_p]),
     "vx_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
                  + [C.c_void_p] * 6 + [C.c_void_p]),
+    "vx_align_batch": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 12 + [C.c_void_p]),
     "vx_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
     "vx_read_buffer": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int64]),
     "vx_buffer_bytes": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
@@ -115,6 +116,9 @@ _SIGS = {
     "vx_op_attn_text_rows": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64] + [C.c_int32] * 8
                              + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
     "vx_op_mono_path": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vx_op_attn_text_segs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int32] + [C.c_void_p] * 3
+                             + [C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "vx_op_mono_path_segs": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vx_op_sample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "vx_op_sample_topp": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
                                     C.c_void_p]),
@@ -549,8 +553,40 @@ class Engine:
                                  _ptr(psc), _ptr(ph), stream))
         return attn, mass, pth, psc, ph
 
+    def align_batch(self, texts, codes, prompt_frames, c0=None, head_w: Optional[torch.Tensor] = None, path: bool = True, stream=None):
+        """``align`` of n utterances in one pass over the concatenated rows (vx_align_batch): lists of per-utterance tensors,
+        prompt lengths and window starts (``c0``, default 0; the windows end at the end of each text); ``head_w`` is shared.
+        Returns a list of per-utterance (attn, mass, path or None, path_score or None) device tensors.  VxError code 5 on an engine
+        vx_align_batch does not serve."""
+        n, Q = len(texts), self.cfg.num_quantizers
+        texts = [t.to(torch.int64).contiguous() for t in texts]
+        codes = [c.to(torch.int64).contiguous() for c in codes]
+        assert all(c.dim() == 2 and c.shape[1] == Q for c in codes), (Q, [tuple(c.shape) for c in codes])
+        P = [int(p) for p in prompt_frames]
+        A = [c.shape[0] for c in codes]
+        S = [t.numel() for t in texts]
+        c0 = [0] * n if c0 is None else [int(v) for v in c0]
+        L, H = self.cfg.num_decoder_layers, self.cfg.nhead
+        hw = None
+        if head_w is not None:
+            hw = torch.as_tensor(head_w).detach().to("cpu", torch.float32).contiguous()
+            assert tuple(hw.shape) == (L, H), (tuple(hw.shape), (L, H))
+        dev = torch.device("cuda", self.device)
+        T = [max(a - p, 0) for a, p in zip(A, P)]
+        Sw = [max(s - c, 0) for s, c in zip(S, c0)]
+        attn = [torch.empty((t, w), dtype=torch.float32, device=dev) for t, w in zip(T, Sw)]
+        mass = [torch.empty(t, dtype=torch.float32, device=dev) for t in T]
+        pth = [torch.empty(t, dtype=torch.int32, device=dev) for t in T] if path else None
+        psc = [torch.empty(1, dtype=torch.float64, device=dev) for _ in T] if path else None
+        ptrs = lambda ts: None if ts is None else (C.c_void_p * n)(*[_ptr(t) for t in ts])
+        ints = lambda vs: (C.c_int32 * n)(*vs)
+        _check(self.lib.vx_align_batch(self.h, n, ptrs(texts), ints(S), ptrs(codes), ints(A), ints(P), ints(c0), ints(S), _ptr(hw),
+                                       ptrs(attn), ptrs(mass), ptrs(pth), ptrs(psc), stream))
+        none = [None] * n
+        return list(zip(attn, mass, pth or none, psc or none))
+
     def align_ms(self) -> float:
-        """Device ms of the last ``align``."""
+        """Device ms of the last ``align`` / ``align_batch``."""
         buf = (C.c_double * 13)()
         _check(self.lib.vx_get_timings(self.h, buf, 13))
         return buf[12]
@@ -839,6 +875,47 @@ def op_mono_path(attn):
     score = torch.empty(1, dtype=torch.float64, device=attn.device)
     _check(lib.vx_op_mono_path(_ptr(attn), T, Sw, _ptr(path), _ptr(score), current_stream_ptr(attn.device)))
     return path, score
+
+
+def op_attn_text_segs(qkv, nhead, segs, head_w, attn, mass=None, first=True):
+    """attn_text_seg_kernel + the head pass on device buffers (vx_op_attn_text_segs): qkv (M, 3 d) bf16 packed rows, d = 64 nhead;
+    ``segs``: one (start, text_len, qfirst, rows, row0, c0, c1, cell_off, row_off) per segment (AlignSeg, csrc/align.hpp); ``attn``
+    (cells,) and ``mass`` (rows_total,) fp32, flat, are updated in place (``first``: stored).  The operands' extents are checked here:
+    the kernel trusts them."""
+    lib = load_library()
+    d = 64 * nhead
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.is_contiguous() and qkv.is_cuda and qkv.shape[1] == 3 * d
+    assert head_w.dtype == torch.float32 and head_w.numel() == nhead and head_w.is_cuda
+    assert attn.dtype == torch.float32 and attn.dim() == 1 and attn.is_contiguous() and attn.is_cuda
+    assert mass is None or (mass.dtype == torch.float32 and mass.dim() == 1 and mass.is_contiguous() and mass.is_cuda)
+    segs = [tuple(int(v) for v in g) for g in segs]
+    for start, text_len, qfirst, rows, row0, c0, c1, cell_off, row_off in segs:
+        assert start % 64 == 0 and start + qfirst + rows <= qkv.shape[0] and start + text_len + row0 + rows <= qkv.shape[0], "rows outside qkv"
+        assert 0 <= cell_off and cell_off + rows * (c1 - c0) <= attn.numel() and 0 <= row_off
+        assert mass is None or row_off + rows <= mass.numel()
+    rows_total = mass.numel() if mass is not None else max(g[8] + g[3] for g in segs)
+    flat = [v for g in segs for v in g]
+    k = qkv.view(-1)[d:]
+    _check(lib.vx_op_attn_text_segs(_ptr(qkv), _ptr(k), 3 * d, len(segs), (C.c_int64 * len(flat))(*flat), nhead, _ptr(head_w), _ptr(attn),
+                                    _ptr(mass), attn.numel(), rows_total, int(bool(first)), current_stream_ptr(qkv.device)))
+    return attn
+
+
+def op_mono_path_segs(attn, maps):
+    """mono_path_seg_kernel on a flat device buffer of maps (vx_op_mono_path_segs): ``maps`` = one (T, Sw, cell_off) per map ->
+    (paths, a list of (T,) int32 views; scores (n,) float64), on the device."""
+    lib = load_library()
+    assert attn.dtype == torch.float32 and attn.dim() == 1 and attn.is_contiguous() and attn.is_cuda
+    flat, row_off = [], 0
+    for T, Sw, cell_off in maps:
+        assert 0 <= cell_off and cell_off + T * Sw <= attn.numel()
+        flat += [int(T), int(Sw), int(cell_off), row_off]
+        row_off += int(T)
+    path = torch.empty(row_off, dtype=torch.int32, device=attn.device)
+    score = torch.empty(len(maps), dtype=torch.float64, device=attn.device)
+    _check(lib.vx_op_mono_path_segs(_ptr(attn), len(maps), (C.c_int64 * len(flat))(*flat), _ptr(path), _ptr(score),
+                                    current_stream_ptr(attn.device)))
+    return list(torch.split(path, [int(m[0]) for m in maps])), score
 
 
 def op_sample(logits, top_k, temperature, exp_noise):

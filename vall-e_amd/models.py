@@ -113,12 +113,16 @@ class GenLogProbs:
 class BestOf:
     """What ``inference_best_of`` reports next to the winner's codes: the winner's ``index`` among the n candidates, their
     ``seeds``, ``ar_mean`` (n floats, GenLogProbs.ar_mean) and ``tokens`` (the n codebook-0 sequences), and the winner's
-    ``logprobs``."""
+    ``logprobs``.  ``rank_key``: the n values the candidates were ranked by (``ar_mean`` itself under ``rank_by="logprob"``);
+    ``alignments``: the n candidates' ``Alignment`` (None for a candidate that emitted nothing) when the ranking asked for them,
+    else None."""
     index: int
     seeds: List[int]
     ar_mean: List[float]
     tokens: List[torch.Tensor]
     logprobs: Optional[GenLogProbs] = None
+    alignments: Optional[list] = None
+    rank_key: Optional[List[float]] = None
 
 
 def best_of_index(ar_mean) -> int:
@@ -128,6 +132,27 @@ def best_of_index(ar_mean) -> int:
     if not vals:
         raise ValueError("no candidates")
     return max(range(len(vals)), key=lambda i: (vals[i], -i))
+
+
+def alignment_rank_key(alignment, genlogprobs=None) -> float:
+    """Best-of-N's key under ``rank_by="alignment"``: the score of the best monotonic path per scored frame, path_score / T; -inf
+    for a candidate without a path (T < Sw) or without output (``alignment`` None)."""
+    if alignment is None or alignment.path is None:
+        return float("-inf")
+    T = int(alignment.attn.shape[0])
+    return float(alignment.path_score) / T if T > 0 else float("-inf")
+
+
+def best_of_rank(keys, ar_mean) -> int:
+    """Best-of-N's choice by a key other than the log-probability: the highest key; a key of -inf or NaN ranks last; ties go to
+    the higher ``ar_mean``, then to the lower index.  When no candidate has a finite-or-+inf key the order is ``best_of_index``'s."""
+    ks = [float("-inf") if k != k else float(k) for k in keys]
+    if len(ks) != len(ar_mean):
+        raise ValueError(f"{len(ks)} keys for {len(ar_mean)} candidates")
+    if all(k == float("-inf") for k in ks):
+        return best_of_index(ar_mean)
+    ms = [float("-inf") if v != v else float(v) for v in ar_mean]
+    return max(range(len(ks)), key=lambda i: (ks[i], ms[i], -i))
 
 
 FRAME_RATE = 75.0  # codec frames per second (EnCodec at 24 kHz, hop 320)
@@ -402,11 +427,15 @@ class VALLE:
 
     @torch.no_grad()
     def inference_batch(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, batched_nar: bool = True,
-                        batched_prefill: bool = True, top_p: float = 1.0, return_logprobs: bool = False):
+                        batched_prefill: bool = True, top_p: float = 1.0, return_logprobs: bool = False,
+                        return_alignment: bool = False):
         """Engine extension (BASELINE configs[2]): ``utterances`` = list of (x, x_lens, y[, enroll_x_lens]) as for
         ``inference``; up to ``max_batch`` of them advance together, one shared weight stream per AR step, each with
         its own KV cache / sampler / stop rule; the NAR stages then run per utterance.  Returns a list of (1,T_i,Q), with
-        ``return_logprobs=True`` (models built with ``logprobs=True``) a list of ((1,T_i,Q), GenLogProbs)."""
+        ``return_logprobs=True`` (models built with ``logprobs=True``) a list of ((1,T_i,Q), GenLogProbs).
+        ``return_alignment=True``: after a group's NAR stages one ``align_batch`` runs over the prompt plus the generated codes of
+        the group, and every entry gains its ``Alignment`` (None for an empty output), placed as ``inference`` places it; the
+        codes are those of the same call without the flag."""
         top_p = _check_top_p(top_p)
         self._check_logprobs(return_logprobs)
         eng = self._batch_engine("inference_batch")
@@ -430,9 +459,23 @@ class VALLE:
                     todo.append((g0 + b,) + r)
             for i, r in self._run_nar(eng, todo, batched_nar, glp if return_logprobs else None):
                 out[i] = r
-            if return_logprobs:
-                for i in glp:
-                    out[i] = (out[i], glp[i])
+            als = self._align_generated(group, out[g0 : g0 + len(group)]) if return_alignment else None
+            for b in range(len(group)):
+                i = g0 + b
+                if return_logprobs or return_alignment:
+                    out[i] = (out[i],) + ((glp[i],) if return_logprobs else ()) + ((als[b],) if return_alignment else ())
+        return out
+
+    def _align_generated(self, group, codes):
+        """One ``align_batch`` over prompt + generated codes of a group: ``codes[b]`` (1, T_b, Q) belongs to ``group[b]``; an
+        utterance with an empty output gets None."""
+        Q = self.num_quantizers
+        idx = [b for b, c in enumerate(codes) if c.shape[1] > 0]
+        full = [(group[b][0], group[b][1], torch.cat([group[b][2][:, :, :Q].to(codes[b].device), codes[b]], 1),
+                 group[b][3] if len(group[b]) > 3 else None) for b in idx]
+        out = [None] * len(codes)
+        for b, al in zip(idx, self.align_batch(full, [int(group[b][2].shape[1]) for b in idx])):
+            out[b] = al
         return out
 
     def _ar_group(self, eng, group, seeds, top_k, temperature, top_p, batched_prefill):
@@ -451,13 +494,23 @@ class VALLE:
 
     @torch.no_grad()
     def inference_best_of(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor, enroll_x_lens: Optional[torch.Tensor],
-                          n: int, top_k: int = -100, temperature: float = 1.0, top_p: float = 1.0, seeds=None):
+                          n: int, top_k: int = -100, temperature: float = 1.0, top_p: float = 1.0, seeds=None, rank_by="logprob"):
         """Engine extension: best-of-N synthesis.  The utterance (arguments as for ``inference``) is sampled ``n`` times with
         ``n`` different seeds (``seeds``, or drawn as ``inference_batch`` draws them) in the slots of the batched decode, in
         groups of max_batch; the candidates are ranked by their mean AR log-probability (GenLogProbs.ar_mean, which the decode
         itself recorded: no scoring pass), highest first, ties to the lower index, and the NAR stages run for the winner only.
         Returns ``(codes (1,T,Q), BestOf)``; the codes are what ``inference_batch`` returns for the utterance with the winner's
-        seed.  Needs a model built with ``logprobs=True`` (ValueError) and ``max_batch >= 2`` (NotImplementedError)."""
+        seed.  Needs a model built with ``logprobs=True`` (ValueError) and ``max_batch >= 2`` (NotImplementedError).
+        ``rank_by="alignment"``: the candidates' prompt + AR tokens are aligned in one ``align_batch`` before any NAR stage (the
+        AR pass reads codebook 0 only; the other codebooks of the generated frames are zeros) and ranked by ``alignment_rank_key``,
+        the best path's score per frame: a candidate without a path or without output ranks last, ties go to the higher
+        ``ar_mean``, then the lower index, and when no candidate has a path the order is the log-probability's.  A callable
+        ``rank_by(alignment, genlogprobs) -> float`` (higher is better; ``alignment`` is None for an empty output) takes the place
+        of that key under the same rules.  ``BestOf.alignments`` and ``BestOf.rank_key`` report both.  Which key picks the better
+        audio on a trained checkpoint is NOT validated here: the weights this project tests with are synthetic, so the mechanics
+        are tested, not the quality."""
+        if not (rank_by in ("logprob", "alignment") or callable(rank_by)):
+            raise ValueError(f"rank_by must be 'logprob', 'alignment' or a callable (got {rank_by!r})")
         top_p = _check_top_p(top_p)
         self._check_logprobs(True, "inference_best_of")
         if self.engine_opts["max_batch"] < 2:
@@ -481,12 +534,27 @@ class VALLE:
                 tokens, reason = eng.batch_result(b)
                 cands.append((tokens, GenLogProbs(lp_ar, None, tokens.numel(), reason)))
         means = [c[1].ar_mean for c in cands]
-        w = best_of_index(means)
+        als, keys = None, means
+        if rank_by == "logprob":
+            w = best_of_index(means)
+        else:
+            Q = self.num_quantizers
+            gen = []  # prompt + AR tokens of every candidate that emitted something
+            for tk, _ in cands:
+                if tk.numel():
+                    rows_ = torch.zeros((1, tk.numel(), Q), dtype=torch.int64, device=y.device)
+                    rows_[0, :, 0] = tk.to(y.device)
+                    gen.append((x, x_lens, torch.cat([y[:, :, :Q], rows_], 1), enroll_x_lens))
+            done = iter(self.align_batch(gen, int(y.shape[1])))
+            als = [next(done) if c[0].numel() else None for c in cands]
+            key = alignment_rank_key if rank_by == "alignment" else rank_by
+            keys = [float(key(a, c[1])) for a, c in zip(als, cands)]
+            w = best_of_rank(keys, means)
         tokens, lp = cands[w]
         glp = {0: lp}
         r = self._ar_finished(u, tokens)
         codes = r if isinstance(r, torch.Tensor) else self._run_nar(eng, [(0,) + r], rows, glp)[0][1]
-        return codes, BestOf(w, used, means, [c[0] for c in cands], lp)
+        return codes, BestOf(w, used, means, [c[0] for c in cands], lp, als, list(keys))
 
     # ---- shared by inference, inference_batch and inference_stream ------------------------------------
     def _check_logprobs(self, wanted: bool, what: str = "return_logprobs=True"):
@@ -549,7 +617,7 @@ class VALLE:
     @torch.no_grad()
     def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
                          poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None,
-                         top_p: float = 1.0, return_logprobs: bool = False):
+                         top_p: float = 1.0, return_logprobs: bool = False, return_alignment: bool = False):
         """Engine extension: continuous batching.  A generator over ``utterances`` (as for ``inference_batch``) that yields
         ``(index, codes)``, codes (1, T_i, Q) as ``inference_batch`` returns them, as utterances finish.  A slot whose utterance
         stopped is refilled from the queue while the others keep decoding: new utterances are admitted once ``refill_at``
@@ -557,7 +625,9 @@ class VALLE:
         wait for their NAR stages until ``nar_group`` (default max_batch) are pending or the queue is empty.  ``seeds[i]``
         belongs to utterance i, so the codes do not depend on the schedule.  ``batched_admit=False`` prefills slot by slot
         (bitwise the static path); ``poll_steps``: steps between stop polls (0: the engine default).  ``return_logprobs=True``
-        (models built with ``logprobs=True``): yields ``(index, (codes, GenLogProbs))``."""
+        (models built with ``logprobs=True``): yields ``(index, (codes, GenLogProbs))``.  ``return_alignment=True``: one
+        ``align_batch`` follows the NAR stages of every NAR group, over the prompt plus the generated codes of that group, and the
+        yield gains the ``Alignment`` (None for an empty output) as in ``inference_batch``."""
         top_p = _check_top_p(top_p)
         self._check_logprobs(return_logprobs)
         eng = self._batch_engine("inference_stream")
@@ -573,13 +643,18 @@ class VALLE:
         nar_group = B if nar_group is None else max(1, int(nar_group))
         batched_admit = batched_admit and eng.mfma_rows
         return self._stream(eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at,
-                            top_p, return_logprobs)
+                            top_p, return_logprobs, return_alignment)
 
     def _stream(self, eng, utterances, seeds, top_k, temperature, nar_group, poll_steps, batched_admit, batched_nar, refill_at,
-                top_p=1.0, return_logprobs=False):
+                top_p=1.0, return_logprobs=False, return_alignment=False):
         N, B = len(utterances), eng.max_batch
         glp = {} if return_logprobs else None  # index -> GenLogProbs of the utterances not yet yielded
-        give = (lambda i, c: (i, (c, glp.pop(i)))) if return_logprobs else (lambda i, c: (i, c))
+
+        def give(i, c, al=None):
+            if not (return_logprobs or return_alignment):
+                return i, c
+            return i, (c,) + ((glp.pop(i),) if return_logprobs else ()) + ((al,) if return_alignment else ())
+
         eng.batch_open()
         free = list(range(B))
         live = {}      # slot -> utterance index
@@ -610,8 +685,10 @@ class VALLE:
                         pending.append((i,) + r)
             if pending and (len(pending) >= nar_group or nxt >= N):
                 done, pending = pending, []
-                for i, c in self._run_nar(eng, done, batched_nar, glp):
-                    yield give(i, c)
+                res = self._run_nar(eng, done, batched_nar, glp)
+                als = self._align_generated([utterances[i] for i, _ in res], [c for _, c in res]) if return_alignment else [None] * len(res)
+                for (i, c), al in zip(res, als):
+                    yield give(i, c, al)
 
     # ---- scoring ---------------------------------------------------------------------------------------
     def _score_args(self, x, x_lens, y, prompt_frames, enroll_x_lens, top_k):
@@ -699,6 +776,46 @@ class VALLE:
         attn, mass, path, score, ph = self.engine().align(text, codes, P, c0=c0, head_w=hw, per_head=per_head)
         return make_alignment(attn, mass, path, score, ph)
 
+    def _align_batch_args(self, utterances, prompt_frames, heads):
+        """Checks of ``align_batch``'s arguments, before any engine exists -> [(text, codes, P, c0)], head weights or None."""
+        utterances = list(utterances)
+        Ps = list(prompt_frames) if isinstance(prompt_frames, (list, tuple)) else [prompt_frames] * len(utterances)
+        if len(Ps) != len(utterances):
+            raise ValueError(f"{len(Ps)} prompt_frames for {len(utterances)} utterances")
+        hw = head_weights(heads, self.cfg.num_decoder_layers, self.cfg.nhead)
+        args = []
+        for u, p in zip(utterances, Ps):
+            if not isinstance(u, (list, tuple)) or not 3 <= len(u) <= 4:
+                raise ValueError("an utterance is (x, x_lens, y[, enroll_x_lens])")
+            args.append(self._align_args(u[0], u[1], u[2], p, u[3] if len(u) > 3 else None, None)[:4])
+        return args, hw
+
+    @torch.no_grad()
+    def align_batch(self, utterances, prompt_frames, heads=None) -> List[Alignment]:
+        """``align`` of several utterances, (x, x_lens, y[, enroll_x_lens]) each; ``prompt_frames``: one value or one per
+        utterance; ``heads`` as for ``align``, shared by all.  The window of each is [enroll_x_lens or 0, S), as in ``align``.
+        Groups of at most 64 go through one pass over the concatenated rows with the attention tap on the matrix pipe
+        (vx_align_batch): the maps agree with ``align``'s within the bf16 bound, not bit for bit.  Where the engine has no such
+        pass (fp32, VALL-F, prenets, post-norm, other head sizes) every utterance is aligned by ``align``'s own call, so this
+        works wherever ``align`` does."""
+        from .engine import BMAX, VxError
+
+        args, hw = self._align_batch_args(utterances, prompt_frames, heads)
+        if not args:
+            return []
+        eng = self.engine()
+        out = []
+        for g0 in range(0, len(args), BMAX):
+            g = args[g0 : g0 + BMAX]
+            try:
+                parts = eng.align_batch([a[0] for a in g], [a[1] for a in g], [a[2] for a in g], [a[3] for a in g], head_w=hw)
+            except VxError as err:
+                if err.code != 5:  # VX_ERR_UNSUPPORTED: exactly where vx_align_batch refuses
+                    raise
+                parts = [eng.align(a[0], a[1], a[2], c0=a[3], head_w=hw)[:4] for a in g]
+            out += [make_alignment(*p) for p in parts]
+        return out
+
     @torch.no_grad()
     def continual(self, x: torch.Tensor, x_lens: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """VALLE.continual (valle.py:1139-1238; reached by bin/infer.py:224-230 with --continual): the first half
@@ -738,25 +855,35 @@ class VALLF(VALLE):
     def continual(self, *a, **k):
         raise AttributeError("'VALLF' object has no attribute 'continual'")  # valle.py:1139 defines it on VALLE only
 
+    @torch.no_grad()
+    def align_batch(self, utterances, prompt_frames, heads=None) -> List[Alignment]:
+        """``align`` of every utterance in turn: the segmented row pass holds one text memory, so VALL-F has no batched tap."""
+        args, hw = self._align_batch_args(utterances, prompt_frames, heads)
+        eng = self.engine() if args else None
+        return [make_alignment(*eng.align(a[0], a[1], a[2], c0=a[3], head_w=hw)[:4]) for a in args]
+
     def _vallf_batched(self, what: str):
         if self.engine_opts["max_batch"] < 2:
             raise NotImplementedError(f"VALL-F {what} needs a model built with max_batch >= 2 (otherwise batch-1 path only)")
 
     def inference_batch(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, batched_nar: bool = True,
-                        batched_prefill: bool = True, top_p: float = 1.0, return_logprobs: bool = False):
+                        batched_prefill: bool = True, top_p: float = 1.0, return_logprobs: bool = False,
+                        return_alignment: bool = False):
         self._vallf_batched("inference_batch")
         rows = self.engine_opts["batched_rows"]
         return super().inference_batch(utterances, top_k=top_k, temperature=temperature, seeds=seeds, batched_nar=rows and batched_nar,
-                                       batched_prefill=rows and batched_prefill, top_p=top_p, return_logprobs=return_logprobs)
+                                       batched_prefill=rows and batched_prefill, top_p=top_p, return_logprobs=return_logprobs,
+                                       return_alignment=return_alignment)
 
     def inference_stream(self, utterances, top_k: int = -100, temperature: float = 1.0, seeds=None, nar_group=None,
                          poll_steps: int = 0, batched_admit: bool = True, batched_nar: bool = True, refill_at=None,
-                         top_p: float = 1.0, return_logprobs: bool = False):
+                         top_p: float = 1.0, return_logprobs: bool = False, return_alignment: bool = False):
         self._vallf_batched("inference_stream")
         rows = self.engine_opts["batched_rows"]
         return super().inference_stream(utterances, top_k=top_k, temperature=temperature, seeds=seeds, nar_group=nar_group,
                                         poll_steps=poll_steps, batched_admit=rows and batched_admit, batched_nar=rows and batched_nar,
-                                        refill_at=refill_at, top_p=top_p, return_logprobs=return_logprobs)
+                                        refill_at=refill_at, top_p=top_p, return_logprobs=return_logprobs,
+                                        return_alignment=return_alignment)
 
 
 def get_model(params) -> VALLE:
