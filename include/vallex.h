@@ -609,6 +609,45 @@ int64_t vx_resample_length(int32_t orig_hz, int32_t new_hz, int64_t n_samples);
 int vx_resample(vx_resampler* r, int32_t n, const float* const* in, const int32_t* channels, const int32_t* n_samples,
                 float* const* out, void* stream);
 
+/* ---- log-mel filterbank (the reference's BigVGANFbank, valle/data/fbank.py:80-131) ------------------------------------------
+ * A handle of its own: no weights, no vx_codec.  Per utterance, a mono fp32 waveform of L samples at 24 kHz:
+ *   frames = (L + 128) / 256 (L / hop rounded half up); zeros are appended up to (frames - 1) 256 + 1024 samples (no centring,
+ *   no reflection); frame f = samples [256 f, 256 f + 1024) times the periodic Hann window; one-sided DFT, bins 0..512;
+ *   mag = sqrt(re^2 + im^2 + 1e-9); mel = basis (n_mels x 513) mag; out[f][m] = log(max(mel, clip)), (frames, n_mels) row-major.
+ * The DFT runs as a 32 x 32 four-step factorisation on the fp32 matrix instruction with tables computed in fp64 and rounded
+ * once; a filter's band is summed in ascending bin order.  A frame's bits depend on its own samples only. */
+typedef struct vx_fbank vx_fbank;
+typedef struct vx_fbank_config {
+  int32_t struct_size;  /* sizeof(vx_fbank_config) */
+  int32_t sample_rate;  /* 24000 */
+  int32_t n_fft;        /* 1024 (also the window length) */
+  int32_t hop;          /* 256 */
+  int32_t n_mels;       /* 1 .. 128; the reference has 100 */
+  float fmin, fmax;     /* band of the built-in Slaney basis, 0 <= fmin < fmax <= 12000 (the reference: 0 .. 12000) */
+  float clip;           /* floor under the log, > 0 (the reference: 1e-5) */
+  int32_t max_batch;    /* utterances per call */
+} vx_fbank_config;
+/* Host only, no HIP call (the tables go to the device current at the first extraction).  Nulls, a wrong struct_size,
+ * max_batch < 1 or a clip that is not positive and finite -> VX_ERR_ARG; another geometry, n_mels or band -> VX_ERR_UNSUPPORTED.
+ * The built-in basis is Slaney's: n_mels + 2 points equally spaced on the mel scale that is linear below 1 kHz (200 / 3 Hz
+ * per mel) and logarithmic above (step log(6.4) / 27), triangular weights between them, each scaled by 2 / (its width in Hz);
+ * fp64, rounded once. */
+int vx_fbank_create(const vx_fbank_config* cfg, vx_fbank** out);
+void vx_fbank_destroy(vx_fbank* fb);
+/* Replaces the basis by a HOST array (n_mels x 513), dense or not; it is copied, and takes effect at the next extraction.
+ * The getter copies the current one out.  Host only. */
+int vx_fbank_set_mel_basis(vx_fbank* fb, const float* basis);
+int vx_fbank_get_mel_basis(const vx_fbank* fb, float* basis);
+/* (L + 128) / 256, the frames an utterance of n_samples = L has; 0 below 128 samples.  Host only. */
+int64_t vx_fbank_frames(int64_t n_samples);
+/* n utterances: wav[i] DEVICE fp32 of n_samples[i] samples, out[i] DEVICE fp32 (frames, n_mels); the pointer arrays live on
+ * the host.  Every utterance is bitwise what it is alone, and two identical calls give the same bits; an utterance without
+ * frames (fewer than 128 samples) writes nothing.  Checked before any HIP call, in this order: null arguments or n < 1 ->
+ * VX_ERR_ARG; n > max_batch -> VX_ERR_CAPACITY; then per utterance a null pointer or n_samples[i] < 1 -> VX_ERR_ARG.  The work
+ * is one launch enqueued on `stream`; the host waits only for the previous call's staging copy (and, after a new basis, for
+ * the previous call).  Calls on one handle must not overlap. */
+int vx_fbank_extract(vx_fbank* fb, int32_t n, const float* const* wav, const int32_t* n_samples, float* const* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

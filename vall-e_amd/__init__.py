@@ -3,7 +3,8 @@ from .config import ModelConfig, add_model_arguments, NUM_AUDIO_TOKENS, NUM_TEXT
 
 
 __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_TOKENS", "AudioTokenizer", "CodecConfig", "EncodecDecoder",
-           "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio"]
+           "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio",
+           "BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -11,4 +12,8 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import codec
 
         return getattr(codec, name)
+    if name in ("BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis"):
+        from . import fbank
+
+        return getattr(fbank, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -302,6 +302,7 @@ class EncodecDecoder:
         self._h = None
         self._final = False
         self._resamplers: Dict[Tuple[int, int], Resampler] = {}
+        self._fbank = None
 
     # ---- weights ------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict: bool = True):
@@ -326,7 +327,18 @@ class EncodecDecoder:
         for r in self._resamplers.values():
             r.close()
         self._resamplers = {}
+        if self._fbank is not None:
+            self._fbank.close()
+            self._fbank = None
         return self
+
+    def fbank(self):
+        """The object's log-mel extractor (`fbank.BigVGANFbank` with the reference's settings), made on first use."""
+        if self._fbank is None:
+            from .fbank import BigVGANFbank
+
+            self._fbank = BigVGANFbank(max_batch=2).to(self.device)
+        return self._fbank
 
     def resampler(self, orig_hz: int, new_hz: int) -> Resampler:
         """The object's `Resampler` for a rate pair (kept per pair, `max_batch` utterances per call)."""
@@ -466,6 +478,20 @@ class EncodecDecoder:
     def encode(self, wav: torch.Tensor, n_q: Optional[int] = None, sr: Optional[int] = None) -> torch.Tensor:
         """(1, 1, L), (1, L) or (L,) float32 -> (1, n_q, ceil(L / hop)) int64 on the device; `sr` as in `encode_batch`."""
         return self.encode_batch([wav], n_q, sr)[0]
+
+    @torch.no_grad()
+    def roundtrip_mel_distance(self, wav: torch.Tensor, n_q: Optional[int] = None, sr: Optional[int] = None) -> torch.Tensor:
+        """Mean absolute log-mel difference between a waveform and decode(encode(waveform)), a 0-dim tensor on the device: the
+        check to run after `load_state_dict` with trained weights (a codec that reproduces speech stays well below 1; on
+        synthetic weights the number means nothing).  `wav` and `sr` as in `encode`; the comparison is at 24 kHz, against the
+        mixed-down and resampled input.  Needs `encoder=True`."""
+        from .fbank import mel_distance
+
+        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
+            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        rec = self.decode(self.encode(wav, n_q))
+        a, b = self.fbank().extract_batch([wav, rec])
+        return mel_distance(a, b)
 
 
 class AudioTokenizer:

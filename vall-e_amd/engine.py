@@ -48,6 +48,11 @@ class VxCodecConfig(C.Structure):
                                          "lstm_layers", "max_frames", "max_batch", "device", "flags")]
 
 
+class VxFbankConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "sample_rate", "n_fft", "hop", "n_mels")] + \
+               [(n, C.c_float) for n in ("fmin", "fmax", "clip")] + [("max_batch", C.c_int32)]
+
+
 class VxError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vallex error {code}: {msg}")
@@ -147,6 +152,14 @@ _SIGS = {
     "vx_resample_length": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "vx_resample": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                               C.POINTER(C.c_void_p), C.c_void_p]),
+    # log-mel filterbank (fbank.BigVGANFbank)
+    "vx_fbank_create": (C.c_int, [C.POINTER(VxFbankConfig), C.POINTER(C.c_void_p)]),
+    "vx_fbank_destroy": (None, [C.c_void_p]),
+    "vx_fbank_set_mel_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vx_fbank_get_mel_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vx_fbank_frames": (C.c_int64, [C.c_int64]),
+    "vx_fbank_extract": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                   C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so
