@@ -648,6 +648,60 @@ int64_t vx_fbank_frames(int64_t n_samples);
  * the previous call).  Calls on one handle must not overlap. */
 int vx_fbank_extract(vx_fbank* fb, int32_t n, const float* const* wav, const int32_t* n_samples, float* const* out, void* stream);
 
+/* ---- dynamic time warping between two feature sequences (mel-cepstral distortion, MCD-DTW) -----------------------------------
+ * A handle of its own: no weights, no vx_engine.  A pair is two fp32 DEVICE matrices A (Ta, D) and B (Tb, D), row-major,
+ * 1 <= D <= 128, Ta, Tb >= 1.
+ *   1. Cepstra (n_ceps >= 1; with n_ceps == 0 the rows are compared as given): every row m becomes
+ *        c_k = sqrt(2 / D) sum_{n = 0 .. D-1} m_n cos(pi k (n + 1/2) / D),  k = 1 .. n_ceps <= D - 1
+ *      (the orthonormal DCT-II without its 0th coefficient).  The table is computed in fp64 on the host and rounded once to fp32;
+ *      a row's products (exact in fp64) are added in ascending n in fp64 and the sum is rounded once to fp32.  A row's cepstra
+ *      depend on that row only.
+ *   2. Local cost d(i, j) = sqrt(sum_k (a_ik - b_jk)^2), fp32: every difference is formed in fp32 first (never |a|^2 + |b|^2 -
+ *      2 a.b: identical rows cost exactly 0), the squares (exact in fp64) are added in ascending k in fp64, and the root of the sum
+ *      is rounded once to fp32.
+ *   3. Warp, accumulated in fp64: G(0, 0) = d(0, 0); G(i, j) = d(i, j) + the minimum over the existing predecessors (i-1, j-1),
+ *      (i-1, j), (i, j-1).  Ties: the diagonal predecessor is kept unless another is strictly smaller; then (i-1, j) is kept
+ *      unless (i, j-1) is strictly smaller.  The path runs from (0, 0) to (Ta-1, Tb-1), is read back from the last cell and has
+ *      at most Ta + Tb - 1 cells.
+ *   4. Per pair: total = G(Ta-1, Tb-1) (double), path_len, and optionally the path, (path_len, 2) int32 pairs (i, j) in
+ *      ascending order.  (The Python layer adds mean = total / path_len and, for n_ceps > 0, mcd_db = (10 sqrt(2) / ln 10) mean.)
+ * Every cell of the warp is one fp64 min chain and one addition on exact inputs: a pair's results are the same bits on every
+ * run, in any batch, and as a host restatement computes them from the same cost matrix.  Non-finite inputs give unspecified
+ * values; the call still ends and writes nothing outside its outputs.
+ * Workspace: 5 bytes per cell of the call (sum of Ta Tb: the fp32 cost matrix and one byte of back-pointer) and 4 n_ceps bytes
+ * per frame, allocated at the first call and replaced by a larger one when a larger call arrives; never at the caps' size. */
+typedef struct vx_dtw vx_dtw;
+typedef struct vx_dtw_config {
+  int32_t struct_size;  /* sizeof(vx_dtw_config) */
+  int32_t dim;          /* D, 1 .. 128 */
+  int32_t n_ceps;       /* 0 (rows as given) .. dim - 1 */
+  int32_t max_frames;   /* capacity: frames per sequence, 1 .. 4096 */
+  int32_t max_batch;    /* capacity: pairs per call, 1 .. 64 */
+} vx_dtw_config;
+/* Host only, no HIP call (the table goes to the device current at the first compare).  Nulls, a wrong struct_size or
+ * max_batch < 1 -> VX_ERR_ARG; then dim outside [1, 128], n_ceps outside [0, dim - 1], max_frames outside [1, 4096] or
+ * max_batch > 64 -> VX_ERR_UNSUPPORTED. */
+int vx_dtw_create(const vx_dtw_config* cfg, vx_dtw** out);
+void vx_dtw_destroy(vx_dtw* h);
+/* n pairs in one ragged call: a[i] / b[i] DEVICE fp32 (Ta[i], dim) / (Tb[i], dim); the pointer arrays and the lengths live on
+ * the host.  total (n doubles) and path_len (n int32): host or device memory.  path: nullable, and so is each entry; path[i]
+ * DEVICE int32 with room for (Ta[i] + Tb[i] - 1, 2), of which the first path_len[i] pairs are written (the rest is scratch of
+ * the call).  Every pair is bitwise what it is alone.  Checked before any HIP call, in this order: null arguments (path
+ * excepted) or n < 1 -> VX_ERR_ARG; n > max_batch -> VX_ERR_CAPACITY; then per pair in order: a null a[i] / b[i] or a length
+ * < 1 -> VX_ERR_ARG, a length > max_frames -> VX_ERR_CAPACITY (the message names the pair).  The work (cepstra, cost, warp: one
+ * launch each for all pairs) is enqueued on `stream`; the host waits only for the previous call's staging copy (and, when the
+ * workspace has to grow, for the previous call).  Calls on one handle must not overlap. */
+int vx_dtw_compare(vx_dtw* h, int32_t n, const float* const* a, const int32_t* Ta, const float* const* b, const int32_t* Tb,
+                   double* total, int32_t* path_len, int32_t* const* path, void* stream);
+/* Test-only, like the vx_op_* entries above.  vx_op_dtw_cost: the cepstra (n_ceps > 0) and cost kernels on one pair; a (Ta, dim),
+ * b (Tb, dim), cost (Ta, Tb) fp32, all DEVICE; frames 1 .. 4096.  vx_op_dtw_path: the warp kernel on n caller-supplied cost
+ * matrices in one launch, one workgroup each.  desc: HOST, n x 4 values per matrix: Ta, Tb, cell_off (of the (Ta, Tb) matrix in
+ * cost), path_off (of its path in path, in cells: int32 pairs; room for Ta + Tb - 1); cost, total (n doubles), path_len (n
+ * int32) and path (nullable) DEVICE.  Bad arguments: VX_ERR_ARG (frames above 4096: VX_ERR_CAPACITY) before any HIP call.  Both
+ * synchronise the stream. */
+int vx_op_dtw_cost(int32_t dim, int32_t n_ceps, const float* a, int32_t Ta, const float* b, int32_t Tb, float* cost, void* stream);
+int vx_op_dtw_path(const float* cost, int32_t n, const int64_t* desc, double* total, int32_t* path_len, int32_t* path, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ from .config import ModelConfig, add_model_arguments, NUM_AUDIO_TOKENS, NUM_TEXT
 
 __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_TOKENS", "AudioTokenizer", "CodecConfig", "EncodecDecoder",
            "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio",
-           "BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis"]
+           "BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis",
+           "DTW", "DTWResult", "mel_cepstral_distortion"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -16,4 +17,8 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import fbank
 
         return getattr(fbank, name)
+    if name in ("DTW", "DTWResult", "mel_cepstral_distortion"):
+        from . import dtw
+
+        return getattr(dtw, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,319 @@
+// Dynamic time warping behind the C ABI (include/vallex.h, vx_dtw_*): the host table of the cepstra, the staging of a ragged call,
+// the workspace that grows with the calls, and the launches of dtw_kernels.hpp.  A translation unit and a handle of its own, like
+// fbank.hip: no other unit sees these kernels, so the device code of every existing path is compiled exactly as before.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#undef VX_STAMPS  // the in-kernel stamps write device globals of engine.hip's unit, out of this unit's reach
+#include "../../include/vallex.h"
+#include "dtw_kernels.hpp"
+
+using namespace vx;
+
+extern "C" void vx_internal_set_error(const char* msg);  // engine.hip: the message vx_last_error() returns
+
+static int dfail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  vx_internal_set_error(buf);
+  return code;
+}
+#define DHIPC(expr)                                                                                                    \
+  do {                                                                                                                 \
+    hipError_t e_ = (expr);                                                                                            \
+    if (e_ != hipSuccess)                                                                                              \
+      return dfail(VX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);              \
+  } while (0)
+
+struct vx_dtw {
+  int dim = 0, n_ceps = 0, max_frames = 0, max_batch = 0;
+  std::vector<float> tab;  // [dim][n_ceps]: sqrt(2 / dim) cos(pi k (n + 1/2) / dim), k = 1 .. n_ceps
+  // device side: made on the device that is current at the first vx_dtw_compare
+  int device = -1;
+  float* d_tab = nullptr;
+  char *stage_dev = nullptr, *stage_host = nullptr;  // per call: DtwPair [max_batch]
+  double* d_total = nullptr;                         // [max_batch]
+  int* d_len = nullptr;                              // [max_batch]
+  // workspace, sized to the largest call so far: 4 (cost) + 1 (back-pointer) bytes per cell, 4 n_ceps bytes per frame
+  float* d_cost = nullptr;
+  unsigned char* d_bp = nullptr;
+  float* d_ceps = nullptr;
+  long long cap_cells = 0, cap_rows = 0;
+  bool poison = false;
+  hipEvent_t ev_copy = nullptr, ev_done = nullptr;
+};
+
+namespace {
+
+struct DDevGuard {
+  int prev = -1;
+  hipError_t err = hipSuccess;
+  explicit DDevGuard(int dev) {
+    err = hipGetDevice(&prev);
+    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
+    else if (err == hipSuccess) prev = -1;
+  }
+  ~DDevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// The orthonormal DCT-II without its 0th row, n-major: fp64, rounded once.
+std::vector<float> dct_table(int dim, int n_ceps) {
+  std::vector<float> t((size_t)dim * n_ceps);
+  const double pi = 3.14159265358979323846, scale = sqrt(2.0 / (double)dim);
+  for (int n = 0; n < dim; ++n)
+    for (int k = 1; k <= n_ceps; ++k) t[(size_t)n * n_ceps + (k - 1)] = (float)(scale * cos(pi * (double)k * ((double)n + 0.5) / (double)dim));
+  return t;
+}
+
+void dtw_free_device(vx_dtw* h) {
+  (void)hipFree(h->d_tab);
+  (void)hipFree(h->stage_dev);
+  (void)hipHostFree(h->stage_host);
+  (void)hipFree(h->d_total);
+  (void)hipFree(h->d_len);
+  (void)hipFree(h->d_cost);
+  (void)hipFree(h->d_bp);
+  (void)hipFree(h->d_ceps);
+  for (hipEvent_t ev : {h->ev_copy, h->ev_done})
+    if (ev) (void)hipEventDestroy(ev);
+  h->d_tab = h->d_cost = h->d_ceps = nullptr; h->stage_dev = h->stage_host = nullptr; h->d_total = nullptr; h->d_len = nullptr;
+  h->d_bp = nullptr; h->ev_copy = h->ev_done = nullptr; h->cap_cells = h->cap_rows = 0;
+}
+
+// First use: the table goes to the current device.  VX_POISON=1 fills the fresh allocations with 0xFF bytes first, as the engine does.
+int dtw_init_device(vx_dtw* h) {
+  int dev = 0;
+  DHIPC(hipGetDevice(&dev));
+  h->device = dev;
+  const char* pv = getenv("VX_POISON");
+  h->poison = pv && atoi(pv) != 0;
+  const size_t MB = (size_t)h->max_batch, sb = MB * sizeof(DtwPair);
+  DHIPC(hipMalloc((void**)&h->stage_dev, sb));
+  DHIPC(hipMalloc((void**)&h->d_total, MB * sizeof(double)));
+  DHIPC(hipMalloc((void**)&h->d_len, MB * sizeof(int)));
+  if (h->poison) {
+    DHIPC(hipMemset(h->stage_dev, 0xFF, sb));
+    DHIPC(hipMemset(h->d_total, 0xFF, MB * sizeof(double)));
+    DHIPC(hipMemset(h->d_len, 0xFF, MB * sizeof(int)));
+  }
+  DHIPC(hipHostMalloc((void**)&h->stage_host, sb));
+  if (h->n_ceps > 0) {
+    DHIPC(hipMalloc((void**)&h->d_tab, h->tab.size() * sizeof(float)));
+    DHIPC(hipMemcpy(h->d_tab, h->tab.data(), h->tab.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  DHIPC(hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
+  DHIPC(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
+  return VX_OK;
+}
+
+// The workspace follows the largest call: a larger one waits for the previous call and replaces the buffers.
+int dtw_grow(vx_dtw* h, long long cells, long long rows) {
+  if (cells <= h->cap_cells && rows <= h->cap_rows) return VX_OK;
+  DHIPC(hipEventSynchronize(h->ev_done));
+  if (cells > h->cap_cells) {
+    (void)hipFree(h->d_cost);
+    (void)hipFree(h->d_bp);
+    h->d_cost = nullptr; h->d_bp = nullptr; h->cap_cells = 0;
+    DHIPC(hipMalloc((void**)&h->d_cost, (size_t)cells * sizeof(float)));
+    DHIPC(hipMalloc((void**)&h->d_bp, (size_t)cells));
+    if (h->poison) {
+      DHIPC(hipMemset(h->d_cost, 0xFF, (size_t)cells * sizeof(float)));
+      DHIPC(hipMemset(h->d_bp, 0xFF, (size_t)cells));
+    }
+    h->cap_cells = cells;
+  }
+  if (rows > h->cap_rows && h->n_ceps > 0) {
+    (void)hipFree(h->d_ceps);
+    h->d_ceps = nullptr; h->cap_rows = 0;
+    DHIPC(hipMalloc((void**)&h->d_ceps, (size_t)rows * h->n_ceps * sizeof(float)));
+    if (h->poison) DHIPC(hipMemset(h->d_ceps, 0xFF, (size_t)rows * h->n_ceps * sizeof(float)));
+    h->cap_rows = rows;
+  }
+  return VX_OK;
+}
+
+// Cepstra (n_ceps > 0) and the cost matrices of the n staged pairs.
+void launch_dtw_cost(const DtwPair* d_pairs, int n, int tiles, long long max_rows, const float* d_tab, int dim, int n_ceps, float* d_ceps,
+                     float* d_cost, hipStream_t s) {
+  if (n_ceps > 0) {
+    const long long blocks = (max_rows * n_ceps + DTW_WG - 1) / DTW_WG;
+    dtw_ceps_kernel<<<dim3((unsigned)std::min<long long>(std::max<long long>(blocks, 1), 1024), n), DTW_WG, 0, s>>>(d_pairs, d_tab, dim,
+                                                                                                                  n_ceps, d_ceps);
+    dtw_cost_kernel<<<tiles, DTW_WG, 0, s>>>(d_pairs, n, d_ceps, n_ceps, d_cost);
+  } else {
+    dtw_cost_kernel<<<tiles, DTW_WG, 0, s>>>(d_pairs, n, nullptr, dim, d_cost);
+  }
+}
+
+// One workgroup per pair; the three diagonals of the longest A of the launch in LDS.
+hipError_t launch_dtw_warp(const float* d_cost, unsigned char* d_bp, const DtwPair* d_pairs, int n, int max_ta, double* d_total, int* d_len,
+                           hipStream_t s) {
+  const size_t lds = (size_t)3 * max_ta * sizeof(double);
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute((const void*)dtw_warp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * DTW_MAX_FRAMES * 8);
+    if (e != hipSuccess) return e;
+  }
+  dtw_warp_kernel<<<n, DTW_WG, lds, s>>>(d_cost, d_bp, d_pairs, d_total, d_len);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int vx_dtw_create(const vx_dtw_config* cfg, vx_dtw** out) {
+  if (!cfg || !out) return dfail(VX_ERR_ARG, "vx_dtw_create: null argument");
+  if (cfg->struct_size != (int32_t)sizeof(vx_dtw_config))
+    return dfail(VX_ERR_ARG, "vx_dtw_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_dtw_config));
+  if (cfg->max_batch < 1) return dfail(VX_ERR_ARG, "vx_dtw_create: max_batch = %d", cfg->max_batch);
+  if (cfg->dim < 1 || cfg->dim > DTW_MAX_DIM) return dfail(VX_ERR_UNSUPPORTED, "vx_dtw_create: dim = %d outside [1, %d]", cfg->dim, DTW_MAX_DIM);
+  if (cfg->n_ceps < 0 || cfg->n_ceps > cfg->dim - 1)
+    return dfail(VX_ERR_UNSUPPORTED, "vx_dtw_create: n_ceps = %d outside [0, dim - 1 = %d]", cfg->n_ceps, cfg->dim - 1);
+  if (cfg->max_frames < 1 || cfg->max_frames > DTW_MAX_FRAMES)
+    return dfail(VX_ERR_UNSUPPORTED, "vx_dtw_create: max_frames = %d outside [1, %d]", cfg->max_frames, DTW_MAX_FRAMES);
+  if (cfg->max_batch > DTW_MAX_BATCH) return dfail(VX_ERR_UNSUPPORTED, "vx_dtw_create: max_batch = %d > %d", cfg->max_batch, DTW_MAX_BATCH);
+  vx_dtw* h = new vx_dtw();
+  h->dim = cfg->dim; h->n_ceps = cfg->n_ceps; h->max_frames = cfg->max_frames; h->max_batch = cfg->max_batch;
+  h->tab = dct_table(cfg->dim, cfg->n_ceps);
+  *out = h;
+  return VX_OK;
+}
+
+extern "C" void vx_dtw_destroy(vx_dtw* h) {
+  if (!h) return;
+  if (h->device >= 0) {
+    DDevGuard g(h->device);
+    if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
+    dtw_free_device(h);
+  }
+  delete h;
+}
+
+extern "C" int vx_dtw_compare(vx_dtw* h, int32_t n, const float* const* a, const int32_t* Ta, const float* const* b, const int32_t* Tb,
+                              double* total, int32_t* path_len, int32_t* const* path, void* stream) {
+  if (!h || !a || !Ta || !b || !Tb || !total || !path_len) return dfail(VX_ERR_ARG, "vx_dtw_compare: null argument");
+  if (n < 1) return dfail(VX_ERR_ARG, "vx_dtw_compare: n = %d pairs", n);
+  if (n > h->max_batch) return dfail(VX_ERR_CAPACITY, "vx_dtw_compare: n = %d pairs > max_batch %d", n, h->max_batch);
+  std::vector<DtwPair> ps(n);
+  long long cells = 0, rows = 0, max_rows = 0;
+  int tiles = 0, max_ta = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!a[i] || !b[i]) return dfail(VX_ERR_ARG, "vx_dtw_compare: pair %d: null pointer", i);
+    if (Ta[i] < 1 || Tb[i] < 1) return dfail(VX_ERR_ARG, "vx_dtw_compare: pair %d: %d x %d frames", i, Ta[i], Tb[i]);
+    if (Ta[i] > h->max_frames || Tb[i] > h->max_frames)
+      return dfail(VX_ERR_CAPACITY, "vx_dtw_compare: pair %d: %d x %d frames > max_frames %d", i, Ta[i], Tb[i], h->max_frames);
+    DtwPair& p = ps[i];
+    p.a = a[i]; p.b = b[i]; p.path = path ? path[i] : nullptr;
+    p.cell_off = cells; p.ceps_off = rows * h->n_ceps;
+    p.Ta = Ta[i]; p.Tb = Tb[i]; p.tile0 = tiles; p.pad_ = 0;
+    cells += (long long)Ta[i] * Tb[i];
+    rows += (long long)Ta[i] + Tb[i];
+    max_rows = std::max(max_rows, (long long)Ta[i] + Tb[i]);
+    tiles += ((Ta[i] + DTW_TILE - 1) / DTW_TILE) * ((Tb[i] + DTW_TILE - 1) / DTW_TILE);  // <= 64 pairs x 64 x 64 tiles
+    max_ta = std::max(max_ta, Ta[i]);
+  }
+  if (h->device < 0) {
+    const int rc = dtw_init_device(h);
+    if (rc != VX_OK) {
+      dtw_free_device(h);
+      h->device = -1;
+      return rc;
+    }
+  }
+  DDevGuard g(h->device);
+  DHIPC(g.err);
+  hipStream_t s = (hipStream_t)stream;
+  DHIPC(hipEventSynchronize(h->ev_copy));  // the previous call's copy out of the pinned buffer has completed
+  {
+    const int rc = dtw_grow(h, cells, rows);
+    if (rc != VX_OK) return rc;
+  }
+  DHIPC(hipStreamWaitEvent(s, h->ev_done, 0));  // the previous call, on whatever stream it ran, is done with stage and workspace
+  memcpy(h->stage_host, ps.data(), (size_t)n * sizeof(DtwPair));
+  DHIPC(hipMemcpyAsync(h->stage_dev, h->stage_host, (size_t)n * sizeof(DtwPair), hipMemcpyHostToDevice, s));
+  DHIPC(hipEventRecord(h->ev_copy, s));
+  const DtwPair* dp = (const DtwPair*)h->stage_dev;
+  launch_dtw_cost(dp, n, tiles, max_rows, h->d_tab, h->dim, h->n_ceps, h->d_ceps, h->d_cost, s);
+  DHIPC(hipGetLastError());
+  DHIPC(launch_dtw_warp(h->d_cost, h->d_bp, dp, n, max_ta, h->d_total, h->d_len, s));
+  hipError_t e1 = hipMemcpyAsync(total, h->d_total, (size_t)n * sizeof(double), hipMemcpyDefault, s);
+  hipError_t e2 = hipMemcpyAsync(path_len, h->d_len, (size_t)n * sizeof(int), hipMemcpyDefault, s);
+  DHIPC(hipEventRecord(h->ev_done, s));
+  DHIPC(e1);
+  DHIPC(e2);
+  return VX_OK;
+}
+
+// The cepstra and cost kernels of one pair on caller data; synchronous.
+extern "C" int vx_op_dtw_cost(int32_t dim, int32_t n_ceps, const float* a, int32_t Ta, const float* b, int32_t Tb, float* cost,
+                              void* stream) {
+  if (!a || !b || !cost) return dfail(VX_ERR_ARG, "vx_op_dtw_cost: null argument");
+  if (dim < 1 || dim > DTW_MAX_DIM || n_ceps < 0 || n_ceps > dim - 1)
+    return dfail(VX_ERR_ARG, "vx_op_dtw_cost: dim = %d, n_ceps = %d (dim in [1, %d], n_ceps in [0, dim - 1])", dim, n_ceps, DTW_MAX_DIM);
+  if (Ta < 1 || Tb < 1 || Ta > DTW_MAX_FRAMES || Tb > DTW_MAX_FRAMES)
+    return dfail(VX_ERR_ARG, "vx_op_dtw_cost: %d x %d frames (1 .. %d each)", Ta, Tb, DTW_MAX_FRAMES);
+  DtwPair p{};
+  p.a = a; p.b = b; p.Ta = Ta; p.Tb = Tb;
+  const int tiles = ((Ta + DTW_TILE - 1) / DTW_TILE) * ((Tb + DTW_TILE - 1) / DTW_TILE);
+  const std::vector<float> tab = dct_table(dim, n_ceps);
+  hipStream_t s = (hipStream_t)stream;
+  void *d_p = nullptr, *d_tab = nullptr, *d_ceps = nullptr;
+  hipError_t err = hipMalloc(&d_p, sizeof(DtwPair));
+  if (err == hipSuccess && n_ceps > 0) err = hipMalloc(&d_tab, tab.size() * sizeof(float));
+  if (err == hipSuccess && n_ceps > 0) err = hipMalloc(&d_ceps, (size_t)(Ta + Tb) * n_ceps * sizeof(float));
+  if (err == hipSuccess) err = hipMemcpyAsync(d_p, &p, sizeof(DtwPair), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess && n_ceps > 0) err = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess) {
+    launch_dtw_cost((const DtwPair*)d_p, 1, tiles, (long long)Ta + Tb, (const float*)d_tab, dim, n_ceps, (float*)d_ceps, cost, s);
+    err = hipGetLastError();
+  }
+  const hipError_t err2 = hipStreamSynchronize(s);  // also: `p` and `tab` outlive their copies
+  (void)hipFree(d_p);
+  (void)hipFree(d_tab);
+  (void)hipFree(d_ceps);
+  DHIPC(err);
+  DHIPC(err2);
+  return VX_OK;
+}
+
+// desc: n x 4 host values per matrix (Ta, Tb, cell_off, path_off); synchronous.
+extern "C" int vx_op_dtw_path(const float* cost, int32_t n, const int64_t* desc, double* total, int32_t* path_len, int32_t* path,
+                              void* stream) {
+  if (!cost || !desc || !total || !path_len) return dfail(VX_ERR_ARG, "vx_op_dtw_path: null argument");
+  if (n < 1) return dfail(VX_ERR_ARG, "vx_op_dtw_path: n = %d matrices", n);
+  std::vector<DtwPair> ps(n);
+  long long cells = 0;
+  int max_ta = 0;
+  for (int z = 0; z < n; ++z) {
+    const int64_t* d = desc + 4 * (size_t)z;
+    if (d[0] < 1 || d[1] < 1 || d[2] < 0 || d[3] < 0) return dfail(VX_ERR_ARG, "vx_op_dtw_path: matrix %d: Ta and Tb must be >= 1, offsets >= 0", z);
+    if (d[0] > DTW_MAX_FRAMES || d[1] > DTW_MAX_FRAMES)
+      return dfail(VX_ERR_CAPACITY, "vx_op_dtw_path: matrix %d: %lld x %lld frames (at most %d each)", z, (long long)d[0], (long long)d[1], DTW_MAX_FRAMES);
+    DtwPair& p = ps[z];
+    p = DtwPair{};
+    p.Ta = (int)d[0]; p.Tb = (int)d[1]; p.cell_off = d[2];
+    p.path = path ? path + 2 * d[3] : nullptr;
+    cells = std::max(cells, (long long)d[2] + (long long)d[0] * d[1]);
+    max_ta = std::max(max_ta, p.Ta);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  void *d_p = nullptr, *bp = nullptr;
+  hipError_t err = hipMalloc(&d_p, ps.size() * sizeof(DtwPair));
+  if (err == hipSuccess) err = hipMalloc(&bp, (size_t)cells);
+  if (err == hipSuccess) err = hipMemcpyAsync(d_p, ps.data(), ps.size() * sizeof(DtwPair), hipMemcpyHostToDevice, s);
+  if (err == hipSuccess) err = launch_dtw_warp(cost, (unsigned char*)bp, (const DtwPair*)d_p, n, max_ta, total, path_len, s);
+  const hipError_t err2 = hipStreamSynchronize(s);
+  (void)hipFree(d_p);
+  (void)hipFree(bp);
+  DHIPC(err);
+  DHIPC(err2);
+  return VX_OK;
+}

@@ -53,6 +53,10 @@ class VxFbankConfig(C.Structure):
                [(n, C.c_float) for n in ("fmin", "fmax", "clip")] + [("max_batch", C.c_int32)]
 
 
+class VxDtwConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "dim", "n_ceps", "max_frames", "max_batch")]
+
+
 class VxError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vallex error {code}: {msg}")
@@ -160,6 +164,13 @@ _SIGS = {
     "vx_fbank_frames": (C.c_int64, [C.c_int64]),
     "vx_fbank_extract": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                    C.c_void_p]),
+    # dynamic time warping (dtw.DTW)
+    "vx_dtw_create": (C.c_int, [C.POINTER(VxDtwConfig), C.POINTER(C.c_void_p)]),
+    "vx_dtw_destroy": (None, [C.c_void_p]),
+    "vx_dtw_compare": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "vx_op_dtw_cost": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "vx_op_dtw_path": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so
@@ -929,6 +940,40 @@ def op_mono_path_segs(attn, maps):
     _check(lib.vx_op_mono_path_segs(_ptr(attn), len(maps), (C.c_int64 * len(flat))(*flat), _ptr(path), _ptr(score),
                                     current_stream_ptr(attn.device)))
     return list(torch.split(path, [int(m[0]) for m in maps])), score
+
+
+def op_dtw_cost(a, b, n_ceps):
+    """The cepstra and cost kernels of vx_dtw_compare on one pair (vx_op_dtw_cost): a (Ta, D), b (Tb, D) float32 on the device ->
+    the (Ta, Tb) float32 cost matrix, of the rows' first ``n_ceps`` cepstra or, with ``n_ceps`` = 0, of the rows as given."""
+    lib = load_library()
+    for t in (a, b):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.is_cuda and t.shape[1] == a.shape[1]
+    cost = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
+    _check(lib.vx_op_dtw_cost(a.shape[1], int(n_ceps), _ptr(a), a.shape[0], _ptr(b), b.shape[0], _ptr(cost),
+                              current_stream_ptr(a.device)))
+    return cost
+
+
+def op_dtw_path(cost, mats, want_path=True):
+    """dtw_warp_kernel on a flat device buffer of cost matrices (vx_op_dtw_path): ``mats`` = one (Ta, Tb, cell_off) per matrix ->
+    (totals (n,) float64, lengths (n,) int32, paths: a list of (length, 2) int32 tensors, or None), on the device."""
+    lib = load_library()
+    assert cost.dtype == torch.float32 and cost.dim() == 1 and cost.is_contiguous() and cost.is_cuda
+    flat, path_off = [], 0
+    for Ta, Tb, cell_off in mats:
+        assert 0 <= cell_off and cell_off + Ta * Tb <= cost.numel()
+        flat += [int(Ta), int(Tb), int(cell_off), path_off]
+        path_off += int(Ta) + int(Tb) - 1
+    path = torch.empty((path_off, 2), dtype=torch.int32, device=cost.device) if want_path else None
+    total = torch.empty(len(mats), dtype=torch.float64, device=cost.device)
+    length = torch.empty(len(mats), dtype=torch.int32, device=cost.device)
+    _check(lib.vx_op_dtw_path(_ptr(cost), len(mats), (C.c_int64 * len(flat))(*flat), _ptr(total), _ptr(length), _ptr(path),
+                              current_stream_ptr(cost.device)))
+    if not want_path:
+        return total, length, None
+    lens = length.tolist()
+    parts = torch.split(path, [int(m[0]) + int(m[1]) - 1 for m in mats])
+    return total, length, [p[:n] for p, n in zip(parts, lens)]
 
 
 def op_sample(logits, top_k, temperature, exp_noise):

@@ -93,12 +93,19 @@ def slaney_mel_basis(sr: int = SAMPLE_RATE, n_fft: int = N_FFT, n_mels: int = 10
     return torch.from_numpy(slaney_mel_basis_f64(sr, n_fft, n_mels, float(fmin), fmax).astype(np.float32))
 
 
-def mel_distance(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """Mean absolute log-mel difference over the frames both (n_frames, n_mels) tensors have; a 0-dim tensor on their device."""
+def mel_distance(a: torch.Tensor, b: torch.Tensor, warp: bool = False) -> torch.Tensor:
+    """Mean absolute log-mel difference over the frames both (n_frames, n_mels) tensors have; a 0-dim tensor on their device.
+    With `warp` the frames are paired along the DTW path of the raw log-mels (`dtw.DTW` with n_ceps = 0: Euclidean local cost)
+    instead of index by index, for two signals whose timing differs; device tensors only then."""
     assert a.dim() == 2 and b.dim() == 2 and a.shape[1] == b.shape[1], "two (n_frames, n_mels) tensors of one n_mels"
     n = min(a.shape[0], b.shape[0])
     if n == 0:
         raise ValueError("mel_distance: no common frame (an input has fewer than 128 samples)")
+    if warp:
+        from .dtw import shared_dtw
+
+        path = shared_dtw(a.device, a.shape[1], 0).compare(a, b, return_path=True).path.long()
+        return (a[path[:, 0]] - b[path[:, 1]]).abs().mean()
     return (a[:n] - b[:n]).abs().mean()
 
 
