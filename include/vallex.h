@@ -378,6 +378,26 @@ int vx_op_gemm(int32_t prec, int32_t use_mfma, const void* A, const void* W, con
  * kernel reads; vt may be NULL); form 1: C (M, N) fp32 += A.W^T + bias (out-projection / FFN2 onto the residual stream). */
 int vx_op_gemm_rows(int32_t form, const void* A_bf16, const void* W_bf16, const float* bias, void* C, int32_t M, int32_t N,
                     int32_t K, int32_t relu, void* vt_bf16, int32_t vt_n0, int32_t vt_ld, void* stream);
+/* The split-K construction of the row path's N = d GEMMs (out-projection, FFN2 at M < 4096 rows), piece by piece on caller
+ * data, through the launchers the engine's stack calls.
+ * vx_op_gemm_partial: slab z (M, N) fp32 of slabs (splits, M, N) = A[:, z K / splits : (z + 1) K / splits] . W[:, same]^T on bf16
+ * A (M, K), W (N, K); no bias.  N % 128 == 0, splits in {1, 2, 4}, K % (64 splits) == 0 (else VX_ERR_UNSUPPORTED); null operands or
+ * M < 1: VX_ERR_ARG.
+ * vx_op_ln_fold: the row LayerNorm with its optional arguments.  part != NULL: x[r] + (pbias + part[0][r] + ... +
+ * part[nsplit-1][r]) (in that order; slab z at part + z part_stride, nsplit in 1..4) replaces the row first; it is written back
+ * to x unless xout redirects the result.  out (fp32 or bf16 per prec) = [ada_w *] (LN(row) gamma + beta) [+ ada_b]; xout (fp32,
+ * may alias x) receives the same values unrounded, and x itself is then left as it was.  out == NULL: fold only (needs part).
+ * d a multiple of 4, <= 1024 (else VX_ERR_UNSUPPORTED); part without pbias, xout without out, out without gamma / beta: VX_ERR_ARG.
+ * vx_op_rows_plan: out[3] = {split-K on, K slices of the out-projection, of FFN2} as the stack chooses them over M rows of
+ * width d on a bf16, head_dim 64 engine without MXFP8 or a text memory, for num_cu compute units (<= 0: the current device's;
+ * with an explicit count the call is host only).
+ * All three check their arguments before any HIP call and return after enqueueing on `stream`. */
+int vx_op_gemm_partial(const void* A_bf16, const void* W_bf16, float* slabs, int32_t M, int32_t N, int32_t K, int32_t splits,
+                       void* stream);
+int vx_op_ln_fold(int32_t prec, float* x, const float* part, int32_t nsplit, int64_t part_stride, const float* pbias,
+                  const float* gamma, const float* beta, const float* ada_w, const float* ada_b, void* out, float* xout, int32_t rows,
+                  int32_t d, void* stream);
+int vx_op_rows_plan(int32_t M, int32_t d, int32_t num_cu, int32_t* out);
 /* The MXFP8 (VX_PREC_FP8_NAR) kernels on caller data.  vx_op_gemm_mx: A (M, K) / W (N, K) fp32 device pointers are quantised
  * on the device as the engine does (e4m3 + one E8M0 scale per 32 k) and multiplied on the block-scaled matrix cores; out_mode 0:
  * c_out = C (M, N) fp32 (+bias, ReLU); out_mode 2 (FFN1's form): c_out = ReLU(C + bias) as e4m3 bytes (M, N), sc_out = its block

@@ -300,6 +300,88 @@ def test_ln_batch_rejects_bad_arguments_without_gpu(lib, kw, match):
     assert rc == 1 and match.encode() in lib.vx_last_error(), (kw, lib.vx_last_error())
 
 
+# ---- vx_op_gemm_partial / vx_op_ln_fold / vx_op_rows_plan: the row path's split-K pieces ------------------------------------------
+def _partial(lib, A=_P, W=_P, slabs=_P, M=300, N=256, K=1024, splits=4):
+    return lib.vx_op_gemm_partial(A, W, slabs, M, N, K, splits, None)
+
+
+@pytest.mark.parametrize("kw,rc,match", [
+    (dict(A=None), 1, "null operand"),
+    (dict(W=None), 1, "null operand"),
+    (dict(slabs=None), 1, "null operand"),
+    (dict(M=0), 1, "M 0"),
+    (dict(N=192), 5, "N 192"),                                     # not whole 128-wide tiles
+    (dict(N=0), 5, "N 0"),
+    (dict(splits=3), 5, "splits 3"),
+    (dict(splits=0), 5, "splits 0"),
+    (dict(splits=8), 5, "splits 8"),
+    (dict(K=128, splits=4), 5, "K 128"),                           # a slice of 32 k
+    (dict(K=192, splits=2), 5, "K 192"),                           # slices of 96 k
+    (dict(K=96, splits=1), 5, "K 96"),
+    (dict(K=0, splits=1), 5, "K 0"),
+])
+def test_gemm_partial_rejects_bad_arguments_without_gpu(lib, kw, rc, match):
+    assert _partial(lib, **kw) == rc and match.encode() in lib.vx_last_error(), (kw, lib.vx_last_error())
+
+
+def _fold(lib, prec=1, x=_P, part=_P, nsplit=4, stride=4 * 256, pbias=_P, gamma=_P, beta=_P, ada_w=None, ada_b=None, out=_P, xout=None,
+          rows=4, d=256):
+    return lib.vx_op_ln_fold(prec, x, part, nsplit, stride, pbias, gamma, beta, ada_w, ada_b, out, xout, rows, d, None)
+
+
+@pytest.mark.parametrize("kw,rc,match", [
+    (dict(d=258), 5, "d 258"),                                     # float4 columns
+    (dict(d=1028), 5, "d 1028"),                                   # 4 float4 per lane
+    (dict(d=0), 5, "d 0"),
+    (dict(prec=2), 1, "prec 2"),
+    (dict(x=None), 1, "null x"),
+    (dict(rows=0), 1, "rows 0"),
+    (dict(nsplit=0), 1, "nsplit 0"),
+    (dict(nsplit=5), 1, "nsplit 5"),
+    (dict(pbias=None), 1, "needs pbias"),
+    (dict(stride=4 * 256 - 1), 1, "part_stride 1023"),             # slabs that overlap
+    (dict(out=None, part=None), 1, "needs part"),                  # fold only without anything to fold
+    (dict(out=None, xout=_P), 1, "xout needs out"),
+    (dict(gamma=None), 1, "gamma and beta"),
+    (dict(beta=None), 1, "gamma and beta"),
+    (dict(ada_w=_P), 1, "come together"),
+    (dict(ada_b=_P), 1, "come together"),
+])
+def test_ln_fold_rejects_bad_arguments_without_gpu(lib, kw, rc, match):
+    assert _fold(lib, **kw) == rc and match.encode() in lib.vx_last_error(), (kw, lib.vx_last_error())
+
+
+@pytest.mark.parametrize("M,d,want", [
+    (1000, 1024, (1, 4, 4)),   # 64 tiles x 4 slices = 256 workgroups: one round
+    (1025, 1024, (1, 2, 2)),   # 72 tiles: 4 slices would be two rounds
+    (2100, 1024, (1, 1, 1)),   # 136 tiles: no slabs, the GEMM epilogue adds the residual
+    (300, 128, (1, 2, 4)),     # K = 128 has two 64-wide slices at most
+    (129, 256, (1, 4, 4)),
+    (70, 1024, (1, 4, 4)),
+    (257, 512, (1, 4, 4)),
+    (4095, 128, (1, 2, 4)),
+])
+def test_rows_plan_table_without_gpu(lib, M, d, want):
+    """vx_op_rows_plan with an explicit CU count is the stack's own host function and makes no HIP call."""
+    from valle_amd.engine import op_rows_plan
+
+    assert op_rows_plan(M, d, 256) == want
+    if M == 2100:
+        assert op_rows_plan(M, d, 304) == (1, 2, 2)  # the plan follows the CU count
+
+
+def test_rows_plan_no_slabs_from_4096_rows_and_bad_arguments_without_gpu(lib):
+    import ctypes as C
+    from valle_amd.engine import op_rows_plan
+
+    for d in (128, 256, 512, 1024):
+        assert op_rows_plan(4096, d, 256)[0] == 0 and op_rows_plan(4095, d, 256)[0] == 1
+    assert op_rows_plan(300, 192, 256)[0] == 0  # d % 128 != 0: no split-K form
+    out = (C.c_int32 * 3)()
+    for args in ((0, 128, 256, out), (300, 0, 256, out), (300, 128, 256, None)):
+        assert lib.vx_op_rows_plan(*args) == 1 and b"rows_plan" in lib.vx_last_error()
+
+
 # ---- batched decode widths: d_model in {128, 256, 512, 1024} ----------------------------------------------------------------------
 def _batch_cfg(d, max_batch=4, flags=0):
     import ctypes as C

@@ -940,11 +940,16 @@ static int gemm_rows(vx_engine* e, const void* A, const void* Wt, const float* b
 
 // fold: the split-K slabs (and bias) of the GEMM in front of this norm, added to x first (rows_kernels.hpp)
 struct Fold { const float* part = nullptr; int nsplit = 0; size_t stride = 0; const float* bias = nullptr; };
+// the launch itself, on any stream (ln_rows below; vx_op_ln_fold on caller buffers)
+static void ln_rows_launch(bool out_bf16, const float* x, const float* g, const float* b, const float* aw, const float* ab, void* out,
+                           int rows, int d, float* xout, const Fold& f, hipStream_t s) {
+  // d <= 1024 in the engine (vx_create): 4 float4 per lane
+  if (out_bf16) layernorm_rows_kernel<bf16, 4><<<(rows + 3) / 4, 256, 0, s>>>(x, g, b, aw, ab, (bf16*)out, rows, d, xout, f.part, f.nsplit, f.stride, f.bias);
+  else layernorm_rows_kernel<float, 4><<<(rows + 3) / 4, 256, 0, s>>>(x, g, b, aw, ab, (float*)out, rows, d, xout, f.part, f.nsplit, f.stride, f.bias);
+}
 static int ln_rows(vx_engine* e, const float* x, const float* g, const float* b, const float* aw, const float* ab,
                    void* out, int rows, int d, float* xout = nullptr, Fold f = Fold()) {
-  // d <= 1024 in the engine (vx_create): 4 float4 per lane
-  if (e->bf16) layernorm_rows_kernel<bf16, 4><<<(rows + 3) / 4, 256, 0, e->es>>>(x, g, b, aw, ab, (bf16*)out, rows, d, xout, f.part, f.nsplit, f.stride, f.bias);
-  else layernorm_rows_kernel<float, 4><<<(rows + 3) / 4, 256, 0, e->es>>>(x, g, b, aw, ab, (float*)out, rows, d, xout, f.part, f.nsplit, f.stride, f.bias);
+  ln_rows_launch(e->bf16, x, g, b, aw, ab, out, rows, d, xout, f, e->es);
   return VX_OK;
 }
 // fp32 linear layer on rows (prenets keep fp32 weights in every precision mode): C = [relu](A W^T + b)
@@ -1049,6 +1054,23 @@ static int split_for(int K) {  // K slices of the split-K GEMMs: a multiple of t
   for (int sp = 4; sp > 1; sp >>= 1)
     if (K % (64 * sp) == 0) return sp;
   return 1;
+}
+
+// The split-K plan of a row stack over M rows of width d.  splitk: the two N = d GEMMs of a layer (out-projection, FFN2) may
+// write fp32 slabs that the next LayerNorm folds (`eligible`: what the engine and the call decide - bf16 MFMA rows, no text
+// memory, no MXFP8, M within the slab buffer); sp_d / sp_ff: their K slices (1 = no slabs, residual add in the GEMM epilogue):
+// the largest of 4 / 2 / 1 that keeps (128^2 tiles) x slices within one round of the chip's CUs - at 1025 rows 72 tiles x 4
+// slices were 288 workgroups, i.e. two rounds, and four slabs for the next LayerNorm to fold (A/B on one box: NAR 7 stages
+// 9.38 ms with 4 / 4 slices, 8.97 ms with 2 / 2; the 272-row prefill is fastest with 4 / 4: 0.91 vs 0.99 ms)
+struct RowsPlan { bool splitk; int sp_d, sp_ff; };
+static RowsPlan rows_plan(bool eligible, int M, int d, int num_cu) {
+  auto fit = [&](int K) {
+    const long long tiles = (long long)((M + 127) / 128) * (d / 128);
+    for (int sp = split_for(K); sp > 1; sp >>= 1)
+      if (tiles * sp <= num_cu) return sp;
+    return 1;
+  };
+  return RowsPlan{eligible && M < 4096 && d % 128 == 0 && d >= 128, fit(d), fit(4 * d)};
 }
 
 static bool use_mfma(const vx_engine* e);
@@ -1174,21 +1196,12 @@ static int run_stack(vx_engine* e, const std::vector<LayerW>& layers, int M, int
   // split over 2-4 workgroups per tile, every slice writes an fp32 slab, and the LayerNorm that follows the GEMM anyway
   // adds bias + slabs to x in a fixed order.  Larger M (batched rows) has enough tiles and adds in the GEMM epilogue.
   // Not with a text memory: the VALL-F stack is a parity path, and slabs would change its bf16 summation order.
-  const bool splitk = !cross && use_mfma(e) && M < 4096 && M <= e->slab_rows && d % 128 == 0 && d >= 128 && !mx_on(e, ada_stage, M, d);
+  const RowsPlan plan = rows_plan(!cross && use_mfma(e) && M <= e->slab_rows && !mx_on(e, ada_stage, M, d), M, d, e->num_cu);
+  const bool splitk = plan.splitk;
   const bool mx = mx_on(e, ada_stage, M, d);
   const bool tg = time_gemms() && ada_stage >= 0;  // NAR stages only (the cross-attention block is not timed)
   const size_t sstride = (size_t)M * d;
-  // K slices of the out-projection / FFN2 (1 = no slabs, residual add in the GEMM epilogue): the largest of 4 / 2 / 1 that keeps
-  // (128^2 tiles) x slices within one round of the chip's CUs - at 1025 rows 72 tiles x 4 slices were 288 workgroups, i.e. two
-  // rounds, and four slabs for the next LayerNorm to fold (A/B on one box: NAR 7 stages 9.38 ms with 4 / 4 slices, 8.97 ms with
-  // 2 / 2; the 272-row prefill is fastest with 4 / 4: 0.91 vs 0.99 ms)
-  auto fit = [&](int K) {
-    const long long tiles = (long long)((M + 127) / 128) * (d / 128);
-    for (int sp = split_for(K); sp > 1; sp >>= 1)
-      if (tiles * sp <= e->num_cu) return sp;
-    return 1;
-  };
-  const int sp_d = fit(d), sp_ff = fit(4 * d);
+  const int sp_d = plan.sp_d, sp_ff = plan.sp_ff;  // K slices of the out-projection / FFN2 (rows_plan)
   Fold pend;  // split-K slabs of the GEMM that closed the previous block, folded by the next norm (or the trailing fold pass)
   // The norm in front of block k of layer li (front_site) into Hn, folding `pend`; post-norm also writes x = norm(x).  Post-norm
   // layer 0 casts x as it is.  MXFP8 (pre-norm, no slabs): the LayerNorm quantises its own row into Hn8 / SHn.
@@ -3110,6 +3123,59 @@ extern "C" int vx_op_gemm_rows(int32_t form, const void* A, const void* Wp, cons
                          (bf16*)vt, vt_n0, vt_ld))
     return fail(VX_ERR_UNSUPPORTED, "gemm_rows: no kernel instance");
   HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// The split-K launch of the row path's N = d GEMMs on caller data (mfma_gemm_partial, as run_stack calls it): slab z (M, N) fp32 =
+// A[:, z K / splits : (z + 1) K / splits] . W[:, same]^T.
+extern "C" int vx_op_gemm_partial(const void* A, const void* Wp, float* slabs, int32_t M, int32_t N, int32_t K, int32_t splits,
+                                  void* stream) {
+  if (!A || !Wp || !slabs || M < 1) return fail(VX_ERR_ARG, "gemm_partial: null operand or M %d < 1", M);
+  if (N < 128 || N % 128) return fail(VX_ERR_UNSUPPORTED, "gemm_partial: N %d (a multiple of the 128-wide tile)", N);
+  if (splits != 1 && splits != 2 && splits != 4) return fail(VX_ERR_UNSUPPORTED, "gemm_partial: splits %d (1, 2 or 4)", splits);
+  if (K < 64 * splits || K % (64 * splits)) return fail(VX_ERR_UNSUPPORTED, "gemm_partial: K %d (a multiple of 64 per slice, %d slices)", K, splits);
+  if ((long long)((M + 127) / 128) > 65535) return fail(VX_ERR_UNSUPPORTED, "gemm_partial: M %d (more than 65535 row tiles)", M);
+  VXC(mfma_gemm_partial((const bf16*)A, (const bf16*)Wp, slabs, M, N, K, splits, (hipStream_t)stream));
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// layernorm_rows_kernel<OT, 4> with every optional argument (the launch ln_rows makes): fold of split-K slabs, xout, fold only.
+extern "C" int vx_op_ln_fold(int32_t prec, float* x, const float* part, int32_t nsplit, int64_t part_stride, const float* pbias,
+                             const float* gamma, const float* beta, const float* ada_w, const float* ada_b, void* out, float* xout,
+                             int32_t rows, int32_t d, void* stream) {
+  if (d < 4 || d % 4 || d > 1024) return fail(VX_ERR_UNSUPPORTED, "ln_fold: d %d (a multiple of 4 in [4, 1024])", d);
+  if (prec != VX_PREC_BF16 && prec != VX_PREC_F32) return fail(VX_ERR_ARG, "ln_fold: prec %d", prec);
+  if (!x || rows < 1) return fail(VX_ERR_ARG, "ln_fold: null x or rows %d < 1", rows);
+  if (part) {
+    if (nsplit < 1 || nsplit > 4) return fail(VX_ERR_ARG, "ln_fold: nsplit %d outside [1, 4]", nsplit);
+    if (!pbias) return fail(VX_ERR_ARG, "ln_fold: part needs pbias");
+    if (nsplit > 1 && part_stride < (int64_t)rows * d) return fail(VX_ERR_ARG, "ln_fold: part_stride %lld < rows d", (long long)part_stride);
+  }
+  if (!out && !part) return fail(VX_ERR_ARG, "ln_fold: the fold-only pass (out == NULL) needs part");
+  if (!out && xout) return fail(VX_ERR_ARG, "ln_fold: xout needs out");
+  if (out && (!gamma || !beta)) return fail(VX_ERR_ARG, "ln_fold: out needs gamma and beta");
+  if ((ada_w == nullptr) != (ada_b == nullptr)) return fail(VX_ERR_ARG, "ln_fold: ada_w and ada_b come together");
+  Fold f;
+  if (part) { f.part = part; f.nsplit = nsplit; f.stride = (size_t)part_stride; f.bias = pbias; }
+  ln_rows_launch(prec == VX_PREC_BF16, x, gamma, beta, ada_w, ada_b, out, rows, d, xout, f, (hipStream_t)stream);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// {splitk, sp_d, sp_ff} as run_stack chooses them (rows_plan) for a bf16, head_dim 64 stack without MXFP8 and without a text
+// memory, over M rows (within the engine's capacity) of width d.  num_cu <= 0: the current device's CU count; with an explicit
+// count no HIP call is made.
+extern "C" int vx_op_rows_plan(int32_t M, int32_t d, int32_t num_cu, int32_t* out) {
+  if (M < 1 || d < 1 || !out) return fail(VX_ERR_ARG, "rows_plan: M %d, d %d or null out", M, d);
+  int cu = num_cu;
+  if (cu <= 0) {
+    int dev = 0;
+    HIPC(hipGetDevice(&dev));
+    HIPC(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  const RowsPlan p = rows_plan(true, M, d, cu);
+  out[0] = p.splitk ? 1 : 0; out[1] = p.sp_d; out[2] = p.sp_ff;
   return VX_OK;
 }
 

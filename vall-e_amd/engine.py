@@ -106,6 +106,10 @@ _SIGS = {
     "vx_op_gemv": (C.c_int, [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "vx_op_gemm": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]),
     "vx_op_gemm_rows": (C.c_int, [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "vx_op_gemm_partial": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
+    "vx_op_ln_fold": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32, C.c_int32,
+                      C.c_void_p]),
+    "vx_op_rows_plan": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int32)]),
     "vx_op_gemm_mx": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p] * 3),
     "vx_op_layernorm_mx": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_void_p]),
     "vx_op_attention": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
@@ -699,6 +703,35 @@ def op_gemm_rows(A, W, bias, relu=False, resid=None, vt_cols=0):
     _check(lib.vx_op_gemm_rows(0, _ptr(A), _ptr(W), _ptr(bias), _ptr(Cm), M, N, K, int(relu), _ptr(vt), N - vt_cols, ld,
                                current_stream_ptr(A.device)))
     return Cm, vt
+
+
+def op_gemm_partial(A, W, slabs, splits, M=None):
+    """The row path's split-K launch (vx_op_gemm_partial) on bf16 A (>= M, K), W (N, K): slab z of the fp32 buffer `slabs` (its
+    first splits * M * N elements, as (splits, M, N)) = A[:M, z K / splits : (z + 1) K / splits] @ W[:, same].T"""
+    lib = load_library()
+    M = A.shape[0] if M is None else M
+    K, N = A.shape[1], W.shape[0]
+    assert slabs.dtype == torch.float32 and slabs.numel() >= splits * M * N and A.shape[0] >= M and W.shape[1] == K
+    _check(lib.vx_op_gemm_partial(_ptr(A), _ptr(W), _ptr(slabs), M, N, K, splits, current_stream_ptr(A.device)))
+    return slabs
+
+
+def op_ln_fold(x, rows, d, out=None, gamma=None, beta=None, ada_w=None, ada_b=None, part=None, nsplit=0, part_stride=0, pbias=None,
+               xout=None, out_dtype=torch.bfloat16):
+    """layernorm_rows_kernel with its optional arguments (vx_op_ln_fold) on the first `rows` rows of fp32 x (>= rows, d), in place:
+    part / nsplit / part_stride / pbias: the split-K fold; out (fp32 or bf16): the normalised rows (None: fold only, on the
+    kernel instance of out_dtype); xout: where the fp32 normalised rows also go (may be x itself)."""
+    lib = load_library()
+    prec = _prec(out) if out is not None else (VX_PREC_BF16 if out_dtype == torch.bfloat16 else VX_PREC_F32)
+    _check(lib.vx_op_ln_fold(prec, _ptr(x), _ptr(part), nsplit, part_stride, _ptr(pbias), _ptr(gamma), _ptr(beta), _ptr(ada_w),
+                             _ptr(ada_b), _ptr(out), _ptr(xout), rows, d, current_stream_ptr(x.device)))
+
+
+def op_rows_plan(M, d, num_cu=0):
+    """(splitk, sp_d, sp_ff) of the row stack over M rows of width d (vx_op_rows_plan); num_cu = 0: the current device's count"""
+    out = (C.c_int32 * 3)()
+    _check(load_library().vx_op_rows_plan(M, d, num_cu, out))
+    return tuple(out)
 
 
 def op_gemm_mx(A, W, bias=None, relu=False, out_mx=False, return_quant=False):
