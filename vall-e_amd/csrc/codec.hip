@@ -1,58 +1,24 @@
 // EnCodec-24 kHz decoder and encoder behind the C ABI (include/vallex.h, vx_codec_*): weights, workspace and the launch
 // sequences of codec_kernels.hpp.  A handle of its own: the codec has its own weights and lifetime and runs without a VALL-E engine.
-// At the end of the file: the sample-rate converter in front of the encoder (vx_resampler_*), a handle without weights.
+// At the end of the file: the sample-rate converter in front of the encoder (vx_resampler_*), a handle without weights, its ragged
+// calls staged through CallStage (host.hpp); the codec handle keeps its own stream protocol (ev_in / ev_out / ev_copy).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "../../include/vallex.h"
+#include "host.hpp"
 #include "codec_kernels.hpp"
 
 using namespace vx;
 
-extern "C" void vx_internal_set_error(const char* msg);  // engine.hip: the message vx_last_error() returns
-
-static int cfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  vx_internal_set_error(buf);
-  return code;
-}
-#define CHIPC(expr)                                                                                                    \
-  do {                                                                                                                 \
-    hipError_t e_ = (expr);                                                                                            \
-    if (e_ != hipSuccess)                                                                                              \
-      return cfail(VX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);              \
-  } while (0)
-#define CVXC(expr)              \
-  do {                          \
-    int r_ = (expr);            \
-    if (r_ != VX_OK) return r_; \
-  } while (0)
-
 namespace {
-
-struct CDevGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit CDevGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else if (err == hipSuccess) prev = -1;
-  }
-  ~CDevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 struct HostW {
   std::vector<int64_t> shape;
@@ -83,8 +49,8 @@ std::vector<float> pack_convtr(const float* w, int Cin, int Cout, int s) {
 }
 
 int upload(const std::vector<float>& h, float** d) {
-  CHIPC(hipMalloc((void**)d, h.size() * sizeof(float) + 16));
-  CHIPC(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIPC(hipMalloc((void**)d, h.size() * sizeof(float) + 16));
+  HIPC(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
   return VX_OK;
 }
 
@@ -102,7 +68,7 @@ int launch_gemm(CodecGemmArgs a, hipStream_t s) {
     if (vec) codec_gemm_rows<2, 2, true><<<g, 256, 0, s>>>(a);
     else codec_gemm_rows<2, 2, false><<<g, 256, 0, s>>>(a);
   }
-  CHIPC(hipGetLastError());
+  HIPC(hipGetLastError());
   return VX_OK;
 }
 
@@ -111,7 +77,7 @@ int run_conv(const float* x, const float* wp, const float* bias, float* out, lon
              const int* seg, int nseg, int rate, hipStream_t s) {
   if (cout == 1 && elu) {
     if (M > 0) codec_conv_out<<<(unsigned)((M + 255) / 256), 256, 0, s>>>(x, wp, bias, out, M, cin, k, seg, nseg, rate);
-    CHIPC(hipGetLastError());
+    HIPC(hipGetLastError());
     return VX_OK;
   }
   CodecGemmArgs a{};
@@ -136,7 +102,7 @@ int run_conv_in(const float* x, const float* w, const float* bias, float* out, l
                 hipStream_t s) {
   const long n = M * cout;
   if (n > 0) codec_conv_in<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(x, w, bias, out, M, cout, k, seg, nseg);
-  CHIPC(hipGetLastError());
+  HIPC(hipGetLastError());
   return VX_OK;
 }
 
@@ -160,7 +126,7 @@ int run_conv_strided(const float* x, const float* wp, const float* bias, float* 
     if (vec) codec_gemm_rows<2, 2, true, true><<<g, 256, 0, s>>>(a);
     else codec_gemm_rows<2, 2, false, true><<<g, 256, 0, s>>>(a);
   }
-  CHIPC(hipGetLastError());
+  HIPC(hipGetLastError());
   return VX_OK;
 }
 
@@ -179,7 +145,7 @@ std::vector<float> codebook_sq(const float* cb, size_t n, int D) {
 
 int run_rvq_encode(const float* emb, const float* cb, const float* cb_sq, int* codes, long rows, int n_q, int S, int D, hipStream_t s) {
   if (rows > 0) codec_rvq_encode<<<(unsigned)((rows + CODEC_RVQ_ROWS - 1) / CODEC_RVQ_ROWS), 256, 0, s>>>(emb, cb, cb_sq, codes, rows, n_q, S, D);
-  CHIPC(hipGetLastError());
+  HIPC(hipGetLastError());
   return VX_OK;
 }
 
@@ -213,7 +179,7 @@ int run_lstm(const LstmDev& w, const float* x, float* gin, float* h0, float* h1,
   g.part[0] = CodecPart{x, H, 1, CODEC_PAD_ZERO, 0};
   g.nparts = 1;
   g.W = w.wih0; g.bias = w.b0; g.out = gin; g.M = rows; g.N = 4 * H; g.K = H; g.seg = seg_dev; g.nseg = nseg; g.rate = 1;
-  CVXC(launch_gemm(g, s));
+  VXC(launch_gemm(g, s));
   CodecLstmArgs a{};
   a.gin0 = gin; a.whh0 = w.whh0; a.w1 = w.w1; a.b1 = w.b1; a.xin = x; a.h0 = h0; a.h1 = h1; a.y = y; a.c0 = c0; a.c1 = c1;
   a.seg = seg_dev; a.nseg = nseg; a.H = H; a.layers = layers;
@@ -221,23 +187,23 @@ int run_lstm(const LstmDev& w, const float* x, float* gin, float* h0, float* h1,
   const int steps = Tmax + layers - 1;
   if (!chain) {
     for (int st = 0; st < steps; ++st) launch_lstm_step(a, H, grid, st, s);
-    CHIPC(hipGetLastError());
+    HIPC(hipGetLastError());
     return VX_OK;
   }
   if (!*chain) {
     a.meta = meta;
     a.nseg = 0;
     hipGraph_t graph = nullptr;
-    CHIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     for (int st = 0; st < CODEC_LSTM_CHAIN; ++st) launch_lstm_step(a, H, grid, st, s);
     codec_lstm_advance<<<1, 64, 0, s>>>(meta, CODEC_LSTM_CHAIN);
     const hipError_t ce = hipStreamEndCapture(s, &graph);
-    if (ce != hipSuccess) return cfail(VX_ERR_HIP, "capturing the LSTM chain failed: %s", hipGetErrorString(ce));
+    if (ce != hipSuccess) return fail(VX_ERR_HIP, "capturing the LSTM chain failed: %s", hipGetErrorString(ce));
     const hipError_t ie = hipGraphInstantiate(chain, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
-    if (ie != hipSuccess) { *chain = nullptr; return cfail(VX_ERR_HIP, "instantiating the LSTM chain failed: %s", hipGetErrorString(ie)); }
+    if (ie != hipSuccess) { *chain = nullptr; return fail(VX_ERR_HIP, "instantiating the LSTM chain failed: %s", hipGetErrorString(ie)); }
   }
-  for (int st = 0; st < steps; st += CODEC_LSTM_CHAIN) CHIPC(hipGraphLaunch(*chain, s));
+  for (int st = 0; st < steps; st += CODEC_LSTM_CHAIN) HIPC(hipGraphLaunch(*chain, s));
   return VX_OK;
 }
 
@@ -246,9 +212,9 @@ int pack_lstm(const float* const* wih, const float* const* whh, const float* con
               LstmDev* d) {
   std::vector<float> b0(4 * H);
   for (int i = 0; i < 4 * H; ++i) b0[i] = bih[0][i] + bhh[0][i];
-  CVXC(upload(std::vector<float>(wih[0], wih[0] + (size_t)4 * H * H), &d->wih0));
-  CVXC(upload(std::vector<float>(whh[0], whh[0] + (size_t)4 * H * H), &d->whh0));
-  CVXC(upload(b0, &d->b0));
+  VXC(upload(std::vector<float>(wih[0], wih[0] + (size_t)4 * H * H), &d->wih0));
+  VXC(upload(std::vector<float>(whh[0], whh[0] + (size_t)4 * H * H), &d->whh0));
+  VXC(upload(b0, &d->b0));
   if (layers == 2) {
     std::vector<float> w1((size_t)4 * H * 2 * H), b1(4 * H);
     for (int n = 0; n < 4 * H; ++n) {
@@ -256,8 +222,8 @@ int pack_lstm(const float* const* wih, const float* const* whh, const float* con
       memcpy(&w1[(size_t)n * 2 * H + H], whh[1] + (size_t)n * H, H * sizeof(float));
       b1[n] = bih[1][n] + bhh[1][n];
     }
-    CVXC(upload(w1, &d->w1));
-    CVXC(upload(b1, &d->b1));
+    VXC(upload(w1, &d->w1));
+    VXC(upload(b1, &d->b1));
   }
   return VX_OK;
 }
@@ -267,10 +233,10 @@ void free_lstm(LstmDev& d) {
 }
 
 int check_segs(const int32_t* seg, int nseg) {
-  if (!seg || nseg < 1 || nseg > CODEC_MAX_SEG) return cfail(VX_ERR_ARG, "segments: 1..%d expected, got %d", CODEC_MAX_SEG, nseg);
-  if (seg[0] != 0) return cfail(VX_ERR_ARG, "segment starts begin at 0");
+  if (!seg || nseg < 1 || nseg > CODEC_MAX_SEG) return fail(VX_ERR_ARG, "segments: 1..%d expected, got %d", CODEC_MAX_SEG, nseg);
+  if (seg[0] != 0) return fail(VX_ERR_ARG, "segment starts begin at 0");
   for (int i = 0; i < nseg; ++i)
-    if (seg[i + 1] <= seg[i]) return cfail(VX_ERR_ARG, "segment %d is empty or starts are not increasing", i);
+    if (seg[i + 1] <= seg[i]) return fail(VX_ERR_ARG, "segment %d is empty or starts are not increasing", i);
   return VX_OK;
 }
 
@@ -379,32 +345,32 @@ static std::map<std::string, std::vector<int64_t>> codec_expected(const vx_codec
 }
 
 extern "C" int vx_codec_create(const vx_codec_config* cfg, vx_codec** out) {
-  if (!cfg || !out) return cfail(VX_ERR_ARG, "vx_codec_create: null argument");
+  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_codec_create: null argument");
   if (cfg->struct_size != (int32_t)sizeof(vx_codec_config))
-    return cfail(VX_ERR_ARG, "vx_codec_config.struct_size %d != %d", cfg->struct_size, (int)sizeof(vx_codec_config));
+    return fail(VX_ERR_ARG, "vx_codec_config.struct_size %d != %d", cfg->struct_size, (int)sizeof(vx_codec_config));
   const vx_codec_config& c = *cfg;
   if (c.hidden < 1 || c.filters < 1 || c.codebook_size < 1 || c.codebook_dim < 1 || c.n_codebooks < 1 || c.max_frames < 1 ||
       c.max_batch < 1 || c.kernel < 1 || c.last_kernel < 1 || c.res_kernel < 1 || c.lstm_layers < 0 || c.device < 0 ||
       (c.flags & ~(VX_CODEC_LSTM_GRAPH | VX_CODEC_ENCODER)))
-    return cfail(VX_ERR_ARG, "vx_codec_config: sizes must be positive and flags known");
+    return fail(VX_ERR_ARG, "vx_codec_config: sizes must be positive and flags known");
   for (int i = 0; i < 4; ++i)
-    if (c.ratios[i] < 1) return cfail(VX_ERR_ARG, "vx_codec_config.ratios[%d] = %d", i, c.ratios[i]);
+    if (c.ratios[i] < 1) return fail(VX_ERR_ARG, "vx_codec_config.ratios[%d] = %d", i, c.ratios[i]);
   const int W = 16 * c.filters;
-  if (c.codebook_dim != c.hidden) return cfail(VX_ERR_UNSUPPORTED, "codebook_dim %d != hidden %d", c.codebook_dim, c.hidden);
-  if (c.lstm_layers < 1 || c.lstm_layers > 2) return cfail(VX_ERR_UNSUPPORTED, "lstm_layers %d: the step kernel serves 1 or 2", c.lstm_layers);
-  if (!lstm_width_ok(W)) return cfail(VX_ERR_UNSUPPORTED, "LSTM width 16 * filters = %d: the step kernel serves 64, 128, 256, 512", W);
-  if (c.kernel > 15 || c.last_kernel > 15 || c.res_kernel > 15) return cfail(VX_ERR_UNSUPPORTED, "kernel sizes above 15");
-  if (c.n_codebooks > CODEC_MAX_Q) return cfail(VX_ERR_UNSUPPORTED, "n_codebooks %d > %d", c.n_codebooks, CODEC_MAX_Q);
-  if (c.max_batch > CODEC_MAX_SEG) return cfail(VX_ERR_UNSUPPORTED, "max_batch %d > %d", c.max_batch, CODEC_MAX_SEG);
+  if (c.codebook_dim != c.hidden) return fail(VX_ERR_UNSUPPORTED, "codebook_dim %d != hidden %d", c.codebook_dim, c.hidden);
+  if (c.lstm_layers < 1 || c.lstm_layers > 2) return fail(VX_ERR_UNSUPPORTED, "lstm_layers %d: the step kernel serves 1 or 2", c.lstm_layers);
+  if (!lstm_width_ok(W)) return fail(VX_ERR_UNSUPPORTED, "LSTM width 16 * filters = %d: the step kernel serves 64, 128, 256, 512", W);
+  if (c.kernel > 15 || c.last_kernel > 15 || c.res_kernel > 15) return fail(VX_ERR_UNSUPPORTED, "kernel sizes above 15");
+  if (c.n_codebooks > CODEC_MAX_Q) return fail(VX_ERR_UNSUPPORTED, "n_codebooks %d > %d", c.n_codebooks, CODEC_MAX_Q);
+  if (c.max_batch > CODEC_MAX_SEG) return fail(VX_ERR_UNSUPPORTED, "max_batch %d > %d", c.max_batch, CODEC_MAX_SEG);
   long hop = 1;
   for (int i = 0; i < 4; ++i) hop *= c.ratios[i];
-  if (hop * (long)c.max_frames * c.max_batch >= (1L << 40)) return cfail(VX_ERR_UNSUPPORTED, "capacity too large");
+  if (hop * (long)c.max_frames * c.max_batch >= (1L << 40)) return fail(VX_ERR_UNSUPPORTED, "capacity too large");
   if (c.flags & VX_CODEC_ENCODER) {
     if (!rvq_shape_ok(c.codebook_size, c.codebook_dim))
-      return cfail(VX_ERR_UNSUPPORTED, "encoder: codebook %d x %d: the search kernel serves sizes in multiples of 32 and dims in multiples of 8 up to %d",
+      return fail(VX_ERR_UNSUPPORTED, "encoder: codebook %d x %d: the search kernel serves sizes in multiples of 32 and dims in multiples of 8 up to %d",
                    c.codebook_size, c.codebook_dim, CODEC_RVQ_MAX_D);
-    if (c.filters % 2) return cfail(VX_ERR_UNSUPPORTED, "encoder: filters %d is odd", c.filters);
-    if (hop * (long)c.max_frames >= (1L << 31)) return cfail(VX_ERR_UNSUPPORTED, "encoder: max_frames * hop samples exceed int32");
+    if (c.filters % 2) return fail(VX_ERR_UNSUPPORTED, "encoder: filters %d is odd", c.filters);
+    if (hop * (long)c.max_frames >= (1L << 31)) return fail(VX_ERR_UNSUPPORTED, "encoder: max_frames * hop samples exceed int32");
   }
   vx_codec* e = new vx_codec();
   e->cfg = c;
@@ -438,7 +404,7 @@ static void codec_free_device(vx_codec* e) {
 extern "C" void vx_codec_destroy(vx_codec* e) {
   if (!e) return;
   if (e->allocated) {
-    CDevGuard g(e->cfg.device);
+    DevGuard g(e->cfg.device);
     if (e->own) (void)hipStreamSynchronize(e->own);
     codec_free_device(e);
   }
@@ -446,35 +412,35 @@ extern "C" void vx_codec_destroy(vx_codec* e) {
 }
 
 extern "C" int vx_codec_set_weight(vx_codec* e, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
-  if (!e || !key || !data || !shape) return cfail(VX_ERR_ARG, "vx_codec_set_weight: null argument");
-  if (e->finalized) return cfail(VX_ERR_STATE, "vx_codec_set_weight after vx_codec_finalize");
+  if (!e || !key || !data || !shape) return fail(VX_ERR_ARG, "vx_codec_set_weight: null argument");
+  if (e->finalized) return fail(VX_ERR_STATE, "vx_codec_set_weight after vx_codec_finalize");
   auto it = e->w.find(key);
-  if (it == e->w.end()) return cfail(VX_ERR_WEIGHTS, "unknown key %s", key);
+  if (it == e->w.end()) return fail(VX_ERR_WEIGHTS, "unknown key %s", key);
   HostW& t = it->second;
   bool same = (size_t)ndim == t.shape.size();
   size_t n = 1;
   for (int i = 0; same && i < ndim; ++i) { same = shape[i] == t.shape[i]; n *= (size_t)shape[i]; }
-  if (!same) return cfail(VX_ERR_WEIGHTS, "wrong shape for %s", key);
+  if (!same) return fail(VX_ERR_WEIGHTS, "wrong shape for %s", key);
   t.v.assign(data, data + n);
   t.set = true;
   return VX_OK;
 }
 
 static int alloc_f(float** p, size_t n) {
-  CHIPC(hipMalloc((void**)p, n * sizeof(float) + 16));
+  HIPC(hipMalloc((void**)p, n * sizeof(float) + 16));
   return VX_OK;
 }
 
 extern "C" int vx_codec_finalize(vx_codec* e) {
-  if (!e) return cfail(VX_ERR_ARG, "vx_codec_finalize: null handle");
+  if (!e) return fail(VX_ERR_ARG, "vx_codec_finalize: null handle");
   if (e->finalized) return VX_OK;
-  if (e->failed) return cfail(VX_ERR_STATE, "vx_codec_finalize failed earlier on this handle: destroy it and create a new one");
+  if (e->failed) return fail(VX_ERR_STATE, "vx_codec_finalize failed earlier on this handle: destroy it and create a new one");
   for (auto& kv : e->w)
-    if (!kv.second.set) return cfail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
+    if (!kv.second.set) return fail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
   const vx_codec_config& c = e->cfg;
   e->failed = true;     // until the last statement: a finalize that stops at a HIP error leaves a handle that refuses further use
-  CDevGuard g(c.device);
-  CHIPC(g.err);
+  DevGuard g(c.device);
+  HIPC(g.err);
   e->allocated = true;  // from here vx_codec_destroy frees what was allocated
   const int W = e->W;
   char k[128], k2[128];
@@ -485,10 +451,10 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
       snprintf(k, sizeof k, "quantizer.layers.%d.codebook.embed", q);
       memcpy(&cb[(size_t)q * c.codebook_size * c.codebook_dim], host(k).data(), host(k).size() * sizeof(float));
     }
-    CVXC(upload(cb, &e->cb));
+    VXC(upload(cb, &e->cb));
   }
-  CVXC(upload(pack_conv(host("decoder.layers.0.conv.weight").data(), W, c.hidden, c.kernel), &e->c0_w));
-  CVXC(upload(host("decoder.layers.0.conv.bias"), &e->c0_b));
+  VXC(upload(pack_conv(host("decoder.layers.0.conv.weight").data(), W, c.hidden, c.kernel), &e->c0_w));
+  VXC(upload(host("decoder.layers.0.conv.bias"), &e->c0_b));
   {
     const float *wih[2] = {}, *whh[2] = {}, *bih[2] = {}, *bhh[2] = {};
     for (int l = 0; l < c.lstm_layers; ++l) {
@@ -497,7 +463,7 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
       snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_ih_l%d", l); bih[l] = host(k).data();
       snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_hh_l%d", l); bhh[l] = host(k).data();
     }
-    CVXC(pack_lstm(wih, whh, bih, bhh, W, c.lstm_layers, &e->lstm));
+    VXC(pack_lstm(wih, whh, bih, bhh, W, c.lstm_layers, &e->lstm));
   }
   int ch = W;
   long rate = 1, per_frame = 0;
@@ -507,19 +473,19 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
     const int up = 3 + 3 * i, res = 4 + 3 * i, r = c.ratios[i];
     st.cin = ch; st.cout = ch / 2; st.stride = r;
     snprintf(k, sizeof k, "decoder.layers.%d.conv.weight", up);
-    CVXC(upload(pack_convtr(host(k).data(), ch, ch / 2, r), &st.up_w));
+    VXC(upload(pack_convtr(host(k).data(), ch, ch / 2, r), &st.up_w));
     snprintf(k, sizeof k, "decoder.layers.%d.conv.bias", up);
     std::vector<float> rep((size_t)r * (ch / 2));
     for (int p = 0; p < r; ++p) memcpy(&rep[(size_t)p * (ch / 2)], host(k).data(), (ch / 2) * sizeof(float));
-    CVXC(upload(rep, &st.up_b));
+    VXC(upload(rep, &st.up_b));
     ch /= 2;
     rate *= r;
     per_frame = std::max(per_frame, rate * ch);
     const int hd = ch / 2;
     snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.weight", res);
-    CVXC(upload(pack_conv(host(k).data(), hd, ch, c.res_kernel), &st.c3_w));
+    VXC(upload(pack_conv(host(k).data(), hd, ch, c.res_kernel), &st.c3_w));
     snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.bias", res);
-    CVXC(upload(host(k), &st.c3_b));
+    VXC(upload(host(k), &st.c3_b));
     snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.weight", res);
     snprintf(k2, sizeof k2, "decoder.layers.%d.shortcut.conv.weight", res);
     std::vector<float> mix((size_t)ch * (hd + ch)), mb(ch);
@@ -530,11 +496,11 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
     snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.bias", res);
     snprintf(k2, sizeof k2, "decoder.layers.%d.shortcut.conv.bias", res);
     for (int n = 0; n < ch; ++n) mb[n] = host(k)[n] + host(k2)[n];
-    CVXC(upload(mix, &st.mix_w));
-    CVXC(upload(mb, &st.mix_b));
+    VXC(upload(mix, &st.mix_w));
+    VXC(upload(mb, &st.mix_b));
   }
-  CVXC(upload(pack_conv(host("decoder.layers.15.conv.weight").data(), 1, ch, c.last_kernel), &e->last_w));
-  CVXC(upload(host("decoder.layers.15.conv.bias"), &e->last_b));
+  VXC(upload(pack_conv(host("decoder.layers.15.conv.weight").data(), 1, ch, c.last_kernel), &e->last_w));
+  VXC(upload(host("decoder.layers.15.conv.bias"), &e->last_b));
   e->enc = (c.flags & VX_CODEC_ENCODER) != 0;
   if (e->enc) {
     {
@@ -544,10 +510,10 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
         const std::vector<float> one = codebook_sq(host(k).data(), (size_t)c.codebook_size, c.codebook_dim);
         sq.insert(sq.end(), one.begin(), one.end());
       }
-      CVXC(upload(sq, &e->cb_sq));
+      VXC(upload(sq, &e->cb_sq));
     }
-    CVXC(upload(pack_conv(host("encoder.layers.0.conv.weight").data(), c.filters, 1, c.kernel), &e->e0_w));
-    CVXC(upload(host("encoder.layers.0.conv.bias"), &e->e0_b));
+    VXC(upload(pack_conv(host("encoder.layers.0.conv.weight").data(), c.filters, 1, c.kernel), &e->e0_w));
+    VXC(upload(host("encoder.layers.0.conv.bias"), &e->e0_b));
     int ec = c.filters;
     e->estages.resize(4);
     for (int i = 0; i < 4; ++i) {
@@ -555,9 +521,9 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
       const int res = 1 + 3 * i, dn = 3 + 3 * i, hd = ec / 2;
       st.c = ec; st.stride = c.ratios[3 - i];
       snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.weight", res);
-      CVXC(upload(pack_conv(host(k).data(), hd, ec, c.res_kernel), &st.c3_w));
+      VXC(upload(pack_conv(host(k).data(), hd, ec, c.res_kernel), &st.c3_w));
       snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.bias", res);
-      CVXC(upload(host(k), &st.c3_b));
+      VXC(upload(host(k), &st.c3_b));
       snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.weight", res);
       snprintf(k2, sizeof k2, "encoder.layers.%d.shortcut.conv.weight", res);
       std::vector<float> mix((size_t)ec * (hd + ec)), mb(ec);
@@ -568,12 +534,12 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
       snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.bias", res);
       snprintf(k2, sizeof k2, "encoder.layers.%d.shortcut.conv.bias", res);
       for (int n = 0; n < ec; ++n) mb[n] = host(k)[n] + host(k2)[n];
-      CVXC(upload(mix, &st.mix_w));
-      CVXC(upload(mb, &st.mix_b));
+      VXC(upload(mix, &st.mix_w));
+      VXC(upload(mb, &st.mix_b));
       snprintf(k, sizeof k, "encoder.layers.%d.conv.weight", dn);
-      CVXC(upload(pack_conv(host(k).data(), 2 * ec, ec, 2 * st.stride), &st.dn_w));
+      VXC(upload(pack_conv(host(k).data(), 2 * ec, ec, 2 * st.stride), &st.dn_w));
       snprintf(k, sizeof k, "encoder.layers.%d.conv.bias", dn);
-      CVXC(upload(host(k), &st.dn_b));
+      VXC(upload(host(k), &st.dn_b));
       ec *= 2;
     }
     {
@@ -584,10 +550,10 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
         snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_ih_l%d", l); bih[l] = host(k).data();
         snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_hh_l%d", l); bhh[l] = host(k).data();
       }
-      CVXC(pack_lstm(wih, whh, bih, bhh, W, c.lstm_layers, &e->elstm));
+      VXC(pack_lstm(wih, whh, bih, bhh, W, c.lstm_layers, &e->elstm));
     }
-    CVXC(upload(pack_conv(host("encoder.layers.15.conv.weight").data(), c.hidden, W, c.last_kernel), &e->elast_w));
-    CVXC(upload(host("encoder.layers.15.conv.bias"), &e->elast_b));
+    VXC(upload(pack_conv(host("encoder.layers.15.conv.weight").data(), c.hidden, W, c.last_kernel), &e->elast_w));
+    VXC(upload(host("encoder.layers.15.conv.bias"), &e->elast_b));
   }
   for (auto& kv : e->w) std::vector<float>().swap(kv.second.v);  // the host copies are not needed any more
 
@@ -597,34 +563,34 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
   e->chunk_frames = std::min(e->cap_frames, std::max<long>(c.max_frames, 8192));
   e->per_frame = std::max<long>(per_frame, 2 * rate);
   const size_t F = (size_t)e->cap_frames;
-  CVXC(alloc_f(&e->x0, F * c.hidden));
-  CVXC(alloc_f(&e->xc, F * W));
-  CVXC(alloc_f(&e->gin, F * 4 * W));
-  CVXC(alloc_f(&e->h0, F * W));
-  CVXC(alloc_f(&e->h1, F * W));
-  CVXC(alloc_f(&e->y, F * W));
-  CVXC(alloc_f(&e->c0, (size_t)c.max_batch * W));
-  CVXC(alloc_f(&e->c1, (size_t)c.max_batch * W));
+  VXC(alloc_f(&e->x0, F * c.hidden));
+  VXC(alloc_f(&e->xc, F * W));
+  VXC(alloc_f(&e->gin, F * 4 * W));
+  VXC(alloc_f(&e->h0, F * W));
+  VXC(alloc_f(&e->h1, F * W));
+  VXC(alloc_f(&e->y, F * W));
+  VXC(alloc_f(&e->c0, (size_t)c.max_batch * W));
+  VXC(alloc_f(&e->c1, (size_t)c.max_batch * W));
   // encoder: the same three buffers hold its stages (filters channels per sample at most, as the decoder's last stage), plus one
   // row per utterance and stage for the rounded-up row counts
   const size_t slack = e->enc ? (size_t)c.max_batch * W : 0;
-  CVXC(alloc_f(&e->bufA, (size_t)e->chunk_frames * e->per_frame + slack));
-  CVXC(alloc_f(&e->bufB, (size_t)e->chunk_frames * e->per_frame + slack));
-  CVXC(alloc_f(&e->bufH, (size_t)e->chunk_frames * e->per_frame / 2 + slack));
+  VXC(alloc_f(&e->bufA, (size_t)e->chunk_frames * e->per_frame + slack));
+  VXC(alloc_f(&e->bufB, (size_t)e->chunk_frames * e->per_frame + slack));
+  VXC(alloc_f(&e->bufH, (size_t)e->chunk_frames * e->per_frame / 2 + slack));
   e->stage_ints = 2 + F * c.n_codebooks + 3 * (size_t)(c.max_batch + 1);
   if (e->enc) {
     e->stage_ints += 8 * (size_t)(c.max_batch + 1);  // four more row tables per utterance group
-    CVXC(alloc_f(&e->wav, (size_t)e->chunk_frames * rate));
-    CHIPC(hipMalloc((void**)&e->ptrs_dev, (size_t)c.max_batch * sizeof(void*)));
-    CHIPC(hipHostMalloc((void**)&e->ptrs_host, (size_t)c.max_batch * sizeof(void*)));
+    VXC(alloc_f(&e->wav, (size_t)e->chunk_frames * rate));
+    HIPC(hipMalloc((void**)&e->ptrs_dev, (size_t)c.max_batch * sizeof(void*)));
+    HIPC(hipHostMalloc((void**)&e->ptrs_host, (size_t)c.max_batch * sizeof(void*)));
   }
-  CHIPC(hipMalloc((void**)&e->codes_dev, e->stage_ints * sizeof(int)));
-  CHIPC(hipHostMalloc((void**)&e->codes_host, e->stage_ints * sizeof(int)));
-  CHIPC(hipStreamCreateWithFlags(&e->own, hipStreamNonBlocking));
-  CHIPC(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
-  CHIPC(hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming));
-  CHIPC(hipEventCreateWithFlags(&e->ev_copy, hipEventDisableTiming));
-  CHIPC(hipEventRecord(e->ev_copy, e->own));
+  HIPC(hipMalloc((void**)&e->codes_dev, e->stage_ints * sizeof(int)));
+  HIPC(hipHostMalloc((void**)&e->codes_host, e->stage_ints * sizeof(int)));
+  HIPC(hipStreamCreateWithFlags(&e->own, hipStreamNonBlocking));
+  HIPC(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
+  HIPC(hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming));
+  HIPC(hipEventCreateWithFlags(&e->ev_copy, hipEventDisableTiming));
+  HIPC(hipEventRecord(e->ev_copy, e->own));
   e->failed = false;
   e->finalized = true;
   return VX_OK;
@@ -632,33 +598,33 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
 
 extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* codes, const int32_t* T, int32_t n_q,
                                float* const* wav_out, void* stream) {
-  if (!e || !codes || !T || !wav_out) return cfail(VX_ERR_ARG, "vx_codec_decode: null argument");
+  if (!e || !codes || !T || !wav_out) return fail(VX_ERR_ARG, "vx_codec_decode: null argument");
   const vx_codec_config& c = e->cfg;
-  if (n < 1) return cfail(VX_ERR_ARG, "n = %d utterances", n);
-  if (n > c.max_batch) return cfail(VX_ERR_CAPACITY, "n = %d utterances > max_batch %d", n, c.max_batch);
-  if (n_q < 1 || n_q > c.n_codebooks) return cfail(VX_ERR_ARG, "n_q = %d outside [1, %d]", n_q, c.n_codebooks);
+  if (n < 1) return fail(VX_ERR_ARG, "n = %d utterances", n);
+  if (n > c.max_batch) return fail(VX_ERR_CAPACITY, "n = %d utterances > max_batch %d", n, c.max_batch);
+  if (n_q < 1 || n_q > c.n_codebooks) return fail(VX_ERR_ARG, "n_q = %d outside [1, %d]", n_q, c.n_codebooks);
   long total = 0;
   for (int i = 0; i < n; ++i) {
-    if (!codes[i] || !wav_out[i]) return cfail(VX_ERR_ARG, "utterance %d: null pointer", i);
-    if (T[i] < 1) return cfail(VX_ERR_ARG, "utterance %d: T = %d", i, T[i]);
-    if (T[i] > c.max_frames) return cfail(VX_ERR_CAPACITY, "utterance %d: T = %d > max_frames %d", i, T[i], c.max_frames);
+    if (!codes[i] || !wav_out[i]) return fail(VX_ERR_ARG, "utterance %d: null pointer", i);
+    if (T[i] < 1) return fail(VX_ERR_ARG, "utterance %d: T = %d", i, T[i]);
+    if (T[i] > c.max_frames) return fail(VX_ERR_CAPACITY, "utterance %d: T = %d > max_frames %d", i, T[i], c.max_frames);
     total += T[i];
   }
   for (int i = 0; i < n; ++i)
     for (long j = 0; j < (long)n_q * T[i]; ++j)
       if (codes[i][j] < 0 || codes[i][j] >= c.codebook_size)
-        return cfail(VX_ERR_ARG, "utterance %d: code %lld outside [0, %d)", i, (long long)codes[i][j], c.codebook_size);
-  if (!e->finalized) return cfail(VX_ERR_STATE, "vx_codec_decode before vx_codec_finalize");
-  CDevGuard g(c.device);
-  CHIPC(g.err);
+        return fail(VX_ERR_ARG, "utterance %d: code %lld outside [0, %d)", i, (long long)codes[i][j], c.codebook_size);
+  if (!e->finalized) return fail(VX_ERR_STATE, "vx_codec_decode before vx_codec_finalize");
+  DevGuard g(c.device);
+  HIPC(g.err);
   // The work runs on the decoder's own stream, ordered after everything already enqueued on `stream`; `stream` waits for it
   // before the call returns (as the engine's entry points do).  The host waits only for the previous call's staging copy.
   hipStream_t s = e->own;
-  CHIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
-  CHIPC(hipStreamWaitEvent(s, e->ev_in, 0));
+  HIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
+  HIPC(hipStreamWaitEvent(s, e->ev_in, 0));
   const int W = e->W;
 
-  CHIPC(hipEventSynchronize(e->ev_copy));  // the previous call's copy out of the pinned buffer has completed
+  HIPC(hipEventSynchronize(e->ev_copy));  // the previous call's copy out of the pinned buffer has completed
   int* hc = e->codes_host;
   const int MB1 = c.max_batch + 1;
   hc[0] = n;
@@ -683,8 +649,8 @@ extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* cod
     u0 = u1;
   }
   const size_t ints = 2 + 3 * (size_t)MB1 + (size_t)n_q * total;
-  CHIPC(hipMemcpyAsync(e->codes_dev, hc, ints * sizeof(int), hipMemcpyHostToDevice, s));
-  CHIPC(hipEventRecord(e->ev_copy, s));
+  HIPC(hipMemcpyAsync(e->codes_dev, hc, ints * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipEventRecord(e->ev_copy, s));
   int* dmeta = e->codes_dev;
   const int* dseg = e->codes_dev + 2;
   const int* drel = dseg + MB1;
@@ -693,9 +659,9 @@ extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* cod
   const long e0 = total * c.hidden;
   e->last_frames = 0;  // x0 no longer holds an encode's embeddings
   codec_rvq_rows<<<(unsigned)((e0 + 255) / 256), 256, 0, s>>>(dcodes, e->cb, e->x0, total, n_q, c.codebook_size, c.codebook_dim);
-  CHIPC(hipGetLastError());
-  CVXC(run_conv(e->x0, e->c0_w, e->c0_b, e->xc, total, c.hidden, W, c.kernel, 0, dseg, n, 1, s));
-  CVXC(run_lstm(e->lstm, e->xc, e->gin, e->h0, e->h1, e->c0, e->c1, e->y, W, c.lstm_layers, dseg, seg.data(), n, s,
+  HIPC(hipGetLastError());
+  VXC(run_conv(e->x0, e->c0_w, e->c0_b, e->xc, total, c.hidden, W, c.kernel, 0, dseg, n, 1, s));
+  VXC(run_lstm(e->lstm, e->xc, e->gin, e->h0, e->h1, e->c0, e->c1, e->y, W, c.lstm_layers, dseg, seg.data(), n, s,
                 (c.flags & VX_CODEC_LSTM_GRAPH) ? &e->chain : nullptr, dmeta));
 
   for (const Group& gr : groups) {
@@ -705,56 +671,56 @@ extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* cod
     const float* x = e->y + (size_t)seg[gr.u0] * W;
     long rate = 1;
     for (const Stage& st : e->stages) {
-      CVXC(run_convtr(x, st.up_w, st.up_b, e->bufA, frames * rate, st.cin, st.cout, st.stride, 1, sg, ns, (int)rate, s));
+      VXC(run_convtr(x, st.up_w, st.up_b, e->bufA, frames * rate, st.cin, st.cout, st.stride, 1, sg, ns, (int)rate, s));
       rate *= st.stride;
       const int ch = st.cout, hd = ch / 2;
-      CVXC(run_conv(e->bufA, st.c3_w, st.c3_b, e->bufH, frames * rate, ch, hd, c.res_kernel, 1, sg, ns, (int)rate, s));
+      VXC(run_conv(e->bufA, st.c3_w, st.c3_b, e->bufH, frames * rate, ch, hd, c.res_kernel, 1, sg, ns, (int)rate, s));
       CodecGemmArgs a{};
       a.part[0] = CodecPart{e->bufH, hd, 1, CODEC_PAD_ZERO, 1};
       a.part[1] = CodecPart{e->bufA, ch, 1, CODEC_PAD_ZERO, 0};
       a.nparts = 2;
       a.W = st.mix_w; a.bias = st.mix_b; a.out = e->bufB; a.M = frames * rate; a.N = ch; a.K = hd + ch;
       a.seg = sg; a.nseg = ns; a.rate = (int)rate;
-      CVXC(launch_gemm(a, s));
+      VXC(launch_gemm(a, s));
       x = e->bufB;
     }
     const int ch = e->stages.back().cout;
-    CVXC(run_conv(e->bufB, e->last_w, e->last_b, e->bufH, frames * rate, ch, 1, c.last_kernel, 1, sg, ns, (int)rate, s));
+    VXC(run_conv(e->bufB, e->last_w, e->last_b, e->bufH, frames * rate, ch, 1, c.last_kernel, 1, sg, ns, (int)rate, s));
     for (int u = gr.u0; u < gr.u1; ++u)
-      CHIPC(hipMemcpyAsync(wav_out[u], e->bufH + (size_t)(seg[u] - seg[gr.u0]) * rate, (size_t)T[u] * rate * sizeof(float),
+      HIPC(hipMemcpyAsync(wav_out[u], e->bufH + (size_t)(seg[u] - seg[gr.u0]) * rate, (size_t)T[u] * rate * sizeof(float),
                            hipMemcpyDeviceToDevice, s));
   }
-  CHIPC(hipEventRecord(e->ev_out, s));
-  CHIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
+  HIPC(hipEventRecord(e->ev_out, s));
+  HIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
   return VX_OK;
 }
 
 extern "C" int vx_codec_encode(vx_codec* e, int32_t n, const float* const* wav, const int32_t* n_samples, int32_t n_q,
                                int64_t* const* codes_out, void* stream) {
-  if (!e || !wav || !n_samples || !codes_out) return cfail(VX_ERR_ARG, "vx_codec_encode: null argument");
+  if (!e || !wav || !n_samples || !codes_out) return fail(VX_ERR_ARG, "vx_codec_encode: null argument");
   const vx_codec_config& c = e->cfg;
-  if (!(c.flags & VX_CODEC_ENCODER)) return cfail(VX_ERR_STATE, "vx_codec_encode on a handle created without VX_CODEC_ENCODER");
-  if (n < 1) return cfail(VX_ERR_ARG, "n = %d utterances", n);
-  if (n > c.max_batch) return cfail(VX_ERR_CAPACITY, "n = %d utterances > max_batch %d", n, c.max_batch);
-  if (n_q < 1 || n_q > c.n_codebooks) return cfail(VX_ERR_ARG, "n_q = %d outside [1, %d]", n_q, c.n_codebooks);
+  if (!(c.flags & VX_CODEC_ENCODER)) return fail(VX_ERR_STATE, "vx_codec_encode on a handle created without VX_CODEC_ENCODER");
+  if (n < 1) return fail(VX_ERR_ARG, "n = %d utterances", n);
+  if (n > c.max_batch) return fail(VX_ERR_CAPACITY, "n = %d utterances > max_batch %d", n, c.max_batch);
+  if (n_q < 1 || n_q > c.n_codebooks) return fail(VX_ERR_ARG, "n_q = %d outside [1, %d]", n_q, c.n_codebooks);
   long hop = 1;
   for (int i = 0; i < 4; ++i) hop *= c.ratios[i];
   const long max_samples = (long)c.max_frames * hop;
   for (int i = 0; i < n; ++i) {
-    if (!wav[i] || !codes_out[i]) return cfail(VX_ERR_ARG, "utterance %d: null pointer", i);
-    if (n_samples[i] < 1) return cfail(VX_ERR_ARG, "utterance %d: %d samples", i, n_samples[i]);
+    if (!wav[i] || !codes_out[i]) return fail(VX_ERR_ARG, "utterance %d: null pointer", i);
+    if (n_samples[i] < 1) return fail(VX_ERR_ARG, "utterance %d: %d samples", i, n_samples[i]);
     if (n_samples[i] > max_samples)
-      return cfail(VX_ERR_CAPACITY, "utterance %d: %d samples > max_frames %d x %ld", i, n_samples[i], c.max_frames, hop);
+      return fail(VX_ERR_CAPACITY, "utterance %d: %d samples > max_frames %d x %ld", i, n_samples[i], c.max_frames, hop);
   }
-  if (!e->finalized) return cfail(VX_ERR_STATE, "vx_codec_encode before vx_codec_finalize");
-  CDevGuard g(c.device);
-  CHIPC(g.err);
+  if (!e->finalized) return fail(VX_ERR_STATE, "vx_codec_encode before vx_codec_finalize");
+  DevGuard g(c.device);
+  HIPC(g.err);
   hipStream_t s = e->own;  // ordering as vx_codec_decode
-  CHIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
-  CHIPC(hipStreamWaitEvent(s, e->ev_in, 0));
+  HIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
+  HIPC(hipStreamWaitEvent(s, e->ev_in, 0));
   const int W = e->W;
 
-  CHIPC(hipEventSynchronize(e->ev_copy));
+  HIPC(hipEventSynchronize(e->ev_copy));
   int* hc = e->codes_host;
   const int MB1 = c.max_batch + 1;
   hc[0] = n;
@@ -793,9 +759,9 @@ extern "C" int vx_codec_encode(vx_codec* e, int32_t n, const float* const* wav, 
   }
   for (int i = 0; i < n; ++i) e->ptrs_host[i] = (long long*)codes_out[i];
   const size_t ints = 2 + 11 * (size_t)MB1;
-  CHIPC(hipMemcpyAsync(e->codes_dev, hc, ints * sizeof(int), hipMemcpyHostToDevice, s));
-  CHIPC(hipMemcpyAsync(e->ptrs_dev, e->ptrs_host, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, s));
-  CHIPC(hipEventRecord(e->ev_copy, s));
+  HIPC(hipMemcpyAsync(e->codes_dev, hc, ints * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(e->ptrs_dev, e->ptrs_host, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, s));
+  HIPC(hipEventRecord(e->ev_copy, s));
   const int* dseg = e->codes_dev + 2;
   const int* drel = dseg + MB1;
   const int* dlv = drel + 2 * MB1;
@@ -806,125 +772,123 @@ extern "C" int vx_codec_encode(vx_codec* e, int32_t n, const float* const* wav, 
     const int* sg[5] = {dlv + gr.off, dlv + 2 * MB1 + gr.off, dlv + 4 * MB1 + gr.off, dlv + 6 * MB1 + gr.off, drel + gr.off};
     long off = 0;
     for (int u = gr.u0; u < gr.u1; ++u) {
-      CHIPC(hipMemcpyAsync(e->wav + off, wav[u], (size_t)n_samples[u] * sizeof(float), hipMemcpyDeviceToDevice, s));
+      HIPC(hipMemcpyAsync(e->wav + off, wav[u], (size_t)n_samples[u] * sizeof(float), hipMemcpyDeviceToDevice, s));
       off += n_samples[u];
     }
-    CVXC(run_conv_in(e->wav, e->e0_w, e->e0_b, e->bufA, gr.rows[0], c.filters, c.kernel, sg[0], ns, s));
+    VXC(run_conv_in(e->wav, e->e0_w, e->e0_b, e->bufA, gr.rows[0], c.filters, c.kernel, sg[0], ns, s));
     for (int l = 0; l < 4; ++l) {
       const EncStage& st = e->estages[l];
       const int ch = st.c, hd = ch / 2;
-      CVXC(run_conv(e->bufA, st.c3_w, st.c3_b, e->bufH, gr.rows[l], ch, hd, c.res_kernel, 1, sg[l], ns, 1, s));
+      VXC(run_conv(e->bufA, st.c3_w, st.c3_b, e->bufH, gr.rows[l], ch, hd, c.res_kernel, 1, sg[l], ns, 1, s));
       CodecGemmArgs a{};
       a.part[0] = CodecPart{e->bufH, hd, 1, CODEC_PAD_ZERO, 1};
       a.part[1] = CodecPart{e->bufA, ch, 1, CODEC_PAD_ZERO, 0};
       a.nparts = 2;
       a.W = st.mix_w; a.bias = st.mix_b; a.out = e->bufB; a.M = gr.rows[l]; a.N = ch; a.K = hd + ch;
       a.seg = sg[l]; a.nseg = ns; a.rate = 1;
-      CVXC(launch_gemm(a, s));
+      VXC(launch_gemm(a, s));
       float* out = l == 3 ? e->xc + (size_t)seg[gr.u0] * W : e->bufA;
-      CVXC(run_conv_strided(e->bufB, st.dn_w, st.dn_b, out, gr.rows[l + 1], ch, 2 * ch, st.stride, 1, sg[l + 1], sg[l], ns, s));
+      VXC(run_conv_strided(e->bufB, st.dn_w, st.dn_b, out, gr.rows[l + 1], ch, 2 * ch, st.stride, 1, sg[l + 1], sg[l], ns, s));
     }
   }
-  CVXC(run_lstm(e->elstm, e->xc, e->gin, e->h0, e->h1, e->c0, e->c1, e->y, W, c.lstm_layers, dseg, seg.data(), n, s));
+  VXC(run_lstm(e->elstm, e->xc, e->gin, e->h0, e->h1, e->c0, e->c1, e->y, W, c.lstm_layers, dseg, seg.data(), n, s));
   e->last_frames = 0;
-  CVXC(run_conv(e->y, e->elast_w, e->elast_b, e->x0, total, W, c.hidden, c.last_kernel, 1, dseg, n, 1, s));
+  VXC(run_conv(e->y, e->elast_w, e->elast_b, e->x0, total, W, c.hidden, c.last_kernel, 1, dseg, n, 1, s));
   e->last_frames = total;
-  CVXC(run_rvq_encode(e->x0, e->cb, e->cb_sq, dcodes, total, n_q, c.codebook_size, c.codebook_dim, s));
+  VXC(run_rvq_encode(e->x0, e->cb, e->cb_sq, dcodes, total, n_q, c.codebook_size, c.codebook_dim, s));
   const long nc = total * n_q;
   codec_codes_out<<<(unsigned)((nc + 255) / 256), 256, 0, s>>>(dcodes, e->ptrs_dev, dseg, n, total, n_q);
-  CHIPC(hipGetLastError());
-  CHIPC(hipEventRecord(e->ev_out, s));
-  CHIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(e->ev_out, s));
+  HIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
   return VX_OK;
 }
 
 // The embeddings (the quantiser's input, [rows][hidden]) of the last vx_codec_encode, rows in the order of its utterances: copied to
 // `out` (device) on the codec's stream, `stream` ordered after it.  For the parity tests.
 extern "C" int vx_codec_last_embeddings(vx_codec* e, float* out, int64_t rows, void* stream) {
-  if (!e || !out) return cfail(VX_ERR_ARG, "vx_codec_last_embeddings: null argument");
-  if (!(e->cfg.flags & VX_CODEC_ENCODER) || !e->finalized) return cfail(VX_ERR_STATE, "vx_codec_last_embeddings: no finalised encoder");
+  if (!e || !out) return fail(VX_ERR_ARG, "vx_codec_last_embeddings: null argument");
+  if (!(e->cfg.flags & VX_CODEC_ENCODER) || !e->finalized) return fail(VX_ERR_STATE, "vx_codec_last_embeddings: no finalised encoder");
   if (rows < 1 || rows > e->last_frames)
-    return cfail(VX_ERR_ARG, "vx_codec_last_embeddings: rows = %lld, the last encode had %ld frames", (long long)rows, e->last_frames);
-  CDevGuard g(e->cfg.device);
-  CHIPC(g.err);
-  CHIPC(hipMemcpyAsync(out, e->x0, (size_t)rows * e->cfg.hidden * sizeof(float), hipMemcpyDeviceToDevice, e->own));
-  CHIPC(hipEventRecord(e->ev_out, e->own));
-  CHIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
+    return fail(VX_ERR_ARG, "vx_codec_last_embeddings: rows = %lld, the last encode had %ld frames", (long long)rows, e->last_frames);
+  DevGuard g(e->cfg.device);
+  HIPC(g.err);
+  HIPC(hipMemcpyAsync(out, e->x0, (size_t)rows * e->cfg.hidden * sizeof(float), hipMemcpyDeviceToDevice, e->own));
+  HIPC(hipEventRecord(e->ev_out, e->own));
+  HIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
   return VX_OK;
 }
 
 // ---- op-level test entries: x / out device fp32 rows, weights and biases HOST fp32 in torch's layouts (packed here exactly as
 // vx_codec_finalize packs them), seg_frames HOST nseg + 1 frame offsets.  Synchronous. ----------------------------------------
 namespace {
-struct OpSeg {
-  int* d = nullptr;
-  ~OpSeg() { (void)hipFree(d); }
-  int init(const int32_t* seg, int nseg) {
-    CHIPC(hipMalloc((void**)&d, (nseg + 1) * sizeof(int)));
-    CHIPC(hipMemcpy(d, seg, (nseg + 1) * sizeof(int), hipMemcpyHostToDevice));
-    return VX_OK;
-  }
-};
-struct OpBuf {
-  float* d = nullptr;
-  ~OpBuf() { (void)hipFree(d); }
-};
+int upload_segs(const int32_t* seg, int nseg, DevBuf<int>& d) {
+  VXC(d.alloc(nseg + 1));
+  HIPC(hipMemcpy(d.get(), seg, (nseg + 1) * sizeof(int), hipMemcpyHostToDevice));
+  return VX_OK;
+}
+// as upload() for the handle's own buffers: 16 spare bytes, a blocking copy
+int upload(const std::vector<float>& h, DevBuf<float>& d) {
+  VXC(d.alloc(h.size() + 4));
+  HIPC(hipMemcpy(d.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  return VX_OK;
+}
 }  // namespace
 
 extern "C" int vx_op_codec_conv(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out, int32_t k,
                                 int32_t elu, int32_t nseg, const int32_t* seg_frames, int32_t rate, void* stream) {
-  if (!x || !w || !out || c_in < 1 || c_out < 1 || k < 1 || k > 15 || rate < 1) return cfail(VX_ERR_ARG, "vx_op_codec_conv: bad argument");
-  CVXC(check_segs(seg_frames, nseg));
+  if (!x || !w || !out || c_in < 1 || c_out < 1 || k < 1 || k > 15 || rate < 1) return fail(VX_ERR_ARG, "vx_op_codec_conv: bad argument");
+  VXC(check_segs(seg_frames, nseg));
   hipStream_t s = (hipStream_t)stream;
-  OpSeg sg;
-  OpBuf wp, bp;
-  CVXC(sg.init(seg_frames, nseg));
-  CVXC(upload(pack_conv(w, c_out, c_in, k), &wp.d));
-  if (bias) CVXC(upload(std::vector<float>(bias, bias + c_out), &bp.d));
-  CVXC(run_conv(x, wp.d, bp.d, out, (long)seg_frames[nseg] * rate, c_in, c_out, k, elu, sg.d, nseg, rate, s));
-  CHIPC(hipStreamSynchronize(s));
+  DevBuf<int> sg;
+  DevBuf<float> wp, bp;
+  VXC(upload_segs(seg_frames, nseg, sg));
+  VXC(upload(pack_conv(w, c_out, c_in, k), wp));
+  if (bias) VXC(upload(std::vector<float>(bias, bias + c_out), bp));
+  VXC(run_conv(x, wp.get(), bp.get(), out, (long)seg_frames[nseg] * rate, c_in, c_out, k, elu, sg.get(), nseg, rate, s));
+  HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }
 
 extern "C" int vx_op_codec_convtr(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out,
                                   int32_t stride, int32_t elu, int32_t nseg, const int32_t* seg_frames, int32_t rate, void* stream) {
-  if (!x || !w || !out || c_in < 1 || c_out < 1 || stride < 1 || rate < 1) return cfail(VX_ERR_ARG, "vx_op_codec_convtr: bad argument");
-  CVXC(check_segs(seg_frames, nseg));
+  if (!x || !w || !out || c_in < 1 || c_out < 1 || stride < 1 || rate < 1) return fail(VX_ERR_ARG, "vx_op_codec_convtr: bad argument");
+  VXC(check_segs(seg_frames, nseg));
   hipStream_t s = (hipStream_t)stream;
-  OpSeg sg;
-  OpBuf wp, bp;
-  CVXC(sg.init(seg_frames, nseg));
-  CVXC(upload(pack_convtr(w, c_in, c_out, stride), &wp.d));
+  DevBuf<int> sg;
+  DevBuf<float> wp, bp;
+  VXC(upload_segs(seg_frames, nseg, sg));
+  VXC(upload(pack_convtr(w, c_in, c_out, stride), wp));
   if (bias) {
     std::vector<float> rep((size_t)stride * c_out);
     for (int p = 0; p < stride; ++p) memcpy(&rep[(size_t)p * c_out], bias, c_out * sizeof(float));
-    CVXC(upload(rep, &bp.d));
+    VXC(upload(rep, bp));
   }
-  CVXC(run_convtr(x, wp.d, bp.d, out, (long)seg_frames[nseg] * rate, c_in, c_out, stride, elu, sg.d, nseg, rate, s));
-  CHIPC(hipStreamSynchronize(s));
+  VXC(run_convtr(x, wp.get(), bp.get(), out, (long)seg_frames[nseg] * rate, c_in, c_out, stride, elu, sg.get(), nseg, rate, s));
+  HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }
 
 extern "C" int vx_op_codec_lstm(const float* x, const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
                                 const float* const* b_hh, float* y, int32_t width, int32_t layers, int32_t nseg,
                                 const int32_t* seg_frames, void* stream) {
-  if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !y) return cfail(VX_ERR_ARG, "vx_op_codec_lstm: null argument");
-  if (layers < 1 || layers > 2 || !lstm_width_ok(width)) return cfail(VX_ERR_UNSUPPORTED, "vx_op_codec_lstm: width %d, layers %d", width, layers);
-  CVXC(check_segs(seg_frames, nseg));
+  if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !y) return fail(VX_ERR_ARG, "vx_op_codec_lstm: null argument");
+  if (layers < 1 || layers > 2 || !lstm_width_ok(width)) return fail(VX_ERR_UNSUPPORTED, "vx_op_codec_lstm: width %d, layers %d", width, layers);
+  VXC(check_segs(seg_frames, nseg));
   hipStream_t s = (hipStream_t)stream;
-  OpSeg sg;
-  CVXC(sg.init(seg_frames, nseg));
+  DevBuf<int> sg;
+  VXC(upload_segs(seg_frames, nseg, sg));
   LstmDev d;
   int r = pack_lstm(w_ih, w_hh, b_ih, b_hh, width, layers, &d);
   const size_t rows = seg_frames[nseg];
-  OpBuf gin, h0, h1, c0, c1;
-  if (r == VX_OK) r = alloc_f(&gin.d, rows * 4 * width);
-  if (r == VX_OK) r = alloc_f(&h0.d, rows * width);
-  if (r == VX_OK) r = alloc_f(&h1.d, rows * width);
-  if (r == VX_OK) r = alloc_f(&c0.d, (size_t)nseg * width);
-  if (r == VX_OK) r = alloc_f(&c1.d, (size_t)nseg * width);
-  if (r == VX_OK) r = run_lstm(d, x, gin.d, h0.d, h1.d, c0.d, c1.d, y, width, layers, sg.d, seg_frames, nseg, s);
-  if (r == VX_OK && hipStreamSynchronize(s) != hipSuccess) r = cfail(VX_ERR_HIP, "vx_op_codec_lstm: synchronise failed");
+  DevBuf<float> gin, h0, h1, c0, c1;  // 16 spare bytes each, as alloc_f()
+  if (r == VX_OK) r = gin.alloc(rows * 4 * width + 4);
+  if (r == VX_OK) r = h0.alloc(rows * width + 4);
+  if (r == VX_OK) r = h1.alloc(rows * width + 4);
+  if (r == VX_OK) r = c0.alloc((size_t)nseg * width + 4);
+  if (r == VX_OK) r = c1.alloc((size_t)nseg * width + 4);
+  if (r == VX_OK) r = run_lstm(d, x, gin.get(), h0.get(), h1.get(), c0.get(), c1.get(), y, width, layers, sg.get(), seg_frames, nseg, s);
+  if (r == VX_OK && hipStreamSynchronize(s) != hipSuccess) r = fail(VX_ERR_HIP, "vx_op_codec_lstm: synchronise failed");
   free_lstm(d);
   return r;
 }
@@ -934,55 +898,59 @@ extern "C" int vx_op_codec_lstm(const float* x, const float* const* w_ih, const 
 // 0 there); stride > 1: k must be 2 stride.
 extern "C" int vx_op_codec_conv_strided(const float* x, const float* w, const float* bias, float* out, int32_t c_in, int32_t c_out,
                                         int32_t k, int32_t stride, int32_t elu, int32_t nseg, const int32_t* seg_rows_in, void* stream) {
-  if (!x || !w || !out || c_in < 1 || c_out < 1 || k < 1 || k > 32 || stride < 1) return cfail(VX_ERR_ARG, "vx_op_codec_conv_strided: bad argument");
-  if (stride > 1 && k != 2 * stride) return cfail(VX_ERR_UNSUPPORTED, "vx_op_codec_conv_strided: k = %d, stride = %d (k = 2 stride is served)", k, stride);
-  if (c_in == 1 && stride == 1 && elu) return cfail(VX_ERR_UNSUPPORTED, "vx_op_codec_conv_strided: the first convolution has no ELU");
-  CVXC(check_segs(seg_rows_in, nseg));
+  if (!x || !w || !out || c_in < 1 || c_out < 1 || k < 1 || k > 32 || stride < 1) return fail(VX_ERR_ARG, "vx_op_codec_conv_strided: bad argument");
+  if (stride > 1 && k != 2 * stride) return fail(VX_ERR_UNSUPPORTED, "vx_op_codec_conv_strided: k = %d, stride = %d (k = 2 stride is served)", k, stride);
+  if (c_in == 1 && stride == 1 && elu) return fail(VX_ERR_UNSUPPORTED, "vx_op_codec_conv_strided: the first convolution has no ELU");
+  VXC(check_segs(seg_rows_in, nseg));
   hipStream_t s = (hipStream_t)stream;
   std::vector<int32_t> so(nseg + 1, 0);
   for (int i = 0; i < nseg; ++i) so[i + 1] = so[i] + (seg_rows_in[i + 1] - seg_rows_in[i] + stride - 1) / stride;
-  OpSeg sg, sgo;
-  OpBuf wp, bp;
-  CVXC(sg.init(seg_rows_in, nseg));
-  CVXC(sgo.init(so.data(), nseg));
-  CVXC(upload(pack_conv(w, c_out, c_in, k), &wp.d));
-  if (bias) CVXC(upload(std::vector<float>(bias, bias + c_out), &bp.d));
-  if (stride > 1) CVXC(run_conv_strided(x, wp.d, bp.d, out, so[nseg], c_in, c_out, stride, elu, sgo.d, sg.d, nseg, s));
-  else if (c_in == 1) CVXC(run_conv_in(x, wp.d, bp.d, out, so[nseg], c_out, k, sg.d, nseg, s));
-  else CVXC(run_conv(x, wp.d, bp.d, out, so[nseg], c_in, c_out, k, elu, sg.d, nseg, 1, s));
-  CHIPC(hipStreamSynchronize(s));
+  DevBuf<int> sg, sgo;
+  DevBuf<float> wp, bp;
+  VXC(upload_segs(seg_rows_in, nseg, sg));
+  VXC(upload_segs(so.data(), nseg, sgo));
+  VXC(upload(pack_conv(w, c_out, c_in, k), wp));
+  if (bias) VXC(upload(std::vector<float>(bias, bias + c_out), bp));
+  if (stride > 1) VXC(run_conv_strided(x, wp.get(), bp.get(), out, so[nseg], c_in, c_out, stride, elu, sgo.get(), sg.get(), nseg, s));
+  else if (c_in == 1) VXC(run_conv_in(x, wp.get(), bp.get(), out, so[nseg], c_out, k, sg.get(), nseg, s));
+  else VXC(run_conv(x, wp.get(), bp.get(), out, so[nseg], c_in, c_out, k, elu, sg.get(), nseg, 1, s));
+  HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }
 
 // The quantiser's search on caller data: emb device [rows][dim], codebooks HOST [n_q][size][dim], codes_out device int32 [n_q][rows].
 extern "C" int vx_op_codec_rvq_encode(const float* emb, const float* codebooks, int32_t* codes_out, int64_t rows, int32_t n_q,
                                       int32_t size, int32_t dim, void* stream) {
-  if (!emb || !codebooks || !codes_out || rows < 1 || n_q < 1 || n_q > CODEC_MAX_Q) return cfail(VX_ERR_ARG, "vx_op_codec_rvq_encode: bad argument");
-  if (size < 1 || dim < 1 || !rvq_shape_ok(size, dim)) return cfail(VX_ERR_UNSUPPORTED, "vx_op_codec_rvq_encode: codebook %d x %d", size, dim);
+  if (!emb || !codebooks || !codes_out || rows < 1 || n_q < 1 || n_q > CODEC_MAX_Q) return fail(VX_ERR_ARG, "vx_op_codec_rvq_encode: bad argument");
+  if (size < 1 || dim < 1 || !rvq_shape_ok(size, dim)) return fail(VX_ERR_UNSUPPORTED, "vx_op_codec_rvq_encode: codebook %d x %d", size, dim);
   hipStream_t s = (hipStream_t)stream;
-  OpBuf cb, sq;
+  DevBuf<float> cb, sq;
   const size_t n = (size_t)n_q * size;
-  CVXC(upload(std::vector<float>(codebooks, codebooks + n * dim), &cb.d));
-  CVXC(upload(codebook_sq(codebooks, n, dim), &sq.d));
-  CVXC(run_rvq_encode(emb, cb.d, sq.d, codes_out, rows, n_q, size, dim, s));
-  CHIPC(hipStreamSynchronize(s));
+  VXC(upload(std::vector<float>(codebooks, codebooks + n * dim), cb));
+  VXC(upload(codebook_sq(codebooks, n, dim), sq));
+  VXC(run_rvq_encode(emb, cb.get(), sq.get(), codes_out, rows, n_q, size, dim, s));
+  HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }
 
 // ---- sample-rate conversion and mix-down (vx_resampler_*, codec_resample) -------------------------------------------------------
+namespace {
+// Device side of a resampler: made on the device that is current at the first vx_resample, dropped as a whole.
+struct ResamplerDev {
+  DevBuf<float> coef;
+  DevBuf<int> phase;  // first [n] | count [n]
+  // per call: in pointers [max_batch] | out pointers [max_batch] | tile0 [max_batch + 1] | len_in | chans | len_out [max_batch each]
+  CallStage stage;
+};
+}  // namespace
+
 struct vx_resampler {
   int orig = 0, neu = 0, max_batch = 0;
   int o = 1, n = 1, T = 1, tile_out = 256;
   std::vector<float> coef;        // [T][n], scale folded in, zero past a phase's count
   std::vector<int> first, count;  // [n]
-  // device side: made on the device that is current at the first vx_resample
-  int device = -1;
-  float* d_coef = nullptr;
-  int* d_phase = nullptr;  // first [n] | count [n]
-  // per call: in pointers [max_batch] | out pointers [max_batch] | tile0 [max_batch + 1] | len_in | chans | len_out [max_batch each]
-  char *stage_dev = nullptr, *stage_host = nullptr;
-  size_t stage_bytes = 0;
-  hipEvent_t ev_copy = nullptr, ev_done = nullptr;
+  int device = -1;  // >= 0: `dev` is complete
+  std::unique_ptr<ResamplerDev> dev;
 };
 
 namespace {
@@ -1014,10 +982,10 @@ int resampler_build(vx_resampler* r) {
   }
   const double base = 0.99 * (double)std::min(o, n), R = RESAMPLE_WIDTH * (double)o / base;
   if ((double)n * (2.0 * R + 2.0) > (double)RESAMPLE_MAX_TABLE)
-    return cfail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz needs %ld phases of about %.0f taps: above %ld coefficients", r->orig,
+    return fail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz needs %ld phases of about %.0f taps: above %ld coefficients", r->orig,
                  r->neu, n, 2.0 * R, RESAMPLE_MAX_TABLE);
   if (2.0 * R + 4.0 > RESAMPLE_SPAN)
-    return cfail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz: %.0f taps per sample exceed the kernel's window of %d", r->orig, r->neu,
+    return fail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz: %.0f taps per sample exceed the kernel's window of %d", r->orig, r->neu,
                  2.0 * R, RESAMPLE_SPAN);
   r->first.resize(n);
   r->count.resize(n);
@@ -1050,44 +1018,25 @@ int resampler_build(vx_resampler* r) {
     if (t >= 64) t &= ~63L;
   }
   if (need(t) > RESAMPLE_SPAN)
-    return cfail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz: one sample's window exceeds %d inputs", r->orig, r->neu, RESAMPLE_SPAN);
+    return fail(VX_ERR_UNSUPPORTED, "vx_resampler_create: %d -> %d Hz: one sample's window exceeds %d inputs", r->orig, r->neu, RESAMPLE_SPAN);
   r->tile_out = (int)t;
   return VX_OK;
 }
 
-void resampler_free_device(vx_resampler* r) {
-  (void)hipFree(r->d_coef);
-  (void)hipFree(r->d_phase);
-  (void)hipFree(r->stage_dev);
-  (void)hipHostFree(r->stage_host);
-  for (hipEvent_t ev : {r->ev_copy, r->ev_done})
-    if (ev) (void)hipEventDestroy(ev);
-  r->d_coef = nullptr; r->d_phase = nullptr; r->stage_dev = nullptr; r->stage_host = nullptr; r->ev_copy = r->ev_done = nullptr;
-}
-
-// First use: the tables go to the current device.  VX_POISON=1 fills the fresh allocations with 0xFF bytes first, as the engine does.
+// First use: the tables go to the current device.
 int resampler_init_device(vx_resampler* r) {
   int dev = 0;
-  CHIPC(hipGetDevice(&dev));
+  HIPC(hipGetDevice(&dev));
   r->device = dev;
-  const char* pv = getenv("VX_POISON");
-  const bool poison = pv && atoi(pv) != 0;
-  const size_t nc = r->coef.size(), MB = (size_t)r->max_batch;
-  r->stage_bytes = 2 * MB * sizeof(void*) + (4 * MB + 1) * sizeof(int);
-  CHIPC(hipMalloc((void**)&r->d_coef, nc * sizeof(float)));
-  CHIPC(hipMalloc((void**)&r->d_phase, 2 * (size_t)r->n * sizeof(int)));
-  CHIPC(hipMalloc((void**)&r->stage_dev, r->stage_bytes));
-  if (poison) {
-    CHIPC(hipMemset(r->d_coef, 0xFF, nc * sizeof(float)));
-    CHIPC(hipMemset(r->d_phase, 0xFF, 2 * (size_t)r->n * sizeof(int)));
-    CHIPC(hipMemset(r->stage_dev, 0xFF, r->stage_bytes));
-  }
-  CHIPC(hipHostMalloc((void**)&r->stage_host, r->stage_bytes));
-  CHIPC(hipMemcpy(r->d_coef, r->coef.data(), nc * sizeof(float), hipMemcpyHostToDevice));
-  CHIPC(hipMemcpy(r->d_phase, r->first.data(), (size_t)r->n * sizeof(int), hipMemcpyHostToDevice));
-  CHIPC(hipMemcpy(r->d_phase + r->n, r->count.data(), (size_t)r->n * sizeof(int), hipMemcpyHostToDevice));
-  CHIPC(hipEventCreateWithFlags(&r->ev_copy, hipEventDisableTiming));
-  CHIPC(hipEventCreateWithFlags(&r->ev_done, hipEventDisableTiming));
+  r->dev.reset(new ResamplerDev());
+  ResamplerDev& d = *r->dev;
+  const size_t nc = r->coef.size(), MB = (size_t)r->max_batch, n = (size_t)r->n;
+  VXC(d.coef.alloc(nc));
+  VXC(d.phase.alloc(2 * n));
+  VXC(d.stage.init(2 * MB * sizeof(void*) + (4 * MB + 1) * sizeof(int)));
+  HIPC(hipMemcpy(d.coef.get(), r->coef.data(), nc * sizeof(float), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d.phase.get(), r->first.data(), n * sizeof(int), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d.phase.get() + n, r->count.data(), n * sizeof(int), hipMemcpyHostToDevice));
   return VX_OK;
 }
 
@@ -1095,7 +1044,7 @@ int resampler_init_device(vx_resampler* r) {
 
 extern "C" int64_t vx_resample_length(int32_t orig_hz, int32_t new_hz, int64_t n_samples) {
   if (orig_hz <= 0 || new_hz <= 0 || n_samples < 1) {
-    cfail(VX_ERR_ARG, "vx_resample_length: %d -> %d Hz, %lld samples", orig_hz, new_hz, (long long)n_samples);
+    fail(VX_ERR_ARG, "vx_resample_length: %d -> %d Hz, %lld samples", orig_hz, new_hz, (long long)n_samples);
     return -1;
   }
   const long g = gcd_l(orig_hz, new_hz), o = orig_hz / g, n = new_hz / g;
@@ -1103,9 +1052,9 @@ extern "C" int64_t vx_resample_length(int32_t orig_hz, int32_t new_hz, int64_t n
 }
 
 extern "C" int vx_resampler_create(int32_t orig_hz, int32_t new_hz, int32_t max_batch, vx_resampler** out) {
-  if (!out) return cfail(VX_ERR_ARG, "vx_resampler_create: null argument");
-  if (orig_hz <= 0 || new_hz <= 0) return cfail(VX_ERR_ARG, "vx_resampler_create: rates %d -> %d Hz", orig_hz, new_hz);
-  if (max_batch < 1) return cfail(VX_ERR_ARG, "vx_resampler_create: max_batch = %d", max_batch);
+  if (!out) return fail(VX_ERR_ARG, "vx_resampler_create: null argument");
+  if (orig_hz <= 0 || new_hz <= 0) return fail(VX_ERR_ARG, "vx_resampler_create: rates %d -> %d Hz", orig_hz, new_hz);
+  if (max_batch < 1) return fail(VX_ERR_ARG, "vx_resampler_create: max_batch = %d", max_batch);
   vx_resampler* r = new vx_resampler();
   r->orig = orig_hz; r->neu = new_hz; r->max_batch = max_batch;
   const int rc = resampler_build(r);
@@ -1117,47 +1066,47 @@ extern "C" int vx_resampler_create(int32_t orig_hz, int32_t new_hz, int32_t max_
 extern "C" void vx_resampler_destroy(vx_resampler* r) {
   if (!r) return;
   if (r->device >= 0) {
-    CDevGuard g(r->device);
-    if (r->ev_done) (void)hipEventSynchronize(r->ev_done);
-    resampler_free_device(r);
+    DevGuard g(r->device);
+    (void)r->dev->stage.drain();
+    r->dev.reset();
   }
   delete r;
 }
 
 extern "C" int vx_resample(vx_resampler* r, int32_t n, const float* const* in, const int32_t* channels, const int32_t* n_samples,
                            float* const* out, void* stream) {
-  if (!r || !in || !channels || !n_samples || !out) return cfail(VX_ERR_ARG, "vx_resample: null argument");
-  if (n < 1) return cfail(VX_ERR_ARG, "vx_resample: n = %d utterances", n);
-  if (n > r->max_batch) return cfail(VX_ERR_CAPACITY, "vx_resample: n = %d utterances > max_batch %d", n, r->max_batch);
+  if (!r || !in || !channels || !n_samples || !out) return fail(VX_ERR_ARG, "vx_resample: null argument");
+  if (n < 1) return fail(VX_ERR_ARG, "vx_resample: n = %d utterances", n);
+  if (n > r->max_batch) return fail(VX_ERR_CAPACITY, "vx_resample: n = %d utterances > max_batch %d", n, r->max_batch);
   std::vector<int> tile0(n + 1, 0), len_out(n);
   for (int i = 0; i < n; ++i) {
-    if (!in[i] || !out[i]) return cfail(VX_ERR_ARG, "vx_resample: utterance %d: null pointer", i);
-    if (channels[i] < 1) return cfail(VX_ERR_ARG, "vx_resample: utterance %d: %d channels", i, channels[i]);
-    if (n_samples[i] < 1) return cfail(VX_ERR_ARG, "vx_resample: utterance %d: %d samples", i, n_samples[i]);
+    if (!in[i] || !out[i]) return fail(VX_ERR_ARG, "vx_resample: utterance %d: null pointer", i);
+    if (channels[i] < 1) return fail(VX_ERR_ARG, "vx_resample: utterance %d: %d channels", i, channels[i]);
+    if (n_samples[i] < 1) return fail(VX_ERR_ARG, "vx_resample: utterance %d: %d samples", i, n_samples[i]);
     const long lo = ((long)r->n * n_samples[i] + r->o - 1) / r->o;
-    if (lo > 0x7fffffffL) return cfail(VX_ERR_UNSUPPORTED, "vx_resample: utterance %d: %ld output samples exceed int32", i, lo);
+    if (lo > 0x7fffffffL) return fail(VX_ERR_UNSUPPORTED, "vx_resample: utterance %d: %ld output samples exceed int32", i, lo);
     len_out[i] = (int)lo;
     const long tiles = tile0[i] + (lo + r->tile_out - 1) / r->tile_out;
-    if (tiles > 0x7fffffffL) return cfail(VX_ERR_UNSUPPORTED, "vx_resample: utterance %d: the call's output tiles exceed int32", i);
+    if (tiles > 0x7fffffffL) return fail(VX_ERR_UNSUPPORTED, "vx_resample: utterance %d: the call's output tiles exceed int32", i);
     tile0[i + 1] = (int)tiles;
   }
   if (r->device < 0) {
     const int rc = resampler_init_device(r);
-    if (rc != VX_OK) {
-      resampler_free_device(r);
+    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
+      r->dev.reset();
       r->device = -1;
       return rc;
     }
   }
-  CDevGuard g(r->device);
-  CHIPC(g.err);
+  DevGuard g(r->device);
+  HIPC(g.err);
+  ResamplerDev& d = *r->dev;
   hipStream_t s = (hipStream_t)stream;
-  CHIPC(hipEventSynchronize(r->ev_copy));      // the previous call's copy out of the pinned buffer has completed
-  CHIPC(hipStreamWaitEvent(s, r->ev_done, 0));  // and its kernel, on whatever stream it ran, is done with the device tables
+  VXC(d.stage.begin(s));
   const size_t MB = (size_t)r->max_batch;
-  const float** hin = (const float**)r->stage_host;
-  float** hout = (float**)(r->stage_host + MB * sizeof(void*));
-  int* hint = (int*)(r->stage_host + 2 * MB * sizeof(void*));
+  const float** hin = d.stage.host<const float*>();
+  float** hout = d.stage.host<float*>(MB * sizeof(void*));
+  int* hint = d.stage.host<int>(2 * MB * sizeof(void*));
   for (int i = 0; i < n; ++i) {
     hin[i] = in[i];
     hout[i] = out[i];
@@ -1166,19 +1115,17 @@ extern "C" int vx_resample(vx_resampler* r, int32_t n, const float* const* in, c
     hint[3 * MB + 1 + i] = len_out[i];
   }
   memcpy(hint, tile0.data(), (n + 1) * sizeof(int));
-  CHIPC(hipMemcpyAsync(r->stage_dev, r->stage_host, r->stage_bytes, hipMemcpyHostToDevice, s));
-  CHIPC(hipEventRecord(r->ev_copy, s));
+  VXC(d.stage.upload(d.stage.bytes, s));
   ResampleArgs a{};
-  a.in = (const float* const*)r->stage_dev;
-  a.out = (float* const*)(r->stage_dev + MB * sizeof(void*));
-  const int* dint = (const int*)(r->stage_dev + 2 * MB * sizeof(void*));
+  a.in = d.stage.dev<const float* const>();
+  a.out = d.stage.dev<float* const>(MB * sizeof(void*));
+  const int* dint = d.stage.dev<const int>(2 * MB * sizeof(void*));
   a.tile0 = dint; a.len_in = dint + MB + 1; a.chans = dint + 2 * MB + 1; a.len_out = dint + 3 * MB + 1;
-  a.coef = r->d_coef; a.first = r->d_phase; a.count = r->d_phase + r->n;
+  a.coef = d.coef.get(); a.first = d.phase.get(); a.count = d.phase.get() + r->n;
   a.nseg = n; a.o = r->o; a.n = r->n; a.T = r->T; a.tile_out = r->tile_out;
   const unsigned grid = (unsigned)std::min(tile0[n], 2048);
   if ((long)r->T * r->n <= RESAMPLE_TAB) codec_resample<true><<<grid, 256, 0, s>>>(a);
   else codec_resample<false><<<grid, 256, 0, s>>>(a);
-  CHIPC(hipGetLastError());
-  CHIPC(hipEventRecord(r->ev_done, s));
-  return VX_OK;
+  HIPC(hipGetLastError());
+  return d.stage.finish(s);
 }

@@ -1,70 +1,43 @@
-// Dynamic time warping behind the C ABI (include/vallex.h, vx_dtw_*): the host table of the cepstra, the staging of a ragged call,
-// the workspace that grows with the calls, and the launches of dtw_kernels.hpp.  A translation unit and a handle of its own, like
-// fbank.hip: no other unit sees these kernels, so the device code of every existing path is compiled exactly as before.
+// Dynamic time warping behind the C ABI (include/vallex.h, vx_dtw_*): the host table of the cepstra, the staging of a ragged call
+// (CallStage, host.hpp), the workspace that grows with the calls, and the launches of dtw_kernels.hpp.  A translation unit and a
+// handle of its own, like fbank.hip: no other unit sees these kernels, so the device code of every existing path is compiled
+// exactly as before.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #undef VX_STAMPS  // the in-kernel stamps write device globals of engine.hip's unit, out of this unit's reach
-#include "../../include/vallex.h"
+#include "host.hpp"
 #include "dtw_kernels.hpp"
 
 using namespace vx;
 
-extern "C" void vx_internal_set_error(const char* msg);  // engine.hip: the message vx_last_error() returns
-
-static int dfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  vx_internal_set_error(buf);
-  return code;
-}
-#define DHIPC(expr)                                                                                                    \
-  do {                                                                                                                 \
-    hipError_t e_ = (expr);                                                                                            \
-    if (e_ != hipSuccess)                                                                                              \
-      return dfail(VX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);              \
-  } while (0)
+namespace {
+// Device side of a handle: made on the device that is current at the first vx_dtw_compare, dropped as a whole.
+struct DtwDev {
+  DevBuf<float> tab;
+  CallStage stage;       // per call: DtwPair [max_batch]
+  DevBuf<double> total;  // [max_batch]
+  DevBuf<int> len;       // [max_batch]
+  // workspace, sized to the largest call so far: 4 (cost) + 1 (back-pointer) bytes per cell, 4 n_ceps bytes per frame
+  DevBuf<float> cost, ceps;
+  DevBuf<unsigned char> bp;
+  long long cap_cells = 0, cap_rows = 0;
+};
+}  // namespace
 
 struct vx_dtw {
   int dim = 0, n_ceps = 0, max_frames = 0, max_batch = 0;
   std::vector<float> tab;  // [dim][n_ceps]: sqrt(2 / dim) cos(pi k (n + 1/2) / dim), k = 1 .. n_ceps
-  // device side: made on the device that is current at the first vx_dtw_compare
-  int device = -1;
-  float* d_tab = nullptr;
-  char *stage_dev = nullptr, *stage_host = nullptr;  // per call: DtwPair [max_batch]
-  double* d_total = nullptr;                         // [max_batch]
-  int* d_len = nullptr;                              // [max_batch]
-  // workspace, sized to the largest call so far: 4 (cost) + 1 (back-pointer) bytes per cell, 4 n_ceps bytes per frame
-  float* d_cost = nullptr;
-  unsigned char* d_bp = nullptr;
-  float* d_ceps = nullptr;
-  long long cap_cells = 0, cap_rows = 0;
-  bool poison = false;
-  hipEvent_t ev_copy = nullptr, ev_done = nullptr;
+  int device = -1;  // >= 0: `dev` is complete
+  std::unique_ptr<DtwDev> dev;
 };
 
 namespace {
-
-struct DDevGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DDevGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else if (err == hipSuccess) prev = -1;
-  }
-  ~DDevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // The orthonormal DCT-II without its 0th row, n-major: fp64, rounded once.
 std::vector<float> dct_table(int dim, int n_ceps) {
@@ -75,69 +48,41 @@ std::vector<float> dct_table(int dim, int n_ceps) {
   return t;
 }
 
-void dtw_free_device(vx_dtw* h) {
-  (void)hipFree(h->d_tab);
-  (void)hipFree(h->stage_dev);
-  (void)hipHostFree(h->stage_host);
-  (void)hipFree(h->d_total);
-  (void)hipFree(h->d_len);
-  (void)hipFree(h->d_cost);
-  (void)hipFree(h->d_bp);
-  (void)hipFree(h->d_ceps);
-  for (hipEvent_t ev : {h->ev_copy, h->ev_done})
-    if (ev) (void)hipEventDestroy(ev);
-  h->d_tab = h->d_cost = h->d_ceps = nullptr; h->stage_dev = h->stage_host = nullptr; h->d_total = nullptr; h->d_len = nullptr;
-  h->d_bp = nullptr; h->ev_copy = h->ev_done = nullptr; h->cap_cells = h->cap_rows = 0;
-}
-
-// First use: the table goes to the current device.  VX_POISON=1 fills the fresh allocations with 0xFF bytes first, as the engine does.
+// First use: the table goes to the current device.
 int dtw_init_device(vx_dtw* h) {
   int dev = 0;
-  DHIPC(hipGetDevice(&dev));
+  HIPC(hipGetDevice(&dev));
   h->device = dev;
-  const char* pv = getenv("VX_POISON");
-  h->poison = pv && atoi(pv) != 0;
-  const size_t MB = (size_t)h->max_batch, sb = MB * sizeof(DtwPair);
-  DHIPC(hipMalloc((void**)&h->stage_dev, sb));
-  DHIPC(hipMalloc((void**)&h->d_total, MB * sizeof(double)));
-  DHIPC(hipMalloc((void**)&h->d_len, MB * sizeof(int)));
-  if (h->poison) {
-    DHIPC(hipMemset(h->stage_dev, 0xFF, sb));
-    DHIPC(hipMemset(h->d_total, 0xFF, MB * sizeof(double)));
-    DHIPC(hipMemset(h->d_len, 0xFF, MB * sizeof(int)));
-  }
-  DHIPC(hipHostMalloc((void**)&h->stage_host, sb));
+  h->dev.reset(new DtwDev());
+  DtwDev& d = *h->dev;
+  const size_t MB = (size_t)h->max_batch;
+  VXC(d.stage.init(MB * sizeof(DtwPair)));
+  VXC(d.total.alloc(MB));
+  VXC(d.len.alloc(MB));
   if (h->n_ceps > 0) {
-    DHIPC(hipMalloc((void**)&h->d_tab, h->tab.size() * sizeof(float)));
-    DHIPC(hipMemcpy(h->d_tab, h->tab.data(), h->tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    VXC(d.tab.alloc(h->tab.size()));
+    HIPC(hipMemcpy(d.tab.get(), h->tab.data(), h->tab.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  DHIPC(hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
-  DHIPC(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
   return VX_OK;
 }
 
 // The workspace follows the largest call: a larger one waits for the previous call and replaces the buffers.
 int dtw_grow(vx_dtw* h, long long cells, long long rows) {
-  if (cells <= h->cap_cells && rows <= h->cap_rows) return VX_OK;
-  DHIPC(hipEventSynchronize(h->ev_done));
-  if (cells > h->cap_cells) {
-    (void)hipFree(h->d_cost);
-    (void)hipFree(h->d_bp);
-    h->d_cost = nullptr; h->d_bp = nullptr; h->cap_cells = 0;
-    DHIPC(hipMalloc((void**)&h->d_cost, (size_t)cells * sizeof(float)));
-    DHIPC(hipMalloc((void**)&h->d_bp, (size_t)cells));
-    if (h->poison) {
-      DHIPC(hipMemset(h->d_cost, 0xFF, (size_t)cells * sizeof(float)));
-      DHIPC(hipMemset(h->d_bp, 0xFF, (size_t)cells));
-    }
-    h->cap_cells = cells;
+  DtwDev& d = *h->dev;
+  if (cells <= d.cap_cells && rows <= d.cap_rows) return VX_OK;
+  VXC(d.stage.drain());
+  if (cells > d.cap_cells) {
+    d.cap_cells = 0;
+    d.cost.reset();
+    d.bp.reset();
+    VXC(d.cost.alloc((size_t)cells));
+    VXC(d.bp.alloc((size_t)cells));
+    d.cap_cells = cells;
   }
-  if (rows > h->cap_rows && h->n_ceps > 0) {
-    (void)hipFree(h->d_ceps);
-    h->d_ceps = nullptr; h->cap_rows = 0;
-    DHIPC(hipMalloc((void**)&h->d_ceps, (size_t)rows * h->n_ceps * sizeof(float)));
-    if (h->poison) DHIPC(hipMemset(h->d_ceps, 0xFF, (size_t)rows * h->n_ceps * sizeof(float)));
-    h->cap_rows = rows;
+  if (rows > d.cap_rows && h->n_ceps > 0) {
+    d.cap_rows = 0;
+    VXC(d.ceps.alloc((size_t)rows * h->n_ceps));
+    d.cap_rows = rows;
   }
   return VX_OK;
 }
@@ -170,16 +115,16 @@ hipError_t launch_dtw_warp(const float* d_cost, unsigned char* d_bp, const DtwPa
 }  // namespace
 
 extern "C" int vx_dtw_create(const vx_dtw_config* cfg, vx_dtw** out) {
-  if (!cfg || !out) return dfail(VX_ERR_ARG, "vx_dtw_create: null argument");
+  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_dtw_create: null argument");
   if (cfg->struct_size != (int32_t)sizeof(vx_dtw_config))
-    return dfail(VX_ERR_ARG, "vx_dtw_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_dtw_config));
-  if (cfg->max_batch < 1) return dfail(VX_ERR_ARG, "vx_dtw_create: max_batch = %d", cfg->max_batch);
-  if (cfg->dim < 1 || cfg->dim > DTW_MAX_DIM) return dfail(VX_ERR_UNSUPPORTED, "vx_dtw_create: dim = %d outside [1, %d]", cfg->dim, DTW_MAX_DIM);
+    return fail(VX_ERR_ARG, "vx_dtw_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_dtw_config));
+  if (cfg->max_batch < 1) return fail(VX_ERR_ARG, "vx_dtw_create: max_batch = %d", cfg->max_batch);
+  if (cfg->dim < 1 || cfg->dim > DTW_MAX_DIM) return fail(VX_ERR_UNSUPPORTED, "vx_dtw_create: dim = %d outside [1, %d]", cfg->dim, DTW_MAX_DIM);
   if (cfg->n_ceps < 0 || cfg->n_ceps > cfg->dim - 1)
-    return dfail(VX_ERR_UNSUPPORTED, "vx_dtw_create: n_ceps = %d outside [0, dim - 1 = %d]", cfg->n_ceps, cfg->dim - 1);
+    return fail(VX_ERR_UNSUPPORTED, "vx_dtw_create: n_ceps = %d outside [0, dim - 1 = %d]", cfg->n_ceps, cfg->dim - 1);
   if (cfg->max_frames < 1 || cfg->max_frames > DTW_MAX_FRAMES)
-    return dfail(VX_ERR_UNSUPPORTED, "vx_dtw_create: max_frames = %d outside [1, %d]", cfg->max_frames, DTW_MAX_FRAMES);
-  if (cfg->max_batch > DTW_MAX_BATCH) return dfail(VX_ERR_UNSUPPORTED, "vx_dtw_create: max_batch = %d > %d", cfg->max_batch, DTW_MAX_BATCH);
+    return fail(VX_ERR_UNSUPPORTED, "vx_dtw_create: max_frames = %d outside [1, %d]", cfg->max_frames, DTW_MAX_FRAMES);
+  if (cfg->max_batch > DTW_MAX_BATCH) return fail(VX_ERR_UNSUPPORTED, "vx_dtw_create: max_batch = %d > %d", cfg->max_batch, DTW_MAX_BATCH);
   vx_dtw* h = new vx_dtw();
   h->dim = cfg->dim; h->n_ceps = cfg->n_ceps; h->max_frames = cfg->max_frames; h->max_batch = cfg->max_batch;
   h->tab = dct_table(cfg->dim, cfg->n_ceps);
@@ -190,26 +135,26 @@ extern "C" int vx_dtw_create(const vx_dtw_config* cfg, vx_dtw** out) {
 extern "C" void vx_dtw_destroy(vx_dtw* h) {
   if (!h) return;
   if (h->device >= 0) {
-    DDevGuard g(h->device);
-    if (h->ev_done) (void)hipEventSynchronize(h->ev_done);
-    dtw_free_device(h);
+    DevGuard g(h->device);
+    (void)h->dev->stage.drain();
+    h->dev.reset();
   }
   delete h;
 }
 
 extern "C" int vx_dtw_compare(vx_dtw* h, int32_t n, const float* const* a, const int32_t* Ta, const float* const* b, const int32_t* Tb,
                               double* total, int32_t* path_len, int32_t* const* path, void* stream) {
-  if (!h || !a || !Ta || !b || !Tb || !total || !path_len) return dfail(VX_ERR_ARG, "vx_dtw_compare: null argument");
-  if (n < 1) return dfail(VX_ERR_ARG, "vx_dtw_compare: n = %d pairs", n);
-  if (n > h->max_batch) return dfail(VX_ERR_CAPACITY, "vx_dtw_compare: n = %d pairs > max_batch %d", n, h->max_batch);
+  if (!h || !a || !Ta || !b || !Tb || !total || !path_len) return fail(VX_ERR_ARG, "vx_dtw_compare: null argument");
+  if (n < 1) return fail(VX_ERR_ARG, "vx_dtw_compare: n = %d pairs", n);
+  if (n > h->max_batch) return fail(VX_ERR_CAPACITY, "vx_dtw_compare: n = %d pairs > max_batch %d", n, h->max_batch);
   std::vector<DtwPair> ps(n);
   long long cells = 0, rows = 0, max_rows = 0;
   int tiles = 0, max_ta = 0;
   for (int i = 0; i < n; ++i) {
-    if (!a[i] || !b[i]) return dfail(VX_ERR_ARG, "vx_dtw_compare: pair %d: null pointer", i);
-    if (Ta[i] < 1 || Tb[i] < 1) return dfail(VX_ERR_ARG, "vx_dtw_compare: pair %d: %d x %d frames", i, Ta[i], Tb[i]);
+    if (!a[i] || !b[i]) return fail(VX_ERR_ARG, "vx_dtw_compare: pair %d: null pointer", i);
+    if (Ta[i] < 1 || Tb[i] < 1) return fail(VX_ERR_ARG, "vx_dtw_compare: pair %d: %d x %d frames", i, Ta[i], Tb[i]);
     if (Ta[i] > h->max_frames || Tb[i] > h->max_frames)
-      return dfail(VX_ERR_CAPACITY, "vx_dtw_compare: pair %d: %d x %d frames > max_frames %d", i, Ta[i], Tb[i], h->max_frames);
+      return fail(VX_ERR_CAPACITY, "vx_dtw_compare: pair %d: %d x %d frames > max_frames %d", i, Ta[i], Tb[i], h->max_frames);
     DtwPair& p = ps[i];
     p.a = a[i]; p.b = b[i]; p.path = path ? path[i] : nullptr;
     p.cell_off = cells; p.ceps_off = rows * h->n_ceps;
@@ -222,81 +167,75 @@ extern "C" int vx_dtw_compare(vx_dtw* h, int32_t n, const float* const* a, const
   }
   if (h->device < 0) {
     const int rc = dtw_init_device(h);
-    if (rc != VX_OK) {
-      dtw_free_device(h);
+    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
+      h->dev.reset();
       h->device = -1;
       return rc;
     }
   }
-  DDevGuard g(h->device);
-  DHIPC(g.err);
+  DevGuard g(h->device);
+  HIPC(g.err);
+  DtwDev& d = *h->dev;
   hipStream_t s = (hipStream_t)stream;
-  DHIPC(hipEventSynchronize(h->ev_copy));  // the previous call's copy out of the pinned buffer has completed
-  {
-    const int rc = dtw_grow(h, cells, rows);
-    if (rc != VX_OK) return rc;
-  }
-  DHIPC(hipStreamWaitEvent(s, h->ev_done, 0));  // the previous call, on whatever stream it ran, is done with stage and workspace
-  memcpy(h->stage_host, ps.data(), (size_t)n * sizeof(DtwPair));
-  DHIPC(hipMemcpyAsync(h->stage_dev, h->stage_host, (size_t)n * sizeof(DtwPair), hipMemcpyHostToDevice, s));
-  DHIPC(hipEventRecord(h->ev_copy, s));
-  const DtwPair* dp = (const DtwPair*)h->stage_dev;
-  launch_dtw_cost(dp, n, tiles, max_rows, h->d_tab, h->dim, h->n_ceps, h->d_ceps, h->d_cost, s);
-  DHIPC(hipGetLastError());
-  DHIPC(launch_dtw_warp(h->d_cost, h->d_bp, dp, n, max_ta, h->d_total, h->d_len, s));
-  hipError_t e1 = hipMemcpyAsync(total, h->d_total, (size_t)n * sizeof(double), hipMemcpyDefault, s);
-  hipError_t e2 = hipMemcpyAsync(path_len, h->d_len, (size_t)n * sizeof(int), hipMemcpyDefault, s);
-  DHIPC(hipEventRecord(h->ev_done, s));
-  DHIPC(e1);
-  DHIPC(e2);
+  VXC(dtw_grow(h, cells, rows));
+  VXC(d.stage.begin(s));
+  memcpy(d.stage.host<DtwPair>(), ps.data(), (size_t)n * sizeof(DtwPair));
+  VXC(d.stage.upload((size_t)n * sizeof(DtwPair), s));
+  const DtwPair* dp = d.stage.dev<const DtwPair>();
+  launch_dtw_cost(dp, n, tiles, max_rows, d.tab.get(), h->dim, h->n_ceps, d.ceps.get(), d.cost.get(), s);
+  HIPC(hipGetLastError());
+  HIPC(launch_dtw_warp(d.cost.get(), d.bp.get(), dp, n, max_ta, d.total.get(), d.len.get(), s));
+  hipError_t e1 = hipMemcpyAsync(total, d.total.get(), (size_t)n * sizeof(double), hipMemcpyDefault, s);
+  hipError_t e2 = hipMemcpyAsync(path_len, d.len.get(), (size_t)n * sizeof(int), hipMemcpyDefault, s);
+  VXC(d.stage.finish(s));
+  HIPC(e1);
+  HIPC(e2);
   return VX_OK;
 }
 
 // The cepstra and cost kernels of one pair on caller data; synchronous.
 extern "C" int vx_op_dtw_cost(int32_t dim, int32_t n_ceps, const float* a, int32_t Ta, const float* b, int32_t Tb, float* cost,
                               void* stream) {
-  if (!a || !b || !cost) return dfail(VX_ERR_ARG, "vx_op_dtw_cost: null argument");
+  if (!a || !b || !cost) return fail(VX_ERR_ARG, "vx_op_dtw_cost: null argument");
   if (dim < 1 || dim > DTW_MAX_DIM || n_ceps < 0 || n_ceps > dim - 1)
-    return dfail(VX_ERR_ARG, "vx_op_dtw_cost: dim = %d, n_ceps = %d (dim in [1, %d], n_ceps in [0, dim - 1])", dim, n_ceps, DTW_MAX_DIM);
+    return fail(VX_ERR_ARG, "vx_op_dtw_cost: dim = %d, n_ceps = %d (dim in [1, %d], n_ceps in [0, dim - 1])", dim, n_ceps, DTW_MAX_DIM);
   if (Ta < 1 || Tb < 1 || Ta > DTW_MAX_FRAMES || Tb > DTW_MAX_FRAMES)
-    return dfail(VX_ERR_ARG, "vx_op_dtw_cost: %d x %d frames (1 .. %d each)", Ta, Tb, DTW_MAX_FRAMES);
+    return fail(VX_ERR_ARG, "vx_op_dtw_cost: %d x %d frames (1 .. %d each)", Ta, Tb, DTW_MAX_FRAMES);
   DtwPair p{};
   p.a = a; p.b = b; p.Ta = Ta; p.Tb = Tb;
   const int tiles = ((Ta + DTW_TILE - 1) / DTW_TILE) * ((Tb + DTW_TILE - 1) / DTW_TILE);
   const std::vector<float> tab = dct_table(dim, n_ceps);
   hipStream_t s = (hipStream_t)stream;
-  void *d_p = nullptr, *d_tab = nullptr, *d_ceps = nullptr;
-  hipError_t err = hipMalloc(&d_p, sizeof(DtwPair));
-  if (err == hipSuccess && n_ceps > 0) err = hipMalloc(&d_tab, tab.size() * sizeof(float));
-  if (err == hipSuccess && n_ceps > 0) err = hipMalloc(&d_ceps, (size_t)(Ta + Tb) * n_ceps * sizeof(float));
-  if (err == hipSuccess) err = hipMemcpyAsync(d_p, &p, sizeof(DtwPair), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess && n_ceps > 0) err = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess) {
-    launch_dtw_cost((const DtwPair*)d_p, 1, tiles, (long long)Ta + Tb, (const float*)d_tab, dim, n_ceps, (float*)d_ceps, cost, s);
-    err = hipGetLastError();
+  DevBuf<DtwPair> d_p;
+  DevBuf<float> d_tab, d_ceps;
+  VXC(d_p.alloc(1));
+  if (n_ceps > 0) {
+    VXC(d_tab.alloc(tab.size()));
+    VXC(d_ceps.alloc((size_t)(Ta + Tb) * n_ceps));
   }
+  VXC(d_p.upload(&p, 1, s));
+  if (n_ceps > 0) VXC(d_tab.upload(tab.data(), tab.size(), s));
+  launch_dtw_cost(d_p.get(), 1, tiles, (long long)Ta + Tb, d_tab.get(), dim, n_ceps, d_ceps.get(), cost, s);
+  const hipError_t err = hipGetLastError();
   const hipError_t err2 = hipStreamSynchronize(s);  // also: `p` and `tab` outlive their copies
-  (void)hipFree(d_p);
-  (void)hipFree(d_tab);
-  (void)hipFree(d_ceps);
-  DHIPC(err);
-  DHIPC(err2);
+  HIPC(err);
+  HIPC(err2);
   return VX_OK;
 }
 
 // desc: n x 4 host values per matrix (Ta, Tb, cell_off, path_off); synchronous.
 extern "C" int vx_op_dtw_path(const float* cost, int32_t n, const int64_t* desc, double* total, int32_t* path_len, int32_t* path,
                               void* stream) {
-  if (!cost || !desc || !total || !path_len) return dfail(VX_ERR_ARG, "vx_op_dtw_path: null argument");
-  if (n < 1) return dfail(VX_ERR_ARG, "vx_op_dtw_path: n = %d matrices", n);
+  if (!cost || !desc || !total || !path_len) return fail(VX_ERR_ARG, "vx_op_dtw_path: null argument");
+  if (n < 1) return fail(VX_ERR_ARG, "vx_op_dtw_path: n = %d matrices", n);
   std::vector<DtwPair> ps(n);
   long long cells = 0;
   int max_ta = 0;
   for (int z = 0; z < n; ++z) {
     const int64_t* d = desc + 4 * (size_t)z;
-    if (d[0] < 1 || d[1] < 1 || d[2] < 0 || d[3] < 0) return dfail(VX_ERR_ARG, "vx_op_dtw_path: matrix %d: Ta and Tb must be >= 1, offsets >= 0", z);
+    if (d[0] < 1 || d[1] < 1 || d[2] < 0 || d[3] < 0) return fail(VX_ERR_ARG, "vx_op_dtw_path: matrix %d: Ta and Tb must be >= 1, offsets >= 0", z);
     if (d[0] > DTW_MAX_FRAMES || d[1] > DTW_MAX_FRAMES)
-      return dfail(VX_ERR_CAPACITY, "vx_op_dtw_path: matrix %d: %lld x %lld frames (at most %d each)", z, (long long)d[0], (long long)d[1], DTW_MAX_FRAMES);
+      return fail(VX_ERR_CAPACITY, "vx_op_dtw_path: matrix %d: %lld x %lld frames (at most %d each)", z, (long long)d[0], (long long)d[1], DTW_MAX_FRAMES);
     DtwPair& p = ps[z];
     p = DtwPair{};
     p.Ta = (int)d[0]; p.Tb = (int)d[1]; p.cell_off = d[2];
@@ -305,15 +244,14 @@ extern "C" int vx_op_dtw_path(const float* cost, int32_t n, const int64_t* desc,
     max_ta = std::max(max_ta, p.Ta);
   }
   hipStream_t s = (hipStream_t)stream;
-  void *d_p = nullptr, *bp = nullptr;
-  hipError_t err = hipMalloc(&d_p, ps.size() * sizeof(DtwPair));
-  if (err == hipSuccess) err = hipMalloc(&bp, (size_t)cells);
-  if (err == hipSuccess) err = hipMemcpyAsync(d_p, ps.data(), ps.size() * sizeof(DtwPair), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess) err = launch_dtw_warp(cost, (unsigned char*)bp, (const DtwPair*)d_p, n, max_ta, total, path_len, s);
+  DevBuf<DtwPair> d_p;
+  DevBuf<unsigned char> bp;
+  VXC(d_p.alloc(ps.size()));
+  VXC(bp.alloc((size_t)cells));
+  VXC(d_p.upload(ps.data(), ps.size(), s));
+  const hipError_t err = launch_dtw_warp(cost, bp.get(), d_p.get(), n, max_ta, total, path_len, s);
   const hipError_t err2 = hipStreamSynchronize(s);
-  (void)hipFree(d_p);
-  (void)hipFree(bp);
-  DHIPC(err);
-  DHIPC(err2);
+  HIPC(err);
+  HIPC(err2);
   return VX_OK;
 }

@@ -14,7 +14,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/vallex.h"
+#include "host.hpp"
 #ifdef VX_STAMPS
 __device__ unsigned long long g_vx_stamps[32];
 __device__ unsigned long long* g_vx_kstamps = nullptr;
@@ -32,8 +32,9 @@ __device__ unsigned long long* g_fq_stamps = nullptr;
 using namespace vx;
 
 // ------------------------------------------------------------------------------ errors
+// the one definition behind every unit's fail / HIPC (host.hpp)
 static thread_local std::string g_err;
-static int fail(int code, const char* fmt, ...) {
+int vx::fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -42,36 +43,8 @@ static int fail(int code, const char* fmt, ...) {
   g_err = buf;
   return code;
 }
-#define HIPC(expr)                                                                                  \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return fail(VX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                      __FILE__, __LINE__);                                          \
-  } while (0)
-#define VXC(expr)               \
-  do {                          \
-    int r_ = (expr);            \
-    if (r_ != VX_OK) return r_; \
-  } while (0)
 
 extern "C" const char* vx_last_error(void) { return g_err.c_str(); }
-// codec.hip (the vx_codec_* entry points) reports through the same thread-local message; not part of the C ABI
-extern "C" __attribute__((visibility("hidden"))) void vx_internal_set_error(const char* msg) { g_err = msg ? msg : ""; }
-
-// Every entry point runs on the engine's device and leaves the caller's current device as it found it.
-struct DevGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DevGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else if (err == hipSuccess) prev = -1;  // already current: nothing to restore
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#define ON_DEVICE(dev)   \
-  DevGuard dev_guard_(dev); \
-  HIPC(dev_guard_.err)
 
 // ------------------------------------------------------------------------------ engine state
 struct Tensor {
@@ -243,15 +216,9 @@ struct vx_engine {
   size_t arena_used = 256, arena_cap = (size_t)4 << 20;  // no sub-block equals the base pointer (which `allocs` owns)
 };
 
-// VX_POISON=1 (tests): every fresh device allocation is filled with 0xFF bytes (NaN as bf16 / fp32, -1 as integers)
-// before the engine's own initialisation runs, so a read of memory nothing wrote shows up as NaN output instead of
-// depending on what the allocator happened to hand back.
-static bool poison_on() {
-  static const bool on = [] { const char* v = getenv("VX_POISON"); return v && atoi(v) != 0; }();
-  return on;
-}
-// Every fill below goes to the engine's stream: `es` is a non-blocking stream, a null-stream hipMemset is not ordered with the
-// kernels enqueued on it right afterwards (a fill landing late would wipe rows the first kernels had already written).
+// Every VX_POISON fill (poison_on(), host.hpp) below goes to the engine's stream: `es` is a non-blocking stream, a null-stream
+// hipMemset is not ordered with the kernels enqueued on it right afterwards (a fill landing late would wipe rows the first kernels
+// had already written).
 static int dalloc(vx_engine* e, void** p, size_t bytes) {
   // small blocks (the decode step's vectors, states, per-site norm parameters) share ONE 4 MB block: one translation entry
   // serves them all (each is touched by every workgroup of every launch of the step)
@@ -418,7 +385,7 @@ extern "C" int vx_create(const vx_config* cfg, vx_engine** out) {
   if (c.precision != VX_PREC_F32 && c.precision != VX_PREC_BF16 && c.precision != VX_PREC_FP8_NAR) return fail(VX_ERR_ARG, "bad precision");
   if (c.precision == VX_PREC_FP8_NAR && (c.num_quantizers < 2 || c.nar_d_model % 256 || c.nar_d_model / c.nar_nhead != 64 ||
                                          (c.flags & (VX_FLAG_POST_NORM | VX_FLAG_PRENET | VX_FLAG_SIMPLE_ROWS))))
-    return fail(VX_ERR_UNSUPPORTED, "VX_PREC_FP8_NAR needs a pre-norm NAR stack without prenets, head_dim 64 and nar_d_model % 256 == 0");
+    return fail(VX_ERR_UNSUPPORTED, "VX_PREC_FP8_NAR needs a pre-norm NAR stack without prenets, head_dim 64 and nar_d_model %% 256 == 0");
   if ((c.flags & (VX_FLAG_POST_NORM | VX_FLAG_PRENET)) && c.max_batch > 1)
     return fail(VX_ERR_UNSUPPORTED, "post-norm / prenet models (VALL-E or VALL-F) run on the batch-1 path only");
   if ((c.flags & VX_FLAG_VALLF) && c.precision == VX_PREC_FP8_NAR) return fail(VX_ERR_UNSUPPORTED, "VX_PREC_FP8_NAR is built for VALL-E only");
@@ -2500,6 +2467,15 @@ extern "C" int vx_nar_continual(vx_engine* e, const int64_t* text_nar, int32_t S
   return vx_nar_ex(e, text_nar, S2, prompts, P, ar_tokens, T, codes_out, nullptr, nullptr, 1, stream);
 }
 
+// A grown buffer replaces *p (null: a first allocation); a caller that replaces a live one has drained e->es.  `allocs` owns it.
+static int regrow(vx_engine* e, void** p, size_t bytes) {
+  for (auto& q : e->allocs) if (*p && q == *p) { (void)hipFree(q); q = nullptr; }
+  HIPC(hipMalloc(p, bytes));
+  if (poison_on()) { HIPC(hipMemsetAsync(*p, 0xFF, bytes, e->es)); HIPC(hipStreamSynchronize(e->es)); }
+  e->allocs.push_back(*p);
+  return VX_OK;
+}
+
 // Row buffers are sized for one utterance at vx_create; the batched NAR concatenates up to max_batch of them.
 static int ensure_rows(vx_engine* e, size_t rows, size_t audio_rows, size_t text_rows) {
   const vx_config& c = e->cfg;
@@ -2510,50 +2486,43 @@ static int ensure_rows(vx_engine* e, size_t rows, size_t audio_rows, size_t text
   if (text_rows < e->cap_text) text_rows = e->cap_text;
   e->cap_audio = audio_rows; e->cap_text = text_rows;
   HIPC(hipStreamSynchronize(e->es));
-  auto regrow = [&](void** p, size_t bytes) -> int {
-    for (auto& q : e->allocs) if (q == *p) { (void)hipFree(q); q = nullptr; }
-    HIPC(hipMalloc(p, bytes));
-    if (poison_on()) { HIPC(hipMemsetAsync(*p, 0xFF, bytes, e->es)); HIPC(hipStreamSynchronize(e->es)); }
-    e->allocs.push_back(*p);
-    return VX_OK;
-  };
   e->n_max = (int)rows;
   e->vt_ld = (int)(((rows + 63) / 64) * 64 + 64);
-  VXC(regrow((void**)&e->X, rows * dmax * 4));
-  VXC(regrow(&e->Hn, rows * dmax * e->esz));
-  VXC(regrow(&e->QKV, rows * 3 * dmax * e->esz));
-  VXC(regrow(&e->ATT, rows * dmax * e->esz));
+  VXC(regrow(e, (void**)&e->X, rows * dmax * 4));
+  VXC(regrow(e, &e->Hn, rows * dmax * e->esz));
+  VXC(regrow(e, &e->QKV, rows * 3 * dmax * e->esz));
+  VXC(regrow(e, &e->ATT, rows * dmax * e->esz));
   HIPC(hipMemsetAsync(e->ATT, 0, rows * dmax * e->esz, e->es));  // padding rows between segments are never written: keep them finite
-  VXC(regrow(&e->FF, rows * 4 * dmax * e->esz));
-  VXC(regrow(&e->VT, dmax * (size_t)e->vt_ld * 2));
+  VXC(regrow(e, &e->FF, rows * 4 * dmax * e->esz));
+  VXC(regrow(e, &e->VT, dmax * (size_t)e->vt_ld * 2));
   HIPC(hipMemsetAsync(e->VT, 0, dmax * (size_t)e->vt_ld * 2, e->es));
   HIPC(hipMemsetAsync(e->X, 0, rows * dmax * 4, e->es));
   if (e->fp8nar) {
     e->mx_ld = (int)((rows + 255) / 256 * 256);
-    VXC(regrow((void**)&e->Hn8, rows * dmax));
-    VXC(regrow((void**)&e->FF8, rows * 4 * dmax));
-    VXC(regrow((void**)&e->SHn, (dmax / 32) * (size_t)e->mx_ld));
-    VXC(regrow((void**)&e->SFF, (4 * dmax / 32) * (size_t)e->mx_ld));
+    VXC(regrow(e, (void**)&e->Hn8, rows * dmax));
+    VXC(regrow(e, (void**)&e->FF8, rows * 4 * dmax));
+    VXC(regrow(e, (void**)&e->SHn, (dmax / 32) * (size_t)e->mx_ld));
+    VXC(regrow(e, (void**)&e->SFF, (4 * dmax / 32) * (size_t)e->mx_ld));
     HIPC(hipMemsetAsync(e->SHn, 0, (dmax / 32) * (size_t)e->mx_ld, e->es));
     HIPC(hipMemsetAsync(e->SFF, 0, (4 * dmax / 32) * (size_t)e->mx_ld, e->es));
   }
   if (e->slab != nullptr) {  // keep the split-K path available for concatenated rows below the 256^2 threshold
     e->slab_rows = rows < 4095 ? (int)rows : 4095;
-    VXC(regrow((void**)&e->slab, (size_t)4 * e->slab_rows * dmax * 4));
+    VXC(regrow(e, (void**)&e->slab, (size_t)4 * e->slab_rows * dmax * 4));
   }
-  VXC(regrow((void**)&e->yemb, audio_rows * dmax * 4));
-  VXC(regrow((void**)&e->nar_logits, audio_rows * 1024 * 4));
-  VXC(regrow((void**)&e->ids_text, text_rows * 8));
-  VXC(regrow((void**)&e->ids_prompts, audio_rows * 8 * 8));
-  VXC(regrow((void**)&e->ids_samples, audio_rows * 8));
-  VXC(regrow((void**)&e->d_codes, audio_rows * 8 * 8));
-  VXC(regrow((void**)&e->d_fcodes, audio_rows * 8 * 8));
+  VXC(regrow(e, (void**)&e->yemb, audio_rows * dmax * 4));
+  VXC(regrow(e, (void**)&e->nar_logits, audio_rows * 1024 * 4));
+  VXC(regrow(e, (void**)&e->ids_text, text_rows * 8));
+  VXC(regrow(e, (void**)&e->ids_prompts, audio_rows * 8 * 8));
+  VXC(regrow(e, (void**)&e->ids_samples, audio_rows * 8));
+  VXC(regrow(e, (void**)&e->d_codes, audio_rows * 8 * 8));
+  VXC(regrow(e, (void**)&e->d_fcodes, audio_rows * 8 * 8));
   if (e->nar_lp != nullptr) {  // VX_FLAG_LOGPROBS; the last call's values do not survive the move
-    VXC(regrow((void**)&e->nar_lp, (size_t)(c.num_quantizers - 1) * audio_rows * 4));
+    VXC(regrow(e, (void**)&e->nar_lp, (size_t)(c.num_quantizers - 1) * audio_rows * 4));
     e->nlp_off.clear(); e->nlp_T.clear();
   }
   if (e->xmem_rows != nullptr)  // VX_FLAG_VALLF_ROWS: the packed text memory of the batched NAR, cap_text rows per head
-    VXC(regrow((void**)&e->xmem_rows, (size_t)c.nar_num_layers * 2 * c.nar_d_model * text_rows * 2));
+    VXC(regrow(e, (void**)&e->xmem_rows, (size_t)c.nar_num_layers * 2 * c.nar_d_model * text_rows * 2));
   return VX_OK;
 }
 
@@ -2606,18 +2575,11 @@ static int score_reserve(vx_engine* e, size_t rows) {
   if (rows <= e->sc_cap) return VX_OK;
   HIPC(hipStreamSynchronize(e->es));
   e->sc_rows = 0;  // the "score_ar_argmax" tap describes the buffer that goes away here
-  auto regrow = [&](void** p, size_t bytes) -> int {
-    for (auto& q : e->allocs) if (*p && q == *p) { (void)hipFree(q); q = nullptr; }
-    HIPC(hipMalloc(p, bytes));
-    if (poison_on()) { HIPC(hipMemsetAsync(*p, 0xFF, bytes, e->es)); HIPC(hipStreamSynchronize(e->es)); }
-    e->allocs.push_back(*p);
-    return VX_OK;
-  };
-  VXC(regrow((void**)&e->sc_logits, rows * e->sc_ld * 4));
-  VXC(regrow((void**)&e->sc_nll, rows * 4));
-  VXC(regrow((void**)&e->sc_rank, rows * 4));
-  VXC(regrow((void**)&e->sc_argmax, rows * 4));
-  VXC(regrow((void**)&e->sc_tgt, rows * 8));
+  VXC(regrow(e, (void**)&e->sc_logits, rows * e->sc_ld * 4));
+  VXC(regrow(e, (void**)&e->sc_nll, rows * 4));
+  VXC(regrow(e, (void**)&e->sc_rank, rows * 4));
+  VXC(regrow(e, (void**)&e->sc_argmax, rows * 4));
+  VXC(regrow(e, (void**)&e->sc_tgt, rows * 8));
   e->sc_cap = rows;
   return VX_OK;
 }
@@ -2845,35 +2807,28 @@ extern "C" int vx_score_batch(vx_engine* e, int32_t n, const int64_t* const* tex
 // Scratch of vx_align / vx_align_batch for maps of `cells` cells and T rows in all, nw head weights and, when staged, ph_cells
 // per-head cells; scr_floats: the per-head scratch of the batched tap (0: none).
 static int align_reserve(vx_engine* e, size_t cells, size_t T, size_t nw, size_t ph_cells, size_t scr_floats = 0) {
-  auto regrow = [&](void** p, size_t bytes) -> int {
-    for (auto& q : e->allocs) if (*p && q == *p) { (void)hipFree(q); q = nullptr; }
-    HIPC(hipMalloc(p, bytes));
-    if (poison_on()) { HIPC(hipMemsetAsync(*p, 0xFF, bytes, e->es)); HIPC(hipStreamSynchronize(e->es)); }
-    e->allocs.push_back(*p);
-    return VX_OK;
-  };
-  if (e->al_w == nullptr) { VXC(regrow((void**)&e->al_w, nw * 4)); VXC(regrow((void**)&e->al_score, 8)); }
+  if (e->al_w == nullptr) { VXC(regrow(e, (void**)&e->al_w, nw * 4)); VXC(regrow(e, (void**)&e->al_score, 8)); }
   if (scr_floats && e->al_segs == nullptr) {
-    VXC(regrow((void**)&e->al_segs, (size_t)2 * BMAX * sizeof(AlignSeg)));
-    VXC(regrow((void**)&e->al_bscore, (size_t)BMAX * 8));
+    VXC(regrow(e, (void**)&e->al_segs, (size_t)2 * BMAX * sizeof(AlignSeg)));
+    VXC(regrow(e, (void**)&e->al_bscore, (size_t)BMAX * 8));
   }
   if (cells > e->al_cells || T > e->al_rows || ph_cells > e->al_ph_cells || scr_floats > e->al_scr_floats) HIPC(hipStreamSynchronize(e->es));
   if (cells > e->al_cells) {
-    VXC(regrow((void**)&e->al_attn, cells * 4));
-    VXC(regrow((void**)&e->al_bp, cells));
+    VXC(regrow(e, (void**)&e->al_attn, cells * 4));
+    VXC(regrow(e, (void**)&e->al_bp, cells));
     e->al_cells = cells;
   }
   if (scr_floats > e->al_scr_floats) {
-    VXC(regrow((void**)&e->al_scr, scr_floats * 4));
+    VXC(regrow(e, (void**)&e->al_scr, scr_floats * 4));
     e->al_scr_floats = scr_floats;
   }
   if (T > e->al_rows) {
-    VXC(regrow((void**)&e->al_mass, T * 4));
-    VXC(regrow((void**)&e->al_path, T * 4));
+    VXC(regrow(e, (void**)&e->al_mass, T * 4));
+    VXC(regrow(e, (void**)&e->al_path, T * 4));
     e->al_rows = T;
   }
   if (ph_cells > e->al_ph_cells) {
-    VXC(regrow((void**)&e->al_ph, ph_cells * 4));
+    VXC(regrow(e, (void**)&e->al_ph, ph_cells * 4));
     e->al_ph_cells = ph_cells;
   }
   return VX_OK;
@@ -3190,27 +3145,24 @@ extern "C" int vx_op_gemm_mx(const float* A, const float* Wt, const float* bias,
   if (out_mode == 2 && !sc_out) return fail(VX_ERR_ARG, "mx gemm: out_mode 2 needs sc_out");  // arguments first, allocations after
   hipStream_t s = (hipStream_t)stream;
   const int ld = (M + 255) / 256 * 256;
-  struct Scratch {  // freed on every exit path
-    uint8_t *qa = nullptr, *sa = nullptr, *qw = nullptr, *sw = nullptr;
-    ~Scratch() { (void)hipFree(qa); (void)hipFree(sa); (void)hipFree(qw); (void)hipFree(sw); }
-  } t;
-  HIPC(hipMalloc((void**)&t.qa, (size_t)M * K)); HIPC(hipMalloc((void**)&t.sa, (size_t)(K / 32) * ld));
-  HIPC(hipMalloc((void**)&t.qw, (size_t)N * K)); HIPC(hipMalloc((void**)&t.sw, (size_t)(K / 32) * N));
-  HIPC(hipMemsetAsync(t.sa, 0, (size_t)(K / 32) * ld, s));
-  mx_quant_rows_kernel<<<(M + 3) / 4, 256, 0, s>>>(A, t.qa, t.sa, M, K, ld);
-  mx_quant_rows_kernel<<<(N + 3) / 4, 256, 0, s>>>(Wt, t.qw, t.sw, N, K, N);
+  DevBuf<uint8_t> qa, sa, qw, sw;
+  VXC(qa.alloc((size_t)M * K)); VXC(sa.alloc((size_t)(K / 32) * ld));
+  VXC(qw.alloc((size_t)N * K)); VXC(sw.alloc((size_t)(K / 32) * N));
+  HIPC(hipMemsetAsync(sa.get(), 0, (size_t)(K / 32) * ld, s));
+  mx_quant_rows_kernel<<<(M + 3) / 4, 256, 0, s>>>(A, qa.get(), sa.get(), M, K, ld);
+  mx_quant_rows_kernel<<<(N + 3) / 4, 256, 0, s>>>(Wt, qw.get(), sw.get(), N, K, N);
   HIPC(hipGetLastError());  // a quantiser launch failure is reported as such, not as the GEMM's
   int rc;
   if (out_mode == 2) {
     HIPC(hipMemsetAsync(sc_out, 0, (size_t)(N / 32) * ld, s));
-    rc = mx_gemm_dispatch(t.qa, t.sa, ld, t.qw, t.sw, N, bias, c_out, (uint8_t*)sc_out, ld, M, N, K, GE_RELU, MX_OUT_MX, s);
+    rc = mx_gemm_dispatch(qa.get(), sa.get(), ld, qw.get(), sw.get(), N, bias, c_out, (uint8_t*)sc_out, ld, M, N, K, GE_RELU, MX_OUT_MX, s);
   } else {
-    rc = mx_gemm_dispatch(t.qa, t.sa, ld, t.qw, t.sw, N, bias, c_out, nullptr, 0, M, N, K, relu ? GE_RELU : (bias ? GE_BIAS : GE_PLAIN), MX_OUT_F32, s);
+    rc = mx_gemm_dispatch(qa.get(), sa.get(), ld, qw.get(), sw.get(), N, bias, c_out, nullptr, 0, M, N, K, relu ? GE_RELU : (bias ? GE_BIAS : GE_PLAIN), MX_OUT_F32, s);
   }
   hipError_t le = hipGetLastError();
   if (rc == 0 && le == hipSuccess) {
-    if (qa_out) le = hipMemcpyAsync(qa_out, t.qa, (size_t)M * K, hipMemcpyDefault, s);
-    if (le == hipSuccess && sa_out) le = hipMemcpyAsync(sa_out, t.sa, (size_t)(K / 32) * ld, hipMemcpyDefault, s);
+    if (qa_out) le = hipMemcpyAsync(qa_out, qa.get(), (size_t)M * K, hipMemcpyDefault, s);
+    if (le == hipSuccess && sa_out) le = hipMemcpyAsync(sa_out, sa.get(), (size_t)(K / 32) * ld, hipMemcpyDefault, s);
   }
   const hipError_t se = hipStreamSynchronize(s);  // the scratch is in use until the stream has drained, whatever happened
   if (rc) return fail(VX_ERR_UNSUPPORTED, "mx gemm: no kernel instance (rc %d)", rc);
@@ -3280,11 +3232,10 @@ extern "C" int vx_op_mono_path(const float* attn, int32_t T, int32_t Sw, int32_t
   if (!attn || !path || !score) return fail(VX_ERR_ARG, "null argument");
   if (T < 1 || Sw < 1) return fail(VX_ERR_ARG, "T and Sw must be >= 1");
   if (Sw > ALIGN_MAX_SW) return fail(VX_ERR_CAPACITY, "a path over %d text tokens (at most %d)", Sw, ALIGN_MAX_SW);
-  unsigned char* bp = nullptr;
-  HIPC(hipMalloc((void**)&bp, (size_t)T * Sw));
-  launch_mono_path(attn, T, Sw, bp, path, score, (hipStream_t)stream);
+  DevBuf<unsigned char> bp;
+  VXC(bp.alloc((size_t)T * Sw));
+  launch_mono_path(attn, T, Sw, bp.get(), path, score, (hipStream_t)stream);
   const hipError_t err = hipGetLastError(), err2 = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(bp);
   HIPC(err);
   HIPC(err2);
   return VX_OK;
@@ -3321,20 +3272,15 @@ extern "C" int vx_op_attn_text_segs(const void* q, const void* k, int64_t ld, in
     max_rows = std::max(max_rows, g.rows);
   }
   hipStream_t s = (hipStream_t)stream;
-  const size_t scr_bytes = align_seg_scratch(nhead, cells, rows_total) * 4;
-  void *d_sg = nullptr, *scr = nullptr;
-  HIPC(hipMalloc(&d_sg, sg.size() * sizeof(AlignSeg)));
-  hipError_t err = hipMalloc(&scr, scr_bytes);
-  if (err == hipSuccess) err = hipMemcpyAsync(d_sg, sg.data(), sg.size() * sizeof(AlignSeg), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess) err = hipMemsetAsync(scr, 0xFF, scr_bytes, s);
-  if (err == hipSuccess) {
-    launch_attn_text_segs(q, k, ld, (const AlignSeg*)d_sg, nseg, max_rows, nhead, head_w, (float*)scr, cells, rows_total, attn, mass,
-                          first ? 1 : 0, s);
-    err = hipGetLastError();
-  }
-  const hipError_t err2 = hipStreamSynchronize(s);
-  (void)hipFree(d_sg);
-  (void)hipFree(scr);
+  const size_t scr_floats = align_seg_scratch(nhead, cells, rows_total);
+  DevBuf<AlignSeg> d_sg;
+  DevBuf<float> scr;
+  VXC(d_sg.alloc(sg.size()));
+  VXC(scr.alloc(scr_floats));
+  VXC(d_sg.upload(sg.data(), sg.size(), s));
+  HIPC(hipMemsetAsync(scr.get(), 0xFF, scr_floats * 4, s));
+  launch_attn_text_segs(q, k, ld, d_sg.get(), nseg, max_rows, nhead, head_w, scr.get(), cells, rows_total, attn, mass, first ? 1 : 0, s);
+  const hipError_t err = hipGetLastError(), err2 = hipStreamSynchronize(s);
   HIPC(err);
   HIPC(err2);
   return VX_OK;
@@ -3355,17 +3301,13 @@ extern "C" int vx_op_mono_path_segs(const float* attn, int32_t n, const int64_t*
     cells = std::max(cells, sg[z].cell_off + (long long)sg[z].rows * sg[z].c1);
   }
   hipStream_t s = (hipStream_t)stream;
-  void *d_sg = nullptr, *bp = nullptr;
-  HIPC(hipMalloc(&d_sg, sg.size() * sizeof(AlignSeg)));
-  hipError_t err = hipMalloc(&bp, (size_t)cells);
-  if (err == hipSuccess) err = hipMemcpyAsync(d_sg, sg.data(), sg.size() * sizeof(AlignSeg), hipMemcpyHostToDevice, s);
-  if (err == hipSuccess) {
-    launch_mono_path_segs(attn, (const AlignSeg*)d_sg, n, max_sw, (unsigned char*)bp, path, score, s);
-    err = hipGetLastError();
-  }
-  const hipError_t err2 = hipStreamSynchronize(s);
-  (void)hipFree(d_sg);
-  (void)hipFree(bp);
+  DevBuf<AlignSeg> d_sg;
+  DevBuf<unsigned char> bp;
+  VXC(d_sg.alloc(sg.size()));
+  VXC(bp.alloc((size_t)cells));
+  VXC(d_sg.upload(sg.data(), sg.size(), s));
+  launch_mono_path_segs(attn, d_sg.get(), n, max_sw, bp.get(), path, score, s);
+  const hipError_t err = hipGetLastError(), err2 = hipStreamSynchronize(s);
   HIPC(err);
   HIPC(err2);
   return VX_OK;
@@ -3385,37 +3327,48 @@ extern "C" int vx_op_nll_rows(const float* logits, int32_t rows, int32_t V, int3
   return VX_OK;
 }
 
-extern "C" int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
-                            int32_t* out, void* stream) {
-  if (V < 2 || V > 2048) return fail(VX_ERR_UNSUPPORTED, "sample: V=%d", V);
-  hipStream_t s = (hipStream_t)stream;
+// The three sampling entries below: a scratch state built from `h`, one sampler launch on the caller's logits, and the words it
+// wrote read back (out[0] = sampled index, out[1] = argmax; lp_out: the log-probability SAMPLE_LP adds).
+enum SampleLaunch { SAMPLE_4WAVE, SAMPLE_1WAVE, SAMPLE_LP };  // sample_embed4_kernel<5, 17> / sample_embed_kernel<32> / launch_sample_lp
+static ArState op_sample_state(int32_t top_k, float temperature, float top_p, const float* exp_noise) {
   ArState h{};
-  h.S = 1 << 20; h.kv_text = h.S; h.top_k = top_k; h.temperature = temperature; h.max_new = -1;
+  h.S = 1 << 20; h.kv_text = h.S; h.top_k = top_k; h.temperature = temperature; h.max_new = -1; h.top_p = top_p;
   h.exp_noise = exp_noise; h.noise_rows = 1; h.seed = 1;
-  ArState* dst = nullptr;
-  int* scratch = nullptr;
-  float* fz = nullptr;
-  HIPC(hipMalloc((void**)&dst, sizeof h));
-  HIPC(hipMalloc((void**)&scratch, 16 * sizeof(int)));
-  HIPC(hipMalloc((void**)&fz, 4096 * sizeof(float)));
-  HIPC(hipMemsetAsync(fz, 0, 4096 * sizeof(float), s));
-  HIPC(hipMemcpyAsync(dst, &h, sizeof h, hipMemcpyHostToDevice, s));
+  return h;
+}
+static int op_sample_run(const ArState& h, const float* logits, int32_t V, SampleLaunch which, int32_t* out, float* lp_out, hipStream_t s) {
+  DevBuf<ArState> dst;
+  DevBuf<int> words;
+  DevBuf<float> fz;
+  VXC(dst.alloc(1));
+  VXC(words.alloc(16));
+  VXC(fz.alloc(4096));
+  HIPC(hipMemsetAsync(fz.get(), 0, 4096 * sizeof(float), s));
+  VXC(dst.upload(&h, 1, s));
   SampleArgs sa{};
-  sa.logits = logits; sa.V = V; sa.st = dst;
-  sa.tokens = scratch; sa.sampled = scratch + 4; sa.argmaxes = scratch + 8;
-  sa.emb = fz; sa.alpha = fz; sa.pe = fz; sa.x = fz + 2048; sa.d = 0;
-  // both variants are exercised by the parity test: the 4-wave kernel of the decode step for the model's vocabulary,
-  // the single-wave one for larger test vocabularies
-  if (V <= 17 * 64) sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(sa);
-  else sample_embed_kernel<32><<<1, 64, 0, s>>>(sa);
+  sa.logits = logits; sa.V = V; sa.st = dst.get();
+  sa.tokens = words.get(); sa.sampled = words.get() + 4; sa.argmaxes = words.get() + 8;
+  sa.emb = fz.get(); sa.alpha = fz.get(); sa.pe = fz.get(); sa.x = fz.get() + 2048; sa.d = 0;
+  if (which == SAMPLE_4WAVE) sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(sa);
+  else if (which == SAMPLE_1WAVE) sample_embed_kernel<32><<<1, 64, 0, s>>>(sa);
+  else launch_sample_lp(sa, reinterpret_cast<float*>(words.get() + 12), -1, 1, s);
   HIPC(hipGetLastError());
   int host[16];
-  HIPC(hipMemcpyAsync(host, scratch, sizeof host, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(host, words.get(), sizeof host, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
   out[0] = host[4];
   out[1] = host[8];
-  (void)hipFree(dst); (void)hipFree(scratch); (void)hipFree(fz);
+  if (lp_out) memcpy(lp_out, &host[12], sizeof(float));
   return VX_OK;
+}
+
+extern "C" int vx_op_sample(const float* logits, int32_t V, int32_t top_k, float temperature, const float* exp_noise,
+                            int32_t* out, void* stream) {
+  if (V < 2 || V > 2048) return fail(VX_ERR_UNSUPPORTED, "sample: V=%d", V);
+  // both variants are exercised by the parity test: the 4-wave kernel of the decode step for the model's vocabulary,
+  // the single-wave one for larger test vocabularies
+  return op_sample_run(op_sample_state(top_k, temperature, 0.f, exp_noise), logits, V, V <= 17 * 64 ? SAMPLE_4WAVE : SAMPLE_1WAVE, out,
+                       nullptr, (hipStream_t)stream);
 }
 
 // vx_op_sample with the nucleus filter: the same scratch state with top_p, on the decode step's four-wave sampler.
@@ -3426,31 +3379,7 @@ extern "C" int vx_op_sample_topp(const float* logits, int32_t V, int32_t top_k, 
   const float tp = state_top_p(top_p);
   if (tp == 0.f) return vx_op_sample(logits, V, top_k, temperature, exp_noise, out, stream);
   if (V < 2 || V > 17 * 64) return fail(VX_ERR_UNSUPPORTED, "sample_topp: V=%d (the nucleus filter is built for V <= 1088)", V);
-  hipStream_t s = (hipStream_t)stream;
-  ArState h{};
-  h.S = 1 << 20; h.kv_text = h.S; h.top_k = top_k; h.temperature = temperature; h.max_new = -1; h.top_p = tp;
-  h.exp_noise = exp_noise; h.noise_rows = 1; h.seed = 1;
-  ArState* dst = nullptr;
-  int* scratch = nullptr;
-  float* fz = nullptr;
-  HIPC(hipMalloc((void**)&dst, sizeof h));
-  HIPC(hipMalloc((void**)&scratch, 16 * sizeof(int)));
-  HIPC(hipMalloc((void**)&fz, 4096 * sizeof(float)));
-  HIPC(hipMemsetAsync(fz, 0, 4096 * sizeof(float), s));
-  HIPC(hipMemcpyAsync(dst, &h, sizeof h, hipMemcpyHostToDevice, s));
-  SampleArgs sa{};
-  sa.logits = logits; sa.V = V; sa.st = dst;
-  sa.tokens = scratch; sa.sampled = scratch + 4; sa.argmaxes = scratch + 8;
-  sa.emb = fz; sa.alpha = fz; sa.pe = fz; sa.x = fz + 2048; sa.d = 0;
-  sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(sa);
-  HIPC(hipGetLastError());
-  int host[16];
-  HIPC(hipMemcpyAsync(host, scratch, sizeof host, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  out[0] = host[4];
-  out[1] = host[8];
-  (void)hipFree(dst); (void)hipFree(scratch); (void)hipFree(fz);
-  return VX_OK;
+  return op_sample_run(op_sample_state(top_k, temperature, tp, exp_noise), logits, V, SAMPLE_4WAVE, out, nullptr, (hipStream_t)stream);
 }
 
 // vx_op_sample_topp on the sampler's VX_FLAG_LOGPROBS instantiation (logprob.hip): the same scratch state, the same [sampled, argmax], and
@@ -3460,34 +3389,8 @@ extern "C" int vx_op_sample_logprob(const float* logits, int32_t V, int32_t top_
   if (!logits || !out || !lp_out) return fail(VX_ERR_ARG, "null argument");
   VXC(check_top_p(top_p));
   if (V < 2 || V > 17 * 64) return fail(VX_ERR_UNSUPPORTED, "sample_logprob: V=%d (built for 2 <= V <= 1088)", V);
-  hipStream_t s = (hipStream_t)stream;
-  ArState h{};
-  h.S = 1 << 20; h.kv_text = h.S; h.top_k = top_k; h.temperature = temperature; h.max_new = -1; h.top_p = state_top_p(top_p);
-  h.exp_noise = exp_noise; h.noise_rows = 1; h.seed = 1;
-  struct Scratch {  // freed on every return
-    ArState* dst = nullptr;
-    int* words = nullptr;
-    float* fz = nullptr;
-    ~Scratch() { (void)hipFree(dst); (void)hipFree(words); (void)hipFree(fz); }
-  } m;
-  HIPC(hipMalloc((void**)&m.dst, sizeof h));
-  HIPC(hipMalloc((void**)&m.words, 16 * sizeof(int)));
-  HIPC(hipMalloc((void**)&m.fz, 4096 * sizeof(float)));
-  HIPC(hipMemsetAsync(m.fz, 0, 4096 * sizeof(float), s));
-  HIPC(hipMemcpyAsync(m.dst, &h, sizeof h, hipMemcpyHostToDevice, s));
-  SampleArgs sa{};
-  sa.logits = logits; sa.V = V; sa.st = m.dst;
-  sa.tokens = m.words; sa.sampled = m.words + 4; sa.argmaxes = m.words + 8;
-  sa.emb = m.fz; sa.alpha = m.fz; sa.pe = m.fz; sa.x = m.fz + 2048; sa.d = 0;
-  launch_sample_lp(sa, reinterpret_cast<float*>(m.words + 12), -1, 1, s);
-  HIPC(hipGetLastError());
-  int host[16];
-  HIPC(hipMemcpyAsync(host, m.words, sizeof host, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  out[0] = host[4];
-  out[1] = host[8];
-  memcpy(lp_out, &host[12], sizeof(float));
-  return VX_OK;
+  return op_sample_run(op_sample_state(top_k, temperature, state_top_p(top_p), exp_noise), logits, V, SAMPLE_LP, out, lp_out,
+                       (hipStream_t)stream);
 }
 
 // Segmented flash attention (the batched NAR / batched prefill launch of attn_rows) on caller rows: nseg segments of a bf16 qkv
@@ -3512,19 +3415,17 @@ extern "C" int vx_op_attention_segs(const void* qkv, void* out, int32_t rows, in
   hipStream_t s = (hipStream_t)stream;
   const int d = nhead * hd;
   const int vt_ld = ((rows + 63) / 64) * 64 + 64;  // as the engine (the key-group split reads one tile past the last)
-  struct Scratch {  // freed on every exit path
-    bf16* vt = nullptr;
-    int* segs = nullptr;
-    ~Scratch() { (void)hipFree(vt); (void)hipFree(segs); }
-  } t;
-  HIPC(hipMalloc((void**)&t.vt, (size_t)d * vt_ld * 2));
-  HIPC(hipMalloc((void**)&t.segs, (size_t)3 * nseg * sizeof(int)));
-  HIPC(hipMemcpyAsync(t.segs, seg_start, nseg * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(t.segs + nseg, seg_len, nseg * sizeof(int), hipMemcpyHostToDevice, s));
-  if (seg_text) HIPC(hipMemcpyAsync(t.segs + 2 * nseg, seg_text, nseg * sizeof(int), hipMemcpyHostToDevice, s));
-  vt_from_qkv_kernel<<<dim3((vt_ld + 255) / 256, d), 256, 0, s>>>((const bf16*)qkv, t.vt, rows, d, vt_ld);
-  const int rc = mfma_attn_dispatch((const bf16*)qkv, t.vt, vt_ld, (bf16*)out, rows, d, nhead, -1, s, t.segs, t.segs + nseg, nseg,
-                                    max_len, seg_text ? t.segs + 2 * nseg : nullptr);
+  DevBuf<bf16> vt;
+  DevBuf<int> segs_buf;  // start | len | text, nseg each
+  VXC(vt.alloc((size_t)d * vt_ld));
+  VXC(segs_buf.alloc((size_t)3 * nseg));
+  int* segs = segs_buf.get();
+  HIPC(hipMemcpyAsync(segs, seg_start, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(segs + nseg, seg_len, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  if (seg_text) HIPC(hipMemcpyAsync(segs + 2 * nseg, seg_text, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  vt_from_qkv_kernel<<<dim3((vt_ld + 255) / 256, d), 256, 0, s>>>((const bf16*)qkv, vt.get(), rows, d, vt_ld);
+  const int rc = mfma_attn_dispatch((const bf16*)qkv, vt.get(), vt_ld, (bf16*)out, rows, d, nhead, -1, s, segs, segs + nseg, nseg,
+                                    max_len, seg_text ? segs + 2 * nseg : nullptr);
   const hipError_t le = hipGetLastError();
   const hipError_t se = hipStreamSynchronize(s);  // the scratch is in use until the stream has drained, whatever happened
   if (rc) return fail(VX_ERR_UNSUPPORTED, "attention_segs: rows x 3 d or d x vt_ld exceed 4 GB");
@@ -3559,20 +3460,18 @@ extern "C" int vx_op_cross_attention_segs(const void* q, int32_t ldq, const void
   }
   if (!q || !mem || !out) return fail(VX_ERR_ARG, "cross_attention_segs: null q, mem or out");
   hipStream_t s = (hipStream_t)stream;
-  struct Scratch {  // freed on every exit path
-    int* segs = nullptr;
-    long long* off = nullptr;
-    ~Scratch() { (void)hipFree(segs); (void)hipFree(off); }
-  } t;
   std::vector<long long> off(mem_off, mem_off + nseg);
-  HIPC(hipMalloc((void**)&t.segs, (size_t)3 * nseg * sizeof(int)));
-  HIPC(hipMalloc((void**)&t.off, (size_t)nseg * sizeof(long long)));
-  HIPC(hipMemcpyAsync(t.segs, seg_start, nseg * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(t.segs + nseg, seg_len, nseg * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(t.segs + 2 * nseg, klen, nseg * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(t.off, off.data(), nseg * sizeof(long long), hipMemcpyHostToDevice, s));
-  cross_attn_seg_launch((const bf16*)q, ldq, (const bf16*)mem, t.off, head_stride, v_offset, t.segs + 2 * nseg, (bf16*)out, nhead * 64, nhead,
-                        t.segs, t.segs + nseg, nseg, max_len, s);
+  DevBuf<int> segs_buf;  // start | len | klen, nseg each
+  DevBuf<long long> d_off;
+  VXC(segs_buf.alloc((size_t)3 * nseg));
+  VXC(d_off.alloc(nseg));
+  int* segs = segs_buf.get();
+  HIPC(hipMemcpyAsync(segs, seg_start, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(segs + nseg, seg_len, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(segs + 2 * nseg, klen, nseg * sizeof(int), hipMemcpyHostToDevice, s));
+  VXC(d_off.upload(off.data(), nseg, s));
+  cross_attn_seg_launch((const bf16*)q, ldq, (const bf16*)mem, d_off.get(), head_stride, v_offset, segs + 2 * nseg, (bf16*)out, nhead * 64, nhead,
+                        segs, segs + nseg, nseg, max_len, s);
   const hipError_t le = hipGetLastError();
   const hipError_t se = hipStreamSynchronize(s);  // the scratch is in use until the stream has drained, whatever happened
   HIPC(le);
@@ -3602,17 +3501,14 @@ extern "C" int vx_op_attn_slots(int32_t kv_fp8, const float* q, const void* kv, 
   }
   hipStream_t s = (hipStream_t)stream;
   const int d = 64 * nhead;
-  struct Scratch {  // freed on every exit path
-    ArState* st = nullptr;
-    ~Scratch() { (void)hipFree(st); }
-  } t;
-  HIPC(hipMalloc((void**)&t.st, (size_t)B * sizeof(ArState)));
-  HIPC(hipMemcpyAsync(t.st, h.data(), (size_t)B * sizeof(ArState), hipMemcpyHostToDevice, s));
+  DevBuf<ArState> st;
+  VXC(st.alloc(B));
+  VXC(st.upload(h.data(), B, s));
   if (kv_fp8)
     attn_batch8_kernel<64><<<dim3(nhead, B), 256, 0, s>>>(q, (const uint8_t*)kv, (const uint8_t*)kv_scale, (size_t)slot_stride,
-                                                          (size_t)v_offset, t.st, ctx_max, d, 0.125f, (bf16*)out);
+                                                          (size_t)v_offset, st.get(), ctx_max, d, 0.125f, (bf16*)out);
   else
-    attn_batch_kernel<64><<<dim3(nhead, B), 256, 0, s>>>(q, (const bf16*)kv, (size_t)slot_stride, (size_t)v_offset, t.st, ctx_max, d,
+    attn_batch_kernel<64><<<dim3(nhead, B), 256, 0, s>>>(q, (const bf16*)kv, (size_t)slot_stride, (size_t)v_offset, st.get(), ctx_max, d,
                                                          0.125f, (bf16*)out);
   const hipError_t le = hipGetLastError();
   const hipError_t se = hipStreamSynchronize(s);
@@ -3640,13 +3536,10 @@ extern "C" int vx_op_attn_mem_slots(const float* q, const void* mem, int64_t slo
     h[b].S = len[b];
   }
   hipStream_t s = (hipStream_t)stream;
-  struct Scratch {  // freed on every exit path
-    ArState* st = nullptr;
-    ~Scratch() { (void)hipFree(st); }
-  } t;
-  HIPC(hipMalloc((void**)&t.st, (size_t)B * sizeof(ArState)));
-  HIPC(hipMemcpyAsync(t.st, h.data(), (size_t)B * sizeof(ArState), hipMemcpyHostToDevice, s));
-  attn_batch_kernel<64, true><<<dim3(nhead, B), 256, 0, s>>>(q, (const bf16*)mem, (size_t)slot_stride, (size_t)v_offset, t.st, max_text,
+  DevBuf<ArState> st;
+  VXC(st.alloc(B));
+  VXC(st.upload(h.data(), B, s));
+  attn_batch_kernel<64, true><<<dim3(nhead, B), 256, 0, s>>>(q, (const bf16*)mem, (size_t)slot_stride, (size_t)v_offset, st.get(), max_text,
                                                              64 * nhead, 0.125f, (bf16*)out);
   const hipError_t le = hipGetLastError();
   const hipError_t se = hipStreamSynchronize(s);
@@ -3702,22 +3595,19 @@ extern "C" int vx_op_bgemm(int32_t epi, int32_t kv8, const void* A, const void* 
     if (h[b].row < 0 || h[b].pass < 0) return fail(VX_ERR_ARG, "bgemm: row[%d] / pass[%d] negative", b, b);
   }
   hipStream_t s = (hipStream_t)stream;
-  struct Scratch {  // freed on every exit path
-    ArState* st = nullptr;
-    int* map = nullptr;
-    ~Scratch() { (void)hipFree(st); (void)hipFree(map); }
-  } t;
-  HIPC(hipMalloc((void**)&t.st, (size_t)nst * sizeof(ArState)));
-  HIPC(hipMemcpyAsync(t.st, h.data(), (size_t)nst * sizeof(ArState), hipMemcpyHostToDevice, s));
+  DevBuf<ArState> st;
+  DevBuf<int> d_map;
+  VXC(st.alloc(nst));
+  VXC(st.upload(h.data(), nst, s));
   if (map) {
-    HIPC(hipMalloc((void**)&t.map, (size_t)B * sizeof(int)));
-    HIPC(hipMemcpyAsync(t.map, slot_map, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    VXC(d_map.alloc(B));
+    VXC(d_map.upload(slot_map, B, s));
   }
   BgemmArgs a{};
-  a.A = (const bf16*)A; a.W = (const bf16*)W; a.bias = bias; a.N = N; a.K = K; a.B = B; a.kgroups = kgroups; a.st = t.st;
+  a.A = (const bf16*)A; a.W = (const bf16*)W; a.bias = bias; a.N = N; a.K = K; a.B = B; a.kgroups = kgroups; a.st = st.get();
   a.q = q; a.kv_slot_stride = (size_t)kv_slot_stride; a.kv_v_offset = (size_t)kv_v_offset; a.d = d; a.hd = 64; a.ctx_max = ctx_max;
   a.f = (bf16*)f; a.part = part; a.logits = logits; a.logits_stride = logits_stride; a.trace = trace; a.trace_rows = trace_rows;
-  a.slot_map = t.map;
+  a.slot_map = d_map.get();
   if (kv8) { a.kv8 = (uint8_t*)kv; a.kv8s = (uint8_t*)kv8s; } else { a.kv = (bf16*)kv; }
   int rc = VX_OK;
   switch (epi) {
@@ -3751,14 +3641,11 @@ extern "C" int vx_op_ln_batch(float* x, const float* part, int32_t kgroups, cons
       if (slot_map[z] < 0 || slot_map[z] >= BMAX) return fail(VX_ERR_ARG, "ln_batch: slot_map[%d] = %d outside [0, %d)", z, slot_map[z], BMAX);
   }
   hipStream_t s = (hipStream_t)stream;
-  struct Scratch {  // freed on every exit path
-    int* map = nullptr;
-    ~Scratch() { (void)hipFree(map); }
-  } t;
+  DevBuf<int> d_map;
   if (slot_map) {
-    HIPC(hipMalloc((void**)&t.map, (size_t)B * sizeof(int)));
-    HIPC(hipMemcpyAsync(t.map, slot_map, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-    ln_batch_map_kernel<<<B, 256, 0, s>>>(x, gamma, beta, (bf16*)h, d, t.map);
+    VXC(d_map.alloc(B));
+    VXC(d_map.upload(slot_map, B, s));
+    ln_batch_map_kernel<<<B, 256, 0, s>>>(x, gamma, beta, (bf16*)h, d, d_map.get());
   } else {
     launch_ln_batch(x, kgroups ? part : nullptr, kgroups, pbias, gamma, beta, (bf16*)h, B, d, s);
   }

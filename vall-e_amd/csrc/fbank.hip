@@ -1,39 +1,29 @@
-// Log-mel filterbank behind the C ABI (include/vallex.h, vx_fbank_*): the host tables, the staging of a ragged call and the one
-// launch of fbank_kernels.hpp.  A translation unit and a handle of its own, like logprob.hip and align.hip: no other unit sees
+// Log-mel filterbank behind the C ABI (include/vallex.h, vx_fbank_*): the host tables, the staging of a ragged call (CallStage,
+// host.hpp) and the one launch of fbank_kernels.hpp.  A translation unit and a handle of its own, like logprob.hip and align.hip: no other unit sees
 // this kernel, so the device code of every existing path is compiled exactly as before.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #undef VX_STAMPS  // the in-kernel stamps write device globals of engine.hip's unit, out of this unit's reach
-#include "../../include/vallex.h"
+#include "host.hpp"
 #include "fbank_kernels.hpp"
 
 using namespace vx;
 
-extern "C" void vx_internal_set_error(const char* msg);  // engine.hip: the message vx_last_error() returns
-
-static int ffail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  vx_internal_set_error(buf);
-  return code;
-}
-#define FHIPC(expr)                                                                                                    \
-  do {                                                                                                                 \
-    hipError_t e_ = (expr);                                                                                            \
-    if (e_ != hipSuccess)                                                                                              \
-      return ffail(VX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);              \
-  } while (0)
+namespace {
+// Device side of a handle: made on the device that is current at the first vx_fbank_extract, dropped as a whole.
+struct FbankDev {
+  DevBuf<float> tab, basis_t;
+  DevBuf<int> band;
+  // per call: wav pointers [max_batch] | out pointers [max_batch] | tile0 [max_batch + 1] | len | frames [max_batch each]
+  CallStage stage;
+};
+}  // namespace
 
 struct vx_fbank {
   int n_mels = 0, max_batch = 0;
@@ -41,28 +31,11 @@ struct vx_fbank {
   std::vector<float> basis;  // [n_mels][513]
   std::vector<float> tab;    // window | cos | sin
   bool basis_dirty = true;   // the device copy is older than `basis`
-  // device side: made on the device that is current at the first vx_fbank_extract
-  int device = -1;
-  float *d_tab = nullptr, *d_basis_t = nullptr;
-  int* d_band = nullptr;
-  // per call: wav pointers [max_batch] | out pointers [max_batch] | tile0 [max_batch + 1] | len | frames [max_batch each]
-  char *stage_dev = nullptr, *stage_host = nullptr;
-  size_t stage_bytes = 0;
-  hipEvent_t ev_copy = nullptr, ev_done = nullptr;
+  int device = -1;  // >= 0: `dev` is complete
+  std::unique_ptr<FbankDev> dev;
 };
 
 namespace {
-
-struct FDevGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit FDevGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else if (err == hipSuccess) prev = -1;
-  }
-  ~FDevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // Slaney's mel scale (Auditory Toolbox): linear below 1 kHz at 200 / 3 Hz per mel, logarithmic above with step log(6.4) / 27.
 double hz_to_mel(double f) {
@@ -91,40 +64,19 @@ std::vector<float> slaney_basis(int sr, int n_mels, double fmin, double fmax) {
   return w;
 }
 
-void fbank_free_device(vx_fbank* fb) {
-  (void)hipFree(fb->d_tab);
-  (void)hipFree(fb->d_basis_t);
-  (void)hipFree(fb->d_band);
-  (void)hipFree(fb->stage_dev);
-  (void)hipHostFree(fb->stage_host);
-  for (hipEvent_t ev : {fb->ev_copy, fb->ev_done})
-    if (ev) (void)hipEventDestroy(ev);
-  fb->d_tab = fb->d_basis_t = nullptr; fb->d_band = nullptr; fb->stage_dev = fb->stage_host = nullptr; fb->ev_copy = fb->ev_done = nullptr;
-}
-
-// First use: the tables go to the current device.  VX_POISON=1 fills the fresh allocations with 0xFF bytes first, as the engine does.
+// First use: the tables go to the current device.
 int fbank_init_device(vx_fbank* fb) {
   int dev = 0;
-  FHIPC(hipGetDevice(&dev));
+  HIPC(hipGetDevice(&dev));
   fb->device = dev;
-  const char* pv = getenv("VX_POISON");
-  const bool poison = pv && atoi(pv) != 0;
-  const size_t MB = (size_t)fb->max_batch, nb = (size_t)fb->n_mels * FBANK_BINS;
-  fb->stage_bytes = 2 * MB * sizeof(void*) + (3 * MB + 1) * sizeof(int);
-  FHIPC(hipMalloc((void**)&fb->d_tab, FBANK_TAB * sizeof(float)));
-  FHIPC(hipMalloc((void**)&fb->d_basis_t, nb * sizeof(float)));
-  FHIPC(hipMalloc((void**)&fb->d_band, 2 * (size_t)fb->n_mels * sizeof(int)));
-  FHIPC(hipMalloc((void**)&fb->stage_dev, fb->stage_bytes));
-  if (poison) {
-    FHIPC(hipMemset(fb->d_tab, 0xFF, FBANK_TAB * sizeof(float)));
-    FHIPC(hipMemset(fb->d_basis_t, 0xFF, nb * sizeof(float)));
-    FHIPC(hipMemset(fb->d_band, 0xFF, 2 * (size_t)fb->n_mels * sizeof(int)));
-    FHIPC(hipMemset(fb->stage_dev, 0xFF, fb->stage_bytes));
-  }
-  FHIPC(hipHostMalloc((void**)&fb->stage_host, fb->stage_bytes));
-  FHIPC(hipMemcpy(fb->d_tab, fb->tab.data(), FBANK_TAB * sizeof(float), hipMemcpyHostToDevice));
-  FHIPC(hipEventCreateWithFlags(&fb->ev_copy, hipEventDisableTiming));
-  FHIPC(hipEventCreateWithFlags(&fb->ev_done, hipEventDisableTiming));
+  fb->dev.reset(new FbankDev());
+  FbankDev& d = *fb->dev;
+  const size_t MB = (size_t)fb->max_batch;
+  VXC(d.tab.alloc(FBANK_TAB));
+  VXC(d.basis_t.alloc((size_t)fb->n_mels * FBANK_BINS));
+  VXC(d.band.alloc(2 * (size_t)fb->n_mels));
+  VXC(d.stage.init(2 * MB * sizeof(void*) + (3 * MB + 1) * sizeof(int)));
+  HIPC(hipMemcpy(d.tab.get(), fb->tab.data(), FBANK_TAB * sizeof(float), hipMemcpyHostToDevice));
   fb->basis_dirty = true;
   return VX_OK;
 }
@@ -144,8 +96,8 @@ int fbank_upload_basis(vx_fbank* fb) {
     band[m] = hi < 0 ? 0 : lo;
     band[M + m] = hi;
   }
-  FHIPC(hipMemcpy(fb->d_basis_t, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-  FHIPC(hipMemcpy(fb->d_band, band.data(), band.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(fb->dev->basis_t.get(), t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(fb->dev->band.get(), band.data(), band.size() * sizeof(int), hipMemcpyHostToDevice));
   fb->basis_dirty = false;
   return VX_OK;
 }
@@ -157,18 +109,18 @@ extern "C" int64_t vx_fbank_frames(int64_t n_samples) {
 }
 
 extern "C" int vx_fbank_create(const vx_fbank_config* cfg, vx_fbank** out) {
-  if (!cfg || !out) return ffail(VX_ERR_ARG, "vx_fbank_create: null argument");
+  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_fbank_create: null argument");
   if (cfg->struct_size != (int32_t)sizeof(vx_fbank_config))
-    return ffail(VX_ERR_ARG, "vx_fbank_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_fbank_config));
-  if (cfg->max_batch < 1) return ffail(VX_ERR_ARG, "vx_fbank_create: max_batch = %d", cfg->max_batch);
-  if (!(cfg->clip > 0.f) || !isfinite(cfg->clip)) return ffail(VX_ERR_ARG, "vx_fbank_create: clip = %g (the floor under the log is positive)", cfg->clip);
+    return fail(VX_ERR_ARG, "vx_fbank_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_fbank_config));
+  if (cfg->max_batch < 1) return fail(VX_ERR_ARG, "vx_fbank_create: max_batch = %d", cfg->max_batch);
+  if (!(cfg->clip > 0.f) || !isfinite(cfg->clip)) return fail(VX_ERR_ARG, "vx_fbank_create: clip = %g (the floor under the log is positive)", cfg->clip);
   if (cfg->sample_rate != 24000 || cfg->n_fft != FBANK_NFFT || cfg->hop != FBANK_HOP)
-    return ffail(VX_ERR_UNSUPPORTED, "vx_fbank_create: %d Hz, n_fft %d, hop %d: 24000 / %d / %d is served", cfg->sample_rate, cfg->n_fft,
+    return fail(VX_ERR_UNSUPPORTED, "vx_fbank_create: %d Hz, n_fft %d, hop %d: 24000 / %d / %d is served", cfg->sample_rate, cfg->n_fft,
                  cfg->hop, FBANK_NFFT, FBANK_HOP);
   if (cfg->n_mels < 1 || cfg->n_mels > FBANK_MAX_MELS)
-    return ffail(VX_ERR_UNSUPPORTED, "vx_fbank_create: n_mels = %d outside [1, %d]", cfg->n_mels, FBANK_MAX_MELS);
+    return fail(VX_ERR_UNSUPPORTED, "vx_fbank_create: n_mels = %d outside [1, %d]", cfg->n_mels, FBANK_MAX_MELS);
   if (!(cfg->fmin >= 0.f) || !(cfg->fmin < cfg->fmax) || !(cfg->fmax <= 12000.f))
-    return ffail(VX_ERR_UNSUPPORTED, "vx_fbank_create: band %g .. %g Hz: 0 <= fmin < fmax <= 12000 is served", cfg->fmin, cfg->fmax);
+    return fail(VX_ERR_UNSUPPORTED, "vx_fbank_create: band %g .. %g Hz: 0 <= fmin < fmax <= 12000 is served", cfg->fmin, cfg->fmax);
   vx_fbank* fb = new vx_fbank();
   fb->n_mels = cfg->n_mels; fb->max_batch = cfg->max_batch; fb->clip = cfg->clip;
   fb->basis = slaney_basis(cfg->sample_rate, cfg->n_mels, cfg->fmin, cfg->fmax);
@@ -189,63 +141,62 @@ extern "C" int vx_fbank_create(const vx_fbank_config* cfg, vx_fbank** out) {
 extern "C" void vx_fbank_destroy(vx_fbank* fb) {
   if (!fb) return;
   if (fb->device >= 0) {
-    FDevGuard g(fb->device);
-    if (fb->ev_done) (void)hipEventSynchronize(fb->ev_done);
-    fbank_free_device(fb);
+    DevGuard g(fb->device);
+    (void)fb->dev->stage.drain();
+    fb->dev.reset();
   }
   delete fb;
 }
 
 extern "C" int vx_fbank_set_mel_basis(vx_fbank* fb, const float* basis) {
-  if (!fb || !basis) return ffail(VX_ERR_ARG, "vx_fbank_set_mel_basis: null argument");
+  if (!fb || !basis) return fail(VX_ERR_ARG, "vx_fbank_set_mel_basis: null argument");
   fb->basis.assign(basis, basis + (size_t)fb->n_mels * FBANK_BINS);
   fb->basis_dirty = true;
   return VX_OK;
 }
 
 extern "C" int vx_fbank_get_mel_basis(const vx_fbank* fb, float* basis) {
-  if (!fb || !basis) return ffail(VX_ERR_ARG, "vx_fbank_get_mel_basis: null argument");
+  if (!fb || !basis) return fail(VX_ERR_ARG, "vx_fbank_get_mel_basis: null argument");
   memcpy(basis, fb->basis.data(), fb->basis.size() * sizeof(float));
   return VX_OK;
 }
 
 extern "C" int vx_fbank_extract(vx_fbank* fb, int32_t n, const float* const* wav, const int32_t* n_samples, float* const* out,
                                 void* stream) {
-  if (!fb || !wav || !n_samples || !out) return ffail(VX_ERR_ARG, "vx_fbank_extract: null argument");
-  if (n < 1) return ffail(VX_ERR_ARG, "vx_fbank_extract: n = %d utterances", n);
-  if (n > fb->max_batch) return ffail(VX_ERR_CAPACITY, "vx_fbank_extract: n = %d utterances > max_batch %d", n, fb->max_batch);
+  if (!fb || !wav || !n_samples || !out) return fail(VX_ERR_ARG, "vx_fbank_extract: null argument");
+  if (n < 1) return fail(VX_ERR_ARG, "vx_fbank_extract: n = %d utterances", n);
+  if (n > fb->max_batch) return fail(VX_ERR_CAPACITY, "vx_fbank_extract: n = %d utterances > max_batch %d", n, fb->max_batch);
   std::vector<int> tile0(n + 1, 0), frames(n);
   for (int i = 0; i < n; ++i) {
-    if (!wav[i] || !out[i]) return ffail(VX_ERR_ARG, "vx_fbank_extract: utterance %d: null pointer", i);
-    if (n_samples[i] < 1) return ffail(VX_ERR_ARG, "vx_fbank_extract: utterance %d: %d samples", i, n_samples[i]);
+    if (!wav[i] || !out[i]) return fail(VX_ERR_ARG, "vx_fbank_extract: utterance %d: null pointer", i);
+    if (n_samples[i] < 1) return fail(VX_ERR_ARG, "vx_fbank_extract: utterance %d: %d samples", i, n_samples[i]);
     frames[i] = (int)vx_fbank_frames(n_samples[i]);
     const long tiles = tile0[i] + ((long)frames[i] + FBANK_TILE - 1) / FBANK_TILE;
-    if (tiles > 0x7fffffffL) return ffail(VX_ERR_UNSUPPORTED, "vx_fbank_extract: utterance %d: the call's tiles exceed int32", i);
+    if (tiles > 0x7fffffffL) return fail(VX_ERR_UNSUPPORTED, "vx_fbank_extract: utterance %d: the call's tiles exceed int32", i);
     tile0[i + 1] = (int)tiles;
   }
   if (tile0[n] == 0) return VX_OK;  // no utterance has a frame: nothing to write
   if (fb->device < 0) {
     const int rc = fbank_init_device(fb);
-    if (rc != VX_OK) {
-      fbank_free_device(fb);
+    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
+      fb->dev.reset();
       fb->device = -1;
       return rc;
     }
   }
-  FDevGuard g(fb->device);
-  FHIPC(g.err);
+  DevGuard g(fb->device);
+  HIPC(g.err);
+  FbankDev& d = *fb->dev;
   hipStream_t s = (hipStream_t)stream;
-  FHIPC(hipEventSynchronize(fb->ev_copy));  // the previous call's copy out of the pinned buffer has completed
   if (fb->basis_dirty) {
-    FHIPC(hipEventSynchronize(fb->ev_done));  // nothing reads the device copy of the basis any more
-    const int rc = fbank_upload_basis(fb);
-    if (rc != VX_OK) return rc;
+    VXC(d.stage.drain());  // nothing reads the device copy of the basis any more
+    VXC(fbank_upload_basis(fb));
   }
-  FHIPC(hipStreamWaitEvent(s, fb->ev_done, 0));  // the previous kernel, on whatever stream it ran, is done with the staged arrays
+  VXC(d.stage.begin(s));
   const size_t MB = (size_t)fb->max_batch;
-  const float** hin = (const float**)fb->stage_host;
-  float** hout = (float**)(fb->stage_host + MB * sizeof(void*));
-  int* hint = (int*)(fb->stage_host + 2 * MB * sizeof(void*));
+  const float** hin = d.stage.host<const float*>();
+  float** hout = d.stage.host<float*>(MB * sizeof(void*));
+  int* hint = d.stage.host<int>(2 * MB * sizeof(void*));
   for (int i = 0; i < n; ++i) {
     hin[i] = wav[i];
     hout[i] = out[i];
@@ -253,18 +204,16 @@ extern "C" int vx_fbank_extract(vx_fbank* fb, int32_t n, const float* const* wav
     hint[2 * MB + 1 + i] = frames[i];
   }
   memcpy(hint, tile0.data(), (n + 1) * sizeof(int));
-  FHIPC(hipMemcpyAsync(fb->stage_dev, fb->stage_host, fb->stage_bytes, hipMemcpyHostToDevice, s));
-  FHIPC(hipEventRecord(fb->ev_copy, s));
+  VXC(d.stage.upload(d.stage.bytes, s));
   FbankArgs a{};
-  a.wav = (const float* const*)fb->stage_dev;
-  a.out = (float* const*)(fb->stage_dev + MB * sizeof(void*));
-  const int* dint = (const int*)(fb->stage_dev + 2 * MB * sizeof(void*));
+  a.wav = d.stage.dev<const float* const>();
+  a.out = d.stage.dev<float* const>(MB * sizeof(void*));
+  const int* dint = d.stage.dev<const int>(2 * MB * sizeof(void*));
   a.tile0 = dint; a.len = dint + MB + 1; a.frames = dint + 2 * MB + 1;
-  a.tab = fb->d_tab; a.basis_t = fb->d_basis_t; a.band = fb->d_band;
+  a.tab = d.tab.get(); a.basis_t = d.basis_t.get(); a.band = d.band.get();
   a.nseg = n; a.n_mels = fb->n_mels; a.clip = fb->clip;
   const unsigned grid = (unsigned)std::min(tile0[n], 4096);
   fbank_kernel<<<grid, 256, 0, s>>>(a);
-  FHIPC(hipGetLastError());
-  FHIPC(hipEventRecord(fb->ev_done, s));
-  return VX_OK;
+  HIPC(hipGetLastError());
+  return d.stage.finish(s);
 }
