@@ -722,6 +722,90 @@ int vx_dtw_compare(vx_dtw* h, int32_t n, const float* const* a, const int32_t* T
 int vx_op_dtw_cost(int32_t dim, int32_t n_ceps, const float* a, int32_t Ta, const float* b, int32_t Tb, float* cost, void* stream);
 int vx_op_dtw_path(const float* cost, int32_t n, const int64_t* desc, double* total, int32_t* path_len, int32_t* path, void* stream);
 
+/* ---- the mel-spectrogram Transformer TTS model (valle/models/transformer.py, --model-name Transformer) ------------------------
+ * The reference's third model: a text encoder, a decoder over log-mel frames with cross-attention to the encoded text, a 100-wide
+ * regression head and a stop head.  There is no vocabulary and no sampler: the predicted frame itself is fed back through
+ * decoder_prenet.  A handle of its own (own weights, KV cache and captured step); batch 1, as the reference's loop.  Its decoder
+ * layer is the VALL-F one, its encoder the row stack without a mask, both through the code the token models run.
+ *   encode  (transformer.py:344-347): text_embedding -> encoder_prenet (identity, or 3 x [Conv1d k=5 same, BatchNorm1d eval, ReLU]
+ *           + Linear) -> x + alpha pe (scale=False) -> L encoder layers (ReLU, FFN 4 d) -> LayerNorm when norm_first; the result is
+ *           projected once into every decoder layer's cross-attention K / V.
+ *   decode  (transformer.py:353-385) with a KV cache, one step per frame where the reference recomputes every row on every pass
+ *           (its TODO at :352).  Input row 0 is decoder_prenet(0) + alpha pe[0]; pass p runs row p through the L decoder layers,
+ *           the final LayerNorm (norm_first) and predict_layer / stop_layer.  Stop rule, tested BEFORE the append (:377-383): rows
+ *           > 10 S (rows = p + 1) or stop logit > 0; the stopping pass's frame is dropped, so S ids give at most 10 S frames and a
+ *           stop on pass 0 gives none.  Otherwise the frame is appended and fed back at position p + 1.
+ * precision VX_PREC_F32 or VX_PREC_BF16 (bf16 attention / FFN matrices, GEMM operands and KV cache; the head, the prenets and the
+ * residual stream stay fp32).  scaling_xformers (ScaledLinear / BasicNorm / DoubleSwish, transformer.py:114-172) is not built. */
+typedef struct vx_mel vx_mel;
+enum vx_mel_stop {
+  VX_MEL_STOP_NONE = 0,
+  VX_MEL_STOP_LOGIT = 1,      /* stop_layer's logit > 0 (transformer.py:376) */
+  VX_MEL_STOP_LENGTH = 2,     /* rows > 10 S (transformer.py:377) */
+  VX_MEL_STOP_MAX_FRAMES = 3  /* engine-level max_frames (not in the reference); also how a teacher-forced decode ends */
+};
+enum vx_mel_flags { VX_MEL_NO_GRAPH = 1 /* launch the step kernel by kernel instead of as a hipGraph */ };
+/* Mirrors Transformer.__init__ (transformer.py:47-55). */
+typedef struct vx_mel_config {
+  int32_t struct_size;      /* = sizeof(vx_mel_config) */
+  int32_t d_model;          /* multiple of 8, <= 1024 */
+  int32_t nhead;            /* d_model / nhead in {4, 8, 16, 32, 64} */
+  int32_t num_layers;       /* encoder layers = decoder layers */
+  int32_t norm_first;
+  int32_t add_prenet;
+  int32_t scaling_xformers; /* != 0: VX_ERR_UNSUPPORTED */
+  int32_t precision;        /* VX_PREC_F32 or VX_PREC_BF16 */
+  int32_t max_text;         /* capacity: phoneme ids per utterance */
+  int32_t max_frames;       /* capacity: frames per utterance */
+  int32_t device;
+  int32_t flags;            /* enum vx_mel_flags */
+} vx_mel_config;
+/* Transformer(...) + .to(device) (transformer.py:47-207).  Checked before any HIP call: nulls, struct_size, non-positive sizes or
+ * capacities, an unknown precision -> VX_ERR_ARG; scaling_xformers, a width or head_dim outside the ranges above ->
+ * VX_ERR_UNSUPPORTED. */
+int vx_mel_create(const vx_mel_config* cfg, vx_mel** out);
+void vx_mel_destroy(vx_mel* m);
+/* model.load_state_dict, one tensor at a time, under the reference's state_dict keys (transformer.py:66-203):
+ * text_embedding.word_embeddings.weight, encoder_position.alpha, decoder_position.alpha, encoder.layers.N.* / decoder.layers.N.*
+ * (torch.nn.TransformerEncoderLayer / TransformerDecoderLayer), encoder.norm.* / decoder.norm.* (norm_first), predict_layer.*,
+ * stop_layer.*, decoder_prenet.weight / .bias or, with add_prenet, decoder_prenet.{0,3,6}.* and encoder_prenet.{1,5,9}.* (Conv1d),
+ * .{2,6,10}.{weight,bias,running_mean,running_var} (BatchNorm1d; num_batches_tracked is not passed), .14.* (Linear).  data: fp32,
+ * host or device.  Unknown key or wrong shape: VX_ERR_WEIGHTS. */
+int vx_mel_set_weight(vx_mel* m, const char* key, const float* data, const int64_t* shape, int32_t ndim);
+/* Optional: the fp32 table of SinePositionalEmbedding (modules/embedding.py:75-88), (rows, d_model) with rows >= max(4000, max_text +
+ * max_frames + 2); both positions share it.  If never set the handle fills it with host sinf / cosf. */
+int vx_mel_set_sine_table(vx_mel* m, const float* data, int64_t rows, int64_t dim);
+/* strict=True + model.eval(): a missing tensor is VX_ERR_WEIGHTS naming it. */
+int vx_mel_finalize(vx_mel* m);
+/* transformer.py:342-347: the encoder over text (S,) int64, host or device, and every decoder layer's memory K / V.  Checked before
+ * any HIP call: nulls -> VX_ERR_ARG; S <= 0 -> VX_ERR_ARG (:340); weights not finalised -> VX_ERR_STATE; S > max_text ->
+ * VX_ERR_CAPACITY. */
+int vx_mel_encode(vx_mel* m, const int64_t* text, int32_t S, void* stream);
+/* transformer.py:353-385 over the text of the last vx_mel_encode.  max_frames < 0: the reference's rule only; otherwise the decode
+ * also ends, with VX_MEL_STOP_MAX_FRAMES, once max_frames frames are appended and the next pass does not stop by the reference's
+ * rule: its frames are bitwise the first max_frames of the unlimited run.  max_frames above the handle's capacity: VX_ERR_CAPACITY
+ * before any work; with max_frames < 0 a text whose worst case 10 S exceeds the capacity is not refused, but a decode that fills the
+ * capacity before the reference's rule fired returns VX_ERR_CAPACITY.  No encode since create / finalize: VX_ERR_STATE. */
+int vx_mel_decode(vx_mel* m, int32_t max_frames, void* stream);
+/* Parity tests: the decode with the fed-back frames taken from `forced` (T, 100) fp32, host or device, instead of the predictions
+ * (which are still what vx_mel_result returns, with their stop logits): T passes, ends with VX_MEL_STOP_MAX_FRAMES, the reference's
+ * stop rule is not applied.  Pass p sees exactly the rows [0; forced[:p]] of the reference's forward (transformer.py:279-300). */
+int vx_mel_decode_forced(vx_mel* m, const float* forced, int32_t T, void* stream);
+/* The last decode: frames (n_frames, 100) fp32 into `frames` (host or device, room for `capacity` frames; rows past n_frames are
+ * not touched; NULL: counts only), the stop logit of every pass into stop_logits (host or device, nullable, room for capacity + 1
+ * values), n_pass of them: n_frames + 1, or n_frames after vx_mel_decode_forced.  capacity < n_frames: VX_ERR_CAPACITY. */
+int vx_mel_result(vx_mel* m, float* frames, int32_t capacity, int32_t* n_frames, int32_t* stop_reason, float* stop_logits,
+                  int32_t* n_pass);
+/* The quantities inside the reference's forward (transformer.py:279-300) for one utterance: text (S,), frames (T, 100) fp32; one
+ * causal row pass over [0; frames[:-1]] gives predict (T, 100) and stop_logits (T,) (host or device).  Encodes the text first (the
+ * handle is then as after vx_mel_encode(text, S)).  Checks as vx_mel_encode, and T < 1 -> VX_ERR_ARG, T > max_frames ->
+ * VX_ERR_CAPACITY. */
+int vx_mel_teacher_forced(vx_mel* m, const int64_t* text, int32_t S, const float* frames, int32_t T, float* predict,
+                          float* stop_logits, void* stream);
+/* out[0] ms of the last decode (device time of the replayed steps), out[1] its step launches, out[2] kernel launches per step (nodes
+ * of the captured graph; 0 with VX_MEL_NO_GRAPH), out[3] ms of the last encode. */
+int vx_mel_get_timings(vx_mel* m, double* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

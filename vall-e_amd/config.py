@@ -76,10 +76,21 @@ class ModelConfig:
         return cls(**kw)
 
 
+@dataclass
+class MelConfig:
+    """Constructor arguments of the reference's mel-spectrogram ``Transformer`` (models/transformer.py:47-55)."""
+
+    d_model: int = 1024
+    nhead: int = 16
+    num_layers: int = 12
+    norm_first: bool = True
+    add_prenet: bool = False
+
+
 def add_model_arguments(parser: argparse.ArgumentParser):
     """Same flags, defaults and dests as the reference (models/__init__.py:18-95).
-    ``--scaling-xformers`` is accepted for CLI compatibility; it only affects the reference's
-    debug mel-Transformer, which is outside the hot path."""
+    ``--scaling-xformers`` selects the ScaledLinear / BasicNorm variant of the mel-Transformer (``--model-name Transformer``),
+    which get_model refuses: that variant is not built."""
     parser.add_argument("--model-name", type=str, default="VALL-E")
     parser.add_argument("--decoder-dim", type=int, default=1024)
     parser.add_argument("--nhead", type=int, default=16)

@@ -28,6 +28,7 @@ __device__ unsigned long long* g_fq_stamps = nullptr;
 #include "mx_kernels.hpp"
 #include "logprob.hpp"
 #include "align.hpp"
+#include "meltf.hpp"
 
 using namespace vx;
 
@@ -80,6 +81,7 @@ struct vx_engine {
   uint8_t *Hn8 = nullptr, *SHn = nullptr, *FF8 = nullptr, *SFF = nullptr;  // MXFP8 row operands and their scales (ld = mx_ld)
   int mx_ld = 0;
   bool vallf = false;  // VX_FLAG_VALLF: decoder layers with cross-attention over the text (valle.py:49-719)
+  bool mel = false;    // the decoder side of a vx_mel handle (mel-Transformer, below): its own key table, no token head
   int npl = 2;         // norms per layer: 2 (encoder layers) / 3 (decoder layers)
   void *xkv_ar = nullptr, *xkv_nar = nullptr;  // VALL-F: per-layer K / V of the text memory, [layer][K|V][head][max_text][hd]
   int mem_len = 0;     // text rows of the current utterance's AR memory
@@ -264,9 +266,10 @@ static bool is_mx_key(const std::string& k) {  // the NAR stack's QKV / FFN matr
 }
 
 // The reference's state_dict layout (valle.py:85-259); mirrored by valle_amd/weights.py.
-static void add_encoder_keys(vx_engine* e, const std::string& pre, int d, int L, bool adaptive) {
+// with_cross: -1 = as the engine (decoder layers in a VALL-F engine), 0 / 1 = encoder / decoder layers whatever the engine is
+static void add_encoder_keys(vx_engine* e, const std::string& pre, int d, int L, bool adaptive, int with_cross = -1) {
   const bool post = e->cfg.flags & VX_FLAG_POST_NORM;  // norm=... if norm_first else None (valle.py:151, 242-246)
-  const bool cross = e->cfg.flags & VX_FLAG_VALLF;     // TransformerDecoderLayer (modules/transformer.py:412-500)
+  const bool cross = with_cross < 0 ? (e->cfg.flags & VX_FLAG_VALLF) != 0 : with_cross != 0;  // TransformerDecoderLayer (modules/transformer.py:412-500)
   auto add = [&](const std::string& k, std::vector<int64_t> s) {
     Tensor t; t.shape = s; t.numel = 1; for (auto v : s) t.numel *= (size_t)v;
     t.low = e->bf16 && is_matrix_key(k);
@@ -296,7 +299,9 @@ static void add_encoder_keys(vx_engine* e, const std::string& pre, int d, int L,
   if (!post) norm(pre + ".norm");
 }
 
+static void mel_key_table(vx_engine* e);
 static void build_key_table(vx_engine* e) {
+  if (e->mel) return mel_key_table(e);
   const vx_config& c = e->cfg;
   const int d = c.d_model, dn = c.nar_d_model, Q = c.num_quantizers;
   auto add = [&](const std::string& k, std::vector<int64_t> s) {
@@ -660,7 +665,8 @@ extern "C" int vx_set_sine_table(vx_engine* e, int32_t which, const float* data,
 
 template <typename T> static const T* W(vx_engine* e, const std::string& k) { return (const T*)e->w.at(k).p; }
 
-static void fill_layers(vx_engine* e, const std::string& pre, int L, bool adaptive, std::vector<LayerW>& out) {
+static void fill_layers(vx_engine* e, const std::string& pre, int L, bool adaptive, std::vector<LayerW>& out, int with_cross = -1) {
+  const bool cross = with_cross < 0 ? e->vallf : with_cross != 0;
   out.resize(L);
   for (int i = 0; i < L; ++i) {
     const std::string p = pre + ".layers." + std::to_string(i);
@@ -674,7 +680,7 @@ static void fill_layers(vx_engine* e, const std::string& pre, int L, bool adapti
     const std::string s = adaptive ? ".norm" : "";
     l.n1_g = W<float>(e, p + ".norm1" + s + ".weight"); l.n1_b = W<float>(e, p + ".norm1" + s + ".bias");
     l.n2_g = W<float>(e, p + ".norm2" + s + ".weight"); l.n2_b = W<float>(e, p + ".norm2" + s + ".bias");
-    if (e->vallf) {
+    if (cross) {
       l.cin_w = W<void>(e, p + ".multihead_attn.in_proj_weight"); l.cin_b = W<float>(e, p + ".multihead_attn.in_proj_bias");
       l.cout_w = W<void>(e, p + ".multihead_attn.out_proj.weight"); l.cout_b = W<float>(e, p + ".multihead_attn.out_proj.bias");
       l.n3_g = W<float>(e, p + ".norm3" + s + ".weight"); l.n3_b = W<float>(e, p + ".norm3" + s + ".bias");
@@ -1644,13 +1650,17 @@ static int launch_attn_decode(vx_engine* e, hipStream_t s, const void* kc, const
 // text memory, its out-projection; then FFN1, FFN2.  Every norm runs in the prologue of the GEMV that consumes it (front_site).
 // Post-norm (transformer.py:303-308): ar_x holds the raw sum x + block(x) of the previous block, and the prologue that normalises
 // it also leaves the normalised vector in ar_xn as the base of the next residual add.
-static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
+// mel: the step of a vx_mel handle - its opening kernel stands where the sampler does, the last layer leaves its row in mel->xh
+// for the next step's opening kernel and there is no token head.
+struct MelStep { MelStepArgs open; };
+static int enqueue_ar_step(vx_engine* e, hipStream_t s, const MelStep* mel = nullptr) {
   const vx_config& c = e->cfg;
   const int d = c.d_model, H = c.nhead, hd = d / H;
-  if (e->lpon) launch_sample_lp(step_sample_args(e), e->d_lp, NUM_AUDIO_TOKENS, 1, s);
+  if (mel) launch_mel_open(mel->open, s);
+  else if (e->lpon) launch_sample_lp(step_sample_args(e), e->d_lp, NUM_AUDIO_TOKENS, 1, s);
   else sample_embed4_kernel<5, 17><<<1, 256, 0, s>>>(step_sample_args(e));
   if (e->tp) return enqueue_ar_step_tp(e, s);
-  if (c.flags & VX_FLAG_PRENET) VXC(enqueue_audio_prenet(e, s));
+  if (!mel && (c.flags & VX_FLAG_PRENET)) VXC(enqueue_audio_prenet(e, s));
   const size_t kv_layer = (size_t)2 * H * e->ctx_max * hd * e->esz;
   const size_t mem_layer = (size_t)2 * d * c.max_text * e->esz;
   // Stamp ids (probe builds, step_sample_args): the 64-entry ring holds 5 launches per layer and 61 for the head, so a VALL-F
@@ -1666,7 +1676,7 @@ static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
     const LayerW& l = e->ar_l[li];
     seq.push_back({l.in_w, 3 * d, d}); seq.push_back({l.out_w, d, d}); seq.push_back({l.w1, 4 * d, d}); seq.push_back({l.w2, d, 4 * d});
   }
-  seq.push_back({W<void>(e, "ar_predict_layer.weight"), AR_VOCAB, d});
+  if (!mel) seq.push_back({W<void>(e, "ar_predict_layer.weight"), AR_VOCAB, d});
   auto warm = [&](GemvArgs& a, int idx) {
     if (pf_dist <= 0) return;
     const PfW& n = seq[(idx + pf_dist) % seq.size()];
@@ -1730,10 +1740,12 @@ static int enqueue_ar_step(vx_engine* e, hipStream_t s) {
     g.st = e->d_st;
     g.W = l.w2; g.bias = l.b2; g.x = e->ar_f; g.y = e->ar_x; g.N = d; g.K = 4 * d; g.pro = PRO_COPY; g.epi = EPI_RESID;
     g.res = fres;
+    if (mel && li == c.num_layers - 1) { g.y = const_cast<float*>(mel->open.xh); g.res = fres ? fres : e->ar_x; }
     warm(g, 4 * li + 3);
     g.kid = kid(li, 4);
     VXC(launch_gemv(e->bf16, g, e->num_cu, s));
   }
+  if (mel) return VX_OK;
   if (pf_dist > 0) {
     const PfW& n = seq[(4 * c.num_layers + pf_dist) % seq.size()];
     return enqueue_head(e, s, nullptr, nullptr, nullptr, false, n.W, n.N, n.K);
@@ -3653,6 +3665,375 @@ extern "C" int vx_op_ln_batch(float* x, const float* part, int32_t kgroups, cons
   const hipError_t se = hipStreamSynchronize(s);
   HIPC(le);
   HIPC(se);
+  return VX_OK;
+}
+
+// ------------------------------------------------------------------------------ mel-spectrogram Transformer (vx_mel_*)
+// valle/models/transformer.py.  The handle owns a vx_engine in VALL-F form that serves as its decoder side - the KV cache, the text
+// memory, the row buffers, the weights under the reference's own keys (mel_key_table) and the captured step - so the decoder
+// layers are run_stack's and enqueue_ar_step's launches as they are; the encoder is run_stack over encoder layers without a mask.
+// New: the step's opening kernel (meltf.hip), the fp32 head / prenet rows of the teacher-forced pass, and the stop rule.
+struct vx_mel {
+  vx_engine* e = nullptr;
+  vx_mel_config cfg{};
+  int cap = 0;  // frames
+  std::vector<LayerW> enc_l;
+  MelCtl* d_ctl = nullptr;
+  MelCtl h_ctl{};  // staging of d_ctl: lives as long as the copy may read it
+  float *xh = nullptr, *frames = nullptr, *stops = nullptr, *headW = nullptr, *headB = nullptr;
+  float *fin = nullptr, *ra = nullptr, *rh1 = nullptr, *rh2 = nullptr, *rn = nullptr, *rhead = nullptr;  // row scratch
+  int S = 0;
+  bool encoded = false, decoded = false;
+  int n_frames = 0, reason = 0, n_pass = 0;
+  double t_decode = 0, n_launch = 0, t_encode = 0;
+};
+
+static void mel_key_table(vx_engine* e) {
+  const int d = e->cfg.d_model, L = e->cfg.num_layers;
+  auto add = [&](const std::string& k, std::vector<int64_t> s) {
+    Tensor t; t.shape = s; t.numel = 1; for (auto v : s) t.numel *= (size_t)v;
+    t.low = e->bf16 && is_matrix_key(k);
+    e->w[k] = t; e->keys.push_back(k);
+  };
+  add("text_embedding.word_embeddings.weight", {512, d});
+  if (e->cfg.flags & VX_FLAG_PRENET) {  // transformer.py:68-95; Sequential indices as in the reference
+    for (int conv : {1, 5, 9}) {
+      const std::string cv = "encoder_prenet." + std::to_string(conv), bn = "encoder_prenet." + std::to_string(conv + 1);
+      add(cv + ".weight", {d, d, 5}); add(cv + ".bias", {d});
+      add(bn + ".weight", {d}); add(bn + ".bias", {d}); add(bn + ".running_mean", {d}); add(bn + ".running_var", {d});
+    }
+    add("encoder_prenet.14.weight", {d, d}); add("encoder_prenet.14.bias", {d});
+    add("decoder_prenet.0.weight", {MEL_PRENET_H, MEL_BINS}); add("decoder_prenet.0.bias", {MEL_PRENET_H});
+    add("decoder_prenet.3.weight", {MEL_PRENET_H, MEL_PRENET_H}); add("decoder_prenet.3.bias", {MEL_PRENET_H});
+    add("decoder_prenet.6.weight", {d, MEL_PRENET_H}); add("decoder_prenet.6.bias", {d});
+  } else {
+    add("decoder_prenet.weight", {d, MEL_BINS}); add("decoder_prenet.bias", {d});
+  }
+  add("encoder_position.alpha", {1});
+  add("decoder_position.alpha", {1});
+  add_encoder_keys(e, "encoder", d, L, false, 0);
+  add_encoder_keys(e, "decoder", d, L, false, 1);
+  add("predict_layer.weight", {MEL_BINS, d}); add("predict_layer.bias", {MEL_BINS});
+  add("stop_layer.weight", {1, d}); add("stop_layer.bias", {1});
+}
+
+extern "C" void vx_mel_destroy(vx_mel* m) {
+  if (!m) return;
+  vx_destroy(m->e);  // every device block of the handle was allocated through the engine
+  delete m;
+}
+
+extern "C" int vx_mel_create(const vx_mel_config* cfg, vx_mel** out) {
+  if (!cfg || !out) return fail(VX_ERR_ARG, "null argument");
+  if (cfg->struct_size != (int32_t)sizeof(vx_mel_config)) return fail(VX_ERR_ARG, "vx_mel_config.struct_size mismatch");
+  const vx_mel_config& c = *cfg;
+  if (c.d_model <= 0 || c.nhead <= 0 || c.num_layers <= 0 || c.d_model % c.nhead) return fail(VX_ERR_ARG, "bad d_model/nhead/num_layers");
+  if (c.max_text <= 0 || c.max_frames <= 0) return fail(VX_ERR_ARG, "capacities must be positive");
+  if (c.precision != VX_PREC_F32 && c.precision != VX_PREC_BF16) return fail(VX_ERR_ARG, "precision must be VX_PREC_F32 or VX_PREC_BF16");
+  if (c.scaling_xformers)
+    return fail(VX_ERR_UNSUPPORTED, "scaling_xformers=True (ScaledLinear / BasicNorm / DoubleSwish, transformer.py:114-172) is not built");
+  const int hd = c.d_model / c.nhead;
+  if (hd != 4 && hd != 8 && hd != 16 && hd != 32 && hd != 64) return fail(VX_ERR_UNSUPPORTED, "head_dim (d_model/nhead) must be 4, 8, 16, 32 or 64");
+  if (c.d_model % 8 || c.d_model > 1024) return fail(VX_ERR_UNSUPPORTED, "d_model must be a multiple of 8 and <= 1024");
+  if (hd == 64 && c.d_model % 64) return fail(VX_ERR_UNSUPPORTED, "d_model must be a multiple of 64 at head_dim 64");
+  if ((long long)c.max_text + c.max_frames + 2 > (1 << 20)) return fail(VX_ERR_UNSUPPORTED, "max_text + max_frames above 2^20 rows");
+  ON_DEVICE(c.device);
+  vx_mel* m = new vx_mel();
+  m->cfg = c; m->cap = c.max_frames;
+  vx_engine* e = m->e = new vx_engine();
+  vx_config& ec = e->cfg;
+  ec.struct_size = sizeof(vx_config);
+  ec.d_model = ec.nar_d_model = c.d_model; ec.nhead = ec.nar_nhead = c.nhead; ec.num_layers = ec.nar_num_layers = c.num_layers;
+  ec.num_quantizers = 1; ec.precision = c.precision; ec.max_text = c.max_text; ec.max_audio = c.max_frames + 2; ec.device = c.device;
+  ec.flags = VX_FLAG_VALLF | (c.norm_first ? 0 : VX_FLAG_POST_NORM) | (c.add_prenet ? VX_FLAG_PRENET : 0) |
+             ((c.flags & VX_MEL_NO_GRAPH) ? VX_FLAG_NO_GRAPH : 0);
+  e->mel = true;
+  auto body = [&]() -> int {
+    VXC(create_body(e));
+    const size_t d = c.d_model, rows = (size_t)c.max_frames;
+    VXC(dalloc_t(e, &m->d_ctl, 1));
+    VXC(dalloc_t(e, &m->xh, d));
+    VXC(dalloc_t(e, &m->frames, rows * MEL_BINS));
+    VXC(dalloc_t(e, &m->stops, rows + 2));
+    VXC(dalloc_t(e, &m->headW, (size_t)MEL_HEAD * d));
+    VXC(dalloc_t(e, &m->headB, 128));
+    VXC(dalloc_t(e, &m->fin, rows * MEL_BINS));
+    VXC(dalloc_t(e, &m->ra, rows * d));
+    VXC(dalloc_t(e, &m->rn, rows * d));
+    VXC(dalloc_t(e, &m->rhead, rows * MEL_HEAD));
+    if (c.add_prenet) {
+      VXC(dalloc_t(e, &m->rh1, rows * MEL_PRENET_H));
+      VXC(dalloc_t(e, &m->rh2, rows * MEL_PRENET_H));
+    }
+    HIPC(hipMemsetAsync(m->d_ctl, 0, sizeof(MelCtl), e->es));
+    HIPC(hipStreamSynchronize(e->es));
+    return VX_OK;
+  };
+  const int rc = body();
+  if (rc != VX_OK) {
+    const std::string keep = g_err;
+    vx_mel_destroy(m);
+    g_err = keep;
+    return rc;
+  }
+  *out = m;
+  return VX_OK;
+}
+
+extern "C" int vx_mel_set_weight(vx_mel* m, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
+  if (!m) return fail(VX_ERR_ARG, "null argument");
+  return vx_set_weight(m->e, key, data, shape, ndim);
+}
+
+extern "C" int vx_mel_set_sine_table(vx_mel* m, const float* data, int64_t rows, int64_t dim) {
+  if (!m) return fail(VX_ERR_ARG, "null argument");
+  return vx_set_sine_table(m->e, 0, data, rows, dim);
+}
+
+extern "C" int vx_mel_finalize(vx_mel* m) {
+  if (!m) return fail(VX_ERR_ARG, "null argument");
+  vx_engine* e = m->e;
+  ON_DEVICE(e->cfg.device);
+  for (auto& k : e->keys)
+    if (!e->w[k].set) return fail(VX_ERR_WEIGHTS, "missing key '%s' (strict load)", k.c_str());
+  const int d = e->cfg.d_model, L = e->cfg.num_layers;
+  fill_layers(e, "decoder", L, false, e->ar_l, 1);
+  fill_layers(e, "encoder", L, false, m->enc_l, 0);
+  if (!e->pe_ar_set) {
+    std::vector<float> t;
+    host_sine_table(t, e->pe_rows, d);
+    HIPC(hipMemcpy(e->pe_ar, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+  }
+  if (m->cfg.add_prenet) {
+    const size_t nel = (size_t)5 * d * d;
+    for (int i = 0; i < 3; ++i)
+      conv_weight_relayout_kernel<<<(unsigned)((nel + 255) / 256), 256, 0, e->es>>>(
+          W<float>(e, "encoder_prenet." + std::to_string(1 + 4 * i) + ".weight"), e->convT[0][i], d);
+    HIPC(hipGetLastError());
+  }
+  // the head as one (101, d) matrix: predict_layer's rows, then stop_layer's
+  HIPC(hipMemcpyAsync(m->headW, W<float>(e, "predict_layer.weight"), (size_t)MEL_BINS * d * 4, hipMemcpyDeviceToDevice, e->es));
+  HIPC(hipMemcpyAsync(m->headW + (size_t)MEL_BINS * d, W<float>(e, "stop_layer.weight"), (size_t)d * 4, hipMemcpyDeviceToDevice, e->es));
+  HIPC(hipMemcpyAsync(m->headB, W<float>(e, "predict_layer.bias"), MEL_BINS * 4, hipMemcpyDeviceToDevice, e->es));
+  HIPC(hipMemcpyAsync(m->headB + MEL_BINS, W<float>(e, "stop_layer.bias"), 4, hipMemcpyDeviceToDevice, e->es));
+  HIPC(hipStreamSynchronize(e->es));
+  e->finalized = true;
+  m->encoded = m->decoded = false;
+  return VX_OK;
+}
+
+// The checks of vx_mel_encode, before any HIP call.
+static int mel_check_text(vx_mel* m, const int64_t* text, int32_t S) {
+  if (!m || !text) return fail(VX_ERR_ARG, "null argument");
+  if (S <= 0) return fail(VX_ERR_ARG, "S must be > 0 (transformer.py:340)");
+  if (!m->e->finalized) return fail(VX_ERR_STATE, "weights not finalized");
+  if (S > m->cfg.max_text) return fail(VX_ERR_CAPACITY, "S=%d exceeds max_text=%d", S, m->cfg.max_text);
+  return VX_OK;
+}
+
+// encode on the engine's stream (no synchronisation): X <- encoder(text), memory K / V of every decoder layer
+static int mel_encode_rows(vx_mel* m, const int64_t* text, int S) {
+  vx_engine* e = m->e;
+  const int d = e->cfg.d_model, H = e->cfg.nhead;
+  const bool post = e->cfg.flags & VX_FLAG_POST_NORM;
+  HIPC(hipMemcpyAsync(e->ids_text, text, (size_t)S * 8, hipMemcpyDefault, e->es));
+  const float* emb = W<float>(e, "text_embedding.word_embeddings.weight");
+  const float* alpha = W<float>(e, "encoder_position.alpha");
+  if (m->cfg.add_prenet) {  // transformer.py:69-85
+    embed_accum_kernel<<<S, 256, 0, e->es>>>(e->ids_text, 1, 0, emb, 512, d, e->pn_a, S, 1);
+    const float* src = e->pn_a;
+    float* bufs[2] = {e->pn_b, e->pn_a};
+    for (int i = 0; i < 3; ++i) {
+      const std::string cv = "encoder_prenet." + std::to_string(1 + 4 * i), bn = "encoder_prenet." + std::to_string(2 + 4 * i);
+      float* dst = bufs[i & 1];
+      conv5_bn_relu_kernel<<<(S + CONV_TT - 1) / CONV_TT, 256, (size_t)(CONV_TT + 4) * d * 4, e->es>>>(
+          src, e->convT[0][i], W<float>(e, cv + ".bias"), W<float>(e, bn + ".weight"), W<float>(e, bn + ".bias"),
+          W<float>(e, bn + ".running_mean"), W<float>(e, bn + ".running_var"), dst, S, d);
+      src = dst;
+    }
+    VXC(linear_rows_f32(e, src, W<float>(e, "encoder_prenet.14.weight"), W<float>(e, "encoder_prenet.14.bias"), e->pn_a, S, d, d, false));
+    add_pos_kernel<<<S, 256, 0, e->es>>>(e->pn_a, d, alpha, e->pe_ar, 0, e->X, S);
+  } else {
+    embed_pos_kernel<<<S, 256, 0, e->es>>>(e->ids_text, 1, 0, emb, 512, d, alpha, e->pe_ar, 0, e->X, S);
+  }
+  {  // encoder layers have two norms each: the engine's norm-site arithmetic (front_site / norm_at) follows npl
+    const int npl = e->npl;
+    e->npl = 2;
+    const int rc = run_stack(e, m->enc_l, S, d, H, -1, -1, RowSegs(), KvDst());
+    e->npl = npl;
+    VXC(rc);
+  }
+  if (post) VXC(cast_rows(e, e->X, e->Hn, (size_t)S * d));  // no final norm (transformer.py:185): X holds the last norm2's rows
+  else VXC(ln_rows(e, e->X, W<float>(e, "encoder.norm.weight"), W<float>(e, "encoder.norm.bias"), nullptr, nullptr, e->Hn, S, d));
+  VXC(memory_kv(e, e->ar_l, e->xkv_ar, S, d, H));
+  e->mem_len = S;
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+extern "C" int vx_mel_encode(vx_mel* m, const int64_t* text, int32_t S, void* stream) {
+  VXC(mel_check_text(m, text, S));
+  vx_engine* e = m->e;
+  ON_DEVICE(e->cfg.device);
+  VXC(sync_in(e, stream));
+  HIPC(hipEventRecord(e->ev_t[0], e->es));
+  VXC(mel_encode_rows(m, text, S));
+  HIPC(hipEventRecord(e->ev_t[1], e->es));
+  HIPC(hipStreamSynchronize(e->es));  // `text` may be host memory the caller frees on return
+  float ms = 0.f;
+  HIPC(hipEventElapsedTime(&ms, e->ev_t[0], e->ev_t[1]));
+  m->t_encode = ms;
+  m->S = S; m->encoded = true; m->decoded = false;
+  VXC(sync_out(e, stream));
+  return VX_OK;
+}
+
+static MelStep mel_step(vx_mel* m) {
+  vx_engine* e = m->e;
+  const vx_config& c = e->cfg;
+  MelStep st{};
+  MelStepArgs& a = st.open;
+  const NormW fin = (c.flags & VX_FLAG_POST_NORM) ? norm_at(e, e->ar_l, front_site(e, c.num_layers, 0))
+                                                  : NormW{W<float>(e, "decoder.norm.weight"), W<float>(e, "decoder.norm.bias")};
+  a.xh = m->xh; a.gamma = fin.g; a.beta = fin.b; a.Wh = m->headW; a.bh = m->headB;
+  if (m->cfg.add_prenet) {
+    a.W1 = W<float>(e, "decoder_prenet.0.weight"); a.b1 = W<float>(e, "decoder_prenet.0.bias");
+    a.W2 = W<float>(e, "decoder_prenet.3.weight"); a.b2 = W<float>(e, "decoder_prenet.3.bias");
+    a.W0 = W<float>(e, "decoder_prenet.6.weight"); a.b0 = W<float>(e, "decoder_prenet.6.bias");
+  } else {
+    a.W0 = W<float>(e, "decoder_prenet.weight"); a.b0 = W<float>(e, "decoder_prenet.bias");
+  }
+  a.alpha = W<float>(e, "decoder_position.alpha"); a.pe = e->pe_ar;
+  a.x = e->ar_x; a.st = e->d_st; a.ctl = m->d_ctl; a.frames = m->frames; a.stops = m->stops; a.d = c.d_model;
+  return st;
+}
+
+// limit: frames the decode may append; forced / n_forced: teacher forcing (frames already in m->fin)
+static int mel_decode_impl(vx_mel* m, int limit, int n_forced, bool cap_limited, void* stream) {
+  vx_engine* e = m->e;
+  ArState& st = e->h_st[0];
+  memset(&st, 0, sizeof st);
+  st.S = m->S; st.row = -1; st.temperature = 1.0f; st.max_new = -1;
+  HIPC(hipMemcpyAsync(e->d_st, &st, sizeof st, hipMemcpyHostToDevice, e->es));
+  MelCtl& ctl = m->h_ctl;
+  ctl = MelCtl{};  // the arrival counter starts from zero every decode, whatever an interrupted one left
+  ctl.max_frames = limit; ctl.n_forced = n_forced; ctl.forced = n_forced > 0 ? m->fin : nullptr;
+  HIPC(hipMemcpyAsync(m->d_ctl, &ctl, sizeof ctl, hipMemcpyHostToDevice, e->es));
+  const MelStep ms_ = mel_step(m);
+  auto step = [e, ms_](hipStream_t s) { return enqueue_ar_step(e, s, &ms_); };
+  VXC(step_graph(e, &e->gexec, step, &e->gexec_nodes));
+  // launch 0 forms input row 0; pass p is launch p + 1; at most limit + 1 passes (the one that stops appends nothing)
+  const long long bound = (long long)(n_forced > 0 ? n_forced : limit + 1) + 1;
+  auto stop_rule = [&](const ArState* hs, long long at) -> int {
+    if (hs->done) return POLL_STOP;
+    return at < bound ? POLL_MORE : fail(VX_ERR_STATE, "mel decode did not terminate within %lld steps", bound);
+  };
+  ArState* const poll[2] = {e->h_st + 1, e->h_st + 2};
+  long long launched = 0;
+  float ms = 0.f;
+  VXC(replay_polled(e, e->gexec, step, bound, POLL_CHUNK, e->d_st, 1, poll, stop_rule, &launched, &ms));
+  HIPC(hipMemcpyAsync(&e->h_st[1], e->d_st, sizeof(ArState), hipMemcpyDeviceToHost, e->es));
+  HIPC(hipStreamSynchronize(e->es));
+  HIPC(hipGetLastError());
+  m->t_decode = ms; m->n_launch = (double)launched;
+  m->n_frames = e->h_st[1].n_gen; m->reason = e->h_st[1].stop_reason; m->n_pass = e->h_st[1].pass;
+  m->decoded = true;
+  VXC(sync_out(e, stream));
+  if (cap_limited && m->reason == VX_MEL_STOP_MAX_FRAMES)
+    return fail(VX_ERR_CAPACITY, "capacity exceeded: %d frames (max_frames of the handle) were generated before the stop rule fired; raise max_frames",
+                m->n_frames);
+  return VX_OK;
+}
+
+extern "C" int vx_mel_decode(vx_mel* m, int32_t max_frames, void* stream) {
+  if (!m) return fail(VX_ERR_ARG, "null argument");
+  if (!m->encoded) return fail(VX_ERR_STATE, "vx_mel_decode needs a vx_mel_encode");
+  if (max_frames > m->cap) return fail(VX_ERR_CAPACITY, "max_frames=%d exceeds the handle's capacity %d", max_frames, m->cap);
+  const long long natural = 10LL * m->S;  // frames the reference's length rule admits
+  int limit = max_frames;
+  bool cap_limited = false;
+  if (max_frames < 0) {
+    cap_limited = natural > m->cap;
+    limit = cap_limited ? m->cap : (int)natural;
+  }
+  vx_engine* e = m->e;
+  ON_DEVICE(e->cfg.device);
+  VXC(sync_in(e, stream));
+  return mel_decode_impl(m, limit, 0, cap_limited, stream);
+}
+
+extern "C" int vx_mel_decode_forced(vx_mel* m, const float* forced, int32_t T, void* stream) {
+  if (!m || !forced) return fail(VX_ERR_ARG, "null argument");
+  if (!m->encoded) return fail(VX_ERR_STATE, "vx_mel_decode_forced needs a vx_mel_encode");
+  if (T < 1) return fail(VX_ERR_ARG, "T must be >= 1");
+  if (T > m->cap) return fail(VX_ERR_CAPACITY, "T=%d exceeds max_frames=%d", T, m->cap);
+  vx_engine* e = m->e;
+  ON_DEVICE(e->cfg.device);
+  VXC(sync_in(e, stream));
+  HIPC(hipMemcpyAsync(m->fin, forced, (size_t)T * MEL_BINS * 4, hipMemcpyDefault, e->es));
+  return mel_decode_impl(m, T, T, false, stream);
+}
+
+extern "C" int vx_mel_result(vx_mel* m, float* frames, int32_t capacity, int32_t* n_frames, int32_t* stop_reason, float* stop_logits,
+                             int32_t* n_pass) {
+  if (!m) return fail(VX_ERR_ARG, "null argument");
+  if (!m->decoded) return fail(VX_ERR_STATE, "no finished decode");
+  ON_DEVICE(m->e->cfg.device);
+  if (n_frames) *n_frames = m->n_frames;
+  if (stop_reason) *stop_reason = m->reason;
+  if (n_pass) *n_pass = m->n_pass;
+  if (frames) {
+    if (capacity < m->n_frames) return fail(VX_ERR_CAPACITY, "frame buffer too small (%d < %d)", capacity, m->n_frames);
+    if (m->n_frames) HIPC(hipMemcpy(frames, m->frames, (size_t)m->n_frames * MEL_BINS * 4, hipMemcpyDefault));
+  }
+  if (stop_logits && m->n_pass) HIPC(hipMemcpy(stop_logits, m->stops, (size_t)m->n_pass * 4, hipMemcpyDefault));
+  return VX_OK;
+}
+
+extern "C" int vx_mel_teacher_forced(vx_mel* m, const int64_t* text, int32_t S, const float* frames, int32_t T, float* predict,
+                                     float* stop_logits, void* stream) {
+  VXC(mel_check_text(m, text, S));
+  if (!frames || !predict || !stop_logits) return fail(VX_ERR_ARG, "null argument");
+  if (T < 1) return fail(VX_ERR_ARG, "T must be >= 1");
+  if (T > m->cap) return fail(VX_ERR_CAPACITY, "T=%d exceeds max_frames=%d", T, m->cap);
+  vx_engine* e = m->e;
+  const int d = e->cfg.d_model, H = e->cfg.nhead;
+  ON_DEVICE(e->cfg.device);
+  VXC(sync_in(e, stream));
+  VXC(mel_encode_rows(m, text, S));
+  m->S = S; m->encoded = true; m->decoded = false;
+  // inputs [0; frames[:-1]] (pad_y, transformer.py:274-279) -> decoder_prenet -> + alpha pe
+  HIPC(hipMemsetAsync(m->fin, 0, MEL_BINS * 4, e->es));
+  if (T > 1) HIPC(hipMemcpyAsync(m->fin + MEL_BINS, frames, (size_t)(T - 1) * MEL_BINS * 4, hipMemcpyDefault, e->es));
+  if (m->cfg.add_prenet) {
+    VXC(linear_rows_f32(e, m->fin, W<float>(e, "decoder_prenet.0.weight"), W<float>(e, "decoder_prenet.0.bias"), m->rh1, T, MEL_PRENET_H, MEL_BINS, true));
+    VXC(linear_rows_f32(e, m->rh1, W<float>(e, "decoder_prenet.3.weight"), W<float>(e, "decoder_prenet.3.bias"), m->rh2, T, MEL_PRENET_H, MEL_PRENET_H, true));
+    VXC(linear_rows_f32(e, m->rh2, W<float>(e, "decoder_prenet.6.weight"), W<float>(e, "decoder_prenet.6.bias"), m->ra, T, d, MEL_PRENET_H, false));
+  } else {
+    VXC(linear_rows_f32(e, m->fin, W<float>(e, "decoder_prenet.weight"), W<float>(e, "decoder_prenet.bias"), m->ra, T, d, MEL_BINS, false));
+  }
+  add_pos_kernel<<<T, 256, 0, e->es>>>(m->ra, d, W<float>(e, "decoder_position.alpha"), e->pe_ar, 0, e->X, T);
+  // causal over the frame rows (text_len 0), no KV destination, the text as cross-attention memory
+  VXC(run_stack(e, e->ar_l, T, d, H, 0, -1, RowSegs(), KvDst(), TextMem{e->xkv_ar, S}));
+  const float* src = e->X;  // post-norm: the rows are the last norm3's output (transformer.py:199)
+  if (!(e->cfg.flags & VX_FLAG_POST_NORM)) {
+    ln_rows_launch(false, e->X, W<float>(e, "decoder.norm.weight"), W<float>(e, "decoder.norm.bias"), nullptr, nullptr, m->rn, T, d, nullptr,
+                   Fold(), e->es);
+    src = m->rn;
+  }
+  VXC(linear_rows_f32(e, src, m->headW, m->headB, m->rhead, T, MEL_HEAD, d, false));
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpy2DAsync(predict, MEL_BINS * 4, m->rhead, MEL_HEAD * 4, MEL_BINS * 4, T, hipMemcpyDefault, e->es));
+  HIPC(hipMemcpy2DAsync(stop_logits, 4, m->rhead + MEL_BINS, MEL_HEAD * 4, 4, T, hipMemcpyDefault, e->es));
+  HIPC(hipStreamSynchronize(e->es));
+  VXC(sync_out(e, stream));
+  return VX_OK;
+}
+
+extern "C" int vx_mel_get_timings(vx_mel* m, double* out, int32_t n) {
+  if (!m || !out) return fail(VX_ERR_ARG, "null argument");
+  const double v[4] = {m->t_decode, m->n_launch, (double)m->e->gexec_nodes, m->t_encode};
+  for (int i = 0; i < n && i < 4; ++i) out[i] = v[i];
   return VX_OK;
 }
 

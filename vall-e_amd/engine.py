@@ -57,6 +57,16 @@ class VxDtwConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "dim", "n_ceps", "max_frames", "max_batch")]
 
 
+class VxMelConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "d_model", "nhead", "num_layers", "norm_first", "add_prenet", "scaling_xformers",
+                                         "precision", "max_text", "max_frames", "device", "flags")]
+
+
+VX_MEL_NO_GRAPH = 1
+MEL_STOP_REASONS = {0: "none", 1: "logit", 2: "length", 3: "max_frames"}
+NUM_MEL_BINS = 100
+
+
 class VxError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vallex error {code}: {msg}")
@@ -175,6 +185,19 @@ _SIGS = {
                                  C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "vx_op_dtw_cost": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "vx_op_dtw_path": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # mel-spectrogram Transformer (meltf.Transformer)
+    "vx_mel_create": (C.c_int, [C.POINTER(VxMelConfig), C.POINTER(C.c_void_p)]),
+    "vx_mel_destroy": (None, [C.c_void_p]),
+    "vx_mel_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "vx_mel_set_sine_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "vx_mel_finalize": (C.c_int, [C.c_void_p]),
+    "vx_mel_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "vx_mel_decode": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "vx_mel_decode_forced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "vx_mel_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                C.POINTER(C.c_int32)]),
+    "vx_mel_teacher_forced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vx_mel_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so
@@ -1056,3 +1079,89 @@ def l2_fill(grid=256, threads=256, unroll=8, region_bytes=2 << 20, iters=200):
     out = (C.c_double * 3)()
     _check(lib.vx_debug_l2_fill(grid, threads, unroll, region_bytes, iters, out))
     return dict(gbs=out[0], bytes_per_clk_per_cu=out[1], ghz=out[2])
+
+
+class MelEngine:
+    """One mel-spectrogram Transformer replica on one GPU (the vx_mel_* entries of include/vallex.h)."""
+
+    def __init__(self, cfg, precision: str = "bf16", max_text: int = 256, max_frames: int = 2560, device: int = 0,
+                 no_graph: bool = False, scaling_xformers: bool = False):
+        self.lib = load_library()
+        self.cfg, self.device, self.precision = cfg, int(device), precision
+        self.max_text, self.max_frames = int(max_text), int(max_frames)
+        c = VxMelConfig()
+        c.struct_size = C.sizeof(VxMelConfig)
+        c.d_model, c.nhead, c.num_layers = cfg.d_model, cfg.nhead, cfg.num_layers
+        c.norm_first, c.add_prenet, c.scaling_xformers = int(cfg.norm_first), int(cfg.add_prenet), int(scaling_xformers)
+        c.precision = {"fp32": VX_PREC_F32, "f32": VX_PREC_F32, "bf16": VX_PREC_BF16}[precision]
+        c.max_text, c.max_frames, c.device = self.max_text, self.max_frames, self.device
+        c.flags = VX_MEL_NO_GRAPH if no_graph else 0
+        h = C.c_void_p()
+        _check(self.lib.vx_mel_create(C.byref(c), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.vx_mel_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load_state_dict(self, sd, sine_table_: bool = True):
+        from .weights import mel_expected_keys, sine_table
+
+        for k, shape in mel_expected_keys(self.cfg).items():
+            if k.endswith("num_batches_tracked"):  # BatchNorm's step counter: not read by the forward pass
+                continue
+            t = sd[k].detach().to(torch.float32).contiguous()
+            assert tuple(t.shape) == tuple(shape), (k, tuple(t.shape), shape)
+            shp = (C.c_int64 * t.dim())(*t.shape)
+            _check(self.lib.vx_mel_set_weight(self.h, k.encode(), _ptr(t), shp, t.dim()))
+        if sine_table_:
+            rows = max(4000, self.max_text + self.max_frames + 2)
+            pe = sine_table(rows, self.cfg.d_model)
+            _check(self.lib.vx_mel_set_sine_table(self.h, _ptr(pe), rows, self.cfg.d_model))
+        _check(self.lib.vx_mel_finalize(self.h))
+
+    def encode(self, text: torch.Tensor, stream=None):
+        text = text.to(torch.int64).contiguous()
+        _check(self.lib.vx_mel_encode(self.h, _ptr(text), text.numel(), stream))
+
+    def decode(self, max_frames: int = -1, stream=None):
+        _check(self.lib.vx_mel_decode(self.h, int(max_frames), stream))
+
+    def decode_forced(self, frames: torch.Tensor, stream=None):
+        frames = frames.to(torch.float32).contiguous()
+        assert frames.dim() == 2 and frames.shape[1] == NUM_MEL_BINS, tuple(frames.shape)
+        _check(self.lib.vx_mel_decode_forced(self.h, _ptr(frames), frames.shape[0], stream))
+
+    def result(self, out: Optional[torch.Tensor] = None, out_device="cpu"):
+        """(frames (T, 100) fp32, stop reason name, stop logits (n_pass,) fp32 on the host).  ``out``: a caller buffer (rows, 100)
+        whose first T rows are written; the returned frames are a view of it."""
+        n, reason, n_pass = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(self.lib.vx_mel_result(self.h, None, 0, C.byref(n), C.byref(reason), None, C.byref(n_pass)))
+        if out is None:
+            out = torch.empty(n.value, NUM_MEL_BINS, dtype=torch.float32, device=out_device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[1] == NUM_MEL_BINS
+        stops = torch.empty(n_pass.value, dtype=torch.float32)
+        _check(self.lib.vx_mel_result(self.h, _ptr(out) if out.shape[0] else None, out.shape[0], C.byref(n), C.byref(reason),
+                                      _ptr(stops) if n_pass.value else None, C.byref(n_pass)))
+        return out[: n.value], MEL_STOP_REASONS[reason.value], stops
+
+    def teacher_forced(self, text: torch.Tensor, frames: torch.Tensor, out_device="cpu", stream=None):
+        text = text.to(torch.int64).contiguous()
+        frames = frames.to(torch.float32).contiguous()
+        T = frames.shape[0]
+        predict = torch.empty(T, NUM_MEL_BINS, dtype=torch.float32, device=out_device)
+        stops = torch.empty(T, dtype=torch.float32, device=out_device)
+        _check(self.lib.vx_mel_teacher_forced(self.h, _ptr(text), text.numel(), _ptr(frames), T, _ptr(predict), _ptr(stops), stream))
+        return predict, stops
+
+    def timings(self):
+        buf = (C.c_double * 4)()
+        _check(self.lib.vx_mel_get_timings(self.h, buf, 4))
+        return {"decode_ms": buf[0], "step_launches": buf[1], "kernels_per_step": buf[2], "encode_ms": buf[3]}

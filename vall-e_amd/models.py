@@ -16,6 +16,7 @@ from typing import List, Optional
 import torch
 
 from .config import NUM_AUDIO_TOKENS, NUM_TEXT_TOKENS, ModelConfig, add_model_arguments  # noqa: F401
+from .meltf import Transformer  # noqa: F401  (the reference's third model, valle/models/transformer.py)
 from .weights import expected_keys, synthetic_state_dict, tied_keys
 
 _IncompatibleKeys = namedtuple("IncompatibleKeys", ["missing_keys", "unexpected_keys"])
@@ -886,17 +887,29 @@ class VALLF(VALLE):
                                         return_alignment=return_alignment)
 
 
-def get_model(params) -> VALLE:
-    """models/__init__.py:98-136 for --model-name VALL-E / VALL-F; the debug mel-Transformer is outside the hot path."""
+def get_model(params):
+    """models/__init__.py:98-136: --model-name VALL-E / VALL-F, and (anything else there) the mel-spectrogram ``Transformer``
+    (models/__init__.py:125-134), which takes --scaling-xformers."""
     cfg = ModelConfig.from_params(params)
+    get = params.get if isinstance(params, dict) else lambda k, d=None: getattr(params, k, d)
+    if cfg.model_name == "Transformer":  # models/__init__.py:126 asserts this spelling
+        # models/__init__.py:133 reads params.scaling_xformers unconditionally: the reference serves this model only from the full
+        # argument set of add_model_arguments.  So does this factory - a params object without the field asks for a model variant
+        # nobody named, and is refused rather than given a default (models.Transformer(...) takes the default directly).
+        if get("scaling_xformers", None) is None:
+            raise NotImplementedError("get_model(model_name='Transformer') needs params.scaling_xformers (add_model_arguments sets it; "
+                                      "models/__init__.py:133 reads it unconditionally): the stock variant (False) is built, "
+                                      "ScaledLinear / BasicNorm (True) is not - or construct valle_amd.models.Transformer directly")
+        extra = {k: get(k) for k in ("precision", "max_text", "max_frames", "no_graph") if get(k, None) is not None}
+        return Transformer(cfg.decoder_dim, cfg.nhead, cfg.num_decoder_layers, norm_first=cfg.norm_first, add_prenet=cfg.add_prenet,
+                           scaling_xformers=bool(get("scaling_xformers", False)), **extra)
     if cfg.model_name.lower() in ("vall-f", "vallf"):
         cls = VALLF
     elif cfg.model_name.lower() in ("vall-e", "valle"):
         cls = VALLE
     else:
-        raise NotImplementedError(f"model {cfg.model_name!r}: only VALL-E and VALL-F are built (DESIGN.md)")
+        raise NotImplementedError(f"model {cfg.model_name!r}: VALL-E, VALL-F and Transformer are built (DESIGN.md)")
     extra = {}
-    get = params.get if isinstance(params, dict) else lambda k, d=None: getattr(params, k, d)
     for k in ("precision", "max_text", "max_audio", "sampling", "max_batch", "kv_cache", "batched_rows", "logprobs"):
         if get(k, None) is not None:
             extra[k] = get(k)

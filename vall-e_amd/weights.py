@@ -238,3 +238,74 @@ def sine_table(length: int, dim: int) -> torch.Tensor:
     pe[:, 0::2] = torch.sin(position * div_term)
     pe[:, 1::2] = torch.cos(position * div_term)
     return pe
+
+
+# ---- the mel-spectrogram Transformer (valle/models/transformer.py:47-207) ---------------------------------------------------
+NUM_MEL_BINS = 100  # valle/models/macros.py
+
+
+def mel_expected_keys(cfg) -> "OrderedDict[str, Tuple[int, ...]]":
+    """state_dict keys -> shapes of ``Transformer(d_model, nhead, num_layers, norm_first, add_prenet)`` in the reference's
+    registration order (``cfg``: config.MelConfig).  The layers are stock torch.nn Transformer{En,De}coderLayers; the prenets'
+    indices are their Sequential positions (transformer.py:69-95)."""
+    d, L = cfg.d_model, cfg.num_layers
+    k: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    k["text_embedding.word_embeddings.weight"] = (NUM_TEXT_TOKENS, d)
+    if cfg.add_prenet:
+        for conv, bn in ((1, 2), (5, 6), (9, 10)):
+            k[f"encoder_prenet.{conv}.weight"] = (d, d, 5)
+            k[f"encoder_prenet.{conv}.bias"] = (d,)
+            k[f"encoder_prenet.{bn}.weight"] = (d,)
+            k[f"encoder_prenet.{bn}.bias"] = (d,)
+            k[f"encoder_prenet.{bn}.running_mean"] = (d,)
+            k[f"encoder_prenet.{bn}.running_var"] = (d,)
+            k[f"encoder_prenet.{bn}.num_batches_tracked"] = ()
+        k["encoder_prenet.14.weight"] = (d, d)
+        k["encoder_prenet.14.bias"] = (d,)
+        k["decoder_prenet.0.weight"] = (PRENET_HIDDEN, NUM_MEL_BINS)
+        k["decoder_prenet.0.bias"] = (PRENET_HIDDEN,)
+        k["decoder_prenet.3.weight"] = (PRENET_HIDDEN, PRENET_HIDDEN)
+        k["decoder_prenet.3.bias"] = (PRENET_HIDDEN,)
+        k["decoder_prenet.6.weight"] = (d, PRENET_HIDDEN)
+        k["decoder_prenet.6.bias"] = (d,)
+    else:
+        k["decoder_prenet.weight"] = (d, NUM_MEL_BINS)
+        k["decoder_prenet.bias"] = (d,)
+    k["encoder_position.alpha"] = (1,)
+    k["decoder_position.alpha"] = (1,)
+    k.update(_encoder_keys("encoder", d, L, adaptive=False, final_norm=cfg.norm_first, cross=False))
+    k.update(_encoder_keys("decoder", d, L, adaptive=False, final_norm=cfg.norm_first, cross=True))
+    k["predict_layer.weight"] = (NUM_MEL_BINS, d)
+    k["predict_layer.bias"] = (NUM_MEL_BINS,)
+    k["stop_layer.weight"] = (1, d)
+    k["stop_layer.bias"] = (1,)
+    return k
+
+
+def mel_synthetic_tensor(key: str, shape: Tuple[int, ...], seed: int = 0) -> torch.Tensor:
+    """Name-seeded like ``synthetic_tensor``, with the distributions of the same kinds of tensor there.  Both position alphas
+    are off 1 and the BatchNorm statistics off (0, 1), so that each is exercised numerically."""
+    if key == "encoder_position.alpha":
+        return torch.tensor([0.9375])
+    if key == "decoder_position.alpha":
+        return torch.tensor([1.0625])
+    g = _gen(key, seed)
+    if key.startswith("encoder_prenet.") and len(shape) == 1 and key.split(".")[1] in ("2", "6", "10") and key.endswith(".weight"):
+        return 1.0 + 0.05 * torch.randn(shape, generator=g)  # BatchNorm gamma
+    if key in ("encoder.norm.weight", "decoder.norm.weight"):
+        return 1.0 + 0.02 * torch.randn(shape, generator=g)
+    if key in ("encoder.norm.bias", "decoder.norm.bias"):
+        return 0.02 * torch.randn(shape, generator=g)
+    return synthetic_tensor(key, shape, seed)
+
+
+def mel_synthetic_state_dict(cfg, seed: int = 0, stop_bias=None) -> "OrderedDict[str, torch.Tensor]":
+    """Full fp32 state_dict of the mel-Transformer.  ``stop_bias``: value of ``stop_layer.bias`` - a random-init model's stop
+    logits straddle 0, so a strongly negative bias makes it run to the length rule (10 S frames), and a chosen one places the
+    stop on a chosen pass."""
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for key, shape in mel_expected_keys(cfg).items():
+        sd[key] = mel_synthetic_tensor(key, shape, seed).contiguous()
+    if stop_bias is not None:
+        sd["stop_layer.bias"] = torch.tensor([float(stop_bias)], dtype=torch.float32)
+    return sd
