@@ -355,7 +355,9 @@ int vx_get_timings(vx_engine* e, double* out, int32_t n);
  * [slot][layer][K|V][head][max_text+max_audio][64] bf16, or e4m3 bytes with VX_FLAG_KV_FP8), "batch_kv_scale" (VX_FLAG_KV_FP8: the
  * E8M0 scale bytes, [slot][layer][K|V][head][max_text+max_audio][4]), "ar_kv" (the batch-1 KV cache,
  * [layer][K|V][head][max_text+max_audio][head_dim], fp32 on VX_PREC_F32 engines, else bf16), "score_ar_argmax" (int32 per AR row
- * of the last vx_score / vx_score_batch, utterances concatenated: the argmax of the scored logits rows). */
+ * of the last vx_score / vx_score_batch, utterances concatenated: the argmax of the scored logits rows), "tp_wo" (engines that run
+ * the XCD-sharded decode step only: layer 0's out-projection in the word order that step streams, d x d elements of the weight
+ * type - the layout test of csrc/ar_tp.hpp tp_repack_kernel). */
 int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t offset_bytes, int64_t nbytes);
 
 /* Bytes vx_read_buffer's tap `name` holds on an engine created with *cfg, for the taps whose size follows from the

@@ -10,9 +10,11 @@
 
 namespace vx {
 
-constexpr int FQ_G = 16;             // workgroups per head = key splits
+constexpr int FQ_G = 16;             // workgroups per head: the q / k / v projection and the hand-over behind it
+constexpr int FQ_S = 8;              // key splits per head: workgroups j < FQ_S of a head run the attention and publish a partial
 constexpr int FQ_QKV = 192;          // granules a head exchanges after the projection: q[64], k_new[64], v_new[64]
-constexpr int FQ_PART = 66;          // granules of one split's partial softmax: o[64], m, l
+constexpr int FQ_PART = 66;          // granules of one split's partial softmax: o[64], m, l; a head's FQ_S x FQ_PART = 528 are what each
+                                     // of its 16 workgroups gathers (3 loads per thread per sweep)
 constexpr int FQ_SPIN_MAX = 1 << 18; // polls before a wave gives up (~0.3 s)
 
 typedef unsigned long long fq_gran;

@@ -6,11 +6,14 @@
 // 0.35-0.6 us (measured in situ).  So the layer is cut like a tensor-parallel transformer over 8 devices, an XCD playing the
 // device (d = 1024, 16 heads; workgroup b: XCD x = b % 8, local index i = b / 8):
 //
-//   tp_attn_kernel  XCD x owns heads 2x, 2x+1.   LN1 of the residual row (every workgroup, cooperatively), the 12 q / k / v rows
-//                   of its quarter-head slice, [exchange inside the head: 192 values], attention over one sixteenth of the
-//                   cached keys (requested at kernel start), [exchange inside the XCD: the 2 x 16 partial softmaxes], combine,
-//                   and the XCD's K-slice of the out-projection: rows 32i..32i+31 over the 128 channels of its two heads,
-//                   added into the residual accumulator.
+//   tp_attn_kernel  XCD x owns heads 2x, 2x+1, 16 workgroups each (head h = 2x + i / 16, j = i % 16).  LN1 of the residual row
+//                   (every workgroup, cooperatively), the 12 q / k / v rows of its quarter-head slice, [exchange inside the
+//                   head: 192 values]; workgroups j < 8: attention over one eighth of the cached keys (requested at kernel
+//                   start: 8 x 128 slots in bf16 cover 1024 rows, a longer split takes further passes), [exchange inside the
+//                   HEAD: its 8 partial softmaxes, 528 values, gathered by all 16 workgroups], combine, and the head's K-slice
+//                   of the out-projection: rows 64j..64j+63 over the head's 64 channels, added into the residual accumulator.
+//                   (Sixteen splits and an XCD-wide gather of 2 x 16 partials by all 32 workgroups, the geometry before,
+//                   cost 15.8 us per token more: profiles/tp_attn_split_ab.jsonl.)
 //   tp_ffn_kernel   LN2 of the residual row, XCD x owns hidden units 512x..512x+511: 16 FFN1 rows per workgroup,
 //                   [exchange inside the XCD: 512 values], the XCD's K-slice of FFN2: rows 32i..32i+31 over its 512 hidden
 //                   units, added into the residual accumulator.
@@ -46,8 +49,9 @@ constexpr int TP_ACH = TP_D / TP_X;    // attention channels per XCD (two heads)
 
 // Residual stream between the launches of a step: 1024 x int64 fixed point (value x 2^32), three buffers in rotation.  Launch n
 // normalises buffer R = n % 3 (complete: the previous launch's adds and the launch boundary), adds its own output into
-// A = (n + 1) % 3 - every workgroup its 32 partial rows of the sharded GEMV, XCD 0's workgroups also the carry (the value of R)
-// and the GEMV's bias - and zeroes Z = (n + 2) % 3 for the launch after next.  One accumulator instead of eight partial
+// A = (n + 1) % 3 - every workgroup its 32 (feed-forward half) or 64 (attention half) partial rows of the sharded GEMV, XCD 0's
+// workgroups (attention half: head 0's, the two heads of an XCD cover the same rows) also the carry (the value of R) and the
+// GEMV's bias - and zeroes Z = (n + 2) % 3 for the launch after next.  One accumulator instead of eight partial
 // vectors + bias + x: the row every workgroup reads shrinks from 12 loads per thread to 4 (2 x int64 quads, gamma, beta) - with all
 // 128 waves of an XCD asking its L2 for the same lines at the same moment that is what the row's latency follows
 // (12 -> 4 loads: 213.5 -> 204.6 us per token in a timing-only experiment, profiles/r03_notes.md).  Exactness: a partial p is added
@@ -55,7 +59,7 @@ constexpr int TP_ACH = TP_D / TP_X;    // attention channels per XCD (two heads)
 struct TpAccArgs {
   long long* add;          // A: this launch's output accumulates here
   long long* zero;         // Z: zeroed by workgroup 1
-  const float* bias;       // bias of this launch's sharded GEMV (out-projection / linear2), added once (by XCD 0)
+  const float* bias;       // bias of this launch's sharded GEMV (out-projection / linear2), added once per row (tp_acc_tail's `lead`)
 };
 constexpr float TP_FIX = 4294967296.0f, TP_UNFIX = 2.3283064365386963e-10f;
 __device__ __forceinline__ long long tp_fix(float v) { return __float2ll_rn(v * TP_FIX); }
@@ -67,7 +71,7 @@ struct TpAttnArgs {
   const float* qkv_bias;   // (3d,)
   unsigned* err;
   fq_gran* gq;             // this layer's (16, FQ_QKV)
-  fq_gran* gp;             // this layer's (16, FQ_G, FQ_PART)
+  fq_gran* gp;             // this layer's (16, FQ_S, FQ_PART)
   TpAccArgs acc;
   void* kcache;
   void* vcache;
@@ -161,15 +165,16 @@ __device__ __forceinline__ void tp_row_norm(TpRowLoads& r, float* xs, float* red
   __syncthreads();
 }
 
-// The tail of both halves: row 32i + tid/8 of the sharded GEMV's partial (in lanes tid % 8 == 0) goes into the accumulator;
-// XCD 0 also adds the carry and the bias (requested in the prologue: `carry` = R's word / the fp32 embedding, `bo` = bias).
+// The tail of both halves: the lanes that hold a row's partial of the sharded GEMV (`writer`) add it into the accumulator's
+// word `row`; exactly one of the workgroups that cover a row (`lead`) also adds the carry and the bias (requested in the
+// prologue: `carry` = R's word / the fp32 embedding, `bo` = bias).
 template <bool FIRST>
-__device__ __forceinline__ void tp_acc_tail(const TpAccArgs& a, float partial, int xcd, int i, int tid, unsigned long long carry_ll,
-                                            float carry_f, float bo) {
-  if ((tid & 7) == 0) {
+__device__ __forceinline__ void tp_acc_tail(const TpAccArgs& a, float partial, bool writer, int row, bool lead, int tid,
+                                            unsigned long long carry_ll, float carry_f, float bo) {
+  if (writer) {
     long long add = tp_fix(partial);
-    if (xcd == 0) add += tp_fix(bo) + (FIRST ? tp_fix(carry_f) : (long long)carry_ll);
-    atomicAdd(reinterpret_cast<unsigned long long*>(a.add) + 32 * i + (tid >> 3), (unsigned long long)add);
+    if (lead) add += tp_fix(bo) + (FIRST ? tp_fix(carry_f) : (long long)carry_ll);
+    atomicAdd(reinterpret_cast<unsigned long long*>(a.add) + row, (unsigned long long)add);
   }
   if (blockIdx.x == 1) {
     *reinterpret_cast<uint4*>(a.zero + 4 * tid) = make_uint4(0u, 0u, 0u, 0u);
@@ -203,28 +208,39 @@ __device__ __forceinline__ float tp_dot(const uint4 (&w)[KCH], const float (&xr)
 }
 
 // ------------------------------------------------------------------------------------------------ attention half
-// Wo_ = this layer's out-projection re-laid out by tp_repack_kernel: [x][i][m][t] 16-byte words, word (m, t) = row 32i + t/8,
-// channels 128x + (t%8 + 8m) * VEC .. + VEC.
-template <typename WT, bool FIRST>
-__global__ __launch_bounds__(256) void tp_attn_kernel(const void* __restrict__ Wqkv_, const float* __restrict__ x_f32,
-                                                      const long long* __restrict__ racc, const float* __restrict__ gbb,
-                                                      const ArState* __restrict__ st, const unsigned* __restrict__ epoch,
-                                                      const void* __restrict__ Wo_, const TpAttnArgs a) {
+// Wo_ = this layer's out-projection re-laid out by tp_repack_kernel: [x][i][m][t] 16-byte words, i = 16 hl + j, head h = 2x + hl,
+// word (m, t) = row 64j + t/4, channels 64h + (t%4 + 4m) * VEC .. + VEC.
+// Two roles inside a head's 16 workgroups (j = local index % 16), both after the same q / k / v projection and publish:
+//   ATT  (j < FQ_S)   requests its split's cached keys at kernel start, gathers the head's q / newest k / newest v, runs the key
+//                     loop and publishes its partial softmax, then joins the gather below;
+//   !ATT (j >= FQ_S)  requests no K / V, publishes nothing more and goes straight to the gather.
+// The role is a template parameter of the body: the counted waits (N_KV loads behind the weights, or none) are exact in each.
+// No workgroup waits before it has published everything it will publish, so the grid drains whenever it is resident.
+template <int NGRP> struct TpAttnSmem {
+  __attribute__((aligned(16))) float xs[TP_D];
+  float red[8];
+  __attribute__((aligned(16))) float s_qkv[FQ_QKV];
+  __attribute__((aligned(16))) float sm_o[NGRP][64 + 4];
+  float sm_m[4], sm_l[4];
+  float s_wo[4][64];
+  float s_part[FQ_S * FQ_PART];
+  float s_fac[FQ_S];
+  __attribute__((aligned(16))) float s_att[64];
+};
+
+template <typename WT, bool FIRST, bool ATT>
+__device__ __forceinline__ void tp_attn_body(const void* __restrict__ Wqkv_, const float* __restrict__ x_f32,
+                                             const long long* __restrict__ racc, const float* __restrict__ gbb,
+                                             const ArState* __restrict__ st, const unsigned* __restrict__ epoch,
+                                             const void* __restrict__ Wo_, const TpAttnArgs& a,
+                                             TpAttnSmem<4 * Vec16<WT>::N>& sm) {
   constexpr int VEC = Vec16<WT>::N;
   constexpr int KCH = TP_D / (64 * VEC);        // 2 (bf16) / 4 (fp32)
   constexpr int HD = 64;
   constexpr int LPK = HD / VEC, KPW = 64 / LPK, KPB = 4 * KPW, UNR = 4;
-  constexpr int NGRP = 4 * KPW;                 // key groups of the workgroup: 32 (bf16) / 16 (fp32)
-  constexpr int OCH = TP_ACH / (8 * VEC);       // out-projection words per thread: 2 (bf16) / 4 (fp32)
-  __shared__ __attribute__((aligned(16))) float xs[TP_D];
-  __shared__ float red[8];
-  __shared__ __attribute__((aligned(16))) float s_qkv[FQ_QKV];
-  __shared__ __attribute__((aligned(16))) float sm_o[NGRP][HD + 4];
-  __shared__ float sm_m[4], sm_l[4];
-  __shared__ float s_wo[4][HD];
-  __shared__ float s_part[2 * FQ_G * FQ_PART];
-  __shared__ float s_fac[2 * FQ_G];
-  __shared__ __attribute__((aligned(16))) float s_att[TP_ACH];
+  constexpr int OCH = HD / (4 * VEC);           // out-projection words per thread: 2 (bf16) / 4 (fp32)
+  float* const xs = sm.xs;
+  float* const s_qkv = sm.s_qkv;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int x = blockIdx.x & (TP_X - 1), i = blockIdx.x >> 3;
   const int hl = i >> 4, j = i & 15, h = 2 * x + hl;
@@ -248,25 +264,29 @@ __global__ __launch_bounds__(256) void tp_attn_kernel(const void* __restrict__ W
     asm volatile("" : "+s"(bp));
     tp_ld4f(e_bias, bp + min(lane, 2) * TP_D + ch);
   }
-  // the accumulator tail's operands of row 32i + tid/8 (used by XCD 0 only; requested by all: the counted waits stay uniform)
+  // the accumulator tail's operands of row 64j + tid/4 (used by head 0's workgroups only; requested by all: the counted waits
+  // stay uniform)
+  const int orow = 64 * j + (tid >> 2);
   unsigned long long carry_ll = 0ull;
   float carry_f = 0.f, bo;
-  if (FIRST) tp_ld4f(carry_f, x_f32 + 32 * i + (tid >> 3));
-  else asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(carry_ll) : "v"(racc + 32 * i + (tid >> 3)) : "memory");
-  tp_ld4f(bo, a.acc.bias + 32 * i + (tid >> 3));
-  // second-stage operands: the out-projection slice and this split's cached keys
+  if (FIRST) tp_ld4f(carry_f, x_f32 + orow);
+  else asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(carry_ll) : "v"(racc + orow) : "memory");
+  tp_ld4f(bo, a.acc.bias + orow);
+  // second-stage operands: the out-projection slice and (ATT) this split's cached keys
   const int n_old = st_row;  // the newest row travels in the granules
-  const int chunk = (n_old + FQ_G - 1) / FQ_G;
+  const int chunk = (n_old + FQ_S - 1) / FQ_S;
   const int j0 = j * chunk, j1 = min(n_old, j0 + chunk);
   const int sub = lane % LPK, grp = lane / LPK;
   vx_u32x4 wo[OCH];
   vx_u32x4 kr[UNR], vr[UNR];
   const WT* kb;
   const WT* vb;
-  auto tp_stage2 = [&]() {
+  {
     const uint4* wb = reinterpret_cast<const uint4*>(Wo_) + (size_t)(x * TP_WG + i) * OCH * 256;
 #pragma unroll
     for (int m = 0; m < OCH; ++m) tp_ld16w(wo[m], wb + m * 256 + tid);
+  }
+  if constexpr (ATT) {
     const void* kcp = a.kcache;
     const void* vcp = a.vcache;
     int ctxm = a.ctx_max;
@@ -281,9 +301,8 @@ __global__ __launch_bounds__(256) void tp_attn_kernel(const void* __restrict__ W
       tp_ld16(kr[u], kb + (size_t)jk * HD);
       tp_ld16(vr[u], vb + (size_t)jk * HD);
     }
-  };
-  tp_stage2();
-  auto load_pass = [&](int base) {  // later passes of a long context (> 16 * UNR * KPB rows): plain loads
+  }
+  auto load_pass = [&](int base) {  // later passes of a long context (> FQ_S * UNR * KPB rows): plain loads
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int jk = min(base + u * KPB + wave * KPW + grp, max(j1, 1) - 1);
@@ -292,12 +311,12 @@ __global__ __launch_bounds__(256) void tp_attn_kernel(const void* __restrict__ W
       vr[u] = vx_u32x4{v4.x, v4.y, v4.z, v4.w};
     }
   };
-  constexpr int N_KV = 2 * UNR, N_WO = OCH, N_W = 3 * KCH;
+  constexpr int N_KV = ATT ? 2 * UNR : 0, N_WO = OCH, N_W = 3 * KCH;
 
   // ---- LN1, the three dot products, publish ----
   tp_row_wait<FIRST, N_W + 3 + N_WO + N_KV>(rl);
   TP_STAMP(0, 7);
-  tp_row_norm<FIRST>(rl, xs, red, tid);
+  tp_row_norm<FIRST>(rl, xs, sm.red, tid);
   TP_STAMP(0, 1);
   {
     float xr[KCH][VEC];
@@ -325,159 +344,177 @@ __global__ __launch_bounds__(256) void tp_attn_kernel(const void* __restrict__ W
     }
   }
   TP_STAMP(0, 2);
-  // ---- the head's q / newest k / newest v ----
-  {
-    float v1[1];
-    gran_gather<1>(a.gq + (size_t)h * FQ_QKV, FQ_QKV, tag, v1, a.err, 1u);
-    if (tid < FQ_QKV) s_qkv[tid] = v1[0];
-  }
-#pragma unroll
-  for (int u = 0; u < UNR; ++u) { tp_wait<0>(kr[u]); tp_wait<0>(vr[u]); }  // the gather waited for everything
-#pragma unroll
-  for (int m = 0; m < OCH; ++m) tp_wait<0>(wo[m]);
-  asm volatile("" : "+v"(carry_ll), "+v"(carry_f), "+v"(bo));
-  TP_STAMP(0, 3);
-  __syncthreads();
-  TP_STAMP(0, 8);
-  float qv[VEC];
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) qv[c] = s_qkv[sub * VEC + c] * a.scale;
-
-  // ---- this split's keys: every WAVE keeps its own running softmax (no workgroup reduction in the loop) ----
-  float M = -INFINITY, L = 0.f, acc[VEC];
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) acc[c] = 0.f;
-  const bool owner = (j == FQ_G - 1) && wave == 0;  // the newest key: wave 0 of the last split (uniform per wave)
-  float sn = -INFINITY;
-  if (owner) {
-    float dot = 0.f;
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) dot = fmaf(s_qkv[HD + sub * VEC + c], qv[c], dot);
-    sn = (LPK == 8) ? group8_sum_dpp(dot) : group16_sum_dpp(dot);  // the same number in every lane group
-  }
-  for (int base = j0; base < j1 || (owner && base == j0); base += UNR * KPB) {
-    if (base != j0) load_pass(base);
-    const int nr = (j1 - base + KPB - 1) / KPB;  // rounds of this pass that hold keys (uniform; <= 0: the newest key only)
-    float sc[UNR], mloc = (base == j0) ? sn : -INFINITY;
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      sc[u] = -INFINITY;
-      if (u < nr) {
-        const int jk = base + u * KPB + wave * KPW + grp;
-        float kf[VEC];
-        unpack<WT>(tp_u4(kr[u]), kf);
-        float dot = 0.f;
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) dot = fmaf(kf[c], qv[c], dot);
-        dot = (LPK == 8) ? group8_sum_dpp(dot) : group16_sum_dpp(dot);
-        sc[u] = (jk < j1) ? dot : -INFINITY;
-        mloc = fmaxf(mloc, sc[u]);
-      }
+  if constexpr (ATT) {
+    // ---- the head's q / newest k / newest v ----
+    {
+      float v1[1];
+      gran_gather<1>(a.gq + (size_t)h * FQ_QKV, FQ_QKV, tag, v1, a.err, 1u);
+      if (tid < FQ_QKV) s_qkv[tid] = v1[0];
     }
-    mloc = wave_max_dpp(mloc);
-    if (mloc != -INFINITY) {  // wave-uniform
-      const float Mn = fmaxf(M, mloc);
-      const float corr = (M == -INFINITY) ? 0.f : tp_exp<WT>(M - Mn);
-      L *= corr;
 #pragma unroll
-      for (int c = 0; c < VEC; ++c) acc[c] *= corr;
-      M = Mn;
+    for (int u = 0; u < UNR; ++u) { tp_wait<0>(kr[u]); tp_wait<0>(vr[u]); }  // the gather waited for everything
 #pragma unroll
-      for (int u = 0; u < UNR; ++u)
+    for (int m = 0; m < OCH; ++m) tp_wait<0>(wo[m]);
+    asm volatile("" : "+v"(carry_ll), "+v"(carry_f), "+v"(bo));
+    TP_STAMP(0, 3);
+    __syncthreads();
+    TP_STAMP(0, 8);
+    float qv[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) qv[c] = s_qkv[sub * VEC + c] * a.scale;
+
+    // ---- this split's keys: every WAVE keeps its own running softmax (no workgroup reduction in the loop) ----
+    float M = -INFINITY, L = 0.f, acc[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) acc[c] = 0.f;
+    const bool owner = (j == FQ_S - 1) && wave == 0;  // the newest key: wave 0 of the last split (uniform per wave)
+    float sn = -INFINITY;
+    if (owner) {
+      float dot = 0.f;
+#pragma unroll
+      for (int c = 0; c < VEC; ++c) dot = fmaf(s_qkv[HD + sub * VEC + c], qv[c], dot);
+      sn = (LPK == 8) ? group8_sum_dpp(dot) : group16_sum_dpp(dot);  // the same number in every lane group
+    }
+    for (int base = j0; base < j1 || (owner && base == j0); base += UNR * KPB) {
+      if (base != j0) load_pass(base);
+      const int nr = (j1 - base + KPB - 1) / KPB;  // rounds of this pass that hold keys (uniform; <= 0: the newest key only)
+      float sc[UNR], mloc = (base == j0) ? sn : -INFINITY;
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        sc[u] = -INFINITY;
         if (u < nr) {
-          float vf[VEC];
-          unpack<WT>(tp_u4(vr[u]), vf);
-          const float p = tp_exp<WT>(sc[u] - M);  // exp(-inf) = 0 for the masked keys
+          const int jk = base + u * KPB + wave * KPW + grp;
+          float kf[VEC];
+          unpack<WT>(tp_u4(kr[u]), kf);
+          float dot = 0.f;
+#pragma unroll
+          for (int c = 0; c < VEC; ++c) dot = fmaf(kf[c], qv[c], dot);
+          dot = (LPK == 8) ? group8_sum_dpp(dot) : group16_sum_dpp(dot);
+          sc[u] = (jk < j1) ? dot : -INFINITY;
+          mloc = fmaxf(mloc, sc[u]);
+        }
+      }
+      mloc = wave_max_dpp(mloc);
+      if (mloc != -INFINITY) {  // wave-uniform
+        const float Mn = fmaxf(M, mloc);
+        const float corr = (M == -INFINITY) ? 0.f : tp_exp<WT>(M - Mn);
+        L *= corr;
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) acc[c] *= corr;
+        M = Mn;
+#pragma unroll
+        for (int u = 0; u < UNR; ++u)
+          if (u < nr) {
+            float vf[VEC];
+            unpack<WT>(tp_u4(vr[u]), vf);
+            const float p = tp_exp<WT>(sc[u] - M);  // exp(-inf) = 0 for the masked keys
+            L += p;
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) acc[c] = fmaf(p, vf[c], acc[c]);
+          }
+        if (owner && base == j0 && grp == 0) {
+          const float p = tp_exp<WT>(sn - M);
           L += p;
 #pragma unroll
-          for (int c = 0; c < VEC; ++c) acc[c] = fmaf(p, vf[c], acc[c]);
+          for (int c = 0; c < VEC; ++c) acc[c] = fmaf(p, s_qkv[2 * HD + sub * VEC + c], acc[c]);
         }
-      if (owner && base == j0 && grp == 0) {
-        const float p = tp_exp<WT>(sn - M);
-        L += p;
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) acc[c] = fmaf(p, s_qkv[2 * HD + sub * VEC + c], acc[c]);
       }
     }
-  }
-  TP_STAMP(0, 9);
-  // merge: a wave's key groups share its maximum, so they add up plainly - through the wave's own LDS rows, no workgroup
-  // barrier (LDS operations of one wave execute in order); lane c then owns channel c of the wave's partial
-  {
+    TP_STAMP(0, 9);
+    // merge: a wave's key groups share its maximum, so they add up plainly - through the wave's own LDS rows, no workgroup
+    // barrier (LDS operations of one wave execute in order); lane c then owns channel c of the wave's partial
+    {
 #pragma unroll
-    for (int c = 0; c < VEC; c += 4)
-      *reinterpret_cast<float4*>(&sm_o[wave * KPW + grp][sub * VEC + c]) = make_float4(acc[c], acc[c + 1], acc[c + 2], acc[c + 3]);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    float oc = 0.f;
+      for (int c = 0; c < VEC; c += 4)
+        *reinterpret_cast<float4*>(&sm.sm_o[wave * KPW + grp][sub * VEC + c]) = make_float4(acc[c], acc[c + 1], acc[c + 2], acc[c + 3]);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      float oc = 0.f;
 #pragma unroll
-    for (int g = 0; g < KPW; ++g) oc += sm_o[wave * KPW + g][lane];
-    const float Lw = wave_sum_dpp(sub == 0 ? L : 0.f);
-    s_wo[wave][lane] = oc;
-    if (lane == 0) { sm_m[wave] = M; sm_l[wave] = Lw; }
-  }
-  TP_STAMP(0, 10);
-  __syncthreads();
-  TP_STAMP(0, 11);
-  if (tid < FQ_PART) {
-    const float Mx = fmaxf(fmaxf(sm_m[0], sm_m[1]), fmaxf(sm_m[2], sm_m[3]));
-    float v = 0.f;
-    if (tid == HD) {
-      v = Mx;
-    } else {
-#pragma unroll
-      for (int wv = 0; wv < 4; ++wv)
-        v = fmaf(tid < HD ? s_wo[wv][tid] : sm_l[wv], (sm_m[wv] == -INFINITY) ? 0.f : tp_exp<WT>(sm_m[wv] - Mx), v);
+      for (int g = 0; g < KPW; ++g) oc += sm.sm_o[wave * KPW + g][lane];
+      const float Lw = wave_sum_dpp(sub == 0 ? L : 0.f);
+      sm.s_wo[wave][lane] = oc;
+      if (lane == 0) { sm.sm_m[wave] = M; sm.sm_l[wave] = Lw; }
     }
-    gran_store(a.gp + ((size_t)h * FQ_G + j) * FQ_PART + tid, v, tag);
+    TP_STAMP(0, 10);
+    __syncthreads();
+    TP_STAMP(0, 11);
+    if (tid < FQ_PART) {
+      const float Mx = fmaxf(fmaxf(sm.sm_m[0], sm.sm_m[1]), fmaxf(sm.sm_m[2], sm.sm_m[3]));
+      float v = 0.f;
+      if (tid == HD) {
+        v = Mx;
+      } else {
+#pragma unroll
+        for (int wv = 0; wv < 4; ++wv)
+          v = fmaf(tid < HD ? sm.s_wo[wv][tid] : sm.sm_l[wv], (sm.sm_m[wv] == -INFINITY) ? 0.f : tp_exp<WT>(sm.sm_m[wv] - Mx), v);
+      }
+      gran_store(a.gp + ((size_t)h * FQ_S + j) * FQ_PART + tid, v, tag);
+    }
+    TP_STAMP(0, 4);
+  } else {  // stamps builds: the phases this role skips carry the time it passed them by (tests/probes/tp_stamps.py reads every slot)
+    TP_STAMP(0, 3); TP_STAMP(0, 8); TP_STAMP(0, 9); TP_STAMP(0, 10); TP_STAMP(0, 11); TP_STAMP(0, 4);
   }
-  TP_STAMP(0, 4);
-  // ---- both heads' partial softmaxes (2 x 16 x 66 granules), combined by every workgroup of the XCD ----
+  // ---- the head's partial softmaxes (8 x 66 granules), combined by every workgroup of the head ----
   {
-    constexpr int NG = (2 * FQ_G * FQ_PART + 255) / 256;
+    constexpr int NG = (FQ_S * FQ_PART + 255) / 256;
     float pv[NG];
-    gran_gather<NG>(a.gp + (size_t)(2 * x) * FQ_G * FQ_PART, 2 * FQ_G * FQ_PART, tag, pv, a.err, 2u);
+    gran_gather<NG>(a.gp + (size_t)h * FQ_S * FQ_PART, FQ_S * FQ_PART, tag, pv, a.err, 2u);
 #pragma unroll
     for (int g = 0; g < NG; ++g)
-      if (tid + 256 * g < 2 * FQ_G * FQ_PART) s_part[tid + 256 * g] = pv[g];
+      if (tid + 256 * g < FQ_S * FQ_PART) sm.s_part[tid + 256 * g] = pv[g];
+  }
+  if constexpr (!ATT) {  // the gather waited for everything
+#pragma unroll
+    for (int m = 0; m < OCH; ++m) tp_wait<0>(wo[m]);
+    asm volatile("" : "+v"(carry_ll), "+v"(carry_f), "+v"(bo));
   }
   TP_STAMP(0, 5);
   __syncthreads();
-  if (tid < 2 * FQ_G) {  // thread (head, split): exp(m_s - M) / L of its split; a head's 16 threads are one DPP row
-    const float* hp = s_part + (tid >> 4) * FQ_G * FQ_PART;
+  if (tid < FQ_S) {  // thread s: exp(m_s - M) / L of split s; the 8 threads are one DPP half-row
+    const float* hp = sm.s_part;
     float Mx = hp[HD];
 #pragma unroll
-    for (int s = 1; s < FQ_G; ++s) Mx = fmaxf(Mx, hp[s * FQ_PART + HD]);
-    const float pm = hp[(tid & 15) * FQ_PART + HD];
+    for (int s = 1; s < FQ_S; ++s) Mx = fmaxf(Mx, hp[s * FQ_PART + HD]);
+    const float pm = hp[tid * FQ_PART + HD];
     const float es = (pm == -INFINITY) ? 0.f : tp_exp<WT>(pm - Mx);
-    const float Ls = group16_sum_dpp(hp[(tid & 15) * FQ_PART + HD + 1] * es);
-    s_fac[tid] = es * (1.0f / Ls);
+    const float Ls = group8_sum_dpp(hp[tid * FQ_PART + HD + 1] * es);
+    sm.s_fac[tid] = es * (1.0f / Ls);
   }
   __syncthreads();
-  if (tid < TP_ACH) {
-    const float* hp = s_part + (tid >> 6) * FQ_G * FQ_PART + (tid & 63);
-    const float* fp = s_fac + (tid >> 6) * FQ_G;
+  if (tid < HD) {
     float o = 0.f;
 #pragma unroll
-    for (int s = 0; s < FQ_G; ++s) o = fmaf(hp[s * FQ_PART], fp[s], o);
-    s_att[tid] = o;
+    for (int s = 0; s < FQ_S; ++s) o = fmaf(sm.s_part[s * FQ_PART + tid], sm.s_fac[s], o);
+    sm.s_att[tid] = o;
   }
   __syncthreads();
-  // ---- the XCD's K-slice of the out-projection: row 32i + tid/8 over the XCD's 128 channels, 8 lanes per row ----
+  // ---- the head's K-slice of the out-projection: row 64j + tid/4 over the head's 64 channels, 4 lanes per row.  The two heads
+  // of an XCD cover the same rows: head 0 (XCD 0, hl 0) alone adds the carry and the bias ----
   {
     float s = 0.f;
 #pragma unroll
     for (int m = 0; m < OCH; ++m) {
       float wf[VEC];
       unpack<WT>(tp_u4(wo[m]), wf);
-      const float* ap = s_att + ((tid & 7) + 8 * m) * VEC;
+      const float* ap = sm.s_att + ((tid & 3) + 4 * m) * VEC;
 #pragma unroll
       for (int c = 0; c < VEC; ++c) s = fmaf(wf[c], ap[c], s);
     }
-    s = group8_sum_dpp(s);
-    tp_acc_tail<FIRST>(a.acc, s, x, i, tid, carry_ll, carry_f, bo);
+    s = group4_sum_dpp(s);
+    tp_acc_tail<FIRST>(a.acc, s, (tid & 3) == 0, orow, h == 0, tid, carry_ll, carry_f, bo);
   }
   TP_STAMP(0, 6);
+}
+
+template <typename WT, bool FIRST>
+__global__ __launch_bounds__(256) void tp_attn_kernel(const void* __restrict__ Wqkv_, const float* __restrict__ x_f32,
+                                                      const long long* __restrict__ racc, const float* __restrict__ gbb,
+                                                      const ArState* __restrict__ st, const unsigned* __restrict__ epoch,
+                                                      const void* __restrict__ Wo_, const TpAttnArgs a) {
+  __shared__ TpAttnSmem<4 * Vec16<WT>::N> sm;
+  if (((blockIdx.x >> 3) & (FQ_G - 1)) < FQ_S) tp_attn_body<WT, FIRST, true>(Wqkv_, x_f32, racc, gbb, st, epoch, Wo_, a, sm);
+  else tp_attn_body<WT, FIRST, false>(Wqkv_, x_f32, racc, gbb, st, epoch, Wo_, a, sm);
 }
 
 // ------------------------------------------------------------------------------------------------ feed-forward half
@@ -568,7 +605,7 @@ __global__ __launch_bounds__(256) void tp_ffn_kernel(const void* __restrict__ W1
       for (int c = 0; c < VEC; ++c) s = fmaf(wf[c], hp[c], s);
     }
     s = group8_sum_dpp(s);
-    tp_acc_tail<false>(a.acc, s, x, i, tid, carry_ll, 0.f, bo);
+    tp_acc_tail<false>(a.acc, s, (tid & 7) == 0, 32 * i + (tid >> 3), x == 0, tid, carry_ll, 0.f, bo);
   }
   TP_STAMP(1, 4);
 }
@@ -614,9 +651,12 @@ __global__ __launch_bounds__(256) void tp_head_kernel(const void* __restrict__ W
   }
 }
 
-// ---- one-time re-layout of a (1024, K) matrix into the sharded word order the two kernels above stream:
-// dst word [(x * 32 + i) * NW + m][t] = src[row 32i + t/8][cols KX * x + (t%8 + 8m) * VEC .. + VEC], KX = K / 8, NW = KX / (8 VEC)
-template <typename WT>
+// ---- one-time re-layout of a (1024, K) matrix into the sharded word order the two kernels above stream, one 256-thread block
+// of words per (workgroup wg = 32 x + i, word m):  dst word [wg * NW + m][t] =
+//   linear2 (HEADS = false, K = 4096, NW = K / (64 VEC)):  src[row 32i + t/8][cols K/8 * x + (t%8 + 8m) * VEC .. + VEC]
+//   out-projection (HEADS = true, K = 1024, NW = 16 / VEC), i = 16 hl + j, head h = 2x + hl:
+//                                                          src[row 64j + t/4][cols 64h + (t%4 + 4m) * VEC .. + VEC]
+template <typename WT, bool HEADS>
 __global__ void tp_repack_kernel(const WT* __restrict__ src, uint4* __restrict__ dst, int K) {
   constexpr int VEC = Vec16<WT>::N;
   const int KX = K / TP_X, NW = KX / (8 * VEC);
@@ -628,7 +668,14 @@ __global__ void tp_repack_kernel(const WT* __restrict__ src, uint4* __restrict__
   const int m = (int)(blk % NW);
   const int wg = (int)(blk / NW);
   const int x = wg / TP_WG, i = wg % TP_WG;
-  const int row = 32 * i + (t >> 3), col = KX * x + ((t & 7) + 8 * m) * VEC;
+  int row, col;
+  if (HEADS) {
+    row = 64 * (i & 15) + (t >> 2);
+    col = 64 * (2 * x + (i >> 4)) + ((t & 3) + 4 * m) * VEC;
+  } else {
+    row = 32 * i + (t >> 3);
+    col = KX * x + ((t & 7) + 8 * m) * VEC;
+  }
   dst[word] = *reinterpret_cast<const uint4*>(src + (size_t)row * K + col);
 }
 

@@ -69,12 +69,6 @@ __device__ __forceinline__ void kv8_unpack(const uint4& r, float (&o)[16]) {
     o[4 * k] = lo[0]; o[4 * k + 1] = lo[1]; o[4 * k + 2] = hi[0]; o[4 * k + 3] = hi[1];
   }
 }
-// sum over aligned groups of 4 lanes; every lane of the group gets the group sum
-__device__ __forceinline__ float group4_sum_dpp(float v) {
-  v += dpp_f<0xB1>(0.f, v);
-  v += dpp_f<0x4E>(0.f, v);
-  return v;
-}
 
 // C[b][n] = sum_k A[b][k] W[n][k] on v_mfma_f32_16x16x32_bf16: one workgroup = one 16-row n tile (x one K
 // group), its 4 waves take 4 K slices of NS steps and are summed through LDS in wave order.  Lane

@@ -136,10 +136,14 @@ __device__ __forceinline__ uint32_t wave_umin_dpp(uint32_t v) {
   v = min(v, (uint32_t)dpp_i<0x143, 0xC>((int)v, (int)v));
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
-// sum over aligned groups of 8 / 16 lanes; every lane of the group gets the group sum
-__device__ __forceinline__ float group8_sum_dpp(float v) {
+// sum over aligned groups of 4 / 8 / 16 lanes; every lane of the group gets the group sum
+__device__ __forceinline__ float group4_sum_dpp(float v) {
   v += dpp_f<0xB1>(0.f, v);
   v += dpp_f<0x4E>(0.f, v);
+  return v;
+}
+__device__ __forceinline__ float group8_sum_dpp(float v) {
+  v = group4_sum_dpp(v);
   v += dpp_f<0x141>(0.f, v);
   return v;
 }

@@ -728,11 +728,11 @@ extern "C" int vx_finalize_weights(vx_engine* e) {
       const LayerW& l = e->ar_l[li];
       const unsigned g1 = (unsigned)((size_t)TP_D * TP_D * e->esz / 16 / 256), g2 = (unsigned)((size_t)TP_D * TP_FF * e->esz / 16 / 256);
       if (e->bf16) {
-        tp_repack_kernel<bf16><<<g1, 256, 0, e->es>>>((const bf16*)l.out_w, (uint4*)e->tp_wo[li], TP_D);
-        tp_repack_kernel<bf16><<<g2, 256, 0, e->es>>>((const bf16*)l.w2, (uint4*)e->tp_w2[li], TP_FF);
+        tp_repack_kernel<bf16, true><<<g1, 256, 0, e->es>>>((const bf16*)l.out_w, (uint4*)e->tp_wo[li], TP_D);
+        tp_repack_kernel<bf16, false><<<g2, 256, 0, e->es>>>((const bf16*)l.w2, (uint4*)e->tp_w2[li], TP_FF);
       } else {
-        tp_repack_kernel<float><<<g1, 256, 0, e->es>>>((const float*)l.out_w, (uint4*)e->tp_wo[li], TP_D);
-        tp_repack_kernel<float><<<g2, 256, 0, e->es>>>((const float*)l.w2, (uint4*)e->tp_w2[li], TP_FF);
+        tp_repack_kernel<float, true><<<g1, 256, 0, e->es>>>((const float*)l.out_w, (uint4*)e->tp_wo[li], TP_D);
+        tp_repack_kernel<float, false><<<g2, 256, 0, e->es>>>((const float*)l.w2, (uint4*)e->tp_w2[li], TP_FF);
       }
     }
     // {gamma, beta, bias arriving with the partials} of every norm site: 2 li = LN1 (bias = previous linear2's; none at layer 0),
@@ -876,12 +876,12 @@ static int tp_setup(vx_engine* e) {
   VXC(dalloc_t(e, &e->tp_gh, L * TP_X * TP_HID));
   VXC(dalloc_t(e, &e->tp_gbb, (2 * L + 1) * 3 * TP_D));
   VXC(dalloc_t(e, &e->fq_gq, L * H * FQ_QKV));
-  VXC(dalloc_t(e, &e->fq_gp, L * H * FQ_G * FQ_PART));
+  VXC(dalloc_t(e, &e->fq_gp, L * H * FQ_S * FQ_PART));
   HIPC(hipMemset(e->tp_gbb, 0, (2 * L + 1) * 3 * TP_D * 4));
   HIPC(hipMemset(e->tp_xacc, 0, (size_t)3 * TP_D * sizeof(long long)));
   HIPC(hipMemset(e->tp_gh, 0, L * TP_X * TP_HID * sizeof(fq_gran)));  // zero tags: never equal to a step counter (starts at 1)
   HIPC(hipMemset(e->fq_gq, 0, L * H * FQ_QKV * sizeof(fq_gran)));
-  HIPC(hipMemset(e->fq_gp, 0, L * H * FQ_G * FQ_PART * sizeof(fq_gran)));
+  HIPC(hipMemset(e->fq_gp, 0, L * H * FQ_S * FQ_PART * sizeof(fq_gran)));
   e->tp_wo.assign(L, nullptr); e->tp_w2.assign(L, nullptr);
   for (size_t li = 0; li < L; ++li) {
     VXC(dalloc(e, &e->tp_wo[li], (size_t)TP_D * TP_D * e->esz));
@@ -1561,7 +1561,7 @@ static int enqueue_ar_step_tp(vx_engine* e, hipStream_t s) {
     TpAttnArgs a{};
     const float* gbb = e->tp_gbb + (size_t)(2 * li) * 3 * TP_D;
     a.qkv_bias = l.in_b; a.err = e->d_epoch + 1;
-    a.gq = e->fq_gq + (size_t)li * H * FQ_QKV; a.gp = e->fq_gp + (size_t)li * H * FQ_G * FQ_PART;
+    a.gq = e->fq_gq + (size_t)li * H * FQ_QKV; a.gp = e->fq_gp + (size_t)li * H * FQ_S * FQ_PART;
     a.acc.add = acc(n + 1); a.acc.zero = acc(n + 2); a.acc.bias = l.out_b;
     a.kcache = kc; a.vcache = kc + kv_layer / 2; a.ctx_max = e->ctx_max;
     a.scale = 1.0f / sqrtf((float)hd); a.layer = li;
@@ -3019,6 +3019,7 @@ extern "C" int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t
     size = (int64_t)e->bmax * e->bkv_slot * (e->kv8 ? 1 : 2);
   }
   else if (n == "ar_kv") { src = (const char*)e->kv; size = config_buffer_bytes(e->cfg, n); }
+  else if (n == "tp_wo" && e->tp) { src = (const char*)e->tp_wo[0]; size = (int64_t)TP_D * TP_D * e->esz; }
   else if (n == "score_ar_argmax" && e->sc_argmax) { src = (const char*)e->sc_argmax; size = (int64_t)e->sc_rows * 4; }
   else if (n == "batch_kv_scale" && e->kv8) { src = (const char*)e->bkv8s; size = (int64_t)e->bmax * e->bkv_slot / 16; }
   else return fail(VX_ERR_ARG, "unknown buffer '%s'", name);
