@@ -808,6 +808,73 @@ int vx_mel_teacher_forced(vx_mel* m, const int64_t* text, int32_t S, const float
  * of the captured graph; 0 with VX_MEL_NO_GRAPH), out[3] ms of the last encode. */
 int vx_mel_get_timings(vx_mel* m, double* out, int32_t n);
 
+/* ---- Griffin-Lim vocoder: log-mel frames to a 24 kHz waveform ------------------------------------------------------------------
+ * The inverse of the filterbank above, with its framing: 24 kHz, n_fft 1024, hop 256, the periodic Hann window w.  A handle of
+ * its own: no weights.  Per utterance, logmel (T, n_mels) fp32 as vx_fbank_extract writes it; B is the (n_mels x 513) mel basis
+ * (by default the built-in Slaney table of vx_fbank_create, from the same routine).
+ *   1. mel = exp(logmel).
+ *   2. mag = max(0, mel P^T), (T, 513), with P = B^T (B B^T)^-1 (513 x n_mels): the minimum-norm least-squares inverse and a clamp
+ *      at zero (the rule of torchaudio's InverseMelScale).  P is computed on the host in fp64 by Cholesky of B B^T and rounded
+ *      once; every cell of mag is summed in ascending filter order.
+ *   3. y = I(X) for X (T, 513) complex: frame f is the inverse real DFT of row f (bins 0..512, Hermitian extension, the
+ *      imaginary parts of bins 0 and 512 ignored, scale 1 / 1024) times w; frames are overlap-added at offsets 256 f in ascending
+ *      frame order; y[n] = ola[n] / max(env[n], env_floor) for n in [0, 256 T) with env[n] = sum_f w^2[n - 256 f].  The 768
+ *      samples past 256 T are dropped, so the length is 256 T and vx_fbank_frames of it is T.  env_floor (default 0.1) is part of
+ *      the definition: w[0] = 0 and frame 0 alone covers the first 256 samples, so the floor makes the first ~8 ms a fade-in;
+ *      the interior has env = 1.5.
+ *   4. S(y) is the filterbank's analysis: y followed by 768 zeros, frame f = samples [256 f, 256 f + 1024) times w, one-sided DFT.
+ *   5. Griffin-Lim with momentum (torchaudio.functional.griffinlim): ang = init (unit complex; 1 + 0i without one), tprev = 0;
+ *      n_iter times { reb = S(I(mag ang)); a = reb - tprev momentum / (1 + momentum); ang = a / (|a| + 1e-16); tprev = reb };
+ *      y = I(mag ang).
+ * fp32 throughout; both transforms are the filterbank's 32 x 32 four-step factorisation on the fp32 matrix instruction with
+ * tables computed in fp64 and rounded once.  There is no random number generator: a random start is the caller's init_phase. */
+typedef struct vx_vocoder vx_vocoder;
+typedef struct vx_vocoder_config {
+  int32_t struct_size;       /* sizeof(vx_vocoder_config) */
+  int32_t sample_rate;       /* 24000 */
+  int32_t n_fft;             /* 1024 (also the window length) */
+  int32_t hop;               /* 256 */
+  int32_t n_mels;            /* 1 .. 128 */
+  float fmin, fmax;          /* band of the built-in Slaney basis, 0 <= fmin < fmax <= 12000 */
+  float env_floor;           /* floor under the window envelope, > 0 (0.1) */
+  int32_t max_batch;         /* utterances per call */
+  int32_t max_total_frames;  /* frames per call, summed over its utterances; <= 2^21 */
+} vx_vocoder_config;
+/* Host only, no HIP call (the tables go to the device current at the first synthesis).  Nulls, a wrong struct_size, max_batch < 1,
+ * max_total_frames < 1 or an env_floor that is not positive and finite -> VX_ERR_ARG; another geometry, n_mels, band, a
+ * max_total_frames above 2^21, or a built-in basis whose B B^T has no Cholesky factor -> VX_ERR_UNSUPPORTED. */
+int vx_vocoder_create(const vx_vocoder_config* cfg, vx_vocoder** out);
+void vx_vocoder_destroy(vx_vocoder* v);
+/* Host only.  set_mel_basis: a HOST (n_mels x 513) basis; its inverse P replaces the current one at the next synthesis.  A basis
+ * whose B B^T has no Cholesky factor (a pivot below 1e-12 of its diagonal entry: empty or linearly dependent filters) ->
+ * VX_ERR_UNSUPPORTED, and the handle keeps what it had.  set_inverse: the caller's own HOST (513 x n_mels) table instead, taken as
+ * it is.  get_inverse copies the current (513 x n_mels) table out. */
+int vx_vocoder_set_mel_basis(vx_vocoder* v, const float* basis);
+int vx_vocoder_set_inverse(vx_vocoder* v, const float* inverse);
+int vx_vocoder_get_inverse(const vx_vocoder* v, float* inverse);
+/* 256 n_frames, the samples a synthesis of n_frames = T frames writes; 0 for a negative T.  Host only. */
+int64_t vx_vocoder_samples(int64_t n_frames);
+/* n utterances: logmel[i] DEVICE fp32 (n_frames[i], n_mels), wav_out[i] DEVICE fp32 of 256 n_frames[i] samples; init_phase:
+ * NULL (the zero-phase start) or per utterance DEVICE fp32 (n_frames[i], 513) radians; phase_out: NULL or per utterance DEVICE
+ * fp32 (n_frames[i], 513, 2), the final ang (re, im).  The pointer arrays and n_frames live on the host.  An utterance with
+ * n_frames[i] = 0 writes nothing and its pointers are not looked at.  Every utterance is bitwise what it is alone, and two
+ * identical calls give the same bits.  Checked before any HIP call, in this order: null arguments (init_phase and phase_out
+ * excepted), n < 1, n_iter < 0, a momentum outside [0, 1) or not finite -> VX_ERR_ARG; n > max_batch -> VX_ERR_CAPACITY; then
+ * per utterance in order n_frames[i] < 0 or, with frames, a null entry -> VX_ERR_ARG, and a running sum of frames above
+ * max_total_frames -> VX_ERR_CAPACITY.  A call without any frame returns here.  The work (one launch for mag and the start, two
+ * per iteration, two for the final y) is enqueued on `stream`; the host waits only for the previous call's staging copy (and,
+ * after a new inverse or when the workspace, 14356 bytes per frame of the largest call so far, has to grow, for the previous
+ * call).  Calls on one handle must not overlap. */
+int vx_vocoder_synthesize(vx_vocoder* v, int32_t n, const float* const* logmel, const int32_t* n_frames,
+                          const float* const* init_phase, int32_t n_iter, float momentum, float* const* wav_out,
+                          float* const* phase_out, void* stream);
+/* The warm start: the same call with the start given as phase_out gives it, init_ang[i] DEVICE fp32 (n_frames[i], 513, 2), taken
+ * as it is (not normalised); init_ang itself must not be NULL.  With n_iter = 0 the phase_out of a synthesis reproduces its
+ * waveform bit for bit. */
+int vx_vocoder_synthesize_warm(vx_vocoder* v, int32_t n, const float* const* logmel, const int32_t* n_frames,
+                               const float* const* init_ang, int32_t n_iter, float momentum, float* const* wav_out,
+                               float* const* phase_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

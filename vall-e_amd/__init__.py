@@ -5,7 +5,7 @@ from .config import ModelConfig, add_model_arguments, NUM_AUDIO_TOKENS, NUM_TEXT
 __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_TOKENS", "AudioTokenizer", "CodecConfig", "EncodecDecoder",
            "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio",
            "BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis",
-           "DTW", "DTWResult", "mel_cepstral_distortion"]
+           "DTW", "DTWResult", "mel_cepstral_distortion", "GriffinLim", "mel_to_waveform"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -21,4 +21,8 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import dtw
 
         return getattr(dtw, name)
+    if name in ("GriffinLim", "mel_to_waveform"):
+        from . import vocoder
+
+        return getattr(vocoder, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,6 +11,7 @@
 
 #undef VX_STAMPS  // the in-kernel stamps write device globals of engine.hip's unit, out of this unit's reach
 #include "host.hpp"
+#include "mel_basis.hpp"
 #include "fbank_kernels.hpp"
 
 using namespace vx;
@@ -36,33 +37,6 @@ struct vx_fbank {
 };
 
 namespace {
-
-// Slaney's mel scale (Auditory Toolbox): linear below 1 kHz at 200 / 3 Hz per mel, logarithmic above with step log(6.4) / 27.
-double hz_to_mel(double f) {
-  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, logstep = log(6.4) / 27.0;
-  return f >= min_log_hz ? min_log_hz / f_sp + log(f / min_log_hz) / logstep : f / f_sp;
-}
-double mel_to_hz(double m) {
-  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-  return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
-}
-
-// Triangular filters between n_mels + 2 points equally spaced in mel, each scaled by 2 / (its width in Hz): fp64, rounded once.
-std::vector<float> slaney_basis(int sr, int n_mels, double fmin, double fmax) {
-  std::vector<double> pts(n_mels + 2);
-  const double m0 = hz_to_mel(fmin), m1 = hz_to_mel(fmax);
-  for (int i = 0; i < n_mels + 2; ++i) pts[i] = mel_to_hz(m0 + (m1 - m0) * (double)i / (double)(n_mels + 1));
-  std::vector<float> w((size_t)n_mels * FBANK_BINS);
-  for (int i = 0; i < n_mels; ++i) {
-    const double norm = 2.0 / (pts[i + 2] - pts[i]);
-    for (int b = 0; b < FBANK_BINS; ++b) {
-      const double f = 0.5 * (double)sr * (double)b / (double)(FBANK_BINS - 1);
-      const double lower = (f - pts[i]) / (pts[i + 1] - pts[i]), upper = (pts[i + 2] - f) / (pts[i + 2] - pts[i + 1]);
-      w[(size_t)i * FBANK_BINS + b] = (float)(std::max(0.0, std::min(lower, upper)) * norm);
-    }
-  }
-  return w;
-}
 
 // First use: the tables go to the current device.
 int fbank_init_device(vx_fbank* fb) {
@@ -123,7 +97,7 @@ extern "C" int vx_fbank_create(const vx_fbank_config* cfg, vx_fbank** out) {
     return fail(VX_ERR_UNSUPPORTED, "vx_fbank_create: band %g .. %g Hz: 0 <= fmin < fmax <= 12000 is served", cfg->fmin, cfg->fmax);
   vx_fbank* fb = new vx_fbank();
   fb->n_mels = cfg->n_mels; fb->max_batch = cfg->max_batch; fb->clip = cfg->clip;
-  fb->basis = slaney_basis(cfg->sample_rate, cfg->n_mels, cfg->fmin, cfg->fmax);
+  fb->basis = slaney_basis(cfg->sample_rate, cfg->n_mels, FBANK_BINS, cfg->fmin, cfg->fmax);
   fb->tab.resize(FBANK_TAB);
   const double pi = 3.14159265358979323846;
   for (int j = 0; j < 1024; ++j) {

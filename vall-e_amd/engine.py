@@ -53,6 +53,11 @@ class VxFbankConfig(C.Structure):
                [(n, C.c_float) for n in ("fmin", "fmax", "clip")] + [("max_batch", C.c_int32)]
 
 
+class VxVocoderConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "sample_rate", "n_fft", "hop", "n_mels")] + \
+               [(n, C.c_float) for n in ("fmin", "fmax", "env_floor")] + [("max_batch", C.c_int32), ("max_total_frames", C.c_int32)]
+
+
 class VxDtwConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "dim", "n_ceps", "max_frames", "max_batch")]
 
@@ -198,6 +203,18 @@ _SIGS = {
                                 C.POINTER(C.c_int32)]),
     "vx_mel_teacher_forced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vx_mel_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    # Griffin-Lim vocoder (vocoder.GriffinLim)
+    "vx_vocoder_create": (C.c_int, [C.POINTER(VxVocoderConfig), C.POINTER(C.c_void_p)]),
+    "vx_vocoder_destroy": (None, [C.c_void_p]),
+    "vx_vocoder_set_mel_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vx_vocoder_set_inverse": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vx_vocoder_get_inverse": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vx_vocoder_samples": (C.c_int64, [C.c_int64]),
+    "vx_vocoder_synthesize": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                        C.c_int32, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
+    "vx_vocoder_synthesize_warm": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so

@@ -130,6 +130,18 @@ class Transformer:
         return (out, stops, reason) if return_stop_logits else out
 
     @torch.no_grad()
+    def inference_waveform(self, x: torch.Tensor, x_lens: torch.Tensor, vocoder=None, **griffinlim_kw):
+        """``inference``, then the Griffin-Lim vocoder (``vocoder.GriffinLim``; the device's shared default one when none is given) on
+        the same device and stream: ``(mel (1, T, 100), wav (256 T,))``.  ``griffinlim_kw``: n_iter, momentum, rand_init, seed.  A stop
+        on pass 0 gives no frame and an empty waveform."""
+        mel = self.inference(x, x_lens)
+        if vocoder is None:
+            from .vocoder import shared_griffinlim
+
+            vocoder = shared_griffinlim(self.device)
+        return mel, vocoder(mel[0], **griffinlim_kw)
+
+    @torch.no_grad()
     def teacher_forced(self, x: torch.Tensor, x_lens: torch.Tensor, mel: torch.Tensor):
         """The quantities inside the reference's ``forward`` (transformer.py:279-300) for one utterance: mel (1, T, 100) or (T, 100)
         -> ``(predict (T, 100), stop_logits (T,))`` from one causal pass over [0; mel[:-1]].  ``F.mse_loss(predict, mel)`` is the
