@@ -875,6 +875,85 @@ int vx_vocoder_synthesize_warm(vx_vocoder* v, int32_t n, const float* const* log
                                const float* const* init_ang, int32_t n_iter, float momentum, float* const* wav_out,
                                float* const* phase_out, void* stream);
 
+/* ---- Neural vocoder: a HiFi-GAN / BigVGAN generator, log-mel frames to a waveform ----------------------------------------------
+ * One generator family with two activation modes, a handle of its own, fp32 storage and accumulation.  Per utterance, logmel
+ * (T, n_mels) fp32; below x is (C, L).  S = n_stages, u_i = rates[i], k_i = kernels[i], C_0 = initial_channels, C_{i+1} = C_i / 2,
+ * R = n_resblocks with kernel sizes rk_r, D = n_dilations with dilations d_{r,m}; every convolution pads with zeros.
+ *   1. x = conv_pre(logmel^T): Conv1d(n_mels -> C_0, k = 7, padding 3).  With `mean` / `scale` set (SpeechT5HifiGan's
+ *      normalize_before) the input is (logmel - mean) / scale first.
+ *   2. for i in 0 .. S-1:  VX_GAN_LRELU only: x = lrelu(x, lrelu_slope).  Then the transposed convolution with p = (k_i - u_i) / 2:
+ *      out[co][n] = b[co] + sum over ci, t, j with n = t u_i - p + j, 0 <= j < k_i of x[ci][t] W[ci][co][j], n in [0, L u_i).
+ *      Then x = (1 / R) sum_r resblock_{i,r}(x), summed in ascending r and divided by R.
+ *   3. resblock_{i,r}(x): for m in 0 .. D-1 { xt = act(x); xt = conv(xt; k = rk_r, dilation d_{r,m}, padding d_{r,m} (rk_r - 1) / 2);
+ *      xt = act(xt); xt = conv(xt; k = rk_r, dilation 1); x = x + xt }.  VX_GAN_LRELU: act = lrelu(., lrelu_slope).  Otherwise every
+ *      act is the anti-aliased activation below with parameters of its own: activations.{2m} before the dilated convolution,
+ *      activations.{2m+1} before the second.
+ *   4. VX_GAN_LRELU: x = lrelu(x, 0.01) (torch's default slope, as SpeechT5HifiGan.forward and the original).  Otherwise the
+ *      anti-aliased activation `activation_post`.
+ *   5. y = tanh(conv_post(x)): Conv1d(C_S -> 1, k = 7, padding 3), the bias optional.  T * prod(u_i) samples.
+ * The anti-aliased activation (ratio 2, 12 taps), per channel on a signal x of length L:
+ *   filter f = kaiser_sinc(cutoff 0.25, half_width 0.3, K = 12): delta_f = 4 half_width, A = 2.285 (K/2 - 1) pi delta_f + 7.95,
+ *      beta = 0.1102 (A - 8.7) if A > 50, 0.5842 (A - 21)^0.4 + 0.07886 (A - 21) if A >= 21, else 0; w = the symmetric Kaiser
+ *      window of K points; time = -K/2 + 0.5 .. K/2 - 0.5; f = 2 cutoff w sinc(2 cutoff time), f /= sum f.  Computed in fp64 and
+ *      rounded once; vx_gan_set_filter replaces it.  The same taps serve up and down.
+ *   up:   xp = x replicate-padded by 5 on each side; full[m] = sum over i, j with m = 2 i + j of xp[i] f[j]; u = 2 full[15 : 15 + 2L].
+ *         Equivalently u[2m] = 2 sum_{s<6} f[2s+1] x[cl(m + 2 - s)], u[2m+1] = 2 sum_{s<6} f[2s] x[cl(m + 3 - s)], cl = clamp to [0, L).
+ *   act:  v = u + sin(a u)^2 / (b + 1e-9); snake: b = a = alpha, snakebeta: a = alpha, b = beta; with alpha_logscale a = exp(alpha),
+ *         b = exp(beta).  a and 1 / (b + 1e-9) are formed on the host in fp64 and rounded once.
+ *   down: y[t] = sum_{j<12} f[j] v[clamp(2t + j - 5, 0, 2L - 1)]: the replicate pad (5 left, 6 right) acts on the cropped 2L-long v.
+ * Weight keys (fp32, host, torch layouts, weight norm already folded): conv_pre.weight (C_0, n_mels, 7), conv_pre.bias;
+ * ups.{i}.weight (C_i, C_{i+1}, k_i), ups.{i}.bias; resblocks.{i R + r}.convs1.{m}.weight (C, C, rk_r) / .bias and convs2 alike;
+ * resblocks.{n}.activations.{a}.alpha (C) and, for snakebeta, .beta; activation_post.alpha / .beta (C_S); conv_post.weight
+ * (1, C_S, 7); optional: conv_post.bias (1), and mean with scale (n_mels). */
+typedef struct vx_gan vx_gan;
+enum { VX_GAN_LRELU = 0, VX_GAN_SNAKE = 1, VX_GAN_SNAKEBETA = 2 };
+typedef struct vx_gan_config {
+  int32_t struct_size;          /* sizeof(vx_gan_config) */
+  int32_t n_mels;
+  int32_t n_stages;             /* 1 .. 8 */
+  int32_t rates[8];
+  int32_t kernels[8];
+  int32_t initial_channels;     /* C_0, a multiple of 2^n_stages */
+  int32_t n_resblocks;          /* 1 .. 4 */
+  int32_t resblock_kernels[4];  /* odd */
+  int32_t n_dilations;          /* 1 .. 4 */
+  int32_t dilations[4][4];      /* [resblock][m] */
+  int32_t activation;           /* VX_GAN_* */
+  int32_t alpha_logscale;       /* 0 / 1 */
+  float lrelu_slope;
+  int32_t max_batch;            /* utterances per call, <= 64 */
+  int32_t max_total_frames;     /* frames per call, summed over its utterances; <= 2^21 */
+} vx_gan_config;
+/* Host only, no HIP call.  In this order: nulls, a wrong struct_size, max_batch < 1, max_total_frames < 1, n_mels < 1, n_stages /
+ * n_resblocks / n_dilations outside their ranges, a rate, kernel, resblock kernel or dilation < 1, initial_channels < 1, an
+ * activation outside VX_GAN_*, alpha_logscale outside 0 / 1, a lrelu_slope that is not finite -> VX_ERR_ARG; then k_i < u_i or
+ * k_i - u_i odd, an even resblock kernel, initial_channels no multiple of 2^n_stages, prod(u_i) > 4096, max_batch > 64,
+ * max_total_frames > 2^21 -> VX_ERR_UNSUPPORTED. */
+int vx_gan_create(const vx_gan_config* cfg, vx_gan** out);
+void vx_gan_destroy(vx_gan* g);
+/* Host only.  data: HOST fp32 of `shape`.  Unknown key or wrong shape -> VX_ERR_WEIGHTS; after vx_gan_finalize -> VX_ERR_STATE. */
+int vx_gan_set_weight(vx_gan* g, const char* key, const float* data, const int64_t* shape, int32_t ndim);
+/* Host only: the 12 taps (HOST fp32) replace the built-in filter of every anti-aliased activation.  Another count -> VX_ERR_UNSUPPORTED;
+ * after vx_gan_finalize -> VX_ERR_STATE. */
+int vx_gan_set_filter(vx_gan* g, const float* taps, int32_t n_taps);
+/* Host only: the 12 taps in use. */
+int vx_gan_get_filter(const vx_gan* g, float* taps);
+/* Host only: checks that every tensor is there (a missing one -> VX_ERR_WEIGHTS naming it; mean without scale too) and packs the
+ * weights for the kernels.  They go to the device that is current at the first synthesis. */
+int vx_gan_finalize(vx_gan* g);
+/* n_frames * prod(u_i); 0 for a negative n_frames or a null handle.  Host only. */
+int64_t vx_gan_samples(const vx_gan* g, int64_t n_frames);
+/* n utterances: logmel[i] DEVICE fp32 (n_frames[i], n_mels), wav_out[i] DEVICE fp32 of n_frames[i] prod(u_i) samples.  The pointer
+ * arrays and n_frames live on the host.  An utterance with n_frames[i] = 0 writes nothing and its pointers are not looked at.
+ * Every utterance is bitwise what it is alone, and two identical calls give the same bits.  Checked before any HIP call, in this
+ * order: null arguments, n < 1 -> VX_ERR_ARG; not finalized -> VX_ERR_STATE; n > max_batch -> VX_ERR_CAPACITY; then per utterance
+ * in order n_frames[i] < 0 or, with frames, a null entry -> VX_ERR_ARG, and a running sum of frames above max_total_frames ->
+ * VX_ERR_CAPACITY.  A call without any frame returns here.  The utterances are served in groups of whole utterances so that the
+ * five row buffers (the widest stage's rows each) are reused; the work is enqueued on `stream`, and the host waits only for the
+ * previous call's staging copy (and for the previous call when the workspace has to grow).  Calls on one handle must not overlap. */
+int vx_gan_synthesize(vx_gan* g, int32_t n, const float* const* logmel, const int32_t* n_frames, float* const* wav_out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ from .config import ModelConfig, add_model_arguments, NUM_AUDIO_TOKENS, NUM_TEXT
 __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_TOKENS", "AudioTokenizer", "CodecConfig", "EncodecDecoder",
            "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio",
            "BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis",
-           "DTW", "DTWResult", "mel_cepstral_distortion", "GriffinLim", "mel_to_waveform"]
+           "DTW", "DTWResult", "mel_cepstral_distortion", "GriffinLim", "mel_to_waveform",
+           "GanVocoder", "BigVGAN"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -25,4 +26,8 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import vocoder
 
         return getattr(vocoder, name)
+    if name in ("GanVocoder", "BigVGAN"):
+        from . import ganvoc
+
+        return getattr(ganvoc, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

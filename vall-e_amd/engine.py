@@ -58,6 +58,17 @@ class VxVocoderConfig(C.Structure):
                [(n, C.c_float) for n in ("fmin", "fmax", "env_floor")] + [("max_batch", C.c_int32), ("max_total_frames", C.c_int32)]
 
 
+class VxGanConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_mels", C.c_int32), ("n_stages", C.c_int32), ("rates", C.c_int32 * 8),
+                ("kernels", C.c_int32 * 8), ("initial_channels", C.c_int32), ("n_resblocks", C.c_int32),
+                ("resblock_kernels", C.c_int32 * 4), ("n_dilations", C.c_int32), ("dilations", (C.c_int32 * 4) * 4),
+                ("activation", C.c_int32), ("alpha_logscale", C.c_int32), ("lrelu_slope", C.c_float), ("max_batch", C.c_int32),
+                ("max_total_frames", C.c_int32)]
+
+
+VX_GAN_LRELU, VX_GAN_SNAKE, VX_GAN_SNAKEBETA = 0, 1, 2
+
+
 class VxDtwConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "dim", "n_ceps", "max_frames", "max_batch")]
 
@@ -215,6 +226,16 @@ _SIGS = {
     "vx_vocoder_synthesize_warm": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_void_p), C.c_void_p]),
+    # HiFi-GAN / BigVGAN generator (ganvoc.GanVocoder)
+    "vx_gan_create": (C.c_int, [C.POINTER(VxGanConfig), C.POINTER(C.c_void_p)]),
+    "vx_gan_destroy": (None, [C.c_void_p]),
+    "vx_gan_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "vx_gan_set_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "vx_gan_get_filter": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vx_gan_finalize": (C.c_int, [C.c_void_p]),
+    "vx_gan_samples": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "vx_gan_synthesize": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                    C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so
