@@ -354,14 +354,18 @@ int vx_get_timings(vx_engine* e, double* out, int32_t n);
  * slot, engines created with VX_FLAG_TRACE_LOGITS and max_batch > 1), "batch_kv" (the slot caches, max_batch > 1:
  * [slot][layer][K|V][head][max_text+max_audio][64] bf16, or e4m3 bytes with VX_FLAG_KV_FP8), "batch_kv_scale" (VX_FLAG_KV_FP8: the
  * E8M0 scale bytes, [slot][layer][K|V][head][max_text+max_audio][4]), "ar_kv" (the batch-1 KV cache,
- * [layer][K|V][head][max_text+max_audio][head_dim], fp32 on VX_PREC_F32 engines, else bf16), "score_ar_argmax" (int32 per AR row
+ * [layer][K|V][head][max_text+max_audio][head_dim], fp32 on VX_PREC_F32 engines, else bf16), "ar_mem" (VX_FLAG_VALLF engines only:
+ * the text memory the batch-1 cross-attention reads, K and V of every layer from the last prefill's text,
+ * [layer][K|V][head][max_text][head_dim] in ar_kv's element type; rows at and past that text's length keep what an earlier,
+ * longer text left there and are never read), "score_ar_argmax" (int32 per AR row
  * of the last vx_score / vx_score_batch, utterances concatenated: the argmax of the scored logits rows), "tp_wo" (engines that run
  * the XCD-sharded decode step only: layer 0's out-projection in the word order that step streams, d x d elements of the weight
  * type - the layout test of csrc/ar_tp.hpp tp_repack_kernel). */
 int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t offset_bytes, int64_t nbytes);
 
 /* Bytes vx_read_buffer's tap `name` holds on an engine created with *cfg, for the taps whose size follows from the
- * configuration alone ("ar_kv"); VX_ERR_ARG for any other name.  Host only: no HIP call. */
+ * configuration alone ("ar_kv"; "ar_mem" with VX_FLAG_VALLF in cfg->flags); VX_ERR_ARG for any other name.  Host only: no HIP
+ * call. */
 int vx_buffer_bytes(const vx_config* cfg, const char* name, int64_t* bytes);
 
 /* Kernel-level entry points (device pointers, fp32 unless noted) used by tests/ to check each

@@ -480,3 +480,45 @@ def test_ar_kv_tap_size_without_gpu(lib):
         c.struct_size, c.precision = C.sizeof(VxConfig), prec
         assert lib.vx_buffer_bytes(C.byref(c), b"ar_kv", C.byref(n)) == 0
         assert e.lib.call == (b"ar_kv", 0, n.value)
+
+
+def test_ar_mem_tap_size_without_gpu(lib):
+    """vx_read_buffer's "ar_mem" ([layer][K|V][head][max_text][head_dim], the cache's element type) is the VALL-F text memory:
+    vx_buffer_bytes gives the size its range check uses on a configuration with VX_FLAG_VALLF and refuses the name on any other,
+    and Engine.read_ar_mem asks for exactly that many bytes."""
+    import ctypes as C
+    from valle_amd.config import ModelConfig
+    from valle_amd.engine import VX_FLAG_VALLF, VX_PREC_BF16, VX_PREC_F32, Engine, VxConfig
+
+    c = VxConfig()
+    c.struct_size = C.sizeof(VxConfig)
+    c.d_model, c.nhead, c.num_layers, c.max_text, c.max_audio = 512, 8, 3, 40, 1000
+    n = C.c_int64()
+    for prec, esz in ((VX_PREC_F32, 4), (VX_PREC_BF16, 2)):
+        c.precision, c.flags = prec, VX_FLAG_VALLF
+        assert lib.vx_buffer_bytes(C.byref(c), b"ar_mem", C.byref(n)) == 0, lib.vx_last_error()
+        assert n.value == 3 * 2 * 8 * 40 * 64 * esz
+        assert lib.vx_buffer_bytes(C.byref(c), b"ar_kv", C.byref(n)) == 0  # the cache tap is unchanged by the flag
+        assert n.value == 3 * 2 * 8 * 1040 * 64 * esz
+        c.flags = 0  # a VALL-E configuration has no text memory
+        assert lib.vx_buffer_bytes(C.byref(c), b"ar_mem", C.byref(n)) == 1
+        assert b"ar_mem" in lib.vx_last_error()
+    c.flags = VX_FLAG_VALLF
+    for bad in (b"ar_mem_", b"ar_me", b"nar_mem"):
+        assert lib.vx_buffer_bytes(C.byref(c), bad, C.byref(n)) == 1
+        assert bad in lib.vx_last_error()
+
+    class Tap:  # records what the reader asks vx_read_buffer for
+        def vx_read_buffer(self, h, name, dst, off, nbytes):
+            self.call = (name, off, nbytes)
+            return 0
+
+    for precision, dtype, prec in (("fp32", torch.float32, VX_PREC_F32), ("bf16", torch.bfloat16, VX_PREC_BF16)):
+        e = Engine.__new__(Engine)
+        e.lib, e.h, e.precision, e.max_text, e.max_audio = Tap(), None, precision, 40, 1000
+        e.cfg = ModelConfig(model_name="VALL-F", decoder_dim=512, nhead=8, num_decoder_layers=3)
+        mem = e.read_ar_mem()
+        assert mem.shape == (3, 2, 8, 40, 64) and mem.dtype == dtype
+        c.precision = prec
+        assert lib.vx_buffer_bytes(C.byref(c), b"ar_mem", C.byref(n)) == 0
+        assert e.lib.call == (b"ar_mem", 0, n.value)

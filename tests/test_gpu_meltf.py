@@ -10,7 +10,8 @@ logit| of the sequence.
      logits leave (+-2 tol), later drift printed (and written where VX_MELTF_PARITY_OUT names a file);
   4. properties: repeat and graph / no-graph bitwise, texts of different lengths back to back, NaN-prefilled output, max_frames
      prefix, the first-pass stop, capacity;
-  5. d 1024 / 16 heads (the tuned width) on random weights against the restatement computed here;
+  5. d 1024 / 16 heads (the tuned width) on random weights against the restatement computed here; d 256 / 4 heads with 70 text
+     ids the same way (encoder stack and both cross-attention kernels past one 64-key tile);
   6. the output goes into mel_distance and the mel-cepstral DTW against a BigVGANFbank result of another length."""
 import json
 import os
@@ -211,6 +212,38 @@ def test_tuned_width(prec):
         assert reason == "max_frames" and frames.shape == (8, 100)
         check_rows(frames, rp, prec, f"d1024 {prec} cached step predict")
         check_stops(st, rs, prec, f"d1024 {prec} cached step stop")
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("prec", ("fp32", "bf16"))
+def test_text_past_one_key_tile(prec):
+    """d 256, 4 heads of 64, one layer, 70 ids (max_text 80), 8 teacher-forced frames: the encoder stack, the row pass's
+    cross-attention (a second, ragged 64-key tile) and the step's (9 keys per split, the last split short) past 64 text keys."""
+    from valle_amd.config import MelConfig
+    from valle_amd.engine import MelEngine
+    from valle_amd.weights import mel_synthetic_state_dict, sine_table
+
+    if "long" not in _TUNED:
+        cfg = MelConfig(256, 4, 1, True, False)
+        sd = mel_synthetic_state_dict(cfg, 13)
+        g = torch.Generator().manual_seed(7)
+        x = torch.randint(3, 100, (70,), generator=g)
+        fed = torch.randn(8, 100, generator=g)
+        ref = MelRef(sd, 256, 4, 1, dtype=torch.float64, pe=sine_table(96, 256)).teacher_forced(x, fed)
+        _TUNED["long"] = (cfg, sd, x, fed, ref)
+    cfg, sd, x, fed, (rp, rs) = _TUNED["long"]
+    e = MelEngine(cfg, precision=prec, max_text=80, max_frames=16)
+    try:
+        e.load_state_dict(sd)
+        predict, stops = e.teacher_forced(x, fed)
+        check_rows(predict, rp, prec, f"70 ids {prec} row pass predict")
+        check_stops(stops, rs, prec, f"70 ids {prec} row pass stop")
+        e.decode_forced(fed)
+        frames, reason, st = e.result()
+        assert reason == "max_frames" and frames.shape == (8, 100)
+        check_rows(frames, rp, prec, f"70 ids {prec} cached step predict")
+        check_stops(st, rs, prec, f"70 ids {prec} cached step stop")
     finally:
         e.close()
 

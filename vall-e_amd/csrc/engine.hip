@@ -2981,6 +2981,7 @@ extern "C" int vx_get_timings(vx_engine* e, double* out, int32_t n) {
 static int64_t config_buffer_bytes(const vx_config& c, const std::string& n) {
   const int64_t esz = c.precision == VX_PREC_F32 ? 4 : 2;
   if (n == "ar_kv") return (int64_t)c.num_layers * 2 * c.d_model * ((int64_t)c.max_text + c.max_audio) * esz;
+  if (n == "ar_mem" && (c.flags & VX_FLAG_VALLF)) return (int64_t)c.num_layers * 2 * c.d_model * (int64_t)c.max_text * esz;
   return -1;
 }
 
@@ -3019,6 +3020,7 @@ extern "C" int vx_read_buffer(vx_engine* e, const char* name, void* dst, int64_t
     size = (int64_t)e->bmax * e->bkv_slot * (e->kv8 ? 1 : 2);
   }
   else if (n == "ar_kv") { src = (const char*)e->kv; size = config_buffer_bytes(e->cfg, n); }
+  else if (n == "ar_mem" && e->vallf) { src = (const char*)e->xkv_ar; size = config_buffer_bytes(e->cfg, n); }
   else if (n == "tp_wo" && e->tp) { src = (const char*)e->tp_wo[0]; size = (int64_t)TP_D * TP_D * e->esz; }
   else if (n == "score_ar_argmax" && e->sc_argmax) { src = (const char*)e->sc_argmax; size = (int64_t)e->sc_rows * 4; }
   else if (n == "batch_kv_scale" && e->kv8) { src = (const char*)e->bkv8s; size = (int64_t)e->bmax * e->bkv_slot / 16; }

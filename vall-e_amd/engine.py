@@ -706,6 +706,15 @@ class Engine:
         dtype = torch.float32 if self.precision in ("fp32", "f32") else torch.bfloat16
         return self.read("ar_kv", (L, 2, H, self.max_text + self.max_audio, hd), dtype)
 
+    def read_ar_mem(self) -> torch.Tensor:
+        """VALL-F engines: the text memory of the batch-1 cross-attention as (L, 2, H, max_text, head_dim), K and V of every
+        layer in the cache's element type.  Rows at and past the last prefilled text's length hold whatever an earlier, longer
+        text left there."""
+        L, H = self.cfg.num_decoder_layers, self.cfg.nhead
+        hd = self.cfg.decoder_dim // H
+        dtype = torch.float32 if self.precision in ("fp32", "f32") else torch.bfloat16
+        return self.read("ar_mem", (L, 2, H, self.max_text, hd), dtype)
+
 
 # ---- kernel-level ops (parity tests call the HIP kernels through the same C ABI) -------------------
 def _struct_top_p(top_p) -> float:
