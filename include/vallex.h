@@ -728,6 +728,74 @@ int vx_dtw_compare(vx_dtw* h, int32_t n, const float* const* a, const int32_t* T
 int vx_op_dtw_cost(int32_t dim, int32_t n_ceps, const float* a, int32_t Ta, const float* b, int32_t Tb, float* cost, void* stream);
 int vx_op_dtw_path(const float* cost, int32_t n, const int64_t* desc, double* total, int32_t* path_len, int32_t* path, void* stream);
 
+/* ---- fundamental frequency (YIN, de Cheveigne & Kawahara 2002) and the F0 figures along a warp path --------------------------
+ * A handle of its own: no weights, no vx_engine.  The framing is the filterbank's, so row t of a track is row t of the log-mel.
+ * Per utterance, a mono fp32 waveform x of L samples at 24 kHz, zeros appended past L:
+ *   frames T = (L + 128) / 256 (none below 128 samples); tau_min = floor(24000 / fmax_hz), tau_max = ceil(24000 / fmin_hz), in
+ *   fp64 on the fp32 fields; 12 <= tau_min < tau_max <= 512 is served.
+ *   1. Half-window differences, for u = 0 .. T and tau = 0 .. tau_max:
+ *        h_u(tau) = sum_{j = 0 .. 255} (x[256 u + j] - x[256 u + j + tau])^2
+ *      on differences in fp32 (never energy minus correlation: at the period the two cancel, and that is where the decision is
+ *      taken).  A product is fused into its sum; (u, tau) has 8 chains, chain q over j = q, q + 8, ... ascending, folded as
+ *      ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).  d_t(tau) = h_t(tau) + h_{t+1}(tau), fp32: an integration window of 512 and a
+ *      reach of 1024 samples, the filterbank frame's.
+ *   2. Cumulative mean normalised difference: d'_t(0) = 1, d'_t(tau) = d_t(tau) tau / sum_{k = 1 .. tau} d_t(k), the running sum
+ *      and the quotient in fp64, rounded once to fp32; 1 where the sum is 0 (a silent frame).
+ *   3. Lag: the first tau in [tau_min, tau_max] with d'(tau) < threshold, then while tau < tau_max and d'(tau + 1) < d'(tau):
+ *      tau += 1; such a frame is voiced.  Without a tau under the threshold the frame is unvoiced and tau* is the first global
+ *      minimum of d' on the range.
+ *   4. Refinement, in fp64 on the fp32 d': if tau* < tau_max, with a, b, c = d'(tau* - 1), d'(tau*), d'(tau* + 1) and den = a -
+ *      2 b + c > 0 the offset is (a - c) / (2 den) clamped to +-0.5, else 0.  f0 = 24000 / (tau* + offset), rounded once, on
+ *      voiced frames; 0 on unvoiced ones.
+ *   5. Per frame: f0 (fp32, Hz), aperiodicity = d'(tau*) (fp32), lag = tau* (int32), voiced (uint8, 0 / 1).
+ * A frame's bits depend on its own 1024 samples only: never on the batch, on the frame's place in the launch or on the run.
+ * Non-finite samples give unspecified values; the call still ends and writes nothing outside its outputs.  There is no
+ * workspace: the differences never leave the chip; a handle holds its staging block and max_batch rows of sums. */
+typedef struct vx_pitch vx_pitch;
+typedef struct vx_pitch_config {
+  int32_t struct_size;  /* sizeof(vx_pitch_config) */
+  int32_t sample_rate;  /* 24000 */
+  float fmin_hz;        /* lowest f0 searched: tau_max = ceil(24000 / fmin_hz) <= 512 (46.875 Hz and up) */
+  float fmax_hz;        /* highest: tau_min = floor(24000 / fmax_hz) >= 12 (up to 2000 Hz) */
+  float threshold;      /* on d', positive and finite; YIN's 0.1 */
+  int32_t max_frames;   /* capacity: frames per utterance, >= 1 */
+  int32_t max_batch;    /* capacity: utterances (or pairs) per call, 1 .. 64 */
+} vx_pitch_config;
+/* Host only, no HIP call.  Nulls, a wrong struct_size, max_batch < 1, max_frames < 1 or a threshold that is not positive and
+ * finite -> VX_ERR_ARG; then another sample rate, a band outside the served lags or max_batch > 64 -> VX_ERR_UNSUPPORTED. */
+int vx_pitch_create(const vx_pitch_config* cfg, vx_pitch** out);
+void vx_pitch_destroy(vx_pitch* h);
+/* The handle's tau_min and tau_max.  Host only. */
+int vx_pitch_lag_range(const vx_pitch* h, int32_t* tau_min, int32_t* tau_max);
+/* n utterances in one ragged launch: wav[i] DEVICE fp32 of n_samples[i] samples; f0[i], aperiodicity[i] DEVICE fp32, lag[i]
+ * DEVICE int32, voiced[i] DEVICE uint8, each of vx_fbank_frames(n_samples[i]) elements.  The pointer arrays and the lengths live
+ * on the host; each of the four output arrays may be null, and so may each of its entries.  An utterance without frames (fewer
+ * than 128 samples) writes nothing.  Checked before any HIP call, in this order: null h, wav or n_samples, or n < 1 ->
+ * VX_ERR_ARG; n > max_batch -> VX_ERR_CAPACITY; then per utterance in order: a null wav[i] or n_samples[i] < 0 -> VX_ERR_ARG,
+ * more frames than max_frames -> VX_ERR_CAPACITY (the message names the utterance).  The work is enqueued on `stream`; the host
+ * waits only for the previous call's staging copy.  Calls on one handle must not overlap. */
+int vx_pitch_track(vx_pitch* h, int32_t n, const float* const* wav, const int32_t* n_samples, float* const* f0,
+                   float* const* aperiodicity, int32_t* const* lag, uint8_t* const* voiced, void* stream);
+/* The F0 figures of n pairs of tracks along caller-supplied paths (those of vx_dtw_compare on the same framing): f0_a[i] (Ta[i])
+ * and f0_b[i] (Tb[i]) DEVICE fp32 in Hz, 0 = unvoiced; path[i] DEVICE int32 (path_len[i], 2) cells (i, j), as vx_dtw_compare
+ * leaves them.  The path is served on the device only: the host never reads it, so a cell outside [0, Ta) x [0, Tb) cannot be
+ * refused and is clamped into the range instead.  sums: n rows of 11 doubles, host or device memory:
+ *   [0] n_path  [1] n_voiced_both  [2] n_vuv_mismatch (voiced in exactly one of the two)
+ *   and over the cells voiced in both, with c = 1200 log2(fa / fb), la = ln fa, lb = ln fb:
+ *   [3] sum c  [4] sum c^2  [5] sum (fa - fb)^2  [6] sum la  [7] sum lb  [8] sum la^2  [9] sum lb^2  [10] sum la lb
+ * all in fp64: thread t of 256 adds the cells t, t + 256, ... in ascending order, then a fixed binary tree; the same bits on
+ * every run and in any batch.  (The Python layer derives rmse_cents = sqrt([4] / [1]), rmse_hz = sqrt([5] / [1]), Pearson's r of
+ * la and lb, and vuv_error = [2] / [0].)  Checked before any HIP call: null arguments or n < 1 -> VX_ERR_ARG; n > max_batch ->
+ * VX_ERR_CAPACITY; then per pair in order: a null pointer, Ta[i], Tb[i] or path_len[i] < 1 -> VX_ERR_ARG, Ta[i] or Tb[i] >
+ * max_frames, or path_len[i] > Ta[i] + Tb[i] - 1 (the longest a warp path gets) -> VX_ERR_CAPACITY (the message names the
+ * pair).  Enqueued on `stream`, as vx_pitch_track. */
+int vx_pitch_compare(vx_pitch* h, int32_t n, const float* const* f0_a, const int32_t* Ta, const float* const* f0_b, const int32_t* Tb,
+                     const int32_t* const* path, const int32_t* path_len, double* sums, void* stream);
+/* Test-only, like the vx_op_* entries above: d' of one utterance, dprime DEVICE fp32 (frames, tau_max + 1) for the band's
+ * tau_max; wav DEVICE.  Null pointers, n_samples < 0 or a band vx_pitch_create refuses -> VX_ERR_ARG before any HIP call.
+ * Synchronises the stream. */
+int vx_op_pitch_diff(float fmin_hz, float fmax_hz, const float* wav, int32_t n_samples, float* dprime, void* stream);
+
 /* ---- the mel-spectrogram Transformer TTS model (valle/models/transformer.py, --model-name Transformer) ------------------------
  * The reference's third model: a text encoder, a decoder over log-mel frames with cross-attention to the encoded text, a 100-wide
  * regression head and a stop head.  There is no vocabulary and no sampler: the predicted frame itself is fed back through

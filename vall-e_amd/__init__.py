@@ -6,7 +6,7 @@ __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_T
            "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio",
            "BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis",
            "DTW", "DTWResult", "mel_cepstral_distortion", "GriffinLim", "mel_to_waveform",
-           "GanVocoder", "BigVGAN"]
+           "GanVocoder", "BigVGAN", "PitchTracker", "PitchTrack", "F0Result", "f0_distance"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -30,4 +30,8 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import ganvoc
 
         return getattr(ganvoc, name)
+    if name in ("PitchTracker", "PitchTrack", "F0Result", "f0_distance"):
+        from . import pitch
+
+        return getattr(pitch, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

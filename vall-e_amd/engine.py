@@ -73,6 +73,14 @@ class VxDtwConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "dim", "n_ceps", "max_frames", "max_batch")]
 
 
+class VxPitchConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("sample_rate", C.c_int32), ("fmin_hz", C.c_float), ("fmax_hz", C.c_float),
+                ("threshold", C.c_float), ("max_frames", C.c_int32), ("max_batch", C.c_int32)]
+
+
+PITCH_NSUMS = 11  # doubles per pair of vx_pitch_compare (csrc/pitch_kernels.hpp)
+
+
 class VxMelConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "d_model", "nhead", "num_layers", "norm_first", "add_prenet", "scaling_xformers",
                                          "precision", "max_text", "max_frames", "device", "flags")]
@@ -201,6 +209,15 @@ _SIGS = {
                                  C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "vx_op_dtw_cost": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "vx_op_dtw_path": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # pitch tracking and F0 figures (pitch.PitchTracker)
+    "vx_pitch_create": (C.c_int, [C.POINTER(VxPitchConfig), C.POINTER(C.c_void_p)]),
+    "vx_pitch_destroy": (None, [C.c_void_p]),
+    "vx_pitch_lag_range": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vx_pitch_track": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)] + [C.POINTER(C.c_void_p)] * 4
+                       + [C.c_void_p]),
+    "vx_pitch_compare": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "vx_op_pitch_diff": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     # mel-spectrogram Transformer (meltf.Transformer)
     "vx_mel_create": (C.c_int, [C.POINTER(VxMelConfig), C.POINTER(C.c_void_p)]),
     "vx_mel_destroy": (None, [C.c_void_p]),
@@ -1077,6 +1094,17 @@ def op_dtw_path(cost, mats, want_path=True):
     lens = length.tolist()
     parts = torch.split(path, [int(m[0]) + int(m[1]) - 1 for m in mats])
     return total, length, [p[:n] for p, n in zip(parts, lens)]
+
+
+def op_pitch_diff(wav, fmin, fmax, tau_max):
+    """d' of pitch_track_kernel for one utterance (vx_op_pitch_diff): wav (L,) float32 on the device -> (frames, tau_max + 1)
+    float32, ``tau_max`` = ceil(24000 / fmin)."""
+    lib = load_library()
+    assert wav.dtype == torch.float32 and wav.dim() == 1 and wav.is_contiguous() and wav.is_cuda
+    out = torch.empty((int(lib.vx_fbank_frames(wav.numel())), int(tau_max) + 1), dtype=torch.float32, device=wav.device)
+    if out.numel():  # an utterance without frames has no storage to point at, and nothing to write
+        _check(lib.vx_op_pitch_diff(float(fmin), float(fmax), _ptr(wav), wav.numel(), _ptr(out), current_stream_ptr(wav.device)))
+    return out
 
 
 def op_sample(logits, top_k, temperature, exp_noise):
