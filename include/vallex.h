@@ -796,6 +796,61 @@ int vx_pitch_compare(vx_pitch* h, int32_t n, const float* const* f0_a, const int
  * Synchronises the stream. */
 int vx_op_pitch_diff(float fmin_hz, float fmax_hz, const float* wav, int32_t n_samples, float* dprime, void* stream);
 
+/* ---- multi-resolution STFT distance between two waveforms (Parallel WaveGAN, Yamamoto et al. 2020; BigVGAN's M-STFT column) ----
+ * A handle of its own: no weights, no vx_engine.  Two mono fp32 waveforms at 24 kHz, pred (X) and target (Y), both cut to the
+ * common length L = min(n_pred, n_target).  For every resolution r = (n_fft, hop, win) of the handle:
+ *   frames     as torch.stft(center=True, pad_mode="reflect") makes them: T = 1 + L / hop frames, frame t centred on sample t hop;
+ *              sample p < 0 is sample -p and sample p >= L is sample 2 (L - 1) - p (the edge sample is not repeated), which needs
+ *              L > n_fft / 2.
+ *   window     periodic Hann of `win` samples, w[j] = 0.5 - 0.5 cos(2 pi j / win), at offset (n_fft - win) / 2 (integer division)
+ *              inside the n_fft frame, zero elsewhere; built in fp64 and rounded once, the product x w is fp32.
+ *   magnitude  bins k = 0 .. n_fft / 2: |S|[t][k] = sqrt(max(re^2 + im^2, eps)), an fp32 number (eps = 1e-8: a floor of 1e-4).  The
+ *              DFT is direct, on the fp32 matrix instruction: sample pair s = (2 s, 2 s + 1) goes to fmaf chain s mod 4, and
+ *              after 8 pairs of every chain (64 samples) the four chains are added, chain 0 first, to an fp64 total and start
+ *              again from zero; re^2 + im^2, the clamp and the root are fp64 on the totals, rounded once.
+ *   sums       in fp64 on the fp32 magnitudes, over the T (n_fft / 2 + 1) cells:
+ *                [0] sum (|Y| - |X|)^2   [1] sum |Y|^2   [2] sum |ln |Y| - ln |X||   [3] cells
+ *              every thread adds its cells in a fixed order, a fixed tree adds the threads of a workgroup (16 frames x 256
+ *              bins), and the workgroups of a (pair, resolution) are added in ascending order.  No atomics: the same bits on every run and in any batch.
+ * (The Python layer derives sc_r = sqrt([0] / [1]), lm_r = [2] / [3] and total = mean over r of sc_r + lm_r.  sc is not symmetric
+ * in (pred, target); lm is.  The clamp keeps [1] >= cells eps, so sc never divides by zero.)
+ * Served: n_fft in {512, 1024, 2048}, 1 <= win <= n_fft, 1 <= hop <= n_fft, 1 .. 4 resolutions, L > max n_fft / 2 (1025 samples
+ * for the default triple (1024, 120, 600), (2048, 240, 1200), (512, 50, 240)).  A shorter pair is an argument error: never a
+ * silently dropped resolution.  Non-finite samples give unspecified values; the call still ends and writes nothing outside its
+ * outputs.  The spectrograms never go to memory; a handle holds its tables, its staging block and three doubles per workgroup. */
+typedef struct vx_stft vx_stft;
+typedef struct vx_stft_config {
+  int32_t struct_size;  /* sizeof(vx_stft_config) */
+  int32_t sample_rate;  /* 24000 */
+  int32_t n_res;        /* 1 .. 4 resolutions */
+  int32_t n_fft[4];     /* each 512, 1024 or 2048 */
+  int32_t hop[4];       /* 1 .. n_fft */
+  int32_t win[4];       /* 1 .. n_fft */
+  float eps;            /* clamp on the power, positive and finite; 1e-8 */
+  int32_t max_samples;  /* capacity: samples per signal, > max n_fft / 2 */
+  int32_t max_batch;    /* capacity: pairs (or signals) per call, 1 .. 64 */
+} vx_stft_config;
+/* Host only, no HIP call.  Nulls, a wrong struct_size, max_batch < 1, max_samples < 1 or an eps that is not positive and finite
+ * -> VX_ERR_ARG; then another sample rate, n_res outside 1 .. 4, a resolution outside the served range, max_batch > 64,
+ * max_samples <= max n_fft / 2 or a workspace above 2^24 tiles -> VX_ERR_UNSUPPORTED. */
+int vx_stft_create(const vx_stft_config* cfg, vx_stft** out);
+void vx_stft_destroy(vx_stft* h);
+/* 1 + n_samples / hop of resolution `res`; 0 for a null handle, a resolution the handle does not have or n_samples < 0.  Host only. */
+int vx_stft_frames(const vx_stft* h, int32_t res, int32_t n_samples);
+/* n pairs in one ragged call: pred[i] (n_pred[i] samples) and target[i] (n_target[i]) DEVICE fp32; the pointer arrays and the
+ * lengths live on the host.  sums: n x n_res x 4 doubles as above, host or device memory.  Samples past the common length are
+ * not read.  Checked before any HIP call, in this order: null arguments or n < 1 -> VX_ERR_ARG; n > max_batch ->
+ * VX_ERR_CAPACITY; then per pair in order: a null pointer or a common length <= max n_fft / 2 -> VX_ERR_ARG, a common length >
+ * max_samples -> VX_ERR_CAPACITY (the message names the pair).  One launch per resolution and one for the sums, enqueued on
+ * `stream`; the host waits only for the previous call's staging copy.  Calls on one handle must not overlap. */
+int vx_stft_compare(vx_stft* h, int32_t n, const float* const* pred, const int32_t* n_pred, const float* const* target,
+                    const int32_t* n_target, double* sums, void* stream);
+/* The magnitudes of resolution `res` themselves, by the same kernel body with the store in place of the reduction: wav[i] DEVICE
+ * fp32 of n_samples[i] samples, out[i] DEVICE fp32 (vx_stft_frames(h, res, n_samples[i]), n_fft / 2 + 1).  Checks as above, with
+ * `res` outside the handle -> VX_ERR_ARG and n_samples[i] > n_fft / 2 of THIS resolution required.  One launch on `stream`. */
+int vx_stft_magnitude(vx_stft* h, int32_t res, int32_t n, const float* const* wav, const int32_t* n_samples, float* const* out,
+                      void* stream);
+
 /* ---- the mel-spectrogram Transformer TTS model (valle/models/transformer.py, --model-name Transformer) ------------------------
  * The reference's third model: a text encoder, a decoder over log-mel frames with cross-attention to the encoded text, a 100-wide
  * regression head and a stop head.  There is no vocabulary and no sampler: the predicted frame itself is fed back through

@@ -6,7 +6,8 @@ __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_T
            "Resampler", "convert_audio", "load_wav", "save_wav", "tokenize_audio",
            "BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis",
            "DTW", "DTWResult", "mel_cepstral_distortion", "GriffinLim", "mel_to_waveform",
-           "GanVocoder", "BigVGAN", "PitchTracker", "PitchTrack", "F0Result", "f0_distance"]
+           "GanVocoder", "BigVGAN", "PitchTracker", "PitchTrack", "F0Result", "f0_distance",
+           "STFTConfig", "MultiResolutionSTFT", "MSTFTResult", "mstft_distance", "copy_synthesis_distance"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -34,4 +35,8 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import pitch
 
         return getattr(pitch, name)
+    if name in ("STFTConfig", "MultiResolutionSTFT", "MSTFTResult", "mstft_distance", "copy_synthesis_distance"):
+        from . import stft
+
+        return getattr(stft, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

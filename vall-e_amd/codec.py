@@ -493,6 +493,20 @@ class EncodecDecoder:
         a, b = self.fbank().extract_batch([wav, rec])
         return mel_distance(a, b)
 
+    @torch.no_grad()
+    def roundtrip_mstft(self, wav: torch.Tensor, n_q: Optional[int] = None, sr: Optional[int] = None):
+        """The multi-resolution STFT distance (`stft.MSTFTResult`: sc, log_mag per resolution, total) of decode(encode(waveform))
+        against the waveform, over their common length: what `roundtrip_mel_distance` averages away at its one framing (pre-echo at
+        the 240-sample window, smearing at the 1200-sample one).  `wav` and `sr` as in `encode`; the comparison is at 24 kHz,
+        against the mixed-down and resampled input, which must keep 1025 samples.  On synthetic weights the number means nothing.
+        Needs `encoder=True`."""
+        from .stft import shared_mstft
+
+        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
+            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        rec = self.decode(self.encode(wav, n_q))
+        return shared_mstft(rec.device).compare(rec.reshape(-1), wav.reshape(-1))
+
 
 class AudioTokenizer:
     """The reference's `valle.data.tokenizer.AudioTokenizer` (tokenizer.py:238-254) on the GPU: `encode(wav)` with wav (B, 1, L)

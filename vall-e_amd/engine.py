@@ -81,6 +81,14 @@ class VxPitchConfig(C.Structure):
 PITCH_NSUMS = 11  # doubles per pair of vx_pitch_compare (csrc/pitch_kernels.hpp)
 
 
+class VxStftConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("sample_rate", C.c_int32), ("n_res", C.c_int32), ("n_fft", C.c_int32 * 4),
+                ("hop", C.c_int32 * 4), ("win", C.c_int32 * 4), ("eps", C.c_float), ("max_samples", C.c_int32), ("max_batch", C.c_int32)]
+
+
+STFT_NSUMS = 4  # doubles per (pair, resolution) of vx_stft_compare (include/vallex.h lists them)
+
+
 class VxMelConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "d_model", "nhead", "num_layers", "norm_first", "add_prenet", "scaling_xformers",
                                          "precision", "max_text", "max_frames", "device", "flags")]
@@ -218,6 +226,14 @@ _SIGS = {
     "vx_pitch_compare": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "vx_op_pitch_diff": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    # multi-resolution STFT distance (stft.MultiResolutionSTFT)
+    "vx_stft_create": (C.c_int, [C.POINTER(VxStftConfig), C.POINTER(C.c_void_p)]),
+    "vx_stft_destroy": (None, [C.c_void_p]),
+    "vx_stft_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "vx_stft_compare": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "vx_stft_magnitude": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                    C.c_void_p]),
     # mel-spectrogram Transformer (meltf.Transformer)
     "vx_mel_create": (C.c_int, [C.POINTER(VxMelConfig), C.POINTER(C.c_void_p)]),
     "vx_mel_destroy": (None, [C.c_void_p]),

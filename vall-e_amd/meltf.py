@@ -133,7 +133,8 @@ class Transformer:
     def inference_waveform(self, x: torch.Tensor, x_lens: torch.Tensor, vocoder=None, **griffinlim_kw):
         """``inference``, then the Griffin-Lim vocoder (``vocoder.GriffinLim``; the device's shared default one when none is given) on
         the same device and stream: ``(mel (1, T, 100), wav (256 T,))``.  ``griffinlim_kw``: n_iter, momentum, rand_init, seed.  A stop
-        on pass 0 gives no frame and an empty waveform."""
+        on pass 0 gives no frame and an empty waveform.  How much of a waveform the vocoder itself keeps is a separate question:
+        ``stft.copy_synthesis_distance(wav, vocoder)`` scores wav -> log-mel -> vocoder against wav (multi-resolution STFT)."""
         mel = self.inference(x, x_lens)
         if vocoder is None:
             from .vocoder import shared_griffinlim
