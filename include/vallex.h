@@ -1081,6 +1081,110 @@ int64_t vx_gan_samples(const vx_gan* g, int64_t n_frames);
 int vx_gan_synthesize(vx_gan* g, int32_t n, const float* const* logmel, const int32_t* n_frames, float* const* wav_out,
                       void* stream);
 
+/* ---- Speaker encoder: the WavLM / Wav2Vec2 x-vector network, a 16 kHz waveform to a speaker embedding ---------------------------
+ * One family with two attention modes, a handle of its own, fp32 storage and accumulation (fp64 wherever a whole utterance is
+ * reduced).  VX_SPK_WAVLM is the network of transformers' WavLMForXVector (gated, bucketed relative position bias), VX_SPK_PLAIN the
+ * same network without the bias (Wav2Vec2ForXVector).  Per utterance, x = mono fp32 of L samples; d = hidden, H = heads,
+ * hd = d / H, C_i = conv_dim[i], k_i / s_i = conv_kernel / conv_stride; no convolution of the feature encoder pads:
+ * L' = (L - k) / s + 1 (integer division).  GELU is the exact one, 0.5 v (1 + erf(v / sqrt 2)).
+ *   0. VX_SPK_NORMALIZE (a flag of the call): x = (x - mean) / sqrt(var + 1e-7), the biased variance of the utterance, the sums
+ *      in fp64 in a fixed order.
+ *   1. feature encoder: layer 0 = Conv1d(1 -> C_0, k_0, s_0), then GroupNorm with one group per channel (mean and biased
+ *      variance over the utterance's own frames, fp64 sums, eps 1e-5, affine), then GELU; layers 1 .. n_conv - 1 = Conv1d(C_{i-1}
+ *      -> C_i, k_i, s_i), GELU.  The result, (T, C) time-major, is the tap "features".
+ *   2. projection: LayerNorm(C) (eps = layer_norm_eps, as every LayerNorm below), Linear C -> d.
+ *   3. positional convolution: Conv1d(d -> d, k = pos_kernel, padding k / 2, groups = pos_groups), the last output frame dropped
+ *      when k is even, GELU; h = LayerNorm(h + that).  This is hidden state 0 (tap "hidden0").
+ *   4. layers l = 0 .. L-1, post-norm:  h = LN(h + Attn(h)); h = LN(h + W2 gelu(W1 h + b1) + b2) (tap "hidden<l+1>").
+ *      Attn: q, k, v = Linear(h) split in H heads; scores[i][j] = (q_i . k_j) / sqrt(hd) + gate[h][i] bias[h][j - i]; softmax over
+ *      j; out_proj of the weighted v.  VX_SPK_WAVLM: bias[h][r] = rel_attn_embed[bucket(r)][h] with layer 0's embedding in every
+ *      layer, bucket(r) as given to vx_spk_set_buckets; the gate comes from the layer INPUT's head slice x_h (hd values), per layer:
+ *      p = W_g x_h + b_g (8 values), a = sigmoid(p0 + p1 + p2 + p3), b = sigmoid(p4 + .. + p7), gate = a (b const_h - 1) + 2
+ *      (tap "gate<l>", (T, H)).  VX_SPK_PLAIN: no bias term.
+ *   5. head: with use_weighted_layer_sum, h = sum_l softmax(layer_weights)[l] hidden_l over the L + 1 hidden states in ascending l
+ *      (tap "layer_sum"; without it the tap is the last hidden state); projector Linear d -> tdnn_dim[0]; TDNN layer i: frames
+ *      t .. of the dilated window, y[t] = relu(W [x[t]; x[t + dil]; ..; x[t + (k-1) dil]] + b) with W (tdnn_dim[i], k * in) in (tap,
+ *      channel) order, no padding (tap "tdnn" after the last); statistics pooling: mean and UNBIASED standard deviation over the
+ *      remaining T' frames in fp64, concatenated (tap "pooled"); embedding = feature_extractor (2 tdnn_dim[-1] -> xvector);
+ *      logits = classifier (xvector -> xvector) of the embedding.
+ * Similarity of two embeddings: a . b / max(|a| |b|, 1e-8), fp64 sums.
+ * Weight keys (fp32, host, torch layouts, transformers' names without the wavlm. / wav2vec2. prefix, weight norm folded):
+ * feature_extractor.conv_layers.{i}.conv.weight (C_i, C_{i-1}, k_i) [+ .conv.bias with conv_bias],
+ * feature_extractor.conv_layers.0.layer_norm.weight / .bias, feature_projection.layer_norm.*, feature_projection.projection.*,
+ * encoder.pos_conv_embed.conv.weight (d, d / groups, k) / .bias, encoder.layer_norm.*, encoder.layers.{l}.attention.{q,k,v,out}_proj.*,
+ * encoder.layers.{l}.layer_norm.*, .feed_forward.intermediate_dense.*, .feed_forward.output_dense.*, .final_layer_norm.*; VX_SPK_WAVLM:
+ * encoder.layers.{l}.attention.gru_rel_pos_linear.weight (8, hd) / .bias, .gru_rel_pos_const (1, H, 1, 1) and
+ * encoder.layers.0.attention.rel_attn_embed.weight (num_buckets, H); layer_weights (L + 1) with use_weighted_layer_sum;
+ * projector.*, tdnn.{i}.kernel.weight (tdnn_dim[i], k_i in_i) / .bias, feature_extractor.weight (xvector, 2 tdnn_dim[-1]) / .bias,
+ * classifier.weight (xvector, xvector) / .bias. */
+typedef struct vx_spk vx_spk;
+enum { VX_SPK_WAVLM = 0, VX_SPK_PLAIN = 1 };
+enum { VX_SPK_KEEP_TAPS = 1 };  /* vx_spk_config.flags: every hidden state keeps a buffer of its own ("hidden<l>" can be read) */
+enum { VX_SPK_NORMALIZE = 1 };  /* vx_spk_embed flags */
+typedef struct vx_spk_config {
+  int32_t struct_size;            /* sizeof(vx_spk_config) */
+  int32_t attention;              /* VX_SPK_* */
+  int32_t hidden, layers, heads, ffn;
+  int32_t n_conv;                 /* 1 .. 8 */
+  int32_t conv_dim[8], conv_kernel[8], conv_stride[8];
+  int32_t conv_bias;              /* 0 / 1 */
+  int32_t pos_kernel, pos_groups;
+  int32_t num_buckets;            /* rows of rel_attn_embed */
+  int32_t n_tdnn;                 /* 1 .. 8 */
+  int32_t tdnn_dim[8], tdnn_kernel[8], tdnn_dilation[8];
+  int32_t xvector;
+  int32_t use_weighted_layer_sum; /* 0 / 1 */
+  int32_t feat_extract_norm;      /* 0 = "group" (served), 1 = "layer" */
+  int32_t do_stable_layer_norm;   /* 0 (served) / 1 */
+  int32_t add_adapter;            /* 0 (served) / 1 */
+  int32_t activation;             /* 0 = gelu (served) */
+  float layer_norm_eps;
+  int32_t max_batch;              /* utterances per call, <= 64 */
+  int32_t max_samples;            /* samples per utterance */
+  int32_t flags;                  /* VX_SPK_KEEP_TAPS */
+} vx_spk_config;
+/* Host only, no HIP call.  In this order: nulls, a wrong struct_size, a count or size outside its range (n_conv, n_tdnn in 1 .. 8;
+ * every dimension, kernel, stride, dilation >= 1; heads dividing hidden, pos_groups dividing hidden; an attention outside VX_SPK_*;
+ * max_batch < 1; eps not finite) -> VX_ERR_ARG; then feat_extract_norm = 1, do_stable_layer_norm, add_adapter, an activation
+ * other than gelu, a head_dim other than 16, 32 or 64, conv_kernel[0] > 32 or conv_stride[0] > 32, max_batch > 64 ->
+ * VX_ERR_UNSUPPORTED; then max_samples below vx_spk_min_samples -> VX_ERR_ARG; then max_batch x the layer-0 frames of max_samples
+ * above 2^31 - 1 rows -> VX_ERR_UNSUPPORTED.  The workspace is sized from (max_batch, max_samples) and allocated on the device
+ * current at the first vx_spk_embed. */
+int vx_spk_create(const vx_spk_config* cfg, vx_spk** out);
+void vx_spk_destroy(vx_spk* h);
+/* Host only.  data: HOST fp32 of `shape`.  Unknown key or wrong shape -> VX_ERR_WEIGHTS; after vx_spk_finalize -> VX_ERR_STATE. */
+int vx_spk_set_weight(vx_spk* h, const char* key, const float* data, const int64_t* shape, int32_t ndim);
+/* Host only, VX_SPK_WAVLM: idx[r + Tmax - 1] = the row of rel_attn_embed for the relative position r = j - i, for every r in
+ * [-(Tmax - 1), Tmax - 1], Tmax = vx_spk_frames(max_samples); n must be 2 Tmax - 1 and every index inside [0, num_buckets), else
+ * VX_ERR_ARG.  The caller computes them by WavLM's rule (positive r offset by num_buckets / 2, exact below num_buckets / 4,
+ * logarithmic above with the logarithm in fp32, saturated at max_bucket_distance): the library does not re-derive them. */
+int vx_spk_set_buckets(vx_spk* h, const int32_t* idx, int32_t n);
+/* Host only: every tensor is there (a missing one -> VX_ERR_WEIGHTS naming it; VX_SPK_WAVLM without buckets -> VX_ERR_STATE); packs
+ * the weights, builds the per-head bias table (H, 2 Tmax - 1) and soft-maxes layer_weights in fp64. */
+int vx_spk_finalize(vx_spk* h);
+/* Frames the feature encoder leaves of n_samples (0 when too few for one); -1 for a null handle.  Host only. */
+int64_t vx_spk_frames(const vx_spk* h, int64_t n_samples);
+/* The shortest utterance served: the one that leaves two pooled frames (5200 at the default strides and TDNN kernels). */
+int64_t vx_spk_min_samples(const vx_spk* h);
+/* n utterances: wav[i] DEVICE fp32 of n_samples[i] samples at 16 kHz; emb_out DEVICE fp32 (n, xvector); logits_out NULL or DEVICE
+ * fp32 (n, xvector).  The pointer array and n_samples live on the host.  Every utterance is bitwise what it is alone, and two
+ * identical calls give the same bits.  Checked before any HIP call, in this order: null arguments (logits_out excepted), n < 1,
+ * unknown flags -> VX_ERR_ARG; not finalized -> VX_ERR_STATE; n > max_batch -> VX_ERR_CAPACITY; then per utterance a null pointer
+ * or n_samples[i] < vx_spk_min_samples (the message states both lengths) -> VX_ERR_ARG, n_samples[i] > max_samples ->
+ * VX_ERR_CAPACITY.  The work is enqueued on `stream`; the host waits only for the previous call's staging copy.  Calls on one
+ * handle must not overlap. */
+int vx_spk_embed(vx_spk* h, int32_t n, const float* const* wav, const int32_t* n_samples, int32_t flags, float* emb_out,
+                 float* logits_out, void* stream);
+/* out[p] = cosine of a[p] and b[p], DEVICE fp32 (n, xvector) each, out DEVICE fp32 (n).  Nulls or n < 1 -> VX_ERR_ARG. */
+int vx_spk_similarity(vx_spk* h, int32_t n, const float* a, const float* b, float* out, void* stream);
+/* A read tap for the tests: waits for the last vx_spk_embed and copies utterance `utt`'s part of "features", "hidden<l>" (needs
+ * VX_SPK_KEEP_TAPS), "gate<l>", "layer_sum", "tdnn" or "pooled" to dst (HOST fp32).  n_floats must be the tap's size (rows x
+ * width), else VX_ERR_ARG naming it; an unknown name -> VX_ERR_ARG; no call yet, or hidden<l> without the flag -> VX_ERR_STATE. */
+int vx_spk_read(vx_spk* h, const char* name, int32_t utt, float* dst, int64_t n_floats);
+/* out[0] = host milliseconds the last vx_spk_embed took to enqueue, out[1] = workspace bytes, out[2] = weight bytes, out[3] =
+ * encoder rows of the last call; n = how many of them are wanted (<= 4). */
+int vx_spk_get_timings(const vx_spk* h, double* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

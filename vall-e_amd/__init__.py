@@ -7,7 +7,8 @@ __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_T
            "BigVGANFbank", "BigVGANFbankConfig", "get_fbank_extractor", "mel_distance", "slaney_mel_basis",
            "DTW", "DTWResult", "mel_cepstral_distortion", "GriffinLim", "mel_to_waveform",
            "GanVocoder", "BigVGAN", "PitchTracker", "PitchTrack", "F0Result", "f0_distance",
-           "STFTConfig", "MultiResolutionSTFT", "MSTFTResult", "mstft_distance", "copy_synthesis_distance"]
+           "STFTConfig", "MultiResolutionSTFT", "MSTFTResult", "mstft_distance", "copy_synthesis_distance",
+           "SpeakerEncoder", "SpeakerConfig", "speaker_similarity"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -39,4 +40,8 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import stft
 
         return getattr(stft, name)
+    if name in ("SpeakerEncoder", "SpeakerConfig", "speaker_similarity"):
+        from . import spk
+
+        return getattr(spk, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -507,6 +507,18 @@ class EncodecDecoder:
         rec = self.decode(self.encode(wav, n_q))
         return shared_mstft(rec.device).compare(rec.reshape(-1), wav.reshape(-1))
 
+    @torch.no_grad()
+    def roundtrip_speaker_similarity(self, wav: torch.Tensor, encoder, n_q: Optional[int] = None, sr: Optional[int] = None,
+                                     normalize: bool = False) -> torch.Tensor:
+        """The speaker similarity (`spk.SpeakerEncoder`: the cosine of the two x-vectors, a 0-dim tensor on the device) of
+        decode(encode(waveform)) against the waveform: whether the codec keeps the voice, which the mel and M-STFT round trips do
+        not say.  `wav` and `sr` as in `encode`; both sides go to the encoder at 24 kHz and are resampled to 16 kHz there.  On
+        synthetic weights (the codec's or the encoder's) the number means nothing.  Needs `encoder=True`."""
+        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
+            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        rec = self.decode(self.encode(wav, n_q))
+        return encoder.similarity(wav.reshape(-1), rec.reshape(-1), sr=SAMPLE_RATE, normalize=normalize)[0]
+
 
 class AudioTokenizer:
     """The reference's `valle.data.tokenizer.AudioTokenizer` (tokenizer.py:238-254) on the GPU: `encode(wav)` with wav (B, 1, L)

@@ -69,6 +69,21 @@ class VxGanConfig(C.Structure):
 VX_GAN_LRELU, VX_GAN_SNAKE, VX_GAN_SNAKEBETA = 0, 1, 2
 
 
+class VxSpkConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "attention", "hidden", "layers", "heads", "ffn", "n_conv")] + \
+               [(n, C.c_int32 * 8) for n in ("conv_dim", "conv_kernel", "conv_stride")] + \
+               [(n, C.c_int32) for n in ("conv_bias", "pos_kernel", "pos_groups", "num_buckets", "n_tdnn")] + \
+               [(n, C.c_int32 * 8) for n in ("tdnn_dim", "tdnn_kernel", "tdnn_dilation")] + \
+               [(n, C.c_int32) for n in ("xvector", "use_weighted_layer_sum", "feat_extract_norm", "do_stable_layer_norm", "add_adapter",
+                                         "activation")] + \
+               [("layer_norm_eps", C.c_float), ("max_batch", C.c_int32), ("max_samples", C.c_int32), ("flags", C.c_int32)]
+
+
+VX_SPK_WAVLM, VX_SPK_PLAIN = 0, 1
+VX_SPK_KEEP_TAPS = 1   # vx_spk_config.flags
+VX_SPK_NORMALIZE = 1   # vx_spk_embed flags
+
+
 class VxDtwConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "dim", "n_ceps", "max_frames", "max_batch")]
 
@@ -269,6 +284,19 @@ _SIGS = {
     "vx_gan_samples": (C.c_int64, [C.c_void_p, C.c_int64]),
     "vx_gan_synthesize": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                     C.c_void_p]),
+    # speaker encoder (spk.SpeakerEncoder)
+    "vx_spk_create": (C.c_int, [C.POINTER(VxSpkConfig), C.POINTER(C.c_void_p)]),
+    "vx_spk_destroy": (None, [C.c_void_p]),
+    "vx_spk_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "vx_spk_set_buckets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "vx_spk_finalize": (C.c_int, [C.c_void_p]),
+    "vx_spk_frames": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "vx_spk_min_samples": (C.c_int64, [C.c_void_p]),
+    "vx_spk_embed": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "vx_spk_similarity": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vx_spk_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),
+    "vx_spk_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so
