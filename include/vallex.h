@@ -1185,6 +1185,104 @@ int vx_spk_read(vx_spk* h, const char* name, int32_t utt, float* dst, int64_t n_
  * encoder rows of the last call; n = how many of them are wanted (<= 4). */
 int vx_spk_get_timings(const vx_spk* h, double* out, int32_t n);
 
+/* ---- CTC speech recogniser: Wav2Vec2ForCTC / HubertForCTC, a 16 kHz waveform to token ids; the edit distance behind WER / CER ------
+ * A handle of its own, fp32 storage and accumulation.  The network is the speaker encoder's (above: the same steps, the same
+ * kernels, VX_SPK_PLAIN attention) up to the last hidden state, in one of two flavours, and a Linear head.  Notation as above.
+ *   0. VX_ASR_NORMALIZE (a flag of the call): as VX_SPK_NORMALIZE.
+ *   1. feature encoder.  group flavour (feat_extract_norm = 0): as the speaker encoder's.  layer flavour (feat_extract_norm = 1):
+ *      every layer i = Conv1d(C_{i-1} -> C_i, k_i, s_i) with bias, then LayerNorm over the C_i channels of each frame (biased
+ *      variance, eps 1e-5, affine), then GELU.  Taps "conv0" (T_0, C_0) after layer 0 and "features" (T, C) after the last.
+ *   2. projection: LayerNorm(C) (eps = layer_norm_eps, as every LayerNorm below; skipped when feat_proj_layer_norm = 0), Linear C -> d.
+ *   3. positional convolution p = gelu(Conv1d(d -> d, k = pos_kernel, padding k / 2, groups = pos_groups)), the last output frame
+ *      dropped when k is even.
+ *   4. encoder.  post-norm (do_stable_layer_norm = 0): h = LN_enc(h + p) (tap "hidden0"), then per layer h = LN1(h + Attn(h));
+ *      h = LN2(h + FFN(h)) (tap "hidden<l+1>").  stable (do_stable_layer_norm = 1): h = h + p (tap "hidden0"), then per layer
+ *      h = h + Attn(LN1(h)); h = h + FFN(LN2(h)) (tap "hidden<l+1>" for l + 1 < L), and after the last layer h = LN_enc(h) (tap
+ *      "hidden<L>").  LN1 = layers.{l}.layer_norm, LN2 = layers.{l}.final_layer_norm, LN_enc = encoder.layer_norm;
+ *      FFN(x) = W2 gelu(W1 x + b1) + b2; Attn as VX_SPK_PLAIN.  The residual is always the un-normed stream.
+ *   5. logits = lm_head h (T, vocab), tap "logits".
+ *   6. greedy CTC decode (vx_ctc_greedy on its own): per frame id[t] = argmax of the logits, the lowest index among equal maxima,
+ *      and lp[t] = x[id] - log sum_c exp(x[c]) with the sum of exp(x[c] - x[id]) taken in fp64; frame t is kept when
+ *      id[t] != blank and (t == 0 or id[t] != id[t - 1]): repeats are merged first, blanks removed second (A A _ A gives A A).
+ *      Per utterance: the kept ids and their frame indices in frame order, their count, and the mean of lp over ALL frames.
+ * Edit distance (vx_edit_distance): Levenshtein with unit costs between a reference and a hypothesis, D(i, 0) = i deletions,
+ * D(0, j) = j insertions, D(i, j) = the cheapest of D(i-1, j-1) + [ref_i != hyp_j] (a match or a substitution), D(i-1, j) + 1 (a
+ * deletion) and D(i, j-1) + 1 (an insertion); among equal costs the first in that order is taken, and S / D / I are the
+ * counts along that choice: those of a backtrace from (R, H) with the same preference.
+ * Weight keys (fp32, host, torch layouts, transformers' names without the wav2vec2. / hubert. prefix, weight norm folded): as the
+ * speaker encoder's feature encoder, projection and encoder without the WavLM tensors; layer flavour: every
+ * feature_extractor.conv_layers.{i}.layer_norm.* and .conv.bias; feature_projection.layer_norm.* only with feat_proj_layer_norm;
+ * lm_head.weight (vocab, d) / .bias. */
+typedef struct vx_asr vx_asr;
+enum { VX_ASR_KEEP_TAPS = 1 };  /* vx_asr_config.flags: every hidden state keeps a buffer of its own ("hidden<l>" can be read) */
+enum { VX_ASR_NORMALIZE = 1 };  /* vx_asr_recognize flags */
+typedef struct vx_asr_config {
+  int32_t struct_size;            /* sizeof(vx_asr_config) */
+  int32_t hidden, layers, heads, ffn;
+  int32_t n_conv;                 /* 1 .. 8 */
+  int32_t conv_dim[8], conv_kernel[8], conv_stride[8];
+  int32_t conv_bias;              /* 0 / 1 */
+  int32_t pos_kernel, pos_groups;
+  int32_t vocab, blank;           /* rows of lm_head; the CTC blank (the tokenizer's <pad>) */
+  int32_t feat_extract_norm;      /* 0 = "group", 1 = "layer" */
+  int32_t do_stable_layer_norm;   /* 0 / 1; served together with feat_extract_norm: 0 / 0 and 1 / 1 */
+  int32_t feat_proj_layer_norm;   /* 1 (Wav2Vec2 always) / 0 (HuBERT's option) */
+  int32_t add_adapter;            /* 0 (served) / 1 */
+  int32_t conv_pos_batch_norm;    /* 0 (served) / 1 */
+  int32_t activation;             /* 0 = gelu (served) */
+  float layer_norm_eps;
+  int32_t max_batch;              /* utterances per call, <= 64 */
+  int32_t max_samples;            /* samples per utterance */
+  int32_t flags;                  /* VX_ASR_KEEP_TAPS */
+} vx_asr_config;
+/* Host only, no HIP call.  In this order: nulls, a wrong struct_size, a count or size outside its range (as vx_spk_create; vocab
+ * < 1, blank outside [0, vocab)) -> VX_ERR_ARG; then add_adapter, conv_pos_batch_norm, an activation other than gelu,
+ * feat_extract_norm != do_stable_layer_norm (a mix the released checkpoints do not have), the layer flavour without conv_bias, a
+ * head_dim other than 16, 32 or 64, conv_kernel[0] > 32 or conv_stride[0] > 32, layer flavour: conv_dim[0] > 1024 or a layer-0 tile
+ * (63 stride + k + k C_0 floats) above 60 KiB, max_batch > 64 -> VX_ERR_UNSUPPORTED with the field named; then max_samples below
+ * vx_asr_min_samples -> VX_ERR_ARG; then max_batch x the layer-0 frames of max_samples above 2^31 - 1 -> VX_ERR_UNSUPPORTED. */
+int vx_asr_create(const vx_asr_config* cfg, vx_asr** out);
+void vx_asr_destroy(vx_asr* h);
+/* Host only.  data: HOST fp32 of `shape`.  Unknown key or wrong shape -> VX_ERR_WEIGHTS; after vx_asr_finalize -> VX_ERR_STATE. */
+int vx_asr_set_weight(vx_asr* h, const char* key, const float* data, const int64_t* shape, int32_t ndim);
+/* Host only: every tensor is there (a missing one -> VX_ERR_WEIGHTS naming it); packs the weights. */
+int vx_asr_finalize(vx_asr* h);
+/* Frames the feature encoder leaves of n_samples (0 when too few for one); -1 for a null handle.  Host only. */
+int64_t vx_asr_frames(const vx_asr* h, int64_t n_samples);
+/* The shortest utterance served: the one that leaves one encoder frame (400 samples at the default kernels and strides). */
+int64_t vx_asr_min_samples(const vx_asr* h);
+/* n utterances: wav[i] DEVICE fp32 of n_samples[i] samples at 16 kHz.  With T_i = vx_asr_frames(n_samples[i]) and o_i = T_0 + ..
+ * + T_{i-1}: tokens_out and token_frames_out are DEVICE int32 of sum T_i entries, utterance i's kept ids and their frame indices at
+ * o_i .. o_i + counts_out[i] (the rest of its T_i entries is not written); counts_out DEVICE int32 (n); mean_logprob_out DEVICE
+ * fp32 (n); logits_out NULL or DEVICE fp32 (sum T_i, vocab).  The pointer array and n_samples live on the host.  Every utterance is
+ * bitwise what it is alone, and two identical calls give the same bits.  Checked before any HIP call, in this order: null
+ * arguments (logits_out excepted), n < 1, unknown flags -> VX_ERR_ARG; not finalized -> VX_ERR_STATE; n > max_batch ->
+ * VX_ERR_CAPACITY; then per utterance a null pointer or n_samples[i] < vx_asr_min_samples (the message states both lengths) ->
+ * VX_ERR_ARG, n_samples[i] > max_samples -> VX_ERR_CAPACITY.  The work is enqueued on `stream`; the host waits only for the
+ * previous call's staging copy.  Calls on one handle must not overlap. */
+int vx_asr_recognize(vx_asr* h, int32_t n, const float* const* wav, const int32_t* n_samples, int32_t flags, int32_t* tokens_out,
+                     int32_t* token_frames_out, int32_t* counts_out, float* mean_logprob_out, float* logits_out, void* stream);
+/* A read tap for the tests: waits for the last vx_asr_recognize and copies utterance `utt`'s part of "conv0", "features",
+ * "hidden<l>" (needs VX_ASR_KEEP_TAPS) or "logits" to dst (HOST fp32).  n_floats must be the tap's size (rows x width), else
+ * VX_ERR_ARG naming it; an unknown name -> VX_ERR_ARG; no call yet, or hidden<l> without the flag -> VX_ERR_STATE. */
+int vx_asr_read(vx_asr* h, const char* name, int32_t utt, float* dst, int64_t n_floats);
+/* out[0] = host milliseconds the last vx_asr_recognize took to enqueue, out[1] = workspace bytes, out[2] = weight bytes, out[3] =
+ * encoder rows of the last call; n = how many of them are wanted (<= 4). */
+int vx_asr_get_timings(const vx_asr* h, double* out, int32_t n);
+/* Step 6 on its own, on the current device: logits DEVICE fp32 (sum frames[i], vocab), the utterances' rows concatenated; frames
+ * HOST (n), each >= 0; outputs as vx_asr_recognize's (an utterance without frames: count 0, mean 0); frame_logprob_out NULL or
+ * DEVICE fp32 (sum frames[i]): lp[t] rounded to fp32.  Nulls, n < 1, vocab < 1, blank outside [0, vocab), a negative frame count
+ * -> VX_ERR_ARG.  Allocates its scratch and waits for `stream` before it returns (a test and tool entry, not a hot path). */
+int vx_ctc_greedy(const float* logits, int32_t vocab, int32_t blank, int32_t n, const int32_t* frames, int32_t* tokens_out,
+                  int32_t* token_frames_out, int32_t* counts_out, float* mean_logprob_out, float* frame_logprob_out, void* stream);
+/* n pairs on the current device: ref / hyp DEVICE int32, the pairs' sequences concatenated (pair p's at the sum of the lengths
+ * before it); ref_len / hyp_len HOST (n), each in [0, 2048]; out DEVICE int32 (n, 4): distance, substitutions, deletions,
+ * insertions.  A zero-length side is legal.  Nulls (a sequence pointer may be null when its lengths are all 0), n < 1, a negative
+ * length or one above 2048 (the message states the limit: three diagonals of 64-bit cells in LDS) -> VX_ERR_ARG.  Waits for
+ * `stream` before it returns. */
+int vx_edit_distance(int32_t n, const int32_t* ref, const int32_t* ref_len, const int32_t* hyp, const int32_t* hyp_len, int32_t* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@ __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_T
            "DTW", "DTWResult", "mel_cepstral_distortion", "GriffinLim", "mel_to_waveform",
            "GanVocoder", "BigVGAN", "PitchTracker", "PitchTrack", "F0Result", "f0_distance",
            "STFTConfig", "MultiResolutionSTFT", "MSTFTResult", "mstft_distance", "copy_synthesis_distance",
-           "SpeakerEncoder", "SpeakerConfig", "speaker_similarity"]
+           "SpeakerEncoder", "SpeakerConfig", "speaker_similarity",
+           "SpeechRecognizer", "RecognizerConfig", "Transcript", "ErrorRate", "edit_distance", "word_error_rate", "char_error_rate",
+           "recognition_error"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -44,4 +46,9 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import spk
 
         return getattr(spk, name)
+    if name in ("SpeechRecognizer", "RecognizerConfig", "Transcript", "ErrorRate", "edit_distance", "word_error_rate", "char_error_rate",
+                "recognition_error"):
+        from . import asr
+
+        return getattr(asr, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

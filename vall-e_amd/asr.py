@@ -1,0 +1,510 @@
+"""CTC speech recogniser on the GPU: `transformers`' `Wav2Vec2ForCTC` / `HubertForCTC` behind `vx_asr_*` (include/vallex.h,
+csrc/asr_kernels.hpp on top of the speaker encoder's kernels), its greedy decode, and the word / character error rate of a
+transcript against the text that was to be said, with the edit distance on the device; there is no CPU fallback.
+
+    from valle_amd import SpeechRecognizer, recognition_error
+    rec = SpeechRecognizer("ckpt/config.json", json.load(open("ckpt/vocab.json")), state_dict=torch.load("ckpt/pytorch_model.bin")).to("cuda")
+    hyp = rec.recognize([synth_wav], sr=24000)[0]          # .text, .tokens, .frames (x 20 ms), .logprob
+    wer = recognition_error(text, synth_wav, rec, sr=24000)  # ErrorRate: .rate, .pairs[0].substitutions / .deletions / .insertions
+
+Two flavours, chosen by the checkpoint's config: group / post-norm (`wav2vec2-base-960h`, HuBERT base) and layer / stable
+(`hubert-large-ls960-ft`, `wav2vec2-large-960h-lv60-self`).  The definition is stated in include/vallex.h and restated in fp64 in
+tests/asr_ref.py, which tests/test_asr_cpu.py pins against the two `transformers` classes.  Nothing has been recognised on trained
+weights: no checkpoint is available where this is built, and on synthetic weights the error rate means nothing.  The S / D / I
+counts are those of the stated tie-break (match or substitution, then deletion, then insertion); only their sum, the distance,
+is independent of it, so parity with another aligner's counts (jiwer's, say) is by definition only."""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import json
+import math
+import re
+from typing import Dict, List, Optional, Sequence, Union
+
+import torch
+
+from . import engine as _e
+from .spk import canonical_state_dict as _canonical
+
+SAMPLE_RATE = 16000
+HEAD_DIMS = (16, 32, 64)
+EDIT_MAX_LEN = 2048  # tokens per side of a pair (csrc/asr_kernels.hpp)
+
+
+@dataclasses.dataclass
+class RecognizerConfig:
+    """The fields of `Wav2Vec2Config` / `HubertConfig` the network reads, under their names and with `Wav2Vec2Config()`'s defaults."""
+    hidden_size: int = 768
+    num_hidden_layers: int = 12
+    num_attention_heads: int = 12
+    intermediate_size: int = 3072
+    conv_dim: Sequence[int] = (512, 512, 512, 512, 512, 512, 512)
+    conv_kernel: Sequence[int] = (10, 3, 3, 3, 3, 2, 2)
+    conv_stride: Sequence[int] = (5, 2, 2, 2, 2, 2, 2)
+    conv_bias: bool = False
+    num_conv_pos_embeddings: int = 128
+    num_conv_pos_embedding_groups: int = 16
+    vocab_size: int = 32
+    pad_token_id: int = 0
+    layer_norm_eps: float = 1e-5
+    feat_extract_norm: str = "group"
+    feat_extract_activation: str = "gelu"
+    hidden_act: str = "gelu"
+    do_stable_layer_norm: bool = False
+    feat_proj_layer_norm: bool = True
+    add_adapter: bool = False
+    conv_pos_batch_norm: bool = False
+
+    def __post_init__(self):  # a config.json gives lists
+        self.conv_dim, self.conv_kernel, self.conv_stride = tuple(self.conv_dim), tuple(self.conv_kernel), tuple(self.conv_stride)
+
+    @classmethod
+    def from_any(cls, cfg) -> "RecognizerConfig":
+        """A dict (a checkpoint's `config.json`), a path to one, or any object with the attributes."""
+        if isinstance(cfg, cls):
+            return cfg
+        if isinstance(cfg, str):
+            with open(cfg) as f:
+                cfg = json.load(f)
+        names = [f.name for f in dataclasses.fields(cls)]
+        if isinstance(cfg, dict):
+            return cls(**{k: cfg[k] for k in names if k in cfg and cfg[k] is not None})
+        return cls(**{k: getattr(cfg, k) for k in names if getattr(cfg, k, None) is not None})
+
+
+def expected_keys(c: RecognizerConfig) -> Dict[str, tuple]:
+    """canonical key -> shape, as vx_asr_create lays them out."""
+    d = int(c.hidden_size)
+    layer = c.feat_extract_norm == "layer"
+    keys: Dict[str, tuple] = {}
+
+    def lin(name, n, k):
+        keys[name + ".weight"], keys[name + ".bias"] = (n, k), (n,)
+
+    def norm(name, n):
+        keys[name + ".weight"], keys[name + ".bias"] = (n,), (n,)
+
+    cin = 1
+    for i, (co, k) in enumerate(zip(c.conv_dim, c.conv_kernel)):
+        keys[f"feature_extractor.conv_layers.{i}.conv.weight"] = (int(co), cin, int(k))
+        if c.conv_bias:
+            keys[f"feature_extractor.conv_layers.{i}.conv.bias"] = (int(co),)
+        if i == 0 or layer:
+            norm(f"feature_extractor.conv_layers.{i}.layer_norm", int(co))
+        cin = int(co)
+    if c.feat_proj_layer_norm:
+        norm("feature_projection.layer_norm", cin)
+    lin("feature_projection.projection", d, cin)
+    keys["encoder.pos_conv_embed.conv.weight"] = (d, d // int(c.num_conv_pos_embedding_groups), int(c.num_conv_pos_embeddings))
+    keys["encoder.pos_conv_embed.conv.bias"] = (d,)
+    norm("encoder.layer_norm", d)
+    for l in range(int(c.num_hidden_layers)):
+        pre = f"encoder.layers.{l}."
+        for nm in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            lin(pre + "attention." + nm, d, d)
+        norm(pre + "layer_norm", d)
+        lin(pre + "feed_forward.intermediate_dense", int(c.intermediate_size), d)
+        lin(pre + "feed_forward.output_dense", d, int(c.intermediate_size))
+        norm(pre + "final_layer_norm", d)
+    lin("lm_head", int(c.vocab_size), d)
+    return keys
+
+
+def canonical_state_dict(sd: dict) -> Dict[str, torch.Tensor]:
+    """A `Wav2Vec2ForCTC` / `HubertForCTC` state dict -> {canonical key: fp32 CPU tensor}: the `wav2vec2.` / `hubert.` prefix dropped,
+    the positional convolution's weight norm folded, `masked_spec_embed` ignored."""
+    return _canonical({re.sub(r"^hubert\.", "wav2vec2.", k): v for k, v in sd.items()})
+
+
+def synthetic_state_dict(config, seed: int = 0, prefix: str = "wav2vec2.", head_scale: float = 4.0) -> Dict[str, torch.Tensor]:
+    """Seeded weights in the `transformers` layout (prefix `wav2vec2.` / `hubert.`, weight norm unfolded) for the tests.  The scales
+    keep every stage alive and make every part of the definition matter (norm gains and biases away from 1 and 0, convolution gains
+    that put the GELUs in their curved range); `head_scale` spreads the logits so that the argmax of nearly every frame is decided by
+    far more than fp32 rounding."""
+    c = RecognizerConfig.from_any(config)
+    g = torch.Generator().manual_seed(int(seed))
+    sd: Dict[str, torch.Tensor] = {}
+
+    def rnd(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    for k, shape in expected_keys(c).items():
+        name = k if k.startswith("lm_head") else prefix + k
+        if k == "encoder.pos_conv_embed.conv.weight":
+            sd[prefix + "encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = 0.5 + torch.rand(1, 1, shape[2], generator=g)
+            sd[prefix + "encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = rnd(*shape)
+        elif k.endswith("layer_norm.weight"):
+            sd[name] = 1.0 + rnd(*shape, scale=0.2)
+        elif k.endswith("layer_norm.bias"):
+            sd[name] = rnd(*shape, scale=0.5)
+        elif k.endswith(".bias"):
+            sd[name] = rnd(*shape, scale=0.1)
+        elif k == "feature_extractor.conv_layers.0.conv.weight":
+            sd[name] = rnd(*shape, scale=1.0)
+        else:  # Linear and convolution weights: unit gain over the fan-in
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            sd[name] = rnd(*shape, scale=(head_scale if k == "lm_head.weight" else 1.5) / math.sqrt(fan_in))
+    sd[prefix + "masked_spec_embed"] = rnd(int(c.hidden_size))
+    return sd
+
+
+@dataclasses.dataclass
+class Transcript:
+    text: str
+    tokens: List[int]      # the kept ids, repeats merged and blanks removed
+    frames: List[int]      # the encoder frame of every kept id (x 20 ms at the default strides: the character's time)
+    logprob: float         # mean over ALL frames of the log-probability of the frame's argmax
+
+
+def ids_to_text(ids: Sequence[int], id_to_token: Dict[int, str], word_delimiter: str = "|", special=()) -> str:
+    """The tokenizer's rule for already collapsed ids: the word delimiter is a space, special tokens are dropped."""
+    out = []
+    for i in ids:
+        tok = id_to_token.get(int(i), "")
+        if tok in special:
+            continue
+        out.append(" " if tok == word_delimiter else tok)
+    return " ".join("".join(out).split())
+
+
+class SpeechRecognizer:
+    """`SpeechRecognizer(config, vocab, max_batch=32, max_seconds=20.0, state_dict=None)`: `config` is a `RecognizerConfig`, a dict or
+    path of the checkpoint's `config.json`, or any object with the `Wav2Vec2Config` / `HubertConfig` attributes; `vocab` is the
+    checkpoint's `vocab.json` mapping token -> id, with `|` as the word delimiter and `<pad>` as the CTC blank unless `blank` names
+    another token.  A call serves up to `max_batch` (<= 64) utterances of up to `max_seconds` at 16 kHz each.  Adapters,
+    `conv_pos_batch_norm`, activations other than GELU, head dimensions other than 16 / 32 / 64 and a feature encoder norm that does
+    not go with the encoder (`group` with post-norm, `layer` with stable) raise NotImplementedError naming the field."""
+
+    def __init__(self, config, vocab: Dict[str, int], max_batch: int = 32, max_seconds: float = 20.0, state_dict: Optional[dict] = None,
+                 keep_taps: bool = False, blank: str = "<pad>", word_delimiter: str = "|"):
+        c = self.config = RecognizerConfig.from_any(config)
+        if c.add_adapter:
+            raise NotImplementedError("add_adapter: adapters are not served")
+        if c.conv_pos_batch_norm:
+            raise NotImplementedError("conv_pos_batch_norm: the weight-normed positional convolution is served")
+        if c.feat_extract_activation != "gelu" or c.hidden_act != "gelu":
+            raise NotImplementedError(f"feat_extract_activation / hidden_act = {c.feat_extract_activation!r} / {c.hidden_act!r}: gelu is served")
+        if c.feat_extract_norm not in ("group", "layer"):
+            raise ValueError(f"feat_extract_norm = {c.feat_extract_norm!r}")
+        if (c.feat_extract_norm == "layer") != bool(c.do_stable_layer_norm):
+            raise NotImplementedError(f"feat_extract_norm = {c.feat_extract_norm!r} with do_stable_layer_norm = {bool(c.do_stable_layer_norm)}: "
+                                      "group / post-norm and layer / stable are served")
+        if int(c.hidden_size) % int(c.num_attention_heads) or int(c.hidden_size) // int(c.num_attention_heads) not in HEAD_DIMS:
+            raise NotImplementedError(f"head_dim = {c.hidden_size} / {c.num_attention_heads}: {HEAD_DIMS} are served")
+        if not (len(c.conv_dim) == len(c.conv_kernel) == len(c.conv_stride)) or not 1 <= len(c.conv_dim) <= 8:
+            raise ValueError("conv_dim, conv_kernel and conv_stride have one entry per layer, 1..8 layers")
+        self.vocab = {str(k): int(v) for k, v in vocab.items()}
+        if blank not in self.vocab:
+            raise ValueError(f"vocab has no blank token {blank!r}")
+        if max(self.vocab.values()) >= int(c.vocab_size) or min(self.vocab.values()) < 0:
+            raise ValueError(f"vocab ids outside [0, vocab_size = {c.vocab_size})")
+        self.blank_id, self.word_delimiter = self.vocab[blank], word_delimiter
+        self.id_to_token = {v: k for k, v in self.vocab.items()}
+        self.special = tuple(t for t in self.vocab if re.fullmatch(r"<.*>", t))
+        self.max_batch, self.max_samples = int(max_batch), int(round(float(max_seconds) * SAMPLE_RATE))
+        self.keep_taps = bool(keep_taps)
+        self.device = torch.device("cpu")
+        self._h = None
+        self._bound = None
+        self._weights: Optional[Dict[str, torch.Tensor]] = None
+        self._resamplers: Dict[int, object] = {}
+        self._create()  # a geometry the kernels do not serve is refused here
+        if state_dict is not None:
+            self.load_state_dict(state_dict)
+
+    # ---- handle -------------------------------------------------------------------------------------
+    def _config_struct(self) -> "_e.VxAsrConfig":
+        s, c = _e.VxAsrConfig(), self.config
+        s.struct_size = C.sizeof(_e.VxAsrConfig)
+        s.hidden, s.layers, s.heads, s.ffn = int(c.hidden_size), int(c.num_hidden_layers), int(c.num_attention_heads), int(c.intermediate_size)
+        s.n_conv = len(c.conv_dim)
+        for i, (dm, k, st) in enumerate(zip(c.conv_dim, c.conv_kernel, c.conv_stride)):
+            s.conv_dim[i], s.conv_kernel[i], s.conv_stride[i] = int(dm), int(k), int(st)
+        s.conv_bias = int(bool(c.conv_bias))
+        s.pos_kernel, s.pos_groups = int(c.num_conv_pos_embeddings), int(c.num_conv_pos_embedding_groups)
+        s.vocab, s.blank = int(c.vocab_size), self.blank_id
+        s.feat_extract_norm = int(c.feat_extract_norm == "layer")
+        s.do_stable_layer_norm = int(bool(c.do_stable_layer_norm))
+        s.feat_proj_layer_norm = int(bool(c.feat_proj_layer_norm))
+        s.add_adapter, s.conv_pos_batch_norm = int(bool(c.add_adapter)), int(bool(c.conv_pos_batch_norm))
+        s.activation = 0
+        s.layer_norm_eps = float(c.layer_norm_eps)
+        s.max_batch, s.max_samples = self.max_batch, self.max_samples
+        s.flags = _e.VX_ASR_KEEP_TAPS if self.keep_taps else 0
+        return s
+
+    def _create(self):
+        lib = _e.load_library()
+        h = C.c_void_p()
+        _e._check(lib.vx_asr_create(C.byref(self._config_struct()), C.byref(h)))
+        self._h, self._bound = h, None
+        if self._weights is not None:
+            try:
+                for k, t in self._weights.items():
+                    shape = (C.c_int64 * t.dim())(*t.shape)
+                    _e._check(lib.vx_asr_set_weight(self._h, k.encode(), t.data_ptr(), shape, t.dim()))
+                _e._check(lib.vx_asr_finalize(self._h))
+            except Exception:
+                self.close()
+                raise
+
+    def _handle(self):
+        if self._h is None:
+            self._create()
+        return self._h
+
+    def num_frames(self, n_samples: int) -> int:
+        """Frames the feature encoder leaves of `n_samples` samples at 16 kHz (host only)."""
+        return int(_e.load_library().vx_asr_frames(self._handle(), int(n_samples)))
+
+    @property
+    def max_frames(self) -> int:
+        return self.num_frames(self.max_samples)
+
+    @property
+    def min_samples(self) -> int:
+        """The shortest utterance served (one encoder frame): 400 samples at the default kernels and strides."""
+        return int(_e.load_library().vx_asr_min_samples(self._handle()))
+
+    def workspace_bytes(self) -> int:
+        out = (C.c_double * 4)()
+        _e._check(_e.load_library().vx_asr_get_timings(self._handle(), out, 4))
+        return int(out[1])
+
+    def load_state_dict(self, sd: dict):
+        """Takes the `transformers` key layout (see `canonical_state_dict`); missing and unexpected keys and wrong shapes raise by
+        name.  Returns self."""
+        w = canonical_state_dict(sd)
+        want = expected_keys(self.config)
+        missing = sorted(k for k in want if k not in w)
+        unexpected = sorted(k for k in w if k not in want)
+        if missing or unexpected:
+            raise KeyError(f"SpeechRecognizer.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
+        for k, shape in want.items():
+            if tuple(w[k].shape) != tuple(shape):
+                raise ValueError(f"SpeechRecognizer.load_state_dict: {k} is {tuple(w[k].shape)}, expected {tuple(shape)}")
+        self._weights = {k: w[k].to(torch.float32).contiguous() for k in want}
+        self.close()
+        self._create()
+        return self
+
+    def to(self, device):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self._bound is not None and self._bound != self.device:
+            self.close()  # another device gets a fresh handle on its first call
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            _e.load_library().vx_asr_destroy(self._h)
+            self._h = self._bound = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- recognition --------------------------------------------------------------------------------
+    def _prepare(self, wavs, sr: int) -> List[torch.Tensor]:
+        if isinstance(wavs, torch.Tensor):
+            wavs = [wavs]
+        ws = []
+        for w in wavs:
+            assert isinstance(w, torch.Tensor) and w.dtype == torch.float32, "waveforms are float32 tensors"
+            assert w.numel() == w.shape[-1], "one mono utterance per entry: (L,), (1, L) or (1, 1, L)"
+            ws.append(w.detach().reshape(-1))
+        if self.device.type != "cuda":
+            raise RuntimeError("valle_amd.SpeechRecognizer runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        if self._weights is None:
+            raise RuntimeError("SpeechRecognizer has no weights: call load_state_dict first")
+        ws = [w.to(self.device).contiguous() for w in ws]
+        if int(sr) != SAMPLE_RATE:
+            from .codec import Resampler
+
+            if sr not in self._resamplers:
+                self._resamplers[sr] = Resampler(int(sr), SAMPLE_RATE, max_batch=self.max_batch)
+            rs = self._resamplers[sr].to(self.device)
+            out = []
+            for i in range(0, len(ws), self.max_batch):
+                out += [o.reshape(-1) for o in rs.resample_batch(ws[i:i + self.max_batch])]
+            ws = out
+        return ws
+
+    def _recognize_raw(self, wav_ptrs, lengths, normalize, tokens_ptr, frames_ptr, counts_ptr, logprob_ptr, logits_ptr):
+        """vx_asr_recognize on raw pointers (the argument checks run before any device work)."""
+        n = len(wav_ptrs)
+        wp = (C.c_void_p * n)(*wav_ptrs)
+        L = (C.c_int32 * n)(*lengths)
+        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
+        h = self._handle()
+        if self.device.type == "cuda":
+            self._bound = self.device
+        _e._check(_e.load_library().vx_asr_recognize(h, n, wp, L, _e.VX_ASR_NORMALIZE if normalize else 0, tokens_ptr, frames_ptr, counts_ptr,
+                                                     logprob_ptr, logits_ptr, stream))
+
+    @torch.no_grad()
+    def _run(self, wavs, sr, normalize, want_logits):
+        ws = self._prepare(wavs, sr)
+        results, logits = [], []
+        V = int(self.config.vocab_size)
+        for i in range(0, len(ws), self.max_batch):
+            chunk = ws[i:i + self.max_batch]
+            T = [self.num_frames(w.numel()) for w in chunk]
+            total = max(sum(T), 1)
+            tok = torch.full((total,), -1, dtype=torch.int32, device=self.device)
+            frm = torch.full((total,), -1, dtype=torch.int32, device=self.device)
+            cnt = torch.zeros(len(chunk), dtype=torch.int32, device=self.device)
+            lp = torch.zeros(len(chunk), dtype=torch.float32, device=self.device)
+            lg = torch.empty((total, V), dtype=torch.float32, device=self.device) if want_logits else None
+            with torch.cuda.device(self.device):
+                self._recognize_raw([w.data_ptr() for w in chunk], [w.numel() for w in chunk], normalize, tok.data_ptr(), frm.data_ptr(),
+                                    cnt.data_ptr(), lp.data_ptr(), None if lg is None else lg.data_ptr())
+            tok, frm, cnt, lp = tok.cpu(), frm.cpu(), cnt.cpu().tolist(), lp.cpu().tolist()
+            o = 0
+            for u, t in enumerate(T):
+                ids = tok[o:o + cnt[u]].tolist()
+                results.append(Transcript(ids_to_text(ids, self.id_to_token, self.word_delimiter, self.special), ids,
+                                          frm[o:o + cnt[u]].tolist(), float(lp[u])))
+                if want_logits:
+                    logits.append(lg[o:o + t])
+                o += t
+        return results, logits
+
+    def recognize(self, wavs: Union[torch.Tensor, Sequence[torch.Tensor]], sr: int = 24000, normalize: bool = False) -> List[Transcript]:
+        """One waveform or a list of ragged ones, float32 (L,), (1, L) or (1, 1, L) at `sr` -> one `Transcript` per utterance.  Audio
+        at another rate than 16 kHz goes through the GPU `Resampler` first.  `normalize=True` applies the feature extractor's
+        zero-mean unit-variance rule per utterance: the checkpoint's `preprocessor_config.json` (`do_normalize`) says which it
+        wants.  More than `max_batch` utterances are served in several calls; every utterance is bitwise what it is alone.  The ids
+        become text on the host: `|` is a space, `<...>` tokens are dropped."""
+        return self._run(wavs, sr, normalize, False)[0]
+
+    def logits(self, wavs, sr: int = 24000, normalize: bool = False) -> List[torch.Tensor]:
+        """Per utterance the (frames, vocab) float32 logits on the device."""
+        return self._run(wavs, sr, normalize, True)[1]
+
+    def read_tap(self, name: str, utt: int, rows: int, width: int) -> torch.Tensor:
+        """(rows, width) float32 on the host: a tap of the last call (`vx_asr_read`; the parity tests)."""
+        out = torch.empty((rows, width), dtype=torch.float32)
+        _e._check(_e.load_library().vx_asr_read(self._handle(), name.encode(), int(utt), out.data_ptr(), out.numel()))
+        return out
+
+
+# ---- greedy CTC on given logits -----------------------------------------------------------------------
+@torch.no_grad()
+def ctc_greedy(logits: torch.Tensor, frames: Sequence[int], blank: int = 0):
+    """`vx_ctc_greedy`: logits (sum frames, vocab) float32 on the device, the utterances' rows concatenated -> (tokens, token_frames)
+    as lists of int lists, mean log-probabilities (n,) and per-frame log-probabilities (sum frames,) on the host."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    n, total = len(frames), int(sum(frames))
+    assert logits.shape[0] == total
+    dev = logits.device
+    tok = torch.full((total + 1,), -1, dtype=torch.int32, device=dev)
+    frm = torch.full((total + 1,), -1, dtype=torch.int32, device=dev)
+    cnt = torch.full((n + 1,), -1, dtype=torch.int32, device=dev)
+    mean = torch.full((n + 1,), float("nan"), dtype=torch.float32, device=dev)
+    flp = torch.full((total + 1,), float("nan"), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _e._check(_e.load_library().vx_ctc_greedy(logits.data_ptr(), logits.shape[1], int(blank), n, (C.c_int32 * n)(*[int(f) for f in frames]),
+                                                  tok.data_ptr(), frm.data_ptr(), cnt.data_ptr(), mean.data_ptr(), flp.data_ptr(),
+                                                  _e.current_stream_ptr(dev)))
+    assert int(tok[-1]) == -1 and int(frm[-1]) == -1 and int(cnt[-1]) == -1 and bool(torch.isnan(mean[-1])) and bool(torch.isnan(flp[-1])), \
+        "a write outside an output"
+    tok, frm, cnt = tok.cpu(), frm.cpu(), cnt[:-1].cpu().tolist()
+    ids, at, o = [], [], 0
+    for u, t in enumerate(frames):
+        ids.append(tok[o:o + cnt[u]].tolist())
+        at.append(frm[o:o + cnt[u]].tolist())
+        o += int(t)
+    return ids, at, mean[:-1].cpu(), flp[:-1].cpu()
+
+
+# ---- edit distance and error rates ------------------------------------------------------------------------
+@dataclasses.dataclass
+class PairErrors:
+    distance: int
+    substitutions: int
+    deletions: int
+    insertions: int
+    ref_len: int
+
+    @property
+    def rate(self) -> float:
+        return self.distance / self.ref_len if self.ref_len else float("nan")
+
+
+@dataclasses.dataclass
+class ErrorRate:
+    rate: float               # (sum S + sum D + sum I) / sum N over the corpus; nan when sum N = 0
+    pairs: List[PairErrors]
+
+
+@torch.no_grad()
+def edit_distance(refs: Sequence[Sequence[int]], hyps: Sequence[Sequence[int]], device="cuda") -> torch.Tensor:
+    """`vx_edit_distance`: per pair (distance, substitutions, deletions, insertions) turning refs[p] into hyps[p], an (n, 4) int32
+    tensor on the host.  Unit costs; among equal costs a match or substitution is preferred, then a deletion, then an insertion.
+    Up to 2048 tokens a side; a zero-length side is legal."""
+    assert len(refs) == len(hyps) and len(refs) >= 1, "one hypothesis per reference"
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("valle_amd.asr.edit_distance runs only on an MI355X (no CPU fallback)")
+    n = len(refs)
+    rl, hl = [len(r) for r in refs], [len(h) for h in hyps]
+    flat_r = torch.tensor([int(t) for r in refs for t in r] or [0], dtype=torch.int32).to(dev)
+    flat_h = torch.tensor([int(t) for h in hyps for t in h] or [0], dtype=torch.int32).to(dev)
+    out = torch.full((n * 4 + 1,), -1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _e._check(_e.load_library().vx_edit_distance(n, flat_r.data_ptr(), (C.c_int32 * n)(*rl), flat_h.data_ptr(), (C.c_int32 * n)(*hl),
+                                                     out.data_ptr(), _e.current_stream_ptr(dev)))
+    assert int(out[-1]) == -1, "a write outside the output"
+    return out[:-1].reshape(n, 4).cpu()
+
+
+def normalize_text(text: str) -> str:
+    """The rule both sides of an error rate go through: upper-case; letters, digits and apostrophes are kept; everything else
+    becomes a space; runs of spaces collapse and the ends are trimmed."""
+    return " ".join("".join(ch if (ch.isalnum() or ch == "'") else " " for ch in str(text).upper()).split())
+
+
+def _error_rate(ref_units: List[list], hyp_units: List[list], device) -> ErrorRate:
+    table: Dict[object, int] = {}
+    enc = lambda seq: [table.setdefault(u, len(table)) for u in seq]  # noqa: E731  ids over the union of both sides
+    refs, hyps = [enc(r) for r in ref_units], [enc(h) for h in hyp_units]
+    pairs: List[PairErrors] = []
+    for i in range(0, len(refs), 64):
+        for (dist, s, d, ins), r in zip(edit_distance(refs[i:i + 64], hyps[i:i + 64], device).tolist(), refs[i:i + 64]):
+            pairs.append(PairErrors(dist, s, d, ins, len(r)))
+    total = sum(p.ref_len for p in pairs)
+    return ErrorRate(sum(p.distance for p in pairs) / total if total else float("nan"), pairs)
+
+
+def word_error_rate(ref_texts: Sequence[str], hyp_texts: Sequence[str], device="cuda") -> ErrorRate:
+    """WER of hypotheses against references (a string each, or equally long lists): both sides through `normalize_text`, split at
+    spaces, words mapped to ids over the union of both sides, the distance on the device.  Per pair S / D / I / N and the rate
+    (S + D + I) / N (`nan` when N = 0); the corpus rate is (sum S + sum D + sum I) / sum N, a pair with N = 0 counted in the sums."""
+    ref_texts = [ref_texts] if isinstance(ref_texts, str) else list(ref_texts)
+    hyp_texts = [hyp_texts] if isinstance(hyp_texts, str) else list(hyp_texts)
+    return _error_rate([normalize_text(t).split() for t in ref_texts], [normalize_text(t).split() for t in hyp_texts], device)
+
+
+def char_error_rate(ref_texts: Sequence[str], hyp_texts: Sequence[str], device="cuda") -> ErrorRate:
+    """CER: as `word_error_rate` over the characters of the normalised texts, the single spaces between words included."""
+    ref_texts = [ref_texts] if isinstance(ref_texts, str) else list(ref_texts)
+    hyp_texts = [hyp_texts] if isinstance(hyp_texts, str) else list(hyp_texts)
+    return _error_rate([list(normalize_text(t)) for t in ref_texts], [list(normalize_text(t)) for t in hyp_texts], device)
+
+
+def recognition_error(text, wav, recognizer: SpeechRecognizer, sr: int = 24000, normalize: bool = False, unit: str = "word") -> ErrorRate:
+    """The WER (`unit="word"`) or CER (`unit="char"`) of synthesised utterance(s) against the text they were given: `wav` goes
+    through `recognizer.recognize`, the transcript and `text` through the error rate.  On synthetic weights the number means
+    nothing."""
+    texts = [text] if isinstance(text, str) else list(text)
+    hyps = [t.text for t in recognizer.recognize(wav, sr=sr, normalize=normalize)]
+    assert len(hyps) == len(texts), "one text per waveform"
+    fn = {"word": word_error_rate, "char": char_error_rate}[unit]
+    return fn(texts, hyps, recognizer.device)

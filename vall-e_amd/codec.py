@@ -519,6 +519,19 @@ class EncodecDecoder:
         rec = self.decode(self.encode(wav, n_q))
         return encoder.similarity(wav.reshape(-1), rec.reshape(-1), sr=SAMPLE_RATE, normalize=normalize)[0]
 
+    def roundtrip_wer(self, wav: torch.Tensor, text: str, recognizer, n_q: Optional[int] = None, sr: Optional[int] = None,
+                      normalize: bool = False, unit: str = "word"):
+        """The word error rate (`asr.recognition_error`, an `asr.ErrorRate`; `unit="char"`: the character error rate) of
+        decode(encode(waveform)) against `text`, what the waveform says: whether the codec keeps the words.  `wav` and `sr` as in
+        `encode`; the reconstruction goes to the recogniser at 24 kHz and is resampled to 16 kHz there.  On synthetic weights (the
+        codec's or the recogniser's) the number means nothing.  Needs `encoder=True`."""
+        from .asr import recognition_error
+
+        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
+            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        rec = self.decode(self.encode(wav, n_q))
+        return recognition_error(text, rec.reshape(-1), recognizer, sr=SAMPLE_RATE, normalize=normalize, unit=unit)
+
 
 class AudioTokenizer:
     """The reference's `valle.data.tokenizer.AudioTokenizer` (tokenizer.py:238-254) on the GPU: `encode(wav)` with wav (B, 1, L)

@@ -1,6 +1,7 @@
 // Speaker encoder (WavLM / Wav2Vec2 x-vector network) behind the C ABI (include/vallex.h, vx_spk_*): the weight table and its
 // packing for the row GEMM, the per-head bias table, the staging of a ragged call (CallStage, host.hpp), the workspace and the
-// launches of spk_kernels.hpp.  A translation unit and a handle of its own, like ganvoc.hip: no other unit sees these kernels.
+// launches of spk_kernels.hpp.  A translation unit and a handle of its own, like ganvoc.hip; the packing and the launches of the kernels
+// the recogniser (asr.hip) runs too are in spk_host.hpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -14,28 +15,12 @@
 #include <vector>
 
 #undef VX_STAMPS  // the in-kernel stamps write device globals of engine.hip's unit, out of this unit's reach
-#include "host.hpp"
-#include "spk_kernels.hpp"
+#include "spk_host.hpp"
 
 using namespace vx;
 
 namespace {
 
-struct HostW {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-  bool set = false;
-};
-
-// One row GEMM: the packed weight [groups][N][K] and bias as offsets into the device block, and the gather rule.
-struct SpkLin {
-  size_t w = 0, b = 0;
-  bool has_bias = false;
-  int C = 0, taps = 1, stride = 1, off0 = 0, step = 1, N = 0, groups = 1;
-};
-struct SpkNorm {
-  size_t w = 0, b = 0;
-};
 struct SpkLayer {
   SpkLin qkv, out, ff1, ff2;
   SpkNorm ln1, ln2;
@@ -97,105 +82,10 @@ long tdnn_frames(const vx_spk_config& c, long T, int upto) {
   return T;
 }
 
-void add_key(vx_spk* g, const std::string& key, std::vector<int64_t> shape) {
-  HostW t;
-  t.shape = std::move(shape);
-  g->w[key] = std::move(t);
-}
-
-size_t push(std::vector<float>& p, const std::vector<float>& v) {
-  while (p.size() % 4) p.push_back(0.f);  // every tensor starts on a 16-byte boundary
-  const size_t at = p.size();
-  p.insert(p.end(), v.begin(), v.end());
-  return at;
-}
-
-SpkNorm pack_norm(vx_spk* g, const std::string& name) {
-  SpkNorm n;
-  n.w = push(g->packed, g->w[name + ".weight"].data);
-  n.b = push(g->packed, g->w[name + ".bias"].data);
-  return n;
-}
-
-// Linear (N, K): the torch layout is the GEMM's.
-SpkLin pack_linear(vx_spk* g, const std::string& name, int N, int K) {
-  SpkLin l;
-  l.w = push(g->packed, g->w[name + ".weight"].data);
-  l.b = push(g->packed, g->w[name + ".bias"].data);
-  l.has_bias = true;
-  l.C = K; l.N = N;
-  return l;
-}
-
-// Conv1d (O, Cg, k) in `groups` groups: W[g][n][j * Cg + c] = w[g * (O / groups) + n][c][j].
-SpkLin pack_conv(vx_spk* g, const std::string& name, int O, int Cg, int k, int groups, bool bias) {
-  const HostW& w = g->w[name + ".weight"];
-  std::vector<float> p((size_t)O * Cg * k);
-  for (int o = 0; o < O; ++o)
-    for (int c = 0; c < Cg; ++c)
-      for (int j = 0; j < k; ++j) p[((size_t)o * k + j) * Cg + c] = w.data[((size_t)o * Cg + c) * k + j];
-  SpkLin l;
-  l.w = push(g->packed, p);
-  l.has_bias = bias;
-  if (bias) l.b = push(g->packed, g->w[name + ".bias"].data);
-  l.C = Cg; l.taps = k; l.N = O / groups; l.groups = groups;
-  return l;
-}
-
-int launch_gemm(const SpkGemmArgs& a, int groups, hipStream_t s) {
-  if (a.M <= 0) return VX_OK;
-  // float4 gathers: every operand address a multiple of 16 bytes (the caller's emb_out is the classifier's operand)
-  const bool vec = a.C % 16 == 0 && a.ldx % 4 == 0 && a.xoff % 4 == 0 && a.xgs % 4 == 0 && (uintptr_t)a.x % 16 == 0;
-  if (a.N <= 32) {
-    dim3 g((unsigned)((a.M + 127) / 128), (unsigned)((a.N + 31) / 32), (unsigned)groups);
-    if (vec) spk_gemm_rows<4, 1, true><<<g, 256, 0, s>>>(a);
-    else spk_gemm_rows<4, 1, false><<<g, 256, 0, s>>>(a);
-  } else {
-    dim3 g((unsigned)((a.M + 63) / 64), (unsigned)((a.N + 63) / 64), (unsigned)groups);
-    if (vec) spk_gemm_rows<2, 2, true><<<g, 256, 0, s>>>(a);
-    else spk_gemm_rows<2, 2, false><<<g, 256, 0, s>>>(a);
-  }
-  HIPC(hipGetLastError());
-  return VX_OK;
-}
-
-struct CallCtx {
+struct CallCtx : SpkCall {
   const vx_spk* g;
-  const float* W;
   float* ws;
-  const int* seg;  // device tables [n_tables][MB + 1]
-  int MB, n;
-  hipStream_t s;
-  const int* table(int i) const { return seg + (size_t)i * (MB + 1); }
 };
-
-// out rows (table t_out, M of them) = act(l(x rows of table t_in)); seg tables null: flat.
-int run_lin(const CallCtx& x, const SpkLin& l, const float* in, int ldx, float* out, long M, int act, int t_out = -1, int t_in = -1) {
-  SpkGemmArgs a{};
-  a.x = in; a.ldx = ldx; a.xoff = 0; a.xgs = l.groups > 1 ? l.C : 0;
-  a.C = l.C; a.taps = l.taps; a.stride = l.stride; a.off0 = l.off0; a.step = l.step;
-  a.W = x.W + l.w; a.bias = l.has_bias ? x.W + l.b : nullptr;
-  a.out = out; a.ldo = l.N * l.groups; a.act = act;
-  a.M = M; a.N = l.N; a.K = l.taps * l.C;
-  a.seg_out = t_out >= 0 ? x.table(t_out) : nullptr;
-  a.seg_in = t_in >= 0 ? x.table(t_in) : nullptr;
-  a.nseg = x.n;
-  return launch_gemm(a, l.groups, x.s);
-}
-
-int run_ln(const CallCtx& x, const SpkNorm& nm, const float* a, const float* b, float* y, long M, int d, float* sum = nullptr,
-           float lw = 0.f, int first = 0) {
-  spk_layernorm<<<(unsigned)((M + 3) / 4), 256, 0, x.s>>>(a, b, x.W + nm.w, x.W + nm.b, y, sum, lw, first, M, d, x.g->cfg.layer_norm_eps);
-  HIPC(hipGetLastError());
-  return VX_OK;
-}
-
-template <int HD>
-int launch_attn(const SpkAttnArgs& a, unsigned tiles, hipStream_t s) {
-  spk_attention<HD><<<dim3(tiles, (unsigned)a.H), SPK_ATT_WAVES * 64, 0, s>>>(a);
-  HIPC(hipGetLastError());
-  return VX_OK;
-}
 
 void make_plan(vx_spk* g) {
   const vx_spk_config& c = g->cfg;
@@ -292,9 +182,7 @@ int run_call(const CallCtx& x, const float* const* wav, const int* n_samples_dev
   float* sum = wsum ? ws + p.sum : nullptr;
   VXC(run_ln(x, g->enc_ln, ws + p.x0, ws + p.tmp, hid(0), M, d, sum, wsum ? g->lw[0] : 0.f, 1));
   // ---- encoder layers
-  long qtiles = 0;
   const int* et = hseg + (size_t)te * (MB + 1);
-  for (int i = 0; i < n; ++i) qtiles += ((long)et[i + 1] - et[i] + 32 * SPK_ATT_WAVES - 1) / (32 * SPK_ATT_WAVES);
   const bool wavlm = c.attention == VX_SPK_WAVLM;
   for (int l = 0; l < c.layers; ++l) {
     const SpkLayer& L = g->layers[l];
@@ -305,12 +193,8 @@ int run_call(const CallCtx& x, const float* const* wav, const int* n_samples_dev
       HIPC(hipGetLastError());
     }
     VXC(run_lin(x, L.qkv, h, d, ws + p.qkv, M, SPK_ACT_NONE));
-    SpkAttnArgs a{};
-    a.qkv = ws + p.qkv; a.gate = wavlm ? gate : nullptr; a.table = wavlm ? x.W + g->table : nullptr; a.out = ws + p.att;
-    a.seg = x.table(te); a.nseg = n; a.H = H; a.d = d; a.Tmax = g->Tmax; a.scale = (float)(1.0 / sqrt((double)g->hd));
-    if (g->hd == 16) VXC(launch_attn<16>(a, (unsigned)qtiles, x.s));
-    else if (g->hd == 32) VXC(launch_attn<32>(a, (unsigned)qtiles, x.s));
-    else VXC(launch_attn<64>(a, (unsigned)qtiles, x.s));
+    VXC(run_attn(x, x.table(te), et, ws + p.qkv, wavlm ? gate : nullptr, wavlm ? x.W + g->table : nullptr, ws + p.att, H, d, g->hd,
+                 g->Tmax));
     VXC(run_lin(x, L.out, ws + p.att, d, ws + p.tmp, M, SPK_ACT_NONE));
     VXC(run_ln(x, L.ln1, h, ws + p.tmp, ws + p.mid, M, d));
     VXC(run_lin(x, L.ff1, ws + p.mid, d, ws + p.ff, M, SPK_ACT_GELU));
@@ -451,26 +335,7 @@ extern "C" void vx_spk_destroy(vx_spk* g) {
 }
 
 extern "C" int vx_spk_set_weight(vx_spk* g, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
-  if (!g || !key || !data || !shape) return fail(VX_ERR_ARG, "vx_spk_set_weight: null argument");
-  if (g->finalized) return fail(VX_ERR_STATE, "vx_spk_set_weight after vx_spk_finalize");
-  auto it = g->w.find(key);
-  if (it == g->w.end()) return fail(VX_ERR_WEIGHTS, "unknown key %s", key);
-  HostW& t = it->second;
-  bool same = ndim == (int32_t)t.shape.size();
-  size_t n = 1;
-  for (size_t i = 0; same && i < t.shape.size(); ++i) {
-    same = shape[i] == t.shape[i];
-    n *= (size_t)t.shape[i];
-  }
-  if (!same) {
-    std::string want, got;
-    for (int64_t v : t.shape) want += (want.empty() ? "" : ", ") + std::to_string(v);
-    for (int i = 0; i < ndim && i < 8; ++i) got += (got.empty() ? "" : ", ") + std::to_string(shape[i]);
-    return fail(VX_ERR_WEIGHTS, "%s: shape (%s), expected (%s)", key, got.c_str(), want.c_str());
-  }
-  t.data.assign(data, data + n);
-  t.set = true;
-  return VX_OK;
+  return set_weight(g, "vx_spk", key, data, shape, ndim);
 }
 
 extern "C" int vx_spk_set_buckets(vx_spk* g, const int32_t* idx, int32_t n) {
@@ -619,7 +484,7 @@ extern "C" int vx_spk_embed(vx_spk* g, int32_t n, const float* const* wav, const
   g->last_stream = s;
   VXC(dv.stage.upload(dv.stage.bytes, s));
   CallCtx x{};
-  x.g = g; x.W = dv.w.get(); x.ws = dv.ws.get(); x.MB = (int)MB; x.n = n; x.s = s;
+  x.g = g; x.eps = c.layer_norm_eps; x.W = dv.w.get(); x.ws = dv.ws.get(); x.MB = (int)MB; x.n = n; x.s = s;
   x.seg = dv.stage.dev<const int>(MB * sizeof(void*) + MB * sizeof(int));
   VXC(run_call(x, dv.stage.dev<const float* const>(), dv.stage.dev<const int>(MB * sizeof(void*)), hseg, flags, emb_out, logits_out));
   const int rc = dv.stage.finish(s);

@@ -23,6 +23,9 @@
 //   spk_layernorm     LayerNorm(a + b) with the optional running weighted layer sum folded in (first layer stores, later add).
 //   spk_pool          mean and unbiased standard deviation over an utterance's frames, fp64, frames in ascending order.
 //   spk_cosine        cosine of pairs of embeddings, fp64 sums in a fixed order.
+//
+// Two translation units include this header (spk.hip, and asr.hip through asr_kernels.hpp), so every kernel is `static`: each unit
+// carries and launches its own copy and the library has no duplicate host symbol.
 #pragma once
 #include "common.hpp"
 
@@ -62,7 +65,7 @@ __device__ __forceinline__ int spk_find_tile(const int* __restrict__ seg, int ns
 
 // ---- input normalisation -----------------------------------------------------------------------------------------------------
 // stats[2 u] = mean, stats[2 u + 1] = 1 / sqrt(var + 1e-7), biased variance.  One workgroup of 256 per utterance.
-__global__ __launch_bounds__(256) void spk_wave_stats(const float* const* __restrict__ wav, const int* __restrict__ n_samples,
+static __global__ __launch_bounds__(256) void spk_wave_stats(const float* const* __restrict__ wav, const int* __restrict__ n_samples,
                                                       float* __restrict__ stats) {
   __shared__ double S[256], Q[256];
   const int u = blockIdx.x, tid = threadIdx.x;
@@ -110,7 +113,7 @@ struct SpkConv0Args {
 // The tile's samples in LDS and this thread's channel weights; v(t) is the convolution output of local frame t0 + t.
 // grid.x >= the tiles of the call (ceil(len / TT) per segment), grid.y = ceil(C / 64); 256 threads = 64 channels x 4 frame groups.
 template <bool APPLY>
-__global__ __launch_bounds__(256) void spk_conv0(const SpkConv0Args a) {
+static __global__ __launch_bounds__(256) void spk_conv0(const SpkConv0Args a) {
   constexpr int TT = SPK_C0_TT;
   extern __shared__ float X[];  // (TT - 1) stride + k samples
   __shared__ double R[2][4][64];
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(256) void spk_conv0(const SpkConv0Args a) {
 }
 
 // One thread per (utterance, channel): the utterance's tiles in ascending order.  grid = (ceil(C / 256), nseg).
-__global__ __launch_bounds__(256) void spk_conv0_reduce(const SpkConv0Args a) {
+static __global__ __launch_bounds__(256) void spk_conv0_reduce(const SpkConv0Args a) {
   const int c = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
   if (c >= a.C) return;
   long first = 0;
@@ -201,7 +204,7 @@ struct SpkGemmArgs {
 // BM = 32 * WM rows x BN = 32 * WN columns per workgroup of WM * WN waves, BK = 16; LDS tiles [row][BK + 1].
 // VEC: C, ldx, xoff and xgs are multiples of 4 and C of 16, so a K chunk lies in one tap and loads as float4.
 template <int WM, int WN, bool VEC>
-__global__ __launch_bounds__(WM * WN * 64) void spk_gemm_rows(const SpkGemmArgs a) {
+static __global__ __launch_bounds__(WM * WN * 64) void spk_gemm_rows(const SpkGemmArgs a) {
   constexpr int BM = 32 * WM, BN = 32 * WN, BK = 16, LD = BK + 1, NT = WM * WN * 64;
   constexpr int A_V = BM * BK / 4 / NT > 0 ? BM * BK / 4 / NT : 1;
   constexpr int B_V = BN * BK / 4 / NT > 0 ? BN * BK / 4 / NT : 1;
@@ -336,7 +339,7 @@ __global__ __launch_bounds__(WM * WN * 64) void spk_gemm_rows(const SpkGemmArgs 
 // ---- gate --------------------------------------------------------------------------------------------------------------------
 // gate[row][h] = a (b const_h - 1) + 2, a = sigmoid(sum p[0:4]), b = sigmoid(sum p[4:8]), p = Wg x[row][h hd : (h + 1) hd] + bg.
 // One thread per (row, head).
-__global__ __launch_bounds__(256) void spk_gate(const float* __restrict__ x, const float* __restrict__ Wg, const float* __restrict__ bg,
+static __global__ __launch_bounds__(256) void spk_gate(const float* __restrict__ x, const float* __restrict__ Wg, const float* __restrict__ bg,
                                                 const float* __restrict__ cst, float* __restrict__ gate, long M, int H, int hd) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= M * H) return;
@@ -376,7 +379,7 @@ struct SpkAttnArgs {
 // lie: register r of lane half h is key (r & 3) + 8 (r >> 2) + 4 h, so the A operand of that step is V[that key][dim = lane & 31].
 // grid = (query tiles counted per segment, H).
 template <int HD>
-__global__ __launch_bounds__(SPK_ATT_WAVES * 64) void spk_attention(const SpkAttnArgs a) {
+static __global__ __launch_bounds__(SPK_ATT_WAVES * 64) void spk_attention(const SpkAttnArgs a) {
   constexpr int QT = 32 * SPK_ATT_WAVES, KT = 32, LDK = HD + 1, DB = (HD + 31) / 32, LDV = 32 * DB + 1;
   typedef float f32x16 __attribute__((ext_vector_type(16)));
   __shared__ float Ks[KT * LDK];
@@ -467,7 +470,7 @@ __global__ __launch_bounds__(SPK_ATT_WAVES * 64) void spk_attention(const SpkAtt
 // y = LayerNorm(a + b) (b may be null); with `sum`: sum = (first ? 0 : sum) + lw * y, and with lw0_src != null the layer-0 term
 // is not needed here (the host runs the first fold on hidden state 0).  One wave per row; the row is read twice (mean, then the
 // squared deviations); the lanes' strided partial sums are joined by a fixed butterfly.
-__global__ __launch_bounds__(256) void spk_layernorm(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ w,
+static __global__ __launch_bounds__(256) void spk_layernorm(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ w,
                                                      const float* __restrict__ beta, float* __restrict__ y, float* __restrict__ sum,
                                                      float lw, int first, long M, int d, float eps) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -498,7 +501,7 @@ __global__ __launch_bounds__(256) void spk_layernorm(const float* __restrict__ a
 // ---- statistics pooling ------------------------------------------------------------------------------------------------------
 // pooled[u][c] = mean, pooled[u][C + c] = unbiased standard deviation over the utterance's rows, fp64, rows in ascending order.
 // grid = (ceil(C / 256), nseg).
-__global__ __launch_bounds__(256) void spk_pool(const float* __restrict__ x, float* __restrict__ pooled, const int* __restrict__ seg, int C) {
+static __global__ __launch_bounds__(256) void spk_pool(const float* __restrict__ x, float* __restrict__ pooled, const int* __restrict__ seg, int C) {
   const int c = blockIdx.x * 256 + threadIdx.x, u = blockIdx.y;
   if (c >= C) return;
   const long lo = seg[u], n = (long)seg[u + 1] - lo;
@@ -516,7 +519,7 @@ __global__ __launch_bounds__(256) void spk_pool(const float* __restrict__ x, flo
 
 // ---- cosine ------------------------------------------------------------------------------------------------------------------
 // out[p] = a_p . b_p / max(|a_p| |b_p|, 1e-8); one wave per pair, lane-strided fp64 sums joined by a fixed butterfly.
-__global__ __launch_bounds__(64) void spk_cosine(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int dim) {
+static __global__ __launch_bounds__(64) void spk_cosine(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int dim) {
   const long p = blockIdx.x;
   const int lane = threadIdx.x;
   double ab = 0.0, aa = 0.0, bb = 0.0;

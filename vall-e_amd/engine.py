@@ -84,6 +84,19 @@ VX_SPK_KEEP_TAPS = 1   # vx_spk_config.flags
 VX_SPK_NORMALIZE = 1   # vx_spk_embed flags
 
 
+class VxAsrConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "hidden", "layers", "heads", "ffn", "n_conv")] + \
+               [(n, C.c_int32 * 8) for n in ("conv_dim", "conv_kernel", "conv_stride")] + \
+               [(n, C.c_int32) for n in ("conv_bias", "pos_kernel", "pos_groups", "vocab", "blank", "feat_extract_norm",
+                                         "do_stable_layer_norm", "feat_proj_layer_norm", "add_adapter", "conv_pos_batch_norm",
+                                         "activation")] + \
+               [("layer_norm_eps", C.c_float), ("max_batch", C.c_int32), ("max_samples", C.c_int32), ("flags", C.c_int32)]
+
+
+VX_ASR_KEEP_TAPS = 1   # vx_asr_config.flags
+VX_ASR_NORMALIZE = 1   # vx_asr_recognize flags
+
+
 class VxDtwConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "dim", "n_ceps", "max_frames", "max_batch")]
 
@@ -297,6 +310,20 @@ _SIGS = {
     "vx_spk_similarity": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vx_spk_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),
     "vx_spk_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    # CTC recogniser, greedy decode and edit distance (asr.SpeechRecognizer)
+    "vx_asr_create": (C.c_int, [C.POINTER(VxAsrConfig), C.POINTER(C.c_void_p)]),
+    "vx_asr_destroy": (None, [C.c_void_p]),
+    "vx_asr_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "vx_asr_finalize": (C.c_int, [C.c_void_p]),
+    "vx_asr_frames": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "vx_asr_min_samples": (C.c_int64, [C.c_void_p]),
+    "vx_asr_recognize": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vx_asr_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),
+    "vx_asr_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    "vx_ctc_greedy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vx_edit_distance": (C.c_int, [C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so
