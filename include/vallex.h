@@ -1283,6 +1283,49 @@ int vx_ctc_greedy(const float* logits, int32_t vocab, int32_t blank, int32_t n, 
 int vx_edit_distance(int32_t n, const int32_t* ref, const int32_t* ref_len, const int32_t* hyp, const int32_t* hyp_len, int32_t* out,
                      void* stream);
 
+/* ---- CTC forced alignment and text likelihood: a known text against the logits of the recogniser above ----------------------------
+ * Two questions about a text that is already known: how likely it is under the audio (the forward algorithm), and where in the
+ * audio each of its tokens sits (the Viterbi path through the same lattice, the rule of torchaudio's forced_align).
+ * Inputs and the extended sequence.  Per utterance: logits x (T, V) fp32, a blank id b, target ids y[0..L), each in [0, V) and not
+ * b.  The extended sequence z has S = 2 L + 1 states, z[2k] = b and z[2k+1] = y[k].  lse[t] = m + log sum_c exp(x[t][c] - m) with
+ * m = max_c x[t][c] and the sum in fp64, as step 6 above takes it.  e[t][s] = (double)x[t][z[s]] - lse[t].  State s may be entered
+ * from s and from s - 1, and from s - 2 when z[s] != b and z[s] != z[s-2].
+ * Likelihood.  a[0][0] = e[0][0], a[0][1] = e[0][1], the rest -inf; a[t][s] = e[t][s] + logaddexp over the allowed predecessors at
+ * t - 1, in fp64; nll = -logaddexp(a[T-1][S-1], a[T-1][S-2]), for L = 0 nll = -a[T-1][0].  An infeasible pair has nll = +inf and
+ * feasible = 0, never a NaN: a pair is infeasible when T < L + #{k : y[k] == y[k-1]}, or when T = 0 with L > 0.  T = 0 with L = 0
+ * gives nll = 0 (and path_logprob = 0).
+ * Best path.  The same recurrence with max, on the raw logits: v[t][s] = max(...) + (double)x[t][z[s]] (lse[t] is constant over the
+ * states of a frame, so it does not move the arg-max): only IEEE additions and comparisons in fp64, so that another
+ * implementation of this text agrees cell for cell.  Among equal predecessors the first in the order s, s - 1, s - 2 is taken; at
+ * the end S - 1 is taken before S - 2.
+ * Reported.  path_logprob = v_end - sum_t lse[t]; per frame the index k of the target token it emits, or -1 for blank; per target
+ * token its frames [start, end) and score = the mean of e over them, summed in fp64 in frame order and rounded to fp32.  For an
+ * infeasible utterance the frame tokens and spans are -1, the scores -inf, nll = +inf and path_logprob = -inf.
+ * Kernel: one workgroup per utterance, a ragged batch in one launch; a and v are double-buffered fp64 rows in LDS with one barrier
+ * per frame; states outside the reachable band (s < 2 t + 2 and S - 1 - s < 2 (T - t)) are not computed; the back-pointers are 2
+ * bits per cell in a workspace, and the backtrace, the spans and the scores run on the device.  No atomics: every utterance is
+ * bitwise what it is alone, and two identical calls give the same bits.  Limits: L <= 1000 targets per utterance (four fp64 rows
+ * of 2 L + 3 cells in 64 KiB of LDS; 20 s of audio are 999 frames, and a longer text cannot be feasible in them), any T, and
+ * frames x states / 4 bytes of back-pointers summed over the call <= 2 GiB. */
+/* On the current device.  logits DEVICE fp32 (sum frames[i], vocab), the utterances' rows concatenated; frames, targets (the
+ * utterances' ids concatenated) and target_len HOST int32.  nll_out, path_logprob_out DEVICE fp64 (n); frame_token_out DEVICE int32
+ * (sum frames[i]); tok_start_out, tok_end_out DEVICE int32 and tok_score_out DEVICE fp32 (sum target_len[i]); feasible_out DEVICE
+ * int32 (n).  Any output may be null: without nll_out the sum is skipped, without all of path_logprob_out .. tok_score_out the max.
+ * Checked before any HIP call: null logits / frames / target_len, no output at all, n < 1, vocab < 1, blank outside [0, vocab), a
+ * negative count, null targets with a positive count, a target id equal to blank or outside [0, vocab) (the message states the
+ * utterance, the position and the id) -> VX_ERR_ARG; a feasible utterance above a limit -> VX_ERR_CAPACITY naming the limit.
+ * Allocates its scratch and waits for `stream` before it returns. */
+int vx_falign(const float* logits, int32_t vocab, int32_t blank, int32_t n, const int32_t* frames, const int32_t* targets,
+              const int32_t* target_len, double* nll_out, double* path_logprob_out, int32_t* frame_token_out, int32_t* tok_start_out,
+              int32_t* tok_end_out, float* tok_score_out, int32_t* feasible_out, void* stream);
+/* The same on the logits the last vx_asr_recognize on `h` left on the device (frames, vocab and blank are that call's and the
+ * handle's): error rate and timestamps from one pass of the network, without a host round trip of the logits.  No previous call,
+ * or n other than that call's -> VX_ERR_STATE; the other checks as above.  The scratch is the handle's and only grows;
+ * vx_asr_get_timings' workspace figure includes it.  Waits for `stream` before it returns. */
+int vx_falign_asr(vx_asr* h, int32_t n, const int32_t* targets, const int32_t* target_len, double* nll_out, double* path_logprob_out,
+                  int32_t* frame_token_out, int32_t* tok_start_out, int32_t* tok_end_out, float* tok_score_out, int32_t* feasible_out,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_T
            "STFTConfig", "MultiResolutionSTFT", "MSTFTResult", "mstft_distance", "copy_synthesis_distance",
            "SpeakerEncoder", "SpeakerConfig", "speaker_similarity",
            "SpeechRecognizer", "RecognizerConfig", "Transcript", "ErrorRate", "edit_distance", "word_error_rate", "char_error_rate",
-           "recognition_error"]
+           "recognition_error", "TextAlignment", "TextScore", "ctc_forced_align", "ctc_nll", "text_likelihood"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -47,7 +47,7 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
 
         return getattr(spk, name)
     if name in ("SpeechRecognizer", "RecognizerConfig", "Transcript", "ErrorRate", "edit_distance", "word_error_rate", "char_error_rate",
-                "recognition_error"):
+                "recognition_error", "TextAlignment", "TextScore", "ctc_forced_align", "ctc_nll", "text_likelihood"):
         from . import asr
 
         return getattr(asr, name)

@@ -12,7 +12,14 @@ Two flavours, chosen by the checkpoint's config: group / post-norm (`wav2vec2-ba
 tests/asr_ref.py, which tests/test_asr_cpu.py pins against the two `transformers` classes.  Nothing has been recognised on trained
 weights: no checkpoint is available where this is built, and on synthetic weights the error rate means nothing.  The S / D / I
 counts are those of the stated tie-break (match or substitution, then deletion, then insertion); only their sum, the distance,
-is independent of it, so parity with another aligner's counts (jiwer's, say) is by definition only."""
+is independent of it, so parity with another aligner's counts (jiwer's, say) is by definition only.
+
+A text that is already known is scored and placed against the same logits (`vx_falign`, csrc/falign_kernels.hpp): the CTC
+likelihood `-log p(text | audio)` by the forward algorithm, and per character and word the frames of the best path
+(`torchaudio.functional.forced_align`'s rule; that package is not a dependency, so parity with its tie-break is by definition only):
+
+    al = rec.align([synth_wav], [text], sr=24000)[0]         # TextAlignment: .words[i] = (word, start_s, end_s, score), .chars, .nll
+    nll = text_likelihood(text, synth_wav, rec)[0].nll_per_char"""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,7 +27,7 @@ import dataclasses
 import json
 import math
 import re
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
@@ -30,6 +37,7 @@ from .spk import canonical_state_dict as _canonical
 SAMPLE_RATE = 16000
 HEAD_DIMS = (16, 32, 64)
 EDIT_MAX_LEN = 2048  # tokens per side of a pair (csrc/asr_kernels.hpp)
+FALIGN_MAX_TARGETS = 1000  # target tokens per utterance of an alignment (csrc/falign_kernels.hpp)
 
 
 @dataclasses.dataclass
@@ -349,7 +357,7 @@ class SpeechRecognizer:
                                                      logprob_ptr, logits_ptr, stream))
 
     @torch.no_grad()
-    def _run(self, wavs, sr, normalize, want_logits):
+    def _run(self, wavs, sr, normalize, want_logits, after_chunk=None):
         ws = self._prepare(wavs, sr)
         results, logits = [], []
         V = int(self.config.vocab_size)
@@ -365,6 +373,8 @@ class SpeechRecognizer:
             with torch.cuda.device(self.device):
                 self._recognize_raw([w.data_ptr() for w in chunk], [w.numel() for w in chunk], normalize, tok.data_ptr(), frm.data_ptr(),
                                     cnt.data_ptr(), lp.data_ptr(), None if lg is None else lg.data_ptr())
+                if after_chunk is not None:  # the call's logits are still the handle's
+                    after_chunk(i, T)
             tok, frm, cnt, lp = tok.cpu(), frm.cpu(), cnt.cpu().tolist(), lp.cpu().tolist()
             o = 0
             for u, t in enumerate(T):
@@ -394,6 +404,76 @@ class SpeechRecognizer:
         _e._check(_e.load_library().vx_asr_read(self._handle(), name.encode(), int(utt), out.data_ptr(), out.numel()))
         return out
 
+    # ---- a known text against the audio -------------------------------------------------------------
+    @property
+    def seconds_per_frame(self) -> float:
+        """The hop of the encoder's frames: the product of the convolution strides over 16 kHz (20 ms at the default strides)."""
+        return math.prod(int(s) for s in self.config.conv_stride) / SAMPLE_RATE
+
+    def text_to_ids(self, text: str) -> List[int]:
+        """`normalize_text`, then one id per character, a space becoming the word delimiter.  A character the vocabulary lacks
+        raises ValueError naming it: nothing is dropped silently."""
+        ids = []
+        for pos, ch in enumerate(normalize_text(text)):
+            tok = self.word_delimiter if ch == " " else ch
+            if tok not in self.vocab or self.vocab[tok] == self.blank_id:
+                raise ValueError(f"character {ch!r} (position {pos} of {normalize_text(text)!r}) is not in the recogniser's vocabulary")
+            ids.append(self.vocab[tok])
+        return ids
+
+    def _falign_raw(self, targets: Sequence[Sequence[int]], nll_ptr, plp_ptr, ftok_ptr, start_ptr, end_ptr, score_ptr, feas_ptr):
+        """vx_falign_asr on raw pointers: the logits are those of the last `recognize` (the argument checks run before any device
+        work)."""
+        n = len(targets)
+        flat = [int(t) for y in targets for t in y]
+        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
+        _e._check(_e.load_library().vx_falign_asr(self._handle(), n, (C.c_int32 * max(len(flat), 1))(*flat),
+                                                  (C.c_int32 * max(n, 1))(*[len(y) for y in targets]), nll_ptr, plp_ptr, ftok_ptr, start_ptr,
+                                                  end_ptr, score_ptr, feas_ptr, stream))
+
+    @torch.no_grad()
+    def _align_ids(self, wavs, targets: Sequence[Sequence[int]], sr, normalize, path: bool):
+        """Recognises, then aligns every chunk on the logits the call left on the device -> (transcripts, raw alignments)."""
+        raws: List[CTCAlignment] = []
+
+        def after_chunk(first, T):
+            ys = targets[first:first + len(T)]
+            out = _FalignOut(len(T), sum(T), sum(len(y) for y in ys), self.device, path)
+            self._falign_raw(ys, *out.pointers())
+            raws.extend(out.split(T, [len(y) for y in ys]))
+
+        ws = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
+        assert len(ws) == len(targets), "one text per waveform"
+        return self._run(ws, sr, normalize, False, after_chunk)[0], raws
+
+    def align(self, wavs, texts: Union[str, Sequence[str]], sr: int = 24000, normalize: bool = False) -> List["TextAlignment"]:
+        """Where in each waveform the characters and words of its known text are, and how likely the text is: one `TextAlignment`
+        per utterance.  One pass of the network serves the transcript and the alignment; the logits never leave the device.  The
+        times are frames x `seconds_per_frame`; an infeasible pair (more characters than frames) has `feasible = False`,
+        `nll = inf` and no spans.  Nothing is validated on trained weights."""
+        texts = [texts] if isinstance(texts, str) else list(texts)
+        ids = [self.text_to_ids(t) for t in texts]
+        hyps, raws = self._align_ids(wavs, ids, sr, normalize, True)
+        inv, spf = self.id_to_token, self.seconds_per_frame
+        out = []
+        for text, y, hyp, r in zip(texts, ids, hyps, raws):
+            chars = []
+            if r.feasible:
+                for k, t in enumerate(y):
+                    tok = inv[t]
+                    chars.append(CharSpan(" " if tok == self.word_delimiter else tok, r.starts[k] * spf, r.ends[k] * spf, r.scores[k]))
+            out.append(TextAlignment(normalize_text(text), hyp, chars, group_words(chars), r.nll, r.nll / max(len(y), 1), r.path_logprob,
+                                     r.feasible, r.frame_tokens))
+        return out
+
+    def score_text(self, wavs, texts: Union[str, Sequence[str]], sr: int = 24000, normalize: bool = False) -> List["TextScore"]:
+        """The likelihoods only: per utterance `-log p(text | audio)` under CTC, its mean per character and whether the pair is
+        feasible (the best path is not computed)."""
+        texts = [texts] if isinstance(texts, str) else list(texts)
+        ids = [self.text_to_ids(t) for t in texts]
+        _, raws = self._align_ids(wavs, ids, sr, normalize, False)
+        return [TextScore(r.nll, r.nll / max(len(y), 1), r.feasible, len(y)) for y, r in zip(ids, raws)]
+
 
 # ---- greedy CTC on given logits -----------------------------------------------------------------------
 @torch.no_grad()
@@ -422,6 +502,133 @@ def ctc_greedy(logits: torch.Tensor, frames: Sequence[int], blank: int = 0):
         at.append(frm[o:o + cnt[u]].tolist())
         o += int(t)
     return ids, at, mean[:-1].cpu(), flp[:-1].cpu()
+
+
+# ---- forced alignment and likelihood on given logits -------------------------------------------------------
+@dataclasses.dataclass
+class CTCAlignment:
+    """One utterance of `ctc_forced_align`, in frames and target positions."""
+    nll: float                 # -log p(targets | logits); inf when infeasible
+    path_logprob: Optional[float]  # the log-probability of the best path; -inf when infeasible
+    feasible: bool
+    frame_tokens: List[int]    # per frame the index of the target it emits, -1 for blank
+    starts: List[int]          # per target its frames [start, end)
+    ends: List[int]
+    scores: List[float]        # per target the mean log-probability over its frames
+
+
+class CharSpan(NamedTuple):
+    char: str
+    start_s: float
+    end_s: float
+    score: float
+
+
+class WordSpan(NamedTuple):
+    word: str
+    start_s: float
+    end_s: float
+    score: float               # the mean of its characters' scores
+
+
+@dataclasses.dataclass
+class TextAlignment:
+    text: str                  # the normalised text that was aligned
+    transcript: Transcript     # what the recogniser heard in the same pass
+    chars: List[CharSpan]      # one per character of `text`, a space for the word delimiter
+    words: List[WordSpan]
+    nll: float
+    nll_per_char: float        # nll / max(L, 1)
+    path_logprob: float
+    feasible: bool
+    frame_tokens: List[int]
+
+
+@dataclasses.dataclass
+class TextScore:
+    nll: float
+    nll_per_char: float
+    feasible: bool
+    n_chars: int
+
+
+def group_words(chars: Sequence[CharSpan]) -> List[WordSpan]:
+    """The characters between word delimiters (spaces): a word runs from its first character's start to its last one's end, and
+    its score is the mean of its characters' scores."""
+    words, cur = [], []
+    for c in list(chars) + [CharSpan(" ", 0.0, 0.0, 0.0)]:
+        if c.char != " ":
+            cur.append(c)
+        elif cur:
+            words.append(WordSpan("".join(x.char for x in cur), cur[0].start_s, cur[-1].end_s, sum(x.score for x in cur) / len(cur)))
+            cur = []
+    return words
+
+
+class _FalignOut:
+    """The device outputs of one vx_falign / vx_falign_asr call, each with a guard entry behind it."""
+
+    def __init__(self, n: int, frames: int, toks: int, dev, path: bool):
+        mk = lambda m, dt, fill: torch.full((m + 1,), fill, dtype=dt, device=dev)  # noqa: E731
+        self.n, self.path = n, path
+        self.nll = mk(n, torch.float64, float("nan"))
+        self.feas = mk(n, torch.int32, -7)
+        self.plp = mk(n, torch.float64, float("nan")) if path else None
+        self.ftok = mk(frames, torch.int32, -7) if path else None
+        self.start = mk(toks, torch.int32, -7) if path else None
+        self.end = mk(toks, torch.int32, -7) if path else None
+        self.score = mk(toks, torch.float32, float("nan")) if path else None
+
+    def pointers(self):
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        return p(self.nll), p(self.plp), p(self.ftok), p(self.start), p(self.end), p(self.score), p(self.feas)
+
+    def split(self, frames: Sequence[int], lens: Sequence[int]) -> List[CTCAlignment]:
+        for t in (self.nll, self.plp, self.score):
+            assert t is None or bool(torch.isnan(t[-1])), "a write outside an output"
+        for t in (self.feas, self.ftok, self.start, self.end):
+            assert t is None or int(t[-1]) == -7, "a write outside an output"
+        host = lambda t: None if t is None else t[:-1].cpu().tolist()  # noqa: E731
+        nll, feas, plp, ftok, start, end, score = (host(t) for t in (self.nll, self.feas, self.plp, self.ftok, self.start, self.end, self.score))
+        out, fo, to = [], 0, 0
+        for u, (T, L) in enumerate(zip(frames, lens)):
+            T, L = int(T), int(L)
+            if self.path:
+                out.append(CTCAlignment(nll[u], plp[u], bool(feas[u]), ftok[fo:fo + T], start[to:to + L], end[to:to + L], score[to:to + L]))
+            else:
+                out.append(CTCAlignment(nll[u], None, bool(feas[u]), [], [], [], []))
+            fo, to = fo + T, to + L
+        return out
+
+
+@torch.no_grad()
+def _falign(logits: torch.Tensor, frames: Sequence[int], targets: Sequence[Sequence[int]], blank: int, path: bool) -> List[CTCAlignment]:
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    n, total = len(frames), int(sum(frames))
+    assert logits.shape[0] == total and len(targets) == n, "one row per frame and one target list per utterance"
+    flat = [int(t) for y in targets for t in y]
+    lens = [len(y) for y in targets]
+    out = _FalignOut(n, total, len(flat), logits.device, path)
+    if total == 0:  # no frame at all: a pointer that is not null, never read
+        logits = logits.new_zeros((1, logits.shape[1]))
+    with torch.cuda.device(logits.device):
+        _e._check(_e.load_library().vx_falign(logits.data_ptr(), logits.shape[1], int(blank), n, (C.c_int32 * n)(*[int(f) for f in frames]),
+                                              (C.c_int32 * max(len(flat), 1))(*flat), (C.c_int32 * n)(*lens), *out.pointers(),
+                                              _e.current_stream_ptr(logits.device)))
+    return out.split(frames, lens)
+
+
+def ctc_forced_align(logits: torch.Tensor, frames: Sequence[int], targets: Sequence[Sequence[int]], blank: int = 0) -> List[CTCAlignment]:
+    """`vx_falign`: logits (sum frames, vocab) float32 on the device, the utterances' rows concatenated, and per utterance the
+    target ids (none equal to `blank`) -> one `CTCAlignment` per utterance: the likelihood, the best path's log-probability, per
+    frame the target it emits, per target its frames [start, end) and mean log-probability.  Up to 1000 targets an utterance."""
+    return _falign(logits, frames, targets, blank, True)
+
+
+def ctc_nll(logits: torch.Tensor, frames: Sequence[int], targets: Sequence[Sequence[int]], blank: int = 0) -> torch.Tensor:
+    """`vx_falign`'s likelihood half alone: `-log p(targets | logits)` per utterance, (n,) float64 on the host, `inf` where the
+    targets do not fit the frames.  `F.ctc_loss(reduction="none")` on a ragged batch, in fp64."""
+    return torch.tensor([r.nll for r in _falign(logits, frames, targets, blank, False)], dtype=torch.float64)
 
 
 # ---- edit distance and error rates ------------------------------------------------------------------------
@@ -508,3 +715,10 @@ def recognition_error(text, wav, recognizer: SpeechRecognizer, sr: int = 24000, 
     assert len(hyps) == len(texts), "one text per waveform"
     fn = {"word": word_error_rate, "char": char_error_rate}[unit]
     return fn(texts, hyps, recognizer.device)
+
+
+def text_likelihood(text, wav, recognizer: SpeechRecognizer, sr: int = 24000, normalize: bool = False) -> List[TextScore]:
+    """How likely the text(s) an utterance was given are under its audio: per utterance a `TextScore` with the CTC likelihood
+    `-log p(text | audio)` and its mean per character.  A continuous companion of `recognition_error`: it still separates two
+    candidates with the same error rate, and needs no decoding decision.  On synthetic weights the number means nothing."""
+    return recognizer.score_text(wav, [text] if isinstance(text, str) else list(text), sr=sr, normalize=normalize)

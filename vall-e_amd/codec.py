@@ -532,6 +532,19 @@ class EncodecDecoder:
         rec = self.decode(self.encode(wav, n_q))
         return recognition_error(text, rec.reshape(-1), recognizer, sr=SAMPLE_RATE, normalize=normalize, unit=unit)
 
+    def roundtrip_text_likelihood(self, wav: torch.Tensor, text: str, recognizer, n_q: Optional[int] = None, sr: Optional[int] = None,
+                                  normalize: bool = False):
+        """The CTC likelihood (`asr.text_likelihood`, an `asr.TextScore`: `-log p(text | audio)` and its per-character mean) of
+        `text` under decode(encode(waveform)): a continuous companion of `roundtrip_wer` that still moves when the error rate is
+        0 on both sides of a comparison.  Arguments as `roundtrip_wer`'s; on synthetic weights the number means nothing.  Needs
+        `encoder=True`."""
+        from .asr import text_likelihood
+
+        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
+            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        rec = self.decode(self.encode(wav, n_q))
+        return text_likelihood(text, rec.reshape(-1), recognizer, sr=SAMPLE_RATE, normalize=normalize)[0]
+
 
 class AudioTokenizer:
     """The reference's `valle.data.tokenizer.AudioTokenizer` (tokenizer.py:238-254) on the GPU: `encode(wav)` with wav (B, 1, L)

@@ -17,6 +17,7 @@
 #undef VX_STAMPS  // the in-kernel stamps write device globals of engine.hip's unit, out of this unit's reach
 #include "spk_host.hpp"
 #include "asr_kernels.hpp"
+#include "falign_kernels.hpp"
 
 using namespace vx;
 
@@ -34,6 +35,8 @@ struct AsrDev {
   DevBuf<int> ids;
   // per call: wav pointers [max_batch] | n_samples [max_batch] | segment tables [n_conv][max_batch + 1]
   CallStage stage;
+  DevBuf<unsigned char> fal;  // vx_falign_asr's scratch, grow-only
+  size_t fal_bytes = 0;
 };
 
 // Offsets (floats) into the workspace.
@@ -508,10 +511,152 @@ extern "C" int vx_asr_read(vx_asr* g, const char* name, int32_t utt, float* dst,
 
 extern "C" int vx_asr_get_timings(const vx_asr* g, double* out, int32_t n) {
   if (!g || !out || n < 0 || n > 4) return fail(VX_ERR_ARG, "vx_asr_get_timings: null argument or n outside [0, 4]");
-  const double v[4] = {g->last_ms, (double)(g->plan.total * sizeof(float) + g->plan.partial * sizeof(double)),
+  const double v[4] = {g->last_ms,
+                       (double)(g->plan.total * sizeof(float) + g->plan.partial * sizeof(double) + (g->dev ? g->dev->fal_bytes : 0)),
                        (double)(g->packed.size() * sizeof(float)),
                        g->last_n ? (double)g->last_seg[(size_t)(g->cfg.n_conv - 1) * (g->last_n + 1) + g->last_n] : 0.0};
   for (int i = 0; i < n; ++i) out[i] = v[i];
+  return VX_OK;
+}
+
+// ---- forced alignment and text likelihood -----------------------------------------------------------------------------------------
+namespace {
+
+constexpr long long FAL_MAX_BP_WORDS = 1ll << 29;  // 2 GiB of back-pointers a call
+
+struct FalOut {
+  double *nll, *path_logprob;
+  int *frame_token, *tok_start, *tok_end;
+  float* tok_score;
+  int* feasible;
+  bool any() const { return nll || path_logprob || frame_token || tok_start || tok_end || tok_score || feasible; }
+  bool max_half() const { return path_logprob || frame_token || tok_start || tok_end || tok_score; }
+};
+
+// The utterance table and the layout of one call's scratch (bytes): utt | targets | lse | path | bp.
+struct FalPlan {
+  std::vector<FalUtt> utt;
+  long rows = 0, toks = 0;
+  long long bp_words = 0;
+  int longest_S = 1;
+  size_t o_tgt = 0, o_lse = 0, o_path = 0, o_bp = 0, bytes = 0;
+};
+
+// Every check of vx_falign / vx_falign_asr on the texts, before any HIP call.
+int fal_plan(const char* what, int vocab, int blank, int n, const int* frames, const int32_t* targets, const int32_t* target_len, bool want_max,
+             FalPlan& p) {
+  p.utt.assign((size_t)n, FalUtt{});
+  for (int i = 0; i < n; ++i) {
+    if (frames[i] < 0 || target_len[i] < 0)
+      return fail(VX_ERR_ARG, "%s: utterance %d: %d frames, %d targets", what, i, frames[i], target_len[i]);
+    if (target_len[i] > 0 && !targets) return fail(VX_ERR_ARG, "%s: null targets", what);
+    if (p.rows + frames[i] > 2147483647L || p.toks + target_len[i] > 2147483647L)
+      return fail(VX_ERR_CAPACITY, "%s: more than 2^31 - 1 frames or targets", what);
+    const int32_t* y = targets + p.toks;
+    int repeats = 0;
+    for (int k = 0; k < target_len[i]; ++k) {
+      if (y[k] < 0 || y[k] >= vocab || y[k] == blank)
+        return fail(VX_ERR_ARG, "%s: utterance %d: target %d is id %d (ids are in [0, %d) and not the blank %d)", what, i, k, y[k], vocab, blank);
+      repeats += k > 0 && y[k] == y[k - 1];
+    }
+    FalUtt& u = p.utt[i];
+    u.row0 = (int)p.rows; u.T = frames[i]; u.tok0 = (int)p.toks; u.L = target_len[i];
+    u.feasible = (long)frames[i] >= (long)target_len[i] + repeats;
+    u.bp_off = p.bp_words;
+    p.rows += frames[i];
+    p.toks += target_len[i];
+  }
+  for (int i = 0; i < n; ++i) {
+    FalUtt& u = p.utt[i];
+    if (!u.feasible || u.T == 0) continue;  // no lattice is walked
+    if (u.L > FAL_MAX_L)
+      return fail(VX_ERR_CAPACITY, "%s: utterance %d: %d targets, up to %d are served (four fp64 rows of 2 L + 3 cells in 64 KiB of LDS)", what, i,
+                  u.L, FAL_MAX_L);
+    p.longest_S = std::max(p.longest_S, 2 * u.L + 1);
+    if (want_max) {
+      u.bp_off = p.bp_words;
+      p.bp_words += (long long)((u.T + 15) / 16) * (2 * u.L + 1);
+      if (p.bp_words > FAL_MAX_BP_WORDS)
+        return fail(VX_ERR_CAPACITY, "%s: utterance %d: the back-pointers (frames x states / 4 bytes, summed over the call) exceed the workspace limit of %lld bytes",
+                    what, i, FAL_MAX_BP_WORDS * 4);
+    }
+  }
+  auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+  p.o_tgt = up((size_t)n * sizeof(FalUtt));
+  p.o_lse = p.o_tgt + up((size_t)(p.toks + 1) * sizeof(int));
+  p.o_path = p.o_lse + up((size_t)(p.rows + 1) * sizeof(double));
+  p.o_bp = p.o_path + up((size_t)(p.rows + 1) * sizeof(int));
+  p.bytes = p.o_bp + up((size_t)(p.bp_words + 1) * sizeof(unsigned));
+  return VX_OK;
+}
+
+// The launches: `scratch` holds p.bytes.  The host arrays are copied before the call returns (the caller waits for `s`).
+int fal_launch(const float* logits, int vocab, int blank, int n, const int32_t* targets, const FalPlan& p, unsigned char* scratch,
+               const FalOut& o, hipStream_t s) {
+  HIPC(hipMemcpyAsync(scratch, p.utt.data(), (size_t)n * sizeof(FalUtt), hipMemcpyHostToDevice, s));
+  if (p.toks > 0) HIPC(hipMemcpyAsync(scratch + p.o_tgt, targets, (size_t)p.toks * sizeof(int), hipMemcpyHostToDevice, s));
+  double* lse = (double*)(scratch + p.o_lse);
+  if (p.rows > 0) {
+    falign_lse_kernel<<<(unsigned)((p.rows + 3) / 4), 256, 0, s>>>(logits, vocab, p.rows, lse);
+    HIPC(hipGetLastError());
+  }
+  FalArgs a{};
+  a.logits = logits; a.lse = lse; a.utt = (const FalUtt*)scratch; a.targets = (const int*)(scratch + p.o_tgt);
+  a.bp = (unsigned*)(scratch + p.o_bp); a.path = (int*)(scratch + p.o_path);
+  a.nll = o.nll; a.path_logprob = o.path_logprob; a.frame_token = o.frame_token; a.tok_start = o.tok_start; a.tok_end = o.tok_end;
+  a.tok_score = o.tok_score; a.feasible = o.feasible;
+  a.vocab = vocab; a.blank = blank; a.row_stride = p.longest_S + 2; a.do_max = o.max_half() ? 1 : 0;
+  falign_kernel<<<(unsigned)n, FAL_WG, 4 * (size_t)a.row_stride * sizeof(double), s>>>(a);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+}  // namespace
+
+extern "C" int vx_falign(const float* logits, int32_t vocab, int32_t blank, int32_t n, const int32_t* frames, const int32_t* targets,
+                         const int32_t* target_len, double* nll_out, double* path_logprob_out, int32_t* frame_token_out,
+                         int32_t* tok_start_out, int32_t* tok_end_out, float* tok_score_out, int32_t* feasible_out, void* stream) {
+  if (!logits || !frames || !target_len) return fail(VX_ERR_ARG, "vx_falign: null argument");
+  const FalOut o{nll_out, path_logprob_out, frame_token_out, tok_start_out, tok_end_out, tok_score_out, feasible_out};
+  if (!o.any()) return fail(VX_ERR_ARG, "vx_falign: no output requested");
+  if (n < 1 || vocab < 1 || blank < 0 || blank >= vocab) return fail(VX_ERR_ARG, "vx_falign: n %d, vocab %d, blank %d", n, vocab, blank);
+  FalPlan p;
+  VXC(fal_plan("vx_falign", vocab, blank, n, frames, targets, target_len, o.max_half(), p));
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf<unsigned char> scratch;
+  VXC(scratch.alloc(p.bytes));
+  VXC(fal_launch(logits, vocab, blank, n, targets, p, scratch.get(), o, s));
+  HIPC(hipStreamSynchronize(s));  // the scratch and the host tables go out of scope
+  return VX_OK;
+}
+
+extern "C" int vx_falign_asr(vx_asr* g, int32_t n, const int32_t* targets, const int32_t* target_len, double* nll_out,
+                             double* path_logprob_out, int32_t* frame_token_out, int32_t* tok_start_out, int32_t* tok_end_out,
+                             float* tok_score_out, int32_t* feasible_out, void* stream) {
+  if (!g || !target_len) return fail(VX_ERR_ARG, "vx_falign_asr: null argument");
+  const FalOut o{nll_out, path_logprob_out, frame_token_out, tok_start_out, tok_end_out, tok_score_out, feasible_out};
+  if (!o.any()) return fail(VX_ERR_ARG, "vx_falign_asr: no output requested");
+  if (n < 1) return fail(VX_ERR_ARG, "vx_falign_asr: n = %d utterances", n);
+  if (g->device < 0 || g->last_n == 0) return fail(VX_ERR_STATE, "vx_falign_asr before any vx_asr_recognize");
+  if (n != g->last_n) return fail(VX_ERR_STATE, "vx_falign_asr: n = %d utterances, the last vx_asr_recognize served %d", n, g->last_n);
+  const vx_asr_config& c = g->cfg;
+  const int* seg = g->last_seg.data() + (size_t)(c.n_conv - 1) * (n + 1);
+  std::vector<int> frames((size_t)n);
+  for (int i = 0; i < n; ++i) frames[i] = seg[i + 1] - seg[i];
+  FalPlan p;
+  VXC(fal_plan("vx_falign_asr", c.vocab, c.blank, n, frames.data(), targets, target_len, o.max_half(), p));
+  DevGuard guard(g->device);
+  HIPC(guard.err);
+  AsrDev& dv = *g->dev;
+  hipStream_t s = (hipStream_t)stream;
+  HIPC(hipStreamWaitEvent(s, dv.stage.ev_done, 0));  // the logits of the last call, whatever stream it ran on
+  if (p.bytes > dv.fal_bytes) {
+    dv.fal_bytes = 0;
+    VXC(dv.fal.alloc(p.bytes));
+    dv.fal_bytes = p.bytes;
+  }
+  VXC(fal_launch(dv.ws.get() + g->plan.logits, c.vocab, c.blank, n, targets, p, dv.fal.get(), o, s));
+  HIPC(hipStreamSynchronize(s));  // the host tables go out of scope, and the next call may replace the scratch
   return VX_OK;
 }
 
