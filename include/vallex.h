@@ -1326,6 +1326,91 @@ int vx_falign_asr(vx_asr* h, int32_t n, const int32_t* targets, const int32_t* t
                   int32_t* frame_token_out, int32_t* tok_start_out, int32_t* tok_end_out, float* tok_score_out, int32_t* feasible_out,
                   void* stream);
 
+/* ---- Whisper recogniser: WhisperForConditionalGeneration, a 16 kHz waveform to token ids by greedy decoding -------------------------
+ * A handle of its own, fp32 storage and accumulation.  Every shape comes from the checkpoint's config.json.  P =
+ * max_source_positions, Tt = max_target_positions, d = d_model, head_dim = 64; a chunk is 320 P samples (480 000 at P = 1500).
+ *   1. log-mel.  The waveform is zero-padded to the chunk and framed as torch.stft(n_fft = 400, hop = 160, center = True, pad_mode =
+ *      "reflect") with the periodic Hann window; power spectrum (201 bins); the last frame is dropped, 2 P frames are left; mel =
+ *      mel_filters (n_mels, 201) applied to the power (the caller's table: Slaney scale and norm, 0 .. 8000 Hz, built in fp64);
+ *      x = log10(max(mel, 1e-10)); x = max(x, max over the utterance of x - 8); x = (x + 4) / 4.  Tap "logmel" (2 P, n_mels).
+ *   2. encoder.  gelu(Conv1d(n_mels -> d, k 3, pad 1)) (tap "conv1" (2 P, d)); gelu(Conv1d(d -> d, k 3, stride 2, pad 1)) (tap
+ *      "features" (P, d)); h = that + embed_positions (tap "enc0"); per layer h = h + Attn(LN1(h)); h = h + W2 gelu(W1 LN2(h) + b1) +
+ *      b2 (tap "enc<l+1>"); then LN_enc(h) (tap "encoder").  Attn: q, v and out with bias, k without, softmax(q k / 8) v per head
+ *      over all P rows of the utterance: there is no attention mask, the padded part of the chunk takes part as in transformers.
+ *      gelu is the exact one; every LayerNorm has eps 1e-5.
+ *   3. decoder.  x = embed_tokens[id] + embed_positions[pos]; per layer x = x + SelfAttn(LN1(x)) over positions 0 .. pos (causal),
+ *      x = x + CrossAttn(LN2(x)) with keys and values from the encoder output (after LN_enc), x = x + FFN(LN3(x)); then
+ *      LN_dec(x); logits = proj_out.weight x, the token embedding when tie_proj = 1.
+ *   4. greedy generation.  The decoder input starts with the utterance's prompt_ids.  Generated step g reads the logits of the last
+ *      position: tokens of suppress_tokens are set to -inf, at g = 0 those of begin_suppress_tokens too; the token is the argmax, the
+ *      lowest index among equal maxima; its log-probability is x[token] - m - log sum_c exp(x[c] - m) over that processed row, m its
+ *      maximum and the sum in fp64, rounded to fp32.  The utterance stops (in this order) on eos_token_id (stop reason 1), on its
+ *      max_new_tokens (2), or when the sequence, the new token included, has Tt tokens (3); the last token is reported.  A stopped
+ *      utterance's later steps change none of its outputs.
+ *   5. teacher forcing (forced != NULL): the same steps with forced[i][g] in place of the argmax, max_new_tokens[i] of them; eos
+ *      does not stop it, and logprobs_out is every step's log-probability of the given token.
+ * The host enqueues 8 decode steps at a time and reads the finished flags between them; no token is read back.  Every utterance is
+ * bitwise what it is alone, and two identical calls give the same bits.
+ * Weight keys (fp32, host, torch layouts, transformers' names): mel_filters (n_mels, 201); model.encoder.conv1 / conv2 .weight /
+ * .bias; model.encoder.embed_positions.weight (P, d); model.encoder.layers.{l}.self_attn.{q,v,out}_proj.weight / .bias and
+ * .k_proj.weight, .self_attn_layer_norm.*, .fc1.*, .fc2.*, .final_layer_norm.*; model.encoder.layer_norm.*;
+ * model.decoder.embed_tokens.weight (vocab, d), model.decoder.embed_positions.weight (Tt, d), model.decoder.layers.{l}. as the
+ * encoder's plus .encoder_attn.* and .encoder_attn_layer_norm.*; model.decoder.layer_norm.*; proj_out.weight (vocab, d) only with
+ * tie_proj = 0.
+ * Not built: beam search, temperature fallback, timestamps, language detection, long-form transcription, bf16. */
+typedef struct vx_wsp vx_wsp;
+enum { VX_WSP_KEEP_TAPS = 1 };  /* vx_wsp_config.flags: "enc<l>" and the per-step "logits" keep buffers of their own */
+enum { VX_WSP_STOP_EOS = 1, VX_WSP_STOP_MAX_NEW = 2, VX_WSP_STOP_MAX_TARGET = 3 };
+typedef struct vx_wsp_config {
+  int32_t struct_size;            /* sizeof(vx_wsp_config) */
+  int32_t n_mels, d_model;        /* num_mel_bins (a multiple of 16), d_model */
+  int32_t enc_layers, enc_heads, enc_ffn;
+  int32_t dec_layers, dec_heads, dec_ffn;
+  int32_t max_source_positions, max_target_positions;
+  int32_t vocab;
+  int32_t activation;             /* 0 = gelu (served) */
+  int32_t tie_proj;               /* 1: proj_out.weight is model.decoder.embed_tokens.weight */
+  int32_t eos_token_id;
+  int32_t max_batch;              /* utterances per call, <= 64 */
+  int32_t flags;                  /* VX_WSP_KEEP_TAPS */
+} vx_wsp_config;
+/* Host only, no HIP call.  In this order: nulls, a wrong struct_size, a count or size below 1 (max_target_positions below 2),
+ * eos_token_id outside [0, vocab), unknown flags -> VX_ERR_ARG; then an activation other than gelu, a head_dim other than 64,
+ * num_mel_bins or an ffn dim that is no multiple of 16, more than 4096 source or target positions, max_batch > 64 ->
+ * VX_ERR_UNSUPPORTED with the field named. */
+int vx_wsp_create(const vx_wsp_config* cfg, vx_wsp** out);
+void vx_wsp_destroy(vx_wsp* h);
+/* Host only.  data: HOST fp32 of `shape`.  Unknown key or wrong shape -> VX_ERR_WEIGHTS; after vx_wsp_finalize -> VX_ERR_STATE. */
+int vx_wsp_set_weight(vx_wsp* h, const char* key, const float* data, const int64_t* shape, int32_t ndim);
+/* Host only: the generation config's suppress_tokens and begin_suppress_tokens (HOST int32, either may be empty); replaces what was
+ * set before.  An id outside [0, vocab) -> VX_ERR_ARG naming the list; after vx_wsp_finalize -> VX_ERR_STATE. */
+int vx_wsp_set_suppress(vx_wsp* h, const int32_t* ids, int32_t n_ids, const int32_t* begin_ids, int32_t n_begin);
+/* Host only: every tensor is there (a missing one -> VX_ERR_WEIGHTS naming it); packs the weights and builds the DFT table. */
+int vx_wsp_finalize(vx_wsp* h);
+/* n utterances: wav[i] DEVICE fp32 of n_samples[i] samples at 16 kHz (the pointer array and every int array below live on the host).
+ * prompt_ids (n, prompt_stride), utterance i's first n_prompt[i] entries; max_new_tokens (n), each in [1, out_stride]; forced NULL
+ * or (n, out_stride), utterance i's first max_new_tokens[i] entries.  tokens_out DEVICE int32 and logprobs_out DEVICE fp32 (n,
+ * out_stride): utterance i's first counts_out[i] entries are written, the rest is left alone; counts_out and stops_out DEVICE int32
+ * (n).  Checked before any HIP call, in this order: null arguments (forced excepted), n < 1 -> VX_ERR_ARG; not finalized ->
+ * VX_ERR_STATE; n > max_batch -> VX_ERR_CAPACITY; strides below 1 or out_stride > Tt -> VX_ERR_ARG; then per utterance: a null
+ * pointer or n_samples[i] < 0 -> VX_ERR_ARG; n_samples[i] above the chunk -> VX_ERR_CAPACITY (long-form is not built); an empty
+ * prompt_ids -> VX_ERR_ARG; a prompt that leaves no room under max_target_positions -> VX_ERR_CAPACITY; an id outside [0, vocab),
+ * max_new_tokens[i] outside its range -> VX_ERR_ARG; forced tokens that do not fit under max_target_positions -> VX_ERR_CAPACITY.
+ * The work is enqueued on `stream`, and the host waits for it between groups of 8 decode steps.  Calls on one handle must not
+ * overlap. */
+int vx_wsp_recognize(vx_wsp* h, int32_t n, const float* const* wav, const int32_t* n_samples, const int32_t* prompt_ids,
+                     const int32_t* n_prompt, int32_t prompt_stride, const int32_t* max_new_tokens, const int32_t* forced,
+                     int32_t out_stride, int32_t* tokens_out, float* logprobs_out, int32_t* counts_out, int32_t* stops_out, void* stream);
+/* A read tap for the tests: waits for the last vx_wsp_recognize and copies utterance `utt`'s "logmel", "conv1", "features",
+ * "enc<l>" (0 .. enc_layers; needs VX_WSP_KEEP_TAPS), "encoder" or "logits" (needs VX_WSP_KEEP_TAPS: the raw rows (count, vocab) of
+ * its generated steps) to dst (HOST fp32).  n_floats must be the tap's size, else VX_ERR_ARG naming it; an unknown name ->
+ * VX_ERR_ARG; no call yet, or a tap without its flag -> VX_ERR_STATE. */
+int vx_wsp_read(vx_wsp* h, const char* name, int32_t utt, float* dst, int64_t n_floats);
+/* out[0] = host milliseconds the last vx_wsp_recognize took, out[1] = workspace bytes, out[2] = weight bytes, out[3] = decode steps
+ * it enqueued, out[4 .. 6] = device milliseconds of its log-mel, encoder (cross keys and values included) and token loop (asking
+ * for them waits for the call); n = how many are wanted (<= 7). */
+int vx_wsp_get_timings(vx_wsp* h, double* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ __all__ = ["ModelConfig", "add_model_arguments", "NUM_AUDIO_TOKENS", "NUM_TEXT_T
            "STFTConfig", "MultiResolutionSTFT", "MSTFTResult", "mstft_distance", "copy_synthesis_distance",
            "SpeakerEncoder", "SpeakerConfig", "speaker_similarity",
            "SpeechRecognizer", "RecognizerConfig", "Transcript", "ErrorRate", "edit_distance", "word_error_rate", "char_error_rate",
-           "recognition_error", "TextAlignment", "TextScore", "ctc_forced_align", "ctc_nll", "text_likelihood"]
+           "recognition_error", "TextAlignment", "TextScore", "ctc_forced_align", "ctc_nll", "text_likelihood",
+           "WhisperRecognizer", "WhisperConfig", "WhisperTranscript"]
 
 
 def __getattr__(name):  # the codec pulls in torch and the ctypes binding: imported on first use, not with the package
@@ -51,4 +52,8 @@ def __getattr__(name):  # the codec pulls in torch and the ctypes binding: impor
         from . import asr
 
         return getattr(asr, name)
+    if name in ("WhisperRecognizer", "WhisperConfig", "WhisperTranscript"):
+        from . import whisper
+
+        return getattr(whisper, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -12,7 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "libvallex.so")
-SRCS = ["engine.hip", "codec.hip", "logprob.hip", "align.hip", "fbank.hip", "dtw.hip", "pitch.hip", "stft.hip", "meltf.hip", "vocoder.hip", "ganvoc.hip", "spk.hip", "asr.hip"]
+SRCS = ["engine.hip", "codec.hip", "logprob.hip", "align.hip", "fbank.hip", "dtw.hip", "pitch.hip", "stft.hip", "meltf.hip", "vocoder.hip", "ganvoc.hip", "spk.hip", "asr.hip", "whisper.hip"]
 # every header next to this file is a dependency (a hand-kept list went stale once: an edited header did not trigger a rebuild)
 DEPS = SRCS + sorted(f for f in os.listdir(HERE) if f.endswith((".hpp", ".h"))) + ["../../include/vallex.h", "build.py"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",

@@ -97,6 +97,15 @@ VX_ASR_KEEP_TAPS = 1   # vx_asr_config.flags
 VX_ASR_NORMALIZE = 1   # vx_asr_recognize flags
 
 
+class VxWspConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "n_mels", "d_model", "enc_layers", "enc_heads", "enc_ffn", "dec_layers", "dec_heads",
+                                         "dec_ffn", "max_source_positions", "max_target_positions", "vocab", "activation", "tie_proj",
+                                         "eos_token_id", "max_batch", "flags")]
+
+
+VX_WSP_KEEP_TAPS = 1   # vx_wsp_config.flags
+
+
 class VxDtwConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "dim", "n_ceps", "max_frames", "max_batch")]
 
@@ -328,6 +337,17 @@ _SIGS = {
     "vx_falign": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
                   + [C.c_void_p] * 8),
     "vx_falign_asr": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_void_p] * 8),
+    # Whisper recogniser (whisper.WhisperRecognizer)
+    "vx_wsp_create": (C.c_int, [C.POINTER(VxWspConfig), C.POINTER(C.c_void_p)]),
+    "vx_wsp_destroy": (None, [C.c_void_p]),
+    "vx_wsp_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
+    "vx_wsp_set_suppress": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "vx_wsp_finalize": (C.c_int, [C.c_void_p]),
+    "vx_wsp_recognize": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vx_wsp_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),
+    "vx_wsp_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so

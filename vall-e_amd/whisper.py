@@ -1,0 +1,502 @@
+"""Whisper recogniser on the GPU: `transformers`' `WhisperForConditionalGeneration` with greedy decoding behind `vx_wsp_*`
+(include/vallex.h, csrc/whisper_kernels.hpp on top of the speaker encoder's kernels); there is no CPU fallback and `transformers` is
+not needed at run time.
+
+    from valle_amd import WhisperRecognizer, recognition_error
+    rec = WhisperRecognizer("ckpt/config.json", json.load(open("ckpt/vocab.json")), "ckpt/generation_config.json",
+                            state_dict=torch.load("ckpt/pytorch_model.bin")).to("cuda")
+    hyp = rec.recognize([synth_wav], sr=24000)[0]           # .text, .tokens, .token_logprobs, .logprob, .stop_reason
+    wer = recognition_error(text, synth_wav, rec, sr=24000)   # the CTC recogniser's function, unchanged
+    nll = rec.score_tokens([synth_wav], [token_ids]).nll      # teacher forcing
+
+The definition is stated in include/vallex.h and restated in fp64 in tests/whisper_ref.py, which tests/test_whisper_cpu.py pins
+against `transformers`.  One chunk (30 s at the released shapes) per utterance; beam search, temperature fallback, timestamps,
+language detection, long-form transcription and bf16 are not built.  Nothing has been recognised on trained weights: no checkpoint
+is available where this is built, and on synthetic weights the transcript means nothing.  Parity with `openai-whisper` and with the
+tokenizer's encode direction is not pinned: text comes from `vocab.json` by the byte-level decode rule only."""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import json
+import math
+from typing import Dict, List, NamedTuple, Optional, Sequence, Union
+
+import torch
+
+from . import engine as _e
+
+SAMPLE_RATE = 16000
+N_FFT, HOP, BINS = 400, 160, 201
+STOP_REASONS = {0: "none", 1: "eos", 2: "max_new_tokens", 3: "max_target_positions"}
+
+
+@dataclasses.dataclass
+class WhisperConfig:
+    """The fields of `transformers.WhisperConfig` the network reads, under their names and with its defaults."""
+    vocab_size: int = 51865
+    num_mel_bins: int = 80
+    encoder_layers: int = 4
+    encoder_attention_heads: int = 6
+    decoder_layers: int = 4
+    decoder_attention_heads: int = 6
+    decoder_ffn_dim: int = 1536
+    encoder_ffn_dim: int = 1536
+    d_model: int = 384
+    activation_function: str = "gelu"
+    max_source_positions: int = 1500
+    max_target_positions: int = 448
+    eos_token_id: int = 50256
+    decoder_start_token_id: int = 50257
+    tie_word_embeddings: bool = True
+
+    @classmethod
+    def from_any(cls, cfg) -> "WhisperConfig":
+        """A dict (a checkpoint's `config.json`), a path to one, or any object with the attributes."""
+        if isinstance(cfg, cls):
+            return cfg
+        if isinstance(cfg, str):
+            with open(cfg) as f:
+                cfg = json.load(f)
+        names = [f.name for f in dataclasses.fields(cls)]
+        if isinstance(cfg, dict):
+            return cls(**{k: cfg[k] for k in names if k in cfg and cfg[k] is not None})
+        return cls(**{k: getattr(cfg, k) for k in names if getattr(cfg, k, None) is not None})
+
+    @property
+    def chunk_samples(self) -> int:
+        return 320 * int(self.max_source_positions)
+
+
+@dataclasses.dataclass
+class WhisperGeneration:
+    """The fields of the checkpoint's `generation_config.json` greedy decoding reads."""
+    decoder_start_token_id: Optional[int] = None
+    eos_token_id: Optional[int] = None
+    no_timestamps_token_id: Optional[int] = None
+    lang_to_id: Optional[Dict[str, int]] = None
+    task_to_id: Optional[Dict[str, int]] = None
+    suppress_tokens: Sequence[int] = ()
+    begin_suppress_tokens: Sequence[int] = ()
+    max_length: Optional[int] = None
+
+    @classmethod
+    def from_any(cls, cfg) -> "WhisperGeneration":
+        if cfg is None:
+            return cls()
+        if isinstance(cfg, cls):
+            return cfg
+        if isinstance(cfg, str):
+            with open(cfg) as f:
+                cfg = json.load(f)
+        names = [f.name for f in dataclasses.fields(cls)]
+        if isinstance(cfg, dict):
+            out = cls(**{k: cfg[k] for k in names if k in cfg and cfg[k] is not None})
+        else:
+            out = cls(**{k: getattr(cfg, k) for k in names if getattr(cfg, k, None) is not None})
+        if isinstance(out.eos_token_id, (list, tuple)):
+            out.eos_token_id = int(out.eos_token_id[0])
+        return out
+
+
+def mel_filters(n_mels: int) -> torch.Tensor:
+    """(n_mels, 201) float64: Whisper's mel table, Slaney scale and norm over 0 .. 8000 Hz at n_fft 400 / 16 kHz, computed in fp64
+    (`transformers.audio_utils.mel_filter_bank(201, n_mels, 0, 8000, 16000, "slaney", "slaney")`, transposed)."""
+    from .fbank import slaney_mel_basis_f64
+
+    return torch.from_numpy(slaney_mel_basis_f64(SAMPLE_RATE, N_FFT, int(n_mels), 0.0, 8000.0))
+
+
+def expected_keys(c: WhisperConfig) -> Dict[str, tuple]:
+    """`transformers` key -> shape, as vx_wsp_create lays them out (without `mel_filters`)."""
+    d, P, Tt, V = int(c.d_model), int(c.max_source_positions), int(c.max_target_positions), int(c.vocab_size)
+    keys: Dict[str, tuple] = {}
+
+    def lin(name, n, k, bias=True):
+        keys[name + ".weight"] = (n, k)
+        if bias:
+            keys[name + ".bias"] = (n,)
+
+    def norm(name):
+        keys[name + ".weight"], keys[name + ".bias"] = (d,), (d,)
+
+    def attn(name):
+        lin(name + ".q_proj", d, d)
+        lin(name + ".k_proj", d, d, bias=False)
+        lin(name + ".v_proj", d, d)
+        lin(name + ".out_proj", d, d)
+
+    keys["model.encoder.conv1.weight"], keys["model.encoder.conv1.bias"] = (d, int(c.num_mel_bins), 3), (d,)
+    keys["model.encoder.conv2.weight"], keys["model.encoder.conv2.bias"] = (d, d, 3), (d,)
+    keys["model.encoder.embed_positions.weight"] = (P, d)
+    for l in range(int(c.encoder_layers)):
+        pre = f"model.encoder.layers.{l}."
+        attn(pre + "self_attn")
+        norm(pre + "self_attn_layer_norm")
+        lin(pre + "fc1", int(c.encoder_ffn_dim), d)
+        lin(pre + "fc2", d, int(c.encoder_ffn_dim))
+        norm(pre + "final_layer_norm")
+    norm("model.encoder.layer_norm")
+    keys["model.decoder.embed_tokens.weight"] = (V, d)
+    keys["model.decoder.embed_positions.weight"] = (Tt, d)
+    for l in range(int(c.decoder_layers)):
+        pre = f"model.decoder.layers.{l}."
+        attn(pre + "self_attn")
+        norm(pre + "self_attn_layer_norm")
+        attn(pre + "encoder_attn")
+        norm(pre + "encoder_attn_layer_norm")
+        lin(pre + "fc1", int(c.decoder_ffn_dim), d)
+        lin(pre + "fc2", d, int(c.decoder_ffn_dim))
+        norm(pre + "final_layer_norm")
+    norm("model.decoder.layer_norm")
+    if not c.tie_word_embeddings:
+        keys["proj_out.weight"] = (V, d)
+    return keys
+
+
+def synthetic_state_dict(config, seed: int = 0, head_scale: float = 3.0, pos_scale: float = 1.5, eos_boost: float = 1.6) -> Dict[str, torch.Tensor]:
+    """Seeded weights in the `transformers` layout for the tests and the benchmark.  The scales keep every stage alive and make every
+    part of the definition matter (norm gains and biases away from 1 and 0, positional tables of the activations' size);
+    `head_scale` spreads the logits so that nearly every step is decided by far more than fp32 rounding, `pos_scale` keeps a tied
+    embedding from repeating its own input for ever, and `eos_boost` lengthens the end-of-text row so that greedy runs end at
+    different steps."""
+    c = WhisperConfig.from_any(config)
+    g = torch.Generator().manual_seed(int(seed))
+    sd: Dict[str, torch.Tensor] = {}
+
+    def rnd(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    for k, shape in expected_keys(c).items():
+        if k.endswith("layer_norm.weight"):
+            sd[k] = 1.0 + rnd(*shape, scale=0.2)
+        elif k.endswith("layer_norm.bias"):
+            sd[k] = rnd(*shape, scale=0.3)
+        elif k.endswith(".bias"):
+            sd[k] = rnd(*shape, scale=0.1)
+        elif k.endswith("embed_positions.weight"):
+            sd[k] = rnd(*shape, scale=pos_scale)
+        elif k.endswith("embed_tokens.weight") or k == "proj_out.weight":
+            sd[k] = rnd(*shape, scale=head_scale / math.sqrt(shape[1]))
+        else:  # Linear and convolution weights: unit gain over the fan-in
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            sd[k] = rnd(*shape, scale=1.5 / math.sqrt(fan_in))
+    for k in ("model.decoder.embed_tokens.weight", "proj_out.weight"):
+        if k in sd:
+            sd[k][int(c.eos_token_id)] *= eos_boost
+    if c.tie_word_embeddings:
+        sd["proj_out.weight"] = sd["model.decoder.embed_tokens.weight"]
+    return sd
+
+
+# ---- ids to text ------------------------------------------------------------------------------------------
+def bytes_to_unicode() -> Dict[int, str]:
+    """GPT-2's table: every byte as a printable character (the printable Latin-1 bytes are themselves, the others are 256 + n in
+    the order they are met)."""
+    bs = list(range(ord("!"), ord("~") + 1)) + list(range(ord("\xa1"), ord("\xac") + 1)) + list(range(ord("\xae"), ord("\xff") + 1))
+    cs = bs[:]
+    n = 0
+    for b in range(256):
+        if b not in bs:
+            bs.append(b)
+            cs.append(256 + n)
+            n += 1
+    return {b: chr(c) for b, c in zip(bs, cs)}
+
+
+_UNICODE_TO_BYTE = {c: b for b, c in bytes_to_unicode().items()}
+
+
+def decode_tokens(ids: Sequence[int], id_to_token: Dict[int, str], first_special: int) -> str:
+    """The byte-level rule: ids at or above `first_special` are dropped, the token strings are concatenated, GPT-2's table is
+    inverted and the bytes are decoded as UTF-8 with errors="replace"."""
+    s = "".join(id_to_token.get(int(i), "") for i in ids if int(i) < first_special)
+    return bytes(_UNICODE_TO_BYTE[ch] for ch in s if ch in _UNICODE_TO_BYTE).decode("utf-8", errors="replace")
+
+
+@dataclasses.dataclass
+class WhisperTranscript:
+    text: str                    # "" without a vocab
+    tokens: List[int]            # the generated ids, the stopping one (eos) included
+    token_logprobs: List[float]  # per token, over the processed row (suppressed tokens at -inf)
+    logprob: float               # their sum
+    stop_reason: str             # "eos", "max_new_tokens" or "max_target_positions"
+
+
+class TokenScores(NamedTuple):
+    nll: List[float]                   # per utterance -sum of the log-probabilities of the given tokens
+    mean: float                        # sum of nll / number of tokens
+    token_logprobs: List[List[float]]
+
+
+class WhisperRecognizer:
+    """`WhisperRecognizer(config, vocab=None, generation_config=None, max_batch=8, state_dict=None, keep_taps=False)`: `config` and
+    `generation_config` are dicts, paths of the checkpoint's `config.json` / `generation_config.json`, or objects with those
+    attributes; `vocab` is the checkpoint's `vocab.json` mapping token -> id (without it `.text` is "").  A call serves up to
+    `max_batch` (<= 64) utterances of up to one chunk (320 x max_source_positions samples at 16 kHz) each.  A head dimension other
+    than 64 and an activation other than GELU raise NotImplementedError naming the field."""
+
+    def __init__(self, config, vocab: Optional[Dict[str, int]] = None, generation_config=None, max_batch: int = 8,
+                 state_dict: Optional[dict] = None, keep_taps: bool = False, mel_basis: Optional[torch.Tensor] = None):
+        c = self.config = WhisperConfig.from_any(config)
+        gen = self.generation = WhisperGeneration.from_any(generation_config)
+        if c.activation_function != "gelu":
+            raise NotImplementedError(f"activation_function = {c.activation_function!r}: gelu is served")
+        for side, heads in (("encoder", c.encoder_attention_heads), ("decoder", c.decoder_attention_heads)):
+            if int(c.d_model) % int(heads) or int(c.d_model) // int(heads) != 64:
+                raise NotImplementedError(f"{side} head_dim = d_model / {side}_attention_heads = {c.d_model} / {heads}: 64 is served")
+        self.eos_token_id = int(gen.eos_token_id if gen.eos_token_id is not None else c.eos_token_id)
+        self.decoder_start_token_id = int(gen.decoder_start_token_id if gen.decoder_start_token_id is not None else c.decoder_start_token_id)
+        self.vocab = None if vocab is None else {str(k): int(v) for k, v in vocab.items()}
+        self.id_to_token = {} if self.vocab is None else {v: k for k, v in self.vocab.items()}
+        # every id from the end-of-text token on is special in the released vocabularies
+        self.first_special = min(self.eos_token_id, self.decoder_start_token_id)
+        self.max_batch, self.keep_taps = int(max_batch), bool(keep_taps)
+        mel = mel_filters(int(c.num_mel_bins)) if mel_basis is None else torch.as_tensor(mel_basis)
+        if tuple(mel.shape) != (int(c.num_mel_bins), BINS):
+            raise ValueError(f"mel_basis is {tuple(mel.shape)}, expected ({c.num_mel_bins}, {BINS})")
+        self.mel_basis = mel.to(torch.float32).contiguous()
+        self.device = torch.device("cpu")
+        self._h = None
+        self._bound = None
+        self._weights: Optional[Dict[str, torch.Tensor]] = None
+        self._resamplers: Dict[int, object] = {}
+        self._create()  # a geometry the kernels do not serve is refused here
+        if state_dict is not None:
+            self.load_state_dict(state_dict)
+
+    # ---- handle -------------------------------------------------------------------------------------
+    def _config_struct(self) -> "_e.VxWspConfig":
+        s, c = _e.VxWspConfig(), self.config
+        s.struct_size = C.sizeof(_e.VxWspConfig)
+        s.n_mels, s.d_model = int(c.num_mel_bins), int(c.d_model)
+        s.enc_layers, s.enc_heads, s.enc_ffn = int(c.encoder_layers), int(c.encoder_attention_heads), int(c.encoder_ffn_dim)
+        s.dec_layers, s.dec_heads, s.dec_ffn = int(c.decoder_layers), int(c.decoder_attention_heads), int(c.decoder_ffn_dim)
+        s.max_source_positions, s.max_target_positions = int(c.max_source_positions), int(c.max_target_positions)
+        s.vocab = int(c.vocab_size)
+        s.activation = 0 if c.activation_function == "gelu" else 1
+        s.tie_proj = int(bool(c.tie_word_embeddings))
+        s.eos_token_id = self.eos_token_id
+        s.max_batch = self.max_batch
+        s.flags = _e.VX_WSP_KEEP_TAPS if self.keep_taps else 0
+        return s
+
+    def _create(self):
+        lib = _e.load_library()
+        h = C.c_void_p()
+        _e._check(lib.vx_wsp_create(C.byref(self._config_struct()), C.byref(h)))
+        self._h, self._bound = h, None
+        try:
+            sup = [int(t) for t in (self.generation.suppress_tokens or ())]
+            beg = [int(t) for t in (self.generation.begin_suppress_tokens or ())]
+            _e._check(lib.vx_wsp_set_suppress(self._h, (C.c_int32 * max(len(sup), 1))(*sup), len(sup), (C.c_int32 * max(len(beg), 1))(*beg),
+                                              len(beg)))
+            if self._weights is not None:
+                for k, t in list(self._weights.items()) + [("mel_filters", self.mel_basis)]:
+                    shape = (C.c_int64 * t.dim())(*t.shape)
+                    _e._check(lib.vx_wsp_set_weight(self._h, k.encode(), t.data_ptr(), shape, t.dim()))
+                _e._check(lib.vx_wsp_finalize(self._h))
+        except Exception:
+            self.close()
+            raise
+
+    def _handle(self):
+        if self._h is None:
+            self._create()
+        return self._h
+
+    def timings(self) -> Dict[str, float]:
+        """Of the last call: host ms, workspace and weight bytes, decode steps enqueued, device ms of log-mel / encoder / token loop."""
+        out = (C.c_double * 7)()
+        _e._check(_e.load_library().vx_wsp_get_timings(self._handle(), out, 7))
+        return dict(zip(("host_ms", "workspace_bytes", "weight_bytes", "steps", "logmel_ms", "encoder_ms", "loop_ms"), out))
+
+    def workspace_bytes(self) -> int:
+        out = (C.c_double * 4)()
+        _e._check(_e.load_library().vx_wsp_get_timings(self._handle(), out, 4))
+        return int(out[1])
+
+    def load_state_dict(self, sd: dict):
+        """Takes the `transformers` key layout (`model.encoder...`, `model.decoder...`, `proj_out.weight`; a tied checkpoint may
+        carry `proj_out.weight` or not); missing and unexpected keys and wrong shapes raise by name.  Returns self."""
+        want = expected_keys(self.config)
+        w = dict(sd)
+        if self.config.tie_word_embeddings:
+            w.pop("proj_out.weight", None)
+        missing = sorted(k for k in want if k not in w)
+        unexpected = sorted(k for k in w if k not in want)
+        if missing or unexpected:
+            raise KeyError(f"WhisperRecognizer.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
+        for k, shape in want.items():
+            if tuple(w[k].shape) != tuple(shape):
+                raise ValueError(f"WhisperRecognizer.load_state_dict: {k} is {tuple(w[k].shape)}, expected {tuple(shape)}")
+        self._weights = {k: w[k].detach().to("cpu", torch.float32).contiguous() for k in want}
+        self.close()
+        self._create()
+        return self
+
+    def to(self, device):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self._bound is not None and self._bound != self.device:
+            self.close()  # another device gets a fresh handle on its first call
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            _e.load_library().vx_wsp_destroy(self._h)
+            self._h = self._bound = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- recognition --------------------------------------------------------------------------------
+    def prompt_prefix(self, language: Optional[str] = "en", task: Optional[str] = "transcribe") -> List[int]:
+        """`[decoder_start, lang_to_id[...], task_to_id[...], no_timestamps]` from the generation config; an English-only checkpoint
+        has no language and task ids and gets `[decoder_start, no_timestamps]`."""
+        g = self.generation
+        ids = [self.decoder_start_token_id]
+        if g.lang_to_id and g.task_to_id:
+            key = language if language in g.lang_to_id else f"<|{language}|>"
+            if key not in g.lang_to_id:
+                raise ValueError(f"language = {language!r} is not in the generation config's lang_to_id")
+            if task not in g.task_to_id:
+                raise ValueError(f"task = {task!r} is not in the generation config's task_to_id")
+            ids += [int(g.lang_to_id[key]), int(g.task_to_id[task])]
+        if g.no_timestamps_token_id is not None:
+            ids.append(int(g.no_timestamps_token_id))
+        return ids
+
+    def _prepare(self, wavs, sr: int) -> List[torch.Tensor]:
+        if isinstance(wavs, torch.Tensor):
+            wavs = [wavs]
+        ws = []
+        for w in wavs:
+            assert isinstance(w, torch.Tensor) and w.dtype == torch.float32, "waveforms are float32 tensors"
+            assert w.numel() == w.shape[-1], "one mono utterance per entry: (L,), (1, L) or (1, 1, L)"
+            ws.append(w.detach().reshape(-1))
+        if self.device.type != "cuda":
+            raise RuntimeError("valle_amd.WhisperRecognizer runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        if self._weights is None:
+            raise RuntimeError("WhisperRecognizer has no weights: call load_state_dict first")
+        ws = [w.to(self.device).contiguous() for w in ws]
+        if int(sr) != SAMPLE_RATE:
+            from .codec import Resampler
+
+            if sr not in self._resamplers:
+                self._resamplers[sr] = Resampler(int(sr), SAMPLE_RATE, max_batch=self.max_batch)
+            rs = self._resamplers[sr].to(self.device)
+            out = []
+            for i in range(0, len(ws), self.max_batch):
+                out += [o.reshape(-1) for o in rs.resample_batch(ws[i:i + self.max_batch])]
+            ws = out
+        return ws
+
+    def _recognize_raw(self, wav_ptrs, lengths, prompts: Sequence[Sequence[int]], max_new: Sequence[int], forced, out_stride: int, tokens_ptr,
+                       logprobs_ptr, counts_ptr, stops_ptr):
+        """vx_wsp_recognize on raw pointers (the argument checks run before any device work)."""
+        n = len(wav_ptrs)
+        wp = (C.c_void_p * n)(*wav_ptrs)
+        L = (C.c_int32 * n)(*lengths)
+        ps = max(max((len(p) for p in prompts), default=1), 1)
+        flat = [0] * (n * ps)
+        for i, p in enumerate(prompts):
+            flat[i * ps:i * ps + len(p)] = [int(t) for t in p]
+        fo = None
+        if forced is not None:
+            ff = [0] * (n * out_stride)
+            for i, y in enumerate(forced):
+                ff[i * out_stride:i * out_stride + len(y)] = [int(t) for t in y]
+            fo = (C.c_int32 * len(ff))(*ff)
+        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
+        h = self._handle()
+        if self.device.type == "cuda":
+            self._bound = self.device
+        _e._check(_e.load_library().vx_wsp_recognize(h, n, wp, L, (C.c_int32 * len(flat))(*flat), (C.c_int32 * n)(*[len(p) for p in prompts]), ps,
+                                                     (C.c_int32 * n)(*[int(m) for m in max_new]), fo, int(out_stride), tokens_ptr, logprobs_ptr,
+                                                     counts_ptr, stops_ptr, stream))
+
+    def _prompts(self, n, language, task, prompt_ids):
+        if prompt_ids is None:
+            return [self.prompt_prefix(language, task)] * n
+        if len(prompt_ids) == 0:
+            raise ValueError("prompt_ids is empty: the decoder input starts with at least decoder_start_token_id")
+        if isinstance(prompt_ids[0], int):
+            return [list(prompt_ids)] * n
+        assert len(prompt_ids) == n, "one prompt per waveform"
+        return [list(p) for p in prompt_ids]
+
+    @torch.no_grad()
+    def _run(self, ws: List[torch.Tensor], prompts, max_new: List[int], forced):
+        Tt = int(self.config.max_target_positions)
+        for i, p in enumerate(prompts):
+            if len(p) == 0:
+                raise ValueError(f"prompt_ids of utterance {i} is empty: the decoder input starts with at least decoder_start_token_id")
+            if len(p) >= Tt:
+                raise ValueError(f"prompt_ids of utterance {i} has {len(p)} tokens: no room under max_target_positions = {Tt}")
+        results = []
+        for i in range(0, len(ws), self.max_batch):
+            chunk, pr, mn = ws[i:i + self.max_batch], prompts[i:i + self.max_batch], max_new[i:i + self.max_batch]
+            fc = None if forced is None else forced[i:i + self.max_batch]
+            n, stride = len(chunk), max(min(max(mn), Tt), 1)
+            tok = torch.full((n, stride), -1, dtype=torch.int32, device=self.device)
+            lp = torch.zeros((n, stride), dtype=torch.float32, device=self.device)
+            cnt = torch.zeros(n, dtype=torch.int32, device=self.device)
+            stop = torch.zeros(n, dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                self._recognize_raw([w.data_ptr() for w in chunk], [w.numel() for w in chunk], pr, [min(m, stride) for m in mn], fc, stride,
+                                    tok.data_ptr(), lp.data_ptr(), cnt.data_ptr(), stop.data_ptr())
+            tok, lp, cnt, stop = tok.cpu(), lp.cpu().double(), cnt.cpu().tolist(), stop.cpu().tolist()
+            for u in range(n):
+                ids, lps = tok[u, :cnt[u]].tolist(), lp[u, :cnt[u]].tolist()
+                text = decode_tokens(ids, self.id_to_token, self.first_special) if self.vocab is not None else ""
+                results.append(WhisperTranscript(text, ids, lps, float(sum(lps)), STOP_REASONS[stop[u]]))
+        return results
+
+    def recognize(self, wavs: Union[torch.Tensor, Sequence[torch.Tensor]], sr: int = 24000, language: Optional[str] = "en",
+                  task: Optional[str] = "transcribe", prompt_ids=None, max_new_tokens: Optional[int] = None,
+                  normalize: bool = False) -> List[WhisperTranscript]:
+        """One waveform or a list of ragged ones, float32 (L,), (1, L) or (1, 1, L) at `sr` -> one `WhisperTranscript` per utterance by
+        greedy decoding.  Audio at another rate than 16 kHz goes through the GPU `Resampler` first; audio longer than a chunk is
+        refused (long-form transcription is not built).  `prompt_ids` (one list, or one per utterance) replaces the prefix
+        `prompt_prefix(language, task)`.  Without `max_new_tokens` an utterance runs until eos or `max_target_positions`.  More
+        than `max_batch` utterances are served in several calls; every utterance is bitwise what it is alone.  `normalize` exists
+        for `recognition_error`'s call and must stay False: Whisper's front end has no such option."""
+        if normalize:
+            raise ValueError("normalize: Whisper's log-mel front end has no input normalisation")
+        ws = self._prepare(wavs, sr)
+        prompts = self._prompts(len(ws), language, task, prompt_ids)
+        Tt = int(self.config.max_target_positions)
+        if max_new_tokens is not None and int(max_new_tokens) < 1:
+            raise ValueError(f"max_new_tokens = {max_new_tokens}")
+        mn = [Tt if max_new_tokens is None else int(max_new_tokens) for p in prompts]
+        return self._run(ws, prompts, mn, None)
+
+    def score_tokens(self, wavs, token_ids: Sequence[Sequence[int]], sr: int = 24000, language: Optional[str] = "en",
+                     task: Optional[str] = "transcribe", prompt_ids=None) -> TokenScores:
+        """Teacher forcing: per utterance the negative log-likelihood of the given tokens after the prompt (each token's
+        log-probability is taken over the same processed row greedy decoding reads), the mean per token and the per-token values."""
+        ws = self._prepare(wavs, sr)
+        if len(token_ids) and isinstance(token_ids[0], int):
+            token_ids = [token_ids]
+        assert len(token_ids) == len(ws), "one token list per waveform"
+        toks = [[int(t) for t in y] for y in token_ids]
+        for i, y in enumerate(toks):
+            if len(y) == 0:
+                raise ValueError(f"token_ids of utterance {i} is empty")
+        prompts = self._prompts(len(ws), language, task, prompt_ids)
+        res = self._run(ws, prompts, [len(y) for y in toks], toks)
+        nll = [-r.logprob for r in res]
+        return TokenScores(nll, sum(nll) / sum(len(y) for y in toks), [r.token_logprobs for r in res])
+
+    def read_tap(self, name: str, utt: int, rows: int, width: int) -> torch.Tensor:
+        """(rows, width) float32 on the host: a tap of the last call (`vx_wsp_read`; the parity tests)."""
+        out = torch.empty((rows, width), dtype=torch.float32)
+        _e._check(_e.load_library().vx_wsp_read(self._handle(), name.encode(), int(utt), out.data_ptr(), out.numel()))
+        return out
