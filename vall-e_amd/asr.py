@@ -24,7 +24,6 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import json
 import math
 import re
 from typing import Dict, List, NamedTuple, Optional, Sequence, Union
@@ -32,9 +31,9 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Union
 import torch
 
 from . import engine as _e
+from ._speech_handle import SAMPLE_RATE, W2vHandle, config_from_any, w2v_backbone_keys, w2v_synthetic_state_dict
 from .spk import canonical_state_dict as _canonical
 
-SAMPLE_RATE = 16000
 HEAD_DIMS = (16, 32, 64)
 EDIT_MAX_LEN = 2048  # tokens per side of a pair (csrc/asr_kernels.hpp)
 FALIGN_MAX_TARGETS = 1000  # target tokens per utterance of an alignment (csrc/falign_kernels.hpp)
@@ -70,52 +69,13 @@ class RecognizerConfig:
     @classmethod
     def from_any(cls, cfg) -> "RecognizerConfig":
         """A dict (a checkpoint's `config.json`), a path to one, or any object with the attributes."""
-        if isinstance(cfg, cls):
-            return cfg
-        if isinstance(cfg, str):
-            with open(cfg) as f:
-                cfg = json.load(f)
-        names = [f.name for f in dataclasses.fields(cls)]
-        if isinstance(cfg, dict):
-            return cls(**{k: cfg[k] for k in names if k in cfg and cfg[k] is not None})
-        return cls(**{k: getattr(cfg, k) for k in names if getattr(cfg, k, None) is not None})
+        return config_from_any(cls, cfg)
 
 
 def expected_keys(c: RecognizerConfig) -> Dict[str, tuple]:
     """canonical key -> shape, as vx_asr_create lays them out."""
-    d = int(c.hidden_size)
-    layer = c.feat_extract_norm == "layer"
-    keys: Dict[str, tuple] = {}
-
-    def lin(name, n, k):
-        keys[name + ".weight"], keys[name + ".bias"] = (n, k), (n,)
-
-    def norm(name, n):
-        keys[name + ".weight"], keys[name + ".bias"] = (n,), (n,)
-
-    cin = 1
-    for i, (co, k) in enumerate(zip(c.conv_dim, c.conv_kernel)):
-        keys[f"feature_extractor.conv_layers.{i}.conv.weight"] = (int(co), cin, int(k))
-        if c.conv_bias:
-            keys[f"feature_extractor.conv_layers.{i}.conv.bias"] = (int(co),)
-        if i == 0 or layer:
-            norm(f"feature_extractor.conv_layers.{i}.layer_norm", int(co))
-        cin = int(co)
-    if c.feat_proj_layer_norm:
-        norm("feature_projection.layer_norm", cin)
-    lin("feature_projection.projection", d, cin)
-    keys["encoder.pos_conv_embed.conv.weight"] = (d, d // int(c.num_conv_pos_embedding_groups), int(c.num_conv_pos_embeddings))
-    keys["encoder.pos_conv_embed.conv.bias"] = (d,)
-    norm("encoder.layer_norm", d)
-    for l in range(int(c.num_hidden_layers)):
-        pre = f"encoder.layers.{l}."
-        for nm in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            lin(pre + "attention." + nm, d, d)
-        norm(pre + "layer_norm", d)
-        lin(pre + "feed_forward.intermediate_dense", int(c.intermediate_size), d)
-        lin(pre + "feed_forward.output_dense", d, int(c.intermediate_size))
-        norm(pre + "final_layer_norm", d)
-    lin("lm_head", int(c.vocab_size), d)
+    keys = w2v_backbone_keys(c, c.feat_extract_norm == "layer")
+    keys["lm_head.weight"], keys["lm_head.bias"] = (int(c.vocab_size), int(c.hidden_size)), (int(c.vocab_size),)
     return keys
 
 
@@ -131,32 +91,8 @@ def synthetic_state_dict(config, seed: int = 0, prefix: str = "wav2vec2.", head_
     that put the GELUs in their curved range); `head_scale` spreads the logits so that the argmax of nearly every frame is decided by
     far more than fp32 rounding."""
     c = RecognizerConfig.from_any(config)
-    g = torch.Generator().manual_seed(int(seed))
-    sd: Dict[str, torch.Tensor] = {}
-
-    def rnd(*shape, scale=1.0):
-        return torch.randn(*shape, generator=g) * scale
-
-    for k, shape in expected_keys(c).items():
-        name = k if k.startswith("lm_head") else prefix + k
-        if k == "encoder.pos_conv_embed.conv.weight":
-            sd[prefix + "encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = 0.5 + torch.rand(1, 1, shape[2], generator=g)
-            sd[prefix + "encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = rnd(*shape)
-        elif k.endswith("layer_norm.weight"):
-            sd[name] = 1.0 + rnd(*shape, scale=0.2)
-        elif k.endswith("layer_norm.bias"):
-            sd[name] = rnd(*shape, scale=0.5)
-        elif k.endswith(".bias"):
-            sd[name] = rnd(*shape, scale=0.1)
-        elif k == "feature_extractor.conv_layers.0.conv.weight":
-            sd[name] = rnd(*shape, scale=1.0)
-        else:  # Linear and convolution weights: unit gain over the fan-in
-            fan_in = 1
-            for s in shape[1:]:
-                fan_in *= s
-            sd[name] = rnd(*shape, scale=(head_scale if k == "lm_head.weight" else 1.5) / math.sqrt(fan_in))
-    sd[prefix + "masked_spec_embed"] = rnd(int(c.hidden_size))
-    return sd
+    own = {"lm_head.weight": (0.0, head_scale / math.sqrt(int(c.hidden_size)))}
+    return w2v_synthetic_state_dict(expected_keys(c), seed, prefix, lambda k: k.startswith("lm_head"), own, int(c.hidden_size))
 
 
 @dataclasses.dataclass
@@ -178,13 +114,14 @@ def ids_to_text(ids: Sequence[int], id_to_token: Dict[int, str], word_delimiter:
     return " ".join("".join(out).split())
 
 
-class SpeechRecognizer:
+class SpeechRecognizer(W2vHandle):
     """`SpeechRecognizer(config, vocab, max_batch=32, max_seconds=20.0, state_dict=None)`: `config` is a `RecognizerConfig`, a dict or
     path of the checkpoint's `config.json`, or any object with the `Wav2Vec2Config` / `HubertConfig` attributes; `vocab` is the
     checkpoint's `vocab.json` mapping token -> id, with `|` as the word delimiter and `<pad>` as the CTC blank unless `blank` names
     another token.  A call serves up to `max_batch` (<= 64) utterances of up to `max_seconds` at 16 kHz each.  Adapters,
     `conv_pos_batch_norm`, activations other than GELU, head dimensions other than 16 / 32 / 64 and a feature encoder norm that does
     not go with the encoder (`group` with post-norm, `layer` with stable) raise NotImplementedError naming the field."""
+    _PREFIX, _NAME = "vx_asr", "SpeechRecognizer"
 
     def __init__(self, config, vocab: Dict[str, int], max_batch: int = 32, max_seconds: float = 20.0, state_dict: Optional[dict] = None,
                  keep_taps: bool = False, blank: str = "<pad>", word_delimiter: str = "|"):
@@ -214,12 +151,7 @@ class SpeechRecognizer:
         self.special = tuple(t for t in self.vocab if re.fullmatch(r"<.*>", t))
         self.max_batch, self.max_samples = int(max_batch), int(round(float(max_seconds) * SAMPLE_RATE))
         self.keep_taps = bool(keep_taps)
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None
-        self._weights: Optional[Dict[str, torch.Tensor]] = None
-        self._resamplers: Dict[int, object] = {}
-        self._create()  # a geometry the kernels do not serve is refused here
+        self._init_handle()
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -227,134 +159,31 @@ class SpeechRecognizer:
     def _config_struct(self) -> "_e.VxAsrConfig":
         s, c = _e.VxAsrConfig(), self.config
         s.struct_size = C.sizeof(_e.VxAsrConfig)
-        s.hidden, s.layers, s.heads, s.ffn = int(c.hidden_size), int(c.num_hidden_layers), int(c.num_attention_heads), int(c.intermediate_size)
-        s.n_conv = len(c.conv_dim)
-        for i, (dm, k, st) in enumerate(zip(c.conv_dim, c.conv_kernel, c.conv_stride)):
-            s.conv_dim[i], s.conv_kernel[i], s.conv_stride[i] = int(dm), int(k), int(st)
-        s.conv_bias = int(bool(c.conv_bias))
-        s.pos_kernel, s.pos_groups = int(c.num_conv_pos_embeddings), int(c.num_conv_pos_embedding_groups)
+        self._fill_backbone(s)
         s.vocab, s.blank = int(c.vocab_size), self.blank_id
         s.feat_extract_norm = int(c.feat_extract_norm == "layer")
         s.do_stable_layer_norm = int(bool(c.do_stable_layer_norm))
         s.feat_proj_layer_norm = int(bool(c.feat_proj_layer_norm))
         s.add_adapter, s.conv_pos_batch_norm = int(bool(c.add_adapter)), int(bool(c.conv_pos_batch_norm))
         s.activation = 0
-        s.layer_norm_eps = float(c.layer_norm_eps)
-        s.max_batch, s.max_samples = self.max_batch, self.max_samples
         s.flags = _e.VX_ASR_KEEP_TAPS if self.keep_taps else 0
         return s
-
-    def _create(self):
-        lib = _e.load_library()
-        h = C.c_void_p()
-        _e._check(lib.vx_asr_create(C.byref(self._config_struct()), C.byref(h)))
-        self._h, self._bound = h, None
-        if self._weights is not None:
-            try:
-                for k, t in self._weights.items():
-                    shape = (C.c_int64 * t.dim())(*t.shape)
-                    _e._check(lib.vx_asr_set_weight(self._h, k.encode(), t.data_ptr(), shape, t.dim()))
-                _e._check(lib.vx_asr_finalize(self._h))
-            except Exception:
-                self.close()
-                raise
-
-    def _handle(self):
-        if self._h is None:
-            self._create()
-        return self._h
-
-    def num_frames(self, n_samples: int) -> int:
-        """Frames the feature encoder leaves of `n_samples` samples at 16 kHz (host only)."""
-        return int(_e.load_library().vx_asr_frames(self._handle(), int(n_samples)))
-
-    @property
-    def max_frames(self) -> int:
-        return self.num_frames(self.max_samples)
 
     @property
     def min_samples(self) -> int:
         """The shortest utterance served (one encoder frame): 400 samples at the default kernels and strides."""
-        return int(_e.load_library().vx_asr_min_samples(self._handle()))
-
-    def workspace_bytes(self) -> int:
-        out = (C.c_double * 4)()
-        _e._check(_e.load_library().vx_asr_get_timings(self._handle(), out, 4))
-        return int(out[1])
+        return super().min_samples
 
     def load_state_dict(self, sd: dict):
         """Takes the `transformers` key layout (see `canonical_state_dict`); missing and unexpected keys and wrong shapes raise by
         name.  Returns self."""
-        w = canonical_state_dict(sd)
-        want = expected_keys(self.config)
-        missing = sorted(k for k in want if k not in w)
-        unexpected = sorted(k for k in w if k not in want)
-        if missing or unexpected:
-            raise KeyError(f"SpeechRecognizer.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        for k, shape in want.items():
-            if tuple(w[k].shape) != tuple(shape):
-                raise ValueError(f"SpeechRecognizer.load_state_dict: {k} is {tuple(w[k].shape)}, expected {tuple(shape)}")
-        self._weights = {k: w[k].to(torch.float32).contiguous() for k in want}
-        self.close()
-        self._create()
-        return self
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_asr_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._check_state_dict(expected_keys(self.config), canonical_state_dict(sd))
 
     # ---- recognition --------------------------------------------------------------------------------
-    def _prepare(self, wavs, sr: int) -> List[torch.Tensor]:
-        if isinstance(wavs, torch.Tensor):
-            wavs = [wavs]
-        ws = []
-        for w in wavs:
-            assert isinstance(w, torch.Tensor) and w.dtype == torch.float32, "waveforms are float32 tensors"
-            assert w.numel() == w.shape[-1], "one mono utterance per entry: (L,), (1, L) or (1, 1, L)"
-            ws.append(w.detach().reshape(-1))
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.SpeechRecognizer runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
-        if self._weights is None:
-            raise RuntimeError("SpeechRecognizer has no weights: call load_state_dict first")
-        ws = [w.to(self.device).contiguous() for w in ws]
-        if int(sr) != SAMPLE_RATE:
-            from .codec import Resampler
-
-            if sr not in self._resamplers:
-                self._resamplers[sr] = Resampler(int(sr), SAMPLE_RATE, max_batch=self.max_batch)
-            rs = self._resamplers[sr].to(self.device)
-            out = []
-            for i in range(0, len(ws), self.max_batch):
-                out += [o.reshape(-1) for o in rs.resample_batch(ws[i:i + self.max_batch])]
-            ws = out
-        return ws
-
     def _recognize_raw(self, wav_ptrs, lengths, normalize, tokens_ptr, frames_ptr, counts_ptr, logprob_ptr, logits_ptr):
         """vx_asr_recognize on raw pointers (the argument checks run before any device work)."""
-        n = len(wav_ptrs)
-        wp = (C.c_void_p * n)(*wav_ptrs)
-        L = (C.c_int32 * n)(*lengths)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_asr_recognize(h, n, wp, L, _e.VX_ASR_NORMALIZE if normalize else 0, tokens_ptr, frames_ptr, counts_ptr,
-                                                     logprob_ptr, logits_ptr, stream))
+        self._call("recognize", wav_ptrs, lengths, _e.VX_ASR_NORMALIZE if normalize else 0, tokens_ptr, frames_ptr, counts_ptr, logprob_ptr,
+                   logits_ptr)
 
     @torch.no_grad()
     def _run(self, wavs, sr, normalize, want_logits, after_chunk=None):
@@ -397,12 +226,6 @@ class SpeechRecognizer:
     def logits(self, wavs, sr: int = 24000, normalize: bool = False) -> List[torch.Tensor]:
         """Per utterance the (frames, vocab) float32 logits on the device."""
         return self._run(wavs, sr, normalize, True)[1]
-
-    def read_tap(self, name: str, utt: int, rows: int, width: int) -> torch.Tensor:
-        """(rows, width) float32 on the host: a tap of the last call (`vx_asr_read`; the parity tests)."""
-        out = torch.empty((rows, width), dtype=torch.float32)
-        _e._check(_e.load_library().vx_asr_read(self._handle(), name.encode(), int(utt), out.data_ptr(), out.numel()))
-        return out
 
     # ---- a known text against the audio -------------------------------------------------------------
     @property

@@ -1,7 +1,8 @@
-// Host side shared by the two units built on spk_kernels.hpp (spk.hip, asr.hip): the weight table of a handle, the packing of its
-// tensors for the row GEMM and the launches of the shared kernels.  A handle type G has `std::map<std::string, HostW> w`,
-// `std::vector<float> packed` and `bool finalized`.  Everything here has internal linkage: each unit launches its own copy of the
-// kernels (they are `static` in spk_kernels.hpp).
+// The leaf pieces of the host side of the units built on spk_kernels.hpp (spk.hip, asr.hip, whisper.hip): the weight table of a
+// handle, the packing of one tensor for the row GEMM and the launches of the shared kernels.  What is built from them - the encoder
+// layer, the Wav2Vec2 backbone, the handle scaffolding - is w2v_host.hpp, which the units include.  A handle type G has
+// `std::map<std::string, HostW> w`, `std::vector<float> packed` and `bool finalized` (w2v_host.hpp's SpeechHandle).  Everything here
+// has internal linkage: each unit launches its own copy of the kernels (they are `static` in spk_kernels.hpp).
 #pragma once
 #include <math.h>
 #include <stdint.h>

@@ -1,6 +1,7 @@
 // Whisper recogniser (WhisperForConditionalGeneration, greedy) behind the C ABI (include/vallex.h, vx_wsp_*).  The encoder runs on the
-// speaker encoder's row GEMM, plain attention and LayerNorm (spk_kernels.hpp through spk_host.hpp) and asr_kernels.hpp's residual-folding
-// LayerNorm; the log-mel front end and the token loop are whisper_kernels.hpp.  A translation unit and a handle of its own, like asr.hip.
+// speaker encoder's row GEMM, plain attention and LayerNorm (spk_kernels.hpp through spk_host.hpp); its layer packing, its pre-norm layer
+// loop (the recogniser's stable flavour) and the handle scaffolding are w2v_host.hpp's.  This unit keeps the log-mel front end, conv1
+// and conv2, the decoder and the token loop (whisper_kernels.hpp).  A translation unit and a handle of its own, like asr.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -14,8 +15,7 @@
 #include <vector>
 
 #undef VX_STAMPS  // the in-kernel stamps write device globals of engine.hip's unit, out of this unit's reach
-#include "spk_host.hpp"
-#include "asr_kernels.hpp"
+#include "w2v_host.hpp"
 #include "whisper_kernels.hpp"
 
 using namespace vx;
@@ -24,10 +24,8 @@ namespace {
 
 constexpr int WSP_POLL = 8;  // decode steps enqueued between two reads of the finished flags
 
-struct WspEncLayer {
-  SpkLin qkv, out, ff1, ff2;
-  SpkNorm ln1, ln2;
-};
+constexpr EncNames WSP_LAYER{"self_attn", "self_attn_layer_norm", "fc1", "fc2", "final_layer_norm"};
+
 struct WspDecLayer {
   SpkLin qkv, out, cq, ckv, cout, ff1, ff2;
   SpkNorm ln1, ln2, ln3;
@@ -39,11 +37,9 @@ struct WspPlan {
          cache = 0, cache_stride = 0, x = 0, dn = 0, dqkv = 0, datt = 0, dq = 0, dff = 0, logits = 0, tmax = 0, tap = 0, total = 0;
 };
 
-struct WspDev {
-  DevBuf<float> w, ws;
+struct WspDev : SpeechDev {
   DevBuf<unsigned char> suppress;
   DevBuf<int> state;  // cur | pos | count | finished, [max_batch] each
-  CallStage stage;
   int* fin_host = nullptr;  // pinned [max_batch]
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   ~WspDev() {
@@ -55,27 +51,20 @@ struct WspDev {
 
 }  // namespace
 
-struct vx_wsp {
+struct vx_wsp : SpeechHandle<WspDev> {
   vx_wsp_config cfg{};
-  std::map<std::string, HostW> w;
-  bool finalized = false;
   int P = 0, F = 0, Tt = 0, tiles = 0;
   long chunk = 0;
   WspPlan plan;
   std::vector<unsigned char> suppress;  // [vocab]
-  std::vector<float> packed;
   size_t window = 0, dft = 0, dft_sin = 0, mel = 0, enc_pos = 0, tok_emb = 0, dec_pos = 0;
   SpkLin conv1, conv2, head;
   SpkNorm enc_ln, dec_ln;
-  std::vector<WspEncLayer> enc;
+  std::vector<EncLayer> enc;
   std::vector<WspDecLayer> dec;
-  int device = -1;
-  std::unique_ptr<WspDev> dev;
   // the last call, for vx_wsp_read
-  int last_n = 0;
   std::vector<int> last_prompt;  // per utterance
-  hipStream_t last_stream = nullptr;
-  double last_ms = 0.0, last_steps = 0.0;
+  double last_steps = 0.0;
 };
 
 namespace {
@@ -121,19 +110,12 @@ size_t stage_bytes(const vx_wsp* g) {
 }
 
 int wsp_init_device(vx_wsp* g) {
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  g->device = dev;
-  g->dev.reset(new WspDev());
+  VXC(init_device(g, new WspDev(), g->plan.total, stage_bytes(g)));
   WspDev& d = *g->dev;
   const size_t MB = (size_t)g->cfg.max_batch;
-  VXC(d.w.alloc(g->packed.size() + 4));
-  HIPC(hipMemcpy(d.w.get(), g->packed.data(), g->packed.size() * sizeof(float), hipMemcpyHostToDevice));
-  VXC(d.ws.alloc(g->plan.total + 4));
   VXC(d.suppress.alloc(g->suppress.size() + 4));
   HIPC(hipMemcpy(d.suppress.get(), g->suppress.data(), g->suppress.size(), hipMemcpyHostToDevice));
   VXC(d.state.alloc(4 * MB));
-  VXC(d.stage.init(stage_bytes(g)));
   HIPC(hipHostMalloc((void**)&d.fin_host, MB * sizeof(int)));
   for (hipEvent_t& e : d.ev) HIPC(hipEventCreate(&e));
   return VX_OK;
@@ -143,12 +125,6 @@ struct CallCtx : SpkCall {
   const vx_wsp* g;
   float* ws;
 };
-
-int run_add_ln(const CallCtx& x, const SpkNorm& nm, const float* a, const float* b, float* sum, float* y, long M, int d) {
-  asr_add_layernorm<<<(unsigned)((M + 3) / 4), 256, 0, x.s>>>(a, b, x.W + nm.w, x.W + nm.b, sum, y, M, d, x.eps);
-  HIPC(hipGetLastError());
-  return VX_OK;
-}
 
 int run_skinny(const CallCtx& x, const SpkLin& l, const float* in, float* out, const float* res, int act) {
   WspSkinnyArgs a{};
@@ -181,23 +157,12 @@ int run_front_and_encoder(const CallCtx& x, const float* const* wav, const int* 
   VXC(run_lin(x, g->conv1, ws + p.mel, c.n_mels, ws + p.c1, (long)n * F, SPK_ACT_GELU, 0, 0));
   VXC(run_lin(x, g->conv2, ws + p.c1, d, ws + p.feat, (long)n * P, SPK_ACT_GELU, 1, 0));
   const long M = (long)n * P;
-  const bool keep = (c.flags & VX_WSP_KEEP_TAPS) != 0;
-  auto hid = [&](int l) { return ws + p.hid + p.hid_stride * (size_t)(keep ? l : (l & 1)); };
-  wsp_add_layernorm<<<(unsigned)((M + 3) / 4), 256, 0, x.s>>>(ws + p.feat, x.W + g->enc_pos, P, x.W + g->enc[0].ln1.w, x.W + g->enc[0].ln1.b, hid(0),
-                                                               ws + p.nrm, M, d, x.eps);
+  EncRun e = enc_run(ws, p, (c.flags & VX_WSP_KEEP_TAPS) != 0);
+  e.M = M; e.d = d; e.H = c.enc_heads; e.hd = 64; e.ffn = c.enc_ffn; e.Tmax = P; e.table = 1; e.hseg = hseg1;
+  wsp_add_layernorm<<<(unsigned)((M + 3) / 4), 256, 0, x.s>>>(ws + p.feat, x.W + g->enc_pos, P, x.W + g->enc[0].ln1.w, x.W + g->enc[0].ln1.b,
+                                                               e.hidden(0), e.nrm, M, d, x.eps);
   HIPC(hipGetLastError());
-  const int L = c.enc_layers;
-  for (int l = 0; l < L; ++l) {
-    const WspEncLayer& ly = g->enc[l];
-    VXC(run_lin(x, ly.qkv, ws + p.nrm, d, ws + p.qkv, M, SPK_ACT_NONE));
-    VXC(run_attn(x, x.table(1), hseg1, ws + p.qkv, nullptr, nullptr, ws + p.att, c.enc_heads, d, 64, P));
-    VXC(run_lin(x, ly.out, ws + p.att, d, ws + p.tmp, M, SPK_ACT_NONE));
-    VXC(run_add_ln(x, ly.ln2, hid(l), ws + p.tmp, ws + p.mid, ws + p.nrm, M, d));
-    VXC(run_lin(x, ly.ff1, ws + p.nrm, d, ws + p.ff, M, SPK_ACT_GELU));
-    VXC(run_lin(x, ly.ff2, ws + p.ff, c.enc_ffn, ws + p.tmp, M, SPK_ACT_NONE));
-    if (l + 1 < L) VXC(run_add_ln(x, g->enc[l + 1].ln1, ws + p.mid, ws + p.tmp, hid(l + 1), ws + p.nrm, M, d));
-    else VXC(run_add_ln(x, g->enc_ln, ws + p.mid, ws + p.tmp, hid(l + 1), ws + p.enc, M, d));
-  }
+  VXC(run_prenorm_layers(x, e, g->enc, g->enc_ln, e.hidden(c.enc_layers), ws + p.enc));
   // every decoder layer's cross-attention keys and values, for the whole call
   for (int l = 0; l < c.dec_layers; ++l) VXC(run_lin(x, g->dec[l].ckv, ws + p.enc, d, ws + p.ckv + p.ckv_stride * (size_t)l, M, SPK_ACT_NONE));
   return VX_OK;
@@ -290,20 +255,6 @@ extern "C" int vx_wsp_create(const vx_wsp_config* cfg, vx_wsp** out) {
   make_plan(g.get());
 
   const int d = c.d_model;
-  auto norm_keys = [&](const std::string& nm) {
-    add_key(g.get(), nm + ".weight", {d});
-    add_key(g.get(), nm + ".bias", {d});
-  };
-  auto lin_keys = [&](const std::string& nm, int N, int K, bool bias = true) {
-    add_key(g.get(), nm + ".weight", {N, K});
-    if (bias) add_key(g.get(), nm + ".bias", {N});
-  };
-  auto attn_keys = [&](const std::string& nm) {
-    lin_keys(nm + ".q_proj", d, d);
-    lin_keys(nm + ".k_proj", d, d, false);
-    lin_keys(nm + ".v_proj", d, d);
-    lin_keys(nm + ".out_proj", d, d);
-  };
   add_key(g.get(), "mel_filters", {c.n_mels, WSP_BINS});
   add_key(g.get(), "model.encoder.conv1.weight", {d, c.n_mels, 3});
   add_key(g.get(), "model.encoder.conv1.bias", {d});
@@ -311,41 +262,28 @@ extern "C" int vx_wsp_create(const vx_wsp_config* cfg, vx_wsp** out) {
   add_key(g.get(), "model.encoder.conv2.bias", {d});
   add_key(g.get(), "model.encoder.embed_positions.weight", {g->P, d});
   for (int l = 0; l < c.enc_layers; ++l) {
-    const std::string pre = "model.encoder.layers." + std::to_string(l) + ".";
-    attn_keys(pre + "self_attn");
-    norm_keys(pre + "self_attn_layer_norm");
-    lin_keys(pre + "fc1", c.enc_ffn, d);
-    lin_keys(pre + "fc2", d, c.enc_ffn);
-    norm_keys(pre + "final_layer_norm");
+    enc_layer_keys(g.get(), "model.encoder.layers." + std::to_string(l) + ".", WSP_LAYER, d, c.enc_ffn, false);
   }
-  norm_keys("model.encoder.layer_norm");
+  norm_keys(g.get(), "model.encoder.layer_norm", d);
   add_key(g.get(), "model.decoder.embed_tokens.weight", {c.vocab, d});
   add_key(g.get(), "model.decoder.embed_positions.weight", {g->Tt, d});
   for (int l = 0; l < c.dec_layers; ++l) {
     const std::string pre = "model.decoder.layers." + std::to_string(l) + ".";
-    attn_keys(pre + "self_attn");
-    norm_keys(pre + "self_attn_layer_norm");
-    attn_keys(pre + "encoder_attn");
-    norm_keys(pre + "encoder_attn_layer_norm");
-    lin_keys(pre + "fc1", c.dec_ffn, d);
-    lin_keys(pre + "fc2", d, c.dec_ffn);
-    norm_keys(pre + "final_layer_norm");
+    attn_keys(g.get(), pre + "self_attn", d, false);
+    norm_keys(g.get(), pre + "self_attn_layer_norm", d);
+    attn_keys(g.get(), pre + "encoder_attn", d, false);
+    norm_keys(g.get(), pre + "encoder_attn_layer_norm", d);
+    lin_keys(g.get(), pre + "fc1", c.dec_ffn, d);
+    lin_keys(g.get(), pre + "fc2", d, c.dec_ffn);
+    norm_keys(g.get(), pre + "final_layer_norm", d);
   }
-  norm_keys("model.decoder.layer_norm");
+  norm_keys(g.get(), "model.decoder.layer_norm", d);
   if (!c.tie_proj) add_key(g.get(), "proj_out.weight", {c.vocab, d});
   *out = g.release();
   return VX_OK;
 }
 
-extern "C" void vx_wsp_destroy(vx_wsp* g) {
-  if (!g) return;
-  if (g->device >= 0) {
-    DevGuard guard(g->device);
-    (void)g->dev->stage.drain();
-    g->dev.reset();
-  }
-  delete g;
-}
+extern "C" void vx_wsp_destroy(vx_wsp* g) { destroy_handle(g); }
 
 extern "C" int vx_wsp_set_weight(vx_wsp* g, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
   return set_weight(g, "vx_wsp", key, data, shape, ndim);
@@ -368,11 +306,9 @@ extern "C" int vx_wsp_set_suppress(vx_wsp* g, const int32_t* ids, int32_t n_ids,
 extern "C" int vx_wsp_finalize(vx_wsp* g) {
   if (!g) return fail(VX_ERR_ARG, "vx_wsp_finalize: null handle");
   if (g->finalized) return VX_OK;
-  for (auto& kv : g->w)
-    if (!kv.second.set) return fail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
+  VXC(finalize_begin(g));
   const vx_wsp_config& c = g->cfg;
   const int d = c.d_model;
-  g->packed.clear();
   {  // the periodic Hann window and the cos / sin table, from fp64 with the argument reduced exactly
     std::vector<float> win(WSP_NFFT), tc((size_t)WSP_DFT_ROWS * WSP_FR_K, 0.f), ts((size_t)WSP_DFT_ROWS * WSP_FR_K, 0.f);
     const double w0 = 2.0 * M_PI / WSP_NFFT;
@@ -401,36 +337,9 @@ extern "C" int vx_wsp_finalize(vx_wsp* g) {
   g->conv2.off0 = -1;
   g->conv2.stride = 2;
   g->enc_pos = push(g->packed, g->w["model.encoder.embed_positions.weight"].data);
-  // q | k | v stacked, k without a bias
-  auto pack_qkv = [&](const std::string& nm) {
-    std::vector<float> wq, bq;
-    for (const char* s : {"q_proj", "k_proj", "v_proj"}) {
-      const HostW& w = g->w[nm + "." + s + ".weight"];
-      wq.insert(wq.end(), w.data.begin(), w.data.end());
-      if (strcmp(s, "k_proj") == 0) {
-        bq.insert(bq.end(), (size_t)d, 0.f);
-      } else {
-        const HostW& b = g->w[nm + "." + s + ".bias"];
-        bq.insert(bq.end(), b.data.begin(), b.data.end());
-      }
-    }
-    SpkLin l;
-    l.w = push(g->packed, wq);
-    l.b = push(g->packed, bq);
-    l.has_bias = true; l.C = d; l.N = 3 * d;
-    return l;
-  };
-  g->enc.assign(c.enc_layers, WspEncLayer());
-  for (int l = 0; l < c.enc_layers; ++l) {
-    const std::string pre = "model.encoder.layers." + std::to_string(l) + ".";
-    WspEncLayer& ly = g->enc[l];
-    ly.qkv = pack_qkv(pre + "self_attn");
-    ly.out = pack_linear(g, pre + "self_attn.out_proj", d, d);
-    ly.ln1 = pack_norm(g, pre + "self_attn_layer_norm");
-    ly.ff1 = pack_linear(g, pre + "fc1", c.enc_ffn, d);
-    ly.ff2 = pack_linear(g, pre + "fc2", d, c.enc_ffn);
-    ly.ln2 = pack_norm(g, pre + "final_layer_norm");
-  }
+  g->enc.clear();  // q | k | v stacked, k without a bias
+  for (int l = 0; l < c.enc_layers; ++l)
+    g->enc.push_back(pack_enc_layer(g, "model.encoder.layers." + std::to_string(l) + ".", WSP_LAYER, d, c.enc_ffn, false));
   g->enc_ln = pack_norm(g, "model.encoder.layer_norm");
   g->tok_emb = push(g->packed, g->w["model.decoder.embed_tokens.weight"].data);
   g->dec_pos = push(g->packed, g->w["model.decoder.embed_positions.weight"].data);
@@ -438,7 +347,7 @@ extern "C" int vx_wsp_finalize(vx_wsp* g) {
   for (int l = 0; l < c.dec_layers; ++l) {
     const std::string pre = "model.decoder.layers." + std::to_string(l) + ".";
     WspDecLayer& ly = g->dec[l];
-    ly.qkv = pack_qkv(pre + "self_attn");
+    ly.qkv = pack_qkv(g, pre + "self_attn", d, false);
     ly.out = pack_linear(g, pre + "self_attn.out_proj", d, d);
     ly.ln1 = pack_norm(g, pre + "self_attn_layer_norm");
     ly.cq = pack_linear(g, pre + "encoder_attn.q_proj", d, d);
@@ -462,8 +371,7 @@ extern "C" int vx_wsp_finalize(vx_wsp* g) {
   g->head = SpkLin();
   g->head.w = c.tie_proj ? g->tok_emb : push(g->packed, g->w["proj_out.weight"].data);
   g->head.has_bias = false; g->head.C = d; g->head.N = c.vocab;
-  for (auto& kv : g->w) std::vector<float>().swap(kv.second.data);  // the packed copy is the one that is kept
-  g->finalized = true;
+  finalize_end(g);
   return VX_OK;
 }
 
@@ -511,14 +419,7 @@ extern "C" int vx_wsp_recognize(vx_wsp* g, int32_t n, const float* const* wav, c
     steps = std::max(steps, n_prompt[i] - 1 + std::min(max_new_tokens[i], room));
   }
   const auto t_begin = std::chrono::steady_clock::now();
-  if (g->device < 0) {
-    const int rc = wsp_init_device(g);
-    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
-      g->dev.reset();
-      g->device = -1;
-      return rc;
-    }
-  }
+  VXC(ensure_device(g, wsp_init_device));
   DevGuard guard(g->device);
   HIPC(guard.err);
   WspDev& dv = *g->dev;
@@ -555,8 +456,8 @@ extern "C" int vx_wsp_recognize(vx_wsp* g, int32_t n, const float* const* wav, c
     for (int k = 0; k < out_stride; ++k) hforced[(size_t)i * out_stride + k] = (forced && k < max_new_tokens[i]) ? forced[(size_t)i * out_stride + k] : 0;
     g->last_prompt[i] = n_prompt[i];
   }
-  g->last_n = n;
-  g->last_stream = s;
+  g->call.last_n = n;
+  g->call.last_stream = s;
   VXC(dv.stage.upload(dv.stage.bytes, s));
   CallCtx x{};
   x.g = g; x.eps = 1e-5f; x.W = dv.w.get(); x.ws = dv.ws.get(); x.MB = (int)MB; x.n = n; x.s = s;
@@ -589,24 +490,21 @@ extern "C" int vx_wsp_recognize(vx_wsp* g, int32_t n, const float* const* wav, c
   HIPC(hipEventRecord(dv.ev[3], s));
   const int rc = dv.stage.finish(s);
   g->last_steps = done_steps;
-  g->last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  g->call.last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   return rc;
 }
 
 extern "C" int vx_wsp_read(vx_wsp* g, const char* name, int32_t utt, float* dst, int64_t n_floats) {
-  if (!g || !name || !dst) return fail(VX_ERR_ARG, "vx_wsp_read: null argument");
-  if (g->device < 0 || g->last_n == 0) return fail(VX_ERR_STATE, "vx_wsp_read before any vx_wsp_recognize");
-  const int n = g->last_n;
-  if (utt < 0 || utt >= n) return fail(VX_ERR_ARG, "vx_wsp_read: utterance %d of %d", utt, n);
+  VXC(read_check(g, "vx_wsp", "recognize", name, utt, dst));
   const vx_wsp_config& c = g->cfg;
   const WspPlan& p = g->plan;
   const std::string nm = name;
   const bool keep = (c.flags & VX_WSP_KEEP_TAPS) != 0;
-  DevGuard guard(g->device);
-  HIPC(guard.err);
-  HIPC(hipStreamSynchronize(g->last_stream));
   if (nm == "logits") {  // the raw rows of the generated steps, one copy a step
     if (!keep) return fail(VX_ERR_STATE, "vx_wsp_read: logits needs VX_WSP_KEEP_TAPS at create");
+    DevGuard guard(g->device);
+    HIPC(guard.err);
+    HIPC(hipStreamSynchronize(g->call.last_stream));
     int count = 0;
     HIPC(hipMemcpy(&count, g->dev->state.get() + 2 * (size_t)c.max_batch + utt, sizeof(int), hipMemcpyDeviceToHost));
     if (n_floats != (int64_t)count * c.vocab)
@@ -620,7 +518,7 @@ extern "C" int vx_wsp_read(vx_wsp* g, const char* name, int32_t utt, float* dst,
   }
   size_t base = 0;
   long rows = g->P;
-  int width = c.d_model;
+  int width = c.d_model, l = 0;
   if (nm == "logmel") {
     base = p.mel; rows = g->F; width = c.n_mels;
   } else if (nm == "conv1") {
@@ -629,25 +527,19 @@ extern "C" int vx_wsp_read(vx_wsp* g, const char* name, int32_t utt, float* dst,
     base = p.feat;
   } else if (nm == "encoder") {
     base = p.enc;
-  } else if (nm.compare(0, 3, "enc") == 0 && nm.size() > 3) {
-    char* end = nullptr;
-    const long l = strtol(nm.c_str() + 3, &end, 10);
-    if (*end != 0 || l < 0 || l > c.enc_layers) return fail(VX_ERR_ARG, "vx_wsp_read: unknown tap %s", name);
+  } else if (tap_index(nm, "enc", c.enc_layers, l)) {
     if (!keep) return fail(VX_ERR_STATE, "vx_wsp_read: %s needs VX_WSP_KEEP_TAPS at create", name);
     base = p.hid + p.hid_stride * (size_t)l;
   } else {
     return fail(VX_ERR_ARG, "vx_wsp_read: unknown tap %s", name);
   }
-  if (n_floats != (int64_t)rows * width)
-    return fail(VX_ERR_ARG, "vx_wsp_read: %s of utterance %d is %ld x %d floats, not %lld", name, utt, rows, width, (long long)n_floats);
-  HIPC(hipMemcpy(dst, g->dev->ws.get() + base + (size_t)utt * rows * width, (size_t)rows * width * sizeof(float), hipMemcpyDeviceToHost));
-  return VX_OK;
+  return read_rows(g, "vx_wsp", name, utt, base, (long)utt * rows, rows, width, dst, n_floats);
 }
 
 extern "C" int vx_wsp_get_timings(vx_wsp* g, double* out, int32_t n) {
   if (!g || !out || n < 0 || n > 7) return fail(VX_ERR_ARG, "vx_wsp_get_timings: null argument or n outside [0, 7]");
-  double v[7] = {g->last_ms, (double)(g->plan.total * sizeof(float)), (double)(g->packed.size() * sizeof(float)), g->last_steps, 0.0, 0.0, 0.0};
-  if (n > 4 && g->device >= 0 && g->last_n > 0) {  // the device times of the last call: waits for it
+  double v[7] = {g->call.last_ms, (double)(g->plan.total * sizeof(float)), (double)(g->packed.size() * sizeof(float)), g->last_steps, 0.0, 0.0, 0.0};
+  if (n > 4 && g->device >= 0 && g->call.last_n > 0) {  // the device times of the last call: waits for it
     DevGuard guard(g->device);
     HIPC(guard.err);
     HIPC(hipEventSynchronize(g->dev->ev[3]));

@@ -15,7 +15,6 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import json
 import math
 import re
 from typing import Dict, Optional, Sequence, Union
@@ -23,9 +22,9 @@ from typing import Dict, Optional, Sequence, Union
 import torch
 
 from . import engine as _e
+from ._speech_handle import SAMPLE_RATE, W2vHandle, config_from_any, w2v_backbone_keys, w2v_synthetic_state_dict
 
 ATTENTION = {"wavlm": _e.VX_SPK_WAVLM, "plain": _e.VX_SPK_PLAIN}
-SAMPLE_RATE = 16000
 HEAD_DIMS = (16, 32, 64)
 
 
@@ -58,16 +57,9 @@ class SpeakerConfig:
 
     @classmethod
     def from_any(cls, cfg) -> "SpeakerConfig":
-        """A dict (a checkpoint's `config.json`), a path to one, or any object with the attributes."""
-        if isinstance(cfg, cls):
-            return cfg
-        if isinstance(cfg, str):
-            with open(cfg) as f:
-                cfg = json.load(f)
-        names = [f.name for f in dataclasses.fields(cls)]
-        if isinstance(cfg, dict):
-            return cls(**{k: cfg[k] for k in names if k in cfg})
-        return cls(**{k: getattr(cfg, k) for k in names if hasattr(cfg, k)})
+        """A dict (a checkpoint's `config.json`), a path to one, or any object with the attributes; a field that is absent or
+        None (a `null` in the json) takes the default."""
+        return config_from_any(cls, cfg)
 
 
 PRESETS: Dict[str, SpeakerConfig] = {
@@ -99,37 +91,16 @@ def fold_pos_conv_weight_norm(g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
 def expected_keys(c: SpeakerConfig, attention: str = "wavlm") -> Dict[str, tuple]:
     """canonical key -> shape, as vx_spk_create lays them out."""
     d, H, L = int(c.hidden_size), int(c.num_attention_heads), int(c.num_hidden_layers)
-    keys: Dict[str, tuple] = {}
+
+    def gate(keys, lin, pre):
+        lin(pre + "attention.gru_rel_pos_linear", 8, d // H)
+        keys[pre + "attention.gru_rel_pos_const"] = (1, H, 1, 1)
+
+    keys = w2v_backbone_keys(c, False, norm0_last=True, per_layer=gate if attention == "wavlm" else None)
 
     def lin(name, n, k):
         keys[name + ".weight"], keys[name + ".bias"] = (n, k), (n,)
 
-    def norm(name, n):
-        keys[name + ".weight"], keys[name + ".bias"] = (n,), (n,)
-
-    cin = 1
-    for i, (co, k) in enumerate(zip(c.conv_dim, c.conv_kernel)):
-        keys[f"feature_extractor.conv_layers.{i}.conv.weight"] = (int(co), cin, int(k))
-        if c.conv_bias:
-            keys[f"feature_extractor.conv_layers.{i}.conv.bias"] = (int(co),)
-        cin = int(co)
-    norm("feature_extractor.conv_layers.0.layer_norm", int(c.conv_dim[0]))
-    norm("feature_projection.layer_norm", cin)
-    lin("feature_projection.projection", d, cin)
-    keys["encoder.pos_conv_embed.conv.weight"] = (d, d // int(c.num_conv_pos_embedding_groups), int(c.num_conv_pos_embeddings))
-    keys["encoder.pos_conv_embed.conv.bias"] = (d,)
-    norm("encoder.layer_norm", d)
-    for l in range(L):
-        pre = f"encoder.layers.{l}."
-        for nm in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            lin(pre + "attention." + nm, d, d)
-        if attention == "wavlm":
-            lin(pre + "attention.gru_rel_pos_linear", 8, d // H)
-            keys[pre + "attention.gru_rel_pos_const"] = (1, H, 1, 1)
-        norm(pre + "layer_norm", d)
-        lin(pre + "feed_forward.intermediate_dense", int(c.intermediate_size), d)
-        lin(pre + "feed_forward.output_dense", d, int(c.intermediate_size))
-        norm(pre + "final_layer_norm", d)
     if attention == "wavlm":
         keys["encoder.layers.0.attention.rel_attn_embed.weight"] = (int(c.num_buckets), H)
     if c.use_weighted_layer_sum:
@@ -176,51 +147,24 @@ def synthetic_state_dict(config, seed: int = 0, attention: str = "wavlm") -> Dic
     one (so the bias, its gate and its direction move the output), a GroupNorm bias and convolution gains that put the GELUs in
     their curved range, unequal layer weights."""
     c = SpeakerConfig.from_any(config)
-    g = torch.Generator().manual_seed(int(seed))
-    prefix = "wavlm." if attention == "wavlm" else "wav2vec2."
-    sd: Dict[str, torch.Tensor] = {}
+    keys = expected_keys(c, attention)
 
-    def rnd(*shape, scale=1.0):
-        return torch.randn(*shape, generator=g) * scale
-
-    for k, shape in expected_keys(c, attention).items():
-        head = k.split(".")[0] in ("projector", "tdnn", "classifier", "layer_weights") or k.startswith("feature_extractor.weight") \
+    def is_head(k):
+        return k.split(".")[0] in ("projector", "tdnn", "classifier", "layer_weights") or k.startswith("feature_extractor.weight") \
             or k.startswith("feature_extractor.bias")
-        name = k if head else prefix + k
-        if k == "encoder.pos_conv_embed.conv.weight":
-            sd[prefix + "encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = 0.5 + torch.rand(1, 1, shape[2], generator=g)
-            sd[prefix + "encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = rnd(*shape)
-        elif k.endswith("rel_attn_embed.weight"):
-            sd[name] = rnd(*shape, scale=2.0)
-        elif k.endswith("gru_rel_pos_linear.weight"):
-            sd[name] = rnd(*shape, scale=0.5)
-        elif k.endswith("gru_rel_pos_const"):
-            sd[name] = 1.0 + rnd(*shape, scale=0.5)
-        elif k == "layer_weights":
-            sd[name] = rnd(*shape, scale=1.0)
-        elif k.endswith("layer_norm.weight"):
-            sd[name] = 1.0 + rnd(*shape, scale=0.2)
-        elif k.endswith("layer_norm.bias"):
-            sd[name] = rnd(*shape, scale=0.5)
-        elif k.endswith(".bias"):
-            sd[name] = rnd(*shape, scale=0.1)
-        elif k == "feature_extractor.conv_layers.0.conv.weight":
-            sd[name] = rnd(*shape, scale=1.0)
-        else:  # Linear and convolution weights: unit gain over the fan-in
-            fan_in = 1
-            for s in shape[1:]:
-                fan_in *= s
-            sd[name] = rnd(*shape, scale=1.5 / math.sqrt(fan_in))
-    sd[prefix + "masked_spec_embed"] = rnd(int(c.hidden_size))
-    return sd
+
+    own = {"rel_attn_embed.weight": (0.0, 2.0), "gru_rel_pos_linear.weight": (0.0, 0.5), "gru_rel_pos_const": (1.0, 0.5),
+           "layer_weights": (0.0, 1.0)}
+    return w2v_synthetic_state_dict(keys, seed, "wavlm." if attention == "wavlm" else "wav2vec2.", is_head, own, int(c.hidden_size))
 
 
-class SpeakerEncoder:
+class SpeakerEncoder(W2vHandle):
     """`SpeakerEncoder(config=None, attention="wavlm", max_batch=32, max_seconds=20.0)`: `config` is a preset name (`PRESETS`,
     default `wavlm_base_plus_sv`), a `SpeakerConfig`, a dict or path of the checkpoint's `config.json`, or any object with the
     `WavLMConfig` / `Wav2Vec2Config` attributes.  A call serves up to `max_batch` (<= 64) utterances of up to `max_seconds` at
     16 kHz each; the workspace is sized from the two.  Head dimensions 16, 32 and 64 are served; `feat_extract_norm="layer"`,
     `do_stable_layer_norm`, adapters and activations other than GELU raise NotImplementedError."""
+    _PREFIX, _NAME = "vx_spk", "SpeakerEncoder"
 
     def __init__(self, config=None, attention: str = "wavlm", max_batch: int = 32, max_seconds: float = 20.0,
                  state_dict: Optional[dict] = None, keep_taps: bool = False):
@@ -249,12 +193,7 @@ class SpeakerEncoder:
         self.config, self.attention = config, attention
         self.max_batch, self.max_samples = int(max_batch), int(round(float(max_seconds) * SAMPLE_RATE))
         self.keep_taps = bool(keep_taps)
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None
-        self._weights: Optional[Dict[str, torch.Tensor]] = None
-        self._resamplers: Dict[int, object] = {}
-        self._create()  # a geometry the kernels do not serve is refused here
+        self._init_handle()
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -263,118 +202,38 @@ class SpeakerEncoder:
         s, c = _e.VxSpkConfig(), self.config
         s.struct_size = C.sizeof(_e.VxSpkConfig)
         s.attention = ATTENTION[self.attention]
-        s.hidden, s.layers, s.heads, s.ffn = int(c.hidden_size), int(c.num_hidden_layers), int(c.num_attention_heads), int(c.intermediate_size)
-        s.n_conv = len(c.conv_dim)
-        for i, (dm, k, st) in enumerate(zip(c.conv_dim, c.conv_kernel, c.conv_stride)):
-            s.conv_dim[i], s.conv_kernel[i], s.conv_stride[i] = int(dm), int(k), int(st)
-        s.conv_bias = int(bool(c.conv_bias))
-        s.pos_kernel, s.pos_groups = int(c.num_conv_pos_embeddings), int(c.num_conv_pos_embedding_groups)
+        self._fill_backbone(s)
         s.num_buckets = int(c.num_buckets)
         s.n_tdnn = len(c.tdnn_dim)
         for i, (dm, k, dl) in enumerate(zip(c.tdnn_dim, c.tdnn_kernel, c.tdnn_dilation)):
             s.tdnn_dim[i], s.tdnn_kernel[i], s.tdnn_dilation[i] = int(dm), int(k), int(dl)
         s.xvector = int(c.xvector_output_dim)
         s.use_weighted_layer_sum = int(bool(c.use_weighted_layer_sum))
-        s.layer_norm_eps = float(c.layer_norm_eps)
-        s.max_batch, s.max_samples = self.max_batch, self.max_samples
         s.flags = _e.VX_SPK_KEEP_TAPS if self.keep_taps else 0
         return s
 
-    def _create(self):
-        lib = _e.load_library()
-        h = C.c_void_p()
-        _e._check(lib.vx_spk_create(C.byref(self._config_struct()), C.byref(h)))
-        self._h, self._bound = h, None
-        if self._weights is not None:
-            try:
-                self._upload()
-            except Exception:
-                self.close()
-                raise
-
-    def _upload(self):
-        lib = _e.load_library()
-        for k, t in self._weights.items():
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _e._check(lib.vx_spk_set_weight(self._h, k.encode(), t.data_ptr(), shape, t.dim()))
-        if self.attention == "wavlm":
+    def _configure(self, lib):
+        if self._weights is not None and self.attention == "wavlm":
             T = self.max_frames
             idx = relative_position_buckets(torch.arange(-(T - 1), T), int(self.config.num_buckets),
                                             int(self.config.max_bucket_distance)).to(torch.int32).contiguous()
             _e._check(lib.vx_spk_set_buckets(self._h, idx.data_ptr(), idx.numel()))
-        _e._check(lib.vx_spk_finalize(self._h))
-
-    def _handle(self):
-        if self._h is None:
-            self._create()
-        return self._h
-
-    def num_frames(self, n_samples: int) -> int:
-        """Frames the feature encoder leaves of `n_samples` samples at 16 kHz (host only)."""
-        return int(_e.load_library().vx_spk_frames(self._handle(), int(n_samples)))
-
-    @property
-    def max_frames(self) -> int:
-        return self.num_frames(self.max_samples)
 
     @property
     def min_samples(self) -> int:
         """The shortest utterance served (two pooled frames): 5200 samples at the default strides and TDNN kernels."""
-        return int(_e.load_library().vx_spk_min_samples(self._handle()))
+        return super().min_samples
 
     @property
     def embedding_dim(self) -> int:
         return int(self.config.xvector_output_dim)
 
-    def workspace_bytes(self) -> int:
-        out = (C.c_double * 4)()
-        _e._check(_e.load_library().vx_spk_get_timings(self._handle(), out, 4))
-        return int(out[1])
-
     def load_state_dict(self, sd: dict):
         """Takes the `transformers` key layout (see `canonical_state_dict`); missing and unexpected keys and wrong shapes raise by
         name.  Returns self."""
-        w = canonical_state_dict(sd)
-        want = expected_keys(self.config, self.attention)
-        missing = sorted(k for k in want if k not in w)
-        unexpected = sorted(k for k in w if k not in want)
-        if missing or unexpected:
-            raise KeyError(f"SpeakerEncoder.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        for k, shape in want.items():
-            if tuple(w[k].shape) != tuple(shape):
-                raise ValueError(f"SpeakerEncoder.load_state_dict: {k} is {tuple(w[k].shape)}, expected {tuple(shape)}")
-        self._weights = {k: w[k].to(torch.float32).contiguous() for k in want}
-        self.close()
-        self._create()
-        return self
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_spk_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._check_state_dict(expected_keys(self.config, self.attention), canonical_state_dict(sd))
 
     # ---- embedding ----------------------------------------------------------------------------------
-    def _resampler(self, sr: int):
-        from .codec import Resampler
-
-        if sr not in self._resamplers:
-            self._resamplers[sr] = Resampler(sr, SAMPLE_RATE, max_batch=self.max_batch)
-        return self._resamplers[sr].to(self.device)
-
     @torch.no_grad()
     def embed(self, wavs: Union[torch.Tensor, Sequence[torch.Tensor]], sr: int = 24000, normalize: bool = False,
               return_logits: bool = False):
@@ -383,24 +242,7 @@ class SpeakerEncoder:
         first.  `normalize=True` applies the Wav2Vec2 feature extractor's zero-mean unit-variance rule per utterance: the
         checkpoint's `preprocessor_config.json` (`do_normalize`) says which it wants.  More than `max_batch` utterances are served
         in several calls; every utterance is bitwise what it is alone."""
-        if isinstance(wavs, torch.Tensor):
-            wavs = [wavs]
-        ws = []
-        for w in wavs:
-            assert isinstance(w, torch.Tensor) and w.dtype == torch.float32, "waveforms are float32 tensors"
-            assert w.numel() == w.shape[-1], "one mono utterance per entry: (L,), (1, L) or (1, 1, L)"
-            ws.append(w.detach().reshape(-1))
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.SpeakerEncoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
-        if self._weights is None:
-            raise RuntimeError("SpeakerEncoder has no weights: call load_state_dict first")
-        ws = [w.to(self.device).contiguous() for w in ws]
-        if int(sr) != SAMPLE_RATE:
-            rs = self._resampler(int(sr))
-            out = []
-            for i in range(0, len(ws), self.max_batch):
-                out += [o.reshape(-1) for o in rs.resample_batch(ws[i:i + self.max_batch])]
-            ws = out
+        ws = self._prepare(wavs, sr)
         n = len(ws)
         emb = torch.empty((n, self.embedding_dim), dtype=torch.float32, device=self.device)
         logits = torch.empty_like(emb) if return_logits else None
@@ -413,14 +255,7 @@ class SpeakerEncoder:
 
     def _embed_raw(self, wav_ptrs, lengths, normalize, emb_ptr, logits_ptr):
         """vx_spk_embed on raw pointers (the argument checks run before any device work)."""
-        n = len(wav_ptrs)
-        wp = (C.c_void_p * n)(*wav_ptrs)
-        L = (C.c_int32 * n)(*lengths)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_spk_embed(h, n, wp, L, _e.VX_SPK_NORMALIZE if normalize else 0, emb_ptr, logits_ptr, stream))
+        self._call("embed", wav_ptrs, lengths, _e.VX_SPK_NORMALIZE if normalize else 0, emb_ptr, logits_ptr)
 
     @torch.no_grad()
     def cosine(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -445,12 +280,6 @@ class SpeakerEncoder:
         assert len(la) == len(lb), "one waveform of b per waveform of a"
         emb = self.embed(la + lb, sr=sr, normalize=normalize)
         return self.cosine(emb[:len(la)], emb[len(la):])
-
-    def read_tap(self, name: str, utt: int, rows: int, width: int) -> torch.Tensor:
-        """(rows, width) float32 on the host: a tap of the last `embed` call (`vx_spk_read`; the parity tests)."""
-        out = torch.empty((rows, width), dtype=torch.float32)
-        _e._check(_e.load_library().vx_spk_read(self._handle(), name.encode(), int(utt), out.data_ptr(), out.numel()))
-        return out
 
 
 def speaker_similarity(prompt_wav: torch.Tensor, synth_wav: torch.Tensor, encoder: SpeakerEncoder, sr: int = 24000,

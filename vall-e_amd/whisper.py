@@ -18,15 +18,14 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import json
 import math
 from typing import Dict, List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
 from . import engine as _e
+from ._speech_handle import SAMPLE_RATE, SpeechHandle, config_from_any
 
-SAMPLE_RATE = 16000
 N_FFT, HOP, BINS = 400, 160, 201
 STOP_REASONS = {0: "none", 1: "eos", 2: "max_new_tokens", 3: "max_target_positions"}
 
@@ -53,15 +52,7 @@ class WhisperConfig:
     @classmethod
     def from_any(cls, cfg) -> "WhisperConfig":
         """A dict (a checkpoint's `config.json`), a path to one, or any object with the attributes."""
-        if isinstance(cfg, cls):
-            return cfg
-        if isinstance(cfg, str):
-            with open(cfg) as f:
-                cfg = json.load(f)
-        names = [f.name for f in dataclasses.fields(cls)]
-        if isinstance(cfg, dict):
-            return cls(**{k: cfg[k] for k in names if k in cfg and cfg[k] is not None})
-        return cls(**{k: getattr(cfg, k) for k in names if getattr(cfg, k, None) is not None})
+        return config_from_any(cls, cfg)
 
     @property
     def chunk_samples(self) -> int:
@@ -86,14 +77,7 @@ class WhisperGeneration:
             return cls()
         if isinstance(cfg, cls):
             return cfg
-        if isinstance(cfg, str):
-            with open(cfg) as f:
-                cfg = json.load(f)
-        names = [f.name for f in dataclasses.fields(cls)]
-        if isinstance(cfg, dict):
-            out = cls(**{k: cfg[k] for k in names if k in cfg and cfg[k] is not None})
-        else:
-            out = cls(**{k: getattr(cfg, k) for k in names if getattr(cfg, k, None) is not None})
+        out = config_from_any(cls, cfg)
         if isinstance(out.eos_token_id, (list, tuple)):
             out.eos_token_id = int(out.eos_token_id[0])
         return out
@@ -231,12 +215,13 @@ class TokenScores(NamedTuple):
     token_logprobs: List[List[float]]
 
 
-class WhisperRecognizer:
+class WhisperRecognizer(SpeechHandle):
     """`WhisperRecognizer(config, vocab=None, generation_config=None, max_batch=8, state_dict=None, keep_taps=False)`: `config` and
     `generation_config` are dicts, paths of the checkpoint's `config.json` / `generation_config.json`, or objects with those
     attributes; `vocab` is the checkpoint's `vocab.json` mapping token -> id (without it `.text` is "").  A call serves up to
     `max_batch` (<= 64) utterances of up to one chunk (320 x max_source_positions samples at 16 kHz) each.  A head dimension other
     than 64 and an activation other than GELU raise NotImplementedError naming the field."""
+    _PREFIX, _NAME = "vx_wsp", "WhisperRecognizer"
 
     def __init__(self, config, vocab: Optional[Dict[str, int]] = None, generation_config=None, max_batch: int = 8,
                  state_dict: Optional[dict] = None, keep_taps: bool = False, mel_basis: Optional[torch.Tensor] = None):
@@ -258,12 +243,7 @@ class WhisperRecognizer:
         if tuple(mel.shape) != (int(c.num_mel_bins), BINS):
             raise ValueError(f"mel_basis is {tuple(mel.shape)}, expected ({c.num_mel_bins}, {BINS})")
         self.mel_basis = mel.to(torch.float32).contiguous()
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None
-        self._weights: Optional[Dict[str, torch.Tensor]] = None
-        self._resamplers: Dict[int, object] = {}
-        self._create()  # a geometry the kernels do not serve is refused here
+        self._init_handle()
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -283,40 +263,19 @@ class WhisperRecognizer:
         s.flags = _e.VX_WSP_KEEP_TAPS if self.keep_taps else 0
         return s
 
-    def _create(self):
-        lib = _e.load_library()
-        h = C.c_void_p()
-        _e._check(lib.vx_wsp_create(C.byref(self._config_struct()), C.byref(h)))
-        self._h, self._bound = h, None
-        try:
-            sup = [int(t) for t in (self.generation.suppress_tokens or ())]
-            beg = [int(t) for t in (self.generation.begin_suppress_tokens or ())]
-            _e._check(lib.vx_wsp_set_suppress(self._h, (C.c_int32 * max(len(sup), 1))(*sup), len(sup), (C.c_int32 * max(len(beg), 1))(*beg),
-                                              len(beg)))
-            if self._weights is not None:
-                for k, t in list(self._weights.items()) + [("mel_filters", self.mel_basis)]:
-                    shape = (C.c_int64 * t.dim())(*t.shape)
-                    _e._check(lib.vx_wsp_set_weight(self._h, k.encode(), t.data_ptr(), shape, t.dim()))
-                _e._check(lib.vx_wsp_finalize(self._h))
-        except Exception:
-            self.close()
-            raise
+    def _configure(self, lib):
+        sup = [int(t) for t in (self.generation.suppress_tokens or ())]
+        beg = [int(t) for t in (self.generation.begin_suppress_tokens or ())]
+        _e._check(lib.vx_wsp_set_suppress(self._h, (C.c_int32 * max(len(sup), 1))(*sup), len(sup), (C.c_int32 * max(len(beg), 1))(*beg), len(beg)))
 
-    def _handle(self):
-        if self._h is None:
-            self._create()
-        return self._h
+    def _tensors(self):
+        return list(self._weights.items()) + [("mel_filters", self.mel_basis)]
 
     def timings(self) -> Dict[str, float]:
         """Of the last call: host ms, workspace and weight bytes, decode steps enqueued, device ms of log-mel / encoder / token loop."""
         out = (C.c_double * 7)()
         _e._check(_e.load_library().vx_wsp_get_timings(self._handle(), out, 7))
         return dict(zip(("host_ms", "workspace_bytes", "weight_bytes", "steps", "logmel_ms", "encoder_ms", "loop_ms"), out))
-
-    def workspace_bytes(self) -> int:
-        out = (C.c_double * 4)()
-        _e._check(_e.load_library().vx_wsp_get_timings(self._handle(), out, 4))
-        return int(out[1])
 
     def load_state_dict(self, sd: dict):
         """Takes the `transformers` key layout (`model.encoder...`, `model.decoder...`, `proj_out.weight`; a tied checkpoint may
@@ -325,36 +284,7 @@ class WhisperRecognizer:
         w = dict(sd)
         if self.config.tie_word_embeddings:
             w.pop("proj_out.weight", None)
-        missing = sorted(k for k in want if k not in w)
-        unexpected = sorted(k for k in w if k not in want)
-        if missing or unexpected:
-            raise KeyError(f"WhisperRecognizer.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        for k, shape in want.items():
-            if tuple(w[k].shape) != tuple(shape):
-                raise ValueError(f"WhisperRecognizer.load_state_dict: {k} is {tuple(w[k].shape)}, expected {tuple(shape)}")
-        self._weights = {k: w[k].detach().to("cpu", torch.float32).contiguous() for k in want}
-        self.close()
-        self._create()
-        return self
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_wsp_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._check_state_dict(want, w)
 
     # ---- recognition --------------------------------------------------------------------------------
     def prompt_prefix(self, language: Optional[str] = "en", task: Optional[str] = "transcribe") -> List[int]:
@@ -373,37 +303,10 @@ class WhisperRecognizer:
             ids.append(int(g.no_timestamps_token_id))
         return ids
 
-    def _prepare(self, wavs, sr: int) -> List[torch.Tensor]:
-        if isinstance(wavs, torch.Tensor):
-            wavs = [wavs]
-        ws = []
-        for w in wavs:
-            assert isinstance(w, torch.Tensor) and w.dtype == torch.float32, "waveforms are float32 tensors"
-            assert w.numel() == w.shape[-1], "one mono utterance per entry: (L,), (1, L) or (1, 1, L)"
-            ws.append(w.detach().reshape(-1))
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.WhisperRecognizer runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
-        if self._weights is None:
-            raise RuntimeError("WhisperRecognizer has no weights: call load_state_dict first")
-        ws = [w.to(self.device).contiguous() for w in ws]
-        if int(sr) != SAMPLE_RATE:
-            from .codec import Resampler
-
-            if sr not in self._resamplers:
-                self._resamplers[sr] = Resampler(int(sr), SAMPLE_RATE, max_batch=self.max_batch)
-            rs = self._resamplers[sr].to(self.device)
-            out = []
-            for i in range(0, len(ws), self.max_batch):
-                out += [o.reshape(-1) for o in rs.resample_batch(ws[i:i + self.max_batch])]
-            ws = out
-        return ws
-
     def _recognize_raw(self, wav_ptrs, lengths, prompts: Sequence[Sequence[int]], max_new: Sequence[int], forced, out_stride: int, tokens_ptr,
                        logprobs_ptr, counts_ptr, stops_ptr):
         """vx_wsp_recognize on raw pointers (the argument checks run before any device work)."""
         n = len(wav_ptrs)
-        wp = (C.c_void_p * n)(*wav_ptrs)
-        L = (C.c_int32 * n)(*lengths)
         ps = max(max((len(p) for p in prompts), default=1), 1)
         flat = [0] * (n * ps)
         for i, p in enumerate(prompts):
@@ -414,13 +317,8 @@ class WhisperRecognizer:
             for i, y in enumerate(forced):
                 ff[i * out_stride:i * out_stride + len(y)] = [int(t) for t in y]
             fo = (C.c_int32 * len(ff))(*ff)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_wsp_recognize(h, n, wp, L, (C.c_int32 * len(flat))(*flat), (C.c_int32 * n)(*[len(p) for p in prompts]), ps,
-                                                     (C.c_int32 * n)(*[int(m) for m in max_new]), fo, int(out_stride), tokens_ptr, logprobs_ptr,
-                                                     counts_ptr, stops_ptr, stream))
+        self._call("recognize", wav_ptrs, lengths, (C.c_int32 * len(flat))(*flat), (C.c_int32 * n)(*[len(p) for p in prompts]), ps,
+                   (C.c_int32 * n)(*[int(m) for m in max_new]), fo, int(out_stride), tokens_ptr, logprobs_ptr, counts_ptr, stops_ptr)
 
     def _prompts(self, n, language, task, prompt_ids):
         if prompt_ids is None:
@@ -494,9 +392,3 @@ class WhisperRecognizer:
         res = self._run(ws, prompts, [len(y) for y in toks], toks)
         nll = [-r.logprob for r in res]
         return TokenScores(nll, sum(nll) / sum(len(y) for y in toks), [r.token_logprobs for r in res])
-
-    def read_tap(self, name: str, utt: int, rows: int, width: int) -> torch.Tensor:
-        """(rows, width) float32 on the host: a tap of the last call (`vx_wsp_read`; the parity tests)."""
-        out = torch.empty((rows, width), dtype=torch.float32)
-        _e._check(_e.load_library().vx_wsp_read(self._handle(), name.encode(), int(utt), out.data_ptr(), out.numel()))
-        return out
