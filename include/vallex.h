@@ -1410,6 +1410,35 @@ int vx_wsp_read(vx_wsp* h, const char* name, int32_t utt, float* dst, int64_t n_
  * it enqueued, out[4 .. 6] = device milliseconds of its log-mel, encoder (cross keys and values included) and token loop (asking
  * for them waits for the call); n = how many are wanted (<= 7). */
 int vx_wsp_get_timings(vx_wsp* h, double* out, int32_t n);
+/* Test-only, like the vx_op_* entries above: the token loop's kernels on caller data, through the launchers vx_wsp_recognize uses
+ * (they choose the columns per workgroup, the K chunk, the grid and the LDS size).  Every pointer is DEVICE; each call waits for
+ * its work.  The argument checks come before any launch.
+ * vx_op_wsp_gemm: out (M, N) = act(x (M, K) . W (N, K)^T + bias) + res; bias (N) or NULL, res (M, N) or NULL (it may be `out`),
+ * act 0 none / 1 exact GELU.  K no multiple of 4, M > 64, a size below 1 -> VX_ERR_ARG.
+ * vx_op_wsp_decode_attn: n utterances x H heads of 64, scale 1/8.  Utterance u's key (value) row j is kcache (vcache) + (u
+ * rows_per_utt + j) ld, head h at columns 64 h; q, knew, vnew rows have ldq floats, out (n, d), d = 64 H.  Self-attention: knew,
+ * vnew and pos (n) given; utterance u attends to keys 0 .. pos[u], the last of which is knew / vnew, which the kernel also stores
+ * to cache row pos[u].  Cross-attention: all three NULL, `keys` keys per utterance.  max_keys sizes the LDS (scores of at most
+ * that many keys): above 4096, or below a pos[u] + 1 or `keys`, or rows_per_utt below them -> VX_ERR_ARG.
+ * vx_op_wsp_head: one greedy (forced: teacher-forced) step on logits (n, V), as point 4 and 5 of the definition above.  suppress
+ * (V) bytes: bit 0 suppress_tokens, bit 1 begin_suppress_tokens.  prompt (n, prompt_stride), n_prompt, max_new (n), forced NULL
+ * or (n, out_stride); cur, pos, count, finished (n) are the utterances' state, read and advanced: pos[u] is the position the
+ * logits belong to; inside the prompt (pos[u] + 1 < n_prompt[u]) the next prompt token is fed and no output is written; a
+ * finished utterance changes nothing.  tokens_out / logprobs_out (n, out_stride) get step g = pos[u] + 1 - n_prompt[u];
+ * counts_out, stops_out (n).  A step outside out_stride, a forced id or eos outside [0, V) -> VX_ERR_ARG.
+ * vx_op_wsp_embed: x (n, d) = tok_emb[cur[u]] + pos_emb[pos[u]]; tok_emb (vocab, d), pos_emb (max_pos, d); an index outside its
+ * table -> VX_ERR_ARG. */
+int vx_op_wsp_gemm(const float* x, const float* W, const float* bias, const float* res, float* out, int32_t M, int32_t N, int32_t K,
+                   int32_t act, void* stream);
+int vx_op_wsp_decode_attn(const float* q, const float* knew, const float* vnew, float* kcache, float* vcache, float* out, int32_t ld,
+                          int32_t ldq, int32_t d, int32_t H, int32_t n, const int32_t* pos, int32_t keys, int64_t rows_per_utt,
+                          int32_t max_keys, void* stream);
+int vx_op_wsp_head(const float* logits, int32_t n, int32_t V, const uint8_t* suppress, const int32_t* prompt, int32_t prompt_stride,
+                   const int32_t* n_prompt, const int32_t* max_new, const int32_t* forced, int32_t* cur, int32_t* pos, int32_t* count,
+                   int32_t* finished, int32_t* tokens_out, float* logprobs_out, int32_t* counts_out, int32_t* stops_out,
+                   int32_t out_stride, int32_t eos, int32_t max_target, void* stream);
+int vx_op_wsp_embed(const float* tok_emb, const float* pos_emb, const int32_t* cur, const int32_t* pos, float* x, int32_t n, int32_t d,
+                    int32_t vocab, int32_t max_pos, void* stream);
 
 #ifdef __cplusplus
 }

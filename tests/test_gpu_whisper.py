@@ -9,10 +9,11 @@ to the first undecided step (test_whisper_cpu.py asserts that the cases have non
 restatement run on the engine's own logits within 2^-22 max(1, |v|).
 
 1. parity per tap on every case of whisper_cases.CASES: audio of 1, 199, 200, 201, 319, 320, 321, chunk - 1 and chunk samples, prompts
-   of 1, 2 and 4 tokens, a cache that passes 31 / 32 / 33 and 63 / 64 / 65 positions (geometry B), whisper-tiny's widths (C);
+   of 1, 2 and 4 tokens, a cache that passes 31 / 32 / 33 and 63 / 64 / 65 positions (geometry B), whisper-tiny's widths (C), two K
+   chunks in fc2, 300 logits and 260 cross keys (D); on D also 260 teacher-forced tokens, which take the self cache across 256 keys;
 2. greedy generation on the same cases;
-3. a ragged batch (1, 3 and max_batch utterances, shuffled lengths, different stop steps) is bitwise every utterance alone, a second
-   run is bitwise the first, nothing is written outside the outputs;
+3. a ragged batch (1, 3 and max_batch utterances, and 9 on a max_batch = 16 recogniser; shuffled lengths, different stop steps) is
+   bitwise every utterance alone, a second run is bitwise the first, nothing is written outside the outputs;
 4. 24 kHz input through the resampler, score_tokens, recognition_error end to end, the refusals."""
 import json
 import os
@@ -45,13 +46,13 @@ def _built():
             json.dump(_PARITY, f, indent=1, sort_keys=True)
 
 
-def _rec(name):
+def _rec(name, max_batch=MAX_BATCH):
     from valle_amd.whisper import WhisperRecognizer
 
-    if name not in _REC:
-        _REC[name] = WhisperRecognizer(WC.config(name), WC.vocab(name), WC.generation(name), max_batch=MAX_BATCH, state_dict=WC.state_dict(name),
-                                       keep_taps=True).to(DEV)
-    return _REC[name]
+    if (name, max_batch) not in _REC:
+        _REC[(name, max_batch)] = WhisperRecognizer(WC.config(name), WC.vocab(name), WC.generation(name), max_batch=max_batch,
+                                                    state_dict=WC.state_dict(name), keep_taps=True).to(DEV)
+    return _REC[(name, max_batch)]
 
 
 def _engine_taps(rec, name, utt, count):
@@ -93,6 +94,36 @@ def test_parity(cid):
         assert abs(a - b) <= 2.0 ** -22 * max(1.0, abs(b)), (a, b)
     assert abs(sc.nll[0] + sum(sc.token_logprobs[0])) <= 1e-9
     assert not bad, f"{cid}: engine error above {WC.TOL_FACTOR} x floor: {bad}"
+
+
+def test_teacher_forced_across_256_self_keys():
+    """Geometry D, 260 forced tokens after a 4-token prompt: the self-attention cache passes 255 / 256 / 257 keys (a thread's second
+    key, quarters of more than 64 keys), every step's cross-attention reads 260 keys, fc2 sums two K chunks, the head reads 300 logits."""
+    name = WC.TF_CASE[0]
+    rec = _rec(name)
+    tokens = WC.tf_tokens()
+    g = WC.generation(name)
+    assert len(WC.tf_prompt()) + len(tokens) == WC.GEOMETRIES[name]["max_target_positions"] and len(tokens) == 260
+    assert not set(tokens) & (set(g["suppress_tokens"]) | set(g["begin_suppress_tokens"]) | {WC.special(name)["eos"]})
+    sc = rec.score_tokens([WC.tf_wave().to(DEV)], [tokens], sr=16000, prompt_ids=WC.tf_prompt())
+    got = _engine_taps(rec, name, 0, len(tokens))
+    want, floors = WC.tf_taps(torch.float64), WC.tf_floors()
+    assert sorted(got) == sorted(want)
+    bad = []
+    for tap in sorted(want):
+        assert got[tap].shape == want[tap].shape, (tap, got[tap].shape, want[tap].shape)
+        assert bool(torch.isfinite(got[tap]).all()), tap
+        err, floor = float((got[tap].double() - want[tap]).abs().max()), floors[tap]
+        ratio = err / floor if floor else float("inf")
+        print(f"D_tf260 {tap:10s}: engine {err:.3e}, floor {floor:.3e}, ratio {ratio:.2f}")
+        _PARITY.setdefault("D_tf260", {})[tap] = {"engine": err, "floor": floor, "ratio": ratio}
+        if not err <= WC.TOL_FACTOR * floor:
+            bad.append((tap, err, floor))
+    own = R.forced_logprobs(got["logits"], tokens, g["suppress_tokens"], g["begin_suppress_tokens"])
+    assert len(sc.token_logprobs[0]) == len(own) == 260
+    for a, b in zip(sc.token_logprobs[0], own):
+        assert abs(a - b) <= 2.0 ** -22 * max(1.0, abs(b)), (a, b)
+    assert not bad, f"engine error above {WC.TOL_FACTOR} x floor: {bad}"
 
 
 # ---- 2. greedy ---------------------------------------------------------------------------------------------------------------------
@@ -137,9 +168,12 @@ def _raw_call(rec, wavs, prompts, max_new, stride):
     ("A", ("A_prompt1", "A_len1", "A_cap3")),
     ("A", ("A_len320", "A_prompt2", "A_len15999", "A_cap3", "A_len1", "A_prompt1", "A_len201", "A_len16000")),
     ("B", ("B_2", "B_0", "B_3", "B_1", "B_0", "B_1", "B_2", "B_3")),
+    # nine utterances on a max_batch = 16 recogniser: a second, ragged row tile of the token loop's GEMM
+    ("D", ("D_1", "D_0", "D_0", "D_1", "D_0", "D_1", "D_1", "D_0", "D_1")),
+    ("B", ("B_2", "B_0", "B_3", "B_1", "B_0", "B_1", "B_2", "B_3", "B_0")),
 ))
 def test_ragged_batch_is_bitwise_solo_and_repeatable(name, cids):
-    rec = _rec(name)
+    rec = _rec(name, MAX_BATCH if len(cids) <= MAX_BATCH else 16)
     Tt, V = WC.GEOMETRIES[name]["max_target_positions"], WC.GEOMETRIES[name]["vocab_size"]
     wavs = [WC.case_wave(c).to(DEV) for c in cids]
     prompts = [WC.case_prompt(c) for c in cids]

@@ -1,8 +1,8 @@
 """No GPU: what the Whisper recogniser's GPU tests stand on.
 
 1. the restatement (whisper_ref.py) in fp64 against `transformers`: the mel table, WhisperFeatureExtractor's features, the encoder's
-   last_hidden_state, teacher-forced logits and generate(do_sample=False) ids with both suppress lists set, on geometries A, B and
-   C, relative bound 1e-10, the measured figures printed.  Measured here: mel table 4.5e-16, encoder 1e-15 .. 1e-14, logits 1e-15 ..
+   last_hidden_state, teacher-forced logits and generate(do_sample=False) ids with both suppress lists set, on geometries A, B, C
+   and D, relative bound 1e-10, the measured figures printed.  Measured here: mel table 4.5e-16, encoder 1e-15 .. 1e-14, logits 1e-15 ..
    1e-14, ids equal.  The features equal the extractor's own lines (its spectrogram asked for fp64 output) to 3.6e-15 once the
    restatement takes the one step in which the extractor differs from the definition: transformers.audio_utils.spectrogram stores the
    STFT as complex64 between its fp64 FFT and its fp64 power (whisper_ref.logmel(stft_complex64=True)).  Without that step, which is
@@ -31,7 +31,7 @@ import whisper_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REL = 1e-10
-HF_CASES = ("A_len16000", "A_prompt1", "A_len201", "B_1", "B_3", "C_0", "C_1")
+HF_CASES = ("A_len16000", "A_prompt1", "A_len201", "B_1", "B_3", "C_0", "C_1", "D_0", "D_1")
 
 
 @pytest.fixture(scope="module")
@@ -236,6 +236,7 @@ def test_prefix_construction():
 
 NAMES = ["vx_wsp_create", "vx_wsp_destroy", "vx_wsp_finalize", "vx_wsp_get_timings", "vx_wsp_read", "vx_wsp_recognize", "vx_wsp_set_suppress",
          "vx_wsp_set_weight"]
+OP_NAMES = ["vx_op_wsp_decode_attn", "vx_op_wsp_embed", "vx_op_wsp_gemm", "vx_op_wsp_head"]
 
 
 def test_header_ctypes_exports(lib):
@@ -248,6 +249,10 @@ def test_header_ctypes_exports(lib):
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in vallex.h but not exported"
     assert C.sizeof(engine.VxWspConfig) == 68  # 17 four-byte fields, as the header lays them out
+    ops = sorted(set(re.findall(r"\b(vx_op_wsp_[a-z0-9_]+)\s*\(", hdr)))  # the token loop's kernels on caller data
+    assert ops == OP_NAMES == [s for s in engine.declared_symbols() if s.startswith("vx_op_wsp_")]
+    for name in ops:
+        assert hasattr(lib, name), f"{name} declared in vallex.h but not exported"
 
 
 def _struct(**over):

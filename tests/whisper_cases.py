@@ -23,6 +23,9 @@ GEOMETRIES = {
     # whisper-tiny's widths, one layer each
     "C": dict(_A, d_model=384, encoder_attention_heads=6, decoder_attention_heads=6, encoder_layers=1, decoder_layers=1, encoder_ffn_dim=1536,
               decoder_ffn_dim=1536, vocab_size=120),
+    # the token loop's launcher rules through the recogniser: an FFN of 2064 is two K chunks of the skinny GEMM (2048 + 16), 300 words are
+    # more than one logit a thread of the head and no multiple of 8, 260 cross keys and 264 targets take both attentions past 256 keys
+    "D": dict(_A, encoder_layers=1, decoder_layers=1, decoder_ffn_dim=2064, vocab_size=300, max_source_positions=260, max_target_positions=264),
 }
 
 
@@ -114,6 +117,8 @@ def _cases():
         c[f"B_{i}"] = ("B", (5000, 13000, 24000, 17001)[i], 30 + i, (4, 1, 2, 4)[i], None)
     c["C_0"] = ("C", 11000, 40, 4, None)
     c["C_1"] = ("C", 16000, 41, 4, 12)
+    c["D_0"] = ("D", 30000, 50, 4, None)
+    c["D_1"] = ("D", 83200, 51, 4, 24)
     return c
 
 
@@ -189,3 +194,43 @@ def decided(cid):
     """Per generated step of fp64's greedy run: the margin of the processed row exceeds 2 x TOL_FACTOR x the case's logits floor."""
     bound = 2 * TOL_FACTOR * floors(cid)["logits"]
     return [m > bound for m in generated(cid)["margins"]]
+
+
+# ---- a teacher-forced run that takes the self-attention cache across 256 keys --------------------------------------------------------
+# geometry, samples, wave seed, prompt length, forced tokens, token seed: 4 + 260 tokens fill D's 264 positions
+TF_CASE = ("D", 40000, 60, 4, 260, 7)
+_TF = {}
+
+
+def tf_wave():
+    return wave(TF_CASE[1], TF_CASE[2])
+
+
+def tf_prompt():
+    return prompt(TF_CASE[0], TF_CASE[3])
+
+
+def tf_tokens():
+    """Seeded tokens that are neither suppressed (either list) nor eos."""
+    name, count, seed = TF_CASE[0], TF_CASE[4], TF_CASE[5]
+    g = generation(name)
+    ok = [t for t in range(GEOMETRIES[name]["vocab_size"]) if t not in g["suppress_tokens"] and t not in g["begin_suppress_tokens"]
+          and t != special(name)["eos"]]
+    pick = torch.randint(0, len(ok), (count,), generator=torch.Generator().manual_seed(seed)).tolist()
+    return [ok[i] for i in pick]
+
+
+def tf_taps(dtype):
+    """The taps of the run at `dtype`, "logits" being the 260 raw rows teacher forcing reads."""
+    if dtype not in _TF:
+        name = TF_CASE[0]
+        e = R.encode(state_dict(name), config(name), tf_wave(), mel(name), dtype)
+        out = {k: e[k] for k in tap_names(name) if k != "logits"}
+        out["logits"] = R.forced_logits(state_dict(name), config(name), e, tf_prompt(), tf_tokens(), dtype)
+        _TF[dtype] = out
+    return _TF[dtype]
+
+
+def tf_floors():
+    r64, r32 = tf_taps(torch.float64), tf_taps(torch.float32)
+    return {k: float((r32[k].double() - r64[k]).abs().max()) for k in r64}

@@ -126,16 +126,30 @@ struct CallCtx : SpkCall {
   float* ws;
 };
 
+// The token loop's GEMM on a filled argument struct: the columns per workgroup (N / 512 rounded down to a multiple of 8, at least 8,
+// which holds up to N = 8191, and at most 64: the vocabulary head runs eight column passes over one staged chunk), the K chunk, the
+// grid and the LDS size are chosen here and nowhere else, for the recogniser and for vx_op_wsp_gemm alike.
+int launch_skinny(WspSkinnyArgs a, hipStream_t s) {
+  a.cpw = std::min(64, std::max(8, a.N / 512 / 8 * 8));
+  const int kc = std::min(a.K, WSP_SK_KC);
+  const dim3 grid((unsigned)((a.N + a.cpw - 1) / a.cpw), (unsigned)((a.M + WSP_SK_MT - 1) / WSP_SK_MT));
+  wsp_skinny_gemm<<<grid, 256, (size_t)WSP_SK_MT * kc * sizeof(float), s>>>(a);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// wsp_decode_attn over n utterances and H heads: the scores of up to max_keys keys and the 4 x 64 partial outputs sit in LDS.
+int launch_decode_attn(const WspAttnArgs& a, int H, int n, int max_keys, hipStream_t s) {
+  wsp_decode_attn<<<dim3((unsigned)H, (unsigned)n), 256, (size_t)(max_keys + 256) * sizeof(float), s>>>(a);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
 int run_skinny(const CallCtx& x, const SpkLin& l, const float* in, float* out, const float* res, int act) {
   WspSkinnyArgs a{};
   a.x = in; a.W = x.W + l.w; a.bias = l.has_bias ? x.W + l.b : nullptr; a.res = res; a.out = out;
   a.M = x.n; a.N = l.N; a.K = l.C; a.ldo = l.N; a.act = act;
-  a.cpw = std::min(64, std::max(8, l.N / 512 / 8 * 8));
-  const int kc = std::min(a.K, WSP_SK_KC);
-  const dim3 grid((unsigned)((a.N + a.cpw - 1) / a.cpw), (unsigned)((a.M + WSP_SK_MT - 1) / WSP_SK_MT));
-  wsp_skinny_gemm<<<grid, 256, (size_t)WSP_SK_MT * kc * sizeof(float), x.s>>>(a);
-  HIPC(hipGetLastError());
-  return VX_OK;
+  return launch_skinny(a, x.s);
 }
 
 int run_front_and_encoder(const CallCtx& x, const float* const* wav, const int* n_samples_dev, const int* hseg1, hipEvent_t after_mel) {
@@ -168,12 +182,6 @@ int run_front_and_encoder(const CallCtx& x, const float* const* wav, const int* 
   return VX_OK;
 }
 
-int run_attn_step(const CallCtx& x, const WspAttnArgs& a, int H, int max_keys) {
-  wsp_decode_attn<<<dim3((unsigned)H, (unsigned)x.n), 256, (size_t)(max_keys + 256) * sizeof(float), x.s>>>(a);
-  HIPC(hipGetLastError());
-  return VX_OK;
-}
-
 // One decode step of every utterance of the call: the same launches at every step, the state is on the device.
 int run_step(const CallCtx& x, const WspState& st, const WspHeadArgs& head) {
   const vx_wsp* g = x.g;
@@ -192,7 +200,7 @@ int run_step(const CallCtx& x, const WspState& st, const WspHeadArgs& head) {
     float* cache = ws + p.cache + p.cache_stride * (size_t)l;
     a.q = ws + p.dqkv; a.knew = ws + p.dqkv + d; a.vnew = ws + p.dqkv + 2 * d; a.kc = cache; a.vc = cache + d; a.out = ws + p.datt;
     a.pos = st.pos; a.ldq = 3 * d; a.ld = 2 * d; a.d = d; a.keys = 0; a.rows_per_utt = g->Tt; a.scale = scale;
-    VXC(run_attn_step(x, a, H, g->Tt));
+    VXC(launch_decode_attn(a, H, n, g->Tt, x.s));
     VXC(run_skinny(x, ly.out, ws + p.datt, ws + p.x, ws + p.x, SPK_ACT_NONE));
     VXC(run_ln(x, ly.ln2, ws + p.x, nullptr, ws + p.dn, n, d));
     VXC(run_skinny(x, ly.cq, ws + p.dn, ws + p.dq, nullptr, SPK_ACT_NONE));
@@ -200,7 +208,7 @@ int run_step(const CallCtx& x, const WspState& st, const WspHeadArgs& head) {
     float* ckv = ws + p.ckv + p.ckv_stride * (size_t)l;
     b.q = ws + p.dq; b.knew = nullptr; b.vnew = nullptr; b.kc = ckv; b.vc = ckv + d; b.out = ws + p.datt;
     b.pos = nullptr; b.ldq = d; b.ld = 2 * d; b.d = d; b.keys = g->P; b.rows_per_utt = g->P; b.scale = scale;
-    VXC(run_attn_step(x, b, H, g->P));
+    VXC(launch_decode_attn(b, H, n, g->P, x.s));
     VXC(run_skinny(x, ly.cout, ws + p.datt, ws + p.x, ws + p.x, SPK_ACT_NONE));
     VXC(run_ln(x, ly.ln3, ws + p.x, nullptr, ws + p.dn, n, d));
     VXC(run_skinny(x, ly.ff1, ws + p.dn, ws + p.dff, nullptr, SPK_ACT_GELU));
@@ -550,5 +558,112 @@ extern "C" int vx_wsp_get_timings(vx_wsp* g, double* out, int32_t n) {
     }
   }
   for (int i = 0; i < n; ++i) out[i] = v[i];
+  return VX_OK;
+}
+
+// ---- the token loop's kernels on caller data (tests): the launchers above, no handle -----------------------------------------------
+namespace {
+
+// n ints of a device array, after what `s` holds has run.
+int fetch_ints(const int* dev, size_t n, hipStream_t s, std::vector<int>& out) {
+  out.resize(n);
+  HIPC(hipMemcpyAsync(out.data(), dev, n * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+}  // namespace
+
+extern "C" int vx_op_wsp_gemm(const float* x, const float* W, const float* bias, const float* res, float* out, int32_t M, int32_t N, int32_t K,
+                              int32_t act, void* stream) {
+  if (!x || !W || !out) return fail(VX_ERR_ARG, "vx_op_wsp_gemm: null argument");
+  if (M < 1 || N < 1 || K < 1) return fail(VX_ERR_ARG, "vx_op_wsp_gemm: M %d, N %d, K %d", M, N, K);
+  if (K % 4 != 0) return fail(VX_ERR_ARG, "vx_op_wsp_gemm: K = %d is no multiple of 4", K);
+  if (M > SPK_MAX_SEG) return fail(VX_ERR_ARG, "vx_op_wsp_gemm: M = %d rows > %d", M, SPK_MAX_SEG);
+  if (act != SPK_ACT_NONE && act != SPK_ACT_GELU) return fail(VX_ERR_ARG, "vx_op_wsp_gemm: act = %d", act);
+  WspSkinnyArgs a{};
+  a.x = x; a.W = W; a.bias = bias; a.res = res; a.out = out;
+  a.M = M; a.N = N; a.K = K; a.ldo = N; a.act = act;
+  hipStream_t s = (hipStream_t)stream;
+  VXC(launch_skinny(a, s));
+  HIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+extern "C" int vx_op_wsp_decode_attn(const float* q, const float* knew, const float* vnew, float* kcache, float* vcache, float* out, int32_t ld,
+                                     int32_t ldq, int32_t d, int32_t H, int32_t n, const int32_t* pos, int32_t keys, int64_t rows_per_utt,
+                                     int32_t max_keys, void* stream) {
+  if (!q || !kcache || !vcache || !out) return fail(VX_ERR_ARG, "vx_op_wsp_decode_attn: null argument");
+  if ((knew == nullptr) != (vnew == nullptr) || (knew == nullptr) != (pos == nullptr))
+    return fail(VX_ERR_ARG, "vx_op_wsp_decode_attn: knew, vnew and pos come together (self-attention) or not at all (cross-attention)");
+  if (max_keys < 1 || max_keys > WSP_MAX_KEYS) return fail(VX_ERR_ARG, "vx_op_wsp_decode_attn: max_keys = %d outside [1, %d]", max_keys, WSP_MAX_KEYS);
+  if (n < 1 || n > SPK_MAX_SEG || H < 1 || d != 64 * H) return fail(VX_ERR_ARG, "vx_op_wsp_decode_attn: n %d, H %d, d %d (d = 64 H)", n, H, d);
+  if (ld < d || ldq < d || ld % 4 != 0 || ldq % 4 != 0) return fail(VX_ERR_ARG, "vx_op_wsp_decode_attn: ld %d, ldq %d (multiples of 4, >= d = %d)", ld, ldq, d);
+  if (rows_per_utt < 1 || rows_per_utt > WSP_MAX_KEYS) return fail(VX_ERR_ARG, "vx_op_wsp_decode_attn: rows_per_utt = %lld", (long long)rows_per_utt);
+  const int room = (int)std::min<int64_t>(max_keys, rows_per_utt);
+  if (!pos && (keys < 1 || keys > room)) return fail(VX_ERR_ARG, "vx_op_wsp_decode_attn: keys = %d outside [1, %d]", keys, room);
+  hipStream_t s = (hipStream_t)stream;
+  if (pos) {  // the kernel appends at row pos[u] and keeps pos[u] + 1 scores
+    std::vector<int> hp;
+    VXC(fetch_ints(pos, (size_t)n, s, hp));
+    for (int u = 0; u < n; ++u)
+      if (hp[u] < 0 || hp[u] >= room) return fail(VX_ERR_ARG, "vx_op_wsp_decode_attn: pos[%d] = %d outside [0, %d)", u, hp[u], room);
+  }
+  WspAttnArgs a{};
+  a.q = q; a.knew = knew; a.vnew = vnew; a.kc = kcache; a.vc = vcache; a.out = out; a.pos = pos;
+  a.ldq = ldq; a.ld = ld; a.d = d; a.keys = pos ? 0 : keys; a.rows_per_utt = rows_per_utt; a.scale = 0.125f;  // 64^-1/2
+  VXC(launch_decode_attn(a, H, n, max_keys, s));
+  HIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+extern "C" int vx_op_wsp_head(const float* logits, int32_t n, int32_t V, const uint8_t* suppress, const int32_t* prompt, int32_t prompt_stride,
+                              const int32_t* n_prompt, const int32_t* max_new, const int32_t* forced, int32_t* cur, int32_t* pos, int32_t* count,
+                              int32_t* finished, int32_t* tokens_out, float* logprobs_out, int32_t* counts_out, int32_t* stops_out,
+                              int32_t out_stride, int32_t eos, int32_t max_target, void* stream) {
+  if (!logits || !suppress || !prompt || !n_prompt || !max_new || !cur || !pos || !count || !finished || !tokens_out || !logprobs_out || !counts_out ||
+      !stops_out)
+    return fail(VX_ERR_ARG, "vx_op_wsp_head: null argument");
+  if (n < 1 || n > SPK_MAX_SEG || V < 1 || prompt_stride < 1 || out_stride < 1)
+    return fail(VX_ERR_ARG, "vx_op_wsp_head: n %d, V %d, prompt_stride %d, out_stride %d", n, V, prompt_stride, out_stride);
+  if (eos < 0 || eos >= V) return fail(VX_ERR_ARG, "vx_op_wsp_head: eos = %d outside [0, %d)", eos, V);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> hpos, hnp, hforced;  // what the kernel indexes with
+  VXC(fetch_ints(pos, (size_t)n, s, hpos));
+  VXC(fetch_ints(n_prompt, (size_t)n, s, hnp));
+  if (forced) VXC(fetch_ints(forced, (size_t)n * out_stride, s, hforced));
+  for (int u = 0; u < n; ++u) {
+    if (hnp[u] < 1 || hnp[u] > prompt_stride) return fail(VX_ERR_ARG, "vx_op_wsp_head: n_prompt[%d] = %d outside [1, %d]", u, hnp[u], prompt_stride);
+    const int g = hpos[u] + 1 - hnp[u];
+    if (hpos[u] < 0 || g >= out_stride) return fail(VX_ERR_ARG, "vx_op_wsp_head: pos[%d] = %d: step %d outside [.., %d)", u, hpos[u], g, out_stride);
+    if (forced && g >= 0 && (hforced[(size_t)u * out_stride + g] < 0 || hforced[(size_t)u * out_stride + g] >= V))
+      return fail(VX_ERR_ARG, "vx_op_wsp_head: forced[%d][%d] = %d outside [0, %d)", u, g, hforced[(size_t)u * out_stride + g], V);
+  }
+  WspHeadArgs a{};
+  a.logits = logits; a.suppress = suppress; a.prompt = prompt; a.n_prompt = n_prompt; a.max_new = max_new; a.forced = forced;
+  a.st = WspState{cur, pos, count, finished};
+  a.tokens_out = tokens_out; a.logprob_out = logprobs_out; a.count_out = counts_out; a.stop_out = stops_out; a.tap = nullptr;
+  a.V = V; a.prompt_stride = prompt_stride; a.out_stride = out_stride; a.eos = eos; a.max_target = max_target; a.MB = n;
+  wsp_head_reduce<<<n, 256, 0, s>>>(a);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+extern "C" int vx_op_wsp_embed(const float* tok_emb, const float* pos_emb, const int32_t* cur, const int32_t* pos, float* x, int32_t n, int32_t d,
+                               int32_t vocab, int32_t max_pos, void* stream) {
+  if (!tok_emb || !pos_emb || !cur || !pos || !x) return fail(VX_ERR_ARG, "vx_op_wsp_embed: null argument");
+  if (n < 1 || n > SPK_MAX_SEG || d < 1 || vocab < 1 || max_pos < 1)
+    return fail(VX_ERR_ARG, "vx_op_wsp_embed: n %d, d %d, vocab %d, max_pos %d", n, d, vocab, max_pos);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> hc, hp;
+  VXC(fetch_ints(cur, (size_t)n, s, hc));
+  VXC(fetch_ints(pos, (size_t)n, s, hp));
+  for (int u = 0; u < n; ++u)
+    if (hc[u] < 0 || hc[u] >= vocab || hp[u] < 0 || hp[u] >= max_pos)
+      return fail(VX_ERR_ARG, "vx_op_wsp_embed: utterance %d: token %d outside [0, %d) or position %d outside [0, %d)", u, hc[u], vocab, hp[u], max_pos);
+  wsp_embed<<<n, 256, 0, s>>>(tok_emb, pos_emb, cur, pos, x, d);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }

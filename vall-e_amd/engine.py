@@ -348,6 +348,12 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vx_wsp_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),
     "vx_wsp_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    # the token loop's kernels on caller data (whisper.op_wsp_*)
+    "vx_op_wsp_gemm": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]),
+    "vx_op_wsp_decode_attn": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "vx_op_wsp_head": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 11
+                       + [C.c_int32] * 3 + [C.c_void_p]),
+    "vx_op_wsp_embed": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so

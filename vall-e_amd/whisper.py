@@ -392,3 +392,65 @@ class WhisperRecognizer(SpeechHandle):
         res = self._run(ws, prompts, [len(y) for y in toks], toks)
         nll = [-r.logprob for r in res]
         return TokenScores(nll, sum(nll) / sum(len(y) for y in toks), [r.token_logprobs for r in res])
+
+
+# ---- the token loop's kernels on caller data (tests) -------------------------------------------------------------------------------
+def _f32(t, *shape):
+    assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and (not shape or tuple(t.shape) == shape), (t.dtype, tuple(t.shape), shape)
+    return t.data_ptr()
+
+
+def _i32(t, *shape):
+    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and (not shape or tuple(t.shape) == shape), (t.dtype, tuple(t.shape), shape)
+    return t.data_ptr()
+
+
+def op_wsp_gemm(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], res: Optional[torch.Tensor], out: torch.Tensor, act: int = 0):
+    """wsp_skinny_gemm through the recogniser's launcher (vx_op_wsp_gemm): out (M, N) = act(x (M, K) W (N, K)^T + bias) + res, fp32 on
+    the device; `res` may be `out`; act 1 is the exact GELU."""
+    (M, K), N = x.shape, W.shape[0]
+    _e._check(_e.load_library().vx_op_wsp_gemm(_f32(x), _f32(W, N, K), None if bias is None else _f32(bias, N),
+                                               None if res is None else _f32(res, M, N), _f32(out, M, N), M, N, K, int(act),
+                                               _e.current_stream_ptr(x.device)))
+    return out
+
+
+def op_wsp_decode_attn(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, out: torch.Tensor, ld: int, heads: int, rows_per_utt: int,
+                       max_keys: int, knew: Optional[torch.Tensor] = None, vnew: Optional[torch.Tensor] = None,
+                       pos: Optional[torch.Tensor] = None, keys: int = 0):
+    """wsp_decode_attn through the recogniser's launcher (vx_op_wsp_decode_attn): q (n, ldq) and out (n, 64 heads) fp32 on the device;
+    `kcache` and `vcache` are the tensors (views into one buffer are fine) whose data pointers are the key and value bases, row stride
+    `ld`.  With knew / vnew (n, ldq) and pos (n) int32 it is the self-attention step, which also appends; without, `keys` cross keys."""
+    n, ldq = q.shape
+    for t in (kcache, vcache):
+        assert t.dtype == torch.float32 and t.is_cuda
+    _e._check(_e.load_library().vx_op_wsp_decode_attn(_f32(q), None if knew is None else _f32(knew, n, ldq), None if vnew is None else _f32(vnew, n, ldq),
+                                                      kcache.data_ptr(), vcache.data_ptr(), _f32(out, n, 64 * heads), int(ld), ldq, 64 * heads,
+                                                      int(heads), n, None if pos is None else _i32(pos, n), int(keys), int(rows_per_utt),
+                                                      int(max_keys), _e.current_stream_ptr(q.device)))
+    return out
+
+
+def op_wsp_head(logits: torch.Tensor, suppress: torch.Tensor, prompt: torch.Tensor, n_prompt: torch.Tensor, max_new: torch.Tensor,
+                forced: Optional[torch.Tensor], state: Sequence[torch.Tensor], outputs: Sequence[torch.Tensor], eos: int, max_target: int):
+    """One wsp_head_reduce step (vx_op_wsp_head) on logits (n, V): `suppress` (V) uint8 (1 suppress_tokens, 2 begin_suppress_tokens),
+    `prompt` (n, stride), `state` = (cur, pos, count, finished) and `outputs` = (tokens (n, out_stride) int32, logprobs (n, out_stride)
+    float32, counts (n), stops (n)), all int32 on the device and changed in place."""
+    n, V = logits.shape
+    assert suppress.dtype == torch.uint8 and suppress.is_cuda and suppress.is_contiguous() and suppress.numel() == V
+    cur, pos, count, finished = state
+    tok, lp, cnt, stop = outputs
+    stride = tok.shape[1]
+    _e._check(_e.load_library().vx_op_wsp_head(_f32(logits), n, V, suppress.data_ptr(), _i32(prompt), prompt.shape[1], _i32(n_prompt, n),
+                                               _i32(max_new, n), None if forced is None else _i32(forced, n, stride), _i32(cur, n), _i32(pos, n),
+                                               _i32(count, n), _i32(finished, n), _i32(tok, n, stride), _f32(lp, n, stride), _i32(cnt, n),
+                                               _i32(stop, n), stride, int(eos), int(max_target), _e.current_stream_ptr(logits.device)))
+
+
+def op_wsp_embed(tok_emb: torch.Tensor, pos_emb: torch.Tensor, cur: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """wsp_embed (vx_op_wsp_embed): (n, d) = tok_emb[cur] + pos_emb[pos], fp32 tables and int32 indices on the device."""
+    n, d = cur.numel(), tok_emb.shape[1]
+    x = torch.empty((n, d), dtype=torch.float32, device=tok_emb.device)
+    _e._check(_e.load_library().vx_op_wsp_embed(_f32(tok_emb), _f32(pos_emb, pos_emb.shape[0], d), _i32(cur, n), _i32(pos, n), _f32(x), n, d,
+                                                tok_emb.shape[0], pos_emb.shape[0], _e.current_stream_ptr(tok_emb.device)))
+    return x
