@@ -934,6 +934,23 @@ int vx_mel_teacher_forced(vx_mel* m, const int64_t* text, int32_t S, const float
 /* out[0] ms of the last decode (device time of the replayed steps), out[1] its step launches, out[2] kernel launches per step (nodes
  * of the captured graph; 0 with VX_MEL_NO_GRAPH), out[3] ms of the last encode. */
 int vx_mel_get_timings(vx_mel* m, double* out, int32_t n);
+/* Parity tests: the decoder side's taps of vx_read_buffer on the handle's inner engine - "ar_kv" (the self-attention cache,
+ * [layer][K|V][head][max_text + max_frames + 2][head_dim]; frame row r is cache row r), "ar_mem" (every decoder layer's cross K / V
+ * of the last encode, [layer][K|V][head][max_text][head_dim]; rows at and past that text's length keep what a longer text left),
+ * "ar_x" (the step's input row, d fp32) - and "xh" (d fp32: the residual row the last decoder layer left for the head). */
+int vx_mel_read(vx_mel* m, const char* name, void* dst, int64_t offset_bytes, int64_t nbytes);
+/* Kernel-level: `launches` launches of the decode step's opening kernel (csrc/meltf.hip, through the launcher the step uses) on
+ * caller device buffers, back to back on one device-resident state, then a synchronisation.  xh / gamma / beta (d), Wh (101, d),
+ * bh (101), W0 (d, K0) / b0 (d) with K0 = 256 when W1 (256, 100) / b1 / W2 (256, 256) / b2 are given and 100 when they are all
+ * NULL, alpha (1), pe (pe_rows, d), forced (n_forced, 100) when n_forced > 0; outputs x (d), frames (frames_cap, 100), stops
+ * (stops_cap).  state: {row, pass, n_gen, S, done, stop_reason} on the host, read before and written after the launches; *arrive
+ * (nullable): the arrival counter after the last launch.  Checked before any HIP call: nulls, d % 8 or d > 1024 (as
+ * vx_mel_create), a prenet given in part, row < -1, and whether `launches` launches could leave pe, frames or stops. */
+int vx_op_mel_open(int32_t d, const float* xh, const float* gamma, const float* beta, const float* Wh, const float* bh,
+                   const float* W1, const float* b1, const float* W2, const float* b2, const float* W0, const float* b0,
+                   const float* alpha, const float* pe, int32_t pe_rows, float* x, float* frames, int32_t frames_cap, float* stops,
+                   int32_t stops_cap, int32_t* state, int32_t max_frames, int32_t n_forced, const float* forced, int32_t launches,
+                   uint32_t* arrive, void* stream);
 
 /* ---- Griffin-Lim vocoder: log-mel frames to a 24 kHz waveform ------------------------------------------------------------------
  * The inverse of the filterbank above, with its framing: 24 kHz, n_fft 1024, hop 256, the periodic Hann window w.  A handle of

@@ -62,6 +62,56 @@ def test_gemm_fp32(eng, M, N, K):
     assert (out - ref).abs().max() <= 1e-4
 
 
+def _gemm_simple_shapes():
+    import mel_step_cases as MC
+
+    return list(MC.GEMM_SHAPES) + [MC.GEMM_EXACT_SHAPE]
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape", _gemm_simple_shapes(), ids=lambda s: "x".join(map(str, s)))
+def test_gemm_simple_ragged(eng, shape, prec):
+    """gemm_simple_kernel (fp32, and bf16 without MFMA) where its `k < K` and `n < N` guards act: the mel Transformer's
+    teacher-forced head (N = 101) and decoder prenets (K = 100).  Reference: fp64 products of the stored values
+    (mel_step_ref.gemm); bound mel_step_cases.C_GEMM_SIMPLE units of 2^-24 sum |a| |w| (the reason for a constant of its own stands
+    next to it); the integer shape bitwise.  The output block ends in a NaN guard, and each wrong answer of
+    mel_step_ref.gemm_wrong lies at least SEP bounds from the kernel's output.  Measured on the MI355X: worst 3.90 units
+    ((60, 101, 192) fp32; bf16 2.97), nearest wrong answer 1.12e+04 bounds ((96, 101, 1024))."""
+    import mel_step_cases as MC
+    import mel_step_ref as R
+    from test_gpu_ar_step import SEP
+
+    C = MC.C_GEMM_SIMPLE
+    M, N, K = shape
+    bf16 = prec == "bf16"
+    A, W, b = MC.gemm_inputs(shape, bf16)
+    cast = (lambda t: t.to(torch.bfloat16).cuda()) if bf16 else (lambda t: t.cuda())
+    Ad, Wd, bd = cast(A), cast(W), b.cuda()
+    fails, worst, nearest = [], 0.0, float("inf")
+    for variant in MC.GEMM_VARIANTS:
+        bias, relu = (b if variant != "plain" else None), variant == "relu"
+        block = torch.full((M * N + 64,), float("nan"), device="cuda")
+        out = eng.op_gemm(Ad, Wd, bd if bias is not None else None, relu=relu, out=block[: M * N].view(M, N)).cpu().double()
+        assert bool(torch.isnan(block[M * N:]).all()), f"{variant}: the guard behind the output was written"
+        ref, scale = R.gemm(A, W, bias, relu)
+        if shape == MC.GEMM_EXACT_SHAPE:
+            assert torch.equal(out, ref), variant
+            continue
+        u = R.units((out - ref).abs(), R.U32 * scale)
+        worst = max(worst, u)
+        if not u <= C:
+            fails.append(f"{variant}: {u:.4g} units")
+        for name, w in R.gemm_wrong(A, W, bias, relu).items():
+            sep = R.units((w - out).abs(), C * R.U32 * scale)
+            nearest = min(nearest, sep)
+            if not sep >= SEP:
+                fails.append(f"{variant} wrong answer {name}: {sep:.3g} bounds")
+    print(f"\ngemm_simple {shape} {prec}: worst {worst:.3g} units (bound {C}), nearest wrong answer {nearest:.3g} bounds")
+    if shape != MC.GEMM_EXACT_SHAPE:
+        MC.parity_note(f"gemm_simple/{'x'.join(map(str, shape))}/{prec}", dict(units=worst, nearest_wrong=nearest))
+    assert not fails, "; ".join(fails)
+
+
 @pytest.mark.parametrize("M,N,K", [(272, 3072, 1024), (1025, 1024, 4096), (100, 384, 128), (753, 1024, 1024), (128, 128, 64),
                                    (1, 256, 256), (4133, 512, 256), (4096, 768, 1024), (4700, 256, 64)])
 @pytest.mark.parametrize("mfma", [False, True])

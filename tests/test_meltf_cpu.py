@@ -150,7 +150,8 @@ def test_abi_tables_are_consistent(lib):
     hdr = open(os.path.join(ROOT, "include", "vallex.h")).read()
     declared = sorted(n for n in set(re.findall(r"\b(vx_[a-z0-9_]+)\s*\(", hdr)) if n.startswith("vx_mel_"))
     assert declared == ["vx_mel_create", "vx_mel_decode", "vx_mel_decode_forced", "vx_mel_destroy", "vx_mel_encode", "vx_mel_finalize",
-                        "vx_mel_get_timings", "vx_mel_result", "vx_mel_set_sine_table", "vx_mel_set_weight", "vx_mel_teacher_forced"]
+                        "vx_mel_get_timings", "vx_mel_read", "vx_mel_result", "vx_mel_set_sine_table", "vx_mel_set_weight",
+                        "vx_mel_teacher_forced"]
     for n in declared:
         assert hasattr(lib, n) and n in engine.declared_symbols()
     assert C.sizeof(engine.VxMelConfig) == 12 * 4

@@ -3069,6 +3069,7 @@ extern "C" int vx_op_gemv(int32_t prec, const void* Wp, const float* bias, const
 
 extern "C" int vx_op_gemm(int32_t prec, int32_t mfma, const void* A, const void* Wp, const float* bias, float* C, int32_t M,
                           int32_t N, int32_t K, int32_t relu, void* stream) {
+  if (relu && !bias) return fail(VX_ERR_ARG, "gemm: the ReLU epilogue adds a bias");
   const int epi = relu ? GE_RELU : (bias ? GE_BIAS : GE_PLAIN);
   hipStream_t s = (hipStream_t)stream;
   if (prec == VX_PREC_BF16) VXC(gemm_rows_t<bf16>(mfma != 0, (const bf16*)A, (const bf16*)Wp, bias, C, M, N, K, epi, true, s));
@@ -4037,6 +4038,66 @@ extern "C" int vx_mel_get_timings(vx_mel* m, double* out, int32_t n) {
   if (!m || !out) return fail(VX_ERR_ARG, "null argument");
   const double v[4] = {m->t_decode, m->n_launch, (double)m->e->gexec_nodes, m->t_encode};
   for (int i = 0; i < n && i < 4; ++i) out[i] = v[i];
+  return VX_OK;
+}
+
+extern "C" int vx_mel_read(vx_mel* m, const char* name, void* dst, int64_t off, int64_t nbytes) {
+  if (!m || !name || !dst) return fail(VX_ERR_ARG, "null argument");
+  const std::string n = name;
+  if (n == "ar_kv" || n == "ar_mem" || n == "ar_x") return vx_read_buffer(m->e, name, dst, off, nbytes);
+  if (n != "xh") return fail(VX_ERR_ARG, "unknown buffer '%s'", name);
+  vx_engine* e = m->e;
+  ON_DEVICE(e->cfg.device);
+  const int64_t size = (int64_t)e->cfg.d_model * 4;
+  if (off < 0 || nbytes < 0 || off + nbytes > size) return fail(VX_ERR_ARG, "read of '%s' out of range (%lld+%lld > %lld)", name, (long long)off, (long long)nbytes, (long long)size);
+  HIPC(hipStreamSynchronize(e->es));
+  HIPC(hipMemcpy(dst, (const char*)m->xh + off, (size_t)nbytes, hipMemcpyDeviceToHost));
+  return VX_OK;
+}
+
+// The step's opening kernel on caller buffers.  The state and the control words live in one device block of this call; the
+// launches are ordered by the stream, nothing waits inside a kernel.
+extern "C" int vx_op_mel_open(int32_t d, const float* xh, const float* gamma, const float* beta, const float* Wh, const float* bh,
+                              const float* W1, const float* b1, const float* W2, const float* b2, const float* W0, const float* b0,
+                              const float* alpha, const float* pe, int32_t pe_rows, float* x, float* frames, int32_t frames_cap,
+                              float* stops, int32_t stops_cap, int32_t* state, int32_t max_frames, int32_t n_forced,
+                              const float* forced, int32_t launches, uint32_t* arrive, void* stream) {
+  if (!xh || !gamma || !beta || !Wh || !bh || !W0 || !b0 || !alpha || !pe || !x || !frames || !stops || !state)
+    return fail(VX_ERR_ARG, "null argument");
+  if (d <= 0 || d % 8 || d > 1024) return fail(VX_ERR_UNSUPPORTED, "d_model must be a multiple of 8 and <= 1024");
+  const int given = (W1 != nullptr) + (b1 != nullptr) + (W2 != nullptr) + (b2 != nullptr);
+  if (given != 0 && given != 4) return fail(VX_ERR_ARG, "mel_open: the MLP prenet needs W1, b1, W2 and b2, the linear one none of them");
+  if (n_forced < 0 || (n_forced > 0 && !forced)) return fail(VX_ERR_ARG, "mel_open: n_forced=%d needs the forced frames", n_forced);
+  const int row = state[0], pass = state[1], n_gen = state[2];
+  if (launches < 1 || row < -1 || pass < 0 || n_gen < 0) return fail(VX_ERR_ARG, "mel_open: launches=%d row=%d pass=%d n_gen=%d", launches, row, pass, n_gen);
+  // every launch may advance each of them by one: position row read row + 1, frame slot n_gen, stop slot pass
+  if ((long long)row + launches >= pe_rows || (long long)n_gen + launches > frames_cap || (long long)pass + launches > stops_cap ||
+      (n_forced > 0 && (long long)n_gen + launches > n_forced))
+    return fail(VX_ERR_CAPACITY, "mel_open: %d launches from row=%d pass=%d n_gen=%d leave pe (%d rows), frames (%d), stops (%d) or forced (%d)",
+                launches, row, pass, n_gen, pe_rows, frames_cap, stops_cap, n_forced);
+  hipStream_t s = (hipStream_t)stream;
+  struct Block { ArState st; MelCtl ctl; } h{};
+  h.st.row = row; h.st.pass = pass; h.st.n_gen = n_gen; h.st.S = state[3]; h.st.done = state[4]; h.st.stop_reason = state[5];
+  h.st.temperature = 1.0f; h.st.max_new = -1;
+  h.ctl.max_frames = max_frames; h.ctl.n_forced = n_forced; h.ctl.forced = n_forced > 0 ? forced : nullptr;
+  Block* dv = nullptr;
+  HIPC(hipMalloc((void**)&dv, sizeof(Block)));
+  auto body = [&]() -> int {
+    HIPC(hipMemcpyAsync(dv, &h, sizeof h, hipMemcpyHostToDevice, s));
+    MelStepArgs a{};
+    a.xh = xh; a.gamma = gamma; a.beta = beta; a.Wh = Wh; a.bh = bh; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.W0 = W0; a.b0 = b0;
+    a.alpha = alpha; a.pe = pe; a.x = x; a.st = &dv->st; a.ctl = &dv->ctl; a.frames = frames; a.stops = stops; a.d = d;
+    for (int i = 0; i < launches; ++i) launch_mel_open(a, s);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(&h, dv, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    return VX_OK;
+  };
+  const int rc = body();
+  (void)hipFree(dv);
+  if (rc != VX_OK) return rc;
+  state[0] = h.st.row; state[1] = h.st.pass; state[2] = h.st.n_gen; state[3] = h.st.S; state[4] = h.st.done; state[5] = h.st.stop_reason;
+  if (arrive) *arrive = h.ctl.arrive;
   return VX_OK;
 }
 

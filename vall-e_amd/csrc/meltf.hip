@@ -28,6 +28,14 @@ constexpr int MEL_HB = 7;      // head rows per batch and wave
 constexpr int MEL_HROWS = 26;  // head rows per wave: 4 x 26 >= 101
 constexpr int MEL_PR = 16;     // prenet rows per wave: 4 x 16 x MEL_GRID >= 1024
 
+// y + alpha p with the product rounded on its own, as torch's two operations.  __fadd_rn(y, __fmul_rn(alpha, p)) does not say
+// that: the two intrinsics are a plain `*` and `+`, which the compiler contracts into one fused multiply-add (one rounding).
+__device__ __forceinline__ float add_scaled_2r(float y, float alpha, float p) {
+#pragma clang fp contract(off)
+  const float m = alpha * p;
+  return y + m;
+}
+
 __global__ __launch_bounds__(256) void mel_open_kernel(const MelStepArgs a) {
   __shared__ __attribute__((aligned(16))) float sx[1024];            // the normalised row
   __shared__ __attribute__((aligned(16))) float sf[128];             // predict [0, 100), stop logit [100]
@@ -186,7 +194,7 @@ __global__ __launch_bounds__(256) void mel_open_kernel(const MelStepArgs a) {
       if (lk) { s = fmaf(w0[j].x, iv.x, s); s = fmaf(w0[j].y, iv.y, s); s = fmaf(w0[j].z, iv.z, s); s = fmaf(w0[j].w, iv.w, s); }
       s = wave_sum_dpp(s);
       const int r = lo + wave * MEL_PR + j;
-      if (lane == 0 && r < hi) a.x[r] = __fadd_rn(s + sb0[wave * MEL_PR + j], __fmul_rn(al, spe[wave * MEL_PR + j]));
+      if (lane == 0 && r < hi) a.x[r] = add_scaled_2r(s + sb0[wave * MEL_PR + j], al, spe[wave * MEL_PR + j]);
     }
   }
 

@@ -284,6 +284,9 @@ _SIGS = {
                                 C.POINTER(C.c_int32)]),
     "vx_mel_teacher_forced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vx_mel_get_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
+    "vx_mel_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "vx_op_mel_open": (C.c_int, [C.c_int32] + [C.c_void_p] * 13 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                 C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_void_p]),
     # Griffin-Lim vocoder (vocoder.GriffinLim)
     "vx_vocoder_create": (C.c_int, [C.POINTER(VxVocoderConfig), C.POINTER(C.c_void_p)]),
     "vx_vocoder_destroy": (None, [C.c_void_p]),
@@ -819,19 +822,22 @@ class Engine:
     def read_ar_kv(self) -> torch.Tensor:
         """The batch-1 KV cache as (L, 2, H, max_text + max_audio, head_dim): K and V of every layer, fp32 on fp32 engines,
         else bfloat16 (the values the decode attention reads)."""
-        L, H = self.cfg.num_decoder_layers, self.cfg.nhead
-        hd = self.cfg.decoder_dim // H
-        dtype = torch.float32 if self.precision in ("fp32", "f32") else torch.bfloat16
-        return self.read("ar_kv", (L, 2, H, self.max_text + self.max_audio, hd), dtype)
+        return _kv_tap(self.read, "ar_kv", self.cfg.num_decoder_layers, self.cfg.nhead, self.cfg.decoder_dim,
+                       self.max_text + self.max_audio, self.precision)
 
     def read_ar_mem(self) -> torch.Tensor:
         """VALL-F engines: the text memory of the batch-1 cross-attention as (L, 2, H, max_text, head_dim), K and V of every
         layer in the cache's element type.  Rows at and past the last prefilled text's length hold whatever an earlier, longer
         text left there."""
-        L, H = self.cfg.num_decoder_layers, self.cfg.nhead
-        hd = self.cfg.decoder_dim // H
-        dtype = torch.float32 if self.precision in ("fp32", "f32") else torch.bfloat16
-        return self.read("ar_mem", (L, 2, H, self.max_text, hd), dtype)
+        return _kv_tap(self.read, "ar_mem", self.cfg.num_decoder_layers, self.cfg.nhead, self.cfg.decoder_dim, self.max_text,
+                       self.precision)
+
+
+def _kv_tap(read, name: str, L: int, H: int, d: int, rows: int, precision: str) -> torch.Tensor:
+    """A K / V tap ("ar_kv", "ar_mem") through ``read(name, shape, dtype)`` as (L, 2, H, rows, head_dim) in the cache's element
+    type: fp32 on fp32 engines, else bfloat16."""
+    dtype = torch.float32 if precision in ("fp32", "f32") else torch.bfloat16
+    return read(name, (L, 2, H, rows, d // H), dtype)
 
 
 # ---- kernel-level ops (parity tests call the HIP kernels through the same C ABI) -------------------
@@ -866,11 +872,13 @@ def op_gemv(W, bias, x, relu=False):
     return y
 
 
-def op_gemm(A, W, bias=None, relu=False, mfma=False):
+def op_gemm(A, W, bias=None, relu=False, mfma=False, out=None):
+    """out: a caller's contiguous fp32 (M, N) buffer (a view into a guarded block, say) in place of a fresh one."""
     lib = load_library()
     M, K = A.shape
     N = W.shape[0]
-    Cm = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    Cm = torch.empty((M, N), dtype=torch.float32, device=A.device) if out is None else out
+    assert Cm.shape == (M, N) and Cm.dtype == torch.float32
     _check(lib.vx_op_gemm(_prec(A), int(mfma), _ptr(A), _ptr(W), _ptr(bias), _ptr(Cm), M, N, K, int(relu),
                           current_stream_ptr(A.device)))
     return Cm
@@ -1341,3 +1349,35 @@ class MelEngine:
         buf = (C.c_double * 4)()
         _check(self.lib.vx_mel_get_timings(self.h, buf, 4))
         return {"decode_ms": buf[0], "step_launches": buf[1], "kernels_per_step": buf[2], "encode_ms": buf[3]}
+
+    def read(self, name: str, shape, dtype=torch.float32, offset_bytes: int = 0) -> torch.Tensor:
+        out = torch.empty(shape, dtype=dtype)
+        _check(self.lib.vx_mel_read(self.h, name.encode(), _ptr(out), offset_bytes, out.numel() * out.element_size()))
+        return out
+
+    def read_kv(self) -> torch.Tensor:
+        """The decoder's self-attention cache as (L, 2, H, max_text + max_frames + 2, head_dim), as Engine.read_ar_kv."""
+        return _kv_tap(self.read, "ar_kv", self.cfg.num_layers, self.cfg.nhead, self.cfg.d_model,
+                       self.max_text + self.max_frames + 2, self.precision)
+
+    def read_mem(self) -> torch.Tensor:
+        """Every decoder layer's cross K / V of the last encode as (L, 2, H, max_text, head_dim), as Engine.read_ar_mem."""
+        return _kv_tap(self.read, "ar_mem", self.cfg.num_layers, self.cfg.nhead, self.cfg.d_model, self.max_text, self.precision)
+
+
+MEL_STATE = ("row", "pass", "n_gen", "S", "done", "stop_reason")
+
+
+def op_mel_open(xh, gamma, beta, Wh, bh, W0, b0, alpha, pe, x, frames, stops, state, W1=None, b1=None, W2=None, b2=None,
+                max_frames=0, n_forced=0, forced=None, launches=1):
+    """``launches`` launches of the mel decode step's opening kernel (vx_op_mel_open) on caller device buffers; x (d), frames
+    (rows, 100) and stops are written in place.  state: dict of MEL_STATE (stop_reason optional).  Returns (state after, the
+    arrival counter after the last launch)."""
+    lib = load_library()
+    st = (C.c_int32 * 6)(*[int(state.get(k, 0)) for k in MEL_STATE])
+    arrive = C.c_uint32(0xFFFFFFFF)
+    _check(lib.vx_op_mel_open(xh.numel(), _ptr(xh), _ptr(gamma), _ptr(beta), _ptr(Wh), _ptr(bh), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2),
+                              _ptr(W0), _ptr(b0), _ptr(alpha), _ptr(pe), pe.shape[0], _ptr(x), _ptr(frames), frames.shape[0], _ptr(stops),
+                              stops.numel(), st, int(max_frames), int(n_forced), _ptr(forced), int(launches), C.byref(arrive),
+                              current_stream_ptr(xh.device)))
+    return dict(zip(MEL_STATE, st)), arrive.value
