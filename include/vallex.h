@@ -1229,9 +1229,27 @@ int vx_spk_get_timings(const vx_spk* h, double* out, int32_t n);
  * Weight keys (fp32, host, torch layouts, transformers' names without the wav2vec2. / hubert. prefix, weight norm folded): as the
  * speaker encoder's feature encoder, projection and encoder without the WavLM tensors; layer flavour: every
  * feature_extractor.conv_layers.{i}.layer_norm.* and .conv.bias; feature_projection.layer_norm.* only with feat_proj_layer_norm;
- * lm_head.weight (vocab, d) / .bias. */
+ * lm_head.weight (vocab, d) / .bias.
+ * The bf16 encoder mode (VX_ASR_ENC_BF16, opt-in; VX_WSP_ENC_BF16 is the same mode of the Whisper recogniser's encoder): the
+ * pre-norm layers of step 4's stable flavour run on the bf16 matrix cores; everything else - the feature encoder, the projection,
+ * the positional convolution, the head, the decode, the alignment - is the fp32 mode's, launch for launch.
+ *   Rounded to bf16, round-to-nearest-even: the weights of the four linears of every encoder layer (q | k | v stacked, out_proj,
+ *   W1, W2), once, at *_finalize (the device keeps no fp32 copy of them); and every operand of those four GEMMs and of the two
+ *   attention products: the LayerNorm outputs LN1(h) and LN2(h), q, k, v, the attention probabilities before P.V, the attention
+ *   output, and gelu(W1 x + b1).
+ *   Kept in fp32: all accumulation; the softmax statistics (the row maximum and the sum, which is taken over the unrounded
+ *   probabilities); biases and LayerNorm parameters; the residual stream - out_proj and W2 add their bias and the residual in
+ *   fp32 and store fp32; LN_enc and its output.  The taps "hidden<l>" / "enc<l>" / "encoder" keep their meaning and their type.
+ * The softmax is an online one: the probabilities are rounded unnormalised, exp(s - running maximum), and the output is divided
+ * by the fp32 sum at the end; a restatement that rounds the normalised probabilities differs by a rounding of the same size, which
+ * the test bound covers.  Served: the stable flavour, head_dim 64, ffn a multiple of 64 (every released pre-norm width: d = 384,
+ * 512, 768, 1024, 1280 with ffn = 4 d); anything else -> VX_ERR_UNSUPPORTED at create.  A ragged batch stays bitwise what each
+ * utterance is alone, and a call is repeatable bit for bit: no atomics, every sum in a fixed order. */
 typedef struct vx_asr vx_asr;
-enum { VX_ASR_KEEP_TAPS = 1 };  /* vx_asr_config.flags: every hidden state keeps a buffer of its own ("hidden<l>" can be read) */
+enum {
+  VX_ASR_KEEP_TAPS = 1, /* vx_asr_config.flags: every hidden state keeps a buffer of its own ("hidden<l>" can be read) */
+  VX_ASR_ENC_BF16 = 2   /* vx_asr_config.flags: the bf16 encoder mode above */
+};
 enum { VX_ASR_NORMALIZE = 1 };  /* vx_asr_recognize flags */
 typedef struct vx_asr_config {
   int32_t struct_size;            /* sizeof(vx_asr_config) */
@@ -1250,14 +1268,16 @@ typedef struct vx_asr_config {
   float layer_norm_eps;
   int32_t max_batch;              /* utterances per call, <= 64 */
   int32_t max_samples;            /* samples per utterance */
-  int32_t flags;                  /* VX_ASR_KEEP_TAPS */
+  int32_t flags;                  /* VX_ASR_KEEP_TAPS | VX_ASR_ENC_BF16 */
 } vx_asr_config;
 /* Host only, no HIP call.  In this order: nulls, a wrong struct_size, a count or size outside its range (as vx_spk_create; vocab
  * < 1, blank outside [0, vocab)) -> VX_ERR_ARG; then add_adapter, conv_pos_batch_norm, an activation other than gelu,
  * feat_extract_norm != do_stable_layer_norm (a mix the released checkpoints do not have), the layer flavour without conv_bias, a
  * head_dim other than 16, 32 or 64, conv_kernel[0] > 32 or conv_stride[0] > 32, layer flavour: conv_dim[0] > 1024 or a layer-0 tile
  * (63 stride + k + k C_0 floats) above 60 KiB, max_batch > 64 -> VX_ERR_UNSUPPORTED with the field named; then max_samples below
- * vx_asr_min_samples -> VX_ERR_ARG; then max_batch x the layer-0 frames of max_samples above 2^31 - 1 -> VX_ERR_UNSUPPORTED. */
+ * vx_asr_min_samples -> VX_ERR_ARG; then max_batch x the layer-0 frames of max_samples above 2^31 - 1 -> VX_ERR_UNSUPPORTED.
+ * VX_ASR_ENC_BF16 (after the max_batch check): the group / post-norm flavour, a head_dim other than 64, an ffn that is no multiple
+ * of 64 -> VX_ERR_UNSUPPORTED with the field named. */
 int vx_asr_create(const vx_asr_config* cfg, vx_asr** out);
 void vx_asr_destroy(vx_asr* h);
 /* Host only.  data: HOST fp32 of `shape`.  Unknown key or wrong shape -> VX_ERR_WEIGHTS; after vx_asr_finalize -> VX_ERR_STATE. */
@@ -1374,9 +1394,16 @@ int vx_falign_asr(vx_asr* h, int32_t n, const int32_t* targets, const int32_t* t
  * model.decoder.embed_tokens.weight (vocab, d), model.decoder.embed_positions.weight (Tt, d), model.decoder.layers.{l}. as the
  * encoder's plus .encoder_attn.* and .encoder_attn_layer_norm.*; model.decoder.layer_norm.*; proj_out.weight (vocab, d) only with
  * tie_proj = 0.
- * Not built: beam search, temperature fallback, timestamps, language detection, long-form transcription, bf16. */
+ * VX_WSP_ENC_BF16 (opt-in): the encoder layers of step 2 in the bf16 encoder mode defined with the CTC recogniser above (LN1, LN2,
+ * q, k, v, the probabilities, the attention output and gelu(W1 ..) rounded to bf16, the four matrices of every layer kept in bf16
+ * only; "enc<l>" and "encoder" stay fp32).  The log-mel front end, conv1 / conv2, the cross-attention K / V projections and the
+ * whole token loop are the fp32 mode's.
+ * Not built: beam search, temperature fallback, timestamps, language detection, long-form transcription, a bf16 token loop. */
 typedef struct vx_wsp vx_wsp;
-enum { VX_WSP_KEEP_TAPS = 1 };  /* vx_wsp_config.flags: "enc<l>" and the per-step "logits" keep buffers of their own */
+enum {
+  VX_WSP_KEEP_TAPS = 1, /* vx_wsp_config.flags: "enc<l>" and the per-step "logits" keep buffers of their own */
+  VX_WSP_ENC_BF16 = 2   /* vx_wsp_config.flags: the encoder layers in the bf16 encoder mode */
+};
 enum { VX_WSP_STOP_EOS = 1, VX_WSP_STOP_MAX_NEW = 2, VX_WSP_STOP_MAX_TARGET = 3 };
 typedef struct vx_wsp_config {
   int32_t struct_size;            /* sizeof(vx_wsp_config) */
@@ -1389,12 +1416,13 @@ typedef struct vx_wsp_config {
   int32_t tie_proj;               /* 1: proj_out.weight is model.decoder.embed_tokens.weight */
   int32_t eos_token_id;
   int32_t max_batch;              /* utterances per call, <= 64 */
-  int32_t flags;                  /* VX_WSP_KEEP_TAPS */
+  int32_t flags;                  /* VX_WSP_KEEP_TAPS | VX_WSP_ENC_BF16 */
 } vx_wsp_config;
 /* Host only, no HIP call.  In this order: nulls, a wrong struct_size, a count or size below 1 (max_target_positions below 2),
  * eos_token_id outside [0, vocab), unknown flags -> VX_ERR_ARG; then an activation other than gelu, a head_dim other than 64,
  * num_mel_bins or an ffn dim that is no multiple of 16, more than 4096 source or target positions, max_batch > 64 ->
- * VX_ERR_UNSUPPORTED with the field named. */
+ * VX_ERR_UNSUPPORTED with the field named; then, with VX_WSP_ENC_BF16, an encoder_ffn_dim that is no multiple of 64 ->
+ * VX_ERR_UNSUPPORTED naming it. */
 int vx_wsp_create(const vx_wsp_config* cfg, vx_wsp** out);
 void vx_wsp_destroy(vx_wsp* h);
 /* Host only.  data: HOST fp32 of `shape`.  Unknown key or wrong shape -> VX_ERR_WEIGHTS; after vx_wsp_finalize -> VX_ERR_STATE. */
@@ -1456,6 +1484,20 @@ int vx_op_wsp_head(const float* logits, int32_t n, int32_t V, const uint8_t* sup
                    int32_t out_stride, int32_t eos, int32_t max_target, void* stream);
 int vx_op_wsp_embed(const float* tok_emb, const float* pos_emb, const int32_t* cur, const int32_t* pos, float* x, int32_t n, int32_t d,
                     int32_t vocab, int32_t max_pos, void* stream);
+/* Test-only: the bf16 encoder mode's kernels on caller data, through the launchers the recognisers use.  Every pointer is DEVICE
+ * unless said otherwise; each call waits for its work.
+ * vx_op_enc16_gemm: A (M, K) and W (N, K) bf16, bias (N) fp32.  epi 0: out (M, N) bf16 = A W^T + bias; 1: bf16 = gelu(A W^T + bias),
+ * the exact GELU; 2: out (M, N) fp32 = (A W^T + bias) + res, res (M, N) fp32 (it may be `out`).  N no multiple of 8, K no multiple
+ * of 64, a null operand, an unknown epi -> VX_ERR_ARG.
+ * vx_op_enc16_add_ln: s = a[row] + b[bmod > 0 ? row % bmod : row] (b NULL: s = a[row]) to sum (fp32, NULL: not stored; it may be
+ * a); y (M, d) bf16 = LayerNorm(s) w + beta.
+ * vx_op_enc16_attn: qkv (rows, 3 x 64 heads) bf16 -> out (rows, 64 heads) bf16, softmax(q k / 8) v per head over each of the n
+ * segments' own rows; seg_len (n) HOST int32, the segments packed tightly in their order; n <= 64. */
+int vx_op_enc16_gemm(int32_t epi, const void* A_bf16, const void* W_bf16, const float* bias, const float* res, void* out, int64_t M,
+                     int32_t N, int32_t K, void* stream);
+int vx_op_enc16_add_ln(const float* a, const float* b, int32_t bmod, const float* w, const float* beta, float* sum, void* y_bf16,
+                       int64_t M, int32_t d, float eps, void* stream);
+int vx_op_enc16_attn(const void* qkv_bf16, void* out_bf16, int32_t n, const int32_t* seg_len, int32_t heads, void* stream);
 
 #ifdef __cplusplus
 }

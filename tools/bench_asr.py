@@ -6,7 +6,13 @@ by an argmax.  Torch runs per utterance: a padded batch is a different function 
 padding in, and both flavours' attention needs a mask).  Weights are `asr.synthetic_state_dict(seed 0)`: seeded, not trained.
 One JSON line on stdout, the same object written to --out.
 
-    python tools/bench_asr.py [--reps 3] [--points 1x3,1x10,32x10,64x20] [--configs base,large]
+    python tools/bench_asr.py [--reps 3] [--points 1x3,1x10,32x10,64x20] [--configs base,large] [--precision fp32|bf16|both]
+
+`--precision both` times the fp32 handle and the bf16 encoder mode (`SpeechRecognizer(precision="bf16")`, the layer / stable flavour
+only: `base` is refused and recorded so) of the same build in one invocation, the timed reps alternating; the rows go to
+profiles/asr_bf16_times.json (the default --out of any precision but fp32; profiles/asr_times.json keeps the fp32 record) with the
+spread (max - min) of the reps.  The handle has no device-event split: the two modes differ in the encoder layers' launches and in
+nothing else, so the difference of the whole calls is the encoder's; `encoder_layer_flops` is B L (2 T (4 d d + 2 d ffn) + 4 T T d).
 
 Each point is warmed per implementation, then timed with device events around `inner` back-to-back calls (chosen so that a rep
 lasts about 50 ms or more); the figure is the best of the reps.  The HIP figure includes the copy of the token ids to the host and
@@ -33,8 +39,12 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--points", default="1x3,1x10,32x10,64x20", help="BxSECONDS,...")
     ap.add_argument("--configs", default="base,large")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "asr_times.json"))
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16", "both"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    precisions = ("fp32", "bf16") if args.precision == "both" else (args.precision,)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "asr_times.json" if args.precision == "fp32" else "asr_bf16_times.json")
     import torch
 
     import __graft_entry__ as ge
@@ -70,18 +80,24 @@ def main():
             n = 16000 * sec
             row = {"config": name, "B": B, "seconds": sec, "samples": n}
             print(f"{name} {B}x{sec}s", file=sys.stderr, flush=True)
+            recs = {}
             try:
-                rec = SpeechRecognizer(cfg, vocab, max_batch=B, max_seconds=sec, state_dict=sd).to(dev)
-                row["workspace_bytes"] = rec.workspace_bytes()
+                for prec in precisions:
+                    recs[prec] = SpeechRecognizer(cfg, vocab, max_batch=B, max_seconds=sec, state_dict=sd, precision=prec).to(dev)
+                    row["workspace_bytes" + ("" if prec == "fp32" else "_" + prec)] = recs[prec].workspace_bytes()
+                rec = recs[precisions[0]]
                 row["frames"] = rec.num_frames(n)
             except Exception as e:  # a geometry the handle refuses
                 row["hip"] = "not measured: " + str(e).splitlines()[0][:200]
                 out["points"].append(row)
+                for r in recs.values():
+                    r.close()
                 continue
             g = torch.Generator().manual_seed(B * 100 + sec)
             wavs = [(0.3 * torch.randn(n, generator=g)).to(dev) for _ in range(B)]
-            impls = {"hip": lambda: rec.recognize(wavs, sr=16000),
-                     "torch_gpu_per_utterance": lambda: [R.forward(rsd, cfg, w, torch.float32)["logits"].argmax(1) for w in wavs]}
+            impls = {("hip" if prec == "fp32" else "hip_" + prec): (lambda r: lambda: r.recognize(wavs, sr=16000))(recs[prec]) for prec in precisions}
+            impls = {**impls, "torch_gpu_per_utterance": lambda: [R.forward(rsd, cfg, w, torch.float32)["logits"].argmax(1) for w in wavs]}
+            n_impls = len(impls)
             inner, ok = {}, {}
             for k, fn in impls.items():
                 try:
@@ -93,7 +109,7 @@ def main():
                 except RuntimeError as e:
                     row[k] = "not measured: " + str(e).splitlines()[0][:200]
                     torch.cuda.empty_cache()
-            if len(ok) == 2:
+            if len(ok) == n_impls:
                 with torch.no_grad():
                     ours, theirs = rec.logits(wavs[:1], sr=16000)[0], R.forward(rsd, cfg, wavs[0], torch.float32)["logits"]
                 row["hip_vs_torch_gpu_max_abs_diff"] = float((ours - theirs).abs().max())
@@ -105,13 +121,24 @@ def main():
                         times[k].append(timed(fn, inner[k]))
             for k, v in times.items():
                 row[k + "_ms"] = round(min(v), 4)
+                row[k + "_ms_spread"] = round(max(v) - min(v), 4)
                 row[k + "_inner"] = inner[k]
+            if "hip" in times and "hip_bf16" in times:
+                T, d, f, L = row["frames"], int(cfg.hidden_size), int(cfg.intermediate_size), int(cfg.num_hidden_layers)
+                row["encoder_layer_flops"] = B * L * (2 * T * (4 * d * d + 2 * d * f) + 4 * T * T * d)
+                row["hip_fp32_over_bf16"] = round(row["hip_ms"] / row["hip_bf16_ms"], 3)
+                row["bf16_faster_by_more_than_the_spread"] = bool(row["hip_ms"] - row["hip_bf16_ms"] > max(row["hip_ms_spread"], row["hip_bf16_ms_spread"]))
+                with torch.no_grad():
+                    a, b = recs["fp32"].recognize(wavs, sr=16000), recs["bf16"].recognize(wavs, sr=16000)
+                row["same_transcript_share"] = sum(x.tokens == y.tokens for x, y in zip(a, b)) / B
             if "hip" in times:
                 row["hip_realtime_factor"] = round(B * sec / (row["hip_ms"] * 1e-3), 1)  # seconds of audio per second
-            if len(ok) == 2:
-                row["torch_over_hip"] = round(row["torch_gpu_per_utterance_ms"] / row["hip_ms"], 3)
+            for k in times:
+                if k.startswith("hip") and "torch_gpu_per_utterance" in times:
+                    row["torch_over_" + k] = round(row["torch_gpu_per_utterance_ms"] / row[k + "_ms"], 3)
             out["points"].append(row)
-            rec.close()
+            for r in recs.values():
+                r.close()
             del wavs
             torch.cuda.empty_cache()
             with open(args.out, "w") as f:  # kept up to date point by point: a run that is cut short leaves what it measured

@@ -120,11 +120,16 @@ class SpeechRecognizer(W2vHandle):
     checkpoint's `vocab.json` mapping token -> id, with `|` as the word delimiter and `<pad>` as the CTC blank unless `blank` names
     another token.  A call serves up to `max_batch` (<= 64) utterances of up to `max_seconds` at 16 kHz each.  Adapters,
     `conv_pos_batch_norm`, activations other than GELU, head dimensions other than 16 / 32 / 64 and a feature encoder norm that does
-    not go with the encoder (`group` with post-norm, `layer` with stable) raise NotImplementedError naming the field."""
+    not go with the encoder (`group` with post-norm, `layer` with stable) raise NotImplementedError naming the field.
+    `precision="bf16"` runs the encoder layers of the layer / stable flavour at head_dim 64 on the bf16 matrix cores (include/vallex.h:
+    the bf16 encoder mode); the other flavour and head dimensions are refused by name.  Any other precision raises ValueError."""
     _PREFIX, _NAME = "vx_asr", "SpeechRecognizer"
 
     def __init__(self, config, vocab: Dict[str, int], max_batch: int = 32, max_seconds: float = 20.0, state_dict: Optional[dict] = None,
-                 keep_taps: bool = False, blank: str = "<pad>", word_delimiter: str = "|"):
+                 keep_taps: bool = False, blank: str = "<pad>", word_delimiter: str = "|", precision: str = "fp32"):
+        if precision not in _e.ENC_PRECISIONS:
+            raise ValueError(f"precision = {precision!r}: one of {_e.ENC_PRECISIONS}")
+        self.precision = precision
         c = self.config = RecognizerConfig.from_any(config)
         if c.add_adapter:
             raise NotImplementedError("add_adapter: adapters are not served")
@@ -166,7 +171,7 @@ class SpeechRecognizer(W2vHandle):
         s.feat_proj_layer_norm = int(bool(c.feat_proj_layer_norm))
         s.add_adapter, s.conv_pos_batch_norm = int(bool(c.add_adapter)), int(bool(c.conv_pos_batch_norm))
         s.activation = 0
-        s.flags = _e.VX_ASR_KEEP_TAPS if self.keep_taps else 0
+        s.flags = (_e.VX_ASR_KEEP_TAPS if self.keep_taps else 0) | (_e.VX_ASR_ENC_BF16 if self.precision == "bf16" else 0)
         return s
 
     @property

@@ -81,8 +81,13 @@ int run_call(const vx_asr* g, const W2vRun& x, int flags, long* rows) {
       VXC(run_ln(x, L.ln2, e.mid, e.tmp, e.hidden(l + 1), M, d));
     }
   } else {  // stable: x0 + the positional term is hidden state 0; encoder.layer_norm closes the stack
-    VXC(run_add_ln(x, bw.layers[0].ln1, ws + p.x0, e.tmp, e.hidden(0), e.nrm, M, d));
-    VXC(run_prenorm_layers(x, e, bw.layers, bw.enc_ln, nullptr, e.hidden(c.layers)));
+    if (g->bf16) {
+      VXC(run_add_ln16(x, bw.layers[0].ln1, ws + p.x0, e.tmp, 0, e.hidden(0), e.nrm16, M, d));
+      VXC(run_prenorm_layers_bf16(x, e, bw.layers, bw.enc_ln, nullptr, e.hidden(c.layers)));
+    } else {
+      VXC(run_add_ln(x, bw.layers[0].ln1, ws + p.x0, e.tmp, e.hidden(0), e.nrm, M, d));
+      VXC(run_prenorm_layers(x, e, bw.layers, bw.enc_ln, nullptr, e.hidden(c.layers)));
+    }
   }
   // ---- head
   return run_lin(x, g->head, e.hidden(c.layers), d, ws + g->p_logits, M, SPK_ACT_NONE);
@@ -102,13 +107,14 @@ extern "C" int vx_asr_create(const vx_asr_config* cfg, vx_asr** out) {
     return fail(VX_ERR_ARG, "vx_asr_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_asr_config));
   const vx_asr_config& c = *cfg;
   const char* what = "vx_asr_create";
-  const W2vGeom q = w2v_geom(c, c.feat_proj_layer_norm, (c.flags & VX_ASR_KEEP_TAPS) != 0);
+  W2vGeom q = w2v_geom(c, c.feat_proj_layer_norm, (c.flags & VX_ASR_KEEP_TAPS) != 0);
+  q.enc_bf16 = (c.flags & VX_ASR_ENC_BF16) != 0;
   VXC(w2v_validate(q, what, W2V_CHECK_SIZES));
   VXC(w2v_validate(q, what, W2V_CHECK_CONVS));
   if (c.pos_kernel < 1 || c.pos_groups < 1) return fail(VX_ERR_ARG, "vx_asr_create: pos_kernel %d, pos_groups %d", c.pos_kernel, c.pos_groups);
   if (c.vocab < 1 || c.blank < 0 || c.blank >= c.vocab) return fail(VX_ERR_ARG, "vx_asr_create: vocab %d, blank %d", c.vocab, c.blank);
   VXC(w2v_validate(q, what, W2V_CHECK_RATIOS));
-  if (c.flags & ~VX_ASR_KEEP_TAPS) return fail(VX_ERR_ARG, "vx_asr_create: flags = %d", c.flags);
+  if (c.flags & ~(VX_ASR_KEEP_TAPS | VX_ASR_ENC_BF16)) return fail(VX_ERR_ARG, "vx_asr_create: flags = %d", c.flags);
   if (c.add_adapter != 0) return fail(VX_ERR_UNSUPPORTED, "vx_asr_create: add_adapter");
   if (c.conv_pos_batch_norm != 0) return fail(VX_ERR_UNSUPPORTED, "vx_asr_create: conv_pos_batch_norm");
   if (c.activation != 0) return fail(VX_ERR_UNSUPPORTED, "vx_asr_create: activation = %d (gelu is served)", c.activation);
@@ -122,9 +128,15 @@ extern "C" int vx_asr_create(const vx_asr_config* cfg, vx_asr** out) {
     return fail(VX_ERR_UNSUPPORTED, "vx_asr_create: conv layer 0: dim %d x kernel %d (up to %d channels and %d bytes of tile are served)",
                 c.conv_dim[0], c.conv_kernel[0], ASR_C0_MAXC, ASR_C0_LDS);
   VXC(w2v_validate(q, what, W2V_CHECK_BATCH));
+  if (q.enc_bf16) {
+    if (!c.do_stable_layer_norm)
+      return fail(VX_ERR_UNSUPPORTED, "vx_asr_create: the bf16 encoder serves do_stable_layer_norm = 1 (the layer / stable flavour), not the group / post-norm one");
+    VXC(enc_bf16_check(what, c.hidden, c.heads, c.ffn, "heads", "ffn"));
+  }
 
   std::unique_ptr<vx_asr> g(new vx_asr());
   g->cfg = c;
+  g->bf16 = q.enc_bf16 != 0;
   g->m.q = q;
   VXC(w2v_size(g->m, what, 1));  // one encoder frame
   w2v_plan_rows(g->m, true);

@@ -13,6 +13,7 @@
 
 #include "spk_host.hpp"
 #include "asr_kernels.hpp"
+#include "enc_bf16_kernels.hpp"
 
 namespace vx {
 namespace {
@@ -27,6 +28,7 @@ struct W2vCallState {  // the last call, for *_read
 
 struct SpeechDev {
   DevBuf<float> w;   // every packed tensor
+  DevBuf<uint16_t> w16;  // the bf16 encoder mode: the encoder layers' matrices
   DevBuf<float> ws;  // the workspace, carved by the unit's plan
   CallStage stage;   // the per-call tables
 };
@@ -37,6 +39,8 @@ struct SpeechHandle {
   std::map<std::string, HostW> w;
   bool finalized = false;
   std::vector<float> packed;  // filled by *_finalize
+  bool bf16 = false;               // the bf16 encoder mode (set at create)
+  std::vector<uint16_t> packed16;  // its encoder matrices, rounded once by *_finalize; `packed` does not hold them
   int device = -1;            // >= 0: `dev` is complete
   std::unique_ptr<Dev> dev;
   W2vCallState call;
@@ -81,10 +85,34 @@ void enc_layer_keys(G* g, const std::string& pre, const EncNames& nm, int d, int
   norm_keys(g, pre + nm.ln2, d);
 }
 
-// q | k | v stacked into one GEMM; a k without a bias (Whisper) gets zeros.
+// fp32 -> bf16 bits, round to nearest even (NaN stays NaN).
+inline uint16_t bf16_rne(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+size_t push16(std::vector<uint16_t>& p, const std::vector<float>& v) {
+  while (p.size() % 8) p.push_back(0);  // every tensor starts on a 16-byte boundary
+  const size_t at = p.size();
+  for (float f : v) p.push_back(bf16_rne(f));
+  return at;
+}
+
+// A linear of the bf16 encoder mode: the matrix rounded into `packed16` (l.w counts its elements), the bias fp32 in `packed`.
 template <class G>
-SpkLin pack_qkv(G* g, const std::string& prefix, int d, bool k_has_bias) {
-  std::vector<float> wq, bq;
+SpkLin pack_linear16(G* g, const std::vector<float>& w, const std::vector<float>& b, int N, int K) {
+  SpkLin l;
+  l.w = push16(g->packed16, w);
+  l.b = push(g->packed, b);
+  l.has_bias = true; l.C = K; l.N = N;
+  return l;
+}
+
+// q | k | v stacked; a k without a bias (Whisper) gets zeros.
+template <class G>
+void stack_qkv(G* g, const std::string& prefix, int d, bool k_has_bias, std::vector<float>& wq, std::vector<float>& bq) {
   for (const char* s : {"q_proj", "k_proj", "v_proj"}) {
     const HostW& w = g->w[prefix + "." + s + ".weight"];
     wq.insert(wq.end(), w.data.begin(), w.data.end());
@@ -95,6 +123,13 @@ SpkLin pack_qkv(G* g, const std::string& prefix, int d, bool k_has_bias) {
       bq.insert(bq.end(), b.data.begin(), b.data.end());
     }
   }
+}
+
+// q | k | v stacked into one GEMM.
+template <class G>
+SpkLin pack_qkv(G* g, const std::string& prefix, int d, bool k_has_bias) {
+  std::vector<float> wq, bq;
+  stack_qkv(g, prefix, d, k_has_bias, wq, bq);
   SpkLin l;
   l.w = push(g->packed, wq);
   l.b = push(g->packed, bq);
@@ -105,6 +140,18 @@ SpkLin pack_qkv(G* g, const std::string& prefix, int d, bool k_has_bias) {
 template <class G>
 EncLayer pack_enc_layer(G* g, const std::string& pre, const EncNames& nm, int d, int ffn, bool k_has_bias) {
   EncLayer ly;
+  if (g->bf16) {  // the four matrices in bf16 only
+    std::vector<float> wq, bq;
+    stack_qkv(g, pre + nm.attn, d, k_has_bias, wq, bq);
+    ly.qkv = pack_linear16(g, wq, bq, 3 * d, d);
+    auto lin16 = [&](const std::string& name, int N, int K) { return pack_linear16(g, g->w[name + ".weight"].data, g->w[name + ".bias"].data, N, K); };
+    ly.out = lin16(pre + nm.attn + ".out_proj", d, d);
+    ly.ln1 = pack_norm(g, pre + nm.ln1);
+    ly.ff1 = lin16(pre + nm.ff1, ffn, d);
+    ly.ff2 = lin16(pre + nm.ff2, d, ffn);
+    ly.ln2 = pack_norm(g, pre + nm.ln2);
+    return ly;
+  }
   ly.qkv = pack_qkv(g, pre + nm.attn, d, k_has_bias);
   ly.out = pack_linear(g, pre + nm.attn + ".out_proj", d, d);
   ly.ln1 = pack_norm(g, pre + nm.ln1);
@@ -120,6 +167,7 @@ int finalize_begin(G* g) {
   for (auto& kv : g->w)
     if (!kv.second.set) return fail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
   g->packed.clear();
+  g->packed16.clear();
   return VX_OK;
 }
 
@@ -138,6 +186,10 @@ int init_device(G* g, Dev* fresh, size_t ws_floats, size_t stage_bytes) {
   g->device = dev;
   VXC(fresh->w.alloc(g->packed.size() + 4));
   HIPC(hipMemcpy(fresh->w.get(), g->packed.data(), g->packed.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (!g->packed16.empty()) {
+    VXC(fresh->w16.alloc(g->packed16.size() + 8));
+    HIPC(hipMemcpy(fresh->w16.get(), g->packed16.data(), g->packed16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
   VXC(fresh->ws.alloc(ws_floats + 4));
   return fresh->stage.init(stage_bytes);
 }
@@ -206,6 +258,9 @@ struct EncRun {
   int d = 0, H = 0, hd = 0, ffn = 0, Tmax = 0;
   int table = 0;              // the rows' segment table
   const int* hseg = nullptr;  // its host copy
+  // the bf16 encoder mode: its rows live where the fp32 mode's nrm / qkv / att / ff do, and its matrices in `W16`
+  ebf_t *nrm16 = nullptr, *qkv16 = nullptr, *att16 = nullptr, *ff16 = nullptr;
+  const ebf_t* W16 = nullptr;
   float* hidden(int l) const { return hid + hid_stride * (size_t)(keep ? l : (l & 1)); }
 };
 
@@ -214,6 +269,8 @@ EncRun enc_run(float* ws, const Plan& p, bool keep) {
   EncRun e;
   e.hid = ws + p.hid; e.mid = ws + p.mid; e.nrm = ws + p.nrm; e.qkv = ws + p.qkv; e.att = ws + p.att; e.tmp = ws + p.tmp; e.ff = ws + p.ff;
   e.hid_stride = p.hid_stride; e.keep = keep;
+  e.nrm16 = reinterpret_cast<ebf_t*>(e.nrm); e.qkv16 = reinterpret_cast<ebf_t*>(e.qkv); e.att16 = reinterpret_cast<ebf_t*>(e.att);
+  e.ff16 = reinterpret_cast<ebf_t*>(e.ff);
   return e;
 }
 
@@ -247,6 +304,81 @@ int run_prenorm_layers(const SpkCall& x, const EncRun& e, const std::vector<EncL
   return VX_OK;
 }
 
+// ---- the bf16 encoder mode (enc_bf16_kernels.hpp) ------------------------------------------------------------------------------------
+// What the mode serves, checked at create: `what` is the entry point, the names are the config's fields.
+int enc_bf16_check(const char* what, int d, int heads, int ffn, const char* heads_name, const char* ffn_name) {
+  if (d % heads != 0 || d / heads != 64)
+    return fail(VX_ERR_UNSUPPORTED, "%s: the bf16 encoder serves head_dim 64, not hidden / %s = %d / %d", what, heads_name, d, heads);
+  if (ffn % 64 != 0) return fail(VX_ERR_UNSUPPORTED, "%s: the bf16 encoder serves %s in multiples of 64, not %d", what, ffn_name, ffn);
+  return VX_OK;
+}
+
+// The launchers: every shape rule of the kernels is checked here, for the recognisers and for the vx_op_enc16_* entries alike.
+int launch_ebf_gemm(int epi, const ebf_t* A, const ebf_t* W, const float* bias, const float* res, void* out, long M, int N, int K, hipStream_t s) {
+  if (M <= 0) return VX_OK;
+  if (N < 8 || N % 8 != 0 || K < EBF_BK || K % EBF_BK != 0) return fail(VX_ERR_ARG, "bf16 encoder GEMM: N = %d (multiples of 8), K = %d (multiples of %d)", N, K, EBF_BK);
+  if (!A || !W || !bias || !out || (epi == EBF_EPI_RESID_F32 && !res)) return fail(VX_ERR_ARG, "bf16 encoder GEMM: null operand");
+  const long mt = (M + EBF_BM - 1) / EBF_BM;
+  if (mt > 65535) return fail(VX_ERR_CAPACITY, "bf16 encoder GEMM: M = %ld rows", M);
+  EbfGemmArgs a{A, W, bias, res, out, M, N, K};
+  const dim3 grid((unsigned)((N + EBF_BN - 1) / EBF_BN), (unsigned)mt);
+  if (epi == EBF_EPI_BF16) ebf_gemm<EBF_EPI_BF16><<<grid, 256, 0, s>>>(a);
+  else if (epi == EBF_EPI_GELU_BF16) ebf_gemm<EBF_EPI_GELU_BF16><<<grid, 256, 0, s>>>(a);
+  else if (epi == EBF_EPI_RESID_F32) ebf_gemm<EBF_EPI_RESID_F32><<<grid, 256, 0, s>>>(a);
+  else return fail(VX_ERR_ARG, "bf16 encoder GEMM: epilogue %d", epi);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+int launch_ebf_add_ln(const float* a, const float* b, int bmod, const float* w, const float* beta, float* sum, ebf_t* y, long M, int d, float eps,
+                      hipStream_t s) {
+  if (M <= 0) return VX_OK;
+  ebf_add_layernorm<<<(unsigned)((M + 3) / 4), 256, 0, s>>>(a, b, bmod, w, beta, sum, y, M, d, eps);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+// Attention over the rows of `seg` (hseg: its host copy, n + 1 offsets), qkv rows [M][3 d] -> out rows [M][d], d = 64 H.
+int launch_ebf_attn(const ebf_t* qkv, ebf_t* out, const int* seg, const int* hseg, int n, int H, hipStream_t s) {
+  long tiles = 0;
+  for (int i = 0; i < n; ++i) tiles += ((long)hseg[i + 1] - hseg[i] + EBF_QT - 1) / EBF_QT;
+  if (tiles <= 0) return VX_OK;
+  if (H < 1 || H > 65535 || tiles > 2147483647L) return fail(VX_ERR_ARG, "bf16 encoder attention: %d heads, %ld query tiles", H, tiles);
+  EbfAttnArgs a{qkv, out, seg, n, H, 64 * H};
+  ebf_attention<<<dim3((unsigned)tiles, (unsigned)H), 256, 0, s>>>(a);
+  HIPC(hipGetLastError());
+  return VX_OK;
+}
+
+int run_add_ln16(const SpkCall& x, const SpkNorm& nm, const float* a, const float* b, int bmod, float* sum, ebf_t* y, long M, int d) {
+  return launch_ebf_add_ln(a, b, bmod, x.W + nm.w, x.W + nm.b, sum, y, M, d, x.eps, x.s);
+}
+
+int run_lin16(const SpkCall& x, const EncRun& e, const SpkLin& l, int epi, const ebf_t* in, const float* res, void* out) {
+  return launch_ebf_gemm(epi, in, e.W16 + l.w, x.W + l.b, res, out, e.M, l.N, l.C, x.s);
+}
+
+// run_prenorm_layers in the bf16 encoder mode.  The caller has written hidden(0) and its ln1 rows `nrm16`.  out_proj and ff2 add
+// their bias and the fp32 residual in the GEMM's epilogue, so the LayerNorms here read one operand; the last one is the fp32
+// LayerNorm of the fp32 mode.
+int run_prenorm_layers_bf16(const SpkCall& x, const EncRun& e, const std::vector<EncLayer>& layers, const SpkNorm& last_ln, float* last_sum,
+                            float* last_out) {
+  const int n_layers = (int)layers.size();
+  for (int l = 0; l < n_layers; ++l) {
+    const EncLayer& L = layers[l];
+    VXC(run_lin16(x, e, L.qkv, EBF_EPI_BF16, e.nrm16, nullptr, e.qkv16));
+    VXC(launch_ebf_attn(e.qkv16, e.att16, x.table(e.table), e.hseg, x.n, e.H, x.s));
+    VXC(run_lin16(x, e, L.out, EBF_EPI_RESID_F32, e.att16, e.hidden(l), e.mid));
+    VXC(run_add_ln16(x, L.ln2, e.mid, nullptr, 0, nullptr, e.nrm16, e.M, e.d));
+    VXC(run_lin16(x, e, L.ff1, EBF_EPI_GELU_BF16, e.nrm16, nullptr, e.ff16));
+    float* next = l + 1 < n_layers ? e.hidden(l + 1) : (last_sum ? last_sum : e.tmp);
+    VXC(run_lin16(x, e, L.ff2, EBF_EPI_RESID_F32, e.ff16, e.mid, next));
+    if (l + 1 < n_layers) VXC(run_add_ln16(x, layers[l + 1].ln1, next, nullptr, 0, nullptr, e.nrm16, e.M, e.d));
+    else VXC(run_ln(x, last_ln, next, nullptr, last_out, e.M, e.d));
+  }
+  return VX_OK;
+}
+
 // ---- the Wav2Vec2 backbone -------------------------------------------------------------------------------------------------------------
 // The geometry vx_spk_config and vx_asr_config share.
 struct W2vGeom {
@@ -256,6 +388,7 @@ struct W2vGeom {
   int feat_extract_norm = 0, do_stable_layer_norm = 0, feat_proj_layer_norm = 1;
   float layer_norm_eps = 0.f;
   int max_batch = 0, max_samples = 0, keep_taps = 0;
+  int enc_bf16 = 0;  // the bf16 encoder mode
 };
 
 template <class C>
@@ -386,12 +519,13 @@ void w2v_plan_rows(W2vModel& m, bool own_c0) {
   p.x0 = p.take(rows * d);
   p.hid_stride = (rows * d + 3) / 4 * 4;
   p.hid = p.take(p.hid_stride * (c.keep_taps ? (size_t)c.layers + 1 : 2));
+  const size_t per = c.enc_bf16 ? 2 : 1;  // the bf16 mode's rows: two elements a float
   p.mid = p.take(rows * d);
-  if (own_c0) p.nrm = p.take(rows * d);
-  p.qkv = p.take(rows * 3 * d);
-  p.att = p.take(rows * d);
+  if (own_c0) p.nrm = p.take(rows * d / per);
+  p.qkv = p.take(rows * 3 * d / per);
+  p.att = p.take(rows * d / per);
   p.tmp = p.take(rows * d);
-  p.ff = p.take(rows * (size_t)c.ffn);
+  p.ff = p.take(rows * (size_t)c.ffn / per);
 }
 
 // The statistics of the waveform and of the GroupNorm, after the unit's own buffers.
@@ -484,6 +618,7 @@ struct W2vRun : SpkCall {
   double* partial;
   const float* const* wav;  // device
   const int* n_samples;     // device
+  const uint16_t* W16;      // the bf16 encoder mode's matrices, else null
   int* hseg;                // host: [n_tables][MB + 1]
   long rows_of(int t) const { return (long)hseg[(size_t)t * (MB + 1) + n]; }
 };
@@ -505,7 +640,7 @@ int w2v_stage_begin(G* g, int n_tables, int n, const float* const* wav, const in
     hns[i] = n_samples[i];
     for (int t = 0; t < c.n_conv; ++t) hseg[(size_t)t * (MB + 1) + i + 1] = hseg[(size_t)t * (MB + 1) + i] + (int)frames_of(c, n_samples[i], t);
   }
-  x.m = &g->m; x.eps = c.layer_norm_eps; x.W = dv.w.get(); x.ws = dv.ws.get(); x.partial = dv.partial.get(); x.MB = (int)MB; x.n = n; x.s = s;
+  x.m = &g->m; x.eps = c.layer_norm_eps; x.W = dv.w.get(); x.ws = dv.ws.get(); x.partial = dv.partial.get(); x.W16 = dv.w16.get(); x.MB = (int)MB; x.n = n; x.s = s;
   x.wav = dv.stage.template dev<const float* const>();
   x.n_samples = dv.stage.template dev<const int>(o_ns);
   x.seg = dv.stage.template dev<const int>(o_seg);
@@ -579,6 +714,7 @@ int w2v_run_features(const W2vRun& x, bool normalize, EncRun& e) {
   e = enc_run(ws, p, c.keep_taps != 0);
   e.M = x.rows_of(te); e.d = d; e.H = c.heads; e.hd = m.hd; e.ffn = c.ffn; e.Tmax = m.Tmax;
   e.table = te; e.hseg = x.hseg + (size_t)te * (x.MB + 1);
+  e.W16 = reinterpret_cast<const ebf_t*>(x.W16);
   const float* feats = conv_buf(te);
   const int Cl = c.conv_dim[te];
   if (c.feat_proj_layer_norm) VXC(run_ln(x, bw.fp_ln, feats, nullptr, ws + p.fpn, e.M, Cl));
@@ -607,7 +743,7 @@ int w2v_timings(const G* g, const char* what, size_t extra_bytes, double* out, i
   if (!g || !out || n < 0 || n > 4) return fail(VX_ERR_ARG, "%s_get_timings: null argument or n outside [0, 4]", what);
   const W2vCallState& cs = g->call;
   const double v[4] = {cs.last_ms, (double)(g->m.p.total * sizeof(float) + g->m.p.partial * sizeof(double) + extra_bytes),
-                       (double)(g->packed.size() * sizeof(float)),
+                       (double)(g->packed.size() * sizeof(float) + g->packed16.size() * sizeof(uint16_t)),
                        cs.last_n ? (double)cs.last_seg[(size_t)(g->m.q.n_conv - 1) * (cs.last_n + 1) + cs.last_n] : 0.0};
   for (int i = 0; i < n; ++i) out[i] = v[i];
   return VX_OK;

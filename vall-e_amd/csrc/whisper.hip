@@ -76,17 +76,18 @@ void make_plan(vx_wsp* g) {
   size_t at = 0;
   auto take = [&](size_t n) { const size_t o = at; at += (n + 3) / 4 * 4; return o; };
   const bool keep = (c.flags & VX_WSP_KEEP_TAPS) != 0;
+  const size_t per = g->bf16 ? 2 : 1;  // the bf16 encoder mode's rows: two elements a float
   p.mel = take(B * F * (size_t)c.n_mels);
   p.c1 = take(B * F * d);
   p.feat = take(B * P * d);
   p.hid_stride = (B * P * d + 3) / 4 * 4;
   p.hid = take(p.hid_stride * (keep ? (size_t)c.enc_layers + 1 : 2));
   p.mid = take(B * P * d);
-  p.nrm = take(B * P * d);
-  p.qkv = take(B * P * 3 * d);
-  p.att = take(B * P * d);
+  p.nrm = take(B * P * d / per);
+  p.qkv = take(B * P * 3 * d / per);
+  p.att = take(B * P * d / per);
   p.tmp = take(B * P * d);
-  p.ff = take(B * P * (size_t)c.enc_ffn);
+  p.ff = take(B * P * (size_t)c.enc_ffn / per);
   p.enc = take(B * P * d);
   p.ckv_stride = (B * P * 2 * d + 3) / 4 * 4;
   p.ckv = take(p.ckv_stride * (size_t)c.dec_layers);
@@ -173,10 +174,16 @@ int run_front_and_encoder(const CallCtx& x, const float* const* wav, const int* 
   const long M = (long)n * P;
   EncRun e = enc_run(ws, p, (c.flags & VX_WSP_KEEP_TAPS) != 0);
   e.M = M; e.d = d; e.H = c.enc_heads; e.hd = 64; e.ffn = c.enc_ffn; e.Tmax = P; e.table = 1; e.hseg = hseg1;
-  wsp_add_layernorm<<<(unsigned)((M + 3) / 4), 256, 0, x.s>>>(ws + p.feat, x.W + g->enc_pos, P, x.W + g->enc[0].ln1.w, x.W + g->enc[0].ln1.b,
-                                                               e.hidden(0), e.nrm, M, d, x.eps);
-  HIPC(hipGetLastError());
-  VXC(run_prenorm_layers(x, e, g->enc, g->enc_ln, e.hidden(c.enc_layers), ws + p.enc));
+  if (g->bf16) {
+    e.W16 = reinterpret_cast<const ebf_t*>(g->dev->w16.get());
+    VXC(run_add_ln16(x, g->enc[0].ln1, ws + p.feat, x.W + g->enc_pos, P, e.hidden(0), e.nrm16, M, d));
+    VXC(run_prenorm_layers_bf16(x, e, g->enc, g->enc_ln, e.hidden(c.enc_layers), ws + p.enc));
+  } else {
+    wsp_add_layernorm<<<(unsigned)((M + 3) / 4), 256, 0, x.s>>>(ws + p.feat, x.W + g->enc_pos, P, x.W + g->enc[0].ln1.w, x.W + g->enc[0].ln1.b,
+                                                                 e.hidden(0), e.nrm, M, d, x.eps);
+    HIPC(hipGetLastError());
+    VXC(run_prenorm_layers(x, e, g->enc, g->enc_ln, e.hidden(c.enc_layers), ws + p.enc));
+  }
   // every decoder layer's cross-attention keys and values, for the whole call
   for (int l = 0; l < c.dec_layers; ++l) VXC(run_lin(x, g->dec[l].ckv, ws + p.enc, d, ws + p.ckv + p.ckv_stride * (size_t)l, M, SPK_ACT_NONE));
   return VX_OK;
@@ -238,7 +245,7 @@ extern "C" int vx_wsp_create(const vx_wsp_config* cfg, vx_wsp** out) {
     return fail(VX_ERR_ARG, "vx_wsp_create: max_source_positions %d, max_target_positions %d", c.max_source_positions, c.max_target_positions);
   if (c.eos_token_id < 0 || c.eos_token_id >= c.vocab) return fail(VX_ERR_ARG, "vx_wsp_create: eos_token_id %d outside [0, %d)", c.eos_token_id, c.vocab);
   if (c.max_batch < 1) return fail(VX_ERR_ARG, "vx_wsp_create: max_batch = %d", c.max_batch);
-  if (c.flags & ~VX_WSP_KEEP_TAPS) return fail(VX_ERR_ARG, "vx_wsp_create: flags = %d", c.flags);
+  if (c.flags & ~(VX_WSP_KEEP_TAPS | VX_WSP_ENC_BF16)) return fail(VX_ERR_ARG, "vx_wsp_create: flags = %d", c.flags);
   if (c.activation != 0) return fail(VX_ERR_UNSUPPORTED, "vx_wsp_create: activation_function = %d (gelu is served)", c.activation);
   if (c.d_model % c.enc_heads != 0 || c.d_model / c.enc_heads != 64)
     return fail(VX_ERR_UNSUPPORTED, "vx_wsp_create: encoder head_dim = %d / %d (64 is served)", c.d_model, c.enc_heads);
@@ -251,9 +258,11 @@ extern "C" int vx_wsp_create(const vx_wsp_config* cfg, vx_wsp** out) {
     return fail(VX_ERR_UNSUPPORTED, "vx_wsp_create: max_source_positions %d, max_target_positions %d (up to %d keys are served)",
                 c.max_source_positions, c.max_target_positions, WSP_MAX_KEYS);
   if (c.max_batch > SPK_MAX_SEG) return fail(VX_ERR_UNSUPPORTED, "vx_wsp_create: max_batch = %d > %d", c.max_batch, SPK_MAX_SEG);
+  if (c.flags & VX_WSP_ENC_BF16) VXC(enc_bf16_check("vx_wsp_create", c.d_model, c.enc_heads, c.enc_ffn, "encoder_attention_heads", "encoder_ffn_dim"));
 
   std::unique_ptr<vx_wsp> g(new vx_wsp());
   g->cfg = c;
+  g->bf16 = (c.flags & VX_WSP_ENC_BF16) != 0;
   g->P = c.max_source_positions;
   g->F = 2 * g->P;
   g->Tt = c.max_target_positions;
@@ -546,7 +555,8 @@ extern "C" int vx_wsp_read(vx_wsp* g, const char* name, int32_t utt, float* dst,
 
 extern "C" int vx_wsp_get_timings(vx_wsp* g, double* out, int32_t n) {
   if (!g || !out || n < 0 || n > 7) return fail(VX_ERR_ARG, "vx_wsp_get_timings: null argument or n outside [0, 7]");
-  double v[7] = {g->call.last_ms, (double)(g->plan.total * sizeof(float)), (double)(g->packed.size() * sizeof(float)), g->last_steps, 0.0, 0.0, 0.0};
+  double v[7] = {g->call.last_ms, (double)(g->plan.total * sizeof(float)),
+                 (double)(g->packed.size() * sizeof(float) + g->packed16.size() * sizeof(uint16_t)), g->last_steps, 0.0, 0.0, 0.0};
   if (n > 4 && g->device >= 0 && g->call.last_n > 0) {  // the device times of the last call: waits for it
     DevGuard guard(g->device);
     HIPC(guard.err);
@@ -665,5 +675,42 @@ extern "C" int vx_op_wsp_embed(const float* tok_emb, const float* pos_emb, const
   wsp_embed<<<n, 256, 0, s>>>(tok_emb, pos_emb, cur, pos, x, d);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+// ---- the bf16 encoder mode's kernels on caller data (tests): w2v_host.hpp's launchers, no handle -----------------------------------
+extern "C" int vx_op_enc16_gemm(int32_t epi, const void* A_bf16, const void* W_bf16, const float* bias, const float* res, void* out, int64_t M,
+                                int32_t N, int32_t K, void* stream) {
+  if (M < 1) return fail(VX_ERR_ARG, "vx_op_enc16_gemm: M = %lld", (long long)M);
+  hipStream_t s = (hipStream_t)stream;
+  VXC(launch_ebf_gemm(epi, (const ebf_t*)A_bf16, (const ebf_t*)W_bf16, bias, res, out, (long)M, N, K, s));
+  HIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+extern "C" int vx_op_enc16_add_ln(const float* a, const float* b, int32_t bmod, const float* w, const float* beta, float* sum, void* y_bf16,
+                                  int64_t M, int32_t d, float eps, void* stream) {
+  if (!a || !w || !beta || !y_bf16) return fail(VX_ERR_ARG, "vx_op_enc16_add_ln: null argument");
+  if (M < 1 || d < 1 || bmod < 0 || (bmod > 0 && !b)) return fail(VX_ERR_ARG, "vx_op_enc16_add_ln: M %lld, d %d, bmod %d", (long long)M, d, bmod);
+  hipStream_t s = (hipStream_t)stream;
+  VXC(launch_ebf_add_ln(a, b, bmod, w, beta, sum, (ebf_t*)y_bf16, (long)M, d, eps, s));
+  HIPC(hipStreamSynchronize(s));
+  return VX_OK;
+}
+
+extern "C" int vx_op_enc16_attn(const void* qkv_bf16, void* out_bf16, int32_t n, const int32_t* seg_len, int32_t heads, void* stream) {
+  if (!qkv_bf16 || !out_bf16 || !seg_len) return fail(VX_ERR_ARG, "vx_op_enc16_attn: null argument");
+  if (n < 1 || n > SPK_MAX_SEG || heads < 1) return fail(VX_ERR_ARG, "vx_op_enc16_attn: n %d segments (up to %d), %d heads", n, SPK_MAX_SEG, heads);
+  std::vector<int> seg((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (seg_len[i] < 0 || (long)seg[i] + seg_len[i] > 2147483647L) return fail(VX_ERR_ARG, "vx_op_enc16_attn: segment %d: %d rows", i, seg_len[i]);
+    seg[i + 1] = seg[i] + seg_len[i];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf<int> dseg;
+  VXC(dseg.alloc((size_t)n + 1));
+  HIPC(hipMemcpyAsync(dseg.get(), seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  VXC(launch_ebf_attn((const ebf_t*)qkv_bf16, (ebf_t*)out_bf16, dseg.get(), seg.data(), n, heads, s));
+  HIPC(hipStreamSynchronize(s));  // the tables go out of scope
   return VX_OK;
 }

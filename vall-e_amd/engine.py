@@ -94,6 +94,7 @@ class VxAsrConfig(C.Structure):
 
 
 VX_ASR_KEEP_TAPS = 1   # vx_asr_config.flags
+VX_ASR_ENC_BF16 = 2    # vx_asr_config.flags: the bf16 encoder mode
 VX_ASR_NORMALIZE = 1   # vx_asr_recognize flags
 
 
@@ -104,6 +105,9 @@ class VxWspConfig(C.Structure):
 
 
 VX_WSP_KEEP_TAPS = 1   # vx_wsp_config.flags
+VX_WSP_ENC_BF16 = 2    # vx_wsp_config.flags: the bf16 encoder mode
+ENC_PRECISIONS = ("fp32", "bf16")  # `precision=` of SpeechRecognizer and WhisperRecognizer
+EBF_EPI_BF16, EBF_EPI_GELU_BF16, EBF_EPI_RESID_F32 = 0, 1, 2  # vx_op_enc16_gemm's epilogues
 
 
 class VxDtwConfig(C.Structure):
@@ -357,6 +361,10 @@ _SIGS = {
     "vx_op_wsp_head": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 11
                        + [C.c_int32] * 3 + [C.c_void_p]),
     "vx_op_wsp_embed": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]),
+    # the bf16 encoder mode's kernels on caller data (whisper.op_enc16_*)
+    "vx_op_enc16_gemm": (C.c_int, [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "vx_op_enc16_add_ln": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_float, C.c_void_p]),
+    "vx_op_enc16_attn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
 }
 
 # measurement probes (csrc/probes.h): exported by the probe builds only (`csrc/build.py --probes|--stamps`), never by libvallex.so

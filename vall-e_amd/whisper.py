@@ -11,7 +11,7 @@ not needed at run time.
 
 The definition is stated in include/vallex.h and restated in fp64 in tests/whisper_ref.py, which tests/test_whisper_cpu.py pins
 against `transformers`.  One chunk (30 s at the released shapes) per utterance; beam search, temperature fallback, timestamps,
-language detection, long-form transcription and bf16 are not built.  Nothing has been recognised on trained weights: no checkpoint
+language detection, long-form transcription and a bf16 token loop are not built (`precision="bf16"` is the encoder's).  Nothing has been recognised on trained weights: no checkpoint
 is available where this is built, and on synthetic weights the transcript means nothing.  Parity with `openai-whisper` and with the
 tokenizer's encode direction is not pinned: text comes from `vocab.json` by the byte-level decode rule only."""
 from __future__ import annotations
@@ -216,15 +216,22 @@ class TokenScores(NamedTuple):
 
 
 class WhisperRecognizer(SpeechHandle):
-    """`WhisperRecognizer(config, vocab=None, generation_config=None, max_batch=8, state_dict=None, keep_taps=False)`: `config` and
+    """`WhisperRecognizer(config, vocab=None, generation_config=None, max_batch=8, state_dict=None, keep_taps=False,
+    precision="fp32")`: `config` and
     `generation_config` are dicts, paths of the checkpoint's `config.json` / `generation_config.json`, or objects with those
     attributes; `vocab` is the checkpoint's `vocab.json` mapping token -> id (without it `.text` is "").  A call serves up to
     `max_batch` (<= 64) utterances of up to one chunk (320 x max_source_positions samples at 16 kHz) each.  A head dimension other
-    than 64 and an activation other than GELU raise NotImplementedError naming the field."""
+    than 64 and an activation other than GELU raise NotImplementedError naming the field.  `precision="bf16"` runs the encoder layers
+    on the bf16 matrix cores (include/vallex.h: the bf16 encoder mode); the front end, the cross-attention projections and the token
+    loop stay fp32.  Any other precision raises ValueError."""
     _PREFIX, _NAME = "vx_wsp", "WhisperRecognizer"
 
     def __init__(self, config, vocab: Optional[Dict[str, int]] = None, generation_config=None, max_batch: int = 8,
-                 state_dict: Optional[dict] = None, keep_taps: bool = False, mel_basis: Optional[torch.Tensor] = None):
+                 state_dict: Optional[dict] = None, keep_taps: bool = False, mel_basis: Optional[torch.Tensor] = None,
+                 precision: str = "fp32"):
+        if precision not in _e.ENC_PRECISIONS:
+            raise ValueError(f"precision = {precision!r}: one of {_e.ENC_PRECISIONS}")
+        self.precision = precision
         c = self.config = WhisperConfig.from_any(config)
         gen = self.generation = WhisperGeneration.from_any(generation_config)
         if c.activation_function != "gelu":
@@ -260,7 +267,7 @@ class WhisperRecognizer(SpeechHandle):
         s.tie_proj = int(bool(c.tie_word_embeddings))
         s.eos_token_id = self.eos_token_id
         s.max_batch = self.max_batch
-        s.flags = _e.VX_WSP_KEEP_TAPS if self.keep_taps else 0
+        s.flags = (_e.VX_WSP_KEEP_TAPS if self.keep_taps else 0) | (_e.VX_WSP_ENC_BF16 if self.precision == "bf16" else 0)
         return s
 
     def _configure(self, lib):
@@ -454,3 +461,48 @@ def op_wsp_embed(tok_emb: torch.Tensor, pos_emb: torch.Tensor, cur: torch.Tensor
     _e._check(_e.load_library().vx_op_wsp_embed(_f32(tok_emb), _f32(pos_emb, pos_emb.shape[0], d), _i32(cur, n), _i32(pos, n), _f32(x), n, d,
                                                 tok_emb.shape[0], pos_emb.shape[0], _e.current_stream_ptr(tok_emb.device)))
     return x
+
+
+# ---- the bf16 encoder mode's kernels on caller data (tests) ------------------------------------------------------------------------
+def _bf16(t, *shape):
+    assert t.dtype == torch.bfloat16 and t.is_cuda and t.is_contiguous() and (not shape or tuple(t.shape) == shape), (t.dtype, tuple(t.shape), shape)
+    return t.data_ptr()
+
+
+def op_enc16_gemm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, epi: int, res: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ebf_gemm through the recognisers' launcher (vx_op_enc16_gemm): A (M, K) and W (N, K) bf16 and bias (N) fp32 on the device.
+    epi 0: bf16 (M, N) = A W^T + bias; 1: bf16 = gelu(A W^T + bias); 2: fp32 = (A W^T + bias) + res, res (M, N) fp32 (it may be `out`)."""
+    (M, K), N = A.shape, W.shape[0]
+    dt = torch.float32 if epi == _e.EBF_EPI_RESID_F32 else torch.bfloat16
+    if out is None:
+        out = torch.empty((M, N), dtype=dt, device=A.device)
+    assert out.dtype == dt and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (M, N)
+    _e._check(_e.load_library().vx_op_enc16_gemm(int(epi), _bf16(A), _bf16(W, N, K), _f32(bias, N), None if res is None else _f32(res, M, N),
+                                                 out.data_ptr(), M, N, K, _e.current_stream_ptr(A.device)))
+    return out
+
+
+def op_enc16_add_ln(a: torch.Tensor, b: Optional[torch.Tensor], w: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, bmod: int = 0,
+                    want_sum: bool = True):
+    """ebf_add_layernorm (vx_op_enc16_add_ln): a (M, d) fp32, b (M, d) or (bmod, d) fp32 or None -> (sum (M, d) fp32 or None, rows (M, d)
+    bf16)."""
+    M, d = a.shape
+    y = torch.empty((M, d), dtype=torch.bfloat16, device=a.device)
+    s = torch.empty((M, d), dtype=torch.float32, device=a.device) if want_sum else None
+    _e._check(_e.load_library().vx_op_enc16_add_ln(_f32(a), None if b is None else _f32(b, bmod if bmod else M, d), int(bmod), _f32(w, d), _f32(beta, d),
+                                                   None if s is None else s.data_ptr(), y.data_ptr(), M, d, float(eps),
+                                                   _e.current_stream_ptr(a.device)))
+    return s, y
+
+
+def op_enc16_attn(qkv: torch.Tensor, seg_len: Sequence[int], heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ebf_attention (vx_op_enc16_attn): qkv (rows, 3 x 64 heads) bf16 on the device, the segments of `seg_len` rows packed tightly ->
+    (rows, 64 heads) bf16."""
+    rows, d = qkv.shape[0], 64 * int(heads)
+    assert sum(seg_len) == rows
+    if out is None:
+        out = torch.empty((rows, d), dtype=torch.bfloat16, device=qkv.device)
+    _e._check(_e.load_library().vx_op_enc16_attn(_bf16(qkv, rows, 3 * d), _bf16(out, rows, d), len(seg_len), (C.c_int32 * len(seg_len))(*[int(t) for t in seg_len]),
+                                                 int(heads), _e.current_stream_ptr(qkv.device)))
+    return out
