@@ -1,17 +1,18 @@
-"""What `SpeakerEncoder`, `SpeechRecognizer` and `WhisperRecognizer` share: the life of a `vx_spk` / `vx_asr` / `vx_wsp` handle, the
-check of a state dict, the preparation of the waveforms, and for the two Wav2Vec2 networks the backbone's key table, config fields
-and synthetic weights.  Private: the public names stay in spk.py, asr.py and whisper.py."""
+"""What `SpeakerEncoder`, `SpeechRecognizer` and `WhisperRecognizer` share on top of `_handle.WeightedHandle`: the preparation of
+the waveforms at 16 kHz, the head of a call on them, and for the two Wav2Vec2 networks the backbone's key table, config fields and
+synthetic weights.  Private: the public names stay in spk.py, asr.py and whisper.py."""
 from __future__ import annotations
 
 import ctypes as C
 import dataclasses
 import json
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List
 
 import torch
 
 from . import engine as _e
+from ._handle import WeightedHandle, i32_array, prepare_waveforms, ptr_array
 
 SAMPLE_RATE = 16000
 
@@ -30,68 +31,9 @@ def config_from_any(cls, cfg):
     return cls(**{k: getattr(cfg, k) for k in names if getattr(cfg, k, None) is not None})
 
 
-class SpeechHandle:
-    """The handle behind the C entry points `<_PREFIX>_*`; `_NAME` is the class name the messages carry.  A subclass gives
-    `_config_struct()` and may give `_configure(lib)`, which runs between create and finalize, and `_tensors()`."""
-    _PREFIX = ""
-    _NAME = ""
-
-    def _init_handle(self):
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None
-        self._weights: Optional[Dict[str, torch.Tensor]] = None
-        self._resamplers: Dict[int, object] = {}
-        self._create()  # a geometry the kernels do not serve is refused here
-
-    def _fn(self, name: str):
-        return getattr(_e.load_library(), f"{self._PREFIX}_{name}")
-
-    def _configure(self, lib):
-        pass
-
-    def _tensors(self):
-        return self._weights.items()
-
-    def _create(self):
-        lib = _e.load_library()
-        h = C.c_void_p()
-        _e._check(self._fn("create")(C.byref(self._config_struct()), C.byref(h)))
-        self._h, self._bound = h, None
-        try:
-            self._configure(lib)
-            if self._weights is not None:
-                for k, t in self._tensors():
-                    shape = (C.c_int64 * t.dim())(*t.shape)
-                    _e._check(self._fn("set_weight")(self._h, k.encode(), t.data_ptr(), shape, t.dim()))
-                _e._check(self._fn("finalize")(self._h))
-        except Exception:
-            self.close()
-            raise
-
-    def _handle(self):
-        if self._h is None:
-            self._create()
-        return self._h
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self._fn("destroy")(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class SpeechHandle(WeightedHandle):
+    """The three speech networks at 16 kHz.  A subclass gives `_PREFIX`, `_NAME` and `_config_struct()` and may give
+    `_configure(lib)`, which runs between create and the hand-over of the weights, and `_tensors()`."""
 
     def workspace_bytes(self) -> int:
         out = (C.c_double * 4)()
@@ -104,21 +46,6 @@ class SpeechHandle:
         _e._check(self._fn("read")(self._handle(), name.encode(), int(utt), out.data_ptr(), out.numel()))
         return out
 
-    def _check_state_dict(self, want: Dict[str, tuple], w: dict):
-        """`w` holds exactly the keys of `want` in their shapes, else KeyError / ValueError by name; then the weights are kept as
-        fp32 CPU tensors and the handle is made again with them.  Returns self."""
-        missing = sorted(k for k in want if k not in w)
-        unexpected = sorted(k for k in w if k not in want)
-        if missing or unexpected:
-            raise KeyError(f"{self._NAME}.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        for k, shape in want.items():
-            if tuple(w[k].shape) != tuple(shape):
-                raise ValueError(f"{self._NAME}.load_state_dict: {k} is {tuple(w[k].shape)}, expected {tuple(shape)}")
-        self._weights = {k: w[k].detach().to("cpu", torch.float32).contiguous() for k in want}
-        self.close()
-        self._create()
-        return self
-
     def _prepare(self, wavs, sr: int) -> List[torch.Tensor]:
         """One waveform or a list -> flat float32 tensors on the device at 16 kHz (through the GPU `Resampler` from another rate)."""
         if isinstance(wavs, torch.Tensor):
@@ -128,33 +55,13 @@ class SpeechHandle:
             assert isinstance(w, torch.Tensor) and w.dtype == torch.float32, "waveforms are float32 tensors"
             assert w.numel() == w.shape[-1], "one mono utterance per entry: (L,), (1, L) or (1, 1, L)"
             ws.append(w.detach().reshape(-1))
-        if self.device.type != "cuda":
-            raise RuntimeError(f"valle_amd.{self._NAME} runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
-        if self._weights is None:
-            raise RuntimeError(f"{self._NAME} has no weights: call load_state_dict first")
-        ws = [w.to(self.device).contiguous() for w in ws]
-        if int(sr) != SAMPLE_RATE:
-            from .codec import Resampler
-
-            if sr not in self._resamplers:
-                self._resamplers[sr] = Resampler(int(sr), SAMPLE_RATE, max_batch=self.max_batch)
-            rs = self._resamplers[sr].to(self.device)
-            out = []
-            for i in range(0, len(ws), self.max_batch):
-                out += [o.reshape(-1) for o in rs.resample_batch(ws[i:i + self.max_batch])]
-            ws = out
-        return ws
+        self._need_device()
+        self._need_weights()
+        return prepare_waveforms(self, ws, sr, SAMPLE_RATE, strict=False)
 
     def _call(self, name: str, wav_ptrs, lengths, *rest):
         """`<_PREFIX>_<name>(handle, n, wav pointers, lengths, *rest, stream)`: the head every call on waveforms has."""
-        n = len(wav_ptrs)
-        wp = (C.c_void_p * n)(*wav_ptrs)
-        L = (C.c_int32 * n)(*lengths)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(self._fn(name)(h, n, wp, L, *rest, stream))
+        self._invoke(name, len(wav_ptrs), ptr_array(wav_ptrs), i32_array(lengths), *rest)
 
 
 class W2vHandle(SpeechHandle):

@@ -254,10 +254,8 @@ class SpeechRecognizer(W2vHandle):
         work)."""
         n = len(targets)
         flat = [int(t) for y in targets for t in y]
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        _e._check(_e.load_library().vx_falign_asr(self._handle(), n, (C.c_int32 * max(len(flat), 1))(*flat),
-                                                  (C.c_int32 * max(n, 1))(*[len(y) for y in targets]), nll_ptr, plp_ptr, ftok_ptr, start_ptr,
-                                                  end_ptr, score_ptr, feas_ptr, stream))
+        self._invoke(_e.load_library().vx_falign_asr, n, (C.c_int32 * max(len(flat), 1))(*flat),
+                     (C.c_int32 * max(n, 1))(*[len(y) for y in targets]), nll_ptr, plp_ptr, ftok_ptr, start_ptr, end_ptr, score_ptr, feas_ptr)
 
     @torch.no_grad()
     def _align_ids(self, wavs, targets: Sequence[Sequence[int]], sr, normalize, path: bool):

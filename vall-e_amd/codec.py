@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import engine as _e
+from ._handle import Handle, i32_array, normalize_device, owner_resampler, prepare_waveforms, ptr_array, shared, to_native_rate
 
 _WN = "parametrizations.weight.original"
 SAMPLE_RATE = 24000  # the model's rate
@@ -148,43 +149,18 @@ def resample_length(orig_hz: int, new_hz: int, n_samples: int) -> int:
     return r
 
 
-class Resampler:
+class Resampler(Handle):
     """`encodec.utils.convert_audio`'s mono path on the GPU: the channel mean, then `torchaudio.transforms.Resample(orig_hz,
     new_hz)` with its defaults (Hann-windowed sinc, width 6, roll-off 0.99; include/vallex.h states the rule).  One rate pair per
     object, up to `max_batch` utterances of any lengths and channel counts per `resample_batch` call."""
+    _PREFIX, _NAME = "vx_resampler", "Resampler"  # the call itself is `vx_resample`
 
     def __init__(self, orig_hz: int, new_hz: int, max_batch: int = 1):
         self.orig_hz, self.new_hz, self.max_batch = int(orig_hz), int(new_hz), int(max_batch)
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None  # the device of the handle's first call: the C side keeps its tables there
-        self._handle()      # a rate pair the kernel does not serve is refused here
+        self._init_handle()  # a rate pair the kernel does not serve is refused here
 
-    def _handle(self):
-        if self._h is None:
-            h = C.c_void_p()
-            _e._check(_e.load_library().vx_resampler_create(self.orig_hz, self.new_hz, self.max_batch, C.byref(h)))
-            self._h, self._bound = h, None
-        return self._h
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_resampler_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create_call(self, lib, out_handle) -> int:
+        return lib.vx_resampler_create(self.orig_hz, self.new_hz, self.max_batch, out_handle)
 
     def output_length(self, n_samples: int) -> int:
         return resample_length(self.orig_hz, self.new_hz, n_samples)
@@ -200,8 +176,7 @@ class Resampler:
                 assert w.shape[0] == 1, "one utterance per entry"
                 w = w[0]
             ws.append(w.detach().reshape(-1, w.shape[-1]))
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.Resampler runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        self._need_device()
         ws = [w.to(self.device).contiguous() for w in ws]
         outs = [torch.empty((1, 1, self.output_length(w.shape[1])), dtype=torch.float32, device=self.device) for w in ws]
         with torch.cuda.device(self.device):
@@ -211,22 +186,14 @@ class Resampler:
 
     def _resample_raw(self, in_ptrs, channels, lengths, out_ptrs):
         """vx_resample on raw pointers (the argument checks run before any device work)."""
-        n = len(in_ptrs)
-        ip = (C.c_void_p * n)(*in_ptrs)
-        ch = (C.c_int32 * n)(*channels)
-        L = (C.c_int32 * n)(*lengths)
-        op = (C.c_void_p * n)(*out_ptrs)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_resample(h, n, ip, ch, L, op, stream))
+        self._invoke(_e.load_library().vx_resample, len(in_ptrs), ptr_array(in_ptrs), i32_array(channels), i32_array(lengths),
+                     ptr_array(out_ptrs))
 
     def __call__(self, wav: torch.Tensor) -> torch.Tensor:
         return self.resample_batch([wav])[0]
 
 
-_RESAMPLERS: Dict[Tuple[int, int, torch.device], Resampler] = {}
+_SHARED: Dict[tuple, Resampler] = {}
 
 
 def convert_audio(wav: torch.Tensor, sr: int, target_sr: int = 24000, target_channels: int = 1) -> torch.Tensor:
@@ -237,10 +204,7 @@ def convert_audio(wav: torch.Tensor, sr: int, target_sr: int = 24000, target_cha
     assert wav.dim() == 2, "wav is (C, L)"
     if wav.device.type != "cuda":
         raise RuntimeError("valle_amd.convert_audio runs only on an MI355X: move the waveform to 'cuda' first (no CPU fallback)")
-    key = (int(sr), int(target_sr), wav.device)
-    if key not in _RESAMPLERS:
-        _RESAMPLERS[key] = Resampler(sr, target_sr).to(wav.device)
-    return _RESAMPLERS[key](wav)[0]
+    return shared(_SHARED, wav.device, (int(sr), int(target_sr)), lambda: Resampler(sr, target_sr))(wav)[0]
 
 
 # ---- WAV files (standard library only) ----------------------------------------------------------------------------------
@@ -320,9 +284,7 @@ class EncodecDecoder:
         return OrderedDict((k, self._sd[k]) for k in expected_keys(self.cfg, self.encoder) if k in self._sd)
 
     def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = normalize_device(device)
         self._drop()
         for r in self._resamplers.values():
             r.close()
@@ -342,10 +304,7 @@ class EncodecDecoder:
 
     def resampler(self, orig_hz: int, new_hz: int) -> Resampler:
         """The object's `Resampler` for a rate pair (kept per pair, `max_batch` utterances per call)."""
-        key = (int(orig_hz), int(new_hz))
-        if key not in self._resamplers:
-            self._resamplers[key] = Resampler(key[0], key[1], self.max_batch).to(self.device)
-        return self._resamplers[key]
+        return owner_resampler(self, orig_hz, new_hz)
 
     def cuda(self, index: int = 0):
         return self.to(torch.device("cuda", index))
@@ -425,9 +384,7 @@ class EncodecDecoder:
         n = len(cs)
         lib = _e.load_library()
         h = self.handle(finalize)
-        cp = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
-        T = (C.c_int32 * n)(*[c.shape[1] for c in cs])
-        op = (C.c_void_p * n)(*out_ptrs)
+        cp, T, op = ptr_array([c.data_ptr() for c in cs]), i32_array([c.shape[1] for c in cs]), ptr_array(out_ptrs)
         stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
         _e._check(lib.vx_codec_decode(h, n, cp, T, cs[0].shape[0], op, stream))
 
@@ -448,12 +405,7 @@ class EncodecDecoder:
         if self.device.type != "cuda":
             raise RuntimeError("valle_amd.EncodecDecoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
         n_q = self.cfg.n_codebooks if n_q is None else int(n_q)
-        if sr is not None and (int(sr) != SAMPLE_RATE or any(w.numel() != w.shape[-1] for w in wavs)):
-            wavs = self.resampler(sr, SAMPLE_RATE).resample_batch(wavs)  # at 24 kHz: the channel mean alone
-        ws = []
-        for w in wavs:
-            assert w.dtype == torch.float32 and w.numel() == w.shape[-1], "one mono float32 waveform per entry"
-            ws.append(w.detach().reshape(-1).to(self.device).contiguous())
+        ws = prepare_waveforms(self, wavs, sr, SAMPLE_RATE, strict=False)
         outs = [torch.empty((1, n_q, -(-w.numel() // self.cfg.hop)), dtype=torch.int64, device=self.device) for w in ws]
         self._encode_raw([w.data_ptr() for w in ws], [w.numel() for w in ws], n_q, [o.data_ptr() for o in outs])
         return outs
@@ -463,9 +415,7 @@ class EncodecDecoder:
         n = len(wav_ptrs)
         lib = _e.load_library()
         h = self.handle(finalize)
-        wp = (C.c_void_p * n)(*wav_ptrs)
-        L = (C.c_int32 * n)(*lengths)
-        op = (C.c_void_p * n)(*out_ptrs)
+        wp, L, op = ptr_array(wav_ptrs), i32_array(lengths), ptr_array(out_ptrs)
         stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
         _e._check(lib.vx_codec_encode(h, n, wp, L, n_q, op, stream))
 
@@ -487,8 +437,7 @@ class EncodecDecoder:
         mixed-down and resampled input.  Needs `encoder=True`."""
         from .fbank import mel_distance
 
-        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
-            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        wav = to_native_rate(self, [wav], sr, SAMPLE_RATE)[0]
         rec = self.decode(self.encode(wav, n_q))
         a, b = self.fbank().extract_batch([wav, rec])
         return mel_distance(a, b)
@@ -502,8 +451,7 @@ class EncodecDecoder:
         Needs `encoder=True`."""
         from .stft import shared_mstft
 
-        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
-            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        wav = to_native_rate(self, [wav], sr, SAMPLE_RATE)[0]
         rec = self.decode(self.encode(wav, n_q))
         return shared_mstft(rec.device).compare(rec.reshape(-1), wav.reshape(-1))
 
@@ -514,8 +462,7 @@ class EncodecDecoder:
         decode(encode(waveform)) against the waveform: whether the codec keeps the voice, which the mel and M-STFT round trips do
         not say.  `wav` and `sr` as in `encode`; both sides go to the encoder at 24 kHz and are resampled to 16 kHz there.  On
         synthetic weights (the codec's or the encoder's) the number means nothing.  Needs `encoder=True`."""
-        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
-            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        wav = to_native_rate(self, [wav], sr, SAMPLE_RATE)[0]
         rec = self.decode(self.encode(wav, n_q))
         return encoder.similarity(wav.reshape(-1), rec.reshape(-1), sr=SAMPLE_RATE, normalize=normalize)[0]
 
@@ -527,8 +474,7 @@ class EncodecDecoder:
         codec's or the recogniser's) the number means nothing.  Needs `encoder=True`."""
         from .asr import recognition_error
 
-        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
-            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        wav = to_native_rate(self, [wav], sr, SAMPLE_RATE)[0]
         rec = self.decode(self.encode(wav, n_q))
         return recognition_error(text, rec.reshape(-1), recognizer, sr=SAMPLE_RATE, normalize=normalize, unit=unit)
 
@@ -540,8 +486,7 @@ class EncodecDecoder:
         `encoder=True`."""
         from .asr import text_likelihood
 
-        if sr is not None and (int(sr) != SAMPLE_RATE or wav.numel() != wav.shape[-1]):
-            wav = self.resampler(sr, SAMPLE_RATE).resample_batch([wav])[0]
+        wav = to_native_rate(self, [wav], sr, SAMPLE_RATE)[0]
         rec = self.decode(self.encode(wav, n_q))
         return text_likelihood(text, rec.reshape(-1), recognizer, sr=SAMPLE_RATE, normalize=normalize)[0]
 

@@ -25,6 +25,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import engine as _e
+from ._handle import Handle, i32_array, ptr_array, shared
 
 MAX_DIM = 128
 MAX_FRAMES = 4096   # frames per sequence (csrc/dtw_kernels.hpp DTW_MAX_FRAMES: three fp64 diagonals of a pair stay in LDS)
@@ -42,15 +43,13 @@ class DTWResult:
     path: Optional[torch.Tensor]   # (length, 2) int32 on the device, (i, j) ascending; None unless asked for
 
 
-class DTW:
+class DTW(Handle):
     """`compare_batch` serves any number of pairs, `max_batch` per call; the handle's workspace follows the largest call."""
+    _PREFIX, _NAME = "vx_dtw", "DTW"
 
     def __init__(self, dim: int = 100, n_ceps: int = 13, max_frames: int = MAX_FRAMES, max_batch: int = MAX_BATCH):
         self.dim, self.n_ceps, self.max_frames, self.max_batch = int(dim), int(n_ceps), int(max_frames), int(max_batch)
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None  # the device of the handle's first call: the C side keeps its table and workspace there
-        self._handle()      # a geometry the kernels do not serve is refused here
+        self._init_handle()  # a geometry the kernels do not serve is refused here
 
     def _config_struct(self) -> "_e.VxDtwConfig":
         c = _e.VxDtwConfig()
@@ -58,37 +57,10 @@ class DTW:
         c.dim, c.n_ceps, c.max_frames, c.max_batch = self.dim, self.n_ceps, self.max_frames, self.max_batch
         return c
 
-    def _handle(self):
-        if self._h is None:
-            h = C.c_void_p()
-            _e._check(_e.load_library().vx_dtw_create(C.byref(self._config_struct()), C.byref(h)))
-            self._h, self._bound = h, None
-        return self._h
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_dtw_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     @torch.no_grad()
     def compare_batch(self, pairs: Sequence[Tuple[torch.Tensor, torch.Tensor]], return_path: bool = False) -> List[DTWResult]:
         """pairs[i] = (A_i (Ta_i, dim), B_i (Tb_i, dim)) float32 on the object's device -> one DTWResult per pair."""
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.DTW runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        self._need_device()
         pairs = [(a, b) for a, b in pairs]
         for i, (a, b) in enumerate(pairs):
             for t in (a, b):
@@ -127,15 +99,8 @@ class DTW:
 
     def _compare_raw(self, a_ptrs, Ta, b_ptrs, Tb, total_ptr, len_ptr, path_ptrs=None):
         """vx_dtw_compare on raw pointers (the argument checks run before any device work)."""
-        n = len(a_ptrs)
-        ap, bp = (C.c_void_p * n)(*a_ptrs), (C.c_void_p * n)(*b_ptrs)
-        ta, tb = (C.c_int32 * n)(*Ta), (C.c_int32 * n)(*Tb)
-        pp = (C.c_void_p * n)(*path_ptrs) if path_ptrs is not None else None
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_dtw_compare(h, n, ap, ta, bp, tb, total_ptr, len_ptr, pp, stream))
+        self._invoke("compare", len(a_ptrs), ptr_array(a_ptrs), i32_array(Ta), ptr_array(b_ptrs), i32_array(Tb), total_ptr, len_ptr,
+                     ptr_array(path_ptrs))
 
 
 _SHARED: Dict[Tuple[torch.device, int, int], DTW] = {}
@@ -143,18 +108,8 @@ _SHARED: Dict[Tuple[torch.device, int, int], DTW] = {}
 
 def shared_dtw(device, dim: int, n_ceps: int) -> DTW:
     """The module's own DTW object for a device and geometry (kept: its workspace is reused by later calls)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("valle_amd.dtw runs only on an MI355X: pass device tensors (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (device, int(dim), int(n_ceps))
-    if key not in _SHARED:
-        _SHARED[key] = DTW(dim, n_ceps).to(device)
-    return _SHARED[key]
+    return shared(_SHARED, device, (int(dim), int(n_ceps)), lambda: DTW(dim, n_ceps), "dtw")
 
-
-_FBANKS: Dict[torch.device, object] = {}
 
 Wave = Union[torch.Tensor, Sequence[torch.Tensor]]
 
@@ -164,7 +119,7 @@ def mel_cepstral_distortion(wav_a: Wave, wav_b: Wave, sr: Optional[int] = None, 
     """MCD-DTW between waveforms on the device: `BigVGANFbank.extract_batch` (with `sr` given: mix-down and resampling to 24 kHz
     first, as there), then `DTW(100, n_ceps).compare_batch`; the features never leave the device.  One pair of tensors gives one
     DTWResult, two lists of equal length a list.  A waveform too short for a frame (fewer than 128 samples at 24 kHz): ValueError."""
-    from .fbank import BigVGANFbank
+    from .fbank import shared_fbank
 
     single = isinstance(wav_a, torch.Tensor)
     wa, wb = ([wav_a], [wav_b]) if single else (list(wav_a), list(wav_b))
@@ -173,10 +128,7 @@ def mel_cepstral_distortion(wav_a: Wave, wav_b: Wave, sr: Optional[int] = None, 
     device = wa[0].device
     if device.type != "cuda" or any(w.device != device for w in wa + wb):
         raise RuntimeError("valle_amd.mel_cepstral_distortion runs only on an MI355X: pass device tensors of one device (no CPU fallback)")
-    if device not in _FBANKS:
-        _FBANKS[device] = BigVGANFbank().to(device)
-    fb = _FBANKS[device]
-    mels = fb.extract_batch([w for p in zip(wa, wb) for w in p], sr)
+    mels = shared_fbank(device).extract_batch([w for p in zip(wa, wb) for w in p], sr)
     if any(m.shape[0] == 0 for m in mels):
         raise ValueError("mel_cepstral_distortion: a waveform has no frame (fewer than 128 samples at 24 kHz)")
     res = shared_dtw(device, mels[0].shape[1], n_ceps).compare_batch(list(zip(mels[0::2], mels[1::2])))

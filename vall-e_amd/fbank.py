@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import engine as _e
+from ._handle import Handle, i32_array, owner_resampler, prepare_waveforms, ptr_array, shared
 
 SAMPLE_RATE = 24000
 N_FFT = 1024
@@ -109,9 +110,10 @@ def mel_distance(a: torch.Tensor, b: torch.Tensor, warp: bool = False) -> torch.
     return (a[:n] - b[:n]).abs().mean()
 
 
-class BigVGANFbank:
+class BigVGANFbank(Handle):
     """The reference's extractor on the GPU.  `extract` is the reference's call (numpy out); `extract_batch` serves up to
     `max_batch` utterances of any lengths per launch and returns device tensors."""
+    _PREFIX, _NAME = "vx_fbank", "BigVGANFbank"
 
     name = "fbank"
     config_type = BigVGANFbankConfig
@@ -129,11 +131,7 @@ class BigVGANFbank:
         if tuple(mel_basis.shape) != (n, N_BINS):
             raise ValueError(f"mel_basis is {tuple(mel_basis.shape)}, expected ({n}, {N_BINS})")
         self.mel_basis = mel_basis
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None  # the device of the handle's first call: the C side keeps its tables there
-        self._resamplers: Dict[int, Any] = {}
-        self._handle()      # a geometry the kernel does not serve is refused here
+        self._init_handle()
 
     def _config_struct(self) -> "_e.VxFbankConfig":
         c, g = _e.VxFbankConfig(), self.config
@@ -144,36 +142,8 @@ class BigVGANFbank:
         c.n_mels, c.fmin, c.fmax, c.clip, c.max_batch = int(g.num_mel_bins), g.low_freq, g.high_freq, self.clip_val, self.max_batch
         return c
 
-    def _handle(self):
-        if self._h is None:
-            lib = _e.load_library()
-            h = C.c_void_p()
-            _e._check(lib.vx_fbank_create(C.byref(self._config_struct()), C.byref(h)))
-            self._h, self._bound = h, None
-            _e._check(lib.vx_fbank_set_mel_basis(h, self.mel_basis.data_ptr()))
-        return self._h
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        for r in self._resamplers.values():
-            r.close()
-        self._resamplers = {}
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_fbank_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _configure(self, lib):
+        _e._check(lib.vx_fbank_set_mel_basis(self._h, self.mel_basis.data_ptr()))
 
     # ---- the reference's surface --------------------------------------------------------------------
     @property
@@ -201,20 +171,14 @@ class BigVGANFbank:
     # ---- ours ---------------------------------------------------------------------------------------
     def resampler(self, orig_hz: int):
         """The object's `Resampler` from a rate to 24 kHz (kept per rate, `max_batch` utterances per call)."""
-        from .codec import Resampler
-
-        key = int(orig_hz)
-        if key not in self._resamplers:
-            self._resamplers[key] = Resampler(key, SAMPLE_RATE, self.max_batch).to(self.device)
-        return self._resamplers[key]
+        return owner_resampler(self, orig_hz, SAMPLE_RATE)
 
     @torch.no_grad()
     def extract_batch(self, wavs: Sequence[torch.Tensor], sr: Optional[int] = None) -> List[torch.Tensor]:
         """wavs[i]: (L_i,), (1, L_i) or (1, 1, L_i) float32 mono at 24 kHz -> [(n_frames_i, num_mel_bins) float32 on the device],
         every utterance bitwise what it is alone.  With `sr` given the entries are (L_i,), (C_i, L_i) or (1, C_i, L_i) at that
         rate and go through `Resampler` (channel mean, windowed sinc) first; mono input at 24000 is taken as it is."""
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.BigVGANFbank runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        self._need_device()
         wavs = list(wavs)
         outs: List[torch.Tensor] = []
         for i in range(0, len(wavs), self.max_batch):
@@ -222,12 +186,7 @@ class BigVGANFbank:
         return outs
 
     def _extract_chunk(self, wavs, sr):
-        if sr is not None and (int(sr) != SAMPLE_RATE or any(w.numel() != w.shape[-1] for w in wavs)):
-            wavs = self.resampler(sr).resample_batch(wavs)  # at 24 kHz: the channel mean alone
-        ws = []
-        for w in wavs:
-            assert w.dtype == torch.float32 and w.numel() == w.shape[-1], "one mono float32 waveform per entry"
-            ws.append(w.detach().reshape(-1).to(self.device).contiguous())
+        ws = prepare_waveforms(self, wavs, sr, SAMPLE_RATE, strict=False)
         n_mels = int(self.config.num_mel_bins)
         outs = [torch.empty((num_frames(w.numel()), n_mels), dtype=torch.float32, device=self.device) for w in ws]
         live = [i for i, o in enumerate(outs) if o.shape[0] > 0]  # an empty result has no storage to point at, and nothing to write
@@ -238,15 +197,15 @@ class BigVGANFbank:
 
     def _extract_raw(self, wav_ptrs, lengths, out_ptrs):
         """vx_fbank_extract on raw pointers (the argument checks run before any device work)."""
-        n = len(wav_ptrs)
-        wp = (C.c_void_p * n)(*wav_ptrs)
-        L = (C.c_int32 * n)(*lengths)
-        op = (C.c_void_p * n)(*out_ptrs)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_fbank_extract(h, n, wp, L, op, stream))
+        self._invoke("extract", len(wav_ptrs), ptr_array(wav_ptrs), i32_array(lengths), ptr_array(out_ptrs))
+
+
+_SHARED: Dict[tuple, BigVGANFbank] = {}
+
+
+def shared_fbank(device) -> BigVGANFbank:
+    """The process-wide default extractor of a device (what the distances on waveforms in dtw, pitch and stft use)."""
+    return shared(_SHARED, device, (), BigVGANFbank, "fbank")
 
 
 def get_fbank_extractor(device: Optional[Union[str, torch.device]] = None) -> BigVGANFbank:

@@ -25,6 +25,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import engine as _e
+from ._handle import WeightedHandle, i32_array, ptr_array
 
 ACTIVATIONS = {"lrelu": _e.VX_GAN_LRELU, "snake": _e.VX_GAN_SNAKE, "snakebeta": _e.VX_GAN_SNAKEBETA}
 N_TAPS = 12
@@ -152,11 +153,12 @@ def expected_keys(config: GanConfig) -> Dict[str, tuple]:
 OPTIONAL_KEYS = ("conv_post.bias", "mean", "scale")
 
 
-class GanVocoder:
+class GanVocoder(WeightedHandle):
     """`GanVocoder(config, state_dict=None, max_batch=32, max_total_frames=65536)`: `config` is a preset name (`PRESETS`), a
     `GanConfig`, or a dict with its fields or those of the generator's own `config.json`, which therefore overrides a preset:
     `GanVocoder(json.load(open("config.json")))`.  The two BigVGAN presets are written from memory of the published
     configurations.  A call serves up to `max_batch` (<= 64) utterances of `max_total_frames` frames in all."""
+    _PREFIX, _NAME = "vx_gan", "GanVocoder"
 
     def __init__(self, config="bigvgan_24khz_100band", state_dict: Optional[dict] = None, max_batch: int = 32,
                  max_total_frames: int = 65536):
@@ -180,12 +182,8 @@ class GanVocoder:
             raise ValueError("dilations has one row per resblock kernel, all of one length")
         self.config = config
         self.max_batch, self.max_total_frames = int(max_batch), int(max_total_frames)
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None
-        self._weights: Optional[Dict[str, torch.Tensor]] = None
         self._taps: Optional[torch.Tensor] = None
-        self._create()  # a geometry the kernels do not serve is refused here
+        self._init_handle()  # a geometry the kernels do not serve is refused here
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -214,34 +212,15 @@ class GanVocoder:
         c.max_batch, c.max_total_frames = self.max_batch, self.max_total_frames
         return c
 
-    def _create(self):
-        lib = _e.load_library()
-        h = C.c_void_p()
-        _e._check(lib.vx_gan_create(C.byref(self._config_struct()), C.byref(h)))
-        self._h, self._bound = h, None
-        if self._weights is not None:
-            try:
-                self._upload()
-            except Exception:
-                self.close()
-                raise
-
-    def _upload(self):
-        lib = _e.load_library()
+    def _configure(self, lib):
         if self._taps is not None:
             _e._check(lib.vx_gan_set_filter(self._h, self._taps.data_ptr(), N_TAPS))
-        for k, t in self._weights.items():
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _e._check(lib.vx_gan_set_weight(self._h, k.encode(), t.data_ptr(), shape, t.dim()))
-        _e._check(lib.vx_gan_finalize(self._h))
 
     @property
     def filter(self) -> torch.Tensor:
         """(12,) float32: the anti-aliasing taps in use (`vx_gan_get_filter`)."""
-        if self._h is None:
-            self._create()
         out = torch.empty(N_TAPS, dtype=torch.float32)
-        _e._check(_e.load_library().vx_gan_get_filter(self._h, out.data_ptr()))
+        _e._check(_e.load_library().vx_gan_get_filter(self._handle(), out.data_ptr()))
         return out
 
     def load_state_dict(self, sd: dict, filter_taps: Optional[torch.Tensor] = None):
@@ -256,40 +235,9 @@ class GanVocoder:
             taps = torch.as_tensor(filter_taps).detach().to("cpu", torch.float32).contiguous()
             if taps.numel() != N_TAPS:
                 raise ValueError(f"filter_taps has {taps.numel()} entries, {N_TAPS} are served")
-        want = expected_keys(self.config)
-        missing = sorted(k for k in want if k not in w)
-        unexpected = sorted(k for k in w if k not in want and k not in OPTIONAL_KEYS)
-        if missing or unexpected:
-            raise KeyError(f"GanVocoder.load_state_dict: missing keys {missing}, unexpected keys {unexpected}")
-        if ("mean" in w) != ("scale" in w):
-            raise KeyError("GanVocoder.load_state_dict: mean and scale come together")
-        for k, shape in want.items():
-            if tuple(w[k].shape) != tuple(shape):
-                raise ValueError(f"GanVocoder.load_state_dict: {k} is {tuple(w[k].shape)}, expected {tuple(shape)}")
-        self._weights = {k: t.to(torch.float32).contiguous() for k, t in w.items()}
+        weights = self._checked(expected_keys(self.config), w, optional=OPTIONAL_KEYS, together=("mean", "scale"))
         self._taps = taps
-        self.close()
-        self._create()
-        return self
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_gan_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._set_weights(weights)
 
     # ---- synthesis ----------------------------------------------------------------------------------
     @torch.no_grad()
@@ -301,10 +249,8 @@ class GanVocoder:
     def synthesize_batch(self, logmels: Sequence[torch.Tensor]) -> List[torch.Tensor]:
         """[(T_i, n_mels)] -> [(T_i * hop,)], every utterance bitwise what it is alone; more than `max_batch` utterances, or more
         frames than `max_total_frames`, are served in several calls."""
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.GanVocoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
-        if self._weights is None:
-            raise RuntimeError("GanVocoder has no weights: call load_state_dict first")
+        self._need_device()
+        self._need_weights()
         n_mels = int(self.config.n_mels)
         mels = []
         for m in logmels:
@@ -329,16 +275,7 @@ class GanVocoder:
 
     def _synthesize_raw(self, mel_ptrs, n_frames, wav_ptrs):
         """vx_gan_synthesize on raw pointers (the argument checks run before any device work)."""
-        n = len(mel_ptrs)
-        mp = (C.c_void_p * n)(*mel_ptrs)
-        T = (C.c_int32 * n)(*n_frames)
-        wp = (C.c_void_p * n)(*wav_ptrs)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        if self._h is None:
-            self._create()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_gan_synthesize(self._h, n, mp, T, wp, stream))
+        self._invoke("synthesize", len(mel_ptrs), ptr_array(mel_ptrs), i32_array(n_frames), ptr_array(wav_ptrs))
 
     def save(self, path: str, wav: torch.Tensor, sample_rate: int = 24000) -> None:
         """16-bit PCM WAV (`codec.save_wav`)."""

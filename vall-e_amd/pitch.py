@@ -29,6 +29,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 import torch
 
 from . import engine as _e
+from ._handle import Handle, i32_array, prepare_waveforms, ptr_array, shared
 
 SAMPLE_RATE = 24000
 HOP = 256
@@ -75,20 +76,17 @@ def result_from_sums(s: Sequence[float], mcd_db: float = float("nan")) -> F0Resu
     return F0Result(rc, rh, corr, n_mis / n_path, int(n_vv), int(n_path), mcd_db)
 
 
-class PitchTracker:
+class PitchTracker(Handle):
     """`track_batch` serves any number of utterances, `max_batch` per call."""
+    _PREFIX, _NAME = "vx_pitch", "PitchTracker"
 
     def __init__(self, fmin: float = 60.0, fmax: float = 600.0, threshold: float = 0.1, max_frames: int = MAX_FRAMES,
                  max_batch: int = MAX_BATCH):
         self.fmin, self.fmax, self.threshold = float(fmin), float(fmax), float(threshold)
         self.max_frames, self.max_batch = int(max_frames), int(max_batch)
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None  # the device of the handle's first call: the C side keeps its staging block there
-        self._resamplers: Dict[int, object] = {}
-        self._handle()      # a band the kernel does not serve is refused here
+        self._init_handle()  # a band the kernel does not serve is refused here
         lo, hi = C.c_int32(), C.c_int32()
-        _e._check(_e.load_library().vx_pitch_lag_range(self._h, C.byref(lo), C.byref(hi)))
+        _e._check(self._fn("lag_range")(self._h, C.byref(lo), C.byref(hi)))
         self.tau_min, self.tau_max = lo.value, hi.value
 
     def _config_struct(self) -> "_e.VxPitchConfig":
@@ -99,54 +97,9 @@ class PitchTracker:
         c.max_frames, c.max_batch = self.max_frames, self.max_batch
         return c
 
-    def _handle(self):
-        if self._h is None:
-            h = C.c_void_p()
-            _e._check(_e.load_library().vx_pitch_create(C.byref(self._config_struct()), C.byref(h)))
-            self._h, self._bound = h, None
-        return self._h
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-            self._resamplers = {}
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_pitch_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _need_device(self, what: str):
-        if self.device.type != "cuda":
-            raise RuntimeError(f"valle_amd.PitchTracker.{what} runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
-
     def _mono_24k(self, wavs: List[torch.Tensor], sr: Optional[int]) -> List[torch.Tensor]:
         """As `BigVGANFbank.extract_batch` takes its input: with `sr`, (L,), (C, L) or (1, C, L) at that rate through `Resampler`."""
-        if sr is not None and (int(sr) != SAMPLE_RATE or any(w.numel() != w.shape[-1] for w in wavs)):
-            from .codec import Resampler
-
-            key = int(sr)
-            if key not in self._resamplers:
-                self._resamplers[key] = Resampler(key, SAMPLE_RATE, self.max_batch).to(self.device)
-            wavs = [r for i in range(0, len(wavs), self.max_batch) for r in self._resamplers[key].resample_batch(wavs[i:i + self.max_batch])]
-        out = []
-        for i, w in enumerate(wavs):
-            assert isinstance(w, torch.Tensor) and w.dtype == torch.float32 and w.numel() == w.shape[-1], \
-                f"utterance {i}: one mono float32 waveform per entry"
-            if w.device != self.device:
-                raise RuntimeError(f"valle_amd.PitchTracker: utterance {i} is on {w.device}, the object on {self.device} (no CPU fallback)")
-            out.append(w.detach().reshape(-1).contiguous())
-        return out
+        return prepare_waveforms(self, wavs, sr, SAMPLE_RATE, strict=True, what="utterance")
 
     @torch.no_grad()
     def track_batch(self, wavs: Sequence[torch.Tensor], sr: Optional[int] = None) -> List[PitchTrack]:
@@ -177,17 +130,8 @@ class PitchTracker:
 
     def _track_raw(self, wav_ptrs, lengths, f0_ptrs=None, ap_ptrs=None, lag_ptrs=None, voiced_ptrs=None):
         """vx_pitch_track on raw pointers (the argument checks run before any device work)."""
-        n = len(lengths)
-
-        def arr(ptrs):
-            return (C.c_void_p * n)(*ptrs) if ptrs is not None else None
-
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_pitch_track(h, n, arr(wav_ptrs), (C.c_int32 * n)(*lengths) if lengths is not None else None,
-                                                   arr(f0_ptrs), arr(ap_ptrs), arr(lag_ptrs), arr(voiced_ptrs), stream))
+        self._invoke("track", len(lengths), ptr_array(wav_ptrs), i32_array(lengths), ptr_array(f0_ptrs), ptr_array(ap_ptrs),
+                     ptr_array(lag_ptrs), ptr_array(voiced_ptrs))
 
     @torch.no_grad()
     def compare_sums(self, pairs: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]) -> torch.Tensor:
@@ -214,14 +158,8 @@ class PitchTracker:
 
     def _compare_raw(self, a_ptrs, Ta, b_ptrs, Tb, path_ptrs, path_len, sums_ptr):
         """vx_pitch_compare on raw pointers (the argument checks run before any device work)."""
-        n = len(Ta)
-        vp, i32 = (C.c_void_p * n), (C.c_int32 * n)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_pitch_compare(h, n, vp(*a_ptrs), i32(*Ta), vp(*b_ptrs), i32(*Tb), vp(*path_ptrs), i32(*path_len),
-                                                     sums_ptr, stream))
+        self._invoke("compare", len(Ta), ptr_array(a_ptrs), i32_array(Ta), ptr_array(b_ptrs), i32_array(Tb), ptr_array(path_ptrs),
+                     i32_array(path_len), sums_ptr)
 
 
 _SHARED: Dict[Tuple[torch.device, float, float, float], PitchTracker] = {}
@@ -231,15 +169,7 @@ Wave = Union[torch.Tensor, Sequence[torch.Tensor]]
 
 def shared_tracker(device, fmin: float = 60.0, fmax: float = 600.0, threshold: float = 0.1) -> PitchTracker:
     """The module's own tracker for a device and band (kept: its handle is reused by later calls)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("valle_amd.pitch runs only on an MI355X: pass device tensors (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (device, float(fmin), float(fmax), float(threshold))
-    if key not in _SHARED:
-        _SHARED[key] = PitchTracker(fmin, fmax, threshold).to(device)
-    return _SHARED[key]
+    return shared(_SHARED, device, (float(fmin), float(fmax), float(threshold)), lambda: PitchTracker(fmin, fmax, threshold), "pitch")
 
 
 @torch.no_grad()
@@ -251,7 +181,7 @@ def f0_distance(wav_a: Wave, wav_b: Wave, sr: Optional[int] = None, n_ceps: int 
     the tracker.  A waveform too short for a frame (fewer than 128 samples at 24 kHz): ValueError.  See the module's docstring
     for what the figures do not tell."""
     from . import dtw as _dtw
-    from .fbank import BigVGANFbank
+    from .fbank import shared_fbank
 
     single = isinstance(wav_a, torch.Tensor)
     wa, wb = ([wav_a], [wav_b]) if single else (list(wav_a), list(wav_b))
@@ -261,12 +191,10 @@ def f0_distance(wav_a: Wave, wav_b: Wave, sr: Optional[int] = None, n_ceps: int 
     if device.type != "cuda" or any(w.device != device for w in wa + wb):
         raise RuntimeError("valle_amd.f0_distance runs only on an MI355X: pass device tensors of one device (no CPU fallback)")
     tracker = shared_tracker(device, fmin, fmax, threshold)
-    if device not in _dtw._FBANKS:
-        _dtw._FBANKS[device] = BigVGANFbank().to(device)
     ws = tracker._mono_24k([w for p in zip(wa, wb) for w in p], sr)
     if any(num_frames(w.numel()) == 0 for w in ws):
         raise ValueError("f0_distance: a waveform has no frame (fewer than 128 samples at 24 kHz)")
-    mels = _dtw._FBANKS[device].extract_batch(ws)
+    mels = shared_fbank(device).extract_batch(ws)
     warps = _dtw.shared_dtw(device, mels[0].shape[1], n_ceps).compare_batch(list(zip(mels[0::2], mels[1::2])), return_path=True)
     tracks = tracker.track_batch(ws)
     sums = tracker.compare_sums([(tracks[2 * i].f0, tracks[2 * i + 1].f0, w.path) for i, w in enumerate(warps)])

@@ -260,15 +260,13 @@ class SpeakerEncoder(W2vHandle):
     @torch.no_grad()
     def cosine(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         """(n, xvector) x (n, xvector) embeddings on the device -> (n,) cosines (`vx_spk_similarity`)."""
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.SpeakerEncoder runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        self._need_device()
         a = a.detach().to(self.device, torch.float32).reshape(-1, self.embedding_dim).contiguous()
         b = b.detach().to(self.device, torch.float32).reshape(-1, self.embedding_dim).contiguous()
         assert a.shape == b.shape, "one embedding of b per embedding of a"
         out = torch.empty(a.shape[0], dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _e._check(_e.load_library().vx_spk_similarity(self._handle(), a.shape[0], a.data_ptr(), b.data_ptr(), out.data_ptr(),
-                                                          _e.current_stream_ptr(self.device)))
+            self._invoke("similarity", a.shape[0], a.data_ptr(), b.data_ptr(), out.data_ptr())
         return out
 
     @torch.no_grad()

@@ -25,6 +25,7 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import engine as _e
+from ._handle import Handle, i32_array, prepare_waveforms, ptr_array, shared, to_native_rate
 
 SAMPLE_RATE = 24000
 RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))  # (n_fft, hop, win)
@@ -76,16 +77,14 @@ def result_from_sums(s: torch.Tensor, n_bins: Sequence[int]) -> MSTFTResult:
     return MSTFTResult(sc, lm, float((sc + lm).mean()), frames)
 
 
-class MultiResolutionSTFT:
+class MultiResolutionSTFT(Handle):
     """`compare_batch` serves any number of pairs, `max_batch` per call."""
+    _PREFIX, _NAME = "vx_stft", "MultiResolutionSTFT"
 
     def __init__(self, config: Optional[STFTConfig] = None, max_batch: int = MAX_BATCH):
         self.config = config if config is not None else STFTConfig()
         self.max_batch = int(max_batch)
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None  # the device of the handle's first call: the C side keeps its tables and workspace there
-        self._handle()      # a geometry the kernel does not serve is refused here
+        self._init_handle()  # a geometry the kernel does not serve is refused here
 
     @property
     def n_res(self) -> int:
@@ -107,48 +106,11 @@ class MultiResolutionSTFT:
         c.max_samples, c.max_batch = int(self.config.max_samples), self.max_batch
         return c
 
-    def _handle(self):
-        if self._h is None:
-            h = C.c_void_p()
-            _e._check(_e.load_library().vx_stft_create(C.byref(self._config_struct()), C.byref(h)))
-            self._h, self._bound = h, None
-        return self._h
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_stft_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def frames(self, n_samples: int, res: int) -> int:
         return 1 + int(n_samples) // self.config.resolutions[res][1]
 
-    def _need_device(self, what: str):
-        if self.device.type != "cuda":
-            raise RuntimeError(f"valle_amd.MultiResolutionSTFT.{what} runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
-
     def _mono(self, wavs: Sequence[torch.Tensor], what: str) -> List[torch.Tensor]:
-        out = []
-        for i, w in enumerate(wavs):
-            assert isinstance(w, torch.Tensor) and w.dtype == torch.float32 and w.numel() == w.shape[-1], \
-                f"{what} {i}: one mono float32 waveform per entry"
-            if w.device != self.device:
-                raise RuntimeError(f"valle_amd.MultiResolutionSTFT: {what} {i} is on {w.device}, the object on {self.device} (no CPU fallback)")
-            out.append(w.detach().reshape(-1).contiguous())
-        return out
+        return prepare_waveforms(self, wavs, None, SAMPLE_RATE, strict=True, what=what)
 
     # ---- the distance ---------------------------------------------------------------------------------
     @torch.no_grad()
@@ -175,16 +137,7 @@ class MultiResolutionSTFT:
 
     def _compare_raw(self, x_ptrs, nx, y_ptrs, ny, sums_ptr):
         """vx_stft_compare on raw pointers (the argument checks run before any device work)."""
-        n = len(nx)
-
-        def arr(ptrs):
-            return (C.c_void_p * n)(*ptrs) if ptrs is not None else None
-
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_stft_compare(h, n, arr(x_ptrs), (C.c_int32 * n)(*nx), arr(y_ptrs), (C.c_int32 * n)(*ny), sums_ptr, stream))
+        self._invoke("compare", len(nx), ptr_array(x_ptrs), i32_array(nx), ptr_array(y_ptrs), i32_array(ny), sums_ptr)
 
     def compare_batch(self, preds: Sequence[torch.Tensor], targets: Sequence[torch.Tensor]) -> List[MSTFTResult]:
         """preds[i], targets[i]: (L,), (1, L) or (1, 1, L) float32 mono at 24 kHz on the object's device, of any two lengths."""
@@ -218,44 +171,15 @@ class MultiResolutionSTFT:
 
     def _magnitude_raw(self, res, w_ptrs, lengths, o_ptrs):
         """vx_stft_magnitude on raw pointers (the argument checks run before any device work)."""
-        n = len(lengths)
-
-        def arr(ptrs):
-            return (C.c_void_p * n)(*ptrs) if ptrs is not None else None
-
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        _e._check(_e.load_library().vx_stft_magnitude(h, int(res), n, arr(w_ptrs), (C.c_int32 * n)(*lengths), arr(o_ptrs), stream))
+        self._invoke("magnitude", int(res), len(lengths), ptr_array(w_ptrs), i32_array(lengths), ptr_array(o_ptrs))
 
 
-_SHARED: Dict[torch.device, MultiResolutionSTFT] = {}
-_RESAMPLERS: Dict[Tuple[torch.device, int], object] = {}
+_SHARED: Dict[tuple, MultiResolutionSTFT] = {}
 
 
 def shared_mstft(device) -> MultiResolutionSTFT:
     """The module's own object of the default configuration for a device (kept: its handle is reused by later calls)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("valle_amd.stft runs only on an MI355X: pass device tensors (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in _SHARED:
-        _SHARED[device] = MultiResolutionSTFT().to(device)
-    return _SHARED[device]
-
-
-def _to_24k(wavs: List[torch.Tensor], sr: Optional[int], device) -> List[torch.Tensor]:
-    """As `BigVGANFbank.extract_batch` takes its input: with `sr`, (L,), (C, L) or (1, C, L) at that rate through `Resampler`."""
-    if sr is None or (int(sr) == SAMPLE_RATE and all(w.numel() == w.shape[-1] for w in wavs)):
-        return wavs
-    from .codec import Resampler
-
-    key = (device, int(sr))
-    if key not in _RESAMPLERS:
-        _RESAMPLERS[key] = Resampler(int(sr), SAMPLE_RATE, MAX_BATCH).to(device)
-    return [r for i in range(0, len(wavs), MAX_BATCH) for r in _RESAMPLERS[key].resample_batch(wavs[i:i + MAX_BATCH])]
+    return shared(_SHARED, device, (), MultiResolutionSTFT, "stft")
 
 
 @torch.no_grad()
@@ -267,8 +191,9 @@ def mstft_distance(pred: torch.Tensor, target: torch.Tensor, sr: Optional[int] =
         raise ValueError(f"mstft_distance: common length {min(pred.shape[-1], target.shape[-1])} < 1025 samples")
     if device.type != "cuda" or target.device != device:
         raise RuntimeError("valle_amd.mstft_distance runs only on an MI355X: pass device tensors of one device (no CPU fallback)")
-    x, y = _to_24k([pred, target], sr, device)
-    return shared_mstft(device).compare(x, y).total
+    m = shared_mstft(device)
+    x, y = to_native_rate(m, [pred, target], sr, SAMPLE_RATE)
+    return m.compare(x, y).total
 
 
 @torch.no_grad()
@@ -280,12 +205,9 @@ def copy_synthesis_distance(wav: torch.Tensor, vocoder, fbank=None) -> MSTFTResu
     if device.type != "cuda":
         raise RuntimeError("valle_amd.copy_synthesis_distance runs only on an MI355X: pass a device tensor (no CPU fallback)")
     if fbank is None:
-        from . import dtw as _dtw
-        from .fbank import BigVGANFbank
+        from .fbank import shared_fbank
 
-        if device not in _dtw._FBANKS:
-            _dtw._FBANKS[device] = BigVGANFbank().to(device)
-        fbank = _dtw._FBANKS[device]
+        fbank = shared_fbank(device)
     mel = fbank.extract_batch([wav])[0]
     rec = vocoder(mel)
     return shared_mstft(device).compare(rec.reshape(-1), wav.reshape(-1))

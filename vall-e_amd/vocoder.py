@@ -23,6 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import engine as _e
+from ._handle import Handle, i32_array, ptr_array, shared
 from .fbank import HOP, N_BINS, SAMPLE_RATE, BigVGANFbankConfig
 
 TILE_FRAMES = 16        # frames one workgroup owns in a large call (csrc/vocoder_kernels.hpp VOC_TILE)
@@ -35,10 +36,11 @@ def num_samples(n_frames: int) -> int:
     return HOP * int(n_frames) if n_frames > 0 else 0
 
 
-class GriffinLim:
+class GriffinLim(Handle):
     """`GriffinLim(config=None, mel_basis=None, max_batch=64, max_total_frames=131072)`: `config` is the filterbank's
     (`BigVGANFbankConfig`, or a dict of it); `mel_basis` (n_mels, 513) replaces the built-in Slaney table, `inverse` (513, n_mels)
     replaces the least-squares inverse itself.  A call serves up to `max_batch` utterances of `max_total_frames` frames in all."""
+    _PREFIX, _NAME = "vx_vocoder", "GriffinLim"
 
     def __init__(self, config=None, mel_basis: Optional[torch.Tensor] = None, max_batch: int = 64, max_total_frames: int = 131072,
                  env_floor: float = ENV_FLOOR, inverse: Optional[torch.Tensor] = None):
@@ -56,10 +58,7 @@ class GriffinLim:
             if tuple(inverse.shape) != (N_BINS, n):
                 raise ValueError(f"inverse is {tuple(inverse.shape)}, expected ({N_BINS}, {n})")
         self.mel_basis, self._inverse = mel_basis, inverse
-        self.device = torch.device("cpu")
-        self._h = None
-        self._bound = None  # the device of the handle's first call: the C side keeps its tables there
-        self._handle()      # a geometry the kernels do not serve, or a basis without an inverse, is refused here
+        self._init_handle()  # a geometry the kernels do not serve, or a basis without an inverse, is refused here
 
     def _config_struct(self) -> "_e.VxVocoderConfig":
         c, g = _e.VxVocoderConfig(), self.config
@@ -71,21 +70,11 @@ class GriffinLim:
         c.max_batch, c.max_total_frames = self.max_batch, self.max_total_frames
         return c
 
-    def _handle(self):
-        if self._h is None:
-            lib = _e.load_library()
-            h = C.c_void_p()
-            _e._check(lib.vx_vocoder_create(C.byref(self._config_struct()), C.byref(h)))
-            try:
-                if self.mel_basis is not None:
-                    _e._check(lib.vx_vocoder_set_mel_basis(h, self.mel_basis.data_ptr()))
-                if self._inverse is not None:
-                    _e._check(lib.vx_vocoder_set_inverse(h, self._inverse.data_ptr()))
-            except Exception:
-                lib.vx_vocoder_destroy(h)
-                raise
-            self._h, self._bound = h, None
-        return self._h
+    def _configure(self, lib):
+        if self.mel_basis is not None:
+            _e._check(lib.vx_vocoder_set_mel_basis(self._h, self.mel_basis.data_ptr()))
+        if self._inverse is not None:
+            _e._check(lib.vx_vocoder_set_inverse(self._h, self._inverse.data_ptr()))
 
     @property
     def inverse(self) -> torch.Tensor:
@@ -93,25 +82,6 @@ class GriffinLim:
         out = torch.empty((N_BINS, int(self.config.num_mel_bins)), dtype=torch.float32)
         _e._check(_e.load_library().vx_vocoder_get_inverse(self._handle(), out.data_ptr()))
         return out
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if self._bound is not None and self._bound != self.device:
-            self.close()  # another device gets a fresh handle on its first call
-        return self
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _e.load_library().vx_vocoder_destroy(self._h)
-            self._h = self._bound = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- synthesis ----------------------------------------------------------------------------------
     @torch.no_grad()
@@ -129,8 +99,7 @@ class GriffinLim:
         """[(T_i, n_mels)] -> [(256 T_i,)] (and [(T_i, 513, 2)] with `return_phase`), every utterance bitwise what it is alone;
         more than `max_batch` utterances, or more frames than `max_total_frames`, are served in several calls.  With `rand_init`
         utterance i starts from phases drawn uniformly in [0, 2 pi) by a CPU generator seeded with `seed + i`."""
-        if self.device.type != "cuda":
-            raise RuntimeError("valle_amd.GriffinLim runs only on an MI355X: call .to('cuda') first (no CPU fallback)")
+        self._need_device()
         if init_phase is not None and rand_init:
             raise ValueError("init_phase and rand_init exclude each other")
         n_mels = int(self.config.num_mel_bins)
@@ -174,19 +143,8 @@ class GriffinLim:
 
     def _synthesize_raw(self, mel_ptrs, n_frames, init_ptrs, n_iter, momentum, wav_ptrs, phase_ptrs, warm: bool = False):
         """vx_vocoder_synthesize (or _warm) on raw pointers (the argument checks run before any device work)."""
-        n = len(mel_ptrs)
-        mp = (C.c_void_p * n)(*mel_ptrs)
-        T = (C.c_int32 * n)(*n_frames)
-        ip = None if init_ptrs is None else (C.c_void_p * n)(*init_ptrs)
-        wp = (C.c_void_p * n)(*wav_ptrs)
-        pp = None if phase_ptrs is None else (C.c_void_p * n)(*phase_ptrs)
-        stream = _e.current_stream_ptr(self.device) if self.device.type == "cuda" else None
-        h = self._handle()
-        if self.device.type == "cuda":
-            self._bound = self.device
-        lib = _e.load_library()
-        fn = lib.vx_vocoder_synthesize_warm if warm else lib.vx_vocoder_synthesize
-        _e._check(fn(h, n, mp, T, ip, int(n_iter), float(momentum), wp, pp, stream))
+        self._invoke("synthesize_warm" if warm else "synthesize", len(mel_ptrs), ptr_array(mel_ptrs), i32_array(n_frames),
+                     ptr_array(init_ptrs), int(n_iter), float(momentum), ptr_array(wav_ptrs), ptr_array(phase_ptrs))
 
     @staticmethod
     def save(path: str, wav: torch.Tensor) -> None:
@@ -201,12 +159,7 @@ _SHARED = {}
 
 def shared_griffinlim(device) -> GriffinLim:
     """The process-wide default vocoder of a device (what `mel_to_waveform` and `Transformer.inference_waveform` use)."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in _SHARED:
-        _SHARED[device] = GriffinLim().to(device)
-    return _SHARED[device]
+    return shared(_SHARED, device, (), GriffinLim)  # any device: a host object answers the host-side surface (`inverse`)
 
 
 def mel_to_waveform(logmel: torch.Tensor, **kw):
