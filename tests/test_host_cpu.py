@@ -1,17 +1,29 @@
 """No GPU: the host support the translation units share (csrc/host.hpp).
 
 Every unit reports through the one thread-local message behind vx_last_error(), and a failing HIP call names the unit that made
-it, also where DevBuf or CallStage made it on the unit's behalf.  Without a device the first HIP call of each entry fails: the
-three small handles (vx_fbank, vx_resampler, vx_dtw) must come out of that failed first use as they went in - the same answer
-a second time, a clean destroy - and the op-level entries must give their scratch back.  Where a GPU is present the same calls
-succeed (the buffers are then real device memory), so either return code is accepted and the message is checked only on failure."""
+it, also where DevBuf, CallStage or open_device made it on the unit's behalf.  Without a device the first HIP call of each entry
+fails: the small handles (vx_fbank, vx_resampler, vx_dtw, vx_gan here; vx_pitch, vx_stft and vx_vocoder in their own files) must
+come out of that failed first use as they went in - the same answer a second time, a clean destroy - and the op-level entries
+must give their scratch back.  Where a GPU is present the same calls succeed (the buffers are then real device memory), so either
+return code is accepted and the message is checked only on failure.  Every handle also closes without ever having reached a
+device, and every *_create on the shared head (create_head) refuses a null argument and a wrong struct_size in the same words."""
 import ctypes as C
 
 import pytest
 import torch
 
+import ganvoc_ref as GR
+from valle_amd import engine as E
+from valle_amd.codec import Resampler
+from valle_amd.dtw import DTW
 from valle_amd.engine import VxDtwConfig
 from valle_amd.fbank import BigVGANFbank
+from valle_amd.ganvoc import GanVocoder
+from valle_amd.pitch import PitchTracker
+from valle_amd.stft import MultiResolutionSTFT
+from valle_amd.vocoder import GriffinLim
+
+VX_ERR_ARG = 1  # include/vallex.h
 
 DEV = "cuda" if torch.cuda.is_available() else "cpu"  # without a GPU the pointers are never dereferenced
 
@@ -78,6 +90,49 @@ def test_dtw_first_use_without_a_device_leaves_a_usable_handle(lib):
            "dtw.hip")
     assert lib.vx_dtw_compare(h, 3, ap, ta, bp, tb, total.data_ptr(), length.data_ptr(), None, None) == 4
     lib.vx_dtw_destroy(h)
+
+
+def _gan():
+    cfg = GR.GEOMETRIES["g1_snakebeta"]
+    return GanVocoder(cfg, state_dict=GR.make_weights(cfg, 1), max_batch=2, max_total_frames=50)
+
+
+def test_gan_first_use_without_a_device_leaves_a_usable_handle(lib):
+    v = _gan()
+    mel, wav = _buf(4, 100), _buf(16)
+    mp, T, wp = (C.c_void_p * 1)(mel.data_ptr()), (C.c_int32 * 1)(4), (C.c_void_p * 1)(wav.data_ptr())
+    _twice(lib, lambda: lib.vx_gan_synthesize(v._h, 1, mp, T, wp, None), "hipGetDevice", "ganvoc.hip")
+    assert lib.vx_gan_synthesize(v._h, 3, mp, T, wp, None) == 4  # the host-side checks still answer
+    v.close()
+
+
+def test_every_handle_closes_without_having_reached_a_device(lib):
+    made = [BigVGANFbank(max_batch=2), Resampler(16000, 24000, max_batch=2), DTW(dim=8, n_ceps=3, max_frames=16, max_batch=2),
+            PitchTracker(max_frames=64, max_batch=2), MultiResolutionSTFT(max_batch=2), GriffinLim(max_batch=2, max_total_frames=50),
+            _gan()]
+    assert [type(h)._PREFIX for h in made] == ["vx_fbank", "vx_resampler", "vx_dtw", "vx_pitch", "vx_stft", "vx_vocoder", "vx_gan"]
+    for h in made:
+        assert h._h is not None and h._bound is None
+        h.close()
+        assert h._h is None
+    for prefix in ("vx_fbank", "vx_resampler", "vx_dtw", "vx_pitch", "vx_stft", "vx_vocoder", "vx_gan"):
+        getattr(lib, prefix + "_destroy")(None)
+
+
+def test_create_heads_refuse_in_the_same_words(lib):
+    """VX_ERR_ARG, and the entry point's own name in front of the two texts of create_head."""
+    for name, cfg_t in (("vx_fbank_create", E.VxFbankConfig), ("vx_dtw_create", E.VxDtwConfig), ("vx_pitch_create", E.VxPitchConfig),
+                        ("vx_stft_create", E.VxStftConfig), ("vx_vocoder_create", E.VxVocoderConfig), ("vx_gan_create", E.VxGanConfig),
+                        ("vx_spk_create", E.VxSpkConfig), ("vx_asr_create", E.VxAsrConfig), ("vx_wsp_create", E.VxWspConfig)):
+        create, size, h = getattr(lib, name), C.sizeof(cfg_t), C.c_void_p()
+        c = cfg_t()
+        c.struct_size = size
+        assert create(C.byref(c), None) == VX_ERR_ARG and lib.vx_last_error().decode() == name + ": null argument"
+        assert create(None, C.byref(h)) == VX_ERR_ARG and lib.vx_last_error().decode() == name + ": null argument"
+        c.struct_size = size + 4
+        assert create(C.byref(c), C.byref(h)) == VX_ERR_ARG
+        assert lib.vx_last_error().decode() == "%s: struct_size %d, expected %d" % (name, size + 4, size)
+        assert not h.value
 
 
 def test_op_entries_name_the_failing_call_and_their_unit(lib):

@@ -102,9 +102,7 @@ extern "C" int64_t vx_asr_frames(const vx_asr* g, int64_t n_samples) {
 extern "C" int64_t vx_asr_min_samples(const vx_asr* g) { return !g ? -1 : (int64_t)g->m.min_samples; }
 
 extern "C" int vx_asr_create(const vx_asr_config* cfg, vx_asr** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_asr_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_asr_config))
-    return fail(VX_ERR_ARG, "vx_asr_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_asr_config));
+  VXC(create_head("vx_asr_create", cfg, out));
   const vx_asr_config& c = *cfg;
   const char* what = "vx_asr_create";
   W2vGeom q = w2v_geom(c, c.feat_proj_layer_norm, (c.flags & VX_ASR_KEEP_TAPS) != 0);
@@ -177,8 +175,7 @@ extern "C" int vx_asr_recognize(vx_asr* g, int32_t n, const float* const* wav, c
   const vx_asr_config& c = g->cfg;
   const auto t_begin = std::chrono::steady_clock::now();
   VXC(ensure_device(g, asr_init_device));
-  DevGuard guard(g->device);
-  HIPC(guard.err);
+  ON_DEVICE(g->device);
   AsrDev& dv = *g->dev;
   W2vRun x{};
   VXC(w2v_stage_begin(g, c.n_conv, n, wav, n_samples, (hipStream_t)stream, x));
@@ -350,8 +347,7 @@ extern "C" int vx_falign_asr(vx_asr* g, int32_t n, const int32_t* targets, const
   for (int i = 0; i < n; ++i) frames[i] = seg[i + 1] - seg[i];
   FalPlan p;
   VXC(fal_plan("vx_falign_asr", c.vocab, c.blank, n, frames.data(), targets, target_len, o.max_half(), p));
-  DevGuard guard(g->device);
-  HIPC(guard.err);
+  ON_DEVICE(g->device);
   AsrDev& dv = *g->dev;
   hipStream_t s = (hipStream_t)stream;
   HIPC(hipStreamWaitEvent(s, dv.stage.ev_done, 0));  // the logits of the last call, whatever stream it ran on

@@ -439,8 +439,7 @@ extern "C" int vx_codec_finalize(vx_codec* e) {
     if (!kv.second.set) return fail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
   const vx_codec_config& c = e->cfg;
   e->failed = true;     // until the last statement: a finalize that stops at a HIP error leaves a handle that refuses further use
-  DevGuard g(c.device);
-  HIPC(g.err);
+  ON_DEVICE(c.device);
   e->allocated = true;  // from here vx_codec_destroy frees what was allocated
   const int W = e->W;
   char k[128], k2[128];
@@ -615,8 +614,7 @@ extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* cod
       if (codes[i][j] < 0 || codes[i][j] >= c.codebook_size)
         return fail(VX_ERR_ARG, "utterance %d: code %lld outside [0, %d)", i, (long long)codes[i][j], c.codebook_size);
   if (!e->finalized) return fail(VX_ERR_STATE, "vx_codec_decode before vx_codec_finalize");
-  DevGuard g(c.device);
-  HIPC(g.err);
+  ON_DEVICE(c.device);
   // The work runs on the decoder's own stream, ordered after everything already enqueued on `stream`; `stream` waits for it
   // before the call returns (as the engine's entry points do).  The host waits only for the previous call's staging copy.
   hipStream_t s = e->own;
@@ -713,8 +711,7 @@ extern "C" int vx_codec_encode(vx_codec* e, int32_t n, const float* const* wav, 
       return fail(VX_ERR_CAPACITY, "utterance %d: %d samples > max_frames %d x %ld", i, n_samples[i], c.max_frames, hop);
   }
   if (!e->finalized) return fail(VX_ERR_STATE, "vx_codec_encode before vx_codec_finalize");
-  DevGuard g(c.device);
-  HIPC(g.err);
+  ON_DEVICE(c.device);
   hipStream_t s = e->own;  // ordering as vx_codec_decode
   HIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
   HIPC(hipStreamWaitEvent(s, e->ev_in, 0));
@@ -811,8 +808,7 @@ extern "C" int vx_codec_last_embeddings(vx_codec* e, float* out, int64_t rows, v
   if (!(e->cfg.flags & VX_CODEC_ENCODER) || !e->finalized) return fail(VX_ERR_STATE, "vx_codec_last_embeddings: no finalised encoder");
   if (rows < 1 || rows > e->last_frames)
     return fail(VX_ERR_ARG, "vx_codec_last_embeddings: rows = %lld, the last encode had %ld frames", (long long)rows, e->last_frames);
-  DevGuard g(e->cfg.device);
-  HIPC(g.err);
+  ON_DEVICE(e->cfg.device);
   HIPC(hipMemcpyAsync(out, e->x0, (size_t)rows * e->cfg.hidden * sizeof(float), hipMemcpyDeviceToDevice, e->own));
   HIPC(hipEventRecord(e->ev_out, e->own));
   HIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
@@ -939,18 +935,18 @@ namespace {
 struct ResamplerDev {
   DevBuf<float> coef;
   DevBuf<int> phase;  // first [n] | count [n]
-  // per call: in pointers [max_batch] | out pointers [max_batch] | tile0 [max_batch + 1] | len_in | chans | len_out [max_batch each]
-  CallStage stage;
+  CallStage stage;  // per call: a RaggedTable of in | out pointers, tile0, len_in | chans | len_out
 };
+
+enum { COL_IN, COL_OUT, N_PTR_COLS };                         // the staged block's pointer columns
+enum { COL_LEN_IN, COL_CHANS, COL_LEN_OUT, N_INT_COLS };      // and its int columns
 }  // namespace
 
-struct vx_resampler {
+struct vx_resampler : LazyDev<ResamplerDev> {
   int orig = 0, neu = 0, max_batch = 0;
   int o = 1, n = 1, T = 1, tile_out = 256;
   std::vector<float> coef;        // [T][n], scale folded in, zero past a phase's count
   std::vector<int> first, count;  // [n]
-  int device = -1;  // >= 0: `dev` is complete
-  std::unique_ptr<ResamplerDev> dev;
 };
 
 namespace {
@@ -1023,17 +1019,16 @@ int resampler_build(vx_resampler* r) {
   return VX_OK;
 }
 
+RaggedTable call_table(const vx_resampler* r) { return RaggedTable(r->max_batch, N_PTR_COLS, N_INT_COLS); }
+
 // First use: the tables go to the current device.
 int resampler_init_device(vx_resampler* r) {
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  r->device = dev;
-  r->dev.reset(new ResamplerDev());
+  VXC(open_device(r));
   ResamplerDev& d = *r->dev;
-  const size_t nc = r->coef.size(), MB = (size_t)r->max_batch, n = (size_t)r->n;
+  const size_t nc = r->coef.size(), n = (size_t)r->n;
   VXC(d.coef.alloc(nc));
   VXC(d.phase.alloc(2 * n));
-  VXC(d.stage.init(2 * MB * sizeof(void*) + (4 * MB + 1) * sizeof(int)));
+  VXC(d.stage.init(call_table(r).bytes()));
   HIPC(hipMemcpy(d.coef.get(), r->coef.data(), nc * sizeof(float), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(d.phase.get(), r->first.data(), n * sizeof(int), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(d.phase.get() + n, r->count.data(), n * sizeof(int), hipMemcpyHostToDevice));
@@ -1063,15 +1058,7 @@ extern "C" int vx_resampler_create(int32_t orig_hz, int32_t new_hz, int32_t max_
   return VX_OK;
 }
 
-extern "C" void vx_resampler_destroy(vx_resampler* r) {
-  if (!r) return;
-  if (r->device >= 0) {
-    DevGuard g(r->device);
-    (void)r->dev->stage.drain();
-    r->dev.reset();
-  }
-  delete r;
-}
+extern "C" void vx_resampler_destroy(vx_resampler* r) { destroy_handle(r); }
 
 extern "C" int vx_resample(vx_resampler* r, int32_t n, const float* const* in, const int32_t* channels, const int32_t* n_samples,
                            float* const* out, void* stream) {
@@ -1090,37 +1077,24 @@ extern "C" int vx_resample(vx_resampler* r, int32_t n, const float* const* in, c
     if (tiles > 0x7fffffffL) return fail(VX_ERR_UNSUPPORTED, "vx_resample: utterance %d: the call's output tiles exceed int32", i);
     tile0[i + 1] = (int)tiles;
   }
-  if (r->device < 0) {
-    const int rc = resampler_init_device(r);
-    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
-      r->dev.reset();
-      r->device = -1;
-      return rc;
-    }
-  }
-  DevGuard g(r->device);
-  HIPC(g.err);
+  VXC(ensure_device(r, resampler_init_device));
+  ON_DEVICE(r->device);
   ResamplerDev& d = *r->dev;
   hipStream_t s = (hipStream_t)stream;
   VXC(d.stage.begin(s));
-  const size_t MB = (size_t)r->max_batch;
-  const float** hin = d.stage.host<const float*>();
-  float** hout = d.stage.host<float*>(MB * sizeof(void*));
-  int* hint = d.stage.host<int>(2 * MB * sizeof(void*));
-  for (int i = 0; i < n; ++i) {
-    hin[i] = in[i];
-    hout[i] = out[i];
-    hint[MB + 1 + i] = n_samples[i];
-    hint[2 * MB + 1 + i] = channels[i];
-    hint[3 * MB + 1 + i] = len_out[i];
-  }
-  memcpy(hint, tile0.data(), (n + 1) * sizeof(int));
-  VXC(d.stage.upload(d.stage.bytes, s));
+  const RaggedTable t = call_table(r);
+  memcpy(t.host_ptrs<const float*>(d.stage, COL_IN), in, n * sizeof(float*));
+  memcpy(t.host_ptrs<float*>(d.stage, COL_OUT), out, n * sizeof(float*));
+  memcpy(t.host_tile0(d.stage), tile0.data(), (n + 1) * sizeof(int));
+  memcpy(t.host_ints(d.stage, COL_LEN_IN), n_samples, n * sizeof(int));
+  memcpy(t.host_ints(d.stage, COL_CHANS), channels, n * sizeof(int));
+  memcpy(t.host_ints(d.stage, COL_LEN_OUT), len_out.data(), n * sizeof(int));
+  VXC(d.stage.upload(t.bytes(), s));
   ResampleArgs a{};
-  a.in = d.stage.dev<const float* const>();
-  a.out = d.stage.dev<float* const>(MB * sizeof(void*));
-  const int* dint = d.stage.dev<const int>(2 * MB * sizeof(void*));
-  a.tile0 = dint; a.len_in = dint + MB + 1; a.chans = dint + 2 * MB + 1; a.len_out = dint + 3 * MB + 1;
+  a.in = t.dev_ptrs<const float* const>(d.stage, COL_IN);
+  a.out = t.dev_ptrs<float* const>(d.stage, COL_OUT);
+  a.tile0 = t.dev_tile0(d.stage); a.len_in = t.dev_ints(d.stage, COL_LEN_IN); a.chans = t.dev_ints(d.stage, COL_CHANS);
+  a.len_out = t.dev_ints(d.stage, COL_LEN_OUT);
   a.coef = d.coef.get(); a.first = d.phase.get(); a.count = d.phase.get() + r->n;
   a.nseg = n; a.o = r->o; a.n = r->n; a.T = r->T; a.tile_out = r->tile_out;
   const unsigned grid = (unsigned)std::min(tile0[n], 2048);

@@ -30,11 +30,9 @@ struct DtwDev {
 };
 }  // namespace
 
-struct vx_dtw {
+struct vx_dtw : LazyDev<DtwDev> {
   int dim = 0, n_ceps = 0, max_frames = 0, max_batch = 0;
   std::vector<float> tab;  // [dim][n_ceps]: sqrt(2 / dim) cos(pi k (n + 1/2) / dim), k = 1 .. n_ceps
-  int device = -1;  // >= 0: `dev` is complete
-  std::unique_ptr<DtwDev> dev;
 };
 
 namespace {
@@ -50,10 +48,7 @@ std::vector<float> dct_table(int dim, int n_ceps) {
 
 // First use: the table goes to the current device.
 int dtw_init_device(vx_dtw* h) {
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  h->device = dev;
-  h->dev.reset(new DtwDev());
+  VXC(open_device(h));
   DtwDev& d = *h->dev;
   const size_t MB = (size_t)h->max_batch;
   VXC(d.stage.init(MB * sizeof(DtwPair)));
@@ -115,9 +110,7 @@ hipError_t launch_dtw_warp(const float* d_cost, unsigned char* d_bp, const DtwPa
 }  // namespace
 
 extern "C" int vx_dtw_create(const vx_dtw_config* cfg, vx_dtw** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_dtw_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_dtw_config))
-    return fail(VX_ERR_ARG, "vx_dtw_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_dtw_config));
+  VXC(create_head("vx_dtw_create", cfg, out));
   if (cfg->max_batch < 1) return fail(VX_ERR_ARG, "vx_dtw_create: max_batch = %d", cfg->max_batch);
   if (cfg->dim < 1 || cfg->dim > DTW_MAX_DIM) return fail(VX_ERR_UNSUPPORTED, "vx_dtw_create: dim = %d outside [1, %d]", cfg->dim, DTW_MAX_DIM);
   if (cfg->n_ceps < 0 || cfg->n_ceps > cfg->dim - 1)
@@ -132,15 +125,7 @@ extern "C" int vx_dtw_create(const vx_dtw_config* cfg, vx_dtw** out) {
   return VX_OK;
 }
 
-extern "C" void vx_dtw_destroy(vx_dtw* h) {
-  if (!h) return;
-  if (h->device >= 0) {
-    DevGuard g(h->device);
-    (void)h->dev->stage.drain();
-    h->dev.reset();
-  }
-  delete h;
-}
+extern "C" void vx_dtw_destroy(vx_dtw* h) { destroy_handle(h); }
 
 extern "C" int vx_dtw_compare(vx_dtw* h, int32_t n, const float* const* a, const int32_t* Ta, const float* const* b, const int32_t* Tb,
                               double* total, int32_t* path_len, int32_t* const* path, void* stream) {
@@ -165,16 +150,8 @@ extern "C" int vx_dtw_compare(vx_dtw* h, int32_t n, const float* const* a, const
     tiles += ((Ta[i] + DTW_TILE - 1) / DTW_TILE) * ((Tb[i] + DTW_TILE - 1) / DTW_TILE);  // <= 64 pairs x 64 x 64 tiles
     max_ta = std::max(max_ta, Ta[i]);
   }
-  if (h->device < 0) {
-    const int rc = dtw_init_device(h);
-    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
-      h->dev.reset();
-      h->device = -1;
-      return rc;
-    }
-  }
-  DevGuard g(h->device);
-  HIPC(g.err);
+  VXC(ensure_device(h, dtw_init_device));
+  ON_DEVICE(h->device);
   DtwDev& d = *h->dev;
   hipStream_t s = (hipStream_t)stream;
   VXC(dtw_grow(h, cells, rows));

@@ -21,35 +21,33 @@ namespace {
 struct FbankDev {
   DevBuf<float> tab, basis_t;
   DevBuf<int> band;
-  // per call: wav pointers [max_batch] | out pointers [max_batch] | tile0 [max_batch + 1] | len | frames [max_batch each]
-  CallStage stage;
+  CallStage stage;  // per call: a RaggedTable of wav | out pointers, tile0, len | frames
 };
 }  // namespace
 
-struct vx_fbank {
+struct vx_fbank : LazyDev<FbankDev> {
   int n_mels = 0, max_batch = 0;
   float clip = 0.f;
   std::vector<float> basis;  // [n_mels][513]
   std::vector<float> tab;    // window | cos | sin
   bool basis_dirty = true;   // the device copy is older than `basis`
-  int device = -1;  // >= 0: `dev` is complete
-  std::unique_ptr<FbankDev> dev;
 };
 
 namespace {
 
+enum { COL_WAV, COL_OUT, N_PTR_COLS };  // the staged block's pointer columns
+enum { COL_LEN, COL_FRAMES, N_INT_COLS };  // and its int columns
+
+RaggedTable call_table(const vx_fbank* fb) { return RaggedTable(fb->max_batch, N_PTR_COLS, N_INT_COLS); }
+
 // First use: the tables go to the current device.
 int fbank_init_device(vx_fbank* fb) {
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  fb->device = dev;
-  fb->dev.reset(new FbankDev());
+  VXC(open_device(fb));
   FbankDev& d = *fb->dev;
-  const size_t MB = (size_t)fb->max_batch;
   VXC(d.tab.alloc(FBANK_TAB));
   VXC(d.basis_t.alloc((size_t)fb->n_mels * FBANK_BINS));
   VXC(d.band.alloc(2 * (size_t)fb->n_mels));
-  VXC(d.stage.init(2 * MB * sizeof(void*) + (3 * MB + 1) * sizeof(int)));
+  VXC(d.stage.init(call_table(fb).bytes()));
   HIPC(hipMemcpy(d.tab.get(), fb->tab.data(), FBANK_TAB * sizeof(float), hipMemcpyHostToDevice));
   fb->basis_dirty = true;
   return VX_OK;
@@ -83,9 +81,7 @@ extern "C" int64_t vx_fbank_frames(int64_t n_samples) {
 }
 
 extern "C" int vx_fbank_create(const vx_fbank_config* cfg, vx_fbank** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_fbank_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_fbank_config))
-    return fail(VX_ERR_ARG, "vx_fbank_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_fbank_config));
+  VXC(create_head("vx_fbank_create", cfg, out));
   if (cfg->max_batch < 1) return fail(VX_ERR_ARG, "vx_fbank_create: max_batch = %d", cfg->max_batch);
   if (!(cfg->clip > 0.f) || !isfinite(cfg->clip)) return fail(VX_ERR_ARG, "vx_fbank_create: clip = %g (the floor under the log is positive)", cfg->clip);
   if (cfg->sample_rate != 24000 || cfg->n_fft != FBANK_NFFT || cfg->hop != FBANK_HOP)
@@ -98,29 +94,12 @@ extern "C" int vx_fbank_create(const vx_fbank_config* cfg, vx_fbank** out) {
   vx_fbank* fb = new vx_fbank();
   fb->n_mels = cfg->n_mels; fb->max_batch = cfg->max_batch; fb->clip = cfg->clip;
   fb->basis = slaney_basis(cfg->sample_rate, cfg->n_mels, FBANK_BINS, cfg->fmin, cfg->fmax);
-  fb->tab.resize(FBANK_TAB);
-  const double pi = 3.14159265358979323846;
-  for (int j = 0; j < 1024; ++j) {
-    const double t = 2.0 * pi * (double)j / 1024.0;
-    fb->tab[j] = (float)(0.5 - 0.5 * cos(t));  // periodic Hann
-    fb->tab[1024 + j] = (float)cos(t);
-    fb->tab[2048 + j] = (float)sin(t);
-  }
-  // the multiples of a quarter turn exactly (cos(pi / 2) in fp64 is 6e-17, not 0)
-  fb->tab[1024 + 256] = 0.f; fb->tab[1024 + 768] = 0.f; fb->tab[2048 + 512] = 0.f;
+  fb->tab = hann_cos_sin_1024();
   *out = fb;
   return VX_OK;
 }
 
-extern "C" void vx_fbank_destroy(vx_fbank* fb) {
-  if (!fb) return;
-  if (fb->device >= 0) {
-    DevGuard g(fb->device);
-    (void)fb->dev->stage.drain();
-    fb->dev.reset();
-  }
-  delete fb;
-}
+extern "C" void vx_fbank_destroy(vx_fbank* fb) { destroy_handle(fb); }
 
 extern "C" int vx_fbank_set_mel_basis(vx_fbank* fb, const float* basis) {
   if (!fb || !basis) return fail(VX_ERR_ARG, "vx_fbank_set_mel_basis: null argument");
@@ -150,16 +129,8 @@ extern "C" int vx_fbank_extract(vx_fbank* fb, int32_t n, const float* const* wav
     tile0[i + 1] = (int)tiles;
   }
   if (tile0[n] == 0) return VX_OK;  // no utterance has a frame: nothing to write
-  if (fb->device < 0) {
-    const int rc = fbank_init_device(fb);
-    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
-      fb->dev.reset();
-      fb->device = -1;
-      return rc;
-    }
-  }
-  DevGuard g(fb->device);
-  HIPC(g.err);
+  VXC(ensure_device(fb, fbank_init_device));
+  ON_DEVICE(fb->device);
   FbankDev& d = *fb->dev;
   hipStream_t s = (hipStream_t)stream;
   if (fb->basis_dirty) {
@@ -167,23 +138,17 @@ extern "C" int vx_fbank_extract(vx_fbank* fb, int32_t n, const float* const* wav
     VXC(fbank_upload_basis(fb));
   }
   VXC(d.stage.begin(s));
-  const size_t MB = (size_t)fb->max_batch;
-  const float** hin = d.stage.host<const float*>();
-  float** hout = d.stage.host<float*>(MB * sizeof(void*));
-  int* hint = d.stage.host<int>(2 * MB * sizeof(void*));
-  for (int i = 0; i < n; ++i) {
-    hin[i] = wav[i];
-    hout[i] = out[i];
-    hint[MB + 1 + i] = n_samples[i];
-    hint[2 * MB + 1 + i] = frames[i];
-  }
-  memcpy(hint, tile0.data(), (n + 1) * sizeof(int));
-  VXC(d.stage.upload(d.stage.bytes, s));
+  const RaggedTable t = call_table(fb);
+  memcpy(t.host_ptrs<const float*>(d.stage, COL_WAV), wav, n * sizeof(float*));
+  memcpy(t.host_ptrs<float*>(d.stage, COL_OUT), out, n * sizeof(float*));
+  memcpy(t.host_tile0(d.stage), tile0.data(), (n + 1) * sizeof(int));
+  memcpy(t.host_ints(d.stage, COL_LEN), n_samples, n * sizeof(int));
+  memcpy(t.host_ints(d.stage, COL_FRAMES), frames.data(), n * sizeof(int));
+  VXC(d.stage.upload(t.bytes(), s));
   FbankArgs a{};
-  a.wav = d.stage.dev<const float* const>();
-  a.out = d.stage.dev<float* const>(MB * sizeof(void*));
-  const int* dint = d.stage.dev<const int>(2 * MB * sizeof(void*));
-  a.tile0 = dint; a.len = dint + MB + 1; a.frames = dint + 2 * MB + 1;
+  a.wav = t.dev_ptrs<const float* const>(d.stage, COL_WAV);
+  a.out = t.dev_ptrs<float* const>(d.stage, COL_OUT);
+  a.tile0 = t.dev_tile0(d.stage); a.len = t.dev_ints(d.stage, COL_LEN); a.frames = t.dev_ints(d.stage, COL_FRAMES);
   a.tab = d.tab.get(); a.basis_t = d.basis_t.get(); a.band = d.band.get();
   a.nseg = n; a.n_mels = fb->n_mels; a.clip = fb->clip;
   const unsigned grid = (unsigned)std::min(tile0[n], 4096);

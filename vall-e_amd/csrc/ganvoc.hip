@@ -55,7 +55,7 @@ constexpr long GAN_GROUP_FLOATS = 1L << 24;  // target size of a row buffer: gro
 
 }  // namespace
 
-struct vx_gan {
+struct vx_gan : LazyDev<GanDev> {
   vx_gan_config cfg{};
   std::map<std::string, HostW> w;
   bool finalized = false;
@@ -69,8 +69,6 @@ struct vx_gan {
   GanStage st[8];
   size_t mean = 0, scale = 0;
   bool has_norm = false;
-  int device = -1;  // >= 0: `dev` is complete
-  std::unique_ptr<GanDev> dev;
 };
 
 namespace {
@@ -280,10 +278,7 @@ int run_group(const GroupCtx& x, const float* const* in_ptrs, float* const* out_
 }
 
 int gan_init_device(vx_gan* g) {
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  g->device = dev;
-  g->dev.reset(new GanDev());
+  VXC(open_device(g));
   GanDev& d = *g->dev;
   const size_t MB = (size_t)g->cfg.max_batch;
   VXC(d.w.alloc(g->packed.size() + 4));
@@ -297,9 +292,7 @@ int gan_init_device(vx_gan* g) {
 extern "C" int64_t vx_gan_samples(const vx_gan* g, int64_t n_frames) { return (!g || n_frames < 0) ? 0 : n_frames * g->hop; }
 
 extern "C" int vx_gan_create(const vx_gan_config* cfg, vx_gan** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_gan_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_gan_config))
-    return fail(VX_ERR_ARG, "vx_gan_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_gan_config));
+  VXC(create_head("vx_gan_create", cfg, out));
   const vx_gan_config& c = *cfg;
   if (c.max_batch < 1) return fail(VX_ERR_ARG, "vx_gan_create: max_batch = %d", c.max_batch);
   if (c.max_total_frames < 1) return fail(VX_ERR_ARG, "vx_gan_create: max_total_frames = %d", c.max_total_frames);
@@ -380,15 +373,7 @@ extern "C" int vx_gan_create(const vx_gan_config* cfg, vx_gan** out) {
   return VX_OK;
 }
 
-extern "C" void vx_gan_destroy(vx_gan* g) {
-  if (!g) return;
-  if (g->device >= 0) {
-    DevGuard guard(g->device);
-    (void)g->dev->stage.drain();
-    g->dev.reset();
-  }
-  delete g;
-}
+extern "C" void vx_gan_destroy(vx_gan* g) { destroy_handle(g); }
 
 extern "C" int vx_gan_set_weight(vx_gan* g, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
   if (!g || !key || !data || !shape) return fail(VX_ERR_ARG, "vx_gan_set_weight: null argument");
@@ -502,16 +487,8 @@ extern "C" int vx_gan_synthesize(vx_gan* g, int32_t n, const float* const* logme
     }
     first.push_back(n);
   }
-  if (g->device < 0) {
-    const int rc = gan_init_device(g);
-    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
-      g->dev.reset();
-      g->device = -1;
-      return rc;
-    }
-  }
-  DevGuard guard(g->device);
-  HIPC(guard.err);
+  VXC(ensure_device(g, gan_init_device));
+  ON_DEVICE(g->device);
   GanDev& d = *g->dev;
   hipStream_t s = (hipStream_t)stream;
   const size_t cap = ((size_t)need * (size_t)g->widest + 3) / 4 * 4;

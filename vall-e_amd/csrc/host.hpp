@@ -1,9 +1,15 @@
-// Host-side support shared by the translation units of libvallex.so: error reporting, the device guard, VX_POISON, an owner of
-// one device block and the staging protocol of a ragged call.  Host code only: no kernel, no kernel header.  A new handle starts
-// from CallStage + DevBuf (fbank.hip is the shortest example).
+// Host-side support shared by the translation units of libvallex.so: error reporting, the head of a *_create, the device guard,
+// VX_POISON, an owner of one device block, the staging protocol of a ragged call, the table most ragged calls stage and the lazy
+// device side of a handle.  Host code only: no kernel, no kernel header.  A new handle derives from LazyDev<its Dev>, keeps a
+// CallStage named `stage` and DevBufs in that Dev, opens its *_init_device with open_device, and writes its entry points as
+//   create_head;  host-side checks;  ensure_device;  ON_DEVICE;  drain before a table is replaced;  begin .. upload .. kernels .. finish
+// with destroy_handle as its destroy (fbank.hip is the shortest example).  A call whose per-utterance arrays are pointer columns,
+// tile0 and int columns lays them out with RaggedTable.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
+
+#include <memory>
 
 #include "../../include/vallex.h"
 
@@ -24,6 +30,14 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3), vi
     int r_ = (expr);            \
     if (r_ != VX_OK) return r_; \
   } while (0)
+
+// The head of a *_create whose config carries its struct_size: `fn` is the entry point's name.
+template <class Cfg, class Handle>
+int create_head(const char* fn, const Cfg* cfg, Handle** out) {
+  if (!cfg || !out) return fail(VX_ERR_ARG, "%s: null argument", fn);
+  if (cfg->struct_size != (int32_t)sizeof(Cfg)) return fail(VX_ERR_ARG, "%s: struct_size %d, expected %zu", fn, cfg->struct_size, sizeof(Cfg));
+  return VX_OK;
+}
 
 // Every entry point runs on its handle's device and leaves the caller's current device as it found it.
 struct DevGuard {
@@ -144,5 +158,65 @@ struct CallStage {
  private:
   char *host_ = nullptr, *dev_ = nullptr;
 };
+
+// The block most ragged calls stage: P pointer columns [max_batch] | tile0 [max_batch + 1] | K int columns [max_batch].  The one
+// place that knows the offsets; host and device accessors over the CallStage that holds the block at its start.
+struct RaggedTable {
+  RaggedTable(int max_batch, int n_ptr_cols, int n_int_cols) : mb_((size_t)max_batch), p_((size_t)n_ptr_cols), k_((size_t)n_int_cols) {}
+  size_t bytes() const { return int_off(k_); }
+  template <typename T> T* host_ptrs(const CallStage& st, int k) const { return st.host<T>(ptr_off(k)); }
+  template <typename T> T* dev_ptrs(const CallStage& st, int k) const { return st.dev<T>(ptr_off(k)); }
+  int* host_tile0(const CallStage& st) const { return st.host<int>(ptr_off(p_)); }
+  const int* dev_tile0(const CallStage& st) const { return st.dev<const int>(ptr_off(p_)); }
+  int* host_ints(const CallStage& st, int k) const { return st.host<int>(int_off(k)); }
+  const int* dev_ints(const CallStage& st, int k) const { return st.dev<const int>(int_off(k)); }
+
+ private:
+  size_t ptr_off(size_t k) const { return k * mb_ * sizeof(void*); }
+  size_t int_off(size_t k) const { return ptr_off(p_) + (mb_ + 1 + k * mb_) * sizeof(int); }
+  size_t mb_, p_, k_;
+};
+
+// The lazy device side of a handle: nothing touches a device until the first call that needs one; that call makes `Dev` (the
+// DevBufs and a CallStage named `stage`) on the device that is current then, and every later call runs there (ON_DEVICE).
+template <class Dev>
+struct LazyDev {
+  typedef Dev dev_type;
+  int device = -1;  // >= 0: `dev` is complete
+  std::unique_ptr<Dev> dev;
+};
+
+// The opening of a unit's *_init_device: the current device becomes the handle's, with a fresh Dev to fill.
+template <class H>
+int open_device(H* h, Site at = Site()) {
+  int dev = 0;
+  VXC(at.check(hipGetDevice(&dev), "hipGetDevice(&dev)"));
+  h->device = dev;
+  h->dev.reset(new typename H::dev_type());
+  return VX_OK;
+}
+
+template <class H, class Init>
+int ensure_device(H* h, Init init) {
+  if (h->device >= 0) return VX_OK;
+  const int rc = init(h);
+  if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
+    h->dev.reset();
+    h->device = -1;
+  }
+  return rc;
+}
+
+// vx_*_destroy: waits for the last call on the handle's device; a handle that never reached a device makes no HIP call.
+template <class H>
+void destroy_handle(H* h) {
+  if (!h) return;
+  if (h->device >= 0) {
+    DevGuard guard(h->device);
+    (void)h->dev->stage.drain();
+    h->dev.reset();
+  }
+  delete h;
+}
 
 }  // namespace vx

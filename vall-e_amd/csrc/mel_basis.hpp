@@ -1,4 +1,5 @@
-// The built-in Slaney mel basis, shared by the filterbank (fbank.hip) and its inverse (vocoder.hip).  Host code only.
+// The built-in Slaney mel basis and the window | cos | sin table of the 1024-point transform, shared by the filterbank (fbank.hip)
+// and its inverse (vocoder.hip).  Host code only.
 #pragma once
 #include <math.h>
 
@@ -38,6 +39,22 @@ inline std::vector<double> slaney_basis_f64(int sr, int n_mels, int n_bins, doub
 inline std::vector<float> slaney_basis(int sr, int n_mels, int n_bins, double fmin, double fmax) {
   const std::vector<double> w = slaney_basis_f64(sr, n_mels, n_bins, fmin, fmax);
   return std::vector<float>(w.begin(), w.end());
+}
+
+// The tables of the 1024-point transform both units run: periodic Hann [1024] | cos [1024] | sin [1024] of 2 pi j / 1024, in
+// fp64, rounded once.  The vocoder appends columns of its own.
+inline std::vector<float> hann_cos_sin_1024() {
+  std::vector<float> tab(3 * 1024);
+  const double pi = 3.14159265358979323846;
+  for (int j = 0; j < 1024; ++j) {
+    const double t = 2.0 * pi * (double)j / 1024.0;
+    tab[j] = (float)(0.5 - 0.5 * cos(t));
+    tab[1024 + j] = (float)cos(t);
+    tab[2048 + j] = (float)sin(t);
+  }
+  // the multiples of a quarter turn exactly (cos(pi / 2) in fp64 is 6e-17, not 0)
+  tab[1024 + 256] = 0.f; tab[1024 + 768] = 0.f; tab[2048 + 512] = 0.f;
+  return tab;
 }
 
 }  // namespace vx

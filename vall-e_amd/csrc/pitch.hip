@@ -18,46 +18,28 @@ using namespace vx;
 namespace {
 // Device side of a handle: made on the device that is current at the first call, dropped as a whole.
 struct PitchDev {
-  // per call, vx_pitch_track:   6 pointer arrays [max_batch each] | tile0 [max_batch + 1] | len | frames [max_batch each]
-  //           vx_pitch_compare: PitchPair [max_batch]
+  // per call, vx_pitch_track: track_table();  vx_pitch_compare: PitchPair [max_batch].  One block, sized to the larger.
   CallStage stage;
   DevBuf<double> sums;  // [max_batch][PITCH_NSUMS]
 };
 
-size_t stage_bytes(int max_batch) {
-  const size_t MB = (size_t)max_batch;
-  return std::max(6 * MB * sizeof(void*) + (3 * MB + 1) * sizeof(int), MB * sizeof(PitchPair));
-}
+enum { COL_WAV, COL_F0, COL_AP, COL_LAG, COL_VOICED, COL_DP, N_PTR_COLS };  // the track table's pointer columns
+enum { COL_LEN, COL_FRAMES, N_INT_COLS };                                   // and its int columns
+
+RaggedTable track_table(int max_batch) { return RaggedTable(max_batch, N_PTR_COLS, N_INT_COLS); }
 }  // namespace
 
-struct vx_pitch {
+struct vx_pitch : LazyDev<PitchDev> {
   int tau_min = 0, tau_max = 0, max_frames = 0, max_batch = 0;
   float threshold = 0.f;
-  int device = -1;  // >= 0: `dev` is complete
-  std::unique_ptr<PitchDev> dev;
 };
 
 namespace {
 
 int pitch_init_device(vx_pitch* h) {
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  h->device = dev;
-  h->dev.reset(new PitchDev());
-  VXC(h->dev->stage.init(stage_bytes(h->max_batch)));
-  VXC(h->dev->sums.alloc((size_t)h->max_batch * PITCH_NSUMS));
-  return VX_OK;
-}
-
-// A failed first use leaves the handle as it was before it.
-int pitch_ensure_device(vx_pitch* h) {
-  if (h->device >= 0) return VX_OK;
-  const int rc = pitch_init_device(h);
-  if (rc != VX_OK) {
-    h->dev.reset();
-    h->device = -1;
-  }
-  return rc;
+  VXC(open_device(h));
+  VXC(h->dev->stage.init(std::max(track_table(h->max_batch).bytes(), (size_t)h->max_batch * sizeof(PitchPair))));
+  return h->dev->sums.alloc((size_t)h->max_batch * PITCH_NSUMS);
 }
 
 // tau_min = floor(24000 / fmax), tau_max = ceil(24000 / fmin), in fp64 on the fp32 arguments.
@@ -104,30 +86,24 @@ int track_check(const char* who, int max_batch, int max_frames, const TrackCall&
 // Stages the call on `st` and launches; the caller has run track_check and begun the stage.
 int track_launch(CallStage& st, int max_batch, int tau_min, int tau_max, float threshold, const TrackCall& c, const std::vector<int>& tile0,
                  const std::vector<int>& frames, hipStream_t s) {
-  const size_t MB = (size_t)max_batch, P = MB * sizeof(void*);
-  const void** hp = st.host<const void*>();
-  int* hint = st.host<int>(6 * P);
-  for (int i = 0; i < c.n; ++i) {
-    hp[i] = c.wav[i];
-    hp[MB + i] = c.f0 ? c.f0[i] : nullptr;
-    hp[2 * MB + i] = c.ap ? c.ap[i] : nullptr;
-    hp[3 * MB + i] = c.lag ? c.lag[i] : nullptr;
-    hp[4 * MB + i] = c.voiced ? c.voiced[i] : nullptr;
-    hp[5 * MB + i] = c.dp ? c.dp[i] : nullptr;
-    hint[MB + 1 + i] = c.len[i];
-    hint[2 * MB + 1 + i] = frames[i];
-  }
-  memcpy(hint, tile0.data(), (c.n + 1) * sizeof(int));
-  VXC(st.upload(6 * P + (3 * MB + 1) * sizeof(int), s));
+  const RaggedTable t = track_table(max_batch);
+  auto put = [&](int k, auto src) {  // an output the caller does not want: null pointers
+    const void** hp = t.host_ptrs<const void*>(st, k);
+    for (int i = 0; i < c.n; ++i) hp[i] = src ? src[i] : nullptr;
+  };
+  put(COL_WAV, c.wav); put(COL_F0, c.f0); put(COL_AP, c.ap); put(COL_LAG, c.lag); put(COL_VOICED, c.voiced); put(COL_DP, c.dp);
+  memcpy(t.host_tile0(st), tile0.data(), (c.n + 1) * sizeof(int));
+  memcpy(t.host_ints(st, COL_LEN), c.len, c.n * sizeof(int));
+  memcpy(t.host_ints(st, COL_FRAMES), frames.data(), c.n * sizeof(int));
+  VXC(st.upload(t.bytes(), s));
   PitchArgs a{};
-  a.wav = st.dev<const float* const>();
-  a.f0 = st.dev<float* const>(P);
-  a.ap = st.dev<float* const>(2 * P);
-  a.lag = st.dev<int* const>(3 * P);
-  a.voiced = st.dev<unsigned char* const>(4 * P);
-  a.dp = st.dev<float* const>(5 * P);
-  const int* dint = st.dev<const int>(6 * P);
-  a.tile0 = dint; a.len = dint + MB + 1; a.frames = dint + 2 * MB + 1;
+  a.wav = t.dev_ptrs<const float* const>(st, COL_WAV);
+  a.f0 = t.dev_ptrs<float* const>(st, COL_F0);
+  a.ap = t.dev_ptrs<float* const>(st, COL_AP);
+  a.lag = t.dev_ptrs<int* const>(st, COL_LAG);
+  a.voiced = t.dev_ptrs<unsigned char* const>(st, COL_VOICED);
+  a.dp = t.dev_ptrs<float* const>(st, COL_DP);
+  a.tile0 = t.dev_tile0(st); a.len = t.dev_ints(st, COL_LEN); a.frames = t.dev_ints(st, COL_FRAMES);
   a.nseg = c.n; a.tau_min = tau_min; a.tau_max = tau_max; a.threshold = threshold;
   const unsigned grid = (unsigned)std::min(tile0[c.n], 1 << 16);
   pitch_track_kernel<<<grid, PITCH_WG, 0, s>>>(a);
@@ -138,9 +114,7 @@ int track_launch(CallStage& st, int max_batch, int tau_min, int tau_max, float t
 }  // namespace
 
 extern "C" int vx_pitch_create(const vx_pitch_config* cfg, vx_pitch** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_pitch_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_pitch_config))
-    return fail(VX_ERR_ARG, "vx_pitch_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_pitch_config));
+  VXC(create_head("vx_pitch_create", cfg, out));
   if (cfg->max_batch < 1) return fail(VX_ERR_ARG, "vx_pitch_create: max_batch = %d", cfg->max_batch);
   if (cfg->max_frames < 1) return fail(VX_ERR_ARG, "vx_pitch_create: max_frames = %d", cfg->max_frames);
   if (!(cfg->threshold > 0.f) || !isfinite(cfg->threshold))
@@ -159,15 +133,7 @@ extern "C" int vx_pitch_create(const vx_pitch_config* cfg, vx_pitch** out) {
   return VX_OK;
 }
 
-extern "C" void vx_pitch_destroy(vx_pitch* h) {
-  if (!h) return;
-  if (h->device >= 0) {
-    DevGuard g(h->device);
-    (void)h->dev->stage.drain();
-    h->dev.reset();
-  }
-  delete h;
-}
+extern "C" void vx_pitch_destroy(vx_pitch* h) { destroy_handle(h); }
 
 extern "C" int vx_pitch_lag_range(const vx_pitch* h, int32_t* tau_min, int32_t* tau_max) {
   if (!h || !tau_min || !tau_max) return fail(VX_ERR_ARG, "vx_pitch_lag_range: null argument");
@@ -183,9 +149,8 @@ extern "C" int vx_pitch_track(vx_pitch* h, int32_t n, const float* const* wav, c
   std::vector<int> tile0, frames;
   VXC(track_check("vx_pitch_track", h->max_batch, h->max_frames, c, tile0, frames));
   if (tile0[n] == 0) return VX_OK;  // no utterance has a frame: nothing to write
-  VXC(pitch_ensure_device(h));
-  DevGuard g(h->device);
-  HIPC(g.err);
+  VXC(ensure_device(h, pitch_init_device));
+  ON_DEVICE(h->device);
   PitchDev& d = *h->dev;
   hipStream_t s = (hipStream_t)stream;
   VXC(d.stage.begin(s));
@@ -211,9 +176,8 @@ extern "C" int vx_pitch_compare(vx_pitch* h, int32_t n, const float* const* f0_a
     p.fa = f0_a[i]; p.fb = f0_b[i]; p.path = path[i];
     p.Ta = Ta[i]; p.Tb = Tb[i]; p.plen = path_len[i]; p.pad_ = 0;
   }
-  VXC(pitch_ensure_device(h));
-  DevGuard g(h->device);
-  HIPC(g.err);
+  VXC(ensure_device(h, pitch_init_device));
+  ON_DEVICE(h->device);
   PitchDev& d = *h->dev;
   hipStream_t s = (hipStream_t)stream;
   VXC(d.stage.begin(s));
@@ -240,7 +204,7 @@ extern "C" int vx_op_pitch_diff(float fmin_hz, float fmax_hz, const float* wav, 
   if (tile0[1] == 0) return VX_OK;
   hipStream_t s = (hipStream_t)stream;
   CallStage st;
-  VXC(st.init(stage_bytes(1)));
+  VXC(st.init(track_table(1).bytes()));
   VXC(track_launch(st, 1, tau_min, tau_max, 1.f, c, tile0, frames, s));
   HIPC(hipStreamSynchronize(s));
   return VX_OK;

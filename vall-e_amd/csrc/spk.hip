@@ -122,9 +122,7 @@ extern "C" int64_t vx_spk_frames(const vx_spk* g, int64_t n_samples) {
 extern "C" int64_t vx_spk_min_samples(const vx_spk* g) { return !g ? -1 : (int64_t)g->m.min_samples; }
 
 extern "C" int vx_spk_create(const vx_spk_config* cfg, vx_spk** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_spk_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_spk_config))
-    return fail(VX_ERR_ARG, "vx_spk_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_spk_config));
+  VXC(create_head("vx_spk_create", cfg, out));
   const vx_spk_config& c = *cfg;
   const char* what = "vx_spk_create";
   const W2vGeom q = w2v_geom(c, 1, (c.flags & VX_SPK_KEEP_TAPS) != 0);
@@ -256,8 +254,7 @@ extern "C" int vx_spk_embed(vx_spk* g, int32_t n, const float* const* wav, const
   const auto t_begin = std::chrono::steady_clock::now();
   const int NT = n_tables(c);
   VXC(ensure_device(g, [NT](vx_spk* h) { return w2v_init_device(h, NT); }));
-  DevGuard guard(g->device);
-  HIPC(guard.err);
+  ON_DEVICE(g->device);
   W2vRun x{};
   VXC(w2v_stage_begin(g, NT, n, wav, n_samples, (hipStream_t)stream, x));
   for (int i = 0; i < n; ++i) {

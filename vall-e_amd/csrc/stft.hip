@@ -32,12 +32,10 @@ struct StftDev {
 };
 }  // namespace
 
-struct vx_stft {
+struct vx_stft : LazyDev<StftDev> {
   int n_res = 0, max_samples = 0, max_batch = 0, max_nfft = 0;
   Res res[STFT_MAX_RES];
   float eps = 0.f;
-  int device = -1;  // >= 0: `dev` is complete
-  std::unique_ptr<StftDev> dev;
 };
 
 namespace {
@@ -51,7 +49,8 @@ long long tiles_of(const Res& r, long long frames, bool compare) {
   return (frames + ft - 1) / ft;
 }
 
-// Byte offsets of the staging block.
+// Byte offsets of the staging block.  Not a RaggedTable: tile0 | frames repeat per resolution, and tbeg, tend and the fp64 cells
+// follow them.
 struct Layout {
   size_t ptr_y, ints, res0, res_stride, tbeg, tend, cells, bytes;
   Layout(int max_batch, int n_res) {
@@ -68,10 +67,7 @@ struct Layout {
 };
 
 int stft_init_device(vx_stft* h) {
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  h->device = dev;
-  h->dev.reset(new StftDev());
+  VXC(open_device(h));
   StftDev& d = *h->dev;
   VXC(d.stage.init(Layout(h->max_batch, h->n_res).bytes));
   long long tiles = 0;
@@ -90,17 +86,6 @@ int stft_init_device(vx_stft* h) {
   VXC(d.ws.alloc((size_t)tiles * 3));
   VXC(d.sums.alloc((size_t)h->max_batch * h->n_res * 4));
   return VX_OK;
-}
-
-// A failed first use leaves the handle as it was before it.
-int stft_ensure_device(vx_stft* h) {
-  if (h->device >= 0) return VX_OK;
-  const int rc = stft_init_device(h);
-  if (rc != VX_OK) {
-    h->dev.reset();
-    h->device = -1;
-  }
-  return rc;
 }
 
 StftArgs args_of(const vx_stft* h, int r, int n, bool compare, const Layout& lay) {
@@ -128,9 +113,7 @@ StftArgs args_of(const vx_stft* h, int r, int n, bool compare, const Layout& lay
 }  // namespace
 
 extern "C" int vx_stft_create(const vx_stft_config* cfg, vx_stft** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_stft_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_stft_config))
-    return fail(VX_ERR_ARG, "vx_stft_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_stft_config));
+  VXC(create_head("vx_stft_create", cfg, out));
   if (cfg->max_batch < 1) return fail(VX_ERR_ARG, "vx_stft_create: max_batch = %d", cfg->max_batch);
   if (cfg->max_samples < 1) return fail(VX_ERR_ARG, "vx_stft_create: max_samples = %d", cfg->max_samples);
   if (!(cfg->eps > 0.f) || !isfinite(cfg->eps)) return fail(VX_ERR_ARG, "vx_stft_create: eps = %g (positive and finite)", cfg->eps);
@@ -169,15 +152,7 @@ extern "C" int vx_stft_create(const vx_stft_config* cfg, vx_stft** out) {
   return VX_OK;
 }
 
-extern "C" void vx_stft_destroy(vx_stft* h) {
-  if (!h) return;
-  if (h->device >= 0) {
-    DevGuard g(h->device);
-    (void)h->dev->stage.drain();
-    h->dev.reset();
-  }
-  delete h;
-}
+extern "C" void vx_stft_destroy(vx_stft* h) { destroy_handle(h); }
 
 extern "C" int vx_stft_frames(const vx_stft* h, int32_t res, int32_t n_samples) {
   if (!h || res < 0 || res >= h->n_res || n_samples < 0) return 0;
@@ -199,9 +174,8 @@ extern "C" int vx_stft_compare(vx_stft* h, int32_t n, const float* const* pred, 
     if (L > h->max_samples) return fail(VX_ERR_CAPACITY, "vx_stft_compare: pair %d: common length %d > max_samples %d", i, L, h->max_samples);
     len[i] = L;
   }
-  VXC(stft_ensure_device(h));
-  DevGuard g(h->device);
-  HIPC(g.err);
+  VXC(ensure_device(h, stft_init_device));
+  ON_DEVICE(h->device);
   StftDev& d = *h->dev;
   hipStream_t s = (hipStream_t)stream;
   const Layout lay(h->max_batch, h->n_res);
@@ -264,9 +238,8 @@ extern "C" int vx_stft_magnitude(vx_stft* h, int32_t res, int32_t n, const float
     if (n_samples[i] > h->max_samples)
       return fail(VX_ERR_CAPACITY, "vx_stft_magnitude: signal %d: %d samples > max_samples %d", i, n_samples[i], h->max_samples);
   }
-  VXC(stft_ensure_device(h));
-  DevGuard g(h->device);
-  HIPC(g.err);
+  VXC(ensure_device(h, stft_init_device));
+  ON_DEVICE(h->device);
   StftDev& d = *h->dev;
   hipStream_t s = (hipStream_t)stream;
   const Layout lay(h->max_batch, h->n_res);

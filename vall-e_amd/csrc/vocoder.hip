@@ -24,24 +24,26 @@ struct VocDev {
   // one block, grown when a larger call arrives: mag [cap][513] | ang [cap][513][2] | tprev [cap][513][2] | frames [cap][1024]
   DevBuf<float> ws;
   long cap = 0;
-  // per call: logmel | init | wav | phase pointers [max_batch each] | tile0 [max_batch + 1] | frames | fr0 [max_batch each]
-  CallStage stage;
+  CallStage stage;  // per call: a RaggedTable of logmel | init | wav | phase pointers, tile0, frames | fr0
 };
 constexpr long VOC_WS_ROW = VOC_BINS * 5 + VOC_NFFT;  // floats per frame of the workspace
+
+enum { COL_LOGMEL, COL_INIT, COL_WAV, COL_PHASE, N_PTR_COLS };  // the staged block's pointer columns
+enum { COL_FRAMES, COL_FR0, N_INT_COLS };                       // and its int columns
 }  // namespace
 
-struct vx_vocoder {
+struct vx_vocoder : LazyDev<VocDev> {
   int n_mels = 0, max_batch = 0;
   long max_total_frames = 0;
   float env_floor = 0.f;
   std::vector<float> pinv;  // [513][n_mels]
   std::vector<float> tab;
   bool pinv_dirty = true;   // the device copy is older than `pinv`
-  int device = -1;          // >= 0: `dev` is complete
-  std::unique_ptr<VocDev> dev;
 };
 
 namespace {
+
+RaggedTable call_table(const vx_vocoder* v) { return RaggedTable(v->max_batch, N_PTR_COLS, N_INT_COLS); }
 
 // P = B^T (B B^T)^-1 for B (M x 513), in fp64 by Cholesky of B B^T, rounded once: (513 x M).  False when B B^T has no factor
 // (a pivot that is not positive, or below 1e-12 of its diagonal entry: the rows of B are linearly dependent to working accuracy).
@@ -89,15 +91,11 @@ bool mel_inverse(const std::vector<double>& B, int M, std::vector<float>& P) {
 
 // First use: the tables go to the current device.
 int voc_init_device(vx_vocoder* v) {
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  v->device = dev;
-  v->dev.reset(new VocDev());
+  VXC(open_device(v));
   VocDev& d = *v->dev;
-  const size_t MB = (size_t)v->max_batch;
   VXC(d.tab.alloc(VOC_TAB));
   VXC(d.pinv_t.alloc((size_t)v->n_mels * VOC_BINS));
-  VXC(d.stage.init(4 * MB * sizeof(void*) + (3 * MB + 1) * sizeof(int)));
+  VXC(d.stage.init(call_table(v).bytes()));
   HIPC(hipMemcpy(d.tab.get(), v->tab.data(), VOC_TAB * sizeof(float), hipMemcpyHostToDevice));
   v->pinv_dirty = true;
   return VX_OK;
@@ -136,16 +134,8 @@ int voc_synthesize(vx_vocoder* v, const char* who, int32_t n, const float* const
       return fail(VX_ERR_CAPACITY, "%s: %ld frames up to utterance %d > max_total_frames %ld", who, total, i, v->max_total_frames);
   }
   if (total == 0) return VX_OK;  // no utterance has a frame: nothing to write
-  if (v->device < 0) {
-    const int rc = voc_init_device(v);
-    if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
-      v->dev.reset();
-      v->device = -1;
-      return rc;
-    }
-  }
-  DevGuard g(v->device);
-  HIPC(g.err);
+  VXC(ensure_device(v, voc_init_device));
+  ON_DEVICE(v->device);
   VocDev& d = *v->dev;
   hipStream_t s = (hipStream_t)stream;
   if (v->pinv_dirty) {
@@ -163,29 +153,22 @@ int voc_synthesize(vx_vocoder* v, const char* who, int32_t n, const float* const
   const int tile = (total + VOC_TILE - 1) / VOC_TILE >= 2L * vx_cu_count() ? VOC_TILE : VOC_TILE_SMALL;
   for (int i = 0; i < n; ++i) tile0[i + 1] = tile0[i] + (n_frames[i] + tile - 1) / tile;
   VXC(d.stage.begin(s));
-  const size_t MB = (size_t)v->max_batch;
-  const float** hin = d.stage.host<const float*>();
-  const float** hinit = d.stage.host<const float*>(MB * sizeof(void*));
-  float** hwav = d.stage.host<float*>(2 * MB * sizeof(void*));
-  float** hph = d.stage.host<float*>(3 * MB * sizeof(void*));
-  int* hint = d.stage.host<int>(4 * MB * sizeof(void*));
-  for (int i = 0; i < n; ++i) {
-    hin[i] = logmel[i];
-    hinit[i] = init ? init[i] : nullptr;
-    hwav[i] = wav_out[i];
-    hph[i] = phase_out ? phase_out[i] : nullptr;
-    hint[MB + 1 + i] = n_frames[i];
-    hint[2 * MB + 1 + i] = fr0[i];
-  }
-  memcpy(hint, tile0.data(), (n + 1) * sizeof(int));
-  VXC(d.stage.upload(d.stage.bytes, s));
+  const RaggedTable t = call_table(v);
+  auto put = [&](int k, const float* const* src) {  // an optional column the caller left out: null pointers
+    const float** hp = t.host_ptrs<const float*>(d.stage, k);
+    for (int i = 0; i < n; ++i) hp[i] = src ? src[i] : nullptr;
+  };
+  put(COL_LOGMEL, logmel); put(COL_INIT, init); put(COL_WAV, wav_out); put(COL_PHASE, phase_out);
+  memcpy(t.host_tile0(d.stage), tile0.data(), (n + 1) * sizeof(int));
+  memcpy(t.host_ints(d.stage, COL_FRAMES), n_frames, n * sizeof(int));
+  memcpy(t.host_ints(d.stage, COL_FR0), fr0.data(), n * sizeof(int));
+  VXC(d.stage.upload(t.bytes(), s));
   VocArgs a{};
-  a.logmel = d.stage.dev<const float* const>();
-  a.init = d.stage.dev<const float* const>(MB * sizeof(void*));
-  a.wav = d.stage.dev<float* const>(2 * MB * sizeof(void*));
-  a.phase = d.stage.dev<float* const>(3 * MB * sizeof(void*));
-  const int* dint = d.stage.dev<const int>(4 * MB * sizeof(void*));
-  a.tile0 = dint; a.frames = dint + MB + 1; a.fr0 = dint + 2 * MB + 1;
+  a.logmel = t.dev_ptrs<const float* const>(d.stage, COL_LOGMEL);
+  a.init = t.dev_ptrs<const float* const>(d.stage, COL_INIT);
+  a.wav = t.dev_ptrs<float* const>(d.stage, COL_WAV);
+  a.phase = t.dev_ptrs<float* const>(d.stage, COL_PHASE);
+  a.tile0 = t.dev_tile0(d.stage); a.frames = t.dev_ints(d.stage, COL_FRAMES); a.fr0 = t.dev_ints(d.stage, COL_FR0);
   a.tab = d.tab.get(); a.pinv_t = d.pinv_t.get();
   a.mag = d.ws.get();
   a.ang = a.mag + d.cap * VOC_BINS;
@@ -211,9 +194,7 @@ int voc_synthesize(vx_vocoder* v, const char* who, int32_t n, const float* const
 extern "C" int64_t vx_vocoder_samples(int64_t n_frames) { return n_frames < 0 ? 0 : n_frames * VOC_HOP; }
 
 extern "C" int vx_vocoder_create(const vx_vocoder_config* cfg, vx_vocoder** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_vocoder_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_vocoder_config))
-    return fail(VX_ERR_ARG, "vx_vocoder_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_vocoder_config));
+  VXC(create_head("vx_vocoder_create", cfg, out));
   if (cfg->max_batch < 1) return fail(VX_ERR_ARG, "vx_vocoder_create: max_batch = %d", cfg->max_batch);
   if (cfg->max_total_frames < 1) return fail(VX_ERR_ARG, "vx_vocoder_create: max_total_frames = %d", cfg->max_total_frames);
   if (!(cfg->env_floor > 0.f) || !isfinite(cfg->env_floor))
@@ -234,31 +215,19 @@ extern "C" int vx_vocoder_create(const vx_vocoder_config* cfg, vx_vocoder** out)
   if (!mel_inverse(slaney_basis_f64(cfg->sample_rate, cfg->n_mels, VOC_BINS, cfg->fmin, cfg->fmax), cfg->n_mels, v->pinv))
     return fail(VX_ERR_UNSUPPORTED, "vx_vocoder_create: the built-in basis of %d filters in %g .. %g Hz has linearly dependent "
                 "filters (B B^T has no Cholesky factor)", cfg->n_mels, cfg->fmin, cfg->fmax);
+  v->tab = hann_cos_sin_1024();
   v->tab.resize(VOC_TAB);
   const double pi = 3.14159265358979323846;
-  for (int j = 0; j < 1024; ++j) {
-    const double t = 2.0 * pi * (double)j / 1024.0, w = 0.5 - 0.5 * cos(t);  // periodic Hann
-    v->tab[j] = (float)w;
-    v->tab[1024 + j] = (float)cos(t);
-    v->tab[2048 + j] = (float)sin(t);
+  for (int j = 0; j < 1024; ++j) {  // the synthesis window and the envelope's term, from the window in fp64
+    const double w = 0.5 - 0.5 * cos(2.0 * pi * (double)j / 1024.0);
     v->tab[3072 + j] = (float)(w / 1024.0);
     v->tab[4096 + j] = (float)(w * w);
   }
-  // the multiples of a quarter turn exactly (cos(pi / 2) in fp64 is 6e-17, not 0)
-  v->tab[1024 + 256] = 0.f; v->tab[1024 + 768] = 0.f; v->tab[2048 + 512] = 0.f;
   *out = v.release();
   return VX_OK;
 }
 
-extern "C" void vx_vocoder_destroy(vx_vocoder* v) {
-  if (!v) return;
-  if (v->device >= 0) {
-    DevGuard g(v->device);
-    (void)v->dev->stage.drain();
-    v->dev.reset();
-  }
-  delete v;
-}
+extern "C" void vx_vocoder_destroy(vx_vocoder* v) { destroy_handle(v); }
 
 extern "C" int vx_vocoder_set_mel_basis(vx_vocoder* v, const float* basis) {
   if (!v || !basis) return fail(VX_ERR_ARG, "vx_vocoder_set_mel_basis: null argument");

@@ -1,7 +1,7 @@
 // Host side shared by the units built on a transformer speech encoder (spk.hip, asr.hip, whisper.hip), on top of spk_host.hpp's
 // leaf pieces.  Two levels:
 //   - what every such handle has (SpeechHandle): the key helpers, the stacked q|k|v and encoder-layer packing (EncLayer), the
-//     attention triple, the pre-norm layer loop, and the first-use / destroy / read scaffolding;
+//     attention triple, the pre-norm layer loop, and the first-use / read scaffolding over host.hpp's LazyDev;
 //   - the Wav2Vec2 backbone of spk.hip and asr.hip (W2vModel): its geometry, create-time checks, key table, packing, workspace
 //     plan, call staging and the launches from the waveform to the positional convolution.
 // Everything here has internal linkage, like spk_host.hpp.
@@ -34,15 +34,12 @@ struct SpeechDev {
 };
 
 template <class Dev>
-struct SpeechHandle {
-  typedef Dev dev_type;
+struct SpeechHandle : LazyDev<Dev> {
   std::map<std::string, HostW> w;
   bool finalized = false;
   std::vector<float> packed;  // filled by *_finalize
   bool bf16 = false;               // the bf16 encoder mode (set at create)
   std::vector<uint16_t> packed16;  // its encoder matrices, rounded once by *_finalize; `packed` does not hold them
-  int device = -1;            // >= 0: `dev` is complete
-  std::unique_ptr<Dev> dev;
   W2vCallState call;
 };
 
@@ -178,12 +175,10 @@ void finalize_end(G* g) {
 }
 
 // The part of *_init_device every handle has: the device, the weights, the workspace and the stage.
-template <class G, class Dev>
-int init_device(G* g, Dev* fresh, size_t ws_floats, size_t stage_bytes) {
-  g->dev.reset(fresh);
-  int dev = 0;
-  HIPC(hipGetDevice(&dev));
-  g->device = dev;
+template <class G>
+int init_device(G* g, size_t ws_floats, size_t stage_bytes) {
+  VXC(open_device(g));
+  auto* fresh = g->dev.get();
   VXC(fresh->w.alloc(g->packed.size() + 4));
   HIPC(hipMemcpy(fresh->w.get(), g->packed.data(), g->packed.size() * sizeof(float), hipMemcpyHostToDevice));
   if (!g->packed16.empty()) {
@@ -192,28 +187,6 @@ int init_device(G* g, Dev* fresh, size_t ws_floats, size_t stage_bytes) {
   }
   VXC(fresh->ws.alloc(ws_floats + 4));
   return fresh->stage.init(stage_bytes);
-}
-
-template <class G, class Init>
-int ensure_device(G* g, Init init) {
-  if (g->device >= 0) return VX_OK;
-  const int rc = init(g);
-  if (rc != VX_OK) {  // a failed first use leaves the handle as it was before it
-    g->dev.reset();
-    g->device = -1;
-  }
-  return rc;
-}
-
-template <class G>
-void destroy_handle(G* g) {
-  if (!g) return;
-  if (g->device >= 0) {
-    DevGuard guard(g->device);
-    (void)g->dev->stage.drain();
-    g->dev.reset();
-  }
-  delete g;
 }
 
 // The head of vx_*_read (`what` is the entry point's prefix, `call` the name of the call whose taps are read).
@@ -230,8 +203,7 @@ template <class G>
 int read_rows(G* g, const char* what, const char* name, int utt, size_t base, long lo, long rows, int width, float* dst, int64_t n_floats) {
   if (n_floats != (int64_t)rows * width)
     return fail(VX_ERR_ARG, "%s_read: %s of utterance %d is %ld x %d floats, not %lld", what, name, utt, rows, width, (long long)n_floats);
-  DevGuard guard(g->device);
-  HIPC(guard.err);
+  ON_DEVICE(g->device);
   HIPC(hipStreamSynchronize(g->call.last_stream));
   HIPC(hipMemcpy(dst, g->dev->ws.get() + base + (size_t)lo * width, (size_t)rows * width * sizeof(float), hipMemcpyDeviceToHost));
   return VX_OK;
@@ -606,9 +578,8 @@ size_t w2v_stage_bytes(const W2vGeom& c, int n_tables) {
 
 template <class G>
 int w2v_init_device(G* g, int n_tables) {
-  auto* d = new typename G::dev_type();
-  VXC(init_device(g, d, g->m.p.total, w2v_stage_bytes(g->m.q, n_tables)));
-  return d->partial.alloc(g->m.p.partial + 2);
+  VXC(init_device(g, g->m.p.total, w2v_stage_bytes(g->m.q, n_tables)));
+  return g->dev->partial.alloc(g->m.p.partial + 2);
 }
 
 // One call on the backbone: the handle's device state, the staged tables and their host copy.

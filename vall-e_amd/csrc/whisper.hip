@@ -111,7 +111,7 @@ size_t stage_bytes(const vx_wsp* g) {
 }
 
 int wsp_init_device(vx_wsp* g) {
-  VXC(init_device(g, new WspDev(), g->plan.total, stage_bytes(g)));
+  VXC(init_device(g, g->plan.total, stage_bytes(g)));
   WspDev& d = *g->dev;
   const size_t MB = (size_t)g->cfg.max_batch;
   VXC(d.suppress.alloc(g->suppress.size() + 4));
@@ -231,9 +231,7 @@ int run_step(const CallCtx& x, const WspState& st, const WspHeadArgs& head) {
 }  // namespace
 
 extern "C" int vx_wsp_create(const vx_wsp_config* cfg, vx_wsp** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_wsp_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_wsp_config))
-    return fail(VX_ERR_ARG, "vx_wsp_create: struct_size %d, expected %zu", cfg->struct_size, sizeof(vx_wsp_config));
+  VXC(create_head("vx_wsp_create", cfg, out));
   const vx_wsp_config& c = *cfg;
   if (c.n_mels < 1 || c.d_model < 1 || c.vocab < 1)
     return fail(VX_ERR_ARG, "vx_wsp_create: num_mel_bins %d, d_model %d, vocab_size %d", c.n_mels, c.d_model, c.vocab);
@@ -437,8 +435,7 @@ extern "C" int vx_wsp_recognize(vx_wsp* g, int32_t n, const float* const* wav, c
   }
   const auto t_begin = std::chrono::steady_clock::now();
   VXC(ensure_device(g, wsp_init_device));
-  DevGuard guard(g->device);
-  HIPC(guard.err);
+  ON_DEVICE(g->device);
   WspDev& dv = *g->dev;
   hipStream_t s = (hipStream_t)stream;
   VXC(dv.stage.begin(s));
@@ -519,8 +516,7 @@ extern "C" int vx_wsp_read(vx_wsp* g, const char* name, int32_t utt, float* dst,
   const bool keep = (c.flags & VX_WSP_KEEP_TAPS) != 0;
   if (nm == "logits") {  // the raw rows of the generated steps, one copy a step
     if (!keep) return fail(VX_ERR_STATE, "vx_wsp_read: logits needs VX_WSP_KEEP_TAPS at create");
-    DevGuard guard(g->device);
-    HIPC(guard.err);
+    ON_DEVICE(g->device);
     HIPC(hipStreamSynchronize(g->call.last_stream));
     int count = 0;
     HIPC(hipMemcpy(&count, g->dev->state.get() + 2 * (size_t)c.max_batch + utt, sizeof(int), hipMemcpyDeviceToHost));
@@ -558,8 +554,7 @@ extern "C" int vx_wsp_get_timings(vx_wsp* g, double* out, int32_t n) {
   double v[7] = {g->call.last_ms, (double)(g->plan.total * sizeof(float)),
                  (double)(g->packed.size() * sizeof(float) + g->packed16.size() * sizeof(uint16_t)), g->last_steps, 0.0, 0.0, 0.0};
   if (n > 4 && g->device >= 0 && g->call.last_n > 0) {  // the device times of the last call: waits for it
-    DevGuard guard(g->device);
-    HIPC(guard.err);
+    ON_DEVICE(g->device);
     HIPC(hipEventSynchronize(g->dev->ev[3]));
     for (int i = 0; i < 3; ++i) {
       float ms = 0.f;
