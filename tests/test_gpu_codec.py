@@ -6,6 +6,7 @@ tests/encodec_ref.py.
 * the whole decoder at T = 1, 2, 6, 7, 75, 753, 1505 (weights from the seeded generator) and at the committed narrow fixture;
 * a ragged batch against each utterance decoded alone (bitwise), two identical calls (bitwise); a batch whose up-sampling half
   spans several utterance groups; the captured LSTM chain against plain launches (bitwise); a decode on a side stream;
+  two handles alive at once, destroyed in interleaved order, against a lone one (bitwise);
 * VALLE.inference -> decode end to end.
 
 Tolerance (encodec_ref.TOL_FACTOR = 4): 4 x the fp32 floor, the floor being the same restatement run in torch fp32 on the CPU
@@ -262,6 +263,45 @@ def test_decode_follows_the_callers_stream():
         host = got.to("cpu", non_blocking=False)
     side.synchronize()
     assert torch.equal(host, want) and torch.isfinite(junk).all()
+
+
+def test_two_handles_alive_at_once_decode_as_a_lone_one():
+    """Every handle owns its device side as a whole: two narrow handles, one of them with the encoder, are finalised before either
+    is used, decode T = 1 and T = 7 in turn (an encode between), and are destroyed in interleaved order with a third made
+    in between.  Every decode is bitwise that of a handle that was alone on the device."""
+    _lib()
+    import encodec_enc_ref as E
+    from valle_amd.codec import CodecConfig, EncodecDecoder
+
+    geo = R.NARROW
+    sd = E.make_enc_weights(geo, 5)
+    dec_sd = {k: v for k, v in sd.items() if not k.startswith("encoder.")}
+
+    def make(encoder):
+        d = EncodecDecoder(CodecConfig(hidden=geo.hidden, filters=geo.filters, codebook_size=geo.codebook_size, n_codebooks=geo.n_codebooks),
+                           max_frames=8, max_batch=2, encoder=encoder)
+        d.load_state_dict(sd if encoder else dec_sd, strict=True)
+        d.to(DEV).handle()  # created and finalised here
+        return d
+
+    codes = {T: R.make_codes(geo, 8, T, 20 + T) for T in (1, 7)}
+    lone = make(False)
+    want = {T: lone.decode(c).clone() for T, c in codes.items()}
+    lone.close()
+    assert all(w.shape == (1, 1, geo.hop * T) and torch.isfinite(w).all() for T, w in want.items())
+
+    a, b = make(False), make(True)
+    assert torch.equal(a.decode(codes[1]), want[1]) and torch.equal(b.decode(codes[7]), want[7])
+    enc = b.encode_batch([E.make_wave(geo.hop * 7, 3).to(DEV)])
+    assert enc[0].shape[-2:] == (geo.n_codebooks, 7)
+    assert torch.equal(b.decode(codes[1]), want[1]) and torch.equal(a.decode(codes[7]), want[7])
+    a.close()
+    assert torch.equal(b.decode(codes[7]), want[7])
+    c = make(False)
+    assert torch.equal(c.decode(codes[7]), want[7]) and torch.equal(b.decode(codes[1]), want[1])
+    b.close()
+    assert torch.equal(c.decode(codes[1]), want[1])
+    c.close()
 
 
 def test_inference_to_waveform_end_to_end():

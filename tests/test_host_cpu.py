@@ -6,7 +6,8 @@ fails: the small handles (vx_fbank, vx_resampler, vx_dtw, vx_gan here; vx_pitch,
 come out of that failed first use as they went in - the same answer a second time, a clean destroy - and the op-level entries
 must give their scratch back.  Where a GPU is present the same calls succeed (the buffers are then real device memory), so either
 return code is accepted and the message is checked only on failure.  Every handle also closes without ever having reached a
-device, and every *_create on the shared head (create_head) refuses a null argument and a wrong struct_size in the same words."""
+device, every *_create on the shared head (create_head) refuses a null argument and a wrong struct_size in the same words, and
+every *_set_weight on the shared weight table (csrc/weights_host.hpp) refuses an unknown key and a wrong shape in the same words."""
 import ctypes as C
 
 import pytest
@@ -123,7 +124,8 @@ def test_create_heads_refuse_in_the_same_words(lib):
     """VX_ERR_ARG, and the entry point's own name in front of the two texts of create_head."""
     for name, cfg_t in (("vx_fbank_create", E.VxFbankConfig), ("vx_dtw_create", E.VxDtwConfig), ("vx_pitch_create", E.VxPitchConfig),
                         ("vx_stft_create", E.VxStftConfig), ("vx_vocoder_create", E.VxVocoderConfig), ("vx_gan_create", E.VxGanConfig),
-                        ("vx_spk_create", E.VxSpkConfig), ("vx_asr_create", E.VxAsrConfig), ("vx_wsp_create", E.VxWspConfig)):
+                        ("vx_spk_create", E.VxSpkConfig), ("vx_asr_create", E.VxAsrConfig), ("vx_wsp_create", E.VxWspConfig),
+                        ("vx_codec_create", E.VxCodecConfig)):
         create, size, h = getattr(lib, name), C.sizeof(cfg_t), C.c_void_p()
         c = cfg_t()
         c.struct_size = size
@@ -133,6 +135,45 @@ def test_create_heads_refuse_in_the_same_words(lib):
         assert create(C.byref(c), C.byref(h)) == VX_ERR_ARG
         assert lib.vx_last_error().decode() == "%s: struct_size %d, expected %d" % (name, size + 4, size)
         assert not h.value
+
+
+def _weighted_handles():
+    """prefix -> (owner of an unfinalised handle, its key table) for the five handles on the shared weight table (weights_host.hpp)."""
+    import asr_cases as AC
+    import spk_cases as SC
+    import whisper_cases as WC
+    from valle_amd import asr, codec, ganvoc, spk, whisper
+
+    dec = codec.EncodecDecoder(max_frames=8)
+    dec.handle(finalize=False)
+    gan = GanVocoder(GR.GEOMETRIES["g1_snakebeta"], max_batch=2, max_total_frames=50)
+    enc = spk.SpeakerEncoder(SC.config("tiny_wavlm"), max_batch=2, max_seconds=1.0)
+    ctc = asr.SpeechRecognizer(AC.config("tiny_group"), AC.vocab("tiny_group"), max_batch=2, max_seconds=1.0)
+    wsp = whisper.WhisperRecognizer(WC.config("A"), max_batch=2)
+    return {"vx_codec": (dec, codec.expected_keys(dec.cfg)), "vx_gan": (gan, ganvoc.expected_keys(gan.config)),
+            "vx_spk": (enc, spk.expected_keys(enc.config, enc.attention)), "vx_asr": (ctc, asr.expected_keys(ctc.config)),
+            "vx_wsp": (wsp, whisper.expected_keys(wsp.config))}
+
+
+def test_set_weight_entries_refuse_in_the_same_words(lib):
+    """VX_ERR_WEIGHTS for an unknown key and for a wrong shape - a wrong extent and a wrong rank - from all five *_set_weight; the
+    shape text names the shape received and the shape expected.  The right shape is then taken."""
+    fmt = lambda s: ", ".join(str(int(v)) for v in s)
+    for prefix, (owner, keys) in _weighted_handles().items():
+        put = getattr(lib, prefix + "_set_weight")
+        key, shape = next((k, tuple(int(v) for v in s)) for k, s in keys.items() if len(s) >= 2)
+        buf = torch.zeros(shape[:-1] + (shape[-1] + 1,))
+
+        def rc_of(k, s):
+            return put(owner._h, k.encode(), buf.data_ptr(), (C.c_int64 * len(s))(*s), len(s))
+
+        assert rc_of(key + "_g", shape) == 6, prefix
+        assert lib.vx_last_error().decode() == "unknown key %s_g" % key, prefix
+        for wrong in (shape[:-1] + (shape[-1] + 1,), shape[:-1], shape + (1,)):
+            assert rc_of(key, wrong) == 6, (prefix, wrong)
+            assert lib.vx_last_error().decode() == "%s: shape (%s), expected (%s)" % (key, fmt(wrong), fmt(shape)), (prefix, wrong)
+        assert rc_of(key, shape) == 0, prefix
+        owner.close()
 
 
 def test_op_entries_name_the_failing_call_and_their_unit(lib):

@@ -1,78 +1,131 @@
-// EnCodec-24 kHz decoder and encoder behind the C ABI (include/vallex.h, vx_codec_*): weights, workspace and the launch
-// sequences of codec_kernels.hpp.  A handle of its own: the codec has its own weights and lifetime and runs without a VALL-E engine.
-// At the end of the file: the sample-rate converter in front of the encoder (vx_resampler_*), a handle without weights, its ragged
-// calls staged through CallStage (host.hpp); the codec handle keeps its own stream protocol (ev_in / ev_out / ev_copy).
+// EnCodec-24 kHz decoder and encoder behind the C ABI (include/vallex.h, vx_codec_*): the packing of the weight table
+// (weights_host.hpp), the workspace and the launch sequences of codec_kernels.hpp.  A handle of its own: the codec has its own
+// weights and lifetime and runs without a VALL-E engine.  Its device side (CodecDev: one packed weight block, one DevBuf per
+// workspace buffer, the CallStage of a call's tables) is made as a whole by vx_codec_finalize on vx_codec_config.device and dropped
+// as a whole; the work runs on the handle's own stream between ev_in and ev_out.
+// At the end of the file: the sample-rate converter in front of the encoder (vx_resampler_*), a handle without weights on
+// host.hpp's LazyDev, its ragged calls staged through CallStage too.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <map>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "host.hpp"
+#include "weights_host.hpp"
 #include "codec_kernels.hpp"
 
 using namespace vx;
 
 namespace {
 
-struct HostW {
-  std::vector<int64_t> shape;
-  std::vector<float> v;
-  bool set = false;
-};
+// ---- weight packing (host): torch layouts -> the [N][K] operands of codec_gemm_rows; a convolution (O, C, k) is conv_rows -----------
+// Every tensor starts at a multiple of 256 bytes of its packed block, which is what a hipMalloc of its own used to give it: the
+// float4 loads and the cache-line layout of the weight rows see the alignment they always saw.
+constexpr size_t CODEC_ALIGN = 64;  // floats
+// Every device block ends in 16 spare bytes, as it has since the first codec.  No load of codec_kernels.hpp needs them:
+// codec_gemm_rows guards every operand read by row < M, n < N and k < K, and takes float4 only where every part's C, and so K, is a
+// multiple of 16; codec_lstm_step reads i * 64 + lane < ldw of whole gate rows; codec_conv_out takes float4 only when C % 4 == 0;
+// codec_rvq_encode reads whole codebook rows (the host checks S % 32 == 0, D % 8 == 0); the per-element kernels leave at
+// i >= rows * dim.  Kept as the margin they always were.
+constexpr size_t CODEC_SPARE = 4;  // floats
 
-// ---- weight packing (host): torch layouts -> the [N][K] operands of codec_gemm_rows -------------------------------------
-// conv (O, C, k): k index = tap * C + c, tap 0 = oldest sample
-std::vector<float> pack_conv(const float* w, int O, int Cc, int k) {
-  std::vector<float> p((size_t)O * Cc * k);
-  for (int o = 0; o < O; ++o)
-    for (int c = 0; c < Cc; ++c)
-      for (int j = 0; j < k; ++j) p[((size_t)o * k + j) * Cc + c] = w[((size_t)o * Cc + c) * k + j];
-  return p;
-}
-// transposed conv (Cin, Cout, 2s), stride s: row n = r * Cout + co; k < Cin: x[t-1] with W[ci][co][r + s]; then x[t] with W[ci][co][r]
-std::vector<float> pack_convtr(const float* w, int Cin, int Cout, int s) {
-  std::vector<float> p((size_t)s * Cout * 2 * Cin);
+// Offsets (floats) into a packed block.
+struct ConvW { size_t w = 0, b = 0; };
+struct ResW { ConvW c3, mix; };  // block.1: ch -> ch / 2, k = res_kernel; [block.3 | shortcut]: K = ch / 2 + ch, bias = sum of the two
+struct LstmW { size_t wih0 = 0, b0 = 0, whh0 = 0, w1 = 0, b1 = 0; };
+
+size_t put(std::vector<float>& p, const std::vector<float>& v) { return push(p, v, CODEC_ALIGN); }
+
+// transposed conv (Cin, Cout, 2s), stride s: row n = r * Cout + co; k < Cin: x[t-1] with W[ci][co][r + s]; then x[t] with W[ci][co][r];
+// the bias repeated per phase
+ConvW pack_convtr(std::vector<float>& p, const float* w, const float* bias, int Cin, int Cout, int s) {
+  std::vector<float> pk((size_t)s * Cout * 2 * Cin), rep;
   for (int r = 0; r < s; ++r)
     for (int co = 0; co < Cout; ++co)
       for (int ci = 0; ci < Cin; ++ci) {
         const size_t n = (size_t)r * Cout + co;
-        p[n * 2 * Cin + ci] = w[((size_t)ci * Cout + co) * 2 * s + r + s];
-        p[n * 2 * Cin + Cin + ci] = w[((size_t)ci * Cout + co) * 2 * s + r];
+        pk[n * 2 * Cin + ci] = w[((size_t)ci * Cout + co) * 2 * s + r + s];
+        pk[n * 2 * Cin + Cin + ci] = w[((size_t)ci * Cout + co) * 2 * s + r];
       }
-  return p;
+  for (int r = 0; bias && r < s; ++r) rep.insert(rep.end(), bias, bias + Cout);
+  ConvW cv;
+  cv.w = put(p, pk);
+  cv.b = put(p, rep);
+  return cv;
 }
 
-int upload(const std::vector<float>& h, float** d) {
-  HIPC(hipMalloc((void**)d, h.size() * sizeof(float) + 16));
-  HIPC(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+ConvW pack_conv(std::vector<float>& p, const float* w, const float* bias, int O, int Cc, int k) {
+  ConvW cv;
+  cv.w = put(p, conv_rows(w, O, Cc, k));
+  cv.b = put(p, bias ? std::vector<float>(bias, bias + O) : std::vector<float>());
+  return cv;
+}
+
+// LSTM weights (torch layouts) -> W_ih0, W_hh0, b_ih0 + b_hh0, [W_ih1 | W_hh1], b_ih1 + b_hh1
+LstmW pack_lstm(std::vector<float>& p, const float* const* wih, const float* const* whh, const float* const* bih, const float* const* bhh,
+                int H, int layers) {
+  LstmW d;
+  std::vector<float> b0(4 * H);
+  for (int i = 0; i < 4 * H; ++i) b0[i] = bih[0][i] + bhh[0][i];
+  d.wih0 = put(p, std::vector<float>(wih[0], wih[0] + (size_t)4 * H * H));
+  d.whh0 = put(p, std::vector<float>(whh[0], whh[0] + (size_t)4 * H * H));
+  d.b0 = put(p, b0);
+  if (layers == 2) {
+    std::vector<float> w1((size_t)4 * H * 2 * H), b1(4 * H);
+    for (int n = 0; n < 4 * H; ++n) {
+      memcpy(&w1[(size_t)n * 2 * H], wih[1] + (size_t)n * H, H * sizeof(float));
+      memcpy(&w1[(size_t)n * 2 * H + H], whh[1] + (size_t)n * H, H * sizeof(float));
+      b1[n] = bih[1][n] + bhh[1][n];
+    }
+    d.w1 = put(p, w1);
+    d.b1 = put(p, b1);
+  }
+  return d;
+}
+
+// |e_j|^2 in fp64, rounded once
+std::vector<float> codebook_sq(const float* cb, size_t n, int D) {
+  std::vector<float> o(n);
+  for (size_t j = 0; j < n; ++j) {
+    double a = 0;
+    for (int c = 0; c < D; ++c) a += (double)cb[j * D + c] * cb[j * D + c];
+    o[j] = (float)a;
+  }
+  return o;
+}
+
+// A packed block goes to the device in one blocking copy.
+int upload_packed(const std::vector<float>& p, DevBuf<float>& d) {
+  VXC(d.alloc(p.size() + CODEC_SPARE));
+  HIPC(hipMemcpy(d.get(), p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice));
   return VX_OK;
 }
 
 // ---- launches --------------------------------------------------------------------------------------------------------
-int launch_gemm(CodecGemmArgs a, hipStream_t s) {
+template <bool STRIDED = false>
+int launch_gemm(const CodecGemmArgs& a, hipStream_t s) {
   bool vec = true;
   for (int p = 0; p < a.nparts; ++p) vec = vec && (a.part[p].C % 16 == 0);
   if (a.M <= 0) return VX_OK;
   if (a.N <= 32) {
     dim3 g((unsigned)((a.M + 127) / 128), (unsigned)((a.N + 31) / 32));
-    if (vec) codec_gemm_rows<4, 1, true><<<g, 256, 0, s>>>(a);
-    else codec_gemm_rows<4, 1, false><<<g, 256, 0, s>>>(a);
+    if (vec) codec_gemm_rows<4, 1, true, STRIDED><<<g, 256, 0, s>>>(a);
+    else codec_gemm_rows<4, 1, false, STRIDED><<<g, 256, 0, s>>>(a);
   } else {
     dim3 g((unsigned)((a.M + 63) / 64), (unsigned)((a.N + 63) / 64));
-    if (vec) codec_gemm_rows<2, 2, true><<<g, 256, 0, s>>>(a);
-    else codec_gemm_rows<2, 2, false><<<g, 256, 0, s>>>(a);
+    if (vec) codec_gemm_rows<2, 2, true, STRIDED><<<g, 256, 0, s>>>(a);
+    else codec_gemm_rows<2, 2, false, STRIDED><<<g, 256, 0, s>>>(a);
   }
   HIPC(hipGetLastError());
   return VX_OK;
 }
 
-// causal k-tap convolution over rows (reflect rule); wp packed by pack_conv.  c_out == 1 runs the bandwidth kernel.
+// causal k-tap convolution over rows (reflect rule); wp packed by conv_rows.  c_out == 1 runs the bandwidth kernel.
 int run_conv(const float* x, const float* wp, const float* bias, float* out, long M, int cin, int cout, int k, int elu,
              const int* seg, int nseg, int rate, hipStream_t s) {
   if (cout == 1 && elu) {
@@ -107,7 +160,7 @@ int run_conv_in(const float* x, const float* w, const float* bias, float* out, l
 }
 
 // encoder: strided convolution k = 2 stride; M_out output rows with starts seg_out, input rows' starts seg_in (both rate 1);
-// wp packed by pack_conv
+// wp packed by conv_rows
 int run_conv_strided(const float* x, const float* wp, const float* bias, float* out, long M_out, int cin, int cout, int stride, int elu,
                      const int* seg_out, const int* seg_in, int nseg, hipStream_t s) {
   CodecGemmArgs a{};
@@ -115,43 +168,29 @@ int run_conv_strided(const float* x, const float* wp, const float* bias, float* 
   a.nparts = 1;
   a.W = wp; a.bias = bias; a.out = out; a.M = M_out; a.N = cout; a.K = 2 * stride * cin; a.seg = seg_out; a.nseg = nseg; a.rate = 1;
   a.seg_in = seg_in; a.stride = stride;
-  if (M_out <= 0) return VX_OK;
-  const bool vec = cin % 16 == 0;
-  if (a.N <= 32) {
-    dim3 g((unsigned)((a.M + 127) / 128), (unsigned)((a.N + 31) / 32));
-    if (vec) codec_gemm_rows<4, 1, true, true><<<g, 256, 0, s>>>(a);
-    else codec_gemm_rows<4, 1, false, true><<<g, 256, 0, s>>>(a);
-  } else {
-    dim3 g((unsigned)((a.M + 63) / 64), (unsigned)((a.N + 63) / 64));
-    if (vec) codec_gemm_rows<2, 2, true, true><<<g, 256, 0, s>>>(a);
-    else codec_gemm_rows<2, 2, false, true><<<g, 256, 0, s>>>(a);
-  }
-  HIPC(hipGetLastError());
-  return VX_OK;
+  return launch_gemm<true>(a, s);
+}
+
+// residual block over M rows of `x` (ch channels): h = block.1(ELU(x)); out = [block.3 | shortcut] over [ELU(h) ; x]
+int run_res(const float* W, const ResW& r, const float* x, float* h, float* out, long M, int ch, int res_kernel, const int* seg, int nseg,
+            int rate, hipStream_t s) {
+  const int hd = ch / 2;
+  VXC(run_conv(x, W + r.c3.w, W + r.c3.b, h, M, ch, hd, res_kernel, 1, seg, nseg, rate, s));
+  CodecGemmArgs a{};
+  a.part[0] = CodecPart{h, hd, 1, CODEC_PAD_ZERO, 1};
+  a.part[1] = CodecPart{x, ch, 1, CODEC_PAD_ZERO, 0};
+  a.nparts = 2;
+  a.W = W + r.mix.w; a.bias = W + r.mix.b; a.out = out; a.M = M; a.N = ch; a.K = hd + ch; a.seg = seg; a.nseg = nseg; a.rate = rate;
+  return launch_gemm(a, s);
 }
 
 bool rvq_shape_ok(int S, int D) { return S >= 32 && S % 32 == 0 && D >= 8 && D % 8 == 0 && D <= CODEC_RVQ_MAX_D; }
-
-// |e_j|^2 in fp64, rounded once
-std::vector<float> codebook_sq(const float* cb, size_t n, int D) {
-  std::vector<float> o(n);
-  for (size_t j = 0; j < n; ++j) {
-    double a = 0;
-    for (int c = 0; c < D; ++c) a += (double)cb[j * D + c] * cb[j * D + c];
-    o[j] = (float)a;
-  }
-  return o;
-}
 
 int run_rvq_encode(const float* emb, const float* cb, const float* cb_sq, int* codes, long rows, int n_q, int S, int D, hipStream_t s) {
   if (rows > 0) codec_rvq_encode<<<(unsigned)((rows + CODEC_RVQ_ROWS - 1) / CODEC_RVQ_ROWS), 256, 0, s>>>(emb, cb, cb_sq, codes, rows, n_q, S, D);
   HIPC(hipGetLastError());
   return VX_OK;
 }
-
-struct LstmDev {
-  float *wih0 = nullptr, *b0 = nullptr, *whh0 = nullptr, *w1 = nullptr, *b1 = nullptr;
-};
 
 bool lstm_width_ok(int H) { return H == 64 || H == 128 || H == 256 || H == 512; }
 
@@ -166,22 +205,24 @@ void launch_lstm_step(const CodecLstmArgs& a, int H, unsigned grid, int st, hipS
 
 constexpr int CODEC_LSTM_CHAIN = 64;  // step launches per replay of the captured chain
 
-// x [rows][H] -> y = lstm(x) + x; gin [rows][4H], h0 / h1 [rows][H], c0 / c1 [nseg][H] are workspace.  chain == nullptr: one plain
-// launch per step.  Otherwise the steps are replayed as a captured LINEAR chain of CODEC_LSTM_CHAIN step launches and one
-// node that advances the step counter: `meta` (device {nseg, step}) was written by the caller, *chain is captured on first use
-// (s must not be the null stream) and serves every batch and length of the handle.
-int run_lstm(const LstmDev& w, const float* x, float* gin, float* h0, float* h1, float* c0, float* c1, float* y, int H, int layers,
-             const int* seg_dev, const int* seg_host, int nseg, hipStream_t s, hipGraphExec_t* chain = nullptr, int* meta = nullptr) {
+// x [rows][H] -> y = lstm(x) + x; W + w: the packed weights; gin [rows][4H], h0 / h1 [rows][H], c0 / c1 [nseg][H] are workspace.
+// chain == nullptr: one plain launch per step.  Otherwise the steps are replayed as a captured LINEAR chain of CODEC_LSTM_CHAIN step
+// launches and one node that advances the step counter: `meta` (device {nseg, step}) was written by the caller, *chain is captured on
+// first use (s must not be the null stream) and serves every batch and length of the handle.
+int run_lstm(const float* W, const LstmW& w, const float* x, float* gin, float* h0, float* h1, float* c0, float* c1, float* y, int H,
+             int layers, const int* seg_dev, const int* seg_host, int nseg, hipStream_t s, hipGraphExec_t* chain = nullptr,
+             int* meta = nullptr) {
   const long rows = seg_host[nseg];
   int Tmax = 0;
   for (int b = 0; b < nseg; ++b) Tmax = std::max(Tmax, seg_host[b + 1] - seg_host[b]);
   CodecGemmArgs g{};
   g.part[0] = CodecPart{x, H, 1, CODEC_PAD_ZERO, 0};
   g.nparts = 1;
-  g.W = w.wih0; g.bias = w.b0; g.out = gin; g.M = rows; g.N = 4 * H; g.K = H; g.seg = seg_dev; g.nseg = nseg; g.rate = 1;
+  g.W = W + w.wih0; g.bias = W + w.b0; g.out = gin; g.M = rows; g.N = 4 * H; g.K = H; g.seg = seg_dev; g.nseg = nseg; g.rate = 1;
   VXC(launch_gemm(g, s));
   CodecLstmArgs a{};
-  a.gin0 = gin; a.whh0 = w.whh0; a.w1 = w.w1; a.b1 = w.b1; a.xin = x; a.h0 = h0; a.h1 = h1; a.y = y; a.c0 = c0; a.c1 = c1;
+  a.gin0 = gin; a.whh0 = W + w.whh0; a.xin = x; a.h0 = h0; a.h1 = h1; a.y = y; a.c0 = c0; a.c1 = c1;
+  if (layers == 2) { a.w1 = W + w.w1; a.b1 = W + w.b1; }
   a.seg = seg_dev; a.nseg = nseg; a.H = H; a.layers = layers;
   const unsigned grid = (unsigned)(layers * H / 4);
   const int steps = Tmax + layers - 1;
@@ -207,31 +248,6 @@ int run_lstm(const LstmDev& w, const float* x, float* gin, float* h0, float* h1,
   return VX_OK;
 }
 
-// LSTM weights (torch layouts, host) -> device operands: W_ih0, b_ih0 + b_hh0, W_hh0, [W_ih1 | W_hh1], b_ih1 + b_hh1
-int pack_lstm(const float* const* wih, const float* const* whh, const float* const* bih, const float* const* bhh, int H, int layers,
-              LstmDev* d) {
-  std::vector<float> b0(4 * H);
-  for (int i = 0; i < 4 * H; ++i) b0[i] = bih[0][i] + bhh[0][i];
-  VXC(upload(std::vector<float>(wih[0], wih[0] + (size_t)4 * H * H), &d->wih0));
-  VXC(upload(std::vector<float>(whh[0], whh[0] + (size_t)4 * H * H), &d->whh0));
-  VXC(upload(b0, &d->b0));
-  if (layers == 2) {
-    std::vector<float> w1((size_t)4 * H * 2 * H), b1(4 * H);
-    for (int n = 0; n < 4 * H; ++n) {
-      memcpy(&w1[(size_t)n * 2 * H], wih[1] + (size_t)n * H, H * sizeof(float));
-      memcpy(&w1[(size_t)n * 2 * H + H], whh[1] + (size_t)n * H, H * sizeof(float));
-      b1[n] = bih[1][n] + bhh[1][n];
-    }
-    VXC(upload(w1, &d->w1));
-    VXC(upload(b1, &d->b1));
-  }
-  return VX_OK;
-}
-void free_lstm(LstmDev& d) {
-  for (float* p : {d.wih0, d.b0, d.whh0, d.w1, d.b1}) (void)hipFree(p);
-  d = LstmDev{};
-}
-
 int check_segs(const int32_t* seg, int nseg) {
   if (!seg || nseg < 1 || nseg > CODEC_MAX_SEG) return fail(VX_ERR_ARG, "segments: 1..%d expected, got %d", CODEC_MAX_SEG, nseg);
   if (seg[0] != 0) return fail(VX_ERR_ARG, "segment starts begin at 0");
@@ -240,18 +256,38 @@ int check_segs(const int32_t* seg, int nseg) {
   return VX_OK;
 }
 
-struct EncStage {
-  int c, stride;                             // c -> 2c at `stride`
-  float *c3_w = nullptr, *c3_b = nullptr;    // block.1: c -> c / 2, k = res_kernel
-  float *mix_w = nullptr, *mix_b = nullptr;  // [block.3 | shortcut]
-  float *dn_w = nullptr, *dn_b = nullptr;    // strided convolution, packed by pack_conv
+struct Stage {  // decoder: cin -> cout = cin / 2 at `stride`
+  int cin, cout, stride;
+  ConvW up;  // transposed convolution
+  ResW res;
 };
 
-struct Stage {
-  int cin, cout, stride;
-  float *up_w = nullptr, *up_b = nullptr;    // packed transposed conv, bias repeated per phase
-  float *c3_w = nullptr, *c3_b = nullptr;    // block.1: cout -> cout / 2, k = res_kernel
-  float *mix_w = nullptr, *mix_b = nullptr;  // [block.3 | shortcut]: K = cout / 2 + cout, bias = sum of the two
+struct EncStage {  // encoder: c -> 2c at `stride`
+  int c, stride;
+  ResW res;
+  ConvW dn;  // strided convolution
+};
+
+// The device side of a finalised handle: made as a whole by vx_codec_finalize, freed as a whole on every way out.
+struct CodecDev {
+  hipStream_t own = nullptr;  // the codec's stream (the LSTM chain cannot be captured on the null stream)
+  hipEvent_t ev_in = nullptr, ev_out = nullptr;
+  hipGraphExec_t chain = nullptr;
+  DevBuf<float> w;  // every packed tensor
+  DevBuf<float> x0, xc, gin, h0, h1, y, c0, c1, bufA, bufH, bufB, wav;  // workspace; wav: the encoder's samples of one group
+  // per call: the encoder's output pointers [max_batch] (encoder handles) | int32 {nseg, step} | frame offsets [max_batch + 1] |
+  // per-group relative offsets [2 (max_batch + 1)] | decode: codes [n_q][frames]; encode: four more row tables per group
+  // [4][2 (max_batch + 1)], then (device only) codes [n_q][frames]
+  CallStage stage;
+  CodecDev() = default;
+  CodecDev(const CodecDev&) = delete;
+  CodecDev& operator=(const CodecDev&) = delete;
+  ~CodecDev() {
+    if (chain) (void)hipGraphExecDestroy(chain);
+    for (hipEvent_t ev : {ev_in, ev_out})
+      if (ev) (void)hipEventDestroy(ev);
+    if (own) (void)hipStreamDestroy(own);
+  }
 };
 
 }  // namespace
@@ -260,94 +296,217 @@ struct vx_codec {
   vx_codec_config cfg{};
   int W = 0;  // LSTM width = 16 * filters
   std::map<std::string, HostW> w;
-  bool allocated = false;  // device objects may exist: vx_codec_destroy frees them
-  bool finalized = false;  // every upload and allocation succeeded: set as vx_codec_finalize's last statement
+  bool finalized = false;  // the device side is complete: set as vx_codec_finalize's last statement
   bool failed = false;     // a finalize failed half way: the handle refuses further use
-  hipStream_t own = nullptr;                 // the decoder's stream (the LSTM chain cannot be captured on the null stream)
-  hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_copy = nullptr;
-  hipGraphExec_t chain = nullptr;
-  float* cb = nullptr;  // [n_codebooks][size][dim]
-  float *c0_w = nullptr, *c0_b = nullptr, *last_w = nullptr, *last_b = nullptr;
-  LstmDev lstm;
+  std::unique_ptr<CodecDev> dev;
+  // offsets into dev->w
+  size_t cb = 0;  // [n_codebooks][size][dim]
+  ConvW c0, last;
+  LstmW lstm;
   std::vector<Stage> stages;
-  // workspace
   long cap_frames = 0, chunk_frames = 0, per_frame = 0;
-  // int32 staging: {nseg, step} | frame offsets [max_batch + 1] | per-group relative offsets [2 (max_batch + 1)] | codes [n_q][frames]
-  int *codes_dev = nullptr, *codes_host = nullptr;
-  size_t stage_ints = 0;
-  float *x0 = nullptr, *xc = nullptr, *gin = nullptr, *h0 = nullptr, *h1 = nullptr, *y = nullptr, *c0 = nullptr, *c1 = nullptr;
-  float *bufA = nullptr, *bufH = nullptr, *bufB = nullptr;
+  size_t ptr_bytes = 0;  // of the stage's pointer column
   // encoder (VX_CODEC_ENCODER)
   bool enc = false;
-  float *cb_sq = nullptr;  // [n_codebooks][size]
-  float *e0_w = nullptr, *e0_b = nullptr, *elast_w = nullptr, *elast_b = nullptr, *wav = nullptr;
-  LstmDev elstm;
+  size_t cb_sq = 0;  // [n_codebooks][size]
+  ConvW e0, elast;
+  LstmW elstm;
   std::vector<EncStage> estages;
-  long long **ptrs_dev = nullptr, **ptrs_host = nullptr;  // the utterances' output tensors
   long last_frames = 0;  // frames of the last vx_codec_encode (what x0 holds of it)
 };
 
-static std::map<std::string, std::vector<int64_t>> codec_expected(const vx_codec_config& c) {
-  std::map<std::string, std::vector<int64_t>> s;
-  const int64_t W = 16 * (int64_t)c.filters;
-  char k[128];
-  s["decoder.layers.0.conv.weight"] = {W, c.hidden, c.kernel};
-  s["decoder.layers.0.conv.bias"] = {W};
-  for (int l = 0; l < c.lstm_layers; ++l) {
-    snprintf(k, sizeof k, "decoder.layers.1.lstm.weight_ih_l%d", l); s[k] = {4 * W, W};
-    snprintf(k, sizeof k, "decoder.layers.1.lstm.weight_hh_l%d", l); s[k] = {4 * W, W};
-    snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_ih_l%d", l); s[k] = {4 * W};
-    snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_hh_l%d", l); s[k] = {4 * W};
-  }
-  int64_t ch = W;
-  for (int i = 0; i < 4; ++i) {
-    const int up = 3 + 3 * i, res = 4 + 3 * i;
-    snprintf(k, sizeof k, "decoder.layers.%d.conv.weight", up); s[k] = {ch, ch / 2, 2 * (int64_t)c.ratios[i]};
-    snprintf(k, sizeof k, "decoder.layers.%d.conv.bias", up); s[k] = {ch / 2};
-    ch /= 2;
-    snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.weight", res); s[k] = {ch / 2, ch, c.res_kernel};
-    snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.bias", res); s[k] = {ch / 2};
-    snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.weight", res); s[k] = {ch, ch / 2, 1};
-    snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.bias", res); s[k] = {ch};
-    snprintf(k, sizeof k, "decoder.layers.%d.shortcut.conv.weight", res); s[k] = {ch, ch, 1};
-    snprintf(k, sizeof k, "decoder.layers.%d.shortcut.conv.bias", res); s[k] = {ch};
-  }
-  s["decoder.layers.15.conv.weight"] = {1, ch, c.last_kernel};
-  s["decoder.layers.15.conv.bias"] = {1};
-  for (int q = 0; q < c.n_codebooks; ++q) {
-    snprintf(k, sizeof k, "quantizer.layers.%d.codebook.embed", q); s[k] = {c.codebook_size, c.codebook_dim};
-  }
-  if (!(c.flags & VX_CODEC_ENCODER)) return s;
-  ch = c.filters;
-  s["encoder.layers.0.conv.weight"] = {ch, 1, c.kernel};
-  s["encoder.layers.0.conv.bias"] = {ch};
-  for (int i = 0; i < 4; ++i) {
-    const int res = 1 + 3 * i, dn = 3 + 3 * i;
-    snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.weight", res); s[k] = {ch / 2, ch, c.res_kernel};
-    snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.bias", res); s[k] = {ch / 2};
-    snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.weight", res); s[k] = {ch, ch / 2, 1};
-    snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.bias", res); s[k] = {ch};
-    snprintf(k, sizeof k, "encoder.layers.%d.shortcut.conv.weight", res); s[k] = {ch, ch, 1};
-    snprintf(k, sizeof k, "encoder.layers.%d.shortcut.conv.bias", res); s[k] = {ch};
-    snprintf(k, sizeof k, "encoder.layers.%d.conv.weight", dn); s[k] = {2 * ch, ch, 2 * (int64_t)c.ratios[3 - i]};
-    snprintf(k, sizeof k, "encoder.layers.%d.conv.bias", dn); s[k] = {2 * ch};
-    ch *= 2;
-  }
-  for (int l = 0; l < c.lstm_layers; ++l) {
-    snprintf(k, sizeof k, "encoder.layers.13.lstm.weight_ih_l%d", l); s[k] = {4 * W, W};
-    snprintf(k, sizeof k, "encoder.layers.13.lstm.weight_hh_l%d", l); s[k] = {4 * W, W};
-    snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_ih_l%d", l); s[k] = {4 * W};
-    snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_hh_l%d", l); s[k] = {4 * W};
-  }
-  s["encoder.layers.15.conv.weight"] = {c.hidden, W, c.last_kernel};
-  s["encoder.layers.15.conv.bias"] = {c.hidden};
-  return s;
+namespace {
+
+void conv_keys(vx_codec* e, const std::string& nm, int64_t O, int64_t Cc, int64_t k) {
+  add_key(e, nm + ".weight", {O, Cc, k});
+  add_key(e, nm + ".bias", {O});
 }
 
+void res_keys(vx_codec* e, const std::string& pre, int64_t ch) {
+  conv_keys(e, pre + "block.1.conv", ch / 2, ch, e->cfg.res_kernel);
+  conv_keys(e, pre + "block.3.conv", ch, ch / 2, 1);
+  conv_keys(e, pre + "shortcut.conv", ch, ch, 1);
+}
+
+void lstm_keys(vx_codec* e, const std::string& pre) {
+  const int64_t W = e->W;
+  for (int l = 0; l < e->cfg.lstm_layers; ++l) {
+    const std::string sl = "_l" + std::to_string(l);
+    add_key(e, pre + "weight_ih" + sl, {4 * W, W});
+    add_key(e, pre + "weight_hh" + sl, {4 * W, W});
+    add_key(e, pre + "bias_ih" + sl, {4 * W});
+    add_key(e, pre + "bias_hh" + sl, {4 * W});
+  }
+}
+
+std::string layer(const char* side, int i) { return std::string(side) + ".layers." + std::to_string(i) + "."; }
+
+void codec_add_keys(vx_codec* e) {
+  const vx_codec_config& c = e->cfg;
+  const int64_t W = e->W;
+  conv_keys(e, "decoder.layers.0.conv", W, c.hidden, c.kernel);
+  lstm_keys(e, "decoder.layers.1.lstm.");
+  int64_t ch = W;
+  for (int i = 0; i < 4; ++i) {
+    add_key(e, layer("decoder", 3 + 3 * i) + "conv.weight", {ch, ch / 2, 2 * (int64_t)c.ratios[i]});
+    add_key(e, layer("decoder", 3 + 3 * i) + "conv.bias", {ch / 2});
+    ch /= 2;
+    res_keys(e, layer("decoder", 4 + 3 * i), ch);
+  }
+  conv_keys(e, "decoder.layers.15.conv", 1, ch, c.last_kernel);
+  for (int q = 0; q < c.n_codebooks; ++q) add_key(e, layer("quantizer", q) + "codebook.embed", {c.codebook_size, c.codebook_dim});
+  if (!(c.flags & VX_CODEC_ENCODER)) return;
+  ch = c.filters;
+  conv_keys(e, "encoder.layers.0.conv", ch, 1, c.kernel);
+  for (int i = 0; i < 4; ++i) {
+    res_keys(e, layer("encoder", 1 + 3 * i), ch);
+    conv_keys(e, layer("encoder", 3 + 3 * i) + "conv", 2 * ch, ch, 2 * (int64_t)c.ratios[3 - i]);
+    ch *= 2;
+  }
+  lstm_keys(e, "encoder.layers.13.lstm.");
+  conv_keys(e, "encoder.layers.15.conv", c.hidden, W, c.last_kernel);
+}
+
+const float* host(vx_codec* e, const std::string& key) { return e->w[key].data.data(); }
+
+ConvW pack_conv(vx_codec* e, std::vector<float>& p, const std::string& nm, int O, int Cc, int k) {
+  return pack_conv(p, host(e, nm + ".weight"), host(e, nm + ".bias"), O, Cc, k);
+}
+
+// One residual stage of ch channels by its key prefix ("decoder.layers.4."): block.1 and [block.3 | shortcut]
+ResW pack_res(vx_codec* e, std::vector<float>& p, const std::string& pre, int ch) {
+  const int hd = ch / 2;
+  ResW r;
+  r.c3 = pack_conv(e, p, pre + "block.1.conv", hd, ch, e->cfg.res_kernel);
+  const float *w3 = host(e, pre + "block.3.conv.weight"), *ws = host(e, pre + "shortcut.conv.weight");
+  const float *b3 = host(e, pre + "block.3.conv.bias"), *bs = host(e, pre + "shortcut.conv.bias");
+  std::vector<float> mix((size_t)ch * (hd + ch)), mb(ch);
+  for (int n = 0; n < ch; ++n) {
+    memcpy(&mix[(size_t)n * (hd + ch)], w3 + (size_t)n * hd, hd * sizeof(float));
+    memcpy(&mix[(size_t)n * (hd + ch) + hd], ws + (size_t)n * ch, ch * sizeof(float));
+    mb[n] = b3[n] + bs[n];
+  }
+  r.mix.w = put(p, mix);
+  r.mix.b = put(p, mb);
+  return r;
+}
+
+// An LSTM's four tensors per layer by its key prefix ("decoder.layers.1.lstm.")
+LstmW pack_lstm(vx_codec* e, std::vector<float>& p, const std::string& pre) {
+  const float *wih[2] = {}, *whh[2] = {}, *bih[2] = {}, *bhh[2] = {};
+  for (int l = 0; l < e->cfg.lstm_layers; ++l) {
+    const std::string sl = "_l" + std::to_string(l);
+    wih[l] = host(e, pre + "weight_ih" + sl);
+    whh[l] = host(e, pre + "weight_hh" + sl);
+    bih[l] = host(e, pre + "bias_ih" + sl);
+    bhh[l] = host(e, pre + "bias_hh" + sl);
+  }
+  return pack_lstm(p, wih, whh, bih, bhh, e->W, e->cfg.lstm_layers);
+}
+
+// Every tensor of the handle into `p`; the offsets into the handle.  Returns the widest decoder stage's floats per frame.
+long codec_pack(vx_codec* e, std::vector<float>& p) {
+  const vx_codec_config& c = e->cfg;
+  const int W = e->W;
+  std::vector<float> cb, sq;
+  for (int q = 0; q < c.n_codebooks; ++q) {
+    const HostW& t = e->w[layer("quantizer", q) + "codebook.embed"];
+    cb.insert(cb.end(), t.data.begin(), t.data.end());
+    const std::vector<float> one = codebook_sq(t.data.data(), (size_t)c.codebook_size, c.codebook_dim);
+    sq.insert(sq.end(), one.begin(), one.end());
+  }
+  e->cb = put(p, cb);
+  e->c0 = pack_conv(e, p, "decoder.layers.0.conv", W, c.hidden, c.kernel);
+  e->lstm = pack_lstm(e, p, "decoder.layers.1.lstm.");
+  int ch = W;
+  long rate = 1, per_frame = 0;
+  e->stages.resize(4);
+  for (int i = 0; i < 4; ++i) {
+    Stage& st = e->stages[i];
+    const std::string up = layer("decoder", 3 + 3 * i) + "conv";
+    st.cin = ch; st.cout = ch / 2; st.stride = c.ratios[i];
+    st.up = pack_convtr(p, host(e, up + ".weight"), host(e, up + ".bias"), ch, ch / 2, st.stride);
+    ch /= 2;
+    rate *= st.stride;
+    per_frame = std::max(per_frame, rate * ch);
+    st.res = pack_res(e, p, layer("decoder", 4 + 3 * i), ch);
+  }
+  e->last = pack_conv(e, p, "decoder.layers.15.conv", 1, ch, c.last_kernel);
+  if (!e->enc) return per_frame;
+  e->cb_sq = put(p, sq);
+  e->e0 = pack_conv(e, p, "encoder.layers.0.conv", c.filters, 1, c.kernel);
+  int ec = c.filters;
+  e->estages.resize(4);
+  for (int i = 0; i < 4; ++i) {
+    EncStage& st = e->estages[i];
+    st.c = ec; st.stride = c.ratios[3 - i];
+    st.res = pack_res(e, p, layer("encoder", 1 + 3 * i), ec);
+    st.dn = pack_conv(e, p, layer("encoder", 3 + 3 * i) + "conv", 2 * ec, ec, 2 * st.stride);
+    ec *= 2;
+  }
+  e->elstm = pack_lstm(e, p, "encoder.layers.13.lstm.");
+  e->elast = pack_conv(e, p, "encoder.layers.15.conv", c.hidden, W, c.last_kernel);
+  return per_frame;
+}
+
+// ---- the common head of vx_codec_decode and vx_codec_encode -------------------------------------------------------------------------
+struct Group { int u0, u1, off; };  // utterances [u0, u1); `off`: where the group's relative offsets start in their table
+
+struct Call {
+  hipStream_t s = nullptr;
+  std::vector<int> seg;       // host: the n + 1 frame offsets of the call
+  std::vector<Group> groups;  // whole utterances of at most chunk_frames frames together: the rows of the sample-rate stages
+  int* meta = nullptr;        // device: {nseg, step}
+  const int *dseg = nullptr, *drel = nullptr;  // device: frame offsets of the call; per group, relative to the group
+  int* rest = nullptr;        // device: what `fill` wrote, and the block's unstaged end behind it
+};
+
+// The work runs on the codec's own stream, ordered after everything already enqueued on `stream`; `stream` waits for it before the
+// call returns (as the engine's entry points do).  The host waits only for the previous call's staging copy.  `frames`: per utterance;
+// fill(host ints behind the three tables) writes the call's own rest_ints, after seg and groups are known.
+template <class Fill>
+int begin_call(vx_codec* e, int n, const std::vector<int>& frames, void* stream, size_t rest_ints, Fill fill, Call& x) {
+  CodecDev& d = *e->dev;
+  x.s = d.own;
+  HIPC(hipEventRecord(d.ev_in, (hipStream_t)stream));
+  HIPC(hipStreamWaitEvent(x.s, d.ev_in, 0));
+  VXC(d.stage.begin(x.s));
+  const int MB1 = e->cfg.max_batch + 1;
+  int* hc = d.stage.host<int>(e->ptr_bytes);
+  hc[0] = n;
+  hc[1] = 0;
+  int *hseg = hc + 2, *hrel = hseg + MB1;
+  x.seg.assign(n + 1, 0);
+  for (int i = 0; i < n; ++i) x.seg[i + 1] = x.seg[i] + frames[i];
+  memcpy(hseg, x.seg.data(), (n + 1) * sizeof(int));
+  int used = 0;
+  for (int u0 = 0; u0 < n;) {
+    int u1 = u0 + 1;
+    while (u1 < n && (long)x.seg[u1 + 1] - x.seg[u0] <= e->chunk_frames) ++u1;
+    x.groups.push_back(Group{u0, u1, used});
+    for (int u = u0; u <= u1; ++u) hrel[used++] = x.seg[u] - x.seg[u0];
+    u0 = u1;
+  }
+  fill(hrel + 2 * MB1);
+  VXC(d.stage.upload(e->ptr_bytes + (2 + 3 * (size_t)MB1 + rest_ints) * sizeof(int), x.s));
+  x.meta = d.stage.dev<int>(e->ptr_bytes);
+  x.dseg = x.meta + 2;
+  x.drel = x.dseg + MB1;
+  x.rest = x.meta + 2 + 3 * MB1;
+  return VX_OK;
+}
+
+// `stream` waits for the call's work.
+int end_call(vx_codec* e, const Call& x, void* stream) {
+  HIPC(hipEventRecord(e->dev->ev_out, x.s));
+  HIPC(hipStreamWaitEvent((hipStream_t)stream, e->dev->ev_out, 0));
+  return e->dev->stage.finish(x.s);
+}
+
+}  // namespace
+
 extern "C" int vx_codec_create(const vx_codec_config* cfg, vx_codec** out) {
-  if (!cfg || !out) return fail(VX_ERR_ARG, "vx_codec_create: null argument");
-  if (cfg->struct_size != (int32_t)sizeof(vx_codec_config))
-    return fail(VX_ERR_ARG, "vx_codec_config.struct_size %d != %d", cfg->struct_size, (int)sizeof(vx_codec_config));
+  VXC(create_head("vx_codec_create", cfg, out));
   const vx_codec_config& c = *cfg;
   if (c.hidden < 1 || c.filters < 1 || c.codebook_size < 1 || c.codebook_dim < 1 || c.n_codebooks < 1 || c.max_frames < 1 ||
       c.max_batch < 1 || c.kernel < 1 || c.last_kernel < 1 || c.res_kernel < 1 || c.lstm_layers < 0 || c.device < 0 ||
@@ -375,221 +534,71 @@ extern "C" int vx_codec_create(const vx_codec_config* cfg, vx_codec** out) {
   vx_codec* e = new vx_codec();
   e->cfg = c;
   e->W = W;
-  for (auto& kv : codec_expected(c)) e->w[kv.first].shape = kv.second;
+  e->enc = (c.flags & VX_CODEC_ENCODER) != 0;
+  codec_add_keys(e);
   *out = e;
   return VX_OK;
 }
 
-static void codec_free_device(vx_codec* e) {
-  for (float* p : {e->cb, e->c0_w, e->c0_b, e->last_w, e->last_b, e->x0, e->xc, e->gin, e->h0, e->h1, e->y, e->c0, e->c1, e->bufA,
-                   e->bufH, e->bufB})
-    (void)hipFree(p);
-  free_lstm(e->lstm);
-  for (float* p : {e->cb_sq, e->e0_w, e->e0_b, e->elast_w, e->elast_b, e->wav}) (void)hipFree(p);
-  free_lstm(e->elstm);
-  for (EncStage& st : e->estages)
-    for (float* p : {st.c3_w, st.c3_b, st.mix_w, st.mix_b, st.dn_w, st.dn_b}) (void)hipFree(p);
-  (void)hipFree(e->ptrs_dev);
-  (void)hipHostFree(e->ptrs_host);
-  for (Stage& st : e->stages)
-    for (float* p : {st.up_w, st.up_b, st.c3_w, st.c3_b, st.mix_w, st.mix_b}) (void)hipFree(p);
-  (void)hipFree(e->codes_dev);
-  (void)hipHostFree(e->codes_host);
-  if (e->chain) (void)hipGraphExecDestroy(e->chain);
-  for (hipEvent_t ev : {e->ev_in, e->ev_out, e->ev_copy})
-    if (ev) (void)hipEventDestroy(ev);
-  if (e->own) (void)hipStreamDestroy(e->own);
-}
-
 extern "C" void vx_codec_destroy(vx_codec* e) {
   if (!e) return;
-  if (e->allocated) {
+  if (e->dev) {
     DevGuard g(e->cfg.device);
-    if (e->own) (void)hipStreamSynchronize(e->own);
-    codec_free_device(e);
+    (void)hipStreamSynchronize(e->dev->own);
+    e->dev.reset();
   }
   delete e;
 }
 
 extern "C" int vx_codec_set_weight(vx_codec* e, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
-  if (!e || !key || !data || !shape) return fail(VX_ERR_ARG, "vx_codec_set_weight: null argument");
-  if (e->finalized) return fail(VX_ERR_STATE, "vx_codec_set_weight after vx_codec_finalize");
-  auto it = e->w.find(key);
-  if (it == e->w.end()) return fail(VX_ERR_WEIGHTS, "unknown key %s", key);
-  HostW& t = it->second;
-  bool same = (size_t)ndim == t.shape.size();
-  size_t n = 1;
-  for (int i = 0; same && i < ndim; ++i) { same = shape[i] == t.shape[i]; n *= (size_t)shape[i]; }
-  if (!same) return fail(VX_ERR_WEIGHTS, "wrong shape for %s", key);
-  t.v.assign(data, data + n);
-  t.set = true;
-  return VX_OK;
-}
-
-static int alloc_f(float** p, size_t n) {
-  HIPC(hipMalloc((void**)p, n * sizeof(float) + 16));
-  return VX_OK;
+  return set_weight(e, "vx_codec", key, data, shape, ndim);
 }
 
 extern "C" int vx_codec_finalize(vx_codec* e) {
   if (!e) return fail(VX_ERR_ARG, "vx_codec_finalize: null handle");
   if (e->finalized) return VX_OK;
   if (e->failed) return fail(VX_ERR_STATE, "vx_codec_finalize failed earlier on this handle: destroy it and create a new one");
-  for (auto& kv : e->w)
-    if (!kv.second.set) return fail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
+  VXC(missing_tensor(e));
   const vx_codec_config& c = e->cfg;
-  e->failed = true;     // until the last statement: a finalize that stops at a HIP error leaves a handle that refuses further use
+  e->failed = true;  // until the last statement: a finalize that stops at a HIP error leaves a handle that refuses further use
   ON_DEVICE(c.device);
-  e->allocated = true;  // from here vx_codec_destroy frees what was allocated
+  std::unique_ptr<CodecDev> d(new CodecDev());  // a finalize that stops half way frees what it took
   const int W = e->W;
-  char k[128], k2[128];
-  auto host = [&](const char* key) -> const std::vector<float>& { return e->w[key].v; };
+  long rate = 1;
+  for (int i = 0; i < 4; ++i) rate *= c.ratios[i];
   {
-    std::vector<float> cb((size_t)c.n_codebooks * c.codebook_size * c.codebook_dim);
-    for (int q = 0; q < c.n_codebooks; ++q) {
-      snprintf(k, sizeof k, "quantizer.layers.%d.codebook.embed", q);
-      memcpy(&cb[(size_t)q * c.codebook_size * c.codebook_dim], host(k).data(), host(k).size() * sizeof(float));
-    }
-    VXC(upload(cb, &e->cb));
+    std::vector<float> packed;
+    e->per_frame = std::max<long>(codec_pack(e, packed), 2 * rate);
+    VXC(upload_packed(packed, d->w));
   }
-  VXC(upload(pack_conv(host("decoder.layers.0.conv.weight").data(), W, c.hidden, c.kernel), &e->c0_w));
-  VXC(upload(host("decoder.layers.0.conv.bias"), &e->c0_b));
-  {
-    const float *wih[2] = {}, *whh[2] = {}, *bih[2] = {}, *bhh[2] = {};
-    for (int l = 0; l < c.lstm_layers; ++l) {
-      snprintf(k, sizeof k, "decoder.layers.1.lstm.weight_ih_l%d", l); wih[l] = host(k).data();
-      snprintf(k, sizeof k, "decoder.layers.1.lstm.weight_hh_l%d", l); whh[l] = host(k).data();
-      snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_ih_l%d", l); bih[l] = host(k).data();
-      snprintf(k, sizeof k, "decoder.layers.1.lstm.bias_hh_l%d", l); bhh[l] = host(k).data();
-    }
-    VXC(pack_lstm(wih, whh, bih, bhh, W, c.lstm_layers, &e->lstm));
-  }
-  int ch = W;
-  long rate = 1, per_frame = 0;
-  e->stages.resize(4);
-  for (int i = 0; i < 4; ++i) {
-    Stage& st = e->stages[i];
-    const int up = 3 + 3 * i, res = 4 + 3 * i, r = c.ratios[i];
-    st.cin = ch; st.cout = ch / 2; st.stride = r;
-    snprintf(k, sizeof k, "decoder.layers.%d.conv.weight", up);
-    VXC(upload(pack_convtr(host(k).data(), ch, ch / 2, r), &st.up_w));
-    snprintf(k, sizeof k, "decoder.layers.%d.conv.bias", up);
-    std::vector<float> rep((size_t)r * (ch / 2));
-    for (int p = 0; p < r; ++p) memcpy(&rep[(size_t)p * (ch / 2)], host(k).data(), (ch / 2) * sizeof(float));
-    VXC(upload(rep, &st.up_b));
-    ch /= 2;
-    rate *= r;
-    per_frame = std::max(per_frame, rate * ch);
-    const int hd = ch / 2;
-    snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.weight", res);
-    VXC(upload(pack_conv(host(k).data(), hd, ch, c.res_kernel), &st.c3_w));
-    snprintf(k, sizeof k, "decoder.layers.%d.block.1.conv.bias", res);
-    VXC(upload(host(k), &st.c3_b));
-    snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.weight", res);
-    snprintf(k2, sizeof k2, "decoder.layers.%d.shortcut.conv.weight", res);
-    std::vector<float> mix((size_t)ch * (hd + ch)), mb(ch);
-    for (int n = 0; n < ch; ++n) {
-      memcpy(&mix[(size_t)n * (hd + ch)], host(k).data() + (size_t)n * hd, hd * sizeof(float));
-      memcpy(&mix[(size_t)n * (hd + ch) + hd], host(k2).data() + (size_t)n * ch, ch * sizeof(float));
-    }
-    snprintf(k, sizeof k, "decoder.layers.%d.block.3.conv.bias", res);
-    snprintf(k2, sizeof k2, "decoder.layers.%d.shortcut.conv.bias", res);
-    for (int n = 0; n < ch; ++n) mb[n] = host(k)[n] + host(k2)[n];
-    VXC(upload(mix, &st.mix_w));
-    VXC(upload(mb, &st.mix_b));
-  }
-  VXC(upload(pack_conv(host("decoder.layers.15.conv.weight").data(), 1, ch, c.last_kernel), &e->last_w));
-  VXC(upload(host("decoder.layers.15.conv.bias"), &e->last_b));
-  e->enc = (c.flags & VX_CODEC_ENCODER) != 0;
-  if (e->enc) {
-    {
-      std::vector<float> sq;
-      for (int q = 0; q < c.n_codebooks; ++q) {
-        snprintf(k, sizeof k, "quantizer.layers.%d.codebook.embed", q);
-        const std::vector<float> one = codebook_sq(host(k).data(), (size_t)c.codebook_size, c.codebook_dim);
-        sq.insert(sq.end(), one.begin(), one.end());
-      }
-      VXC(upload(sq, &e->cb_sq));
-    }
-    VXC(upload(pack_conv(host("encoder.layers.0.conv.weight").data(), c.filters, 1, c.kernel), &e->e0_w));
-    VXC(upload(host("encoder.layers.0.conv.bias"), &e->e0_b));
-    int ec = c.filters;
-    e->estages.resize(4);
-    for (int i = 0; i < 4; ++i) {
-      EncStage& st = e->estages[i];
-      const int res = 1 + 3 * i, dn = 3 + 3 * i, hd = ec / 2;
-      st.c = ec; st.stride = c.ratios[3 - i];
-      snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.weight", res);
-      VXC(upload(pack_conv(host(k).data(), hd, ec, c.res_kernel), &st.c3_w));
-      snprintf(k, sizeof k, "encoder.layers.%d.block.1.conv.bias", res);
-      VXC(upload(host(k), &st.c3_b));
-      snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.weight", res);
-      snprintf(k2, sizeof k2, "encoder.layers.%d.shortcut.conv.weight", res);
-      std::vector<float> mix((size_t)ec * (hd + ec)), mb(ec);
-      for (int n = 0; n < ec; ++n) {
-        memcpy(&mix[(size_t)n * (hd + ec)], host(k).data() + (size_t)n * hd, hd * sizeof(float));
-        memcpy(&mix[(size_t)n * (hd + ec) + hd], host(k2).data() + (size_t)n * ec, ec * sizeof(float));
-      }
-      snprintf(k, sizeof k, "encoder.layers.%d.block.3.conv.bias", res);
-      snprintf(k2, sizeof k2, "encoder.layers.%d.shortcut.conv.bias", res);
-      for (int n = 0; n < ec; ++n) mb[n] = host(k)[n] + host(k2)[n];
-      VXC(upload(mix, &st.mix_w));
-      VXC(upload(mb, &st.mix_b));
-      snprintf(k, sizeof k, "encoder.layers.%d.conv.weight", dn);
-      VXC(upload(pack_conv(host(k).data(), 2 * ec, ec, 2 * st.stride), &st.dn_w));
-      snprintf(k, sizeof k, "encoder.layers.%d.conv.bias", dn);
-      VXC(upload(host(k), &st.dn_b));
-      ec *= 2;
-    }
-    {
-      const float *wih[2] = {}, *whh[2] = {}, *bih[2] = {}, *bhh[2] = {};
-      for (int l = 0; l < c.lstm_layers; ++l) {
-        snprintf(k, sizeof k, "encoder.layers.13.lstm.weight_ih_l%d", l); wih[l] = host(k).data();
-        snprintf(k, sizeof k, "encoder.layers.13.lstm.weight_hh_l%d", l); whh[l] = host(k).data();
-        snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_ih_l%d", l); bih[l] = host(k).data();
-        snprintf(k, sizeof k, "encoder.layers.13.lstm.bias_hh_l%d", l); bhh[l] = host(k).data();
-      }
-      VXC(pack_lstm(wih, whh, bih, bhh, W, c.lstm_layers, &e->elstm));
-    }
-    VXC(upload(pack_conv(host("encoder.layers.15.conv.weight").data(), c.hidden, W, c.last_kernel), &e->elast_w));
-    VXC(upload(host("encoder.layers.15.conv.bias"), &e->elast_b));
-  }
-  for (auto& kv : e->w) std::vector<float>().swap(kv.second.v);  // the host copies are not needed any more
+  for (auto& kv : e->w) std::vector<float>().swap(kv.second.data);  // the host copies are not needed any more
 
   // workspace: the LSTM part holds every frame of a call; the up-sampling part runs over groups of whole utterances of at
   // most chunk_frames frames (its rows are 320x as many)
   e->cap_frames = (long)c.max_frames * c.max_batch;
   e->chunk_frames = std::min(e->cap_frames, std::max<long>(c.max_frames, 8192));
-  e->per_frame = std::max<long>(per_frame, 2 * rate);
-  const size_t F = (size_t)e->cap_frames;
-  VXC(alloc_f(&e->x0, F * c.hidden));
-  VXC(alloc_f(&e->xc, F * W));
-  VXC(alloc_f(&e->gin, F * 4 * W));
-  VXC(alloc_f(&e->h0, F * W));
-  VXC(alloc_f(&e->h1, F * W));
-  VXC(alloc_f(&e->y, F * W));
-  VXC(alloc_f(&e->c0, (size_t)c.max_batch * W));
-  VXC(alloc_f(&e->c1, (size_t)c.max_batch * W));
+  const size_t F = (size_t)e->cap_frames, MB1 = (size_t)c.max_batch + 1;
+  VXC(d->x0.alloc(F * c.hidden + CODEC_SPARE));
+  VXC(d->xc.alloc(F * W + CODEC_SPARE));
+  VXC(d->gin.alloc(F * 4 * W + CODEC_SPARE));
+  VXC(d->h0.alloc(F * W + CODEC_SPARE));
+  VXC(d->h1.alloc(F * W + CODEC_SPARE));
+  VXC(d->y.alloc(F * W + CODEC_SPARE));
+  VXC(d->c0.alloc((size_t)c.max_batch * W + CODEC_SPARE));
+  VXC(d->c1.alloc((size_t)c.max_batch * W + CODEC_SPARE));
   // encoder: the same three buffers hold its stages (filters channels per sample at most, as the decoder's last stage), plus one
   // row per utterance and stage for the rounded-up row counts
-  const size_t slack = e->enc ? (size_t)c.max_batch * W : 0;
-  VXC(alloc_f(&e->bufA, (size_t)e->chunk_frames * e->per_frame + slack));
-  VXC(alloc_f(&e->bufB, (size_t)e->chunk_frames * e->per_frame + slack));
-  VXC(alloc_f(&e->bufH, (size_t)e->chunk_frames * e->per_frame / 2 + slack));
-  e->stage_ints = 2 + F * c.n_codebooks + 3 * (size_t)(c.max_batch + 1);
-  if (e->enc) {
-    e->stage_ints += 8 * (size_t)(c.max_batch + 1);  // four more row tables per utterance group
-    VXC(alloc_f(&e->wav, (size_t)e->chunk_frames * rate));
-    HIPC(hipMalloc((void**)&e->ptrs_dev, (size_t)c.max_batch * sizeof(void*)));
-    HIPC(hipHostMalloc((void**)&e->ptrs_host, (size_t)c.max_batch * sizeof(void*)));
-  }
-  HIPC(hipMalloc((void**)&e->codes_dev, e->stage_ints * sizeof(int)));
-  HIPC(hipHostMalloc((void**)&e->codes_host, e->stage_ints * sizeof(int)));
-  HIPC(hipStreamCreateWithFlags(&e->own, hipStreamNonBlocking));
-  HIPC(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
-  HIPC(hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming));
-  HIPC(hipEventCreateWithFlags(&e->ev_copy, hipEventDisableTiming));
-  HIPC(hipEventRecord(e->ev_copy, e->own));
+  const size_t slack = e->enc ? (size_t)c.max_batch * W : 0, rows = (size_t)e->chunk_frames * e->per_frame;
+  VXC(d->bufA.alloc(rows + slack + CODEC_SPARE));
+  VXC(d->bufB.alloc(rows + slack + CODEC_SPARE));
+  VXC(d->bufH.alloc(rows / 2 + slack + CODEC_SPARE));
+  if (e->enc) VXC(d->wav.alloc((size_t)e->chunk_frames * rate + CODEC_SPARE));
+  e->ptr_bytes = e->enc ? (size_t)c.max_batch * sizeof(void*) : 0;
+  VXC(d->stage.init(e->ptr_bytes + (2 + 3 * MB1 + (e->enc ? 8 * MB1 : 0) + F * c.n_codebooks) * sizeof(int)));
+  HIPC(hipStreamCreateWithFlags(&d->own, hipStreamNonBlocking));
+  HIPC(hipEventCreateWithFlags(&d->ev_in, hipEventDisableTiming));
+  HIPC(hipEventCreateWithFlags(&d->ev_out, hipEventDisableTiming));
+  e->dev = std::move(d);
   e->failed = false;
   e->finalized = true;
   return VX_OK;
@@ -615,82 +624,45 @@ extern "C" int vx_codec_decode(vx_codec* e, int32_t n, const int64_t* const* cod
         return fail(VX_ERR_ARG, "utterance %d: code %lld outside [0, %d)", i, (long long)codes[i][j], c.codebook_size);
   if (!e->finalized) return fail(VX_ERR_STATE, "vx_codec_decode before vx_codec_finalize");
   ON_DEVICE(c.device);
-  // The work runs on the decoder's own stream, ordered after everything already enqueued on `stream`; `stream` waits for it
-  // before the call returns (as the engine's entry points do).  The host waits only for the previous call's staging copy.
-  hipStream_t s = e->own;
-  HIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
-  HIPC(hipStreamWaitEvent(s, e->ev_in, 0));
+  CodecDev& d = *e->dev;
+  const float* Wt = d.w.get();
   const int W = e->W;
-
-  HIPC(hipEventSynchronize(e->ev_copy));  // the previous call's copy out of the pinned buffer has completed
-  int* hc = e->codes_host;
-  const int MB1 = c.max_batch + 1;
-  hc[0] = n;
-  hc[1] = 0;
-  int* hseg = hc + 2;
-  int* hrel = hseg + MB1;
-  int* hcodes = hrel + 2 * MB1;
-  std::vector<int> seg(n + 1, 0);
-  for (int i = 0; i < n; ++i) seg[i + 1] = seg[i] + T[i];
-  for (int i = 0; i < n; ++i)
-    for (int q = 0; q < n_q; ++q)
-      for (int t = 0; t < T[i]; ++t) hcodes[(size_t)q * total + seg[i] + t] = (int)codes[i][(size_t)q * T[i] + t];
-  memcpy(hseg, seg.data(), (n + 1) * sizeof(int));
-  struct Group { int u0, u1, off; };
-  std::vector<Group> groups;
-  int used = 0;
-  for (int u0 = 0; u0 < n;) {
-    int u1 = u0 + 1;
-    while (u1 < n && (long)seg[u1 + 1] - seg[u0] <= e->chunk_frames) ++u1;
-    groups.push_back(Group{u0, u1, used});
-    for (int u = u0; u <= u1; ++u) hrel[used++] = seg[u] - seg[u0];
-    u0 = u1;
-  }
-  const size_t ints = 2 + 3 * (size_t)MB1 + (size_t)n_q * total;
-  HIPC(hipMemcpyAsync(e->codes_dev, hc, ints * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPC(hipEventRecord(e->ev_copy, s));
-  int* dmeta = e->codes_dev;
-  const int* dseg = e->codes_dev + 2;
-  const int* drel = dseg + MB1;
-  const int* dcodes = drel + 2 * MB1;
+  Call x;
+  VXC(begin_call(e, n, std::vector<int>(T, T + n), stream, (size_t)n_q * total, [&](int* hcodes) {
+    for (int i = 0; i < n; ++i)
+      for (int q = 0; q < n_q; ++q)
+        for (int t = 0; t < T[i]; ++t) hcodes[(size_t)q * total + x.seg[i] + t] = (int)codes[i][(size_t)q * T[i] + t];
+  }, x));
+  hipStream_t s = x.s;
+  const std::vector<int>& seg = x.seg;
 
   const long e0 = total * c.hidden;
   e->last_frames = 0;  // x0 no longer holds an encode's embeddings
-  codec_rvq_rows<<<(unsigned)((e0 + 255) / 256), 256, 0, s>>>(dcodes, e->cb, e->x0, total, n_q, c.codebook_size, c.codebook_dim);
+  codec_rvq_rows<<<(unsigned)((e0 + 255) / 256), 256, 0, s>>>(x.rest, Wt + e->cb, d.x0.get(), total, n_q, c.codebook_size, c.codebook_dim);
   HIPC(hipGetLastError());
-  VXC(run_conv(e->x0, e->c0_w, e->c0_b, e->xc, total, c.hidden, W, c.kernel, 0, dseg, n, 1, s));
-  VXC(run_lstm(e->lstm, e->xc, e->gin, e->h0, e->h1, e->c0, e->c1, e->y, W, c.lstm_layers, dseg, seg.data(), n, s,
-                (c.flags & VX_CODEC_LSTM_GRAPH) ? &e->chain : nullptr, dmeta));
+  VXC(run_conv(d.x0.get(), Wt + e->c0.w, Wt + e->c0.b, d.xc.get(), total, c.hidden, W, c.kernel, 0, x.dseg, n, 1, s));
+  VXC(run_lstm(Wt, e->lstm, d.xc.get(), d.gin.get(), d.h0.get(), d.h1.get(), d.c0.get(), d.c1.get(), d.y.get(), W, c.lstm_layers, x.dseg,
+                seg.data(), n, s, (c.flags & VX_CODEC_LSTM_GRAPH) ? &d.chain : nullptr, x.meta));
 
-  for (const Group& gr : groups) {
+  for (const Group& gr : x.groups) {
     const int ns = gr.u1 - gr.u0;
-    const int* sg = drel + gr.off;
+    const int* sg = x.drel + gr.off;
     const long frames = seg[gr.u1] - seg[gr.u0];
-    const float* x = e->y + (size_t)seg[gr.u0] * W;
+    const float* in = d.y.get() + (size_t)seg[gr.u0] * W;
     long rate = 1;
     for (const Stage& st : e->stages) {
-      VXC(run_convtr(x, st.up_w, st.up_b, e->bufA, frames * rate, st.cin, st.cout, st.stride, 1, sg, ns, (int)rate, s));
+      VXC(run_convtr(in, Wt + st.up.w, Wt + st.up.b, d.bufA.get(), frames * rate, st.cin, st.cout, st.stride, 1, sg, ns, (int)rate, s));
       rate *= st.stride;
-      const int ch = st.cout, hd = ch / 2;
-      VXC(run_conv(e->bufA, st.c3_w, st.c3_b, e->bufH, frames * rate, ch, hd, c.res_kernel, 1, sg, ns, (int)rate, s));
-      CodecGemmArgs a{};
-      a.part[0] = CodecPart{e->bufH, hd, 1, CODEC_PAD_ZERO, 1};
-      a.part[1] = CodecPart{e->bufA, ch, 1, CODEC_PAD_ZERO, 0};
-      a.nparts = 2;
-      a.W = st.mix_w; a.bias = st.mix_b; a.out = e->bufB; a.M = frames * rate; a.N = ch; a.K = hd + ch;
-      a.seg = sg; a.nseg = ns; a.rate = (int)rate;
-      VXC(launch_gemm(a, s));
-      x = e->bufB;
+      VXC(run_res(Wt, st.res, d.bufA.get(), d.bufH.get(), d.bufB.get(), frames * rate, st.cout, c.res_kernel, sg, ns, (int)rate, s));
+      in = d.bufB.get();
     }
     const int ch = e->stages.back().cout;
-    VXC(run_conv(e->bufB, e->last_w, e->last_b, e->bufH, frames * rate, ch, 1, c.last_kernel, 1, sg, ns, (int)rate, s));
+    VXC(run_conv(d.bufB.get(), Wt + e->last.w, Wt + e->last.b, d.bufH.get(), frames * rate, ch, 1, c.last_kernel, 1, sg, ns, (int)rate, s));
     for (int u = gr.u0; u < gr.u1; ++u)
-      HIPC(hipMemcpyAsync(wav_out[u], e->bufH + (size_t)(seg[u] - seg[gr.u0]) * rate, (size_t)T[u] * rate * sizeof(float),
+      HIPC(hipMemcpyAsync(wav_out[u], d.bufH.get() + (size_t)(seg[u] - seg[gr.u0]) * rate, (size_t)T[u] * rate * sizeof(float),
                            hipMemcpyDeviceToDevice, s));
   }
-  HIPC(hipEventRecord(e->ev_out, s));
-  HIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
-  return VX_OK;
+  return end_call(e, x, stream);
 }
 
 extern "C" int vx_codec_encode(vx_codec* e, int32_t n, const float* const* wav, const int32_t* n_samples, int32_t n_q,
@@ -712,93 +684,63 @@ extern "C" int vx_codec_encode(vx_codec* e, int32_t n, const float* const* wav, 
   }
   if (!e->finalized) return fail(VX_ERR_STATE, "vx_codec_encode before vx_codec_finalize");
   ON_DEVICE(c.device);
-  hipStream_t s = e->own;  // ordering as vx_codec_decode
-  HIPC(hipEventRecord(e->ev_in, (hipStream_t)stream));
-  HIPC(hipStreamWaitEvent(s, e->ev_in, 0));
-  const int W = e->W;
-
-  HIPC(hipEventSynchronize(e->ev_copy));
-  int* hc = e->codes_host;
-  const int MB1 = c.max_batch + 1;
-  hc[0] = n;
-  hc[1] = 0;
-  int* hseg = hc + 2;          // frame offsets of the call
-  int* hrel = hseg + MB1;      // per group: frame offsets relative to the group (stage 4 rows)
-  int* hlv = hrel + 2 * MB1;   // per stage 0..3: per group row offsets, [4][2 MB1]
-  std::vector<int> seg(n + 1, 0);
+  CodecDev& d = *e->dev;
+  const float* Wt = d.w.get();
+  const int W = e->W, MB1 = c.max_batch + 1;
   auto cdiv = [](long a, long b) { return (a + b - 1) / b; };
-  for (int i = 0; i < n; ++i) seg[i + 1] = seg[i] + (int)cdiv(n_samples[i], hop);
-  const long total = seg[n];
-  memcpy(hseg, seg.data(), (n + 1) * sizeof(int));
-  struct Group { int u0, u1, off; long rows[5]; };
-  std::vector<Group> groups;
-  int used = 0;
-  for (int u0 = 0; u0 < n;) {
-    int u1 = u0 + 1;
-    while (u1 < n && (long)seg[u1 + 1] - seg[u0] <= e->chunk_frames) ++u1;
-    Group gr{u0, u1, used, {0, 0, 0, 0, 0}};
-    long acc[5] = {0, 0, 0, 0, 0};
-    for (int u = u0; u <= u1; ++u) {
-      for (int l = 0; l < 4; ++l) hlv[l * 2 * MB1 + used] = (int)acc[l];
-      hrel[used] = (int)acc[4];
-      ++used;
-      if (u == u1) break;
-      long rows = n_samples[u];
-      acc[0] += rows;
-      for (int l = 0; l < 4; ++l) {
-        rows = cdiv(rows, e->estages[l].stride);
-        acc[l + 1] += rows;
+  std::vector<int> frames(n);
+  for (int i = 0; i < n; ++i) frames[i] = (int)cdiv(n_samples[i], hop);
+  std::vector<std::array<long, 5>> rows;  // per group: its rows at stages 0..3 and its frames
+  Call x;
+  // behind the three tables: per stage 0..3 the groups' row offsets [4][2 MB1] (the frames' relative offsets are stage 4's)
+  VXC(begin_call(e, n, frames, stream, 8 * (size_t)MB1, [&](int* hlv) {
+    for (const Group& gr : x.groups) {
+      std::array<long, 5> acc = {0, 0, 0, 0, 0};
+      for (int u = gr.u0; u <= gr.u1; ++u) {
+        for (int l = 0; l < 4; ++l) hlv[l * 2 * MB1 + gr.off + u - gr.u0] = (int)acc[l];
+        if (u == gr.u1) break;
+        long r = n_samples[u];
+        acc[0] += r;
+        for (int l = 0; l < 4; ++l) acc[l + 1] += (r = cdiv(r, e->estages[l].stride));
       }
+      rows.push_back(acc);
     }
-    for (int l = 0; l < 5; ++l) gr.rows[l] = acc[l];
-    groups.push_back(gr);
-    u0 = u1;
-  }
-  for (int i = 0; i < n; ++i) e->ptrs_host[i] = (long long*)codes_out[i];
-  const size_t ints = 2 + 11 * (size_t)MB1;
-  HIPC(hipMemcpyAsync(e->codes_dev, hc, ints * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(e->ptrs_dev, e->ptrs_host, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, s));
-  HIPC(hipEventRecord(e->ev_copy, s));
-  const int* dseg = e->codes_dev + 2;
-  const int* drel = dseg + MB1;
-  const int* dlv = drel + 2 * MB1;
-  int* dcodes = e->codes_dev + 2 + 11 * MB1;  // [n_q][total]
+    long long** hp = d.stage.host<long long*>();  // the utterances' output tensors
+    for (int i = 0; i < n; ++i) hp[i] = (long long*)codes_out[i];
+  }, x));
+  hipStream_t s = x.s;
+  const std::vector<int>& seg = x.seg;
+  const long total = seg[n];
+  const int* dlv = x.rest;
+  int* dcodes = x.rest + 8 * MB1;  // [n_q][total]
 
-  for (const Group& gr : groups) {
+  for (size_t gi = 0; gi < x.groups.size(); ++gi) {
+    const Group& gr = x.groups[gi];
     const int ns = gr.u1 - gr.u0;
-    const int* sg[5] = {dlv + gr.off, dlv + 2 * MB1 + gr.off, dlv + 4 * MB1 + gr.off, dlv + 6 * MB1 + gr.off, drel + gr.off};
+    const int* sg[5] = {dlv + gr.off, dlv + 2 * MB1 + gr.off, dlv + 4 * MB1 + gr.off, dlv + 6 * MB1 + gr.off, x.drel + gr.off};
     long off = 0;
     for (int u = gr.u0; u < gr.u1; ++u) {
-      HIPC(hipMemcpyAsync(e->wav + off, wav[u], (size_t)n_samples[u] * sizeof(float), hipMemcpyDeviceToDevice, s));
+      HIPC(hipMemcpyAsync(d.wav.get() + off, wav[u], (size_t)n_samples[u] * sizeof(float), hipMemcpyDeviceToDevice, s));
       off += n_samples[u];
     }
-    VXC(run_conv_in(e->wav, e->e0_w, e->e0_b, e->bufA, gr.rows[0], c.filters, c.kernel, sg[0], ns, s));
+    VXC(run_conv_in(d.wav.get(), Wt + e->e0.w, Wt + e->e0.b, d.bufA.get(), rows[gi][0], c.filters, c.kernel, sg[0], ns, s));
     for (int l = 0; l < 4; ++l) {
       const EncStage& st = e->estages[l];
-      const int ch = st.c, hd = ch / 2;
-      VXC(run_conv(e->bufA, st.c3_w, st.c3_b, e->bufH, gr.rows[l], ch, hd, c.res_kernel, 1, sg[l], ns, 1, s));
-      CodecGemmArgs a{};
-      a.part[0] = CodecPart{e->bufH, hd, 1, CODEC_PAD_ZERO, 1};
-      a.part[1] = CodecPart{e->bufA, ch, 1, CODEC_PAD_ZERO, 0};
-      a.nparts = 2;
-      a.W = st.mix_w; a.bias = st.mix_b; a.out = e->bufB; a.M = gr.rows[l]; a.N = ch; a.K = hd + ch;
-      a.seg = sg[l]; a.nseg = ns; a.rate = 1;
-      VXC(launch_gemm(a, s));
-      float* out = l == 3 ? e->xc + (size_t)seg[gr.u0] * W : e->bufA;
-      VXC(run_conv_strided(e->bufB, st.dn_w, st.dn_b, out, gr.rows[l + 1], ch, 2 * ch, st.stride, 1, sg[l + 1], sg[l], ns, s));
+      VXC(run_res(Wt, st.res, d.bufA.get(), d.bufH.get(), d.bufB.get(), rows[gi][l], st.c, c.res_kernel, sg[l], ns, 1, s));
+      float* out = l == 3 ? d.xc.get() + (size_t)seg[gr.u0] * W : d.bufA.get();
+      VXC(run_conv_strided(d.bufB.get(), Wt + st.dn.w, Wt + st.dn.b, out, rows[gi][l + 1], st.c, 2 * st.c, st.stride, 1, sg[l + 1], sg[l], ns, s));
     }
   }
-  VXC(run_lstm(e->elstm, e->xc, e->gin, e->h0, e->h1, e->c0, e->c1, e->y, W, c.lstm_layers, dseg, seg.data(), n, s));
+  VXC(run_lstm(Wt, e->elstm, d.xc.get(), d.gin.get(), d.h0.get(), d.h1.get(), d.c0.get(), d.c1.get(), d.y.get(), W, c.lstm_layers, x.dseg,
+                seg.data(), n, s));
   e->last_frames = 0;
-  VXC(run_conv(e->y, e->elast_w, e->elast_b, e->x0, total, W, c.hidden, c.last_kernel, 1, dseg, n, 1, s));
+  VXC(run_conv(d.y.get(), Wt + e->elast.w, Wt + e->elast.b, d.x0.get(), total, W, c.hidden, c.last_kernel, 1, x.dseg, n, 1, s));
   e->last_frames = total;
-  VXC(run_rvq_encode(e->x0, e->cb, e->cb_sq, dcodes, total, n_q, c.codebook_size, c.codebook_dim, s));
+  VXC(run_rvq_encode(d.x0.get(), Wt + e->cb, Wt + e->cb_sq, dcodes, total, n_q, c.codebook_size, c.codebook_dim, s));
   const long nc = total * n_q;
-  codec_codes_out<<<(unsigned)((nc + 255) / 256), 256, 0, s>>>(dcodes, e->ptrs_dev, dseg, n, total, n_q);
+  codec_codes_out<<<(unsigned)((nc + 255) / 256), 256, 0, s>>>(dcodes, d.stage.dev<long long* const>(), x.dseg, n, total, n_q);
   HIPC(hipGetLastError());
-  HIPC(hipEventRecord(e->ev_out, s));
-  HIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
-  return VX_OK;
+  return end_call(e, x, stream);
 }
 
 // The embeddings (the quantiser's input, [rows][hidden]) of the last vx_codec_encode, rows in the order of its utterances: copied to
@@ -809,24 +751,19 @@ extern "C" int vx_codec_last_embeddings(vx_codec* e, float* out, int64_t rows, v
   if (rows < 1 || rows > e->last_frames)
     return fail(VX_ERR_ARG, "vx_codec_last_embeddings: rows = %lld, the last encode had %ld frames", (long long)rows, e->last_frames);
   ON_DEVICE(e->cfg.device);
-  HIPC(hipMemcpyAsync(out, e->x0, (size_t)rows * e->cfg.hidden * sizeof(float), hipMemcpyDeviceToDevice, e->own));
-  HIPC(hipEventRecord(e->ev_out, e->own));
-  HIPC(hipStreamWaitEvent((hipStream_t)stream, e->ev_out, 0));
+  CodecDev& d = *e->dev;
+  HIPC(hipMemcpyAsync(out, d.x0.get(), (size_t)rows * e->cfg.hidden * sizeof(float), hipMemcpyDeviceToDevice, d.own));
+  HIPC(hipEventRecord(d.ev_out, d.own));
+  HIPC(hipStreamWaitEvent((hipStream_t)stream, d.ev_out, 0));
   return VX_OK;
 }
 
-// ---- op-level test entries: x / out device fp32 rows, weights and biases HOST fp32 in torch's layouts (packed here exactly as
-// vx_codec_finalize packs them), seg_frames HOST nseg + 1 frame offsets.  Synchronous. ----------------------------------------
+// ---- op-level test entries: x / out device fp32 rows, weights and biases HOST fp32 in torch's layouts (packed here by the helpers
+// vx_codec_finalize packs with), seg_frames HOST nseg + 1 frame offsets.  Synchronous. ------------------------------------------------
 namespace {
 int upload_segs(const int32_t* seg, int nseg, DevBuf<int>& d) {
   VXC(d.alloc(nseg + 1));
   HIPC(hipMemcpy(d.get(), seg, (nseg + 1) * sizeof(int), hipMemcpyHostToDevice));
-  return VX_OK;
-}
-// as upload() for the handle's own buffers: 16 spare bytes, a blocking copy
-int upload(const std::vector<float>& h, DevBuf<float>& d) {
-  VXC(d.alloc(h.size() + 4));
-  HIPC(hipMemcpy(d.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
   return VX_OK;
 }
 }  // namespace
@@ -837,11 +774,12 @@ extern "C" int vx_op_codec_conv(const float* x, const float* w, const float* bia
   VXC(check_segs(seg_frames, nseg));
   hipStream_t s = (hipStream_t)stream;
   DevBuf<int> sg;
-  DevBuf<float> wp, bp;
+  DevBuf<float> W;
+  std::vector<float> p;
+  const ConvW cv = pack_conv(p, w, bias, c_out, c_in, k);
   VXC(upload_segs(seg_frames, nseg, sg));
-  VXC(upload(pack_conv(w, c_out, c_in, k), wp));
-  if (bias) VXC(upload(std::vector<float>(bias, bias + c_out), bp));
-  VXC(run_conv(x, wp.get(), bp.get(), out, (long)seg_frames[nseg] * rate, c_in, c_out, k, elu, sg.get(), nseg, rate, s));
+  VXC(upload_packed(p, W));
+  VXC(run_conv(x, W.get() + cv.w, bias ? W.get() + cv.b : nullptr, out, (long)seg_frames[nseg] * rate, c_in, c_out, k, elu, sg.get(), nseg, rate, s));
   HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }
@@ -852,15 +790,12 @@ extern "C" int vx_op_codec_convtr(const float* x, const float* w, const float* b
   VXC(check_segs(seg_frames, nseg));
   hipStream_t s = (hipStream_t)stream;
   DevBuf<int> sg;
-  DevBuf<float> wp, bp;
+  DevBuf<float> W;
+  std::vector<float> p;
+  const ConvW cv = pack_convtr(p, w, bias, c_in, c_out, stride);
   VXC(upload_segs(seg_frames, nseg, sg));
-  VXC(upload(pack_convtr(w, c_in, c_out, stride), wp));
-  if (bias) {
-    std::vector<float> rep((size_t)stride * c_out);
-    for (int p = 0; p < stride; ++p) memcpy(&rep[(size_t)p * c_out], bias, c_out * sizeof(float));
-    VXC(upload(rep, bp));
-  }
-  VXC(run_convtr(x, wp.get(), bp.get(), out, (long)seg_frames[nseg] * rate, c_in, c_out, stride, elu, sg.get(), nseg, rate, s));
+  VXC(upload_packed(p, W));
+  VXC(run_convtr(x, W.get() + cv.w, bias ? W.get() + cv.b : nullptr, out, (long)seg_frames[nseg] * rate, c_in, c_out, stride, elu, sg.get(), nseg, rate, s));
   HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }
@@ -873,20 +808,20 @@ extern "C" int vx_op_codec_lstm(const float* x, const float* const* w_ih, const 
   VXC(check_segs(seg_frames, nseg));
   hipStream_t s = (hipStream_t)stream;
   DevBuf<int> sg;
-  VXC(upload_segs(seg_frames, nseg, sg));
-  LstmDev d;
-  int r = pack_lstm(w_ih, w_hh, b_ih, b_hh, width, layers, &d);
+  DevBuf<float> W, gin, h0, h1, c0, c1;
+  std::vector<float> p;
+  const LstmW lw = pack_lstm(p, w_ih, w_hh, b_ih, b_hh, width, layers);
   const size_t rows = seg_frames[nseg];
-  DevBuf<float> gin, h0, h1, c0, c1;  // 16 spare bytes each, as alloc_f()
-  if (r == VX_OK) r = gin.alloc(rows * 4 * width + 4);
-  if (r == VX_OK) r = h0.alloc(rows * width + 4);
-  if (r == VX_OK) r = h1.alloc(rows * width + 4);
-  if (r == VX_OK) r = c0.alloc((size_t)nseg * width + 4);
-  if (r == VX_OK) r = c1.alloc((size_t)nseg * width + 4);
-  if (r == VX_OK) r = run_lstm(d, x, gin.get(), h0.get(), h1.get(), c0.get(), c1.get(), y, width, layers, sg.get(), seg_frames, nseg, s);
-  if (r == VX_OK && hipStreamSynchronize(s) != hipSuccess) r = fail(VX_ERR_HIP, "vx_op_codec_lstm: synchronise failed");
-  free_lstm(d);
-  return r;
+  VXC(upload_segs(seg_frames, nseg, sg));
+  VXC(upload_packed(p, W));
+  VXC(gin.alloc(rows * 4 * width + CODEC_SPARE));
+  VXC(h0.alloc(rows * width + CODEC_SPARE));
+  VXC(h1.alloc(rows * width + CODEC_SPARE));
+  VXC(c0.alloc((size_t)nseg * width + CODEC_SPARE));
+  VXC(c1.alloc((size_t)nseg * width + CODEC_SPARE));
+  VXC(run_lstm(W.get(), lw, x, gin.get(), h0.get(), h1.get(), c0.get(), c1.get(), y, width, layers, sg.get(), seg_frames, nseg, s));
+  HIPC(hipStreamSynchronize(s));
+  return VX_OK;
 }
 
 // Encoder convolution on caller data: x device rows [seg_rows_in[nseg]][c_in], w HOST (c_out, c_in, k), out device rows
@@ -902,14 +837,16 @@ extern "C" int vx_op_codec_conv_strided(const float* x, const float* w, const fl
   std::vector<int32_t> so(nseg + 1, 0);
   for (int i = 0; i < nseg; ++i) so[i + 1] = so[i] + (seg_rows_in[i + 1] - seg_rows_in[i] + stride - 1) / stride;
   DevBuf<int> sg, sgo;
-  DevBuf<float> wp, bp;
+  DevBuf<float> W;
+  std::vector<float> p;
+  const ConvW cv = pack_conv(p, w, bias, c_out, c_in, k);
   VXC(upload_segs(seg_rows_in, nseg, sg));
   VXC(upload_segs(so.data(), nseg, sgo));
-  VXC(upload(pack_conv(w, c_out, c_in, k), wp));
-  if (bias) VXC(upload(std::vector<float>(bias, bias + c_out), bp));
-  if (stride > 1) VXC(run_conv_strided(x, wp.get(), bp.get(), out, so[nseg], c_in, c_out, stride, elu, sgo.get(), sg.get(), nseg, s));
-  else if (c_in == 1) VXC(run_conv_in(x, wp.get(), bp.get(), out, so[nseg], c_out, k, sg.get(), nseg, s));
-  else VXC(run_conv(x, wp.get(), bp.get(), out, so[nseg], c_in, c_out, k, elu, sg.get(), nseg, 1, s));
+  VXC(upload_packed(p, W));
+  const float *wp = W.get() + cv.w, *bp = bias ? W.get() + cv.b : nullptr;
+  if (stride > 1) VXC(run_conv_strided(x, wp, bp, out, so[nseg], c_in, c_out, stride, elu, sgo.get(), sg.get(), nseg, s));
+  else if (c_in == 1) VXC(run_conv_in(x, wp, bp, out, so[nseg], c_out, k, sg.get(), nseg, s));
+  else VXC(run_conv(x, wp, bp, out, so[nseg], c_in, c_out, k, elu, sg.get(), nseg, 1, s));
   HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }
@@ -920,11 +857,12 @@ extern "C" int vx_op_codec_rvq_encode(const float* emb, const float* codebooks, 
   if (!emb || !codebooks || !codes_out || rows < 1 || n_q < 1 || n_q > CODEC_MAX_Q) return fail(VX_ERR_ARG, "vx_op_codec_rvq_encode: bad argument");
   if (size < 1 || dim < 1 || !rvq_shape_ok(size, dim)) return fail(VX_ERR_UNSUPPORTED, "vx_op_codec_rvq_encode: codebook %d x %d", size, dim);
   hipStream_t s = (hipStream_t)stream;
-  DevBuf<float> cb, sq;
+  DevBuf<float> W;
+  std::vector<float> p;
   const size_t n = (size_t)n_q * size;
-  VXC(upload(std::vector<float>(codebooks, codebooks + n * dim), cb));
-  VXC(upload(codebook_sq(codebooks, n, dim), sq));
-  VXC(run_rvq_encode(emb, cb.get(), sq.get(), codes_out, rows, n_q, size, dim, s));
+  const size_t cb = put(p, std::vector<float>(codebooks, codebooks + n * dim)), sq = put(p, codebook_sq(codebooks, n, dim));
+  VXC(upload_packed(p, W));
+  VXC(run_rvq_encode(emb, W.get() + cb, W.get() + sq, codes_out, rows, n_q, size, dim, s));
   HIPC(hipStreamSynchronize(s));
   return VX_OK;
 }

@@ -1,6 +1,6 @@
-// HiFi-GAN / BigVGAN generator behind the C ABI (include/vallex.h, vx_gan_*): the weight table and its packing for the row GEMM,
-// the anti-aliasing filter, the staging of a ragged call (CallStage, host.hpp), the five row buffers and the launches of
-// ganvoc_kernels.hpp.  A translation unit and a handle of its own, like vocoder.hip: no other unit sees these kernels.
+// HiFi-GAN / BigVGAN generator behind the C ABI (include/vallex.h, vx_gan_*): the packing of its weight table (weights_host.hpp)
+// for the row GEMM, the anti-aliasing filter, the staging of a ragged call (CallStage, host.hpp), the five row buffers and the
+// launches of ganvoc_kernels.hpp.  A translation unit and a handle of its own, like vocoder.hip: no other unit sees these kernels.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -13,17 +13,11 @@
 
 #undef VX_STAMPS  // the in-kernel stamps write device globals of engine.hip's unit, out of this unit's reach
 #include "ganvoc_kernels.hpp"
-#include "host.hpp"
+#include "weights_host.hpp"
 
 using namespace vx;
 
 namespace {
-
-struct HostW {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-  bool set = false, optional = false;
-};
 
 // One row GEMM: the packed weight [N][K] and bias [N] as offsets into the device block, and the gather rule.
 struct GanConv {
@@ -73,13 +67,6 @@ struct vx_gan : LazyDev<GanDev> {
 
 namespace {
 
-void add_key(vx_gan* g, const std::string& key, std::vector<int64_t> shape, bool optional = false) {
-  HostW t;
-  t.shape = std::move(shape);
-  t.optional = optional;
-  g->w[key] = std::move(t);
-}
-
 // I0 by its power series (fp64; the terms fall below 1e-17 of the sum long before 64 of them at beta ~ 6.5)
 double bessel_i0(double x) {
   double sum = 1.0, term = 1.0;
@@ -106,22 +93,10 @@ void kaiser_sinc12(float* out) {
   for (int n = 0; n < K; ++n) out[n] = (float)(f[n] / sum);
 }
 
-size_t push(std::vector<float>& p, const std::vector<float>& v) {
-  while (p.size() % 4) p.push_back(0.f);  // every tensor starts on a 16-byte boundary
-  const size_t at = p.size();
-  p.insert(p.end(), v.begin(), v.end());
-  return at;
-}
-
 // Conv1d (O, C, k), dilation d, "same" zero padding: W[o][j * C + c] = w[o][c][j]; tap j reads row t + (j - (k-1)/2) d.
-GanConv pack_conv(vx_gan* g, const std::string& name, int O, int Cc, int k, int d, bool bias_optional = false) {
-  const HostW& w = g->w[name + ".weight"];
-  std::vector<float> p((size_t)O * Cc * k);
-  for (int o = 0; o < O; ++o)
-    for (int c = 0; c < Cc; ++c)
-      for (int j = 0; j < k; ++j) p[((size_t)o * k + j) * Cc + c] = w.data[((size_t)o * Cc + c) * k + j];
+GanConv pack_conv(vx_gan* g, const std::string& name, int O, int Cc, int k, int d) {
   GanConv cv;
-  cv.w = push(g->packed, p);
+  cv.w = push(g->packed, conv_rows(g->w[name + ".weight"].data.data(), O, Cc, k));
   const HostW& b = g->w[name + ".bias"];
   cv.has_bias = b.set;
   if (b.set) cv.b = push(g->packed, b.data);
@@ -376,26 +351,7 @@ extern "C" int vx_gan_create(const vx_gan_config* cfg, vx_gan** out) {
 extern "C" void vx_gan_destroy(vx_gan* g) { destroy_handle(g); }
 
 extern "C" int vx_gan_set_weight(vx_gan* g, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
-  if (!g || !key || !data || !shape) return fail(VX_ERR_ARG, "vx_gan_set_weight: null argument");
-  if (g->finalized) return fail(VX_ERR_STATE, "vx_gan_set_weight after vx_gan_finalize");
-  auto it = g->w.find(key);
-  if (it == g->w.end()) return fail(VX_ERR_WEIGHTS, "unknown key %s", key);
-  HostW& t = it->second;
-  bool same = ndim == (int32_t)t.shape.size();
-  size_t n = 1;
-  for (size_t i = 0; same && i < t.shape.size(); ++i) {
-    same = shape[i] == t.shape[i];
-    n *= (size_t)t.shape[i];
-  }
-  if (!same) {
-    std::string want, got;
-    for (int64_t v : t.shape) want += (want.empty() ? "" : ", ") + std::to_string(v);
-    for (int i = 0; i < ndim && i < 8; ++i) got += (got.empty() ? "" : ", ") + std::to_string(shape[i]);
-    return fail(VX_ERR_WEIGHTS, "%s: shape (%s), expected (%s)", key, got.c_str(), want.c_str());
-  }
-  t.data.assign(data, data + n);
-  t.set = true;
-  return VX_OK;
+  return set_weight(g, "vx_gan", key, data, shape, ndim);
 }
 
 extern "C" int vx_gan_set_filter(vx_gan* g, const float* taps, int32_t n_taps) {
@@ -415,8 +371,7 @@ extern "C" int vx_gan_get_filter(const vx_gan* g, float* taps) {
 extern "C" int vx_gan_finalize(vx_gan* g) {
   if (!g) return fail(VX_ERR_ARG, "vx_gan_finalize: null handle");
   if (g->finalized) return VX_OK;
-  for (auto& kv : g->w)
-    if (!kv.second.set && !kv.second.optional) return fail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
+  VXC(missing_tensor(g));
   if (g->w["mean"].set != g->w["scale"].set)
     return fail(VX_ERR_WEIGHTS, "missing tensor %s (mean and scale come together)", g->w["mean"].set ? "scale" : "mean");
   const vx_gan_config& c = g->cfg;

@@ -4,7 +4,9 @@
 // CallStage named `stage` and DevBufs in that Dev, opens its *_init_device with open_device, and writes its entry points as
 //   create_head;  host-side checks;  ensure_device;  ON_DEVICE;  drain before a table is replaced;  begin .. upload .. kernels .. finish
 // with destroy_handle as its destroy (fbank.hip is the shortest example).  A call whose per-utterance arrays are pointer columns,
-// tile0 and int columns lays them out with RaggedTable.
+// tile0 and int columns lays them out with RaggedTable.  A handle that takes weights keeps its table with weights_host.hpp.
+// One handle is not lazy: vx_codec names its device in its config and makes its device side (DevBufs and a CallStage, too) at
+// vx_codec_finalize; its calls run on a stream of its own, handed over from and back to the caller's around begin .. finish.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>

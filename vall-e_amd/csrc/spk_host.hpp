@@ -1,27 +1,16 @@
-// The leaf pieces of the host side of the units built on spk_kernels.hpp (spk.hip, asr.hip, whisper.hip): the weight table of a
-// handle, the packing of one tensor for the row GEMM and the launches of the shared kernels.  What is built from them - the encoder
-// layer, the Wav2Vec2 backbone, the handle scaffolding - is w2v_host.hpp, which the units include.  A handle type G has
+// The leaf pieces of the host side of the units built on spk_kernels.hpp (spk.hip, asr.hip, whisper.hip): the packing of one tensor
+// of the handle's weight table (weights_host.hpp) for the row GEMM and the launches of the shared kernels.  What is built from them -
+// the encoder layer, the Wav2Vec2 backbone, the handle scaffolding - is w2v_host.hpp, which the units include.  A handle type G has
 // `std::map<std::string, HostW> w`, `std::vector<float> packed` and `bool finalized` (w2v_host.hpp's SpeechHandle).  Everything here
 // has internal linkage: each unit launches its own copy of the kernels (they are `static` in spk_kernels.hpp).
 #pragma once
 #include <math.h>
-#include <stdint.h>
 
-#include <map>
-#include <string>
-#include <vector>
-
-#include "host.hpp"
+#include "weights_host.hpp"
 #include "spk_kernels.hpp"
 
 namespace vx {
 namespace {
-
-struct HostW {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-  bool set = false;
-};
 
 // One row GEMM: the packed weight [groups][N][K] and bias as offsets into the device block, and the gather rule.
 struct SpkLin {
@@ -32,20 +21,6 @@ struct SpkLin {
 struct SpkNorm {
   size_t w = 0, b = 0;
 };
-
-template <class G>
-void add_key(G* g, const std::string& key, std::vector<int64_t> shape) {
-  HostW t;
-  t.shape = std::move(shape);
-  g->w[key] = std::move(t);
-}
-
-size_t push(std::vector<float>& p, const std::vector<float>& v) {
-  while (p.size() % 4) p.push_back(0.f);  // every tensor starts on a 16-byte boundary
-  const size_t at = p.size();
-  p.insert(p.end(), v.begin(), v.end());
-  return at;
-}
 
 template <class G>
 SpkNorm pack_norm(G* g, const std::string& name) {
@@ -69,42 +44,12 @@ SpkLin pack_linear(G* g, const std::string& name, int N, int K) {
 // Conv1d (O, Cg, k) in `groups` groups: W[g][n][j * Cg + c] = w[g * (O / groups) + n][c][j].
 template <class G>
 SpkLin pack_conv(G* g, const std::string& name, int O, int Cg, int k, int groups, bool bias) {
-  const HostW& w = g->w[name + ".weight"];
-  std::vector<float> p((size_t)O * Cg * k);
-  for (int o = 0; o < O; ++o)
-    for (int c = 0; c < Cg; ++c)
-      for (int j = 0; j < k; ++j) p[((size_t)o * k + j) * Cg + c] = w.data[((size_t)o * Cg + c) * k + j];
   SpkLin l;
-  l.w = push(g->packed, p);
+  l.w = push(g->packed, conv_rows(g->w[name + ".weight"].data.data(), O, Cg, k));
   l.has_bias = bias;
   if (bias) l.b = push(g->packed, g->w[name + ".bias"].data);
   l.C = Cg; l.taps = k; l.N = O / groups; l.groups = groups;
   return l;
-}
-
-// The body of vx_spk_set_weight / vx_asr_set_weight (`what` names the entry point in the messages).
-template <class G>
-int set_weight(G* g, const char* what, const char* key, const float* data, const int64_t* shape, int32_t ndim) {
-  if (!g || !key || !data || !shape) return fail(VX_ERR_ARG, "%s_set_weight: null argument", what);
-  if (g->finalized) return fail(VX_ERR_STATE, "%s_set_weight after %s_finalize", what, what);
-  auto it = g->w.find(key);
-  if (it == g->w.end()) return fail(VX_ERR_WEIGHTS, "unknown key %s", key);
-  HostW& t = it->second;
-  bool same = ndim == (int32_t)t.shape.size();
-  size_t n = 1;
-  for (size_t i = 0; same && i < t.shape.size(); ++i) {
-    same = shape[i] == t.shape[i];
-    n *= (size_t)t.shape[i];
-  }
-  if (!same) {
-    std::string want, got;
-    for (int64_t v : t.shape) want += (want.empty() ? "" : ", ") + std::to_string(v);
-    for (int i = 0; i < ndim && i < 8; ++i) got += (got.empty() ? "" : ", ") + std::to_string(shape[i]);
-    return fail(VX_ERR_WEIGHTS, "%s: shape (%s), expected (%s)", key, got.c_str(), want.c_str());
-  }
-  t.data.assign(data, data + n);
-  t.set = true;
-  return VX_OK;
 }
 
 int launch_gemm(const SpkGemmArgs& a, int groups, hipStream_t s) {

@@ -161,8 +161,7 @@ EncLayer pack_enc_layer(G* g, const std::string& pre, const EncNames& nm, int d,
 // The start of *_finalize: every tensor is there; the packed block starts empty.
 template <class G>
 int finalize_begin(G* g) {
-  for (auto& kv : g->w)
-    if (!kv.second.set) return fail(VX_ERR_WEIGHTS, "missing tensor %s", kv.first.c_str());
+  VXC(missing_tensor(g));
   g->packed.clear();
   g->packed16.clear();
   return VX_OK;
